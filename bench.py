@@ -17,6 +17,12 @@ Launch: `python bench.py --gpus N` spawns N ranks itself (before anything touche
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` the ranks are already there (RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_PORT from the env).  No torch is imported either way: the collective is RCCL, called by libsbv2_hip.so.
 
+`--dump-outputs DIR` (rank 0) writes the PCM that rank 0's host received in the LAST timed step, after the timed region: DIR/pcm.npy
+(float32, the step's samples in the order they arrived: sub-batch, then rank, then utterance) and DIR/pcm_lengths.npy (float64, the
+lengths of the segments pcm.npy is made of: one per utterance, or one per rank when RCCL gathers the PCM).  Above DUMP_BYTES in all, a fixed
+seeded sample of the samples is written instead (pcm_sample.npy + pcm_sample_index.npy, float64 positions in the concatenated PCM).  The
+inputs are generated from fixed seeds, so two builds run with the same arguments can be compared file by file.
+
 Extra objects on the JSON line:
   roofline     — the dominant kernel (the implicit-GEMM conv tile configuration with the most time), algorithmic FLOP
                  over HIP-event durations of one extra instrumented step run right after the timed ones.
@@ -38,6 +44,21 @@ import numpy as np  # noqa: E402
 
 PEAK_F32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA peak (not the 2:1-sparsity headline)
+DUMP_BYTES = 64_000_000          # cap of --dump-outputs (u128's 32 x 459 264 samples, 58.8 MB, are written whole)
+
+
+def write_dump(d: str, parts) -> None:
+    """parts: (PCM float32, segment lengths) per collected sub-batch of the last timed step -> d/*.npy (see the module docstring)."""
+    os.makedirs(d, exist_ok=True)
+    pcm = np.concatenate([p for p, _ in parts]).astype(np.float32, copy=False)
+    lens = np.concatenate([np.asarray(n, np.float64).reshape(-1) for _, n in parts])
+    np.save(os.path.join(d, "pcm_lengths.npy"), lens)
+    if pcm.nbytes + lens.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(d, "pcm.npy"), pcm)
+        return
+    idx = np.unique(np.random.default_rng(0).integers(0, pcm.size, (DUMP_BYTES - lens.nbytes) // 12))
+    np.save(os.path.join(d, "pcm_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "pcm_sample.npy"), pcm[idx])
 
 
 def spawn_ranks(n: int) -> int:
@@ -161,7 +182,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="time budget of the CPU baseline sample")
     ap.add_argument("--tiny", action="store_true", help="tiny model shapes (plumbing check only; not a valid bench number)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the PCM of the last timed step to DIR/*.npy (rank 0; see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))     # nothing above has touched the GPU
@@ -253,18 +277,28 @@ def main():
 
     pending = []
     counts_seen = []
+    dump = args.dump_outputs is not None and rank == 0
+    # --dump-outputs: (PCM, segment lengths) of each sub-batch of the last timed step as rank 0 received it.  The newest entry stays a view
+    # of `pin` until the next collect overwrites it, so u128 (one sub-batch) copies nothing inside the timed region.
+    dumped = []
 
-    def collect(ticket):
+    def collect(entry):
         """PCM of one step -> host of rank 0 (inside the timed region)."""
+        ticket, lens, last = entry
+        if dumped and np.may_share_memory(dumped[-1][0], pin.array):
+            dumped[-1] = (dumped[-1][0].copy(), dumped[-1][1])
         if comm is not None:
             counts_seen.append(comm.gather_pcm(pipe, ticket, pin.array if rank == 0 else None))
+            lens = counts_seen[-1]
         else:
             _lib.check(l.sbv2_pipeline_fetch_pcm_ticket(pipe.h, ticket, C.c_void_p(pin.ptr), pin.array.size, 0))
+        if dump and last:
+            dumped.append((pin.array[:int(lens.sum())], lens))
 
-    def step():
+    def step(last=False):
         for bb in batches:
             pipe.run(bb)
-            pending.append(bb.ticket)
+            pending.append((bb.ticket, bb.lens.copy() if dump and last else None, last))
             if len(pending) > 1:
                 collect(pending.pop(0))
 
@@ -281,10 +315,12 @@ def main():
         step()
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(last=i == args.steps - 1)
     fence()
     dt = time.perf_counter() - t0
+    if dump:
+        write_dump(args.dump_outputs, dumped)
     if comm is None and host is not None:
         dt = host.max(dt)
         total_samples_per_step = int(host.sum(float(sum(s * w for s, w in zip(sub_samples, sub_weight)))))

@@ -1412,6 +1412,34 @@ def test_orchestrator_request_tiny():
     pipe.close(); bs.close(); vs.close()
 
 
+def test_bench_dump_outputs_tiny(tmp_path):
+    """bench.py --dump-outputs in a fresh interpreter (tiny shapes): the line reports the requested steps and ms_per_step, and the dump of the
+    last timed step is the PCM one pipeline call returns for the same seeded utterances."""
+    import json
+    import subprocess
+    import sys
+    from sbv2_api_amd import configs
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--tiny", "--batch", "4", "--phones", "20", "--steps", "3",
+                        "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads([s for s in r.stdout.splitlines() if s.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    bc, vc = configs.DEBERTA_TINY, configs.VITS_TINY
+    bs = model.load_model(synth.pack_blob(synth.KIND_BERT, bc, synth.make_deberta_weights(bc)), True)
+    vs = model.load_model(synth.pack_blob(synth.KIND_VITS, vc, synth.make_vits_weights(vc)), False)
+    pipe = model.Pipeline(bs, vs)
+    b = pipe.prepare([synth.make_utterance(20, bc, vc, seed=i) for i in range(4)], forced=True)
+    pipe.run(b)
+    ref = pipe.fetch(b)
+    np.testing.assert_array_equal(np.load(d / "pcm_lengths.npy"), [len(x) for x in ref])
+    got = np.load(d / "pcm.npy")
+    assert got.dtype == np.float32
+    np.testing.assert_allclose(got, np.concatenate(ref), atol=1e-5, rtol=0)
+    pipe.close(); bs.close(); vs.close()
+
+
 def test_cpp_host_mirror(tmp_path):
     """include/sbv2_core.hpp (C++ mirror of model.rs / bert.rs: load_model, predict, synthesize, Error) through a plain g++ program
     linked against the C ABI only: same results as the oracle, errors surface as exceptions with the library's message."""

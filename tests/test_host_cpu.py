@@ -265,6 +265,33 @@ def test_bench_host_group_world3(tmp_path):
         assert o == ["3.5", "1.5", "6.0", "done"], o
 
 
+def test_bench_dump_writer(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the whole PCM (float32) and its segment lengths (float64) under the cap; above it the same seeded sample
+    of positions on every call, within the cap."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(7)
+    parts = [(rng.standard_normal(n).astype(np.float32), np.array([n // 2, n - n // 2], np.int64)) for n in (1000, 501)]
+    pcm = np.concatenate([p for p, _ in parts])
+    bench.write_dump(str(tmp_path / "a"), parts)
+    assert sorted(os.listdir(tmp_path / "a")) == ["pcm.npy", "pcm_lengths.npy"]
+    got, lens = np.load(tmp_path / "a" / "pcm.npy"), np.load(tmp_path / "a" / "pcm_lengths.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, pcm)
+    assert lens.dtype == np.float64 and lens.tolist() == [500, 500, 250, 251]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 6000)
+    for d in ("b", "c"):
+        bench.write_dump(str(tmp_path / d), parts)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["pcm_lengths.npy", "pcm_sample.npy", "pcm_sample_index.npy"]
+    assert sum(np.load(tmp_path / "b" / f).nbytes for f in files) <= 6000
+    idx, sample = np.load(tmp_path / "b" / "pcm_sample_index.npy"), np.load(tmp_path / "b" / "pcm_sample.npy")
+    assert idx.dtype == np.float64 and sample.dtype == np.float32 and len(idx) > 100
+    np.testing.assert_array_equal(sample, pcm[idx.astype(np.int64)])
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+
+
 def test_rest_contract():
     """main.rs:24-100,192-196 + error.rs:10-18: routes, JSON defaults, audio/wav, 'Something went wrong: ...' with status 500."""
     from fastapi.testclient import TestClient

@@ -1,5 +1,5 @@
 import ctypes as C, os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sbv2_api_amd import _lib
 l = _lib.lib()
 for (m, n, kk) in ((3072, 2048, 1024), (1024, 2048, 1024), (4096, 2048, 1024), (1024, 2048, 4096), (576, 28704, 192), (192, 28704, 192), (192, 8224, 1024)):

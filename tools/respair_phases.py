@@ -1,6 +1,5 @@
 import ctypes as C, json, os, sys
-sys.path.insert(0, "/root/repo")
-sys.path.insert(0, os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sbv2_api_amd import _lib
 l = _lib.lib()
 NAMES = {1: "staged", 7: "c1_chunk0_mfma", 8: "c1_chunk0_bar", 2: "conv1_done", 3: "mid_written", 4: "mid_bar", 5: "conv2_done", 6: "stores_issued"}
