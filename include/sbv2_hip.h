@@ -130,6 +130,30 @@ int sbv2_pipeline_fetch_pcm(sbv2_pipeline* p, float* dst, int64_t capacity, int 
 void* sbv2_host_alloc(size_t bytes);
 void sbv2_host_free(void* p);
 
+/* ---- new: output formats (the reference returns 44.1 kHz mono f32 only: tts_util.rs:163-180).  The PCM of a run is resampled to a common rate
+ * (rational polyphase, L / M = rate / 44100 in lowest terms), optionally peak-normalised per output signal and quantised to 16 bits ON THE DEVICE,
+ * before it crosses PCIe.  Convention: y[j] = sum_k h[j M - k L + half] x[k], j < ceil(N L / M), x = 0 outside [0, N); h = a Kaiser-windowed sinc
+ * (cutoff 0.45 min(44100, rate), beta 8.6, half = 32 max(L, M)), every polyphase branch summing to 1; i.e. scipy.signal.resample_poly(x, L, M,
+ * window = h / L).  s16 = clamp(rint(y g 32767), -32767, 32767), little-endian; g = 1 / max|y| of the signal when normalising (1 for silence). */
+typedef struct sbv2_pcm_format {
+    int32_t sample_rate;   /* 8000 16000 22050 24000 32000 44100 48000; anything else is refused */
+    int32_t encoding;      /* 0 = f32, 1 = s16 little-endian */
+    int32_t normalize;     /* 0 = none, 1 = peak of each output signal -> full scale */
+    int32_t reserved;      /* must be 0 */
+} sbv2_pcm_format;
+/* Host only: samples of a signal of n_native samples at 44.1 kHz in that format, ceil(n L / M); -1 (message in sbv2_last_error) when fmt is bad. */
+int64_t sbv2_pcm_format_length(const sbv2_pcm_format* fmt, int64_t n_native);
+/* Host-only test hook: the prototype h of a rate (*len = 2 half + 1 taps at 44100 L Hz) and L, M.  h may be NULL (query); else cap >= *len. */
+int sbv2_pcm_format_taps(int32_t sample_rate, float* h, int64_t cap, int64_t* len, int32_t* L, int32_t* M);
+/* Formats run `ticket` on its context's stream (waits for it) and copies the result into HOST memory dst (capacity_bytes; a longer result is refused
+ * and nothing is written).
+ *   place == NULL: one signal per utterance, concatenated in utterance order; out_lens[n] = samples of each.
+ *   place != NULL: ONE signal: the run's utterances laid on a silent timeline of joined_len native samples, utterance i starting at place[i]
+ *                  (in bounds and non-overlapping, else refused); out_lens[0] = its samples.
+ * f32 at 44100 without normalisation and place == NULL returns exactly the bytes of sbv2_pipeline_fetch_pcm_ticket. */
+int sbv2_pipeline_fetch_pcm_format(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len,
+                                   void* dst, int64_t capacity_bytes, int64_t* out_lens);
+
 /* ---- sbv2file.rs:15-37 `parse_sbv2file(bytes) -> (style_vectors, vits2)`: a .sbv2 file is zstd(tar{version.txt, model.onnx,
  * style_vectors.json}) (writer: scripts/convert/convert_model.py:156-175).  Both outputs are owned copies (sbv2_bytes_free).
  * Errors: "model not found: style_vectors" / "model not found: vits2" (Error::ModelNotFoundError, sbv2file.rs:31-36). ------------------- */
@@ -192,6 +216,13 @@ int sbv2_stream_begin(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch,
                       const int64_t* word2ph, int64_t chunk_frames, sbv2_stream** out, int64_t* total_samples);
 /* next chunk -> dst (host; capacity samples, chunk_frames * hop always suffices); *n = samples written, 0 at the end */
 int sbv2_stream_next(sbv2_stream* s, float* dst, int64_t capacity, int64_t* n);
+/* Streaming with an output format (see sbv2_pcm_format): inputs as sbv2_stream_begin; *total_samples at fmt->sample_rate; fmt->normalize must be 0
+ * (a stream cannot know the peak ahead).  Chunk c of native samples [a, b) emits output samples [ceil(a L / M), ceil(b L / M)), so the chunks
+ * concatenate to the formatted whole utterance.  sbv2_stream_next is refused on such a stream, sbv2_stream_next_format on any other. */
+int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
+                             const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, sbv2_stream** out, int64_t* total_samples);
+/* next chunk -> dst (host; capacity_bytes); *n = samples written, 0 at the end */
+int sbv2_stream_next_format(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n);
 int sbv2_stream_uses_graph(const sbv2_stream* s);
 int64_t sbv2_stream_workspace_bytes(const sbv2_stream* s);
 void sbv2_stream_end(sbv2_stream* s);

@@ -19,6 +19,11 @@ class Sbv2Batch(C.Structure):
     ]
 
 
+class Sbv2PcmFormat(C.Structure):
+    """struct sbv2_pcm_format (include/sbv2_hip.h)."""
+    _fields_ = [("sample_rate", C.c_int32), ("encoding", C.c_int32), ("normalize", C.c_int32), ("reserved", C.c_int32)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -57,6 +62,9 @@ SYMBOLS = {
     "sbv2_pipeline_fetch_pcm_ticket": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),
     "sbv2_pipeline_last_ticket": (C.c_int64, [C.c_void_p]),
     "sbv2_pipeline_wait": (C.c_int, [C.c_void_p, C.c_int64]),
+    "sbv2_pcm_format_length": (C.c_int64, [C.POINTER(Sbv2PcmFormat), C.c_int64]),
+    "sbv2_pcm_format_taps": (C.c_int, [C.c_int32, f32p, C.c_int64, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sbv2_pipeline_fetch_pcm_format": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, C.c_int64, C.c_void_p, C.c_int64, i64p]),
     "sbv2_host_alloc": (C.c_void_p, [C.c_size_t]),
     "sbv2_host_free": (None, [C.c_void_p]),
     "sbv2_deal": (C.c_int, [C.c_int64, i64p, C.c_int, C.POINTER(C.c_int32)]),
@@ -77,6 +85,9 @@ SYMBOLS = {
     "sbv2_node_last_deal": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int64]),
     "sbv2_stream_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), i64p, i64p, i64p, C.c_int64, C.POINTER(C.c_void_p), i64p]),
     "sbv2_stream_next": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, i64p]),
+    "sbv2_stream_begin_format": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), i64p, i64p, i64p, C.c_int64, C.POINTER(Sbv2PcmFormat),
+                                           C.POINTER(C.c_void_p), i64p]),
+    "sbv2_stream_next_format": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, i64p]),
     "sbv2_stream_uses_graph": (C.c_int, [C.c_void_p]),
     "sbv2_stream_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "sbv2_stream_end": (None, [C.c_void_p]),

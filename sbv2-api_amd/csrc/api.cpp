@@ -322,6 +322,93 @@ int sbv2_pipeline_fetch_pcm(sbv2_pipeline* p, float* dst, int64_t capacity, int 
     return sbv2_pipeline_fetch_pcm_ticket(p, p ? p->calls : -1, dst, capacity, dst_is_device);
 }
 
+// ---- output formats (pcm_format.hip) ----
+int64_t sbv2_pcm_format_length(const sbv2_pcm_format* fmt, int64_t n_native) {
+    try {
+        const PcmFmtSpec spec = pcm_format_spec(fmt);
+        SBV2_REQUIRE(n_native >= 0, "negative sample count");
+        return pcm_format_out_len(spec, n_native);
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+int sbv2_pcm_format_taps(int32_t sample_rate, float* h, int64_t cap, int64_t* len, int32_t* L, int32_t* M) {
+    API_BEGIN
+    SBV2_REQUIRE(len, "bad arguments");
+    int l, m, half;
+    const std::vector<double> proto = pcm_format_prototype(sample_rate, &l, &m, &half);
+    SBV2_REQUIRE(!h || cap >= (int64_t)proto.size(), "tap buffer too small: " + std::to_string(cap) + " < " + std::to_string(proto.size()));
+    *len = (int64_t)proto.size();
+    if (L) *L = l;
+    if (M) *M = m;
+    if (h)
+        for (size_t i = 0; i < proto.size(); ++i) h[i] = (float)proto[i];
+    API_END
+}
+
+// The run's packed PCM (pcm_device + pcm_offs / pcm_lens) is formatted by one launch on the run's own stream, then crosses PCIe in the format.
+int sbv2_pipeline_fetch_pcm_format(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len,
+                                   void* dst, int64_t capacity_bytes, int64_t* out_lens) {
+    API_BEGIN
+    SBV2_REQUIRE(p && dst && out_lens, "bad arguments");
+    const PcmFmtSpec spec = pcm_format_spec(fmt);
+    const int ctx = p->ctx_of(ticket);
+    VitsModel& vm = p->vm(ctx);
+    const std::vector<int64_t>& lens = vm.pcm_lens();
+    const std::vector<int64_t>& offs = vm.pcm_offs();
+    const int n = (int)lens.size();
+    const float* pcm = vm.pcm_device();
+    std::vector<FmtPiece> pieces;
+    std::vector<FmtSignal> sig;
+    std::vector<int64_t> outs;
+    int64_t total = 0;
+    if (!place) {
+        for (int i = 0; i < n; ++i) {
+            const int64_t j1 = pcm_format_out_len(spec, lens[i]);
+            pieces.push_back(FmtPiece{pcm + offs[i], 0, lens[i]});
+            sig.push_back(FmtSignal{0, j1, total, i, i + 1});
+            outs.push_back(j1);
+            total += j1;
+        }
+    } else {
+        SBV2_REQUIRE(joined_len >= 0, "joined_len must be >= 0");
+        std::vector<int> order(n);
+        for (int i = 0; i < n; ++i) {
+            order[i] = i;
+            SBV2_REQUIRE(place[i] >= 0 && place[i] + lens[i] <= joined_len,
+                         "placement of utterance " + std::to_string(i) + " (" + std::to_string(place[i]) + " + " + std::to_string(lens[i]) +
+                             " samples) is outside the joined timeline of " + std::to_string(joined_len) + " samples");
+        }
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return place[a] < place[b]; });
+        for (int r = 0; r < n; ++r) {
+            const int i = order[r];
+            if (r) SBV2_REQUIRE(place[order[r - 1]] + lens[order[r - 1]] <= place[i], "placements of utterances overlap on the joined timeline");
+            if (lens[i]) pieces.push_back(FmtPiece{pcm + offs[i], place[i], lens[i]});
+        }
+        total = pcm_format_out_len(spec, joined_len);
+        sig.push_back(FmtSignal{0, total, 0, 0, (int32_t)pieces.size()});
+        outs.push_back(total);
+    }
+    SBV2_REQUIRE(capacity_bytes >= total * spec.bytes(),
+                 "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(total * spec.bytes()) + " bytes");
+    HIP_CHECK(hipSetDevice(vm.device()));
+    if (spec.identity() && !place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
+        HIP_CHECK(hipMemcpyAsync(dst, pcm, sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, vm.stream()));
+    } else if (total > 0) {
+        if ((int)p->fmts.size() < p->contexts()) p->fmts.resize(p->contexts());
+        if (!p->fmts[ctx]) p->fmts[ctx].reset(new PcmFormatter(vm.device()));
+        PcmFormatter& f = *p->fmts[ctx];
+        void* dev = f.out_buffer((size_t)total * spec.bytes(), vm.stream());
+        f.run(spec, pieces, sig, total, dev, 0, vm.stream());
+        HIP_CHECK(hipMemcpyAsync(dst, dev, (size_t)total * spec.bytes(), hipMemcpyDeviceToHost, vm.stream()));
+    }
+    HIP_CHECK(hipStreamSynchronize(vm.stream()));
+    for (size_t i = 0; i < outs.size(); ++i) out_lens[i] = outs[i];
+    API_END
+}
+
 // Pinned host memory for PCM destinations: a device -> host copy into pageable memory is staged by the runtime at a fraction of the
 // PCIe rate; into these buffers it is one DMA that overlaps the other execution context's kernels.
 void* sbv2_host_alloc(size_t bytes) {

@@ -8,6 +8,7 @@
 
 #include "../../include/sbv2_hip.h"
 #include "models.h"
+#include "pcm_format.h"
 
 namespace sbv2 {
 const char* last_error_cstr();
@@ -26,6 +27,7 @@ struct sbv2_pipeline {
     // execution contexts: context 0 is the caller's pair of handles, the others are clones (shared weights, own stream + arena)
     std::vector<std::unique_ptr<BertModel>> bclones;
     std::vector<std::unique_ptr<VitsModel>> vclones;
+    std::vector<std::unique_ptr<PcmFormatter>> fmts;   // per context: the formatting launches of sbv2_pipeline_fetch_pcm_format
     int64_t calls = 0;   // tickets are call numbers 1, 2, ...: ticket t ran on context (t - 1) % depth and is valid until that context is reused
     BertModel& bm(int i) { return i == 0 ? *bert->m : *bclones[i - 1]; }
     VitsModel& vm(int i) { return i == 0 ? *vits->m : *vclones[i - 1]; }

@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "ops.h"
+#include "pcm_format.h"
 
 #include <memory>
 
@@ -230,8 +231,13 @@ class VitsModel {
     // [f0, f0 + chunk_frames) into dst (host) and returns the number of samples written.
     // halo frames per side = the generator's receptive field (from the config: 13.4 frames -> 16 for JP-Extra, SURVEY.md §5 "Long-context")
     int stream_halo() const;
-    int64_t stream_begin(int chunk_frames);
+    double stream_receptive_field() const;   // frames per side, before the margin and rounding of stream_halo
+    // fmt (optional): the chunks leave the device in that output format (pcm_format.h; normalize must be 0): chunk [a, b) of native samples
+    // emits output samples [ceil(a L / M), ceil(b L / M)), computed from the window's exact samples beyond the centre
+    int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr);
     int64_t stream_chunk(int64_t f0, float* dst_host, int64_t capacity);
+    // formatted stream: output samples of the chunk at f0 -> dst_host (capacity_bytes); returns the samples written
+    int64_t stream_chunk_format(int64_t f0, void* dst_host, int64_t capacity_bytes);
     bool stream_graph_captured() const { return chunk_ && chunk_->exec != nullptr; }
     size_t stream_workspace_bytes() const { return (chunk_ ? chunk_->ar.capacity() : 0) + (burst_ ? burst_->ar.capacity() : 0); }
     // results of the last forward
@@ -338,6 +344,8 @@ class VitsModel {
         float* host[2] = {nullptr, nullptr};
         hipEvent_t ev[2] = {nullptr, nullptr};
         int64_t slot_f0[2] = {-1, -1}, slot_n[2] = {0, 0};
+        size_t host_bytes = 0;                      // capacity of each pinned slot
+        std::vector<int64_t> fmt_off[2], fmt_n[2];  // formatted stream: each window's output samples in its slot (offset, count)
         ~ChunkPlan() {
             if (exec) (void)hipGraphExecDestroy(exec);
             if (graph) (void)hipGraphDestroy(graph);
@@ -349,6 +357,11 @@ class VitsModel {
     };
     void ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, int nwin);
     void stream_enqueue(ChunkPlan& c, int64_t f0, int slot);
+    int64_t stream_take(int64_t f0, void* dst_host, int64_t capacity_bytes, bool formatted);
+    size_t stream_fmt_bytes(const ChunkPlan& c) const;   // formatted output of one replay of c, upper bound
+    bool sfmt_on_ = false;                       // the running stream is formatted (stream_begin with fmt)
+    PcmFmtSpec sfmt_;
+    std::shared_ptr<PcmFormatter> sfmtr_;          // its launches: slots 0 / 1 = chunk_'s, 2 / 3 = burst_'s
     bool stream_bursts_ = false;                 // the running stream uses burst_ behind its first chunk
     std::shared_ptr<ChunkPlan> chunk_, burst_;   // one window (an utterance's first chunk) / kStreamBurst windows per replay (every later one)
     Plane z_{};              // flow output of the last forward (frame-rate plane, packed layout fl_)

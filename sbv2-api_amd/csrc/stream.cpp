@@ -11,6 +11,7 @@ struct sbv2_stream {
     sbv2_bert* bert = nullptr;
     sbv2_vits* vits = nullptr;
     int64_t frames = 0, next = 0, chunk = 0;
+    bool formatted = false;
 };
 
 extern "C" {
@@ -42,9 +43,45 @@ int sbv2_stream_begin(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch,
 int sbv2_stream_next(sbv2_stream* s, float* dst, int64_t capacity, int64_t* n) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n, "bad arguments");
+    SBV2_REQUIRE(!s->formatted, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
     *n = 0;
     if (s->next < s->frames) {
         *n = s->vits->m->stream_chunk(s->next, dst, capacity);
+        s->next += s->chunk;
+    }
+    API_END
+}
+
+// Same as sbv2_stream_begin with the chunks leaving the device in `fmt` (formatted by one launch per decoder replay, vits.cpp stream_enqueue).
+int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
+                             const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, sbv2_stream** out, int64_t* total_samples) {
+    API_BEGIN
+    SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
+    SBV2_REQUIRE(batch->n == 1, "sbv2_stream_begin_format takes one utterance");
+    SBV2_REQUIRE(bert->m->device() == vits->m->device(), "bert and vits handles live on different devices");
+    const PcmFmtSpec spec = pcm_format_spec(fmt);
+    SBV2_REQUIRE(!spec.normalize, "a formatted stream cannot normalise (normalize must be 0): the peak of the utterance is not known ahead");
+    VitsBatch v = to_batch(batch);
+    v.skip_decoder = true;
+    pipeline_run_one(*bert->m, *vits->m, v, token_ids, s_lens, word2ph);
+    std::unique_ptr<sbv2_stream> s(new sbv2_stream);
+    s->bert = bert;
+    s->vits = vits;
+    s->chunk = chunk_frames;
+    s->formatted = true;
+    s->frames = vits->m->stream_begin((int)chunk_frames, &spec);
+    if (total_samples) *total_samples = pcm_format_out_len(spec, s->frames * vits->m->cfg().hop());
+    *out = s.release();
+    API_END
+}
+
+int sbv2_stream_next_format(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n) {
+    API_BEGIN
+    SBV2_REQUIRE(s && dst && n, "bad arguments");
+    SBV2_REQUIRE(s->formatted, "this stream has no output format: take its chunks with sbv2_stream_next");
+    *n = 0;
+    if (s->next < s->frames) {
+        *n = s->vits->m->stream_chunk_format(s->next, dst, capacity_bytes);
         s->next += s->chunk;
     }
     API_END

@@ -335,6 +335,8 @@ VitsModel* VitsModel::clone() const {
     c->traces_.clear();
     c->chunk_.reset();
     c->burst_.reset();
+    c->sfmtr_.reset();
+    c->sfmt_on_ = false;
     c->z_ = Plane{};
     c->trace_ = false;
     return c;
@@ -843,7 +845,7 @@ void VitsModel::forward(const VitsBatch& b) {
 // hipGraph and replayed per chunk; all device pointers of the captured launches live in the plan's own arena.
 // Receptive field of the generator per side, in frames: conv_pre + per stage {transposed-conv taps at the input rate, the widest MRF branch
 // sum_d (d + 1)(k - 1) / 2 at the output rate} + conv_post; + 1 frame of margin, rounded up to a multiple of 4.
-int VitsModel::stream_halo() const {
+double VitsModel::stream_receptive_field() const {
     double rf = (dec_pre_.k - 1) / 2.0;
     double rate = 1.0;
     for (size_t i = 0; i < stages_.size(); ++i) {
@@ -861,8 +863,9 @@ int VitsModel::stream_halo() const {
         rf += mrf / rate;
     }
     rf += (dec_post_k_ - 1) / 2.0 / rate;
-    return round_up((int)std::ceil(rf) + 1, 4);
+    return rf;
 }
+int VitsModel::stream_halo() const { return round_up((int)std::ceil(stream_receptive_field()) + 1, 4); }
 
 // A decode plan = nwin windows of chunk + 2 * halo frames packed into one batch (the packed-batch layout: the gaps between the windows are
 // the zero padding of every convolution), its persistent input / conditioning buffers, its own arena and the graph captured for that shape.
@@ -884,6 +887,7 @@ void VitsModel::ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, 
         c.mark = c.ar.mark();
         for (int i = 0; i < 2; ++i) {
             HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.host[i]), sizeof(float) * (size_t)nwin * chunk_frames * cfg_.hop(), hipHostMallocDefault));
+            c.host_bytes = sizeof(float) * (size_t)nwin * chunk_frames * cfg_.hop();
             HIP_CHECK(hipEventCreateWithFlags(&c.ev[i], hipEventDisableTiming));
         }
     }
@@ -924,10 +928,22 @@ void VitsModel::ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, 
     c.slot_f0[0] = c.slot_f0[1] = -1;
 }
 
-int64_t VitsModel::stream_begin(int chunk_frames) {
+int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(fl_.n == 1 && z_.p, "stream_begin needs a preceding forward of ONE utterance with skip_decoder");
     SBV2_REQUIRE(chunk_frames >= 16 && chunk_frames <= (1 << 20), "chunk_frames must be in [16, 2^20]");
+    sfmt_on_ = false;
+    if (fmt) {
+        SBV2_REQUIRE(!fmt->normalize, "a formatted stream cannot normalise: the peak of the utterance is not known ahead");
+        // the filter of an output sample at a chunk edge reaches ceil(half / L) native samples past the window centre; they must lie in the
+        // part of the halo that the decoder computes exactly (halo minus the generator's receptive field)
+        const int64_t reach = (fmt->half + fmt->L - 1) / fmt->L;
+        const double exact = (stream_halo() - stream_receptive_field()) * cfg_.hop();
+        SBV2_REQUIRE((double)reach <= exact, "the " + std::to_string(fmt->rate) + " Hz filter reaches " + std::to_string(reach) +
+                                                 " samples past a chunk edge, the stream halo holds only " + std::to_string((int64_t)exact) + " exact samples");
+        sfmt_ = *fmt;
+        if (!sfmtr_) sfmtr_ = std::make_shared<PcmFormatter>(device_);
+    }
     constexpr int burst = kStreamBurst;   // (1 / 2 / 4 / 8 / 12 / 16 windows per replay measured in round 3: 2.62 / 1.88 / 1.64 / 1.41 / 1.39 / 1.47 ms per chunk)
     const int64_t Tf = fl_.len[0];
     ensure_plan(chunk_, chunk_frames, 1);
@@ -944,6 +960,26 @@ int64_t VitsModel::stream_begin(int chunk_frames) {
         ensure_plan(burst_, chunk_frames, nw);
     }
     stream_bursts_ = want_burst;
+    if (fmt) {   // pinned slots and the device output sized for the format (f32 at 48 kHz is larger than native)
+        size_t dev = 0;
+        for (ChunkPlan* c : {chunk_.get(), want_burst ? burst_.get() : nullptr}) {
+            if (!c) continue;
+            const size_t need = stream_fmt_bytes(*c);
+            dev = std::max(dev, need);
+            if (need > c->host_bytes) {
+                HIP_CHECK(hipStreamSynchronize(stream_));
+                for (int i = 0; i < 2; ++i) {
+                    HIP_CHECK(hipHostFree(c->host[i]));
+                    c->host[i] = nullptr;
+                }
+                c->host_bytes = 0;
+                for (int i = 0; i < 2; ++i) HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c->host[i]), need, hipHostMallocDefault));
+                c->host_bytes = need;
+            }
+        }
+        sfmtr_->out_buffer(dev, stream_);
+        sfmt_on_ = true;
+    }
     stream_enqueue(*chunk_, 0, 0);                            // the first chunk starts right behind the flow ...
     if (want_burst) stream_enqueue(*burst_, chunk_frames, 0); // ... and the first burst right behind it
     return Tf;
@@ -971,6 +1007,33 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
         c.pcm = pcm_;
     }
     int64_t total = 0;
+    if (sfmt_on_) {
+        // ONE formatting launch over the replay's windows: window w holds native samples [(fw - halo) hop, (fw - halo + W) hop) of the utterance,
+        // clipped to [0, N) (the decoder's output outside the utterance is not silence); its chunk [a, b) emits [ceil(a L / M), ceil(b L / M))
+        const int64_t N = Tf * hop;
+        std::vector<FmtPiece> pieces;
+        std::vector<FmtSignal> sig;
+        c.fmt_off[slot].clear();
+        c.fmt_n[slot].clear();
+        for (int w = 0; w < c.nwin; ++w) {
+            const int64_t fw = f0 + (int64_t)w * c.chunk;
+            if (fw >= Tf) break;
+            const int64_t ws = (fw - halo) * hop, lo = std::max<int64_t>(0, ws), hi = std::min<int64_t>(N, ws + (int64_t)c.W * hop);
+            pieces.push_back(FmtPiece{c.pcm + (size_t)w * c.W * hop + (lo - ws), lo, hi - lo});
+            const int64_t j0 = pcm_format_out_len(sfmt_, fw * hop), j1 = pcm_format_out_len(sfmt_, std::min<int64_t>(fw + c.chunk, Tf) * hop);
+            sig.push_back(FmtSignal{j0, j1, total, w, w + 1});
+            c.fmt_off[slot].push_back(total);
+            c.fmt_n[slot].push_back(j1 - j0);
+            total += j1 - j0;
+        }
+        void* dev = sfmtr_->out_buffer(stream_fmt_bytes(c), stream_);
+        sfmtr_->run(sfmt_, pieces, sig, total, dev, (&c == burst_.get() ? 2 : 0) + slot, stream_);
+        if (total) HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)total * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipEventRecord(c.ev[slot], stream_));
+        c.slot_f0[slot] = f0;
+        c.slot_n[slot] = total;
+        return;
+    }
     for (int w = 0; w < c.nwin; ++w) {
         const int64_t fw = f0 + (int64_t)w * c.chunk;
         if (fw >= Tf) break;
@@ -984,7 +1047,21 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
     c.slot_n[slot] = total;
 }
 
+size_t VitsModel::stream_fmt_bytes(const ChunkPlan& c) const {
+    return (size_t)c.nwin * (size_t)(pcm_format_out_len(sfmt_, (int64_t)c.chunk * cfg_.hop()) + 1) * sfmt_.bytes();
+}
+
 int64_t VitsModel::stream_chunk(int64_t f0, float* dst_host, int64_t capacity) {
+    SBV2_REQUIRE(!sfmt_on_, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
+    return stream_take(f0, dst_host, capacity * (int64_t)sizeof(float), false);
+}
+
+int64_t VitsModel::stream_chunk_format(int64_t f0, void* dst_host, int64_t capacity_bytes) {
+    SBV2_REQUIRE(sfmt_on_, "this stream has no output format: take its chunks with sbv2_stream_next");
+    return stream_take(f0, dst_host, capacity_bytes, true);
+}
+
+int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bool formatted) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(chunk_ && z_.p && fl_.n == 1, "stream_chunk without stream_begin");
     ChunkPlan& c1 = *chunk_;
@@ -992,7 +1069,21 @@ int64_t VitsModel::stream_chunk(int64_t f0, float* dst_host, int64_t capacity) {
     SBV2_REQUIRE(f0 >= 0 && f0 < Tf && f0 % c1.chunk == 0, "chunk start out of range");
     const int hop = cfg_.hop();
     const int64_t nsamp = std::min<int64_t>(c1.chunk, Tf - f0) * hop;
-    SBV2_REQUIRE(capacity >= nsamp, "PCM buffer too small for the chunk");
+    const int64_t esz = formatted ? sfmt_.bytes() : (int64_t)sizeof(float);
+    SBV2_REQUIRE(formatted || capacity_bytes >= nsamp * esz, "PCM buffer too small for the chunk");
+    char* dst_host = static_cast<char*>(dst);
+    // formatted: window w of the slot's replay -> its recorded output range
+    auto deliver = [&](ChunkPlan& c, int slot, int64_t w) -> int64_t {
+        if (!formatted) {
+            std::memcpy(dst_host, c.host[slot] + (size_t)w * c1.chunk * hop, sizeof(float) * (size_t)nsamp);
+            return nsamp;
+        }
+        SBV2_REQUIRE(w < (int64_t)c.fmt_n[slot].size(), "formatted chunk missing from its replay");
+        const int64_t n = c.fmt_n[slot][w];
+        SBV2_REQUIRE(capacity_bytes >= n * esz, "PCM buffer too small for the chunk: " + std::to_string(capacity_bytes) + " < " + std::to_string(n * esz) + " bytes");
+        std::memcpy(dst_host, reinterpret_cast<const char*>(c.host[slot]) + (size_t)c.fmt_off[slot][w] * esz, (size_t)(n * esz));
+        return n;
+    };
     const int64_t ci = f0 / c1.chunk;
     const bool bursts = stream_bursts_ && burst_ && burst_->chunk == c1.chunk;
     if (ci == 0 || !bursts) {
@@ -1001,9 +1092,9 @@ int64_t VitsModel::stream_chunk(int64_t f0, float* dst_host, int64_t capacity) {
         if (c1.slot_f0[slot] != f0) stream_enqueue(c1, f0, slot);                                  // (random access: not the streaming order)
         if (!bursts && f0 + c1.chunk < Tf && c1.slot_f0[slot ^ 1] != f0 + c1.chunk) stream_enqueue(c1, f0 + c1.chunk, slot ^ 1);
         HIP_CHECK(hipEventSynchronize(c1.ev[slot]));
-        std::memcpy(dst_host, c1.host[slot], sizeof(float) * (size_t)nsamp);
+        const int64_t n = deliver(c1, slot, 0);
         c1.slot_f0[slot] = -1;
-        return nsamp;
+        return n;
     }
     ChunkPlan& cb = *burst_;
     const int64_t bi = (ci - 1) / cb.nwin, within = (ci - 1) % cb.nwin;
@@ -1014,8 +1105,7 @@ int64_t VitsModel::stream_chunk(int64_t f0, float* dst_host, int64_t capacity) {
     const int64_t nf0 = bf0 + (int64_t)cb.nwin * c1.chunk;
     if (within == 0 && nf0 < Tf && cb.slot_f0[slot ^ 1] != nf0) stream_enqueue(cb, nf0, slot ^ 1);
     HIP_CHECK(hipEventSynchronize(cb.ev[slot]));
-    std::memcpy(dst_host, cb.host[slot] + (size_t)within * c1.chunk * hop, sizeof(float) * (size_t)nsamp);
-    return nsamp;
+    return deliver(cb, slot, within);
 }
 
 void VitsModel::copy_pcm(float* host) {

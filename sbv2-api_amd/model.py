@@ -11,7 +11,8 @@ import numpy as np
 from . import _lib
 from ._lib import Sbv2Batch, Sbv2Error, check, f32p, i64p
 
-__all__ = ["Session", "load_model", "predict", "synthesize", "predict_batch", "synthesize_batch", "Pipeline", "Node", "Comm", "deal", "Sbv2Error"]
+__all__ = ["Session", "load_model", "predict", "synthesize", "predict_batch", "synthesize_batch", "Pipeline", "Node", "Comm", "deal", "Sbv2Error",
+           "PcmFormat", "pcm_format_length", "pcm_format_taps"]
 
 
 def _i64(a):
@@ -107,6 +108,49 @@ def synthesize(session: Session, bert_ori, x_tst, spk_ids, tones, lang_ids, styl
     finally:
         l.sbv2_pcm_free(pcm)
     return out.reshape(1, 1, -1)
+
+
+ENCODINGS = {"f32": 0, "s16": 1}
+
+
+class PcmFormat:
+    """Output format of the PCM (struct sbv2_pcm_format): sample_rate in {8000, 16000, 22050, 24000, 32000, 44100, 48000}, encoding "f32" or
+    "s16", normalize = peak of each output signal to full scale.  Resampling, normalisation and quantisation run on the device."""
+
+    def __init__(self, sample_rate: int = 44100, encoding: str = "f32", normalize: bool = False):
+        if encoding not in ENCODINGS:
+            raise Sbv2Error(f"unsupported PCM encoding {encoding!r} (f32, s16)")
+        self.sample_rate, self.encoding, self.normalize = int(sample_rate), encoding, bool(normalize)
+        self.c = _lib.Sbv2PcmFormat(self.sample_rate, ENCODINGS[encoding], int(self.normalize), 0)
+
+    @property
+    def dtype(self):
+        return np.int16 if self.encoding == "s16" else np.float32
+
+    @property
+    def is_default(self) -> bool:
+        return self.sample_rate == 44100 and self.encoding == "f32" and not self.normalize
+
+    def __repr__(self):
+        return f"PcmFormat({self.sample_rate}, {self.encoding!r}, normalize={self.normalize})"
+
+
+def pcm_format_length(fmt: PcmFormat, n_native: int) -> int:
+    """Samples of an n_native-sample 44.1 kHz signal in `fmt`: ceil(n L / M) (host only)."""
+    n = _lib.lib().sbv2_pcm_format_length(C.byref(fmt.c), int(n_native))
+    if n < 0:
+        raise Sbv2Error(_lib.lib().sbv2_last_error().decode(errors="replace"))
+    return n
+
+
+def pcm_format_taps(sample_rate: int):
+    """(h, L, M): the library's resampling prototype for a rate (host only; test hook)."""
+    l = _lib.lib()
+    n, L, M = C.c_int64(), C.c_int32(), C.c_int32()
+    check(l.sbv2_pcm_format_taps(sample_rate, None, 0, C.byref(n), C.byref(L), C.byref(M)))
+    h = np.empty(n.value, np.float32)
+    check(l.sbv2_pcm_format_taps(sample_rate, h.ctypes.data_as(f32p), h.size, C.byref(n), C.byref(L), C.byref(M)))
+    return h, L.value, M.value
 
 
 class _Batch:
@@ -226,6 +270,28 @@ class Pipeline:
         check(_lib.lib().sbv2_pipeline_fetch_pcm_ticket(self.h, b.ticket, pcm.ctypes.data_as(C.c_void_p), pcm.size, 0))
         return np.split(pcm[:n], np.cumsum(b.lens)[:-1])
 
+    def fetch_format(self, b, fmt: PcmFormat, place=None, joined_len=None):
+        """PCM of the run `b` in the output format `fmt` (resampled / normalised / quantised on the device; int16 or float32 arrays).
+        place None: one array per utterance.  place [n] native-sample offsets + joined_len: ONE array, the utterances laid on a silent
+        timeline of joined_len native samples."""
+        l = _lib.lib()
+        lens = [int(v) for v in b.lens]
+        if place is None:
+            outs = [pcm_format_length(fmt, n) for n in lens]
+            pp, jl = None, 0
+        else:
+            if joined_len is None:
+                raise Sbv2Error("a placement needs joined_len")
+            pl, pp = _i64(place)
+            if pl.shape != (len(lens),):
+                raise Sbv2Error(f"place must hold one offset per utterance ({len(lens)})")
+            outs, jl = [pcm_format_length(fmt, joined_len)], int(joined_len)
+        out = np.empty(max(sum(outs), 1), fmt.dtype)
+        got = np.zeros(len(outs), np.int64)
+        check(l.sbv2_pipeline_fetch_pcm_format(self.h, b.ticket, C.byref(fmt.c), pp, jl, out.ctypes.data_as(C.c_void_p), out.nbytes,
+                                               got.ctypes.data_as(i64p)))
+        return np.split(out[:int(got.sum())], np.cumsum(got)[:-1])
+
     def close(self):
         if self.h:
             _lib.lib().sbv2_pipeline_destroy(self.h)
@@ -248,21 +314,33 @@ def stream_synthesize(bert: Session, vits: Session, utt, chunk_frames=256, **kw)
 
 
 class StreamHandle:
-    def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, **kw):
+    """fmt (PcmFormat, optional): the chunks leave the device in that format (normalize is refused: a stream cannot know the peak ahead);
+    total_samples is then counted at fmt.sample_rate."""
+
+    def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, **kw):
         l = _lib.lib()
         self.b = Pipeline.prepare(None, [utt], **kw)
         self.h = C.c_void_p()
+        self.fmt = fmt
         tot = C.c_int64()
-        check(l.sbv2_stream_begin(bert.handle, vits.handle, C.byref(self.b.c), self.b.ids.ctypes.data_as(i64p), self.b.s_lens.ctypes.data_as(i64p),
-                                  self.b.w2p.ctypes.data_as(i64p), chunk_frames, C.byref(self.h), C.byref(tot)))
+        args = (bert.handle, vits.handle, C.byref(self.b.c), self.b.ids.ctypes.data_as(i64p), self.b.s_lens.ctypes.data_as(i64p),
+                self.b.w2p.ctypes.data_as(i64p), chunk_frames)
+        if fmt is None:
+            check(l.sbv2_stream_begin(*args, C.byref(self.h), C.byref(tot)))
+            self.buf = np.empty(chunk_frames * l.sbv2_vits_hop(vits.handle), np.float32)
+        else:
+            check(l.sbv2_stream_begin_format(*args, C.byref(fmt.c), C.byref(self.h), C.byref(tot)))
+            self.buf = np.empty(pcm_format_length(fmt, chunk_frames * l.sbv2_vits_hop(vits.handle)) + 1, fmt.dtype)
         self.total_samples = tot.value
-        self.buf = np.empty(chunk_frames * l.sbv2_vits_hop(vits.handle), np.float32)
         self.uses_graph = bool(l.sbv2_stream_uses_graph(self.h))
         self.workspace_bytes = l.sbv2_stream_workspace_bytes(self.h)
 
     def next(self):
         n = C.c_int64()
-        check(_lib.lib().sbv2_stream_next(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.size, C.byref(n)))
+        if self.fmt is None:
+            check(_lib.lib().sbv2_stream_next(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.size, C.byref(n)))
+        else:
+            check(_lib.lib().sbv2_stream_next_format(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.nbytes, C.byref(n)))
         return None if n.value == 0 else self.buf[:n.value].copy()
 
     def close(self):

@@ -30,10 +30,13 @@ NOISE_SCALE_W = 0.8         # tts.rs:314 / :344
 
 
 class SynthesizeOptions:
-    """tts.rs:359-375 (same defaults)."""
+    """tts.rs:359-375 (same defaults).  sample_rate / encoding / normalize are new (the reference writes 44.1 kHz f32 only): when any of
+    them differs from its default the request's WAV signal is resampled / normalised / quantised on the device (model.PcmFormat)."""
 
-    def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True):
+    def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
+                 normalize=False):
         self.sdp_ratio, self.length_scale, self.style_weight, self.split_sentences = sdp_ratio, length_scale, style_weight, split_sentences
+        self.sample_rate, self.encoding, self.normalize = sample_rate, encoding, normalize
 
 
 def load_style(data: bytes) -> np.ndarray:
@@ -61,14 +64,42 @@ def array_to_wav(audio: np.ndarray) -> bytes:
     a = np.ascontiguousarray(np.asarray(audio, np.float32))
     if a.ndim != 3:
         raise ValueError("audio must be [B, 1, L]")
-    samples = a[:, 0, :].reshape(-1).astype("<f4")
-    data = samples.tobytes()
-    channels, bits = 1, 32
-    block = channels * bits // 8
-    fmt = struct.pack("<HHIIHHHHI", 0xFFFE, channels, SAMPLE_RATE, SAMPLE_RATE * block, block, bits, 22, bits, (1 << channels) - 1)
-    fmt += bytes([0x03, 0x00, 0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xAA, 0x00, 0x38, 0x9B, 0x71])
+    return float_wav(a[:, 0, :].reshape(-1), SAMPLE_RATE)
+
+
+def _riff(fmt: bytes, data: bytes) -> bytes:
     body = b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt + b"data" + struct.pack("<I", len(data)) + data
     return b"RIFF" + struct.pack("<I", len(body)) + body
+
+
+def float_wav(samples: np.ndarray, rate: int) -> bytes:
+    """Mono 32-bit float WAV at any rate, in the WAVE_FORMAT_EXTENSIBLE form of array_to_wav."""
+    data = np.ascontiguousarray(samples, dtype="<f4").tobytes()
+    channels, bits = 1, 32
+    block = channels * bits // 8
+    fmt = struct.pack("<HHIIHHHHI", 0xFFFE, channels, rate, rate * block, block, bits, 22, bits, (1 << channels) - 1)
+    fmt += bytes([0x03, 0x00, 0x00, 0x00, 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xAA, 0x00, 0x38, 0x9B, 0x71])
+    return _riff(fmt, data)
+
+
+def pcm16_wav(samples: np.ndarray, rate: int) -> bytes:
+    """Mono 16-bit integer WAV at any rate: WAVE_FORMAT_PCM, 16-byte fmt chunk, 44-byte header (hound's form for <= 16-bit integer mono)."""
+    data = np.ascontiguousarray(samples, dtype="<i2").tobytes()
+    channels, bits = 1, 16
+    block = channels * bits // 8
+    return _riff(struct.pack("<HHIIHH", 0x0001, channels, rate, rate * block, block, bits), data)
+
+
+def joined_placement(lens, live_index, n_lines, split_sentences=True):
+    """Offsets of the live sentences on the WAV timeline of easy_synthesize (22050 zero samples after every sentence that is not the last
+    line) and the timeline's length, in native samples."""
+    place, pos = [], 0
+    for n, i in zip(lens, live_index):
+        place.append(pos)
+        pos += int(n)
+        if split_sentences and i != n_lines - 1:
+            pos += SENTENCE_GAP
+    return place, pos
 
 
 def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
@@ -83,10 +114,16 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     live = [(i, s) for i, s in enumerate(sentences) if s]
     if not live:
         raise model.Sbv2Error("nothing to synthesize (the reference's concatenate fails on an empty list)")
+    fmt = model.PcmFormat(options.sample_rate, options.encoding, options.normalize)
+    model.pcm_format_length(fmt, 0)   # a bad rate is refused before any GPU work
     utts = [dict(s, style=style, sid=speaker_id) for _, s in live]
     b = pipe.prepare(utts, sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
                      noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     pipe.run(b)
+    if not fmt.is_default:   # ONE joined fetch: the WAV signal below, resampled / normalised / quantised as a whole on the device
+        place, joined = joined_placement(b.lens, [i for i, _ in live], len(sentences), options.split_sentences)
+        out = pipe.fetch_format(b, fmt, place, joined)[0]
+        return pcm16_wav(out, fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out, fmt.sample_rate)
     pcm = pipe.fetch(b)
     parts = []
     for (i, _), wav in zip(live, pcm):
