@@ -154,6 +154,25 @@ int sbv2_pcm_format_taps(int32_t sample_rate, float* h, int64_t cap, int64_t* le
 int sbv2_pipeline_fetch_pcm_format(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len,
                                    void* dst, int64_t capacity_bytes, int64_t* out_lens);
 
+/* ---- new: FLAC output (RFC 9639), encoded ON THE DEVICE from the s16 samples of sbv2_pipeline_fetch_pcm_format.  One stream per signal: mono,
+ * 16 bits, fMT->sample_rate, fixed 4096-sample blocks (the last may be shorter), STREAMINFO with min / max frame size and total samples, MD5
+ * zero ("not computed"); each block is the cheapest of CONSTANT, FIXED 0-4, LPC 1-12 (Tukey(0.5) window, precision 15) and VERBATIM, with
+ * Rice partition orders <= 8; streamable subset.  The bytes are a pure function of the samples: two fetches of one ticket are identical. */
+/* Host only: an upper bound on the bytes of one signal's stream, n = sbv2_pcm_format_length(fmt, n_native) samples in frames of 4096:
+ * 42 + 16 ceil(n / 4096) + 2 n (per frame the largest header, a VERBATIM subframe and the CRC-16).  -1 (message in sbv2_last_error) when
+ * fmt is bad or its encoding is not 1 (s16). */
+int64_t sbv2_flac_bound(const sbv2_pcm_format* fmt, int64_t n_native);
+/* The signals of sbv2_pipeline_fetch_pcm_format (same place / joined_len rules; fmt->encoding must be 1 = s16, fmt->normalize as there),
+ * each encoded as one FLAC stream; the streams are written back to back into HOST memory dst, out_bytes[i] = stream i's size (one entry
+ * per utterance, or one for the joined timeline).  Waits for the run.  A result longer than capacity_bytes is refused and nothing is
+ * written (sbv2_flac_bound sums give a capacity that always suffices). */
+int sbv2_pipeline_fetch_flac(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len,
+                             uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes);
+/* Test hook: the same device encoder on host s16 signals (nsig >= 1 signals of lens[i] samples, back to back in x) on `device`, at
+ * sample_rate (a rate of sbv2_pcm_format).  Output as sbv2_pipeline_fetch_flac. */
+int sbv2_debug_flac_encode(int device, const int16_t* x, const int64_t* lens, int nsig, int32_t sample_rate, uint8_t* dst, int64_t capacity,
+                           int64_t* out_bytes);
+
 /* ---- sbv2file.rs:15-37 `parse_sbv2file(bytes) -> (style_vectors, vits2)`: a .sbv2 file is zstd(tar{version.txt, model.onnx,
  * style_vectors.json}) (writer: scripts/convert/convert_model.py:156-175).  Both outputs are owned copies (sbv2_bytes_free).
  * Errors: "model not found: style_vectors" / "model not found: vits2" (Error::ModelNotFoundError, sbv2file.rs:31-36). ------------------- */

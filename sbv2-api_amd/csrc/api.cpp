@@ -348,6 +348,50 @@ int sbv2_pcm_format_taps(int32_t sample_rate, float* h, int64_t cap, int64_t* le
     API_END
 }
 
+// The signals of a formatted fetch: one per utterance (place == NULL), or the run's utterances on one joined timeline.  outs = output samples
+// of each signal; the result is `total` samples.
+static void format_layout(const PcmFmtSpec& spec, VitsModel& vm, const int64_t* place, int64_t joined_len, std::vector<FmtPiece>* pieces,
+                          std::vector<FmtSignal>* sig, std::vector<int64_t>* outs, int64_t* total) {
+    const std::vector<int64_t>& lens = vm.pcm_lens();
+    const std::vector<int64_t>& offs = vm.pcm_offs();
+    const int n = (int)lens.size();
+    const float* pcm = vm.pcm_device();
+    *total = 0;
+    if (!place) {
+        for (int i = 0; i < n; ++i) {
+            const int64_t j1 = pcm_format_out_len(spec, lens[i]);
+            pieces->push_back(FmtPiece{pcm + offs[i], 0, lens[i]});
+            sig->push_back(FmtSignal{0, j1, *total, i, i + 1});
+            outs->push_back(j1);
+            *total += j1;
+        }
+        return;
+    }
+    SBV2_REQUIRE(joined_len >= 0, "joined_len must be >= 0");
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) {
+        order[i] = i;
+        SBV2_REQUIRE(place[i] >= 0 && place[i] + lens[i] <= joined_len,
+                     "placement of utterance " + std::to_string(i) + " (" + std::to_string(place[i]) + " + " + std::to_string(lens[i]) +
+                         " samples) is outside the joined timeline of " + std::to_string(joined_len) + " samples");
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return place[a] < place[b]; });
+    for (int r = 0; r < n; ++r) {
+        const int i = order[r];
+        if (r) SBV2_REQUIRE(place[order[r - 1]] + lens[order[r - 1]] <= place[i], "placements of utterances overlap on the joined timeline");
+        if (lens[i]) pieces->push_back(FmtPiece{pcm + offs[i], place[i], lens[i]});
+    }
+    *total = pcm_format_out_len(spec, joined_len);
+    sig->push_back(FmtSignal{0, *total, 0, 0, (int32_t)pieces->size()});
+    outs->push_back(*total);
+}
+
+static PcmFormatter& formatter(sbv2_pipeline* p, int ctx, int device) {
+    if ((int)p->fmts.size() < p->contexts()) p->fmts.resize(p->contexts());
+    if (!p->fmts[ctx]) p->fmts[ctx].reset(new PcmFormatter(device));
+    return *p->fmts[ctx];
+}
+
 // The run's packed PCM (pcm_device + pcm_offs / pcm_lens) is formatted by one launch on the run's own stream, then crosses PCIe in the format.
 int sbv2_pipeline_fetch_pcm_format(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len,
                                    void* dst, int64_t capacity_bytes, int64_t* out_lens) {
@@ -356,56 +400,109 @@ int sbv2_pipeline_fetch_pcm_format(sbv2_pipeline* p, int64_t ticket, const sbv2_
     const PcmFmtSpec spec = pcm_format_spec(fmt);
     const int ctx = p->ctx_of(ticket);
     VitsModel& vm = p->vm(ctx);
-    const std::vector<int64_t>& lens = vm.pcm_lens();
-    const std::vector<int64_t>& offs = vm.pcm_offs();
-    const int n = (int)lens.size();
-    const float* pcm = vm.pcm_device();
     std::vector<FmtPiece> pieces;
     std::vector<FmtSignal> sig;
     std::vector<int64_t> outs;
     int64_t total = 0;
-    if (!place) {
-        for (int i = 0; i < n; ++i) {
-            const int64_t j1 = pcm_format_out_len(spec, lens[i]);
-            pieces.push_back(FmtPiece{pcm + offs[i], 0, lens[i]});
-            sig.push_back(FmtSignal{0, j1, total, i, i + 1});
-            outs.push_back(j1);
-            total += j1;
-        }
-    } else {
-        SBV2_REQUIRE(joined_len >= 0, "joined_len must be >= 0");
-        std::vector<int> order(n);
-        for (int i = 0; i < n; ++i) {
-            order[i] = i;
-            SBV2_REQUIRE(place[i] >= 0 && place[i] + lens[i] <= joined_len,
-                         "placement of utterance " + std::to_string(i) + " (" + std::to_string(place[i]) + " + " + std::to_string(lens[i]) +
-                             " samples) is outside the joined timeline of " + std::to_string(joined_len) + " samples");
-        }
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return place[a] < place[b]; });
-        for (int r = 0; r < n; ++r) {
-            const int i = order[r];
-            if (r) SBV2_REQUIRE(place[order[r - 1]] + lens[order[r - 1]] <= place[i], "placements of utterances overlap on the joined timeline");
-            if (lens[i]) pieces.push_back(FmtPiece{pcm + offs[i], place[i], lens[i]});
-        }
-        total = pcm_format_out_len(spec, joined_len);
-        sig.push_back(FmtSignal{0, total, 0, 0, (int32_t)pieces.size()});
-        outs.push_back(total);
-    }
+    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
     SBV2_REQUIRE(capacity_bytes >= total * spec.bytes(),
                  "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(total * spec.bytes()) + " bytes");
     HIP_CHECK(hipSetDevice(vm.device()));
     if (spec.identity() && !place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
-        HIP_CHECK(hipMemcpyAsync(dst, pcm, sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, vm.stream()));
+        HIP_CHECK(hipMemcpyAsync(dst, vm.pcm_device(), sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, vm.stream()));
     } else if (total > 0) {
-        if ((int)p->fmts.size() < p->contexts()) p->fmts.resize(p->contexts());
-        if (!p->fmts[ctx]) p->fmts[ctx].reset(new PcmFormatter(vm.device()));
-        PcmFormatter& f = *p->fmts[ctx];
+        PcmFormatter& f = formatter(p, ctx, vm.device());
         void* dev = f.out_buffer((size_t)total * spec.bytes(), vm.stream());
         f.run(spec, pieces, sig, total, dev, 0, vm.stream());
         HIP_CHECK(hipMemcpyAsync(dst, dev, (size_t)total * spec.bytes(), hipMemcpyDeviceToHost, vm.stream()));
     }
     HIP_CHECK(hipStreamSynchronize(vm.stream()));
     for (size_t i = 0; i < outs.size(); ++i) out_lens[i] = outs[i];
+    API_END
+}
+
+// ---- FLAC (flac_encode.hip) ----
+static PcmFmtSpec flac_spec(const sbv2_pcm_format* fmt) {
+    const PcmFmtSpec spec = pcm_format_spec(fmt);
+    SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
+    return spec;
+}
+
+int64_t sbv2_flac_bound(const sbv2_pcm_format* fmt, int64_t n_native) {
+    try {
+        const PcmFmtSpec spec = flac_spec(fmt);
+        SBV2_REQUIRE(n_native >= 0, "negative sample count");
+        return flac_bound(pcm_format_out_len(spec, n_native));
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// The s16 signals of sbv2_pipeline_fetch_pcm_format stay in HBM; the encoder's three launches follow on the run's stream, the host reads back
+// the stream sizes, then exactly the encoded bytes cross PCIe.
+int sbv2_pipeline_fetch_flac(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len, uint8_t* dst,
+                             int64_t capacity_bytes, int64_t* out_bytes) {
+    API_BEGIN
+    SBV2_REQUIRE(p && dst && out_bytes, "bad arguments");
+    const PcmFmtSpec spec = flac_spec(fmt);
+    const int ctx = p->ctx_of(ticket);
+    VitsModel& vm = p->vm(ctx);
+    std::vector<FmtPiece> pieces;
+    std::vector<FmtSignal> sig;
+    std::vector<int64_t> outs;
+    int64_t total = 0;
+    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
+    HIP_CHECK(hipSetDevice(vm.device()));
+    PcmFormatter& f = formatter(p, ctx, vm.device());
+    void* dev = f.out_buffer((size_t)std::max<int64_t>(total, 1) * spec.bytes(), vm.stream());
+    f.run(spec, pieces, sig, total, dev, 0, vm.stream());
+    if ((int)p->flacs.size() < p->contexts()) p->flacs.resize(p->contexts());
+    if (!p->flacs[ctx]) p->flacs[ctx].reset(new FlacEncoder(vm.device()));
+    FlacEncoder& enc = *p->flacs[ctx];
+    std::vector<int64_t> offs(outs.size()), bytes;
+    for (size_t i = 1; i < outs.size(); ++i) offs[i] = offs[i - 1] + outs[i - 1];
+    const int64_t nbytes = enc.encode(static_cast<const int16_t*>(dev), offs, outs, spec.rate, vm.stream(), &bytes);
+    SBV2_REQUIRE(capacity_bytes >= nbytes, "FLAC buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(nbytes) + " bytes");
+    HIP_CHECK(hipMemcpyAsync(dst, enc.output(), (size_t)nbytes, hipMemcpyDeviceToHost, vm.stream()));
+    HIP_CHECK(hipStreamSynchronize(vm.stream()));
+    for (size_t i = 0; i < bytes.size(); ++i) out_bytes[i] = bytes[i];
+    API_END
+}
+
+int sbv2_debug_flac_encode(int device, const int16_t* x, const int64_t* lens, int nsig, int32_t sample_rate, uint8_t* dst, int64_t capacity,
+                           int64_t* out_bytes) {
+    API_BEGIN
+    SBV2_REQUIRE(nsig >= 1 && lens && dst && out_bytes, "bad arguments");
+    flac_rate_code(sample_rate);
+    std::vector<int64_t> ls(lens, lens + nsig), offs(nsig);
+    int64_t total = 0;
+    for (int i = 0; i < nsig; ++i) {
+        SBV2_REQUIRE(ls[i] >= 0, "negative signal length");
+        offs[i] = total;
+        total += ls[i];
+    }
+    SBV2_REQUIRE(total == 0 || x, "bad arguments");
+    HIP_CHECK(hipSetDevice(device));
+    struct Res {
+        hipStream_t s = nullptr;
+        void* x = nullptr;
+        ~Res() {
+            if (s) (void)hipStreamSynchronize(s);
+            if (x) (void)hipFree(x);
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } r;
+    HIP_CHECK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
+    HIP_CHECK(hipMalloc(&r.x, sizeof(int16_t) * (size_t)std::max<int64_t>(total, 1)));
+    if (total) HIP_CHECK(hipMemcpyAsync(r.x, x, sizeof(int16_t) * (size_t)total, hipMemcpyHostToDevice, r.s));
+    FlacEncoder enc(device);
+    std::vector<int64_t> bytes;
+    const int64_t nbytes = enc.encode(static_cast<const int16_t*>(r.x), offs, ls, sample_rate, r.s, &bytes);
+    SBV2_REQUIRE(capacity >= nbytes, "FLAC buffer too small: " + std::to_string(capacity) + " < " + std::to_string(nbytes) + " bytes");
+    HIP_CHECK(hipMemcpyAsync(dst, enc.output(), (size_t)nbytes, hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    for (int i = 0; i < nsig; ++i) out_bytes[i] = bytes[i];
     API_END
 }
 

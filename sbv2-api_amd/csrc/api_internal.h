@@ -7,6 +7,7 @@
 #include <new>
 
 #include "../../include/sbv2_hip.h"
+#include "flac_encode.h"
 #include "models.h"
 #include "pcm_format.h"
 
@@ -28,6 +29,7 @@ struct sbv2_pipeline {
     std::vector<std::unique_ptr<BertModel>> bclones;
     std::vector<std::unique_ptr<VitsModel>> vclones;
     std::vector<std::unique_ptr<PcmFormatter>> fmts;   // per context: the formatting launches of sbv2_pipeline_fetch_pcm_format
+    std::vector<std::unique_ptr<FlacEncoder>> flacs;   // per context: the encoding launches of sbv2_pipeline_fetch_flac
     int64_t calls = 0;   // tickets are call numbers 1, 2, ...: ticket t ran on context (t - 1) % depth and is valid until that context is reused
     BertModel& bm(int i) { return i == 0 ? *bert->m : *bclones[i - 1]; }
     VitsModel& vm(int i) { return i == 0 ? *vits->m : *vclones[i - 1]; }

@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import Sbv2Batch, Sbv2Error, check, f32p, i64p
 
 __all__ = ["Session", "load_model", "predict", "synthesize", "predict_batch", "synthesize_batch", "Pipeline", "Node", "Comm", "deal", "Sbv2Error",
-           "PcmFormat", "pcm_format_length", "pcm_format_taps"]
+           "PcmFormat", "pcm_format_length", "pcm_format_taps", "flac_bound", "debug_flac_encode"]
 
 
 def _i64(a):
@@ -153,6 +153,35 @@ def pcm_format_taps(sample_rate: int):
     return h, L.value, M.value
 
 
+def flac_bound(fmt: PcmFormat, n_native: int) -> int:
+    """Upper bound on the bytes of the FLAC stream of an n_native-sample 44.1 kHz signal in `fmt` (s16 only; host only)."""
+    n = _lib.lib().sbv2_flac_bound(C.byref(fmt.c), int(n_native))
+    if n < 0:
+        raise Sbv2Error(_lib.lib().sbv2_last_error().decode(errors="replace"))
+    return n
+
+
+def _split_bytes(buf, sizes):
+    out, o = [], 0
+    for n in sizes:
+        out.append(bytes(buf[o:o + int(n)]))
+        o += int(n)
+    return out
+
+
+def debug_flac_encode(signals, sample_rate: int, device: int = 0):
+    """Test hook: the device FLAC encoder on host int16 signals -> one FLAC stream (bytes) per signal."""
+    sigs = [np.ascontiguousarray(np.asarray(x, np.int16)).reshape(-1) for x in signals]
+    x = np.concatenate(sigs) if sigs else np.zeros(0, np.int16)
+    lens = np.array([s.size for s in sigs], np.int64)
+    cap = sum(42 + 16 * (-(-int(n) // 4096)) + 2 * int(n) for n in lens)
+    dst = np.empty(max(cap, 1), np.uint8)
+    got = np.zeros(len(sigs), np.int64)
+    check(_lib.lib().sbv2_debug_flac_encode(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(sigs),
+                                            int(sample_rate), dst.ctypes.data_as(C.c_void_p), dst.nbytes, got.ctypes.data_as(i64p)))
+    return _split_bytes(dst, got)
+
+
 class _Batch:
     """Keeps the numpy buffers of one sbv2_batch alive."""
 
@@ -291,6 +320,26 @@ class Pipeline:
         check(l.sbv2_pipeline_fetch_pcm_format(self.h, b.ticket, C.byref(fmt.c), pp, jl, out.ctypes.data_as(C.c_void_p), out.nbytes,
                                                got.ctypes.data_as(i64p)))
         return np.split(out[:int(got.sum())], np.cumsum(got)[:-1])
+
+    def fetch_flac(self, b, fmt: PcmFormat, place=None, joined_len=None):
+        """The signals of fetch_format(b, fmt, place, joined_len), each as one FLAC stream (bytes) encoded on the device; fmt must be s16."""
+        if fmt.encoding != "s16":
+            raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
+        lens = [int(v) for v in b.lens]
+        if place is None:
+            cap, pp, jl, nout = sum(flac_bound(fmt, n) for n in lens), None, 0, len(lens)
+        else:
+            if joined_len is None:
+                raise Sbv2Error("a placement needs joined_len")
+            pl, pp = _i64(place)
+            if pl.shape != (len(lens),):
+                raise Sbv2Error(f"place must hold one offset per utterance ({len(lens)})")
+            cap, jl, nout = flac_bound(fmt, joined_len), int(joined_len), 1
+        dst = np.empty(max(cap, 1), np.uint8)
+        got = np.zeros(nout, np.int64)
+        check(_lib.lib().sbv2_pipeline_fetch_flac(self.h, b.ticket, C.byref(fmt.c), pp, jl, dst.ctypes.data_as(C.c_void_p), dst.nbytes,
+                                                  got.ctypes.data_as(i64p)))
+        return _split_bytes(dst, got)
 
     def close(self):
         if self.h:

@@ -31,7 +31,8 @@ NOISE_SCALE_W = 0.8         # tts.rs:314 / :344
 
 class SynthesizeOptions:
     """tts.rs:359-375 (same defaults).  sample_rate / encoding / normalize are new (the reference writes 44.1 kHz f32 only): when any of
-    them differs from its default the request's WAV signal is resampled / normalised / quantised on the device (model.PcmFormat)."""
+    them differs from its default the request's WAV signal is resampled / normalised / quantised on the device (model.PcmFormat).
+    encoding "flac": the same signal as s16, returned as a FLAC stream encoded on the device instead of a WAV."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
                  normalize=False):
@@ -114,7 +115,8 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     live = [(i, s) for i, s in enumerate(sentences) if s]
     if not live:
         raise model.Sbv2Error("nothing to synthesize (the reference's concatenate fails on an empty list)")
-    fmt = model.PcmFormat(options.sample_rate, options.encoding, options.normalize)
+    flac = options.encoding == "flac"   # a FLAC stream of the s16 signal, encoded on the device
+    fmt = model.PcmFormat(options.sample_rate, "s16" if flac else options.encoding, options.normalize)
     model.pcm_format_length(fmt, 0)   # a bad rate is refused before any GPU work
     utts = [dict(s, style=style, sid=speaker_id) for _, s in live]
     b = pipe.prepare(utts, sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
@@ -122,6 +124,8 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     pipe.run(b)
     if not fmt.is_default:   # ONE joined fetch: the WAV signal below, resampled / normalised / quantised as a whole on the device
         place, joined = joined_placement(b.lens, [i for i, _ in live], len(sentences), options.split_sentences)
+        if flac:
+            return pipe.fetch_flac(b, fmt, place, joined)[0]
         out = pipe.fetch_format(b, fmt, place, joined)[0]
         return pcm16_wav(out, fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out, fmt.sample_rate)
     pcm = pipe.fetch(b)

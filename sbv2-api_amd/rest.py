@@ -4,7 +4,8 @@ and error mapping, so that a client of the reference's server cannot tell the di
   GET  /            "Hello, World!"                                              main.rs:193
   GET  /models      JSON list of idents                                          main.rs:24-33
   POST /synthesize  {text, ident, sdp_ratio = 0.0, length_scale = 1.0, style_id = 0, speaker_id = 0} -> audio/wav     main.rs:51-100
-                    (+ sample_rate = 44100, encoding = "f32" | "s16", normalize = false: new output formats, defaults = the reference's)
+                    (+ sample_rate = 44100, encoding = "f32" | "s16" | "flac", normalize = false: new output formats, defaults = the
+                    reference's; "flac" -> audio/flac)
   any error         500 text/plain "Something went wrong: <message>"            sbv2_api/src/error.rs:10-18
   one request at a time (Arc<Mutex<TTSModelHolder>>, main.rs:86,104)             -> a lock around the holder
 
@@ -28,7 +29,7 @@ def make_app(holder):
         style_id: int = 0
         speaker_id: int = 0
         sample_rate: int = 44100            # new: output format of the WAV (the reference's is 44.1 kHz f32)
-        encoding: str = "f32"               # "f32" | "s16"
+        encoding: str = "f32"               # "f32" | "s16" | "flac"
         normalize: bool = False             # peak of the signal -> full scale
 
     app = FastAPI(docs_url="/docs")          # main.rs:196 serves the OpenAPI document at /docs as well
@@ -57,6 +58,6 @@ def make_app(holder):
                                                                             normalize=req.normalize))
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
-        return Response(content=wav, media_type="audio/wav")
+        return Response(content=wav, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
 
     return app
