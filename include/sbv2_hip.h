@@ -275,7 +275,8 @@ int sbv2_debug_time_conv1d(int device, int64_t cin, int64_t cout, int64_t k, int
 int sbv2_debug_set_skinny_max(int workgroups);
 /* 1 (default): the ResBlocks of the wide decoder stages run on conv_clx.hip when the launch has >= 128 tiles; 2: always; 0: on conv_cl.hip.
    The two kernels sum in different orders (round 5: conv_clx on 16 x 16 x 32 MFMAs) and agree to f32 rounding; with 0 (and sbv2_debug_set_ksplit(0)) every
-   launch size takes the same kernels and a batch row equals its single-utterance call bit for bit.  Returns the previous value. */
+   launch size takes the same kernels and a batch row equals its single-utterance call bit for bit.  Returns the previous value, or -1 for any other value
+   (the setting stays). */
 int sbv2_debug_set_clx(int on);
 /* 1 (default): the small-grid dispatch of a single utterance's launches: gemm_bfs products with a long K loop split it over workgroups (K >= 2048) or over the
    four waves of a 32 x 32 tile (the 1024 x 1024 products) and add the partial sums in group order, and LayerNorm runs few columns per workgroup; other
@@ -310,21 +311,22 @@ int sbv2_debug_clx_timeline(int device, int64_t C, int64_t k, int64_t dilation, 
    number of clamped values since the last call, on `device`.  A non-zero count on a real checkpoint means: run with SBV2_BERT_GEMM=bf16x6. */
 int sbv2_debug_f16x3_saturation(int device, int enable, uint64_t* count);
 /* 1 (default): the fused ResBlock steps of the <= 64-channel decoder stages run on respair_x16.hip where it exists (C = 32 / 64, k = 7 / 11: 16x16x32 MFMAs,
-   step pairs in the K dimension; f32 rounding apart) and on respair_clx.hip (split-bf16, k in {3, 7, 11}) otherwise; 2 (SBV2_RESPAIR_X16=0): respair_clx.hip
-   at every shape; 0: respair_cl.hip (the bits of mode 2).  Returns the previous value. */
+   step pairs in the K dimension; f32 rounding apart) and on respair_clx.hip (split-bf16, k in {3, 7, 11}) otherwise; 0: respair_cl.hip (respair_clx.hip's
+   bits at C = 32 / 64).  Returns the previous value, or -1 for any other value (the setting stays). */
 int sbv2_debug_set_respair_clx(int on);
 /* One fused ResBlock1 step y' = beta (conv2(lrelu(conv1(lrelu(x), dilation) + b1)) + b2 + x) [+ y when accumulate], masked by mask[n / mask_div] (may be
-   null), channels-last x / y [N][C], w [C][C][k], split-bf16, through respair_cl.hip (variant 0), the default dispatch (variant 1: respair_x16.hip /
-   respair_clx.hip) or respair_clx.hip at every shape (variant 2).  Test hook. */
+   null; mask_div a power of two), channels-last x / y [N][C], w [C][C][k], split-bf16, through respair_cl.hip (variant 0), the default dispatch's kernel
+   (variant 1: respair_x16.hip where it exists, else respair_clx.hip) or respair_clx.hip (variant 2).  Test hook. */
 int sbv2_debug_respair(int device, const float* x, const float* w1, const float* w2, const float* b1, const float* b2, int64_t C, int64_t N, int64_t k,
                        int64_t dilation, const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, float* y);
 /* 1 (default; SBV2_RESBRANCH): the k = 3 branches of the 128- / 64- / 32- / 16-channel decoder stages and the k = 7 / 11 branches of the 16-channel stage
-   run their three steps in ONE launch (resbranch_clx.hip: y_1, y_2 stay on the chip, 2 plane passes through HBM per branch instead of 6); 2: the k = 3
-   branches only; 0: three fused-step launches (same bits; at 128 channels six conv_clx launches: f32 rounding apart).  Returns the previous value. */
+   run their three steps in ONE launch (resbranch_clx.hip: y_1, y_2 stay on the chip, 2 plane passes through HBM per branch instead of 6); 0: three fused-step
+   launches (same bits; at 128 channels six conv_clx launches: f32 rounding apart).  Returns the previous value, or -1 for any other value (the setting
+   stays). */
 int sbv2_debug_set_resbranch(int on);
 /* 1 (default; SBV2_UPX): the ConvTranspose1d of the wide decoder stages (large launches) runs as ONE phased conv_clx.hip launch on pre-split operands
-   (rows = (phase, cout), every phase on its own input taps); read when the weights are packed: 2 = rows in plain (phase, channel) order (same bits), 3 = the
-   union of all phases' taps with a zero tap per phase (f32 rounding apart); 0: conv_cl.hip's phase groups (f32 rounding apart).  Returns the previous value. */
+   (rows = (phase, cout), every phase on its own input taps); 0: conv_cl.hip's phase groups (f32 rounding apart).  Returns the previous value, or -1 for any
+   other value (the setting stays). */
 int sbv2_debug_set_upx(int on);
 /* ConvTranspose1d(lrelu(x, pre_slope)) [cin][L] -> y [cout][L * stride] (weight [cin][cout][k], padding (k - stride) / 2) through the phased conv_clx launch;
    mask (may be null): input position n and its `stride` outputs are kept iff mask[n / mask_div]; ys_sum (may be null): hi + lo of the bf16 parts of

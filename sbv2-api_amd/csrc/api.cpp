@@ -597,7 +597,7 @@ int sbv2_debug_conv_transpose1d_clx(int device, const float* x, const float* w, 
     SBV2_REQUIRE(x && w && bias && y && mask_div >= 1 && (mask_div & (mask_div - 1)) == 0, "bad arguments");
     Blob b = one_conv_blob(w, bias, {cin, cout, k}, cout);
     WeightStore ws(b);
-    ClUpX u = build_upx(ws, w, bias, (int)cin, (int)cout, (int)k, (int)stride, /*parts_out=*/ys_sum != nullptr);   // (sbv2_debug_set_upx(2): plain row order)
+    ClUpX u = build_upx(ws, w, bias, (int)cin, (int)cout, (int)k, (int)stride, /*parts_out=*/ys_sum != nullptr);
     SBV2_REQUIRE(u.wx, "shape not supported by the phased conv_clx transposed convolution");
     const int64_t Lo = L * stride;
     std::vector<float> xt((size_t)L * cin), yt((size_t)Lo * cout);
@@ -1060,7 +1060,8 @@ int sbv2_debug_respair(int device, const float* x, const float* w1, const float*
                        int64_t dilation, const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, float* y) {
     API_BEGIN
     HIP_CHECK(hipSetDevice(device));
-    SBV2_REQUIRE(x && w1 && w2 && b1 && b2 && y && (C == 16 || C == 32 || C == 64) && N >= 1 && k >= 1 && k <= kMaxTaps && (k & 1) && mask_div >= 1, "bad arguments");
+    SBV2_REQUIRE(x && w1 && w2 && b1 && b2 && y && (C == 16 || C == 32 || C == 64) && N >= 1 && k >= 1 && k <= kMaxTaps && (k & 1) && mask_div >= 1 &&
+                     (mask_div & (mask_div - 1)) == 0, "bad arguments");
     Blob b = one_conv_blob(w1, b1, {C, C, k}, C);
     WeightStore ws(b);
     ClConv c1 = pack_cl(ws, w1, (int)C, (int)C, (int)k, 2, b1);
@@ -1096,16 +1097,15 @@ int sbv2_debug_respair(int device, const float* x, const float* w1, const float*
     rp.accumulate = accumulate;
     rp.mask = dm;
     rp.mask_div = (int)mask_div;
-    const int prev = set_respair_clx(variant == 0 ? 0 : (variant == 2 ? 2 : 1));   // 0 = respair_cl, 1 = the default dispatch (respair_clx / respair_x16), 2 = respair_clx at every shape
-    try {
-        launch_respair_cl(rp, nullptr);
+    rp.mask_shift = 0;
+    while (dm && (1 << rp.mask_shift) < mask_div) ++rp.mask_shift;
+    try {   // 0 = respair_cl, 1 = the default dispatch's kernel, 2 = respair_clx
+        launch_respair(rp, variant == 0 ? BranchKernel::respair_cl : (variant == 2 ? BranchKernel::respair_clx : respair_default(rp)), nullptr);
         HIP_CHECK(hipDeviceSynchronize());
     } catch (...) {
-        set_respair_clx(prev);
         if (dm) (void)hipFree(dm);
         throw;
     }
-    set_respair_clx(prev);
     HIP_CHECK(hipMemcpy(y, dy.p, sizeof(float) * N * C, hipMemcpyDeviceToHost));
     if (dm) (void)hipFree(dm);
     API_END
@@ -1218,7 +1218,8 @@ int sbv2_debug_resbranch(int device, const float* x, const float* w, const float
                 rp.accumulate = last ? accumulate : 0;
                 rp.mask = dm;
                 rp.mask_div = (int)mask_div;
-                launch_respair_cl(rp, nullptr);
+                rp.mask_shift = shift;
+                launch_respair(rp, respair_default(rp), nullptr);
                 cur = rp.Y;
             }
         }
@@ -1322,12 +1323,12 @@ int sbv2_debug_respair_clock(int device, int64_t C, int64_t k, int64_t dilation,
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_st), sizeof(unsigned long long) * 16 * nwg));
     HIP_CHECK(hipMemset(d_st, 0, sizeof(unsigned long long) * 16 * nwg));
     rp.stamps = d_st;
-    const int prev_rpx = set_respair_clx(variant == 3 ? 1 : 0);
     auto launch = [&]() {
         if (variant == 0) launch_respair_cl_diag(rp, nullptr);
         else if (variant == 2) launch_respair_clx_diag(rp, nullptr);
         else if (variant == 4) launch_respair_x16_diag(rp, nullptr);   // respair_x16.hip, stamped
-        else launch_respair_cl(rp, nullptr);   // the product kernels (no stamps: clock and phases read 0): 1 = respair_cl, 3 = respair_clx
+        else if (variant == 3) launch_respair_clx(rp, nullptr);   // the product kernels (no stamps: clock and phases read 0): 1 = respair_cl, 3 = respair_clx
+        else launch_respair_cl(rp, nullptr);
     };
     hipEvent_t e0, e1;
     HIP_CHECK(hipEventCreate(&e0));
@@ -1353,7 +1354,6 @@ int sbv2_debug_respair_clock(int device, int64_t C, int64_t k, int64_t dilation,
     (void)hipFree(d_st);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    set_respair_clx(prev_rpx);
     for (int i = 0; i < nout; ++i) out[i] = 0.0;
     out[1] = t50 / 50.0;
     std::vector<double> mhz;

@@ -492,14 +492,15 @@ struct ConvClxParams {
 };
 int64_t clx_grid_workgroups(const ConvClxParams& p);   // workgroups launch_conv_clx starts for p
 bool conv_clx_usable(const ConvClxParams& p);
-bool clx_enabled();   // decoder_cl.cpp: the wide decoder stages take conv_clx (default) or conv_cl
-int set_clx(int on);  // returns the previous setting
-int set_upx(int on);  // the wide stages' transposed convolutions as phased conv_clx launches (default 1; read when the weights are packed: 2 = their rows in plain (phase, channel) order, 3 = odd tap counts, a zero tap behind the last one); returns the previous setting
-int upx_mode();
+// decoder_cl.cpp's dispatch knobs: each setter returns the previous setting, or -1 for a value it does not take (the setting stays)
+int set_clx(int on);        // 1 (default): conv_clx for large launches of the wide decoder stages and the flow's FFN; 2: at every size; 0: conv_cl
+int set_upx(int on);        // 1 (default): the wide stages' transposed convolutions as phased conv_clx launches; 0: conv_cl's phase groups
+int set_resbranch(int on);  // 1 (default): the fused ResBlock branch (resbranch_clx.hip) where it fits; 0: the branch's steps
+int set_respair_clx(int on);   // 1 (default): the fused step on respair_default's kernel; 0: respair_cl.hip
 // gemm_bfs: small grids split their K loop over groups of waves (another summation order than the batch's tiles; 0 = the unsplit, batch-order dispatch)
 bool ksplit_enabled();
 int set_ksplit(int on);  // returns the previous setting
-bool clx_wanted(int64_t tiles, int64_t min_tiles);   // mode 1: launches of >= min_tiles tiles; mode 2: always; mode 0: never
+bool clx_wanted(int64_t tiles, int64_t min_tiles);   // set_clx 1: launches of >= min_tiles tiles; 2: always; 0: never
 void launch_conv_clx(const ConvClxParams& p, hipStream_t stream);
 
 // One fused ResBlock1 step y' = beta * (conv2(lrelu(conv1(lrelu(y), dil) + b1)) + b2 + y) on a channels-last plane (respair_cl.hip)
@@ -519,7 +520,7 @@ struct ResPairParams {
     int accumulate = 0;
     const unsigned char* mask = nullptr;
     int mask_div = 1;
-    int mask_shift = -1;   // set by launch_respair_cl
+    int mask_shift = -1;   // mask_div = 1 << mask_shift: the caller's for respair_clx / respair_x16, set by launch_respair_cl
     int alias_x2 = 1;      // set by launch_respair_cl: the intermediate window re-uses the conv1 window's LDS
     int abl = 0;           // diagnostics (wrong results): 1 = every global read hits the same few cache-hot rows, 2 = no global stores; diag kernel only: 4 = no MFMAs, 8 = no conv1 window conversion, 16 = no intermediate epilogue
     unsigned long long* stamps = nullptr;   // diag kernel only: 16 per workgroup
@@ -533,11 +534,15 @@ void launch_respair_cl_diag(const ResPairParams& p, hipStream_t stream);
 bool respair_clx_usable(const ResPairParams& p);          // p.mask_shift set
 void launch_respair_clx(const ResPairParams& p, hipStream_t stream);
 void launch_respair_clx_diag(const ResPairParams& p, hipStream_t stream);
-int set_respair_clx(int on);   // returns the previous setting (default 1; 2: respair_clx.hip at every shape, none on respair_x16.hip)
 // respair_x16.hip (round 6): the step at C = 32 / 64, k = 7 / 11 on v_mfma_f32_16x16x32_bf16 (conv_clx.hip's operand scheme); f32 rounding apart from respair_clx
 bool respair_x16_usable(const ResPairParams& p);          // p.mask_shift set
 void launch_respair_x16(const ResPairParams& p, hipStream_t stream);
 void launch_respair_x16_diag(const ResPairParams& p, hipStream_t stream);
+// The kernels that run one ResBlock branch of the decoder (decoder_cl.cpp's plan): the fused branch, two conv_clx launches per step, one fused-step launch
+// per step, two conv_cl launches per step
+enum class BranchKernel { resbranch, clx_steps, respair_x16, respair_clx, respair_cl, conv_cl_steps };
+BranchKernel respair_default(const ResPairParams& p);   // the fused-step kernel of the default dispatch (p.mask_shift set)
+void launch_respair(const ResPairParams& p, BranchKernel kernel, hipStream_t stream);   // p on that fused-step kernel
 
 // resbranch_clx.hip (round 6): the THREE steps of a ResBlock1 branch in one launch (k = 3, C in {16, 32, 64}): y_1 and y_2 never leave the chip, 2 plane passes
 // through HBM per branch instead of 6; bit-identical to three respair_clx launches
@@ -559,9 +564,6 @@ struct ResBranchParams {
     unsigned long long* stamps = nullptr;      // diagnostics: 16 per workgroup (sbv2_debug_resbranch_clock)
 };
 bool resbranch_usable(const ResBranchParams& p);
-bool resbranch_enabled();
-bool resbranch_wanted(int C, int k);   // mode 1 (default): every shape resbranch_clx.hip instantiates; 2: its k = 3 branches only
-int set_resbranch(int on);      // returns the previous setting (default 1; SBV2_RESBRANCH=0)
 void launch_resbranch(const ResBranchParams& p, hipStream_t stream);
 
 }  // namespace sbv2

@@ -705,7 +705,7 @@ bool conv_clx_usable(const ConvClxParams& p) {
     if (p.R && (p.ldr & 3)) return false;
     if (p.phase_rows) {   // phased output (a polyphase transposed convolution)
         if ((p.phase_rows & 63) || p.M % p.phase_rows || p.M / p.phase_rows > kMaxPhases || p.out_stride < 1 || p.R || p.accumulate || p.Ykm || p.N < kClxNT ||
-            !(p.ntaps >= 2 && p.ntaps <= 5)) return false;
+            (p.ntaps & 1)) return false;
         if (p.Y && p.ldy < p.phase_rows) return false;
         if (p.Ys.p && (p.Ys.C != p.phase_rows || p.Ys.N != (int64_t)p.N * p.out_stride)) return false;
         for (int q = 0; q < p.M / p.phase_rows; ++q)
@@ -728,13 +728,13 @@ static void launch_clx_e(ClxKernelParams kp, hipStream_t stream);
 
 template <int NTAPS, int WR, int XB, int XR>
 static void launch_clx(const ClxKernelParams& kp, hipStream_t stream) {
-    if constexpr (NTAPS <= 5 && XR == 288) {
+    if constexpr ((NTAPS == 2 || NTAPS == 4) && XR == 288) {
         if (kp.p.phase_rows) {   // (conv_clx_usable: whole tiles, nothing accumulates)
             if ((int64_t)kp.p.N * kp.p.M * 4 >= ((int64_t)128 << 20)) return launch_clx_e<NTAPS, WR, XB, XR, 3, true>(kp, stream);
             return launch_clx_e<NTAPS, WR, XB, XR, 0, true>(kp, stream);
         }
     }
-    SBV2_REQUIRE(!kp.p.phase_rows, "conv_clx: phased output is instantiated for 2 .. 5 taps on 288-row windows");
+    SBV2_REQUIRE(!kp.p.phase_rows, "conv_clx: phased output is instantiated for 2 and 4 taps on 288-row windows");
     if constexpr ((NTAPS & 1) == 0) {
         SBV2_REQUIRE(false, "conv_clx: even kernel sizes are instantiated for phased output only");
     } else {

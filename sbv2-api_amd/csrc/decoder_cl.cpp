@@ -157,9 +157,7 @@ ClUpX build_upx(WeightStore& ws, const float* wt, const float* ub, int cin, int 
                 tmax = std::max(tmax, tt);
             }
         }
-    // every phase multiplies its OWN input taps (k 16, s 8: two, one position later for the first four phases than for the last four; k 8, s 2: four);
-    // SBV2_UPX=3 (A/B runs): the first build's union of all phases' taps (three / five), zero weights where a phase has none
-    const bool uni = upx_mode() == 3;
+    // every phase multiplies its OWN input taps (k 16, s 8: two, one position later for the first four phases than for the last four; k 8, s 2: four)
     int t0[kMaxPhases], U = 0;
     for (int r = 0; r < s; ++r) {
         int lo = 1 << 30, hi = -(1 << 30);
@@ -170,14 +168,13 @@ ClUpX build_upx(WeightStore& ws, const float* wt, const float* ub, int cin, int 
                 hi = std::max(hi, tt);
             }
         }
-        t0[r] = uni ? tmin : lo;
-        U = std::max(U, uni ? tmax - tmin + 1 : hi - lo + 1);
+        t0[r] = lo;
+        U = std::max(U, hi - lo + 1);
     }
-    if (uni && (U & 1) == 0) ++U;
-    if (U < 2 || U > 5) return u;
+    if (U != 2 && U != 4) return u;   // (the tap counts conv_clx instantiates for phased output)
     const int M = s * cout;
     // a launch that also writes the next stage's operand parts packs its rows as (phase pair, 16 channels, phase in pair, channel): common.h, phase_group
-    int group = parts_out && (s & 1) == 0 && upx_mode() != 2 ? 2 : 1;
+    int group = parts_out && (s & 1) == 0 ? 2 : 1;
     if (group == 2)
         for (int r = 0; r < s; r += 2)
             if (t0[r] != t0[r + 1]) group = 1;   // (the two phases of a pair share the window rows they read: s = 2 keeps the plain order)
@@ -303,23 +300,29 @@ void VitsModel::load_decoder_cl(const Blob& blob) {
     }
 }
 
-// conv_clx.hip for the wide stages' ResBlocks (SBV2_CLX=0 / sbv2_debug_set_clx(0): the conv_cl path, bit-identical, for A/B runs and the test)
-static std::atomic<int> g_clx{getenv("SBV2_CLX") ? atoi(getenv("SBV2_CLX")) : 1};
-bool clx_enabled() { return g_clx.load(std::memory_order_relaxed) != 0; }
-static int64_t clx_min_tiles() {
-    // 128 tiles: a single 128-phoneme utterance's 128-channel stage (448 tiles) takes conv_clx, its 256-channel stage (112) stays on conv_cl: 11.93 -> 11.79 ms
-    // per call (profiles/r05k_b1_clx_min_tiles.txt); rounds 3-4 required 1024 tiles.
-    return g_clx.load(std::memory_order_relaxed) == 2 ? 0 : 128;   // set_clx(2): every size (the bit-equality test runs small batches)
+// The decoder's dispatch knobs (common.h: set_clx, set_upx, set_resbranch, set_respair_clx); SBV2_CLX, SBV2_UPX and SBV2_RESBRANCH give their start-up
+// values.  A decoder run reads each once (plan_decoder_cl); the flow's FFN reads g_clx through clx_wanted.  clx 1's 128 tiles: a single 128-phoneme
+// utterance's 128-channel stage (448 tiles) takes conv_clx, its 256-channel stage (112) stays on conv_cl: 11.93 -> 11.79 ms per call (profiles/r05k_b1_clx_min_tiles.txt).
+static int env_knob(const char* name, int maxv) {   // -1: a value outside 0 .. maxv, refused where the knob is read
+    const char* e = getenv(name);
+    if (!e || !*e) return 1;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    return !*end && v >= 0 && v <= maxv ? (int)v : -1;
 }
-bool clx_wanted(int64_t tiles, int64_t min_tiles) {
-    const int m = g_clx.load(std::memory_order_relaxed);
-    return m == 2 || (m == 1 && tiles >= min_tiles);
+static std::atomic<int> g_clx{env_knob("SBV2_CLX", 2)}, g_upx{env_knob("SBV2_UPX", 1)}, g_rb{env_knob("SBV2_RESBRANCH", 1)}, g_rpx{1};
+static int read_knob(const std::atomic<int>& g, const char* refusal) {
+    const int v = g.load(std::memory_order_relaxed);
+    SBV2_REQUIRE(v >= 0, refusal);
+    return v;
 }
-int set_clx(int on) { return g_clx.exchange(on); }
-// the transposed convolutions of the wide stages as phased conv_clx launches (round 6; SBV2_UPX=0 / sbv2_debug_set_upx(0): conv_cl's phase groups, for A/B runs)
-static std::atomic<int> g_upx{getenv("SBV2_UPX") ? atoi(getenv("SBV2_UPX")) : 1};
-int set_upx(int on) { return g_upx.exchange(on); }
-int upx_mode() { return g_upx.load(std::memory_order_relaxed); }
+static int set_knob(std::atomic<int>& g, int v, int maxv) { return v >= 0 && v <= maxv ? g.exchange(v) : -1; }
+int set_clx(int on) { return set_knob(g_clx, on, 2); }
+int set_upx(int on) { return set_knob(g_upx, on, 1); }
+int set_resbranch(int on) { return set_knob(g_rb, on, 1); }
+int set_respair_clx(int on) { return set_knob(g_rpx, on, 1); }
+static bool clx_size_ok(int mode, int64_t tiles, int64_t min_tiles) { return mode == 2 || (mode == 1 && tiles >= min_tiles); }
+bool clx_wanted(int64_t tiles, int64_t min_tiles) { return clx_size_ok(read_knob(g_clx, "SBV2_CLX must be 0, 1 or 2"), tiles, min_tiles); }
 
 void VitsModel::conv_cl(const ClConv& c, const float* X, int ldx, int NB, float* Y, int ldy, int N, int dil, int pad_l,
                         const unsigned char* mask, int mask_div, float pre_slope, const float* R, int ldr, float beta, int accumulate) {
@@ -350,9 +353,132 @@ void VitsModel::conv_cl(const ClConv& c, const float* X, int ldx, int NB, float*
     launch_conv_cl(p, stream_);
 }
 
+// The operands of a fused ResBlock branch (resbranch_clx.hip); X, Y, beta and accumulate are the caller's
+static ResBranchParams branch_params(const std::vector<ClConv>& c1, const std::vector<ClConv>& c2, const std::vector<int>& dil, int k, int C, int64_t N,
+                                     const unsigned char* mask, int mask_shift) {
+    ResBranchParams bp;
+    for (int q = 0; q < kResBranchSteps; ++q) {
+        bp.W[2 * q] = C == 16 ? c1[q].wp : c1[q].w;
+        bp.W[2 * q + 1] = C == 16 ? c2[q].wp : c2[q].w;
+        bp.b[2 * q] = c1[q].bias;
+        bp.b[2 * q + 1] = c2[q].bias;
+        bp.dil[q] = dil[q];
+    }
+    bp.C = C;
+    bp.N = (int)N;
+    bp.k = k;
+    bp.mask = mask;
+    bp.mask_shift = mask_shift;
+    return bp;
+}
+
+// The operands of one fused ResBlock step (respair_*.hip); X, Y, beta and accumulate are the caller's
+static ResPairParams step_params(const ClConv& c1, const ClConv& c2, int k, int dil, int mode, int C, int64_t N, const unsigned char* mask, int U, int ushift) {
+    ResPairParams rp;
+    rp.W1 = c1.w;
+    rp.W2 = c2.w;
+    rp.W1p = c1.wp;
+    rp.W2p = c2.wp;
+    rp.W1x = c1.wxp;
+    rp.W2x = c2.wxp;
+    rp.b1 = c1.bias;
+    rp.b2 = c2.bias;
+    rp.C = C;
+    rp.N = (int)N;
+    rp.k = k;
+    rp.dil = dil;
+    rp.split = mode == 1;
+    rp.f16 = mode == 3;
+    rp.mask = mask;
+    rp.mask_div = U;
+    rp.mask_shift = ushift;
+    return rp;
+}
+
+// Which kernels one decoder run launches, per upsampling stage: filled by plan_decoder_cl, carried out by run_decoder_cl, which decides nothing itself
+struct VitsModel::ClStagePlan {
+    bool upx = false;           // the transposed convolution as ONE phased conv_clx launch (else conv_cl's phase groups)
+    bool upx_in_parts = false;  // ... on operand parts the previous stage's last launch wrote (else a split_cl pass makes them)
+    bool clx = false;           // the ResBlocks on conv_clx, their operands as parts planes
+    bool up_parts = false;      // clx: the transposed convolution's epilogue writes the ResBlocks' operand parts (else a split_cl pass after it)
+    bool next_parts = false;    // the stage's last launch writes the next stage's upx operand parts (that stage's upx_in_parts)
+    std::vector<BranchKernel> branch;   // per ResBlock branch
+};
+
+std::vector<VitsModel::ClStagePlan> VitsModel::plan_decoder_cl(int64_t Lf, const unsigned char* mask) const {
+    const int clx_mode = read_knob(g_clx, "SBV2_CLX must be 0, 1 or 2"), upx_on = read_knob(g_upx, "SBV2_UPX must be 0 or 1"),
+              rb_on = read_knob(g_rb, "SBV2_RESBRANCH must be 0 or 1"), rp_on = g_rpx.load(std::memory_order_relaxed);
+    const int nk = (int)cfg_.res_kernels.size();
+    // stage si's transposed convolution as ONE phased conv_clx launch (round 6; conv_cl's phase groups ran one 8-wave workgroup per CU at 233 registers:
+    // 1.0 ms per launch at the 128-channel stage for 0.24 ms of bytes and 0.33 ms of MFMA work, profiles/r06d_decoder_kernel_list.txt)
+    auto upx_at = [&](size_t si, int64_t Lin, int Uin) {
+        const ClStage& st = cl_stages_[si];
+        return clx_mode && upx_on && st.mode == 1 && st.upx.wx && Lin >= 256 && (Uin & (Uin - 1)) == 0 &&
+               clx_size_ok(clx_mode, (Lin / 256) * (st.upx.M / 64), 128);
+    };
+    std::vector<ClStagePlan> plan(cl_stages_.size());
+    plan[0].upx = upx_at(0, Lf, 1);
+    int64_t Lin = Lf;
+    int U = 1;
+    for (size_t si = 0; si < cl_stages_.size(); ++si) {
+        const ClStage& st = cl_stages_[si];
+        ClStagePlan& sp = plan[si];
+        U *= st.rate;
+        const int64_t Lo = Lf * U;
+        const int C = st.ch;
+        const bool pow2 = (U & (U - 1)) == 0;
+        int ushift = 0;
+        while ((1 << ushift) < U) ++ushift;
+        // the ResBlocks on conv_clx for launches of at least 128 tiles (clx 1): smaller ones do not pay for the extra halo launches.  The two paths agree to f32
+        // rounding, tests/test_gpu_parity.py::test_decoder_clx_path_agrees_with_conv_cl_path.  The 64-channel stage stays on the fused step: unfused on
+        // conv_clx it moves three times the bytes, measured in round 3.
+        sp.clx = clx_mode && st.mode == 1 && C >= 128 && (C & 63) == 0 && pow2 && clx_size_ok(clx_mode, (Lo / 256) * (C / 64), 128);
+        for (const ClBranch& rb : st.branches) {
+            if (!(rb.k == 3 || rb.k == 7 || rb.k == 11) || !rb.c1[0].wx) sp.clx = false;
+            for (int d : rb.dil)
+                if (d * (rb.k - 1) > 64 || d * (rb.k - 1) / 2 > kClxFront) sp.clx = false;
+        }
+        // the next stage's phased transposed convolution reads lrelu(this stage's sum) as bf16 parts: this stage's last launch writes them next to it
+        if (si + 1 < cl_stages_.size()) {
+            plan[si + 1].upx = upx_at(si + 1, Lo, U);
+            sp.next_parts = plan[si + 1].upx_in_parts = sp.clx && plan[si + 1].upx;
+        }
+        sp.up_parts = sp.clx;
+        if (sp.clx && !sp.upx)
+            for (const ClUpGroup& g : st.up) {
+                ConvClParams p;
+                p.split = 1;
+                p.tm = g.c.tm;
+                p.nmt = g.c.nmt;
+                p.N = (int)Lin;
+                sp.up_parts = sp.up_parts && conv_cl_parts_ok(p);
+            }
+        for (int j = 0; j < nk; ++j) {
+            const ClBranch& rb = st.branches[j];
+            // k = 3 branches of the <= 64-channel stages, and the 16-channel stage's k = 7 / 11 ones: all three steps in ONE launch (resbranch_clx.hip: the
+            // residual stream stays in registers, the operands in LDS; 2 plane passes through HBM instead of 6; same bits as the three fused steps).  The same
+            // at C = 128, where it replaces the branch's six conv_clx launches: f32 XU in, f32 XS out, no parts planes; C = 256 does not fit: its window alone
+            // is 143 KB at 128 rows.  It has no parts epilogue, so the last branch before a phased transposed convolution runs its steps.
+            if (rb_on && ((!sp.clx && C <= 64) || (sp.clx && C == 128)) && st.mode == 1 && (int)rb.dil.size() == kResBranchSteps && pow2 &&
+                !(sp.next_parts && j + 1 == nk) && resbranch_usable(branch_params(rb.c1, rb.c2, rb.dil, rb.k, C, Lo, mask, ushift)))
+                sp.branch.push_back(BranchKernel::resbranch);
+            else if (sp.clx)
+                sp.branch.push_back(BranchKernel::clx_steps);
+            else if (C <= 64 && pow2)   // stages of <= 64 channels are HBM bound: conv1 -> conv2 fused, the intermediate stays on chip (respair_*.hip)
+                sp.branch.push_back(rp_on ? respair_default(step_params(rb.c1[0], rb.c2[0], rb.k, rb.dil[0], st.mode, C, Lo, mask, U, ushift))
+                                          : BranchKernel::respair_cl);
+            else
+                sp.branch.push_back(BranchKernel::conv_cl_steps);
+        }
+        Lin = Lo;
+    }
+    return plan;
+}
+
 void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const float* cond_vec) {
     const int n = fl.n, Lf = fl.L, I = cfg_.inter;
     SBV2_REQUIRE(I % 16 == 0, "flow channels must be a multiple of 16 for the channels-last decoder");
+    const std::vector<ClStagePlan> plan = plan_decoder_cl(Lf, fl.d_mask);
     // z [inter][Lf] -> channels-last [Lf][inter]
     float* zc = ar.array<float>((size_t)Lf * I);
     transpose_out(z, 0, Lf, zc, stream_);
@@ -363,18 +489,10 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
     int U = 1;
     int64_t Lcur = Lf;
     const int nk = (int)cfg_.res_kernels.size();
-    SplitClPlanes cur_s;         // bf16 parts of lrelu(cur, 0.1) when the previous stage's last launch wrote them (the operand of a conv_clx transposed convolution)
-    bool cur_s_ok = false;
-    // whether stage si's transposed convolution runs as ONE phased conv_clx launch (round 6; conv_cl's phase groups ran one 8-wave workgroup per CU at 233
-    // registers: 1.0 ms per launch at the 128-channel stage for 0.24 ms of bytes and 0.33 ms of MFMA work, profiles/r06d_decoder_kernel_list.txt)
-    auto upx_wanted = [&](size_t si, int64_t Lin, int Uin) {
-        if (si >= cl_stages_.size()) return false;
-        const ClStage& s2 = cl_stages_[si];
-        return clx_enabled() && g_upx.load(std::memory_order_relaxed) != 0 && s2.mode == 1 && s2.upx.wx != nullptr && Lin >= 256 && (Uin & (Uin - 1)) == 0 &&
-               clx_wanted((Lin / 256) * (s2.upx.M / 64), clx_min_tiles());
-    };
+    SplitClPlanes cur_s;         // bf16 parts of lrelu(cur, 0.1) when the previous stage's last launch wrote them (plan upx_in_parts)
     for (size_t si = 0; si < cl_stages_.size(); ++si) {
         const ClStage& st = cl_stages_[si];
+        const ClStagePlan& sp = plan[si];
         const int Uin = U;
         U *= st.rate;
         const int64_t Lo = (int64_t)Lf * U;
@@ -383,41 +501,28 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
         float* XS = ar.array<float>((size_t)Lo * C);
         int ushift = 0;
         while ((1 << ushift) < U) ++ushift;
-        // (launches of at least clx_min_tiles() tiles: smaller ones do not pay for the extra halo launches.  The two paths agree to f32 rounding,
-        // tests/test_gpu_parity.py::test_decoder_clx_path_agrees_with_conv_cl_path.  The 64-channel stage stays on the fused step: unfused on conv_clx it
-        // moves three times the bytes, measured in round 3.)
-        bool clx = clx_enabled() && st.mode == 1 && C >= 128 && (C & 63) == 0 && (1 << ushift) == U && (Lo / 256) * (C / 64) >= clx_min_tiles();
-        for (int j = 0; j < nk && clx; ++j) {
-            const ClBranch& rb = st.branches[j];
-            if (!(rb.k == 3 || rb.k == 7 || rb.k == 11) || !rb.c1[0].wx) clx = false;
-            for (int d : rb.dil)
-                if (d * (rb.k - 1) > 64 || d * (rb.k - 1) / 2 > kClxFront) clx = false;
-        }
-        // the NEXT stage's transposed convolution on conv_clx reads lrelu(XS) as bf16 parts: this stage's last launch writes them next to XS
-        const bool next_upx = clx && upx_wanted(si + 1, Lo, U);
         SplitClPlanes XSs;
-        if (next_upx) XSs = make_split_cl(ar.alloc(split_cl_bytes(C, Lo)), C, Lo, stream_);
+        if (sp.next_parts) XSs = make_split_cl(ar.alloc(split_cl_bytes(C, Lo)), C, Lo, stream_);
         const Arena::Mark mk = ar.mark();
         float* XU = ar.array<float>((size_t)Lo * C);
         float* T1 = ar.array<float>((size_t)Lo * C);
         float* YA = ar.array<float>((size_t)Lo * C);
         float* YB = ar.array<float>((size_t)Lo * C);
         // Wide stages (>= 128 channels, split-bf16): the ResBlock convolutions read PRE-SPLIT operands (conv_clx.hip: LDS-DMA only, one barrier
-        // per tap).  The stage input is split once (split_cl); every other operand is written by the producing convolution's epilogue as the
-        // bf16 parts of lrelu(result), next to (conv2) or instead of (conv1) the f32 plane.  Same bits as the conv_cl path.
+        // per tap).  The stage input's parts are written by the transposed convolution's epilogue (or one split_cl pass over it); every other operand
+        // is written by the producing convolution's epilogue as the bf16 parts of lrelu(result), next to (conv2) or instead of (conv1) the f32 plane.
+        // Same bits as the conv_cl path.
         SplitClPlanes XUs, T1s, YsA, YsB;
-        if (clx) {
+        if (sp.clx) {
             const size_t sb = split_cl_bytes(C, Lo);
             XUs = make_split_cl(ar.alloc(sb), C, Lo, stream_);
             T1s = make_split_cl(ar.alloc(sb), C, Lo, stream_);
             YsA = make_split_cl(ar.alloc(sb), C, Lo, stream_);
             YsB = make_split_cl(ar.alloc(sb), C, Lo, stream_);
         }
-        // (the stage input's parts are written by the transposed convolution's own epilogue below: no separate split pass over XU)
-        bool parts_done = clx;   // every phase group's launch wrote its share of XUs
-        if (upx_wanted(si, Lcur, Uin)) {
-            // ONE phased conv_clx launch: rows (phase, cout), the union of the phases' taps; its operand = bf16 parts of lrelu(cur, 0.1)
-            if (!cur_s_ok) {
+        if (sp.upx) {
+            // ONE phased conv_clx launch: rows (phase, cout), each phase's own taps; its operand = bf16 parts of lrelu(cur, 0.1)
+            if (!sp.upx_in_parts) {
                 cur_s = make_split_cl(ar.alloc(split_cl_bytes(st.cin, Lcur)), st.cin, Lcur, stream_);
                 split_cl(cur, st.cin, Lcur, st.cin, 0.1f, cur_s, stream_);
             }
@@ -435,7 +540,7 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
             pu.shift_step = -1;
             pu.Y = XU;
             pu.ldy = C;
-            if (clx) {
+            if (sp.clx) {
                 pu.Ys = XUs;
                 pu.ys_slope = 0.1f;
             }
@@ -450,7 +555,6 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
                 pu.phase_tap0[q] = st.upx.phase_tap0[q];
             }
             pu.prof_flops = 2.0 * st.upx.alg_macs_per_pos * (double)Lcur;
-            SBV2_REQUIRE(conv_clx_usable(pu), "decoder: the phased transposed convolution does not fit conv_clx");
             launch_conv_clx(pu, stream_);
         } else {
             for (const auto& g : st.up) {
@@ -477,57 +581,36 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
                 p.out_stride = st.rate;
                 p.phase_rows = C;
                 for (int q = 0; q < kMaxPhases; ++q) p.phase_off[q] = g.phase_off[q];
-                if (clx && conv_cl_parts_ok(p)) {
+                if (sp.up_parts) {   // (launch_conv_cl refuses a launch whose parts it cannot write)
                     p.ys_p = XUs.p;
                     p.ys_rows = (int64_t)XUs.front + XUs.N + XUs.back;
                     p.ys_front = XUs.front;
                     p.ys_slope = 0.1f;
-                } else {
-                    parts_done = false;
                 }
                 launch_conv_cl(p, stream_);
             }
-            if (clx && !parts_done) split_cl(XU, C, Lo, C, 0.1f, XUs, stream_);   // (small launches: one pass over the finished plane, same bits)
+            if (sp.clx && !sp.up_parts) split_cl(XU, C, Lo, C, 0.1f, XUs, stream_);   // (small launches: one pass over the finished plane, same bits)
         }
         for (int j = 0; j < nk; ++j) {
             const ClBranch& rb = st.branches[j];
+            const BranchKernel kern = sp.branch[j];
             const float* y = XU;
             const SplitClPlanes* ys = &XUs;   // bf16 parts of lrelu(y)
             const int nd = (int)rb.dil.size();
-            // k = 3 branches of the <= 64-channel stages: all three steps in ONE launch (resbranch_clx.hip: the residual stream stays in registers, the
-            // operands in LDS; 2 plane passes through HBM instead of 6; same bits as the three fused steps below)
-            // (the same at C = 128, where it replaces the branch's six conv_clx launches: f32 XU in, f32 XS out, no parts planes; C = 256 does not fit: its
-            // window alone is 143 KB at 128 rows)
-            if (((!clx && C <= 64) || (clx && C == 128)) && fuse_pairs_ && resbranch_wanted(C, rb.k) && st.mode == 1 && nd == kResBranchSteps && (U & (U - 1)) == 0 &&
-                !(next_upx && j + 1 == nk)) {
-                ResBranchParams bp;
+            if (kern == BranchKernel::resbranch) {
+                ResBranchParams bp = branch_params(rb.c1, rb.c2, rb.dil, rb.k, C, Lo, fl.d_mask, ushift);
                 bp.X = XU;
                 bp.Y = XS;
-                for (int q = 0; q < nd; ++q) {
-                    bp.W[2 * q] = C == 16 ? rb.c1[q].wp : rb.c1[q].w;
-                    bp.W[2 * q + 1] = C == 16 ? rb.c2[q].wp : rb.c2[q].w;
-                    bp.b[2 * q] = rb.c1[q].bias;
-                    bp.b[2 * q + 1] = rb.c2[q].bias;
-                    bp.dil[q] = rb.dil[q];
-                }
-                bp.C = C;
-                bp.N = (int)Lo;
-                bp.k = rb.k;
-                bp.slope = 0.1f;
                 bp.beta = 1.0f / nk;
                 bp.accumulate = j > 0;
-                bp.mask = fl.d_mask;
-                bp.mask_shift = ushift;
-                if (resbranch_usable(bp)) {
-                    launch_resbranch(bp, stream_);
-                    continue;
-                }
+                launch_resbranch(bp, stream_);
+                continue;
             }
             for (int q = 0; q < nd; ++q) {
                 const int d = rb.dil[q];
                 const bool last = q + 1 == nd;
                 float* yn = last ? XS : ((y == YA) ? YB : YA);
-                if (clx) {
+                if (kern == BranchKernel::clx_steps) {
                     ConvClxParams p1;
                     p1.X = *ys;
                     p1.W = rb.c1[q].wx;
@@ -560,7 +643,7 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
                     if (!last) {
                         p2.Ys = *yns;
                         p2.ys_slope = 0.1f;
-                    } else if (next_upx && j + 1 == nk) {   // the stage's finished sum: lrelu(XS, 0.1) as the next transposed convolution's operand
+                    } else if (sp.next_parts && j + 1 == nk) {   // the stage's finished sum: lrelu(XS, 0.1) as the next transposed convolution's operand
                         p2.Ys = XSs;
                         p2.ys_slope = 0.1f;
                     }
@@ -573,38 +656,17 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
                     p2.mask_shift = ushift;
                     launch_conv_clx(p2, stream_);
                     ys = yns;
-                    y = yn;
-                    continue;
-                }
-                if (fuse_pairs_ && C <= 64 && (U & (U - 1)) == 0) {
-                    // stages of <= 64 channels are HBM bound: conv1 -> conv2 fused, the intermediate stays in LDS (respair_cl.hip)
-                    ResPairParams rp;
-                    rp.X = y;
-                    rp.Y = yn;
-                    rp.W1 = rb.c1[q].w;
-                    rp.W2 = rb.c2[q].w;
-                    rp.W1p = rb.c1[q].wp;
-                    rp.W2p = rb.c2[q].wp;
-                    rp.W1x = rb.c1[q].wxp;
-                    rp.W2x = rb.c2[q].wxp;
-                    rp.b1 = rb.c1[q].bias;
-                    rp.b2 = rb.c2[q].bias;
-                    rp.C = C;
-                    rp.N = (int)Lo;
-                    rp.k = rb.k;
-                    rp.dil = d;
-                    rp.split = st.mode == 1;
-                    rp.f16 = st.mode == 3;
-                    rp.slope = 0.1f;
-                    rp.beta = last ? 1.0f / nk : 1.0f;
-                    rp.accumulate = last && j > 0;
-                    rp.mask = fl.d_mask;
-                    rp.mask_div = U;
-                    launch_respair_cl(rp, stream_);
-                } else {
+                } else if (kern == BranchKernel::conv_cl_steps) {
                     conv_cl(rb.c1[q], y, C, (int)Lo, T1, C, (int)Lo, d, d * (rb.k - 1) / 2, fl.d_mask, U, 0.1f, nullptr, 0, 1.0f, 0);
                     conv_cl(rb.c2[q], T1, C, (int)Lo, yn, C, (int)Lo, 1, (rb.k - 1) / 2, fl.d_mask, U, 0.1f, y, C, last ? 1.0f / nk : 1.0f,
                             last && j > 0);
+                } else {
+                    ResPairParams rp = step_params(rb.c1[q], rb.c2[q], rb.k, d, st.mode, C, Lo, fl.d_mask, U, ushift);
+                    rp.X = y;
+                    rp.Y = yn;
+                    rp.beta = last ? 1.0f / nk : 1.0f;
+                    rp.accumulate = last && j > 0;
+                    launch_respair(rp, kern, stream_);
                 }
                 y = yn;
             }
@@ -613,7 +675,6 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
         cur = XS;
         Lcur = Lo;
         cur_s = XSs;
-        cur_s_ok = next_upx;
     }
     pcm_lens_.assign(n, 0);
     pcm_offs_.assign(n, 0);

@@ -323,7 +323,9 @@ class VitsModel {
         int cin, ch, rate;
         int mode = 1;   // the stage's arithmetic (dec_mode_ codes 1 .. 3; SBV2_DECODER_STAGES)
     };
+    struct ClStagePlan;
     void load_decoder_cl(const Blob& blob);
+    std::vector<ClStagePlan> plan_decoder_cl(int64_t Lf, const unsigned char* mask) const;
     void run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const float* cond_vec);
     void conv_cl(const ClConv& c, const float* X, int ldx, int NB, float* Y, int ldy, int N, int dil, int pad_l, const unsigned char* mask,
                  int mask_div, float pre_slope, const float* R, int ldr, float beta, int accumulate);
@@ -389,7 +391,6 @@ class VitsModel {
     float* dec_cond_vec_ = nullptr;  // cond(g) per utterance of the running forward
     int dec_post_k_ = 7;
     std::vector<Stage> stages_;
-    bool fuse_pairs_ = true;  // the fused ResBlock step of the <= 64-channel stages (always on in the product; false only in kernel tests)
     int dec_mode_ = 0;  // 0 = exact f32 MFMA (k-major), 1 = split-bf16 (f32-grade), 2 = plain bf16, 3 = fp16 operands
     ClConv cl_pre_;
     std::vector<ClStage> cl_stages_;

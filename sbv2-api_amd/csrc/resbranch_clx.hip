@@ -634,17 +634,6 @@ static void launch_rb(const ResBranchParams& p, hipStream_t stream) {
     }
 }
 
-// 0: the unfused paths (three respair_clx launches; at C = 128 six conv_clx launches); 1 (default): the fused branch at C = 16 / 32 / 64 / 128 (k = 3) and
-// at C = 16 (k = 7 / 11); 2: the k = 3 branches only
-static std::atomic<int> g_rb{getenv("SBV2_RESBRANCH") ? atoi(getenv("SBV2_RESBRANCH")) : 1};   // sbv2_debug_set_resbranch
-int set_resbranch(int on) { return g_rb.exchange(on); }
-bool resbranch_enabled() { return g_rb.load(std::memory_order_relaxed) != 0; }
-bool resbranch_wanted(int C, int k) {
-    const int mode = g_rb.load(std::memory_order_relaxed);
-    if (mode == 0 || !(C == 16 || C == 32 || C == 64 || C == 128)) return false;
-    return k == 3 || mode == 1;
-}
-
 // rows of the window of the instance launch_rb_any picks (0: none)
 static int rb_rows(int C, int k) {
     if (k == 3) return C == 128 ? 192 : (C == 64 ? 384 : ((C == 32 || C == 16) ? 256 : 0));

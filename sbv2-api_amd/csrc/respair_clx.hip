@@ -652,7 +652,7 @@ static void launch_rpx_any(const ResPairParams& p, hipStream_t stream) {
     SBV2_REQUIRE(false, "respair_clx: shape not instantiated");
 }
 
-// p.mask_shift must be set (launch_respair_cl does it)
+// p.mask_shift must be set
 void launch_respair_clx(const ResPairParams& p0, hipStream_t stream) {
     SBV2_REQUIRE(respair_clx_usable(p0), "respair_clx: operands do not fit the kernel");
     ResPairParams p = p0;

@@ -619,7 +619,7 @@ static void launch_x6(const ResPairParams& p, hipStream_t stream) {
     }
 }
 
-// p.mask_shift set (launch_respair_cl does it)
+// p.mask_shift set
 bool respair_x16_usable(const ResPairParams& p) {
     return p.W1x && p.W2x && p.split && !p.f16 && (p.C == 32 || p.C == 64) && (p.k == 7 || p.k == 11) && p.dil >= 1 && p.dil * (p.k - 1) <= 64 && p.slope >= 0.f &&
            p.slope <= 1.f && p.N >= 1 && (!p.mask || p.mask_shift >= 0);

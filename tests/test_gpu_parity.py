@@ -384,9 +384,9 @@ def test_conv_transpose_kernel(cin, cout, k, s, p, L):
 
 @pytest.mark.parametrize("cin,cout,k,s,L", [(64, 64, 16, 8, 300), (128, 64, 8, 2, 1000), (64, 128, 16, 8, 256), (256, 128, 16, 8, 515), (128, 64, 8, 2, 4097)])
 def test_conv_transpose_clx_kernel(cin, cout, k, s, L):
-    """The wide stages' ConvTranspose1d as ONE phased conv_clx launch (round 6): rows = (phase, cout), taps = the union of the phases' input taps padded to an
-    odd count with zero weights, output row n * stride + phase, on pre-split bf16 hi / lo operands: against the oracle's conv_transpose1d (the checker), with a
-    column mask on the input positions, every output row written (the buffer starts as NaN), and the bf16 parts of lrelu(result) it leaves for the ResBlocks."""
+    """The wide stages' ConvTranspose1d as ONE phased conv_clx launch (round 6): rows = (phase, cout), taps = each phase's own input taps, output row
+    n * stride + phase, on pre-split bf16 hi / lo operands: against the oracle's conv_transpose1d (the checker), with a column mask on the input positions,
+    every output row written (the buffer starts as NaN), and the bf16 parts of lrelu(result) it leaves for the ResBlocks."""
     rng = np.random.default_rng(k * 100 + s + L)
     x = rng.standard_normal((cin, L)).astype(np.float32)
     w = (rng.standard_normal((cin, cout, k)) / np.sqrt(cin * k / s)).astype(np.float32)
@@ -400,22 +400,6 @@ def test_conv_transpose_clx_kernel(cin, cout, k, s, L):
     np.testing.assert_allclose(y, ref, atol=3e-5, rtol=1e-5)
     lr = np.where(y >= 0, y, y * np.float32(0.1)).astype(np.float32)
     assert float(np.abs(ys - lr).max()) <= 2.0 ** -16 * float(np.abs(lr).max())
-    # a launch that writes parts packs its rows as (phase pair, 16 channels, phase in pair, channel) so that the 32-byte parts rows of two adjacent output rows
-    # leave together (ConvClxParams::phase_group); the plain (phase, channel) order (sbv2_debug_set_upx(2)) gives the same bits
-    y0, ys0, y1, ys1 = np.empty_like(y), np.empty_like(ys), np.empty_like(y), np.empty_like(ys)
-    prev = _lib.lib().sbv2_debug_set_upx(1)
-    try:
-        _lib.check(_lib.lib().sbv2_debug_conv_transpose1d_clx(0, P(x), P(w), P(b), cin, cout, k, L, s, 0.1, None, 1, 0, P(y0), P(ys0), None))
-        _lib.lib().sbv2_debug_set_upx(2)
-        _lib.check(_lib.lib().sbv2_debug_conv_transpose1d_clx(0, P(x), P(w), P(b), cin, cout, k, L, s, 0.1, None, 1, 0, P(y1), P(ys1), None))
-        _lib.lib().sbv2_debug_set_upx(3)    # the union of all phases' taps (a zero tap per phase): another pairing of the steps, f32 rounding apart
-        y3 = np.empty_like(y)
-        _lib.check(_lib.lib().sbv2_debug_conv_transpose1d_clx(0, P(x), P(w), P(b), cin, cout, k, L, s, 0.1, None, 1, 0, P(y3), P(ys1.copy()), None))
-    finally:
-        _lib.lib().sbv2_debug_set_upx(prev)
-    np.testing.assert_array_equal(y1, y0)
-    np.testing.assert_array_equal(ys1, ys0)
-    np.testing.assert_allclose(y3, y0, atol=1e-5, rtol=1e-5)
     mask = (rng.random((L + 3) // 4) > 0.2).astype(np.uint8)
     keep = np.repeat(mask, 4)[:L]
     xm = x * keep[None, :]

@@ -44,6 +44,20 @@ def test_errors_are_reported_not_thrown():
     assert rc != 0 and b"SBV2W001" in l.sbv2_last_error()
 
 
+def test_decoder_knob_setters_refuse_removed_values():
+    """The decoder's dispatch setters are host-only: a value they no longer take returns -1 and leaves the setting in place."""
+    l = _lib.lib()
+    for setter, keep, refused in ((l.sbv2_debug_set_clx, 2, (3, -1)), (l.sbv2_debug_set_upx, 0, (2, 3, -1)), (l.sbv2_debug_set_resbranch, 0, (2, -1)),
+                                  (l.sbv2_debug_set_respair_clx, 0, (2, -1))):
+        prev = setter(keep)
+        try:
+            for v in refused:
+                assert setter(v) == -1, (setter.__name__, v)
+            assert setter(keep) == keep, setter.__name__
+        finally:
+            setter(prev)
+
+
 def test_product_code_never_touches_the_oracle():
     pkg = os.path.join(ROOT, "sbv2-api_amd")
     for dp, _, fs in os.walk(pkg):
