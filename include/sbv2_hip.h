@@ -292,19 +292,6 @@ int sbv2_debug_set_flash_parts(int on);
    convolution reads the parts; y = (conv + bias + res) * beta; ys_sum (optional) = hi + lo of the parts of lrelu(y, 0.1) the epilogue emits. */
 int sbv2_debug_conv1d_clx(int device, const float* x, const float* w, const float* bias, const float* res, int64_t cin, int64_t cout, int64_t k,
                           int64_t L, int64_t dilation, float pre_slope, float beta, int64_t iters, float* y, float* ys_sum, float* ms);
-/* Diagnostics (MI355X_MICROARCH.md "DVFS give-back" item 6): the dominant decoder convolution (C x C, k taps, channels-last, split-bf16,
-   128-row workgroups) on random data, `seconds` of back-to-back launches, then out4 = {in-kernel shader clock in MHz = d s_memtime /
-   d s_memrealtime x 100 (median over workgroups), ms per launch, shader cycles of a workgroup's chunk loop, workgroups stamped}.
-   abl: 0 = the kernel, 1 = without its MFMAs, 2 = its MFMAs only, 3 = staging + barriers only. */
-int sbv2_debug_conv_cl_clock(int device, int64_t C, int64_t k, int64_t dilation, int64_t L, int abl, double seconds, double* out4);
-/* Diagnostics: the life of a conv_clx workgroup (the ResBlock convolutions of the 128- / 256-channel decoder stages: scripts/convert/convert_model.py:97-110
-   exports them; no reference counterpart).  kind 1 = conv1 (parts in, parts out), 2 = conv2 (+ residual in, f32 + parts out), 3 = a branch's last conv2
-   (accumulating).  `seconds` of back-to-back launches, then the stamps of one more: 12 words per workgroup {loop start / end in shader cycles and in
-   100 MHz ticks, kernel entry, last store issued, stores acknowledged (100 MHz), HW_ID | XCC_ID << 32, epilogue: behind the post-loop barrier, its
-   global reads arrived, the first half's stores issued (100 MHz), 0}; *ms_per_launch is of the un-stamped kernel.  `variant` selects a kernel variant under
-   test in builder experiments; the library holds only variant 0 (the product kernel), other values run the same kernel. */
-int sbv2_debug_clx_timeline(int device, int64_t C, int64_t k, int64_t dilation, int64_t L, int kind, int variant, double seconds, uint64_t* stamps,
-                            int64_t capacity_words, int64_t* workgroups, double* ms_per_launch);
 /* Diagnostics for the f16x3 operand format (DeBERTa's and the flow's 1x1 products): the split of an activation into the f16 hi / scaled-lo pair clamps
    finite values beyond +-65504 (NaN and infinities propagate).  enable = 1 / 0 switches the device-side counter of clamped values on / off for planes
    allocated from then on (-1: leave as is; the SBV2_F16X3_SATCOUNT=1 environment variable switches it on from the start); *count (optional) receives the
@@ -338,20 +325,9 @@ int sbv2_debug_conv_transpose1d_clx(int device, const float* x, const float* w, 
    y_q = conv2_q(lrelu(conv1_q(lrelu(y_{q-1}), dilations[q]) + b1_q)) + b2_q + y_{q-1}, result beta * y_3 [+ y when accumulate], masked by mask[n / mask_div]
    (a power of two; mask may be null) at every layer; channels-last x / y [N][C], w [6][C][C][k] and bias [6][C] in the order conv1_0, conv2_0, conv1_1, ...,
    split-bf16, C in {16, 32, 64, 128}; variant 0 = three launches of the fused step (respair_clx.hip, C <= 64), 1 = one launch (resbranch_clx.hip), 2 = six
-   launches of conv_cl.hip (any C).  iters > 0: *ms = average duration of
-   `iters` further runs; stamps (variant 1, may be null): 16 words per workgroup of one more, stamped launch (s_memtime at entry [0], window converted [1], end
-   of step 1 / 2 / 3 [2 .. 4], stores issued [6]; s_memrealtime at entry / exit [14, 15]).  Test / measurement hook. */
+   launches of conv_cl.hip (any C).  iters > 0: *ms = average duration of `iters` further runs.  Test / measurement hook. */
 int sbv2_debug_resbranch(int device, const float* x, const float* w, const float* bias, int64_t C, int64_t N, int64_t k, const int64_t* dilations,
-                         const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, int64_t iters, float* y, float* ms,
-                         uint64_t* stamps, int64_t stamps_cap);
-/* Diagnostics: one fused ResBlock step (respair_cl.hip, split-bf16, C = 16 / 32 / 64) on random data, `seconds` of back-to-back launches,
-   then out[0] = in-kernel clock (MHz, median over workgroups), out[1] = ms per launch, out[2] = workgroups stamped, out[2 + i] = median shader
-   cycles from a workgroup's entry to phase stamp i (1 = conv1 window staged, 7 / 8 / 9 / 10 = first chunk's MFMAs / barrier / next chunk staged /
-   barrier, 2 = conv1 done, 3 = intermediate written, 4 = barrier, 5 = conv2 done, 6 = stores issued).  variant 0 = the stamped instantiation of
-   respair_cl (abl bits: 1 cache-hot reads, 2 no stores, 4 no MFMAs, 8 no window conversion, 16 no intermediate epilogue), 1 = the product respair_cl
-   (time only), 2 = respair_clx stamped, 3 = the product respair_clx (time only), 4 = respair_x16 stamped (C = 32 / 64, k = 7 / 11; stamps 7 - 9: chunk
-   pair 0 done / chunk pair 1 converted / first pair done). */
-int sbv2_debug_respair_clock(int device, int64_t C, int64_t k, int64_t dilation, int64_t L, int variant, int abl, double seconds, double* out, int nout);
+                         const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, int64_t iters, float* y, float* ms);
 /* y[M][N] = act(w[M][K] x[K][N] + bias) (+ res) through the split-bf16 1x1 GEMM (gemm_bfs.hip; parts 2 = bf16x3, 3 = bf16x6).  split_out != 0:
    the result is also emitted as that many bf16 parts and y returns their sum.  iters > 0: average launch time in *ms.  Test hook. */
 int sbv2_debug_gemm_bfs(int device, const float* x, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,

@@ -1,4 +1,4 @@
-// Shared by the translation units behind the C ABI (api.cpp, node.cpp, stream.cpp): handle structs and the exception -> return-code
+// Shared by the translation units behind the C ABI (api.cpp, test_hooks.cpp, node.cpp, stream.cpp): handle structs and the exception -> return-code
 // convention.  Not installed; include/sbv2_hip.h is the public contract.
 #pragma once
 #include <cstdlib>

@@ -878,11 +878,10 @@ __device__ __forceinline__ void fq_wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// DG: builder's timeline variant (a diagnostic instantiation, not launched by the product path): s_memtime at every barrier / phase boundary of every wave of workgroup (0, 0), kept in LDS
-template <int DT, int NW, bool DG = false>
+template <int DT, int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_vits_flash_x3q(const AttnGroup* groups, const float* Q, int ld, const __bf16* Kp, const __bf16* Vp,
                                                               int64_t pstride, int ldp, float* ctx, int ldc, int dk, const float* erk, const float* erv,
-                                                              int w, float qscale, unsigned long long* stamps = nullptr) {
+                                                              int w, float qscale) {
     constexpr int DR = DT * 32;
     constexpr int KS = DR / 16;            // bf16 k-steps over the head dimension
     constexpr int NB8 = DR / 8;            // 8-row DMA blocks per part (1 KB each)
@@ -903,21 +902,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // the lo parts of q: in LDS as B fragments [NW][KS][64 lanes][16 bytes] for the 4-wave workgroup (one wave per SIMD, the registers go to deeper
     // fragment prefetch); in registers for the 8-wave one (two waves per SIMD hide each other's fragment latency; its LDS holds 18 KB of band state)
     constexpr bool QL_LDS = NW == 4;
-    constexpr int QL_BYTES = QL_LDS ? NW * KS * 1024 : 0;
     const unsigned lds_ql = lds_dummy + NW * 64 * 4;
-    constexpr int kStampMax = 160;   // per wave
-    const unsigned lds_st = lds_ql + QL_BYTES;
-    int nst = 0;
-    auto stamp = [&]() {
-        if constexpr (DG) {
-            if (nst < kStampMax) {
-                const unsigned long long tm = __builtin_amdgcn_s_memtime();
-                const unsigned a = lds_st + ((threadIdx.x >> 6) * kStampMax + nst) * 8;
-                asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(tm) : "memory");
-                ++nst;
-            }
-        }
-    };
 
     const AttnGroup g = groups[blockIdx.y];
     const int T = g.T;
@@ -1270,14 +1255,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             fq_static_for<0, 18>([&](auto nc) { slice(nc); });
         }
         read_vg(std::integral_constant<int, 3>{});
-        stamp();
         if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) cacc[dt][r] *= alpha;
         }
-        stamp();
         // phase B: PV(t).  Groups g = (key half sp, row tile dt) = 0 .. 2 DT - 1, three MFMAs each (lo * hi, hi * lo, hi * hi on accumulator dt), in PAIRS with
         // their MFMAs interleaved (two independent accumulators back to back).  Four fragment sets: groups 0 .. 3 are on their way when the phase starts,
         // groups 4 and 5 are requested behind the last MFMA of groups 0 and 1.
@@ -1344,9 +1327,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // steps 0 .. nsteps - 2 with QK of their successor in flight, two per loop iteration (the two accumulators swap roles); the last one on its own
     f32x16 sa, sb;
     float mt = kFaNegBig;
-    stamp();
     step_barrier(-1);
-    stamp();
     if (active) {
         qk(sa, 0, [](auto) {});
 #pragma unroll
@@ -1358,35 +1339,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int n1 = nsteps - 1;
     int t = 0;
     for (; t + 2 <= n1; t += 2) {
-        stamp();
         step_barrier(t);
-        stamp();
         if (active) iter(t, sa, sb, mt, std::true_type{});
-        stamp();
         step_barrier(t + 1);
-        stamp();
         if (active) iter(t + 1, sb, sa, mt, std::true_type{});
     }
     if (t < n1) {
-        stamp();
         step_barrier(t);
-        stamp();
         if (active) iter(t, sa, sb, mt, std::true_type{});
-        stamp();
         step_barrier(t + 1);
-        stamp();
         if (active) iter(t + 1, sb, sa, mt, std::false_type{});
     } else {
-        stamp();
         step_barrier(t);
-        stamp();
         if (active) iter(t, sa, sb, mt, std::false_type{});
-    }
-    stamp();
-    if constexpr (DG) {
-        __syncthreads();
-        if (blockIdx.x == 0 && blockIdx.y == 0 && stamps)
-            for (int q = threadIdx.x; q < NW * kStampMax; q += NTH) stamps[q] = q % kStampMax < nst ? reinterpret_cast<unsigned long long*>(fq_smem + 4 * IMG + sizeof(float) * (2 * kFaBand * DR + 2 * NW * kFaBand * 32) + NW * 64 * 4 + QL_BYTES)[q] : 0ull;
     }
     if (!active) return;
 
@@ -1414,13 +1379,11 @@ void launch_flash_x3q(const AttnGroup* groups, int ngroups, int maxT, const floa
     constexpr size_t lds = 4 * 2 * DR * 128 + sizeof(float) * (2 * kFaBand * DR + 2 * NW * kFaBand * 32) + NW * 64 * 4 + (NW == 4 ? NW * (DR / 16) * 1024 : 0);
     const __bf16* base = static_cast<const __bf16*>(kv.p);
     const dim3 grid((maxT + 32 * NW - 1) / (32 * NW), ngroups);
-    // (the timeline instantiation <DT, NW, true> of round 4 - s_memtime stamps at every phase boundary, profiles/r04i_flash_attention_timeline.txt - is not
-    // launched by the library any more)
     auto kern = k_vits_flash_x3q<DT, NW>;
     static std::atomic<uint64_t> lds_allowed{0};   // per (kernel instantiation, device)
     allow_full_lds(reinterpret_cast<const void*>(kern), lds_allowed);
     hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, s, groups, Q, ld, base + (int64_t)k_row0 * kv.ld, base + (int64_t)v_row0 * kv.ld, kv.pstride, kv.ld,
-                       ctx, ldc, dk, erk, erv, window, qscale, (unsigned long long*)nullptr);
+                       ctx, ldc, dk, erk, erv, window, qscale);
 }
 
 template <int DT>

@@ -279,7 +279,6 @@ struct ConvClParams {
 void launch_conv_cl(const ConvClParams& p, hipStream_t stream);
 bool conv_cl_parts_ok(const ConvClParams& p);   // launch_conv_cl(p) would honour p.ys_p
 bool launch_conv_cl_small(const ConvClParams& p, int mask_shift, hipStream_t stream);   // conv_cl_small.hip
-void launch_conv_cl_diag(const ConvClParams& p, int abl, unsigned long long* stamps, hipStream_t stream);   // diagnostics (clock stamps + ablations)
 
 // ---------------------------------------------------------------------------------------------
 // Split-bf16 1x1 products on k-major planes (gemm_bfs.hip): Y[m][n] = epi(sum_k W[m][k] X[k][n]) on the bf16 matrix cores with both
@@ -437,7 +436,6 @@ __device__ __forceinline__ void split_store1(const SplitPlanes& sp, int64_t off,
 // ---------------------------------------------------------------------------------------------
 // conv_clx.hip: the ResBlock convolutions of the wide decoder stages on pre-split, pre-activated operands (LDS-DMA only, no staging registers)
 // ---------------------------------------------------------------------------------------------
-constexpr int kClxStampWords = 12;   // sbv2_debug_clx_timeline: words per workgroup
 constexpr int kClxFront = 64;    // zero rows in front of every (chunk, part) plane: the left zero padding of the first tile's window
 constexpr int kClxBack = 384;    // ... and behind it: right padding + the last position tile's overhang + DMA piece rounding
 struct SplitClPlanes {           // bf16 hi / lo of a channels-last activation, chunk-major: [C / 16][2 parts][front + N + back][16] bf16
@@ -471,8 +469,6 @@ struct ConvClxParams {
     int accumulate = 0;         // Y += result
     const unsigned char* mask = nullptr;   // position n is kept iff mask[n >> mask_shift]
     int mask_shift = -1;
-    unsigned long long* stamps = nullptr;  // diagnostics: kClxStampWords per workgroup (sbv2_debug_clx_timeline)
-    int variant = 0;            // diagnostics (sbv2_debug_clx_timeline): kernel variant under test in a builder experiment; the library holds variant 0 only
     // Phased output (round 6: the polyphase ConvTranspose1d of the wide decoder stages): row m of the product is output channel m % phase_rows of phase
     // m / phase_rows, and position n of that phase is OUTPUT row n * out_stride + phase_off[phase] of Y / Ys (Ys.C == phase_rows, Ys.N == N * out_stride;
     // phase_rows a multiple of 64).  N, X and the mask stay indexed by the INPUT position: pass mask_shift = (output positions per mask entry) / out_stride.
@@ -522,22 +518,16 @@ struct ResPairParams {
     int mask_div = 1;
     int mask_shift = -1;   // mask_div = 1 << mask_shift: the caller's for respair_clx / respair_x16, set by launch_respair_cl
     int alias_x2 = 1;      // set by launch_respair_cl: the intermediate window re-uses the conv1 window's LDS
-    int abl = 0;           // diagnostics (wrong results): 1 = every global read hits the same few cache-hot rows, 2 = no global stores; diag kernel only: 4 = no MFMAs, 8 = no conv1 window conversion, 16 = no intermediate epilogue
-    unsigned long long* stamps = nullptr;   // diag kernel only: 16 per workgroup
     int nt_store = 0;      // set by launch_respair_clx: the plane does not fit the caches, its stores bypass them
-    int rres_late = 0;     // respair_clx diagnostics only (sbv2_debug_respair_clock): request the residual rows before conv2 (rounds 1-3) instead of with the window
 };
 void launch_respair_cl(const ResPairParams& p, hipStream_t stream);
-void launch_respair_cl_diag(const ResPairParams& p, hipStream_t stream);
 // respair_clx.hip: the same step, split-bf16, k in {3, 7, 11}, rebuilt around its instruction count (round 4); bit-identical to respair_cl at C = 32 / 64,
 // f32-grade (two taps per 16x16x32 MFMA: another summation order; tests hold 1e-5) at C = 16
 bool respair_clx_usable(const ResPairParams& p);          // p.mask_shift set
 void launch_respair_clx(const ResPairParams& p, hipStream_t stream);
-void launch_respair_clx_diag(const ResPairParams& p, hipStream_t stream);
 // respair_x16.hip (round 6): the step at C = 32 / 64, k = 7 / 11 on v_mfma_f32_16x16x32_bf16 (conv_clx.hip's operand scheme); f32 rounding apart from respair_clx
 bool respair_x16_usable(const ResPairParams& p);          // p.mask_shift set
 void launch_respair_x16(const ResPairParams& p, hipStream_t stream);
-void launch_respair_x16_diag(const ResPairParams& p, hipStream_t stream);
 // The kernels that run one ResBlock branch of the decoder (decoder_cl.cpp's plan): the fused branch, two conv_clx launches per step, one fused-step launch
 // per step, two conv_cl launches per step
 enum class BranchKernel { resbranch, clx_steps, respair_x16, respair_clx, respair_cl, conv_cl_steps };
@@ -561,7 +551,6 @@ struct ResBranchParams {
     int mask_shift = -1;
     int halo = 0;               // set by launch_resbranch: sum over the steps of (dil + 1) * (k - 1) / 2
     int nt_store = 0;           // set by launch_resbranch
-    unsigned long long* stamps = nullptr;      // diagnostics: 16 per workgroup (sbv2_debug_resbranch_clock)
 };
 bool resbranch_usable(const ResBranchParams& p);
 void launch_resbranch(const ResBranchParams& p, hipStream_t stream);

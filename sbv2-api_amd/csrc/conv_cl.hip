@@ -63,18 +63,14 @@ struct ClKernelParams {
     int mask_shift;
     int aux_off;      // LDS offset of the staged bias / mask bytes (channels-last epilogue), 0 = not staged
     int mask_nshift;  // mask index of position n * out_stride + phase offset == n >> mask_nshift (power-of-two strides)
-    unsigned long long* stamps;   // diagnostics only (sbv2_debug_conv_cl_clock): per workgroup {s_memtime, s_memrealtime} before / after the chunk loop
 };
 
 // WM = 2: eight waves; waves 0-3 and 4-7 compute two DIFFERENT row groups (TM * 32 rows each) over the SAME 256 positions, so the activation
 // window of a position tile is fetched, converted and written to LDS once for 2 * TM * 32 output rows instead of once per TM * 32.
-// ABL (diagnostic builds only, never launched by the product path): 0 = the kernel; 1 = no MFMAs (fragments still read); 2 = MFMAs only (no
-// staging, no fragment reads inside the loop); 3 = staging + barriers only.  Used with the clock stamps to tell a scheduling bound from
-// a clock (power) bound: MI355X_MICROARCH.md "DVFS give-back" item 6.
-template <int TM, int PREC, bool IN_KM, bool OUT_KM, int WM, int ABL = 0>
+// YS: the channels-last epilogue also writes the result's bf16 parts (ConvClParams::ys_p): the transposed convs of the wide stages.
+template <int TM, int PREC, bool IN_KM, bool OUT_KM, int WM, bool YS = false>
 __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernelParams kp) {
     constexpr int kT = kClThreads * WM;
-    constexpr bool YS = ABL == 20;   // the channels-last epilogue also writes the result's bf16 parts (ConvClParams::ys_p): the transposed convs of the wide stages
     constexpr bool SPLIT = PREC == PREC_BF16X3;
     using elem_t = std::conditional_t<PREC == PREC_F16, _Float16, __bf16>;
     using ex8 = std::conditional_t<PREC == PREC_F16, f16x8, bf16x8>;
@@ -274,14 +270,9 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
     __syncthreads();
 
     const int lcol = lane & 31, lh = lane >> 5;
-    unsigned long long st_t0 = 0, st_r0 = 0;
-    if (kp.stamps) {
-        st_t0 = __builtin_amdgcn_s_memtime();
-        st_r0 = __builtin_amdgcn_s_memrealtime();
-    }
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         const bool more = chunk + 1 < nchunks;
-        if (more && ABL != 2) {
+        if (more) {
             load_w(chunk + 1);
             if (IN_KM) load_xk(chunk + 1);
             else if (((chunk + 1) & 1) == 0) load_x(chunk + 1);
@@ -309,13 +300,6 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
             }
         };
         auto mfma_frags = [&](const Frags& f) {
-            if (ABL == 1 || ABL == 3) {   // keep the fragments live, issue nothing
-#pragma unroll
-                for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(f.ah[i]), "v"(f.al[i]));
-#pragma unroll
-                for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(f.bh[j]), "v"(f.bl[j]));
-                return;
-            }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -328,17 +312,6 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
                 }
         };
         Frags fa, fb;
-        if (ABL == 2 || ABL == 3) {   // fragments read once per chunk (ABL 2: MFMA stream only; ABL 3: nothing but staging)
-            if (ABL == 2 || chunk == 0) {
-                load_frags(fa, 0);
-                load_frags(fb, 0);
-            }
-            if (ABL == 2)
-                for (int tap = 0; tap < ntaps; tap += 2) {
-                    mfma_frags(fa);
-                    if (tap + 1 < ntaps) mfma_frags(fb);
-                }
-        } else {
         load_frags(fa, 0);
         int tap = 0;
         for (; tap + 2 <= ntaps; tap += 2) {
@@ -348,19 +321,13 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
             mfma_frags(fb);
         }
         if (tap < ntaps) mfma_frags(fa);
-        }
-        if (ABL != 2) __syncthreads();   // every wave is done reading this chunk's tiles
-        if (more && ABL != 2) {
+        __syncthreads();   // every wave is done reading this chunk's tiles
+        if (more) {
             xchunk = chunk + 1;
             store_w();
             if (IN_KM) store_xk(); else store_x();
         }
-        if (ABL != 2) __syncthreads();
-    }
-    if (kp.stamps && tid == 0) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        unsigned long long* o = kp.stamps + (size_t)blockIdx.x * 4;
-        o[0] = st_t0; o[1] = st_r0; o[2] = t1; o[3] = r1;
+        __syncthreads();
     }
 
     // ---- epilogue ------------------------------------------------------------------------------------------------------------
@@ -524,7 +491,7 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
                     if (!p.mask[mi]) v = make_float4(0.f, 0.f, 0.f, 0.f);
                 }
                 *reinterpret_cast<float4*>(yp) = v;
-                if (YS && p.ys_p) {   // (uniform; compiled into the ABL = 20 instantiation only: in every kernel of the family it cost 40 registers) bf16 parts of lrelu(result): 4 channels = 8 bytes of a 32-byte row of chunk co >> 4; the lo plane follows the hi plane
+                if (YS && p.ys_p) {   // (uniform; compiled into the YS instantiation only: in every kernel of the family it cost 40 registers) bf16 parts of lrelu(result): 4 channels = 8 bytes of a 32-byte row of chunk co >> 4; the lo plane follows the hi plane
                     typedef __bf16 cl_bf16x4 __attribute__((ext_vector_type(4)));
                     const float vv[4] = {v.x, v.y, v.z, v.w};
                     cl_bf16x4 h, l;
@@ -578,7 +545,7 @@ static void launch_cl(ClKernelParams kp, hipStream_t stream) {
     allow_full_lds(reinterpret_cast<const void*>(kern), lds_allowed);
     if constexpr (SPLIT && !IN_KM && !OUT_KM && TM == 2) {
         if (p.ys_p) {
-            kern = conv_cl_kernel<TM, PREC, IN_KM, OUT_KM, WM, 20>;
+            kern = conv_cl_kernel<TM, PREC, IN_KM, OUT_KM, WM, true>;
             static std::atomic<uint64_t> lds_allowed_ys{0};
             allow_full_lds(reinterpret_cast<const void*>(kern), lds_allowed_ys);
         }
@@ -648,7 +615,6 @@ void launch_conv_cl(const ConvClParams& p, hipStream_t stream) {
     kp.sh_step = p.ntaps > 1 ? p.shift[1] - p.shift[0] : 0;
     for (int t = 1; t < p.ntaps; ++t) SBV2_REQUIRE(p.shift[t] - p.shift[t - 1] == kp.sh_step, "conv_cl: tap shifts must be an arithmetic progression");
     kp.nmt = p.nmt;
-    kp.stamps = nullptr;
     kp.mask_shift = -1;
     if (p.mask && p.mask_div > 0 && (p.mask_div & (p.mask_div - 1)) == 0) {
         int s = 0;
@@ -682,45 +648,6 @@ bool conv_cl_parts_ok(const ConvClParams& p) {
     if (!p.split || p.f16 || p.in_km || p.out_km || p.tm != 2 || p.N <= 0) return false;
     const int64_t tiles = (p.N + kClNT - 1) / kClNT;
     return tiles * std::max(1, p.nmt / 2) >= small_grid_max() && tiles * (p.nmt / 2) >= 128;
-}
-
-// Diagnostic launch of the dominant configuration (128-row workgroups, split-bf16, channels-last in and out) with an ablation variant and
-// the clock stamps: stamps[4 * workgroup] = {s_memtime, s_memrealtime} before, {..} after the chunk loop.  Results of abl != 0 are garbage.
-void launch_conv_cl_diag(const ConvClParams& p, int abl, unsigned long long* stamps, hipStream_t stream) {
-    SBV2_REQUIRE(p.split && !p.in_km && !p.out_km && p.tm == 2 && (p.nmt & 3) == 0, "conv_cl diag: the 128-row split-bf16 configuration only");
-    ClKernelParams kp;
-    kp.p = p;
-    int smin = p.shift[0], smax = p.shift[0];
-    for (int t = 1; t < p.ntaps; ++t) {
-        smin = std::min(smin, p.shift[t]);
-        smax = std::max(smax, p.shift[t]);
-    }
-    kp.wshift0 = smin;
-    kp.xrows = kClNT + (smax - smin);
-    kp.sh0 = p.shift[0] - kp.wshift0;
-    kp.sh_step = p.ntaps > 1 ? p.shift[1] - p.shift[0] : 0;
-    kp.nmt = p.nmt;
-    kp.mask_shift = -1;
-    kp.stamps = stamps;
-    kp.wbytes = p.ntaps * 2 * 2 * 2 * 1024;
-    size_t lds = std::max<size_t>((size_t)kp.wbytes + (size_t)kp.xrows * 32 * 2, 4 * 2 * 64 * 36 * sizeof(float));
-    lds = (lds + 15) / 16 * 16;
-    kp.aux_off = (int)lds;
-    kp.mask_nshift = 0;
-    lds += 128 * sizeof(float) + kClNT;
-    const int ntx = round_up((p.N + kClNT - 1) / kClNT, 8);
-    dim3 grid(ntx * (kp.nmt / 4));
-    auto go = [&](auto kern) {
-        static std::atomic<uint64_t> lds_allowed{0};
-        (void)lds_allowed;
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(kern, grid, dim3(kClThreads * 2), lds, stream, kp);
-        HIP_CHECK(hipGetLastError());
-    };
-    if (abl == 0) go(conv_cl_kernel<2, PREC_BF16X3, false, false, 2, 0>);
-    else if (abl == 1) go(conv_cl_kernel<2, PREC_BF16X3, false, false, 2, 1>);
-    else if (abl == 2) go(conv_cl_kernel<2, PREC_BF16X3, false, false, 2, 2>);
-    else go(conv_cl_kernel<2, PREC_BF16X3, false, false, 2, 3>);
 }
 
 }  // namespace sbv2

@@ -12,7 +12,7 @@
 //     step and the DMAs dealt BETWEEN them.  Waves 0, 1 issue the weight DMAs, waves 2, 3 the window DMAs (vmcnt is per wave and in order: a wave that
 //     issued both kinds would have to wait for young window pieces to reach an old weight block).
 //
-// Round 5: v_mfma_f32_16x16x32_bf16 instead of 32x32x16.  These launches are POWER bound: the timeline of a workgroup's life (sbv2_debug_clx_timeline,
+// Round 5: v_mfma_f32_16x16x32_bf16 instead of 32x32x16.  These launches are POWER bound: the clock-stamp timeline of a workgroup's life (since removed,
 // profiles/r05*_clx_timeline*.jsonl) shows the chip trading clock for every cycle a denser schedule saves (epilogue 30 -> 20 us: launch -2 %, loop clock
 // 1.70 -> 1.61 GHz, aggregate MFMA rate unchanged), and a probe build of this loop that issued the same FLOP from the same fragment registers as 16x16x32
 // instructions ran 11-12.5 % faster at k = 7 / 11 (profiles/r05d_clx_shape_probe.jsonl; MI355X_MICROARCH.md, DVFS give-back item 7: 1.12-1.14x).
@@ -118,7 +118,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
 
-    const unsigned long long st_entry = p.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;   // (diagnostics only)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wq = wave;
@@ -253,11 +252,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
         pend.bh[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
 
-    unsigned long long st_t0 = 0, st_r0 = 0;
-    if (p.stamps) {
-        st_t0 = __builtin_amdgcn_s_memtime();
-        st_r0 = __builtin_amdgcn_s_memrealtime();
-    }
     for (int chunk = 0; chunk < nchunks; chunk += 2) {
         const int s0 = chunk * NTAPS;
         clx_static_for<0, NTAPS>([&](auto jc) {
@@ -336,17 +330,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
     keep4(pend.ah);
     keep4(pend.bh);
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // (the accumulators are read by LDS writes next; the compiler does not see these MFMAs)
-    if (p.stamps && tid == 0) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        unsigned long long* o = p.stamps + (size_t)blockIdx.x * kClxStampWords;
-        o[0] = st_t0; o[1] = st_r0; o[2] = t1; o[3] = r1;
-        o[4] = st_entry;
-        // where this workgroup ran: HW_ID (wave / SIMD / CU / SH / SE) and XCC_ID
-        o[7] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);
-    }
     __syncthreads();   // the epilogue re-uses the rings as its transpose tiles
-    unsigned long long st_e0 = 0, st_e1 = 0, st_e2 = 0;   // (diagnostics) behind the barrier / mask + bias + residual rows arrived / first half's stores issued
-    if (p.stamps) st_e0 = __builtin_amdgcn_s_memrealtime();
 
     // accumulator tile [it][jt]: lane (column l16 = position 16 jt + l16 of the wave's 64, row group lg) holds rows 16 it + 4 lg .. + 3
     // ---- k-major result (the flow's second FFN convolution: Y[m][n] = (conv + b + R[m][n]) * mask): one accumulator register of a 16-lane group is 16
@@ -480,10 +464,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
                 const unsigned long long bal = __builtin_amdgcn_ballot_w64(mv != 0);
                 allkeep = bal == ~0ull;
                 mbits = (unsigned)(bal >> ((lane >> 2) * 4)) & 0xFu;
-                if (p.stamps) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    st_e1 = __builtin_amdgcn_s_memrealtime();
-                }
             }
             const int m = m0 + i * 32 + c8;
             if constexpr (i == 1) {
@@ -553,18 +533,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
                     }
                 }
             }
-            if constexpr (i == 0) {
-                if (p.stamps) st_e2 = __builtin_amdgcn_s_memrealtime();
-            }
             __builtin_amdgcn_sched_barrier(0);
         });
-        if (p.stamps && tid == 0) {   // (diagnostics) last store issued / every store of this wave acknowledged
-            unsigned long long* o = p.stamps + (size_t)blockIdx.x * kClxStampWords;
-            o[8] = st_e0; o[9] = st_e1; o[10] = st_e2;
-            o[5] = __builtin_amdgcn_s_memrealtime();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            o[6] = __builtin_amdgcn_s_memrealtime();
-        }
         return;
     }
     // ---- the batch's last position tile: the same arithmetic with clamped reads and guarded stores, one row at a time (a handful of workgroups per launch)

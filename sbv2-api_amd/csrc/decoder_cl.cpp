@@ -211,13 +211,17 @@ ClUpX build_upx(WeightStore& ws, const float* wt, const float* ub, int cin, int 
 // pack_cl's precision code of a decoder arithmetic (dec_mode_ / ClStage::mode)
 static int cl_parts_of(int mode) { return mode == 1 ? 2 : (mode == 2 ? 1 : 3); }
 
+ClConv pack_decoder_conv(WeightStore& ws, const float* w, int M, int K, int k, int mode, const float* bias) {
+    ClConv c = pack_cl(ws, w, M, K, k, cl_parts_of(mode), bias);
+    if (mode == 1 && M == 16 && K == 16) c.wp = pack_cl_pairs(ws, w, k);
+    return c;
+}
+
 void VitsModel::load_decoder_cl(const Blob& blob) {
     auto conv = [&](const std::string& prefix, int mode) {
         const HostTensor& t = blob.get(prefix + ".weight");
         const float* b = blob.has(prefix + ".bias") ? blob.get(prefix + ".bias").data : nullptr;
-        ClConv c = pack_cl(*ws_, t.data, (int)t.dims[0], (int)t.dims[1], (int)t.dims[2], cl_parts_of(mode), b);
-        if (mode == 1 && t.dims[0] == 16 && t.dims[1] == 16) c.wp = pack_cl_pairs(*ws_, t.data, (int)t.dims[2]);
-        return c;
+        return pack_decoder_conv(*ws_, t.data, (int)t.dims[0], (int)t.dims[1], (int)t.dims[2], mode, b);
     };
     // SBV2_DECODER_STAGES = one arithmetic per upsampling stage ("f16,f16,bf16x3,bf16x3,bf16x3"): the per-stage precision map of profiles/r05_precision_map.json.
     // An experiment knob: the default is SBV2_DECODER's arithmetic for every stage.
@@ -324,8 +328,8 @@ int set_respair_clx(int on) { return set_knob(g_rpx, on, 1); }
 static bool clx_size_ok(int mode, int64_t tiles, int64_t min_tiles) { return mode == 2 || (mode == 1 && tiles >= min_tiles); }
 bool clx_wanted(int64_t tiles, int64_t min_tiles) { return clx_size_ok(read_knob(g_clx, "SBV2_CLX must be 0, 1 or 2"), tiles, min_tiles); }
 
-void VitsModel::conv_cl(const ClConv& c, const float* X, int ldx, int NB, float* Y, int ldy, int N, int dil, int pad_l,
-                        const unsigned char* mask, int mask_div, float pre_slope, const float* R, int ldr, float beta, int accumulate) {
+ConvClParams conv_cl_params(const ClConv& c, const float* X, int ldx, int NB, float* Y, int ldy, int N, int dil, int pad_l, const unsigned char* mask,
+                            int mask_div, float pre_slope, const float* R, int ldr, float beta, int accumulate) {
     ConvClParams p;
     p.X = X;
     p.ldx = ldx;
@@ -350,12 +354,16 @@ void VitsModel::conv_cl(const ClConv& c, const float* X, int ldx, int NB, float*
     p.accumulate = accumulate;
     p.mask = mask;
     p.mask_div = mask_div;
-    launch_conv_cl(p, stream_);
+    return p;
 }
 
-// The operands of a fused ResBlock branch (resbranch_clx.hip); X, Y, beta and accumulate are the caller's
-static ResBranchParams branch_params(const std::vector<ClConv>& c1, const std::vector<ClConv>& c2, const std::vector<int>& dil, int k, int C, int64_t N,
-                                     const unsigned char* mask, int mask_shift) {
+void VitsModel::conv_cl(const ClConv& c, const float* X, int ldx, int NB, float* Y, int ldy, int N, int dil, int pad_l,
+                        const unsigned char* mask, int mask_div, float pre_slope, const float* R, int ldr, float beta, int accumulate) {
+    launch_conv_cl(conv_cl_params(c, X, ldx, NB, Y, ldy, N, dil, pad_l, mask, mask_div, pre_slope, R, ldr, beta, accumulate), stream_);
+}
+
+ResBranchParams branch_params(const std::vector<ClConv>& c1, const std::vector<ClConv>& c2, const std::vector<int>& dil, int k, int C, int64_t N,
+                              const unsigned char* mask, int mask_shift) {
     ResBranchParams bp;
     for (int q = 0; q < kResBranchSteps; ++q) {
         bp.W[2 * q] = C == 16 ? c1[q].wp : c1[q].w;
@@ -372,8 +380,7 @@ static ResBranchParams branch_params(const std::vector<ClConv>& c1, const std::v
     return bp;
 }
 
-// The operands of one fused ResBlock step (respair_*.hip); X, Y, beta and accumulate are the caller's
-static ResPairParams step_params(const ClConv& c1, const ClConv& c2, int k, int dil, int mode, int C, int64_t N, const unsigned char* mask, int U, int ushift) {
+ResPairParams step_params(const ClConv& c1, const ClConv& c2, int k, int dil, int mode, int C, int64_t N, const unsigned char* mask, int U, int ushift) {
     ResPairParams rp;
     rp.W1 = c1.w;
     rp.W2 = c2.w;

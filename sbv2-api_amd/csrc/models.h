@@ -78,6 +78,16 @@ struct ClUpX {
 ClUpX build_upx(WeightStore& ws, const float* wt, const float* ub, int cin, int cout, int k, int s, bool parts_out);
 void* pack_step_pairs(WeightStore& ws, const float* w, int C, int k);   // w [C][C][k], C in {32, 64} -> step-pair fragments (split-bf16) for respair_x16.hip
 void* pack_cl_pairs(WeightStore& ws, const float* w, int k);   // w [16][16][k] -> tap-pair fragments (split-bf16) for respair_clx's 16-channel kernel
+// One convolution of the channels-last decoder in decoder arithmetic `mode` (1 = bf16x3, 2 = bf16, 3 = f16): pack_cl, plus pack_cl_pairs for a 16 x 16 split-bf16 conv
+ClConv pack_decoder_conv(WeightStore& ws, const float* w, int M, int K, int k, int mode, const float* bias);
+// The decoder's launch parameters (decoder_cl.cpp), shared with the test hooks.  A conv_cl launch of c: tap t reads position n + t * dil - pad_l
+ConvClParams conv_cl_params(const ClConv& c, const float* X, int ldx, int NB, float* Y, int ldy, int N, int dil, int pad_l, const unsigned char* mask,
+                            int mask_div, float pre_slope, const float* R, int ldr, float beta, int accumulate);
+// The operands of one fused ResBlock step (respair_*.hip); X, Y, beta and accumulate are the caller's
+ResPairParams step_params(const ClConv& c1, const ClConv& c2, int k, int dil, int mode, int C, int64_t N, const unsigned char* mask, int U, int ushift);
+// The operands of a fused ResBlock branch (resbranch_clx.hip); X, Y, beta and accumulate are the caller's
+ResBranchParams branch_params(const std::vector<ClConv>& c1, const std::vector<ClConv>& c2, const std::vector<int>& dil, int k, int C, int64_t N,
+                              const unsigned char* mask, int mask_shift);
 // w is [M][K] (Linear / 1x1 conv): bf16 parts (2 = hi + lo, 3 = hi + mid + lo) as MFMA A fragments; K must be a multiple of 16
 BfsWeights pack_bfs(WeightStore& ws, const float* w, int M, int K, int parts);
 

@@ -112,29 +112,16 @@ struct RbCfg {
     static constexpr int NTOT = NS * NSEQ;             // ... of the branch
 };
 
-// DG >= 0: diagnostic instantiation (phase stamps of thread 0 into p.stamps[16 per workgroup]; sbv2_debug_resbranch_clock)
-template <int C, int NTAPS, int WNP, int GT, int NBUFP, int DG>
+template <int C, int NTAPS, int WNP, int GT, int NBUFP>
 __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__((amdgpu_waves_per_eu(3))) void resbranch_clx_kernel(const ResBranchParams p) {
     using K = RbCfg<C, NTAPS, WNP, GT, NBUFP>;
     constexpr int T = K::T, NW = K::NW, WN = K::WN, RB = K::RB, R = K::R, NS = K::NS, MARG = K::MARG;
-    constexpr bool DIAG = DG >= 0;
     constexpr int NCH = K::NCH, NMT = K::NMT, G = K::G, NG = K::NG, NXC = K::NXC, NTW = K::NTW, NBUF = K::NBUF, NSEQ = K::NSEQ, NTOT = K::NTOT;
     constexpr bool TWOTAP = K::TWOTAP;
     constexpr int NQ = 4;                              // 4-row groups of a 32 x 32 accumulator tile
     constexpr int h2 = (NTAPS - 1) / 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
-
-    unsigned st_[16];
-    auto stamp = [&](int i) __attribute__((always_inline)) {
-        if constexpr (DIAG) st_[i] = (unsigned)(i >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime());
-    };
-    if constexpr (DIAG) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) st_[i] = 0;
-    }
-    stamp(0);
-    stamp(14);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -279,7 +266,6 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
         if (interior) convert_all(std::false_type{});
         else convert_all(std::true_type{});
     }
-    stamp(1);
 
     // ---- fragments (respair_clx.hip).  C >= 32: v_mfma_f32_32x32x16_bf16, a wave owns 32 channels x 64 rows.  C = 16: v_mfma_f32_16x16x32_bf16 whose 32-deep K
     // carries TWO taps x 16 channels (weights packed as tap pairs, pack_cl_pairs; the lanes of k groups 2, 3 read the window one tap further), 16 channels x 64
@@ -538,7 +524,6 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
         } else {
             emit_any(std::true_type{}, std::false_type{}, 2 * q + 1);
         }
-        stamp(2 + q);
     });
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();   // the transpose tiles overlay the weight buffers and the window
@@ -598,28 +583,20 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     };
     if (p.nt_store) store_rows(std::true_type{});
     else store_rows(std::false_type{});
-    stamp(6);
-    stamp(15);
-    if constexpr (DIAG) {
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) p.stamps[(size_t)blockIdx.x * 16 + i] = st_[i];
-        }
-    }
 }
 
-template <int C, int NTAPS, int WNP, int GT, int NBUFP, int DG>
+template <int C, int NTAPS, int WNP, int GT, int NBUFP>
 static void launch_rb(const ResBranchParams& p, hipStream_t stream) {
     using K = RbCfg<C, NTAPS, WNP, GT, NBUFP>;
     static_assert(K::LDS <= 160 * 1024, "LDS budget");
-    auto kern = resbranch_clx_kernel<C, NTAPS, WNP, GT, NBUFP, DG>;
+    auto kern = resbranch_clx_kernel<C, NTAPS, WNP, GT, NBUFP>;
     static std::atomic<uint64_t> lds_allowed{0};   // per (kernel instantiation, device)
     allow_full_lds(reinterpret_cast<const void*>(kern), lds_allowed);
     const int nto = K::R - 2 * p.halo;
     const int ntiles = (p.N + nto - 1) / nto;
     const int grid = ((ntiles + 7) >> 3) * 8;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool prof = DG < 0 && conv_prof_active();
+    const bool prof = conv_prof_active();
     if (prof) {
         HIP_CHECK(hipEventCreate(&e0));
         HIP_CHECK(hipEventCreate(&e1));
@@ -634,7 +611,7 @@ static void launch_rb(const ResBranchParams& p, hipStream_t stream) {
     }
 }
 
-// rows of the window of the instance launch_rb_any picks (0: none)
+// rows of the window of the instance launch_resbranch picks (0: none)
 static int rb_rows(int C, int k) {
     if (k == 3) return C == 128 ? 192 : (C == 64 ? 384 : ((C == 32 || C == 16) ? 256 : 0));
     if (C == 16 && (k == 7 || k == 11)) return 512;
@@ -653,8 +630,13 @@ bool resbranch_usable(const ResBranchParams& p) {
     return halo * 4 <= R;   // (leaves >= half of the window as output)
 }
 
-template <int DG>
-static void launch_rb_any(const ResBranchParams& p, hipStream_t stream) {
+// p.mask_shift must be set by the caller (mask_div = 1 << mask_shift)
+void launch_resbranch(const ResBranchParams& p0, hipStream_t stream) {
+    SBV2_REQUIRE(resbranch_usable(p0), "resbranch: operands do not fit the kernel");
+    ResBranchParams p = p0;
+    p.halo = 0;
+    for (int q = 0; q < kResBranchSteps; ++q) p.halo += (p.dil[q] + 1) * (p.k - 1) / 2;
+    p.nt_store = (int64_t)p.N * p.C * 4 >= ((int64_t)128 << 20);
     // Window sizes / weight rings, each the best of a same-box sweep (profiles/r06c, r06l, r06m, r06n *_probe*):
     //   C = 128: 192 rows on 12 waves, a chunk's three taps per weight group, 2 ring slots: 155 KB, ONE workgroup per CU (1.84 ms per half plane; 128 rows
     //            on 8 waves 2.14-2.28; the six conv_clx launches it replaces 2.2)
@@ -672,27 +654,16 @@ static void launch_rb_any(const ResBranchParams& p, hipStream_t stream) {
     // on 512 / 768 / 1024 rows: 1.25 -> 1.15 and 1.66 -> 1.62 ms isolated at 1024 rows, equal at 512) gains nothing in the step: not instantiated.
     // (profiles/r06w_resbranch_k_probe*.jsonl, r06x_bench_resbranch_k_ab*.txt)
     if (p.k == 3) {
-        if (p.C == 128) return launch_rb<128, 3, 3, 3, 2, DG>(p, stream);
-        if (p.C == 64) return launch_rb<64, 3, 6, 3, 3, DG>(p, stream);
-        if (p.C == 32) return launch_rb<32, 3, 4, 4, 3, DG>(p, stream);
-        if (p.C == 16) return launch_rb<16, 3, 4, 4, 3, DG>(p, stream);
+        if (p.C == 128) return launch_rb<128, 3, 3, 3, 2>(p, stream);
+        if (p.C == 64) return launch_rb<64, 3, 6, 3, 3>(p, stream);
+        if (p.C == 32) return launch_rb<32, 3, 4, 4, 3>(p, stream);
+        if (p.C == 16) return launch_rb<16, 3, 4, 4, 3>(p, stream);
     } else if (p.C == 16 && p.k == 7) {
-        return launch_rb<16, 7, 8, 4, 3, DG>(p, stream);
+        return launch_rb<16, 7, 8, 4, 3>(p, stream);
     } else if (p.C == 16 && p.k == 11) {
-        return launch_rb<16, 11, 8, 6, 3, DG>(p, stream);
+        return launch_rb<16, 11, 8, 6, 3>(p, stream);
     }
     SBV2_REQUIRE(false, "resbranch: shape not instantiated");
-}
-
-// p.mask_shift must be set by the caller (mask_div = 1 << mask_shift)
-void launch_resbranch(const ResBranchParams& p0, hipStream_t stream) {
-    SBV2_REQUIRE(resbranch_usable(p0), "resbranch: operands do not fit the kernel");
-    ResBranchParams p = p0;
-    p.halo = 0;
-    for (int q = 0; q < kResBranchSteps; ++q) p.halo += (p.dil[q] + 1) * (p.k - 1) / 2;
-    p.nt_store = (int64_t)p.N * p.C * 4 >= ((int64_t)128 << 20);
-    if (p.stamps) launch_rb_any<0>(p, stream);
-    else launch_rb_any<-1>(p, stream);
 }
 
 }  // namespace sbv2

@@ -29,12 +29,6 @@
 
 #include "common.h"
 
-// RPX_PROBE16 (diagnostic builds only, tools/respair_shape_probe.sh; results WRONG): every v_mfma_f32_32x32x16_bf16 of the C >= 32 kernels issued as two
-// v_mfma_f32_16x16x32_bf16 from the same fragment registers: what the instruction shape alone is worth at the managed clock
-#ifndef RPX_PROBE16
-#define RPX_PROBE16 0
-#endif
-
 namespace sbv2 {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -115,12 +109,10 @@ struct RpxCfg {
     static constexpr int NSEQ = 2 * NCH * NG;          // weight groups of a tile, in order: (conv, chunk, group)
 };
 
-// DG >= 0: diagnostic instantiation (phase stamps of thread 0 into p.stamps[16 per workgroup]; sbv2_debug_respair_clock)
-template <int C, int NTAPS, int DG, int GT, int WNP = 0>
+template <int C, int NTAPS, int GT, int WNP = 0>
 __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdgpu_waves_per_eu(3))) void respair_clx_kernel(const ResPairParams p) {
     using K = RpxCfg<C, NTAPS, GT, WNP>;
     constexpr int T = K::T, NW = K::NW, WN = K::WN, RB = K::RB;
-    constexpr bool DIAG = DG >= 0;
     constexpr int NCH = K::NCH, NMT = K::NMT, NT = K::NT, G = K::G, NG = K::NG, NXC = K::NXC, NTW = K::NTW;
     constexpr bool TWOTAP = K::TWOTAP;
     constexpr int PAIR = NCH >= 2 ? 2 : 1;             // chunks whose 64-byte row pieces are requested together (one 128-byte line)
@@ -128,21 +120,6 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
     constexpr int h2 = (NTAPS - 1) / 2, nto = NT - 2 * h2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
-
-    unsigned st_[16];
-    auto stamp = [&](auto ic) {
-        if constexpr (DIAG) {
-            constexpr int i = decltype(ic)::value;
-            st_[i] = (unsigned)(i >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime());
-        }
-    };
-#define RPX_STAMP(i) stamp(std::integral_constant<int, i>{})
-    if constexpr (DIAG) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) st_[i] = 0;
-    }
-    RPX_STAMP(0);
-    RPX_STAMP(14);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -251,16 +228,7 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
     const unsigned b1last = b1base - (lg >> 1) * d * 16, b2last = b2base - (lg >> 1) * 16;
     f32x16 acc[TWOTAP ? 1 : 2];
     f32x4v acc4[TWOTAP ? 4 : 1];
-#if RPX_PROBE16
-    f32x4v accq[2][4];     // (shape probe: the 32x32 tiles as four 16x16x32 accumulators each; results are WRONG)
-#endif
     auto zero_acc = [&]() {
-#if RPX_PROBE16
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) accq[j][q] = f32x4v{0.f, 0.f, 0.f, 0.f};
-#endif
         if constexpr (TWOTAP) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc4[j] = f32x4v{0.f, 0.f, 0.f, 0.f};
@@ -317,39 +285,15 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
     auto mfma_one = [&](const Frags& f, auto nc) {   // term-major; per accumulator: lo*hi, hi*lo, hi*hi (conv_cl's order)
         constexpr int n = decltype(nc)::value;
         constexpr int t = n / NB_, j = n % NB_;
-#if RPX_PROBE16
-        auto& aq = accq;   // (named outside the discarded branch: the generic lambda captures it)
-#endif
         if constexpr (TWOTAP) {
             if constexpr (t == 0) acc4[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.al, f.bh[j], acc4[j], 0, 0, 0);
             else if constexpr (t == 1) acc4[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.ah, f.bl[j], acc4[j], 0, 0, 0);
             else acc4[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.ah, f.bh[j], acc4[j], 0, 0, 0);
         } else {
-#if RPX_PROBE16
-            // the same FLOP from the same fragment registers as two v_mfma_f32_16x16x32_bf16 per 32x32x16 instruction (timing only)
-            constexpr int sl = (t & 1) * 2;
-            const bf16x8& a = t == 0 ? f.al : f.ah;
-            const bf16x8& b = t == 1 ? f.bl[j] : f.bh[j];
-            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(aq[j & 1][sl]) : "v"(a), "v"(b));
-            asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(aq[j & 1][sl + 1]) : "v"(a), "v"(b));
-#else
             if constexpr (t == 0) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al, f.bh[j], acc[j], 0, 0, 0);
             else if constexpr (t == 1) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah, f.bl[j], acc[j], 0, 0, 0);
             else acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah, f.bh[j], acc[j], 0, 0, 0);
-#endif
         }
-    };
-    auto probe_fold = [&]() {   // (shape probe) the 16x16 accumulators -> the registers the epilogues read
-#if RPX_PROBE16
-        if constexpr (!TWOTAP) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[j][4 * q + e] = accq[j][q][e];
-        }
-#endif
     };
     // one weight group: its steps; the fragment reads of step t + 1 are dealt one per gap between the MFMAs of step t (a burst of reads in front of
     // the MFMAs fills the LDS command queue and leaves the matrix pipe idle while it drains)
@@ -390,7 +334,6 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
     // flight (or just landed) is served by L2.  Requested before conv2, as rounds 1-3 did, they were HBM reads again: with three 64 KB tiles per CU the
     // XCD's 4 MB L2 has turned over by then (PMC: 2.14 GB fetched per C = 32 launch for 0.94 GB of plane, profiles/r04f_pmc_hbm_traffic.csv).  Price: NIT x 4
     // registers live over the tile.
-    const bool rres_early = !p.rres_late;
     constexpr int LPR = C == 16 ? 4 : 8;               // lanes per output row of the wave's transposed tile (32 channels = 128 bytes; C = 16: 64 bytes)
     constexpr int RPI = 64 / LPR, NIT = 64 / RPI;      // rows per iteration, iterations
     const int c4 = wm * 32 + (lane % LPR) * 4, rowi = lane / LPR;
@@ -409,7 +352,7 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
             }
         }
     };
-    if (rres_early) load_rres();
+    load_rres();
     {
         // biases and the keep flags of the intermediate's rows (position inside the batch and not masked), parked in LDS for both epilogues
         const float bval = tid < 128 ? (tid < 64 ? p.b1[min(tid, C - 1)] : p.b2[min(tid - 64, C - 1)]) : 0.f;
@@ -428,7 +371,6 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
             if (tid + h * T < K::ROWS2) rpx_write_b8(lds0 + K::MASK_OFF + tid + h * T, mval[h]);
     }
     convert(std::integral_constant<int, 0>{});
-    RPX_STAMP(1);
 
     // ---- phase 1: t = lrelu(conv1(lrelu(y)) + b1) on positions [t0, t0 + NT) -> LDS ----------------------------------------------------
     zero_acc();
@@ -447,20 +389,16 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
             group_barrier(std::integral_constant<int, 0>{});
             run_group(std::integral_constant<int, 0>{});
         }
-        if constexpr (chunk == 0) RPX_STAMP(7);
         rpx_for<1, NG>([&](auto gc) {
             constexpr int s = chunk * NG + decltype(gc)::value;
             group_barrier(std::integral_constant<int, s>{});
             run_group(std::integral_constant<int, s>{});
         });
-        if constexpr (chunk == 0) RPX_STAMP(8);
     });
-    RPX_STAMP(2);
 
     // ---- intermediate: + b1, lrelu, keep flag, hi / lo -> the window conv2 reads (aliases the conv1 window: behind a barrier) -------------
     constexpr int S2 = NCH * NG;   // first group of conv2
     group_barrier(std::integral_constant<int, S2>{});
-    probe_fold();
     if constexpr (TWOTAP) {
         // accumulator tile jt: lane (column l16 = position, k group lg) holds channels 4 lg .. 4 lg + 3 of position wn * 64 + 16 jt + l16
         f32x4v bq = rpx_read_f128<0>(lds0 + K::BIAS_OFF + lg * 16);
@@ -523,13 +461,10 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
         if (allkeep) mid(std::true_type{});
         else mid(std::false_type{});
     }
-    RPX_STAMP(3);
     zero_acc();
-    if (!rres_early) load_rres();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    RPX_STAMP(4);
 
     // ---- phase 2: conv2 over the LDS-resident intermediate -----------------------------------------------------------------------------------
     run_group(std::integral_constant<int, S2>{});
@@ -537,8 +472,6 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
         group_barrier(sc);
         run_group(sc);
     });
-    RPX_STAMP(5);
-    probe_fold();
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();   // the transpose tiles overlay the weight buffers and the window
 
@@ -594,29 +527,20 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
     };
     if (p.nt_store) store_rows(std::true_type{});
     else store_rows(std::false_type{});
-    RPX_STAMP(6);
-    RPX_STAMP(15);
-    if constexpr (DIAG) {
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) p.stamps[(size_t)blockIdx.x * 16 + i] = st_[i];
-        }
-    }
-#undef RPX_STAMP
 }
 
-template <int C, int NTAPS, int DG, int GT, int WNP = 0>
+template <int C, int NTAPS, int GT, int WNP = 0>
 static void launch_rpx(const ResPairParams& p, hipStream_t stream) {
     using K = RpxCfg<C, NTAPS, GT, WNP>;
     static_assert(K::LDS <= 160 * 1024, "LDS budget");
-    auto kern = respair_clx_kernel<C, NTAPS, DG, GT, WNP>;
+    auto kern = respair_clx_kernel<C, NTAPS, GT, WNP>;
     static std::atomic<uint64_t> lds_allowed{0};   // per (kernel instantiation, device)
     allow_full_lds(reinterpret_cast<const void*>(kern), lds_allowed);
     constexpr int nto = K::NT - (NTAPS - 1);
     const int ntiles = (p.N + nto - 1) / nto;
     const int grid = ((ntiles + 7) >> 3) * 8;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool prof = DG < 0 && conv_prof_active();
+    const bool prof = conv_prof_active();
     if (prof) {
         HIP_CHECK(hipEventCreate(&e0));
         HIP_CHECK(hipEventCreate(&e1));
@@ -636,36 +560,23 @@ bool respair_clx_usable(const ResPairParams& p) {
            p.slope >= 0.f && p.slope <= 1.f && p.N >= 1 && (!p.mask || p.mask_shift >= 0);
 }
 
-template <int DG>
-static void launch_rpx_any(const ResPairParams& p, hipStream_t stream) {
-    // taps per weight group at C = 64: 2 = 52 KB of LDS, three workgroups per CU (11.75 vs 12.3 ms per step for the stage against groups of 4 / two per CU;
-    // wider tiles on 6-wave workgroups measured 20-30 % slower: profiles/HISTORY.md)
-#define RPX_CASE(CC, KK) \
-    if (p.C == CC && p.k == KK) return launch_rpx<CC, KK, DG, 4>(p, stream);
-    if (p.C == 64) {
-        if (p.k == 3) return launch_rpx<64, 3, DG, 2>(p, stream);
-        if (p.k == 7) return launch_rpx<64, 7, DG, 2>(p, stream);
-        if (p.k == 11) return launch_rpx<64, 11, DG, 2>(p, stream);
-    }
-    RPX_CASE(16, 3) RPX_CASE(16, 7) RPX_CASE(16, 11) RPX_CASE(32, 3) RPX_CASE(32, 7) RPX_CASE(32, 11)
-#undef RPX_CASE
-    SBV2_REQUIRE(false, "respair_clx: shape not instantiated");
-}
-
 // p.mask_shift must be set
 void launch_respair_clx(const ResPairParams& p0, hipStream_t stream) {
     SBV2_REQUIRE(respair_clx_usable(p0), "respair_clx: operands do not fit the kernel");
     ResPairParams p = p0;
-    p.rres_late = 0;
     p.nt_store = (int64_t)p.N * p.C * 4 >= ((int64_t)128 << 20);
-    launch_rpx_any<-1>(p, stream);
-}
-void launch_respair_clx_diag(const ResPairParams& p0, hipStream_t stream) {
-    ResPairParams p = p0;
-    p.mask_shift = 0;
-    while (p.mask && (1 << p.mask_shift) < p.mask_div) ++p.mask_shift;
-    SBV2_REQUIRE(respair_clx_usable(p) && p.stamps, "respair_clx diag: operands do not fit the kernel");
-    launch_rpx_any<0>(p, stream);
+    // taps per weight group at C = 64: 2 = 52 KB of LDS, three workgroups per CU (11.75 vs 12.3 ms per step for the stage against groups of 4 / two per CU;
+    // wider tiles on 6-wave workgroups measured 20-30 % slower: profiles/HISTORY.md)
+#define RPX_CASE(CC, KK) \
+    if (p.C == CC && p.k == KK) return launch_rpx<CC, KK, 4>(p, stream);
+    if (p.C == 64) {
+        if (p.k == 3) return launch_rpx<64, 3, 2>(p, stream);
+        if (p.k == 7) return launch_rpx<64, 7, 2>(p, stream);
+        if (p.k == 11) return launch_rpx<64, 11, 2>(p, stream);
+    }
+    RPX_CASE(16, 3) RPX_CASE(16, 7) RPX_CASE(16, 11) RPX_CASE(32, 3) RPX_CASE(32, 7) RPX_CASE(32, 11)
+#undef RPX_CASE
+    SBV2_REQUIRE(false, "respair_clx: shape not instantiated");
 }
 
 }  // namespace sbv2

@@ -4,7 +4,7 @@
 //     y' = beta * ( conv2( lrelu( conv1( lrelu(y), dilation d ) + b1 ) ) + b2 + y )  [+ previous contents]  (then column mask)
 //
 // Why: these launches run at a power-managed clock, and a probe build of respair_clx.hip that issued every 32x32x16 MFMA as two 16x16x32 instructions from the
-// same registers (wrong results, -DRPX_PROBE16=1) ran 7.5 / 12.6 % faster at C = 64, k = 7 / 11 and 6 / 9.5 % at C = 32 (profiles/r06z_respair_shape_probe.jsonl):
+// same registers (wrong results; the probe build is gone) ran 7.5 / 12.6 % faster at C = 64, k = 7 / 11 and 6 / 9.5 % at C = 32 (profiles/r06z_respair_shape_probe.jsonl):
 // // half the accumulator traffic per FLOP.  The 32-deep K dimension carries a PAIR of consecutive steps a, b (step = one tap of one 16-channel chunk), as the
 // 16-channel kernel of respair_clx.hip carries two taps:
 //     A_part = [W_part(a) | W_part(b)] (k groups 0, 1 | 2, 3; packed at load: pack_step_pairs),   B_part = [X_part(a) ; X_part(b)] (k groups 0, 1 read step a's
@@ -153,30 +153,13 @@ struct X6Cfg {
     static_assert(T == 256 && (NTAPS & 1) == 1 && NPC % NW == 0, "4 waves, odd kernel sizes");
 };
 
-// DG >= 0: diagnostic instantiation (phase stamps of thread 0 into p.stamps[16 per workgroup]; sbv2_debug_respair_clock)
-template <int C, int NTAPS, int DG>
+template <int C, int NTAPS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void respair_x16_kernel(const ResPairParams p) {
     using K = X6Cfg<C, NTAPS>;
     constexpr int T = K::T, WN = K::WN, RB = K::RB, NMT = K::NMT, NT = K::NT, NXC = K::NXC, NCP = K::NCP, NP1 = K::NP1, NP2 = K::NP2;
-    constexpr bool DIAG = DG >= 0;
     constexpr int h2 = (NTAPS - 1) / 2, nto = NT - 2 * h2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
-
-    unsigned st_[16];
-    auto stamp = [&](auto ic) __attribute__((always_inline)) {
-        if constexpr (DIAG) {
-            constexpr int i = decltype(ic)::value;
-            st_[i] = (unsigned)(i >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime());
-        }
-    };
-#define X6_STAMP(i) stamp(std::integral_constant<int, i>{})
-    if constexpr (DIAG) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) st_[i] = 0;
-    }
-    X6_STAMP(0);
-    X6_STAMP(14);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -322,7 +305,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
 #pragma unroll
         for (int i = 0; i < NXC; ++i) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(rx[0][c][i]) : "n"(NYOUNG0));
     convert(std::integral_constant<int, 0>{});
-    X6_STAMP(1);
 
     // ---- fragment addresses.  A: 1 KB block (row tile 2 wm + r, part) of the pair in slot s: immediate.  B: lane (column l16, k group lg): k groups 0, 1 read
     // step a's row, 2, 3 step b's; 16-byte half lg & 1 of the 32-byte row; the lo plane is an immediate further.  The two steps of a pair are one tap apart,
@@ -475,17 +457,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (blk == 1) X6_STAMP(8);
         pair_body(std::integral_constant<int, u0>{}, std::false_type{});
-        if constexpr (blk == 0) X6_STAMP(9);
         x6_for<1, NTAPS>([&](auto pc) __attribute__((always_inline)) {
             constexpr int u = u0 + decltype(pc)::value;
             pair_barrier(std::integral_constant<int, u>{});
             pair_body(std::integral_constant<int, u>{}, std::true_type{});
         });
-        if constexpr (blk == 0) X6_STAMP(7);
     });
-    X6_STAMP(2);
 
     // ---- intermediate: + b1, lrelu, keep flag, hi / lo -> the window conv2 reads (aliases the conv1 window: behind a barrier) -------------
     pair_barrier(std::integral_constant<int, NP1>{});
@@ -523,12 +501,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
         if (allkeep) mid(std::true_type{});
         else mid(std::false_type{});
     }
-    X6_STAMP(3);
     zero_acc();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    X6_STAMP(4);
 
     // ---- phase 2: conv2 over the LDS-resident intermediate -----------------------------------------------------------------------------------
     pair_body(std::integral_constant<int, NP1>{}, std::false_type{});
@@ -536,7 +512,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
         pair_barrier(uc);
         pair_body(uc, std::true_type{});
     });
-    X6_STAMP(5);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();   // the transpose tiles overlay the weight buffers and the window
     flush_m2(std::integral_constant<int, NP1 + NP2 - 1>{});
@@ -583,29 +558,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     };
     if (p.nt_store) store_rows(std::true_type{});
     else store_rows(std::false_type{});
-    X6_STAMP(6);
-    X6_STAMP(15);
-    if constexpr (DIAG) {
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) p.stamps[(size_t)blockIdx.x * 16 + i] = st_[i];
-        }
-    }
-#undef X6_STAMP
 }
 
-template <int C, int NTAPS, int DG>
+template <int C, int NTAPS>
 static void launch_x6(const ResPairParams& p, hipStream_t stream) {
     using K = X6Cfg<C, NTAPS>;
     static_assert(K::LDS * 3 <= 160 * 1024, "three workgroups per CU");
-    auto kern = respair_x16_kernel<C, NTAPS, DG>;
+    auto kern = respair_x16_kernel<C, NTAPS>;
     static std::atomic<uint64_t> lds_allowed{0};   // per (kernel instantiation, device)
     allow_full_lds(reinterpret_cast<const void*>(kern), lds_allowed);
     constexpr int nto = K::NT - (NTAPS - 1);
     const int ntiles = (p.N + nto - 1) / nto;
     const int grid = ((ntiles + 7) >> 3) * 8;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool prof = DG < 0 && conv_prof_active();
+    const bool prof = conv_prof_active();
     if (prof) {
         HIP_CHECK(hipEventCreate(&e0));
         HIP_CHECK(hipEventCreate(&e1));
@@ -625,24 +591,15 @@ bool respair_x16_usable(const ResPairParams& p) {
            p.slope <= 1.f && p.N >= 1 && (!p.mask || p.mask_shift >= 0);
 }
 
-template <int DG>
-static void launch_x6_any(const ResPairParams& p, hipStream_t stream) {
-    if (p.C == 64 && p.k == 7) return launch_x6<64, 7, DG>(p, stream);
-    if (p.C == 64 && p.k == 11) return launch_x6<64, 11, DG>(p, stream);
-    if (p.C == 32 && p.k == 7) return launch_x6<32, 7, DG>(p, stream);
-    if (p.C == 32 && p.k == 11) return launch_x6<32, 11, DG>(p, stream);
-    SBV2_REQUIRE(false, "respair_x16: shape not instantiated");
-}
-
 void launch_respair_x16(const ResPairParams& p0, hipStream_t stream) {
     SBV2_REQUIRE(respair_x16_usable(p0), "respair_x16: operands do not fit the kernel");
     ResPairParams p = p0;
     p.nt_store = (int64_t)p.N * p.C * 4 >= ((int64_t)128 << 20);
-    launch_x6_any<-1>(p, stream);
-}
-void launch_respair_x16_diag(const ResPairParams& p, hipStream_t stream) {
-    SBV2_REQUIRE(respair_x16_usable(p) && p.stamps, "respair_x16 diag: operands do not fit the kernel");
-    launch_x6_any<0>(p, stream);
+    if (p.C == 64 && p.k == 7) return launch_x6<64, 7>(p, stream);
+    if (p.C == 64 && p.k == 11) return launch_x6<64, 11>(p, stream);
+    if (p.C == 32 && p.k == 7) return launch_x6<32, 7>(p, stream);
+    if (p.C == 32 && p.k == 11) return launch_x6<32, 11>(p, stream);
+    SBV2_REQUIRE(false, "respair_x16: shape not instantiated");
 }
 
 }  // namespace sbv2

@@ -1,0 +1,558 @@
+// The test hooks of libsbv2_hip.so (the sbv2_debug_* entry points of include/sbv2_hip.h): one kernel or launcher at a time on host data, for the tests
+// and the probe tools.  The decoder's kernels get their parameters from the decoder's own builders (decoder_cl.cpp: pack_decoder_conv, conv_cl_params,
+// step_params, branch_params), so a test of a kernel also tests what the decoder launches.
+#include <cstring>
+
+#include "api_internal.h"
+
+namespace {
+
+// Device memory, freed on scope exit (at least 16 bytes, so that an empty operand is still a valid address)
+struct DevMem {
+    void* p = nullptr;
+    explicit DevMem(size_t bytes) { HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
+    DevMem(const void* src, size_t bytes) : DevMem(bytes) {
+        if (bytes) HIP_CHECK(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+    }
+    ~DevMem() { (void)hipFree(p); }
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    float* f() const { return static_cast<float*>(p); }
+    unsigned char* u8() const { return static_cast<unsigned char*>(p); }
+};
+
+Blob one_conv_blob(const float* w, const float* bias, std::vector<int64_t> dims, int64_t nbias) {
+    Blob b;
+    b.kind = 0;
+    HostTensor t;
+    t.dims = std::move(dims);
+    t.data = w;
+    b.tensors.emplace("c.weight", t);
+    if (bias) {
+        HostTensor tb;
+        tb.dims = {nbias};
+        tb.data = bias;
+        b.tensors.emplace("c.bias", tb);
+    }
+    return b;
+}
+
+// Average milliseconds of one run() over `iters` back-to-back runs on the null stream
+template <class F>
+float time_ms(int64_t iters, F&& run) {
+    struct Event {
+        hipEvent_t e = nullptr;
+        Event() { HIP_CHECK(hipEventCreate(&e)); }
+        ~Event() { (void)hipEventDestroy(e); }
+    } e0, e1;
+    HIP_CHECK(hipEventRecord(e0.e, nullptr));
+    for (int64_t i = 0; i < iters; ++i) run();
+    HIP_CHECK(hipEventRecord(e1.e, nullptr));
+    HIP_CHECK(hipEventSynchronize(e1.e));
+    float t = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&t, e0.e, e1.e));
+    return t / (float)iters;
+}
+
+// A channel-major host plane x [C][L] as a channels-last device plane [L][C], and back
+DevMem upload_cl(const float* x, int64_t C, int64_t L) {
+    std::vector<float> t((size_t)L * C);
+    for (int64_t c = 0; c < C; ++c)
+        for (int64_t n = 0; n < L; ++n) t[(size_t)n * C + c] = x[(size_t)c * L + n];
+    return DevMem(t.data(), sizeof(float) * t.size());
+}
+void download_cl(const float* d, int64_t C, int64_t L, float* y) {
+    std::vector<float> t((size_t)L * C);
+    HIP_CHECK(hipMemcpy(t.data(), d, sizeof(float) * t.size(), hipMemcpyDeviceToHost));
+    for (int64_t c = 0; c < C; ++c)
+        for (int64_t n = 0; n < L; ++n) y[(size_t)c * L + n] = t[(size_t)n * C + c];
+}
+
+// hi + lo of the bf16 parts planes sp (conv_clx.hip's operand format) as a channel-major host plane [C][N]
+void read_parts(const SplitClPlanes& sp, float* out) {
+    const int64_t rows = sp.front + sp.N + sp.back;
+    std::vector<uint16_t> h(split_cl_bytes(sp.C, sp.N) / 2);
+    HIP_CHECK(hipMemcpy(h.data(), sp.p, h.size() * 2, hipMemcpyDeviceToHost));
+    auto f = [](uint16_t v) {
+        const uint32_t u = (uint32_t)v << 16;
+        float o;
+        std::memcpy(&o, &u, 4);
+        return o;
+    };
+    for (int64_t c = 0; c < sp.C; ++c)
+        for (int64_t n = 0; n < sp.N; ++n) {
+            const size_t hi = ((size_t)(c >> 4) * 2 * rows + sp.front + n) * 16 + (c & 15);
+            out[(size_t)c * sp.N + n] = f(h[hi]) + f(h[hi + (size_t)rows * 16]);
+        }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sbv2_debug_flac_encode(int device, const int16_t* x, const int64_t* lens, int nsig, int32_t sample_rate, uint8_t* dst, int64_t capacity,
+                           int64_t* out_bytes) {
+    API_BEGIN
+    SBV2_REQUIRE(nsig >= 1 && lens && dst && out_bytes, "bad arguments");
+    flac_rate_code(sample_rate);
+    std::vector<int64_t> ls(lens, lens + nsig), offs(nsig);
+    int64_t total = 0;
+    for (int i = 0; i < nsig; ++i) {
+        SBV2_REQUIRE(ls[i] >= 0, "negative signal length");
+        offs[i] = total;
+        total += ls[i];
+    }
+    SBV2_REQUIRE(total == 0 || x, "bad arguments");
+    HIP_CHECK(hipSetDevice(device));
+    struct Res {
+        hipStream_t s = nullptr;
+        void* x = nullptr;
+        ~Res() {
+            if (s) (void)hipStreamSynchronize(s);
+            if (x) (void)hipFree(x);
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } r;
+    HIP_CHECK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
+    HIP_CHECK(hipMalloc(&r.x, sizeof(int16_t) * (size_t)std::max<int64_t>(total, 1)));
+    if (total) HIP_CHECK(hipMemcpyAsync(r.x, x, sizeof(int16_t) * (size_t)total, hipMemcpyHostToDevice, r.s));
+    FlacEncoder enc(device);
+    std::vector<int64_t> bytes;
+    const int64_t nbytes = enc.encode(static_cast<const int16_t*>(r.x), offs, ls, sample_rate, r.s, &bytes);
+    SBV2_REQUIRE(capacity >= nbytes, "FLAC buffer too small: " + std::to_string(capacity) + " < " + std::to_string(nbytes) + " bytes");
+    HIP_CHECK(hipMemcpyAsync(dst, enc.output(), (size_t)nbytes, hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    for (int i = 0; i < nsig; ++i) out_bytes[i] = bytes[i];
+    API_END
+}
+
+int sbv2_debug_bucket_table(int64_t max_s, int64_t buckets, int64_t max_rel, int32_t* out) {
+    API_BEGIN
+    SBV2_REQUIRE(max_s >= 1 && out, "bad arguments");
+    const std::vector<int> t = BertModel::bucket_table((int)max_s, (int)buckets, (int)max_rel);
+    for (size_t i = 0; i < t.size(); ++i) out[i] = t[i];
+    API_END
+}
+
+int sbv2_debug_conv1d(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k, int64_t L,
+                      int64_t dilation, float pre_slope, float* y) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    Blob b = one_conv_blob(w, bias, {cout, cin, k}, cout);
+    WeightStore ws(b);
+    PackedConv pc = ws.conv("c");
+    Plane X{nullptr, (int)cin, (int)L, round_up((int)L, 64)}, Y{nullptr, (int)cout, (int)L, round_up((int)L, 64)};
+    DevMem dx(sizeof(float) * cin * X.ld), dy(sizeof(float) * cout * Y.ld);
+    X.p = dx.f();
+    Y.p = dy.f();
+    HIP_CHECK(hipMemcpy2D(X.p, sizeof(float) * X.ld, x, sizeof(float) * L, sizeof(float) * L, cin, hipMemcpyHostToDevice));
+    conv_plain(pc, X, Y, (int)dilation, (int)(dilation * (k - 1) / 2), nullptr, 1, nullptr, ACT_NONE, pre_slope);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy2D(y, sizeof(float) * L, Y.p, sizeof(float) * Y.ld, sizeof(float) * L, cout, hipMemcpyDeviceToHost));
+    API_END
+}
+
+int sbv2_debug_conv_transpose1d(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k,
+                                int64_t L, int64_t stride, int64_t padding, float pre_slope, float* y) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(bias, "bias required");
+    Blob b = one_conv_blob(w, bias, {cin, cout, k}, cout);
+    WeightStore ws(b);
+    PackedUpsample up = ws.upsample("c", (int)stride, (int)padding);
+    const int Lo = (int)(L * stride);
+    Plane X{nullptr, (int)cin, (int)L, round_up((int)L, 64)}, Y{nullptr, (int)cout, Lo, round_up(Lo, 64)};
+    DevMem dx(sizeof(float) * cin * X.ld), dy(sizeof(float) * cout * Y.ld);
+    X.p = dx.f();
+    Y.p = dy.f();
+    HIP_CHECK(hipMemcpy2D(X.p, sizeof(float) * X.ld, x, sizeof(float) * L, sizeof(float) * L, cin, hipMemcpyHostToDevice));
+    for (const auto& g : up.groups) {
+        ConvParams p;
+        p.A = g.w;
+        p.lda = g.lda;
+        p.a_tap_stride = (int64_t)up.cin * g.lda;
+        p.B = X.p;
+        p.ldb = X.ld;
+        p.nb = X.L;
+        p.C = Y.p;
+        p.ldc = Y.ld;
+        p.M = g.nph * up.cout;
+        p.N = X.L;
+        p.K = up.cin;
+        p.ntaps = g.ntaps;
+        for (int t = 0; t < g.ntaps; ++t) p.shift[t] = g.shift[t];
+        p.bias = up.bias;
+        p.bias_mode = BIAS_ROW;
+        p.pre_slope = pre_slope;
+        p.out_stride = (int)stride;
+        p.phase_rows = up.cout;
+        for (int q = 0; q < kMaxPhases; ++q) p.phase_off[q] = g.phase_off[q];
+        launch_conv(p, nullptr);
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy2D(y, sizeof(float) * Lo, Y.p, sizeof(float) * Y.ld, sizeof(float) * Lo, cout, hipMemcpyDeviceToHost));
+    API_END
+}
+
+int sbv2_debug_set_upx(int on) { return set_upx(on); }
+int sbv2_debug_conv_transpose1d_clx(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k, int64_t L,
+                                    int64_t stride, float pre_slope, const uint8_t* mask, int64_t mask_div, int64_t iters, float* y, float* ys_sum, float* ms) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && w && bias && y && mask_div >= 1 && (mask_div & (mask_div - 1)) == 0, "bad arguments");
+    Blob b = one_conv_blob(w, bias, {cin, cout, k}, cout);
+    WeightStore ws(b);
+    ClUpX u = build_upx(ws, w, bias, (int)cin, (int)cout, (int)k, (int)stride, /*parts_out=*/ys_sum != nullptr);
+    SBV2_REQUIRE(u.wx, "shape not supported by the phased conv_clx transposed convolution");
+    const int64_t Lo = L * stride;
+    DevMem dx = upload_cl(x, cin, L), dy(sizeof(float) * Lo * cout);
+    HIP_CHECK(hipMemset(dy.p, 0xFF, sizeof(float) * Lo * cout));   // (NaN: every output row must be written)
+    DevMem dxs(split_cl_bytes((int)cin, L) + 16), dys(split_cl_bytes((int)cout, Lo) + 16);
+    SplitClPlanes xs = make_split_cl(dxs.p, (int)cin, L, nullptr), ysp = make_split_cl(dys.p, (int)cout, Lo, nullptr);
+    split_cl(dx.f(), (int)cin, L, (int)cin, pre_slope, xs, nullptr);
+    DevMem dm(mask, mask ? (size_t)((L + mask_div - 1) / mask_div) : 0);
+    int shift = 0;
+    while ((1 << shift) < mask_div) ++shift;
+    ConvClxParams p;
+    p.X = xs;
+    p.W = u.wx;
+    p.nmt = u.M / 32;
+    p.M = u.M;
+    p.N = (int)L;
+    p.K = (int)cin;
+    p.ntaps = u.ntaps;
+    p.shift0 = u.shift0;
+    p.shift_step = -1;
+    p.Y = dy.f();
+    p.ldy = (int)cout;
+    if (ys_sum) {
+        p.Ys = ysp;
+        p.ys_slope = 0.1f;
+    }
+    p.bias = u.bias;
+    p.mask = mask ? dm.u8() : nullptr;   // indexed by the INPUT position >> shift
+    p.mask_shift = shift;
+    p.out_stride = (int)stride;
+    p.phase_rows = (int)cout;
+    p.phase_group = u.group;
+    for (int q = 0; q < kMaxPhases; ++q) {
+        p.phase_off[q] = u.phase_off[q];
+        p.phase_tap0[q] = u.phase_tap0[q];
+    }
+    SBV2_REQUIRE(conv_clx_usable(p), "shape not supported by conv_clx");
+    launch_conv_clx(p, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (iters > 0 && ms) *ms = time_ms(iters, [&] { launch_conv_clx(p, nullptr); });
+    download_cl(dy.f(), cout, Lo, y);
+    if (ys_sum) read_parts(ysp, ys_sum);
+    API_END
+}
+
+int sbv2_debug_conv1d_cl(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k, int64_t L,
+                         int64_t dilation, float pre_slope, int mode, int64_t iters, float* y, float* ms) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(mode >= 1 && mode <= 3, "mode: 1 = split-bf16, 2 = bf16, 3 = f16");
+    Blob b = one_conv_blob(w, bias, {cout, cin, k}, cout);
+    WeightStore ws(b);
+    ClConv c = pack_decoder_conv(ws, w, (int)cout, (int)cin, (int)k, mode, bias);
+    DevMem dx = upload_cl(x, cin, L), dy(sizeof(float) * L * cout);
+    const ConvClParams p = conv_cl_params(c, dx.f(), (int)cin, (int)L, dy.f(), (int)cout, (int)L, (int)dilation, (int)(dilation * (k - 1) / 2), nullptr, 1,
+                                          pre_slope, nullptr, 0, 1.0f, 0);
+    launch_conv_cl(p, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (iters > 0 && ms) *ms = time_ms(iters, [&] { launch_conv_cl(p, nullptr); });
+    download_cl(dy.f(), cout, L, y);
+    API_END
+}
+
+int sbv2_debug_set_skinny_max(int workgroups) { return set_skinny_max(workgroups); }
+int sbv2_debug_set_clx(int on) { return set_clx(on); }
+int sbv2_debug_set_ksplit(int on) { return set_ksplit(on); }
+int sbv2_debug_set_flash_parts(int on) { return set_flash_parts(on); }
+
+int sbv2_debug_conv1d_clx(int device, const float* x, const float* w, const float* bias, const float* res, int64_t cin, int64_t cout, int64_t k,
+                          int64_t L, int64_t dilation, float pre_slope, float beta, int64_t iters, float* y, float* ys_sum, float* ms) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && w && y, "bad arguments");
+    Blob b = one_conv_blob(w, bias, {cout, cin, k}, cout);
+    WeightStore ws(b);
+    ClConv c = pack_decoder_conv(ws, w, (int)cout, (int)cin, (int)k, 1, bias);
+    DevMem dx = upload_cl(x, cin, L), dy(sizeof(float) * L * cout), dr = res ? upload_cl(res, cout, L) : DevMem(0);
+    DevMem dxs(split_cl_bytes((int)cin, L) + 16), dys(split_cl_bytes((int)cout, L) + 16);
+    SplitClPlanes xs = make_split_cl(dxs.p, (int)cin, L, nullptr), ysp = make_split_cl(dys.p, (int)cout, L, nullptr);
+    split_cl(dx.f(), (int)cin, L, (int)cin, pre_slope, xs, nullptr);
+    ConvClxParams p;
+    p.X = xs;
+    p.W = c.wx;
+    p.nmt = c.nmt;
+    p.M = (int)cout;
+    p.N = (int)L;
+    p.K = (int)cin;
+    p.ntaps = (int)k;
+    p.shift0 = (int)(-dilation * (k - 1) / 2);
+    p.shift_step = (int)dilation;
+    p.Y = dy.f();
+    p.ldy = (int)cout;
+    if (ys_sum) {
+        p.Ys = ysp;
+        p.ys_slope = 0.1f;
+    }
+    p.bias = c.bias;
+    if (res) {
+        p.R = dr.f();
+        p.ldr = (int)cout;
+    }
+    p.beta = beta;
+    SBV2_REQUIRE(conv_clx_usable(p), "shape not supported by conv_clx");
+    launch_conv_clx(p, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (iters > 0 && ms) *ms = time_ms(iters, [&] { launch_conv_clx(p, nullptr); });
+    download_cl(dy.f(), cout, L, y);
+    if (ys_sum) read_parts(ysp, ys_sum);
+    API_END
+}
+
+int sbv2_debug_f16x3_saturation(int device, int enable, uint64_t* count) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    if (enable >= 0) f16x3_sat_enable(enable);
+    if (count) *count = f16x3_sat_read(true);
+    API_END
+}
+
+int sbv2_debug_set_respair_clx(int on) { return set_respair_clx(on); }
+
+int sbv2_debug_respair(int device, const float* x, const float* w1, const float* w2, const float* b1, const float* b2, int64_t C, int64_t N, int64_t k,
+                       int64_t dilation, const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, float* y) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && w1 && w2 && b1 && b2 && y && (C == 16 || C == 32 || C == 64) && N >= 1 && k >= 1 && k <= kMaxTaps && (k & 1) && mask_div >= 1 &&
+                     (mask_div & (mask_div - 1)) == 0, "bad arguments");
+    Blob b = one_conv_blob(w1, b1, {C, C, k}, C);
+    WeightStore ws(b);
+    ClConv c1 = pack_decoder_conv(ws, w1, (int)C, (int)C, (int)k, 1, b1);
+    ClConv c2 = pack_decoder_conv(ws, w2, (int)C, (int)C, (int)k, 1, b2);
+    DevMem dx(x, sizeof(float) * N * C), dy(y, sizeof(float) * N * C);   // (the previous contents of y matter when accumulate is set)
+    DevMem dm(mask, mask ? (size_t)((N + mask_div - 1) / mask_div) : 0);
+    int shift = 0;
+    while ((1 << shift) < mask_div) ++shift;
+    ResPairParams rp = step_params(c1, c2, (int)k, (int)dilation, 1, (int)C, N, mask ? dm.u8() : nullptr, (int)mask_div, shift);
+    rp.X = dx.f();
+    rp.Y = dy.f();
+    rp.beta = beta;
+    rp.accumulate = accumulate;
+    // 0 = respair_cl, 1 = the default dispatch's kernel, 2 = respair_clx
+    launch_respair(rp, variant == 0 ? BranchKernel::respair_cl : (variant == 2 ? BranchKernel::respair_clx : respair_default(rp)), nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(y, dy.p, sizeof(float) * N * C, hipMemcpyDeviceToHost));
+    API_END
+}
+
+int sbv2_debug_resbranch(int device, const float* x, const float* w, const float* bias, int64_t C, int64_t N, int64_t k, const int64_t* dilations,
+                         const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, int64_t iters, float* y, float* ms) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && w && bias && y && dilations && (C == 16 || C == 32 || C == 64 || C == 128) && N >= 1 && k >= 1 && k <= kMaxTaps && (k & 1) && mask_div >= 1 &&
+                     (mask_div & (mask_div - 1)) == 0, "bad arguments");
+    SBV2_REQUIRE(variant != 0 || C <= 64, "the fused step exists for C <= 64 (variant 2 = the two-launch conv_cl path at any C)");
+    const size_t wsz = (size_t)C * C * k;
+    Blob b = one_conv_blob(w, bias, {C, C, k}, C);
+    WeightStore ws(b);
+    std::vector<ClConv> c1, c2;   // conv1 / conv2 of each step
+    std::vector<int> dil;
+    for (int q = 0; q < kResBranchSteps; ++q) {
+        c1.push_back(pack_decoder_conv(ws, w + 2 * q * wsz, (int)C, (int)C, (int)k, 1, bias + (size_t)2 * q * C));
+        c2.push_back(pack_decoder_conv(ws, w + (2 * q + 1) * wsz, (int)C, (int)C, (int)k, 1, bias + (size_t)(2 * q + 1) * C));
+        dil.push_back((int)dilations[q]);
+    }
+    const size_t bytes = sizeof(float) * N * C;
+    DevMem dx(x, bytes), dy(y, bytes), da(bytes), db(bytes), dt(bytes);   // (the previous contents of y matter when accumulate is set)
+    DevMem dm(mask, mask ? (size_t)((N + mask_div - 1) / mask_div) : 0);
+    const unsigned char* m = mask ? dm.u8() : nullptr;
+    int shift = 0;
+    while ((1 << shift) < mask_div) ++shift;
+    auto run = [&]() {
+        if (variant == 1) {     // 1 = the fused branch (resbranch_clx.hip)
+            ResBranchParams rb = branch_params(c1, c2, dil, (int)k, (int)C, N, m, shift);
+            rb.X = dx.f();
+            rb.Y = dy.f();
+            rb.beta = beta;
+            rb.accumulate = accumulate;
+            launch_resbranch(rb, nullptr);
+            return;
+        }
+        // 0 = three launches of the fused step (respair_clx.hip), 2 = six launches of conv_cl.hip (conv1 -> T, conv2 + residual): the unfused path, any C
+        const float* cur = dx.f();
+        for (int q = 0; q < kResBranchSteps; ++q) {
+            const bool last = q + 1 == kResBranchSteps;
+            float* yn = last ? dy.f() : (q & 1 ? db.f() : da.f());
+            if (variant == 2) {
+                launch_conv_cl(conv_cl_params(c1[q], cur, (int)C, (int)N, dt.f(), (int)C, (int)N, dil[q], dil[q] * (int)(k - 1) / 2, m, (int)mask_div, 0.1f,
+                                              nullptr, (int)C, 1.0f, 0),
+                               nullptr);
+                launch_conv_cl(conv_cl_params(c2[q], dt.f(), (int)C, (int)N, yn, (int)C, (int)N, 1, (int)(k - 1) / 2, m, (int)mask_div, 0.1f, cur, (int)C,
+                                              last ? beta : 1.0f, last ? accumulate : 0),
+                               nullptr);
+            } else {
+                ResPairParams rp = step_params(c1[q], c2[q], (int)k, dil[q], 1, (int)C, N, m, (int)mask_div, shift);
+                rp.X = cur;
+                rp.Y = yn;
+                rp.beta = last ? beta : 1.0f;
+                rp.accumulate = last ? accumulate : 0;
+                launch_respair(rp, respair_default(rp), nullptr);
+            }
+            cur = yn;
+        }
+    };
+    run();
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(y, dy.p, bytes, hipMemcpyDeviceToHost));
+    if (iters > 0 && ms) *ms = time_ms(iters, run);
+    API_END
+}
+int sbv2_debug_set_resbranch(int on) { return set_resbranch(on); }
+
+// x2 / y2 (sbv2_debug_gemm_bfs_alt): a second input; the launches alternate between the two on ONE scratch buffer that is never cleared in between, so a
+// workgroup that read a stale partial sum (the other input's, left in its XCD's L2 by the previous launch) would show up in the result
+static int debug_gemm_bfs_impl(int device, const float* x, const float* x2, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
+                               int parts, int act, int split_out, int64_t iters, float* y, float* y2, float* ms) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE((parts == 2 || parts == 3 || parts == kPartsF16x3) && x && w && y && M >= 1 && N >= 4 && (N & 3) == 0 && (K & 15) == 0, "bad arguments");
+    Blob b = one_conv_blob(w, bias, {M, K, 1}, M);
+    WeightStore ws(b);
+    ws.set_bfs_parts(parts);
+    PackedConv pc = ws.conv("c");
+    const int ld = round_up((int)N, 64);
+    Plane X{nullptr, (int)K, (int)N, ld}, Y{nullptr, (int)M, (int)N, ld}, R{nullptr, (int)M, (int)N, ld};
+    const size_t xs_bytes = (size_t)split_nplanes(parts) * K * ld * 2 + 64;
+    DevMem dx(sizeof(float) * K * ld), dy(sizeof(float) * M * ld), dr(sizeof(float) * M * ld), dxs(xs_bytes), dys((size_t)3 * M * ld * 2 + 64);
+    X.p = dx.f();
+    Y.p = dy.f();
+    R.p = dr.f();
+    HIP_CHECK(hipMemset(X.p, 0, sizeof(float) * (size_t)K * ld));
+    HIP_CHECK(hipMemcpy2D(X.p, sizeof(float) * ld, x, sizeof(float) * N, sizeof(float) * N, K, hipMemcpyHostToDevice));
+    if (res) HIP_CHECK(hipMemcpy2D(R.p, sizeof(float) * ld, res, sizeof(float) * N, sizeof(float) * N, M, hipMemcpyHostToDevice));
+    SplitPlanes xs;
+    xs.p = dxs.p;
+    xs.parts = split_nplanes(parts);
+    xs.f16 = parts == kPartsF16x3;
+    xs.sat = xs.f16 ? f16x3_sat_counter() : nullptr;
+    xs.C = (int)K;
+    xs.L = (int)N;
+    xs.ld = ld;
+    xs.pstride = (int64_t)K * ld;
+    split_planes(X, xs, nullptr);
+    DevMem dx2(x2 ? sizeof(float) * K * ld : 0), dxs2(x2 ? xs_bytes : 0);
+    SplitPlanes xs2 = xs;
+    if (x2) {
+        Plane X2{dx2.f(), (int)K, (int)N, ld};
+        HIP_CHECK(hipMemset(X2.p, 0, sizeof(float) * (size_t)K * ld));
+        HIP_CHECK(hipMemcpy2D(X2.p, sizeof(float) * ld, x2, sizeof(float) * N, sizeof(float) * N, K, hipMemcpyHostToDevice));
+        xs2.p = dxs2.p;
+        split_planes(X2, xs2, nullptr);
+    }
+    SplitPlanes ys;
+    ys.p = dys.p;
+    ys.parts = split_nplanes(split_out);
+    ys.f16 = split_out == kPartsF16x3;
+    ys.C = (int)M;
+    ys.L = (int)N;
+    ys.ld = ld;
+    ys.pstride = (int64_t)M * ld;
+    // split_out: 0 = f32 result only; 2 / 3 = the result is ALSO written as that many bf16 parts, and y returns their sum (what a consumer sees)
+    // (scratch for the small-grid K split, as DeBERTa's forward provides it)
+    constexpr size_t kWs = (size_t)48 << 20;   // (as BertModel::kSkWsBytes / kSkCounters)
+    DevMem dsk(kWs + 1024 * sizeof(float));
+    HIP_CHECK(hipMemset(dsk.p, 0, kWs + 1024 * sizeof(float)));
+    BfsSplitK sk;
+    sk.ws = dsk.f();
+    sk.ws_bytes = kWs;
+    sk.counters = reinterpret_cast<unsigned*>(dsk.f() + (kWs / sizeof(float)));
+    sk.ncounters = 1024;
+    int turn = 0;
+    auto run = [&]() {
+        conv_bfs(pc, (x2 && (turn++ & 1)) ? xs2 : xs, &Y, split_out ? &ys : nullptr, nullptr, 1, nullptr, act, res ? &R : nullptr, 1.0f, 1.0f, -1, 0, &sk);
+    };
+    run();
+    HIP_CHECK(hipDeviceSynchronize());
+    if (iters > 0 && ms) *ms = time_ms(iters, run);
+    if (x2) {   // the last launch of each input, back to back on the used scratch
+        turn = 1;
+        run();
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy2D(y2, sizeof(float) * N, Y.p, sizeof(float) * ld, sizeof(float) * N, M, hipMemcpyDeviceToHost));
+        turn = 0;
+        run();
+        HIP_CHECK(hipDeviceSynchronize());
+    }
+    HIP_CHECK(hipMemcpy2D(y, sizeof(float) * N, Y.p, sizeof(float) * ld, sizeof(float) * N, M, hipMemcpyDeviceToHost));
+    if (split_out) {
+        const int np = ys.parts;
+        std::vector<uint16_t> hs((size_t)np * M * ld);
+        HIP_CHECK(hipMemcpy(hs.data(), ys.p, hs.size() * 2, hipMemcpyDeviceToHost));
+        for (int64_t m = 0; m < M; ++m)
+            for (int64_t n = 0; n < N; ++n) {
+                float acc = 0.f;
+                if (ys.f16) {
+                    _Float16 hi, lo;
+                    memcpy(&hi, &hs[(size_t)m * ld + n], 2);
+                    memcpy(&lo, &hs[((size_t)M + m) * ld + n], 2);
+                    y[(size_t)m * N + n] = (float)hi + (float)lo * (1.0f / kF16LoScale);
+                    continue;
+                }
+                for (int pp = np - 1; pp >= 0; --pp) {
+                    const uint32_t u = (uint32_t)hs[((size_t)pp * M + m) * ld + n] << 16;
+                    float f;
+                    memcpy(&f, &u, 4);
+                    acc += f;
+                }
+                y[(size_t)m * N + n] = acc;
+            }
+    }
+    API_END
+}
+
+int sbv2_debug_gemm_bfs(int device, const float* x, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
+                        int parts, int act, int split_out, int64_t iters, float* y, float* ms) {
+    return debug_gemm_bfs_impl(device, x, nullptr, w, bias, res, M, N, K, parts, act, split_out, iters, y, nullptr, ms);
+}
+int sbv2_debug_gemm_bfs_alt(int device, const float* xa, const float* xb, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
+                            int parts, int64_t iters, float* ya, float* yb) {
+    if (!xb || !yb) {
+        set_last_error("bad arguments");
+        return 1;
+    }
+    float ms = 0.f;
+    return debug_gemm_bfs_impl(device, xa, xb, w, bias, res, M, N, K, parts, 0, 0, iters, ya, yb, &ms);
+}
+
+int sbv2_debug_time_conv1d(int device, int64_t cin, int64_t cout, int64_t k, int64_t L, int64_t dilation, int64_t iters, float* ms) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(ms && iters >= 1, "bad arguments");
+    std::vector<float> w((size_t)cout * cin * k), bias((size_t)cout, 0.1f);
+    uint32_t st = 12345u;
+    auto rnd = [&]() {
+        st = st * 1664525u + 1013904223u;
+        return ((st >> 8) * (1.0f / 16777216.0f) - 0.5f);
+    };
+    for (auto& v : w) v = rnd() * 0.1f;
+    Blob b = one_conv_blob(w.data(), bias.data(), {cout, cin, k}, cout);
+    WeightStore ws(b);
+    PackedConv pc = ws.conv("c");
+    Plane X{nullptr, (int)cin, (int)L, round_up((int)L, 64)}, Y{nullptr, (int)cout, (int)L, round_up((int)L, 64)};
+    std::vector<float> hx((size_t)cin * X.ld);
+    for (auto& v : hx) v = rnd() * 2.f;
+    DevMem dx(hx.data(), sizeof(float) * hx.size()), dy(sizeof(float) * cout * Y.ld);
+    X.p = dx.f();
+    Y.p = dy.f();
+    auto run = [&] { conv_plain(pc, X, Y, (int)dilation, (int)(dilation * (k - 1) / 2), nullptr, 1, nullptr, ACT_NONE, 1.0f); };
+    for (int i = 0; i < 3; ++i) run();
+    *ms = time_ms(iters, run);
+    API_END
+}
+
+}  // extern "C"

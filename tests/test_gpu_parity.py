@@ -128,7 +128,7 @@ def _resbranch(x, w, b, k, dils, mask, mask_div, beta, prev, variant):
     m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
     d = np.asarray(dils, np.int64)
     _lib.check(_lib.lib().sbv2_debug_resbranch(0, P(x), P(w), P(b), C, N, k, d.ctypes.data_as(_lib.i64p), None if m is None else m.ctypes.data, mask_div,
-                                               float(beta), 1 if prev is not None else 0, variant, 0, P(y), None, None, 0))
+                                               float(beta), 1 if prev is not None else 0, variant, 0, P(y), None))
     return y
 
 

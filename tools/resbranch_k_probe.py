@@ -19,7 +19,7 @@ for c, k, n in ((16, 7, 459264 * 16), (16, 11, 459264 * 16)):
     for variant in (0, 1, 0, 1):
         y = np.zeros((n, c), np.float32)
         ms = C.c_float(0)
-        _lib.check(l.sbv2_debug_resbranch(0, P(x), P(w), P(b), c, n, k, d.ctypes.data_as(_lib.i64p), None, 1, 1.0 / 3, 0, variant, iters, P(y), C.byref(ms), None, 0))
+        _lib.check(l.sbv2_debug_resbranch(0, P(x), P(w), P(b), c, n, k, d.ctypes.data_as(_lib.i64p), None, 1, 1.0 / 3, 0, variant, iters, P(y), C.byref(ms)))
         res.setdefault(variant, []).append(round(ms.value, 4))
         ys[variant] = y
     print(json.dumps({"C": c, "k": k, "positions": n, "three_steps_ms": res[0], "one_launch_ms": res[1],

@@ -1,5 +1,5 @@
 export TMPDIR=/tmp
-V=${1:-3}
+V=${1:-2}
 O=$GRAFT_REPO_ROOT/gpurun_out/r04_rp_pmc_v$V
 mkdir -p $O
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS --output-format csv -d $O/p1 -- python3 tools/respair_pmc.py $V > $O/p1.log 2>&1
