@@ -337,6 +337,23 @@ int sbv2_debug_gemm_bfs(int device, const float* x, const float* w, const float*
    wrong result: the race screen of gemm_bfs.hip's cross-workgroup K split.  parts as above. */
 int sbv2_debug_gemm_bfs_alt(int device, const float* xa, const float* xb, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
                             int parts, int64_t iters, float* ya, float* yb);
+/* One window-relative attention of the VITS encoders (attn_flash.hip / ops.hip) on a packed batch, laid out and planned by the model's own builders
+   (make_layout, make_attn_plan, flash_choice).  q, k, v, ctx: [heads * dk][sum lens] (utterances concatenated, head h = rows h dk .. + dk); erk, erv:
+   [2 window + 1][dk]; layout: 0 = text-rate layout, 1 = frame-rate layout (the flow's); qscale = 1 / sqrt(dk).  variant: -1 = the flow's own choice for
+   this batch, 0 = unfused (grouped GEMMs, k_vits_softmax, k_vits_relv_add), 1 = k_vits_flash (exact f32), 2 = k_vits_flash_x3, 3 = k_vits_flash_x3p,
+   4 / 5 = k_vits_flash_x3q on its 4- / 8-wave shape (3 .. 5 read k and v as the bf16 parts the q | k | v product's epilogue writes).  poison != 0: every
+   column of q, k, v and their parts outside an utterance (layout gaps and the tail up to the pitch) holds NaN and ctx is filled with a sentinel first;
+   *stray (optional) = the number of ctx elements outside an utterance that no longer hold it. */
+int sbv2_debug_vits_attention(int device, const float* q, const float* k, const float* v, const float* erk, const float* erv, const int64_t* lens, int nutt,
+                              int64_t heads, int64_t dk, int64_t window, int layout, int variant, int poison, float* ctx, int64_t* stray);
+/* One disentangled attention of DeBERTa (attn_deberta.hip / ops.hip) on a packed batch, planned by the model's own builder (make_deberta_attn_plan).
+   q, k, v, ctx: [heads * d][sum lens]; pos_k, pos_q: [heads * d][2 span] (the model's position planes, span = buckets > 0 ? buckets : max_rel);
+   tok_mask: [sum lens] attention mask per token (null: all ones); gap: zero columns between utterances.  variant: -1 = the model's per-utterance dispatch,
+   0 = unfused (grouped GEMMs + deberta_softmax), 1 / 2 / 3 = every utterance on the short / 128-token / long kernel (an error, and no launch, when one
+   does not fit).  poison: as sbv2_debug_vits_attention. */
+int sbv2_debug_deberta_attention(int device, const float* q, const float* k, const float* v, const float* pos_k, const float* pos_q, const int64_t* lens,
+                                 int nutt, int64_t heads, int64_t d, int64_t buckets, int64_t max_rel, const uint8_t* tok_mask, int64_t gap, int variant,
+                                 int poison, float* ctx, int64_t* stray);
 
 #ifdef __cplusplus
 }

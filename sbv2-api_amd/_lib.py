@@ -126,6 +126,10 @@ SYMBOLS = {
     "sbv2_debug_gemm_bfs_alt": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, f32p, f32p]),
     "sbv2_debug_gemm_bfs": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64,
                                       f32p, f32p]),
+    "sbv2_debug_vits_attention": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, i64p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                            C.c_int, f32p, i64p]),
+    "sbv2_debug_deberta_attention": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, i64p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_int64, C.c_int, C.c_int, f32p, i64p]),
 }
 
 _lib = None

@@ -213,6 +213,165 @@ BertModel::~BertModel() {
     if (sk_counters_) (void)hipFree(sk_counters_);
 }
 
+DebertaAttnPlan make_deberta_attn_plan(const SegLayout& lay, int H, int heads, int buckets, int max_rel, int ld, int ldp, int mode) {
+    DebertaAttnPlan ap;
+    const int d = H / heads;
+    const int span = ap.span = buckets > 0 ? buckets : max_rel;
+    const int maxT = ap.maxT = lay.max_len();
+    // relative-position window used by this batch
+    ap.tab = BertModel::bucket_table(maxT, buckets, max_rel);
+    const std::vector<int>& tab = ap.tab;
+    auto clampi = [&](int v) { return std::min(std::max(v, 0), 2 * span - 1); };
+    int dmin = 2 * span, dmax = 0;
+    for (int v : tab) {
+        dmin = std::min(dmin, std::min(clampi(v + span), clampi(-v + span)));
+        dmax = std::max(dmax, std::max(clampi(v + span), clampi(-v + span)));
+    }
+    const int win_lo = ap.win_lo = dmin / 4 * 4;
+    const int wlen = ap.wlen = dmax - win_lo + 1;
+    const int win_ld = ap.win_ld = round_up(wlen, 4);
+
+    // attention problem descriptors.  Utterances of <= 64 tokens (the usual sentence) take the fused kernel of attn_deberta.hip, 65 .. 128
+    // tokens its tiled variant (the reference's TensorRT profile allows 100 tokens: model.rs:15), longer ones its key-tile loop (long-form
+    // text); a batch may hold all three.  The grouped-GEMM + softmax path (five launches per layer) takes what a head dimension the fused kernels
+    // do not cover falls back to.
+    const bool want_fused = mode != kDbUnfused;
+    const bool want_long = mode != kDbNoLong;
+    // bucket window reachable by a short utterance (|i - j| <= 63)
+    {
+        int lo = 2 * span, hi2 = 0;
+        const int c = maxT - 1, r = std::min(maxT - 1, 63);
+        for (int dlt = -r; dlt <= r; ++dlt) {
+            const int v = tab[c + dlt];
+            lo = std::min(lo, std::min(clampi(v + span), clampi(-v + span)));
+            hi2 = std::max(hi2, std::max(clampi(v + span), clampi(-v + span)));
+        }
+        ap.win_lo_s = lo / 4 * 4;
+        ap.wlen_s = hi2 - ap.win_lo_s + 1;
+    }
+    // ... and by a sequence of up to 128 tokens (|i - j| <= 127): the tiled fused kernel
+    {
+        int lo = 2 * span, hi2 = 0;
+        const int c = maxT - 1, r = std::min(maxT - 1, 127);
+        for (int dlt = -r; dlt <= r; ++dlt) {
+            const int v = tab[c + dlt];
+            lo = std::min(lo, std::min(clampi(v + span), clampi(-v + span)));
+            hi2 = std::max(hi2, std::max(clampi(v + span), clampi(-v + span)));
+        }
+        ap.win_lo_m = lo / 4 * 4;
+        ap.wlen_m = hi2 - ap.win_lo_m + 1;
+    }
+    const int lds = ap.lds = round_up(maxT, 4);
+    for (int u = 0; u < lay.n; ++u) {
+        const int T = lay.len[u];
+        bool is_short = want_fused && deberta_attention_fits(T, ap.wlen_s, d);
+        bool is_mid = want_fused && !is_short && deberta_attention128_fits(T, d);
+        bool is_long = want_fused && want_long && !is_short && !is_mid && deberta_attention_long_fits(T, d);
+        if (mode == kDbShort || mode == kDbMid || mode == kDbLong) {   // one kernel for every utterance (the tests)
+            is_short = mode == kDbShort;
+            is_mid = mode == kDbMid;
+            is_long = mode == kDbLong;
+            SBV2_REQUIRE(!is_short || deberta_attention_fits(T, ap.wlen_s, d), "deberta attention: an utterance does not fit the short kernel");
+            SBV2_REQUIRE(!is_mid || deberta_attention128_fits(T, d), "deberta attention: an utterance does not fit the 128-token kernel");
+            SBV2_REQUIRE(!is_long || deberta_attention_long_fits(T, d), "deberta attention: an utterance does not fit the long kernel");
+        }
+        if (is_long) ap.maxTF = std::max(ap.maxTF, T);
+        else if (!is_short && !is_mid) ap.maxTL = std::max(ap.maxTL, T);
+        for (int h = 0; h < heads; ++h) {
+            AttnGroup a;
+            a.qk_off = (int64_t)h * d * ld + lay.start[u];
+            a.s_off = ap.s_off;
+            a.aux_off = ap.c_off;
+            a.aux2_off = ap.p_off;
+            a.T = T;
+            a.lds = lds;
+            a.col0 = lay.start[u];
+            a.head = h;
+            if (is_short) {
+                ap.ag_s.push_back(a);
+                continue;
+            }
+            if (is_mid) {
+                ap.ag_m.push_back(a);
+                continue;
+            }
+            if (is_long) {
+                ap.ag_f.push_back(a);
+                continue;
+            }
+            ap.ag_l.push_back(a);
+            ap.g_st.push_back(GemmGroup{a.qk_off, a.qk_off, ap.s_off, 0, T, T, d, T});                                   // S^T = K^T Q
+            ap.g_c2p.push_back(GemmGroup{(int64_t)h * d * ldp + win_lo, a.qk_off, ap.c_off, 0, wlen, T, d, T});          // posK^T Q
+            ap.g_p2c.push_back(GemmGroup{a.qk_off, (int64_t)h * d * ldp + win_lo, ap.p_off, 0, T, wlen, d, wlen});       // K^T posQ
+            ap.g_pv.push_back(GemmGroup{(int64_t)lay.start[u] * H + h * d, ap.s_off, a.qk_off, 0, d, T, T, T});          // V P^T
+            ap.s_off += (int64_t)T * lds;
+            ap.c_off += (int64_t)wlen * lds;
+            ap.p_off += (int64_t)T * win_ld;
+            ap.fl_tt += 2.0 * (double)T * T * d;
+            ap.fl_tw += 2.0 * (double)T * wlen * d;
+        }
+    }
+    return ap;
+}
+
+void DebertaAttnPlan::upload_table(Arena& ar, hipStream_t stream) {
+    d_tab = ar.array<int>(tab.size());
+    ar.upload(d_tab, tab.data(), sizeof(int) * tab.size(), stream);
+}
+
+void DebertaAttnPlan::upload_groups(Arena& ar, hipStream_t stream, int N, int H) {
+    const int nS = ngS(), nM = ngM(), nF = ngF(), nL = ngL();
+    if (nF) {
+        d_agF = ar.array<AttnGroup>(nF);
+        ar.upload(d_agF, ag_f.data(), sizeof(AttnGroup) * nF, stream);
+    }
+    if (nM) {
+        d_agM = ar.array<AttnGroup>(nM);
+        ar.upload(d_agM, ag_m.data(), sizeof(AttnGroup) * nM, stream);
+    }
+    if (nS) {
+        d_agS = ar.array<AttnGroup>(nS);
+        ar.upload(d_agS, ag_s.data(), sizeof(AttnGroup) * nS, stream);
+    }
+    if (nL) {
+        S = ar.array<float>((size_t)s_off);
+        C2P = ar.array<float>((size_t)c_off);
+        P2C = ar.array<float>((size_t)p_off);
+        VT = ar.array<float>((size_t)N * H);
+        d_agL = ar.array<AttnGroup>(nL);
+        d_g = ar.array<GemmGroup>((size_t)4 * nL);
+        ar.upload(d_agL, ag_l.data(), sizeof(AttnGroup) * nL, stream);
+        ar.upload(d_g, g_st.data(), sizeof(GemmGroup) * nL, stream);
+        ar.upload(d_g + nL, g_c2p.data(), sizeof(GemmGroup) * nL, stream);
+        ar.upload(d_g + 2 * nL, g_p2c.data(), sizeof(GemmGroup) * nL, stream);
+        ar.upload(d_g + 3 * nL, g_pv.data(), sizeof(GemmGroup) * nL, stream);
+    }
+}
+
+void deberta_attention_fused(const DebertaAttnPlan& ap, const float* Q, const float* K, const float* V, int ld, const float* posk, const float* posq,
+                             int ldp, int d, float inv_scale, const unsigned char* tok_mask, float* ctx, int ldc, hipStream_t s) {
+    if (ap.ngS())
+        deberta_attention(ap.d_agS, ap.ngS(), Q, K, ld, V, posk, posq, ldp, ap.win_lo_s, ap.wlen_s, ap.d_tab, ap.maxT - 1, ap.span, inv_scale, tok_mask,
+                          d, ctx, ldc, s);
+    if (ap.ngM())
+        deberta_attention128(ap.d_agM, ap.ngM(), Q, K, ld, V, posk, posq, ldp, ap.win_lo_m, ap.wlen_m, ap.d_tab, ap.maxT - 1, ap.span, inv_scale, tok_mask,
+                             d, ctx, ldc, s);
+    if (ap.ngF())
+        deberta_attention_long(ap.d_agF, ap.ngF(), ap.maxTF, Q, K, ld, V, posk, posq, ldp, ap.win_lo, ap.wlen, ap.d_tab, ap.maxT - 1, ap.span, inv_scale,
+                               tok_mask, d, ctx, ldc, s);
+}
+
+void deberta_attention_unfused(const DebertaAttnPlan& ap, const float* Q, const float* K, int ld, const float* VT, int ldvt, const float* posk,
+                               const float* posq, int ldp, int d, float inv_scale, const unsigned char* tok_mask, float* ctx, int ldc, hipStream_t s) {
+    const int nL = ap.ngL();
+    if (!nL) return;
+    grouped_gemm(K, ld, Q, ld, ap.S, ap.lds, ap.d_g, nL, ap.maxTL, ap.maxTL, inv_scale, ap.fl_tt, s);
+    grouped_gemm(posk, ldp, Q, ld, ap.C2P, ap.lds, ap.d_g + nL, nL, ap.wlen, ap.maxTL, 1.0f, ap.fl_tw, s);
+    grouped_gemm(K, ld, posq, ldp, ap.P2C, ap.win_ld, ap.d_g + 2 * nL, nL, ap.maxTL, ap.wlen, 1.0f, ap.fl_tw, s);
+    deberta_softmax(ap.d_agL, nL, ap.maxTL, ap.S, ap.C2P, ap.P2C, ap.d_tab, ap.maxT - 1, ap.span, ap.win_lo, ap.win_ld, inv_scale, tok_mask, s);
+    grouped_gemm(VT, ldvt, ap.S, ap.lds, ctx, ldc, ap.d_g + 3 * nL, nL, d, ap.maxTL, 1.0f, ap.fl_tt, s);
+}
+
 void BertModel::forward(int n, const int64_t* ids, const int64_t* mask, const int64_t* lens) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(n >= 1, "empty batch");
@@ -221,7 +380,6 @@ void BertModel::forward(int n, const int64_t* ids, const int64_t* mask, const in
     arena_.reset();
     arena_.begin_uploads();   // every table of the pass is uploaded before the first kernel (deberta_embed_ln below): held back, neighbours merged
     const int H = cfg_.hidden, nh = cfg_.heads, d = H / nh;
-    const int span = cfg_.buckets > 0 ? cfg_.buckets : cfg_.max_rel;
     std::vector<int> L(n);
     int64_t total = 0;
     for (int i = 0; i < n; ++i) {
@@ -236,7 +394,6 @@ void BertModel::forward(int n, const int64_t* ids, const int64_t* mask, const in
     layout_ = make_layout(L, cfg_.conv_k / 2, arena_, stream_, am.data());
     const SegLayout& lay = layout_;
     const int N = lay.L;
-    const int maxT = lay.max_len();
 
     // token ids in the packed layout (-1 in alignment gaps)
     std::vector<int> hid(N, -1);
@@ -257,53 +414,15 @@ void BertModel::forward(int n, const int64_t* ids, const int64_t* mask, const in
     unsigned char* d_valid = arena_.array<unsigned char>(N);
     arena_.upload(d_valid, valid.data(), N, stream_);
 
-    // relative-position window used by this batch
-    const std::vector<int> tab = bucket_table(maxT, cfg_.buckets, cfg_.max_rel);
-    auto clampi = [&](int v) { return std::min(std::max(v, 0), 2 * span - 1); };
-    int dmin = 2 * span, dmax = 0;
-    for (int v : tab) {
-        dmin = std::min(dmin, std::min(clampi(v + span), clampi(-v + span)));
-        dmax = std::max(dmax, std::max(clampi(v + span), clampi(-v + span)));
-    }
-    const int win_lo = dmin / 4 * 4;
-    const int wlen = dmax - win_lo + 1;
-    const int win_ld = round_up(wlen, 4);
-    int* d_tab = arena_.array<int>(tab.size());
-    arena_.upload(d_tab, tab.data(), sizeof(int) * tab.size(), stream_);
-
-    // attention problem descriptors.  Utterances of <= 64 tokens (the usual sentence) take the fused kernel of attn_deberta.hip, 65 .. 128
-    // tokens its tiled variant (the reference's TensorRT profile allows 100 tokens: model.rs:15), longer ones its key-tile loop (long-form
-    // text); a batch may hold all three.  SBV2_BERT_ATTN=unfused sends everything down the grouped-GEMM + softmax path (five launches per
-    // layer; also what a head dimension the fused kernels do not cover falls back to), SBV2_BERT_ATTN=nolong only the > 128-token ones.
-    static const bool want_fused = !(getenv("SBV2_BERT_ATTN") && std::string(getenv("SBV2_BERT_ATTN")) == "unfused");
-    static const bool want_long = !(getenv("SBV2_BERT_ATTN") && std::string(getenv("SBV2_BERT_ATTN")) == "nolong");
-    // bucket window reachable by a short utterance (|i - j| <= 63)
-    int win_lo_s = 0, wlen_s = 1;
-    {
-        int lo = 2 * span, hi2 = 0;
-        const int c = maxT - 1, r = std::min(maxT - 1, 63);
-        for (int dlt = -r; dlt <= r; ++dlt) {
-            const int v = tab[c + dlt];
-            lo = std::min(lo, std::min(clampi(v + span), clampi(-v + span)));
-            hi2 = std::max(hi2, std::max(clampi(v + span), clampi(-v + span)));
-        }
-        win_lo_s = lo / 4 * 4;
-        wlen_s = hi2 - win_lo_s + 1;
-    }
-    // ... and by a sequence of up to 128 tokens (|i - j| <= 127): the tiled fused kernel
-    int win_lo_m = 0, wlen_m = 1;
-    {
-        int lo = 2 * span, hi2 = 0;
-        const int c = maxT - 1, r = std::min(maxT - 1, 127);
-        for (int dlt = -r; dlt <= r; ++dlt) {
-            const int v = tab[c + dlt];
-            lo = std::min(lo, std::min(clampi(v + span), clampi(-v + span)));
-            hi2 = std::max(hi2, std::max(clampi(v + span), clampi(-v + span)));
-        }
-        win_lo_m = lo / 4 * 4;
-        wlen_m = hi2 - win_lo_m + 1;
-    }
-    const int lds = round_up(maxT, 4);
+    // attention plan: bucket table, windows, the class of each utterance, problem descriptors (uploaded in the order the pass has always used)
+    // SBV2_BERT_ATTN=unfused sends everything down the grouped-GEMM + softmax path, SBV2_BERT_ATTN=nolong only the > 128-token ones.
+    static const int attn_mode = !getenv("SBV2_BERT_ATTN") ? kDbAuto
+                                 : std::string(getenv("SBV2_BERT_ATTN")) == "unfused" ? kDbUnfused
+                                 : std::string(getenv("SBV2_BERT_ATTN")) == "nolong"  ? kDbNoLong
+                                                                                       : kDbAuto;
+    const int ldp = layers_[0].pos_k.ld;
+    DebertaAttnPlan ap = make_deberta_attn_plan(lay, H, nh, cfg_.buckets, cfg_.max_rel, round_up(N, 64), ldp, attn_mode);
+    ap.upload_table(arena_, stream_);
     Plane X = arena_.plane(H, N), QKV = arena_.plane(3 * H, N), ctx = arena_.plane(H, N), A = arena_.plane(H, N);
     Plane Q = QKV.rows(0, H), Kp = QKV.rows(H, H), Vp = QKV.rows(2 * H, H);
     const int SP = bfs_parts_;
@@ -318,79 +437,9 @@ void BertModel::forward(int n, const int64_t* ids, const int64_t* mask, const in
     }
     Plane E0{};   // the embedding output is ConvLayer's input (modeling_deberta_v2.py:664: self.conv(hidden_states, output_states, input_mask))
     if (cfg_.conv_k > 0) E0 = arena_.plane(H, N);
-    std::vector<AttnGroup> ag_s, ag_m, ag_f, ag_l;   // short / mid / long fused, grouped-GEMM path
-    std::vector<GemmGroup> g_st, g_c2p, g_p2c, g_pv;
-    int64_t s_off = 0, c_off = 0, p_off = 0;
-    int maxTL = 0, maxTF = 0;
-    const int ldp = layers_[0].pos_k.ld;
-    for (int u = 0; u < n; ++u) {
-        const int T = L[u];
-        const bool is_short = want_fused && deberta_attention_fits(T, wlen_s, d);
-        const bool is_mid = want_fused && !is_short && deberta_attention128_fits(T, d);
-        const bool is_long = want_fused && want_long && !is_short && !is_mid && deberta_attention_long_fits(T, d);
-        if (is_long) maxTF = std::max(maxTF, T);
-        else if (!is_short && !is_mid) maxTL = std::max(maxTL, T);
-        for (int h = 0; h < nh; ++h) {
-            AttnGroup a;
-            a.qk_off = (int64_t)h * d * X.ld + lay.start[u];
-            a.s_off = s_off;
-            a.aux_off = c_off;
-            a.aux2_off = p_off;
-            a.T = T;
-            a.lds = lds;
-            a.col0 = lay.start[u];
-            a.head = h;
-            if (is_short) {
-                ag_s.push_back(a);
-                continue;
-            }
-            if (is_mid) {
-                ag_m.push_back(a);
-                continue;
-            }
-            if (is_long) {
-                ag_f.push_back(a);
-                continue;
-            }
-            ag_l.push_back(a);
-            g_st.push_back(GemmGroup{a.qk_off, a.qk_off, s_off, 0, T, T, d, T});                                   // S^T = K^T Q
-            g_c2p.push_back(GemmGroup{(int64_t)h * d * ldp + win_lo, a.qk_off, c_off, 0, wlen, T, d, T});          // posK^T Q
-            g_p2c.push_back(GemmGroup{a.qk_off, (int64_t)h * d * ldp + win_lo, p_off, 0, T, wlen, d, wlen});       // K^T posQ
-            g_pv.push_back(GemmGroup{(int64_t)lay.start[u] * H + h * d, s_off, a.qk_off, 0, d, T, T, T});          // V P^T
-            s_off += (int64_t)T * lds;
-            c_off += (int64_t)wlen * lds;
-            p_off += (int64_t)T * win_ld;
-        }
-    }
-    const int ngS = (int)ag_s.size(), ngM = (int)ag_m.size(), ngF = (int)ag_f.size(), ngL = (int)ag_l.size();
-    float *S = nullptr, *C2P = nullptr, *P2C = nullptr, *VT = nullptr;
-    AttnGroup *d_agS = nullptr, *d_agM = nullptr, *d_agF = nullptr, *d_agL = nullptr;
-    if (ngF) {
-        d_agF = arena_.array<AttnGroup>(ngF);
-        arena_.upload(d_agF, ag_f.data(), sizeof(AttnGroup) * ngF, stream_);
-    }
-    if (ngM) {
-        d_agM = arena_.array<AttnGroup>(ngM);
-        arena_.upload(d_agM, ag_m.data(), sizeof(AttnGroup) * ngM, stream_);
-    }
-    GemmGroup* d_g = nullptr;
-    if (ngS) {
-        d_agS = arena_.array<AttnGroup>(ngS);
-        arena_.upload(d_agS, ag_s.data(), sizeof(AttnGroup) * ngS, stream_);
-    }
-    if (ngL) {
-        S = arena_.array<float>((size_t)s_off);
-        C2P = arena_.array<float>((size_t)c_off);
-        P2C = arena_.array<float>((size_t)p_off);
-        VT = arena_.array<float>((size_t)N * H);
-        d_agL = arena_.array<AttnGroup>(ngL);
-        d_g = arena_.array<GemmGroup>((size_t)4 * ngL);
-        arena_.upload(d_agL, ag_l.data(), sizeof(AttnGroup) * ngL, stream_);
-        arena_.upload(d_g, g_st.data(), sizeof(GemmGroup) * ngL, stream_);
-        arena_.upload(d_g + ngL, g_c2p.data(), sizeof(GemmGroup) * ngL, stream_);
-        arena_.upload(d_g + 2 * ngL, g_p2c.data(), sizeof(GemmGroup) * ngL, stream_);
-        arena_.upload(d_g + 3 * ngL, g_pv.data(), sizeof(GemmGroup) * ngL, stream_);
-    }
+    SBV2_REQUIRE(QKV.ld == round_up(N, 64), "plane pitch mismatch");
+    ap.upload_groups(arena_, stream_, N, H);
+    const int ngL = ap.ngL();
 
     const float inv_scale = 1.0f / std::sqrt((float)d * 3.0f);  // c2p + p2c => scale_factor 3 (:226-232)
 
@@ -412,29 +461,6 @@ void BertModel::forward(int n, const int64_t* ids, const int64_t* mask, const in
 
     if (cfg_.conv_k > 0) HIP_CHECK(hipMemcpyAsync(E0.p, X.p, sizeof(float) * (size_t)H * X.ld, hipMemcpyDeviceToDevice, stream_));
 
-    auto grouped = [&](const float* Aop, int lda, const float* Bop, int ldb, float* Cop, int ldc, const GemmGroup* grp, int maxM, int maxN,
-                       float alpha, double flops) {
-        ConvParams p;
-        p.A = Aop;
-        p.lda = lda;
-        p.B = Bop;
-        p.ldb = ldb;
-        p.C = Cop;
-        p.ldc = ldc;
-        p.alpha = alpha;
-        p.groups = grp;
-        p.ngroups = ngL;
-        p.maxM = maxM;
-        p.maxN = maxN;
-        p.flops_hint = flops;
-        launch_conv(p, stream_);
-    };
-    double fl_tt = 0, fl_tw = 0;  // algorithmic FLOP of the grouped products (profiling only)
-    for (const AttnGroup& a : ag_l) {
-        fl_tt += 2.0 * (double)a.T * a.T * d;
-        fl_tw += 2.0 * (double)a.T * wlen * d;
-    }
-
     // scratch for the K split of small grids (gemm_bfs.hip: a single utterance's products; larger grids ignore it)
     BfsSplitK sk;
     if (SP) {
@@ -449,22 +475,10 @@ void BertModel::forward(int n, const int64_t* ids, const int64_t* mask, const in
         // q | k | v in one product (k-major planes)
         if (SP) conv_bfs(Ly.qkv, Xs, &QKV, nullptr, nullptr, 1, stream_, ACT_NONE, nullptr, 1.0f, 1.0f, -1, 0, &sk);
         else conv_plain(Ly.qkv, X, QKV, 1, 0, nullptr, 1, stream_);
-        if (ngS)
-            deberta_attention(d_agS, ngS, Q.p, Kp.p, QKV.ld, Vp.p, Ly.pos_k.p, Ly.pos_q.p, ldp, win_lo_s, wlen_s, d_tab, maxT - 1, span, inv_scale,
-                              lay.d_mask, d, ctx.p, ctx.ld, stream_);
-        if (ngM)
-            deberta_attention128(d_agM, ngM, Q.p, Kp.p, QKV.ld, Vp.p, Ly.pos_k.p, Ly.pos_q.p, ldp, win_lo_m, wlen_m, d_tab, maxT - 1, span, inv_scale,
-                                 lay.d_mask, d, ctx.p, ctx.ld, stream_);
-        if (ngF)
-            deberta_attention_long(d_agF, ngF, maxTF, Q.p, Kp.p, QKV.ld, Vp.p, Ly.pos_k.p, Ly.pos_q.p, ldp, win_lo, wlen, d_tab, maxT - 1, span,
-                                   inv_scale, lay.d_mask, d, ctx.p, ctx.ld, stream_);
+        deberta_attention_fused(ap, Q.p, Kp.p, Vp.p, QKV.ld, Ly.pos_k.p, Ly.pos_q.p, ldp, d, inv_scale, lay.d_mask, ctx.p, ctx.ld, stream_);
         if (ngL) {
-            linear_tokmajor(Ly.v, X, VT, H, stream_);   // the grouped V P^T product wants V token-major
-            grouped(Kp.p, Kp.ld, Q.p, Q.ld, S, lds, d_g, maxTL, maxTL, inv_scale, fl_tt);
-            grouped(Ly.pos_k.p, ldp, Q.p, Q.ld, C2P, lds, d_g + ngL, wlen, maxTL, 1.0f, fl_tw);
-            grouped(Kp.p, Kp.ld, Ly.pos_q.p, ldp, P2C, win_ld, d_g + 2 * ngL, maxTL, wlen, 1.0f, fl_tw);
-            deberta_softmax(d_agL, ngL, maxTL, S, C2P, P2C, d_tab, maxT - 1, span, win_lo, win_ld, inv_scale, lay.d_mask, stream_);
-            grouped(VT, H, S, lds, ctx.p, ctx.ld, d_g + 3 * ngL, d, maxTL, 1.0f, fl_tt);
+            linear_tokmajor(Ly.v, X, ap.VT, H, stream_);   // the grouped V P^T product wants V token-major
+            deberta_attention_unfused(ap, Q.p, Kp.p, QKV.ld, ap.VT, H, Ly.pos_k.p, Ly.pos_q.p, ldp, d, inv_scale, lay.d_mask, ctx.p, ctx.ld, stream_);
         }
         if (SP) {
             split_planes(ctx, Cs, stream_);

@@ -141,6 +141,72 @@ void linear_tokmajor(const PackedConv& w, Plane x, float* y, int ldy, hipStream_
 int default_bert_bfs_parts();
 bool flash_parts_enabled();   // vits.cpp: the flow's attention reads pre-split keys / values
 int set_flash_parts(int on);
+
+// The VITS encoders' attention (vits.cpp; built here for run_encoder and sbv2_debug_vits_attention alike)
+constexpr int kTextGap = 16;   // >= 9: DDSConv depthwise dilation 3^2 with k=3
+constexpr int kFrameGap = 4;   // >= 25/8 frames: widest decoder tap offset (k=11, d=5) at the first upsampled rate
+struct AttnPlan {
+    int ng = 0, maxT = 0, lds = 0;
+    AttnGroup* d_ag = nullptr;
+    GemmGroup* d_st = nullptr;
+    GemmGroup* d_pv = nullptr;
+    float* S = nullptr;
+    float* PW = nullptr;
+    double flops = 0;  // algorithmic FLOP of one grouped product over all (utterance, head) problems
+};
+// one group per (utterance, head) of the packed layout; scores: the unfused path's T x T score blocks and probability bands are allocated as well
+AttnPlan make_attn_plan(const SegLayout& lay, int H, int heads, int ld, int window, Arena& ar, hipStream_t stream, bool scores);
+// C[groups] = alpha A^T B per GemmGroup (gemm_conv.hip): the unfused attention's S^T = K^T Q and ctx = V P^T
+void grouped_gemm(const float* A, int lda, const float* B, int ldb, float* C, int ldc, const GemmGroup* grp, int ng, int maxM, int maxN,
+                  float alpha, double flops, hipStream_t s);
+// Which fused kernel an encoder's attention takes (same bits whichever it is): kv_parts = keys / values read as bf16 parts written by the q | k | v
+// product (vits_flash_attention_parts with `pipelined`), otherwise vits_flash_attention (split-bf16 when split_attn).  SP: the encoder's 1x1 parts code.
+struct FlashChoice {
+    bool kv_parts = false;
+    int pipelined = 1;
+};
+FlashChoice flash_choice(const AttnPlan& pl, int SP, bool split_attn, int dk);
+
+// DeBERTa's disentangled attention (bert.cpp; built here for BertModel::forward and sbv2_debug_deberta_attention alike).  Each utterance takes one class:
+// short (deberta_attention, <= 64 tokens), mid (deberta_attention128), long (deberta_attention_long) or the unfused grouped-GEMM + deberta_softmax path.
+enum DebertaAttnMode {
+    kDbAuto = -1,      // the model's per-utterance dispatch
+    kDbUnfused = 0,    // every utterance on the unfused path (SBV2_BERT_ATTN=unfused)
+    kDbShort = 1,      // every utterance on one fused kernel: an utterance it does not fit is an error
+    kDbMid = 2,
+    kDbLong = 3,
+    kDbNoLong = 4,     // the model's dispatch without the long kernel (SBV2_BERT_ATTN=nolong)
+};
+struct DebertaAttnPlan {
+    int span = 0, maxT = 0, lds = 0;
+    std::vector<int> tab;            // bucket(i - j) at tab[maxT - 1 + i - j]
+    int win_lo = 0, wlen = 0, win_ld = 0;        // bucket window reachable by the batch (long kernel, unfused path)
+    int win_lo_s = 0, wlen_s = 1;                // ... by |i - j| <= 63 (short kernel)
+    int win_lo_m = 0, wlen_m = 1;                // ... by |i - j| <= 127 (mid kernel)
+    std::vector<AttnGroup> ag_s, ag_m, ag_f, ag_l;   // short / mid / long fused, grouped-GEMM path
+    std::vector<GemmGroup> g_st, g_c2p, g_p2c, g_pv;
+    int64_t s_off = 0, c_off = 0, p_off = 0;
+    int maxTL = 0, maxTF = 0;
+    double fl_tt = 0, fl_tw = 0;     // algorithmic FLOP of the grouped products (profiling only)
+    // device side (upload_table, then upload_groups)
+    int* d_tab = nullptr;
+    AttnGroup *d_agS = nullptr, *d_agM = nullptr, *d_agF = nullptr, *d_agL = nullptr;
+    GemmGroup* d_g = nullptr;        // [4][ngL]: S^T, c2p, p2c, PV
+    float *S = nullptr, *C2P = nullptr, *P2C = nullptr, *VT = nullptr;
+    int ngS() const { return (int)ag_s.size(); }
+    int ngM() const { return (int)ag_m.size(); }
+    int ngF() const { return (int)ag_f.size(); }
+    int ngL() const { return (int)ag_l.size(); }
+    void upload_table(Arena& ar, hipStream_t stream);
+    void upload_groups(Arena& ar, hipStream_t stream, int N, int H);   // also allocates the unfused path's score blocks and V^T
+};
+// lay: the packed batch; ld: pitch of the q / k / v planes; ldp: pitch of the position planes [H][2 span]
+DebertaAttnPlan make_deberta_attn_plan(const SegLayout& lay, int H, int heads, int buckets, int max_rel, int ld, int ldp, int mode);
+// the fused kernels' launches of a plan (short, mid, long), then the unfused path's (VT: V token-major [N][ldvt], filled by the caller)
+void deberta_attention_fused(const DebertaAttnPlan& ap, const float* Q, const float* K, const float* V, int ld, const float* posk, const float* posq,
+                             int ldp, int d, float inv_scale, const unsigned char* tok_mask, float* ctx, int ldc, hipStream_t s);
+void deberta_attention_unfused(const DebertaAttnPlan& ap, const float* Q, const float* K, int ld, const float* VT, int ldvt, const float* posk,
+                               const float* posq, int ldp, int d, float inv_scale, const unsigned char* tok_mask, float* ctx, int ldc, hipStream_t s);
 struct BertConfig {
     int vocab, hidden, layers, heads, inter, buckets, max_rel;
     float eps;

@@ -2,6 +2,7 @@
 // and the probe tools.  The decoder's kernels get their parameters from the decoder's own builders (decoder_cl.cpp: pack_decoder_conv, conv_cl_params,
 // step_params, branch_params), so a test of a kernel also tests what the decoder launches.
 #include <cstring>
+#include <limits>
 
 #include "api_internal.h"
 
@@ -83,6 +84,56 @@ void read_parts(const SplitClPlanes& sp, float* out) {
         for (int64_t n = 0; n < sp.N; ++n) {
             const size_t hi = ((size_t)(c >> 4) * 2 * rows + sp.front + n) * 16 + (c & 15);
             out[(size_t)c * sp.N + n] = f(h[hi]) + f(h[hi + (size_t)rows * 16]);
+        }
+}
+
+// Packed planes of the attention hooks: host [R][sum lens] (utterances concatenated) <-> rows of a device plane at the layout's columns.  poison: every
+// column outside an utterance, up to the pitch, holds NaN (all bits set) instead of zero.
+void upload_packed(const float* x, const SegLayout& lay, Plane P, bool poison) {
+    HIP_CHECK(hipMemset(P.p, poison ? 0xFF : 0, sizeof(float) * (size_t)P.C * P.ld));
+    int64_t total = 0;
+    for (int v : lay.len) total += v;
+    int64_t e = 0;
+    for (int u = 0; u < lay.n; ++u) {
+        HIP_CHECK(hipMemcpy2D(P.p + lay.start[u], sizeof(float) * P.ld, x + e, sizeof(float) * total, sizeof(float) * lay.len[u], P.C, hipMemcpyHostToDevice));
+        e += lay.len[u];
+    }
+}
+// V token-major [N][ldvt] (the unfused path's V^T operand; linear_tokmajor in the model), same poison rule
+DevMem upload_tokmajor(const float* x, const SegLayout& lay, int R, bool poison) {
+    std::vector<float> t((size_t)lay.L * R, poison ? std::numeric_limits<float>::quiet_NaN() : 0.f);
+    int64_t total = 0;
+    for (int v : lay.len) total += v;
+    int64_t e = 0;
+    for (int u = 0; u < lay.n; ++u)
+        for (int j = 0; j < lay.len[u]; ++j, ++e)
+            for (int c = 0; c < R; ++c) t[(size_t)(lay.start[u] + j) * R + c] = x[(size_t)c * total + e];
+    return DevMem(t.data(), sizeof(float) * t.size());
+}
+// ctx fill before the launch: the sentinel (poison) or zero (as the models clear it)
+constexpr unsigned char kCtxSentinel = 0x5A;
+void download_packed(Plane P, const SegLayout& lay, bool poison, float* y, int64_t* stray) {
+    std::vector<float> h((size_t)P.C * P.ld);
+    HIP_CHECK(hipMemcpy(h.data(), P.p, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
+    int64_t total = 0;
+    for (int v : lay.len) total += v;
+    std::vector<unsigned char> inside(P.ld, 0);
+    int64_t e = 0;
+    for (int u = 0; u < lay.n; ++u) {
+        for (int c = 0; c < P.C; ++c) std::memcpy(y + (size_t)c * total + e, &h[(size_t)c * P.ld + lay.start[u]], sizeof(float) * lay.len[u]);
+        std::memset(&inside[lay.start[u]], 1, lay.len[u]);
+        e += lay.len[u];
+    }
+    if (!stray) return;
+    *stray = 0;
+    if (!poison) return;
+    uint32_t sent;
+    std::memset(&sent, kCtxSentinel, 4);
+    for (int c = 0; c < P.C; ++c)
+        for (int n = 0; n < P.ld; ++n) {
+            uint32_t b;
+            std::memcpy(&b, &h[(size_t)c * P.ld + n], 4);
+            *stray += !inside[n] && b != sent;
         }
 }
 
@@ -552,6 +603,114 @@ int sbv2_debug_time_conv1d(int device, int64_t cin, int64_t cout, int64_t k, int
     auto run = [&] { conv_plain(pc, X, Y, (int)dilation, (int)(dilation * (k - 1) / 2), nullptr, 1, nullptr, ACT_NONE, 1.0f); };
     for (int i = 0; i < 3; ++i) run();
     *ms = time_ms(iters, run);
+    API_END
+}
+
+int sbv2_debug_vits_attention(int device, const float* q, const float* k, const float* v, const float* erk, const float* erv, const int64_t* lens, int nutt,
+                              int64_t heads, int64_t dk, int64_t window, int layout, int variant, int poison, float* ctx, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(q && k && v && erk && erv && lens && ctx && nutt >= 1 && heads >= 1 && dk >= 1 && window >= 0 && (layout == 0 || layout == 1) &&
+                     variant >= -1 && variant <= 5,
+                 "bad arguments");
+    std::vector<int> L(nutt);
+    for (int i = 0; i < nutt; ++i) {
+        SBV2_REQUIRE(lens[i] >= 1 && lens[i] < (1 << 20), "bad sequence length");
+        L[i] = (int)lens[i];
+    }
+    const int H = (int)(heads * dk), nw = 2 * (int)window + 1;
+    Arena ar;
+    // the text encoder's layout (kTextGap, columns rounded to 4) or the flow's (kFrameGap, rounded to 32), as VitsModel builds them
+    const SegLayout lay = layout ? make_layout(L, kFrameGap, ar, nullptr, nullptr, 32) : make_layout(L, kTextGap, ar, nullptr);
+    const int N = lay.L;
+    Plane QKV = ar.plane(3 * H, N), C = ar.plane(H, N);
+    Plane Q = QKV.rows(0, H), K = QKV.rows(H, H), V = QKV.rows(2 * H, H);
+    upload_packed(q, lay, Q, poison);
+    upload_packed(k, lay, K, poison);
+    upload_packed(v, lay, V, poison);
+    DevMem d_erk(erk, sizeof(float) * nw * dk), d_erv(erv, sizeof(float) * nw * dk);
+    const AttnPlan pl = make_attn_plan(lay, H, (int)heads, QKV.ld, (int)window, ar, nullptr, variant == 0);
+    HIP_CHECK(hipMemset(C.p, poison ? kCtxSentinel : 0, sizeof(float) * (size_t)H * C.ld));
+    const float qscale = 1.0f / std::sqrt((float)dk);   // as run_encoder
+    // keys / values as the bf16 parts the flow's q | k | v product writes next to the f32 plane (its epilogue: split_store4's bf16 split, the one
+    // split_planes uses), in the same place: rows H .. 3 H of a [3 H][N] split plane
+    auto kv_parts = [&]() {
+        SplitPlanes s = alloc_split(ar, 2, 3 * H, N);
+        HIP_CHECK(hipMemset(s.p, poison ? 0xFF : 0, (size_t)2 * s.pstride * 2));
+        split_planes(QKV.rows(H, 2 * H), s.rows(H, 2 * H), nullptr);
+        return s;
+    };
+    const bool split_attn = dk % 16 == 0;   // run_encoder: the flow's split-bf16 attention takes head dimensions of whole 16-row steps
+    const int dki = (int)dk, w = (int)window;
+    if (variant == -1) {
+        const FlashChoice fc = flash_choice(pl, kPartsF16x3, split_attn, dki);   // the flow: its 1x1 products on pre-split operands
+        if (fc.kv_parts) vits_flash_attention_parts(pl.d_ag, pl.ng, pl.maxT, Q.p, Q.ld, kv_parts(), H, 2 * H, C.p, C.ld, dki, d_erk.f(), d_erv.f(), w, qscale,
+                                                    nullptr, fc.pipelined);
+        else vits_flash_attention(pl.d_ag, pl.ng, pl.maxT, Q.p, K.p, V.p, Q.ld, C.p, C.ld, dki, d_erk.f(), d_erv.f(), w, qscale, split_attn, nullptr);
+    } else if (variant == 0) {
+        DevMem vt = upload_tokmajor(v, lay, H, poison);
+        grouped_gemm(K.p, K.ld, Q.p, Q.ld, pl.S, pl.lds, pl.d_st, pl.ng, pl.maxT, pl.maxT, qscale, pl.flops, nullptr);
+        vits_softmax(pl.d_ag, pl.ng, pl.maxT, pl.S, Q.p, Q.ld, dki, d_erk.f(), w, qscale, pl.PW, nullptr);
+        grouped_gemm(vt.f(), H, pl.S, pl.lds, C.p, C.ld, pl.d_pv, pl.ng, dki, pl.maxT, 1.0f, pl.flops, nullptr);
+        vits_relv_add(pl.d_ag, pl.ng, pl.maxT, C.p, C.ld, dki, d_erv.f(), w, pl.PW, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+    } else if (variant <= 2) {
+        vits_flash_attention(pl.d_ag, pl.ng, pl.maxT, Q.p, K.p, V.p, Q.ld, C.p, C.ld, dki, d_erk.f(), d_erv.f(), w, qscale, variant == 2, nullptr);
+    } else {
+        SBV2_REQUIRE(variant == 3 || flash_pipelined_usable(dki), "k_vits_flash_x3q does not take this head dimension");
+        vits_flash_attention_parts(pl.d_ag, pl.ng, pl.maxT, Q.p, Q.ld, kv_parts(), H, 2 * H, C.p, C.ld, dki, d_erk.f(), d_erv.f(), w, qscale, nullptr,
+                                   variant == 3 ? 0 : (variant == 4 ? 3 : 2));
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    download_packed(C, lay, poison, ctx, stray);
+    API_END
+}
+
+int sbv2_debug_deberta_attention(int device, const float* q, const float* k, const float* v, const float* pos_k, const float* pos_q, const int64_t* lens,
+                                 int nutt, int64_t heads, int64_t d, int64_t buckets, int64_t max_rel, const uint8_t* tok_mask, int64_t gap, int variant,
+                                 int poison, float* ctx, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(q && k && v && pos_k && pos_q && lens && ctx && nutt >= 1 && heads >= 1 && d >= 1 && gap >= 0 && variant >= -1 && variant <= 3 &&
+                     (buckets > 0 || max_rel > 0),
+                 "bad arguments");
+    std::vector<int> L(nutt);
+    int64_t total = 0;
+    for (int i = 0; i < nutt; ++i) {
+        SBV2_REQUIRE(lens[i] >= 1 && lens[i] < (1 << 20), "bad sequence length");
+        L[i] = (int)lens[i];
+        total += lens[i];
+    }
+    const int H = (int)(heads * d), span = (int)(buckets > 0 ? buckets : max_rel);
+    std::vector<unsigned char> am((size_t)total, 1);
+    if (tok_mask)
+        for (int64_t e = 0; e < total; ++e) am[e] = tok_mask[e] != 0;
+    Arena ar;
+    const SegLayout lay = make_layout(L, (int)gap, ar, nullptr, am.data());   // as BertModel::forward
+    const int N = lay.L;
+    Plane QKV = ar.plane(3 * H, N), C = ar.plane(H, N), PK = ar.plane(H, 2 * span), PQ = ar.plane(H, 2 * span);
+    Plane Q = QKV.rows(0, H), K = QKV.rows(H, H), V = QKV.rows(2 * H, H);
+    upload_packed(q, lay, Q, poison);
+    upload_packed(k, lay, K, poison);
+    upload_packed(v, lay, V, poison);
+    for (Plane* P : {&PK, &PQ}) {
+        HIP_CHECK(hipMemset(P->p, 0, sizeof(float) * (size_t)H * P->ld));
+        HIP_CHECK(hipMemcpy2D(P->p, sizeof(float) * P->ld, P == &PK ? pos_k : pos_q, sizeof(float) * 2 * span, sizeof(float) * 2 * span, H,
+                              hipMemcpyHostToDevice));
+    }
+    DebertaAttnPlan ap = make_deberta_attn_plan(lay, H, (int)heads, (int)buckets, (int)max_rel, QKV.ld, PK.ld, variant);
+    ap.upload_table(ar, nullptr);
+    ap.upload_groups(ar, nullptr, N, H);
+    HIP_CHECK(hipMemset(C.p, poison ? kCtxSentinel : 0, sizeof(float) * (size_t)H * C.ld));
+    const float inv_scale = 1.0f / std::sqrt((float)d * 3.0f);   // as BertModel::forward
+    deberta_attention_fused(ap, Q.p, K.p, V.p, QKV.ld, PK.p, PQ.p, PK.ld, (int)d, inv_scale, lay.d_mask, C.p, C.ld, nullptr);
+    if (ap.ngL()) {
+        DevMem vt = upload_tokmajor(v, lay, H, poison);
+        HIP_CHECK(hipMemcpy(ap.VT, vt.p, sizeof(float) * (size_t)N * H, hipMemcpyDeviceToDevice));
+        deberta_attention_unfused(ap, Q.p, K.p, QKV.ld, ap.VT, H, PK.p, PQ.p, PK.ld, (int)d, inv_scale, lay.d_mask, C.p, C.ld, nullptr);
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    download_packed(C, lay, poison, ctx, stray);
     API_END
 }
 

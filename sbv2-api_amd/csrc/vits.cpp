@@ -24,20 +24,6 @@ bool flash_parts_enabled() { return g_flash_parts.load(std::memory_order_relaxed
 static int flash_parts_mode() { return g_flash_parts.load(std::memory_order_relaxed); }
 int set_flash_parts(int on) { return g_flash_parts.exchange(on); }
 
-static const int kTextGap = 16;   // >= 9: DDSConv depthwise dilation 3^2 with k=3
-static const int kFrameGap = 4;   // >= 25/8 frames: widest decoder tap offset (k=11, d=5) at the first upsampled rate
-
-namespace {
-struct AttnPlan {
-    int ng = 0, maxT = 0, lds = 0;
-    AttnGroup* d_ag = nullptr;
-    GemmGroup* d_st = nullptr;
-    GemmGroup* d_pv = nullptr;
-    float* S = nullptr;
-    float* PW = nullptr;
-    double flops = 0;  // algorithmic FLOP of one grouped product over all (utterance, head) problems
-};
-
 AttnPlan make_attn_plan(const SegLayout& lay, int H, int heads, int ld, int window, Arena& ar, hipStream_t stream, bool scores) {
     AttnPlan pl;
     const int dk = H / heads;
@@ -99,7 +85,24 @@ void grouped_gemm(const float* A, int lda, const float* B, int ldb, float* C, in
     p.flops_hint = flops;
     launch_conv(p, s);
 }
-}  // namespace
+
+// The split-bf16 attention reads its keys / values as bf16 hi / lo planes written by the q | k | v product's epilogue next to the f32
+// plane (attn_flash.hip, k_vits_flash_x3p: no conversion per key tile; the same bits as converting while staging).
+// Which kernel (same bits, so the choice is free).  The software-pipelined kernel on pre-split tiles (k_vits_flash_x3q, attn_flash.hip) at every size when
+// the head dimension fits its DMA blocks: 4-wave workgroups while they leave at most one per CU (a single utterance: 58 us per launch at 897 frames
+// against 84 for k_vits_flash_x3p and ~80 for the converting kernel), 8-wave workgroups beyond (32 x 897 frames: 84 us against 113; the q | k | v product
+// then writes q as f32 and k / v as parts only: the same bytes).  Otherwise the un-pipelined pre-split kernel from 4096 frames (at 897
+// frames x 32 it is slower than converting, 138 against 124 us; at 14 001 it wins) and for launches of <= 64 workgroups; the converting kernel for the rest.
+// set_flash_parts: 2 = parts at every length, 3 = ... on the un-pipelined kernel, 4 = ... on the 8-wave shape, 0 = never (the tests).
+FlashChoice flash_choice(const AttnPlan& pl, int SP, bool split_attn, int dk) {
+    constexpr int parts_min_t = 4096, parts_max_wgs = 64;
+    const int64_t attn_wgs = (int64_t)((pl.maxT + 127) / 128) * pl.ng;
+    FlashChoice c;
+    c.kv_parts = SP && split_attn && flash_parts_enabled() &&
+                 ((flash_parts_mode() != 3 && flash_pipelined_usable(dk)) || pl.maxT >= parts_min_t || attn_wgs <= parts_max_wgs || flash_parts_mode() >= 2);
+    c.pipelined = flash_parts_mode() == 3 ? 0 : (flash_parts_mode() == 4 ? 2 : 1);
+    return c;
+}
 
 VitsModel::Encoder VitsModel::load_encoder(const std::string& p, int n_layers) {
     Encoder e;
@@ -402,18 +405,8 @@ void VitsModel::run_encoder(const Encoder& e, Plane x, const SegLayout& lay, con
         Cs = alloc_split(ar, SP, H, N);
         split_planes(x, Xs, stream_);
     }
-    // the split-bf16 attention reads its keys / values as bf16 hi / lo planes written by the q | k | v product's epilogue next to the f32
-    // plane (attn_flash.hip, k_vits_flash_x3p: no conversion per key tile; the same bits as converting while staging)
-    // Which kernel (same bits, so the choice is free).  The software-pipelined kernel on pre-split tiles (k_vits_flash_x3q, attn_flash.hip) at every size when
-    // the head dimension fits its DMA blocks: 4-wave workgroups while they leave at most one per CU (a single utterance: 58 us per launch at 897 frames
-    // against 84 for k_vits_flash_x3p and ~80 for the converting kernel), 8-wave workgroups beyond (32 x 897 frames: 84 us against 113; the q | k | v product
-    // then writes q as f32 and k / v as parts only: the same bytes).  Otherwise the un-pipelined pre-split kernel from 4096 frames (at 897
-    // frames x 32 it is slower than converting, 138 against 124 us; at 14 001 it wins) and for launches of <= 64 workgroups; the converting kernel for the rest.
-    // set_flash_parts: 2 = parts at every length, 3 = ... on the un-pipelined kernel, 0 = never (the tests).
-    constexpr int parts_min_t = 4096, parts_max_wgs = 64;
-    const int64_t attn_wgs = (int64_t)((pl.maxT + 127) / 128) * pl.ng;
-    const bool kv_parts = SP && split_attn && flash_parts_enabled() &&
-                          ((flash_parts_mode() != 3 && flash_pipelined_usable(dk)) || pl.maxT >= parts_min_t || attn_wgs <= parts_max_wgs || flash_parts_mode() >= 2);
+    const FlashChoice fc = flash_choice(pl, SP, split_attn, dk);
+    const bool kv_parts = fc.kv_parts;
     if (kv_parts) QKVs = alloc_split(ar, 2, 3 * H, N);
     // Large batches: the FFN pair on conv_clx.hip (pre-split chunk-major operands by LDS-DMA instead of conv_cl's transposing register staging):
     // x is split once per layer from its k-major plane (split_cl_km), conv_1's epilogue writes relu(.) as conv_2's operand parts, conv_2 writes
@@ -439,7 +432,7 @@ void VitsModel::run_encoder(const Encoder& e, Plane x, const SegLayout& lay, con
             else conv_plain(L.attn.qkv, x, QKV, 1, 0, nullptr, 1, stream_);
             if (kv_parts)
                 vits_flash_attention_parts(pl.d_ag, pl.ng, pl.maxT, Q.p, Q.ld, QKVs, H, 2 * H, ctx.p, ctx.ld, dk, L.attn.erk, L.attn.erv, cfg_.window,
-                                           qscale, stream_, flash_parts_mode() == 3 ? 0 : (flash_parts_mode() == 4 ? 2 : 1));
+                                           qscale, stream_, fc.pipelined);
             else
                 vits_flash_attention(pl.d_ag, pl.ng, pl.maxT, Q.p, K.p, Vp.p, Q.ld, ctx.p, ctx.ld, dk, L.attn.erk, L.attn.erv, cfg_.window, qscale,
                                      split_attn, stream_);
