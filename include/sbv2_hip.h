@@ -173,6 +173,41 @@ int sbv2_pipeline_fetch_flac(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_fo
 int sbv2_debug_flac_encode(int device, const int16_t* x, const int64_t* lens, int nsig, int32_t sample_rate, uint8_t* dst, int64_t capacity,
                            int64_t* out_bytes);
 
+/* ---- new: loudness normalisation (ITU-R BS.1770-4 integrated loudness, EBU R128 / ATSC A/85 style targets) ON THE DEVICE.  Measured in f64
+ * on each output signal y of sbv2_pipeline_fetch_pcm_format (resampled to fs, before any gain or quantisation; mono, channel weight 1):
+ *   K-weighting: shelf (f0 1681.974450955533 Hz, G 3.999843853973347 dB, Q 0.7071752369554196) then high-pass (f0 38.13547087602444 Hz,
+ *     Q 0.5003270373238773), biquads derived at fs in the libebur128 form, transposed direct form II from zero state -> w;
+ *   S = fs / 10; quarter q = sum w^2 over [q S, (q + 1) S) (complete quarters only); block j = quarters j..j+3, z_j = sum / (4 S),
+ *     l_j = -0.691 + 10 log10 z_j; blocks with l_j > -70 pass the absolute gate; Gr = -0.691 + 10 log10(mean z of those) - 10; blocks with
+ *     l_j > Gr pass as well; L = -0.691 + 10 log10(mean z of the blocks passing both) LUFS, -inf when none does.  A signal shorter than 4 S
+ *     samples is one block over its whole length; an empty one gives -inf.
+ *   True peak: TP = 20 log10 max |z| dBTP, z = scipy.signal.resample_poly(y, 4, 1, window = h4 / 4), h4[n] = sinc(n / 4) I0(8.6 sqrt(1 -
+ *     (n / 48)^2)) / I0(8.6), n in [-48, 48], each phase (n mod 4) scaled to sum to 1; -inf for silence.  TP >= the sample peak.
+ *   Gain: G = min(target - L, ceiling - TP) dB when L is finite, else 0 (G may be positive); output y 10^(G / 20), then the f32 cast or the
+ *     s16 quantiser of sbv2_pcm_format.  With ceiling <= 0 s16 never clips.
+ * The sbv2_stream_* and sbv2_node_* paths have no loudness: integrated loudness needs the whole signal (as peak normalisation does). */
+typedef struct sbv2_loudness {
+    double target_lufs;          /* [-70, -5] */
+    double true_peak_max_dbtp;   /* [-20, 0] */
+} sbv2_loudness;
+/* The signals of sbv2_pipeline_fetch_pcm_format (same place / joined_len rules; fmt->normalize must be 0), each measured and scaled as above;
+ * out-of-range or non-finite ln fields are refused.  ln == NULL: measure only (the bytes equal sbv2_pipeline_fetch_pcm_format's).
+ * stats (NULL or 3 doubles per signal): L before the gain (LUFS), TP before the gain (dBTP), the applied G (dB).  Two fetches of one run give
+ * identical bytes and stats. */
+int sbv2_pipeline_fetch_pcm_loudness(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_loudness* ln,
+                                     const int64_t* place, int64_t joined_len, void* dst, int64_t capacity_bytes, int64_t* out_lens,
+                                     double* stats);
+/* The same signals as FLAC streams (fmt->encoding must be 1), exactly as sbv2_pipeline_fetch_flac encodes them; stats as above. */
+int sbv2_pipeline_fetch_flac_loudness(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_loudness* ln,
+                                      const int64_t* place, int64_t joined_len, uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes,
+                                      double* stats);
+/* Host only: the K-weighting at a supported rate: coef[10] = shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2 (a0 = 1). */
+int sbv2_loudness_kweight(int32_t sample_rate, double* coef);
+/* Test hook: the device meter on host f64 signals (nsig >= 1 signals of lens[i] samples, back to back in x) on `device` at sample_rate (a rate
+ * of sbv2_pcm_format; no resampling); stats (3 doubles per signal) as above, G from ln (NULL: 0). */
+int sbv2_debug_loudness(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_loudness* ln,
+                        double* stats);
+
 /* ---- sbv2file.rs:15-37 `parse_sbv2file(bytes) -> (style_vectors, vits2)`: a .sbv2 file is zstd(tar{version.txt, model.onnx,
  * style_vectors.json}) (writer: scripts/convert/convert_model.py:156-175).  Both outputs are owned copies (sbv2_bytes_free).
  * Errors: "model not found: style_vectors" / "model not found: vits2" (Error::ModelNotFoundError, sbv2file.rs:31-36). ------------------- */
@@ -237,7 +272,8 @@ int sbv2_stream_begin(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch,
 int sbv2_stream_next(sbv2_stream* s, float* dst, int64_t capacity, int64_t* n);
 /* Streaming with an output format (see sbv2_pcm_format): inputs as sbv2_stream_begin; *total_samples at fmt->sample_rate; fmt->normalize must be 0
  * (a stream cannot know the peak ahead).  Chunk c of native samples [a, b) emits output samples [ceil(a L / M), ceil(b L / M)), so the chunks
- * concatenate to the formatted whole utterance.  sbv2_stream_next is refused on such a stream, sbv2_stream_next_format on any other. */
+ * concatenate to the formatted whole utterance.  sbv2_stream_next is refused on such a stream, sbv2_stream_next_format on any other.  There is
+ * no loudness (sbv2_loudness) on a stream either: integrated loudness needs the whole signal. */
 int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
                              const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, sbv2_stream** out, int64_t* total_samples);
 /* next chunk -> dst (host; capacity_bytes); *n = samples written, 0 at the end */

@@ -24,6 +24,11 @@ class Sbv2PcmFormat(C.Structure):
     _fields_ = [("sample_rate", C.c_int32), ("encoding", C.c_int32), ("normalize", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Sbv2Loudness(C.Structure):
+    """struct sbv2_loudness (include/sbv2_hip.h)."""
+    _fields_ = [("target_lufs", C.c_double), ("true_peak_max_dbtp", C.c_double)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -68,6 +73,12 @@ SYMBOLS = {
     "sbv2_flac_bound": (C.c_int64, [C.POINTER(Sbv2PcmFormat), C.c_int64]),
     "sbv2_pipeline_fetch_flac": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, C.c_int64, C.c_void_p, C.c_int64, i64p]),
     "sbv2_debug_flac_encode": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, i64p]),
+    "sbv2_pipeline_fetch_pcm_loudness": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2PcmFormat), C.POINTER(Sbv2Loudness), i64p, C.c_int64,
+                                                   C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double)]),
+    "sbv2_pipeline_fetch_flac_loudness": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2PcmFormat), C.POINTER(Sbv2Loudness), i64p, C.c_int64,
+                                                    C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double)]),
+    "sbv2_loudness_kweight": (C.c_int, [C.c_int32, C.POINTER(C.c_double)]),
+    "sbv2_debug_loudness": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Loudness), C.POINTER(C.c_double)]),
     "sbv2_host_alloc": (C.c_void_p, [C.c_size_t]),
     "sbv2_host_free": (None, [C.c_void_p]),
     "sbv2_deal": (C.c_int, [C.c_int64, i64p, C.c_int, C.POINTER(C.c_int32)]),

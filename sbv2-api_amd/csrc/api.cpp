@@ -405,6 +405,25 @@ static PcmFmtSpec flac_spec(const sbv2_pcm_format* fmt) {
     return spec;
 }
 
+static FlacEncoder& flac_encoder(sbv2_pipeline* p, int ctx, int device) {
+    if ((int)p->flacs.size() < p->contexts()) p->flacs.resize(p->contexts());
+    if (!p->flacs[ctx]) p->flacs[ctx].reset(new FlacEncoder(device));
+    return *p->flacs[ctx];
+}
+
+// the s16 signals dev[total] of a fetch -> FLAC streams into host dst (reads back the sizes: synchronises the stream)
+static void encode_flac(sbv2_pipeline* p, int ctx, VitsModel& vm, const PcmFmtSpec& spec, const void* dev, const std::vector<int64_t>& outs,
+                        uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes) {
+    FlacEncoder& enc = flac_encoder(p, ctx, vm.device());
+    std::vector<int64_t> offs(outs.size()), bytes;
+    for (size_t i = 1; i < outs.size(); ++i) offs[i] = offs[i - 1] + outs[i - 1];
+    const int64_t nbytes = enc.encode(static_cast<const int16_t*>(dev), offs, outs, spec.rate, vm.stream(), &bytes);
+    SBV2_REQUIRE(capacity_bytes >= nbytes, "FLAC buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(nbytes) + " bytes");
+    HIP_CHECK(hipMemcpyAsync(dst, enc.output(), (size_t)nbytes, hipMemcpyDeviceToHost, vm.stream()));
+    HIP_CHECK(hipStreamSynchronize(vm.stream()));
+    for (size_t i = 0; i < bytes.size(); ++i) out_bytes[i] = bytes[i];
+}
+
 int64_t sbv2_flac_bound(const sbv2_pcm_format* fmt, int64_t n_native) {
     try {
         const PcmFmtSpec spec = flac_spec(fmt);
@@ -434,16 +453,80 @@ int sbv2_pipeline_fetch_flac(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_fo
     PcmFormatter& f = formatter(p, ctx, vm.device());
     void* dev = f.out_buffer((size_t)std::max<int64_t>(total, 1) * spec.bytes(), vm.stream());
     f.run(spec, pieces, sig, total, dev, 0, vm.stream());
-    if ((int)p->flacs.size() < p->contexts()) p->flacs.resize(p->contexts());
-    if (!p->flacs[ctx]) p->flacs[ctx].reset(new FlacEncoder(vm.device()));
-    FlacEncoder& enc = *p->flacs[ctx];
-    std::vector<int64_t> offs(outs.size()), bytes;
-    for (size_t i = 1; i < outs.size(); ++i) offs[i] = offs[i - 1] + outs[i - 1];
-    const int64_t nbytes = enc.encode(static_cast<const int16_t*>(dev), offs, outs, spec.rate, vm.stream(), &bytes);
-    SBV2_REQUIRE(capacity_bytes >= nbytes, "FLAC buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(nbytes) + " bytes");
-    HIP_CHECK(hipMemcpyAsync(dst, enc.output(), (size_t)nbytes, hipMemcpyDeviceToHost, vm.stream()));
+    encode_flac(p, ctx, vm, spec, dev, outs, dst, capacity_bytes, out_bytes);
+    API_END
+}
+
+// ---- loudness (loudness.hip) ----
+int sbv2_loudness_kweight(int32_t sample_rate, double* coef) {
+    API_BEGIN
+    SBV2_REQUIRE(coef, "bad arguments");
+    loudness_kweight(sample_rate, coef);
+    API_END
+}
+
+static PcmFmtSpec loudness_format(const sbv2_pcm_format* fmt) {
+    const PcmFmtSpec spec = pcm_format_spec(fmt);
+    SBV2_REQUIRE(!spec.normalize, "loudness normalisation replaces peak normalisation: fmt->normalize must be 0");
+    return spec;
+}
+
+// the signals of a fetch, formatted with their loudness gains into the formatter's output buffer (enqueued on the run's stream); the
+// stats reach meter.stats_host() once the stream is synchronised
+static void* format_loudness(sbv2_pipeline* p, int ctx, VitsModel& vm, const PcmFmtSpec& spec, const LoudnessSpec& ln,
+                             const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, LoudnessMeter** meter) {
+    HIP_CHECK(hipSetDevice(vm.device()));
+    if ((int)p->meters.size() < p->contexts()) p->meters.resize(p->contexts());
+    if (!p->meters[ctx]) p->meters[ctx].reset(new LoudnessMeter(vm.device()));
+    *meter = p->meters[ctx].get();
+    PcmFormatter& f = formatter(p, ctx, vm.device());
+    void* dev = f.out_buffer((size_t)std::max<int64_t>(total, 1) * spec.bytes(), vm.stream());
+    f.run_loudness(spec, pieces, sig, total, dev, 0, vm.stream(), **meter, ln);
+    return dev;
+}
+
+int sbv2_pipeline_fetch_pcm_loudness(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_loudness* ln, const int64_t* place,
+                                     int64_t joined_len, void* dst, int64_t capacity_bytes, int64_t* out_lens, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(p && dst && out_lens, "bad arguments");
+    const PcmFmtSpec spec = loudness_format(fmt);
+    const LoudnessSpec lspec = loudness_spec(ln);
+    const int ctx = p->ctx_of(ticket);
+    VitsModel& vm = p->vm(ctx);
+    std::vector<FmtPiece> pieces;
+    std::vector<FmtSignal> sig;
+    std::vector<int64_t> outs;
+    int64_t total = 0;
+    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
+    SBV2_REQUIRE(capacity_bytes >= total * spec.bytes(),
+                 "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(total * spec.bytes()) + " bytes");
+    LoudnessMeter* meter = nullptr;
+    void* dev = format_loudness(p, ctx, vm, spec, lspec, pieces, sig, total, &meter);
+    if (total > 0) HIP_CHECK(hipMemcpyAsync(dst, dev, (size_t)total * spec.bytes(), hipMemcpyDeviceToHost, vm.stream()));
     HIP_CHECK(hipStreamSynchronize(vm.stream()));
-    for (size_t i = 0; i < bytes.size(); ++i) out_bytes[i] = bytes[i];
+    for (size_t i = 0; i < outs.size(); ++i) out_lens[i] = outs[i];
+    if (stats) std::memcpy(stats, meter->stats_host(), sizeof(double) * 3 * outs.size());
+    API_END
+}
+
+int sbv2_pipeline_fetch_flac_loudness(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_loudness* ln, const int64_t* place,
+                                      int64_t joined_len, uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(p && dst && out_bytes, "bad arguments");
+    const PcmFmtSpec spec = loudness_format(fmt);
+    SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
+    const LoudnessSpec lspec = loudness_spec(ln);
+    const int ctx = p->ctx_of(ticket);
+    VitsModel& vm = p->vm(ctx);
+    std::vector<FmtPiece> pieces;
+    std::vector<FmtSignal> sig;
+    std::vector<int64_t> outs;
+    int64_t total = 0;
+    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
+    LoudnessMeter* meter = nullptr;
+    void* dev = format_loudness(p, ctx, vm, spec, lspec, pieces, sig, total, &meter);
+    encode_flac(p, ctx, vm, spec, dev, outs, dst, capacity_bytes, out_bytes);
+    if (stats) std::memcpy(stats, meter->stats_host(), sizeof(double) * 3 * outs.size());
     API_END
 }
 

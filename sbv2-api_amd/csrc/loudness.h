@@ -1,0 +1,47 @@
+// Integrated loudness (ITU-R BS.1770-4 gating, EBU R128) and true peak of formatted signals on the device (loudness.hip): the meter of
+// sbv2_pipeline_fetch_pcm_loudness / _fetch_flac_loudness, run on the f64 signal y the normalising path of PcmFormatter leaves in HBM, and of
+// the test hook sbv2_debug_loudness.
+#pragma once
+#include "common.h"
+#include "pcm_format.h"
+
+struct sbv2_loudness;
+
+namespace sbv2 {
+
+// a checked sbv2_loudness; apply = false: measure only (G = 0)
+struct LoudnessSpec {
+    bool apply = false;
+    double target = 0.0, ceiling = 0.0;
+};
+// throws with a message for out-of-range or non-finite fields; NULL -> measure only
+LoudnessSpec loudness_spec(const sbv2_loudness* ln);
+// the K-weighting at a supported rate (libebur128 form): coef = shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2; throws for other rates
+void loudness_kweight(int rate, double coef[10]);
+
+// Device state of the meter of one execution context: the signal table (pinned + device), the per-segment K-weighting states and partial
+// sums, the per-signal true peaks, stats and gains (all grown on demand; growing synchronises the stream).
+class LoudnessMeter {
+  public:
+    explicit LoudnessMeter(int device) : device_(device) {}
+    ~LoudnessMeter();
+    LoudnessMeter(const LoudnessMeter&) = delete;
+    LoudnessMeter& operator=(const LoudnessMeter&) = delete;
+    // Enqueues on s the meter of the signals sig[i] = y[out_off, out_off + j1 - j0) (y: device f64, may be null when every signal is
+    // empty) at `rate`: K-weighting (three launches), true peak, gate.  Returns the device gains 10^(G / 20), one per signal, and enqueues
+    // the copy of the stats to the host: stats_host() holds 3 doubles per signal (L, TP, G) once s has been synchronised.
+    const double* measure(const double* y, const std::vector<FmtSignal>& sig, int rate, const LoudnessSpec& ln, hipStream_t s);
+    const double* stats_host() const { return stats_host_; }
+
+  private:
+    const std::vector<double>& tables(int rate);
+    int device_;
+    std::map<int, std::vector<double>> tables_;
+    void* host_ = nullptr;   // pinned: signal table, then the stats
+    size_t host_cap_ = 0;
+    void* dev_ = nullptr;    // device: signal table, peaks, stats, gains, then the per-segment states and partial sums
+    size_t dev_cap_ = 0;
+    double* stats_host_ = nullptr;
+};
+
+}  // namespace sbv2

@@ -25,6 +25,9 @@ int64_t pcm_format_out_len(const PcmFmtSpec& s, int64_t n);
 // branch scaled to sum to 1; h = {1} at 44100
 std::vector<double> pcm_format_prototype(int rate, int* L, int* M, int* half);
 
+// the modified Bessel function I0 (Kaiser windows)
+double bessel_i0(double x);
+
 // Input of one formatting launch.  A piece = native samples src[0, len) lying at positions [t0, t0 + len) of a signal's silent timeline;
 // a signal = output samples [j0, j1) of that timeline, written at dst[out_off ...]; its pieces are [p0, p1), sorted by t0, disjoint.
 struct FmtPiece {
@@ -35,6 +38,9 @@ struct FmtSignal {
     int64_t j0, j1, out_off;
     int32_t p0, p1;
 };
+
+class LoudnessMeter;   // loudness.h
+struct LoudnessSpec;
 
 // Device state of the formatting launches of one execution context: the polyphase tables (per rate, built once), the tables of pieces /
 // signals (one pinned + device pair per `slot`: a slot's host copy is rewritten only once the launch that used it has completed), the
@@ -50,8 +56,14 @@ class PcmFormatter {
     // enqueues the formatting of `sig` on `s`: total = sum of the signals' j1 - j0 samples into dst_dev (device, total * spec.bytes() bytes)
     void run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
              int slot, hipStream_t s);
+    // the same with a loudness gain (spec.normalize must be 0): y in f64, meter.measure(y) (loudness.hip), then y times each signal's gain.
+    // Runs the meter also when every signal is empty.
+    void run_loudness(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
+                      void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, const LoudnessSpec& ln);
 
   private:
+    void run_impl(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
+                  int slot, hipStream_t s, LoudnessMeter* meter, const LoudnessSpec* ln);
     struct Slot {
         void* host = nullptr;
         void* dev = nullptr;

@@ -17,6 +17,7 @@
 #include <numeric>
 
 #include "../../include/sbv2_hip.h"
+#include "loudness.h"
 #include "pcm_format.h"
 
 namespace sbv2 {
@@ -30,16 +31,6 @@ constexpr double kCutoff = 0.45, kBeta = 8.6;
 bool branch_major() {
     static const bool on = getenv("SBV2_PCM_TAPS") && std::string(getenv("SBV2_PCM_TAPS")) == "branch";
     return on;
-}
-
-double bessel_i0(double x) {
-    double sum = 1.0, term = 1.0;
-    for (int k = 1; k < 500; ++k) {
-        term *= (x / (2.0 * k)) * (x / (2.0 * k));
-        sum += term;
-        if (term < 1e-17 * sum) break;
-    }
-    return sum;
 }
 
 struct KArgs {
@@ -117,7 +108,7 @@ __device__ __forceinline__ short quantise(double v) {
 }
 
 // ENC 0: f32 out, 1: s16 out, 2: f64 y into dst + per-signal max |y| for the normalising pass (atomicMax on the bit pattern of a non-negative
-// double: exact and order-independent, so the gain is the same on every run)
+// double: exact and order-independent, so the gain is the same on every run), 3: f64 y alone (the loudness path: its meter finds the peak)
 template <int ENC>
 __global__ __launch_bounds__(256) void k_pcm_resample(KArgs a, void* dst, unsigned long long* peak) {
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -129,6 +120,8 @@ __global__ __launch_bounds__(256) void k_pcm_resample(KArgs a, void* dst, unsign
         if (live) static_cast<float*>(dst)[o] = (float)y;
     } else if constexpr (ENC == 1) {
         if (live) static_cast<short*>(dst)[o] = quantise(y);
+    } else if constexpr (ENC == 3) {
+        if (live) static_cast<double*>(dst)[o] = y;
     } else {
         if (live) static_cast<double*>(dst)[o] = y;
         double m = live ? fabs(y) : 0.0;
@@ -156,7 +149,28 @@ __global__ __launch_bounds__(256) void k_pcm_gain(const double* y, const FmtSign
     else static_cast<short*>(dst)[o] = quantise(v);
 }
 
+// y * gain[s] (the loudness gain of y's signal, loudness.hip) -> f32 or s16
+template <int ENC>
+__global__ __launch_bounds__(256) void k_pcm_gain_sig(const double* y, const FmtSignal* sig, int nsig, const double* gain, int64_t total,
+                                                      void* dst) {
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const double v = y[o] * gain[find_signal(sig, nsig, o)];
+    if constexpr (ENC == 0) static_cast<float*>(dst)[o] = (float)v;
+    else static_cast<short*>(dst)[o] = quantise(v);
+}
+
 }  // namespace
+
+double bessel_i0(double x) {
+    double sum = 1.0, term = 1.0;
+    for (int k = 1; k < 500; ++k) {
+        term *= (x / (2.0 * k)) * (x / (2.0 * k));
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return sum;
+}
 
 // L, M and half of a supported rate: the one place both the table (pcm_format_prototype) and the kernel geometry (pcm_format_spec) come from
 static void rate_geometry(int rate, int* L, int* M, int* half) {
@@ -247,7 +261,22 @@ const float* PcmFormatter::taps(const PcmFmtSpec& spec, hipStream_t s) {
 
 void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
                        int slot, hipStream_t s) {
-    if (total <= 0 || sig.empty()) return;
+    run_impl(spec, pieces, sig, total, dst_dev, slot, s, nullptr, nullptr);
+}
+
+void PcmFormatter::run_loudness(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
+                                void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, const LoudnessSpec& ln) {
+    SBV2_REQUIRE(!spec.normalize, "internal: a loudness gain on a peak-normalised format");
+    run_impl(spec, pieces, sig, total, dst_dev, slot, s, &meter, &ln);
+}
+
+void PcmFormatter::run_impl(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
+                            void* dst_dev, int slot, hipStream_t s, LoudnessMeter* meter, const LoudnessSpec* ln) {
+    if (sig.empty()) return;
+    if (total <= 0) {
+        if (meter) meter->measure(nullptr, sig, spec.rate, *ln, s);
+        return;
+    }
     const float* tp = taps(spec, s);
     if ((int)slots_.size() <= slot) slots_.resize(slot + 1);
     Slot& sl = slots_[slot];
@@ -281,7 +310,7 @@ void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& piec
     a.st = branch_major() ? 1 : spec.L;
     a.total = total;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (!spec.normalize) {
+    if (!spec.normalize && !meter) {
         if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_resample<1>, grid, block, 0, s, a, dst_dev, nullptr);
         else hipLaunchKernelGGL(k_pcm_resample<0>, grid, block, 0, s, a, dst_dev, nullptr);
         HIP_CHECK(hipGetLastError());
@@ -302,6 +331,14 @@ void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& piec
         peak_cap_ = 0;
         HIP_CHECK(hipMalloc(&peak_, sizeof(unsigned long long) * sig.size()));
         peak_cap_ = sig.size();
+    }
+    if (meter) {
+        hipLaunchKernelGGL(k_pcm_resample<3>, grid, block, 0, s, a, tmp_, nullptr);
+        const double* gain = meter->measure(tmp_, sig, spec.rate, *ln, s);
+        if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain_sig<1>, grid, block, 0, s, tmp_, a.sig, a.nsig, gain, total, dst_dev);
+        else hipLaunchKernelGGL(k_pcm_gain_sig<0>, grid, block, 0, s, tmp_, a.sig, a.nsig, gain, total, dst_dev);
+        HIP_CHECK(hipGetLastError());
+        return;
     }
     HIP_CHECK(hipMemsetAsync(peak_, 0, sizeof(unsigned long long) * sig.size(), s));
     hipLaunchKernelGGL(k_pcm_resample<2>, grid, block, 0, s, a, tmp_, peak_);

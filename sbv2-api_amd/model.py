@@ -12,7 +12,8 @@ from . import _lib
 from ._lib import Sbv2Batch, Sbv2Error, check, f32p, i64p
 
 __all__ = ["Session", "load_model", "predict", "synthesize", "predict_batch", "synthesize_batch", "Pipeline", "Node", "Comm", "deal", "Sbv2Error",
-           "PcmFormat", "pcm_format_length", "pcm_format_taps", "flac_bound", "debug_flac_encode"]
+           "PcmFormat", "pcm_format_length", "pcm_format_taps", "flac_bound", "debug_flac_encode", "Loudness", "loudness_kweight",
+           "debug_loudness"]
 
 
 def _i64(a):
@@ -182,6 +183,48 @@ def debug_flac_encode(signals, sample_rate: int, device: int = 0):
     return _split_bytes(dst, got)
 
 
+class Loudness:
+    """Loudness normalisation of each output signal (struct sbv2_loudness): integrated loudness (BS.1770-4 gating) to target_lufs in
+    [-70, -5], capped so the 4x true peak stays at or below true_peak_max dBTP in [-20, 0].  Measurement and gain run on the device."""
+
+    def __init__(self, target_lufs: float, true_peak_max: float = -1.0):
+        self.target_lufs, self.true_peak_max = float(target_lufs), float(true_peak_max)
+        if not (np.isfinite(self.target_lufs) and -70.0 <= self.target_lufs <= -5.0):
+            raise Sbv2Error(f"loudness target {target_lufs} LUFS is outside [-70, -5]")
+        if not (np.isfinite(self.true_peak_max) and -20.0 <= self.true_peak_max <= 0.0):
+            raise Sbv2Error(f"true-peak ceiling {true_peak_max} dBTP is outside [-20, 0]")
+        self.c = _lib.Sbv2Loudness(self.target_lufs, self.true_peak_max)
+
+    def __repr__(self):
+        return f"Loudness({self.target_lufs}, true_peak_max={self.true_peak_max})"
+
+
+def _loudness_arg(ln):
+    return C.byref(ln.c) if ln is not None else None
+
+
+def _f64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def loudness_kweight(sample_rate: int):
+    """The library's K-weighting at a rate (host only): [shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2]."""
+    c = np.zeros(10, np.float64)
+    check(_lib.lib().sbv2_loudness_kweight(int(sample_rate), _f64p(c)))
+    return c
+
+
+def debug_loudness(signals, sample_rate: int, loudness=None, device: int = 0):
+    """Test hook: the device meter on host float64 signals at sample_rate -> stats [n, 3] (L LUFS, TP dBTP, G dB)."""
+    sigs = [np.ascontiguousarray(np.asarray(x, np.float64)).reshape(-1) for x in signals]
+    x = np.concatenate(sigs) if sigs else np.zeros(0, np.float64)
+    lens = np.array([s.size for s in sigs], np.int64)
+    stats = np.zeros((len(sigs), 3), np.float64)
+    check(_lib.lib().sbv2_debug_loudness(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(sigs),
+                                         int(sample_rate), _loudness_arg(loudness), _f64p(stats)))
+    return stats
+
+
 class _Batch:
     """Keeps the numpy buffers of one sbv2_batch alive."""
 
@@ -320,6 +363,44 @@ class Pipeline:
         check(l.sbv2_pipeline_fetch_pcm_format(self.h, b.ticket, C.byref(fmt.c), pp, jl, out.ctypes.data_as(C.c_void_p), out.nbytes,
                                                got.ctypes.data_as(i64p)))
         return np.split(out[:int(got.sum())], np.cumsum(got)[:-1])
+
+    def _layout(self, b, place, joined_len):
+        lens = [int(v) for v in b.lens]
+        if place is None:
+            return lens, None, 0
+        if joined_len is None:
+            raise Sbv2Error("a placement needs joined_len")
+        pl, pp = _i64(place)
+        if pl.shape != (len(lens),):
+            raise Sbv2Error(f"place must hold one offset per utterance ({len(lens)})")
+        return [int(joined_len)], (pl, pp), int(joined_len)
+
+    def fetch_loudness(self, b, fmt: PcmFormat, loudness=None, place=None, joined_len=None):
+        """(signals, stats): the signals of fetch_format(b, fmt, place, joined_len), each measured (BS.1770-4 integrated loudness, 4x true
+        peak) and scaled to `loudness` (a Loudness; None: measure only, the signals equal fetch_format's) on the device.  fmt must not
+        normalise.  stats [n, 3]: L (LUFS) and TP (dBTP) before the gain, the applied gain G (dB)."""
+        native, pl, jl = self._layout(b, place, joined_len)
+        outs = [pcm_format_length(fmt, n) for n in native]
+        out = np.empty(max(sum(outs), 1), fmt.dtype)
+        got = np.zeros(len(outs), np.int64)
+        stats = np.zeros((len(outs), 3), np.float64)
+        check(_lib.lib().sbv2_pipeline_fetch_pcm_loudness(self.h, b.ticket, C.byref(fmt.c), _loudness_arg(loudness), None if pl is None else pl[1], jl,
+                                                          out.ctypes.data_as(C.c_void_p), out.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
+        return np.split(out[:int(got.sum())], np.cumsum(got)[:-1]), stats
+
+    def fetch_flac_loudness(self, b, fmt: PcmFormat, loudness=None, place=None, joined_len=None):
+        """(streams, stats): the signals of fetch_loudness(b, fmt, loudness, place, joined_len), each as one FLAC stream encoded on the
+        device; fmt must be s16."""
+        if fmt.encoding != "s16":
+            raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
+        native, pl, jl = self._layout(b, place, joined_len)
+        cap = sum(flac_bound(fmt, n) for n in native)
+        dst = np.empty(max(cap, 1), np.uint8)
+        got = np.zeros(len(native), np.int64)
+        stats = np.zeros((len(native), 3), np.float64)
+        check(_lib.lib().sbv2_pipeline_fetch_flac_loudness(self.h, b.ticket, C.byref(fmt.c), _loudness_arg(loudness), None if pl is None else pl[1], jl,
+                                                           dst.ctypes.data_as(C.c_void_p), dst.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
+        return _split_bytes(dst, got), stats
 
     def fetch_flac(self, b, fmt: PcmFormat, place=None, joined_len=None):
         """The signals of fetch_format(b, fmt, place, joined_len), each as one FLAC stream (bytes) encoded on the device; fmt must be s16."""

@@ -32,12 +32,17 @@ NOISE_SCALE_W = 0.8         # tts.rs:314 / :344
 class SynthesizeOptions:
     """tts.rs:359-375 (same defaults).  sample_rate / encoding / normalize are new (the reference writes 44.1 kHz f32 only): when any of
     them differs from its default the request's WAV signal is resampled / normalised / quantised on the device (model.PcmFormat).
-    encoding "flac": the same signal as s16, returned as a FLAC stream encoded on the device instead of a WAV."""
+    encoding "flac": the same signal as s16, returned as a FLAC stream encoded on the device instead of a WAV.
+    loudness (target LUFS) / true_peak_max (dBTP) are new as well: the signal's integrated loudness is brought to the target, capped by the
+    true-peak ceiling (model.Loudness); it replaces peak normalisation, so normalize=True with a loudness is refused."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
-                 normalize=False):
+                 normalize=False, loudness=None, true_peak_max=-1.0):
+        if loudness is not None and normalize:
+            raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
         self.sdp_ratio, self.length_scale, self.style_weight, self.split_sentences = sdp_ratio, length_scale, style_weight, split_sentences
         self.sample_rate, self.encoding, self.normalize = sample_rate, encoding, normalize
+        self.loudness, self.true_peak_max = loudness, true_peak_max
 
 
 def load_style(data: bytes) -> np.ndarray:
@@ -104,11 +109,15 @@ def joined_placement(lens, live_index, n_lines, split_sentences=True):
 
 
 def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
-                    noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W) -> bytes:
+                    noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, loudness_stats=None) -> bytes:
     """tts.rs:280-349 for one request whose lines are already parsed: `sentences` is the list obtained from text.split('\\n'),
     each entry a dict {input_ids, word2ph, phones, tones, langs} (parse_text's products) or None / {} for an empty line.
-    With options.split_sentences False the caller passes the single parsed text as a one-element list."""
+    With options.split_sentences False the caller passes the single parsed text as a one-element list.
+    loudness_stats: an optional list that receives [L, TP, G] of the signal when options.loudness is set."""
     options = options or SynthesizeOptions()
+    if options.loudness is not None and options.normalize:
+        raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
+    ln = model.Loudness(options.loudness, options.true_peak_max) if options.loudness is not None else None
     if noise_seed is None:      # the reference draws fresh noise per request; tests pass an explicit seed
         noise_seed = model.fresh_noise_seed()
     style = get_style_vector(style_vectors, style_id, options.style_weight)
@@ -122,6 +131,17 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     b = pipe.prepare(utts, sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
                      noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     pipe.run(b)
+    if ln is not None:   # ONE joined fetch, measured and scaled as a whole on the device (the gates leave the silent gaps out)
+        place, joined = joined_placement(b.lens, [i for i, _ in live], len(sentences), options.split_sentences)
+        if flac:
+            streams, stats = pipe.fetch_flac_loudness(b, fmt, ln, place, joined)
+        else:
+            out, stats = pipe.fetch_loudness(b, fmt, ln, place, joined)
+        if loudness_stats is not None:
+            loudness_stats.append([float(v) for v in stats[0]])
+        if flac:
+            return streams[0]
+        return pcm16_wav(out[0], fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out[0], fmt.sample_rate)
     if not fmt.is_default:   # ONE joined fetch: the WAV signal below, resampled / normalised / quantised as a whole on the device
         place, joined = joined_placement(b.lens, [i for i, _ in live], len(sentences), options.split_sentences)
         if flac:

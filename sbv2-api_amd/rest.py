@@ -5,13 +5,15 @@ and error mapping, so that a client of the reference's server cannot tell the di
   GET  /models      JSON list of idents                                          main.rs:24-33
   POST /synthesize  {text, ident, sdp_ratio = 0.0, length_scale = 1.0, style_id = 0, speaker_id = 0} -> audio/wav     main.rs:51-100
                     (+ sample_rate = 44100, encoding = "f32" | "s16" | "flac", normalize = false: new output formats, defaults = the
-                    reference's; "flac" -> audio/flac)
+                    reference's; "flac" -> audio/flac; loudness = null (target LUFS), true_peak_max = -1.0 (dBTP): loudness
+                    normalisation, exclusive with normalize)
   any error         500 text/plain "Something went wrong: <message>"            sbv2_api/src/error.rs:10-18
   one request at a time (Arc<Mutex<TTSModelHolder>>, main.rs:86,104)             -> a lock around the holder
 
 FastAPI / starlette are plumbing here; `python -m sbv2_api_amd.rest` is not provided on purpose: a deployment needs the text front end
 (G2P + tokenizer, out of scope: SURVEY.md §2 #7-12) plugged into the holder's `parse_text`."""
 import threading
+from typing import Optional
 
 
 def make_app(holder):
@@ -31,6 +33,8 @@ def make_app(holder):
         sample_rate: int = 44100            # new: output format of the WAV (the reference's is 44.1 kHz f32)
         encoding: str = "f32"               # "f32" | "s16" | "flac"
         normalize: bool = False             # peak of the signal -> full scale
+        loudness: Optional[float] = None    # integrated loudness target (LUFS, BS.1770-4); exclusive with normalize
+        true_peak_max: float = -1.0         # true-peak ceiling (dBTP) of the loudness gain
 
     app = FastAPI(docs_url="/docs")          # main.rs:196 serves the OpenAPI document at /docs as well
     lock = threading.Lock()
@@ -55,7 +59,8 @@ def make_app(holder):
                 wav = holder.easy_synthesize(req.ident, req.text, req.style_id, req.speaker_id,
                                              orchestrator.SynthesizeOptions(sdp_ratio=req.sdp_ratio, length_scale=req.length_scale,
                                                                             sample_rate=req.sample_rate, encoding=req.encoding,
-                                                                            normalize=req.normalize))
+                                                                            normalize=req.normalize, loudness=req.loudness,
+                                                                            true_peak_max=req.true_peak_max))
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
         return Response(content=wav, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
