@@ -208,6 +208,56 @@ int sbv2_loudness_kweight(int32_t sample_rate, double* coef);
 int sbv2_debug_loudness(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_loudness* ln,
                         double* stats);
 
+/* ---- new: look-ahead true-peak limiter ON THE DEVICE, for loudness targets the gain above cannot reach.  G = min(target - L, ceiling - TP)
+ * is peak-bound whenever the signal's peak-to-loudness ratio TP - L exceeds ceiling - target (speech: near 20 dB, so under -1 dBTP every
+ * target above about -21 LUFS is missed).  The limiter takes the peaks down by at most max_reduction_db and raises the rest.  In f64 on each
+ * output signal y at fs (before any gain), with L and TP as above, c = 10^(ceiling / 20), D = max_reduction_db, K = fs div 100 (10 ms):
+ *   1. Envelope, once per signal: z = the 4x interpolation of y defined for TP (h4); e[n] = max |z[4 n + d]| for d in -3..3, z = 0 outside
+ *      the signal.  So e[n] >= |y[n]|, and every z sample is seen by both neighbours.
+ *   2. For a pre-gain G dB, g0 = 10^(G / 20):
+ *        r[n] = min(1, c / (g0 e[n])), 1 where e[n] = 0;
+ *        m[n] = min r[n .. n + K - 1], with r = 1 past the end;
+ *        s[n] = sum_{k < K} h[k] m[n - k], with m = m[0] before the start, h[k] = sin^2(pi (k + 0.5) / K) scaled to sum to 1;
+ *        x[n] = y[n] g0 s[n].
+ *      Every m[n - k] is a minimum over a window that contains n (m[0] = min r[0 .. K - 1] stands in before the start, and contains every
+ *      n < K - 1), and s[n] is a convex combination of them, so s[n] <= r[n] and |x[n]| <= c for every sample: with ceiling <= 0 s16 cannot
+ *      clip.  In floating point the bounds hold up to a few ulp (the taps sum to 1 within rounding); s[n] is therefore taken as
+ *      min(sum, r[n]) and x[n] is clamped to [-c, c], which moves a value by rounding errors only.  A signal whose first 10 ms hold a peak
+ *      starts at that peak's gain instead of fading down from 1: with m = 1 before the start the sum would stay near 1 over the first
+ *      K - 1 samples whatever r is, and only a per-sample min could hold a loud onset, in steps of up to D dB between neighbours.
+ *      Windows never cross a signal edge.
+ *   3. Make-up, three evaluations: Gcap = ceiling - TP + D; G_0 = min(target - L, Gcap); for i = 0, 1: L_i = the integrated loudness of x
+ *      at G_i, G_{i+1} = min(G_i + target - L_i, Gcap) (G_i when L_i = -inf).  The output is x at G_2.  Gcap bounds the depth: no sample is
+ *      reduced by more than D dB, and an unreachable target cannot run away.
+ *   4. Idle rule: when G_0 <= ceiling - TP (g0 max e <= c: the scale alone fits under the ceiling, or D = 0) or L = -inf, the signal takes
+ *      the gain path above: the delivered bytes and the first three stats equal those of sbv2_pipeline_fetch_pcm_loudness /
+ *      _fetch_flac_loudness with the same target and ceiling, bit for bit.
+ *   stats, 6 doubles per signal: L and TP before (as above), G_2, L_out and TP_out of the delivered x (before the cast or quantiser), and
+ *      the deepest reduction 20 log10 min s (<= 0; 0 when idle).  Step 2 bounds the samples, not the interpolated peak of the
+ *      gain-modulated signal: TP_out is reported, not bounded.  Measured at most 1e-5 dB above the ceiling, on speech-like
+ *      signals and on dense noise-like audio limited at the full depth alike (s moves slowly against the interpolator's 24 samples).
+ * The sbv2_stream_* and sbv2_node_* paths have no limiter, as they have no loudness. */
+typedef struct sbv2_limiter {
+    double target_lufs;          /* [-70, -5] */
+    double true_peak_max_dbtp;   /* [-20, 0] */
+    double max_reduction_db;     /* [0, 12] */
+    double reserved;             /* must be 0 */
+} sbv2_limiter;
+/* The signals of sbv2_pipeline_fetch_pcm_loudness (same place / joined_len rules; fmt->normalize must be 0) through the limiter; lim must
+ * not be NULL, out-of-range or non-finite fields and a non-zero reserved are refused.  stats: NULL or 6 doubles per signal.  Two fetches of
+ * one run give identical bytes and stats. */
+int sbv2_pipeline_fetch_pcm_limited(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_limiter* lim,
+                                    const int64_t* place, int64_t joined_len, void* dst, int64_t capacity_bytes, int64_t* out_lens,
+                                    double* stats);
+/* The same signals as FLAC streams (fmt->encoding must be 1), exactly as sbv2_pipeline_fetch_flac encodes them; stats as above. */
+int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_limiter* lim,
+                                     const int64_t* place, int64_t joined_len, uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes,
+                                     double* stats);
+/* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
+ * doubles per signal. */
+int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,
+                       double* out_x, double* stats);
+
 /* ---- sbv2file.rs:15-37 `parse_sbv2file(bytes) -> (style_vectors, vits2)`: a .sbv2 file is zstd(tar{version.txt, model.onnx,
  * style_vectors.json}) (writer: scripts/convert/convert_model.py:156-175).  Both outputs are owned copies (sbv2_bytes_free).
  * Errors: "model not found: style_vectors" / "model not found: vits2" (Error::ModelNotFoundError, sbv2file.rs:31-36). ------------------- */

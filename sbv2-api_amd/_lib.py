@@ -29,6 +29,11 @@ class Sbv2Loudness(C.Structure):
     _fields_ = [("target_lufs", C.c_double), ("true_peak_max_dbtp", C.c_double)]
 
 
+class Sbv2Limiter(C.Structure):
+    """struct sbv2_limiter (include/sbv2_hip.h)."""
+    _fields_ = [("target_lufs", C.c_double), ("true_peak_max_dbtp", C.c_double), ("max_reduction_db", C.c_double), ("reserved", C.c_double)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -79,6 +84,11 @@ SYMBOLS = {
                                                     C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double)]),
     "sbv2_loudness_kweight": (C.c_int, [C.c_int32, C.POINTER(C.c_double)]),
     "sbv2_debug_loudness": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Loudness), C.POINTER(C.c_double)]),
+    "sbv2_pipeline_fetch_pcm_limited": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2PcmFormat), C.POINTER(Sbv2Limiter), i64p, C.c_int64,
+                                                  C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double)]),
+    "sbv2_pipeline_fetch_flac_limited": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2PcmFormat), C.POINTER(Sbv2Limiter), i64p, C.c_int64,
+                                                   C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double)]),
+    "sbv2_debug_limiter": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Limiter), C.c_void_p, C.POINTER(C.c_double)]),
     "sbv2_host_alloc": (C.c_void_p, [C.c_size_t]),
     "sbv2_host_free": (None, [C.c_void_p]),
     "sbv2_deal": (C.c_int, [C.c_int64, i64p, C.c_int, C.POINTER(C.c_int32)]),

@@ -530,6 +530,67 @@ int sbv2_pipeline_fetch_flac_loudness(sbv2_pipeline* p, int64_t ticket, const sb
     API_END
 }
 
+// ---- look-ahead true-peak limiter (limiter.hip) ----
+// as format_loudness, through the limiter: the stats (6 per signal) reach limiter.stats_host() once the stream is synchronised
+static void* format_limited(sbv2_pipeline* p, int ctx, VitsModel& vm, const PcmFmtSpec& spec, const LimiterSpec& lim,
+                            const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, Limiter** limiter) {
+    HIP_CHECK(hipSetDevice(vm.device()));
+    if ((int)p->meters.size() < p->contexts()) p->meters.resize(p->contexts());
+    if (!p->meters[ctx]) p->meters[ctx].reset(new LoudnessMeter(vm.device()));
+    if ((int)p->limiters.size() < p->contexts()) p->limiters.resize(p->contexts());
+    if (!p->limiters[ctx]) p->limiters[ctx].reset(new Limiter(vm.device()));
+    *limiter = p->limiters[ctx].get();
+    PcmFormatter& f = formatter(p, ctx, vm.device());
+    void* dev = f.out_buffer((size_t)std::max<int64_t>(total, 1) * spec.bytes(), vm.stream());
+    f.run_limited(spec, pieces, sig, total, dev, 0, vm.stream(), *p->meters[ctx], **limiter, lim);
+    return dev;
+}
+
+int sbv2_pipeline_fetch_pcm_limited(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_limiter* lim, const int64_t* place,
+                                    int64_t joined_len, void* dst, int64_t capacity_bytes, int64_t* out_lens, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(p && dst && out_lens, "bad arguments");
+    const PcmFmtSpec spec = loudness_format(fmt);
+    const LimiterSpec lspec = limiter_spec(lim);
+    const int ctx = p->ctx_of(ticket);
+    VitsModel& vm = p->vm(ctx);
+    std::vector<FmtPiece> pieces;
+    std::vector<FmtSignal> sig;
+    std::vector<int64_t> outs;
+    int64_t total = 0;
+    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
+    SBV2_REQUIRE(capacity_bytes >= total * spec.bytes(),
+                 "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(total * spec.bytes()) + " bytes");
+    Limiter* limiter = nullptr;
+    void* dev = format_limited(p, ctx, vm, spec, lspec, pieces, sig, total, &limiter);
+    if (total > 0) HIP_CHECK(hipMemcpyAsync(dst, dev, (size_t)total * spec.bytes(), hipMemcpyDeviceToHost, vm.stream()));
+    HIP_CHECK(hipStreamSynchronize(vm.stream()));
+    for (size_t i = 0; i < outs.size(); ++i) out_lens[i] = outs[i];
+    if (stats) std::memcpy(stats, limiter->stats_host(), sizeof(double) * 6 * outs.size());
+    API_END
+}
+
+int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_limiter* lim, const int64_t* place,
+                                     int64_t joined_len, uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(p && dst && out_bytes, "bad arguments");
+    const PcmFmtSpec spec = loudness_format(fmt);
+    SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
+    const LimiterSpec lspec = limiter_spec(lim);
+    const int ctx = p->ctx_of(ticket);
+    VitsModel& vm = p->vm(ctx);
+    std::vector<FmtPiece> pieces;
+    std::vector<FmtSignal> sig;
+    std::vector<int64_t> outs;
+    int64_t total = 0;
+    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
+    Limiter* limiter = nullptr;
+    void* dev = format_limited(p, ctx, vm, spec, lspec, pieces, sig, total, &limiter);
+    encode_flac(p, ctx, vm, spec, dev, outs, dst, capacity_bytes, out_bytes);
+    if (stats) std::memcpy(stats, limiter->stats_host(), sizeof(double) * 6 * outs.size());
+    API_END
+}
+
 // Pinned host memory for PCM destinations: a device -> host copy into pageable memory is staged by the runtime at a fraction of the
 // PCIe rate; into these buffers it is one DMA that overlaps the other execution context's kernels.
 void* sbv2_host_alloc(size_t bytes) {

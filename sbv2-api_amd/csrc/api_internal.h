@@ -8,6 +8,7 @@
 
 #include "../../include/sbv2_hip.h"
 #include "flac_encode.h"
+#include "limiter.h"
 #include "loudness.h"
 #include "models.h"
 #include "pcm_format.h"
@@ -32,6 +33,7 @@ struct sbv2_pipeline {
     std::vector<std::unique_ptr<PcmFormatter>> fmts;   // per context: the formatting launches of sbv2_pipeline_fetch_pcm_format
     std::vector<std::unique_ptr<FlacEncoder>> flacs;   // per context: the encoding launches of sbv2_pipeline_fetch_flac
     std::vector<std::unique_ptr<LoudnessMeter>> meters;   // per context: the meter of sbv2_pipeline_fetch_pcm_loudness / _flac_loudness
+    std::vector<std::unique_ptr<Limiter>> limiters;   // per context: the limiter of sbv2_pipeline_fetch_pcm_limited / _flac_limited
     int64_t calls = 0;   // tickets are call numbers 1, 2, ...: ticket t ran on context (t - 1) % depth and is valid until that context is reused
     BertModel& bm(int i) { return i == 0 ? *bert->m : *bclones[i - 1]; }
     VitsModel& vm(int i) { return i == 0 ? *vits->m : *vclones[i - 1]; }

@@ -18,6 +18,9 @@ struct LoudnessSpec {
 LoudnessSpec loudness_spec(const sbv2_loudness* ln);
 // the K-weighting at a supported rate (libebur128 form): coef = shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2; throws for other rates
 void loudness_kweight(int rate, double coef[10]);
+// the true-peak interpolator's phases 1..3 (the kernel arguments of k_true_peak): h[p][d] = h4(p + 1 + 4 (d - 12)), d in [0, 24)
+constexpr int kTruePeakTaps = 24;
+void loudness_true_peak_taps(double h[3][kTruePeakTaps]);
 
 // Device state of the meter of one execution context: the signal table (pinned + device), the per-segment K-weighting states and partial
 // sums, the per-signal true peaks, stats and gains (all grown on demand; growing synchronises the stream).
@@ -30,8 +33,12 @@ class LoudnessMeter {
     // Enqueues on s the meter of the signals sig[i] = y[out_off, out_off + j1 - j0) (y: device f64, may be null when every signal is
     // empty) at `rate`: K-weighting (three launches), true peak, gate.  Returns the device gains 10^(G / 20), one per signal, and enqueues
     // the copy of the stats to the host: stats_host() holds 3 doubles per signal (L, TP, G) once s has been synchronised.
-    const double* measure(const double* y, const std::vector<FmtSignal>& sig, int rate, const LoudnessSpec& ln, hipStream_t s);
+    // with_peak = false (the limiter's intermediate evaluations, limiter.hip) leaves the true-peak pass out: TP reads -inf.
+    const double* measure(const double* y, const std::vector<FmtSignal>& sig, int rate, const LoudnessSpec& ln, hipStream_t s,
+                          bool with_peak = true);
     const double* stats_host() const { return stats_host_; }
+    // the device copy of the last measure()'s stats (valid on its stream, until the next measure())
+    const double* stats_dev() const { return stats_dev_; }
 
   private:
     const std::vector<double>& tables(int rate);
@@ -42,6 +49,7 @@ class LoudnessMeter {
     void* dev_ = nullptr;    // device: signal table, peaks, stats, gains, then the per-segment states and partial sums
     size_t dev_cap_ = 0;
     double* stats_host_ = nullptr;
+    double* stats_dev_ = nullptr;
 };
 
 }  // namespace sbv2

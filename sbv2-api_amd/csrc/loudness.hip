@@ -394,8 +394,12 @@ void host_matmul(const double* X, const double* Y, double* R) {
     std::memcpy(R, t, sizeof(t));
 }
 
+}  // namespace
+
+static_assert(kTpTaps == kTruePeakTaps, "loudness.h states the tap count");
+
 // the 4x interpolator's phases 1..3: h[p][d] = h4(p + 1 + 4 (d - 12)), every phase of h4 scaled to sum to 1
-void true_peak_taps(double h[3][kTpTaps]) {
+void loudness_true_peak_taps(double h[3][kTruePeakTaps]) {
     double h4[2 * kTpHalf + 1], sum[4] = {0, 0, 0, 0};
     const double i0b = bessel_i0(8.6);
     for (int n = -kTpHalf; n <= kTpHalf; ++n) {
@@ -410,8 +414,6 @@ void true_peak_taps(double h[3][kTpTaps]) {
             h[p - 1][d] = h4[n + kTpHalf] / sum[p];
         }
 }
-
-}  // namespace
 
 void loudness_kweight(int rate, double coef[10]) {
     segment_len(rate);   // refuses unsupported rates
@@ -466,11 +468,12 @@ const std::vector<double>& LoudnessMeter::tables(int rate) {
     transition(v.data(), A1);
     std::memcpy(v.data() + 10, A1, sizeof(A1));
     for (int i = 1, m = segment_len(rate); i < m; ++i) host_matmul(A1, v.data() + 10, v.data() + 10);
-    true_peak_taps(reinterpret_cast<double(*)[kTpTaps]>(v.data() + 26));
+    loudness_true_peak_taps(reinterpret_cast<double(*)[kTpTaps]>(v.data() + 26));
     return tables_[rate] = std::move(v);
 }
 
-const double* LoudnessMeter::measure(const double* y, const std::vector<FmtSignal>& sig, int rate, const LoudnessSpec& ln, hipStream_t s) {
+const double* LoudnessMeter::measure(const double* y, const std::vector<FmtSignal>& sig, int rate, const LoudnessSpec& ln, hipStream_t s,
+                                     bool with_peak) {
     const int nsig = (int)sig.size();
     SBV2_REQUIRE(nsig >= 1, "internal: no signal to measure");
     const int m = segment_len(rate), S = rate / 10;
@@ -515,6 +518,7 @@ const double* LoudnessMeter::measure(const double* y, const std::vector<FmtSigna
     const LSig* sig_dev = reinterpret_cast<const LSig*>(d);
     auto* peak = reinterpret_cast<unsigned long long*>(d + o_peak);
     auto* stats = reinterpret_cast<double*>(d + o_stats);
+    stats_dev_ = stats;
     auto* gain = reinterpret_cast<double*>(d + o_gain);
     if (total > 0) {
         KwArgs a;
@@ -541,7 +545,8 @@ const double* LoudnessMeter::measure(const double* y, const std::vector<FmtSigna
         std::memcpy(t.h, tv.data() + 26, sizeof(t.h));
         t.peak = peak;
         t.bmax = reinterpret_cast<double*>(d + o_bmax);
-        hipLaunchKernelGGL(k_true_peak, dim3((unsigned)((total + 255) / 256)), blk, 0, s, t);
+        if (with_peak) hipLaunchKernelGGL(k_true_peak, dim3((unsigned)((total + 255) / 256)), blk, 0, s, t);
+        else HIP_CHECK(hipMemsetAsync(t.bmax, 0, 8 * (size_t)((total + 255) / 256), s));   // no peak: k_gate reports TP = -inf
     }
     GateArgs g;
     g.sig = sig_dev;

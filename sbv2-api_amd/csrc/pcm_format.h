@@ -41,6 +41,8 @@ struct FmtSignal {
 
 class LoudnessMeter;   // loudness.h
 struct LoudnessSpec;
+class Limiter;   // limiter.h
+struct LimiterSpec;
 
 // Device state of the formatting launches of one execution context: the polyphase tables (per rate, built once), the tables of pieces /
 // signals (one pinned + device pair per `slot`: a slot's host copy is rewritten only once the launch that used it has completed), the
@@ -61,9 +63,14 @@ class PcmFormatter {
     void run_loudness(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
                       void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, const LoudnessSpec& ln);
 
+    // the same through the look-ahead limiter (spec.normalize must be 0): y in f64, limiter.run(y, meter) (limiter.hip), then its x as it is.
+    void run_limited(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
+                     void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, Limiter& limiter, const LimiterSpec& lim);
+
   private:
     void run_impl(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
-                  int slot, hipStream_t s, LoudnessMeter* meter, const LoudnessSpec* ln);
+                  int slot, hipStream_t s, LoudnessMeter* meter, const LoudnessSpec* ln, Limiter* limiter = nullptr,
+                  const LimiterSpec* lim = nullptr);
     struct Slot {
         void* host = nullptr;
         void* dev = nullptr;

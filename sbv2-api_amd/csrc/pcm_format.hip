@@ -17,6 +17,7 @@
 #include <numeric>
 
 #include "../../include/sbv2_hip.h"
+#include "limiter.h"
 #include "loudness.h"
 #include "pcm_format.h"
 
@@ -270,11 +271,20 @@ void PcmFormatter::run_loudness(const PcmFmtSpec& spec, const std::vector<FmtPie
     run_impl(spec, pieces, sig, total, dst_dev, slot, s, &meter, &ln);
 }
 
+void PcmFormatter::run_limited(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
+                               void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, Limiter& limiter, const LimiterSpec& lim) {
+    SBV2_REQUIRE(!spec.normalize, "internal: a limiter on a peak-normalised format");
+    run_impl(spec, pieces, sig, total, dst_dev, slot, s, &meter, nullptr, &limiter, &lim);
+}
+
 void PcmFormatter::run_impl(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
-                            void* dst_dev, int slot, hipStream_t s, LoudnessMeter* meter, const LoudnessSpec* ln) {
+                            void* dst_dev, int slot, hipStream_t s, LoudnessMeter* meter, const LoudnessSpec* ln, Limiter* limiter,
+                            const LimiterSpec* lim) {
     if (sig.empty()) return;
     if (total <= 0) {
-        if (meter) meter->measure(nullptr, sig, spec.rate, *ln, s);
+        const double* unit = nullptr;
+        if (limiter) limiter->run(nullptr, sig, spec.rate, *lim, *meter, s, &unit);
+        else if (meter) meter->measure(nullptr, sig, spec.rate, *ln, s);
         return;
     }
     const float* tp = taps(spec, s);
@@ -334,9 +344,12 @@ void PcmFormatter::run_impl(const PcmFmtSpec& spec, const std::vector<FmtPiece>&
     }
     if (meter) {
         hipLaunchKernelGGL(k_pcm_resample<3>, grid, block, 0, s, a, tmp_, nullptr);
-        const double* gain = meter->measure(tmp_, sig, spec.rate, *ln, s);
-        if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain_sig<1>, grid, block, 0, s, tmp_, a.sig, a.nsig, gain, total, dst_dev);
-        else hipLaunchKernelGGL(k_pcm_gain_sig<0>, grid, block, 0, s, tmp_, a.sig, a.nsig, gain, total, dst_dev);
+        const double* gain = nullptr;
+        const double* x = tmp_;   // the limiter hands back its own x and unit gains: the kernels below deliver it as it is
+        if (limiter) x = limiter->run(tmp_, sig, spec.rate, *lim, *meter, s, &gain);
+        else gain = meter->measure(tmp_, sig, spec.rate, *ln, s);
+        if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain_sig<1>, grid, block, 0, s, x, a.sig, a.nsig, gain, total, dst_dev);
+        else hipLaunchKernelGGL(k_pcm_gain_sig<0>, grid, block, 0, s, x, a.sig, a.nsig, gain, total, dst_dev);
         HIP_CHECK(hipGetLastError());
         return;
     }

@@ -213,6 +213,46 @@ int sbv2_debug_loudness(int device, const double* x, const int64_t* lens, int ns
     API_END
 }
 
+int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim, double* out_x,
+                       double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(nsig >= 1 && lens && stats, "bad arguments");
+    const LimiterSpec spec = limiter_spec(lim);
+    double coef[10];
+    loudness_kweight(sample_rate, coef);   // refuses unsupported rates
+    std::vector<FmtSignal> sig(nsig);
+    int64_t total = 0;
+    for (int i = 0; i < nsig; ++i) {
+        SBV2_REQUIRE(lens[i] >= 0, "negative signal length");
+        sig[i] = FmtSignal{0, lens[i], total, 0, 0};
+        total += lens[i];
+    }
+    SBV2_REQUIRE(total == 0 || (x && out_x), "bad arguments");
+    HIP_CHECK(hipSetDevice(device));
+    struct Res {
+        hipStream_t s = nullptr;
+        void* x = nullptr;
+        ~Res() {
+            if (s) (void)hipStreamSynchronize(s);
+            if (x) (void)hipFree(x);
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } r;
+    HIP_CHECK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
+    if (total) {
+        HIP_CHECK(hipMalloc(&r.x, sizeof(double) * (size_t)total));
+        HIP_CHECK(hipMemcpyAsync(r.x, x, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, r.s));
+    }
+    LoudnessMeter meter(device);
+    Limiter limiter(device);
+    const double* unit = nullptr;
+    const double* lx = limiter.run(static_cast<const double*>(r.x), sig, sample_rate, spec, meter, r.s, &unit);
+    if (total) HIP_CHECK(hipMemcpyAsync(out_x, lx, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    std::memcpy(stats, limiter.stats_host(), sizeof(double) * 6 * nsig);
+    API_END
+}
+
 int sbv2_debug_bucket_table(int64_t max_s, int64_t buckets, int64_t max_rel, int32_t* out) {
     API_BEGIN
     SBV2_REQUIRE(max_s >= 1 && out, "bad arguments");

@@ -13,7 +13,7 @@ from ._lib import Sbv2Batch, Sbv2Error, check, f32p, i64p
 
 __all__ = ["Session", "load_model", "predict", "synthesize", "predict_batch", "synthesize_batch", "Pipeline", "Node", "Comm", "deal", "Sbv2Error",
            "PcmFormat", "pcm_format_length", "pcm_format_taps", "flac_bound", "debug_flac_encode", "Loudness", "loudness_kweight",
-           "debug_loudness"]
+           "debug_loudness", "Limiter", "debug_limiter"]
 
 
 def _i64(a):
@@ -225,6 +225,39 @@ def debug_loudness(signals, sample_rate: int, loudness=None, device: int = 0):
     return stats
 
 
+class Limiter:
+    """Look-ahead true-peak limiter of each output signal (struct sbv2_limiter): integrated loudness to target_lufs in [-70, -5] with the
+    sample peaks held at or below true_peak_max dBTP in [-20, 0] by a 10 ms look-ahead gain curve that takes no sample down by more than
+    max_reduction dB in [0, 12].  Reaches targets that Loudness misses because the true peak binds first; where the plain scale fits (or
+    max_reduction is 0) the output equals Loudness's bit for bit.  Runs on the device."""
+
+    def __init__(self, target_lufs: float, true_peak_max: float = -1.0, max_reduction: float = 6.0):
+        self.target_lufs, self.true_peak_max, self.max_reduction = float(target_lufs), float(true_peak_max), float(max_reduction)
+        if not (np.isfinite(self.target_lufs) and -70.0 <= self.target_lufs <= -5.0):
+            raise Sbv2Error(f"loudness target {target_lufs} LUFS is outside [-70, -5]")
+        if not (np.isfinite(self.true_peak_max) and -20.0 <= self.true_peak_max <= 0.0):
+            raise Sbv2Error(f"true-peak ceiling {true_peak_max} dBTP is outside [-20, 0]")
+        if not (np.isfinite(self.max_reduction) and 0.0 <= self.max_reduction <= 12.0):
+            raise Sbv2Error(f"limiter depth {max_reduction} dB is outside [0, 12]")
+        self.c = _lib.Sbv2Limiter(self.target_lufs, self.true_peak_max, self.max_reduction, 0.0)
+
+    def __repr__(self):
+        return f"Limiter({self.target_lufs}, true_peak_max={self.true_peak_max}, max_reduction={self.max_reduction})"
+
+
+def debug_limiter(signals, sample_rate: int, limiter: Limiter, device: int = 0):
+    """Test hook: the device limiter on host float64 signals at sample_rate -> (the limited float64 signals, stats [n, 6]: L LUFS, TP dBTP,
+    G dB, L_out LUFS, TP_out dBTP, deepest reduction dB)."""
+    sigs = [np.ascontiguousarray(np.asarray(x, np.float64)).reshape(-1) for x in signals]
+    x = np.concatenate(sigs) if sigs else np.zeros(0, np.float64)
+    lens = np.array([s.size for s in sigs], np.int64)
+    out = np.zeros(max(x.size, 1), np.float64)
+    stats = np.zeros((len(sigs), 6), np.float64)
+    check(_lib.lib().sbv2_debug_limiter(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(sigs),
+                                        int(sample_rate), C.byref(limiter.c), out.ctypes.data_as(C.c_void_p), _f64p(stats)))
+    return np.split(out[:x.size], np.cumsum(lens)[:-1]), stats
+
+
 class _Batch:
     """Keeps the numpy buffers of one sbv2_batch alive."""
 
@@ -400,6 +433,37 @@ class Pipeline:
         stats = np.zeros((len(native), 3), np.float64)
         check(_lib.lib().sbv2_pipeline_fetch_flac_loudness(self.h, b.ticket, C.byref(fmt.c), _loudness_arg(loudness), None if pl is None else pl[1], jl,
                                                            dst.ctypes.data_as(C.c_void_p), dst.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
+        return _split_bytes(dst, got), stats
+
+    def fetch_limited(self, b, fmt: PcmFormat, limiter: Limiter, place=None, joined_len=None):
+        """(signals, stats): the signals of fetch_format(b, fmt, place, joined_len), each brought to limiter.target_lufs through the
+        look-ahead true-peak limiter on the device.  fmt must not normalise.  stats [n, 6]: L (LUFS) and TP (dBTP) before, the pre-gain G
+        (dB), L_out and TP_out of the delivered signal, the deepest gain reduction (dB, <= 0; 0 when the plain scale was enough)."""
+        if limiter is None:
+            raise Sbv2Error("fetch_limited needs a Limiter")
+        native, pl, jl = self._layout(b, place, joined_len)
+        outs = [pcm_format_length(fmt, n) for n in native]
+        out = np.empty(max(sum(outs), 1), fmt.dtype)
+        got = np.zeros(len(outs), np.int64)
+        stats = np.zeros((len(outs), 6), np.float64)
+        check(_lib.lib().sbv2_pipeline_fetch_pcm_limited(self.h, b.ticket, C.byref(fmt.c), C.byref(limiter.c), None if pl is None else pl[1], jl,
+                                                         out.ctypes.data_as(C.c_void_p), out.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
+        return np.split(out[:int(got.sum())], np.cumsum(got)[:-1]), stats
+
+    def fetch_flac_limited(self, b, fmt: PcmFormat, limiter: Limiter, place=None, joined_len=None):
+        """(streams, stats): the signals of fetch_limited(b, fmt, limiter, place, joined_len), each as one FLAC stream encoded on the
+        device; fmt must be s16."""
+        if limiter is None:
+            raise Sbv2Error("fetch_flac_limited needs a Limiter")
+        if fmt.encoding != "s16":
+            raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
+        native, pl, jl = self._layout(b, place, joined_len)
+        cap = sum(flac_bound(fmt, n) for n in native)
+        dst = np.empty(max(cap, 1), np.uint8)
+        got = np.zeros(len(native), np.int64)
+        stats = np.zeros((len(native), 6), np.float64)
+        check(_lib.lib().sbv2_pipeline_fetch_flac_limited(self.h, b.ticket, C.byref(fmt.c), C.byref(limiter.c), None if pl is None else pl[1], jl,
+                                                          dst.ctypes.data_as(C.c_void_p), dst.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
         return _split_bytes(dst, got), stats
 
     def fetch_flac(self, b, fmt: PcmFormat, place=None, joined_len=None):

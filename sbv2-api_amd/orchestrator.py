@@ -34,12 +34,18 @@ class SynthesizeOptions:
     them differs from its default the request's WAV signal is resampled / normalised / quantised on the device (model.PcmFormat).
     encoding "flac": the same signal as s16, returned as a FLAC stream encoded on the device instead of a WAV.
     loudness (target LUFS) / true_peak_max (dBTP) are new as well: the signal's integrated loudness is brought to the target, capped by the
-    true-peak ceiling (model.Loudness); it replaces peak normalisation, so normalize=True with a loudness is refused."""
+    true-peak ceiling (model.Loudness); it replaces peak normalisation, so normalize=True with a loudness is refused.  That gain is one
+    scale, so a target is missed whenever the signal's peak-to-loudness ratio exceeds true_peak_max - loudness (speech: about 20 dB, which
+    puts -16 and -14 LUFS out of reach under -1 dBTP).  limiter=True (new) reaches such targets with a look-ahead true-peak limiter that
+    takes peaks down by at most max_reduction dB (model.Limiter); it needs a loudness target."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
-                 normalize=False, loudness=None, true_peak_max=-1.0):
+                 normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0):
         if loudness is not None and normalize:
             raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
+        if limiter and loudness is None:
+            raise model.Sbv2Error("limiter needs a loudness target: set loudness (LUFS)")
+        self.limiter, self.max_reduction = bool(limiter), max_reduction
         self.sdp_ratio, self.length_scale, self.style_weight, self.split_sentences = sdp_ratio, length_scale, style_weight, split_sentences
         self.sample_rate, self.encoding, self.normalize = sample_rate, encoding, normalize
         self.loudness, self.true_peak_max = loudness, true_peak_max
@@ -113,11 +119,18 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     """tts.rs:280-349 for one request whose lines are already parsed: `sentences` is the list obtained from text.split('\\n'),
     each entry a dict {input_ids, word2ph, phones, tones, langs} (parse_text's products) or None / {} for an empty line.
     With options.split_sentences False the caller passes the single parsed text as a one-element list.
-    loudness_stats: an optional list that receives [L, TP, G] of the signal when options.loudness is set."""
+    loudness_stats: an optional list that receives [L, TP, G] of the signal when options.loudness is set, or the limiter's 6 values
+    [L, TP, G, L_out, TP_out, deepest reduction] when options.limiter is set as well."""
     options = options or SynthesizeOptions()
     if options.loudness is not None and options.normalize:
         raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
-    ln = model.Loudness(options.loudness, options.true_peak_max) if options.loudness is not None else None
+    limited = bool(options.limiter)
+    if limited and options.loudness is None:
+        raise model.Sbv2Error("limiter needs a loudness target: set loudness (LUFS)")
+    if limited:
+        ln = model.Limiter(options.loudness, options.true_peak_max, options.max_reduction)
+    else:
+        ln = model.Loudness(options.loudness, options.true_peak_max) if options.loudness is not None else None
     if noise_seed is None:      # the reference draws fresh noise per request; tests pass an explicit seed
         noise_seed = model.fresh_noise_seed()
     style = get_style_vector(style_vectors, style_id, options.style_weight)
@@ -134,9 +147,9 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     if ln is not None:   # ONE joined fetch, measured and scaled as a whole on the device (the gates leave the silent gaps out)
         place, joined = joined_placement(b.lens, [i for i, _ in live], len(sentences), options.split_sentences)
         if flac:
-            streams, stats = pipe.fetch_flac_loudness(b, fmt, ln, place, joined)
+            streams, stats = (pipe.fetch_flac_limited if limited else pipe.fetch_flac_loudness)(b, fmt, ln, place, joined)
         else:
-            out, stats = pipe.fetch_loudness(b, fmt, ln, place, joined)
+            out, stats = (pipe.fetch_limited if limited else pipe.fetch_loudness)(b, fmt, ln, place, joined)
         if loudness_stats is not None:
             loudness_stats.append([float(v) for v in stats[0]])
         if flac:
