@@ -212,6 +212,7 @@ int sbv2_pipeline_create(sbv2_bert* bert, sbv2_vits* vits, sbv2_pipeline** out) 
         p->bclones.emplace_back(bert->m->clone());
         p->vclones.emplace_back(vits->m->clone());
     }
+    p->chains = std::vector<OutputChain>(k);
     *out = p.release();
     API_END
 }
@@ -363,70 +364,89 @@ static void format_layout(const PcmFmtSpec& spec, VitsModel& vm, const int64_t* 
     outs->push_back(*total);
 }
 
-static PcmFormatter& formatter(sbv2_pipeline* p, int ctx, int device) {
-    if ((int)p->fmts.size() < p->contexts()) p->fmts.resize(p->contexts());
-    if (!p->fmts[ctx]) p->fmts[ctx].reset(new PcmFormatter(device));
-    return *p->fmts[ctx];
+}  // extern "C"
+
+// ---- the formatted fetches: output formats (pcm_format.hip), FLAC (flac_encode.hip), loudness (loudness.hip), limiter (limiter.hip) ----
+// A formatted fetch = a gain stage and a sink.  The gain stage: none (peak-normalise or not, as fmt->normalize says), a loudness gain
+// (ln; NULL = measure only) or the look-ahead limiter (lim).  The sink: PCM bytes in fmt's encoding, or one FLAC stream per signal.
+struct FetchGain {
+    enum Kind { kNone, kLoudness, kLimiter } kind = kNone;
+    const sbv2_loudness* ln = nullptr;
+    const sbv2_limiter* lim = nullptr;
+    int stats_per_signal() const { return kind == kLimiter ? 6 : kind == kLoudness ? 3 : 0; }
+};
+enum class Sink { kPcm, kFlac };
+
+static PcmFmtSpec fetch_spec(const sbv2_pcm_format* fmt, bool gain_stage, Sink sink) {
+    const PcmFmtSpec spec = pcm_format_spec(fmt);
+    if (gain_stage) SBV2_REQUIRE(!spec.normalize, "loudness normalisation replaces peak normalisation: fmt->normalize must be 0");
+    if (sink == Sink::kFlac) SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
+    return spec;
 }
 
-// The run's packed PCM (pcm_device + pcm_offs / pcm_lens) is formatted by one launch on the run's own stream, then crosses PCIe in the format.
-int sbv2_pipeline_fetch_pcm_format(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len,
-                                   void* dst, int64_t capacity_bytes, int64_t* out_lens) {
-    API_BEGIN
-    SBV2_REQUIRE(p && dst && out_lens, "bad arguments");
-    const PcmFmtSpec spec = pcm_format_spec(fmt);
+// The run's packed PCM (pcm_device + pcm_offs / pcm_lens) is formatted on the run's own stream and crosses PCIe in the format: every
+// check first (format, gain options, ticket, placement, PCM capacity), then the formatter's launches with the gain stage between the
+// resampler and the quantiser, then the sink.  out_counts: samples (PCM) or bytes (FLAC) of each signal; stats (may be NULL): the gain
+// stage's 3 or 6 doubles per signal.
+static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
+                            int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats) {
+    const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
+    const LoudnessSpec ln = gain.kind == FetchGain::kLoudness ? loudness_spec(gain.ln) : LoudnessSpec();
+    const LimiterSpec lim = gain.kind == FetchGain::kLimiter ? limiter_spec(gain.lim) : LimiterSpec();
     const int ctx = p->ctx_of(ticket);
     VitsModel& vm = p->vm(ctx);
     std::vector<FmtPiece> pieces;
     std::vector<FmtSignal> sig;
-    std::vector<int64_t> outs;
+    std::vector<int64_t> outs, flac_bytes;   // per signal: samples, bytes of its FLAC stream
     int64_t total = 0;
     format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
-    SBV2_REQUIRE(capacity_bytes >= total * spec.bytes(),
-                 "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(total * spec.bytes()) + " bytes");
+    const int64_t pcm_bytes = total * spec.bytes();
+    if (sink == Sink::kPcm)   // (the FLAC sink checks its capacity after encoding, when the sizes are known)
+        SBV2_REQUIRE(capacity_bytes >= pcm_bytes,
+                     "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(pcm_bytes) + " bytes");
     HIP_CHECK(hipSetDevice(vm.device()));
-    if (spec.identity() && !place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
-        HIP_CHECK(hipMemcpyAsync(dst, vm.pcm_device(), sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, vm.stream()));
-    } else if (total > 0) {
-        PcmFormatter& f = formatter(p, ctx, vm.device());
-        void* dev = f.out_buffer((size_t)total * spec.bytes(), vm.stream());
-        f.run(spec, pieces, sig, total, dev, 0, vm.stream());
-        HIP_CHECK(hipMemcpyAsync(dst, dev, (size_t)total * spec.bytes(), hipMemcpyDeviceToHost, vm.stream()));
+    OutputChain& c = p->chains[ctx];
+    const hipStream_t s = vm.stream();
+    if (sink == Sink::kPcm && gain.kind == FetchGain::kNone && spec.identity() && !place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
+        HIP_CHECK(hipMemcpyAsync(dst, vm.pcm_device(), sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, s));
+    } else if (total > 0 || gain.kind != FetchGain::kNone || sink == Sink::kFlac) {   // a gain stage and the encoder run on empty signals too
+        void* dev = c.formatter.out_buffer((size_t)std::max<int64_t>(pcm_bytes, spec.bytes()), s);
+        const GainStage stage = gain.kind == FetchGain::kLimiter    ? GainStage(c.meter, c.limiter, lim)
+                                : gain.kind == FetchGain::kLoudness ? GainStage(c.meter, ln)
+                                                                    : GainStage();
+        c.formatter.run(spec, pieces, sig, total, dev, 0, s, stage);
+        if (sink == Sink::kFlac) {   // the signals stay in HBM; the encoder reads the stream sizes back, then exactly the encoded bytes cross PCIe
+            std::vector<int64_t> offs(outs.size());
+            for (size_t i = 1; i < outs.size(); ++i) offs[i] = offs[i - 1] + outs[i - 1];
+            const int64_t nbytes = c.flac.encode(static_cast<const int16_t*>(dev), offs, outs, spec.rate, s, &flac_bytes);
+            SBV2_REQUIRE(capacity_bytes >= nbytes,
+                         "FLAC buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(nbytes) + " bytes");
+            HIP_CHECK(hipMemcpyAsync(dst, c.flac.output(), (size_t)nbytes, hipMemcpyDeviceToHost, s));
+        } else if (total > 0) {
+            HIP_CHECK(hipMemcpyAsync(dst, dev, (size_t)pcm_bytes, hipMemcpyDeviceToHost, s));
+        }
     }
-    HIP_CHECK(hipStreamSynchronize(vm.stream()));
-    for (size_t i = 0; i < outs.size(); ++i) out_lens[i] = outs[i];
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < outs.size(); ++i) out_counts[i] = sink == Sink::kFlac ? flac_bytes[i] : outs[i];
+    if (stats) {   // written by the stage's last copy on s
+        const double* from = gain.kind == FetchGain::kLimiter ? c.limiter.stats_host() : c.meter.stats_host();
+        std::memcpy(stats, from, sizeof(double) * gain.stats_per_signal() * sig.size());
+    }
+}
+
+extern "C" {
+
+int sbv2_pipeline_fetch_pcm_format(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len,
+                                   void* dst, int64_t capacity_bytes, int64_t* out_lens) {
+    API_BEGIN
+    SBV2_REQUIRE(p && dst && out_lens, "bad arguments");
+    fetch_formatted(p, ticket, fmt, FetchGain(), place, joined_len, Sink::kPcm, dst, capacity_bytes, out_lens, nullptr);
     API_END
-}
-
-// ---- FLAC (flac_encode.hip) ----
-static PcmFmtSpec flac_spec(const sbv2_pcm_format* fmt) {
-    const PcmFmtSpec spec = pcm_format_spec(fmt);
-    SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
-    return spec;
-}
-
-static FlacEncoder& flac_encoder(sbv2_pipeline* p, int ctx, int device) {
-    if ((int)p->flacs.size() < p->contexts()) p->flacs.resize(p->contexts());
-    if (!p->flacs[ctx]) p->flacs[ctx].reset(new FlacEncoder(device));
-    return *p->flacs[ctx];
-}
-
-// the s16 signals dev[total] of a fetch -> FLAC streams into host dst (reads back the sizes: synchronises the stream)
-static void encode_flac(sbv2_pipeline* p, int ctx, VitsModel& vm, const PcmFmtSpec& spec, const void* dev, const std::vector<int64_t>& outs,
-                        uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes) {
-    FlacEncoder& enc = flac_encoder(p, ctx, vm.device());
-    std::vector<int64_t> offs(outs.size()), bytes;
-    for (size_t i = 1; i < outs.size(); ++i) offs[i] = offs[i - 1] + outs[i - 1];
-    const int64_t nbytes = enc.encode(static_cast<const int16_t*>(dev), offs, outs, spec.rate, vm.stream(), &bytes);
-    SBV2_REQUIRE(capacity_bytes >= nbytes, "FLAC buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(nbytes) + " bytes");
-    HIP_CHECK(hipMemcpyAsync(dst, enc.output(), (size_t)nbytes, hipMemcpyDeviceToHost, vm.stream()));
-    HIP_CHECK(hipStreamSynchronize(vm.stream()));
-    for (size_t i = 0; i < bytes.size(); ++i) out_bytes[i] = bytes[i];
 }
 
 int64_t sbv2_flac_bound(const sbv2_pcm_format* fmt, int64_t n_native) {
     try {
-        const PcmFmtSpec spec = flac_spec(fmt);
+        const PcmFmtSpec spec = fetch_spec(fmt, false, Sink::kFlac);
         SBV2_REQUIRE(n_native >= 0, "negative sample count");
         return flac_bound(pcm_format_out_len(spec, n_native));
     } catch (const std::exception& e) {
@@ -435,29 +455,14 @@ int64_t sbv2_flac_bound(const sbv2_pcm_format* fmt, int64_t n_native) {
     }
 }
 
-// The s16 signals of sbv2_pipeline_fetch_pcm_format stay in HBM; the encoder's three launches follow on the run's stream, the host reads back
-// the stream sizes, then exactly the encoded bytes cross PCIe.
 int sbv2_pipeline_fetch_flac(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const int64_t* place, int64_t joined_len, uint8_t* dst,
                              int64_t capacity_bytes, int64_t* out_bytes) {
     API_BEGIN
     SBV2_REQUIRE(p && dst && out_bytes, "bad arguments");
-    const PcmFmtSpec spec = flac_spec(fmt);
-    const int ctx = p->ctx_of(ticket);
-    VitsModel& vm = p->vm(ctx);
-    std::vector<FmtPiece> pieces;
-    std::vector<FmtSignal> sig;
-    std::vector<int64_t> outs;
-    int64_t total = 0;
-    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
-    HIP_CHECK(hipSetDevice(vm.device()));
-    PcmFormatter& f = formatter(p, ctx, vm.device());
-    void* dev = f.out_buffer((size_t)std::max<int64_t>(total, 1) * spec.bytes(), vm.stream());
-    f.run(spec, pieces, sig, total, dev, 0, vm.stream());
-    encode_flac(p, ctx, vm, spec, dev, outs, dst, capacity_bytes, out_bytes);
+    fetch_formatted(p, ticket, fmt, FetchGain(), place, joined_len, Sink::kFlac, dst, capacity_bytes, out_bytes, nullptr);
     API_END
 }
 
-// ---- loudness (loudness.hip) ----
 int sbv2_loudness_kweight(int32_t sample_rate, double* coef) {
     API_BEGIN
     SBV2_REQUIRE(coef, "bad arguments");
@@ -465,47 +470,11 @@ int sbv2_loudness_kweight(int32_t sample_rate, double* coef) {
     API_END
 }
 
-static PcmFmtSpec loudness_format(const sbv2_pcm_format* fmt) {
-    const PcmFmtSpec spec = pcm_format_spec(fmt);
-    SBV2_REQUIRE(!spec.normalize, "loudness normalisation replaces peak normalisation: fmt->normalize must be 0");
-    return spec;
-}
-
-// the signals of a fetch, formatted with their loudness gains into the formatter's output buffer (enqueued on the run's stream); the
-// stats reach meter.stats_host() once the stream is synchronised
-static void* format_loudness(sbv2_pipeline* p, int ctx, VitsModel& vm, const PcmFmtSpec& spec, const LoudnessSpec& ln,
-                             const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, LoudnessMeter** meter) {
-    HIP_CHECK(hipSetDevice(vm.device()));
-    if ((int)p->meters.size() < p->contexts()) p->meters.resize(p->contexts());
-    if (!p->meters[ctx]) p->meters[ctx].reset(new LoudnessMeter(vm.device()));
-    *meter = p->meters[ctx].get();
-    PcmFormatter& f = formatter(p, ctx, vm.device());
-    void* dev = f.out_buffer((size_t)std::max<int64_t>(total, 1) * spec.bytes(), vm.stream());
-    f.run_loudness(spec, pieces, sig, total, dev, 0, vm.stream(), **meter, ln);
-    return dev;
-}
-
 int sbv2_pipeline_fetch_pcm_loudness(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_loudness* ln, const int64_t* place,
                                      int64_t joined_len, void* dst, int64_t capacity_bytes, int64_t* out_lens, double* stats) {
     API_BEGIN
     SBV2_REQUIRE(p && dst && out_lens, "bad arguments");
-    const PcmFmtSpec spec = loudness_format(fmt);
-    const LoudnessSpec lspec = loudness_spec(ln);
-    const int ctx = p->ctx_of(ticket);
-    VitsModel& vm = p->vm(ctx);
-    std::vector<FmtPiece> pieces;
-    std::vector<FmtSignal> sig;
-    std::vector<int64_t> outs;
-    int64_t total = 0;
-    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
-    SBV2_REQUIRE(capacity_bytes >= total * spec.bytes(),
-                 "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(total * spec.bytes()) + " bytes");
-    LoudnessMeter* meter = nullptr;
-    void* dev = format_loudness(p, ctx, vm, spec, lspec, pieces, sig, total, &meter);
-    if (total > 0) HIP_CHECK(hipMemcpyAsync(dst, dev, (size_t)total * spec.bytes(), hipMemcpyDeviceToHost, vm.stream()));
-    HIP_CHECK(hipStreamSynchronize(vm.stream()));
-    for (size_t i = 0; i < outs.size(); ++i) out_lens[i] = outs[i];
-    if (stats) std::memcpy(stats, meter->stats_host(), sizeof(double) * 3 * outs.size());
+    fetch_formatted(p, ticket, fmt, FetchGain{FetchGain::kLoudness, ln, nullptr}, place, joined_len, Sink::kPcm, dst, capacity_bytes, out_lens, stats);
     API_END
 }
 
@@ -513,60 +482,15 @@ int sbv2_pipeline_fetch_flac_loudness(sbv2_pipeline* p, int64_t ticket, const sb
                                       int64_t joined_len, uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes, double* stats) {
     API_BEGIN
     SBV2_REQUIRE(p && dst && out_bytes, "bad arguments");
-    const PcmFmtSpec spec = loudness_format(fmt);
-    SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
-    const LoudnessSpec lspec = loudness_spec(ln);
-    const int ctx = p->ctx_of(ticket);
-    VitsModel& vm = p->vm(ctx);
-    std::vector<FmtPiece> pieces;
-    std::vector<FmtSignal> sig;
-    std::vector<int64_t> outs;
-    int64_t total = 0;
-    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
-    LoudnessMeter* meter = nullptr;
-    void* dev = format_loudness(p, ctx, vm, spec, lspec, pieces, sig, total, &meter);
-    encode_flac(p, ctx, vm, spec, dev, outs, dst, capacity_bytes, out_bytes);
-    if (stats) std::memcpy(stats, meter->stats_host(), sizeof(double) * 3 * outs.size());
+    fetch_formatted(p, ticket, fmt, FetchGain{FetchGain::kLoudness, ln, nullptr}, place, joined_len, Sink::kFlac, dst, capacity_bytes, out_bytes, stats);
     API_END
-}
-
-// ---- look-ahead true-peak limiter (limiter.hip) ----
-// as format_loudness, through the limiter: the stats (6 per signal) reach limiter.stats_host() once the stream is synchronised
-static void* format_limited(sbv2_pipeline* p, int ctx, VitsModel& vm, const PcmFmtSpec& spec, const LimiterSpec& lim,
-                            const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, Limiter** limiter) {
-    HIP_CHECK(hipSetDevice(vm.device()));
-    if ((int)p->meters.size() < p->contexts()) p->meters.resize(p->contexts());
-    if (!p->meters[ctx]) p->meters[ctx].reset(new LoudnessMeter(vm.device()));
-    if ((int)p->limiters.size() < p->contexts()) p->limiters.resize(p->contexts());
-    if (!p->limiters[ctx]) p->limiters[ctx].reset(new Limiter(vm.device()));
-    *limiter = p->limiters[ctx].get();
-    PcmFormatter& f = formatter(p, ctx, vm.device());
-    void* dev = f.out_buffer((size_t)std::max<int64_t>(total, 1) * spec.bytes(), vm.stream());
-    f.run_limited(spec, pieces, sig, total, dev, 0, vm.stream(), *p->meters[ctx], **limiter, lim);
-    return dev;
 }
 
 int sbv2_pipeline_fetch_pcm_limited(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_limiter* lim, const int64_t* place,
                                     int64_t joined_len, void* dst, int64_t capacity_bytes, int64_t* out_lens, double* stats) {
     API_BEGIN
     SBV2_REQUIRE(p && dst && out_lens, "bad arguments");
-    const PcmFmtSpec spec = loudness_format(fmt);
-    const LimiterSpec lspec = limiter_spec(lim);
-    const int ctx = p->ctx_of(ticket);
-    VitsModel& vm = p->vm(ctx);
-    std::vector<FmtPiece> pieces;
-    std::vector<FmtSignal> sig;
-    std::vector<int64_t> outs;
-    int64_t total = 0;
-    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
-    SBV2_REQUIRE(capacity_bytes >= total * spec.bytes(),
-                 "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(total * spec.bytes()) + " bytes");
-    Limiter* limiter = nullptr;
-    void* dev = format_limited(p, ctx, vm, spec, lspec, pieces, sig, total, &limiter);
-    if (total > 0) HIP_CHECK(hipMemcpyAsync(dst, dev, (size_t)total * spec.bytes(), hipMemcpyDeviceToHost, vm.stream()));
-    HIP_CHECK(hipStreamSynchronize(vm.stream()));
-    for (size_t i = 0; i < outs.size(); ++i) out_lens[i] = outs[i];
-    if (stats) std::memcpy(stats, limiter->stats_host(), sizeof(double) * 6 * outs.size());
+    fetch_formatted(p, ticket, fmt, FetchGain{FetchGain::kLimiter, nullptr, lim}, place, joined_len, Sink::kPcm, dst, capacity_bytes, out_lens, stats);
     API_END
 }
 
@@ -574,20 +498,7 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
                                      int64_t joined_len, uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes, double* stats) {
     API_BEGIN
     SBV2_REQUIRE(p && dst && out_bytes, "bad arguments");
-    const PcmFmtSpec spec = loudness_format(fmt);
-    SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
-    const LimiterSpec lspec = limiter_spec(lim);
-    const int ctx = p->ctx_of(ticket);
-    VitsModel& vm = p->vm(ctx);
-    std::vector<FmtPiece> pieces;
-    std::vector<FmtSignal> sig;
-    std::vector<int64_t> outs;
-    int64_t total = 0;
-    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
-    Limiter* limiter = nullptr;
-    void* dev = format_limited(p, ctx, vm, spec, lspec, pieces, sig, total, &limiter);
-    encode_flac(p, ctx, vm, spec, dev, outs, dst, capacity_bytes, out_bytes);
-    if (stats) std::memcpy(stats, limiter->stats_host(), sizeof(double) * 6 * outs.size());
+    fetch_formatted(p, ticket, fmt, FetchGain{FetchGain::kLimiter, nullptr, lim}, place, joined_len, Sink::kFlac, dst, capacity_bytes, out_bytes, stats);
     API_END
 }
 

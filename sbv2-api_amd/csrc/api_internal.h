@@ -24,16 +24,22 @@ struct sbv2_bert {
 struct sbv2_vits {
     std::unique_ptr<VitsModel> m;
 };
+// The output chain of one execution context: what the formatted fetches (fetch_formatted, api.cpp) launch on that context's stream.  Every
+// member grows its device and pinned buffers on first use and holds none before: a pipeline that never asks for FLAC or a limiter pays
+// nothing for them, and creating the pipeline allocates nothing here.
+struct OutputChain {
+    PcmFormatter formatter;
+    FlacEncoder flac;
+    LoudnessMeter meter;
+    Limiter limiter;   // (owns a second meter, for its evaluations)
+};
 struct sbv2_pipeline {
     sbv2_bert* bert;
     sbv2_vits* vits;
     // execution contexts: context 0 is the caller's pair of handles, the others are clones (shared weights, own stream + arena)
     std::vector<std::unique_ptr<BertModel>> bclones;
     std::vector<std::unique_ptr<VitsModel>> vclones;
-    std::vector<std::unique_ptr<PcmFormatter>> fmts;   // per context: the formatting launches of sbv2_pipeline_fetch_pcm_format
-    std::vector<std::unique_ptr<FlacEncoder>> flacs;   // per context: the encoding launches of sbv2_pipeline_fetch_flac
-    std::vector<std::unique_ptr<LoudnessMeter>> meters;   // per context: the meter of sbv2_pipeline_fetch_pcm_loudness / _flac_loudness
-    std::vector<std::unique_ptr<Limiter>> limiters;   // per context: the limiter of sbv2_pipeline_fetch_pcm_limited / _flac_limited
+    std::vector<OutputChain> chains;   // one per context
     int64_t calls = 0;   // tickets are call numbers 1, 2, ...: ticket t ran on context (t - 1) % depth and is valid until that context is reused
     BertModel& bm(int i) { return i == 0 ? *bert->m : *bclones[i - 1]; }
     VitsModel& vm(int i) { return i == 0 ? *vits->m : *vclones[i - 1]; }

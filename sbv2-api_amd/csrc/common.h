@@ -138,6 +138,59 @@ struct UploadBatch {
 };
 
 // ---------------------------------------------------------------------------------------------
+// Grow-on-demand buffers outside the arenas (the output chain: pcm_format / loudness / limiter / flac_encode): a move-only owner of one
+// device (DeviceBuffer) or pinned host (PinnedBuffer) allocation.  It is freed on the device that was current when it was allocated.
+// ---------------------------------------------------------------------------------------------
+struct DeviceMem {
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t free(void* p) { return hipFree(p); }
+};
+struct PinnedMem {
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static hipError_t free(void* p) { return hipHostFree(p); }
+};
+template <class Mem>
+class GrowBuffer {
+  public:
+    GrowBuffer() = default;
+    GrowBuffer(GrowBuffer&& o) noexcept : p_(o.p_), cap_(o.cap_), device_(o.device_) { o.p_ = nullptr, o.cap_ = 0; }
+    GrowBuffer& operator=(GrowBuffer&& o) noexcept {
+        std::swap(p_, o.p_), std::swap(cap_, o.cap_), std::swap(device_, o.device_);
+        return *this;
+    }
+    ~GrowBuffer() {
+        if (!p_) return;
+        (void)hipSetDevice(device_);
+        (void)Mem::free(p_);
+    }
+    // A buffer of >= need bytes.  One that is too small is replaced by `bytes_to_allocate` (>= need) bytes, its contents lost: `s`, the
+    // one stream the buffer is used on, is synchronised first, so nothing enqueued still reads or writes the old allocation.
+    void* reserve(size_t need, size_t bytes_to_allocate, hipStream_t s) {
+        if (need > cap_) {
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (p_) HIP_CHECK(Mem::free(p_));
+            p_ = nullptr;
+            cap_ = 0;
+            HIP_CHECK(hipGetDevice(&device_));
+            HIP_CHECK(Mem::alloc(&p_, bytes_to_allocate));
+            cap_ = bytes_to_allocate;
+        }
+        return p_;
+    }
+    void* reserve(size_t need, hipStream_t s) { return reserve(need, need, s); }   // exact size
+    void* get() const { return p_; }
+    template <class T>
+    T* as() const { return static_cast<T*>(p_); }
+
+  private:
+    void* p_ = nullptr;
+    size_t cap_ = 0;
+    int device_ = 0;
+};
+using DeviceBuffer = GrowBuffer<DeviceMem>;
+using PinnedBuffer = GrowBuffer<PinnedMem>;
+
+// ---------------------------------------------------------------------------------------------
 // Weight blob ("SBV2W001", see sbv2-api_amd/synth.py)
 // ---------------------------------------------------------------------------------------------
 struct HostTensor {

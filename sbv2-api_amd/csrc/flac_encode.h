@@ -1,5 +1,5 @@
 // FLAC encoder on the device (flac_encode.hip): mono 16-bit streams of the s16 samples PcmFormatter::run leaves in HBM, encoded before the
-// copy to the host.  Used by sbv2_pipeline_fetch_flac and sbv2_debug_flac_encode (api.cpp).
+// copy to the host.  Used by the FLAC sink of the formatted fetches (fetch_formatted, api.cpp) and sbv2_debug_flac_encode (test_hooks.cpp).
 #pragma once
 #include "common.h"
 
@@ -19,30 +19,21 @@ int flac_rate_code(int rate);
 // offsets and per-signal sizes, and the output buffer of the streams (all grown on demand; growing synchronises the stream).
 class FlacEncoder {
   public:
-    explicit FlacEncoder(int device) : device_(device) {}
-    ~FlacEncoder();
+    FlacEncoder() = default;
     FlacEncoder(const FlacEncoder&) = delete;
     FlacEncoder& operator=(const FlacEncoder&) = delete;
     // Encodes signal i = x_dev[offs[i], offs[i] + lens[i]) (device s16) as one FLAC stream at `rate`; the streams lie back to back in output().
     // Enqueues three launches on s, then reads back the per-signal sizes (synchronises s): bytes[i] = stream i's size, returns the total.
     int64_t encode(const int16_t* x_dev, const std::vector<int64_t>& offs, const std::vector<int64_t>& lens, int rate, hipStream_t s,
                    std::vector<int64_t>* bytes);
-    const void* output() const { return out_; }
+    const void* output() const { return out_.get(); }
 
   private:
-    template <typename T>
-    T* grow(T*& p, size_t& cap, size_t n, hipStream_t s);
-    int device_;
-    void* sig_host_ = nullptr;   // pinned signal table
-    size_t sig_host_cap_ = 0;
-    void* sig_ = nullptr;        // device: signal table, then per-signal outputs
-    size_t sig_cap_ = 0;
-    void* frames_ = nullptr;     // device: per-frame descriptors and the scan's prefix
-    size_t frames_cap_ = 0;
-    int64_t* sizes_host_ = nullptr;   // pinned: per-signal stream sizes + total + error word
-    size_t sizes_host_cap_ = 0;
-    uint8_t* out_ = nullptr;
-    size_t out_cap_ = 0;
+    PinnedBuffer sig_host_;     // signal table
+    DeviceBuffer sig_;          // signal table, then per-signal outputs
+    DeviceBuffer frames_;       // per-frame descriptors and the scan's prefix
+    PinnedBuffer sizes_host_;   // per-signal stream sizes + total + error word
+    DeviceBuffer out_;
 };
 
 }  // namespace sbv2

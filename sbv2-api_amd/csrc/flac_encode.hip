@@ -600,28 +600,6 @@ int flac_rate_code(int rate) {
     throw std::runtime_error("unsupported sample rate " + std::to_string(rate) + " (8000 16000 22050 24000 32000 44100 48000)");
 }
 
-FlacEncoder::~FlacEncoder() {
-    (void)hipSetDevice(device_);
-    if (sig_host_) (void)hipHostFree(sig_host_);
-    if (sizes_host_) (void)hipHostFree(sizes_host_);
-    if (sig_) (void)hipFree(sig_);
-    if (frames_) (void)hipFree(frames_);
-    if (out_) (void)hipFree(out_);
-}
-
-template <typename T>
-T* FlacEncoder::grow(T*& p, size_t& cap, size_t n, hipStream_t s) {
-    if (n > cap) {
-        HIP_CHECK(hipStreamSynchronize(s));   // the buffers are only used on this context's stream
-        if (p) HIP_CHECK(hipFree(p));
-        p = nullptr;
-        cap = 0;
-        HIP_CHECK(hipMalloc((void**)&p, n));
-        cap = n;
-    }
-    return p;
-}
-
 int64_t FlacEncoder::encode(const int16_t* x_dev, const std::vector<int64_t>& offs, const std::vector<int64_t>& lens, int rate, hipStream_t s,
                             std::vector<int64_t>* bytes) {
     const int rate_code = flac_rate_code(rate);
@@ -640,24 +618,11 @@ int64_t FlacEncoder::encode(const int16_t* x_dev, const std::vector<int64_t>& of
     const size_t sig_b = round_up64(sizeof(FlacSig) * nsig, 64), sz_b = round_up64(8 * (nsig + 2), 64), off_b = round_up64(8 * nsig, 64),
                  mm_b = round_up64(4 * nsig, 64);
     const size_t desc_b = round_up64(sizeof(FlacDesc) * nframes, 64), pre_b = 8 * (nframes + 1);
-    if (sig_b > sig_host_cap_) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (sig_host_) HIP_CHECK(hipHostFree(sig_host_));
-        sig_host_ = nullptr;
-        sig_host_cap_ = 0;
-        HIP_CHECK(hipHostMalloc(&sig_host_, sig_b, hipHostMallocDefault));
-        sig_host_cap_ = sig_b;
-    }
-    if (sz_b > sizes_host_cap_) {
-        if (sizes_host_) HIP_CHECK(hipHostFree(sizes_host_));
-        sizes_host_ = nullptr;
-        sizes_host_cap_ = 0;
-        HIP_CHECK(hipHostMalloc((void**)&sizes_host_, sz_b, hipHostMallocDefault));
-        sizes_host_cap_ = sz_b;
-    }
-    char* sd = static_cast<char*>(grow(sig_, sig_cap_, sig_b + sz_b + off_b + 2 * mm_b, s));
-    char* fd = static_cast<char*>(grow(frames_, frames_cap_, desc_b + pre_b, s));
-    uint8_t* out = grow(out_, out_cap_, (size_t)std::max<int64_t>(cap, 1), s);
+    void* sig_host = sig_host_.reserve(sig_b, s);   // (the buffers are only used on this context's stream)
+    const int64_t* sizes_host = static_cast<const int64_t*>(sizes_host_.reserve(sz_b, s));
+    char* sd = static_cast<char*>(sig_.reserve(sig_b + sz_b + off_b + 2 * mm_b, s));
+    char* fd = static_cast<char*>(frames_.reserve(desc_b + pre_b, s));
+    uint8_t* out = static_cast<uint8_t*>(out_.reserve((size_t)std::max<int64_t>(cap, 1), s));
     FlacSig* d_sig = reinterpret_cast<FlacSig*>(sd);
     int64_t* d_sizes = reinterpret_cast<int64_t*>(sd + sig_b);
     int64_t* d_off = reinterpret_cast<int64_t*>(sd + sig_b + sz_b);
@@ -666,8 +631,8 @@ int64_t FlacEncoder::encode(const int16_t* x_dev, const std::vector<int64_t>& of
     FlacDesc* d_desc = reinterpret_cast<FlacDesc*>(fd);
     int64_t* d_pre = reinterpret_cast<int64_t*>(fd + desc_b);
 
-    std::memcpy(sig_host_, sig.data(), sizeof(FlacSig) * nsig);
-    HIP_CHECK(hipMemcpyAsync(d_sig, sig_host_, sizeof(FlacSig) * nsig, hipMemcpyHostToDevice, s));
+    std::memcpy(sig_host, sig.data(), sizeof(FlacSig) * nsig);
+    HIP_CHECK(hipMemcpyAsync(d_sig, sig_host, sizeof(FlacSig) * nsig, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemsetAsync(d_sizes, 0, 8 * (nsig + 2), s));
     HIP_CHECK(hipMemsetAsync(d_min, 0xFF, 4 * nsig, s));
     HIP_CHECK(hipMemsetAsync(d_max, 0, 4 * nsig, s));
@@ -677,12 +642,12 @@ int64_t FlacEncoder::encode(const int16_t* x_dev, const std::vector<int64_t>& of
     hipLaunchKernelGGL(k_flac_pack, dim3((unsigned)(nframes + (nsig + kT - 1) / kT)), dim3(kT), 0, s, xs, d_sig, nsig, rate, rate_code, d_desc,
                        d_pre, (int)nframes, d_off, d_min, d_max, out, cap, d_sizes + nsig + 1);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(sizes_host_, d_sizes, 8 * (nsig + 2), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(sizes_host_.get(), d_sizes, 8 * (nsig + 2), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    SBV2_REQUIRE(sizes_host_[nsig + 1] == 0, "FLAC encoder: internal error " + std::to_string(sizes_host_[nsig + 1]) + " (frame sizes disagree)");
-    bytes->assign(sizes_host_, sizes_host_ + nsig);
-    SBV2_REQUIRE(sizes_host_[nsig] <= cap, "FLAC encoder: stream larger than its bound");
-    return sizes_host_[nsig];
+    SBV2_REQUIRE(sizes_host[nsig + 1] == 0, "FLAC encoder: internal error " + std::to_string(sizes_host[nsig + 1]) + " (frame sizes disagree)");
+    bytes->assign(sizes_host, sizes_host + nsig);
+    SBV2_REQUIRE(sizes_host[nsig] <= cap, "FLAC encoder: stream larger than its bound");
+    return sizes_host[nsig];
 }
 
 }  // namespace sbv2

@@ -1,6 +1,6 @@
 // Look-ahead true-peak limiter on the device (limiter.hip): the stage between the loudness meter and the gain / quantiser / FLAC encoder of
-// sbv2_pipeline_fetch_pcm_limited / _fetch_flac_limited, and of the test hook sbv2_debug_limiter.  The convention is the header comment of
-// struct sbv2_limiter (include/sbv2_hip.h).
+// sbv2_pipeline_fetch_pcm_limited / _fetch_flac_limited (the limiter GainStage of PcmFormatter::run), and of the test hook
+// sbv2_debug_limiter.  The convention is the header comment of struct sbv2_limiter (include/sbv2_hip.h).
 #pragma once
 #include "common.h"
 #include "loudness.h"
@@ -22,8 +22,7 @@ LimiterSpec limiter_spec(const sbv2_limiter* lim);
 // synchronises the stream), and a second meter for the evaluations of x.
 class Limiter {
   public:
-    explicit Limiter(int device) : device_(device), xmeter_(device) {}
-    ~Limiter();
+    Limiter() = default;
     Limiter(const Limiter&) = delete;
     Limiter& operator=(const Limiter&) = delete;
     // Enqueues on s: meter.measure(y) (L, TP and the scale-only gain of the signals sig[i] = y[out_off, out_off + j1 - j0) at `rate`), the
@@ -35,12 +34,9 @@ class Limiter {
     const double* stats_host() const { return stats_host_; }
 
   private:
-    int device_;
     LoudnessMeter xmeter_;   // the meter of x (its own scratch: the stats of y stay in the caller's meter)
-    void* host_ = nullptr;   // pinned: signal table, Hann taps, then the stats
-    size_t host_cap_ = 0;
-    void* dev_ = nullptr;
-    size_t dev_cap_ = 0;
+    PinnedBuffer host_;      // signal table, Hann taps, then the stats
+    DeviceBuffer dev_;
     double* stats_host_ = nullptr;
 };
 

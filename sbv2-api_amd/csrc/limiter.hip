@@ -312,12 +312,6 @@ LimiterSpec limiter_spec(const sbv2_limiter* lim) {
     return s;
 }
 
-Limiter::~Limiter() {
-    (void)hipSetDevice(device_);
-    if (host_) (void)hipHostFree(host_);
-    if (dev_) (void)hipFree(dev_);
-}
-
 const double* Limiter::run(const double* y, const std::vector<FmtSignal>& sig, int rate, const LimiterSpec& lim, LoudnessMeter& meter,
                            hipStream_t s, const double** unit) {
     const int nsig = (int)sig.size();
@@ -345,25 +339,8 @@ const double* Limiter::run(const double* y, const std::vector<FmtSignal>& sig, i
     const size_t o_st = tb, o_stats = o_st + sb, o_unit = o_stats + stb, o_h = o_unit + ub, o_t = o_h + hb, o_x = o_t + xb, o_smin = o_x + xb,
                  dbytes = o_smin + round_up64(8 * std::max<int64_t>(tiles, 1), 64);
     const size_t hbytes = tb + hb + stb;
-    if (dbytes > dev_cap_ || hbytes > host_cap_) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (dbytes > dev_cap_) {
-            if (dev_) HIP_CHECK(hipFree(dev_));
-            dev_ = nullptr;
-            dev_cap_ = 0;
-            HIP_CHECK(hipMalloc(&dev_, dbytes * 2));
-            dev_cap_ = dbytes * 2;
-        }
-        if (hbytes > host_cap_) {
-            if (host_) HIP_CHECK(hipHostFree(host_));
-            host_ = nullptr;
-            host_cap_ = 0;
-            HIP_CHECK(hipHostMalloc(&host_, std::max<size_t>(hbytes * 2, 8192), hipHostMallocDefault));
-            host_cap_ = std::max<size_t>(hbytes * 2, 8192);
-        }
-    }
-    char* d = static_cast<char*>(dev_);
-    char* h = static_cast<char*>(host_);
+    char* d = static_cast<char*>(dev_.reserve(dbytes, dbytes * 2, s));
+    char* h = static_cast<char*>(host_.reserve(hbytes, std::max<size_t>(hbytes * 2, 8192), s));
     std::memcpy(h, tab.data(), sizeof(LimSig) * nsig);
     double* hann = reinterpret_cast<double*>(h + tb);   // sin^2(pi (k + 0.5) / K), scaled to sum to 1
     double sum = 0.0, hsum = 0.0;

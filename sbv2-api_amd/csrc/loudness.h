@@ -1,6 +1,6 @@
 // Integrated loudness (ITU-R BS.1770-4 gating, EBU R128) and true peak of formatted signals on the device (loudness.hip): the meter of
-// sbv2_pipeline_fetch_pcm_loudness / _fetch_flac_loudness, run on the f64 signal y the normalising path of PcmFormatter leaves in HBM, and of
-// the test hook sbv2_debug_loudness.
+// sbv2_pipeline_fetch_pcm_loudness / _fetch_flac_loudness (the loudness GainStage of PcmFormatter::run, on the f64 signal y its resampler
+// leaves in HBM), and of the test hook sbv2_debug_loudness.
 #pragma once
 #include "common.h"
 #include "pcm_format.h"
@@ -26,8 +26,7 @@ void loudness_true_peak_taps(double h[3][kTruePeakTaps]);
 // sums, the per-signal true peaks, stats and gains (all grown on demand; growing synchronises the stream).
 class LoudnessMeter {
   public:
-    explicit LoudnessMeter(int device) : device_(device) {}
-    ~LoudnessMeter();
+    LoudnessMeter() = default;
     LoudnessMeter(const LoudnessMeter&) = delete;
     LoudnessMeter& operator=(const LoudnessMeter&) = delete;
     // Enqueues on s the meter of the signals sig[i] = y[out_off, out_off + j1 - j0) (y: device f64, may be null when every signal is
@@ -42,12 +41,9 @@ class LoudnessMeter {
 
   private:
     const std::vector<double>& tables(int rate);
-    int device_;
     std::map<int, std::vector<double>> tables_;
-    void* host_ = nullptr;   // pinned: signal table, then the stats
-    size_t host_cap_ = 0;
-    void* dev_ = nullptr;    // device: signal table, peaks, stats, gains, then the per-segment states and partial sums
-    size_t dev_cap_ = 0;
+    PinnedBuffer host_;   // signal table, then the stats
+    DeviceBuffer dev_;    // signal table, peaks, stats, gains, then the per-segment states and partial sums
     double* stats_host_ = nullptr;
     double* stats_dev_ = nullptr;
 };

@@ -452,12 +452,6 @@ LoudnessSpec loudness_spec(const sbv2_loudness* ln) {
     return s;
 }
 
-LoudnessMeter::~LoudnessMeter() {
-    (void)hipSetDevice(device_);
-    if (host_) (void)hipHostFree(host_);
-    if (dev_) (void)hipFree(dev_);
-}
-
 // c[10], A^m[16], then the true-peak taps [3][24] of a rate: built once per rate
 const std::vector<double>& LoudnessMeter::tables(int rate) {
     auto it = tables_.find(rate);
@@ -492,25 +486,8 @@ const double* LoudnessMeter::measure(const double* y, const std::vector<FmtSigna
                  o_part = o_st + round_up64(32 * nseg, 64), o_bmax = o_part + round_up64(8 * std::max<int64_t>(nseg, 1), 64),
                  dbytes = o_bmax + round_up64(8 * std::max<int64_t>((total + 255) / 256, 1), 64);
     const size_t hbytes = tb + stb;
-    if (dbytes > dev_cap_ || hbytes > host_cap_) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (dbytes > dev_cap_) {
-            if (dev_) HIP_CHECK(hipFree(dev_));
-            dev_ = nullptr;
-            dev_cap_ = 0;
-            HIP_CHECK(hipMalloc(&dev_, dbytes * 2));
-            dev_cap_ = dbytes * 2;
-        }
-        if (hbytes > host_cap_) {
-            if (host_) HIP_CHECK(hipHostFree(host_));
-            host_ = nullptr;
-            host_cap_ = 0;
-            HIP_CHECK(hipHostMalloc(&host_, std::max<size_t>(hbytes * 2, 4096), hipHostMallocDefault));
-            host_cap_ = std::max<size_t>(hbytes * 2, 4096);
-        }
-    }
-    char* d = static_cast<char*>(dev_);
-    char* h = static_cast<char*>(host_);
+    char* d = static_cast<char*>(dev_.reserve(dbytes, dbytes * 2, s));
+    char* h = static_cast<char*>(host_.reserve(hbytes, std::max<size_t>(hbytes * 2, 4096), s));
     std::memcpy(h, tab.data(), sizeof(LSig) * nsig);
     stats_host_ = reinterpret_cast<double*>(h + tb);
     HIP_CHECK(hipMemcpyAsync(d, h, sizeof(LSig) * nsig, hipMemcpyHostToDevice, s));

@@ -1,5 +1,5 @@
 // Output formats of the PCM (pcm_format.hip): rational polyphase resampling from 44.1 kHz, optional peak normalisation and the f32 -> s16
-// quantiser, on the device, next to the PCM a run leaves in HBM.  Used by the pipeline fetch (api.cpp) and the streaming decoder (vits.cpp).
+// quantiser, on the device, next to the PCM a run leaves in HBM.  Used by the formatted fetches (fetch_formatted, api.cpp) and the streaming decoder (vits.cpp).
 #pragma once
 #include "common.h"
 
@@ -44,48 +44,47 @@ struct LoudnessSpec;
 class Limiter;   // limiter.h
 struct LimiterSpec;
 
+// The gain stage of a formatting run, between the resampler and the quantiser: none (peak-normalise or not, as spec.normalize says), a
+// loudness gain from `meter` (loudness.hip), or the look-ahead limiter (limiter.hip).  Only these three can be built.
+struct GainStage {
+    enum Kind { kNone, kLoudness, kLimiter };
+    GainStage() = default;
+    GainStage(LoudnessMeter& m, const LoudnessSpec& l) : kind(kLoudness), meter(&m), ln(&l) {}
+    GainStage(LoudnessMeter& m, Limiter& li, const LimiterSpec& l) : kind(kLimiter), meter(&m), limiter(&li), lim(&l) {}
+    const Kind kind = kNone;
+    LoudnessMeter* const meter = nullptr;   // the meter of y (both stages)
+    const LoudnessSpec* const ln = nullptr;
+    Limiter* const limiter = nullptr;
+    const LimiterSpec* const lim = nullptr;
+};
+
 // Device state of the formatting launches of one execution context: the polyphase tables (per rate, built once), the tables of pieces /
 // signals (one pinned + device pair per `slot`: a slot's host copy is rewritten only once the launch that used it has completed), the
-// per-signal peaks, the f64 intermediate of the normalising path and an output buffer.
+// per-signal peaks, the f64 intermediate of the normalising path and an output buffer.  Nothing is allocated before the first run.
 class PcmFormatter {
   public:
-    explicit PcmFormatter(int device) : device_(device) {}
-    ~PcmFormatter();
+    PcmFormatter() = default;
     PcmFormatter(const PcmFormatter&) = delete;
     PcmFormatter& operator=(const PcmFormatter&) = delete;
     // device buffer of >= bytes, used on stream s only (grown on demand; growing synchronises s, callers size it before a stream starts)
-    void* out_buffer(size_t bytes, hipStream_t s);
-    // enqueues the formatting of `sig` on `s`: total = sum of the signals' j1 - j0 samples into dst_dev (device, total * spec.bytes() bytes)
+    void* out_buffer(size_t bytes, hipStream_t s) { return out_.reserve(bytes, s); }
+    // enqueues the formatting of `sig` on `s`: total = sum of the signals' j1 - j0 samples into dst_dev (device, total * spec.bytes() bytes).
+    // With a gain stage (spec.normalize must be 0): y in f64, then meter.measure(y) and y times each signal's gain, or limiter.run(y, meter)
+    // and its x as it is; the stage runs also when every signal is empty, so that its stats are written.
     void run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
-             int slot, hipStream_t s);
-    // the same with a loudness gain (spec.normalize must be 0): y in f64, meter.measure(y) (loudness.hip), then y times each signal's gain.
-    // Runs the meter also when every signal is empty.
-    void run_loudness(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
-                      void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, const LoudnessSpec& ln);
-
-    // the same through the look-ahead limiter (spec.normalize must be 0): y in f64, limiter.run(y, meter) (limiter.hip), then its x as it is.
-    void run_limited(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
-                     void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, Limiter& limiter, const LimiterSpec& lim);
+             int slot, hipStream_t s, const GainStage& gain = GainStage());
 
   private:
-    void run_impl(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
-                  int slot, hipStream_t s, LoudnessMeter* meter, const LoudnessSpec* ln, Limiter* limiter = nullptr,
-                  const LimiterSpec* lim = nullptr);
     struct Slot {
-        void* host = nullptr;
-        void* dev = nullptr;
-        size_t cap = 0;
+        PinnedBuffer host;
+        DeviceBuffer dev;
     };
     const float* taps(const PcmFmtSpec& spec, hipStream_t s);
-    int device_;
-    std::map<int, float*> taps_;       // rate -> [L][T] polyphase table
+    std::map<int, DeviceBuffer> taps_;   // rate -> [L][T] polyphase table
     std::vector<Slot> slots_;
-    double* tmp_ = nullptr;            // normalising path: y before the gain
-    size_t tmp_cap_ = 0;
-    unsigned long long* peak_ = nullptr;   // max |y| (f64 bit pattern), one per signal
-    size_t peak_cap_ = 0;
-    void* out_ = nullptr;
-    size_t out_cap_ = 0;
+    DeviceBuffer tmp_;    // normalising path: y (f64) before the gain
+    DeviceBuffer peak_;   // max |y| (f64 bit pattern), one per signal
+    DeviceBuffer out_;
 };
 
 }  // namespace sbv2

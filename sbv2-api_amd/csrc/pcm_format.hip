@@ -218,33 +218,9 @@ PcmFmtSpec pcm_format_spec(const sbv2_pcm_format* f) {
 
 int64_t pcm_format_out_len(const PcmFmtSpec& s, int64_t n) { return n <= 0 ? 0 : (n * s.L + s.M - 1) / s.M; }
 
-PcmFormatter::~PcmFormatter() {
-    (void)hipSetDevice(device_);
-    for (auto& kv : taps_) (void)hipFree(kv.second);
-    for (auto& sl : slots_) {
-        if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.dev) (void)hipFree(sl.dev);
-    }
-    if (tmp_) (void)hipFree(tmp_);
-    if (peak_) (void)hipFree(peak_);
-    if (out_) (void)hipFree(out_);
-}
-
-void* PcmFormatter::out_buffer(size_t bytes, hipStream_t s) {
-    if (bytes > out_cap_) {
-        HIP_CHECK(hipStreamSynchronize(s));   // the buffer is only used on this context's stream
-        if (out_) HIP_CHECK(hipFree(out_));
-        out_ = nullptr;
-        out_cap_ = 0;
-        HIP_CHECK(hipMalloc(&out_, bytes));
-        out_cap_ = bytes;
-    }
-    return out_;
-}
-
 const float* PcmFormatter::taps(const PcmFmtSpec& spec, hipStream_t s) {
     auto it = taps_.find(spec.rate);
-    if (it != taps_.end()) return it->second;
+    if (it != taps_.end()) return it->second.as<float>();
     int L, M, half;
     const std::vector<double> h = pcm_format_prototype(spec.rate, &L, &M, &half);
     // default [T][L]: tap t of branch p = h[p + t L] sits at t L + p, i.e. the table is h itself, zero-padded to T L.  At step t the lanes of a wave
@@ -252,64 +228,44 @@ const float* PcmFormatter::taps(const PcmFmtSpec& spec, hipStream_t s) {
     // every lane on its own row: the A/B of DESIGN.md §8b; same values, same summation order, same bits)
     std::vector<float> tab((size_t)L * spec.T, 0.f);
     for (size_t i = 0; i < h.size(); ++i) tab[branch_major() ? (i % L) * spec.T + i / L : i] = (float)h[i];
-    float* d = nullptr;
-    HIP_CHECK(hipMalloc(&d, sizeof(float) * tab.size()));
-    taps_[spec.rate] = d;
+    float* d = static_cast<float*>(taps_[spec.rate].reserve(sizeof(float) * tab.size(), s));
     HIP_CHECK(hipMemcpyAsync(d, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamSynchronize(s));
     return d;
 }
 
+// the stage on the f64 signal y (null when there is no sample): returns the signal to deliver, *gain = one gain per signal for it
+static const double* apply_gain(const GainStage& g, const double* y, const std::vector<FmtSignal>& sig, int rate, hipStream_t s,
+                                const double** gain) {
+    if (g.kind == GainStage::kLimiter) return g.limiter->run(y, sig, rate, *g.lim, *g.meter, s, gain);   // its own x and unit gains
+    *gain = g.meter->measure(y, sig, rate, *g.ln, s);
+    return y;
+}
+
 void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
-                       int slot, hipStream_t s) {
-    run_impl(spec, pieces, sig, total, dst_dev, slot, s, nullptr, nullptr);
-}
-
-void PcmFormatter::run_loudness(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
-                                void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, const LoudnessSpec& ln) {
-    SBV2_REQUIRE(!spec.normalize, "internal: a loudness gain on a peak-normalised format");
-    run_impl(spec, pieces, sig, total, dst_dev, slot, s, &meter, &ln);
-}
-
-void PcmFormatter::run_limited(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
-                               void* dst_dev, int slot, hipStream_t s, LoudnessMeter& meter, Limiter& limiter, const LimiterSpec& lim) {
-    SBV2_REQUIRE(!spec.normalize, "internal: a limiter on a peak-normalised format");
-    run_impl(spec, pieces, sig, total, dst_dev, slot, s, &meter, nullptr, &limiter, &lim);
-}
-
-void PcmFormatter::run_impl(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total,
-                            void* dst_dev, int slot, hipStream_t s, LoudnessMeter* meter, const LoudnessSpec* ln, Limiter* limiter,
-                            const LimiterSpec* lim) {
+                       int slot, hipStream_t s, const GainStage& stage) {
+    const bool staged = stage.kind != GainStage::kNone;
+    SBV2_REQUIRE(!(staged && spec.normalize), "internal: a gain stage on a peak-normalised format");
     if (sig.empty()) return;
+    const double* gain = nullptr;
     if (total <= 0) {
-        const double* unit = nullptr;
-        if (limiter) limiter->run(nullptr, sig, spec.rate, *lim, *meter, s, &unit);
-        else if (meter) meter->measure(nullptr, sig, spec.rate, *ln, s);
+        if (staged) apply_gain(stage, nullptr, sig, spec.rate, s, &gain);
         return;
     }
     const float* tp = taps(spec, s);
     if ((int)slots_.size() <= slot) slots_.resize(slot + 1);
     Slot& sl = slots_[slot];
     const size_t pb = sizeof(FmtPiece) * pieces.size(), bytes = round_up64((int64_t)pb, 64) + sizeof(FmtSignal) * sig.size();
-    if (bytes > sl.cap) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (sl.host) HIP_CHECK(hipHostFree(sl.host));
-        if (sl.dev) HIP_CHECK(hipFree(sl.dev));
-        sl.host = sl.dev = nullptr;
-        sl.cap = 0;
-        const size_t cap = std::max<size_t>(bytes * 2, 4096);
-        HIP_CHECK(hipHostMalloc(&sl.host, cap, hipHostMallocDefault));
-        HIP_CHECK(hipMalloc(&sl.dev, cap));
-        sl.cap = cap;
-    }
-    char* hb = static_cast<char*>(sl.host);
+    const size_t cap = std::max<size_t>(bytes * 2, 4096);
+    char* hb = static_cast<char*>(sl.host.reserve(bytes, cap, s));
+    char* db = static_cast<char*>(sl.dev.reserve(bytes, cap, s));
     const size_t so = round_up64((int64_t)pb, 64);
     if (pb) std::memcpy(hb, pieces.data(), pb);
     std::memcpy(hb + so, sig.data(), sizeof(FmtSignal) * sig.size());
-    HIP_CHECK(hipMemcpyAsync(sl.dev, sl.host, bytes, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, s));
     KArgs a;
-    a.pieces = reinterpret_cast<const FmtPiece*>(sl.dev);
-    a.sig = reinterpret_cast<const FmtSignal*>(static_cast<char*>(sl.dev) + so);
+    a.pieces = reinterpret_cast<const FmtPiece*>(db);
+    a.sig = reinterpret_cast<const FmtSignal*>(db + so);
     a.nsig = (int)sig.size();
     a.taps = tp;
     a.L = spec.L;
@@ -320,43 +276,26 @@ void PcmFormatter::run_impl(const PcmFmtSpec& spec, const std::vector<FmtPiece>&
     a.st = branch_major() ? 1 : spec.L;
     a.total = total;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-    if (!spec.normalize && !meter) {
+    if (!spec.normalize && !staged) {
         if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_resample<1>, grid, block, 0, s, a, dst_dev, nullptr);
         else hipLaunchKernelGGL(k_pcm_resample<0>, grid, block, 0, s, a, dst_dev, nullptr);
         HIP_CHECK(hipGetLastError());
         return;
     }
-    if ((size_t)total > tmp_cap_) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (tmp_) HIP_CHECK(hipFree(tmp_));
-        tmp_ = nullptr;
-        tmp_cap_ = 0;
-        HIP_CHECK(hipMalloc(&tmp_, sizeof(double) * (size_t)total));
-        tmp_cap_ = (size_t)total;
-    }
-    if (sig.size() > peak_cap_) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (peak_) HIP_CHECK(hipFree(peak_));
-        peak_ = nullptr;
-        peak_cap_ = 0;
-        HIP_CHECK(hipMalloc(&peak_, sizeof(unsigned long long) * sig.size()));
-        peak_cap_ = sig.size();
-    }
-    if (meter) {
-        hipLaunchKernelGGL(k_pcm_resample<3>, grid, block, 0, s, a, tmp_, nullptr);
-        const double* gain = nullptr;
-        const double* x = tmp_;   // the limiter hands back its own x and unit gains: the kernels below deliver it as it is
-        if (limiter) x = limiter->run(tmp_, sig, spec.rate, *lim, *meter, s, &gain);
-        else gain = meter->measure(tmp_, sig, spec.rate, *ln, s);
+    double* tmp = static_cast<double*>(tmp_.reserve(sizeof(double) * (size_t)total, s));
+    auto* peak = static_cast<unsigned long long*>(peak_.reserve(sizeof(unsigned long long) * sig.size(), s));
+    if (staged) {
+        hipLaunchKernelGGL(k_pcm_resample<3>, grid, block, 0, s, a, tmp, nullptr);
+        const double* x = apply_gain(stage, tmp, sig, spec.rate, s, &gain);
         if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain_sig<1>, grid, block, 0, s, x, a.sig, a.nsig, gain, total, dst_dev);
         else hipLaunchKernelGGL(k_pcm_gain_sig<0>, grid, block, 0, s, x, a.sig, a.nsig, gain, total, dst_dev);
         HIP_CHECK(hipGetLastError());
         return;
     }
-    HIP_CHECK(hipMemsetAsync(peak_, 0, sizeof(unsigned long long) * sig.size(), s));
-    hipLaunchKernelGGL(k_pcm_resample<2>, grid, block, 0, s, a, tmp_, peak_);
-    if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain<1>, grid, block, 0, s, tmp_, a.sig, a.nsig, peak_, total, dst_dev);
-    else hipLaunchKernelGGL(k_pcm_gain<0>, grid, block, 0, s, tmp_, a.sig, a.nsig, peak_, total, dst_dev);
+    HIP_CHECK(hipMemsetAsync(peak, 0, sizeof(unsigned long long) * sig.size(), s));
+    hipLaunchKernelGGL(k_pcm_resample<2>, grid, block, 0, s, a, tmp, peak);
+    if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain<1>, grid, block, 0, s, tmp, a.sig, a.nsig, peak, total, dst_dev);
+    else hipLaunchKernelGGL(k_pcm_gain<0>, grid, block, 0, s, tmp, a.sig, a.nsig, peak, total, dst_dev);
     HIP_CHECK(hipGetLastError());
 }
 

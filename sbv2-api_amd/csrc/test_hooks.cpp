@@ -137,6 +137,44 @@ void download_packed(Plane P, const SegLayout& lay, bool poison, float* y, int64
         }
 }
 
+// the signals of the audio hooks: lens[i] samples each, back to back; *total = their sum
+std::vector<FmtSignal> packed_signals(const int64_t* lens, int nsig, int64_t* total) {
+    std::vector<FmtSignal> sig(nsig);
+    *total = 0;
+    for (int i = 0; i < nsig; ++i) {
+        SBV2_REQUIRE(lens[i] >= 0, "negative signal length");
+        sig[i] = FmtSignal{0, lens[i], *total, 0, 0};
+        *total += lens[i];
+    }
+    return sig;
+}
+
+// Scratch of one audio hook call on `device`: a non-blocking stream and the hook's input uploaded on it (x stays null for an empty input
+// unless min_bytes asks for an allocation anyway).  The stream is drained before the buffer and the stream go.
+struct AudioScratch {
+    hipStream_t s = nullptr;
+    DeviceBuffer x;
+    AudioScratch(int device, const void* src, size_t bytes, size_t min_bytes = 0) {
+        HIP_CHECK(hipSetDevice(device));
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        try {
+            if (std::max(bytes, min_bytes)) x.reserve(std::max(bytes, min_bytes), s);
+            if (bytes) HIP_CHECK(hipMemcpyAsync(x.get(), src, bytes, hipMemcpyHostToDevice, s));
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+    ~AudioScratch() { release(); }
+    void release() {
+        (void)hipStreamSynchronize(s);
+        x = DeviceBuffer();
+        (void)hipStreamDestroy(s);
+    }
+    AudioScratch(const AudioScratch&) = delete;
+    AudioScratch& operator=(const AudioScratch&) = delete;
+};
+
 }  // namespace
 
 extern "C" {
@@ -146,30 +184,15 @@ int sbv2_debug_flac_encode(int device, const int16_t* x, const int64_t* lens, in
     API_BEGIN
     SBV2_REQUIRE(nsig >= 1 && lens && dst && out_bytes, "bad arguments");
     flac_rate_code(sample_rate);
-    std::vector<int64_t> ls(lens, lens + nsig), offs(nsig);
     int64_t total = 0;
-    for (int i = 0; i < nsig; ++i) {
-        SBV2_REQUIRE(ls[i] >= 0, "negative signal length");
-        offs[i] = total;
-        total += ls[i];
-    }
+    const std::vector<FmtSignal> sig = packed_signals(lens, nsig, &total);
+    std::vector<int64_t> ls(lens, lens + nsig), offs(nsig);
+    for (int i = 0; i < nsig; ++i) offs[i] = sig[i].out_off;
     SBV2_REQUIRE(total == 0 || x, "bad arguments");
-    HIP_CHECK(hipSetDevice(device));
-    struct Res {
-        hipStream_t s = nullptr;
-        void* x = nullptr;
-        ~Res() {
-            if (s) (void)hipStreamSynchronize(s);
-            if (x) (void)hipFree(x);
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } r;
-    HIP_CHECK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
-    HIP_CHECK(hipMalloc(&r.x, sizeof(int16_t) * (size_t)std::max<int64_t>(total, 1)));
-    if (total) HIP_CHECK(hipMemcpyAsync(r.x, x, sizeof(int16_t) * (size_t)total, hipMemcpyHostToDevice, r.s));
-    FlacEncoder enc(device);
+    AudioScratch r(device, x, sizeof(int16_t) * (size_t)total, sizeof(int16_t));
+    FlacEncoder enc;
     std::vector<int64_t> bytes;
-    const int64_t nbytes = enc.encode(static_cast<const int16_t*>(r.x), offs, ls, sample_rate, r.s, &bytes);
+    const int64_t nbytes = enc.encode(r.x.as<int16_t>(), offs, ls, sample_rate, r.s, &bytes);
     SBV2_REQUIRE(capacity >= nbytes, "FLAC buffer too small: " + std::to_string(capacity) + " < " + std::to_string(nbytes) + " bytes");
     HIP_CHECK(hipMemcpyAsync(dst, enc.output(), (size_t)nbytes, hipMemcpyDeviceToHost, r.s));
     HIP_CHECK(hipStreamSynchronize(r.s));
@@ -183,31 +206,12 @@ int sbv2_debug_loudness(int device, const double* x, const int64_t* lens, int ns
     const LoudnessSpec spec = loudness_spec(ln);
     double coef[10];
     loudness_kweight(sample_rate, coef);   // refuses unsupported rates
-    std::vector<FmtSignal> sig(nsig);
     int64_t total = 0;
-    for (int i = 0; i < nsig; ++i) {
-        SBV2_REQUIRE(lens[i] >= 0, "negative signal length");
-        sig[i] = FmtSignal{0, lens[i], total, 0, 0};
-        total += lens[i];
-    }
+    const std::vector<FmtSignal> sig = packed_signals(lens, nsig, &total);
     SBV2_REQUIRE(total == 0 || x, "bad arguments");
-    HIP_CHECK(hipSetDevice(device));
-    struct Res {
-        hipStream_t s = nullptr;
-        void* x = nullptr;
-        ~Res() {
-            if (s) (void)hipStreamSynchronize(s);
-            if (x) (void)hipFree(x);
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } r;
-    HIP_CHECK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
-    if (total) {
-        HIP_CHECK(hipMalloc(&r.x, sizeof(double) * (size_t)total));
-        HIP_CHECK(hipMemcpyAsync(r.x, x, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, r.s));
-    }
-    LoudnessMeter meter(device);
-    meter.measure(static_cast<const double*>(r.x), sig, sample_rate, spec, r.s);
+    AudioScratch r(device, x, sizeof(double) * (size_t)total);
+    LoudnessMeter meter;
+    meter.measure(r.x.as<double>(), sig, sample_rate, spec, r.s);
     HIP_CHECK(hipStreamSynchronize(r.s));
     std::memcpy(stats, meter.stats_host(), sizeof(double) * 3 * nsig);
     API_END
@@ -220,33 +224,14 @@ int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsi
     const LimiterSpec spec = limiter_spec(lim);
     double coef[10];
     loudness_kweight(sample_rate, coef);   // refuses unsupported rates
-    std::vector<FmtSignal> sig(nsig);
     int64_t total = 0;
-    for (int i = 0; i < nsig; ++i) {
-        SBV2_REQUIRE(lens[i] >= 0, "negative signal length");
-        sig[i] = FmtSignal{0, lens[i], total, 0, 0};
-        total += lens[i];
-    }
+    const std::vector<FmtSignal> sig = packed_signals(lens, nsig, &total);
     SBV2_REQUIRE(total == 0 || (x && out_x), "bad arguments");
-    HIP_CHECK(hipSetDevice(device));
-    struct Res {
-        hipStream_t s = nullptr;
-        void* x = nullptr;
-        ~Res() {
-            if (s) (void)hipStreamSynchronize(s);
-            if (x) (void)hipFree(x);
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } r;
-    HIP_CHECK(hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking));
-    if (total) {
-        HIP_CHECK(hipMalloc(&r.x, sizeof(double) * (size_t)total));
-        HIP_CHECK(hipMemcpyAsync(r.x, x, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, r.s));
-    }
-    LoudnessMeter meter(device);
-    Limiter limiter(device);
+    AudioScratch r(device, x, sizeof(double) * (size_t)total);
+    LoudnessMeter meter;
+    Limiter limiter;
     const double* unit = nullptr;
-    const double* lx = limiter.run(static_cast<const double*>(r.x), sig, sample_rate, spec, meter, r.s, &unit);
+    const double* lx = limiter.run(r.x.as<double>(), sig, sample_rate, spec, meter, r.s, &unit);
     if (total) HIP_CHECK(hipMemcpyAsync(out_x, lx, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, r.s));
     HIP_CHECK(hipStreamSynchronize(r.s));
     std::memcpy(stats, limiter.stats_host(), sizeof(double) * 6 * nsig);

@@ -935,7 +935,7 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt) {
         SBV2_REQUIRE((double)reach <= exact, "the " + std::to_string(fmt->rate) + " Hz filter reaches " + std::to_string(reach) +
                                                  " samples past a chunk edge, the stream halo holds only " + std::to_string((int64_t)exact) + " exact samples");
         sfmt_ = *fmt;
-        if (!sfmtr_) sfmtr_ = std::make_shared<PcmFormatter>(device_);
+        if (!sfmtr_) sfmtr_ = std::make_shared<PcmFormatter>();
     }
     constexpr int burst = kStreamBurst;   // (1 / 2 / 4 / 8 / 12 / 16 windows per replay measured in round 3: 2.62 / 1.88 / 1.64 / 1.41 / 1.39 / 1.47 ms per chunk)
     const int64_t Tf = fl_.len[0];

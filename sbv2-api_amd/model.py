@@ -375,29 +375,8 @@ class Pipeline:
         check(_lib.lib().sbv2_pipeline_fetch_pcm_ticket(self.h, b.ticket, pcm.ctypes.data_as(C.c_void_p), pcm.size, 0))
         return np.split(pcm[:n], np.cumsum(b.lens)[:-1])
 
-    def fetch_format(self, b, fmt: PcmFormat, place=None, joined_len=None):
-        """PCM of the run `b` in the output format `fmt` (resampled / normalised / quantised on the device; int16 or float32 arrays).
-        place None: one array per utterance.  place [n] native-sample offsets + joined_len: ONE array, the utterances laid on a silent
-        timeline of joined_len native samples."""
-        l = _lib.lib()
-        lens = [int(v) for v in b.lens]
-        if place is None:
-            outs = [pcm_format_length(fmt, n) for n in lens]
-            pp, jl = None, 0
-        else:
-            if joined_len is None:
-                raise Sbv2Error("a placement needs joined_len")
-            pl, pp = _i64(place)
-            if pl.shape != (len(lens),):
-                raise Sbv2Error(f"place must hold one offset per utterance ({len(lens)})")
-            outs, jl = [pcm_format_length(fmt, joined_len)], int(joined_len)
-        out = np.empty(max(sum(outs), 1), fmt.dtype)
-        got = np.zeros(len(outs), np.int64)
-        check(l.sbv2_pipeline_fetch_pcm_format(self.h, b.ticket, C.byref(fmt.c), pp, jl, out.ctypes.data_as(C.c_void_p), out.nbytes,
-                                               got.ctypes.data_as(i64p)))
-        return np.split(out[:int(got.sum())], np.cumsum(got)[:-1])
-
     def _layout(self, b, place, joined_len):
+        """(native lengths of the fetch's signals, place pointer, joined_len): the one place a placement is validated."""
         lens = [int(v) for v in b.lens]
         if place is None:
             return lens, None, 0
@@ -406,34 +385,47 @@ class Pipeline:
         pl, pp = _i64(place)
         if pl.shape != (len(lens),):
             raise Sbv2Error(f"place must hold one offset per utterance ({len(lens)})")
-        return [int(joined_len)], (pl, pp), int(joined_len)
+        return [int(joined_len)], pp, int(joined_len)
+
+    def _fetch(self, symbol, sizes, dtype, b, fmt, gain, place, joined_len, nstats):
+        """One formatted fetch through the C entry point `symbol`: sizes(fmt, n) bounds a signal of n native samples in `dtype` elements;
+        gain: the option arguments between fmt and place.  -> (buffer, per-signal counts, stats [n, nstats] or None)."""
+        native, pp, jl = self._layout(b, place, joined_len)
+        dst = np.empty(max(sum(sizes(fmt, n) for n in native), 1), dtype)
+        got = np.zeros(len(native), np.int64)
+        stats = np.zeros((len(native), nstats), np.float64) if nstats else None
+        tail = (_f64p(stats),) if nstats else ()
+        check(getattr(_lib.lib(), symbol)(self.h, b.ticket, C.byref(fmt.c), *gain, pp, jl, dst.ctypes.data_as(C.c_void_p), dst.nbytes,
+                                          got.ctypes.data_as(i64p), *tail))
+        return dst, got, stats
+
+    def _fetch_pcm(self, symbol, b, fmt, gain, place, joined_len, nstats=0):
+        out, got, stats = self._fetch(symbol, pcm_format_length, fmt.dtype, b, fmt, gain, place, joined_len, nstats)
+        signals = np.split(out[:int(got.sum())], np.cumsum(got)[:-1])
+        return (signals, stats) if nstats else signals
+
+    def _fetch_flac(self, symbol, b, fmt, gain, place, joined_len, nstats=0):
+        if fmt.encoding != "s16":
+            raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
+        dst, got, stats = self._fetch(symbol, flac_bound, np.uint8, b, fmt, gain, place, joined_len, nstats)
+        return (_split_bytes(dst, got), stats) if nstats else _split_bytes(dst, got)
+
+    def fetch_format(self, b, fmt: PcmFormat, place=None, joined_len=None):
+        """PCM of the run `b` in the output format `fmt` (resampled / normalised / quantised on the device; int16 or float32 arrays).
+        place None: one array per utterance.  place [n] native-sample offsets + joined_len: ONE array, the utterances laid on a silent
+        timeline of joined_len native samples."""
+        return self._fetch_pcm("sbv2_pipeline_fetch_pcm_format", b, fmt, (), place, joined_len)
 
     def fetch_loudness(self, b, fmt: PcmFormat, loudness=None, place=None, joined_len=None):
         """(signals, stats): the signals of fetch_format(b, fmt, place, joined_len), each measured (BS.1770-4 integrated loudness, 4x true
         peak) and scaled to `loudness` (a Loudness; None: measure only, the signals equal fetch_format's) on the device.  fmt must not
         normalise.  stats [n, 3]: L (LUFS) and TP (dBTP) before the gain, the applied gain G (dB)."""
-        native, pl, jl = self._layout(b, place, joined_len)
-        outs = [pcm_format_length(fmt, n) for n in native]
-        out = np.empty(max(sum(outs), 1), fmt.dtype)
-        got = np.zeros(len(outs), np.int64)
-        stats = np.zeros((len(outs), 3), np.float64)
-        check(_lib.lib().sbv2_pipeline_fetch_pcm_loudness(self.h, b.ticket, C.byref(fmt.c), _loudness_arg(loudness), None if pl is None else pl[1], jl,
-                                                          out.ctypes.data_as(C.c_void_p), out.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
-        return np.split(out[:int(got.sum())], np.cumsum(got)[:-1]), stats
+        return self._fetch_pcm("sbv2_pipeline_fetch_pcm_loudness", b, fmt, (_loudness_arg(loudness),), place, joined_len, 3)
 
     def fetch_flac_loudness(self, b, fmt: PcmFormat, loudness=None, place=None, joined_len=None):
         """(streams, stats): the signals of fetch_loudness(b, fmt, loudness, place, joined_len), each as one FLAC stream encoded on the
         device; fmt must be s16."""
-        if fmt.encoding != "s16":
-            raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
-        native, pl, jl = self._layout(b, place, joined_len)
-        cap = sum(flac_bound(fmt, n) for n in native)
-        dst = np.empty(max(cap, 1), np.uint8)
-        got = np.zeros(len(native), np.int64)
-        stats = np.zeros((len(native), 3), np.float64)
-        check(_lib.lib().sbv2_pipeline_fetch_flac_loudness(self.h, b.ticket, C.byref(fmt.c), _loudness_arg(loudness), None if pl is None else pl[1], jl,
-                                                           dst.ctypes.data_as(C.c_void_p), dst.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
-        return _split_bytes(dst, got), stats
+        return self._fetch_flac("sbv2_pipeline_fetch_flac_loudness", b, fmt, (_loudness_arg(loudness),), place, joined_len, 3)
 
     def fetch_limited(self, b, fmt: PcmFormat, limiter: Limiter, place=None, joined_len=None):
         """(signals, stats): the signals of fetch_format(b, fmt, place, joined_len), each brought to limiter.target_lufs through the
@@ -441,50 +433,18 @@ class Pipeline:
         (dB), L_out and TP_out of the delivered signal, the deepest gain reduction (dB, <= 0; 0 when the plain scale was enough)."""
         if limiter is None:
             raise Sbv2Error("fetch_limited needs a Limiter")
-        native, pl, jl = self._layout(b, place, joined_len)
-        outs = [pcm_format_length(fmt, n) for n in native]
-        out = np.empty(max(sum(outs), 1), fmt.dtype)
-        got = np.zeros(len(outs), np.int64)
-        stats = np.zeros((len(outs), 6), np.float64)
-        check(_lib.lib().sbv2_pipeline_fetch_pcm_limited(self.h, b.ticket, C.byref(fmt.c), C.byref(limiter.c), None if pl is None else pl[1], jl,
-                                                         out.ctypes.data_as(C.c_void_p), out.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
-        return np.split(out[:int(got.sum())], np.cumsum(got)[:-1]), stats
+        return self._fetch_pcm("sbv2_pipeline_fetch_pcm_limited", b, fmt, (C.byref(limiter.c),), place, joined_len, 6)
 
     def fetch_flac_limited(self, b, fmt: PcmFormat, limiter: Limiter, place=None, joined_len=None):
         """(streams, stats): the signals of fetch_limited(b, fmt, limiter, place, joined_len), each as one FLAC stream encoded on the
         device; fmt must be s16."""
         if limiter is None:
             raise Sbv2Error("fetch_flac_limited needs a Limiter")
-        if fmt.encoding != "s16":
-            raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
-        native, pl, jl = self._layout(b, place, joined_len)
-        cap = sum(flac_bound(fmt, n) for n in native)
-        dst = np.empty(max(cap, 1), np.uint8)
-        got = np.zeros(len(native), np.int64)
-        stats = np.zeros((len(native), 6), np.float64)
-        check(_lib.lib().sbv2_pipeline_fetch_flac_limited(self.h, b.ticket, C.byref(fmt.c), C.byref(limiter.c), None if pl is None else pl[1], jl,
-                                                          dst.ctypes.data_as(C.c_void_p), dst.nbytes, got.ctypes.data_as(i64p), _f64p(stats)))
-        return _split_bytes(dst, got), stats
+        return self._fetch_flac("sbv2_pipeline_fetch_flac_limited", b, fmt, (C.byref(limiter.c),), place, joined_len, 6)
 
     def fetch_flac(self, b, fmt: PcmFormat, place=None, joined_len=None):
         """The signals of fetch_format(b, fmt, place, joined_len), each as one FLAC stream (bytes) encoded on the device; fmt must be s16."""
-        if fmt.encoding != "s16":
-            raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
-        lens = [int(v) for v in b.lens]
-        if place is None:
-            cap, pp, jl, nout = sum(flac_bound(fmt, n) for n in lens), None, 0, len(lens)
-        else:
-            if joined_len is None:
-                raise Sbv2Error("a placement needs joined_len")
-            pl, pp = _i64(place)
-            if pl.shape != (len(lens),):
-                raise Sbv2Error(f"place must hold one offset per utterance ({len(lens)})")
-            cap, jl, nout = flac_bound(fmt, joined_len), int(joined_len), 1
-        dst = np.empty(max(cap, 1), np.uint8)
-        got = np.zeros(nout, np.int64)
-        check(_lib.lib().sbv2_pipeline_fetch_flac(self.h, b.ticket, C.byref(fmt.c), pp, jl, dst.ctypes.data_as(C.c_void_p), dst.nbytes,
-                                                  got.ctypes.data_as(i64p)))
-        return _split_bytes(dst, got)
+        return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
     def close(self):
         if self.h:

@@ -144,23 +144,20 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     b = pipe.prepare(utts, sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
                      noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     pipe.run(b)
-    if ln is not None:   # ONE joined fetch, measured and scaled as a whole on the device (the gates leave the silent gaps out)
+    if ln is not None or not fmt.is_default:
+        # ONE joined fetch: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target it is
+        # measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(b.lens, [i for i, _ in live], len(sentences), options.split_sentences)
-        if flac:
-            streams, stats = (pipe.fetch_flac_limited if limited else pipe.fetch_flac_loudness)(b, fmt, ln, place, joined)
+        if ln is None:
+            out = (pipe.fetch_flac if flac else pipe.fetch_format)(b, fmt, place, joined)
         else:
-            out, stats = (pipe.fetch_limited if limited else pipe.fetch_loudness)(b, fmt, ln, place, joined)
-        if loudness_stats is not None:
-            loudness_stats.append([float(v) for v in stats[0]])
+            fetch = (pipe.fetch_flac_limited if flac else pipe.fetch_limited) if limited else (pipe.fetch_flac_loudness if flac else pipe.fetch_loudness)
+            out, stats = fetch(b, fmt, ln, place, joined)
+            if loudness_stats is not None:
+                loudness_stats.append([float(v) for v in stats[0]])
         if flac:
-            return streams[0]
+            return out[0]
         return pcm16_wav(out[0], fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out[0], fmt.sample_rate)
-    if not fmt.is_default:   # ONE joined fetch: the WAV signal below, resampled / normalised / quantised as a whole on the device
-        place, joined = joined_placement(b.lens, [i for i, _ in live], len(sentences), options.split_sentences)
-        if flac:
-            return pipe.fetch_flac(b, fmt, place, joined)[0]
-        out = pipe.fetch_format(b, fmt, place, joined)[0]
-        return pcm16_wav(out, fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out, fmt.sample_rate)
     pcm = pipe.fetch(b)
     parts = []
     for (i, _), wav in zip(live, pcm):
