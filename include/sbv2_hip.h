@@ -328,6 +328,26 @@ int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch*
                              const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, sbv2_stream** out, int64_t* total_samples);
 /* next chunk -> dst (host; capacity_bytes); *n = samples written, 0 at the end */
 int sbv2_stream_next_format(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n);
+/* ---- new: the stream as FLAC.  Inputs as sbv2_stream_begin_format; fmt->encoding must be 1 (s16), fmt->normalize 0; *total_samples at
+ * fmt->sample_rate.  The s16 samples that sbv2_stream_next_format would deliver are encoded on the device instead, replay by replay, as ONE
+ * FLAC stream in the convention of sbv2_pipeline_fetch_flac (mono, 16 bits, fixed 4096-sample blocks, frames numbered from 0); the samples
+ * that do not fill a block yet are carried on the device to the next chunk.  Call c of sbv2_stream_next_flac consumes the samples of chunk c
+ * (*n_samples; 0 once the utterance is complete) and writes into HOST memory dst the bytes of every frame those samples complete (*n_bytes,
+ * which may be 0 while *n_samples > 0); the first call starts with the 42-byte stream header, whose STREAMINFO names total_samples and
+ * min / max frame size 0 (unknown, RFC 9639 8.2), the last one that consumes samples ends with the short final frame.  The concatenated
+ * output equals sbv2_debug_flac_encode of the stream's samples in every byte except stream bytes 12..17 (min / max frame size).  A
+ * capacity_bytes that does not hold the call's bytes is refused with nothing written and nothing consumed: repeat the call with more room.
+ * sbv2_stream_next and sbv2_stream_next_format are refused on such a stream, sbv2_stream_next_flac on any other. */
+/* Host only: a capacity that always suffices for one call, 42 + 16 ceil((n + 4095) / 4096) + 2 (n + 4095) with
+ * n = sbv2_pcm_format_length(fmt, chunk_native_samples), chunk_native_samples = chunk_frames * sbv2_vits_hop; -1 for a bad fmt. */
+int64_t sbv2_flac_stream_bound(const sbv2_pcm_format* fmt, int64_t chunk_native_samples);
+int sbv2_stream_begin_flac(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
+                           const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, sbv2_stream** out, int64_t* total_samples);
+int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, int64_t* n_bytes, int64_t* n_samples);
+/* Test hook: the fed encoder on its own.  x[n] (host s16) is cut at the ascending sample positions cuts[ncuts] into ncuts + 1 pushes (empty
+ * ones allowed, the last one ends the stream); dst receives the pushes' bytes back to back, out_bytes_per_push[ncuts + 1] their sizes. */
+int sbv2_debug_flac_stream_encode(int device, const int16_t* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, uint8_t* dst,
+                                  int64_t capacity, int64_t* out_bytes_per_push);
 int sbv2_stream_uses_graph(const sbv2_stream* s);
 int64_t sbv2_stream_workspace_bytes(const sbv2_stream* s);
 void sbv2_stream_end(sbv2_stream* s);

@@ -112,6 +112,11 @@ SYMBOLS = {
     "sbv2_stream_begin_format": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), i64p, i64p, i64p, C.c_int64, C.POINTER(Sbv2PcmFormat),
                                            C.POINTER(C.c_void_p), i64p]),
     "sbv2_stream_next_format": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, i64p]),
+    "sbv2_flac_stream_bound": (C.c_int64, [C.POINTER(Sbv2PcmFormat), C.c_int64]),
+    "sbv2_stream_begin_flac": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), i64p, i64p, i64p, C.c_int64, C.POINTER(Sbv2PcmFormat),
+                                         C.POINTER(C.c_void_p), i64p]),
+    "sbv2_stream_next_flac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, i64p, i64p]),
+    "sbv2_debug_flac_stream_encode": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, i64p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, i64p]),
     "sbv2_stream_uses_graph": (C.c_int, [C.c_void_p]),
     "sbv2_stream_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "sbv2_stream_end": (None, [C.c_void_p]),

@@ -32,6 +32,9 @@ enum { kConstant = 0, kVerbatim = 1, kFixed = 2, kLpc = 3 };
 
 struct FlacSig {
     int64_t x_off, n, f0;   // samples at x[x_off, x_off + n); frames [f0, f0 + ceil(n / 4096)) of the launch
+    int64_t fno0;           // frame number of the signal's first frame (0 for a whole stream; a push of a fed stream continues its count)
+    int64_t hoff;           // stream-header bytes in the output before the signal's first frame, its own included
+    int64_t hdr;            // 1: the signal starts a stream (42-byte header, written by k_flac_pack), 0: frames only
 };
 
 struct FlacDesc {
@@ -85,9 +88,10 @@ __global__ __launch_bounds__(kT) void k_flac_analyse(const short* __restrict__ x
 
     const int f = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int s = find_sig(sg, nsig, f);
-    const int fno = f - (int)sg[s].f0;
-    const int64_t x0 = sg[s].x_off + (int64_t)fno * kFlacBlock;
-    const int n = (int)min((int64_t)kFlacBlock, sg[s].n - (int64_t)fno * kFlacBlock);
+    const int fi = f - (int)sg[s].f0;   // frame of the signal; its number in the stream:
+    const int fno = (int)sg[s].fno0 + fi;
+    const int64_t x0 = sg[s].x_off + (int64_t)fi * kFlacBlock;
+    const int n = (int)min((int64_t)kFlacBlock, sg[s].n - (int64_t)fi * kFlacBlock);
     const int hdr = header_bytes(n, fno);
     FlacDesc& d = dd[f];
 
@@ -357,10 +361,11 @@ __global__ __launch_bounds__(kScanT) void k_flac_scan(const FlacDesc* __restrict
     __syncthreads();
     for (int s = t; s < nsig; s += kScanT) {
         const int64_t f0 = sg[s].f0, f1 = f0 + (sg[s].n + kFlacBlock - 1) / kFlacBlock;
-        sig_off[s] = (int64_t)kFlacStreamHeader * s + pre[f0];
-        sig_bytes[s] = kFlacStreamHeader + pre[f1] - pre[f0];
+        const int64_t own = sg[s].hdr ? kFlacStreamHeader : 0;
+        sig_off[s] = sg[s].hoff - own + pre[f0];
+        sig_bytes[s] = own + pre[f1] - pre[f0];
     }
-    if (t == 0) sig_bytes[nsig] = (int64_t)kFlacStreamHeader * nsig + carry_s;
+    if (t == 0) sig_bytes[nsig] = sg[nsig - 1].hoff + carry_s;
 }
 
 // ---- pack ----
@@ -401,7 +406,7 @@ __device__ __forceinline__ unsigned x8pow(unsigned nbytes) {
     return r;
 }
 
-__device__ void write_streaminfo(uint8_t* o, int64_t n, unsigned fmin, unsigned fmax, int rate) {
+__host__ __device__ void write_streaminfo(uint8_t* o, int64_t n, unsigned fmin, unsigned fmax, int rate) {
     const uint8_t head[12] = {'f', 'L', 'a', 'C', 0x80, 0, 0, 34, kFlacBlock >> 8, kFlacBlock & 0xFF, kFlacBlock >> 8, kFlacBlock & 0xFF};
     for (int i = 0; i < 12; ++i) o[i] = head[i];
     for (int i = 0; i < 3; ++i) {
@@ -420,7 +425,7 @@ __global__ __launch_bounds__(kT) void k_flac_pack(const short* __restrict__ x, c
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if ((int)blockIdx.x >= nframes) {   // STREAMINFO of signals (blockIdx - nframes) * 256 + t
         const int s = ((int)blockIdx.x - nframes) * kT + t;
-        if (s >= nsig) return;
+        if (s >= nsig || !sg[s].hdr) return;
         const bool any = sg[s].n > 0;
         if (sig_off[s] + kFlacStreamHeader > cap) {
             atomicOr((unsigned long long*)err, 2ull);
@@ -490,7 +495,7 @@ __global__ __launch_bounds__(kT) void k_flac_pack(const short* __restrict__ x, c
     }
     const long long body = method == kConstant ? 8 + 16 : method == kVerbatim ? 8 + 16LL * n : preamble_bits(method, order) + (long long)all;
     const int F = hdr + (int)((body + 7) / 8);   // frame bytes before the CRC-16
-    const int64_t off = (int64_t)kFlacStreamHeader * (d.sig + 1) + pre[f];
+    const int64_t off = sg[d.sig].hoff + pre[f];
     if (F + 2 != d.bytes || F + 2 > 4 * kBitWords || off + F + 2 > cap) {   // the analysis and the packing disagree, or no room: refuse
         if (t == 0) atomicOr((unsigned long long*)err, 1ull);
         return;
@@ -609,7 +614,7 @@ int64_t FlacEncoder::encode(const int16_t* x_dev, const std::vector<int64_t>& of
     int64_t nframes = 0, cap = 0;
     for (int i = 0; i < nsig; ++i) {
         SBV2_REQUIRE(lens[i] >= 0 && lens[i] < (1ll << 36), "FLAC: signal length out of range");
-        sig[i] = FlacSig{offs[i], lens[i], nframes};
+        sig[i] = FlacSig{offs[i], lens[i], nframes, 0, (int64_t)kFlacStreamHeader * (i + 1), 1};
         nframes += (lens[i] + kFlacBlock - 1) / kFlacBlock;
         cap += flac_bound(lens[i]);
     }
@@ -648,6 +653,107 @@ int64_t FlacEncoder::encode(const int16_t* x_dev, const std::vector<int64_t>& of
     bytes->assign(sizes_host, sizes_host + nsig);
     SBV2_REQUIRE(sizes_host[nsig] <= cap, "FLAC encoder: stream larger than its bound");
     return sizes_host[nsig];
+}
+
+// ---- the encoder fed piece by piece ----
+//
+// One contiguous s16 buffer on the device: the carried tail (< 4096 samples) at its start, the push's samples written right behind it by the
+// caller (dst()).  A push encodes the complete blocks of [tail | new samples] as ONE signal without a stream header whose first frame
+// continues the count (FlacSig.fno0), with the three launches of FlacEncoder::encode, and moves the remainder to the front of the buffer (one
+// device-to-device copy of < 8 KB; source and destination cannot overlap: the source starts at a block edge >= 4096).  The scan's prefix of
+// the frame sizes and the error word lie in front of the packed bytes in one device region that ONE copy takes to the caller's pinned
+// region: the frames' bound is copied, the host reads the sizes next to the bytes once the stream has passed the push.
+
+namespace {
+constexpr size_t kPushSig = 64;   // the push's FlacSig at the head of the pinned region (uploaded from there: the region lives until the push is delivered)
+int64_t push_frames_max(int64_t max_push) { return (max_push + 2 * (kFlacBlock - 1)) / kFlacBlock; }   // ceil((4095 + n) / 4096), the short last frame included
+size_t push_meta_bytes(int64_t max_push) { return round_up64(8 * (push_frames_max(max_push) + 2), 64); }   // error word + prefix[frames + 1], at most
+}  // namespace
+
+int64_t flac_stream_bound(int64_t n) { return kFlacStreamHeader + push_frames_max(n) * (kFlacMaxFrameHeader + 1 + 2) + 2 * (n + kFlacBlock - 1); }
+
+size_t FlacStreamEncoder::host_bytes(int64_t max_push) {
+    return kPushSig + push_meta_bytes(max_push) + (size_t)(flac_stream_bound(max_push) - kFlacStreamHeader);
+}
+
+void FlacStreamEncoder::begin(int rate, int64_t total_samples, int64_t max_push, hipStream_t s) {
+    rate_code_ = flac_rate_code(rate);
+    SBV2_REQUIRE(total_samples >= 0 && total_samples < (1ll << 36) && max_push >= 0, "FLAC: stream length out of range");
+    static_assert(sizeof(FlacSig) <= kPushSig, "the push's signal entry outgrew its place");
+    rate_ = rate;
+    total_ = total_samples;
+    max_push_ = max_push;
+    fed_ = frames_ = tail_ = 0;
+    done_ = false;
+    const int64_t fmax = push_frames_max(max_push);
+    buf_.reserve(sizeof(int16_t) * (size_t)(kFlacBlock + max_push), s);
+    // [signal][sizes: 1 + total][offset][min frame][max frame] (what k_flac_scan writes per signal; a fed stream reads none of it back)
+    tab_.reserve(kPushSig + 64 * 4, s);
+    desc_.reserve(sizeof(FlacDesc) * (size_t)fmax, s);
+    out_.reserve(push_meta_bytes(max_push) + (size_t)(flac_stream_bound(max_push) - kFlacStreamHeader), s);
+}
+
+int16_t* FlacStreamEncoder::dst() const { return buf_.as<int16_t>() + tail_; }
+
+void FlacStreamEncoder::header(uint8_t* out) const { write_streaminfo(out, total_, 0, 0, rate_); }   // frame sizes unknown ahead: 0 (RFC 9639 8.2)
+
+FlacStreamEncoder::Push FlacStreamEncoder::push(int64_t n, bool last, void* host, hipStream_t s) {
+    SBV2_REQUIRE(rate_code_ >= 0 && !done_, "FLAC stream: push without begin, or after the last push");
+    SBV2_REQUIRE(n >= 0 && n <= max_push_ && fed_ + n <= total_, "FLAC stream: push of " + std::to_string(n) + " samples outgrows what begin announced");
+    SBV2_REQUIRE(!last || fed_ + n == total_, "FLAC stream: the last push ends " + std::to_string(total_ - fed_ - n) + " samples short of the announced length");
+    const int64_t have = tail_ + n;
+    const int64_t enc = last ? have : have / kFlacBlock * kFlacBlock;   // samples this push encodes
+    const int nf = (int)((enc + kFlacBlock - 1) / kFlacBlock);
+    SBV2_REQUIRE(frames_ + nf < (1ll << 31), "FLAC: too many frames in one stream");
+    char* hb = static_cast<char*>(host);
+    const size_t meta = round_up64(8 * (nf + 2), 64);   // the push's own error word + prefix[nf + 1]: a region sized for n samples holds a push of n
+    Push r;
+    r.first_frame = frames_;
+    r.frames = nf;
+    r.err = reinterpret_cast<const int64_t*>(hb + kPushSig);
+    r.pre = r.err + 1;
+    r.bytes = reinterpret_cast<const uint8_t*>(hb + kPushSig + meta);
+    if (nf) {
+        const FlacSig sig{0, enc, 0, frames_, 0, 0};
+        std::memcpy(hb, &sig, sizeof sig);
+        char* tab = tab_.as<char>();
+        FlacSig* d_sig = reinterpret_cast<FlacSig*>(tab);
+        int64_t* d_sizes = reinterpret_cast<int64_t*>(tab + kPushSig);
+        int64_t* d_off = reinterpret_cast<int64_t*>(tab + kPushSig + 64);
+        unsigned* d_min = reinterpret_cast<unsigned*>(tab + kPushSig + 128);
+        unsigned* d_max = reinterpret_cast<unsigned*>(tab + kPushSig + 192);
+        int64_t* d_err = out_.as<int64_t>();
+        int64_t* d_pre = d_err + 1;
+        uint8_t* d_bytes = out_.as<uint8_t>() + meta;
+        const int64_t cap = (int64_t)nf * (kFlacMaxFrameHeader + 1 + 2) + 2 * enc;
+        const short* xs = reinterpret_cast<const short*>(buf_.get());
+        HIP_CHECK(hipMemcpyAsync(d_sig, hb, sizeof sig, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(d_err, 0, 8, s));
+        hipLaunchKernelGGL(k_flac_analyse, dim3((unsigned)nf), dim3(kT), 0, s, xs, d_sig, 1, desc_.as<FlacDesc>());
+        // (d_min / d_max are not initialised here, unlike in FlacEncoder::encode: the scan's atomicMin / atomicMax need valid words only.  Their
+        // results feed the STREAMINFO that k_flac_pack writes for a signal with a header; a push has none, and nothing reads them back.)
+        hipLaunchKernelGGL(k_flac_scan, dim3(1), dim3(kScanT), 0, s, desc_.as<FlacDesc>(), nf, d_sig, 1, d_pre, d_sizes, d_off, d_min, d_max);
+        hipLaunchKernelGGL(k_flac_pack, dim3((unsigned)nf), dim3(kT), 0, s, xs, d_sig, 1, rate_, rate_code_, desc_.as<FlacDesc>(), d_pre, nf, d_off,
+                           d_min, d_max, d_bytes, cap, d_err);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(hb + kPushSig, d_err, meta + (size_t)cap, hipMemcpyDeviceToHost, s));
+        const int64_t rest = have - enc;
+        if (rest) HIP_CHECK(hipMemcpyAsync(buf_.get(), buf_.as<int16_t>() + enc, sizeof(int16_t) * (size_t)rest, hipMemcpyDeviceToDevice, s));
+        tail_ = rest;
+    } else {
+        tail_ = have;
+    }
+    fed_ += n;
+    frames_ += nf;
+    done_ = last;
+    return r;
+}
+
+int64_t FlacStreamEncoder::Push::size(int f0, int f1) const {
+    if (f0 >= f1) return 0;
+    SBV2_REQUIRE(f0 >= 0 && f1 <= frames, "FLAC stream: frame range outside its push");
+    SBV2_REQUIRE(*err == 0, "FLAC encoder: internal error " + std::to_string(*err) + " (frame sizes disagree)");
+    return pre[f1] - pre[f0];
 }
 
 }  // namespace sbv2

@@ -2,6 +2,7 @@
 // batched forward passes expressed as sequences of kernel launches on one HIP stream.
 #pragma once
 #include "common.h"
+#include "flac_encode.h"
 #include "ops.h"
 #include "pcm_format.h"
 
@@ -310,10 +311,14 @@ class VitsModel {
     double stream_receptive_field() const;   // frames per side, before the margin and rounding of stream_halo
     // fmt (optional): the chunks leave the device in that output format (pcm_format.h; normalize must be 0): chunk [a, b) of native samples
     // emits output samples [ceil(a L / M), ceil(b L / M)), computed from the window's exact samples beyond the centre
-    int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr);
+    // flac (fmt must be s16): the chunks' samples are not delivered but pushed into a FlacStreamEncoder (flac_encode.h) behind each replay
+    int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false);
     int64_t stream_chunk(int64_t f0, float* dst_host, int64_t capacity);
     // formatted stream: output samples of the chunk at f0 -> dst_host (capacity_bytes); returns the samples written
     int64_t stream_chunk_format(int64_t f0, void* dst_host, int64_t capacity_bytes);
+    // FLAC stream: the bytes of every frame the chunk at f0 completes (the stream header before the first) -> dst_host, *n_bytes of them
+    // (possibly 0); returns the s16 samples the chunk consumed.  Chunks in order only.
+    int64_t stream_chunk_flac(int64_t f0, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes);
     bool stream_graph_captured() const { return chunk_ && chunk_->exec != nullptr; }
     size_t stream_workspace_bytes() const { return (chunk_ ? chunk_->ar.capacity() : 0) + (burst_ ? burst_->ar.capacity() : 0); }
     // results of the last forward
@@ -424,6 +429,8 @@ class VitsModel {
         int64_t slot_f0[2] = {-1, -1}, slot_n[2] = {0, 0};
         size_t host_bytes = 0;                      // capacity of each pinned slot
         std::vector<int64_t> fmt_off[2], fmt_n[2];  // formatted stream: each window's output samples in its slot (offset, count)
+        FlacStreamEncoder::Push flac_push[2];       // FLAC stream: the slot's push (its pinned region is host[slot]) and, per window, the
+        std::vector<int> flac_fr[2];                // frames of the push it completes: [flac_fr[w], flac_fr[w + 1])
         ~ChunkPlan() {
             if (exec) (void)hipGraphExecDestroy(exec);
             if (graph) (void)hipGraphDestroy(graph);
@@ -435,11 +442,14 @@ class VitsModel {
     };
     void ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, int nwin);
     void stream_enqueue(ChunkPlan& c, int64_t f0, int slot);
-    int64_t stream_take(int64_t f0, void* dst_host, int64_t capacity_bytes, bool formatted);
-    size_t stream_fmt_bytes(const ChunkPlan& c) const;   // formatted output of one replay of c, upper bound
+    int64_t stream_take(int64_t f0, void* dst_host, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes);   // flac_bytes: FLAC delivery
+    int64_t stream_fmt_samples(const ChunkPlan& c) const;   // formatted output of one replay of c, upper bound
+    size_t stream_fmt_bytes(const ChunkPlan& c) const;
     bool sfmt_on_ = false;                       // the running stream is formatted (stream_begin with fmt)
     PcmFmtSpec sfmt_;
     std::shared_ptr<PcmFormatter> sfmtr_;          // its launches: slots 0 / 1 = chunk_'s, 2 / 3 = burst_'s
+    bool sflac_on_ = false;                      // ... and encoded as FLAC replay by replay (stream_begin with flac; implies sfmt_on_)
+    std::shared_ptr<FlacStreamEncoder> sflac_;
     bool stream_bursts_ = false;                 // the running stream uses burst_ behind its first chunk
     std::shared_ptr<ChunkPlan> chunk_, burst_;   // one window (an utterance's first chunk) / kStreamBurst windows per replay (every later one)
     Plane z_{};              // flow output of the last forward (frame-rate plane, packed layout fl_)

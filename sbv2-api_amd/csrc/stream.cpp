@@ -11,8 +11,18 @@ struct sbv2_stream {
     sbv2_bert* bert = nullptr;
     sbv2_vits* vits = nullptr;
     int64_t frames = 0, next = 0, chunk = 0;
-    bool formatted = false;
+    bool formatted = false, flac = false;
 };
+
+namespace {
+// the checked format of a FLAC stream: s16, not normalised (throws with the reason otherwise)
+PcmFmtSpec flac_stream_spec(const sbv2_pcm_format* fmt) {
+    const PcmFmtSpec spec = pcm_format_spec(fmt);
+    SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
+    SBV2_REQUIRE(!spec.normalize, "a FLAC stream cannot normalise (normalize must be 0): the peak of the utterance is not known ahead");
+    return spec;
+}
+}  // namespace
 
 extern "C" {
 
@@ -43,6 +53,7 @@ int sbv2_stream_begin(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch,
 int sbv2_stream_next(sbv2_stream* s, float* dst, int64_t capacity, int64_t* n) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n, "bad arguments");
+    SBV2_REQUIRE(!s->flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
     SBV2_REQUIRE(!s->formatted, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
     *n = 0;
     if (s->next < s->frames) {
@@ -78,10 +89,60 @@ int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch*
 int sbv2_stream_next_format(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n, "bad arguments");
+    SBV2_REQUIRE(!s->flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
     SBV2_REQUIRE(s->formatted, "this stream has no output format: take its chunks with sbv2_stream_next");
     *n = 0;
     if (s->next < s->frames) {
         *n = s->vits->m->stream_chunk_format(s->next, dst, capacity_bytes);
+        s->next += s->chunk;
+    }
+    API_END
+}
+
+// Host only: bytes that always suffice for one sbv2_stream_next_flac call of a stream with chunks of chunk_native_samples (-1: bad fmt)
+int64_t sbv2_flac_stream_bound(const sbv2_pcm_format* fmt, int64_t chunk_native_samples) {
+    try {
+        const PcmFmtSpec spec = flac_stream_spec(fmt);
+        SBV2_REQUIRE(chunk_native_samples >= 0, "negative sample count");
+        return flac_stream_bound(pcm_format_out_len(spec, chunk_native_samples));
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// Same as sbv2_stream_begin_format (fmt: s16, normalize 0) with the chunks' samples encoded as ONE FLAC stream on the device, replay by
+// replay (vits.cpp stream_enqueue, flac_encode.hip FlacStreamEncoder).
+int sbv2_stream_begin_flac(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
+                           const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, sbv2_stream** out, int64_t* total_samples) {
+    API_BEGIN
+    SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
+    SBV2_REQUIRE(batch->n == 1, "sbv2_stream_begin_flac takes one utterance");
+    SBV2_REQUIRE(bert->m->device() == vits->m->device(), "bert and vits handles live on different devices");
+    const PcmFmtSpec spec = flac_stream_spec(fmt);
+    VitsBatch v = to_batch(batch);
+    v.skip_decoder = true;
+    pipeline_run_one(*bert->m, *vits->m, v, token_ids, s_lens, word2ph);
+    std::unique_ptr<sbv2_stream> s(new sbv2_stream);
+    s->bert = bert;
+    s->vits = vits;
+    s->chunk = chunk_frames;
+    s->formatted = s->flac = true;
+    s->frames = vits->m->stream_begin((int)chunk_frames, &spec, true);
+    if (total_samples) *total_samples = pcm_format_out_len(spec, s->frames * vits->m->cfg().hop());
+    *out = s.release();
+    API_END
+}
+
+// The bytes of every FLAC frame that the next chunk's samples complete -> dst (host; the stream header in front on the first call).
+// *n_samples = s16 samples the chunk consumed (0 once the utterance is complete), *n_bytes may be 0 while *n_samples > 0.
+int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, int64_t* n_bytes, int64_t* n_samples) {
+    API_BEGIN
+    SBV2_REQUIRE(s && dst && n_bytes && n_samples, "bad arguments");
+    SBV2_REQUIRE(s->flac, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
+    *n_bytes = *n_samples = 0;
+    if (s->next < s->frames) {
+        *n_samples = s->vits->m->stream_chunk_flac(s->next, dst, capacity_bytes, n_bytes);
         s->next += s->chunk;
     }
     API_END

@@ -200,6 +200,48 @@ int sbv2_debug_flac_encode(int device, const int16_t* x, const int64_t* lens, in
     API_END
 }
 
+int sbv2_debug_flac_stream_encode(int device, const int16_t* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, uint8_t* dst,
+                                  int64_t capacity, int64_t* out_bytes_per_push) {
+    API_BEGIN
+    SBV2_REQUIRE(n >= 0 && ncuts >= 0 && (ncuts == 0 || cuts) && dst && out_bytes_per_push && (n == 0 || x), "bad arguments");
+    flac_rate_code(sample_rate);
+    // push i = samples [edge[i], edge[i + 1])
+    std::vector<int64_t> edge(1, 0);
+    for (int i = 0; i < ncuts; ++i) {
+        SBV2_REQUIRE(cuts[i] >= edge.back() && cuts[i] <= n, "cuts must ascend within [0, n]");
+        edge.push_back(cuts[i]);
+    }
+    edge.push_back(n);
+    const int npush = ncuts + 1;
+    int64_t longest = 0;
+    for (int i = 0; i < npush; ++i) longest = std::max(longest, edge[i + 1] - edge[i]);
+    AudioScratch r(device, x, sizeof(int16_t) * (size_t)n);
+    // every push is enqueued before the host waits once: one pinned region per push
+    const size_t region = round_up64((int64_t)FlacStreamEncoder::host_bytes(longest), 64);
+    PinnedBuffer host;
+    char* hb = static_cast<char*>(host.reserve(region * npush, r.s));
+    FlacStreamEncoder enc;
+    enc.begin(sample_rate, n, longest, r.s);
+    std::vector<FlacStreamEncoder::Push> pushes;
+    for (int i = 0; i < npush; ++i) {
+        const int64_t len = edge[i + 1] - edge[i];
+        if (len) HIP_CHECK(hipMemcpyAsync(enc.dst(), r.x.as<int16_t>() + edge[i], sizeof(int16_t) * (size_t)len, hipMemcpyDeviceToDevice, r.s));
+        pushes.push_back(enc.push(len, i + 1 == npush, hb + region * i, r.s));
+    }
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    int64_t at = 0;
+    for (int i = 0; i < npush; ++i) {
+        const FlacStreamEncoder::Push& p = pushes[i];
+        const int64_t head = i == 0 ? kFlacStreamHeader : 0, nb = p.size(0, p.frames);
+        SBV2_REQUIRE(capacity >= at + head + nb, "FLAC buffer too small: " + std::to_string(capacity) + " < " + std::to_string(at + head + nb) + " bytes");
+        if (head) enc.header(dst + at);
+        if (nb) std::memcpy(dst + at + head, p.bytes + p.pre[0], (size_t)nb);
+        out_bytes_per_push[i] = head + nb;
+        at += head + nb;
+    }
+    API_END
+}
+
 int sbv2_debug_loudness(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_loudness* ln, double* stats) {
     API_BEGIN
     SBV2_REQUIRE(nsig >= 1 && lens && stats, "bad arguments");

@@ -921,11 +921,12 @@ void VitsModel::ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, 
     c.slot_f0[0] = c.slot_f0[1] = -1;
 }
 
-int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt) {
+int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(fl_.n == 1 && z_.p, "stream_begin needs a preceding forward of ONE utterance with skip_decoder");
     SBV2_REQUIRE(chunk_frames >= 16 && chunk_frames <= (1 << 20), "chunk_frames must be in [16, 2^20]");
-    sfmt_on_ = false;
+    sfmt_on_ = sflac_on_ = false;
+    SBV2_REQUIRE(!flac || (fmt && fmt->encoding == 1), "a FLAC stream needs encoding = 1 (s16): f32 samples have no FLAC form");
     if (fmt) {
         SBV2_REQUIRE(!fmt->normalize, "a formatted stream cannot normalise: the peak of the utterance is not known ahead");
         // the filter of an output sample at a chunk edge reaches ceil(half / L) native samples past the window centre; they must lie in the
@@ -957,8 +958,8 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt) {
         size_t dev = 0;
         for (ChunkPlan* c : {chunk_.get(), want_burst ? burst_.get() : nullptr}) {
             if (!c) continue;
-            const size_t need = stream_fmt_bytes(*c);
-            dev = std::max(dev, need);
+            const size_t need = flac ? FlacStreamEncoder::host_bytes(stream_fmt_samples(*c)) : stream_fmt_bytes(*c);
+            dev = std::max(dev, stream_fmt_bytes(*c));
             if (need > c->host_bytes) {
                 HIP_CHECK(hipStreamSynchronize(stream_));
                 for (int i = 0; i < 2; ++i) {
@@ -970,7 +971,13 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt) {
                 c->host_bytes = need;
             }
         }
-        sfmtr_->out_buffer(dev, stream_);
+        if (flac) {   // the replays' s16 samples go straight behind the encoder's carried tail instead (stream_enqueue)
+            if (!sflac_) sflac_ = std::make_shared<FlacStreamEncoder>();
+            sflac_->begin(sfmt_.rate, pcm_format_out_len(sfmt_, Tf * cfg_.hop()), (int64_t)(dev / sfmt_.bytes()), stream_);
+            sflac_on_ = true;
+        } else {
+            sfmtr_->out_buffer(dev, stream_);
+        }
         sfmt_on_ = true;
     }
     stream_enqueue(*chunk_, 0, 0);                            // the first chunk starts right behind the flow ...
@@ -1019,9 +1026,23 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
             c.fmt_n[slot].push_back(j1 - j0);
             total += j1 - j0;
         }
-        void* dev = sfmtr_->out_buffer(stream_fmt_bytes(c), stream_);
-        sfmtr_->run(sfmt_, pieces, sig, total, dev, (&c == burst_.get() ? 2 : 0) + slot, stream_);
-        if (total) HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)total * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
+        if (sflac_on_) {
+            // ONE push per replay: the formatter writes behind the carried tail, the encoder packs every block that completes (with the
+            // utterance's last chunk also the short final frame).  Window w completes frames [flac_fr[w], flac_fr[w + 1]) of the push.
+            const int64_t t0 = sflac_->tail();
+            const bool last = f0 + (int64_t)c.nwin * c.chunk >= Tf;
+            sfmtr_->run(sfmt_, pieces, sig, total, sflac_->dst(), (&c == burst_.get() ? 2 : 0) + slot, stream_);
+            c.flac_push[slot] = sflac_->push(total, last, c.host[slot], stream_);
+            c.flac_fr[slot].assign(1, 0);
+            for (size_t w = 0; w < c.fmt_n[slot].size(); ++w) {
+                const int64_t upto = t0 + c.fmt_off[slot][w] + c.fmt_n[slot][w];
+                c.flac_fr[slot].push_back(w + 1 == c.fmt_n[slot].size() ? c.flac_push[slot].frames : (int)(upto / kFlacBlock));
+            }
+        } else {
+            void* dev = sfmtr_->out_buffer(stream_fmt_bytes(c), stream_);
+            sfmtr_->run(sfmt_, pieces, sig, total, dev, (&c == burst_.get() ? 2 : 0) + slot, stream_);
+            if (total) HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)total * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
+        }
         HIP_CHECK(hipEventRecord(c.ev[slot], stream_));
         c.slot_f0[slot] = f0;
         c.slot_n[slot] = total;
@@ -1040,21 +1061,28 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
     c.slot_n[slot] = total;
 }
 
-size_t VitsModel::stream_fmt_bytes(const ChunkPlan& c) const {
-    return (size_t)c.nwin * (size_t)(pcm_format_out_len(sfmt_, (int64_t)c.chunk * cfg_.hop()) + 1) * sfmt_.bytes();
+int64_t VitsModel::stream_fmt_samples(const ChunkPlan& c) const {
+    return (int64_t)c.nwin * (pcm_format_out_len(sfmt_, (int64_t)c.chunk * cfg_.hop()) + 1);
 }
+size_t VitsModel::stream_fmt_bytes(const ChunkPlan& c) const { return (size_t)stream_fmt_samples(c) * sfmt_.bytes(); }
 
 int64_t VitsModel::stream_chunk(int64_t f0, float* dst_host, int64_t capacity) {
     SBV2_REQUIRE(!sfmt_on_, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
-    return stream_take(f0, dst_host, capacity * (int64_t)sizeof(float), false);
+    return stream_take(f0, dst_host, capacity * (int64_t)sizeof(float), false, nullptr);
 }
 
 int64_t VitsModel::stream_chunk_format(int64_t f0, void* dst_host, int64_t capacity_bytes) {
     SBV2_REQUIRE(sfmt_on_, "this stream has no output format: take its chunks with sbv2_stream_next");
-    return stream_take(f0, dst_host, capacity_bytes, true);
+    SBV2_REQUIRE(!sflac_on_, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
+    return stream_take(f0, dst_host, capacity_bytes, true, nullptr);
 }
 
-int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bool formatted) {
+int64_t VitsModel::stream_chunk_flac(int64_t f0, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes) {
+    SBV2_REQUIRE(sflac_on_, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
+    return stream_take(f0, dst_host, capacity_bytes, true, n_bytes);
+}
+
+int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(chunk_ && z_.p && fl_.n == 1, "stream_chunk without stream_begin");
     ChunkPlan& c1 = *chunk_;
@@ -1073,6 +1101,20 @@ int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bo
         }
         SBV2_REQUIRE(w < (int64_t)c.fmt_n[slot].size(), "formatted chunk missing from its replay");
         const int64_t n = c.fmt_n[slot][w];
+        if (flac_bytes) {
+            // the frames this window completed, the stream header in front of the utterance's first ones.  Too small a buffer is refused before
+            // anything is written or marked as taken: the call can be repeated.
+            const FlacStreamEncoder::Push& p = c.flac_push[slot];
+            const int fa = c.flac_fr[slot][w], fb = c.flac_fr[slot][w + 1];
+            const int64_t head = f0 == 0 ? kFlacStreamHeader : 0, nb = p.size(fa, fb);
+            SBV2_REQUIRE(capacity_bytes >= head + nb, "FLAC buffer too small for the chunk: " + std::to_string(capacity_bytes) + " < " +
+                                                          std::to_string(head + nb) + " bytes (sbv2_flac_stream_bound always suffices)");
+            uint8_t* o = reinterpret_cast<uint8_t*>(dst_host);
+            if (head) sflac_->header(o);
+            if (nb) std::memcpy(o + head, p.bytes + p.pre[fa], (size_t)nb);
+            *flac_bytes = head + nb;
+            return n;
+        }
         SBV2_REQUIRE(capacity_bytes >= n * esz, "PCM buffer too small for the chunk: " + std::to_string(capacity_bytes) + " < " + std::to_string(n * esz) + " bytes");
         std::memcpy(dst_host, reinterpret_cast<const char*>(c.host[slot]) + (size_t)c.fmt_off[slot][w] * esz, (size_t)(n * esz));
         return n;
@@ -1082,6 +1124,7 @@ int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bo
     if (ci == 0 || !bursts) {
         // the single-window plan: the utterance's first chunk (and everything when bursts are off); the next chunk runs while this one is delivered
         const int slot = (int)(ci & 1);
+        SBV2_REQUIRE(!flac_bytes || c1.slot_f0[slot] == f0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
         if (c1.slot_f0[slot] != f0) stream_enqueue(c1, f0, slot);                                  // (random access: not the streaming order)
         if (!bursts && f0 + c1.chunk < Tf && c1.slot_f0[slot ^ 1] != f0 + c1.chunk) stream_enqueue(c1, f0 + c1.chunk, slot ^ 1);
         HIP_CHECK(hipEventSynchronize(c1.ev[slot]));
@@ -1093,6 +1136,7 @@ int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bo
     const int64_t bi = (ci - 1) / cb.nwin, within = (ci - 1) % cb.nwin;
     const int64_t bf0 = (1 + bi * cb.nwin) * c1.chunk;      // first frame of this chunk's burst
     const int slot = (int)(bi & 1);
+    SBV2_REQUIRE(!flac_bytes || cb.slot_f0[slot] == bf0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
     if (cb.slot_f0[slot] != bf0) stream_enqueue(cb, bf0, slot);                                    // (random access)
     // the following burst is decoded while this one is delivered (its slot was drained one burst ago)
     const int64_t nf0 = bf0 + (int64_t)cb.nwin * c1.chunk;

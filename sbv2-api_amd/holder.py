@@ -164,6 +164,23 @@ class TTSModelHolder:
             m.pipe = self._make_pipeline(self.bert, m.vits2)
         return orchestrator.easy_synthesize(m.pipe, sentences, m.style_vectors, style_id, speaker_id, options, noise_seed=noise_seed)
 
+    def easy_synthesize_stream(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, chunk_frames=256):
+        """The request as ONE utterance, delivered while it is synthesised (orchestrator.easy_synthesize_stream): a generator over the bytes of
+        the FLAC stream or WAV (an orchestrator.SynthesisStream: close() it when it is abandoned before its end).  `text`: a str, parsed as a whole (as split_sentences = False does), or the already parsed text as a one-entry
+        list.  Errors of the request are raised here, before the first piece."""
+        options = options or orchestrator.SynthesizeOptions()
+        self.find_and_load_model(ident)
+        m = self._find(ident)
+        if isinstance(text, str):
+            if self.parse_text is None:
+                raise model.Sbv2Error("no text front end configured (parse_text): pass parsed sentences instead")
+            sentences = [self.parse_text(text) if text else None]
+        else:
+            sentences = list(text)
+        # (the stream runs on the two sessions themselves, which the model's pipeline shares: the caller keeps requests one at a time, as rest.py does)
+        return orchestrator.easy_synthesize_stream(self.bert, m.vits2, sentences, m.style_vectors, style_id, speaker_id, options,
+                                                   noise_seed=noise_seed, chunk_frames=chunk_frames)
+
     def close(self):
         for m in self.models_:
             self._drop(m)

@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import Sbv2Batch, Sbv2Error, check, f32p, i64p
 
 __all__ = ["Session", "load_model", "predict", "synthesize", "predict_batch", "synthesize_batch", "Pipeline", "Node", "Comm", "deal", "Sbv2Error",
-           "PcmFormat", "pcm_format_length", "pcm_format_taps", "flac_bound", "debug_flac_encode", "Loudness", "loudness_kweight",
+           "PcmFormat", "pcm_format_length", "pcm_format_taps", "flac_bound", "debug_flac_encode", "flac_stream_bound", "debug_flac_stream_encode", "Loudness", "loudness_kweight",
            "debug_loudness", "Limiter", "debug_limiter"]
 
 
@@ -180,6 +180,27 @@ def debug_flac_encode(signals, sample_rate: int, device: int = 0):
     got = np.zeros(len(sigs), np.int64)
     check(_lib.lib().sbv2_debug_flac_encode(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(sigs),
                                             int(sample_rate), dst.ctypes.data_as(C.c_void_p), dst.nbytes, got.ctypes.data_as(i64p)))
+    return _split_bytes(dst, got)
+
+
+def flac_stream_bound(fmt: PcmFormat, n_native: int) -> int:
+    """Bytes that always suffice for one call of a FLAC stream whose chunks hold n_native 44.1 kHz samples (s16, not normalised; host only)."""
+    n = _lib.lib().sbv2_flac_stream_bound(C.byref(fmt.c), int(n_native))
+    if n < 0:
+        raise Sbv2Error(_lib.lib().sbv2_last_error().decode(errors="replace"))
+    return n
+
+
+def debug_flac_stream_encode(x, cuts, sample_rate: int, device: int = 0):
+    """Test hook: the device FLAC encoder fed piece by piece.  The host int16 signal x is cut at the ascending sample positions `cuts` into
+    len(cuts) + 1 pushes (empty ones allowed) -> the bytes each push delivered, in order (their concatenation is the FLAC stream)."""
+    x = np.ascontiguousarray(np.asarray(x, np.int16)).reshape(-1)
+    cuts = np.ascontiguousarray(np.asarray(cuts, np.int64)).reshape(-1)
+    dst = np.empty(42 + 16 * (-(-x.size // 4096)) + 2 * x.size, np.uint8)
+    got = np.zeros(cuts.size + 1, np.int64)
+    check(_lib.lib().sbv2_debug_flac_stream_encode(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, x.size,
+                                                   cuts.ctypes.data_as(i64p) if cuts.size else None, cuts.size, int(sample_rate),
+                                                   dst.ctypes.data_as(C.c_void_p), dst.nbytes, got.ctypes.data_as(i64p)))
     return _split_bytes(dst, got)
 
 
@@ -455,7 +476,8 @@ class Pipeline:
 def stream_synthesize(bert: Session, vits: Session, utt, chunk_frames=256, **kw):
     """Generator over the PCM chunks of ONE long utterance (BASELINE configs[4]): whole-sequence DeBERTa / text / flow, then the HiFi-GAN
     decoder chunk by chunk through a captured hipGraph.  Yields float32 arrays; `.info` of the generator's first item is not needed:
-    use stream_open for the handle-level interface."""
+    use stream_open for the handle-level interface.  With fmt=PcmFormat(...) the chunks come in that format, with flac=True as well as
+    the pieces (bytes, possibly empty) of one FLAC stream of those s16 samples."""
     st = StreamHandle(bert, vits, utt, chunk_frames, **kw)
     try:
         while True:
@@ -469,19 +491,26 @@ def stream_synthesize(bert: Session, vits: Session, utt, chunk_frames=256, **kw)
 
 class StreamHandle:
     """fmt (PcmFormat, optional): the chunks leave the device in that format (normalize is refused: a stream cannot know the peak ahead);
-    total_samples is then counted at fmt.sample_rate."""
+    total_samples is then counted at fmt.sample_rate.  flac=True (fmt must be s16): the chunks' samples are encoded on the device as ONE FLAC
+    stream; next() returns the bytes of the frames the chunk completed (b"" when it completed none: FLAC frames hold 4096 samples), the
+    42-byte stream header in front of the first ones; samples_taken counts the s16 samples consumed so far."""
 
-    def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, **kw):
+    def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False, **kw):
         l = _lib.lib()
         self.b = Pipeline.prepare(None, [utt], **kw)
         self.h = C.c_void_p()
-        self.fmt = fmt
+        self.fmt, self.flac, self.samples_taken = fmt, bool(flac), 0
+        if flac and fmt is None:
+            raise Sbv2Error("a FLAC stream needs a format: fmt=PcmFormat(rate, \"s16\")")
         tot = C.c_int64()
         args = (bert.handle, vits.handle, C.byref(self.b.c), self.b.ids.ctypes.data_as(i64p), self.b.s_lens.ctypes.data_as(i64p),
                 self.b.w2p.ctypes.data_as(i64p), chunk_frames)
         if fmt is None:
             check(l.sbv2_stream_begin(*args, C.byref(self.h), C.byref(tot)))
             self.buf = np.empty(chunk_frames * l.sbv2_vits_hop(vits.handle), np.float32)
+        elif flac:
+            check(l.sbv2_stream_begin_flac(*args, C.byref(fmt.c), C.byref(self.h), C.byref(tot)))
+            self.buf = np.empty(flac_stream_bound(fmt, chunk_frames * l.sbv2_vits_hop(vits.handle)), np.uint8)
         else:
             check(l.sbv2_stream_begin_format(*args, C.byref(fmt.c), C.byref(self.h), C.byref(tot)))
             self.buf = np.empty(pcm_format_length(fmt, chunk_frames * l.sbv2_vits_hop(vits.handle)) + 1, fmt.dtype)
@@ -491,6 +520,11 @@ class StreamHandle:
 
     def next(self):
         n = C.c_int64()
+        if self.flac:
+            nb = C.c_int64()
+            check(_lib.lib().sbv2_stream_next_flac(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.nbytes, C.byref(nb), C.byref(n)))
+            self.samples_taken += n.value
+            return None if n.value == 0 else self.buf[:nb.value].tobytes()
         if self.fmt is None:
             check(_lib.lib().sbv2_stream_next(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.size, C.byref(n)))
         else:
@@ -501,6 +535,12 @@ class StreamHandle:
         if self.h:
             _lib.lib().sbv2_stream_end(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def deal(costs, world: int) -> np.ndarray:

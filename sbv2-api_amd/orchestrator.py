@@ -165,3 +165,88 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
         if options.split_sentences and i != len(sentences) - 1:
             parts.append(np.zeros(SENTENCE_GAP, np.float32))
     return array_to_wav(np.concatenate(parts).reshape(1, 1, -1))
+
+
+def wav_stream_header(rate: int, encoding: str, n_samples: int) -> bytes:
+    """The header of pcm16_wav ("s16") / float_wav ("f32") for a signal of n_samples whose samples follow later: the same bytes as the header
+    of the finished file."""
+    empty = pcm16_wav(np.zeros(0, np.int16), rate) if encoding == "s16" else float_wav(np.zeros(0, np.float32), rate)
+    data = int(n_samples) * (2 if encoding == "s16" else 4)
+    riff = struct.unpack("<I", empty[4:8])[0] + data
+    return empty[:4] + struct.pack("<I", riff) + empty[8:-4] + struct.pack("<I", data)
+
+
+class SynthesisStream:
+    """The pieces (bytes) of one streamed answer, in order: an iterator that owns the model.StreamHandle behind it.  The handle is closed when
+    the pieces run out, when one fails, by close(), and when the object is dropped, iterated or not: the replays of a stream are already
+    enqueued when this object is returned, so its end cannot hang on a generator's `finally`, which never runs for a generator nobody started."""
+
+    def __init__(self, st, head, to_bytes):
+        self._st, self._head, self._to_bytes = st, head, to_bytes
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._head is not None:
+            head, self._head = self._head, None
+            return head
+        try:
+            while self._st is not None:
+                c = self._st.next()
+                if c is None:
+                    break
+                if len(c):
+                    return self._to_bytes(c)
+        except BaseException:
+            self.close()
+            raise
+        self.close()
+        raise StopIteration
+
+    def close(self):
+        st, self._st, self._head = self._st, None, None
+        if st is not None:
+            st.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
+                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256):
+    """easy_synthesize for long text, delivered while it is synthesised: an iterator (SynthesisStream; close() it when it is abandoned early)
+    over the pieces of the request's container.  A stream
+    takes ONE utterance (model.StreamHandle: whole-sequence DeBERTa / text / flow, then the decoder chunk by chunk), so `sentences` must hold
+    one parsed text: the request's lines joined, as options.split_sentences = False passes them (empty entries are skipped, a second live one
+    is refused).  encoding "flac": the pieces of one FLAC stream encoded on the device, as its frames complete (chunks that complete none
+    yield nothing); "s16" / "f32": the WAV header of pcm16_wav / float_wav written with the known total length, then the chunks' samples.
+    normalize, loudness and limiter are refused: they need the whole signal before the first sample can leave.
+    Everything up to the first replay (options, DeBERTa, flow, the header) runs before the iterator is returned."""
+    options = options or SynthesizeOptions()
+    if options.normalize:
+        raise model.Sbv2Error("a stream cannot normalise: the peak needs the whole signal (use /synthesize)")
+    if options.loudness is not None or options.limiter:
+        raise model.Sbv2Error("a stream has no loudness or limiter: integrated loudness needs the whole signal (use /synthesize)")
+    if noise_seed is None:
+        noise_seed = model.fresh_noise_seed()
+    style = get_style_vector(style_vectors, style_id, options.style_weight)
+    live = [s for s in sentences if s]
+    if not live:
+        raise model.Sbv2Error("nothing to synthesize (the reference's concatenate fails on an empty list)")
+    if len(live) != 1:
+        raise model.Sbv2Error(f"a stream takes one utterance, not {len(live)} sentences: pass the text parsed as a whole (split_sentences = False)")
+    flac = options.encoding == "flac"
+    fmt = model.PcmFormat(options.sample_rate, "s16" if flac else options.encoding, False)
+    model.pcm_format_length(fmt, 0)   # a bad rate is refused before any GPU work
+    st = model.StreamHandle(bert, vits, dict(live[0], style=style, sid=speaker_id), chunk_frames, fmt=None if fmt.is_default else fmt, flac=flac,
+                            sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
+                            noise_scale_w=noise_scale_w, noise_seed=noise_seed)
+    if flac:
+        return SynthesisStream(st, None, lambda c: c)
+    dtype = "<i2" if fmt.encoding == "s16" else "<f4"
+    return SynthesisStream(st, wav_stream_header(fmt.sample_rate, fmt.encoding, st.total_samples),
+                           lambda c: np.ascontiguousarray(c, dtype).tobytes())

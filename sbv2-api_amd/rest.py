@@ -9,6 +9,11 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     normalisation, exclusive with normalize.  The loudness gain is one scale: a target louder than the signal's
                     true_peak_max - (TP - L), about -21 LUFS for speech under -1 dBTP, is missed unless limiter = true (default false;
                     max_reduction = 6.0 dB): a look-ahead true-peak limiter that reaches it; limiter needs loudness)
+  POST /synthesize_stream  new: the same request, answered while it is synthesised (chunked transfer): the text as ONE utterance (joined, as
+                    split_sentences = false does), encoding "flac" -> audio/flac, one FLAC stream encoded on the device chunk by chunk;
+                    "s16" / "f32" -> audio/wav, the header written with the known length, then the chunks.  normalize / loudness / limiter
+                    are refused (they need the whole signal).  Errors before the first byte map as below; the lock is held until the last byte
+                    has left or the client has gone, whichever comes first (_HeldPieces, _ClosingStream).
   any error         500 text/plain "Something went wrong: <message>"            sbv2_api/src/error.rs:10-18
   one request at a time (Arc<Mutex<TTSModelHolder>>, main.rs:86,104)             -> a lock around the holder
 
@@ -18,9 +23,54 @@ import threading
 from typing import Optional
 
 
+class _HeldPieces:
+    """The pieces of one streamed answer together with the holder's lock, which the handler took before it asked the holder for them.
+    close() ends the pieces (their own close(), if they have one) and gives the lock back, exactly once, whoever calls it: the end of the
+    pieces, a failing piece, the response once it is over (_ClosingStream), or the collector.  Nothing here hangs on a generator's `finally`:
+    a client that goes away before the first piece is asked for leaves a generator that was never started, and such a one never runs it.
+    next and close exclude each other, so a piece still being fetched on a worker thread is never cut off by a close from the event loop."""
+
+    def __init__(self, lock, pieces):
+        self._lock, self._pieces, self._busy, self._open = lock, iter(pieces), threading.Lock(), True
+        self._close_pieces = getattr(pieces, "close", None)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        with self._busy:
+            if not self._open:
+                raise StopIteration
+            try:
+                return next(self._pieces)
+            except BaseException:      # the end (StopIteration) or a failing piece
+                self._close()
+                raise
+
+    def close(self):
+        with self._busy:
+            self._close()
+
+    def _close(self):
+        if not self._open:
+            return
+        self._open = False
+        try:
+            if self._close_pieces is not None:
+                self._close_pieces()
+        finally:
+            self._lock.release()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def make_app(holder):
     from fastapi import FastAPI, Request
-    from fastapi.responses import JSONResponse, PlainTextResponse, Response
+    from fastapi.responses import JSONResponse, PlainTextResponse, Response, StreamingResponse
     from pydantic import BaseModel
 
     from . import orchestrator
@@ -40,6 +90,20 @@ def make_app(holder):
         limiter: bool = False               # look-ahead true-peak limiter for targets the plain gain misses; needs loudness
         max_reduction: float = 6.0          # the limiter's deepest gain reduction (dB)
 
+    class _ClosingStream(StreamingResponse):
+        """A StreamingResponse that closes its _HeldPieces when the response is over, however it ends: sent to the end, cut by the client's
+        disconnect (before the first piece was asked for included) or failed."""
+
+        def __init__(self, held, **kw):
+            super().__init__(held, **kw)
+            self._held = held
+
+        async def __call__(self, scope, receive, send):
+            try:
+                await super().__call__(scope, receive, send)
+            finally:
+                self._held.close()
+
     app = FastAPI(docs_url="/docs")          # main.rs:196 serves the OpenAPI document at /docs as well
     lock = threading.Lock()
 
@@ -56,18 +120,30 @@ def make_app(holder):
         with lock:
             return JSONResponse(holder.models())
 
+    def options_of(req):
+        return orchestrator.SynthesizeOptions(sdp_ratio=req.sdp_ratio, length_scale=req.length_scale, sample_rate=req.sample_rate,
+                                              encoding=req.encoding, normalize=req.normalize, loudness=req.loudness,
+                                              true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction)
+
     @app.post("/synthesize")
     def synthesize(req: SynthesizeRequest):
         try:
             with lock:
-                wav = holder.easy_synthesize(req.ident, req.text, req.style_id, req.speaker_id,
-                                             orchestrator.SynthesizeOptions(sdp_ratio=req.sdp_ratio, length_scale=req.length_scale,
-                                                                            sample_rate=req.sample_rate, encoding=req.encoding,
-                                                                            normalize=req.normalize, loudness=req.loudness,
-                                                                            true_peak_max=req.true_peak_max, limiter=req.limiter,
-                                                                            max_reduction=req.max_reduction))
+                wav = holder.easy_synthesize(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
         return Response(content=wav, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
+
+    @app.post("/synthesize_stream")
+    def synthesize_stream(req: SynthesizeRequest):
+        lock.acquire()                        # one request at a time: given back by _HeldPieces.close when the response is over
+        try:
+            held = _HeldPieces(lock, holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req)))
+        except BaseException as e:            # before the first byte: the same mapping
+            lock.release()
+            if not isinstance(e, Exception):
+                raise
+            return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
+        return _ClosingStream(held, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
 
     return app
