@@ -461,6 +461,60 @@ int sbv2_debug_deberta_attention(int device, const float* q, const float* k, con
                                  int nutt, int64_t heads, int64_t d, int64_t buckets, int64_t max_rel, const uint8_t* tok_mask, int64_t gap, int variant,
                                  int poison, float* ctx, int64_t* stray);
 
+/* ---- One launcher of ops.h at a time on host data (test hooks; tests/test_ops_kernels.py) ----
+   Planes are host arrays [C][L] (row-major, no pitch); on the device they get the library's pitch (a multiple of 64 floats).  poison (where it is a
+   parameter; the other hooks always do it): the columns between L and the pitch of every input hold NaN, outputs are pre-filled with a sentinel, and *stray
+   (optional) = the number of words outside the valid region (pad columns, guard words behind a compact output) that the launch changed.  Packed-utterance
+   layouts are built by the models' own make_layout: kind 0 = the text encoder's (16-column gaps, columns rounded to 4), 1 = the flow's / decoder's
+   (4-column gaps, rounded to 32); sbv2_debug_layout returns the first column of every utterance and the column count L of that layout. */
+int sbv2_debug_layout(const int64_t* lens, int nutt, int kind, int32_t* start, int64_t* L);
+/* layernorm_ch: y = mask * (act(LN_c(x)) + res) (act 0 / 2 = none / GELU; res, mask may be null; inplace: out == in); split_code 2 / 4: the
+   result is also written as two bf16 parts / the f16 hi + scaled-lo pair, and ysplit = hi + lo (the lo scale undone).  dw_w != null: dds_dw_ln_gelu instead
+   (depthwise k = 3 conv with dilation dil and bias dw_b, LayerNorm eps 1e-5, GELU; eps / act ignored).  Which kernel runs is launch_layernorm's choice
+   (sbv2_debug_set_ksplit is honoured). */
+int sbv2_debug_layernorm(int device, const float* x, const float* gamma, const float* beta, float eps, int act, const float* res, const uint8_t* mask,
+                         const float* dw_w, const float* dw_b, int64_t dil, int64_t C, int64_t L, int inplace, int split_code, int poison, float* y,
+                         float* ysplit, int64_t* stray);
+/* deberta_embed_ln: y [H][N] = LN(emb[ids[n]]) per column; ids < 0 give a zero column */
+int sbv2_debug_deberta_embed_ln(int device, const int32_t* ids, const float* emb, int64_t V, int64_t H, const float* gamma, const float* beta, float eps,
+                                int64_t N, int poison, float* y, int64_t* stray);
+/* spline_inverse on z [2][L] (row 0 = z0, row 1 = z1, in place) with params [3 nbins - 1][L] */
+int sbv2_debug_spline_inverse(int device, const float* params, const float* z, const uint8_t* mask, int64_t L, int64_t nbins, float tail, float inv_sqrt_f,
+                              int poison, float* z_out, int64_t* stray);
+int sbv2_debug_durations(int device, const float* sdp, const float* dp, const uint8_t* mask, int64_t L, float ratio, float length_scale, float* logw,
+                         int32_t* dur, int64_t* stray);
+/* affine_reverse on z [2][L] in place: (z - m) * exp(-logs), or * scale when logs is null */
+int sbv2_debug_affine_reverse(int device, const float* z, const float* m, const float* logs, const float* scale, const uint8_t* mask, int64_t L,
+                              float* z_out, int64_t* stray);
+int sbv2_debug_convflow_pre(int device, const float* z0, const float* w, const float* b, const float* cond, const uint8_t* mask, int64_t C, int64_t L,
+                            float* y, int64_t* stray);
+/* noise_fill: y [rows][L of the layout]; seg_utt [nutt] = the caller-batch index of every utterance (the noise key) */
+int sbv2_debug_noise_fill(int device, const int64_t* lens, int nutt, int kind, const int32_t* seg_utt, uint64_t seed, int stream_id, float scale,
+                          int64_t rows, float* y, int64_t* stray);
+/* expand_frames: m_p, logs_p [C][Lt]; tok_of_frame [L of the frame layout of lens] (text column or -1); y [C][L] */
+int sbv2_debug_expand_frames(int device, const float* m_p, const float* logs_p, int64_t C, int64_t Lt, const int32_t* tok_of_frame, const int64_t* lens,
+                             int nutt, const int32_t* seg_utt, uint64_t seed, float noise_scale, float* y, int64_t* stray);
+/* conv_post_tanh (cl = 0) / conv_post_tanh_cl (cl = 1): x [C][L up] = the whole gapped plane of the frame layout of lens at `up` samples per frame,
+   w [C][k], slope 0.01; pcm = the utterances' samples back to back (lens[i] up each) */
+int sbv2_debug_conv_post_tanh(int device, const float* x, const float* w, int64_t C, int64_t k, const int64_t* lens, int nutt, int64_t up, int cl,
+                              float* pcm, int64_t* stray);
+int sbv2_debug_linear_vec(int device, const float* W, const float* bias, int64_t M, int64_t K, const float* v, int64_t B, float* y);
+int sbv2_debug_gather_rows(int device, const float* table, int64_t V, int64_t K, const int32_t* idx, int64_t B, float* y);
+/* text_embed on the text layout of lens: phones / tones / langs [L], bertproj [H][L], styleproj [nutt][H], y [H][L] */
+int sbv2_debug_text_embed(int device, const int32_t* phones, const int32_t* tones, const int32_t* langs, const int64_t* lens, int nutt, const float* emb,
+                          int64_t nph, const float* tone_emb, int64_t ntone, const float* lang_emb, int64_t nlang, const float* bertproj,
+                          const float* styleproj, float scale, int64_t H, float* y, int64_t* stray);
+/* add_segvec (cl = 0; x [C][L div], column n belongs to layout column n / div) / add_segvec_cl (cl = 1: the plane is transposed to [L][C] for the launch);
+   tok_mask [sum lens] (may be null) is the layout's extra mask; use_mask = 0 passes no mask to the kernel */
+int sbv2_debug_add_segvec(int device, const float* x, const float* vec, int64_t C, const int64_t* lens, int nutt, int kind, int64_t div,
+                          const uint8_t* tok_mask, int use_mask, int cl, float* y, int64_t* stray);
+/* op 0 = gather_cols (map [a], y [C][a]); 1 = transpose_out (col0 = a, T = b, y [T][C]); 2 = window_cols (col0 = a, width b, y [C][b], mask_out [b]);
+   3 = flip_channels; 4 = swap_rows (C = 2) */
+int sbv2_debug_plane_op(int device, int op, const float* x, int64_t C, int64_t L, const int32_t* map, int64_t a, int64_t b, float* y, uint8_t* mask_out,
+                        int64_t* stray);
+/* copy_segments: table [nseg][3] = (source offset, destination offset, length); dst is read and written (what no segment covers stays) */
+int sbv2_debug_copy_segments(int device, const float* src, int64_t nsrc, const int64_t* table, int nseg, float* dst, int64_t ndst);
+
 #ifdef __cplusplus
 }
 #endif

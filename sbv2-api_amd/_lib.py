@@ -156,6 +156,26 @@ SYMBOLS = {
                                             C.c_int, f32p, i64p]),
     "sbv2_debug_deberta_attention": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, i64p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                                C.c_void_p, C.c_int64, C.c_int, C.c_int, f32p, i64p]),
+    "sbv2_debug_layout": (C.c_int, [i64p, C.c_int, C.c_int, C.POINTER(C.c_int32), i64p]),
+    "sbv2_debug_layernorm": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_float, C.c_int, f32p, C.c_void_p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                       C.c_int, C.c_int, f32p, f32p, i64p]),
+    "sbv2_debug_deberta_embed_ln": (C.c_int, [C.c_int, C.POINTER(C.c_int32), f32p, C.c_int64, C.c_int64, f32p, f32p, C.c_float, C.c_int64, C.c_int, f32p,
+                                              i64p]),
+    "sbv2_debug_spline_inverse": (C.c_int, [C.c_int, f32p, f32p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_int, f32p, i64p]),
+    "sbv2_debug_durations": (C.c_int, [C.c_int, f32p, f32p, C.c_void_p, C.c_int64, C.c_float, C.c_float, f32p, C.POINTER(C.c_int32), i64p]),
+    "sbv2_debug_affine_reverse": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_void_p, C.c_int64, f32p, i64p]),
+    "sbv2_debug_convflow_pre": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_void_p, C.c_int64, C.c_int64, f32p, i64p]),
+    "sbv2_debug_noise_fill": (C.c_int, [C.c_int, i64p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_uint64, C.c_int, C.c_float, C.c_int64, f32p, i64p]),
+    "sbv2_debug_expand_frames": (C.c_int, [C.c_int, f32p, f32p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), i64p, C.c_int, C.POINTER(C.c_int32), C.c_uint64,
+                                           C.c_float, f32p, i64p]),
+    "sbv2_debug_conv_post_tanh": (C.c_int, [C.c_int, f32p, f32p, C.c_int64, C.c_int64, i64p, C.c_int, C.c_int64, C.c_int, f32p, i64p]),
+    "sbv2_debug_linear_vec": (C.c_int, [C.c_int, f32p, f32p, C.c_int64, C.c_int64, f32p, C.c_int64, f32p]),
+    "sbv2_debug_gather_rows": (C.c_int, [C.c_int, f32p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64, f32p]),
+    "sbv2_debug_text_embed": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64p, C.c_int, f32p, C.c_int64, f32p,
+                                        C.c_int64, f32p, C.c_int64, f32p, f32p, C.c_float, C.c_int64, f32p, i64p]),
+    "sbv2_debug_add_segvec": (C.c_int, [C.c_int, f32p, f32p, C.c_int64, i64p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, f32p, i64p]),
+    "sbv2_debug_plane_op": (C.c_int, [C.c_int, C.c_int, f32p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64, f32p, C.c_void_p, i64p]),
+    "sbv2_debug_copy_segments": (C.c_int, [C.c_int, f32p, C.c_int64, i64p, C.c_int, f32p, C.c_int64]),
 }
 
 _lib = None

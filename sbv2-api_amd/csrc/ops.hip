@@ -112,6 +112,22 @@ __global__ __launch_bounds__(256) void k_layernorm_ch(Plane in, Plane out, const
         }
     };
     if (EARLY) load_params();
+    // The column's sum over the G channel groups, the same value in every thread of the column.  Up to 32 groups: one chain in group order.  128 groups
+    // (COLS == 2): eight interleaved chains joined pairwise.  One chain of 128 partial sums rounds 127 times at the magnitude of the total; on columns whose
+    // mean is 1e3 x their spread that put the mean ~9 ulp off (768 channels: 5.5e-4), and every output of the column with it.
+    auto group_sum = [&]() -> float {
+        if constexpr (G <= 32) {
+            float t = 0.f;
+#pragma unroll
+            for (int g = 0; g < G; ++g) t += red[g][tx];
+            return t;
+        } else {
+            float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int g = 0; g < G; ++g) a[g & 7] += red[g][tx];
+            return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+        }
+    };
     float s = 0.f;
     if (CPT > 0) {
 #pragma unroll
@@ -122,9 +138,7 @@ __global__ __launch_bounds__(256) void k_layernorm_ch(Plane in, Plane out, const
     }
     red[ty][tx] = s;
     __syncthreads();
-    float mean = 0.f;
-#pragma unroll
-    for (int g = 0; g < G; ++g) mean += red[g][tx];
+    float mean = group_sum();
     mean /= C;
     __syncthreads();
     float q = 0.f;
@@ -143,9 +157,7 @@ __global__ __launch_bounds__(256) void k_layernorm_ch(Plane in, Plane out, const
     }
     red[ty][tx] = q;
     __syncthreads();
-    float var = 0.f;
-#pragma unroll
-    for (int g = 0; g < G; ++g) var += red[g][tx];
+    const float var = group_sum();
     const float rstd = 1.0f / sqrtf(var / C + eps);
     if (!ok) return;
     const bool keep = !mask || mask[n];

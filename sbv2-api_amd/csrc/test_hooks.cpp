@@ -1,6 +1,8 @@
 // The test hooks of libsbv2_hip.so (the sbv2_debug_* entry points of include/sbv2_hip.h): one kernel or launcher at a time on host data, for the tests
 // and the probe tools.  The decoder's kernels get their parameters from the decoder's own builders (decoder_cl.cpp: pack_decoder_conv, conv_cl_params,
-// step_params, branch_params), so a test of a kernel also tests what the decoder launches.
+// step_params, branch_params), so a test of a kernel also tests what the decoder launches.  The launchers of ops.h (LayerNorm, the duration flow's pieces,
+// noise, the generator tail, the movers) have one hook per launcher or family, on planes at the library's pitches and layouts built by the models' own
+// make_layout, with the attention hooks' poison / sentinel / stray-count convention (tests/test_ops_kernels.py).
 #include <cstring>
 #include <limits>
 
@@ -174,6 +176,61 @@ struct AudioScratch {
     AudioScratch(const AudioScratch&) = delete;
     AudioScratch& operator=(const AudioScratch&) = delete;
 };
+
+// ---- the hooks of ops.h's launchers (tests/test_ops_kernels.py) ----------------------------------------------------------------------------------------
+// A host plane [C][L] on the device at the library's pitch (Arena::plane's rule: a multiple of 64 floats).  poison: the columns between L and the pitch,
+// and every column where inside[n] == 0 (inside may be null), hold NaN (all bits set) instead of zero.  Outputs are pre-filled with the sentinel; after
+// the launch get() counts the pad words (columns L .. pitch) that no longer hold what they held before it.
+constexpr uint32_t kSentinelWord = 0x5A5A5A5Au, kNanWord = 0xFFFFFFFFu;
+struct DevPlane {
+    Plane P;
+    DevMem m;
+    DevPlane(int64_t C, int64_t L) : P{nullptr, (int)C, (int)L, round_up((int)L, 64)}, m(sizeof(float) * (size_t)C * round_up((int)L, 64)) {
+        SBV2_REQUIRE(C >= 1 && L >= 1 && L < (1 << 28) && C < (1 << 20), "bad plane shape");
+        P.p = m.f();
+    }
+    void put(const float* x, bool poison, const unsigned char* inside = nullptr) {
+        std::vector<float> h((size_t)P.C * P.ld, poison ? std::numeric_limits<float>::quiet_NaN() : 0.f);
+        if (poison) std::memset(h.data(), 0xFF, sizeof(float) * h.size());
+        for (int c = 0; c < P.C; ++c)
+            for (int n = 0; n < P.L; ++n)
+                if (!poison || !inside || inside[n]) h[(size_t)c * P.ld + n] = x[(size_t)c * P.L + n];
+        HIP_CHECK(hipMemcpy(P.p, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
+    }
+    void fill(bool poison) { HIP_CHECK(hipMemset(P.p, poison ? kCtxSentinel : 0, sizeof(float) * (size_t)P.C * P.ld)); }
+    // y [C][L] (any 4-byte element type); returns the number of pad words that are not `pad`
+    int64_t get(void* y, uint32_t pad) const {
+        std::vector<uint32_t> h((size_t)P.C * P.ld);
+        HIP_CHECK(hipMemcpy(h.data(), P.p, 4 * h.size(), hipMemcpyDeviceToHost));
+        int64_t stray = 0;
+        for (int c = 0; c < P.C; ++c) {
+            std::memcpy(static_cast<uint32_t*>(y) + (size_t)c * P.L, &h[(size_t)c * P.ld], 4 * (size_t)P.L);
+            for (int n = P.L; n < P.ld; ++n) stray += h[(size_t)c * P.ld + n] != pad;
+        }
+        return stray;
+    }
+};
+// the text encoder's layout (kind 0: kTextGap, columns rounded to 4) or the flow's / decoder's (kind 1: kFrameGap, rounded to 32), as VitsModel builds them
+SegLayout hook_layout(const int64_t* lens, int nutt, int kind, Arena& ar, const unsigned char* extra_mask = nullptr) {
+    SBV2_REQUIRE(lens && nutt >= 1 && (kind == 0 || kind == 1), "bad layout arguments");
+    std::vector<int> L(nutt);
+    for (int i = 0; i < nutt; ++i) {
+        SBV2_REQUIRE(lens[i] >= 1 && lens[i] < (1 << 20), "bad sequence length");
+        L[i] = (int)lens[i];
+    }
+    return kind ? make_layout(L, kFrameGap, ar, nullptr, extra_mask, 32) : make_layout(L, kTextGap, ar, nullptr, extra_mask);
+}
+// inside[n] = column n / div belongs to an utterance
+std::vector<unsigned char> layout_inside(const SegLayout& lay, int div = 1) {
+    std::vector<unsigned char> in((size_t)lay.L * div, 0);
+    for (int u = 0; u < lay.n; ++u) std::memset(&in[(size_t)lay.start[u] * div], 1, (size_t)lay.len[u] * div);
+    return in;
+}
+int* upload_ints(Arena& ar, const int32_t* v, size_t n) {
+    int* d = ar.array<int>(std::max<size_t>(n, 1));
+    if (n) HIP_CHECK(hipMemcpy(d, v, sizeof(int) * n, hipMemcpyHostToDevice));
+    return d;
+}
 
 }  // namespace
 
@@ -814,6 +871,376 @@ int sbv2_debug_deberta_attention(int device, const float* q, const float* k, con
     }
     HIP_CHECK(hipDeviceSynchronize());
     download_packed(C, lay, poison, ctx, stray);
+    API_END
+}
+
+int sbv2_debug_layout(const int64_t* lens, int nutt, int kind, int32_t* start, int64_t* L) {
+    API_BEGIN
+    SBV2_REQUIRE(start && L, "bad arguments");
+    Arena ar;
+    const SegLayout lay = hook_layout(lens, nutt, kind, ar);
+    HIP_CHECK(hipDeviceSynchronize());
+    for (int u = 0; u < nutt; ++u) start[u] = lay.start[u];
+    *L = lay.L;
+    API_END
+}
+
+int sbv2_debug_layernorm(int device, const float* x, const float* gamma, const float* beta, float eps, int act, const float* res, const uint8_t* mask,
+                         const float* dw_w, const float* dw_b, int64_t dil, int64_t C, int64_t L, int inplace, int split_code, int poison, float* y,
+                         float* ysplit, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && gamma && beta && y && (act == ACT_NONE || act == ACT_GELU) && (split_code == 0 || split_code == 2 || split_code == kPartsF16x3) &&
+                     (!split_code || ysplit) && (!dw_w || (dw_b && !res && !inplace && !split_code && dil >= 1)),
+                 "bad arguments");
+    Arena ar;
+    DevPlane X(C, L), Yo(inplace ? 1 : C, inplace ? 1 : L), R(res ? C : 1, res ? L : 1);
+    X.put(x, poison);
+    if (res) R.put(res, poison);
+    if (!inplace) Yo.fill(poison);
+    const Plane Y = inplace ? X.P : Yo.P;
+    DevMem dg(gamma, sizeof(float) * C), db(beta, sizeof(float) * C), dm(mask, mask ? (size_t)L : 0), dw(dw_w, dw_w ? sizeof(float) * 3 * C : 0),
+        dwb(dw_b, dw_w ? sizeof(float) * C : 0);
+    SplitPlanes sp;
+    if (split_code) {
+        sp = alloc_split(ar, split_code, (int)C, (int)L);
+        HIP_CHECK(hipMemset(sp.p, kCtxSentinel, (size_t)sp.parts * sp.pstride * 2));
+    }
+    if (dw_w) dds_dw_ln_gelu(X.P, Y, dw.f(), dwb.f(), (int)dil, dg.f(), db.f(), mask ? dm.u8() : nullptr, nullptr);
+    else layernorm_ch(X.P, Y, dg.f(), db.f(), eps, act, res ? R.P.p : nullptr, R.P.ld, mask ? dm.u8() : nullptr, nullptr, split_code ? &sp : nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    int64_t bad = (inplace ? X : Yo).get(y, inplace ? kNanWord : kSentinelWord);
+    if (split_code) {   // hi + lo of the parts (the f16 pair: lo scaled back), and the pad columns of every part
+        std::vector<uint16_t> hs((size_t)sp.parts * sp.pstride);
+        HIP_CHECK(hipMemcpy(hs.data(), sp.p, hs.size() * 2, hipMemcpyDeviceToHost));
+        for (int64_t c = 0; c < C; ++c)
+            for (int64_t n = 0; n < sp.ld; ++n) {
+                if (n >= L) {
+                    for (int pp = 0; pp < sp.parts; ++pp) bad += hs[(size_t)pp * sp.pstride + c * sp.ld + n] != (uint16_t)(kSentinelWord & 0xFFFF);
+                    continue;
+                }
+                if (sp.f16) {
+                    _Float16 hi, lo;
+                    memcpy(&hi, &hs[(size_t)c * sp.ld + n], 2);
+                    memcpy(&lo, &hs[(size_t)sp.pstride + c * sp.ld + n], 2);
+                    ysplit[(size_t)c * L + n] = (float)hi + (float)lo * (1.0f / kF16LoScale);
+                    continue;
+                }
+                float acc = 0.f;
+                for (int pp = sp.parts - 1; pp >= 0; --pp) {
+                    const uint32_t u = (uint32_t)hs[(size_t)pp * sp.pstride + c * sp.ld + n] << 16;
+                    float f;
+                    memcpy(&f, &u, 4);
+                    acc += f;
+                }
+                ysplit[(size_t)c * L + n] = acc;
+            }
+    }
+    if (stray) *stray = poison ? bad : 0;
+    API_END
+}
+
+int sbv2_debug_deberta_embed_ln(int device, const int32_t* ids, const float* emb, int64_t V, int64_t H, const float* gamma, const float* beta, float eps,
+                                int64_t N, int poison, float* y, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(ids && emb && gamma && beta && y && V >= 1 && H >= 1, "bad arguments");
+    for (int64_t n = 0; n < N; ++n) SBV2_REQUIRE(ids[n] < V, "token id outside the table");
+    DevPlane Y(H, N);
+    Y.fill(poison);
+    DevMem di(ids, sizeof(int) * N), de(emb, sizeof(float) * V * H), dg(gamma, sizeof(float) * H), db(beta, sizeof(float) * H);
+    deberta_embed_ln(static_cast<const int*>(di.p), de.f(), (int)H, dg.f(), db.f(), eps, Y.P, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = Y.get(y, kSentinelWord);
+    if (stray) *stray = poison ? bad : 0;
+    API_END
+}
+
+int sbv2_debug_spline_inverse(int device, const float* params, const float* z, const uint8_t* mask, int64_t L, int64_t nbins, float tail, float inv_sqrt_f,
+                              int poison, float* z_out, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(params && z && mask && z_out && nbins >= 1, "bad arguments");
+    DevPlane PR(3 * nbins - 1, L), Z(2, L);   // z0 | z1 as the two rows of one plane, as the duration flow keeps them
+    PR.put(params, poison);
+    Z.put(z, poison);
+    DevMem dm(mask, (size_t)L);
+    spline_inverse(PR.P, Z.P.p, Z.P.p + Z.P.ld, (int)nbins, tail, inv_sqrt_f, dm.u8(), (int)L, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = Z.get(z_out, kNanWord);
+    if (stray) *stray = poison ? bad : 0;
+    API_END
+}
+
+int sbv2_debug_durations(int device, const float* sdp, const float* dp, const uint8_t* mask, int64_t L, float ratio, float length_scale, float* logw,
+                         int32_t* dur, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(sdp && dp && mask && logw && dur, "bad arguments");
+    DevPlane S(1, L), D(1, L), W(1, L), U(1, L);
+    S.put(sdp, true);
+    D.put(dp, true);
+    W.fill(true);
+    U.fill(true);
+    DevMem dm(mask, (size_t)L);
+    durations(S.P.p, D.P.p, ratio, length_scale, dm.u8(), (int)L, W.P.p, reinterpret_cast<int*>(U.P.p), nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = W.get(logw, kSentinelWord) + U.get(dur, kSentinelWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_affine_reverse(int device, const float* z, const float* m, const float* logs, const float* scale, const uint8_t* mask, int64_t L,
+                              float* z_out, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(z && m && (logs || scale) && mask && z_out, "bad arguments");
+    DevPlane Z(2, L);
+    Z.put(z, true);
+    DevMem dmn(m, 8), dl(logs, logs ? 8 : 0), ds(scale, scale ? 8 : 0), dm(mask, (size_t)L);
+    affine_reverse(Z.P.p, Z.P.p + Z.P.ld, dmn.f(), logs ? dl.f() : nullptr, scale ? ds.f() : nullptr, dm.u8(), (int)L, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = Z.get(z_out, kNanWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_convflow_pre(int device, const float* z0, const float* w, const float* b, const float* cond, const uint8_t* mask, int64_t C, int64_t L,
+                            float* y, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(z0 && w && b && cond && mask && y, "bad arguments");
+    DevPlane Z(1, L), CO(C, L), Y(C, L);
+    Z.put(z0, true);
+    CO.put(cond, true);
+    Y.fill(true);
+    DevMem dw(w, sizeof(float) * C), db(b, sizeof(float) * C), dm(mask, (size_t)L);
+    convflow_pre(Z.P.p, dw.f(), db.f(), CO.P, Y.P, dm.u8(), nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = Y.get(y, kSentinelWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_noise_fill(int device, const int64_t* lens, int nutt, int kind, const int32_t* seg_utt, uint64_t seed, int stream_id, float scale,
+                          int64_t rows, float* y, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(seg_utt && y && rows >= 1, "bad arguments");
+    Arena ar;
+    const SegLayout lay = hook_layout(lens, nutt, kind, ar);
+    DevPlane Y(rows, lay.L);
+    Y.fill(true);
+    noise_fill(Y.P.p, Y.P.ld, (int)rows, lay.d_seg_of, lay.d_start, lay.d_len, upload_ints(ar, seg_utt, nutt), lay.L, seed, stream_id, scale, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = Y.get(y, kSentinelWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_expand_frames(int device, const float* m_p, const float* logs_p, int64_t C, int64_t Lt, const int32_t* tok_of_frame, const int64_t* lens,
+                             int nutt, const int32_t* seg_utt, uint64_t seed, float noise_scale, float* y, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(m_p && logs_p && tok_of_frame && seg_utt && y, "bad arguments");
+    Arena ar;
+    const SegLayout lay = hook_layout(lens, nutt, 1, ar);
+    const std::vector<unsigned char> inside = layout_inside(lay);
+    for (int n = 0; n < lay.L; ++n) SBV2_REQUIRE(tok_of_frame[n] < Lt && (inside[n] || tok_of_frame[n] < 0), "token map outside the text plane or in a gap");
+    DevPlane M(C, Lt), S(C, Lt), Y(C, lay.L);
+    M.put(m_p, true);
+    S.put(logs_p, true);
+    Y.fill(true);
+    expand_frames(M.P, S.P, upload_ints(ar, tok_of_frame, lay.L), lay.d_seg_of, lay.d_start, lay.d_len, upload_ints(ar, seg_utt, nutt), seed, noise_scale,
+                  Y.P, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = Y.get(y, kSentinelWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_conv_post_tanh(int device, const float* x, const float* w, int64_t C, int64_t k, const int64_t* lens, int nutt, int64_t up, int cl,
+                              float* pcm, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && w && pcm && C >= 1 && k >= 1 && up >= 1, "bad arguments");
+    Arena ar;
+    const SegLayout lay = hook_layout(lens, nutt, 1, ar);
+    const int64_t L = (int64_t)lay.L * up;
+    std::vector<int64_t> off(nutt);
+    int64_t tot = 0, maxlen = 0;
+    for (int u = 0; u < nutt; ++u) {   // compact PCM, one contiguous block per utterance (as the decoders)
+        off[u] = tot;
+        tot += (int64_t)lay.len[u] * up;
+        maxlen = std::max(maxlen, (int64_t)lay.len[u] * up);
+    }
+    constexpr int64_t kGuard = 256;
+    DevMem dp(sizeof(float) * (size_t)(tot + kGuard)), dw(w, sizeof(float) * C * k), doff(off.data(), sizeof(int64_t) * nutt);
+    HIP_CHECK(hipMemset(dp.p, kCtxSentinel, sizeof(float) * (size_t)(tot + kGuard)));
+    if (cl) {
+        DevMem dx = upload_cl(x, C, L);
+        conv_post_tanh_cl(dx.f(), (int)C, L, dw.f(), (int)k, 0.01f, lay.d_start, lay.d_len, static_cast<const int64_t*>(doff.p), nutt, (int)up, maxlen,
+                          dp.f(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+    } else {
+        DevPlane X(C, L);
+        X.put(x, true);
+        conv_post_tanh(X.P, dw.f(), (int)k, 0.01f, lay.d_start, lay.d_len, static_cast<const int64_t*>(doff.p), nutt, (int)up, maxlen, dp.f(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+    }
+    std::vector<uint32_t> h((size_t)(tot + kGuard));
+    HIP_CHECK(hipMemcpy(h.data(), dp.p, 4 * h.size(), hipMemcpyDeviceToHost));
+    std::memcpy(pcm, h.data(), 4 * (size_t)tot);
+    int64_t bad = 0;
+    for (int64_t e = tot; e < tot + kGuard; ++e) bad += h[e] != kSentinelWord;
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_linear_vec(int device, const float* W, const float* bias, int64_t M, int64_t K, const float* v, int64_t B, float* y) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(W && v && y && M >= 1 && K >= 1 && B >= 1, "bad arguments");
+    DevMem dW(W, sizeof(float) * M * K), db(bias, bias ? sizeof(float) * M : 0), dv(v, sizeof(float) * B * K), dy(sizeof(float) * B * M);
+    linear_vec(dW.f(), bias ? db.f() : nullptr, (int)M, (int)K, dv.f(), (int)K, dy.f(), (int)M, (int)B, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(y, dy.p, sizeof(float) * B * M, hipMemcpyDeviceToHost));
+    API_END
+}
+
+int sbv2_debug_gather_rows(int device, const float* table, int64_t V, int64_t K, const int32_t* idx, int64_t B, float* y) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(table && idx && y && V >= 1 && K >= 1 && B >= 1, "bad arguments");
+    for (int64_t b = 0; b < B; ++b) SBV2_REQUIRE(idx[b] >= 0 && idx[b] < V, "row index outside the table");
+    DevMem dt(table, sizeof(float) * V * K), di(idx, sizeof(int) * B), dy(sizeof(float) * B * K);
+    gather_rows(dt.f(), (int)K, static_cast<const int*>(di.p), dy.f(), (int)B, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(y, dy.p, sizeof(float) * B * K, hipMemcpyDeviceToHost));
+    API_END
+}
+
+int sbv2_debug_text_embed(int device, const int32_t* phones, const int32_t* tones, const int32_t* langs, const int64_t* lens, int nutt, const float* emb,
+                          int64_t nph, const float* tone_emb, int64_t ntone, const float* lang_emb, int64_t nlang, const float* bertproj,
+                          const float* styleproj, float scale, int64_t H, float* y, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(phones && tones && langs && emb && tone_emb && lang_emb && bertproj && styleproj && y && H >= 1, "bad arguments");
+    Arena ar;
+    const SegLayout lay = hook_layout(lens, nutt, 0, ar);
+    const std::vector<unsigned char> inside = layout_inside(lay);
+    for (int n = 0; n < lay.L; ++n)
+        SBV2_REQUIRE(!inside[n] || (phones[n] >= 0 && phones[n] < nph && tones[n] >= 0 && tones[n] < ntone && langs[n] >= 0 && langs[n] < nlang),
+                     "symbol outside its table");
+    DevPlane BP(H, lay.L), Y(H, lay.L);
+    BP.put(bertproj, true, inside.data());
+    Y.fill(true);
+    DevMem de(emb, sizeof(float) * nph * H), dt(tone_emb, sizeof(float) * ntone * H), dl(lang_emb, sizeof(float) * nlang * H),
+        ds(styleproj, sizeof(float) * nutt * H);
+    text_embed(upload_ints(ar, phones, lay.L), upload_ints(ar, tones, lay.L), upload_ints(ar, langs, lay.L), lay.d_seg_of, de.f(), dt.f(), dl.f(), BP.P.p,
+               BP.P.ld, ds.f(), (int)H, scale, Y.P, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = Y.get(y, kSentinelWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_add_segvec(int device, const float* x, const float* vec, int64_t C, const int64_t* lens, int nutt, int kind, int64_t div,
+                          const uint8_t* tok_mask, int use_mask, int cl, float* y, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && vec && y && C >= 1 && div >= 1 && (!cl || (div == 1 && use_mask && (C & 3) == 0)), "bad arguments");
+    Arena ar;
+    const SegLayout lay = hook_layout(lens, nutt, kind, ar, tok_mask);
+    const int64_t L = (int64_t)lay.L * div;
+    DevMem dv(vec, sizeof(float) * nutt * C);
+    int64_t bad = 0;
+    if (cl) {
+        DevMem dx = upload_cl(x, C, L);
+        add_segvec_cl(dx.f(), (int)L, (int)C, dv.f(), (int)C, lay.d_seg_of, lay.d_mask, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        download_cl(dx.f(), C, L, y);
+    } else {
+        const std::vector<unsigned char> inside = layout_inside(lay, (int)div);
+        DevPlane X(C, L);
+        X.put(x, true, inside.data());
+        add_segvec(X.P, dv.f(), (int)C, lay.d_seg_of, (int)div, use_mask ? lay.d_mask : nullptr, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        bad = X.get(y, kNanWord);
+    }
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_plane_op(int device, int op, const float* x, int64_t C, int64_t L, const int32_t* map, int64_t a, int64_t b, float* y, uint8_t* mask_out,
+                        int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && y && op >= 0 && op <= 4, "bad arguments");
+    DevPlane X(C, L);
+    X.put(x, true);
+    int64_t bad = 0;
+    if (op == 0) {          // gather_cols: map [a], y [C][a]
+        SBV2_REQUIRE(map && a >= 1, "bad arguments");
+        for (int64_t n = 0; n < a; ++n) SBV2_REQUIRE(map[n] < L, "column map outside the plane");
+        DevPlane Y(C, a);
+        Y.fill(true);
+        DevMem dmap(map, sizeof(int) * a);
+        gather_cols(X.P, static_cast<const int*>(dmap.p), Y.P, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        bad = Y.get(y, kSentinelWord);
+    } else if (op == 1) {   // transpose_out: col0 = a, T = b, y [T][C]
+        SBV2_REQUIRE(a >= 0 && b >= 1 && a + b <= L, "bad arguments");
+        constexpr int64_t kGuard = 64;
+        DevMem dy(sizeof(float) * (size_t)(b * C + kGuard));
+        HIP_CHECK(hipMemset(dy.p, kCtxSentinel, sizeof(float) * (size_t)(b * C + kGuard)));
+        transpose_out(X.P, (int)a, (int)b, dy.f(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        std::vector<uint32_t> h((size_t)(b * C + kGuard));
+        HIP_CHECK(hipMemcpy(h.data(), dy.p, 4 * h.size(), hipMemcpyDeviceToHost));
+        std::memcpy(y, h.data(), 4 * (size_t)(b * C));
+        for (int64_t e = b * C; e < b * C + kGuard; ++e) bad += h[e] != kSentinelWord;
+    } else if (op == 2) {   // window_cols: col0 = a (any sign), width = b, y [C][b], mask_out [b]
+        SBV2_REQUIRE(b >= 1 && mask_out && a > -(1 << 28) && a < (1 << 28), "bad arguments");
+        DevPlane Y(C, b);
+        Y.fill(true);
+        DevMem dm((size_t)round_up((int)b, 64));
+        HIP_CHECK(hipMemset(dm.p, kCtxSentinel, (size_t)round_up((int)b, 64)));
+        window_cols(X.P, (int)a, Y.P, dm.u8(), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        bad = Y.get(y, kSentinelWord);
+        std::vector<unsigned char> hm((size_t)round_up((int)b, 64));
+        HIP_CHECK(hipMemcpy(hm.data(), dm.p, hm.size(), hipMemcpyDeviceToHost));
+        std::memcpy(mask_out, hm.data(), (size_t)b);
+        for (size_t n = (size_t)b; n < hm.size(); ++n) bad += hm[n] != kCtxSentinel;
+    } else if (op == 3) {   // flip_channels
+        DevPlane Y(C, L);
+        Y.fill(true);
+        flip_channels(X.P, Y.P, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        bad = Y.get(y, kSentinelWord);
+    } else {                // swap_rows: rows 0 and 1 of a two-row plane, in place
+        SBV2_REQUIRE(C == 2, "swap_rows: two rows");
+        swap_rows(X.P.p, X.P.p + X.P.ld, (int)L, nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        bad = X.get(y, kNanWord);
+    }
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_copy_segments(int device, const float* src, int64_t nsrc, const int64_t* table, int nseg, float* dst, int64_t ndst) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(src && table && dst && nsrc >= 1 && ndst >= 1 && nseg >= 0, "bad arguments");
+    for (int i = 0; i < nseg; ++i)
+        SBV2_REQUIRE(table[3 * i] >= 0 && table[3 * i + 1] >= 0 && table[3 * i + 2] >= 0 && table[3 * i] + table[3 * i + 2] <= nsrc &&
+                         table[3 * i + 1] + table[3 * i + 2] <= ndst,
+                     "segment outside its buffer");
+    DevMem ds(src, sizeof(float) * nsrc), dd(dst, sizeof(float) * ndst), dt(table, sizeof(int64_t) * 3 * nseg);   // (dst keeps what no segment covers)
+    copy_segments(ds.f(), dd.f(), static_cast<const int64_t*>(dt.p), nseg, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(dst, dd.p, sizeof(float) * ndst, hipMemcpyDeviceToHost));
     API_END
 }
 
