@@ -443,6 +443,31 @@ int sbv2_debug_gemm_bfs(int device, const float* x, const float* w, const float*
    wrong result: the race screen of gemm_bfs.hip's cross-workgroup K split.  parts as above. */
 int sbv2_debug_gemm_bfs_alt(int device, const float* xa, const float* xb, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
                             int parts, int64_t iters, float* ya, float* yb);
+/* ---- conv_plain, conv_bfs, the encoders' FFN pair and linear_tokmajor with every argument the models pass (tests/test_gemm_conv_kernels.py) ----
+   Host planes [C][L] without pitch; on the device every plane sits at the library's pitch, every input holds NaN in the columns L .. pitch, outputs are
+   pre-filled with a sentinel (0x5A bytes) and *stray (optional) = the number of pad words of the outputs that the launch changed.
+   Epilogue order of all of them: bias, act (0 none, 1 ReLU, 2 erf-GELU, 3 tanh), * alpha, + res, * beta, + previous contents (accumulate), mask.
+   sbv2_debug_conv_plain: exactly conv_plain on a WeightStore(blob, cl_parts): y[co][n] = epi(sum_ci sum_j w[co][ci][j] lrelu(x, pre_slope)[ci][n + j dilation -
+   pad_l]); cl_parts 0 = launch_conv (f32 MFMA, the skinny kernels under sbv2_debug_set_skinny_max), 2 / 1 / 3 = split-bf16 / bf16 / f16 fragments, which k >= 3
+   takes through the k-major launch_conv_cl.  bias, mask, res may be null; output column n is kept iff mask[n / mask_div]; y_inout is read when accumulate. */
+int sbv2_debug_conv_plain(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k, int64_t L, int64_t dilation,
+                          int64_t pad_l, int cl_parts, const uint8_t* mask, int64_t mask_div, int act, float pre_slope, const float* res, float alpha,
+                          float beta, int accumulate, float* y_inout, int64_t* stray);
+/* The encoder FFN as VitsModel runs it on the matrix cores (split-bf16): mid = mask * (conv(x, w1 [F][H][k]) + b1) kept channels-last on the device
+   (conv_km_to_cl; returned as [F][L]), y = mask * (conv(relu(mid), w2 [H][F][k]) + b2 + res) (conv_cl_to_km with pre_slope 0); 'same' padding (k - 1) / 2.
+   Fails where either function refuses the shape. */
+int sbv2_debug_conv_ffn_cl(int device, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, int64_t H, int64_t F, int64_t k,
+                           int64_t L, const uint8_t* mask, const float* res, float* y, float* mid, int64_t* stray);
+/* sbv2_debug_gemm_bfs with the rest of conv_bfs' arguments: the result is act(w x + bias) * alpha (+ res) * beta, column n kept iff mask[n / mask_div]; the
+   f32 plane y receives rows < y_rows (-1: all; want_y = 0: no f32 plane is passed), the parts rows >= ys_row0; ys = the recombined parts, separately from
+   y.  Rows a plane does not receive still hold the sentinel (ys: the recombination of sentinel halves). */
+int sbv2_debug_gemm_bfs_ex(int device, const float* x, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K, int parts, int act,
+                           int split_out, int64_t iters, const uint8_t* mask, int64_t mask_div, float alpha, float beta, int64_t y_rows, int64_t ys_row0,
+                           int want_y, float* y, float* ys, float* ms, int64_t* stray);
+/* linear_tokmajor: y [L][cout] = x^T w^T + bias from x [cin][L], w [cout][cin]; on the device y has the row pitch ldy >= cout (columns cout .. ldy and the
+   words behind the last row are counted in *stray) */
+int sbv2_debug_linear_tokmajor(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t L, int64_t ldy, float* y,
+                               int64_t* stray);
 /* One window-relative attention of the VITS encoders (attn_flash.hip / ops.hip) on a packed batch, laid out and planned by the model's own builders
    (make_layout, make_attn_plan, flash_choice).  q, k, v, ctx: [heads * dk][sum lens] (utterances concatenated, head h = rows h dk .. + dk); erk, erv:
    [2 window + 1][dk]; layout: 0 = text-rate layout, 1 = frame-rate layout (the flow's); qscale = 1 / sqrt(dk).  variant: -1 = the flow's own choice for

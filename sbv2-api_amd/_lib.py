@@ -152,6 +152,13 @@ SYMBOLS = {
     "sbv2_debug_gemm_bfs_alt": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, f32p, f32p]),
     "sbv2_debug_gemm_bfs": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64,
                                       f32p, f32p]),
+    "sbv2_debug_conv_plain": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,
+                                        C.c_int64, C.c_int, C.c_float, f32p, C.c_float, C.c_float, C.c_int, f32p, i64p]),
+    "sbv2_debug_conv_ffn_cl": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, f32p, f32p, f32p,
+                                         i64p]),
+    "sbv2_debug_gemm_bfs_ex": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                         C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int64, C.c_int, f32p, f32p, f32p, i64p]),
+    "sbv2_debug_linear_tokmajor": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, f32p, i64p]),
     "sbv2_debug_vits_attention": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, i64p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                             C.c_int, f32p, i64p]),
     "sbv2_debug_deberta_attention": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, i64p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,

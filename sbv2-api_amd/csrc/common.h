@@ -244,6 +244,13 @@ struct GemmGroup {
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_TANH = 3 };
 enum BiasMode { BIAS_NONE = 0, BIAS_ROW = 1, BIAS_COL = 2 };
 
+// Epilogue, in this order (every implementation: the staged-tile and scalar forms of conv_gemm_kernel, the ring instantiations, which share them, and
+// gemm_skinny.hip's): v = acc + bias; v = act(v) (GELU is the erf form); v *= alpha; v += R; v *= beta; v += C (accumulate); v = mask ? v : 0.
+// Pad contract: B is read as zero outside columns [0, nb) whatever the memory holds there, and a 16-byte load that starts at a column < N may cover up to
+// three pad columns of A / B / R / C, which only feed outputs that are never stored: the columns between a plane's L and its pitch may hold anything (NaN
+// included); nothing is written behind column N.  The same holds for whichever operand is an activation plane: conv_plain passes the weights as A (their
+// rows zero-padded to lda by the packer, WeightStore::conv) and the plane as B, linear_tokmajor the plane as A (it may hold anything behind column M: those
+// columns feed only output rows >= M, never stored) and the zero-padded weights as B.
 struct ConvParams {
     const float* A = nullptr;  // [tap][K][lda]: k-major, m contiguous
     int lda = 0;
@@ -300,6 +307,11 @@ void conv_prof_add(int cfg, double flops, hipEvent_t e0, hipEvent_t e1);
 // ---------------------------------------------------------------------------------------------
 // Channels-last bf16 / split-bf16 convolution (conv_cl.hip): X[pos][C] f32 in HBM, weights pre-packed as MFMA fragments
 // ---------------------------------------------------------------------------------------------
+// Epilogue order: k-major output (out_km = 1; conv_cl_small.hip's is the same): v = acc + bias; v = act(v); v *= alpha; v += R; v *= beta; v += Y (accumulate);
+// v = mask ? v : 0.  Channels-last output (out_km = 0): v = acc + bias; v += R; v *= beta; v += Y; mask: NO activation and NO alpha there (the encoders' FFN
+// applies its ReLU as the next convolution's pre_slope = 0).
+// Pad contract: positions outside [0, NB) are staged as zero whatever the memory holds (k-major input: the columns NB .. pitch may hold anything, NaN
+// included); nothing is written behind position N / row M.
 struct ConvClParams {
     const float* X = nullptr;  // [NB][ldx]
     int ldx = 0, NB = 0;
@@ -413,6 +425,10 @@ struct BfsSplitK {
     unsigned* counters = nullptr;
     int ncounters = 0;
 };
+// Epilogue order (both forms of gemm_bfs_kernel's): v = acc + bias; v = act(v); v *= alpha; v += R; v *= beta; v = mask ? v : 0; then the f32 plane takes rows
+// < y_rows and the split copy rows >= ys_row0 of the SAME v.  No accumulate.
+// Pad contract: a column's result depends on that column of X alone, and a 16-byte piece that starts at a column < N may cover up to four pad columns, which
+// only feed outputs that are never stored: the columns N .. pitch of X's parts and of R may hold anything (NaN included); nothing is written behind column N.
 struct GemmBfsParams {
     BfsWeights W;
     SplitPlanes X;

@@ -363,6 +363,96 @@ int sbv2_debug_conv1d(int device, const float* x, const float* w, const float* b
     API_END
 }
 
+// ---- conv_plain / the encoders' FFN pair / linear_tokmajor with every argument the models pass (tests/test_gemm_conv_kernels.py): planes at the library's
+// pitch, NaN behind L in every input, outputs pre-filled with the sentinel (or the caller's previous contents under `accumulate`, NaN behind L), *stray =
+// the pad words of the outputs that the launch changed
+int sbv2_debug_conv_plain(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k, int64_t L, int64_t dilation,
+                          int64_t pad_l, int cl_parts, const uint8_t* mask, int64_t mask_div, int act, float pre_slope, const float* res, float alpha,
+                          float beta, int accumulate, float* y_inout, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && w && y_inout && cin >= 1 && cout >= 1 && k >= 1 && k <= kMaxTaps && dilation >= 1 && pad_l >= 0 && cl_parts >= 0 && cl_parts <= 3 &&
+                     mask_div >= 1 && act >= ACT_NONE && act <= ACT_TANH,
+                 "bad arguments");
+    Blob b = one_conv_blob(w, bias, {cout, cin, k}, cout);
+    WeightStore ws(b, cl_parts);
+    PackedConv pc = ws.conv("c");
+    DevPlane X(cin, L), Y(cout, L), R(res ? cout : 1, res ? L : 1);
+    X.put(x, true);
+    if (res) R.put(res, true);
+    if (accumulate) Y.put(y_inout, true);
+    else Y.fill(true);
+    DevMem dm(mask, mask ? (size_t)((L + mask_div - 1) / mask_div) : 0);
+    conv_plain(pc, X.P, Y.P, (int)dilation, (int)pad_l, mask ? dm.u8() : nullptr, (int)mask_div, nullptr, act, pre_slope, res ? &R.P : nullptr, alpha, beta,
+               accumulate);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = Y.get(y_inout, accumulate ? kNanWord : kSentinelWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_conv_ffn_cl(int device, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, int64_t H, int64_t F, int64_t k,
+                           int64_t L, const uint8_t* mask, const float* res, float* y, float* mid, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && w1 && w2 && y && mid && H >= 1 && F >= 1 && k >= 1 && k <= kMaxTaps && (k & 1) && L >= 1, "bad arguments");
+    Blob bl1 = one_conv_blob(w1, b1, {F, H, k}, F), bl2 = one_conv_blob(w2, b2, {H, F, k}, H);
+    WeightStore ws1(bl1, 2), ws2(bl2, 2);   // split-bf16 fragments, as the flow's encoder loads its FFN
+    PackedConv c1 = ws1.conv("c"), c2 = ws2.conv("c");
+    DevPlane X(H, L), Y(H, L), R(res ? H : 1, res ? L : 1);
+    X.put(x, true);
+    if (res) R.put(res, true);
+    Y.fill(true);
+    // the channels-last intermediate [L][F] (pitch F, as VitsModel::run_encoder allocates it) with guard words behind it
+    constexpr int64_t kGuard = 256;
+    const size_t nmid = (size_t)L * F;
+    DevMem dmid(sizeof(float) * (nmid + kGuard)), dm(mask, mask ? (size_t)L : 0);
+    HIP_CHECK(hipMemset(dmid.p, kCtxSentinel, sizeof(float) * (nmid + kGuard)));
+    const unsigned char* m = mask ? dm.u8() : nullptr;
+    SBV2_REQUIRE(conv_km_to_cl(c1, X.P, dmid.f(), (int)F, 1, (int)(k - 1) / 2, m, 1, nullptr),
+                 "conv_km_to_cl refused the shape (k >= 3 and a multiple of 16 output channels)");
+    SBV2_REQUIRE(conv_cl_to_km(c2, dmid.f(), (int)F, Y.P, 1, (int)(k - 1) / 2, m, 1, nullptr, 0.0f, res ? &R.P : nullptr),
+                 "conv_cl_to_km refused the shape (k >= 3 and a multiple of 16 input channels)");
+    HIP_CHECK(hipDeviceSynchronize());
+    int64_t bad = Y.get(y, kSentinelWord);
+    std::vector<uint32_t> h(nmid + kGuard);
+    HIP_CHECK(hipMemcpy(h.data(), dmid.p, 4 * h.size(), hipMemcpyDeviceToHost));
+    for (size_t e = nmid; e < nmid + kGuard; ++e) bad += h[e] != kSentinelWord;
+    for (int64_t c = 0; c < F; ++c)   // returned channel-major [F][L] like every other plane of the hooks
+        for (int64_t n = 0; n < L; ++n) std::memcpy(&mid[(size_t)c * L + n], &h[(size_t)n * F + c], 4);
+    if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_linear_tokmajor(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t L, int64_t ldy, float* y,
+                               int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(x && w && y && cin >= 1 && cout >= 1 && L >= 1 && ldy >= cout && ldy < (1 << 20), "bad arguments");
+    Blob b = one_conv_blob(w, bias, {cout, cin, 1}, cout);
+    WeightStore ws(b);
+    PackedConv pc = ws.conv("c");
+    DevPlane X(cin, L);
+    X.put(x, true);
+    // y [L][ldy] token-major: columns cout .. ldy of every row and the guard words behind the last row must keep the sentinel
+    constexpr int64_t kGuard = 256;
+    const size_t ny = (size_t)L * ldy;
+    DevMem dy(sizeof(float) * (ny + kGuard));
+    HIP_CHECK(hipMemset(dy.p, kCtxSentinel, sizeof(float) * (ny + kGuard)));
+    linear_tokmajor(pc, X.P, dy.f(), (int)ldy, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<uint32_t> h(ny + kGuard);
+    HIP_CHECK(hipMemcpy(h.data(), dy.p, 4 * h.size(), hipMemcpyDeviceToHost));
+    int64_t bad = 0;
+    for (int64_t n = 0; n < L; ++n) {
+        std::memcpy(y + (size_t)n * cout, &h[(size_t)n * ldy], 4 * (size_t)cout);
+        for (int64_t c = cout; c < ldy; ++c) bad += h[(size_t)n * ldy + c] != kSentinelWord;
+    }
+    for (size_t e = ny; e < ny + kGuard; ++e) bad += h[e] != kSentinelWord;
+    if (stray) *stray = bad;
+    API_END
+}
+
 int sbv2_debug_conv_transpose1d(int device, const float* x, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k,
                                 int64_t L, int64_t stride, int64_t padding, float pre_slope, float* y) {
     API_BEGIN
@@ -627,11 +717,26 @@ int sbv2_debug_set_resbranch(int on) { return set_resbranch(on); }
 
 // x2 / y2 (sbv2_debug_gemm_bfs_alt): a second input; the launches alternate between the two on ONE scratch buffer that is never cleared in between, so a
 // workgroup that read a stale partial sum (the other input's, left in its XCD's L2 by the previous launch) would show up in the result
+// ex (sbv2_debug_gemm_bfs_ex): the rest of conv_bfs' arguments, and the poison / sentinel / stray-count convention of the ops.h hooks: x and res hold NaN
+// in the columns N .. pitch (so do x's parts: split_planes converts the whole pitch), the f32 plane and the parts planes are pre-filled with the sentinel,
+// y returns the f32 plane and ys the recombined parts separately, *stray = the pad words of either (columns N .. pitch, and one guard row behind row M
+// of the plane and of every part) that the launch changed.
+struct BfsHookEx {
+    const uint8_t* mask = nullptr;
+    int64_t mask_div = 1;
+    float alpha = 1.0f, beta = 1.0f;
+    int64_t y_rows = -1, ys_row0 = 0;
+    int want_y = 1;
+    float* ys = nullptr;
+    int64_t* stray = nullptr;
+};
 static int debug_gemm_bfs_impl(int device, const float* x, const float* x2, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
-                               int parts, int act, int split_out, int64_t iters, float* y, float* y2, float* ms) {
+                               int parts, int act, int split_out, int64_t iters, float* y, float* y2, float* ms, const BfsHookEx* ex = nullptr) {
     API_BEGIN
     HIP_CHECK(hipSetDevice(device));
     SBV2_REQUIRE((parts == 2 || parts == 3 || parts == kPartsF16x3) && x && w && y && M >= 1 && N >= 4 && (N & 3) == 0 && (K & 15) == 0, "bad arguments");
+    SBV2_REQUIRE(!ex || ((ex->want_y || split_out) && (!split_out || ex->ys) && ex->mask_div >= 1 && ex->y_rows >= -1 && ex->ys_row0 >= 0 && !x2), "bad arguments");
+    const bool poison = ex != nullptr;
     Blob b = one_conv_blob(w, bias, {M, K, 1}, M);
     WeightStore ws(b);
     ws.set_bfs_parts(parts);
@@ -639,13 +744,21 @@ static int debug_gemm_bfs_impl(int device, const float* x, const float* x2, cons
     const int ld = round_up((int)N, 64);
     Plane X{nullptr, (int)K, (int)N, ld}, Y{nullptr, (int)M, (int)N, ld}, R{nullptr, (int)M, (int)N, ld};
     const size_t xs_bytes = (size_t)split_nplanes(parts) * K * ld * 2 + 64;
-    DevMem dx(sizeof(float) * K * ld), dy(sizeof(float) * M * ld), dr(sizeof(float) * M * ld), dxs(xs_bytes), dys((size_t)3 * M * ld * 2 + 64);
+    const int64_t Mg = M + (poison ? 1 : 0);   // poison: one guard row behind the f32 plane and behind EVERY part (a write one row past M lands there)
+    const size_t ys_bytes = (size_t)3 * Mg * ld * 2 + 64;
+    DevMem dx(sizeof(float) * K * ld), dy(sizeof(float) * Mg * ld), dr(sizeof(float) * M * ld), dxs(xs_bytes), dys(ys_bytes);
     X.p = dx.f();
     Y.p = dy.f();
     R.p = dr.f();
-    HIP_CHECK(hipMemset(X.p, 0, sizeof(float) * (size_t)K * ld));
+    HIP_CHECK(hipMemset(X.p, poison ? 0xFF : 0, sizeof(float) * (size_t)K * ld));
     HIP_CHECK(hipMemcpy2D(X.p, sizeof(float) * ld, x, sizeof(float) * N, sizeof(float) * N, K, hipMemcpyHostToDevice));
+    if (poison) {
+        HIP_CHECK(hipMemset(R.p, 0xFF, sizeof(float) * (size_t)M * ld));
+        HIP_CHECK(hipMemset(Y.p, kCtxSentinel, sizeof(float) * (size_t)Mg * ld));
+        HIP_CHECK(hipMemset(dys.p, kCtxSentinel, ys_bytes));
+    }
     if (res) HIP_CHECK(hipMemcpy2D(R.p, sizeof(float) * ld, res, sizeof(float) * N, sizeof(float) * N, M, hipMemcpyHostToDevice));
+    DevMem dmask(ex ? ex->mask : nullptr, ex && ex->mask ? (size_t)((N + ex->mask_div - 1) / ex->mask_div) : 0);
     SplitPlanes xs;
     xs.p = dxs.p;
     xs.parts = split_nplanes(parts);
@@ -672,7 +785,7 @@ static int debug_gemm_bfs_impl(int device, const float* x, const float* x2, cons
     ys.C = (int)M;
     ys.L = (int)N;
     ys.ld = ld;
-    ys.pstride = (int64_t)M * ld;
+    ys.pstride = (int64_t)Mg * ld;
     // split_out: 0 = f32 result only; 2 / 3 = the result is ALSO written as that many bf16 parts, and y returns their sum (what a consumer sees)
     // (scratch for the small-grid K split, as DeBERTa's forward provides it)
     constexpr size_t kWs = (size_t)48 << 20;   // (as BertModel::kSkWsBytes / kSkCounters)
@@ -685,7 +798,11 @@ static int debug_gemm_bfs_impl(int device, const float* x, const float* x2, cons
     sk.ncounters = 1024;
     int turn = 0;
     auto run = [&]() {
-        conv_bfs(pc, (x2 && (turn++ & 1)) ? xs2 : xs, &Y, split_out ? &ys : nullptr, nullptr, 1, nullptr, act, res ? &R : nullptr, 1.0f, 1.0f, -1, 0, &sk);
+        if (ex)
+            conv_bfs(pc, xs, ex->want_y ? &Y : nullptr, split_out ? &ys : nullptr, ex->mask ? dmask.u8() : nullptr, (int)ex->mask_div, nullptr, act,
+                     res ? &R : nullptr, ex->alpha, ex->beta, (int)ex->y_rows, (int)ex->ys_row0, &sk);
+        else
+            conv_bfs(pc, (x2 && (turn++ & 1)) ? xs2 : xs, &Y, split_out ? &ys : nullptr, nullptr, 1, nullptr, act, res ? &R : nullptr, 1.0f, 1.0f, -1, 0, &sk);
     };
     run();
     HIP_CHECK(hipDeviceSynchronize());
@@ -700,22 +817,34 @@ static int debug_gemm_bfs_impl(int device, const float* x, const float* x2, cons
         HIP_CHECK(hipDeviceSynchronize());
     }
     HIP_CHECK(hipMemcpy2D(y, sizeof(float) * N, Y.p, sizeof(float) * ld, sizeof(float) * N, M, hipMemcpyDeviceToHost));
+    int64_t bad = 0;
+    if (poison) {
+        std::vector<uint32_t> hy((size_t)Mg * ld);
+        HIP_CHECK(hipMemcpy(hy.data(), Y.p, 4 * hy.size(), hipMemcpyDeviceToHost));
+        for (int64_t m = 0; m < Mg; ++m)
+            for (int64_t n = m < M ? N : 0; n < ld; ++n) bad += hy[(size_t)m * ld + n] != kSentinelWord;
+    }
     if (split_out) {
         const int np = ys.parts;
-        std::vector<uint16_t> hs((size_t)np * M * ld);
+        std::vector<uint16_t> hs((size_t)np * Mg * ld);
         HIP_CHECK(hipMemcpy(hs.data(), ys.p, hs.size() * 2, hipMemcpyDeviceToHost));
+        if (poison)
+            for (int pp = 0; pp < np; ++pp)
+                for (int64_t m = 0; m < Mg; ++m)
+                    for (int64_t n = m < M ? N : 0; n < ld; ++n) bad += hs[((size_t)pp * Mg + m) * ld + n] != (uint16_t)(kSentinelWord & 0xFFFF);
+        if (ex) y = ex->ys;   // (the f32 plane went to the caller's y above)
         for (int64_t m = 0; m < M; ++m)
             for (int64_t n = 0; n < N; ++n) {
                 float acc = 0.f;
                 if (ys.f16) {
                     _Float16 hi, lo;
                     memcpy(&hi, &hs[(size_t)m * ld + n], 2);
-                    memcpy(&lo, &hs[((size_t)M + m) * ld + n], 2);
+                    memcpy(&lo, &hs[((size_t)Mg + m) * ld + n], 2);
                     y[(size_t)m * N + n] = (float)hi + (float)lo * (1.0f / kF16LoScale);
                     continue;
                 }
                 for (int pp = np - 1; pp >= 0; --pp) {
-                    const uint32_t u = (uint32_t)hs[((size_t)pp * M + m) * ld + n] << 16;
+                    const uint32_t u = (uint32_t)hs[((size_t)pp * Mg + m) * ld + n] << 16;
                     float f;
                     memcpy(&f, &u, 4);
                     acc += f;
@@ -723,7 +852,24 @@ static int debug_gemm_bfs_impl(int device, const float* x, const float* x2, cons
                 y[(size_t)m * N + n] = acc;
             }
     }
+    if (ex && ex->stray) *ex->stray = bad;
     API_END
+}
+
+int sbv2_debug_gemm_bfs_ex(int device, const float* x, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K, int parts, int act,
+                           int split_out, int64_t iters, const uint8_t* mask, int64_t mask_div, float alpha, float beta, int64_t y_rows, int64_t ys_row0,
+                           int want_y, float* y, float* ys, float* ms, int64_t* stray) {
+    BfsHookEx ex;
+    ex.mask = mask;
+    ex.mask_div = mask_div;
+    ex.alpha = alpha;
+    ex.beta = beta;
+    ex.y_rows = y_rows;
+    ex.ys_row0 = ys_row0;
+    ex.want_y = want_y;
+    ex.ys = ys;
+    ex.stray = stray;
+    return debug_gemm_bfs_impl(device, x, nullptr, w, bias, res, M, N, K, parts, act, split_out, iters, y, nullptr, ms, &ex);
 }
 
 int sbv2_debug_gemm_bfs(int device, const float* x, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,

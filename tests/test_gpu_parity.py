@@ -204,8 +204,9 @@ def _gemm_bfs(x, w, b, r, parts, act=0, split_out=0, iters=0):
 @pytest.mark.parametrize("K,M,N", [(16, 1, 4), (32, 29, 68), (48, 50, 132), (96, 192, 900), (192, 576, 2052), (1024, 1024, 68), (1024, 3072, 260),
                                    (4096, 1024, 132), (1024, 4096, 2112), (64, 130, 388), (1024, 1024, 2112), (192, 192, 28704)])
 def test_gemm_bfs_kernel(K, M, N):
-    """The split-bf16 1x1 GEMM on k-major planes (gemm_bfs.hip: pre-split operands, LDS-DMA ring, transposing LDS reads), every tile / ring
-    configuration the launcher can pick, against an f64 product of the SAME f32 inputs.  Tolerances: bf16x3 drops the lo*lo term
+    """The split-bf16 1x1 GEMM on k-major planes (gemm_bfs.hip: pre-split operands, LDS-DMA ring, transposing LDS reads) at the models' shapes, against an
+    f64 product of the SAME f32 inputs (tests/test_gemm_conv_kernels.py names the instantiation of every case, checks against launch_gemm_bfs' source that
+    each one is reached, and runs them with the models' epilogues).  Tolerances: bf16x3 drops the lo*lo term
     (2^-16 relative per product: ~2e-5 on O(1) sums), bf16x6 only 2^-24 terms (f32-grade: compared with numpy's own f32 product)."""
     rng = np.random.default_rng(K + M + N)
     x = rng.standard_normal((K, N)).astype(np.float32)
