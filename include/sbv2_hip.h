@@ -115,6 +115,24 @@ void sbv2_pipeline_destroy(sbv2_pipeline* p);
 int sbv2_pipeline_run(sbv2_pipeline* p, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
                       const int64_t* word2ph, int64_t* pcm_lens);
 
+/* ---- new: options per utterance.  Every array is [n] of the batch; a NULL array = the batch's scalar for every row.  Row u's two noise streams
+ * are keyed by (noise_seed[u], noise_index[u]): a request's sentence j that is given the request's seed and index j draws the noise it draws
+ * when the request runs alone, whatever shares the run with it.  noise_index NULL = the row number.  Refused before any GPU work, with the
+ * row named in sbv2_last_error: a non-finite or <= 0 length_scale, an sdp_ratio outside [0, 1], a negative or non-finite noise scale, a
+ * negative noise_index (or one >= 2^30). */
+typedef struct sbv2_utt_options {
+    const float* sdp_ratio;
+    const float* length_scale;
+    const float* noise_scale;
+    const float* noise_scale_w;
+    const uint64_t* noise_seed;
+    const int64_t* noise_index;
+} sbv2_utt_options;
+/* sbv2_vits_synthesize_batch / sbv2_pipeline_run with per-utterance options; opts == NULL is exactly the call without them. */
+int sbv2_vits_synthesize_batch_opts(sbv2_vits* h, const sbv2_batch* batch, const sbv2_utt_options* opts, int64_t* pcm_lens);
+int sbv2_pipeline_run_opts(sbv2_pipeline* p, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids,
+                           const int64_t* s_lens, const int64_t* word2ph, int64_t* pcm_lens);
+
 /* Calls are pipelined: call n runs on execution context n % SBV2_PIPELINE_DEPTH (default 2; own stream + workspace, shared
  * weights) and returns once its kernels are enqueued, so the latency-bound DeBERTa / text / flow part of the next batch overlaps
  * the HiFi-GAN kernels of this one.  Every run gets a TICKET (1, 2, 3, ...: the call number); its results stay available until the
@@ -253,6 +271,25 @@ int sbv2_pipeline_fetch_pcm_limited(sbv2_pipeline* p, int64_t ticket, const sbv2
 int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const sbv2_limiter* lim,
                                      const int64_t* place, int64_t joined_len, uint8_t* dst, int64_t capacity_bytes, int64_t* out_bytes,
                                      double* stats);
+/* ---- new: ONE signal from a subset of a run's rows, through the same output chain as the six formatted fetches above: a run that holds
+ * several requests hands each of them its own joined, resampled, gain-staged and encoded signal.  The listed rows are laid on a silent timeline
+ * of joined_len native samples, row utts[i] starting at place[i].  Refused (nothing written): a row outside [0, n) or listed twice, a placement
+ * out of bounds or overlapping, both loudness and limiter given, a stale ticket, a result longer than capacity_bytes, and whatever the
+ * corresponding joined fetch refuses in fmt / loudness / limiter.  out_count: samples (flac = 0) or bytes (flac = 1); stats: NULL, or 3
+ * (loudness) / 6 (limiter) doubles.  The run's PCM is only read: any number of requests may be fetched from one ticket, in any order. */
+typedef struct sbv2_fetch_request {
+    const int32_t* utts;         /* [n_utts] rows of the run that form this signal */
+    int32_t n_utts;
+    const int64_t* place;        /* [n_utts] */
+    int64_t joined_len;
+    const sbv2_pcm_format* fmt;
+    const sbv2_loudness* loudness;   /* at most one of loudness / limiter non-NULL */
+    const sbv2_limiter* limiter;
+    int32_t flac;                /* 0 = PCM bytes in fmt's encoding, 1 = one FLAC stream (fmt->encoding must be 1) */
+} sbv2_fetch_request;
+int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
+                                int64_t* out_count, double* stats);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,
@@ -509,6 +546,9 @@ int sbv2_debug_spline_inverse(int device, const float* params, const float* z, c
 int sbv2_debug_durations(int device, const float* sdp, const float* dp, const uint8_t* mask, int64_t L, float ratio, float length_scale, float* logw,
                          int32_t* dur, int64_t* stray);
 /* affine_reverse on z [2][L] in place: (z - m) * exp(-logs), or * scale when logs is null */
+/* durations over a TEXT layout of nutt segments, row u with ratio[u] / length_scale[u]; sdp, dp, mask, logw, dur: [L of that layout] */
+int sbv2_debug_durations_rows(int device, const float* sdp, const float* dp, const uint8_t* mask, const int64_t* lens, int nutt, const float* ratio,
+                              const float* length_scale, float* logw, int32_t* dur, int64_t* stray);
 int sbv2_debug_affine_reverse(int device, const float* z, const float* m, const float* logs, const float* scale, const uint8_t* mask, int64_t L,
                               float* z_out, int64_t* stray);
 int sbv2_debug_convflow_pre(int device, const float* z0, const float* w, const float* b, const float* cond, const uint8_t* mask, int64_t C, int64_t L,
@@ -519,6 +559,11 @@ int sbv2_debug_noise_fill(int device, const int64_t* lens, int nutt, int kind, c
 /* expand_frames: m_p, logs_p [C][Lt]; tok_of_frame [L of the frame layout of lens] (text column or -1); y [C][L] */
 int sbv2_debug_expand_frames(int device, const float* m_p, const float* logs_p, int64_t C, int64_t Lt, const int32_t* tok_of_frame, const int64_t* lens,
                              int nutt, const int32_t* seg_utt, uint64_t seed, float noise_scale, float* y, int64_t* stray);
+/* noise_fill / expand_frames with row u's own (seed[u], index[u], scale[u]); the two hooks above are these with one seed and scale for every row */
+int sbv2_debug_noise_fill_rows(int device, const int64_t* lens, int nutt, int kind, const uint64_t* seed, const int32_t* index, int stream_id,
+                               const float* scale, int64_t rows, float* y, int64_t* stray);
+int sbv2_debug_expand_frames_rows(int device, const float* m_p, const float* logs_p, int64_t C, int64_t Lt, const int32_t* tok_of_frame, const int64_t* lens,
+                                  int nutt, const uint64_t* seed, const int32_t* index, const float* noise_scale, float* y, int64_t* stray);
 /* conv_post_tanh (cl = 0) / conv_post_tanh_cl (cl = 1): x [C][L up] = the whole gapped plane of the frame layout of lens at `up` samples per frame,
    w [C][k], slope 0.01; pcm = the utterances' samples back to back (lens[i] up each) */
 int sbv2_debug_conv_post_tanh(int device, const float* x, const float* w, int64_t C, int64_t k, const int64_t* lens, int nutt, int64_t up, int cl,

@@ -34,6 +34,18 @@ class Sbv2Limiter(C.Structure):
     _fields_ = [("target_lufs", C.c_double), ("true_peak_max_dbtp", C.c_double), ("max_reduction_db", C.c_double), ("reserved", C.c_double)]
 
 
+class Sbv2UttOptions(C.Structure):
+    """struct sbv2_utt_options (include/sbv2_hip.h)."""
+    _fields_ = [("sdp_ratio", f32p), ("length_scale", f32p), ("noise_scale", f32p), ("noise_scale_w", f32p),
+                ("noise_seed", C.POINTER(C.c_uint64)), ("noise_index", i64p)]
+
+
+class Sbv2FetchRequest(C.Structure):
+    """struct sbv2_fetch_request (include/sbv2_hip.h)."""
+    _fields_ = [("utts", C.POINTER(C.c_int32)), ("n_utts", C.c_int32), ("place", i64p), ("joined_len", C.c_int64),
+                ("fmt", C.POINTER(Sbv2PcmFormat)), ("loudness", C.POINTER(Sbv2Loudness)), ("limiter", C.POINTER(Sbv2Limiter)), ("flac", C.c_int32)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -67,6 +79,9 @@ SYMBOLS = {
     "sbv2_pipeline_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "sbv2_pipeline_destroy": (None, [C.c_void_p]),
     "sbv2_pipeline_run": (C.c_int, [C.c_void_p, C.POINTER(Sbv2Batch), i64p, i64p, i64p, i64p]),
+    "sbv2_vits_synthesize_batch_opts": (C.c_int, [C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p]),
+    "sbv2_pipeline_run_opts": (C.c_int, [C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p, i64p, i64p, i64p]),
+    "sbv2_pipeline_fetch_request": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double)]),
     "sbv2_pipeline_sync": (C.c_int, [C.c_void_p]),
     "sbv2_pipeline_fetch_pcm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
     "sbv2_pipeline_fetch_pcm_ticket": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),
@@ -170,11 +185,16 @@ SYMBOLS = {
                                               i64p]),
     "sbv2_debug_spline_inverse": (C.c_int, [C.c_int, f32p, f32p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_int, f32p, i64p]),
     "sbv2_debug_durations": (C.c_int, [C.c_int, f32p, f32p, C.c_void_p, C.c_int64, C.c_float, C.c_float, f32p, C.POINTER(C.c_int32), i64p]),
+    "sbv2_debug_durations_rows": (C.c_int, [C.c_int, f32p, f32p, C.c_void_p, i64p, C.c_int, f32p, f32p, f32p, C.POINTER(C.c_int32), i64p]),
     "sbv2_debug_affine_reverse": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_void_p, C.c_int64, f32p, i64p]),
     "sbv2_debug_convflow_pre": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_void_p, C.c_int64, C.c_int64, f32p, i64p]),
     "sbv2_debug_noise_fill": (C.c_int, [C.c_int, i64p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_uint64, C.c_int, C.c_float, C.c_int64, f32p, i64p]),
     "sbv2_debug_expand_frames": (C.c_int, [C.c_int, f32p, f32p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), i64p, C.c_int, C.POINTER(C.c_int32), C.c_uint64,
                                            C.c_float, f32p, i64p]),
+    "sbv2_debug_noise_fill_rows": (C.c_int, [C.c_int, i64p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int, f32p, C.c_int64, f32p,
+                                             i64p]),
+    "sbv2_debug_expand_frames_rows": (C.c_int, [C.c_int, f32p, f32p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), i64p, C.c_int, C.POINTER(C.c_uint64),
+                                                C.POINTER(C.c_int32), f32p, f32p, i64p]),
     "sbv2_debug_conv_post_tanh": (C.c_int, [C.c_int, f32p, f32p, C.c_int64, C.c_int64, i64p, C.c_int, C.c_int64, C.c_int, f32p, i64p]),
     "sbv2_debug_linear_vec": (C.c_int, [C.c_int, f32p, f32p, C.c_int64, C.c_int64, f32p, C.c_int64, f32p]),
     "sbv2_debug_gather_rows": (C.c_int, [C.c_int, f32p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64, f32p]),

@@ -1,4 +1,5 @@
 // extern "C" boundary of libsbv2_hip.so (see include/sbv2_hip.h for what each entry point replaces).
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -25,6 +26,34 @@ VitsBatch to_batch(const sbv2_batch* b) {
     v.seed = b->noise_seed;
     v.forced_durations = b->forced_durations;
     return v;
+}
+
+// The per-row arrays of sbv2_utt_options onto the batch (host pointers, read by forward()); every check here, before any GPU work.
+static void apply_utt_options(VitsBatch* v, const sbv2_utt_options* o) {
+    if (!o) return;
+    const auto row = [](int u) { return " of row " + std::to_string(u); };
+    for (int u = 0; u < v->n; ++u) {
+        if (o->length_scale)
+            SBV2_REQUIRE(std::isfinite(o->length_scale[u]) && o->length_scale[u] > 0.f,
+                         "length_scale" + row(u) + " must be finite and > 0: " + std::to_string(o->length_scale[u]));
+        if (o->sdp_ratio)
+            SBV2_REQUIRE(o->sdp_ratio[u] >= 0.f && o->sdp_ratio[u] <= 1.f, "sdp_ratio" + row(u) + " must be in [0, 1]: " + std::to_string(o->sdp_ratio[u]));
+        if (o->noise_scale)
+            SBV2_REQUIRE(std::isfinite(o->noise_scale[u]) && o->noise_scale[u] >= 0.f,
+                         "noise_scale" + row(u) + " must be finite and >= 0: " + std::to_string(o->noise_scale[u]));
+        if (o->noise_scale_w)
+            SBV2_REQUIRE(std::isfinite(o->noise_scale_w[u]) && o->noise_scale_w[u] >= 0.f,
+                         "noise_scale_w" + row(u) + " must be finite and >= 0: " + std::to_string(o->noise_scale_w[u]));
+        if (o->noise_index)
+            SBV2_REQUIRE(o->noise_index[u] >= 0 && o->noise_index[u] < (1 << 30),
+                         "noise_index" + row(u) + " must be in [0, 2^30): " + std::to_string(o->noise_index[u]));
+    }
+    v->row_sdp_ratio = o->sdp_ratio;
+    v->row_length_scale = o->length_scale;
+    v->row_noise_scale = o->noise_scale;
+    v->row_noise_scale_w = o->noise_scale_w;
+    v->row_seed = o->noise_seed;
+    v->row_index = o->noise_index;
 }
 
 extern "C" {
@@ -78,14 +107,22 @@ int64_t sbv2_vits_style_dim(const sbv2_vits* h) { return h ? h->m->cfg().style_d
 int sbv2_vits_decoder_mode(const sbv2_vits* h) { return h ? h->m->decoder_mode() : -1; }
 int64_t sbv2_vits_workspace_bytes(const sbv2_vits* h) { return h ? (int64_t)h->m->workspace_bytes() : -1; }
 
-int sbv2_vits_synthesize_batch(sbv2_vits* h, const sbv2_batch* batch, int64_t* pcm_lens) {
+int sbv2_vits_synthesize_batch_opts(sbv2_vits* h, const sbv2_batch* batch, const sbv2_utt_options* opts, int64_t* pcm_lens) {
     API_BEGIN
-    SBV2_REQUIRE(h && pcm_lens, "bad arguments");
     VitsBatch v = to_batch(batch);
+    apply_utt_options(&v, opts);
+    SBV2_REQUIRE(h && pcm_lens, "bad arguments");
     SBV2_REQUIRE(v.bert_host, "sbv2_batch.bert is required here");
     h->m->forward(v);
     for (int i = 0; i < v.n; ++i) pcm_lens[i] = h->m->pcm_lens()[i];
     API_END
+}
+int sbv2_vits_synthesize_batch(sbv2_vits* h, const sbv2_batch* batch, int64_t* pcm_lens) {
+    if (!h || !pcm_lens) {   // (checked before the batch, as ever)
+        set_last_error("bad arguments");
+        return 1;
+    }
+    return sbv2_vits_synthesize_batch_opts(h, batch, nullptr, pcm_lens);
 }
 int sbv2_vits_fetch_pcm(sbv2_vits* h, float* pcm, int64_t capacity) {
     API_BEGIN
@@ -252,16 +289,25 @@ extern "C" {
 // latency-bound part of batch n+1 (DeBERTa, text encoder, duration predictors, flow: ~1300 small launches, ~55 ms whatever the
 // batch size) executes beside the throughput-bound HiFi-GAN kernels of batch n.  A call returns once its kernels are enqueued (the
 // host only waits for the batch's own integer durations); results are collected with sbv2_pipeline_wait / _fetch_pcm by ticket.
-int sbv2_pipeline_run(sbv2_pipeline* p, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
-                      int64_t* pcm_lens) {
+int sbv2_pipeline_run_opts(sbv2_pipeline* p, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids, const int64_t* s_lens,
+                           const int64_t* word2ph, int64_t* pcm_lens) {
     API_BEGIN
+    VitsBatch v = to_batch(batch);
+    apply_utt_options(&v, opts);
     SBV2_REQUIRE(p && token_ids && s_lens && word2ph && pcm_lens, "bad arguments");
-    const VitsBatch v = to_batch(batch);
     const int ctx = (int)(p->calls % p->contexts());
     ++p->calls;
     pipeline_run_one(p->bm(ctx), p->vm(ctx), v, token_ids, s_lens, word2ph);
     for (int i = 0; i < v.n; ++i) pcm_lens[i] = p->vm(ctx).pcm_lens()[i];
     API_END
+}
+int sbv2_pipeline_run(sbv2_pipeline* p, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
+                      int64_t* pcm_lens) {
+    if (!p || !token_ids || !s_lens || !word2ph || !pcm_lens) {   // (checked before the batch, as ever)
+        set_last_error("bad arguments");
+        return 1;
+    }
+    return sbv2_pipeline_run_opts(p, batch, nullptr, token_ids, s_lens, word2ph, pcm_lens);
 }
 
 int64_t sbv2_pipeline_last_ticket(sbv2_pipeline* p) { return p ? p->calls : -1; }
@@ -328,8 +374,9 @@ int sbv2_pcm_format_taps(int32_t sample_rate, float* h, int64_t cap, int64_t* le
 
 // The signals of a formatted fetch: one per utterance (place == NULL), or the run's utterances on one joined timeline.  outs = output samples
 // of each signal; the result is `total` samples.
-static void format_layout(const PcmFmtSpec& spec, VitsModel& vm, const int64_t* place, int64_t joined_len, std::vector<FmtPiece>* pieces,
-                          std::vector<FmtSignal>* sig, std::vector<int64_t>* outs, int64_t* total) {
+// utts != NULL: the joined timeline holds those n_utts rows only, place[k] belonging to row utts[k] (sbv2_pipeline_fetch_request).
+static void format_layout(const PcmFmtSpec& spec, VitsModel& vm, const int32_t* utts, int n_utts, const int64_t* place, int64_t joined_len,
+                          std::vector<FmtPiece>* pieces, std::vector<FmtSignal>* sig, std::vector<int64_t>* outs, int64_t* total) {
     const std::vector<int64_t>& lens = vm.pcm_lens();
     const std::vector<int64_t>& offs = vm.pcm_offs();
     const int n = (int)lens.size();
@@ -346,18 +393,28 @@ static void format_layout(const PcmFmtSpec& spec, VitsModel& vm, const int64_t* 
         return;
     }
     SBV2_REQUIRE(joined_len >= 0, "joined_len must be >= 0");
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) {
-        order[i] = i;
-        SBV2_REQUIRE(place[i] >= 0 && place[i] + lens[i] <= joined_len,
-                     "placement of utterance " + std::to_string(i) + " (" + std::to_string(place[i]) + " + " + std::to_string(lens[i]) +
+    const int m = utts ? n_utts : n;   // entry k of place belongs to row row(k)
+    const auto row = [&](int k) { return utts ? (int)utts[k] : k; };
+    if (utts) {
+        std::vector<char> seen(n, 0);
+        for (int k = 0; k < m; ++k) {
+            SBV2_REQUIRE(utts[k] >= 0 && utts[k] < n, "row " + std::to_string(utts[k]) + " is outside the run's " + std::to_string(n) + " utterances");
+            SBV2_REQUIRE(!seen[utts[k]], "row " + std::to_string(utts[k]) + " is listed twice");
+            seen[utts[k]] = 1;
+        }
+    }
+    std::vector<int> order(m);
+    for (int k = 0; k < m; ++k) {
+        order[k] = k;
+        SBV2_REQUIRE(place[k] >= 0 && place[k] + lens[row(k)] <= joined_len,
+                     "placement of utterance " + std::to_string(row(k)) + " (" + std::to_string(place[k]) + " + " + std::to_string(lens[row(k)]) +
                          " samples) is outside the joined timeline of " + std::to_string(joined_len) + " samples");
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return place[a] < place[b]; });
-    for (int r = 0; r < n; ++r) {
-        const int i = order[r];
-        if (r) SBV2_REQUIRE(place[order[r - 1]] + lens[order[r - 1]] <= place[i], "placements of utterances overlap on the joined timeline");
-        if (lens[i]) pieces->push_back(FmtPiece{pcm + offs[i], place[i], lens[i]});
+    for (int r = 0; r < m; ++r) {
+        const int k = order[r], i = row(k);
+        if (r) SBV2_REQUIRE(place[order[r - 1]] + lens[row(order[r - 1])] <= place[k], "placements of utterances overlap on the joined timeline");
+        if (lens[i]) pieces->push_back(FmtPiece{pcm + offs[i], place[k], lens[i]});
     }
     *total = pcm_format_out_len(spec, joined_len);
     sig->push_back(FmtSignal{0, *total, 0, 0, (int32_t)pieces->size()});
@@ -388,8 +445,10 @@ static PcmFmtSpec fetch_spec(const sbv2_pcm_format* fmt, bool gain_stage, Sink s
 // check first (format, gain options, ticket, placement, PCM capacity), then the formatter's launches with the gain stage between the
 // resampler and the quantiser, then the sink.  out_counts: samples (PCM) or bytes (FLAC) of each signal; stats (may be NULL): the gain
 // stage's 3 or 6 doubles per signal.
+// utts (with place): the one signal of those rows only.
 static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
-                            int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats) {
+                            int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats,
+                            const int32_t* utts = nullptr, int n_utts = 0) {
     const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
     const LoudnessSpec ln = gain.kind == FetchGain::kLoudness ? loudness_spec(gain.ln) : LoudnessSpec();
     const LimiterSpec lim = gain.kind == FetchGain::kLimiter ? limiter_spec(gain.lim) : LimiterSpec();
@@ -399,7 +458,7 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
     std::vector<FmtSignal> sig;
     std::vector<int64_t> outs, flac_bytes;   // per signal: samples, bytes of its FLAC stream
     int64_t total = 0;
-    format_layout(spec, vm, place, joined_len, &pieces, &sig, &outs, &total);
+    format_layout(spec, vm, utts, n_utts, place, joined_len, &pieces, &sig, &outs, &total);
     const int64_t pcm_bytes = total * spec.bytes();
     if (sink == Sink::kPcm)   // (the FLAC sink checks its capacity after encoding, when the sizes are known)
         SBV2_REQUIRE(capacity_bytes >= pcm_bytes,
@@ -499,6 +558,22 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
     API_BEGIN
     SBV2_REQUIRE(p && dst && out_bytes, "bad arguments");
     fetch_formatted(p, ticket, fmt, FetchGain{FetchGain::kLimiter, nullptr, lim}, place, joined_len, Sink::kFlac, dst, capacity_bytes, out_bytes, stats);
+    API_END
+}
+
+int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes, int64_t* out_count,
+                                double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(req && req->n_utts >= 0 && (req->n_utts == 0 || (req->utts && req->place)), "bad fetch request");
+    SBV2_REQUIRE(!(req->loudness && req->limiter), "a fetch request takes a loudness target or a limiter, not both");
+    SBV2_REQUIRE(p && dst && out_count, "bad arguments");
+    const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter}
+                           : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr}
+                                           : FetchGain();
+    static const int32_t no_rows[1] = {0};
+    static const int64_t no_place[1] = {0};
+    fetch_formatted(p, ticket, req->fmt, gain, req->n_utts ? req->place : no_place, req->joined_len, req->flac ? Sink::kFlac : Sink::kPcm, dst,
+                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts);
     API_END
 }
 

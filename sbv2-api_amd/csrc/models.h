@@ -289,6 +289,14 @@ struct VitsBatch {
     const int64_t* forced_durations = nullptr;  // concatenated, optional
     int utt0 = 0;                               // index of the first utterance in the caller's batch (noise stream keys) ...
     const int64_t* utt_ids = nullptr;           // ... or, for an arbitrary subset (a shard dealt to this GPU), every utterance's index
+    // Optional per-row options, host arrays [n]; a null array = the scalar above for every row (row_index null = utt_ids / utt0 + u).
+    // forward() broadcasts the scalars into one RowOpts record per row either way: the kernels know rows only.
+    const float* row_sdp_ratio = nullptr;
+    const float* row_length_scale = nullptr;
+    const float* row_noise_scale = nullptr;
+    const float* row_noise_scale_w = nullptr;
+    const uint64_t* row_seed = nullptr;
+    const int64_t* row_index = nullptr;
     hipStream_t after_stream = nullptr;         // when set, the forward's kernels wait for the work queued on this stream
     bool skip_decoder = false;                  // stop after the flow (streaming: the decoder then runs chunk by chunk, stream_*)
 };

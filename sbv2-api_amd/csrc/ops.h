@@ -72,12 +72,21 @@ void swap_rows(float* a, float* b, int L, hipStream_t s);
 void flip_channels(Plane in, Plane out, hipStream_t s);
 void affine_reverse(float* z0, float* z1, const float* m, const float* logs, const float* scale, const unsigned char* mask, int L,
                     hipStream_t s);   // (x - m) * exp(-logs), or * scale when logs is null (exp(-logs) folded into the weight file)
-void durations(const float* sdp, const float* dp, float ratio, float length_scale, const unsigned char* mask, int L,
+// The synthesis options of one row (utterance) of a batch, [n] on the device; the kernels below reach a column's record through seg_of.
+// (seed, index) key the row's two noise streams: noise_key(seed, index, stream).
+struct RowOpts {
+    uint64_t seed;
+    int index;
+    float sdp_ratio, length_scale, noise_scale, noise_scale_w;
+    int pad_;
+};
+static_assert(sizeof(RowOpts) == 32, "RowOpts is one 32-byte record");
+void durations(const float* sdp, const float* dp, const int* seg_of, const RowOpts* rows, const unsigned char* mask, int L,
                float* logw, int* dur, hipStream_t s);
-void noise_fill(float* out, int ld, int rows, const int* seg_of, const int* seg_start, const int* seg_len, const int* seg_utt, int L,
-                uint64_t seed, int stream_id, float scale, hipStream_t s);
+void noise_fill(float* out, int ld, int rows, const int* seg_of, const int* seg_start, const int* seg_len, const RowOpts* opts, int L,
+                int stream_id, hipStream_t s);   // scaled by the row's noise_scale_w
 void expand_frames(Plane m_p, Plane logs_p, const int* tok_of_frame, const int* seg_of, const int* seg_start,
-                   const int* seg_len, const int* seg_utt, uint64_t seed, float noise_scale, Plane out, hipStream_t s);
+                   const int* seg_len, const RowOpts* opts, Plane out, hipStream_t s);   // prior noise scaled by the row's noise_scale
 // out[c][j] = in[c][col0 + j] or 0 outside the plane; mask[j] = 1 where the column exists (the chunk window of the streaming decoder)
 void window_cols(Plane in, int col0, Plane out, unsigned char* mask, hipStream_t s);
 // dst[tab[3i + 1] + e] = src[tab[3i] + e] for e < tab[3i + 2], i < n (device table)

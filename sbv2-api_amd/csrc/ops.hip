@@ -738,18 +738,27 @@ void affine_reverse(float* z0, float* z1, const float* m, const float* logs, con
     hipLaunchKernelGGL(k_affine_reverse, dim3((L + 255) / 256), dim3(256), 0, s, z0, z1, m, logs, scale, mask, L);
 }
 
-// w_ceil = ceil(exp(logw) * mask * length_scale)   (SynthesizerTrn.infer)
-__global__ void k_durations(const float* sdp, const float* dp, float ratio, float length_scale, const unsigned char* mask, int L,
+// w_ceil = ceil(exp(logw) * mask * length_scale)   (SynthesizerTrn.infer), with the sdp / dp mix and the length scale of the column's own row:
+// rows[seg_of[n]], read once per thread.  A wave's columns lie in one segment unless it straddles a gap, so the address is wave-uniform.
+__global__ void k_durations(const float* sdp, const float* dp, const int* seg_of, const RowOpts* rows, const unsigned char* mask, int L,
                             float* logw, int* dur) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= L) return;
+    const int sg = seg_of[n];
+    if (sg < 0 || !mask[n]) {
+        logw[n] = 0.f;
+        dur[n] = 0;
+        return;
+    }
+    const RowOpts o = rows[sg];   // the record, once
+    const float ratio = o.sdp_ratio, length_scale = o.length_scale;
     const float lw = sdp[n] * ratio + dp[n] * (1.0f - ratio);
-    logw[n] = mask[n] ? lw : 0.f;
-    dur[n] = mask[n] ? (int)ceilf(expf(lw) * length_scale) : 0;
+    logw[n] = lw;
+    dur[n] = (int)ceilf(expf(lw) * length_scale);
 }
-void durations(const float* sdp, const float* dp, float ratio, float length_scale, const unsigned char* mask, int L, float* logw,
+void durations(const float* sdp, const float* dp, const int* seg_of, const RowOpts* rows, const unsigned char* mask, int L, float* logw,
                int* dur, hipStream_t s) {
-    hipLaunchKernelGGL(k_durations, dim3((L + 255) / 256), dim3(256), 0, s, sdp, dp, ratio, length_scale, mask, L, logw, dur);
+    hipLaunchKernelGGL(k_durations, dim3((L + 255) / 256), dim3(256), 0, s, sdp, dp, seg_of, rows, mask, L, logw, dur);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -772,30 +781,36 @@ __device__ __forceinline__ uint64_t noise_key(uint64_t seed, int utt, int stream
     return seed + (uint64_t)(2 * utt + stream) * 0x9E3779B97F4A7C15ull;
 }
 
-// seg_utt[sg] = index of segment sg's utterance in the CALLER's batch (the noise streams are keyed by it, so a shard of a batch that was
-// dealt to another GPU draws exactly the noise the whole batch would have drawn on one GPU)
-__global__ void k_noise_fill(float* out, int ld, int rows, const int* seg_of, const int* seg_start, const int* seg_len, const int* seg_utt, int L,
-                             uint64_t seed, int stream_id, float scale) {
+// rows[sg] = the options of segment sg's utterance.  Its noise streams are keyed by (rows[sg].seed, rows[sg].index, stream): index is the
+// utterance's number in the CALLER's batch or request, so a shard of a batch that was dealt to another GPU, or a request that shares a run
+// with others, draws exactly the noise it would have drawn alone.  The record is read through the segment number the kernels need anyway
+// for seg_start / seg_len, once per thread into locals: the address is wave-uniform except in a wave that straddles a gap (the cost of that
+// load is argued from the access pattern, not measured with a counter).
+__global__ void k_noise_fill(float* out, int ld, int rows, const int* seg_of, const int* seg_start, const int* seg_len, const RowOpts* opts, int L,
+                             int stream_id) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     const int r = blockIdx.y;
     if (n >= L) return;
     const int sg = seg_of[n];
     float v = 0.f;
-    if (sg >= 0 && scale != 0.f) {
-        const uint64_t e = (uint64_t)r * seg_len[sg] + (n - seg_start[sg]);
-        v = hash_normal(noise_key(seed, seg_utt[sg], stream_id), e) * scale;
+    if (sg >= 0) {
+        const RowOpts o = opts[sg];   // the record, once
+        const float scale = o.noise_scale_w;
+        if (scale != 0.f) {
+            const uint64_t e = (uint64_t)r * seg_len[sg] + (n - seg_start[sg]);
+            v = hash_normal(noise_key(o.seed, o.index, stream_id), e) * scale;
+        }
     }
     out[(size_t)r * ld + n] = v;
 }
-void noise_fill(float* out, int ld, int rows, const int* seg_of, const int* seg_start, const int* seg_len, const int* seg_utt, int L,
-                uint64_t seed, int stream_id, float scale, hipStream_t s) {
-    hipLaunchKernelGGL(k_noise_fill, dim3((L + 255) / 256, rows), dim3(256), 0, s, out, ld, rows, seg_of, seg_start, seg_len, seg_utt, L, seed,
-                       stream_id, scale);
+void noise_fill(float* out, int ld, int rows, const int* seg_of, const int* seg_start, const int* seg_len, const RowOpts* opts, int L,
+                int stream_id, hipStream_t s) {
+    hipLaunchKernelGGL(k_noise_fill, dim3((L + 255) / 256, rows), dim3(256), 0, s, out, ld, rows, seg_of, seg_start, seg_len, opts, L, stream_id);
 }
 
-// generate_path + the two matmuls + prior sampling: z_p[c][y] = m_p[c][tok(y)] + randn * exp(logs_p[c][tok(y)]) * noise_scale
+// generate_path + the two matmuls + prior sampling: z_p[c][y] = m_p[c][tok(y)] + randn * exp(logs_p[c][tok(y)]) * noise_scale of y's row
 __global__ void k_expand_frames(Plane m_p, Plane logs_p, const int* tok_of_frame, const int* seg_of, const int* seg_start,
-                                const int* seg_len, const int* seg_utt, uint64_t seed, float noise_scale, Plane out) {
+                                const int* seg_len, const RowOpts* opts, Plane out) {
     const int y = blockIdx.x * 256 + threadIdx.x;
     const int c = blockIdx.y;
     if (y >= out.L) return;
@@ -803,18 +818,20 @@ __global__ void k_expand_frames(Plane m_p, Plane logs_p, const int* tok_of_frame
     float v = 0.f;
     if (tok >= 0) {
         v = m_p.p[(size_t)c * m_p.ld + tok];
+        const int sg = seg_of[y];
+        const RowOpts o = opts[sg];   // the record, once
+        const float noise_scale = o.noise_scale;
         if (noise_scale != 0.f) {
-            const int sg = seg_of[y];
             const uint64_t e = (uint64_t)c * seg_len[sg] + (y - seg_start[sg]);
-            v += hash_normal(noise_key(seed, seg_utt[sg], 1), e) * noise_scale * expf(logs_p.p[(size_t)c * logs_p.ld + tok]);
+            v += hash_normal(noise_key(o.seed, o.index, 1), e) * noise_scale * expf(logs_p.p[(size_t)c * logs_p.ld + tok]);
         }
     }
     out.p[(size_t)c * out.ld + y] = v;
 }
 void expand_frames(Plane m_p, Plane logs_p, const int* tok_of_frame, const int* seg_of, const int* seg_start, const int* seg_len,
-                   const int* seg_utt, uint64_t seed, float noise_scale, Plane out, hipStream_t s) {
+                   const RowOpts* opts, Plane out, hipStream_t s) {
     hipLaunchKernelGGL(k_expand_frames, dim3((out.L + 255) / 256, out.C), dim3(256), 0, s, m_p, logs_p, tok_of_frame, seg_of,
-                       seg_start, seg_len, seg_utt, seed, noise_scale, out);
+                       seg_start, seg_len, opts, out);
 }
 
 // ------------------------------------------------------------------------------------------------

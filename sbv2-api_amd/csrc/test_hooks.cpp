@@ -232,6 +232,19 @@ int* upload_ints(Arena& ar, const int32_t* v, size_t n) {
     return d;
 }
 
+// the per-row option records of durations / noise_fill / expand_frames: null array = the scalar for every row (index null = the row number)
+RowOpts* upload_rows(Arena& ar, int n, const uint64_t* seed, uint64_t seed1, const int32_t* index, const float* sdp_ratio, float sdp_ratio1,
+                     const float* length_scale, float length_scale1, const float* noise_scale, float noise_scale1, const float* noise_scale_w,
+                     float noise_scale_w1) {
+    std::vector<RowOpts> r((size_t)std::max(n, 1));
+    for (int u = 0; u < n; ++u)
+        r[u] = RowOpts{seed ? seed[u] : seed1, index ? index[u] : u, sdp_ratio ? sdp_ratio[u] : sdp_ratio1, length_scale ? length_scale[u] : length_scale1,
+                       noise_scale ? noise_scale[u] : noise_scale1, noise_scale_w ? noise_scale_w[u] : noise_scale_w1, 0};
+    RowOpts* d = ar.array<RowOpts>(r.size());
+    HIP_CHECK(hipMemcpy(d, r.data(), sizeof(RowOpts) * r.size(), hipMemcpyHostToDevice));
+    return d;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1118,18 +1131,46 @@ int sbv2_debug_spline_inverse(int device, const float* params, const float* z, c
     API_END
 }
 
-int sbv2_debug_durations(int device, const float* sdp, const float* dp, const uint8_t* mask, int64_t L, float ratio, float length_scale, float* logw,
-                         int32_t* dur, int64_t* stray) {
+// durations over a text layout of nutt segments with each row's (ratio, length_scale); sdp, dp, mask, logw, dur: [L of the layout]
+int sbv2_debug_durations_rows(int device, const float* sdp, const float* dp, const uint8_t* mask, const int64_t* lens, int nutt, const float* ratio,
+                              const float* length_scale, float* logw, int32_t* dur, int64_t* stray) {
     API_BEGIN
     HIP_CHECK(hipSetDevice(device));
-    SBV2_REQUIRE(sdp && dp && mask && logw && dur, "bad arguments");
+    SBV2_REQUIRE(sdp && dp && mask && ratio && length_scale && logw && dur, "bad arguments");
+    Arena ar;
+    const SegLayout lay = hook_layout(lens, nutt, 0, ar);
+    const int64_t L = lay.L;
     DevPlane S(1, L), D(1, L), W(1, L), U(1, L);
     S.put(sdp, true);
     D.put(dp, true);
     W.fill(true);
     U.fill(true);
     DevMem dm(mask, (size_t)L);
-    durations(S.P.p, D.P.p, ratio, length_scale, dm.u8(), (int)L, W.P.p, reinterpret_cast<int*>(U.P.p), nullptr);
+    durations(S.P.p, D.P.p, lay.d_seg_of, upload_rows(ar, nutt, nullptr, 0, nullptr, ratio, 0.f, length_scale, 1.f, nullptr, 0.f, nullptr, 0.f), dm.u8(),
+              (int)L, W.P.p, reinterpret_cast<int*>(U.P.p), nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    const int64_t bad = W.get(logw, kSentinelWord) + U.get(dur, kSentinelWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
+// (one segment of L columns without gaps: the row's scalars are the call's)
+int sbv2_debug_durations(int device, const float* sdp, const float* dp, const uint8_t* mask, int64_t L, float ratio, float length_scale, float* logw,
+                         int32_t* dur, int64_t* stray) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(sdp && dp && mask && logw && dur, "bad arguments");
+    Arena ar;
+    DevPlane S(1, L), D(1, L), W(1, L), U(1, L);
+    S.put(sdp, true);
+    D.put(dp, true);
+    W.fill(true);
+    U.fill(true);
+    DevMem dm(mask, (size_t)L);
+    const std::vector<int32_t> seg_of((size_t)std::max<int64_t>(L, 0), 0);
+    durations(S.P.p, D.P.p, upload_ints(ar, seg_of.data(), (size_t)L),
+              upload_rows(ar, 1, nullptr, 0, nullptr, nullptr, ratio, nullptr, length_scale, nullptr, 0.f, nullptr, 0.f), dm.u8(), (int)L, W.P.p,
+              reinterpret_cast<int*>(U.P.p), nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     const int64_t bad = W.get(logw, kSentinelWord) + U.get(dur, kSentinelWord);
     if (stray) *stray = bad;
@@ -1168,27 +1209,36 @@ int sbv2_debug_convflow_pre(int device, const float* z0, const float* w, const f
     API_END
 }
 
-int sbv2_debug_noise_fill(int device, const int64_t* lens, int nutt, int kind, const int32_t* seg_utt, uint64_t seed, int stream_id, float scale,
-                          int64_t rows, float* y, int64_t* stray) {
+// noise_fill / expand_frames with each row's (seed, index, scale); the scalar hooks below are the same calls with one seed and scale for every row
+int sbv2_debug_noise_fill_rows(int device, const int64_t* lens, int nutt, int kind, const uint64_t* seed, const int32_t* index, int stream_id,
+                               const float* scale, int64_t rows, float* y, int64_t* stray) {
     API_BEGIN
     HIP_CHECK(hipSetDevice(device));
-    SBV2_REQUIRE(seg_utt && y && rows >= 1, "bad arguments");
+    SBV2_REQUIRE(seed && index && scale && y && rows >= 1, "bad arguments");
     Arena ar;
     const SegLayout lay = hook_layout(lens, nutt, kind, ar);
     DevPlane Y(rows, lay.L);
     Y.fill(true);
-    noise_fill(Y.P.p, Y.P.ld, (int)rows, lay.d_seg_of, lay.d_start, lay.d_len, upload_ints(ar, seg_utt, nutt), lay.L, seed, stream_id, scale, nullptr);
+    noise_fill(Y.P.p, Y.P.ld, (int)rows, lay.d_seg_of, lay.d_start, lay.d_len,
+               upload_rows(ar, nutt, seed, 0, index, nullptr, 0.f, nullptr, 1.f, nullptr, 0.f, scale, 0.f), lay.L, stream_id, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     const int64_t bad = Y.get(y, kSentinelWord);
     if (stray) *stray = bad;
     API_END
 }
 
-int sbv2_debug_expand_frames(int device, const float* m_p, const float* logs_p, int64_t C, int64_t Lt, const int32_t* tok_of_frame, const int64_t* lens,
-                             int nutt, const int32_t* seg_utt, uint64_t seed, float noise_scale, float* y, int64_t* stray) {
+int sbv2_debug_noise_fill(int device, const int64_t* lens, int nutt, int kind, const int32_t* seg_utt, uint64_t seed, int stream_id, float scale,
+                          int64_t rows, float* y, int64_t* stray) {
+    const std::vector<uint64_t> seeds((size_t)std::max(nutt, 1), seed);   // (a null seg_utt and nutt < 1 are refused by the call below, as ever)
+    const std::vector<float> scales((size_t)std::max(nutt, 1), scale);
+    return sbv2_debug_noise_fill_rows(device, lens, nutt, kind, seeds.data(), seg_utt, stream_id, scales.data(), rows, y, stray);
+}
+
+int sbv2_debug_expand_frames_rows(int device, const float* m_p, const float* logs_p, int64_t C, int64_t Lt, const int32_t* tok_of_frame, const int64_t* lens,
+                                  int nutt, const uint64_t* seed, const int32_t* index, const float* noise_scale, float* y, int64_t* stray) {
     API_BEGIN
     HIP_CHECK(hipSetDevice(device));
-    SBV2_REQUIRE(m_p && logs_p && tok_of_frame && seg_utt && y, "bad arguments");
+    SBV2_REQUIRE(m_p && logs_p && tok_of_frame && seed && index && noise_scale && y, "bad arguments");
     Arena ar;
     const SegLayout lay = hook_layout(lens, nutt, 1, ar);
     const std::vector<unsigned char> inside = layout_inside(lay);
@@ -1197,12 +1247,19 @@ int sbv2_debug_expand_frames(int device, const float* m_p, const float* logs_p, 
     M.put(m_p, true);
     S.put(logs_p, true);
     Y.fill(true);
-    expand_frames(M.P, S.P, upload_ints(ar, tok_of_frame, lay.L), lay.d_seg_of, lay.d_start, lay.d_len, upload_ints(ar, seg_utt, nutt), seed, noise_scale,
-                  Y.P, nullptr);
+    expand_frames(M.P, S.P, upload_ints(ar, tok_of_frame, lay.L), lay.d_seg_of, lay.d_start, lay.d_len,
+                  upload_rows(ar, nutt, seed, 0, index, nullptr, 0.f, nullptr, 1.f, noise_scale, 0.f, nullptr, 0.f), Y.P, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     const int64_t bad = Y.get(y, kSentinelWord);
     if (stray) *stray = bad;
     API_END
+}
+
+int sbv2_debug_expand_frames(int device, const float* m_p, const float* logs_p, int64_t C, int64_t Lt, const int32_t* tok_of_frame, const int64_t* lens,
+                             int nutt, const int32_t* seg_utt, uint64_t seed, float noise_scale, float* y, int64_t* stray) {
+    const std::vector<uint64_t> seeds((size_t)std::max(nutt, 1), seed);   // (a null seg_utt and nutt < 1 are refused by the call below, as ever)
+    const std::vector<float> scales((size_t)std::max(nutt, 1), noise_scale);
+    return sbv2_debug_expand_frames_rows(device, m_p, logs_p, C, Lt, tok_of_frame, lens, nutt, seeds.data(), seg_utt, scales.data(), y, stray);
 }
 
 int sbv2_debug_conv_post_tanh(int device, const float* x, const float* w, int64_t C, int64_t k, const int64_t* lens, int nutt, int64_t up, int cl,

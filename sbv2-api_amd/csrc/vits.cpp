@@ -610,7 +610,6 @@ void VitsModel::forward(const VitsBatch& b) {
     }
     Arena& ar = arena_;
     const int n = b.n, H = cfg_.hidden, I = cfg_.inter;
-    const uint64_t seed = b.seed;   // noise streams: noise_key(seed, index of the utterance in the caller's batch, stream)
     std::vector<int> T(n);
     int64_t total_t = 0;
     for (int u = 0; u < n; ++u) {
@@ -643,18 +642,27 @@ void VitsModel::forward(const VitsBatch& b) {
     int* d_tn = ar.array<int>(Lt);
     int* d_lg = ar.array<int>(Lt);
     int* d_sid = ar.array<int>(n);
-    int* d_uid = ar.array<int>(n);
+    RowOpts* d_rows = ar.array<RowOpts>(n);   // every row's options and noise key (seed, index of the utterance in the caller's batch)
     float* d_style = ar.array<float>((size_t)n * cfg_.style_dim);
     {
         // six neighbours in the arena, uploaded in allocation order: one copy (Arena::begin_uploads)
         UploadBatch ub(ar);
-        std::vector<int> uid(n);
-        for (int u = 0; u < n; ++u) uid[u] = b.utt_ids ? (int)b.utt_ids[u] : b.utt0 + u;
+        std::vector<RowOpts> rows(n);
+        for (int u = 0; u < n; ++u) {
+            RowOpts& r = rows[u];
+            r.seed = b.row_seed ? b.row_seed[u] : b.seed;
+            r.index = b.row_index ? (int)b.row_index[u] : b.utt_ids ? (int)b.utt_ids[u] : b.utt0 + u;
+            r.sdp_ratio = b.row_sdp_ratio ? b.row_sdp_ratio[u] : b.sdp_ratio;
+            r.length_scale = b.row_length_scale ? b.row_length_scale[u] : b.length_scale;
+            r.noise_scale = b.row_noise_scale ? b.row_noise_scale[u] : b.noise_scale;
+            r.noise_scale_w = b.row_noise_scale_w ? b.row_noise_scale_w[u] : b.noise_scale_w;
+            r.pad_ = 0;
+        }
         ar.upload(d_ph, ph.data(), sizeof(int) * Lt, stream_);
         ar.upload(d_tn, tn.data(), sizeof(int) * Lt, stream_);
         ar.upload(d_lg, lg.data(), sizeof(int) * Lt, stream_);
         ar.upload(d_sid, sid.data(), sizeof(int) * n, stream_);
-        ar.upload(d_uid, uid.data(), sizeof(int) * n, stream_);
+        ar.upload(d_rows, rows.data(), sizeof(RowOpts) * n, stream_);
         ar.upload(d_style, b.styles, sizeof(float) * (size_t)n * cfg_.style_dim, stream_);
     }
 
@@ -732,7 +740,7 @@ void VitsModel::forward(const VitsBatch& b) {
     conv_plain(sdp_proj_, XSd, COND, 1, 0, tl.d_mask, 1, stream_);
     float* z0 = Z.p;
     float* z1 = Z.p + Z.ld;
-    noise_fill(Z.p, Z.ld, 2, tl.d_seg_of, tl.d_start, tl.d_len, d_uid, Lt, seed, 0, b.noise_scale_w, stream_);
+    noise_fill(Z.p, Z.ld, 2, tl.d_seg_of, tl.d_start, tl.d_len, d_rows, Lt, 0, stream_);
     const float inv_sqrt_f = 1.0f / std::sqrt((float)H);
     for (int i = (int)sdp_cf_.size() - 1; i >= 0; --i) {
         const ConvFlow& cf = sdp_cf_[i];
@@ -748,7 +756,7 @@ void VitsModel::forward(const VitsBatch& b) {
     // ---- durations (the one device -> host sync of the batch: T_frames is data dependent) ----------------
     float* d_logw = ar.array<float>(Lt);
     int* d_dur = ar.array<int>(Lt);
-    sbv2::durations(z0, DPO.p, b.sdp_ratio, b.length_scale, tl.d_mask, Lt, d_logw, d_dur, stream_);
+    sbv2::durations(z0, DPO.p, tl.d_seg_of, d_rows, tl.d_mask, Lt, d_logw, d_dur, stream_);
     std::vector<int> dur_p(Lt);
     std::vector<float> logw_p(Lt);
     HIP_CHECK(hipMemcpyAsync(dur_p.data(), d_dur, sizeof(int) * Lt, hipMemcpyDeviceToHost, stream_));
@@ -799,7 +807,7 @@ void VitsModel::forward(const VitsBatch& b) {
     tr.reset();
     tr.reset(new TraceRange("flow"));
     Plane ZA = ar.plane(I, Lf), ZB = ar.plane(I, Lf);
-    expand_frames(m_p, logs_p, d_tok, fl.d_seg_of, fl.d_start, fl.d_len, d_uid, seed, b.noise_scale, ZA, stream_);
+    expand_frames(m_p, logs_p, d_tok, fl.d_seg_of, fl.d_start, fl.d_len, d_rows, ZA, stream_);
     trace("z_p", ZA, fl);
 
     // ---- TransformerCouplingBlock, reverse ----------------------------------------------------------------

@@ -17,8 +17,9 @@ Reference behaviour kept, quirks included:
 What differs on purpose: the sentences of a request go through ONE batched pipeline call (orchestrator.easy_synthesize).
 """
 import ctypes as C
+import threading
 
-from . import _lib, model, orchestrator
+from . import _lib, batcher, model, orchestrator
 
 
 class ModelNotFoundError(model.Sbv2Error):
@@ -57,6 +58,8 @@ class _TTSModel:
     def __init__(self, ident, vits2, style_vectors, raw):
         self.ident, self.vits2, self.style_vectors, self.bytes = ident, vits2, style_vectors, raw
         self.pipe = None
+        self.batcher = None   # batcher.RequestBatcher over pipe, once easy_synthesize_batched was used
+        self.streams = 0      # open streams of this model: they run on the pipeline's first execution context, so the batcher is paused meanwhile
 
 
 class TTSModelHolder:
@@ -69,6 +72,7 @@ class TTSModelHolder:
         self.parse_text = parse_text
         self.max_loaded_models = max_loaded_models
         self.models_ = []
+        self._stream_lock = threading.Lock()   # the stream counts and the pause / resume of the batchers (a stream is closed from any thread)
 
     # ---- tts.rs:74-76
     def models(self):
@@ -123,6 +127,9 @@ class TTSModelHolder:
 
     @staticmethod
     def _drop(m):
+        if m.batcher is not None:   # drains: the requests it holds are answered before the weights go
+            m.batcher.close()
+            m.batcher = None
         if m.pipe is not None:
             m.pipe.close()
             m.pipe = None
@@ -153,16 +160,37 @@ class TTSModelHolder:
         options = options or orchestrator.SynthesizeOptions()
         self.find_and_load_model(ident)
         m = self._find(ident)
-        if isinstance(text, str):
-            if self.parse_text is None:
-                raise model.Sbv2Error("no text front end configured (parse_text): pass parsed sentences instead")
-            lines = text.split("\n") if options.split_sentences else [text]
-            sentences = [self.parse_text(t) if t else None for t in lines]
-        else:
-            sentences = list(text)
+        sentences = self._sentences(text, options)
         if m.pipe is None:
             m.pipe = self._make_pipeline(self.bert, m.vits2)
         return orchestrator.easy_synthesize(m.pipe, sentences, m.style_vectors, style_id, speaker_id, options, noise_seed=noise_seed)
+
+    def easy_synthesize_batched(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, batching=None):
+        """easy_synthesize answered through a concurrent.futures.Future of the bytes: the request joins a pipeline run with whatever other
+        requests for the same model wait at that moment (batcher.RequestBatcher; one per resident model: rows of different models have
+        different weights and never share a run).  batching: the batcher's keyword arguments (max_utts, max_symbols, max_wait_ms), read
+        when the model's batcher is created.  The caller serialises calls of this method (rest.py: under its lock); waiting for the
+        Future needs no lock.  A model with a batcher is served through it alone: easy_synthesize on the same ident would share its pipeline."""
+        options = options or orchestrator.SynthesizeOptions()
+        self.find_and_load_model(ident)
+        m = self._find(ident)
+        sentences = self._sentences(text, options)
+        if m.pipe is None:
+            m.pipe = self._make_pipeline(self.bert, m.vits2)
+        with self._stream_lock:
+            if m.batcher is None:
+                m.batcher = batcher.RequestBatcher(m.pipe, **(batching or {}))
+                for _ in range(m.streams):   # a stream of this model is open: the request queues until it is closed
+                    m.batcher.pause()
+        return m.batcher.submit(sentences, m.style_vectors, style_id, speaker_id, options, noise_seed=noise_seed)
+
+    def _sentences(self, text, options):
+        if not isinstance(text, str):
+            return list(text)
+        if self.parse_text is None:
+            raise model.Sbv2Error("no text front end configured (parse_text): pass parsed sentences instead")
+        lines = text.split("\n") if options.split_sentences else [text]
+        return [self.parse_text(t) if t else None for t in lines]
 
     def easy_synthesize_stream(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, chunk_frames=256):
         """The request as ONE utterance, delivered while it is synthesised (orchestrator.easy_synthesize_stream): a generator over the bytes of
@@ -177,9 +205,28 @@ class TTSModelHolder:
             sentences = [self.parse_text(text) if text else None]
         else:
             sentences = list(text)
-        # (the stream runs on the two sessions themselves, which the model's pipeline shares: the caller keeps requests one at a time, as rest.py does)
-        return orchestrator.easy_synthesize_stream(self.bert, m.vits2, sentences, m.style_vectors, style_id, speaker_id, options,
-                                                   noise_seed=noise_seed, chunk_frames=chunk_frames)
+        # The stream runs on the two sessions themselves, which are the first execution context of the model's pipeline (same stream, arena and
+        # PCM buffer).  Callers keep plain requests one at a time (rest.py's lock); a batcher works beside them, so it is paused first (every run
+        # it launched is answered, nothing is launched) and resumed when the stream is closed.  Requests queue meanwhile.
+        with self._stream_lock:
+            m.streams += 1
+            if m.batcher is not None:
+                m.batcher.pause()
+
+        def release():
+            with self._stream_lock:
+                m.streams -= 1
+                if m.batcher is not None:
+                    m.batcher.resume()
+
+        try:
+            st = orchestrator.easy_synthesize_stream(self.bert, m.vits2, sentences, m.style_vectors, style_id, speaker_id, options,
+                                                     noise_seed=noise_seed, chunk_frames=chunk_frames)
+        except BaseException:
+            release()
+            raise
+        st.on_close = release
+        return st
 
     def close(self):
         for m in self.models_:

@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Sbv2Batch, Sbv2Error, check, f32p, i64p
+from ._lib import Sbv2Batch, Sbv2Error, Sbv2FetchRequest, Sbv2UttOptions, check, f32p, i64p
 
 __all__ = ["Session", "load_model", "predict", "synthesize", "predict_batch", "synthesize_batch", "Pipeline", "Node", "Comm", "deal", "Sbv2Error",
            "PcmFormat", "pcm_format_length", "pcm_format_taps", "flac_bound", "debug_flac_encode", "flac_stream_bound", "debug_flac_stream_encode", "Loudness", "loudness_kweight",
@@ -295,6 +295,20 @@ class _Batch:
         self.c = Sbv2Batch(len(utts), p(self.t_lens, i64p), p(self.x, i64p), p(self.tones, i64p), p(self.langs, i64p), p(self.sids, i64p),
                            p(self.styles, f32p), p(self.bert, f32p), sdp_ratio, length_scale, noise_scale, noise_scale_w, noise_seed,
                            p(self.forced, i64p))
+        self.opts = None   # Sbv2UttOptions when an utterance overrides an option (set_row_options)
+
+    ROW_KEYS = ("sdp_ratio", "length_scale", "noise_scale", "noise_scale_w", "noise_seed", "noise_index")
+
+    def set_row_options(self, utts):
+        """Per-utterance options (struct sbv2_utt_options): a key of ROW_KEYS in an utterance dict wins over the batch's scalar; noise_index
+        defaults to the row number.  Nothing is built when no utterance overrides anything: the run is then the scalar call."""
+        if not any(k in u for u in utts for k in self.ROW_KEYS):
+            return
+        col = lambda key, dt, default: np.array([u.get(key, default(i)) for i, u in enumerate(utts)], dt)
+        self.rows = [col(k, np.float32, lambda i, k=k: getattr(self.c, k)) for k in self.ROW_KEYS[:4]]
+        self.rows.append(np.array([int(u.get("noise_seed", self.c.noise_seed)) & (2 ** 64 - 1) for u in utts], np.uint64))
+        self.rows.append(col("noise_index", np.int64, lambda i: i))
+        self.opts = Sbv2UttOptions(*[a.ctypes.data_as(t) for a, t in zip(self.rows, [f32p] * 4 + [C.POINTER(C.c_uint64), i64p])])
 
 
 def synthesize_batch(session: Session, utts, sdp_ratio=0.0, length_scale=1.0, noise_scale=0.0, noise_scale_w=0.0, noise_seed=0,
@@ -370,11 +384,15 @@ class Pipeline:
         b.s_lens = np.array([len(u["input_ids"]) for u in utts], np.int64)
         b.w2p = np.ascontiguousarray(np.concatenate([np.asarray(u["word2ph"], np.int64) for u in utts]))
         b.lens = np.zeros(len(utts), np.int64)
+        b.set_row_options(utts)   # keys sdp_ratio / length_scale / noise_scale / noise_scale_w / noise_seed / noise_index of an utterance win
         return b
 
     def run(self, b):
-        check(_lib.lib().sbv2_pipeline_run(self.h, C.byref(b.c), b.ids.ctypes.data_as(i64p), b.s_lens.ctypes.data_as(i64p),
-                                           b.w2p.ctypes.data_as(i64p), b.lens.ctypes.data_as(i64p)))
+        tail = (b.ids.ctypes.data_as(i64p), b.s_lens.ctypes.data_as(i64p), b.w2p.ctypes.data_as(i64p), b.lens.ctypes.data_as(i64p))
+        if b.opts is not None:
+            check(_lib.lib().sbv2_pipeline_run_opts(self.h, C.byref(b.c), C.byref(b.opts), *tail))
+        else:
+            check(_lib.lib().sbv2_pipeline_run(self.h, C.byref(b.c), *tail))
         b.ticket = _lib.lib().sbv2_pipeline_last_ticket(self.h)   # identifies this run's results until `depth` further runs
         return b.lens
 
@@ -466,6 +484,29 @@ class Pipeline:
     def fetch_flac(self, b, fmt: PcmFormat, place=None, joined_len=None):
         """The signals of fetch_format(b, fmt, place, joined_len), each as one FLAC stream (bytes) encoded on the device; fmt must be s16."""
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
+
+    def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False):
+        """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
+        joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
+        or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
+        read: the requests that share a run are fetched one by one from the same ticket."""
+        if flac and fmt.encoding != "s16":
+            raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
+        rw = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
+        pl, pp = _i64(place)
+        if pl.shape != rw.shape:
+            raise Sbv2Error(f"place must hold one offset per listed row ({rw.size})")
+        limited = isinstance(gain, Limiter)
+        nstats = 0 if gain is None else 6 if limited else 3
+        req = Sbv2FetchRequest(rw.ctypes.data_as(C.POINTER(C.c_int32)), rw.size, pp, int(joined_len), C.pointer(fmt.c),
+                               None if gain is None or limited else C.pointer(gain.c), C.pointer(gain.c) if limited else None, int(bool(flac)))
+        size = (flac_bound if flac else pcm_format_length)(fmt, int(joined_len))
+        dst = np.empty(max(size, 1), np.uint8 if flac else fmt.dtype)
+        got = C.c_int64(0)
+        stats = np.zeros(nstats, np.float64) if nstats else None
+        check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
+                                                     _f64p(stats) if nstats else None))
+        return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
 
     def close(self):
         if self.h:

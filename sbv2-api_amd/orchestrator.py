@@ -114,57 +114,73 @@ def joined_placement(lens, live_index, n_lines, split_sentences=True):
     return place, pos
 
 
+class RequestPlan:
+    """Everything easy_synthesize decides about one request before the run: the output side (fmt, flac, gain) and the request's rows
+    (utts: one dict per live sentence, ready for Pipeline.prepare; live: their line numbers among the request's n_lines lines)."""
+
+    def __init__(self, sentences, style_vectors, style_id, speaker_id, options):
+        options = options or SynthesizeOptions()
+        if options.loudness is not None and options.normalize:
+            raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
+        self.limited = bool(options.limiter)
+        if self.limited and options.loudness is None:
+            raise model.Sbv2Error("limiter needs a loudness target: set loudness (LUFS)")
+        if self.limited:
+            self.gain = model.Limiter(options.loudness, options.true_peak_max, options.max_reduction)
+        else:
+            self.gain = model.Loudness(options.loudness, options.true_peak_max) if options.loudness is not None else None
+        style = get_style_vector(style_vectors, style_id, options.style_weight)
+        live = [(i, s) for i, s in enumerate(sentences) if s]
+        if not live:
+            raise model.Sbv2Error("nothing to synthesize (the reference's concatenate fails on an empty list)")
+        self.flac = options.encoding == "flac"   # a FLAC stream of the s16 signal, encoded on the device
+        self.fmt = model.PcmFormat(options.sample_rate, "s16" if self.flac else options.encoding, options.normalize)
+        model.pcm_format_length(self.fmt, 0)   # a bad rate is refused before any GPU work
+        self.options, self.n_lines = options, len(sentences)
+        self.live = [i for i, _ in live]
+        self.utts = [dict(s, style=style, sid=speaker_id) for _, s in live]
+
+
+def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPlan, loudness_stats=None, pcm=None) -> bytes:
+    """The answer of one request from rows r0 .. r1 - 1 of run `b` (plan.utts were prepared as those rows): the request's WAV or FLAC bytes,
+    whatever else the run holds.  pcm: the run's plain fetch (pipe.fetch(b)) when the caller already has it."""
+    options, fmt, ln = plan.options, plan.fmt, plan.gain
+    lens = b.lens[r0:r1]
+    if ln is not None or not fmt.is_default:
+        # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
+        # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
+        place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
+        out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac)
+        if stats is not None and loudness_stats is not None:
+            loudness_stats.append([float(v) for v in stats])
+        if plan.flac:
+            return out
+        return pcm16_wav(out, fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out, fmt.sample_rate)
+    if pcm is None:
+        pcm = pipe.fetch(b)
+    parts = []
+    for i, wav in zip(plan.live, pcm[r0:r1]):
+        parts.append(wav)
+        if options.split_sentences and i != plan.n_lines - 1:
+            parts.append(np.zeros(SENTENCE_GAP, np.float32))
+    return array_to_wav(np.concatenate(parts).reshape(1, 1, -1))
+
+
 def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
                     noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, loudness_stats=None) -> bytes:
     """tts.rs:280-349 for one request whose lines are already parsed: `sentences` is the list obtained from text.split('\\n'),
     each entry a dict {input_ids, word2ph, phones, tones, langs} (parse_text's products) or None / {} for an empty line.
     With options.split_sentences False the caller passes the single parsed text as a one-element list.
     loudness_stats: an optional list that receives [L, TP, G] of the signal when options.loudness is set, or the limiter's 6 values
-    [L, TP, G, L_out, TP_out, deepest reduction] when options.limiter is set as well."""
-    options = options or SynthesizeOptions()
-    if options.loudness is not None and options.normalize:
-        raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
-    limited = bool(options.limiter)
-    if limited and options.loudness is None:
-        raise model.Sbv2Error("limiter needs a loudness target: set loudness (LUFS)")
-    if limited:
-        ln = model.Limiter(options.loudness, options.true_peak_max, options.max_reduction)
-    else:
-        ln = model.Loudness(options.loudness, options.true_peak_max) if options.loudness is not None else None
+    [L, TP, G, L_out, TP_out, deepest reduction] when options.limiter is set as well.
+    = finish_request over all rows of a run that holds this request alone (batcher.RequestBatcher: the same, several requests to a run)."""
+    plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
     if noise_seed is None:      # the reference draws fresh noise per request; tests pass an explicit seed
         noise_seed = model.fresh_noise_seed()
-    style = get_style_vector(style_vectors, style_id, options.style_weight)
-    live = [(i, s) for i, s in enumerate(sentences) if s]
-    if not live:
-        raise model.Sbv2Error("nothing to synthesize (the reference's concatenate fails on an empty list)")
-    flac = options.encoding == "flac"   # a FLAC stream of the s16 signal, encoded on the device
-    fmt = model.PcmFormat(options.sample_rate, "s16" if flac else options.encoding, options.normalize)
-    model.pcm_format_length(fmt, 0)   # a bad rate is refused before any GPU work
-    utts = [dict(s, style=style, sid=speaker_id) for _, s in live]
-    b = pipe.prepare(utts, sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
+    b = pipe.prepare(plan.utts, sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=noise_scale,
                      noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     pipe.run(b)
-    if ln is not None or not fmt.is_default:
-        # ONE joined fetch: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target it is
-        # measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
-        place, joined = joined_placement(b.lens, [i for i, _ in live], len(sentences), options.split_sentences)
-        if ln is None:
-            out = (pipe.fetch_flac if flac else pipe.fetch_format)(b, fmt, place, joined)
-        else:
-            fetch = (pipe.fetch_flac_limited if flac else pipe.fetch_limited) if limited else (pipe.fetch_flac_loudness if flac else pipe.fetch_loudness)
-            out, stats = fetch(b, fmt, ln, place, joined)
-            if loudness_stats is not None:
-                loudness_stats.append([float(v) for v in stats[0]])
-        if flac:
-            return out[0]
-        return pcm16_wav(out[0], fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out[0], fmt.sample_rate)
-    pcm = pipe.fetch(b)
-    parts = []
-    for (i, _), wav in zip(live, pcm):
-        parts.append(wav)
-        if options.split_sentences and i != len(sentences) - 1:
-            parts.append(np.zeros(SENTENCE_GAP, np.float32))
-    return array_to_wav(np.concatenate(parts).reshape(1, 1, -1))
+    return finish_request(pipe, b, 0, len(plan.utts), plan, loudness_stats)
 
 
 def wav_stream_header(rate: int, encoding: str, n_samples: int) -> bytes:
@@ -204,10 +220,17 @@ class SynthesisStream:
         self.close()
         raise StopIteration
 
+    on_close = None   # optional callable, run once when the stream is closed (the holder resumes the model's batcher with it)
+
     def close(self):
         st, self._st, self._head = self._st, None, None
-        if st is not None:
-            st.close()
+        try:
+            if st is not None:
+                st.close()
+        finally:
+            cb, self.on_close = self.on_close, None
+            if cb is not None:
+                cb()
 
     def __del__(self):
         try:

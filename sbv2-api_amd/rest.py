@@ -16,6 +16,7 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     has left or the client has gone, whichever comes first (_HeldPieces, _ClosingStream).
   any error         500 text/plain "Something went wrong: <message>"            sbv2_api/src/error.rs:10-18
   one request at a time (Arc<Mutex<TTSModelHolder>>, main.rs:86,104)             -> a lock around the holder
+  make_app(holder, batching={...})  new, off by default: concurrent /synthesize requests share pipeline runs (batcher.py)
 
 FastAPI / starlette are plumbing here; `python -m sbv2_api_amd.rest` is not provided on purpose: a deployment needs the text front end
 (G2P + tokenizer, out of scope: SURVEY.md §2 #7-12) plugged into the holder's `parse_text`."""
@@ -68,7 +69,11 @@ class _HeldPieces:
             pass
 
 
-def make_app(holder):
+def make_app(holder, batching=None):
+    """batching None: one request at a time, as the reference.  A dict of batcher.RequestBatcher keyword arguments (max_utts, max_symbols,
+    max_wait_ms; {} = the defaults): /synthesize holds the lock only while the request is parsed and queued, then awaits its answer, so
+    concurrent requests for a model share pipeline runs.  /synthesize_stream keeps the lock either way: a /synthesize that arrives during a
+    stream waits for it on a worker thread, and the holder keeps the streamed model's batcher paused while the stream is open."""
     from fastapi import FastAPI, Request
     from fastapi.responses import JSONResponse, PlainTextResponse, Response, StreamingResponse
     from pydantic import BaseModel
@@ -125,7 +130,6 @@ def make_app(holder):
                                               encoding=req.encoding, normalize=req.normalize, loudness=req.loudness,
                                               true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction)
 
-    @app.post("/synthesize")
     def synthesize(req: SynthesizeRequest):
         try:
             with lock:
@@ -133,6 +137,19 @@ def make_app(holder):
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
         return Response(content=wav, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
+
+    def synthesize_batched(req: SynthesizeRequest):
+        # a plain function: it runs on a worker thread, so neither the lock (which a stream holds until its last byte has left, and gives back
+        # only with the event loop's help) nor parse_text, a model load or an eviction's drain inside the holder ever stall the event loop
+        try:
+            with lock:                        # parse and queue only: the answer is awaited without it
+                fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching)
+            wav = fut.result()
+        except Exception as e:
+            return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
+        return Response(content=wav, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
+
+    app.post("/synthesize")(synthesize if batching is None else synthesize_batched)
 
     @app.post("/synthesize_stream")
     def synthesize_stream(req: SynthesizeRequest):
