@@ -290,6 +290,47 @@ typedef struct sbv2_fetch_request {
 int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
                                 int64_t* out_count, double* stats);
 
+/* ---- new: speech marks.  When each token (phone id, blanks included) is spoken in a delivered signal, and how loud it is there.
+ * Token spans.  Row u of a run has tokens t < t_lens[u]; token t has the duration d[t] in frames as the run expanded it: the batch's
+ *   forced_durations where given, the predicted ones otherwise.  With c the exclusive prefix sum of d and hop = sbv2_vits_hop, token t occupies
+ *   native samples [hop c[t], hop c[t + 1]) of its row.  A row placed at native position `place` of a joined timeline and delivered at the rate
+ *   L / M of a sbv2_pcm_format maps native position a to the delivered index J(a) = ceil(a L / M), the rule of sbv2_pcm_format_length, so the
+ *   delivered span of token t is [J(place + hop c[t]), J(place + hop c[t + 1])).  Hence: the spans of a row are contiguous and monotone
+ *   (end[t] == start[t + 1]); the first starts at J(place); where the row's durations sum to >= 1 the last ends at J(place + pcm_len); a
+ *   zero-duration token has an empty span; a row whose durations sum to 0 still synthesises one frame (clamp_min(sum, 1)), all its spans are
+ *   empty at J(place) and that frame belongs to no token.  The silence between the rows of a joined timeline belongs to no token either.
+ * Levels.  For a span [s, e) of the DELIVERED samples v: sumsq = sum v[j]^2 and peak = max |v[j]| as f64, both 0 for an empty span.  The
+ *   delivered samples are the f32 values, or the s16 integers as integers (full scale 32767), after the resampler, the gain stage and the
+ *   quantiser: exactly what crosses PCIe or enters the FLAC encoder.  For s16 sumsq is exact (integers below 2^53); for f32 every square is
+ *   exact in f64 and only the order of the sum is the library's (within len 2^-52 relative of any other order).  The order is fixed: two
+ *   fetches of one ticket give identical bits.  dBFS = 10 log10(sumsq / n) (s16: divided by 32767^2) is the caller's arithmetic.
+ * Envelope (optional, env_hop > 0 delivered samples): frame f = [f env_hop, min((f + 1) env_hop, out_len)), n_env = ceil(out_len / env_hop)
+ *   frames, each with the same sumsq and peak; out_len = the delivered samples of the signal.
+ * The levels are ONE segmented reduction over the samples in HBM (marks.hip), enqueued before the fetch's only synchronisation; timing alone
+ *   (tok_sumsq == tok_peak == NULL, env_hop == 0) launches nothing, and a fetch without marks does nothing new at all. */
+typedef struct sbv2_marks {
+    int64_t tok_capacity;                 /* in: entries each token array holds */
+    int64_t* tok_start; int64_t* tok_end; /* out: delivered-sample spans */
+    double* tok_sumsq; double* tok_peak;  /* out; either may be NULL with the other: timing only, no kernel launch */
+    int64_t n_tokens;                     /* out: sum of t_lens over the listed rows */
+    int32_t env_hop; int32_t reserved;    /* in: 0 = no envelope; reserved must be 0 */
+    int64_t env_capacity; double* env_sumsq; double* env_peak; int64_t n_env;
+} sbv2_marks;
+/* sbv2_pipeline_fetch_request that also fills *marks: the tokens of the rows in the order of req->utts, then token order within each row.
+ * marks == NULL is exactly sbv2_pipeline_fetch_request; with marks the audio bytes, out_count and stats are those of the same fetch without.
+ * All six gain / sink combinations are supported, FLAC included.  Refused with nothing written, besides everything that call refuses: a
+ * tok_capacity below the rows' token count, an env_capacity below n_env, a negative env_hop, a non-zero reserved, env_hop > 0 with NULL
+ * envelope arrays, one of tok_sumsq / tok_peak NULL without the other. */
+int sbv2_pipeline_fetch_request_marks(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
+                                      int64_t* out_count, double* stats, sbv2_marks* marks);
+/* Host only: the span arithmetic above in one place (the fetch and the stream both call it): start[t], end[t] for n_tokens durations (>= 0)
+ * of one row at `place`, at fmt's rate (its encoding and normalize do not matter).  Refused: a bad fmt, a negative duration or place, hop < 1. */
+int sbv2_marks_spans(const int64_t* durations, int64_t n_tokens, int32_t hop, int64_t place, const sbv2_pcm_format* fmt, int64_t* start,
+                     int64_t* end);
+/* Test hook: the level reduction on host samples x[n] (encoding 0 = f32, 1 = s16) over the segments [starts[i], ends[i]) within [0, n]. */
+int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n, const int64_t* starts, const int64_t* ends, int64_t nseg,
+                              double* sumsq, double* peak);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,
@@ -385,6 +426,12 @@ int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, 
  * ones allowed, the last one ends the stream); dst receives the pushes' bytes back to back, out_bytes_per_push[ncuts + 1] their sizes. */
 int sbv2_debug_flac_stream_encode(int device, const int16_t* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, uint8_t* dst,
                                   int64_t capacity, int64_t* out_bytes_per_push);
+/* ---- new: speech marks of a stream.  Host only, valid from sbv2_stream_begin* onwards: the token spans (see sbv2_marks) of the stream's one
+ * utterance at place 0 and at the stream's delivered rate (native for sbv2_stream_begin).  Every duration is known before the first replay, so
+ * the client has the full timing before the first audio byte; the samples of all chunks sum to the last token's end (durations summing to >= 1).
+ * Levels and the envelope are NOT built on streams: they would need partial sums carried across chunks, and a streaming client decodes the
+ * audio anyway.  Refused: capacity below the token count. */
+int sbv2_stream_marks(sbv2_stream* s, int64_t* tok_start, int64_t* tok_end, int64_t capacity, int64_t* n_tokens);
 int sbv2_stream_uses_graph(const sbv2_stream* s);
 int64_t sbv2_stream_workspace_bytes(const sbv2_stream* s);
 void sbv2_stream_end(sbv2_stream* s);

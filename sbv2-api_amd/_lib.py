@@ -46,6 +46,13 @@ class Sbv2FetchRequest(C.Structure):
                 ("fmt", C.POINTER(Sbv2PcmFormat)), ("loudness", C.POINTER(Sbv2Loudness)), ("limiter", C.POINTER(Sbv2Limiter)), ("flac", C.c_int32)]
 
 
+class Sbv2Marks(C.Structure):
+    """struct sbv2_marks (include/sbv2_hip.h)."""
+    _fields_ = [("tok_capacity", C.c_int64), ("tok_start", i64p), ("tok_end", i64p), ("tok_sumsq", C.POINTER(C.c_double)),
+                ("tok_peak", C.POINTER(C.c_double)), ("n_tokens", C.c_int64), ("env_hop", C.c_int32), ("reserved", C.c_int32),
+                ("env_capacity", C.c_int64), ("env_sumsq", C.POINTER(C.c_double)), ("env_peak", C.POINTER(C.c_double)), ("n_env", C.c_int64)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -82,6 +89,12 @@ SYMBOLS = {
     "sbv2_vits_synthesize_batch_opts": (C.c_int, [C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p]),
     "sbv2_pipeline_run_opts": (C.c_int, [C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p, i64p, i64p, i64p]),
     "sbv2_pipeline_fetch_request": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double)]),
+    "sbv2_pipeline_fetch_request_marks": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.c_void_p, C.c_int64, i64p,
+                                                    C.POINTER(C.c_double), C.POINTER(Sbv2Marks)]),
+    "sbv2_marks_spans": (C.c_int, [i64p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, i64p]),
+    "sbv2_debug_segment_levels": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, i64p, i64p, C.c_int64, C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double)]),
+    "sbv2_stream_marks": (C.c_int, [C.c_void_p, i64p, i64p, C.c_int64, i64p]),
     "sbv2_pipeline_sync": (C.c_int, [C.c_void_p]),
     "sbv2_pipeline_fetch_pcm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
     "sbv2_pipeline_fetch_pcm_ticket": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),

@@ -23,8 +23,8 @@ from . import model, orchestrator
 
 
 class _Request:
-    def __init__(self, args, future):
-        self.args, self.future, self.plan = args, future, None
+    def __init__(self, args, future, marks=False):
+        self.args, self.future, self.plan, self.marks = args, future, None, bool(marks)
         self.n_utts = self.n_symbols = 0
 
 
@@ -52,10 +52,12 @@ class RequestBatcher:
             self._started = True
             self._thread.start()
 
-    def submit(self, sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None) -> Future:
-        """orchestrator.easy_synthesize's request, answered through a Future of its bytes."""
+    def submit(self, sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None, marks=False) -> Future:
+        """orchestrator.easy_synthesize's request, answered through a Future of its bytes.  marks=True: orchestrator.easy_synthesize_marks'
+        request, answered with (bytes, marks): the marks come from the request's own rows of the shared run (its own fetch, its own timeline)
+        and equal those of the request run alone."""
         fut = Future()
-        req = _Request((list(sentences), style_vectors, style_id, speaker_id, options, noise_seed), fut)
+        req = _Request((list(sentences), style_vectors, style_id, speaker_id, options, noise_seed), fut, marks)
         with self._cond:
             if self._closing:
                 raise model.Sbv2Error("the batcher is closed")
@@ -91,6 +93,8 @@ class RequestBatcher:
             sentences, style_vectors, style_id, speaker_id, options, seed = req.args
             plan = orchestrator.RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
             self._check(plan.options)
+            if req.marks:
+                orchestrator.envelope_hop(plan.options, plan.fmt.sample_rate)
             seed = model.fresh_noise_seed() if seed is None else seed
             for j, u in enumerate(plan.utts):   # noise_index restarts per request: the keys of the request run alone
                 u.update(sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=orchestrator.NOISE_SCALE,
@@ -168,6 +172,11 @@ class RequestBatcher:
                 if req.future.done():
                     continue
                 try:
+                    if req.marks:   # (its own fetch at every format: the levels are taken of its delivered signal)
+                        got = []
+                        audio = orchestrator.finish_request(self.pipe, b, r0, r1, req.plan, marks=got)
+                        req.future.set_result((audio, got[0]))
+                        continue
                     if pcm is None and req.plan.gain is None and req.plan.fmt.is_default:
                         pcm = self.pipe.fetch(b)   # the plain f32 requests of a run share one fetch
                     req.future.set_result(orchestrator.finish_request(self.pipe, b, r0, r1, req.plan, pcm=pcm))

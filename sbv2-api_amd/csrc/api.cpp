@@ -441,14 +441,65 @@ static PcmFmtSpec fetch_spec(const sbv2_pcm_format* fmt, bool gain_stage, Sink s
     return spec;
 }
 
+// The speech marks of a request fetch (marks.h), planned on the host before anything is enqueued: the listed rows' token spans on the delivered
+// timeline and the segment table of the level reduction (the token spans when levels are asked for, then the envelope frames).
+struct MarksPlan {
+    std::vector<int64_t> start, end;   // per token, in the order of the request's rows
+    std::vector<int64_t> seg;          // [levels ? n_tok : 0][2], then [n_env][2]
+    int64_t n_tok = 0, n_env = 0;
+    bool levels = false;
+};
+// the checks of sbv2_marks that need no run
+static void check_marks_static(const sbv2_marks* m) {
+    SBV2_REQUIRE(m->reserved == 0, "sbv2_marks.reserved must be 0");
+    SBV2_REQUIRE(m->env_hop >= 0, "sbv2_marks.env_hop must be >= 0: " + std::to_string(m->env_hop));
+    SBV2_REQUIRE(m->env_hop == 0 || (m->env_sumsq && m->env_peak), "sbv2_marks.env_hop > 0 needs env_sumsq and env_peak");
+    SBV2_REQUIRE(!m->tok_sumsq == !m->tok_peak, "sbv2_marks.tok_sumsq and tok_peak are given together or not at all");
+    SBV2_REQUIRE(m->tok_capacity >= 0 && m->env_capacity >= 0, "negative sbv2_marks capacity");
+}
+static MarksPlan plan_marks(const sbv2_marks* m, const PcmFmtSpec& spec, const VitsModel& vm, const int32_t* utts, int n_utts, const int64_t* place,
+                            int64_t total) {
+    check_marks_static(m);
+    SBV2_REQUIRE(utts && place, "internal: marks need a request's rows");
+    const std::vector<int64_t>& offs = vm.used_offs();
+    const std::vector<int64_t>& used = vm.used_durations();
+    SBV2_REQUIRE(offs.size() == vm.pcm_lens().size() + 1, "internal: the run kept no durations");
+    MarksPlan mp;
+    for (int k = 0; k < n_utts; ++k) mp.n_tok += offs[utts[k] + 1] - offs[utts[k]];
+    SBV2_REQUIRE(m->tok_capacity >= mp.n_tok,
+                 "token arrays too small: " + std::to_string(m->tok_capacity) + " < " + std::to_string(mp.n_tok) + " tokens");
+    SBV2_REQUIRE(mp.n_tok == 0 || (m->tok_start && m->tok_end), "sbv2_marks.tok_start and tok_end must not be NULL");
+    if (m->env_hop > 0) {
+        mp.n_env = (total + m->env_hop - 1) / m->env_hop;
+        SBV2_REQUIRE(m->env_capacity >= mp.n_env,
+                     "envelope arrays too small: " + std::to_string(m->env_capacity) + " < " + std::to_string(mp.n_env) + " frames");
+    }
+    mp.levels = m->tok_sumsq != nullptr;
+    mp.start.resize((size_t)mp.n_tok);
+    mp.end.resize((size_t)mp.n_tok);
+    int64_t e = 0;
+    for (int k = 0; k < n_utts; ++k) {
+        const int64_t o = offs[utts[k]], nt = offs[utts[k] + 1] - o;
+        marks_spans(used.data() + o, nt, vm.cfg().hop(), place[k], spec, mp.start.data() + e, mp.end.data() + e);
+        e += nt;
+    }
+    mp.seg.reserve((size_t)(2 * ((mp.levels ? mp.n_tok : 0) + mp.n_env)));
+    if (mp.levels)
+        for (int64_t t = 0; t < mp.n_tok; ++t) mp.seg.push_back(mp.start[t]), mp.seg.push_back(mp.end[t]);
+    for (int64_t f = 0; f < mp.n_env; ++f) mp.seg.push_back(f * m->env_hop), mp.seg.push_back(std::min((f + 1) * (int64_t)m->env_hop, total));
+    return mp;
+}
+
 // The run's packed PCM (pcm_device + pcm_offs / pcm_lens) is formatted on the run's own stream and crosses PCIe in the format: every
 // check first (format, gain options, ticket, placement, PCM capacity), then the formatter's launches with the gain stage between the
 // resampler and the quantiser, then the sink.  out_counts: samples (PCM) or bytes (FLAC) of each signal; stats (may be NULL): the gain
 // stage's 3 or 6 doubles per signal.
 // utts (with place): the one signal of those rows only.
+// marks (with utts): the speech marks of that signal; their reduction reads the delivered samples in HBM, on the same stream, before the one
+// synchronisation of the fetch, and the caller's arrays are written only once everything else has succeeded.
 static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
                             int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats,
-                            const int32_t* utts = nullptr, int n_utts = 0) {
+                            const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr) {
     const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
     const LoudnessSpec ln = gain.kind == FetchGain::kLoudness ? loudness_spec(gain.ln) : LoudnessSpec();
     const LimiterSpec lim = gain.kind == FetchGain::kLimiter ? limiter_spec(gain.lim) : LimiterSpec();
@@ -463,6 +514,9 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
     if (sink == Sink::kPcm)   // (the FLAC sink checks its capacity after encoding, when the sizes are known)
         SBV2_REQUIRE(capacity_bytes >= pcm_bytes,
                      "PCM buffer too small: " + std::to_string(capacity_bytes) + " < " + std::to_string(pcm_bytes) + " bytes");
+    const MarksPlan mp = marks ? plan_marks(marks, spec, vm, utts, n_utts, place, total) : MarksPlan();
+    const int64_t nseg = (int64_t)mp.seg.size() / 2;
+    bool marks_ran = false;
     HIP_CHECK(hipSetDevice(vm.device()));
     OutputChain& c = p->chains[ctx];
     const hipStream_t s = vm.stream();
@@ -474,6 +528,10 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
                                 : gain.kind == FetchGain::kLoudness ? GainStage(c.meter, ln)
                                                                     : GainStage();
         c.formatter.run(spec, pieces, sig, total, dev, 0, s, stage);
+        if (nseg > 0 && total > 0) {   // the delivered samples, as they cross PCIe or enter the encoder
+            c.marks.run(dev, spec.encoding, total, mp.seg.data(), nseg, s);
+            marks_ran = true;
+        }
         if (sink == Sink::kFlac) {   // the signals stay in HBM; the encoder reads the stream sizes back, then exactly the encoded bytes cross PCIe
             std::vector<int64_t> offs(outs.size());
             for (size_t i = 1; i < outs.size(); ++i) offs[i] = offs[i - 1] + outs[i - 1];
@@ -490,6 +548,22 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
     if (stats) {   // written by the stage's last copy on s
         const double* from = gain.kind == FetchGain::kLimiter ? c.limiter.stats_host() : c.meter.stats_host();
         std::memcpy(stats, from, sizeof(double) * gain.stats_per_signal() * sig.size());
+    }
+    if (marks) {
+        std::copy(mp.start.begin(), mp.start.end(), marks->tok_start);
+        std::copy(mp.end.begin(), mp.end.end(), marks->tok_end);
+        // (an empty signal has only empty segments: 0, without a launch)
+        const int64_t nt = mp.levels ? mp.n_tok : 0;
+        for (int64_t t = 0; t < nt; ++t) {
+            marks->tok_sumsq[t] = marks_ran ? c.marks.sumsq_host()[t] : 0.0;
+            marks->tok_peak[t] = marks_ran ? c.marks.peak_host()[t] : 0.0;
+        }
+        for (int64_t f = 0; f < mp.n_env; ++f) {
+            marks->env_sumsq[f] = marks_ran ? c.marks.sumsq_host()[nt + f] : 0.0;
+            marks->env_peak[f] = marks_ran ? c.marks.peak_host()[nt + f] : 0.0;
+        }
+        marks->n_tokens = mp.n_tok;
+        marks->n_env = mp.n_env;
     }
 }
 
@@ -561,11 +635,15 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
     API_END
 }
 
-int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes, int64_t* out_count,
-                                double* stats) {
+int sbv2_pipeline_fetch_request_marks(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
+                                      int64_t* out_count, double* stats, sbv2_marks* marks) {
     API_BEGIN
     SBV2_REQUIRE(req && req->n_utts >= 0 && (req->n_utts == 0 || (req->utts && req->place)), "bad fetch request");
     SBV2_REQUIRE(!(req->loudness && req->limiter), "a fetch request takes a loudness target or a limiter, not both");
+    if (marks) {   // what needs no run is refused before the handle is looked at
+        check_marks_static(marks);
+        (void)pcm_format_spec(req->fmt);
+    }
     SBV2_REQUIRE(p && dst && out_count, "bad arguments");
     const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter}
                            : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr}
@@ -573,7 +651,18 @@ int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fet
     static const int32_t no_rows[1] = {0};
     static const int64_t no_place[1] = {0};
     fetch_formatted(p, ticket, req->fmt, gain, req->n_utts ? req->place : no_place, req->joined_len, req->flac ? Sink::kFlac : Sink::kPcm, dst,
-                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts);
+                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks);
+    API_END
+}
+int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes, int64_t* out_count,
+                                double* stats) {
+    return sbv2_pipeline_fetch_request_marks(p, ticket, req, dst, capacity_bytes, out_count, stats, nullptr);
+}
+
+int sbv2_marks_spans(const int64_t* durations, int64_t n_tokens, int32_t hop, int64_t place, const sbv2_pcm_format* fmt, int64_t* start, int64_t* end) {
+    API_BEGIN
+    const PcmFmtSpec spec = pcm_format_spec(fmt);
+    marks_spans(durations, n_tokens, hop, place, spec, start, end);
     API_END
 }
 

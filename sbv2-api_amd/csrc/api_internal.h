@@ -10,6 +10,7 @@
 #include "flac_encode.h"
 #include "limiter.h"
 #include "loudness.h"
+#include "marks.h"
 #include "models.h"
 #include "pcm_format.h"
 
@@ -32,6 +33,7 @@ struct OutputChain {
     FlacEncoder flac;
     LoudnessMeter meter;
     Limiter limiter;   // (owns a second meter, for its evaluations)
+    Marks marks;       // speech marks: levels of token spans and envelope frames (fetch_request_marks only)
 };
 struct sbv2_pipeline {
     sbv2_bert* bert;

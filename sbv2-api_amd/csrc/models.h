@@ -337,6 +337,10 @@ class VitsModel {
     void copy_pcm(float* host);  // concatenated
     const std::vector<int>& durations() const { return dur_host_; }   // concatenated predicted w_ceil
     const std::vector<float>& logw() const { return logw_host_; }
+    // the durations the last forward expanded (forced where the batch gave them, predicted otherwise), concatenated; row u's tokens are
+    // [used_offs()[u], used_offs()[u + 1]).  On the host once forward() has returned (speech marks, marks.h).
+    const std::vector<int64_t>& used_durations() const { return used_host_; }
+    const std::vector<int64_t>& used_offs() const { return used_offs_; }
     hipStream_t stream() const { return stream_; }
     void set_trace(bool on) { trace_ = on; }
     int decoder_mode() const { return dec_mode_; }
@@ -494,6 +498,7 @@ class VitsModel {
     std::vector<int64_t> pcm_lens_, pcm_offs_;
     std::vector<int> dur_host_;
     std::vector<float> logw_host_;
+    std::vector<int64_t> used_host_, used_offs_;
     bool trace_ = false;
     std::map<std::string, TraceEntry> traces_;
     SegLayout tl_, fl_;

@@ -12,6 +12,9 @@ struct sbv2_stream {
     sbv2_vits* vits = nullptr;
     int64_t frames = 0, next = 0, chunk = 0;
     bool formatted = false, flac = false;
+    // speech marks (sbv2_stream_marks): the utterance's expanded durations, on the host since the forward's one sync, and the delivered format
+    std::vector<int64_t> durations;
+    PcmFmtSpec spec;
 };
 
 namespace {
@@ -42,6 +45,7 @@ int sbv2_stream_begin(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch,
     s->bert = bert;
     s->vits = vits;
     s->chunk = chunk_frames;
+    s->durations = vits->m->used_durations();
     s->frames = vits->m->stream_begin((int)chunk_frames);
     if (total_samples) *total_samples = s->frames * vits->m->cfg().hop();
     *out = s.release();
@@ -79,6 +83,8 @@ int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch*
     s->bert = bert;
     s->vits = vits;
     s->chunk = chunk_frames;
+    s->durations = vits->m->used_durations();
+    s->spec = spec;
     s->formatted = true;
     s->frames = vits->m->stream_begin((int)chunk_frames, &spec);
     if (total_samples) *total_samples = pcm_format_out_len(spec, s->frames * vits->m->cfg().hop());
@@ -127,6 +133,8 @@ int sbv2_stream_begin_flac(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* b
     s->bert = bert;
     s->vits = vits;
     s->chunk = chunk_frames;
+    s->durations = vits->m->used_durations();
+    s->spec = spec;
     s->formatted = s->flac = true;
     s->frames = vits->m->stream_begin((int)chunk_frames, &spec, true);
     if (total_samples) *total_samples = pcm_format_out_len(spec, s->frames * vits->m->cfg().hop());
@@ -145,6 +153,19 @@ int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, 
         *n_samples = s->vits->m->stream_chunk_flac(s->next, dst, capacity_bytes, n_bytes);
         s->next += s->chunk;
     }
+    API_END
+}
+
+// Host only: the token spans of the stream's utterance at its delivered rate (marks.h; place 0).  Every duration is known once _begin* has
+// returned, so the whole timing is there before the first chunk is decoded.
+int sbv2_stream_marks(sbv2_stream* s, int64_t* tok_start, int64_t* tok_end, int64_t capacity, int64_t* n_tokens) {
+    API_BEGIN
+    SBV2_REQUIRE(s && n_tokens, "bad arguments");
+    const int64_t n = (int64_t)s->durations.size();
+    SBV2_REQUIRE(capacity >= n, "token arrays too small: " + std::to_string(capacity) + " < " + std::to_string(n) + " tokens");
+    SBV2_REQUIRE(n == 0 || (tok_start && tok_end), "bad arguments");
+    marks_spans(s->durations.data(), n, s->vits->m->cfg().hop(), 0, s->spec, tok_start, tok_end);
+    *n_tokens = n;
     API_END
 }
 

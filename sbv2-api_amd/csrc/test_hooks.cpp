@@ -1447,4 +1447,21 @@ int sbv2_debug_copy_segments(int device, const float* src, int64_t nsrc, const i
     API_END
 }
 
+// The level reduction of the speech marks (marks.hip) on host samples: x = n samples (encoding 0 = f32, 1 = s16), segments [starts[i], ends[i]).
+int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n, const int64_t* starts, const int64_t* ends, int64_t nseg, double* sumsq,
+                              double* peak) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE((encoding == 0 || encoding == 1) && n >= 0 && nseg >= 0 && (x || n == 0), "bad arguments");
+    SBV2_REQUIRE(nseg == 0 || (starts && ends && sumsq && peak), "bad arguments");
+    std::vector<int64_t> seg((size_t)(2 * nseg));
+    for (int64_t i = 0; i < nseg; ++i) seg[2 * i] = starts[i], seg[2 * i + 1] = ends[i];
+    DevMem dx(x, (size_t)n * (encoding == 1 ? 2 : 4));
+    Marks m;
+    m.run(dx.p, encoding, n, seg.data(), nseg, nullptr);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    for (int64_t i = 0; i < nseg; ++i) sumsq[i] = m.sumsq_host()[i], peak[i] = m.peak_host()[i];
+    API_END
+}
+
 }  // extern "C"

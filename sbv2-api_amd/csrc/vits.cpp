@@ -770,17 +770,21 @@ void VitsModel::forward(const VitsBatch& b) {
     logw_host_.assign((size_t)total_t, 0.f);
     std::vector<int> Tf(n);
     std::vector<std::vector<int>> used(n);
+    used_host_.assign((size_t)total_t, 0);
+    used_offs_.assign((size_t)n + 1, 0);
     {
         int64_t e = 0;
         for (int u = 0; u < n; ++u) {
             int64_t sum = 0;
             used[u].resize(T[u]);
+            used_offs_[u + 1] = used_offs_[u] + T[u];
             for (int t = 0; t < T[u]; ++t, ++e) {
                 dur_host_[e] = dur_p[tl.start[u] + t];
                 logw_host_[e] = logw_p[tl.start[u] + t];
                 const int64_t dv = b.forced_durations ? b.forced_durations[e] : dur_host_[e];
                 SBV2_REQUIRE(dv >= 0 && dv < (1 << 20), "duration out of range");
                 used[u][t] = (int)dv;
+                used_host_[e] = dv;
                 sum += dv;
             }
             SBV2_REQUIRE(sum < (1 << 24), "utterance too long");

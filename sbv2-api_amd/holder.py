@@ -165,12 +165,24 @@ class TTSModelHolder:
             m.pipe = self._make_pipeline(self.bert, m.vits2)
         return orchestrator.easy_synthesize(m.pipe, sentences, m.style_vectors, style_id, speaker_id, options, noise_seed=noise_seed)
 
-    def easy_synthesize_batched(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, batching=None):
+    def easy_synthesize_marks(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None):
+        """easy_synthesize with speech marks: (bytes, marks) (orchestrator.easy_synthesize_marks)."""
+        options = options or orchestrator.SynthesizeOptions()
+        self.find_and_load_model(ident)
+        m = self._find(ident)
+        sentences = self._sentences(text, options)
+        if m.pipe is None:
+            m.pipe = self._make_pipeline(self.bert, m.vits2)
+        return orchestrator.easy_synthesize_marks(m.pipe, sentences, m.style_vectors, style_id, speaker_id, options, noise_seed=noise_seed)
+
+    def easy_synthesize_batched(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, batching=None,
+                                marks=False):
         """easy_synthesize answered through a concurrent.futures.Future of the bytes: the request joins a pipeline run with whatever other
         requests for the same model wait at that moment (batcher.RequestBatcher; one per resident model: rows of different models have
         different weights and never share a run).  batching: the batcher's keyword arguments (max_utts, max_symbols, max_wait_ms), read
         when the model's batcher is created.  The caller serialises calls of this method (rest.py: under its lock); waiting for the
-        Future needs no lock.  A model with a batcher is served through it alone: easy_synthesize on the same ident would share its pipeline."""
+        Future needs no lock.  A model with a batcher is served through it alone: easy_synthesize on the same ident would share its pipeline.
+        marks=True: the Future holds (bytes, marks), as easy_synthesize_marks returns them."""
         options = options or orchestrator.SynthesizeOptions()
         self.find_and_load_model(ident)
         m = self._find(ident)
@@ -182,6 +194,8 @@ class TTSModelHolder:
                 m.batcher = batcher.RequestBatcher(m.pipe, **(batching or {}))
                 for _ in range(m.streams):   # a stream of this model is open: the request queues until it is closed
                     m.batcher.pause()
+        if marks:
+            return m.batcher.submit(sentences, m.style_vectors, style_id, speaker_id, options, noise_seed=noise_seed, marks=True)
         return m.batcher.submit(sentences, m.style_vectors, style_id, speaker_id, options, noise_seed=noise_seed)
 
     def _sentences(self, text, options):
@@ -195,7 +209,8 @@ class TTSModelHolder:
     def easy_synthesize_stream(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, chunk_frames=256):
         """The request as ONE utterance, delivered while it is synthesised (orchestrator.easy_synthesize_stream): a generator over the bytes of
         the FLAC stream or WAV (an orchestrator.SynthesisStream: close() it when it is abandoned before its end).  `text`: a str, parsed as a whole (as split_sentences = False does), or the already parsed text as a one-entry
-        list.  Errors of the request are raised here, before the first piece."""
+        list.  Errors of the request are raised here, before the first piece.  The stream's `.marks` holds the token and word timing of the whole
+        utterance from the start (no levels: see orchestrator.easy_synthesize_stream)."""
         options = options or orchestrator.SynthesizeOptions()
         self.find_and_load_model(ident)
         m = self._find(ident)

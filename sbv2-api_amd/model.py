@@ -279,6 +279,48 @@ def debug_limiter(signals, sample_rate: int, limiter: Limiter, device: int = 0):
     return np.split(out[:x.size], np.cumsum(lens)[:-1]), stats
 
 
+class Marks:
+    """Speech marks of one fetched signal (struct sbv2_marks): per token of the listed rows, in row then token order, the delivered-sample span
+    [start, end) and, when levels were asked for, sumsq / peak of the delivered samples in it (s16 as integers; None otherwise); env_sumsq /
+    env_peak per envelope frame of env_hop delivered samples (None without an envelope); out_len = the delivered samples of the signal."""
+
+    def __init__(self, start, end, sumsq=None, peak=None, env_hop=0, env_sumsq=None, env_peak=None, out_len=0):
+        self.start, self.end, self.sumsq, self.peak = start, end, sumsq, peak
+        self.env_hop, self.env_sumsq, self.env_peak, self.out_len = int(env_hop), env_sumsq, env_peak, int(out_len)
+
+    def arrays(self):
+        return [a for a in (self.start, self.end, self.sumsq, self.peak, self.env_sumsq, self.env_peak) if a is not None]
+
+
+def level_dbfs(sumsq, n, encoding: str = "f32"):
+    """10 log10(sumsq / n) re full scale (s16: 32767) of a span of n delivered samples; None for an empty or all-zero one."""
+    if n <= 0 or sumsq <= 0:
+        return None
+    return float(10.0 * np.log10(float(sumsq) / n / (32767.0 ** 2 if encoding == "s16" else 1.0)))
+
+
+def marks_spans(durations, hop: int, place: int, fmt: PcmFormat):
+    """(start, end): delivered-sample spans of one row's tokens with `durations` frames each, the row at native sample `place`, in fmt's
+    rate (sbv2_marks_spans; host only)."""
+    d = np.ascontiguousarray(np.asarray(durations, np.int64).reshape(-1))
+    st, en = np.zeros(d.size, np.int64), np.zeros(d.size, np.int64)
+    check(_lib.lib().sbv2_marks_spans(d.ctypes.data_as(i64p), d.size, int(hop), int(place), C.byref(fmt.c), st.ctypes.data_as(i64p),
+                                      en.ctypes.data_as(i64p)))
+    return st, en
+
+
+def debug_segment_levels(x, starts, ends, device: int = 0):
+    """Test hook: the device level reduction on host samples x (int16 or float32) -> (sumsq, peak) per segment [starts[i], ends[i])."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"levels are taken of int16 or float32 samples, not {x.dtype}")
+    st, en = (np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1)) for a in (starts, ends))
+    ss, pk = np.zeros(st.size, np.float64), np.zeros(st.size, np.float64)
+    check(_lib.lib().sbv2_debug_segment_levels(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, int(x.dtype == np.int16), x.size,
+                                               st.ctypes.data_as(i64p), en.ctypes.data_as(i64p), st.size, _f64p(ss), _f64p(pk)))
+    return ss, pk
+
+
 class _Batch:
     """Keeps the numpy buffers of one sbv2_batch alive."""
 
@@ -485,11 +527,14 @@ class Pipeline:
         """The signals of fetch_format(b, fmt, place, joined_len), each as one FLAC stream (bytes) encoded on the device; fmt must be s16."""
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
-    def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False):
+    def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
-        read: the requests that share a run are fetched one by one from the same ticket."""
+        read: the requests that share a run are fetched one by one from the same ticket.
+        marks=True: (signal, stats, Marks) through sbv2_pipeline_fetch_request_marks: the listed rows' token spans on the delivered timeline, with
+        their levels (levels=False: timing only, no kernel) and, with env_hop > 0 delivered samples, the envelope.  The signal and stats are
+        those of the same call without marks."""
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
         rw = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
@@ -504,9 +549,23 @@ class Pipeline:
         dst = np.empty(max(size, 1), np.uint8 if flac else fmt.dtype)
         got = C.c_int64(0)
         stats = np.zeros(nstats, np.float64) if nstats else None
-        check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
-                                                     _f64p(stats) if nstats else None))
-        return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
+        if not marks:
+            check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
+                                                         _f64p(stats) if nstats else None))
+            return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
+        ntok = int(sum(int(b.t_lens[r]) for r in rw))
+        out_len = pcm_format_length(fmt, int(joined_len))
+        nenv = -(-out_len // int(env_hop)) if env_hop > 0 else 0
+        m = Marks(np.zeros(ntok, np.int64), np.zeros(ntok, np.int64), np.zeros(ntok, np.float64) if levels else None,
+                  np.zeros(ntok, np.float64) if levels else None, env_hop, np.zeros(nenv, np.float64) if env_hop > 0 else None,
+                  np.zeros(nenv, np.float64) if env_hop > 0 else None, out_len)
+        cm = _lib.Sbv2Marks(ntok, m.start.ctypes.data_as(i64p), m.end.ctypes.data_as(i64p), _f64p(m.sumsq) if levels else None,
+                            _f64p(m.peak) if levels else None, 0, int(env_hop), 0, nenv, _f64p(m.env_sumsq) if env_hop > 0 else None,
+                            _f64p(m.env_peak) if env_hop > 0 else None, 0)
+        check(_lib.lib().sbv2_pipeline_fetch_request_marks(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
+                                                           _f64p(stats) if nstats else None, C.byref(cm)))
+        assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
+        return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats, m
 
     def close(self):
         if self.h:
@@ -571,6 +630,14 @@ class StreamHandle:
         else:
             check(_lib.lib().sbv2_stream_next_format(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.nbytes, C.byref(n)))
         return None if n.value == 0 else self.buf[:n.value].copy()
+
+    def marks(self):
+        """(start, end): the spans of the utterance's tokens in delivered samples of this stream (sbv2_stream_marks; host only, complete from
+        the moment the stream exists).  Streams carry no levels."""
+        n = int(self.b.t_lens[0])
+        st, en, got = np.zeros(n, np.int64), np.zeros(n, np.int64), C.c_int64()
+        check(_lib.lib().sbv2_stream_marks(self.h, st.ctypes.data_as(i64p), en.ctypes.data_as(i64p), n, C.byref(got)))
+        return st[:got.value], en[:got.value]
 
     def close(self):
         if self.h:

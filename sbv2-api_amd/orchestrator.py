@@ -37,10 +37,12 @@ class SynthesizeOptions:
     true-peak ceiling (model.Loudness); it replaces peak normalisation, so normalize=True with a loudness is refused.  That gain is one
     scale, so a target is missed whenever the signal's peak-to-loudness ratio exceeds true_peak_max - loudness (speech: about 20 dB, which
     puts -16 and -14 LUFS out of reach under -1 dBTP).  limiter=True (new) reaches such targets with a look-ahead true-peak limiter that
-    takes peaks down by at most max_reduction dB (model.Limiter); it needs a loudness target."""
+    takes peaks down by at most max_reduction dB (model.Limiter); it needs a loudness target.
+    envelope_hz (new; read by easy_synthesize_marks only): the speech marks carry a level envelope of sample_rate // envelope_hz delivered
+    samples per frame."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
-                 normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0):
+                 normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None):
         if loudness is not None and normalize:
             raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
         if limiter and loudness is None:
@@ -49,6 +51,7 @@ class SynthesizeOptions:
         self.sdp_ratio, self.length_scale, self.style_weight, self.split_sentences = sdp_ratio, length_scale, style_weight, split_sentences
         self.sample_rate, self.encoding, self.normalize = sample_rate, encoding, normalize
         self.loudness, self.true_peak_max = loudness, true_peak_max
+        self.envelope_hz = envelope_hz
 
 
 def load_style(data: bytes) -> np.ndarray:
@@ -141,16 +144,76 @@ class RequestPlan:
         self.utts = [dict(s, style=style, sid=speaker_id) for _, s in live]
 
 
-def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPlan, loudness_stats=None, pcm=None) -> bytes:
+def envelope_hop(options, rate: int) -> int:
+    """Delivered samples per envelope frame of a request: rate // envelope_hz, 0 without an envelope."""
+    hz = getattr(options, "envelope_hz", None)
+    if hz is None:
+        return 0
+    if not (isinstance(hz, int) and not isinstance(hz, bool) and 1 <= hz <= rate):
+        raise model.Sbv2Error(f"envelope_hz must be an integer in [1, {rate}]: {hz!r}")
+    return rate // hz
+
+
+def token_marks(utts, live, rate: int, start, end):
+    """The timing part of the marks dict: utts = the request's live sentences (phones, word2ph), live = their line numbers, start / end = the
+    delivered-sample spans of their tokens, sentence after sentence.  tokens: one entry per phone id (blanks included); words: one entry per
+    word2ph entry (`index` = its position in input_ids), the union of its tokens' spans, empty at the running position when it has none."""
+    tokens, words, e = [], [], 0
+    sec = lambda n: int(n) / float(rate)
+    for line, u in zip(live, utts):
+        first = e
+        for t, ph in enumerate(np.asarray(u["phones"]).reshape(-1)):
+            s0, s1 = int(start[e]), int(end[e])
+            tokens.append({"line": int(line), "index": t, "phone": int(ph), "start": s0, "end": s1, "start_s": sec(s0), "end_s": sec(s1)})
+            e += 1
+        k = first
+        for w, cnt in enumerate(np.asarray(u["word2ph"]).reshape(-1)):
+            cnt = int(cnt)
+            if cnt > 0:
+                s0, s1 = int(start[k]), int(end[k + cnt - 1])
+            else:
+                s0 = s1 = int(start[k]) if k < e else (int(end[e - 1]) if e > first else 0)
+            words.append({"line": int(line), "index": w, "start": s0, "end": s1, "start_s": sec(s0), "end_s": sec(s1)})
+            k += cnt
+        if k != e:
+            raise model.Sbv2Error("sum(word2ph) must equal the text length (tts_util.rs:122-127)")
+    return {"sample_rate": int(rate), "tokens": tokens, "words": words}
+
+
+def marks_dict(utts, live, fmt, m) -> dict:
+    """The JSON-ready speech marks of one request from a model.Marks of its rows: token_marks plus, per token, level_dbfs (10 log10 of the mean
+    square of its delivered samples re full scale; None for an empty or silent span) and peak (largest |sample| re full scale), and `envelope`
+    {hop, level_dbfs [n], peak [n]} when the marks hold one.  The gaps between sentences belong to no token."""
+    d = token_marks(utts, live, fmt.sample_rate, m.start, m.end)
+    full = 32767.0 if fmt.encoding == "s16" else 1.0
+    if m.sumsq is not None:
+        for t, ss, pk in zip(d["tokens"], m.sumsq, m.peak):
+            t["level_dbfs"] = model.level_dbfs(ss, t["end"] - t["start"], fmt.encoding)
+            t["peak"] = float(pk) / full
+    if m.env_hop > 0:
+        n = [min(m.env_hop, m.out_len - f * m.env_hop) for f in range(len(m.env_sumsq))]   # (the last frame may be short)
+        d["envelope"] = {"hop": int(m.env_hop), "level_dbfs": [model.level_dbfs(ss, k, fmt.encoding) for ss, k in zip(m.env_sumsq, n)],
+                         "peak": [float(pk) / full for pk in m.env_peak]}
+    return d
+
+
+def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPlan, loudness_stats=None, pcm=None, marks=None) -> bytes:
     """The answer of one request from rows r0 .. r1 - 1 of run `b` (plan.utts were prepared as those rows): the request's WAV or FLAC bytes,
-    whatever else the run holds.  pcm: the run's plain fetch (pipe.fetch(b)) when the caller already has it."""
+    whatever else the run holds.  pcm: the run's plain fetch (pipe.fetch(b)) when the caller already has it.
+    marks: an optional list that receives the request's speech marks (marks_dict); the signal then always comes from ONE fetch of the
+    request's rows with marks (at the identity format for the default output: the same samples, hence the same bytes)."""
     options, fmt, ln = plan.options, plan.fmt, plan.gain
     lens = b.lens[r0:r1]
-    if ln is not None or not fmt.is_default:
+    if ln is not None or not fmt.is_default or marks is not None:
         # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
-        out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac)
+        if marks is not None:
+            out, stats, m = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, marks=True,
+                                               env_hop=envelope_hop(options, fmt.sample_rate))
+            marks.append(marks_dict(plan.utts, plan.live, fmt, m))
+        else:
+            out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac)
         if stats is not None and loudness_stats is not None:
             loudness_stats.append([float(v) for v in stats])
         if plan.flac:
@@ -183,6 +246,23 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     return finish_request(pipe, b, 0, len(plan.utts), plan, loudness_stats)
 
 
+def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
+                          noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, loudness_stats=None):
+    """(audio_bytes, marks): easy_synthesize's bytes for the same arguments, and the speech marks of that signal (marks_dict): when each
+    phone id and each word (word2ph entry) is spoken, in samples and seconds of the delivered signal, how loud it is there, and with
+    options.envelope_hz a level envelope.  Levels are computed on the device from the delivered samples (also behind the FLAC sink)."""
+    plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
+    envelope_hop(plan.options, plan.fmt.sample_rate)   # a bad envelope_hz is refused before any GPU work
+    if noise_seed is None:
+        noise_seed = model.fresh_noise_seed()
+    b = pipe.prepare(plan.utts, sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=noise_scale,
+                     noise_scale_w=noise_scale_w, noise_seed=noise_seed)
+    pipe.run(b)
+    got = []
+    audio = finish_request(pipe, b, 0, len(plan.utts), plan, loudness_stats, marks=got)
+    return audio, got[0]
+
+
 def wav_stream_header(rate: int, encoding: str, n_samples: int) -> bytes:
     """The header of pcm16_wav ("s16") / float_wav ("f32") for a signal of n_samples whose samples follow later: the same bytes as the header
     of the finished file."""
@@ -197,8 +277,9 @@ class SynthesisStream:
     the pieces run out, when one fails, by close(), and when the object is dropped, iterated or not: the replays of a stream are already
     enqueued when this object is returned, so its end cannot hang on a generator's `finally`, which never runs for a generator nobody started."""
 
-    def __init__(self, st, head, to_bytes):
+    def __init__(self, st, head, to_bytes, marks=None):
         self._st, self._head, self._to_bytes = st, head, to_bytes
+        self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece (streams carry no levels)
 
     def __iter__(self):
         return self
@@ -248,7 +329,8 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     is refused).  encoding "flac": the pieces of one FLAC stream encoded on the device, as its frames complete (chunks that complete none
     yield nothing); "s16" / "f32": the WAV header of pcm16_wav / float_wav written with the known total length, then the chunks' samples.
     normalize, loudness and limiter are refused: they need the whole signal before the first sample can leave.
-    Everything up to the first replay (options, DeBERTa, flow, the header) runs before the iterator is returned."""
+    Everything up to the first replay (options, DeBERTa, flow, the header) runs before the iterator is returned.
+    The iterator's `.marks` holds the utterance's token and word timing (token_marks: every duration is known before the first replay)."""
     options = options or SynthesizeOptions()
     if options.normalize:
         raise model.Sbv2Error("a stream cannot normalise: the peak needs the whole signal (use /synthesize)")
@@ -268,8 +350,13 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     st = model.StreamHandle(bert, vits, dict(live[0], style=style, sid=speaker_id), chunk_frames, fmt=None if fmt.is_default else fmt, flac=flac,
                             sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
                             noise_scale_w=noise_scale_w, noise_seed=noise_seed)
+    try:
+        marks = token_marks([live[0]], [sentences.index(live[0])], fmt.sample_rate, *st.marks())
+    except BaseException:
+        st.close()
+        raise
     if flac:
-        return SynthesisStream(st, None, lambda c: c)
+        return SynthesisStream(st, None, lambda c: c, marks)
     dtype = "<i2" if fmt.encoding == "s16" else "<f4"
     return SynthesisStream(st, wav_stream_header(fmt.sample_rate, fmt.encoding, st.total_samples),
-                           lambda c: np.ascontiguousarray(c, dtype).tobytes())
+                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks)

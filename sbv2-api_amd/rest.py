@@ -14,12 +14,22 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     "s16" / "f32" -> audio/wav, the header written with the known length, then the chunks.  normalize / loudness / limiter
                     are refused (they need the whole signal).  Errors before the first byte map as below; the lock is held until the last byte
                     has left or the client has gone, whichever comes first (_HeldPieces, _ClosingStream).
+                    marks = true (new, default false): the response carries the header X-Speech-Marks, compact JSON {"sample_rate", "tokens":
+                    [[line, index, phone, start, end], ...], "words": [[line, index, start, end], ...]} in delivered samples: the timing of the
+                    whole utterance, known before the first audio byte (a header rather than a leading body part: the body stays the audio alone).
+                    No levels on a stream.  A server in front may cap header sizes: very long texts should ask /synthesize_marks instead.
+  POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
+                    answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
+                    (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
+                    samples per frame.  With batching the request shares runs like /synthesize.
   any error         500 text/plain "Something went wrong: <message>"            sbv2_api/src/error.rs:10-18
   one request at a time (Arc<Mutex<TTSModelHolder>>, main.rs:86,104)             -> a lock around the holder
   make_app(holder, batching={...})  new, off by default: concurrent /synthesize requests share pipeline runs (batcher.py)
 
 FastAPI / starlette are plumbing here; `python -m sbv2_api_amd.rest` is not provided on purpose: a deployment needs the text front end
 (G2P + tokenizer, out of scope: SURVEY.md §2 #7-12) plugged into the holder's `parse_text`."""
+import base64
+import json
 import threading
 from typing import Optional
 
@@ -95,6 +105,12 @@ def make_app(holder, batching=None):
         limiter: bool = False               # look-ahead true-peak limiter for targets the plain gain misses; needs loudness
         max_reduction: float = 6.0          # the limiter's deepest gain reduction (dB)
 
+    class SynthesizeMarksRequest(SynthesizeRequest):
+        envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
+
+    class SynthesizeStreamRequest(SynthesizeRequest):
+        marks: bool = False                 # the utterance's timing in the X-Speech-Marks response header
+
     class _ClosingStream(StreamingResponse):
         """A StreamingResponse that closes its _HeldPieces when the response is over, however it ends: sent to the end, cut by the client's
         disconnect (before the first piece was asked for included) or failed."""
@@ -128,7 +144,8 @@ def make_app(holder, batching=None):
     def options_of(req):
         return orchestrator.SynthesizeOptions(sdp_ratio=req.sdp_ratio, length_scale=req.length_scale, sample_rate=req.sample_rate,
                                               encoding=req.encoding, normalize=req.normalize, loudness=req.loudness,
-                                              true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction)
+                                              true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction,
+                                              envelope_hz=getattr(req, "envelope_hz", None))
 
     def synthesize(req: SynthesizeRequest):
         try:
@@ -151,16 +168,39 @@ def make_app(holder, batching=None):
 
     app.post("/synthesize")(synthesize if batching is None else synthesize_batched)
 
+    @app.post("/synthesize_marks")
+    def synthesize_marks(req: SynthesizeMarksRequest):
+        try:
+            if batching is None:
+                with lock:
+                    audio, marks = holder.easy_synthesize_marks(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
+            else:
+                with lock:
+                    fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching,
+                                                         marks=True)
+                audio, marks = fut.result()
+        except Exception as e:
+            return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
+        return JSONResponse({"audio": base64.b64encode(audio).decode("ascii"), "media_type": "audio/flac" if req.encoding == "flac" else "audio/wav",
+                             "sample_rate": marks["sample_rate"], "marks": marks})
+
+    def stream_marks_header(marks):
+        return json.dumps({"sample_rate": marks["sample_rate"],
+                           "tokens": [[t["line"], t["index"], t["phone"], t["start"], t["end"]] for t in marks["tokens"]],
+                           "words": [[w["line"], w["index"], w["start"], w["end"]] for w in marks["words"]]}, separators=(",", ":"))
+
     @app.post("/synthesize_stream")
-    def synthesize_stream(req: SynthesizeRequest):
+    def synthesize_stream(req: SynthesizeStreamRequest):
         lock.acquire()                        # one request at a time: given back by _HeldPieces.close when the response is over
         try:
-            held = _HeldPieces(lock, holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req)))
+            pieces = holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
+            held = _HeldPieces(lock, pieces)
+            headers = {"X-Speech-Marks": stream_marks_header(pieces.marks)} if req.marks else None
         except BaseException as e:            # before the first byte: the same mapping
             lock.release()
             if not isinstance(e, Exception):
                 raise
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
-        return _ClosingStream(held, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
+        return _ClosingStream(held, media_type="audio/flac" if req.encoding == "flac" else "audio/wav", headers=headers)
 
     return app
