@@ -16,11 +16,10 @@
 #include <cfloat>
 
 #include "common.h"
+#include "device_prims.h"
 #include "ops.h"
 
 namespace sbv2 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 constexpr int kDaT = 64;         // max tokens

@@ -26,6 +26,7 @@
 #include <cstdio>
 
 #include "common.h"
+#include "device_prims.h"
 #include "ops.h"
 
 // No floating-point contraction in this file: the three split-bf16 kernels below (converting, pre-split, pre-split + pipelined) promise the SAME bits
@@ -34,8 +35,6 @@
 #pragma clang fp contract(off)
 
 namespace sbv2 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 constexpr int kFaThreads = 256;
@@ -263,9 +262,8 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
 //              (bits 2 and 3 of the key index swapped), so that the A fragment of PV's k-step s' is one 16-byte read and the B fragment is
 //              simply the eight score registers 8 s' .. 8 s' + 7 converted to bf16 hi / lo
 // ---------------------------------------------------------------------------------------------------------------------------------
-typedef __bf16 fa_bf16x8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void fa_split8(const float (&v)[8], fa_bf16x8& hi, fa_bf16x8& lo) {
+__device__ __forceinline__ void fa_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         hi[t] = (__bf16)v[t];
@@ -318,13 +316,11 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
     // MFMAs).  K image [key][d]: key = tid & 31, d = 4 g .. 4 g + 3 with g = (tid >> 5) + 8 p: four scalar loads (coalesced over the keys), one store
     // per part.  V image [d][key, bits 2 and 3 swapped]: d = (tid >> 3) + 32 p, keys 4 q .. 4 q + 3 with q = tid & 7 (a group of four consecutive keys stays
     // consecutive under the swap): ONE 16-byte load, one store per part.  Same values in the same places: bit-identical results.
-    typedef __bf16 fa_bf16x4 __attribute__((ext_vector_type(4)));
-    typedef float fa_f32x4 __attribute__((ext_vector_type(4)));
     const int sc = tid & 31, sg = tid >> 5;            // K: key, first d group
     const int vq = tid & 7, vd = tid >> 3;             // V: key quad, first d
     const int vqp = (vq & 4) | ((vq & 1) << 1) | ((vq >> 1) & 1);   // the quad's place in the V image (bits 2 and 3 of the key index swapped)
     float kreg[DT][4];
-    fa_f32x4 vreg[DT];
+    f32x4v vreg[DT];
     auto load_tile = [&](int j0) {
         const int jc = min(j0 + sc, T - 1);
 #pragma unroll
@@ -333,7 +329,7 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
             for (int e = 0; e < 4; ++e) kreg[p][e] = Kg[(int64_t)min(4 * (sg + 8 * p) + e, dk - 1) * ld + jc];
         if (j0 + 32 <= T) {   // (uniform) whole tile inside the utterance: 16-byte loads (columns are 16-byte aligned: starts and pitches are multiples of 4)
 #pragma unroll
-            for (int p = 0; p < DT; ++p) vreg[p] = *reinterpret_cast<const fa_f32x4*>(Vg + (int64_t)min(vd + 32 * p, dk - 1) * ld + j0 + 4 * vq);
+            for (int p = 0; p < DT; ++p) vreg[p] = *reinterpret_cast<const f32x4v*>(Vg + (int64_t)min(vd + 32 * p, dk - 1) * ld + j0 + 4 * vq);
         } else {
 #pragma unroll
             for (int p = 0; p < DT; ++p)
@@ -346,28 +342,28 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
 #pragma unroll
         for (int p = 0; p < DT; ++p) {
             const int g = sg + 8 * p;
-            fa_bf16x4 h, l;
+            bf16x4 h, l;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float kv = (4 * g + e < dk && jin) ? kreg[p][e] : 0.f;
                 h[e] = (__bf16)kv;
                 l[e] = (__bf16)(kv - (float)h[e]);
             }
-            *reinterpret_cast<fa_bf16x4*>(kt_hi + sc * PK + g * 8) = h;
-            *reinterpret_cast<fa_bf16x4*>(kt_lo + sc * PK + g * 8) = l;
+            *reinterpret_cast<bf16x4*>(kt_hi + sc * PK + g * 8) = h;
+            *reinterpret_cast<bf16x4*>(kt_lo + sc * PK + g * 8) = l;
         }
 #pragma unroll
         for (int p = 0; p < DT; ++p) {
             const int d = vd + 32 * p;
-            fa_bf16x4 h, l;
+            bf16x4 h, l;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float vv = (d < dk && j0 + 4 * vq + e < T) ? vreg[p][e] : 0.f;
                 h[e] = (__bf16)vv;
                 l[e] = (__bf16)(vv - (float)h[e]);
             }
-            *reinterpret_cast<fa_bf16x4*>(vt_hi + d * PV + vqp * 8) = h;
-            *reinterpret_cast<fa_bf16x4*>(vt_lo + d * PV + vqp * 8) = l;
+            *reinterpret_cast<bf16x4*>(vt_hi + d * PV + vqp * 8) = h;
+            *reinterpret_cast<bf16x4*>(vt_lo + d * PV + vqp * 8) = l;
         }
     };
     load_tile(0);
@@ -402,7 +398,7 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
         }
     }
     // q fragments: lane (column i, half h) holds d = 16 s + 8 h + t
-    fa_bf16x8 qh[KS], ql[KS];
+    bf16x8 qh[KS], ql[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         float v[8];
@@ -434,8 +430,8 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
             for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
-                const fa_bf16x8 ah = *reinterpret_cast<const fa_bf16x8*>(kt_hi + col * PK + (16 * s + 8 * kh) * 2);
-                const fa_bf16x8 al = *reinterpret_cast<const fa_bf16x8*>(kt_lo + col * PK + (16 * s + 8 * kh) * 2);
+                const bf16x8 ah = *reinterpret_cast<const bf16x8*>(kt_hi + col * PK + (16 * s + 8 * kh) * 2);
+                const bf16x8 al = *reinterpret_cast<const bf16x8*>(kt_lo + col * PK + (16 * s + 8 * kh) * 2);
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh[s], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[s], sacc, 0, 0, 0);
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qh[s], sacc, 0, 0, 0);
@@ -507,12 +503,12 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
                 float pv8[8];
 #pragma unroll
                 for (int t = 0; t < 8; ++t) pv8[t] = sacc[8 * sp + t];
-                fa_bf16x8 ph, pl;
+                bf16x8 ph, pl;
                 fa_split8(pv8, ph, pl);
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) {
-                    const fa_bf16x8 vh = *reinterpret_cast<const fa_bf16x8*>(vt_hi + (dt * 32 + col) * PV + (16 * sp + 8 * kh) * 2);
-                    const fa_bf16x8 vl = *reinterpret_cast<const fa_bf16x8*>(vt_lo + (dt * 32 + col) * PV + (16 * sp + 8 * kh) * 2);
+                    const bf16x8 vh = *reinterpret_cast<const bf16x8*>(vt_hi + (dt * 32 + col) * PV + (16 * sp + 8 * kh) * 2);
+                    const bf16x8 vl = *reinterpret_cast<const bf16x8*>(vt_lo + (dt * 32 + col) * PV + (16 * sp + 8 * kh) * 2);
                     cacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, cacc[dt], 0, 0, 0);
                     cacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, cacc[dt], 0, 0, 0);
                     cacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph, cacc[dt], 0, 0, 0);
@@ -551,9 +547,6 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
 //   V image [part][d][64 keys] (row pitch 136 B): the A fragment of ctx += V P (channel row = lane & 31) takes the keys in the order the score
 //           registers hold them, 16 sp + 4 h + {0..3, 8..11}: two 8-byte reads (34-dword pitch: 16 rows on 16 distinct bank pairs).
 // ---------------------------------------------------------------------------------------------------------------------------------
-typedef short fa_s16x4 __attribute__((ext_vector_type(4)));
-typedef short fa_s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) fa_s16x4 fa_lds_s16x4;
 constexpr int kFpKeys = 64;
 constexpr int kFpKS = 160;   // bytes per d row of the K image
 constexpr int kFpVS = 136;   // ... of the V image
@@ -674,7 +667,7 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
             band_s[wave][r][col] = kFaNegBig;
         }
     }
-    fa_bf16x8 qh[KS], ql[KS];
+    bf16x8 qh[KS], ql[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         float v[8];
@@ -696,21 +689,21 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
 
     // fragment addresses inside a tile image (LDS byte offsets)
     const int g16 = lane >> 4, q4 = (lane >> 2) & 3, p4 = lane & 3;
-    const unsigned kt0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)kt);
+    const unsigned kt0 = lds_addr(kt);
     const unsigned kfrag = kt0 + (8 * (g16 >> 1) + q4) * kFpKS + (16 * (g16 & 1) + 4 * p4) * 2;   // + 16 s rows + 64 h2 bytes (+ 4 rows: the upper half)
     const char* vfrag = vt + col * kFpVS + 8 * kh;                                              // + dt 32 rows + (32 sp + 64 h2) bytes (+ 16: keys + 8)
     auto k_frag = [&](int part, int s, int h2) {
         const unsigned a = kfrag + (part * DR + 16 * s) * kFpKS + 64 * h2;
-        const fa_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((fa_lds_s16x4*)(uintptr_t)a);
-        const fa_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((fa_lds_s16x4*)(uintptr_t)(a + 4 * kFpKS));
-        const fa_s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(fa_bf16x8, v);
+        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)a);
+        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(a + 4 * kFpKS));
+        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        return __builtin_bit_cast(bf16x8, v);
     };
     auto v_frag = [&](int part, int dt, int sp, int h2) {
         const char* a = vfrag + (part * DR + dt * 32) * kFpVS + 32 * sp + 64 * h2;
         const uint2 x = *reinterpret_cast<const uint2*>(a), y = *reinterpret_cast<const uint2*>(a + 16);
         const uint4 v = {x.x, x.y, y.x, y.y};
-        return __builtin_bit_cast(fa_bf16x8, v);
+        return __builtin_bit_cast(bf16x8, v);
     };
 
     const int ntiles = (T + kFpKeys - 1) / kFpKeys;
@@ -729,7 +722,7 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
                 for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
 #pragma unroll
                 for (int s = 0; s < KS; ++s) {
-                    const fa_bf16x8 ah = k_frag(0, s, h2), al = k_frag(1, s, h2);
+                    const bf16x8 ah = k_frag(0, s, h2), al = k_frag(1, s, h2);
                     sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh[s], sacc, 0, 0, 0);
                     sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[s], sacc, 0, 0, 0);
                     sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qh[s], sacc, 0, 0, 0);
@@ -801,11 +794,11 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
                     float pv8[8];
 #pragma unroll
                     for (int t = 0; t < 8; ++t) pv8[t] = sacc[8 * sp + t];
-                    fa_bf16x8 ph, pl;
+                    bf16x8 ph, pl;
                     fa_split8(pv8, ph, pl);
 #pragma unroll
                     for (int dt = 0; dt < DT; ++dt) {
-                        const fa_bf16x8 vh = v_frag(0, dt, sp, h2), vl = v_frag(1, dt, sp, h2);
+                        const bf16x8 vh = v_frag(0, dt, sp, h2), vl = v_frag(1, dt, sp, h2);
                         cacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph, cacc[dt], 0, 0, 0);
                         cacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl, cacc[dt], 0, 0, 0);
                         cacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph, cacc[dt], 0, 0, 0);
@@ -852,31 +845,6 @@ __global__ __launch_bounds__(kFaThreads) __attribute__((amdgpu_waves_per_eu(2)))
 // The utterance's last tile, when T is no multiple of 64, is completed by a fix-up pass (keys >= T zero: V must not carry garbage; the segment that
 // straddles T copied element-wise: the DMA of such a segment reads a clamped in-row address instead).
 // ---------------------------------------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void fq_lds_t;
-typedef const __attribute__((address_space(1))) void fq_gbl_t;
-template <int OFF>
-__device__ __forceinline__ fa_s16x4 fq_read_tr(unsigned addr) {
-    fa_s16x4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ uint2 fq_read_b64(unsigned addr) {
-    uint2 v;
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void fq_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        fq_static_for<I + 1, N>(f);
-    }
-}
-template <int N>
-__device__ __forceinline__ void fq_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int DT, int NW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_vits_flash_x3q(const AttnGroup* groups, const float* Q, int ld, const __bf16* Kp, const __bf16* Vp,
@@ -896,7 +864,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     float* erv_s = erk_s + kFaBand * DR;
     float (*rk_s)[kFaBand][32] = reinterpret_cast<float (*)[kFaBand][32]>(erv_s + kFaBand * DR);
     float (*band_s)[kFaBand][32] = rk_s + NW;
-    const unsigned lds_k0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)fq_smem);
+    const unsigned lds_k0 = lds_addr(fq_smem);
     const unsigned lds_v0 = lds_k0 + 2 * IMG;
     const unsigned lds_dummy = lds_k0 + 4 * IMG + sizeof(float) * (2 * kFaBand * DR + 2 * NW * kFaBand * 32);   // NW x 64 floats
     // the lo parts of q: in LDS as B fragments [NW][KS][64 lanes][16 bytes] for the 4-wave workgroup (one wave per SIMD, the registers go to deeper
@@ -939,13 +907,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const char* ub = reinterpret_cast<const char*>(base + poff + (int64_t)part * pstride + (int64_t)min(blk, nblk - 1) * 8 * ldp + u * 64);   // wave-uniform
             const unsigned dst = img + part * PART + blk * 1024;
             if (whole) {
-                __builtin_amdgcn_global_load_lds((fq_gbl_t*)(ub + ((blk & 1) ? loff_odd : loff_even)), (fq_lds_t*)(uintptr_t)dst, 16, 0, 0);
+                dma16(ub + ((blk & 1) ? loff_odd : loff_even), dst);
             } else {
                 // a segment that is not whole inside the utterance reads a clamped in-row address instead (the fix-up pass rewrites it)
                 const int js = 8 * (gseg ^ ((blk & 1) ? odd_xor : 0));
                 const int jq = u * 64 + js;
                 const int colq = jq + 8 <= T ? jq : max(min(jq, T - 8), 0);
-                __builtin_amdgcn_global_load_lds((fq_gbl_t*)(ub + ((int64_t)drow * ldp + (colq - u * 64)) * 2), (fq_lds_t*)(uintptr_t)dst, 16, 0, 0);
+                dma16(ub + ((int64_t)drow * ldp + (colq - u * 64)) * 2, dst);
             }
         }
     };
@@ -1010,7 +978,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
     }
     // q: the hi parts stay in registers; the lo parts live in LDS (24 registers the pipelined loop needs), read with the K fragments of their k-step
-    fa_bf16x8 qh[KS], qlr[QL_LDS ? 1 : KS];
+    bf16x8 qh[KS], qlr[QL_LDS ? 1 : KS];
     const unsigned ql_a = lds_ql + (wave * KS * 64 + lane) * 16;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -1021,7 +989,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             const float x = Qg[(int64_t)min(d, dk - 1) * ld + ic];
             v[t] = d < dk ? x : 0.f;
         }
-        fa_bf16x8 qlo;
+        bf16x8 qlo;
         fa_split8(v, qh[s], qlo);
         if constexpr (QL_LDS) asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(ql_a), "v"(qlo), "n"(s * 1024) : "memory");
         else qlr[s] = qlo;
@@ -1036,22 +1004,22 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const unsigned kb_hi = (krow + 4) * 128 + ((ksegl ^ (4 * (((krow + 4) >> 1) & 1))) << 4) + (p4 & 1) * 8;      // rows d + 4 .. d + 7
     const unsigned vb = col * 128 + (((col >> 1) & 7) << 4) + 8 * kh;                                            // segment 0 (segment g: ^ (g << 4))
     // the wave's row of rk_s / band_s (+ rr * 128), and a dummy slot the band stores of elements outside the band go to
-    const unsigned rk_a = (unsigned)(uintptr_t)((__attribute__((address_space(3))) float*)&rk_s[wave][0][col]);
+    const unsigned rk_a = lds_addr(&rk_s[wave][0][col]);
     constexpr unsigned band_off = NW * kFaBand * 32 * 4;   // band_s[wave][rr][col] = rk_s[wave][rr][col] + band_off
 
     struct KF {
-        fa_s16x4 hl, hh, ll, lh;   // hi part: rows d .. d + 3 | d + 4 .. d + 7; lo part
-        fa_bf16x8 ql;              // the lo part of q of the same k-step
+        s16x4 hl, hh, ll, lh;   // hi part: rows d .. d + 3 | d + 4 .. d + 7; lo part
+        bf16x8 ql;              // the lo part of q of the same k-step
     };
     struct VF {
         uint2 h0, h1, l0, l1;      // hi part: keys .. + 3 | + 8 .. + 11; lo part
     };
     auto read_k = [&](KF& f, auto sc, unsigned alo, unsigned ahi) {
         constexpr int s = decltype(sc)::value;
-        f.hl = fq_read_tr<s * 2048>(alo);
-        f.hh = fq_read_tr<s * 2048>(ahi);
-        f.ll = fq_read_tr<PART + s * 2048>(alo);
-        f.lh = fq_read_tr<PART + s * 2048>(ahi);
+        f.hl = lds_read_tr<s * 2048>(alo);
+        f.hh = lds_read_tr<s * 2048>(ahi);
+        f.ll = lds_read_tr<PART + s * 2048>(alo);
+        f.lh = lds_read_tr<PART + s * 2048>(ahi);
         if constexpr (QL_LDS) {
             const unsigned qa = ql_a;   // (a local: an asm operand cannot name a captured variable)
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f.ql) : "v"(qa), "n"(s * 1024));
@@ -1059,26 +1027,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     };
     auto read_v = [&](VF& f, auto dtc, unsigned a0, unsigned a1) {
         constexpr int dt = decltype(dtc)::value;
-        f.h0 = fq_read_b64<dt * 4096>(a0);
-        f.h1 = fq_read_b64<dt * 4096>(a1);
-        f.l0 = fq_read_b64<PART + dt * 4096>(a0);
-        f.l1 = fq_read_b64<PART + dt * 4096>(a1);
+        f.h0 = lds_read_b64<dt * 4096>(a0);
+        f.h1 = lds_read_b64<dt * 4096>(a1);
+        f.l0 = lds_read_b64<PART + dt * 4096>(a0);
+        f.l1 = lds_read_b64<PART + dt * 4096>(a1);
     };
     auto k_hi = [](const KF& f) {
-        const fa_s16x8 v = {f.hl[0], f.hl[1], f.hl[2], f.hl[3], f.hh[0], f.hh[1], f.hh[2], f.hh[3]};
-        return __builtin_bit_cast(fa_bf16x8, v);
+        const s16x8 v = {f.hl[0], f.hl[1], f.hl[2], f.hl[3], f.hh[0], f.hh[1], f.hh[2], f.hh[3]};
+        return __builtin_bit_cast(bf16x8, v);
     };
     auto k_lo = [](const KF& f) {
-        const fa_s16x8 v = {f.ll[0], f.ll[1], f.ll[2], f.ll[3], f.lh[0], f.lh[1], f.lh[2], f.lh[3]};
-        return __builtin_bit_cast(fa_bf16x8, v);
+        const s16x8 v = {f.ll[0], f.ll[1], f.ll[2], f.ll[3], f.lh[0], f.lh[1], f.lh[2], f.lh[3]};
+        return __builtin_bit_cast(bf16x8, v);
     };
     auto v_hi = [](const VF& f) {
         const uint4 v = {f.h0.x, f.h0.y, f.h1.x, f.h1.y};
-        return __builtin_bit_cast(fa_bf16x8, v);
+        return __builtin_bit_cast(bf16x8, v);
     };
     auto v_lo = [](const VF& f) {
         const uint4 v = {f.l0.x, f.l0.y, f.l1.x, f.l1.y};
-        return __builtin_bit_cast(fa_bf16x8, v);
+        return __builtin_bit_cast(bf16x8, v);
     };
     // the reads are asm the compiler does not count: waits are explicit and tied to the registers they release
     auto wait_k = [](KF& f, auto nc) {
@@ -1101,13 +1069,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     auto step_barrier = [&](int t) {
         const int uy = t < 0 ? 1 : (t & 1 ? (t - 1) / 2 + 1 : t / 2 + 1);   // tile of the younger group (K tile for even t, V tile for odd t)
         if (t == t_fix && has_tail) {
-            fq_wait_vm<0>();
+            wait_vm<0>();
             __builtin_amdgcn_s_barrier();
             fixup_tail();
             __syncthreads();
         } else {
-            if (t >= 0 && uy < ntiles) fq_wait_vm<NI>();
-            else fq_wait_vm<0>();
+            if (t >= 0 && uy < ntiles) wait_vm<NI>();
+            else wait_vm<0>();
             __builtin_amdgcn_s_barrier();
         }
         // requests: odd t (and -1): K tile (t + 3) / 2; even t: V tile t / 2 + 1.  (Dealt into the step's first MFMA gaps instead they cost more than they hid:
@@ -1129,7 +1097,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         read_k(kf[0], std::integral_constant<int, 0>{}, alo, ahi);
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        fq_static_for<0, 3 * KS>([&](auto nc) {
+        static_for<0, 3 * KS>([&](auto nc) {
             constexpr int n = decltype(nc)::value;
             constexpr int s = n / 3, term = n % 3;
             KF& f = kf[s % 2];
@@ -1156,7 +1124,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         constexpr bool NEXT = decltype(nextc)::value;
         const int j0 = t * 32;
         float mn = 0.f, alpha = 0.f, ps = 0.f, mtn = kFaNegBig;
-        fa_bf16x8 ph[2], pl[2];
+        bf16x8 ph[2], pl[2];
         const unsigned va0 = lds_v0 + ((t >> 1) & 1) * IMG + (vb ^ ((t & 1) << 6));   // (sp = 0, keys + 0); sp: ^ 32; keys + 8: ^ 16
         const bool diag = j0 <= i0 + 31 + w && j0 + 31 >= i0 - w, tail = j0 + 32 > T;   // (wave-uniform)
         if (diag) {
@@ -1250,9 +1218,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         };
         if constexpr (NEXT) {
             qk(nxt, t + 1, slice);
-            if constexpr (3 * KS < 18) fq_static_for<3 * KS, 18>([&](auto nc) { slice(nc); });
+            if constexpr (3 * KS < 18) static_for<3 * KS, 18>([&](auto nc) { slice(nc); });
         } else {
-            fq_static_for<0, 18>([&](auto nc) { slice(nc); });
+            static_for<0, 18>([&](auto nc) { slice(nc); });
         }
         read_vg(std::integral_constant<int, 3>{});
         if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
@@ -1293,14 +1261,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             __builtin_amdgcn_sched_barrier(0);
         };
         if constexpr (DT == 1) {   // one accumulator: its two groups in order (the second key half of P split in front of them)
-            fq_static_for<0, 4>([&](auto nc) { split2(std::integral_constant<int, 1>{}, std::integral_constant<int, 2 * decltype(nc)::value>{}); });
+            static_for<0, 4>([&](auto nc) { split2(std::integral_constant<int, 1>{}, std::integral_constant<int, 2 * decltype(nc)::value>{}); });
             wait_vg(std::integral_constant<int, 0>{});
-            fq_static_for<0, 3>([&](auto tc) { pv_mfma(std::integral_constant<int, 0>{}, tc); });
+            static_for<0, 3>([&](auto tc) { pv_mfma(std::integral_constant<int, 0>{}, tc); });
             wait_vg(std::integral_constant<int, 1>{});
-            fq_static_for<0, 3>([&](auto tc) { pv_mfma(std::integral_constant<int, 1>{}, tc); });
-            fq_static_for<6, 14>([&](auto nc) { bgap(nc); });
+            static_for<0, 3>([&](auto tc) { pv_mfma(std::integral_constant<int, 1>{}, tc); });
+            static_for<6, 14>([&](auto nc) { bgap(nc); });
         } else {
-            fq_static_for<0, NG / 2>([&](auto pc) {
+            static_for<0, NG / 2>([&](auto pc) {
                 constexpr int p = decltype(pc)::value, g0 = 2 * p, g1 = g0 + 1;
                 wait_vg(std::integral_constant<int, g0>{});
                 pv_mfma(std::integral_constant<int, g0>{}, std::integral_constant<int, 0>{});
@@ -1319,7 +1287,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 if constexpr (p == 0) read_vg(std::integral_constant<int, 5>{});      // into group 1's set
                 bgap(std::integral_constant<int, 6 * p + 5>{});
             });
-            if constexpr (3 * NG < 14) fq_static_for<3 * NG, 14>([&](auto nc) { bgap(nc); });
+            if constexpr (3 * NG < 14) static_for<3 * NG, 14>([&](auto nc) { bgap(nc); });
         }
         mt = mtn;   // (of the next step, when it is interior; a step on the band or at the utterance's end computes its own)
     };

@@ -23,31 +23,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
 
 namespace sbv2 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // operand precision of the matrix-core path: bf16 (1 MFMA per product), split bf16 hi/lo (3 MFMAs, f32-grade) or fp16 (1 MFMA,
 // 11-bit significands: 8x finer than bf16 at the same rate; f32 accumulation and f32 storage in every mode)
 enum { PREC_BF16 = 0, PREC_BF16X3 = 1, PREC_F16 = 2 };
-__device__ __forceinline__ f32x16 mfma_32x32x16(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 mfma_32x32x16(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-
-// compile-time loop: indices are constants before SROA runs, so per-thread staging arrays stay in registers (a late-unrolled
-// `for` over a 12-entry float4 array was left in scratch by hipcc)
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 constexpr int kClThreads = 256;
 constexpr int kClNT = 256;
@@ -305,10 +287,10 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     if (SPLIT) {
-                        acc[i][j] = mfma_32x32x16(f.al[i], f.bh[j], acc[i][j]);
-                        acc[i][j] = mfma_32x32x16(f.ah[i], f.bl[j], acc[i][j]);
+                        acc[i][j] = mfma32(f.al[i], f.bh[j], acc[i][j]);
+                        acc[i][j] = mfma32(f.ah[i], f.bl[j], acc[i][j]);
                     }
-                    acc[i][j] = mfma_32x32x16(f.ah[i], f.bh[j], acc[i][j]);
+                    acc[i][j] = mfma32(f.ah[i], f.bh[j], acc[i][j]);
                 }
         };
         Frags fa, fb;
@@ -455,9 +437,8 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
                 if (!mask_s[nfirst + it * 8 - n0]) v = make_float4(0.f, 0.f, 0.f, 0.f);
                 *reinterpret_cast<float4*>(yp + it * ystep) = v;
                 if (YS && p.ys_p) {   // bf16 parts of lrelu(result): 4 channels = 8 bytes of a 32-byte row of chunk co >> 4; the lo plane follows the hi plane
-                    typedef __bf16 cl_bf16x4 __attribute__((ext_vector_type(4)));
                     const float vv[4] = {v.x, v.y, v.z, v.w};
-                    cl_bf16x4 h, l;
+                    bf16x4 h, l;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float x = vv[e] >= 0.f ? vv[e] : vv[e] * p.ys_slope;
@@ -465,8 +446,8 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
                         l[e] = (__bf16)(x - (float)h[e]);
                     }
                     char* qs = static_cast<char*>(p.ys_p) + ((int64_t)(co >> 4) * 2 * p.ys_rows + p.ys_front + pos + it * pstep) * 32 + (co & 15) * 2;
-                    *reinterpret_cast<cl_bf16x4*>(qs) = h;
-                    *reinterpret_cast<cl_bf16x4*>(qs + p.ys_rows * 32) = l;
+                    *reinterpret_cast<bf16x4*>(qs) = h;
+                    *reinterpret_cast<bf16x4*>(qs + p.ys_rows * 32) = l;
                 }
             }
             continue;
@@ -492,9 +473,8 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
                 }
                 *reinterpret_cast<float4*>(yp) = v;
                 if (YS && p.ys_p) {   // (uniform; compiled into the YS instantiation only: in every kernel of the family it cost 40 registers) bf16 parts of lrelu(result): 4 channels = 8 bytes of a 32-byte row of chunk co >> 4; the lo plane follows the hi plane
-                    typedef __bf16 cl_bf16x4 __attribute__((ext_vector_type(4)));
                     const float vv[4] = {v.x, v.y, v.z, v.w};
-                    cl_bf16x4 h, l;
+                    bf16x4 h, l;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float x = vv[e] >= 0.f ? vv[e] : vv[e] * p.ys_slope;
@@ -502,8 +482,8 @@ __global__ __launch_bounds__(kClThreads * WM) void conv_cl_kernel(const ClKernel
                         l[e] = (__bf16)(x - (float)h[e]);
                     }
                     char* qs = static_cast<char*>(p.ys_p) + ((int64_t)(co >> 4) * 2 * p.ys_rows + p.ys_front + pos) * 32 + (co & 15) * 2;
-                    *reinterpret_cast<cl_bf16x4*>(qs) = h;
-                    *reinterpret_cast<cl_bf16x4*>(qs + p.ys_rows * 32) = l;
+                    *reinterpret_cast<bf16x4*>(qs) = h;
+                    *reinterpret_cast<bf16x4*>(qs + p.ys_rows * 32) = l;
                 }
             }
             pos += pstep;

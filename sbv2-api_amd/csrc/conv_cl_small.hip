@@ -16,17 +16,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
 
 namespace sbv2 {
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void gbl_void_t;
 
 constexpr int kSlots = 8;
 
@@ -40,19 +34,6 @@ struct ClSmallParams {
     int slot_bytes; // ring slot: ntaps * 2 KB of weight fragments, then xg KB of raw window
     int ahead;      // chunks in flight (1 .. 3)
 };
-
-__device__ __forceinline__ void wait_vm_dyn(int n) {
-    // s_waitcnt takes an immediate: n is wave-uniform, one scalar branch
-    switch (n) {
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15)
-        W_(16) W_(17) W_(18) W_(19) W_(20) W_(21) W_(22) W_(23) W_(24) W_(25) W_(26) W_(27) W_(28) W_(29) W_(30) W_(31)
-        W_(32) W_(33) W_(34) W_(35) W_(36) W_(37) W_(38) W_(39) W_(40) W_(41) W_(42) W_(43) W_(44) W_(45) W_(46) W_(47)
-        W_(48) W_(49) W_(50) W_(51) W_(52) W_(53) W_(54) W_(55) W_(56) W_(57) W_(58) W_(59) W_(60) W_(61) W_(62)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
 
 constexpr int kLoaders = 3;      // helper waves: wave 1 issues the DMAs, waves 2 and 3 convert the windows; wave 0 only runs the MFMA chain
 constexpr int kConverters = 2;
@@ -94,10 +75,10 @@ __global__ __launch_bounds__(64 * (kLoaders + 1)) void conv_cl_small_kernel(cons
         char* dst = ring + (c & (kSlots - 1)) * kp.slot_bytes;
         const char* ws = wsrc + c * wstep;
         for (int i = 0; i < 2 * ntaps; ++i)
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(ws + i * 1024), (lds_void_t*)(dst + i * 1024), 16, 0, 0);
+            dma16(ws + i * 1024, lds_addr(dst + i * 1024));
 #pragma unroll
         for (int g = 0; g < kMaxXg; ++g)
-            if (g < kp.xg) __builtin_amdgcn_global_load_lds((gbl_void_t*)(xsrc[g] + c * 64), (lds_void_t*)(dst + wbytes + g * 1024), 16, 0, 0);
+            if (g < kp.xg) dma16(xsrc[g] + c * 64, lds_addr(dst + wbytes + g * 1024));
     };
     // raw window of chunk c (slot c & 3) -> converted image (buffer c & 1); conv_cl.hip's store_x, with LDS as the source
     const int nxf4 = kp.xrows * 4;

@@ -29,19 +29,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
 
 // No floating-point contraction in this file: the epilogue's (sum) * beta + previous contents must round the same way whatever shape the surrounding
 // control flow has (an fma there moved the waveform by 9e-7 between two epilogue variants that promise the same bits)
 #pragma clang fp contract(off)
 
 namespace sbv2 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void clx_lds_t;
-typedef const __attribute__((address_space(1))) void clx_gbl_t;
 
 constexpr int kClxNT = 256;          // positions per workgroup
 constexpr int kClxXR = 320;          // window rows per buffer (256 + span <= 64)
@@ -54,45 +48,6 @@ struct ClxKernelParams {
     int gy;        // row tiles (of 64 rows)
 };
 
-template <int I, int N, class F>
-__device__ __forceinline__ void clx_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        clx_static_for<I + 1, N>(f);
-    }
-}
-template <int N>
-__device__ __forceinline__ void clx_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void clx_wait_vm_dyn(int n) {   // wave-uniform n
-    switch (n) {
-        case 0: clx_wait_vm<0>(); break;
-        case 1: clx_wait_vm<1>(); break;
-        case 2: clx_wait_vm<2>(); break;
-        case 3: clx_wait_vm<3>(); break;
-        case 4: clx_wait_vm<4>(); break;
-        case 5: clx_wait_vm<5>(); break;
-        case 6: clx_wait_vm<6>(); break;
-        case 7: clx_wait_vm<7>(); break;
-        case 8: clx_wait_vm<8>(); break;
-        case 9: clx_wait_vm<9>(); break;
-        default: clx_wait_vm<10>(); break;
-    }
-}
-template <int OFF>
-__device__ __forceinline__ bf16x8 clx_read_b128o(unsigned addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-__device__ __forceinline__ unsigned clx_opaque(unsigned x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
-__device__ __forceinline__ void clx_mfma16(f32x4v& c, const bf16x8& a, const bf16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
 // 4 waves, 64 rows x 256 positions per workgroup (wave: 64 rows x 64 positions = 4 x 4 accumulator tiles of 16 x 16); kClxWR weight ring slots (4 KB: one
 // step), kClxXB window buffers of XR rows (both parts).  <= 53 KB of LDS and <= 168 registers: THREE workgroups per CU.
 // EDGE: the launch has a partial last position tile (N % 256 != 0): its guarded epilogue is compiled in.  (Compiled into every instance, that rarely taken
@@ -116,7 +71,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
     constexpr int XPART = XR * 32, XBUF = 2 * XPART;   // (XR = window rows per buffer: 320 holds every tap span <= 64; 288 those <= 32); hi plane, then lo plane
     const ConvClxParams& p = kp.p;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
+    const unsigned lds0 = lds_addr(smem);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -147,8 +102,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
     const unsigned wdst0 = lds0 + (wave & (NWW - 1)) * 2048;
     unsigned wdoff = 0;                                             // ring offset the next half pair goes to
     auto dma_w = [&]() {
-        __builtin_amdgcn_global_load_lds((clx_gbl_t*)(wptr + lane16), (clx_lds_t*)(uintptr_t)(wdst0 + wdoff), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((clx_gbl_t*)(wptr + lane16), (clx_lds_t*)(uintptr_t)(wdst0 + wdoff), 16, 1024, 0);   // (the immediate offset applies to both addresses)
+        dma16(wptr + lane16, wdst0 + wdoff);
+        dma16<1024>(wptr + lane16, wdst0 + wdoff);
         wptr += WSLOT;
         wdoff = wdoff + WSLOT == WBYTES ? 0 : wdoff + WSLOT;
     };
@@ -174,7 +129,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
     auto dma_x = [&](auto ic) {                // piece i of the next window; the last piece of a window advances to the following chunk
         constexpr int i = decltype(ic)::value;
         if (i < nmine) {
-            __builtin_amdgcn_global_load_lds((clx_gbl_t*)(xptr[i] + lane16), (clx_lds_t*)(uintptr_t)(xdst[i] + xdoff), 16, 0, 0);
+            dma16(xptr[i] + lane16, xdst[i] + xdoff);
             xptr[i] += 2 * xplane;
         }
     };
@@ -204,10 +159,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
     auto mfma_one = [&](const bf16x8 (&a)[4], const bf16x8 (&b)[4], auto nc) {   // MFMA n of a 16-instruction set: row tile n / 4, position tile n % 4
         constexpr int n = decltype(nc)::value;
-        // (inline asm: the accumulator stays in ITS registers.  Given the builtin, hipcc wrote each result to another register quad and took the old one for
-        // a fragment, then restored the mapping with ~200 v_mov per loop iteration.  An accumulate chain needs no wait states; the A / B operands were
-        // written by LDS reads waited for before the set.)
-        clx_mfma16(acc[n >> 2][n & 3], a[n >> 2], b[n & 3]);
+        mfma16_bf16(acc[n >> 2][n & 3], a[n >> 2], b[n & 3]);
     };
     // The operands of a set of MFMAs stay allocated until the set has been issued: the fragment reads dealt between the MFMAs return asynchronously, and the
     // compiler (which sees neither: inline asm) may otherwise hand a read the registers of an operand whose last MFMA in program order is still queued in
@@ -241,7 +193,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
         dma_w();
         dma_w();               // pair 0
     } else {
-        clx_static_for<0, kClxPW>([&](auto ic) { dma_x(ic); });
+        static_for<0, kClxPW>([&](auto ic) { dma_x(ic); });
         next_window();
     }
     unsigned wroff = 0;        // ring offset of the pair slot the fragment reads take
@@ -254,29 +206,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
 
     for (int chunk = 0; chunk < nchunks; chunk += 2) {
         const int s0 = chunk * NTAPS;
-        clx_static_for<0, NTAPS>([&](auto jc) {
+        static_for<0, NTAPS>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int ra = 2 * j, rb = 2 * j + 1;         // steps a, b relative to s0
             constexpr int tapa = ra % NTAPS, bufa = (ra / NTAPS) & 1, tapb = rb % NTAPS, bufb = (rb / NTAPS) & 1;
             // ---- TOP
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (wwave) clx_wait_vm<0>();
-            else if constexpr (j == J0 || j == 0) clx_wait_vm<0>();
+            if (wwave) wait_vm<0>();
+            else if constexpr (j == J0 || j == 0) wait_vm<0>();
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
             Frags f;
-            // (fragment addresses are formed where they are used, from opaque copies of the lane bases: hoisted out of the loop they took up to 33 registers)
-            const unsigned aaddr = clx_opaque(abase) + wroff;
-            const unsigned b0 = clx_opaque(bhlane) + (unsigned)(lg < 2 ? tapa * shs32 + bufa * XBUF : tapb * shs32 + bufb * XBUF);
+            const unsigned aaddr = opaque(abase) + wroff;
+            const unsigned b0 = opaque(bhlane) + (unsigned)(lg < 2 ? tapa * shs32 + bufa * XBUF : tapb * shs32 + bufb * XBUF);
             wroff ^= 2 * WSLOT;
             // ---- S0: the previous pair's hi x hi; A_lo, B_hi of this pair; the weight blocks of the next pair
             {
                 const bool wn = wwave && s0 + 2 * j + 2 < S;
-                clx_static_for<0, 16>([&](auto nc) {
+                static_for<0, 16>([&](auto nc) {
                     constexpr int n = decltype(nc)::value;
                     mfma_one(pend.ah, pend.bh, nc);
-                    if constexpr (n < 4) f.al[n] = clx_read_b128o<n * 2048 + 1024>(aaddr);
-                    else if constexpr (n < 8) f.bh[n - 4] = clx_read_b128o<(n - 4) * 512>(b0);
+                    if constexpr (n < 4) f.al[n] = lds_read_b128<n * 2048 + 1024>(aaddr);
+                    else if constexpr (n < 8) f.bh[n - 4] = lds_read_b128<(n - 4) * 512>(b0);
                     if constexpr (n == 2 || n == 6) {
                         if (wn) dma_w();
                     }
@@ -292,11 +243,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
                 constexpr bool first = j < J0;
                 constexpr int jj = first ? j : j - J0 - (EVEN ? 0 : 1);
                 const bool stx = !wwave && (first ? chunk + 1 < nchunks : chunk + 2 < nchunks);
-                clx_static_for<0, 16>([&](auto nc) {
+                static_for<0, 16>([&](auto nc) {
                     constexpr int n = decltype(nc)::value;
                     mfma_one(f.al, f.bh, nc);
-                    if constexpr (n < 4) f.ah[n] = clx_read_b128o<n * 2048>(aaddr);
-                    else if constexpr (n < 8) f.bl[n - 4] = clx_read_b128o<XPART + (n - 4) * 512>(b0);
+                    if constexpr (n < 4) f.ah[n] = lds_read_b128<n * 2048>(aaddr);
+                    else if constexpr (n < 8) f.bl[n - 4] = lds_read_b128<XPART + (n - 4) * 512>(b0);
                     if constexpr ((EVEN || j != J0) && n < PPP) {
                         constexpr int i = jj * PPP + n;
                         if constexpr (i < kClxPW) {
@@ -313,7 +264,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.ah[0]), "+v"(f.ah[1]), "+v"(f.ah[2]), "+v"(f.ah[3]), "+v"(f.bl[0]), "+v"(f.bl[1]), "+v"(f.bl[2]), "+v"(f.bl[3]));
             __builtin_amdgcn_sched_barrier(0);
             // ---- S2: hi x lo
-            clx_static_for<0, 16>([&](auto nc) {
+            static_for<0, 16>([&](auto nc) {
                 mfma_one(f.ah, f.bl, nc);
                 __builtin_amdgcn_sched_barrier(0);
             });
@@ -326,7 +277,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
         });
     }
     // the last pair's hi x hi
-    clx_static_for<0, 16>([&](auto nc) { mfma_one(pend.ah, pend.bh, nc); });
+    static_for<0, 16>([&](auto nc) { mfma_one(pend.ah, pend.bh, nc); });
     keep4(pend.ah);
     keep4(pend.bh);
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // (the accumulators are read by LDS writes next; the compiler does not see these MFMAs)
@@ -347,7 +298,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
         for (int e = 0; e < 4; ++e) keep4[e] = nq + e < N && (!p.mask || p.mask[min(nq + e, N - 1) >> p.mask_shift] != 0);
         const bool whole4 = nq + 4 <= N;
         const int nqc = whole4 ? nq : max(min(nq, N - 4), 0);   // (a clamped, valid address for the residual rows of a ragged tail: their values are not used)
-        clx_static_for<0, 2>([&](auto hc) {
+        static_for<0, 2>([&](auto hc) {
             constexpr int i2 = decltype(hc)::value;        // rows 32 i2 .. + 31 of the wave's 64
 #pragma unroll
             for (int it2 = 0; it2 < 2; ++it2)
@@ -450,7 +401,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
         // bypass them (same-box A/B profiles/r05o_nt_store_ab.txt: C = 256 k = 3 conv1 238 -> 217 us, C = 128 k = 3 conv2 760 -> 737, step -0.3 ms; a single
         // utterance's 29 MB planes are re-read from L2 / MALL and lose 0.1 ms per call with it: the launch decides by size).  An instance of its own: both
         // store flavours behind a uniform branch in one kernel spilled 132 bytes.
-        clx_static_for<0, 2>([&](auto ic) {
+        static_for<0, 2>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             __builtin_amdgcn_sched_barrier(0);
             tile_write(ic);
@@ -538,7 +489,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kClxWR * 40
         return;
     }
     // ---- the batch's last position tile: the same arithmetic with clamped reads and guarded stores, one row at a time (a handful of workgroups per launch)
-    if constexpr (EDGE) clx_static_for<0, 2>([&](auto ic) {
+    if constexpr (EDGE) static_for<0, 2>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         tile_write(ic);
         const int m = m0 + i * 32 + c4;

@@ -1,6 +1,7 @@
 // NOT BUILT, NOT SHIPPED: round 5's persistent-workgroup form of conv_clx_kernel (a fragment: it sat in ../conv_clx.hip behind conv_clx_kernel and uses its
-// helpers - clx_mfma16, clx_halves, clx_read_b128o, clx_opaque, clx_wait_vm, clx_static_for - and its launch, with `persistent` selecting it for launches of
-// more tiles than the chip has slots that do not accumulate).  Same bits as conv_clx_kernel (tests/test_gpu_parity.py -k clx passed with it in place).
+// launch, with `persistent` selecting it for launches of more tiles than the chip has slots that do not accumulate, and the helpers that now come from
+// ../device_prims.h under these names: mfma16_bf16 (here clx_mfma16), lds_read_b128 (clx_read_b128o), opaque (clx_opaque), wait_vm (clx_wait_vm),
+// static_for (clx_static_for); clx_halves is gone).  Same bits as conv_clx_kernel (tests/test_gpu_parity.py -k clx passed with it in place).
 //
 // Measured on the decoder's own shapes (sbv2_debug_clx_timeline, un-stamped launch time, same box, profiles/r05k_clx_persistent_ab.jsonl; variant 0 = this
 // kernel, 1 = one workgroup per tile): SLOWER on every shape, conv1 (no residual rows: the spill-free path of this kernel) by 5 - 15 %, conv2 by 8 - 37 %

@@ -27,19 +27,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
 
 namespace sbv2 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void bfs_lds_t;
-typedef const __attribute__((address_space(1))) void bfs_gbl_t;
-typedef __attribute__((address_space(3))) s16x4 bfs_lds_s16x4;
 
 struct BfsKernelParams {
     GemmBfsParams p;
@@ -47,33 +37,6 @@ struct BfsKernelParams {
     int gm, gn, total;
     int ksplit;   // SK instances: workgroups per output tile (total = gm * gn * ksplit)
 };
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void bfs_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// LDS reads the compiler does not count (see the kernel): 16 bytes per lane / the transposing 4 x 16-bit read
-template <int OFF>
-__device__ __forceinline__ bf16x8 bfs_read_b128(unsigned addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ s16x4 bfs_read_tr(unsigned addr) {
-    s16x4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
 
 // XOR applied to the 64-byte segment index of row k of the B image (row = RB bytes): rows k .. k + 3 of one segment column then fall on
 // four different quarters of the 256-byte bank row
@@ -163,9 +126,9 @@ __global__ __launch_bounds__(64 * WM * WN * KG) __attribute__((amdgpu_waves_per_
         if (SK) src[q] += (int64_t)kg * nchunks * step[q];
         if (KG > 1) src[q] += (int64_t)grp * nchunks * step[q];
     }
-    const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem) + (KG > 1 ? grp * (NSLOT * SLOT) : 0);
+    const unsigned lds0 = lds_addr(smem) + (KG > 1 ? grp * (NSLOT * SLOT) : 0);
     auto dma = [&](int q, int off) {   // DMA q of the next chunk to stage (chunk image at LDS offset off); advances its source pointer
-        __builtin_amdgcn_global_load_lds((bfs_gbl_t*)src[q], (bfs_lds_t*)(uintptr_t)(lds0 + off + sdst[q]), 16, 0, 0);
+        dma16(src[q], lds0 + off + sdst[q]);
         src[q] += step[q];
     };
 
@@ -194,11 +157,11 @@ __global__ __launch_bounds__(64 * WM * WN * KG) __attribute__((amdgpu_waves_per_
     auto read_one = [&](Frags& f, auto rc, unsigned aaddr, const unsigned (&baddr)[TN]) {
         constexpr int r = decltype(rc)::value;
         if constexpr (r < NRA) {
-            f.a[r / PARTS][r % PARTS] = bfs_read_b128<r * 1024>(aaddr);
+            f.a[r / PARTS][r % PARTS] = lds_read_b128<r * 1024>(aaddr);
         } else {
             constexpr int e = r - NRA, j = e / (2 * PARTS), pp = (e % (2 * PARTS)) / 2, half = e & 1;
-            if constexpr (half == 0) f.blo[j][pp] = bfs_read_tr<pp * B_PART>(baddr[j]);
-            else f.bhi[j][pp] = bfs_read_tr<pp * B_PART + 4 * RB>(baddr[j]);
+            if constexpr (half == 0) f.blo[j][pp] = lds_read_tr<pp * B_PART>(baddr[j]);
+            else f.bhi[j][pp] = lds_read_tr<pp * B_PART + 4 * RB>(baddr[j]);
         }
     };
     auto frag_b = [](const Frags& f, int j, int pp) {
@@ -249,8 +212,8 @@ __global__ __launch_bounds__(64 * WM * WN * KG) __attribute__((amdgpu_waves_per_
     for (int c = 0; c < npre; ++c)
 #pragma unroll
         for (int q = 0; q < PERW; ++q) dma(q, (c / KSUB) * SLOT + (c % KSUB) * CH);
-    if (npre == AHEAD + 1) bfs_wait_vm<(AHEAD + 1 - KSUB) * PERW>();   // slot 0 has landed
-    else bfs_wait_vm<0>();
+    if (npre == AHEAD + 1) wait_vm<(AHEAD + 1 - KSUB) * PERW>();   // slot 0 has landed
+    else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     Frags fa, fb;
     {
@@ -275,8 +238,8 @@ __global__ __launch_bounds__(64 * WM * WN * KG) __attribute__((amdgpu_waves_per_
         constexpr bool BAR = decltype(barc)::value;     // chunk c + 1 opens a new slot
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the fragments of chunk c (requested one chunk ago)
         if (BAR) {
-            if (MAIN) bfs_wait_vm<(AHEAD - KSUB) * PERW>();
-            else bfs_wait_vm<0>();
+            if (MAIN) wait_vm<(AHEAD - KSUB) * PERW>();
+            else wait_vm<0>();
             __builtin_amdgcn_s_barrier();
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -501,8 +464,7 @@ __global__ __launch_bounds__(64 * WM * WN * KG) __attribute__((amdgpu_waves_per_
                 if (toYs) {
                     const int64_t off = (int64_t)m * p.Ys.ld + n;
                     if constexpr (F16) {
-                        typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-                        f16x4v h, l;
+                        f16x4 h, l;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {   // split_store4's f16 pair: finite values beyond f16's range saturate, NaN / infinity pass through
                             const float c = (v[e] != v[e] || fabsf(v[e]) == __builtin_inff()) ? v[e] : fminf(fmaxf(v[e], -65504.f), 65504.f);
@@ -510,20 +472,19 @@ __global__ __launch_bounds__(64 * WM * WN * KG) __attribute__((amdgpu_waves_per_
                             h[e] = (_Float16)c;
                             l[e] = (_Float16)((c - (float)h[e]) * kF16LoScale);
                         }
-                        *reinterpret_cast<f16x4v*>(static_cast<_Float16*>(p.Ys.p) + off) = h;
-                        *reinterpret_cast<f16x4v*>(static_cast<_Float16*>(p.Ys.p) + p.Ys.pstride + off) = l;
+                        *reinterpret_cast<f16x4*>(static_cast<_Float16*>(p.Ys.p) + off) = h;
+                        *reinterpret_cast<f16x4*>(static_cast<_Float16*>(p.Ys.p) + p.Ys.pstride + off) = l;
                     } else {
-                        typedef __bf16 b16x4v __attribute__((ext_vector_type(4)));
                         float res[4] = {v[0], v[1], v[2], v[3]};
 #pragma unroll
                         for (int pp = 0; pp < PARTS; ++pp) {
-                            b16x4v h;
+                            bf16x4 h;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 h[e] = (__bf16)res[e];
                                 res[e] -= (float)h[e];
                             }
-                            *reinterpret_cast<b16x4v*>(static_cast<__bf16*>(p.Ys.p) + (int64_t)pp * p.Ys.pstride + off) = h;
+                            *reinterpret_cast<bf16x4*>(static_cast<__bf16*>(p.Ys.p) + (int64_t)pp * p.Ys.pstride + off) = h;
                         }
                     }
                 }

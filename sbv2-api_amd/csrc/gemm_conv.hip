@@ -23,11 +23,9 @@
 #include <atomic>
 
 #include "common.h"
+#include "device_prims.h"
 
 namespace sbv2 {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 constexpr int kMaxSpan = 64;  // max (max shift - floor4(min shift)), host-checked
@@ -52,7 +50,7 @@ struct Mfma<32> {
 };
 template <>
 struct Mfma<16> {
-    using acc_t = f32x4;
+    using acc_t = f32x4v;
     static constexpr int KS = 4, NACC = 4;
     static __device__ __forceinline__ acc_t run(float a, float b, acc_t c) {
         return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -78,12 +76,6 @@ __device__ __forceinline__ float4 load4_guard(const float* src, int j, int lo, i
 // of overlapping, and 64 x 128 tiles pulling 7.5 TB/s from L2 at that rate: the ring removes the staging instructions, and having no
 // staging registers makes 128 x 128 tiles (half the L2 bytes per FLOP) affordable.  Same fragments, same MFMA order, same epilogue: same bits.
 constexpr int kRingSlots = 4;
-template <int N>
-__device__ __forceinline__ void ring_wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-typedef __attribute__((address_space(3))) void ring_lds_t;
-typedef const __attribute__((address_space(1))) void ring_gbl_t;
 
 template <int MF, int TM, int TN, int WM, int WN, int KC, bool RING = false>
 __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams kp) {
@@ -137,9 +129,8 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams 
 #pragma unroll
             for (int r = 0; r < MM::NACC; ++r) acc[i][j][r] = 0.f;
 
-    typedef float f32x4r __attribute__((ext_vector_type(4)));
-    f32x4r rw[NW], rx[NX];     // staging registers of the next step / chunk
-    f32x4r rw2[NW], rx2[NX];   // second set: 1x1 products prefetch two chunks ahead (see the GEMM loop below)
+    f32x4v rw[NW], rx[NX];     // staging registers of the next step / chunk
+    f32x4v rw2[NW], rx2[NX];   // second set: 1x1 products prefetch two chunks ahead (see the GEMM loop below)
 
     // Staging loads are BRANCH-FREE (clamped always-valid addresses; out-of-range elements are zeroed when the registers
     // are written to LDS) so that they stay in flight across the MFMA block: any control flow around a load makes hipcc
@@ -151,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams 
             const int k = min(k0 + idx / (MT / 4), K - 1);
             const int m = m0 + (idx % (MT / 4)) * 4;
             const int mm = m < M ? m : 0;
-            regs[i] = *reinterpret_cast<const f32x4r*>(Ag + (int64_t)tap * p.a_tap_stride + (int64_t)k * p.lda + mm);
+            regs[i] = *reinterpret_cast<const f32x4v*>(Ag + (int64_t)tap * p.a_tap_stride + (int64_t)k * p.lda + mm);
         }
     };
     auto store_w = [&](auto& regs, int buf, int k0) {
@@ -161,13 +152,13 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams 
             if (idx < F4W) {
                 const int k = k0 + idx / (MT / 4);
                 const int m = m0 + (idx % (MT / 4)) * 4;
-                f32x4r v = regs[i];
+                f32x4v v = regs[i];
                 const bool kin = k < K;
                 v[0] = (kin && m < M) ? v[0] : 0.f;
                 v[1] = (kin && m + 1 < M) ? v[1] : 0.f;
                 v[2] = (kin && m + 2 < M) ? v[2] : 0.f;
                 v[3] = (kin && m + 3 < M) ? v[3] : 0.f;
-                *reinterpret_cast<f32x4r*>(ws + buf * (KC * MT) + idx * 4) = v;
+                *reinterpret_cast<f32x4v*>(ws + buf * (KC * MT) + idx * 4) = v;
             }
         }
     };
@@ -179,7 +170,7 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams 
             const int j = wstart + (idx - kr * xw4) * 4;
             const int k = min(k0 + kr, K - 1);
             const int jj = (j >= 0 && j < nb) ? j : 0;
-            regs[i] = *reinterpret_cast<const f32x4r*>(Bg + (int64_t)k * p.ldb + jj);
+            regs[i] = *reinterpret_cast<const f32x4v*>(Bg + (int64_t)k * p.ldb + jj);
         }
     };
     // zero fill + the fused input activation happen here, AFTER the MFMA block
@@ -191,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams 
                 const int kr = idx / xw4;
                 const int j = wstart + (idx - kr * xw4) * 4;
                 const bool kin = (k0 + kr < K) && j >= 0;
-                f32x4r v = regs[i];
+                f32x4v v = regs[i];
                 v[0] = (kin && j < nb) ? v[0] : 0.f;
                 v[1] = (kin && j + 1 < nb) ? v[1] : 0.f;
                 v[2] = (kin && j + 2 < nb) ? v[2] : 0.f;
@@ -200,7 +191,7 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = v[e] >= 0.f ? v[e] : v[e] * slope;
                 }
-                *reinterpret_cast<f32x4r*>(xs + buf * (KC * XW) + idx * 4) = v;
+                *reinterpret_cast<f32x4v*>(xs + buf * (KC * XW) + idx * 4) = v;
             }
         }
     };
@@ -255,7 +246,7 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams 
             float* slot = smem + (c & (kRingSlots - 1)) * SLOT;
 #pragma unroll
             for (int q = 0; q < PERW; ++q)
-                __builtin_amdgcn_global_load_lds((ring_gbl_t*)(src[q] + c * step[q]), (ring_lds_t*)(slot + dst[q]), 16, 0, 0);
+                dma16(src[q] + c * step[q], lds_addr(slot + dst[q]));
         };
         auto compute_ring = [&](int c) {
             const float* wsb = smem + (c & (kRingSlots - 1)) * SLOT + wm0 + (lane % MF);
@@ -291,8 +282,8 @@ __global__ __launch_bounds__(kThreads) void conv_gemm_kernel(const KernelParams 
         for (int c = 0; c < min(kRingSlots - 1, nchunks); ++c) stage(c);
         for (int c = 0; c < nchunks; ++c) {
             // this wave's DMAs of chunk c have landed (loads retire in order; at the tail fewer chunks are behind it: wait for all)
-            if (c + kRingSlots - 2 < nchunks) ring_wait_vm<(kRingSlots - 2) * PERW>();
-            else ring_wait_vm<0>();
+            if (c + kRingSlots - 2 < nchunks) wait_vm<(kRingSlots - 2) * PERW>();
+            else wait_vm<0>();
             __builtin_amdgcn_s_barrier();   // ... and everybody else's; every wave is also done with chunk c - 1, whose slot is refilled now
             if (c + kRingSlots - 1 < nchunks) stage(c + kRingSlots - 1);
             compute_ring(c);

@@ -15,30 +15,20 @@
 // LDS image of a 16-k chunk: A [16 k][16 m] then TN x B [16 k][16 n], 1 KB each, row-major = lane-linear for the DMA (lane l carries
 // row l >> 2, floats 4 * (l & 3) ..) AND for the MFMA fragments (k-step s of lane l is dword 64 s + l): conflict-free ds_read_b32.
 #include "common.h"
+#include "device_prims.h"
 
 namespace sbv2 {
 
 namespace {
-
-typedef float f32x4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void gbl_void_t;
-
 
 struct SkinnyParams {
     ConvParams p;
     int mask_shift;
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // ---- epilogue: the arithmetic of gemm_conv.hip's, element for element; every global read before the first store -------------------------
 template <int TN>
-__device__ __forceinline__ void skinny_epilogue(const SkinnyParams& kp, const f32x4s (&acc)[TN], int m0, int n0, int lane) {
+__device__ __forceinline__ void skinny_epilogue(const SkinnyParams& kp, const f32x4v (&acc)[TN], int m0, int n0, int lane) {
     const ConvParams& p = kp.p;
     const int M = p.M, N = p.N;
     const float* Rg = p.R;
@@ -107,15 +97,15 @@ __global__ __launch_bounds__(64) void gemm_skinny_kernel(const SkinnyParams kp) 
     const int64_t astep = (int64_t)16 * p.lda, bstep = (int64_t)16 * p.ldb;
     auto stage = [&](int c) {
         char* dst = smem + (c & (kStages - 1)) * SB;
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(asrc + c * astep), (lds_void_t*)dst, 16, 0, 0);
+        dma16(asrc + c * astep, lds_addr(dst));
 #pragma unroll
         for (int t = 0; t < TN; ++t)
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(bsrc[t] + c * bstep), (lds_void_t*)(dst + 1024 * (1 + t)), 16, 0, 0);
+            dma16(bsrc[t] + c * bstep, lds_addr(dst + 1024 * (1 + t)));
     };
 
-    f32x4s acc[TN];
+    f32x4v acc[TN];
 #pragma unroll
-    for (int t = 0; t < TN; ++t) acc[t] = f32x4s{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < TN; ++t) acc[t] = f32x4v{0.f, 0.f, 0.f, 0.f};
     const float slope = p.pre_slope;
     // the fragments of chunk c + 1 are read from LDS before the MFMAs of chunk c are issued (a lone wave has nobody to hide the ds_read
     // latency behind)
@@ -184,18 +174,6 @@ struct SkinnyTapParams {
 };
 constexpr int kTapSlots = 8;
 
-__device__ __forceinline__ void wait_vm_dyn(int n) {
-    switch (n) {   // s_waitcnt takes an immediate; n is wave-uniform
-#define W_(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-        W_(0) W_(1) W_(2) W_(3) W_(4) W_(5) W_(6) W_(7) W_(8) W_(9) W_(10) W_(11) W_(12) W_(13) W_(14) W_(15)
-        W_(16) W_(17) W_(18) W_(19) W_(20) W_(21) W_(22) W_(23) W_(24) W_(25) W_(26) W_(27) W_(28) W_(29) W_(30) W_(31)
-        W_(32) W_(33) W_(34) W_(35) W_(36) W_(37) W_(38) W_(39) W_(40) W_(41) W_(42) W_(43) W_(44) W_(45) W_(46) W_(47)
-        W_(48) W_(49) W_(50) W_(51) W_(52) W_(53) W_(54) W_(55) W_(56) W_(57) W_(58) W_(59) W_(60) W_(61) W_(62)
-#undef W_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
 __global__ __launch_bounds__(64) void gemm_skinny_taps_kernel(const SkinnyTapParams kp) {
     const ConvParams& p = kp.p;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -216,12 +194,12 @@ __global__ __launch_bounds__(64) void gemm_skinny_taps_kernel(const SkinnyTapPar
     auto stage = [&](int c) {
         char* dst = smem + (c & (kTapSlots - 1)) * kp.slot_bytes;
         for (int t = 0; t < ntaps; ++t)
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(asrc + (int64_t)t * p.a_tap_stride + (int64_t)c * 16 * p.lda), (lds_void_t*)(dst + t * 1024), 16, 0, 0);
+            dma16(asrc + (int64_t)t * p.a_tap_stride + (int64_t)c * 16 * p.lda, lds_addr(dst + t * 1024));
         for (int g = 0; g < xg; ++g)
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(bsrc + ((int64_t)c * 16 + g * rpg) * p.ldb), (lds_void_t*)(dst + wbytes + g * 1024), 16, 0, 0);
+            dma16(bsrc + ((int64_t)c * 16 + g * rpg) * p.ldb, lds_addr(dst + wbytes + g * 1024));
     };
-    f32x4s acc[1];
-    acc[0] = f32x4s{0.f, 0.f, 0.f, 0.f};
+    f32x4v acc[1];
+    acc[0] = f32x4v{0.f, 0.f, 0.f, 0.f};
     const float slope = p.pre_slope;
     const int krow = lane >> 4, lcol = lane & 15;
     auto mma_chunk = [&](int c) {

@@ -26,50 +26,22 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
 
 #pragma clang fp contract(off)
 
 namespace sbv2 {
 
-typedef __bf16 rb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 rb_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float rb_f32x16 __attribute__((ext_vector_type(16)));
-typedef float rb_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void rb_lds_t;
-typedef const __attribute__((address_space(1))) void rb_gbl_t;
-
-template <int I, int N, class F>
-__device__ __forceinline__ void rb_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rb_for<I + 1, N>(f);
-    }
-}
-// (LDS instructions take a 16-bit immediate offset: what lies beyond - the lo part of a 128-channel window - goes into the address, one add the compiler shares)
+// The shared LDS accessors with offsets beyond the instructions' 16-bit immediate: what lies beyond - the lo part of a 128-channel window - goes into the
+// address, one add the compiler shares
 template <int OFF>
-__device__ __forceinline__ rb_bf16x8 rb_read_b128(unsigned addr) {
-    rb_bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr + (unsigned)(OFF & ~0xFFFF)), "i"(OFF & 0xFFFF));
-    return v;
-}
+__device__ __forceinline__ bf16x8 rb_read_b128(unsigned addr) { return lds_read_b128<(OFF & 0xFFFF)>(addr + (unsigned)(OFF & ~0xFFFF)); }
 template <int OFF>
-__device__ __forceinline__ rb_f32x4 rb_read_f128(unsigned addr) {
-    rb_f32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr + (unsigned)(OFF & ~0xFFFF)), "i"(OFF & 0xFFFF));
-    return v;
-}
+__device__ __forceinline__ f32x4v rb_read_f128(unsigned addr) { return lds_read_f128<(OFF & 0xFFFF)>(addr + (unsigned)(OFF & ~0xFFFF)); }
 template <int OFF>
-__device__ __forceinline__ unsigned rb_read_u8(unsigned addr) {
-    unsigned v;
-    asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(v) : "v"(addr + (unsigned)(OFF & ~0xFFFF)), "i"(OFF & 0xFFFF));
-    return v;
-}
+__device__ __forceinline__ unsigned rb_read_u8(unsigned addr) { return lds_read_u8<(OFF & 0xFFFF)>(addr + (unsigned)(OFF & ~0xFFFF)); }
 template <int OFF>
-__device__ __forceinline__ void rb_write_b64(unsigned addr, rb_bf16x4 v) {
-    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr + (unsigned)(OFF & ~0xFFFF)), "v"(v), "i"(OFF & 0xFFFF) : "memory");
-}
-__device__ __forceinline__ void rb_write_b32(unsigned addr, float v) { asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void rb_write_b8(unsigned addr, unsigned v) { asm volatile("ds_write_b8 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
+__device__ __forceinline__ void rb_write_b64(unsigned addr, bf16x4 v) { lds_write_b64<(OFF & 0xFFFF)>(addr + (unsigned)(OFF & ~0xFFFF), v); }
 
 constexpr int rb_max(int a, int b) { return a > b ? a : b; }
 // rows in front of / behind the window that a tap may reach: k = 3 with dilation <= 6 keeps the layout the sweeps below were measured on; the wider kernels
@@ -121,7 +93,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     constexpr int NQ = 4;                              // 4-row groups of a 32 x 32 accumulator tile
     constexpr int h2 = (NTAPS - 1) / 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
+    const unsigned lds0 = lds_addr(smem);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -154,7 +126,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
             const int part = pc & 1, tgx = pc >> 1, mt = tgx / G, tg = tgx - mt * G;
             if (pc < NP && tg < ntg) {
                 const char* src = W + ((((int64_t)(chunk * NMT + mt) * NTW + g * G + tg) * 2 + part) << 10) + lane * 16;
-                __builtin_amdgcn_global_load_lds((rb_gbl_t*)src, (rb_lds_t*)(uintptr_t)__builtin_amdgcn_readfirstlane(lds0 + (gs % NBUF) * K::WSLOT + pc * 1024), 16, 0, 0);
+                dma16(src, __builtin_amdgcn_readfirstlane(lds0 + (gs % NBUF) * K::WSLOT + pc * 1024));
             }
         }
     };
@@ -174,7 +146,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     };
     // ---- the window of y_0: f32 rows -> registers -> lrelu, hi / lo -> LDS, all chunks.  Thread: row (tid >> 2) of every RB-row block, 16-byte quad
     // (tid & 3) of a chunk's 64-byte row piece.
-    rb_f32x4 rx[NCH][NXC];
+    f32x4v rx[NCH][NXC];
     {
         const unsigned xlane = (unsigned)((tid >> 2) * (C * 4) + (tid & 3) * 16);
         if (interior) {
@@ -182,29 +154,29 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
 #pragma unroll
-                for (int i = 0; i < NXC; ++i) rx[c][i] = *reinterpret_cast<const rb_f32x4*>(xwin + (i * RB * C * 4 + c * 64) + (size_t)xlane);
+                for (int i = 0; i < NXC; ++i) rx[c][i] = *reinterpret_cast<const f32x4v*>(xwin + (i * RB * C * 4 + c * 64) + (size_t)xlane);
         } else {
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
 #pragma unroll
                 for (int i = 0; i < NXC; ++i) {
                     const int pos = min(max(w0 + i * RB + (tid >> 2), 0), NB - 1);
-                    rx[c][i] = *reinterpret_cast<const rb_f32x4*>(p.X + (int64_t)pos * C + c * 16 + (tid & 3) * 4);
+                    rx[c][i] = *reinterpret_cast<const f32x4v*>(p.X + (int64_t)pos * C + c * 16 + (tid & 3) * 4);
                 }
         }
     }
-    rb_for<0, (NBUF - 1 < NTOT ? NBUF - 1 : NTOT)>([&](auto gsc) __attribute__((always_inline)) { dma_group(gsc); });
+    static_for<0, (NBUF - 1 < NTOT ? NBUF - 1 : NTOT)>([&](auto gsc) __attribute__((always_inline)) { dma_group(gsc); });
 
     // ---- the residual stream in ACCUMULATOR layout, from the same lines (L2 / L1 hits): 32x32 tile j, register 4 q + e of lane (lcol, lh) = channel
     // wm * 32 + 8 q + 4 lh + e of row wn * 64 + 32 j + lcol; C = 16: 16x16 tile j, register e of lane (l16, lg) = channel 4 lg + e of row wn * 64 + 16 j + l16
     const int lg = lane >> 4, l16 = lane & 15;         // (TWOTAP) k group / column of a 16x16x32 operand
-    rb_f32x16 yres[TWOTAP ? 1 : 2];
-    rb_f32x4 yres4[TWOTAP ? 4 : 1];
+    f32x16 yres[TWOTAP ? 1 : 2];
+    f32x4v yres4[TWOTAP ? 4 : 1];
     if constexpr (TWOTAP) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int pos = min(max(w0 + wn * 64 + 16 * j + l16, 0), NB - 1);
-            yres4[j] = *reinterpret_cast<const rb_f32x4*>(p.X + (int64_t)pos * C + 4 * lg);
+            yres4[j] = *reinterpret_cast<const f32x4v*>(p.X + (int64_t)pos * C + 4 * lg);
         }
     } else {
 #pragma unroll
@@ -213,7 +185,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
             const float* src = p.X + (int64_t)pos * C + wm * 32 + 4 * lh;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                const rb_f32x4 v = *reinterpret_cast<const rb_f32x4*>(src + 8 * q);
+                const f32x4v v = *reinterpret_cast<const f32x4v*>(src + 8 * q);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) yres[j][4 * q + e] = v[e];
             }
@@ -225,7 +197,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
 #pragma unroll
         for (int h = 0; h < NBV; ++h) {
             const int i = tid + h * T;
-            if (i < 2 * NS * C) rb_write_b32(lds0 + K::BIAS_OFF + i * 4, p.b[i / C][i % C]);
+            if (i < 2 * NS * C) lds_write_b32(lds0 + K::BIAS_OFF + i * 4, p.b[i / C][i % C]);
         }
         constexpr int NMV = (R + T - 1) / T;
 #pragma unroll
@@ -234,7 +206,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
             const int pos = w0 + r;
             const int pc = min(max(pos, 0), NB - 1);
             const unsigned m = p.mask ? p.mask[pc >> p.mask_shift] : 1u;
-            if (r < R) rb_write_b8(lds0 + K::MASK_OFF + r, (pos >= 0 && pos < NB) ? m : 0u);
+            if (r < R) lds_write_b8(lds0 + K::MASK_OFF + r, (pos >= 0 && pos < NB) ? m : 0u);
         }
     }
     const float slope = p.slope;
@@ -242,16 +214,16 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
         const unsigned x1w = lds0 + K::WREG + ((tid & 3) >> 1) * K::XHALF + (MARG + (tid >> 2)) * 16 + (tid & 1) * 8;
         auto convert_all = [&](auto edgec) __attribute__((always_inline)) {
             constexpr bool EDGE = decltype(edgec)::value;
-            rb_for<0, NCH>([&](auto cc) __attribute__((always_inline)) {
+            static_for<0, NCH>([&](auto cc) __attribute__((always_inline)) {
                 constexpr int c = decltype(cc)::value;
-                rb_for<0, NXC>([&](auto ic) __attribute__((always_inline)) {
+                static_for<0, NXC>([&](auto ic) __attribute__((always_inline)) {
                     constexpr int i = decltype(ic)::value;
-                    rb_f32x4 v = rx[c][i];
+                    f32x4v v = rx[c][i];
                     if constexpr (EDGE) {
                         const int pos = w0 + i * RB + (tid >> 2);
-                        if (pos < 0 || pos >= NB) v = rb_f32x4{0.f, 0.f, 0.f, 0.f};
+                        if (pos < 0 || pos >= NB) v = f32x4v{0.f, 0.f, 0.f, 0.f};
                     }
-                    rb_bf16x4 h, l;
+                    bf16x4 h, l;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float x = fmaxf(v[e], v[e] * slope);   // leaky ReLU for 0 <= slope <= 1
@@ -274,7 +246,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     constexpr int NRD = 2 + 2 * NB_;                   // fragment reads per weight step
     constexpr int NMF = 3 * NB_;                       // MFMAs per weight step
     struct Frags {
-        rb_bf16x8 ah, al, bh[NB_], bl[NB_];
+        bf16x8 ah, al, bh[NB_], bl[NB_];
     };
     const unsigned abase = lds0 + lane * 16 + wm * (G * 2048);
     // row r of the window lives in cell MARG + r of its (part, chunk, half) plane
@@ -284,12 +256,12 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     const unsigned c2last = bbase - h2 * 16;           // (TWOTAP, odd kernel size) the lanes of the phantom tap read the row of the last real tap
     unsigned c1base = 0, c1last = 0;                   // conv1 of the current step (dilation d): set per step
     int dcur = 1;
-    rb_f32x16 acc[TWOTAP ? 1 : 2];
-    rb_f32x4 acc4[TWOTAP ? 4 : 1];
+    f32x16 acc[TWOTAP ? 1 : 2];
+    f32x4v acc4[TWOTAP ? 4 : 1];
     auto zero_acc = [&]() __attribute__((always_inline)) {
         if constexpr (TWOTAP) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc4[j] = rb_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < 4; ++j) acc4[j] = f32x4v{0.f, 0.f, 0.f, 0.f};
         } else {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -362,12 +334,12 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
         using CV = std::integral_constant<int, conv>;
         using CK = std::integral_constant<int, chunk>;
         Frags f[2];
-        rb_for<0, NRD>([&](auto rc) __attribute__((always_inline)) { read_one(f[0], rc, CV{}, CK{}, std::integral_constant<int, g * G>{}, gsc, std::integral_constant<int, 0>{}); });
-        rb_for<0, ntg>([&](auto tc) __attribute__((always_inline)) {
+        static_for<0, NRD>([&](auto rc) __attribute__((always_inline)) { read_one(f[0], rc, CV{}, CK{}, std::integral_constant<int, g * G>{}, gsc, std::integral_constant<int, 0>{}); });
+        static_for<0, ntg>([&](auto tc) __attribute__((always_inline)) {
             constexpr int tg = decltype(tc)::value;
             wait_frags(f[tg & 1]);
             __builtin_amdgcn_sched_barrier(0);
-            rb_for<0, NMF>([&](auto nc) __attribute__((always_inline)) {
+            static_for<0, NMF>([&](auto nc) __attribute__((always_inline)) {
                 mfma_one(f[tg & 1], nc);
                 if constexpr (tg + 1 < ntg && decltype(nc)::value < NRD)
                     read_one(f[(tg + 1) & 1], nc, CV{}, CK{}, std::integral_constant<int, g * G + tg + 1>{}, gsc, std::integral_constant<int, tg + 1>{});
@@ -382,7 +354,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
         constexpr int gs = decltype(gsc)::value;
         constexpr int ahead = NTOT - 1 - gs < NBUF - 2 ? NTOT - 1 - gs : NBUF - 2;   // younger groups already requested
         int young = 0;
-        rb_for<0, ahead>([&](auto ac) __attribute__((always_inline)) { young += pieces_of(std::integral_constant<int, gs + 1 + decltype(ac)::value>{}); });
+        static_for<0, ahead>([&](auto ac) __attribute__((always_inline)) { young += pieces_of(std::integral_constant<int, gs + 1 + decltype(ac)::value>{}); });
         // (a few immediates: vmcnt takes no register)
         if (young <= 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         else if (young == 1) asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
@@ -402,7 +374,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     for (int j = 0; j < NB_; ++j) mk[j] = 0;
     auto load_flags = [&]() __attribute__((always_inline)) {
         if constexpr (TWOTAP) {
-            rb_for<0, 4>([&](auto jc) __attribute__((always_inline)) { mk[decltype(jc)::value] = rb_read_u8<decltype(jc)::value * 16>(lds0 + K::MASK_OFF + wn * 64 + l16); });
+            static_for<0, 4>([&](auto jc) __attribute__((always_inline)) { mk[decltype(jc)::value] = rb_read_u8<decltype(jc)::value * 16>(lds0 + K::MASK_OFF + wn * 64 + l16); });
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(mk[0]), "+v"(mk[1]), "+v"(mk[2]), "+v"(mk[3]));
         } else {
             mk[0] = rb_read_u8<0>(lds0 + K::MASK_OFF + wn * 64 + lcol);
@@ -420,11 +392,11 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     auto emit = [&](auto resc, auto partsc, auto keepc, int bias_row) __attribute__((always_inline)) {
         constexpr bool RES = decltype(resc)::value, PARTS = decltype(partsc)::value, ALL = decltype(keepc)::value;
         if constexpr (TWOTAP) {
-            rb_f32x4 bq = rb_read_f128<0>(lds0 + K::BIAS_OFF + bias_row * (C * 4) + lg * 16);
+            f32x4v bq = rb_read_f128<0>(lds0 + K::BIAS_OFF + bias_row * (C * 4) + lg * 16);
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq));
-            rb_for<0, 4>([&](auto jc) __attribute__((always_inline)) {
+            static_for<0, 4>([&](auto jc) __attribute__((always_inline)) {
                 constexpr int j = decltype(jc)::value;
-                rb_bf16x4 h, l;
+                bf16x4 h, l;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float t = acc4[j][e] + bq[e];
@@ -444,17 +416,17 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
                 }
             });
         } else {
-            rb_f32x4 bq[NQ];
-            rb_for<0, NQ>([&](auto qc) __attribute__((always_inline)) {
+            f32x4v bq[NQ];
+            static_for<0, NQ>([&](auto qc) __attribute__((always_inline)) {
                 constexpr int q = decltype(qc)::value;
                 bq[q] = rb_read_f128<q * 32>(lds0 + K::BIAS_OFF + bias_row * (C * 4) + (wm * 32 + 4 * lh) * 4);
             });
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]));
-            rb_for<0, 2>([&](auto jc) __attribute__((always_inline)) {
+            static_for<0, 2>([&](auto jc) __attribute__((always_inline)) {
                 constexpr int j = decltype(jc)::value;
-                rb_for<0, NQ>([&](auto qc) __attribute__((always_inline)) {
+                static_for<0, NQ>([&](auto qc) __attribute__((always_inline)) {
                     constexpr int q = decltype(qc)::value;
-                    rb_bf16x4 h, l;
+                    bf16x4 h, l;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float t = acc[j][4 * q + e] + bq[q][e];
@@ -483,7 +455,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     };
 
     // ================================================================================================================================
-    rb_for<0, NS>([&](auto qc) __attribute__((always_inline)) {
+    static_for<0, NS>([&](auto qc) __attribute__((always_inline)) {
         constexpr int q = decltype(qc)::value;
         constexpr bool more = q + 1 < NS;
         constexpr int S0 = q * NSEQ;           // first group of the step (conv1), S2: first group of conv2
@@ -493,7 +465,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
         c1last = bbase - h2 * dcur * 16;
         // ---- conv1 (dilation d) over the window's lrelu(y) parts ---------------------------------------------------------------------------
         zero_acc();
-        rb_for<S0, S2>([&](auto gsc) __attribute__((always_inline)) {
+        static_for<S0, S2>([&](auto gsc) __attribute__((always_inline)) {
             group_barrier(gsc);
             if constexpr (decltype(gsc)::value == 0) {   // the keep flags other threads parked are visible now
                 load_flags();
@@ -511,7 +483,7 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
         __builtin_amdgcn_sched_barrier(0);
         // ---- conv2 over the intermediate ----------------------------------------------------------------------------------------------------
         run_group(std::integral_constant<int, S2>{});
-        rb_for<S2 + 1, S0 + NSEQ>([&](auto gsc) __attribute__((always_inline)) {
+        static_for<S2 + 1, S0 + NSEQ>([&](auto gsc) __attribute__((always_inline)) {
             group_barrier(gsc);
             run_group(gsc);
         });
@@ -536,23 +508,23 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
     float* ttile = reinterpret_cast<float*>(smem) + wave * (64 * TP);
     if constexpr (TWOTAP) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) *reinterpret_cast<rb_f32x4*>(ttile + (j * 16 + l16) * TP + 4 * lg) = yres4[j];
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4v*>(ttile + (j * 16 + l16) * TP + 4 * lg) = yres4[j];
     } else {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                rb_f32x4 v = {yres[j][4 * q], yres[j][4 * q + 1], yres[j][4 * q + 2], yres[j][4 * q + 3]};
-                *reinterpret_cast<rb_f32x4*>(ttile + (j * 32 + lcol) * TP + 8 * q + 4 * lh) = v;
+                f32x4v v = {yres[j][4 * q], yres[j][4 * q + 1], yres[j][4 * q + 2], yres[j][4 * q + 3]};
+                *reinterpret_cast<f32x4v*>(ttile + (j * 32 + lcol) * TP + 8 * q + 4 * lh) = v;
             }
     }
     const unsigned char* mask_s = reinterpret_cast<const unsigned char*>(smem + K::MASK_OFF);
-    rb_f32x4 rold[NIT];
+    f32x4v rold[NIT];
     if (p.accumulate) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int64_t po = min(max((int64_t)w0 + wn * 64 + it * RPI + rowi, (int64_t)0), (int64_t)NB - 1);
-            rold[it] = *reinterpret_cast<const rb_f32x4*>(p.Y + po * C + c4);
+            rold[it] = *reinterpret_cast<const f32x4v*>(p.Y + po * C + c4);
         }
     }
     const float beta = p.beta;
@@ -563,11 +535,11 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
             const int row = it * RPI + rowi;
             const int r = wn * 64 + row;                    // window row
             const int pos = w0 + r;                         // < 2^31 (checked by the caller)
-            const rb_f32x4 a = *reinterpret_cast<const rb_f32x4*>(ttile + row * TP + (lane % LPR) * 4);
+            const f32x4v a = *reinterpret_cast<const f32x4v*>(ttile + row * TP + (lane % LPR) * 4);
             if (r < halo || r >= R - halo || pos >= NB) continue;
             // (contraction is off in this file; respair_clx.hip / conv_cl.hip are compiled with hipcc's default, which fuses `x * beta + old` into one fma:
             // written out here, so that the branch's last step keeps their bits)
-            rb_f32x4 v;
+            f32x4v v;
             if (p.accumulate) {
                 // (C >= 128 replaces conv_cl / conv_clx launches, whose accumulate epilogue rounds the product before the sum)
 #pragma unroll
@@ -576,9 +548,9 @@ __global__ __launch_bounds__((RbCfg<C, NTAPS, WNP, GT, NBUFP>::T)) __attribute__
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = a[e] * beta;
             }
-            if (!mask_s[r]) v = rb_f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<rb_f32x4*>(p.Y + (int64_t)pos * C + c4));
-            else *reinterpret_cast<rb_f32x4*>(p.Y + (int64_t)pos * C + c4) = v;
+            if (!mask_s[r]) v = f32x4v{0.f, 0.f, 0.f, 0.f};
+            if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4v*>(p.Y + (int64_t)pos * C + c4));
+            else *reinterpret_cast<f32x4v*>(p.Y + (int64_t)pos * C + c4) = v;
         }
     };
     if (p.nt_store) store_rows(std::true_type{});

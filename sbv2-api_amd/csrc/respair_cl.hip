@@ -11,31 +11,15 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
 
 namespace sbv2 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 enum { PREC_BF16 = 0, PREC_BF16X3 = 1, PREC_F16 = 2 };   // as in conv_cl.hip
-__device__ __forceinline__ f32x16 rp_mfma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x16 rp_mfma(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
 constexpr int kRpThreads = 256;
 constexpr int kRpNT = 256;        // positions of the intermediate per workgroup
 constexpr int kRpWin2Rows = 272;  // 256 + tap overrun of the last wave (read for discarded columns only)
-
-template <int I, int N, class F>
-__device__ __forceinline__ void rp_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rp_static_for<I + 1, N>(f);
-    }
-}
 
 // WM = 32-row tiles of the output channels, one group of four waves each: 1 for C = 16 / 32 (256 threads), 2 for C = 64 (512 threads: the
 // 134 KB of LDS at k = 11 allow one workgroup per CU, so the second wave per SIMD has to come from inside the workgroup)
@@ -100,13 +84,13 @@ __global__ __launch_bounds__(kRpThreads * WM) __attribute__((amdgpu_waves_per_eu
     f32x4v rx[NX], rx1[NX];
     auto load_w = [&](const void* W, int chunk) {
         const f32x4v* src = reinterpret_cast<const f32x4v*>(W) + (int64_t)chunk * ntaps * WM * PARTS * 64;   // nmt == WM
-        rp_static_for<0, MAXW>([&](auto ic) {
+        static_for<0, MAXW>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             rw[i] = src[min(tid + i * T, nwf4 - 1)];
         });
     };
     auto store_w = [&]() {
-        rp_static_for<0, MAXW>([&](auto ic) {
+        static_for<0, MAXW>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const int idx = tid + i * T;
             if (idx < nwf4) reinterpret_cast<f32x4v*>(wsm)[idx] = rw[i];
@@ -170,10 +154,10 @@ __global__ __launch_bounds__(kRpThreads * WM) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 if (SPLIT) {
-                    acc[j] = rp_mfma(f.al, f.bh[j], acc[j]);
-                    acc[j] = rp_mfma(f.ah, f.bl[j], acc[j]);
+                    acc[j] = mfma32(f.al, f.bh[j], acc[j]);
+                    acc[j] = mfma32(f.ah, f.bl[j], acc[j]);
                 }
-                acc[j] = rp_mfma(f.ah, f.bh[j], acc[j]);
+                acc[j] = mfma32(f.ah, f.bh[j], acc[j]);
             }
         };
         Frags fa, fb;

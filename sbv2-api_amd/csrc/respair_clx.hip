@@ -22,53 +22,13 @@
 // weight group (the per-tile dependency chain fell from 15.2k to 7.5k cycles at C = 16, 28.6k to 19.3k at C = 32) ran 5-10 % SLOWER: the loop keeps 40-60
 // more registers live (one wave per SIMD less at C = 16), and these launches are not latency bound any more: C = 16 and every k = 3 launch move their
 // 0.94 GB per half-size launch at 3.5-3.7 TB/s, C >= 32 at k >= 7 run 0.85-1.1 PFLOP/s of executed MFMA at a power-managed 1.65-1.75 GHz.
-// Fragment reads, window writes and the waits that cover them are inline asm: with an LDS-DMA pending hipcc puts s_waitcnt vmcnt(0) in front of every
-// LDS access it can see, which would serialise the weight stream with the MFMAs (conv_clx.hip has the same note).
 #include <atomic>
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
 
 namespace sbv2 {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void rpx_lds_t;
-typedef const __attribute__((address_space(1))) void rpx_gbl_t;
-
-template <int I, int N, class F>
-__device__ __forceinline__ void rpx_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rpx_for<I + 1, N>(f);
-    }
-}
-template <int OFF>
-__device__ __forceinline__ bf16x8 rpx_read_b128(unsigned addr) {
-    bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ f32x4v rpx_read_f128(unsigned addr) {
-    f32x4v v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ unsigned rpx_read_u8(unsigned addr) {
-    unsigned v;
-    asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ void rpx_write_b64(unsigned addr, bf16x4 v) {
-    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "i"(OFF) : "memory");
-}
-__device__ __forceinline__ void rpx_write_b32(unsigned addr, float v) { asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void rpx_write_b8(unsigned addr, unsigned v) { asm volatile("ds_write_b8 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
 
 constexpr int rpx_max(int a, int b) { return a > b ? a : b; }
 
@@ -119,7 +79,7 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
     constexpr int NQ = 4;                              // 4-row groups of a 32 x 32 accumulator tile
     constexpr int h2 = (NTAPS - 1) / 2, nto = NT - 2 * h2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
+    const unsigned lds0 = lds_addr(smem);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -150,7 +110,7 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
             const int part = pc & 1, tgx = pc >> 1, mt = tgx / G, tg = tgx - mt * G;
             if (pc < NP && tg < ntg) {
                 const char* src = W + ((((int64_t)(chunk * NMT + mt) * NTW + g * G + tg) * 2 + part) << 10) + lane * 16;
-                __builtin_amdgcn_global_load_lds((rpx_gbl_t*)src, (rpx_lds_t*)(uintptr_t)__builtin_amdgcn_readfirstlane(lds0 + (s & 1) * K::WSLOT + pc * 1024), 16, 0, 0);
+                dma16(src, __builtin_amdgcn_readfirstlane(lds0 + (s & 1) * K::WSLOT + pc * 1024));
             }
         }
     };
@@ -182,7 +142,7 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
     auto convert_one = [&](auto cc, auto edgec) {
         constexpr int c = decltype(cc)::value;
         constexpr bool EDGE = decltype(edgec)::value;
-        rpx_for<0, NXC>([&](auto ic) {
+        static_for<0, NXC>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             f32x4v v = rx[c][i];
             if constexpr (EDGE) {
@@ -196,8 +156,8 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
                 h[e] = (__bf16)x;
                 l[e] = (__bf16)(x - (float)h[e]);
             }
-            rpx_write_b64<i * RB * 16>(x1w, h);
-            rpx_write_b64<K::X1PART + i * RB * 16>(x1w, l);
+            lds_write_b64<i * RB * 16>(x1w, h);
+            lds_write_b64<K::X1PART + i * RB * 16>(x1w, l);
         });
     };
     auto convert = [&](auto cc) {
@@ -245,8 +205,8 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
         constexpr int r = decltype(rc)::value;
         constexpr int conv = decltype(convc)::value, chunk = decltype(chunkc)::value, ws = decltype(wsc)::value;
         constexpr int aoff = (decltype(sc)::value & 1) * K::WSLOT + decltype(tgc)::value * 2048;
-        if constexpr (r == 0) f.al = rpx_read_b128<aoff + 1024>(abase);
-        else if constexpr (r == 2) f.ah = rpx_read_b128<aoff>(abase);
+        if constexpr (r == 0) f.al = lds_read_b128<aoff + 1024>(abase);
+        else if constexpr (r == 2) f.ah = lds_read_b128<aoff>(abase);
         else if constexpr (TWOTAP) {
             // B read order: bh0 (r 1), bh1 (3), bh2 (4), bh3 (5), bl0 .. bl3 (6 .. 9)
             constexpr int e = r == 1 ? 0 : r - 2;                    // 0 .. 7: bh0..3, bl0..3
@@ -254,25 +214,25 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
             constexpr bool LASTP = (NTAPS & 1) && ws == NTW - 1;     // the pair with the phantom tap
             if constexpr (conv == 0) {
                 const unsigned b = (LASTP ? b1last : b1base) + ws * 2 * d * 16;
-                if constexpr (part == 0) f.bh[j] = rpx_read_b128<j * 256>(b);
-                else f.bl[j] = rpx_read_b128<K::X1PART + j * 256>(b);
+                if constexpr (part == 0) f.bh[j] = lds_read_b128<j * 256>(b);
+                else f.bl[j] = lds_read_b128<K::X1PART + j * 256>(b);
             } else {
                 constexpr int o = ws * 2 * 16 + j * 256;
-                if constexpr (part == 0) f.bh[j] = rpx_read_b128<o>(LASTP ? b2last : b2base);
-                else f.bl[j] = rpx_read_b128<K::X2PART + o>(LASTP ? b2last : b2base);
+                if constexpr (part == 0) f.bh[j] = lds_read_b128<o>(LASTP ? b2last : b2base);
+                else f.bl[j] = lds_read_b128<K::X2PART + o>(LASTP ? b2last : b2base);
             }
         } else if constexpr (conv == 0) {
             const unsigned b = b1base + ws * d * 16;
-            if constexpr (r == 1) f.bh[0] = rpx_read_b128<0>(b);
-            else if constexpr (r == 3) f.bh[1] = rpx_read_b128<512>(b);
-            else if constexpr (r == 4) f.bl[0] = rpx_read_b128<K::X1PART>(b);
-            else f.bl[1] = rpx_read_b128<K::X1PART + 512>(b);
+            if constexpr (r == 1) f.bh[0] = lds_read_b128<0>(b);
+            else if constexpr (r == 3) f.bh[1] = lds_read_b128<512>(b);
+            else if constexpr (r == 4) f.bl[0] = lds_read_b128<K::X1PART>(b);
+            else f.bl[1] = lds_read_b128<K::X1PART + 512>(b);
         } else {
             constexpr int o = chunk * K::X2CH + ws * 16;
-            if constexpr (r == 1) f.bh[0] = rpx_read_b128<o>(b2base);
-            else if constexpr (r == 3) f.bh[1] = rpx_read_b128<o + 512>(b2base);
-            else if constexpr (r == 4) f.bl[0] = rpx_read_b128<K::X2PART + o>(b2base);
-            else f.bl[1] = rpx_read_b128<K::X2PART + o + 512>(b2base);
+            if constexpr (r == 1) f.bh[0] = lds_read_b128<o>(b2base);
+            else if constexpr (r == 3) f.bh[1] = lds_read_b128<o + 512>(b2base);
+            else if constexpr (r == 4) f.bl[0] = lds_read_b128<K::X2PART + o>(b2base);
+            else f.bl[1] = lds_read_b128<K::X2PART + o + 512>(b2base);
         }
     };
     // the wait is tied to the registers it covers: the MFMAs that consume them cannot be scheduled above it
@@ -304,12 +264,12 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
         using CV = std::integral_constant<int, conv>;
         using CK = std::integral_constant<int, chunk>;
         Frags f[2];
-        rpx_for<0, NRD>([&](auto rc) { read_one(f[0], rc, CV{}, CK{}, std::integral_constant<int, g * G>{}, sc, std::integral_constant<int, 0>{}); });
-        rpx_for<0, ntg>([&](auto tc) {
+        static_for<0, NRD>([&](auto rc) { read_one(f[0], rc, CV{}, CK{}, std::integral_constant<int, g * G>{}, sc, std::integral_constant<int, 0>{}); });
+        static_for<0, ntg>([&](auto tc) {
             constexpr int tg = decltype(tc)::value;
             wait_frags(f[tg & 1]);
             __builtin_amdgcn_sched_barrier(0);
-            rpx_for<0, NMF>([&](auto nc) {
+            static_for<0, NMF>([&](auto nc) {
                 mfma_one(f[tg & 1], nc);
                 if constexpr (tg + 1 < ntg && decltype(nc)::value < NRD)
                     read_one(f[(tg + 1) & 1], nc, CV{}, CK{}, std::integral_constant<int, g * G + tg + 1>{}, sc, std::integral_constant<int, tg + 1>{});
@@ -365,16 +325,16 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
             const unsigned m = p.mask ? p.mask[pc >> p.mask_shift] : 1u;
             mval[h] = (pos >= 0 && pos < NB) ? m : 0u;
         }
-        if (tid < 128) rpx_write_b32(lds0 + K::BIAS_OFF + tid * 4, bval);
+        if (tid < 128) lds_write_b32(lds0 + K::BIAS_OFF + tid * 4, bval);
 #pragma unroll
         for (int h = 0; h < NMV; ++h)
-            if (tid + h * T < K::ROWS2) rpx_write_b8(lds0 + K::MASK_OFF + tid + h * T, mval[h]);
+            if (tid + h * T < K::ROWS2) lds_write_b8(lds0 + K::MASK_OFF + tid + h * T, mval[h]);
     }
     convert(std::integral_constant<int, 0>{});
 
     // ---- phase 1: t = lrelu(conv1(lrelu(y)) + b1) on positions [t0, t0 + NT) -> LDS ----------------------------------------------------
     zero_acc();
-    rpx_for<0, NCH>([&](auto cc) {
+    static_for<0, NCH>([&](auto cc) {
         constexpr int chunk = decltype(cc)::value;
         if constexpr (chunk > 0) {
             // the window buffer is free once everybody has passed the barrier of this chunk's first group (all reads of chunk - 1 were waited for)
@@ -389,7 +349,7 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
             group_barrier(std::integral_constant<int, 0>{});
             run_group(std::integral_constant<int, 0>{});
         }
-        rpx_for<1, NG>([&](auto gc) {
+        static_for<1, NG>([&](auto gc) {
             constexpr int s = chunk * NG + decltype(gc)::value;
             group_barrier(std::integral_constant<int, s>{});
             run_group(std::integral_constant<int, s>{});
@@ -401,15 +361,15 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
     group_barrier(std::integral_constant<int, S2>{});
     if constexpr (TWOTAP) {
         // accumulator tile jt: lane (column l16 = position, k group lg) holds channels 4 lg .. 4 lg + 3 of position wn * 64 + 16 jt + l16
-        f32x4v bq = rpx_read_f128<0>(lds0 + K::BIAS_OFF + lg * 16);
+        f32x4v bq = lds_read_f128<0>(lds0 + K::BIAS_OFF + lg * 16);
         unsigned mk[4];
-        rpx_for<0, 4>([&](auto jc) { mk[decltype(jc)::value] = rpx_read_u8<decltype(jc)::value * 16>(lds0 + K::MASK_OFF + wn * 64 + l16); });
+        static_for<0, 4>([&](auto jc) { mk[decltype(jc)::value] = lds_read_u8<decltype(jc)::value * 16>(lds0 + K::MASK_OFF + wn * 64 + l16); });
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq), "+v"(mk[0]), "+v"(mk[1]), "+v"(mk[2]), "+v"(mk[3]));
         const bool allkeep = __builtin_amdgcn_ballot_w64(mk[0] != 0 && mk[1] != 0 && mk[2] != 0 && mk[3] != 0) == ~0ull;
         const unsigned x2w = lds0 + K::WREG + (lg >> 1) * K::X2HALF + (wn * 64 + l16) * 16 + (lg & 1) * 8;
         auto mid = [&](auto keepc) {
             constexpr bool ALL = decltype(keepc)::value;
-            rpx_for<0, 4>([&](auto jc) {
+            static_for<0, 4>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 bf16x4 h, l;
 #pragma unroll
@@ -420,28 +380,28 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
                     h[e] = (__bf16)t;
                     l[e] = (__bf16)(t - (float)h[e]);
                 }
-                rpx_write_b64<j * 256>(x2w, h);
-                rpx_write_b64<K::X2PART + j * 256>(x2w, l);
+                lds_write_b64<j * 256>(x2w, h);
+                lds_write_b64<K::X2PART + j * 256>(x2w, l);
             });
         };
         if (allkeep) mid(std::true_type{});
         else mid(std::false_type{});
     } else {
         f32x4v bq[NQ];
-        rpx_for<0, NQ>([&](auto qc) {
+        static_for<0, NQ>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
-            bq[q] = rpx_read_f128<q * 32>(lds0 + K::BIAS_OFF + (wm * 32 + 4 * lh) * 4);
+            bq[q] = lds_read_f128<q * 32>(lds0 + K::BIAS_OFF + (wm * 32 + 4 * lh) * 4);
         });
-        unsigned mk0 = rpx_read_u8<0>(lds0 + K::MASK_OFF + wn * 64 + lcol), mk1 = rpx_read_u8<32>(lds0 + K::MASK_OFF + wn * 64 + lcol);
+        unsigned mk0 = lds_read_u8<0>(lds0 + K::MASK_OFF + wn * 64 + lcol), mk1 = lds_read_u8<32>(lds0 + K::MASK_OFF + wn * 64 + lcol);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(mk0), "+v"(mk1));
         const bool keep0 = mk0 != 0, keep1 = mk1 != 0;
         const bool allkeep = __builtin_amdgcn_ballot_w64(keep0 && keep1) == ~0ull;   // (uniform) the usual tile: no masked column, no batch end
         const unsigned x2w = lds0 + K::WREG + wm * 2 * K::X2CH + (wn * 64 + lcol) * 16 + lh * 8;
         auto mid = [&](auto keepc) {
             constexpr bool ALL = decltype(keepc)::value;
-            rpx_for<0, 2>([&](auto jc) {
+            static_for<0, 2>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
-                rpx_for<0, NQ>([&](auto qc) {
+                static_for<0, NQ>([&](auto qc) {
                     constexpr int q = decltype(qc)::value;
                     bf16x4 h, l;
 #pragma unroll
@@ -453,8 +413,8 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
                         l[e] = (__bf16)(t - (float)h[e]);
                     }
                     constexpr int o = (q >> 1) * K::X2CH + (q & 1) * K::X2HALF + j * 512;
-                    rpx_write_b64<o>(x2w, h);
-                    rpx_write_b64<K::X2PART + o>(x2w, l);
+                    lds_write_b64<o>(x2w, h);
+                    lds_write_b64<K::X2PART + o>(x2w, l);
                 });
             });
         };
@@ -468,7 +428,7 @@ __global__ __launch_bounds__((RpxCfg<C, NTAPS, GT, WNP>::T)) __attribute__((amdg
 
     // ---- phase 2: conv2 over the LDS-resident intermediate -----------------------------------------------------------------------------------
     run_group(std::integral_constant<int, S2>{});
-    rpx_for<S2 + 1, K::NSEQ>([&](auto sc) {
+    static_for<S2 + 1, K::NSEQ>([&](auto sc) {
         group_barrier(sc);
         run_group(sc);
     });

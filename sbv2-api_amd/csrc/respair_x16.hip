@@ -27,78 +27,35 @@
 #include <type_traits>
 
 #include "common.h"
+#include "device_prims.h"
 
 #pragma clang fp contract(off)
 
 namespace sbv2 {
 
-typedef __bf16 x6_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 x6_bf16x4 __attribute__((ext_vector_type(4)));
-typedef float x6_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned x6_u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void x6_lds_t;
-typedef const __attribute__((address_space(1))) void x6_gbl_t;
-
-template <int I, int N, class F>
-__device__ __forceinline__ void x6_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        x6_for<I + 1, N>(f);
-    }
-}
-template <int OFF>
-__device__ __forceinline__ x6_bf16x8 x6_read_b128(unsigned addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "LDS immediate");
-    x6_bf16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ x6_f32x4 x6_read_f128(unsigned addr) {
-    x6_f32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ unsigned x6_read_u8(unsigned addr) {
-    unsigned v;
-    asm volatile("ds_read_u8 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ void x6_write_b64(unsigned addr, x6_bf16x4 v) {
-    static_assert(OFF >= 0 && OFF < 65536, "LDS immediate");
-    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "i"(OFF) : "memory");
-}
-__device__ __forceinline__ void x6_write_b32(unsigned addr, float v) { asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-__device__ __forceinline__ void x6_write_b8(unsigned addr, unsigned v) { asm volatile("ds_write_b8 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
-// (inline asm: the accumulator stays in its registers; conv_clx.hip has the note)
-__device__ __forceinline__ void x6_mfma(x6_f32x4& c, const x6_bf16x8& a, const x6_bf16x8& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
 // the low halves (lanes 0-31) of two fragments side by side: [W_hi(a) | W_hi(b)] out of [W_hi | W_lo](a), [W_hi | W_lo](b); one v_permlane32_swap per register
-__device__ __forceinline__ x6_bf16x8 x6_lows(const x6_bf16x8& a, const x6_bf16x8& b) {
-    const x6_u32x4 ua = __builtin_bit_cast(x6_u32x4, a), ub = __builtin_bit_cast(x6_u32x4, b);
-    x6_u32x4 l;
+__device__ __forceinline__ bf16x8 x6_lows(const bf16x8& a, const bf16x8& b) {
+    const u32x4 ua = __builtin_bit_cast(u32x4, a), ub = __builtin_bit_cast(u32x4, b);
+    u32x4 l;
 #pragma unroll
     for (int r = 0; r < 4; ++r) l[r] = __builtin_amdgcn_permlane32_swap(ua[r], ub[r], false, false)[0];   // lanes 32-63 of the first <-> lanes 0-31 of the second
-    return __builtin_bit_cast(x6_bf16x8, l);
+    return __builtin_bit_cast(bf16x8, l);
 }
 
 // Global loads the COMPILER DOES NOT SEE (inline asm), waited for with counted vmcnt written by hand.  With an LDS-DMA in flight hipcc's wait-count pass puts
 // vmcnt(0) in front of every use of a loaded register (it treats the DMA and the loads as out of order with each other), so a tile's first conversion waited
 // for EVERY request of the tile (both chunk pairs, the residual rows): 3.5k cycles per tile.  vmcnt returns in order: the requests are issued oldest-needed
 // first, and each consumer waits for exactly what is older than it.
-__device__ __forceinline__ x6_f32x4 x6_gload128(const float* ptr) {
-    x6_f32x4 v;
+__device__ __forceinline__ f32x4v x6_gload128(const float* ptr) {
+    f32x4v v;
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(ptr));
     return v;
 }
 // ... uniform base (scalar registers) + this lane's 32-bit byte offset + immediate: no 64-bit address per request
 template <int OFF>
-__device__ __forceinline__ x6_f32x4 x6_gload128s(const char* base, unsigned voff) {
+__device__ __forceinline__ f32x4v x6_gload128s(const char* base, unsigned voff) {
     static_assert(OFF >= 0 && OFF < 4096, "global immediate offset");
-    x6_f32x4 v;
+    f32x4v v;
     asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(v) : "v"(voff), "s"(base), "n"(OFF));
     return v;
 }
@@ -111,13 +68,6 @@ __device__ __forceinline__ unsigned x6_gload8(const unsigned char* ptr) {
     unsigned v;
     asm volatile("global_load_ubyte %0, %1, off" : "=v"(v) : "v"(ptr));
     return v;
-}
-
-// (fragment addresses are formed where they are used, from an opaque copy of the lane base: left to the compiler, the per-tap sums are hoisted over the whole
-// unrolled tile and held in registers; conv_clx.hip has the same note)
-__device__ __forceinline__ unsigned x6_opaque(unsigned x) {
-    asm volatile("" : "+v"(x));
-    return x;
 }
 
 constexpr int x6_max(int a, int b) { return a > b ? a : b; }
@@ -159,7 +109,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     constexpr int T = K::T, WN = K::WN, RB = K::RB, NMT = K::NMT, NT = K::NT, NXC = K::NXC, NCP = K::NCP, NP1 = K::NP1, NP2 = K::NP2;
     constexpr int h2 = (NTAPS - 1) / 2, nto = NT - 2 * h2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
+    const unsigned lds0 = lds_addr(smem);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -185,8 +135,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
 #pragma unroll
         for (int i = 0; i < K::NPC / K::NW; ++i) {
             const int pc = wave + K::NW * i;            // (uniform)
-            __builtin_amdgcn_global_load_lds((x6_gbl_t*)(W + pc * 1024 + lane * 16),
-                                             (x6_lds_t*)(uintptr_t)__builtin_amdgcn_readfirstlane(lds0 + (u & 1) * K::PAIRB + pc * 1024), 16, 0, 0);
+            dma16(W + pc * 1024 + lane * 16, __builtin_amdgcn_readfirstlane(lds0 + (u & 1) * K::PAIRB + pc * 1024));
         }
     };
 
@@ -206,16 +155,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     }
     // ---- conv1 window: f32 rows -> registers -> lrelu, hi / lo -> LDS, a chunk PAIR (one 128-byte line of a row) at a time.  Thread: row (tid >> 2) of every
     // 64-row block, 16-byte quad (tid & 3) of a chunk's 64-byte row piece.  Interior tiles read one contiguous range.
-    x6_f32x4 rx[NCP][2][NXC];
+    f32x4v rx[NCP][2][NXC];
     {
         dma_pair(std::integral_constant<int, 0>{});
         __builtin_amdgcn_sched_barrier(0);   // (pair 0's weights are the OLDEST request in flight: pair_barrier(0) relies on it)
         if (interior) {   // one contiguous range: uniform row-block bases + one lane offset + immediates
             const char* xwin = reinterpret_cast<const char*>(p.X) + (int64_t)wstart * (C * 4);
             const unsigned xlane = (unsigned)((tid >> 2) * (C * 4) + (tid & 3) * 16);
-            x6_for<0, NCP>([&](auto prc) __attribute__((always_inline)) {
-                x6_for<0, 2>([&](auto cc) __attribute__((always_inline)) {
-                    x6_for<0, NXC>([&](auto ic) __attribute__((always_inline)) {
+            static_for<0, NCP>([&](auto prc) __attribute__((always_inline)) {
+                static_for<0, 2>([&](auto cc) __attribute__((always_inline)) {
+                    static_for<0, NXC>([&](auto ic) __attribute__((always_inline)) {
                         constexpr int pr = decltype(prc)::value, c = decltype(cc)::value, i = decltype(ic)::value;
                         rx[pr][c][i] = x6_gload128s<pr * 128 + c * 64>(xwin + (int64_t)i * (RB * C * 4), xlane);
                     });
@@ -239,24 +188,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     auto convert_pair = [&](auto prc, auto edgec) __attribute__((always_inline)) {
         constexpr int pr = decltype(prc)::value;
         constexpr bool EDGE = decltype(edgec)::value;
-        x6_for<0, 2>([&](auto cc) __attribute__((always_inline)) {
+        static_for<0, 2>([&](auto cc) __attribute__((always_inline)) {
             constexpr int c = decltype(cc)::value;
-            x6_for<0, NXC>([&](auto ic) __attribute__((always_inline)) {
+            static_for<0, NXC>([&](auto ic) __attribute__((always_inline)) {
                 constexpr int i = decltype(ic)::value;
-                x6_f32x4 v = rx[pr][c][i];
+                f32x4v v = rx[pr][c][i];
                 if constexpr (EDGE) {
                     const int pos = wstart + i * RB + (tid >> 2);
-                    if (pos < 0 || pos >= NB) v = x6_f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (pos < 0 || pos >= NB) v = f32x4v{0.f, 0.f, 0.f, 0.f};
                 }
-                x6_bf16x4 h, l;
+                bf16x4 h, l;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float x = fmaxf(v[e], v[e] * slope);   // leaky ReLU for 0 <= slope <= 1
                     h[e] = (__bf16)x;
                     l[e] = (__bf16)(x - (float)h[e]);
                 }
-                x6_write_b64<c * K::X1CH + i * RB * 32>(x1w, h);
-                x6_write_b64<K::X1PART + c * K::X1CH + i * RB * 32>(x1w, l);
+                lds_write_b64<c * K::X1CH + i * RB * 32>(x1w, h);
+                lds_write_b64<K::X1PART + c * K::X1CH + i * RB * 32>(x1w, l);
             });
         });
     };
@@ -269,11 +218,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     constexpr int LPR = 8;                             // lanes per output row of the wave's transposed tile (32 channels = 128 bytes)
     constexpr int RPI = 64 / LPR, NIT = 64 / RPI;      // rows per iteration, iterations
     const int c4 = wm * 32 + (lane % LPR) * 4, rowi = lane / LPR;
-    x6_f32x4 rres[NIT];
+    f32x4v rres[NIT];
     if (interior) {
         const char* rb = reinterpret_cast<const char*>(p.X) + (int64_t)n0 * (C * 4);
         const unsigned rl = (unsigned)((wn * 64 + rowi) * (C * 4) + c4 * 4);
-        x6_for<0, NIT>([&](auto ic) __attribute__((always_inline)) {
+        static_for<0, NIT>([&](auto ic) __attribute__((always_inline)) {
             constexpr int it = decltype(ic)::value;
             rres[it] = x6_gload128s<0>(rb + (int64_t)it * (RPI * C * 4), rl);
         });
@@ -295,10 +244,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
         const int pos = t0 + tid + h * T;
         mval[h] = (p.mask == nullptr || mval[h] != 0) && pos >= 0 && pos < NB ? 1u : 0u;
     }
-    if (tid < 128) x6_write_b32(lds0 + K::BIAS_OFF + tid * 4, bval);
+    if (tid < 128) lds_write_b32(lds0 + K::BIAS_OFF + tid * 4, bval);
 #pragma unroll
     for (int h = 0; h < NMV; ++h)
-        if (tid + h * T < K::ROWS2) x6_write_b8(lds0 + K::MASK_OFF + tid + h * T, mval[h]);
+        if (tid + h * T < K::ROWS2) lds_write_b8(lds0 + K::MASK_OFF + tid + h * T, mval[h]);
     // chunk pair 0's rows (and, older than them, weight pair 0: pair_barrier(0) relies on it); the younger requests stay in flight
 #pragma unroll
     for (int c = 0; c < 2; ++c)
@@ -317,14 +266,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     const unsigned h2same = lds0 + K::WREG + rowl + (lg >= 2 ? 32 : 0);
     const unsigned h2wrap = lds0 + K::WREG + rowl + (lg >= 2 ? K::X2CH - (NTAPS - 1) * 32 : 0);
     struct Fr {
-        x6_bf16x8 ah[2], al[2], bh[4], bl[4];
+        bf16x8 ah[2], al[2], bh[4], bl[4];
     };
-    x6_f32x4 acc[2][4];
+    f32x4v acc[2][4];
     auto zero_acc = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[r][j] = x6_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < 4; ++j) acc[r][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
         // (the zeros are written HERE, wait states before the first MFMA that takes them: left alone the compiler moves each v_mov in front of its first use,
         // and it inserts no wait states in front of an inline-asm MFMA)
         asm volatile("s_nop 3" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[1][2]), "+v"(acc[1][3]));
@@ -335,13 +284,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
         constexpr int aoff = decltype(slotc)::value * K::PAIRB + part * 1024;
         constexpr int cpa = sa / NTAPS, tapa = sa % NTAPS;
         constexpr bool WRAP = tapa == NTAPS - 1;     // step b is the next chunk's first tap
-        if constexpr (rr == 0) (part ? f.al[0] : f.ah[0]) = x6_read_b128<aoff>(abase);
-        else if constexpr (rr == 5) (part ? f.al[1] : f.ah[1]) = x6_read_b128<aoff + 2048>(abase);
+        if constexpr (rr == 0) (part ? f.al[0] : f.ah[0]) = lds_read_b128<aoff>(abase);
+        else if constexpr (rr == 5) (part ? f.al[1] : f.ah[1]) = lds_read_b128<aoff + 2048>(abase);
         else {
             constexpr int j = rr - 1;
-            x6_bf16x8& dst = part ? f.bl[j] : f.bh[j];
-            if constexpr (conv == 0) dst = x6_read_b128<part * K::X1PART + cpa * K::X1CH + j * 512>(x6_opaque(WRAP ? h1wrap : h1same) + (unsigned)(tapa * d32));
-            else dst = x6_read_b128<part * K::X2PART + (blk * 2 + cpa) * K::X2CH + tapa * 32 + j * 512>(WRAP ? h2wrap : h2same);
+            bf16x8& dst = part ? f.bl[j] : f.bh[j];
+            if constexpr (conv == 0) dst = lds_read_b128<part * K::X1PART + cpa * K::X1CH + j * 512>(opaque(WRAP ? h1wrap : h1same) + (unsigned)(tapa * d32));
+            else dst = lds_read_b128<part * K::X2PART + (blk * 2 + cpa) * K::X2CH + tapa * 32 + j * 512>(WRAP ? h2wrap : h2same);
         }
     };
     // the waits are tied to the registers they cover
@@ -351,9 +300,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     auto wait_hi_a_lo_b = [&](Fr& f) __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.ah[0]), "+v"(f.ah[1]), "+v"(f.bl[0]), "+v"(f.bl[1]), "+v"(f.bl[2]), "+v"(f.bl[3]));
     };
-    auto mfma_n = [&](const x6_bf16x8 (&a)[2], const x6_bf16x8 (&b)[4], auto nc) __attribute__((always_inline)) {
+    auto mfma_n = [&](const bf16x8 (&a)[2], const bf16x8 (&b)[4], auto nc) __attribute__((always_inline)) {
         constexpr int n = decltype(nc)::value;
-        x6_mfma(acc[n >> 2][n & 3], a[n >> 2], b[n & 3]);
+        mfma16_bf16(acc[n >> 2][n & 3], a[n >> 2], b[n & 3]);
     };
     Fr fr[2];                    // the fragments of pair u live in fr[u & 1]: a pair's hi x hi product is issued behind the NEXT barrier
     // the barrier in front of pair u: its weights have landed (every wave's DMA pieces: vmcnt(0) then barrier), everybody is done with pair u - 1 (its slot
@@ -379,8 +328,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     // The operands of a set of MFMAs stay allocated until the set has been issued: the fragment reads dealt between the MFMAs return asynchronously, and
     // the compiler (which sees neither the MFMAs nor the loads: inline asm) would otherwise give a load the registers of an operand whose last MFMA in
     // program order is still queued in front of the matrix pipe: the rows of the set's second half then saw the NEXT pair's data (run- and pair-dependent).
-    auto keep_a = [&](const x6_bf16x8 (&a)[2]) __attribute__((always_inline)) { asm volatile("" ::"v"(a[0]), "v"(a[1])); };
-    auto keep_b = [&](const x6_bf16x8 (&b)[4]) __attribute__((always_inline)) { asm volatile("" ::"v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3])); };
+    auto keep_a = [&](const bf16x8 (&a)[2]) __attribute__((always_inline)) { asm volatile("" ::"v"(a[0]), "v"(a[1])); };
+    auto keep_b = [&](const bf16x8 (&b)[4]) __attribute__((always_inline)) { asm volatile("" ::"v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3])); };
     // pair u behind its barrier: [the previous pair's hi x hi products, covering this pair's first reads] -> lo x hi -> hi x lo; its hi x hi stays pending
     auto pair_body = [&](auto uc, auto pendc) __attribute__((always_inline)) {
         constexpr int u = decltype(uc)::value;
@@ -397,7 +346,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
         Fr& g = fr[(u & 1) ^ 1];
         // ---- W_lo (A) and X_hi (B) of this pair
         if constexpr (PEND) {
-            x6_for<0, 8>([&](auto nc) __attribute__((always_inline)) {
+            static_for<0, 8>([&](auto nc) __attribute__((always_inline)) {
                 constexpr int n = decltype(nc)::value;
                 mfma_n(g.ah, g.bh, nc);
                 if constexpr (n == 0 || n == 5) read_one(f, nc, LO{}, CV{}, BK{}, SA{}, SL{});   // al[0], al[1]
@@ -408,13 +357,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
             keep_b(g.bh);
         } else {
             read_one(f, std::integral_constant<int, 0>{}, LO{}, CV{}, BK{}, SA{}, SL{});
-            x6_for<1, 5>([&](auto rc) __attribute__((always_inline)) { read_one(f, rc, HI{}, CV{}, BK{}, SA{}, SL{}); });
+            static_for<1, 5>([&](auto rc) __attribute__((always_inline)) { read_one(f, rc, HI{}, CV{}, BK{}, SA{}, SL{}); });
             read_one(f, std::integral_constant<int, 5>{}, LO{}, CV{}, BK{}, SA{}, SL{});
         }
         wait_lo_a_hi_b(f);
         __builtin_amdgcn_sched_barrier(0);
         // ---- lo x hi; W_hi and X_lo
-        x6_for<0, 8>([&](auto nc) __attribute__((always_inline)) {
+        static_for<0, 8>([&](auto nc) __attribute__((always_inline)) {
             constexpr int n = decltype(nc)::value;
             mfma_n(f.al, f.bh, nc);
             if constexpr (n == 0 || n == 5) read_one(f, nc, HI{}, CV{}, BK{}, SA{}, SL{});   // ah[0], ah[1]
@@ -425,7 +374,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
         wait_hi_a_lo_b(f);
         __builtin_amdgcn_sched_barrier(0);
         // ---- hi x lo
-        x6_for<0, 8>([&](auto nc) __attribute__((always_inline)) {
+        static_for<0, 8>([&](auto nc) __attribute__((always_inline)) {
             mfma_n(f.ah, f.bl, nc);
             __builtin_amdgcn_sched_barrier(0);
         });
@@ -434,7 +383,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     // the pending hi x hi products of pair u without a following pair (the end of a convolution / of a chunk pair)
     auto flush_m2 = [&](auto uc) __attribute__((always_inline)) {
         Fr& g = fr[decltype(uc)::value & 1];
-        x6_for<0, 8>([&](auto nc) __attribute__((always_inline)) { mfma_n(g.ah, g.bh, nc); });
+        static_for<0, 8>([&](auto nc) __attribute__((always_inline)) { mfma_n(g.ah, g.bh, nc); });
         keep_a(g.ah);
         keep_b(g.bh);
         // the accumulators are read by VALU / LDS instructions next: the compiler does not see these MFMAs (inline asm) and inserts no wait states
@@ -445,7 +394,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     // ================================================================================================================================
     // ---- phase 1: t = lrelu(conv1(lrelu(y)) + b1) on positions [t0, t0 + NT) ------------------------------------------------------------
     zero_acc();
-    x6_for<0, NCP>([&](auto bc) __attribute__((always_inline)) {
+    static_for<0, NCP>([&](auto bc) __attribute__((always_inline)) {
         constexpr int blk = decltype(bc)::value;
         constexpr int u0 = blk * NTAPS;
         pair_barrier(std::integral_constant<int, u0>{});
@@ -458,7 +407,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
             __builtin_amdgcn_sched_barrier(0);
         }
         pair_body(std::integral_constant<int, u0>{}, std::false_type{});
-        x6_for<1, NTAPS>([&](auto pc) __attribute__((always_inline)) {
+        static_for<1, NTAPS>([&](auto pc) __attribute__((always_inline)) {
             constexpr int u = u0 + decltype(pc)::value;
             pair_barrier(std::integral_constant<int, u>{});
             pair_body(std::integral_constant<int, u>{}, std::true_type{});
@@ -470,21 +419,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
     flush_m2(std::integral_constant<int, NP1 - 1>{});
     {
         // accumulator tile [r][j]: lane (column l16, row group lg) holds channels wm * 32 + 16 r + 4 lg .. + 3 of position wn * 64 + 16 j + l16
-        x6_f32x4 bq[2];
-        bq[0] = x6_read_f128<0>(lds0 + K::BIAS_OFF + (wm * 32 + 4 * lg) * 4);
-        bq[1] = x6_read_f128<64>(lds0 + K::BIAS_OFF + (wm * 32 + 4 * lg) * 4);
+        f32x4v bq[2];
+        bq[0] = lds_read_f128<0>(lds0 + K::BIAS_OFF + (wm * 32 + 4 * lg) * 4);
+        bq[1] = lds_read_f128<64>(lds0 + K::BIAS_OFF + (wm * 32 + 4 * lg) * 4);
         unsigned mk[4];
-        x6_for<0, 4>([&](auto jc) __attribute__((always_inline)) { mk[decltype(jc)::value] = x6_read_u8<decltype(jc)::value * 16>(lds0 + K::MASK_OFF + wn * 64 + l16); });
+        static_for<0, 4>([&](auto jc) __attribute__((always_inline)) { mk[decltype(jc)::value] = lds_read_u8<decltype(jc)::value * 16>(lds0 + K::MASK_OFF + wn * 64 + l16); });
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(mk[0]), "+v"(mk[1]), "+v"(mk[2]), "+v"(mk[3]));
         const bool allkeep = __builtin_amdgcn_ballot_w64(mk[0] != 0 && mk[1] != 0 && mk[2] != 0 && mk[3] != 0) == ~0ull;
         const unsigned x2w = lds0 + K::WREG + wm * 2 * K::X2CH + (wn * 64 + l16) * 32 + lg * 8;
         auto mid = [&](auto keepc) __attribute__((always_inline)) {
             constexpr bool ALL = decltype(keepc)::value;
-            x6_for<0, 2>([&](auto rc) __attribute__((always_inline)) {
+            static_for<0, 2>([&](auto rc) __attribute__((always_inline)) {
                 constexpr int r = decltype(rc)::value;
-                x6_for<0, 4>([&](auto jc) __attribute__((always_inline)) {
+                static_for<0, 4>([&](auto jc) __attribute__((always_inline)) {
                     constexpr int j = decltype(jc)::value;
-                    x6_bf16x4 h, l;
+                    bf16x4 h, l;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float t = acc[r][j][e] + bq[r][e];
@@ -493,8 +442,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
                         h[e] = (__bf16)t;
                         l[e] = (__bf16)(t - (float)h[e]);
                     }
-                    x6_write_b64<r * K::X2CH + j * 512>(x2w, h);
-                    x6_write_b64<K::X2PART + r * K::X2CH + j * 512>(x2w, l);
+                    lds_write_b64<r * K::X2CH + j * 512>(x2w, h);
+                    lds_write_b64<K::X2PART + r * K::X2CH + j * 512>(x2w, l);
                 });
             });
         };
@@ -508,7 +457,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
 
     // ---- phase 2: conv2 over the LDS-resident intermediate -----------------------------------------------------------------------------------
     pair_body(std::integral_constant<int, NP1>{}, std::false_type{});
-    x6_for<NP1 + 1, NP1 + NP2>([&](auto uc) __attribute__((always_inline)) {
+    static_for<NP1 + 1, NP1 + NP2>([&](auto uc) __attribute__((always_inline)) {
         pair_barrier(uc);
         pair_body(uc, std::true_type{});
     });
@@ -522,16 +471,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) *reinterpret_cast<x6_f32x4*>(ttile + (j * 16 + l16) * TP + 16 * r + 4 * lg) = acc[r][j];
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4v*>(ttile + (j * 16 + l16) * TP + 16 * r + 4 * lg) = acc[r][j];
     const float* bias_s = reinterpret_cast<const float*>(smem + K::BIAS_OFF);
     const unsigned char* mask_s = reinterpret_cast<const unsigned char*>(smem + K::MASK_OFF);
-    const x6_f32x4 b4 = *reinterpret_cast<const x6_f32x4*>(bias_s + 64 + c4);
-    x6_f32x4 rold[NIT];
+    const f32x4v b4 = *reinterpret_cast<const f32x4v*>(bias_s + 64 + c4);
+    f32x4v rold[NIT];
     if (p.accumulate) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int64_t po = min((int64_t)n0 + wn * 64 + it * RPI + rowi, (int64_t)NB - 1);
-            rold[it] = *reinterpret_cast<const x6_f32x4*>(p.Y + po * C + c4);
+            rold[it] = *reinterpret_cast<const f32x4v*>(p.Y + po * C + c4);
         }
     }
     const float beta = p.beta;
@@ -542,18 +491,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void r
             const int row = it * RPI + rowi;
             const int o = wn * 64 + row;                    // output index inside the workgroup's range
             const int pos = n0 + o;                         // < 2^31 (checked by the caller)
-            const x6_f32x4 a = *reinterpret_cast<const x6_f32x4*>(ttile + row * TP + (lane % LPR) * 4);
+            const f32x4v a = *reinterpret_cast<const f32x4v*>(ttile + row * TP + (lane % LPR) * 4);
             if (o >= nto || pos >= NB) continue;
             // (contraction is off in this file; respair_clx.hip is compiled with hipcc's default, which fuses `x * beta + old` into one fma: written out)
-            x6_f32x4 v;
+            f32x4v v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float s = a[e] + b4[e] + rres[it][e];
                 v[e] = p.accumulate ? __builtin_fmaf(s, beta, rold[it][e]) : s * beta;
             }
-            if (!mask_s[o + h2]) v = x6_f32x4{0.f, 0.f, 0.f, 0.f};   // position n0 + o = intermediate row o + h2
-            if constexpr (NTS) __builtin_nontemporal_store(v, reinterpret_cast<x6_f32x4*>(p.Y + (int64_t)pos * C + c4));
-            else *reinterpret_cast<x6_f32x4*>(p.Y + (int64_t)pos * C + c4) = v;
+            if (!mask_s[o + h2]) v = f32x4v{0.f, 0.f, 0.f, 0.f};   // position n0 + o = intermediate row o + h2
+            if constexpr (NTS) __builtin_nontemporal_store(v, reinterpret_cast<f32x4v*>(p.Y + (int64_t)pos * C + c4));
+            else *reinterpret_cast<f32x4v*>(p.Y + (int64_t)pos * C + c4) = v;
         }
     };
     if (p.nt_store) store_rows(std::true_type{});
