@@ -254,7 +254,8 @@ int sbv2_debug_loudness(int device, const double* x, const int64_t* lens, int ns
  *      the deepest reduction 20 log10 min s (<= 0; 0 when idle).  Step 2 bounds the samples, not the interpolated peak of the
  *      gain-modulated signal: TP_out is reported, not bounded.  Measured at most 1e-5 dB above the ceiling, on speech-like
  *      signals and on dense noise-like audio limited at the full depth alike (s moves slowly against the interpolator's 24 samples).
- * The sbv2_stream_* and sbv2_node_* paths have no limiter, as they have no loudness. */
+ * The sbv2_stream_* and sbv2_node_* paths have no limiter, as they have no loudness; a stream can take step 2 alone at a gain fixed ahead:
+ * struct sbv2_stream_level. */
 typedef struct sbv2_limiter {
     double target_lufs;          /* [-70, -5] */
     double true_peak_max_dbtp;   /* [-20, 0] */
@@ -426,6 +427,59 @@ int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, 
  * ones allowed, the last one ends the stream); dst receives the pushes' bytes back to back, out_bytes_per_push[ncuts + 1] their sizes. */
 int sbv2_debug_flac_stream_encode(int device, const int16_t* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, uint8_t* dst,
                                   int64_t capacity, int64_t* out_bytes_per_push);
+/* ---- new: level control on a stream: a fixed gain and the look-ahead limiter of sbv2_limiter, carried from chunk to chunk ON THE DEVICE.
+ * Step 3 of sbv2_limiter, the make-up loop, needs the whole signal; step 2, its gain curve for a pre-gain named ahead, does not.  For the whole
+ * delivered signal y of the stream (resampled to fs, f64, before any cast or quantiser), g0 = 10^(gain_db / 20), c = 10^(ceiling / 20),
+ * K = fs div 100:  x = y g0 s, with e, r, m and s exactly those of sbv2_limiter step 2 at that g0, the onset rule (m = m[0] before the start),
+ * the end rule (r = 1 past the end), s = min(sum, r) and the clamp of x to [-c, c] included.  So |x[n]| <= c for every sample and s16 cannot
+ * clip, whatever the gain.  There is no make-up loop and no max_reduction: the depth is whatever the signal needs at that gain, and it is
+ * reported (sbv2_stream_level_stats), not bounded.  There is no idle rule either: a stream whose r is 1 throughout still delivers
+ * y g0 min(sum of the K taps over ones, 1), which may differ from y g0 in the last bit.  The gain is the caller's: for a consistent level,
+ * target - L from the loudness stats of any /synthesize answer of the same voice.
+ * Look-ahead: t[o], the interpolated magnitude behind e, reads y[o - 11 .. o + 12]; r[p] reads t[p - 1 .. p]; m[j] reads r[j .. j + K - 1];
+ * s[n] reads m[n - K + 1 .. n].  Sample n of x therefore depends on y[n - K - 11 .. n + K + 11] and on nothing else, and is final once
+ * A = K - 1 + 12 samples follow it (91 at 8 kHz, 452 at 44.1 kHz, 491 at 48 kHz).
+ * Delivery rule: after chunks of S samples in all have been taken and the utterance has not ended, exactly max(0, S - A) samples of x have
+ * been delivered; the call that takes the last chunk delivers all the rest.  Time is not shifted: sample j of the output is sample j of the
+ * utterance (sbv2_stream_marks stays valid as it is); only delivery runs A samples late.  x does not depend on the chunk size: bit for bit
+ * the samples sbv2_debug_limiter_fixed gives for the whole y. */
+typedef struct sbv2_stream_level {
+    double gain_db;              /* [-40, 40]; g0 = 10^(gain_db / 20) */
+    double true_peak_max_dbtp;   /* [-20, 0];  c = 10^(ceiling / 20) */
+    double reserved[2];          /* must be 0 */
+} sbv2_stream_level;
+/* Host only: A at fmt->sample_rate; -1 for a bad fmt. */
+int64_t sbv2_stream_level_lookahead(const sbv2_pcm_format* fmt);
+/* Host only: bytes that always suffice for one sbv2_stream_next_level call of a stream with chunks of chunk_native_samples (chunk_frames * hop):
+ * n = sbv2_pcm_format_length of the chunk + A samples, as n * bytes per sample, or with flac != 0 (fmt s16) the bound of sbv2_flac_stream_bound
+ * for a push of n samples.  -1 for a bad fmt. */
+int64_t sbv2_stream_level_bound(const sbv2_pcm_format* fmt, int64_t chunk_native_samples, int flac);
+/* Inputs as sbv2_stream_begin_format; fmt must not be NULL, fmt->normalize must be 0, f32 or s16; flac != 0 needs s16 and encodes the delivered
+ * s16 samples as ONE FLAC stream, as sbv2_stream_begin_flac does.  A NULL level, out-of-range or non-finite fields and non-zero reserved
+ * fields are refused.  *total_samples at fmt->sample_rate: the same total as without a level. */
+int sbv2_stream_begin_level(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
+                            const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, const sbv2_stream_level* level, int flac,
+                            sbv2_stream** out, int64_t* total_samples);
+/* Takes the next chunk.  *n_consumed = the chunk's samples at fmt->sample_rate (those sbv2_stream_next_format would have written), 0 once the
+ * utterance is complete: the end signal.  *n_out = samples of x written to dst in fmt's encoding by the delivery rule, or for a FLAC stream
+ * the bytes of the frames those samples complete (the 42-byte header in front on the first call); *n_out may be 0 while *n_consumed > 0 (a
+ * 16-frame chunk of a decoder with hop 16 is 256 samples at 44.1 kHz, A is 452).  Too small a capacity is refused with nothing written and
+ * nothing consumed: the call can be repeated (sbv2_stream_level_bound always suffices).  The other three sbv2_stream_next* calls are refused on
+ * a level stream, this one on any other stream. */
+int sbv2_stream_next_level(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n_out, int64_t* n_consumed);
+/* stats[0] = 20 log10 min s, the deepest reduction over the utterance in dB (<= 0); stats[1] = max |x| before the cast / quantiser (<= c).
+ * Kept on the device across the chunks (min and max are exact: the values do not depend on the chunk size), read once here.  Refused before
+ * the stream is complete (sbv2_stream_next_level has answered *n_consumed = 0, or has taken the last chunk). */
+int sbv2_stream_level_stats(sbv2_stream* s, double* stats);
+/* Test hook: step 2 at the fixed gain of `level`, in one shot, on host f64 signals (layout as sbv2_debug_limiter) -> out_x, stats 2 doubles per
+ * signal as sbv2_stream_level_stats.  The yardstick of the streamed path. */
+int sbv2_debug_limiter_fixed(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_stream_level* level,
+                             double* out_x, double* stats);
+/* Test hook: the same limiter fed piece by piece: the n samples of x cut at the ascending positions cuts[ncuts] into ncuts + 1 pushes (empty
+ * ones allowed, the last one ends the stream); out_x receives the pushes' samples back to back (n in all), out_per_push[ncuts + 1] their
+ * counts (the delivery rule), stats the 2 doubles.  level, rate and cuts are checked before any device call. */
+int sbv2_debug_limiter_stream(int device, const double* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
+                              const sbv2_stream_level* level, double* out_x, int64_t* out_per_push, double* stats);
 /* ---- new: speech marks of a stream.  Host only, valid from sbv2_stream_begin* onwards: the token spans (see sbv2_marks) of the stream's one
  * utterance at place 0 and at the stream's delivered rate (native for sbv2_stream_begin).  Every duration is known before the first replay, so
  * the client has the full timing before the first audio byte; the samples of all chunks sum to the last token's end (durations summing to >= 1).

@@ -34,6 +34,11 @@ class Sbv2Limiter(C.Structure):
     _fields_ = [("target_lufs", C.c_double), ("true_peak_max_dbtp", C.c_double), ("max_reduction_db", C.c_double), ("reserved", C.c_double)]
 
 
+class Sbv2StreamLevel(C.Structure):
+    """struct sbv2_stream_level (include/sbv2_hip.h)."""
+    _fields_ = [("gain_db", C.c_double), ("true_peak_max_dbtp", C.c_double), ("reserved", C.c_double * 2)]
+
+
 class Sbv2UttOptions(C.Structure):
     """struct sbv2_utt_options (include/sbv2_hip.h)."""
     _fields_ = [("sdp_ratio", f32p), ("length_scale", f32p), ("noise_scale", f32p), ("noise_scale_w", f32p),
@@ -145,6 +150,16 @@ SYMBOLS = {
                                          C.POINTER(C.c_void_p), i64p]),
     "sbv2_stream_next_flac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, i64p, i64p]),
     "sbv2_debug_flac_stream_encode": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, i64p, C.c_int, C.c_int32, C.c_void_p, C.c_int64, i64p]),
+    "sbv2_stream_level_lookahead": (C.c_int64, [C.POINTER(Sbv2PcmFormat)]),
+    "sbv2_stream_level_bound": (C.c_int64, [C.POINTER(Sbv2PcmFormat), C.c_int64, C.c_int]),
+    "sbv2_stream_begin_level": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), i64p, i64p, i64p, C.c_int64, C.POINTER(Sbv2PcmFormat),
+                                          C.POINTER(Sbv2StreamLevel), C.c_int, C.POINTER(C.c_void_p), i64p]),
+    "sbv2_stream_next_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, i64p, i64p]),
+    "sbv2_stream_level_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "sbv2_debug_limiter_fixed": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2StreamLevel), C.c_void_p,
+                                           C.POINTER(C.c_double)]),
+    "sbv2_debug_limiter_stream": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2StreamLevel), C.c_void_p, i64p,
+                                            C.POINTER(C.c_double)]),
     "sbv2_stream_uses_graph": (C.c_int, [C.c_void_p]),
     "sbv2_stream_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "sbv2_stream_end": (None, [C.c_void_p]),

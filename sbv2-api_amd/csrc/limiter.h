@@ -1,12 +1,15 @@
 // Look-ahead true-peak limiter on the device (limiter.hip): the stage between the loudness meter and the gain / quantiser / FLAC encoder of
 // sbv2_pipeline_fetch_pcm_limited / _fetch_flac_limited (the limiter GainStage of PcmFormatter::run), and of the test hook
-// sbv2_debug_limiter.  The convention is the header comment of struct sbv2_limiter (include/sbv2_hip.h).
+// sbv2_debug_limiter.  The convention is the header comment of struct sbv2_limiter (include/sbv2_hip.h).  Its step 2 alone, at a gain the
+// caller fixes, is the level control of a stream (struct sbv2_stream_level): in one shot (Limiter::run_fixed) or fed piece by piece with an
+// O(K) tail carried on the device (StreamLimiter; vits.cpp stream_enqueue and the sbv2_debug_limiter_fixed / _stream hooks).
 #pragma once
 #include "common.h"
 #include "loudness.h"
 #include "pcm_format.h"
 
 struct sbv2_limiter;
+struct sbv2_stream_level;
 
 namespace sbv2 {
 
@@ -16,6 +19,15 @@ struct LimiterSpec {
 };
 // throws with a message for a null pointer, out-of-range or non-finite fields and a non-zero reserved field
 LimiterSpec limiter_spec(const sbv2_limiter* lim);
+
+// a checked sbv2_stream_level
+struct StreamLevelSpec {
+    double gain_db = 0.0, ceiling = 0.0;   // dB, dBTP
+};
+// throws with a message for a null pointer, out-of-range or non-finite fields and non-zero reserved fields
+StreamLevelSpec stream_level_spec(const sbv2_stream_level* lv);
+// A = K - 1 + 12 at `rate`: the samples that must follow a sample before its gain is final (throws for a rate the limiter has no window for)
+int64_t stream_level_lookahead(int rate);
 
 // Device state of the limiter of one execution context, beside the LoudnessMeter and outside the activation arena: the signal table, the
 // per-signal gains and stats, the interpolated magnitudes, the evaluated signal x and the per-tile minima (grown on demand; growing
@@ -31,6 +43,9 @@ class Limiter {
     // is.  stats_host() holds 6 doubles per signal (L, TP, G, L_out, TP_out, deepest reduction in dB) once s has been synchronised.
     const double* run(const double* y, const std::vector<FmtSignal>& sig, int rate, const LimiterSpec& lim, LoudnessMeter& meter, hipStream_t s,
                       const double** unit);
+    // Step 2 alone at the fixed gain of lv, once, without a meter: returns x as run does; stats_host() then holds 2 doubles per signal
+    // (20 log10 min s, max |x|) once s has been synchronised.
+    const double* run_fixed(const double* y, const std::vector<FmtSignal>& sig, int rate, const StreamLevelSpec& lv, hipStream_t s);
     const double* stats_host() const { return stats_host_; }
 
   private:
@@ -38,6 +53,43 @@ class Limiter {
     PinnedBuffer host_;      // signal table, Hann taps, then the stats
     DeviceBuffer dev_;
     double* stats_host_ = nullptr;
+};
+
+// The fixed-gain limiter fed piece by piece (a synthesis stream's replays): begin, then pushes in stream order.  Every emitted sample has the
+// bits run_fixed gives it on the whole signal, however the signal is cut.  After pushes of S samples in all, max(0, S - A) samples have been
+// emitted, A = stream_level_lookahead(rate); the last push emits the rest.  Nothing here waits for the GPU after begin (which may grow the
+// buffers): what a push emits follows from the sample counts.
+class StreamLimiter {
+  public:
+    StreamLimiter() = default;
+    StreamLimiter(const StreamLimiter&) = delete;
+    StreamLimiter& operator=(const StreamLimiter&) = delete;
+    // a stream of total_samples at `rate`, fed in pushes of up to max_push samples: nothing fed, the running stats at (1, 0)
+    void begin(int rate, int64_t total_samples, int64_t max_push, const StreamLevelSpec& lv, hipStream_t s);
+    // where the next push's f64 samples go (device): right behind the carried tail
+    double* dst() const;
+    // The n samples at dst() join the stream; `last`: the stream ends with them.  Writes the samples this push completes to out (device f64,
+    // up to n + A of them) and returns their count = emitted_after(fed) - emitted_after(fed before).  The last push also enqueues the copy
+    // of the stats to the host.
+    int64_t push(int64_t n, bool last, double* out, hipStream_t s);
+    int64_t emitted_after(int64_t fed, bool last) const;
+    int64_t lookahead() const { return A_; }
+    int64_t fed() const { return fed_; }   // samples pushed so far
+    double* out_buffer() const;     // max_push + A doubles of this object's for `out`
+    const double* unit() const;     // one device double of 1.0: the gain the cast kernel multiplies the emitted x by
+    // (20 log10 min s, max |x|) over the whole stream; valid once s has passed the last push
+    void stats(double* out) const;
+
+  private:
+    DeviceBuffer buf_[2];   // [tail | new samples], taking turns
+    DeviceBuffer t_;        // the window's interpolated magnitudes
+    DeviceBuffer x_;
+    DeviceBuffer aux_;      // running stats and the unit gain | Hann taps | per-tile min s | per-tile max |x|
+    PinnedBuffer host_;     // Hann taps, then the stats
+    int K_ = 0, cur_ = 0;
+    int64_t A_ = 0, total_ = 0, max_push_ = 0, fed_ = 0, emitted_ = 0, pos0_ = 0, tail_ = 0;
+    double g0_ = 1.0, c_ = 1.0, hsum_ = 1.0;
+    bool done_ = false;
 };
 
 }  // namespace sbv2

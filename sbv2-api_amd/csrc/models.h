@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "flac_encode.h"
+#include "limiter.h"
 #include "ops.h"
 #include "pcm_format.h"
 
@@ -320,13 +321,20 @@ class VitsModel {
     // fmt (optional): the chunks leave the device in that output format (pcm_format.h; normalize must be 0): chunk [a, b) of native samples
     // emits output samples [ceil(a L / M), ceil(b L / M)), computed from the window's exact samples beyond the centre
     // flac (fmt must be s16): the chunks' samples are not delivered but pushed into a FlacStreamEncoder (flac_encode.h) behind each replay
-    int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false);
+    // level (needs fmt): the formatter stops at y (f64), a StreamLimiter (limiter.h) takes it replay by replay at the fixed gain and holds the
+    // ceiling; what it emits is cast / quantised and delivered (or, with flac, pushed into the encoder): delivery runs A samples behind
+    int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false, const StreamLevelSpec* level = nullptr);
     int64_t stream_chunk(int64_t f0, float* dst_host, int64_t capacity);
     // formatted stream: output samples of the chunk at f0 -> dst_host (capacity_bytes); returns the samples written
     int64_t stream_chunk_format(int64_t f0, void* dst_host, int64_t capacity_bytes);
     // FLAC stream: the bytes of every frame the chunk at f0 completes (the stream header before the first) -> dst_host, *n_bytes of them
     // (possibly 0); returns the s16 samples the chunk consumed.  Chunks in order only.
     int64_t stream_chunk_flac(int64_t f0, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes);
+    // level stream: what the chunk at f0 completes -> dst_host; *n_out = samples written (bytes when FLAC; possibly 0); returns the samples
+    // of the chunk taken.  Chunks in order only.
+    int64_t stream_chunk_level(int64_t f0, void* dst_host, int64_t capacity_bytes, int64_t* n_out);
+    // level stream, after its last chunk was taken: 20 log10 min s and max |x| over the utterance
+    void stream_level_stats(double* out) const;
     bool stream_graph_captured() const { return chunk_ && chunk_->exec != nullptr; }
     size_t stream_workspace_bytes() const { return (chunk_ ? chunk_->ar.capacity() : 0) + (burst_ ? burst_->ar.capacity() : 0); }
     // results of the last forward
@@ -443,6 +451,7 @@ class VitsModel {
         std::vector<int64_t> fmt_off[2], fmt_n[2];  // formatted stream: each window's output samples in its slot (offset, count)
         FlacStreamEncoder::Push flac_push[2];       // FLAC stream: the slot's push (its pinned region is host[slot]) and, per window, the
         std::vector<int> flac_fr[2];                // frames of the push it completes: [flac_fr[w], flac_fr[w + 1])
+        std::vector<int64_t> lvl_taken[2];          // level stream: the samples each window fed (fmt_off / fmt_n then hold what it was handed back)
         ~ChunkPlan() {
             if (exec) (void)hipGraphExecDestroy(exec);
             if (graph) (void)hipGraphDestroy(graph);
@@ -454,7 +463,8 @@ class VitsModel {
     };
     void ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, int nwin);
     void stream_enqueue(ChunkPlan& c, int64_t f0, int slot);
-    int64_t stream_take(int64_t f0, void* dst_host, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes);   // flac_bytes: FLAC delivery
+    // flac_bytes: FLAC delivery; taken (level stream): receives the samples the chunk fed, the return value being what was delivered
+    int64_t stream_take(int64_t f0, void* dst_host, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes, int64_t* taken = nullptr);
     int64_t stream_fmt_samples(const ChunkPlan& c) const;   // formatted output of one replay of c, upper bound
     size_t stream_fmt_bytes(const ChunkPlan& c) const;
     bool sfmt_on_ = false;                       // the running stream is formatted (stream_begin with fmt)
@@ -462,6 +472,9 @@ class VitsModel {
     std::shared_ptr<PcmFormatter> sfmtr_;          // its launches: slots 0 / 1 = chunk_'s, 2 / 3 = burst_'s
     bool sflac_on_ = false;                      // ... and encoded as FLAC replay by replay (stream_begin with flac; implies sfmt_on_)
     std::shared_ptr<FlacStreamEncoder> sflac_;
+    bool slevel_on_ = false;                     // ... and level-controlled replay by replay (stream_begin with level; implies sfmt_on_)
+    int64_t slevel_A_ = 0;                       // its look-ahead in delivered samples (0 without a level)
+    std::shared_ptr<StreamLimiter> slim_;
     bool stream_bursts_ = false;                 // the running stream uses burst_ behind its first chunk
     std::shared_ptr<ChunkPlan> chunk_, burst_;   // one window (an utterance's first chunk) / kStreamBurst windows per replay (every later one)
     Plane z_{};              // flow output of the last forward (frame-rate plane, packed layout fl_)

@@ -45,10 +45,12 @@ class Limiter;   // limiter.h
 struct LimiterSpec;
 
 // The gain stage of a formatting run, between the resampler and the quantiser: none (peak-normalise or not, as spec.normalize says), a
-// loudness gain from `meter` (loudness.hip), or the look-ahead limiter (limiter.hip).  Only these three can be built.
+// loudness gain from `meter` (loudness.hip), or the look-ahead limiter (limiter.hip).  A fourth kind ends the run at the stage's input: y
+// (f64) is written to a caller-given address and nothing else happens (the level control of a stream takes it from there, vits.cpp).
 struct GainStage {
-    enum Kind { kNone, kLoudness, kLimiter };
+    enum Kind { kNone, kLoudness, kLimiter, kExposeY };
     GainStage() = default;
+    explicit GainStage(double* y_dev) : kind(kExposeY), y_out(y_dev) {}
     GainStage(LoudnessMeter& m, const LoudnessSpec& l) : kind(kLoudness), meter(&m), ln(&l) {}
     GainStage(LoudnessMeter& m, Limiter& li, const LimiterSpec& l) : kind(kLimiter), meter(&m), limiter(&li), lim(&l) {}
     const Kind kind = kNone;
@@ -56,6 +58,7 @@ struct GainStage {
     const LoudnessSpec* const ln = nullptr;
     Limiter* const limiter = nullptr;
     const LimiterSpec* const lim = nullptr;
+    double* const y_out = nullptr;          // kExposeY: total doubles on the device
 };
 
 // Device state of the formatting launches of one execution context: the polyphase tables (per rate, built once), the tables of pieces /
@@ -70,7 +73,7 @@ class PcmFormatter {
     void* out_buffer(size_t bytes, hipStream_t s) { return out_.reserve(bytes, s); }
     // enqueues the formatting of `sig` on `s`: total = sum of the signals' j1 - j0 samples into dst_dev (device, total * spec.bytes() bytes).
     // With a gain stage (spec.normalize must be 0): y in f64, then meter.measure(y) and y times each signal's gain, or limiter.run(y, meter)
-    // and its x as it is; the stage runs also when every signal is empty, so that its stats are written.
+    // and its x as it is; the stage runs also when every signal is empty, so that its stats are written.  kExposeY: y to gain.y_out, dst_dev unused.
     void run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
              int slot, hipStream_t s, const GainStage& gain = GainStage());
 
@@ -86,5 +89,8 @@ class PcmFormatter {
     DeviceBuffer peak_;   // max |y| (f64 bit pattern), one per signal
     DeviceBuffer out_;
 };
+
+// n f64 samples x (device) times *unit (one device double) -> dst in `encoding` (0: f32, 1: s16), with the cast / quantiser of the gain stages
+void pcm_cast(const double* x, int64_t n, const double* unit, int encoding, void* dst_dev, hipStream_t s);
 
 }  // namespace sbv2

@@ -249,7 +249,7 @@ void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& piec
     if (sig.empty()) return;
     const double* gain = nullptr;
     if (total <= 0) {
-        if (staged) apply_gain(stage, nullptr, sig, spec.rate, s, &gain);
+        if (staged && stage.kind != GainStage::kExposeY) apply_gain(stage, nullptr, sig, spec.rate, s, &gain);
         return;
     }
     const float* tp = taps(spec, s);
@@ -282,6 +282,11 @@ void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& piec
         HIP_CHECK(hipGetLastError());
         return;
     }
+    if (stage.kind == GainStage::kExposeY) {
+        hipLaunchKernelGGL(k_pcm_resample<3>, grid, block, 0, s, a, stage.y_out, nullptr);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
     double* tmp = static_cast<double*>(tmp_.reserve(sizeof(double) * (size_t)total, s));
     auto* peak = static_cast<unsigned long long*>(peak_.reserve(sizeof(unsigned long long) * sig.size(), s));
     if (staged) {
@@ -296,6 +301,15 @@ void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& piec
     hipLaunchKernelGGL(k_pcm_resample<2>, grid, block, 0, s, a, tmp, peak);
     if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain<1>, grid, block, 0, s, tmp, a.sig, a.nsig, peak, total, dst_dev);
     else hipLaunchKernelGGL(k_pcm_gain<0>, grid, block, 0, s, tmp, a.sig, a.nsig, peak, total, dst_dev);
+    HIP_CHECK(hipGetLastError());
+}
+
+void pcm_cast(const double* x, int64_t n, const double* unit, int encoding, void* dst_dev, hipStream_t s) {
+    if (n <= 0) return;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    // (one signal: find_signal answers 0 without reading the table)
+    if (encoding == 1) hipLaunchKernelGGL(k_pcm_gain_sig<1>, grid, block, 0, s, x, nullptr, 1, unit, n, dst_dev);
+    else hipLaunchKernelGGL(k_pcm_gain_sig<0>, grid, block, 0, s, x, nullptr, 1, unit, n, dst_dev);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -11,7 +11,7 @@ struct sbv2_stream {
     sbv2_bert* bert = nullptr;
     sbv2_vits* vits = nullptr;
     int64_t frames = 0, next = 0, chunk = 0;
-    bool formatted = false, flac = false;
+    bool formatted = false, flac = false, level = false;
     // speech marks (sbv2_stream_marks): the utterance's expanded durations, on the host since the forward's one sync, and the delivered format
     std::vector<int64_t> durations;
     PcmFmtSpec spec;
@@ -57,6 +57,7 @@ int sbv2_stream_begin(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch,
 int sbv2_stream_next(sbv2_stream* s, float* dst, int64_t capacity, int64_t* n) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n, "bad arguments");
+    SBV2_REQUIRE(!s->level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
     SBV2_REQUIRE(!s->flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
     SBV2_REQUIRE(!s->formatted, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
     *n = 0;
@@ -95,6 +96,7 @@ int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch*
 int sbv2_stream_next_format(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n, "bad arguments");
+    SBV2_REQUIRE(!s->level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
     SBV2_REQUIRE(!s->flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
     SBV2_REQUIRE(s->formatted, "this stream has no output format: take its chunks with sbv2_stream_next");
     *n = 0;
@@ -147,12 +149,96 @@ int sbv2_stream_begin_flac(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* b
 int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, int64_t* n_bytes, int64_t* n_samples) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n_bytes && n_samples, "bad arguments");
+    SBV2_REQUIRE(!s->level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
     SBV2_REQUIRE(s->flac, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
     *n_bytes = *n_samples = 0;
     if (s->next < s->frames) {
         *n_samples = s->vits->m->stream_chunk_flac(s->next, dst, capacity_bytes, n_bytes);
         s->next += s->chunk;
     }
+    API_END
+}
+
+// Host only: A, the delivered samples a level stream runs behind (-1: bad fmt)
+int64_t sbv2_stream_level_lookahead(const sbv2_pcm_format* fmt) {
+    try {
+        return stream_level_lookahead(pcm_format_spec(fmt).rate);
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// Host only: bytes that always suffice for one sbv2_stream_next_level call of a stream with chunks of chunk_native_samples: a call hands
+// back at most the chunk's samples and the A the stream held back (-1: bad fmt)
+int64_t sbv2_stream_level_bound(const sbv2_pcm_format* fmt, int64_t chunk_native_samples, int flac) {
+    try {
+        const PcmFmtSpec spec = flac ? flac_stream_spec(fmt) : pcm_format_spec(fmt);
+        SBV2_REQUIRE(!spec.normalize, "a level stream cannot normalise (normalize must be 0): the peak of the utterance is not known ahead");
+        SBV2_REQUIRE(chunk_native_samples >= 0, "negative sample count");
+        const int64_t n = pcm_format_out_len(spec, chunk_native_samples) + stream_level_lookahead(spec.rate);
+        return flac ? flac_stream_bound(n) : n * spec.bytes();
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// Same as sbv2_stream_begin_format (or, with flac, sbv2_stream_begin_flac) with the fixed-gain limiter of `level` between the resampler and
+// the cast / quantiser (vits.cpp stream_enqueue, limiter.hip StreamLimiter).
+int sbv2_stream_begin_level(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
+                            const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, const sbv2_stream_level* level, int flac,
+                            sbv2_stream** out, int64_t* total_samples) {
+    API_BEGIN
+    SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
+    SBV2_REQUIRE(batch->n == 1, "sbv2_stream_begin_level takes one utterance");
+    SBV2_REQUIRE(bert->m->device() == vits->m->device(), "bert and vits handles live on different devices");
+    const PcmFmtSpec spec = flac ? flac_stream_spec(fmt) : pcm_format_spec(fmt);
+    SBV2_REQUIRE(!spec.normalize, "a level stream cannot normalise (normalize must be 0): the peak of the utterance is not known ahead");
+    const StreamLevelSpec lv = stream_level_spec(level);
+    VitsBatch v = to_batch(batch);
+    v.skip_decoder = true;
+    pipeline_run_one(*bert->m, *vits->m, v, token_ids, s_lens, word2ph);
+    std::unique_ptr<sbv2_stream> s(new sbv2_stream);
+    s->bert = bert;
+    s->vits = vits;
+    s->chunk = chunk_frames;
+    s->durations = vits->m->used_durations();
+    s->spec = spec;
+    s->formatted = s->level = true;
+    s->flac = flac != 0;
+    s->frames = vits->m->stream_begin((int)chunk_frames, &spec, flac != 0, &lv);
+    if (total_samples) *total_samples = pcm_format_out_len(spec, s->frames * vits->m->cfg().hop());
+    *out = s.release();
+    API_END
+}
+
+// What the next chunk completes -> dst (host): *n_out samples in the stream's encoding, or with FLAC the *n_out bytes of the frames that
+// those samples complete (the stream header in front on the first call).  *n_consumed = samples of the chunk taken, 0 once the utterance
+// is complete; *n_out may be 0 while *n_consumed > 0.
+int sbv2_stream_next_level(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n_out, int64_t* n_consumed) {
+    API_BEGIN
+    SBV2_REQUIRE(s && dst && n_out && n_consumed, "bad arguments");
+    SBV2_REQUIRE(s->level, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
+    if (s->next < s->frames) {
+        int64_t out = 0;
+        const int64_t taken = s->vits->m->stream_chunk_level(s->next, dst, capacity_bytes, &out);
+        *n_out = out;
+        *n_consumed = taken;
+        s->next += s->chunk;
+    } else {
+        *n_out = *n_consumed = 0;
+    }
+    API_END
+}
+
+// 20 log10 min s (the deepest reduction, <= 0) and max |x| (before the cast / quantiser) over the utterance, once its last chunk was taken
+int sbv2_stream_level_stats(sbv2_stream* s, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(s && stats, "bad arguments");
+    SBV2_REQUIRE(s->level, "this stream was not begun with a level");
+    SBV2_REQUIRE(s->next >= s->frames, "the level stats exist once the stream is complete: take its chunks to the end first");
+    s->vits->m->stream_level_stats(stats);
     API_END
 }
 

@@ -350,6 +350,61 @@ int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsi
     API_END
 }
 
+int sbv2_debug_limiter_fixed(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_stream_level* level,
+                             double* out_x, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(nsig >= 1 && lens && stats, "bad arguments");
+    const StreamLevelSpec spec = stream_level_spec(level);
+    double coef[10];
+    loudness_kweight(sample_rate, coef);   // refuses unsupported rates
+    int64_t total = 0;
+    const std::vector<FmtSignal> sig = packed_signals(lens, nsig, &total);
+    SBV2_REQUIRE(total == 0 || (x && out_x), "bad arguments");
+    AudioScratch r(device, x, sizeof(double) * (size_t)total);
+    Limiter limiter;
+    const double* lx = limiter.run_fixed(r.x.as<double>(), sig, sample_rate, spec, r.s);
+    if (total) HIP_CHECK(hipMemcpyAsync(out_x, lx, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    std::memcpy(stats, limiter.stats_host(), sizeof(double) * 2 * nsig);
+    API_END
+}
+
+int sbv2_debug_limiter_stream(int device, const double* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
+                              const sbv2_stream_level* level, double* out_x, int64_t* out_per_push, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(n >= 0 && ncuts >= 0 && (ncuts == 0 || cuts) && out_per_push && stats && (n == 0 || (x && out_x)), "bad arguments");
+    const StreamLevelSpec spec = stream_level_spec(level);
+    double coef[10];
+    loudness_kweight(sample_rate, coef);   // refuses unsupported rates
+    // push i = samples [edge[i], edge[i + 1])
+    std::vector<int64_t> edge(1, 0);
+    for (int i = 0; i < ncuts; ++i) {
+        SBV2_REQUIRE(cuts[i] >= edge.back() && cuts[i] <= n, "cuts must ascend within [0, n]");
+        edge.push_back(cuts[i]);
+    }
+    edge.push_back(n);
+    const int npush = ncuts + 1;
+    int64_t longest = 0;
+    for (int i = 0; i < npush; ++i) longest = std::max(longest, edge[i + 1] - edge[i]);
+    AudioScratch r(device, x, sizeof(double) * (size_t)n);
+    DeviceBuffer out;   // every push is enqueued before the host waits once: the pushes' samples back to back
+    out.reserve(sizeof(double) * (size_t)std::max<int64_t>(n, 1), r.s);
+    StreamLimiter lim;
+    lim.begin(sample_rate, n, longest, spec, r.s);
+    int64_t at = 0;
+    for (int i = 0; i < npush; ++i) {
+        const int64_t len = edge[i + 1] - edge[i];
+        if (len) HIP_CHECK(hipMemcpyAsync(lim.dst(), r.x.as<double>() + edge[i], sizeof(double) * (size_t)len, hipMemcpyDeviceToDevice, r.s));
+        out_per_push[i] = lim.push(len, i + 1 == npush, out.as<double>() + at, r.s);
+        at += out_per_push[i];
+    }
+    SBV2_REQUIRE(at == n, "internal: the fed limiter emitted " + std::to_string(at) + " of " + std::to_string(n) + " samples");
+    if (n) HIP_CHECK(hipMemcpyAsync(out_x, out.get(), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    lim.stats(stats);
+    API_END
+}
+
 int sbv2_debug_bucket_table(int64_t max_s, int64_t buckets, int64_t max_rel, int32_t* out) {
     API_BEGIN
     SBV2_REQUIRE(max_s >= 1 && out, "bad arguments");

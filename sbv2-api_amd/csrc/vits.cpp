@@ -933,12 +933,14 @@ void VitsModel::ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, 
     c.slot_f0[0] = c.slot_f0[1] = -1;
 }
 
-int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac) {
+int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac, const StreamLevelSpec* level) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(fl_.n == 1 && z_.p, "stream_begin needs a preceding forward of ONE utterance with skip_decoder");
     SBV2_REQUIRE(chunk_frames >= 16 && chunk_frames <= (1 << 20), "chunk_frames must be in [16, 2^20]");
-    sfmt_on_ = sflac_on_ = false;
+    sfmt_on_ = sflac_on_ = slevel_on_ = false;
+    slevel_A_ = 0;
     SBV2_REQUIRE(!flac || (fmt && fmt->encoding == 1), "a FLAC stream needs encoding = 1 (s16): f32 samples have no FLAC form");
+    SBV2_REQUIRE(!level || fmt, "a level stream needs an output format");
     if (fmt) {
         SBV2_REQUIRE(!fmt->normalize, "a formatted stream cannot normalise: the peak of the utterance is not known ahead");
         // the filter of an output sample at a chunk edge reaches ceil(half / L) native samples past the window centre; they must lie in the
@@ -949,6 +951,7 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
                                                  " samples past a chunk edge, the stream halo holds only " + std::to_string((int64_t)exact) + " exact samples");
         sfmt_ = *fmt;
         if (!sfmtr_) sfmtr_ = std::make_shared<PcmFormatter>();
+        if (level) slevel_A_ = stream_level_lookahead(fmt->rate);   // (sizes the slots below: a replay may hand back A samples more than it fed)
     }
     constexpr int burst = kStreamBurst;   // (1 / 2 / 4 / 8 / 12 / 16 windows per replay measured in round 3: 2.62 / 1.88 / 1.64 / 1.41 / 1.39 / 1.47 ms per chunk)
     const int64_t Tf = fl_.len[0];
@@ -989,6 +992,11 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
             sflac_on_ = true;
         } else {
             sfmtr_->out_buffer(dev, stream_);
+        }
+        if (level) {   // the formatter's y goes behind the limiter's carried tail, what the limiter emits to one of the two sinks above
+            if (!slim_) slim_ = std::make_shared<StreamLimiter>();
+            slim_->begin(sfmt_.rate, pcm_format_out_len(sfmt_, Tf * cfg_.hop()), (int64_t)(dev / sfmt_.bytes()), *level, stream_);
+            slevel_on_ = true;
         }
         sfmt_on_ = true;
     }
@@ -1038,7 +1046,40 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
             c.fmt_n[slot].push_back(j1 - j0);
             total += j1 - j0;
         }
-        if (sflac_on_) {
+        if (slevel_on_) {
+            // ONE level push per replay: y (f64) behind the limiter's carried tail, then the samples the push completes through the cast /
+            // quantiser.  With S samples fed up to a window's end the stream has emitted max(0, S - A), the utterance's last window
+            // everything: window w is handed the samples between its predecessor's count and its own.
+            const bool last = f0 + (int64_t)c.nwin * c.chunk >= Tf;
+            const int64_t fed0 = sig.empty() ? 0 : sig[0].j0, e0 = slim_->emitted_after(fed0, false);
+            SBV2_REQUIRE(fed0 == slim_->fed(), "internal: a level replay out of stream order (" + std::to_string(fed0) + " samples before it, " +
+                                                   std::to_string(slim_->fed()) + " fed)");
+            sfmtr_->run(sfmt_, pieces, sig, total, nullptr, (&c == burst_.get() ? 2 : 0) + slot, stream_, GainStage(slim_->dst()));
+            const int64_t em = slim_->push(total, last, slim_->out_buffer(), stream_);
+            c.lvl_taken[slot] = c.fmt_n[slot];
+            int64_t at = e0;
+            for (size_t w = 0; w < sig.size(); ++w) {
+                const int64_t upto = slim_->emitted_after(sig[w].j1, last && w + 1 == sig.size());
+                c.fmt_off[slot][w] = at - e0;
+                c.fmt_n[slot][w] = upto - at;
+                at = upto;
+            }
+            SBV2_REQUIRE(at - e0 == em, "internal: the level stream's counts disagree");
+            total = em;
+            void* dev = sflac_on_ ? static_cast<void*>(sflac_->dst()) : sfmtr_->out_buffer(stream_fmt_bytes(c), stream_);
+            pcm_cast(slim_->out_buffer(), em, slim_->unit(), sfmt_.encoding, dev, stream_);
+            if (sflac_on_) {
+                const int64_t t0 = sflac_->tail();
+                c.flac_push[slot] = sflac_->push(em, last, c.host[slot], stream_);
+                c.flac_fr[slot].assign(1, 0);
+                for (size_t w = 0; w < c.fmt_n[slot].size(); ++w) {
+                    const int64_t upto = t0 + c.fmt_off[slot][w] + c.fmt_n[slot][w];
+                    c.flac_fr[slot].push_back(w + 1 == c.fmt_n[slot].size() ? c.flac_push[slot].frames : (int)(upto / kFlacBlock));
+                }
+            } else if (em) {
+                HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)em * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
+            }
+        } else if (sflac_on_) {
             // ONE push per replay: the formatter writes behind the carried tail, the encoder packs every block that completes (with the
             // utterance's last chunk also the short final frame).  Window w completes frames [flac_fr[w], flac_fr[w + 1]) of the push.
             const int64_t t0 = sflac_->tail();
@@ -1074,7 +1115,7 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
 }
 
 int64_t VitsModel::stream_fmt_samples(const ChunkPlan& c) const {
-    return (int64_t)c.nwin * (pcm_format_out_len(sfmt_, (int64_t)c.chunk * cfg_.hop()) + 1);
+    return (int64_t)c.nwin * (pcm_format_out_len(sfmt_, (int64_t)c.chunk * cfg_.hop()) + 1) + slevel_A_;
 }
 size_t VitsModel::stream_fmt_bytes(const ChunkPlan& c) const { return (size_t)stream_fmt_samples(c) * sfmt_.bytes(); }
 
@@ -1085,16 +1126,32 @@ int64_t VitsModel::stream_chunk(int64_t f0, float* dst_host, int64_t capacity) {
 
 int64_t VitsModel::stream_chunk_format(int64_t f0, void* dst_host, int64_t capacity_bytes) {
     SBV2_REQUIRE(sfmt_on_, "this stream has no output format: take its chunks with sbv2_stream_next");
+    SBV2_REQUIRE(!slevel_on_, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
     SBV2_REQUIRE(!sflac_on_, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
     return stream_take(f0, dst_host, capacity_bytes, true, nullptr);
 }
 
 int64_t VitsModel::stream_chunk_flac(int64_t f0, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes) {
+    SBV2_REQUIRE(!slevel_on_, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
     SBV2_REQUIRE(sflac_on_, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
     return stream_take(f0, dst_host, capacity_bytes, true, n_bytes);
 }
 
-int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes) {
+int64_t VitsModel::stream_chunk_level(int64_t f0, void* dst_host, int64_t capacity_bytes, int64_t* n_out) {
+    SBV2_REQUIRE(slevel_on_, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
+    int64_t taken = 0, bytes = 0;
+    const int64_t n = stream_take(f0, dst_host, capacity_bytes, true, sflac_on_ ? &bytes : nullptr, &taken);
+    *n_out = sflac_on_ ? bytes : n;
+    return taken;
+}
+
+void VitsModel::stream_level_stats(double* out) const {
+    SBV2_REQUIRE(slevel_on_ && slim_, "this stream was not begun with a level");
+    HIP_CHECK(hipStreamSynchronize(stream_));
+    slim_->stats(out);
+}
+
+int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes, int64_t* taken) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(chunk_ && z_.p && fl_.n == 1, "stream_chunk without stream_begin");
     ChunkPlan& c1 = *chunk_;
@@ -1125,10 +1182,12 @@ int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bo
             if (head) sflac_->header(o);
             if (nb) std::memcpy(o + head, p.bytes + p.pre[fa], (size_t)nb);
             *flac_bytes = head + nb;
+            if (taken) *taken = c.lvl_taken[slot][w];
             return n;
         }
         SBV2_REQUIRE(capacity_bytes >= n * esz, "PCM buffer too small for the chunk: " + std::to_string(capacity_bytes) + " < " + std::to_string(n * esz) + " bytes");
-        std::memcpy(dst_host, reinterpret_cast<const char*>(c.host[slot]) + (size_t)c.fmt_off[slot][w] * esz, (size_t)(n * esz));
+        if (n) std::memcpy(dst_host, reinterpret_cast<const char*>(c.host[slot]) + (size_t)c.fmt_off[slot][w] * esz, (size_t)(n * esz));
+        if (taken) *taken = c.lvl_taken[slot][w];
         return n;
     };
     const int64_t ci = f0 / c1.chunk;
@@ -1136,6 +1195,7 @@ int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bo
     if (ci == 0 || !bursts) {
         // the single-window plan: the utterance's first chunk (and everything when bursts are off); the next chunk runs while this one is delivered
         const int slot = (int)(ci & 1);
+        SBV2_REQUIRE(!slevel_on_ || c1.slot_f0[slot] == f0, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
         SBV2_REQUIRE(!flac_bytes || c1.slot_f0[slot] == f0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
         if (c1.slot_f0[slot] != f0) stream_enqueue(c1, f0, slot);                                  // (random access: not the streaming order)
         if (!bursts && f0 + c1.chunk < Tf && c1.slot_f0[slot ^ 1] != f0 + c1.chunk) stream_enqueue(c1, f0 + c1.chunk, slot ^ 1);
@@ -1148,6 +1208,7 @@ int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bo
     const int64_t bi = (ci - 1) / cb.nwin, within = (ci - 1) % cb.nwin;
     const int64_t bf0 = (1 + bi * cb.nwin) * c1.chunk;      // first frame of this chunk's burst
     const int slot = (int)(bi & 1);
+    SBV2_REQUIRE(!slevel_on_ || cb.slot_f0[slot] == bf0, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
     SBV2_REQUIRE(!flac_bytes || cb.slot_f0[slot] == bf0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
     if (cb.slot_f0[slot] != bf0) stream_enqueue(cb, bf0, slot);                                    // (random access)
     // the following burst is decoded while this one is delivered (its slot was drained one burst ago)

@@ -279,6 +279,66 @@ def debug_limiter(signals, sample_rate: int, limiter: Limiter, device: int = 0):
     return np.split(out[:x.size], np.cumsum(lens)[:-1]), stats
 
 
+class StreamLevel:
+    """Level control of a stream (struct sbv2_stream_level): a fixed gain of gain_db in [-40, 40] and the look-ahead gain curve of Limiter at
+    that gain, which holds every sample at or below true_peak_max dBTP in [-20, 0].  No loudness target and no depth bound: the gain is the
+    caller's (for a consistent level, target - L from the loudness stats of the voice), the depth is reported by StreamHandle.level_stats."""
+
+    def __init__(self, gain_db: float, true_peak_max: float = -1.0):
+        self.gain_db, self.true_peak_max = float(gain_db), float(true_peak_max)
+        if not (np.isfinite(self.gain_db) and -40.0 <= self.gain_db <= 40.0):
+            raise Sbv2Error(f"stream gain {gain_db} dB is outside [-40, 40]")
+        if not (np.isfinite(self.true_peak_max) and -20.0 <= self.true_peak_max <= 0.0):
+            raise Sbv2Error(f"true-peak ceiling {true_peak_max} dBTP is outside [-20, 0]")
+        self.c = _lib.Sbv2StreamLevel(self.gain_db, self.true_peak_max, (C.c_double * 2)(0.0, 0.0))
+
+    def __repr__(self):
+        return f"StreamLevel({self.gain_db}, true_peak_max={self.true_peak_max})"
+
+
+def stream_level_lookahead(fmt: PcmFormat) -> int:
+    """A: the delivered samples a level stream runs behind, sample_rate // 100 + 11 (host only)."""
+    n = _lib.lib().sbv2_stream_level_lookahead(C.byref(fmt.c))
+    if n < 0:
+        raise Sbv2Error(_lib.lib().sbv2_last_error().decode(errors="replace"))
+    return n
+
+
+def stream_level_bound(fmt: PcmFormat, n_native: int, flac: bool = False) -> int:
+    """Bytes that always suffice for one call of a level stream whose chunks hold n_native 44.1 kHz samples (host only)."""
+    n = _lib.lib().sbv2_stream_level_bound(C.byref(fmt.c), int(n_native), int(bool(flac)))
+    if n < 0:
+        raise Sbv2Error(_lib.lib().sbv2_last_error().decode(errors="replace"))
+    return n
+
+
+def debug_limiter_fixed(signals, sample_rate: int, level: StreamLevel, device: int = 0):
+    """Test hook: the limiter's gain curve at the fixed gain of `level`, in one shot, on host float64 signals -> (the limited float64
+    signals, stats [n, 2]: deepest reduction dB, max |x|)."""
+    sigs = [np.ascontiguousarray(np.asarray(x, np.float64)).reshape(-1) for x in signals]
+    x = np.concatenate(sigs) if sigs else np.zeros(0, np.float64)
+    lens = np.array([s.size for s in sigs], np.int64)
+    out = np.zeros(max(x.size, 1), np.float64)
+    stats = np.zeros((len(sigs), 2), np.float64)
+    check(_lib.lib().sbv2_debug_limiter_fixed(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(sigs),
+                                              int(sample_rate), C.byref(level.c), out.ctypes.data_as(C.c_void_p), _f64p(stats)))
+    return np.split(out[:x.size], np.cumsum(lens)[:-1]), stats
+
+
+def debug_limiter_stream(x, cuts, sample_rate: int, level: StreamLevel, device: int = 0):
+    """Test hook: the same limiter fed piece by piece.  The host float64 signal x is cut at the ascending sample positions `cuts` into
+    len(cuts) + 1 pushes (empty ones allowed) -> (the samples each push emitted, in order; stats [2])."""
+    x = np.ascontiguousarray(np.asarray(x, np.float64)).reshape(-1)
+    cuts = np.ascontiguousarray(np.asarray(cuts, np.int64)).reshape(-1)
+    out = np.zeros(max(x.size, 1), np.float64)
+    got = np.zeros(cuts.size + 1, np.int64)
+    stats = np.zeros(2, np.float64)
+    check(_lib.lib().sbv2_debug_limiter_stream(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, x.size,
+                                               cuts.ctypes.data_as(i64p) if cuts.size else None, cuts.size, int(sample_rate), C.byref(level.c),
+                                               out.ctypes.data_as(C.c_void_p), got.ctypes.data_as(i64p), _f64p(stats)))
+    return np.split(out[:x.size], np.cumsum(got)[:-1]), stats
+
+
 class Marks:
     """Speech marks of one fetched signal (struct sbv2_marks): per token of the listed rows, in row then token order, the delivered-sample span
     [start, end) and, when levels were asked for, sumsq / peak of the delivered samples in it (s16 as integers; None otherwise); env_sumsq /
@@ -593,21 +653,31 @@ class StreamHandle:
     """fmt (PcmFormat, optional): the chunks leave the device in that format (normalize is refused: a stream cannot know the peak ahead);
     total_samples is then counted at fmt.sample_rate.  flac=True (fmt must be s16): the chunks' samples are encoded on the device as ONE FLAC
     stream; next() returns the bytes of the frames the chunk completed (b"" when it completed none: FLAC frames hold 4096 samples), the
-    42-byte stream header in front of the first ones; samples_taken counts the s16 samples consumed so far."""
+    42-byte stream header in front of the first ones; samples_taken counts the s16 samples consumed so far.
+    level (StreamLevel; needs fmt, f32 or s16, with or without flac): the samples pass a fixed gain and the look-ahead limiter on the device,
+    carried from chunk to chunk.  Delivery runs stream_level_lookahead(fmt) samples behind the chunks: next() returns what the chunk
+    completed (possibly an empty array or b""), the last chunk everything; samples_taken counts the chunks' samples; level_stats() after
+    the end."""
 
-    def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False, **kw):
+    def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
+                 level: "StreamLevel | None" = None, **kw):
         l = _lib.lib()
         self.b = Pipeline.prepare(None, [utt], **kw)
         self.h = C.c_void_p()
-        self.fmt, self.flac, self.samples_taken = fmt, bool(flac), 0
+        self.fmt, self.flac, self.level, self.samples_taken = fmt, bool(flac), level, 0
         if flac and fmt is None:
             raise Sbv2Error("a FLAC stream needs a format: fmt=PcmFormat(rate, \"s16\")")
+        if level is not None and fmt is None:
+            raise Sbv2Error("a level stream needs a format: fmt=PcmFormat(rate, \"f32\" or \"s16\")")
         tot = C.c_int64()
         args = (bert.handle, vits.handle, C.byref(self.b.c), self.b.ids.ctypes.data_as(i64p), self.b.s_lens.ctypes.data_as(i64p),
                 self.b.w2p.ctypes.data_as(i64p), chunk_frames)
         if fmt is None:
             check(l.sbv2_stream_begin(*args, C.byref(self.h), C.byref(tot)))
             self.buf = np.empty(chunk_frames * l.sbv2_vits_hop(vits.handle), np.float32)
+        elif level is not None:
+            check(l.sbv2_stream_begin_level(*args, C.byref(fmt.c), C.byref(level.c), int(self.flac), C.byref(self.h), C.byref(tot)))
+            self.buf = np.empty(stream_level_bound(fmt, chunk_frames * l.sbv2_vits_hop(vits.handle), self.flac), np.uint8)
         elif flac:
             check(l.sbv2_stream_begin_flac(*args, C.byref(fmt.c), C.byref(self.h), C.byref(tot)))
             self.buf = np.empty(flac_stream_bound(fmt, chunk_frames * l.sbv2_vits_hop(vits.handle)), np.uint8)
@@ -620,6 +690,13 @@ class StreamHandle:
 
     def next(self):
         n = C.c_int64()
+        if self.level is not None:
+            out = C.c_int64()
+            check(_lib.lib().sbv2_stream_next_level(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.nbytes, C.byref(out), C.byref(n)))
+            self.samples_taken += n.value
+            if n.value == 0:
+                return None
+            return self.buf[:out.value].tobytes() if self.flac else self.buf[:out.value * np.dtype(self.fmt.dtype).itemsize].view(self.fmt.dtype).copy()
         if self.flac:
             nb = C.c_int64()
             check(_lib.lib().sbv2_stream_next_flac(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.nbytes, C.byref(nb), C.byref(n)))
@@ -630,6 +707,12 @@ class StreamHandle:
         else:
             check(_lib.lib().sbv2_stream_next_format(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.nbytes, C.byref(n)))
         return None if n.value == 0 else self.buf[:n.value].copy()
+
+    def level_stats(self):
+        """(deepest reduction in dB, max |x|) of a level stream, once next() has returned None or the last chunk (sbv2_stream_level_stats)."""
+        st = np.zeros(2, np.float64)
+        check(_lib.lib().sbv2_stream_level_stats(self.h, _f64p(st)))
+        return float(st[0]), float(st[1])
 
     def marks(self):
         """(start, end): the spans of the utterance's tokens in delivered samples of this stream (sbv2_stream_marks; host only, complete from

@@ -39,10 +39,13 @@ class SynthesizeOptions:
     puts -16 and -14 LUFS out of reach under -1 dBTP).  limiter=True (new) reaches such targets with a look-ahead true-peak limiter that
     takes peaks down by at most max_reduction dB (model.Limiter); it needs a loudness target.
     envelope_hz (new; read by easy_synthesize_marks only): the speech marks carry a level envelope of sample_rate // envelope_hz delivered
-    samples per frame."""
+    samples per frame.
+    gain_db (new; read by easy_synthesize_stream only, refused everywhere else): a fixed gain in dB on a stream, with the limiter's gain curve
+    holding the samples under true_peak_max (model.StreamLevel).  A stream cannot measure its loudness; the caller names the gain, for
+    example target - L from the loudness stats of an earlier answer of the same voice."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
-                 normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None):
+                 normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None):
         if loudness is not None and normalize:
             raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
         if limiter and loudness is None:
@@ -52,6 +55,7 @@ class SynthesizeOptions:
         self.sample_rate, self.encoding, self.normalize = sample_rate, encoding, normalize
         self.loudness, self.true_peak_max = loudness, true_peak_max
         self.envelope_hz = envelope_hz
+        self.gain_db = gain_db
 
 
 def load_style(data: bytes) -> np.ndarray:
@@ -123,6 +127,8 @@ class RequestPlan:
 
     def __init__(self, sentences, style_vectors, style_id, speaker_id, options):
         options = options or SynthesizeOptions()
+        if options.gain_db is not None:
+            raise model.Sbv2Error("gain_db is the level control of a stream (/synthesize_stream): a whole signal is measured, set loudness (LUFS) instead")
         if options.loudness is not None and options.normalize:
             raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
         self.limited = bool(options.limiter)
@@ -280,6 +286,7 @@ class SynthesisStream:
     def __init__(self, st, head, to_bytes, marks=None):
         self._st, self._head, self._to_bytes = st, head, to_bytes
         self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece (streams carry no levels)
+        self.level_stats = None   # a level stream's (deepest reduction in dB, max |x|), once its last piece has been handed out
 
     def __iter__(self):
         return self
@@ -292,6 +299,8 @@ class SynthesisStream:
             while self._st is not None:
                 c = self._st.next()
                 if c is None:
+                    if getattr(self._st, "level", None) is not None:
+                        self.level_stats = self._st.level_stats()
                     break
                 if len(c):
                     return self._to_bytes(c)
@@ -329,6 +338,9 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     is refused).  encoding "flac": the pieces of one FLAC stream encoded on the device, as its frames complete (chunks that complete none
     yield nothing); "s16" / "f32": the WAV header of pcm16_wav / float_wav written with the known total length, then the chunks' samples.
     normalize, loudness and limiter are refused: they need the whole signal before the first sample can leave.
+    options.gain_db: the level stream (model.StreamLevel(gain_db, true_peak_max)) for "f32", "s16" and "flac" alike: a fixed gain, no sample above
+    the ceiling; the pieces run stream_level_lookahead samples behind the decoder, the total length is unchanged, and after the last piece
+    the iterator's `.level_stats` holds (deepest reduction in dB, max |x|).
     Everything up to the first replay (options, DeBERTa, flow, the header) runs before the iterator is returned.
     The iterator's `.marks` holds the utterance's token and word timing (token_marks: every duration is known before the first replay)."""
     options = options or SynthesizeOptions()
@@ -347,7 +359,10 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     flac = options.encoding == "flac"
     fmt = model.PcmFormat(options.sample_rate, "s16" if flac else options.encoding, False)
     model.pcm_format_length(fmt, 0)   # a bad rate is refused before any GPU work
-    st = model.StreamHandle(bert, vits, dict(live[0], style=style, sid=speaker_id), chunk_frames, fmt=None if fmt.is_default else fmt, flac=flac,
+    # (with a level the default format is an explicit one: the level stream always formats)
+    level = model.StreamLevel(options.gain_db, options.true_peak_max) if options.gain_db is not None else None
+    st = model.StreamHandle(bert, vits, dict(live[0], style=style, sid=speaker_id), chunk_frames,
+                            fmt=None if fmt.is_default and level is None else fmt, flac=flac, level=level,
                             sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
                             noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     try:

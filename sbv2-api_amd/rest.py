@@ -12,7 +12,9 @@ and error mapping, so that a client of the reference's server cannot tell the di
   POST /synthesize_stream  new: the same request, answered while it is synthesised (chunked transfer): the text as ONE utterance (joined, as
                     split_sentences = false does), encoding "flac" -> audio/flac, one FLAC stream encoded on the device chunk by chunk;
                     "s16" / "f32" -> audio/wav, the header written with the known length, then the chunks.  normalize / loudness / limiter
-                    are refused (they need the whole signal).  Errors before the first byte map as below; the lock is held until the last byte
+                    are refused (they need the whole signal).  gain_db = null (new): a fixed gain in dB with the limiter's look-ahead gain
+                    curve holding every sample under true_peak_max, carried from chunk to chunk on the device; same length, same header;
+                    the other routes refuse it.  Errors before the first byte map as below; the lock is held until the last byte
                     has left or the client has gone, whichever comes first (_HeldPieces, _ClosingStream).
                     marks = true (new, default false): the response carries the header X-Speech-Marks, compact JSON {"sample_rate", "tokens":
                     [[line, index, phone, start, end], ...], "words": [[line, index, start, end], ...]} in delivered samples: the timing of the
@@ -104,6 +106,7 @@ def make_app(holder, batching=None):
         true_peak_max: float = -1.0         # true-peak ceiling (dBTP) of the loudness gain
         limiter: bool = False               # look-ahead true-peak limiter for targets the plain gain misses; needs loudness
         max_reduction: float = 6.0          # the limiter's deepest gain reduction (dB)
+        gain_db: Optional[float] = None     # /synthesize_stream only: fixed gain (dB) under the true_peak_max ceiling; refused elsewhere
 
     class SynthesizeMarksRequest(SynthesizeRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
@@ -145,7 +148,7 @@ def make_app(holder, batching=None):
         return orchestrator.SynthesizeOptions(sdp_ratio=req.sdp_ratio, length_scale=req.length_scale, sample_rate=req.sample_rate,
                                               encoding=req.encoding, normalize=req.normalize, loudness=req.loudness,
                                               true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction,
-                                              envelope_hz=getattr(req, "envelope_hz", None))
+                                              envelope_hz=getattr(req, "envelope_hz", None), gain_db=req.gain_db)
 
     def synthesize(req: SynthesizeRequest):
         try:
