@@ -152,15 +152,44 @@ void sbv2_host_free(void* p);
  * (rational polyphase, L / M = rate / 44100 in lowest terms), optionally peak-normalised per output signal and quantised to 16 bits ON THE DEVICE,
  * before it crosses PCIe.  Convention: y[j] = sum_k h[j M - k L + half] x[k], j < ceil(N L / M), x = 0 outside [0, N); h = a Kaiser-windowed sinc
  * (cutoff 0.45 min(44100, rate), beta 8.6, half = 32 max(L, M)), every polyphase branch summing to 1; i.e. scipy.signal.resample_poly(x, L, M,
- * window = h / L).  s16 = clamp(rint(y g 32767), -32767, 32767), little-endian; g = 1 / max|y| of the signal when normalising (1 for silence). */
+ * window = h / L).  s16 = clamp(rint(y g 32767), -32767, 32767), little-endian; g = 1 / max|y| of the signal when normalising (1 for silence).
+ *
+ * G.711 (telephony: PCMU / PCMA), encoded ON THE DEVICE.  encoding 7 = mu-law, 6 = A-law: the WAVE format tags of the two laws, so the number
+ * a caller writes into a WAV header is the number it passes here (2, 3, 4 and 5 stay refused).  Each delivered sample is ONE byte: the G.711
+ * code of q, the s16 integer that encoding 1 delivers for the same sample (q = clamp(rint(v 32767), -32767, 32767) after the gain stage).  A
+ * mu-law or A-law fetch is therefore byte for byte enc(the s16 fetch) with the same format fields; capacities and out_lens are in samples,
+ * and samples equal bytes.  With >> an arithmetic shift and lg = floor(log2):
+ *   mu-law encode:  s = q < 0;  m = min(|q|, 32635) + 132;  e = lg(m) - 7 (0..7);  mant = (m >> (e + 3)) & 15;
+ *                   code = ~(s * 0x80 | e << 4 | mant) & 0xFF
+ *   mu-law decode:  u = ~code & 0xFF;  t = (((u & 15) << 3) + 132) << ((u >> 4) & 7);  value = u & 0x80 ? 132 - t : t - 132
+ *   A-law encode:   p = q >= 0;  m = (p ? q : -q - 1) >> 3;  e = m < 32 ? 0 : lg(m) - 4;  mant = e == 0 ? (m >> 1) & 15 : (m >> e) & 15;
+ *                   code = (p * 0x80 | e << 4 | mant) ^ 0x55
+ *   A-law decode:   a = code ^ 0x55;  e = (a >> 4) & 7;  t = ((a & 15) << 4) + 8;  if e >= 1: t = (t + 256) << (e - 1);
+ *                   value = a & 0x80 ? t : -t
+ * The decoders are the tables of ITU-T G.711 scaled to 16 bits; the mu-law encoder is the common 16-bit form (bias 132, clip 32635), the
+ * A-law encoder the common 13-bit form on q >> 3.  Anchors: mu-law enc(0) = 0xFF, enc(-1) = 0x7F ("minus zero": decodes to 0, re-encodes to
+ * 0xFF, the one code of 256 that does not round-trip), enc(32767) = 0x80, enc(-32767) = 0x00, decoded range +-32124; A-law enc(0) = 0xD5,
+ * enc(-1) = 0x55, enc(32767) = 0xAA, enc(-32767) = 0x2A, decoded range +-32256, every code round-trips.  dec(enc(q)) is non-decreasing in q
+ * and |dec(enc(q)) - q| is at most half the segment's step (mu-law 1 << (e + 3), A-law 16 for e = 0, else 8 << e).  Saturation: mu-law
+ * clips |q| above 32635 (-0.035 dBFS) to its top level 32124 (an error of at most 643, never a wrap); A-law's top level 32256 stands for
+ * every q >= 31744 or q <= -31745.  normalize, the loudness gain and the limiter come before the quantiser and compose unchanged: their
+ * stats are those of the s16 fetch bit for bit.  FLAC takes s16 only: 7 / 6 are refused by everything FLAC. */
 typedef struct sbv2_pcm_format {
     int32_t sample_rate;   /* 8000 16000 22050 24000 32000 44100 48000; anything else is refused */
-    int32_t encoding;      /* 0 = f32, 1 = s16 little-endian */
+    int32_t encoding;      /* 0 = f32, 1 = s16 little-endian, 7 = G.711 mu-law, 6 = G.711 A-law (one byte per sample) */
     int32_t normalize;     /* 0 = none, 1 = peak of each output signal -> full scale */
     int32_t reserved;      /* must be 0 */
 } sbv2_pcm_format;
 /* Host only: samples of a signal of n_native samples at 44.1 kHz in that format, ceil(n L / M); -1 (message in sbv2_last_error) when fmt is bad. */
 int64_t sbv2_pcm_format_length(const sbv2_pcm_format* fmt, int64_t n_native);
+/* Host only: the G.711 laws above on n s16 integers (-32768 is taken as -32767) / n codes; encoding 7 = mu-law, 6 = A-law, anything else is
+ * refused with a message.  What a client needs to play, mix or check the delivered bytes. */
+int sbv2_g711_encode(int32_t encoding, const int16_t* q, int64_t n, uint8_t* codes);
+int sbv2_g711_decode(int32_t encoding, const uint8_t* codes, int64_t n, int16_t* q);
+/* Test hook: the gain-stage kernel of the output chain on host f64 signals (nsig >= 1 signals of lens[i] samples, back to back in x), signal i
+ * times gains[i], delivered in `encoding` (0, 1, 7, 6) -> dst (host; sum of lens samples, back to back as well: a G.711 signal starts at any
+ * byte offset).  The device output lies between guard bands; a byte written outside it fails the call. */
+int sbv2_debug_pcm_cast(int device, const double* x, const int64_t* lens, int nsig, const double* gains, int32_t encoding, void* dst);
 /* Host-only test hook: the prototype h of a rate (*len = 2 half + 1 taps at 44100 L Hz) and L, M.  h may be NULL (query); else cap >= *len. */
 int sbv2_pcm_format_taps(int32_t sample_rate, float* h, int64_t cap, int64_t* len, int32_t* L, int32_t* M);
 /* Formats run `ticket` on its context's stream (waits for it) and copies the result into HOST memory dst (capacity_bytes; a longer result is refused
@@ -178,7 +207,7 @@ int sbv2_pipeline_fetch_pcm_format(sbv2_pipeline* p, int64_t ticket, const sbv2_
  * Rice partition orders <= 8; streamable subset.  The bytes are a pure function of the samples: two fetches of one ticket are identical. */
 /* Host only: an upper bound on the bytes of one signal's stream, n = sbv2_pcm_format_length(fmt, n_native) samples in frames of 4096:
  * 42 + 16 ceil(n / 4096) + 2 n (per frame the largest header, a VERBATIM subframe and the CRC-16).  -1 (message in sbv2_last_error) when
- * fmt is bad or its encoding is not 1 (s16). */
+ * fmt is bad or its encoding is not 1 (s16; G.711 codes have no FLAC form either). */
 int64_t sbv2_flac_bound(const sbv2_pcm_format* fmt, int64_t n_native);
 /* The signals of sbv2_pipeline_fetch_pcm_format (same place / joined_len rules; fmt->encoding must be 1 = s16, fmt->normalize as there),
  * each encoded as one FLAC stream; the streams are written back to back into HOST memory dst, out_bytes[i] = stream i's size (one entry
@@ -286,7 +315,7 @@ typedef struct sbv2_fetch_request {
     const sbv2_pcm_format* fmt;
     const sbv2_loudness* loudness;   /* at most one of loudness / limiter non-NULL */
     const sbv2_limiter* limiter;
-    int32_t flac;                /* 0 = PCM bytes in fmt's encoding, 1 = one FLAC stream (fmt->encoding must be 1) */
+    int32_t flac;                /* 0 = PCM bytes (or G.711 codes) in fmt's encoding, 1 = one FLAC stream (fmt->encoding must be 1) */
 } sbv2_fetch_request;
 int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
                                 int64_t* out_count, double* stats);
@@ -305,6 +334,8 @@ int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fet
  *   quantiser: exactly what crosses PCIe or enters the FLAC encoder.  For s16 sumsq is exact (integers below 2^53); for f32 every square is
  *   exact in f64 and only the order of the sum is the library's (within len 2^-52 relative of any other order).  The order is fixed: two
  *   fetches of one ticket give identical bits.  dBFS = 10 log10(sumsq / n) (s16: divided by 32767^2) is the caller's arithmetic.
+ *   G.711 (encoding 7 / 6): v[j] is the integer the delivered byte decodes to (the decode rules of sbv2_pcm_format), so sumsq and peak are
+ *   exact as for s16 and full scale stays 32767.
  * Envelope (optional, env_hop > 0 delivered samples): frame f = [f env_hop, min((f + 1) env_hop, out_len)), n_env = ceil(out_len / env_hop)
  *   frames, each with the same sumsq and peak; out_len = the delivered samples of the signal.
  * The levels are ONE segmented reduction over the samples in HBM (marks.hip), enqueued before the fetch's only synchronisation; timing alone
@@ -328,7 +359,7 @@ int sbv2_pipeline_fetch_request_marks(sbv2_pipeline* p, int64_t ticket, const sb
  * of one row at `place`, at fmt's rate (its encoding and normalize do not matter).  Refused: a bad fmt, a negative duration or place, hop < 1. */
 int sbv2_marks_spans(const int64_t* durations, int64_t n_tokens, int32_t hop, int64_t place, const sbv2_pcm_format* fmt, int64_t* start,
                      int64_t* end);
-/* Test hook: the level reduction on host samples x[n] (encoding 0 = f32, 1 = s16) over the segments [starts[i], ends[i]) within [0, n]. */
+/* Test hook: the level reduction on host samples x[n] (encoding 0 = f32, 1 = s16, 7 / 6 = G.711 codes, one byte each) over the segments [starts[i], ends[i]) within [0, n]. */
 int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n, const int64_t* starts, const int64_t* ends, int64_t nseg,
                               double* sumsq, double* peak);
 
@@ -448,15 +479,19 @@ typedef struct sbv2_stream_level {
     double true_peak_max_dbtp;   /* [-20, 0];  c = 10^(ceiling / 20) */
     double reserved[2];          /* must be 0 */
 } sbv2_stream_level;
-/* Host only: A at fmt->sample_rate; -1 for a bad fmt. */
+/* Host only: A at fmt->sample_rate; -1 for a bad fmt.  A depends on the rate alone and this query takes encodings 0 and 1 only, as it
+ * always did: for a G.711 level stream ask with either at the same rate. */
 int64_t sbv2_stream_level_lookahead(const sbv2_pcm_format* fmt);
 /* Host only: bytes that always suffice for one sbv2_stream_next_level call of a stream with chunks of chunk_native_samples (chunk_frames * hop):
  * n = sbv2_pcm_format_length of the chunk + A samples, as n * bytes per sample, or with flac != 0 (fmt s16) the bound of sbv2_flac_stream_bound
  * for a push of n samples.  -1 for a bad fmt. */
 int64_t sbv2_stream_level_bound(const sbv2_pcm_format* fmt, int64_t chunk_native_samples, int flac);
-/* Inputs as sbv2_stream_begin_format; fmt must not be NULL, fmt->normalize must be 0, f32 or s16; flac != 0 needs s16 and encodes the delivered
+/* Inputs as sbv2_stream_begin_format; fmt must not be NULL, fmt->normalize must be 0, any encoding; flac != 0 needs s16 and encodes the delivered
  * s16 samples as ONE FLAC stream, as sbv2_stream_begin_flac does.  A NULL level, out-of-range or non-finite fields and non-zero reserved
- * fields are refused.  *total_samples at fmt->sample_rate: the same total as without a level. */
+ * fields are refused.  *total_samples at fmt->sample_rate: the same total as without a level.
+ * G.711 (encoding 7 / 6): the guarantee holds BEFORE the quantiser: no sample of x above the ceiling, and the codes are enc(the s16 level
+ * stream's samples).  The laws then saturate on their own: mu-law above 32635 / 32767 (-0.035 dBFS), A-law at its top level (q >= 31744 or
+ * q <= -31745). */
 int sbv2_stream_begin_level(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
                             const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, const sbv2_stream_level* level, int flac,
                             sbv2_stream** out, int64_t* total_samples);

@@ -358,6 +358,25 @@ int64_t sbv2_pcm_format_length(const sbv2_pcm_format* fmt, int64_t n_native) {
     }
 }
 
+// Host only: the two G.711 laws on s16 integers, the very lines the device quantisers and the level reduction run (pcm_format.h)
+int sbv2_g711_encode(int32_t encoding, const int16_t* q, int64_t n, uint8_t* codes) {
+    API_BEGIN
+    SBV2_REQUIRE(pcm_encoding_g711(encoding), "unsupported G.711 encoding " + std::to_string(encoding) + " (7 = mu-law, 6 = A-law)");
+    SBV2_REQUIRE(n >= 0 && (n == 0 || (q && codes)), "bad arguments");
+    for (int64_t i = 0; i < n; ++i) {
+        const int v = std::max<int>(q[i], -32767);   // (the quantiser never delivers -32768)
+        codes[i] = encoding == kEncMulaw ? mulaw_encode(v) : alaw_encode(v);
+    }
+    API_END
+}
+int sbv2_g711_decode(int32_t encoding, const uint8_t* codes, int64_t n, int16_t* q) {
+    API_BEGIN
+    SBV2_REQUIRE(pcm_encoding_g711(encoding), "unsupported G.711 encoding " + std::to_string(encoding) + " (7 = mu-law, 6 = A-law)");
+    SBV2_REQUIRE(n >= 0 && (n == 0 || (q && codes)), "bad arguments");
+    for (int64_t i = 0; i < n; ++i) q[i] = (int16_t)(encoding == kEncMulaw ? mulaw_decode(codes[i]) : alaw_decode(codes[i]));
+    API_END
+}
+
 int sbv2_pcm_format_taps(int32_t sample_rate, float* h, int64_t cap, int64_t* len, int32_t* L, int32_t* M) {
     API_BEGIN
     SBV2_REQUIRE(len, "bad arguments");
@@ -437,7 +456,7 @@ enum class Sink { kPcm, kFlac };
 static PcmFmtSpec fetch_spec(const sbv2_pcm_format* fmt, bool gain_stage, Sink sink) {
     const PcmFmtSpec spec = pcm_format_spec(fmt);
     if (gain_stage) SBV2_REQUIRE(!spec.normalize, "loudness normalisation replaces peak normalisation: fmt->normalize must be 0");
-    if (sink == Sink::kFlac) SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
+    if (sink == Sink::kFlac) SBV2_REQUIRE(spec.encoding == kEncS16, "FLAC needs encoding = 1 (s16): f32 samples and G.711 codes have no FLAC form");
     return spec;
 }
 

@@ -25,7 +25,7 @@ class Marks {
     // segments longer than this take a whole workgroup (256 lanes) instead of one wave
     static constexpr int64_t kLongSegment = 4096;
     // Enqueues on s: sumsq / peak of x[seg[2 i], seg[2 i + 1]) for i < nseg, x = n delivered samples on the device (encoding 0 = f32,
-    // 1 = s16, taken as integers), and the copy of the results to the host: sumsq_host()[i] / peak_host()[i] hold them once s has been
+    // 1 = s16, taken as integers, 7 / 6 = G.711 codes, taken as the integers they decode to), and the copy of the results to the host: sumsq_host()[i] / peak_host()[i] hold them once s has been
     // synchronised.  Every segment is checked against [0, n] before anything is enqueued (throws); nseg = 0 enqueues nothing.
     void run(const void* x, int encoding, int64_t n, const int64_t* seg, int64_t nseg, hipStream_t s);
     const double* sumsq_host() const { return res_host_; }

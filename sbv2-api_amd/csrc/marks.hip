@@ -9,7 +9,7 @@
 // Offsets are relative to the segment's start, loads are single elements (a wave reads 64 consecutive samples: 256 or 128 contiguous bytes),
 // so an odd start in an s16 buffer needs no peeling and nothing outside [start, end) is ever addressed.  The order of the additions depends
 // on the segment's length alone: no atomics, equal samples give equal bits wherever the segment lies.  s16 samples are squared as integers
-// (exact in f64, as are their sums below 2^53); an f32 sample's square is exact in f64 too, so only the order of the sum is this kernel's own.
+// (exact in f64, as are their sums below 2^53), and so are the integers that G.711 codes decode to (one byte per sample, any start); an f32 sample's square is exact in f64 too, so only the order of the sum is this kernel's own.
 // Each sample is read once per table it appears in (tokens, frames): the launch is bound by its few MB of HBM reads.
 #include "marks.h"
 
@@ -50,6 +50,15 @@ template <class T>
 __device__ inline double level_load(const T* x, int64_t i) {
     return (double)x[i];
 }
+// G.711: the delivered byte is a code; its level is that of the integer it decodes to (pcm_format.h), exact like an s16 sample's
+struct MulawCode {
+    uint8_t c;
+};
+struct AlawCode {
+    uint8_t c;
+};
+__device__ inline double level_load(const MulawCode* x, int64_t i) { return (double)mulaw_decode(x[i].c); }
+__device__ inline double level_load(const AlawCode* x, int64_t i) { return (double)alaw_decode(x[i].c); }
 
 // partial results of the lanes of a wave -> lane 0, in a fixed tree
 __device__ inline void wave_reduce(double& ss, double& pk) {
@@ -113,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void k_segment_levels(const LevelArgs a) {
 }  // namespace
 
 void Marks::run(const void* x, int encoding, int64_t n, const int64_t* seg, int64_t nseg, hipStream_t s) {
-    SBV2_REQUIRE(encoding == 0 || encoding == 1, "internal: levels of an unknown encoding");
+    SBV2_REQUIRE(pcm_encoding_known(encoding), "internal: levels of an unknown encoding");
     SBV2_REQUIRE(nseg >= 0 && nseg < (1 << 30) && n >= 0, "internal: bad segment table");
     nseg_ = nseg;
     if (nseg == 0) return;
@@ -144,7 +153,9 @@ void Marks::run(const void* x, int encoding, int64_t n, const int64_t* seg, int6
     a.sumsq = reinterpret_cast<double*>(d + o_res);
     a.peak = a.sumsq + nseg;
     const dim3 grid((unsigned)(a.short_blocks + (nseg - nshort))), blk(kBlock);
-    if (encoding == 1) hipLaunchKernelGGL(k_segment_levels<int16_t>, grid, blk, 0, s, a);
+    if (encoding == kEncS16) hipLaunchKernelGGL(k_segment_levels<int16_t>, grid, blk, 0, s, a);
+    else if (encoding == kEncMulaw) hipLaunchKernelGGL(k_segment_levels<MulawCode>, grid, blk, 0, s, a);
+    else if (encoding == kEncAlaw) hipLaunchKernelGGL(k_segment_levels<AlawCode>, grid, blk, 0, s, a);
     else hipLaunchKernelGGL(k_segment_levels<float>, grid, blk, 0, s, a);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(res_host_, a.sumsq, 16 * (size_t)nseg, hipMemcpyDeviceToHost, s));

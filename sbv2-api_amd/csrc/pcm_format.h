@@ -1,5 +1,5 @@
 // Output formats of the PCM (pcm_format.hip): rational polyphase resampling from 44.1 kHz, optional peak normalisation and the f32 -> s16
-// quantiser, on the device, next to the PCM a run leaves in HBM.  Used by the formatted fetches (fetch_formatted, api.cpp) and the streaming decoder (vits.cpp).
+// quantiser (with the G.711 mu-law / A-law codes of its integers as two more deliveries), on the device, next to the PCM a run leaves in HBM.  Used by the formatted fetches (fetch_formatted, api.cpp) and the streaming decoder (vits.cpp).
 #pragma once
 #include "common.h"
 
@@ -9,12 +9,48 @@ namespace sbv2 {
 
 constexpr int kNativeRate = 44100;
 
+// sbv2_pcm_format.encoding: f32, s16 and the two G.711 laws under their WAVE format tags (one byte per sample)
+constexpr int kEncF32 = 0, kEncS16 = 1, kEncAlaw = 6, kEncMulaw = 7;
+inline bool pcm_encoding_known(int e) { return e == kEncF32 || e == kEncS16 || e == kEncAlaw || e == kEncMulaw; }
+inline bool pcm_encoding_g711(int e) { return e == kEncAlaw || e == kEncMulaw; }
+inline int pcm_encoding_bytes(int e) { return e == kEncS16 ? 2 : pcm_encoding_g711(e) ? 1 : 4; }
+
+// G.711 on the s16 integer q in [-32767, 32767] (the convention above sbv2_pcm_format, include/sbv2_hip.h), in integer arithmetic: the same
+// lines serve the device quantisers (pcm_format.hip), the level reduction (marks.hip) and the host functions sbv2_g711_encode / _decode.
+__host__ __device__ inline int g711_lg(int m) {   // floor(log2 m), m >= 1
+#ifdef __HIP_DEVICE_COMPILE__
+    return 31 - __clz(m);
+#else
+    return 31 - __builtin_clz((unsigned)m);
+#endif
+}
+__host__ __device__ inline uint8_t mulaw_encode(int q) {
+    const int a = q < 0 ? -q : q, m = (a < 32635 ? a : 32635) + 132;   // saturates, never wraps
+    const int e = g711_lg(m) - 7;                                      // 0 .. 7
+    return (uint8_t)~((q < 0 ? 0x80 : 0) | e << 4 | ((m >> (e + 3)) & 15));
+}
+__host__ __device__ inline int mulaw_decode(uint8_t code) {
+    const int u = ~code & 0xFF, t = (((u & 15) << 3) + 132) << ((u >> 4) & 7);
+    return u & 0x80 ? 132 - t : t - 132;
+}
+__host__ __device__ inline uint8_t alaw_encode(int q) {
+    const int m = (q >= 0 ? q : -q - 1) >> 3;
+    const int e = m < 32 ? 0 : g711_lg(m) - 4;   // 0 .. 7
+    return (uint8_t)(((q >= 0 ? 0x80 : 0) | e << 4 | ((m >> (e == 0 ? 1 : e)) & 15)) ^ 0x55);
+}
+__host__ __device__ inline int alaw_decode(uint8_t code) {
+    const int a = code ^ 0x55, e = (a >> 4) & 7;
+    int t = ((a & 15) << 4) + 8;
+    if (e >= 1) t = (t + 256) << (e - 1);
+    return a & 0x80 ? t : -t;
+}
+
 // A checked output format and its filter geometry: y[j] = sum_k h[j M - k L + half] x[k], h of length 2 half + 1 at 44100 L Hz,
 // seen as L polyphase branches of T taps each (branch p = h[p], h[p + L], ..., zero-padded).
 struct PcmFmtSpec {
     int rate = kNativeRate, encoding = 0, normalize = 0;
     int L = 1, M = 1, half = 0, T = 1;
-    int bytes() const { return encoding == 1 ? 2 : 4; }
+    int bytes() const { return pcm_encoding_bytes(encoding); }
     bool identity() const { return L == 1 && M == 1 && encoding == 0 && normalize == 0; }
 };
 // throws with a message for unsupported rates / encodings / normalise modes and a non-zero reserved field
@@ -90,7 +126,11 @@ class PcmFormatter {
     DeviceBuffer out_;
 };
 
-// n f64 samples x (device) times *unit (one device double) -> dst in `encoding` (0: f32, 1: s16), with the cast / quantiser of the gain stages
+// n f64 samples x (device) times *unit (one device double) -> dst in `encoding` (0: f32, 1: s16, 7 / 6: G.711 codes), with the cast /
+// quantiser of the gain stages
 void pcm_cast(const double* x, int64_t n, const double* unit, int encoding, void* dst_dev, hipStream_t s);
+// The gain-stage kernel on its own (the test hook's entry): total f64 samples y (device) of the signals in `sig` (device, nsig entries; only
+// out_off is read), sample o times gain[its signal] (device) -> dst in `encoding`
+void pcm_gain_signals(const double* y, const FmtSignal* sig, int nsig, const double* gain, int64_t total, int encoding, void* dst_dev, hipStream_t s);
 
 }  // namespace sbv2

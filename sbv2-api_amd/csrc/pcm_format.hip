@@ -1,4 +1,5 @@
-// PCM output formats on the device: 44.1 kHz -> R rational polyphase resampling, optional per-signal peak normalisation, f32 -> s16 quantiser.
+// PCM output formats on the device: 44.1 kHz -> R rational polyphase resampling, optional per-signal peak normalisation, f32 -> s16 quantiser,
+// G.711 mu-law / A-law codes of the s16 integers.
 //
 // Convention (the one tests/test_pcm_format.py pins): for a native signal x[0, N) (zero outside), L / M = R / 44100 in lowest terms,
 //   y[j] = sum_k h[j M - k L + half] x[k],   j in [0, ceil(N L / M)),
@@ -15,6 +16,7 @@
 #include <cmath>
 #include <cstring>
 #include <numeric>
+#include <type_traits>
 
 #include "../../include/sbv2_hip.h"
 #include "limiter.h"
@@ -108,7 +110,35 @@ __device__ __forceinline__ short quantise(double v) {
     return (short)fmin(fmax(rint(v * 32767.0), -32767.0), 32767.0);
 }
 
-// ENC 0: f32 out, 1: s16 out, 2: f64 y into dst + per-signal max |y| for the normalising pass (atomicMax on the bit pattern of a non-negative
+// The G.711 quantisers: the code of the s16 integer that quantise() delivers (mulaw_encode / alaw_encode, pcm_format.h), one byte per sample
+__device__ __forceinline__ uint8_t quantise_mulaw(double v) { return mulaw_encode(quantise(v)); }
+__device__ __forceinline__ uint8_t quantise_alaw(double v) { return alaw_encode(quantise(v)); }
+
+// The delivered encodings as the kernels number them (ENC): 0 f32, 1 s16, 4 mu-law, 5 A-law (2 and 3 are the f64 paths below; the public
+// values of sbv2_pcm_format.encoding are translated in with_enc and mean nothing here).  One store per thread: signals lie back to back, so a
+// G.711 signal starts at any byte offset and a byte store needs no alignment, no tail and no care for a dword that straddles two signals.
+constexpr int kEncKernelMulaw = 4, kEncKernelAlaw = 5;
+template <int ENC>
+__device__ __forceinline__ void deliver(void* dst, int64_t o, double v) {
+    static_assert(ENC == 0 || ENC == 1 || ENC == kEncKernelMulaw || ENC == kEncKernelAlaw, "not a delivered encoding");
+    if constexpr (ENC == 0) static_cast<float*>(dst)[o] = (float)v;
+    else if constexpr (ENC == 1) static_cast<short*>(dst)[o] = quantise(v);
+    else if constexpr (ENC == kEncKernelMulaw) static_cast<uint8_t*>(dst)[o] = quantise_mulaw(v);
+    else static_cast<uint8_t*>(dst)[o] = quantise_alaw(v);
+}
+// f(std::integral_constant<int, ENC>) for the ENC of a checked sbv2_pcm_format.encoding
+template <class F>
+void with_enc(int encoding, F&& f) {
+    switch (encoding) {
+        case kEncF32: f(std::integral_constant<int, 0>()); break;
+        case kEncS16: f(std::integral_constant<int, 1>()); break;
+        case kEncMulaw: f(std::integral_constant<int, kEncKernelMulaw>()); break;
+        case kEncAlaw: f(std::integral_constant<int, kEncKernelAlaw>()); break;
+        default: SBV2_REQUIRE(false, "internal: unknown PCM encoding " + std::to_string(encoding));
+    }
+}
+
+// ENC 0 / 1 / 4 / 5: delivered as above, 2: f64 y into dst + per-signal max |y| for the normalising pass (atomicMax on the bit pattern of a non-negative
 // double: exact and order-independent, so the gain is the same on every run), 3: f64 y alone (the loudness path: its meter finds the peak)
 template <int ENC>
 __global__ __launch_bounds__(256) void k_pcm_resample(KArgs a, void* dst, unsigned long long* peak) {
@@ -117,12 +147,10 @@ __global__ __launch_bounds__(256) void k_pcm_resample(KArgs a, void* dst, unsign
     int s = -1;
     double y = 0.0;
     if (live) y = resample_one(a, o, &s);
-    if constexpr (ENC == 0) {
-        if (live) static_cast<float*>(dst)[o] = (float)y;
-    } else if constexpr (ENC == 1) {
-        if (live) static_cast<short*>(dst)[o] = quantise(y);
-    } else if constexpr (ENC == 3) {
+    if constexpr (ENC == 3) {
         if (live) static_cast<double*>(dst)[o] = y;
+    } else if constexpr (ENC != 2) {
+        if (live) deliver<ENC>(dst, o, y);
     } else {
         if (live) static_cast<double*>(dst)[o] = y;
         double m = live ? fabs(y) : 0.0;
@@ -136,7 +164,7 @@ __global__ __launch_bounds__(256) void k_pcm_resample(KArgs a, void* dst, unsign
     }
 }
 
-// y * g, g = 1 / peak of y's signal (1 for a silent signal), -> f32 or s16
+// y * g, g = 1 / peak of y's signal (1 for a silent signal), -> a delivered encoding
 template <int ENC>
 __global__ __launch_bounds__(256) void k_pcm_gain(const double* y, const FmtSignal* sig, int nsig, const unsigned long long* peak, int64_t total,
                                                   void* dst) {
@@ -145,20 +173,16 @@ __global__ __launch_bounds__(256) void k_pcm_gain(const double* y, const FmtSign
     const int s = find_signal(sig, nsig, o);
     const double pk = __longlong_as_double((long long)peak[s]);
     const double g = pk > 0.0 ? 1.0 / pk : 1.0;
-    const double v = y[o] * g;
-    if constexpr (ENC == 0) static_cast<float*>(dst)[o] = (float)v;
-    else static_cast<short*>(dst)[o] = quantise(v);
+    deliver<ENC>(dst, o, y[o] * g);
 }
 
-// y * gain[s] (the loudness gain of y's signal, loudness.hip) -> f32 or s16
+// y * gain[s] (the loudness gain of y's signal, loudness.hip) -> a delivered encoding
 template <int ENC>
 __global__ __launch_bounds__(256) void k_pcm_gain_sig(const double* y, const FmtSignal* sig, int nsig, const double* gain, int64_t total,
                                                       void* dst) {
     const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (o >= total) return;
-    const double v = y[o] * gain[find_signal(sig, nsig, o)];
-    if constexpr (ENC == 0) static_cast<float*>(dst)[o] = (float)v;
-    else static_cast<short*>(dst)[o] = quantise(v);
+    deliver<ENC>(dst, o, y[o] * gain[find_signal(sig, nsig, o)]);
 }
 
 }  // namespace
@@ -204,7 +228,8 @@ std::vector<double> pcm_format_prototype(int rate, int* L, int* M, int* half) {
 
 PcmFmtSpec pcm_format_spec(const sbv2_pcm_format* f) {
     SBV2_REQUIRE(f, "no PCM format given");
-    SBV2_REQUIRE(f->encoding == 0 || f->encoding == 1, "unsupported PCM encoding " + std::to_string(f->encoding) + " (0 = f32, 1 = s16)");
+    SBV2_REQUIRE(pcm_encoding_known(f->encoding),
+                 "unsupported PCM encoding " + std::to_string(f->encoding) + " (0 = f32, 1 = s16, 7 = G.711 mu-law, 6 = G.711 A-law)");
     SBV2_REQUIRE(f->normalize == 0 || f->normalize == 1, "unsupported normalize mode " + std::to_string(f->normalize) + " (0 = none, 1 = peak)");
     SBV2_REQUIRE(f->reserved == 0, "sbv2_pcm_format.reserved must be 0");
     PcmFmtSpec s;
@@ -277,8 +302,7 @@ void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& piec
     a.total = total;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
     if (!spec.normalize && !staged) {
-        if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_resample<1>, grid, block, 0, s, a, dst_dev, nullptr);
-        else hipLaunchKernelGGL(k_pcm_resample<0>, grid, block, 0, s, a, dst_dev, nullptr);
+        with_enc(spec.encoding, [&](auto e) { hipLaunchKernelGGL(k_pcm_resample<decltype(e)::value>, grid, block, 0, s, a, dst_dev, nullptr); });
         HIP_CHECK(hipGetLastError());
         return;
     }
@@ -292,25 +316,25 @@ void PcmFormatter::run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& piec
     if (staged) {
         hipLaunchKernelGGL(k_pcm_resample<3>, grid, block, 0, s, a, tmp, nullptr);
         const double* x = apply_gain(stage, tmp, sig, spec.rate, s, &gain);
-        if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain_sig<1>, grid, block, 0, s, x, a.sig, a.nsig, gain, total, dst_dev);
-        else hipLaunchKernelGGL(k_pcm_gain_sig<0>, grid, block, 0, s, x, a.sig, a.nsig, gain, total, dst_dev);
-        HIP_CHECK(hipGetLastError());
+        pcm_gain_signals(x, a.sig, a.nsig, gain, total, spec.encoding, dst_dev, s);
         return;
     }
     HIP_CHECK(hipMemsetAsync(peak, 0, sizeof(unsigned long long) * sig.size(), s));
     hipLaunchKernelGGL(k_pcm_resample<2>, grid, block, 0, s, a, tmp, peak);
-    if (spec.encoding == 1) hipLaunchKernelGGL(k_pcm_gain<1>, grid, block, 0, s, tmp, a.sig, a.nsig, peak, total, dst_dev);
-    else hipLaunchKernelGGL(k_pcm_gain<0>, grid, block, 0, s, tmp, a.sig, a.nsig, peak, total, dst_dev);
+    with_enc(spec.encoding, [&](auto e) { hipLaunchKernelGGL(k_pcm_gain<decltype(e)::value>, grid, block, 0, s, tmp, a.sig, a.nsig, peak, total, dst_dev); });
+    HIP_CHECK(hipGetLastError());
+}
+
+void pcm_gain_signals(const double* y, const FmtSignal* sig, int nsig, const double* gain, int64_t total, int encoding, void* dst_dev, hipStream_t s) {
+    if (total <= 0) return;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    with_enc(encoding, [&](auto e) { hipLaunchKernelGGL(k_pcm_gain_sig<decltype(e)::value>, grid, block, 0, s, y, sig, nsig, gain, total, dst_dev); });
     HIP_CHECK(hipGetLastError());
 }
 
 void pcm_cast(const double* x, int64_t n, const double* unit, int encoding, void* dst_dev, hipStream_t s) {
-    if (n <= 0) return;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     // (one signal: find_signal answers 0 without reading the table)
-    if (encoding == 1) hipLaunchKernelGGL(k_pcm_gain_sig<1>, grid, block, 0, s, x, nullptr, 1, unit, n, dst_dev);
-    else hipLaunchKernelGGL(k_pcm_gain_sig<0>, grid, block, 0, s, x, nullptr, 1, unit, n, dst_dev);
-    HIP_CHECK(hipGetLastError());
+    pcm_gain_signals(x, nullptr, 1, unit, n, encoding, dst_dev, s);
 }
 
 }  // namespace sbv2

@@ -21,7 +21,7 @@ namespace {
 // the checked format of a FLAC stream: s16, not normalised (throws with the reason otherwise)
 PcmFmtSpec flac_stream_spec(const sbv2_pcm_format* fmt) {
     const PcmFmtSpec spec = pcm_format_spec(fmt);
-    SBV2_REQUIRE(spec.encoding == 1, "FLAC needs encoding = 1 (s16): f32 samples have no FLAC form");
+    SBV2_REQUIRE(spec.encoding == kEncS16, "FLAC needs encoding = 1 (s16): f32 samples and G.711 codes have no FLAC form");
     SBV2_REQUIRE(!spec.normalize, "a FLAC stream cannot normalise (normalize must be 0): the peak of the utterance is not known ahead");
     return spec;
 }
@@ -159,9 +159,12 @@ int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, 
     API_END
 }
 
-// Host only: A, the delivered samples a level stream runs behind (-1: bad fmt)
+// Host only: A, the delivered samples a level stream runs behind (-1: bad fmt).  A depends on the rate alone and this call keeps its first
+// contract: encodings 0 and 1 only (a G.711 level stream runs the A of its rate: ask with either)
 int64_t sbv2_stream_level_lookahead(const sbv2_pcm_format* fmt) {
     try {
+        SBV2_REQUIRE(!fmt || !pcm_encoding_g711(fmt->encoding),
+                     "unsupported PCM encoding " + std::to_string(fmt->encoding) + " for the look-ahead query (0 = f32, 1 = s16: A depends on the rate alone)");
         return stream_level_lookahead(pcm_format_spec(fmt).rate);
     } catch (const std::exception& e) {
         set_last_error(e.what());

@@ -1502,16 +1502,45 @@ int sbv2_debug_copy_segments(int device, const float* src, int64_t nsrc, const i
     API_END
 }
 
-// The level reduction of the speech marks (marks.hip) on host samples: x = n samples (encoding 0 = f32, 1 = s16), segments [starts[i], ends[i]).
+// The gain-stage kernel of the output chain (k_pcm_gain_sig, pcm_format.hip) on host f64 signals laid back to back, signal i times gains[i],
+// delivered in `encoding` (0, 1, 7, 6) -> dst (host, total samples).  The device output lies between two guard bands; a byte written there
+// fails the call.
+int sbv2_debug_pcm_cast(int device, const double* x, const int64_t* lens, int nsig, const double* gains, int32_t encoding, void* dst) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(nsig >= 1 && lens && gains, "bad arguments");
+    SBV2_REQUIRE(pcm_encoding_known(encoding), "unsupported PCM encoding " + std::to_string(encoding) + " (0 = f32, 1 = s16, 7 = G.711 mu-law, 6 = G.711 A-law)");
+    int64_t total = 0;
+    const std::vector<FmtSignal> sig = packed_signals(lens, nsig, &total);
+    SBV2_REQUIRE(total == 0 || (x && dst), "bad arguments");
+    constexpr size_t kGuard = 64;
+    constexpr unsigned char kFill = 0xA5;
+    const size_t nb = (size_t)total * pcm_encoding_bytes(encoding);
+    DevMem dx(x, sizeof(double) * (size_t)total), dsig(sig.data(), sizeof(FmtSignal) * sig.size()), dg(gains, sizeof(double) * (size_t)nsig),
+        dout(nb + 2 * kGuard);
+    HIP_CHECK(hipMemset(dout.p, kFill, nb + 2 * kGuard));
+    pcm_gain_signals(static_cast<const double*>(dx.p), static_cast<const FmtSignal*>(dsig.p), nsig, static_cast<const double*>(dg.p), total, encoding,
+                     dout.u8() + kGuard, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<unsigned char> h(nb + 2 * kGuard);
+    HIP_CHECK(hipMemcpy(h.data(), dout.p, h.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < kGuard; ++i)
+        SBV2_REQUIRE(h[i] == kFill && h[kGuard + nb + i] == kFill, "the cast wrote outside its " + std::to_string(nb) + " bytes");
+    if (nb) std::memcpy(dst, h.data() + kGuard, nb);
+    API_END
+}
+
+// The level reduction of the speech marks (marks.hip) on host samples: x = n samples (encoding 0 = f32, 1 = s16, 7 / 6 = G.711 codes), segments
+// [starts[i], ends[i]).
 int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n, const int64_t* starts, const int64_t* ends, int64_t nseg, double* sumsq,
                               double* peak) {
     API_BEGIN
     HIP_CHECK(hipSetDevice(device));
-    SBV2_REQUIRE((encoding == 0 || encoding == 1) && n >= 0 && nseg >= 0 && (x || n == 0), "bad arguments");
+    SBV2_REQUIRE(pcm_encoding_known(encoding) && n >= 0 && nseg >= 0 && (x || n == 0), "bad arguments");
     SBV2_REQUIRE(nseg == 0 || (starts && ends && sumsq && peak), "bad arguments");
     std::vector<int64_t> seg((size_t)(2 * nseg));
     for (int64_t i = 0; i < nseg; ++i) seg[2 * i] = starts[i], seg[2 * i + 1] = ends[i];
-    DevMem dx(x, (size_t)n * (encoding == 1 ? 2 : 4));
+    DevMem dx(x, (size_t)n * pcm_encoding_bytes(encoding));
     Marks m;
     m.run(dx.p, encoding, n, seg.data(), nseg, nullptr);
     HIP_CHECK(hipStreamSynchronize(nullptr));

@@ -939,7 +939,7 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     SBV2_REQUIRE(chunk_frames >= 16 && chunk_frames <= (1 << 20), "chunk_frames must be in [16, 2^20]");
     sfmt_on_ = sflac_on_ = slevel_on_ = false;
     slevel_A_ = 0;
-    SBV2_REQUIRE(!flac || (fmt && fmt->encoding == 1), "a FLAC stream needs encoding = 1 (s16): f32 samples have no FLAC form");
+    SBV2_REQUIRE(!flac || (fmt && fmt->encoding == kEncS16), "a FLAC stream needs encoding = 1 (s16): f32 samples and G.711 codes have no FLAC form");
     SBV2_REQUIRE(!level || fmt, "a level stream needs an output format");
     if (fmt) {
         SBV2_REQUIRE(!fmt->normalize, "a formatted stream cannot normalise: the peak of the utterance is not known ahead");

@@ -111,22 +111,25 @@ def synthesize(session: Session, bert_ori, x_tst, spk_ids, tones, lang_ids, styl
     return out.reshape(1, 1, -1)
 
 
-ENCODINGS = {"f32": 0, "s16": 1}
+ENCODINGS = {"f32": 0, "s16": 1, "mulaw": 7, "alaw": 6}   # the G.711 laws under their WAVE format tags
+G711 = ("mulaw", "alaw")
+_DTYPES = {"f32": np.float32, "s16": np.int16, "mulaw": np.uint8, "alaw": np.uint8}
 
 
 class PcmFormat:
-    """Output format of the PCM (struct sbv2_pcm_format): sample_rate in {8000, 16000, 22050, 24000, 32000, 44100, 48000}, encoding "f32" or
-    "s16", normalize = peak of each output signal to full scale.  Resampling, normalisation and quantisation run on the device."""
+    """Output format of the PCM (struct sbv2_pcm_format): sample_rate in {8000, 16000, 22050, 24000, 32000, 44100, 48000}, encoding "f32",
+    "s16", or G.711 "mulaw" / "alaw" (one byte per sample: the code of the s16 sample), normalize = peak of each output signal to full
+    scale.  Resampling, normalisation and quantisation run on the device."""
 
     def __init__(self, sample_rate: int = 44100, encoding: str = "f32", normalize: bool = False):
         if encoding not in ENCODINGS:
-            raise Sbv2Error(f"unsupported PCM encoding {encoding!r} (f32, s16)")
+            raise Sbv2Error(f"unsupported PCM encoding {encoding!r} (f32, s16, mulaw, alaw)")
         self.sample_rate, self.encoding, self.normalize = int(sample_rate), encoding, bool(normalize)
         self.c = _lib.Sbv2PcmFormat(self.sample_rate, ENCODINGS[encoding], int(self.normalize), 0)
 
     @property
     def dtype(self):
-        return np.int16 if self.encoding == "s16" else np.float32
+        return _DTYPES[self.encoding]
 
     @property
     def is_default(self) -> bool:
@@ -142,6 +145,54 @@ def pcm_format_length(fmt: PcmFormat, n_native: int) -> int:
     if n < 0:
         raise Sbv2Error(_lib.lib().sbv2_last_error().decode(errors="replace"))
     return n
+
+
+def _g711_law(encoding) -> int:
+    if encoding not in G711:
+        raise Sbv2Error(f"unsupported G.711 encoding {encoding!r} (mulaw, alaw)")
+    return ENCODINGS[encoding]
+
+
+def g711_encode(q, encoding: str) -> np.ndarray:
+    """The G.711 codes (uint8) of int16 samples q under "mulaw" / "alaw": the library's own rule, on the host (sbv2_g711_encode)."""
+    law = _g711_law(encoding)
+    q = np.ascontiguousarray(np.asarray(q, np.int16))
+    out = np.empty(q.shape, np.uint8)
+    check(_lib.lib().sbv2_g711_encode(law, q.ctypes.data_as(C.c_void_p), q.size, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def g711_decode(codes, encoding: str) -> np.ndarray:
+    """The int16 samples that G.711 codes (uint8 array or bytes) stand for under "mulaw" / "alaw" (sbv2_g711_decode; host only)."""
+    law = _g711_law(encoding)
+    c = np.frombuffer(codes, np.uint8) if isinstance(codes, (bytes, bytearray, memoryview)) else np.asarray(codes, np.uint8)
+    c = np.ascontiguousarray(c)
+    out = np.empty(c.shape, np.int16)
+    check(_lib.lib().sbv2_g711_decode(law, c.ctypes.data_as(C.c_void_p), c.size, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def debug_pcm_cast(signals, gains, encoding: str, device: int = 0, guard: int = 64):
+    """Test hook: the gain-stage kernel of the output chain on host float64 signals laid back to back, signal i times gains[i], delivered in
+    `encoding` -> one array per signal.  The host destination lies between two `guard`-byte bands of 0xA5, checked here; the hook checks
+    the bands around its device output."""
+    if encoding not in ENCODINGS:
+        raise Sbv2Error(f"unsupported PCM encoding {encoding!r} (f32, s16, mulaw, alaw)")
+    sigs = [np.ascontiguousarray(np.asarray(x, np.float64)).reshape(-1) for x in signals]
+    x = np.concatenate(sigs) if sigs else np.zeros(0, np.float64)
+    lens = np.array([s.size for s in sigs], np.int64)
+    g = np.ascontiguousarray(np.asarray(gains, np.float64).reshape(-1))
+    if g.size != len(sigs):
+        raise Sbv2Error(f"one gain per signal ({len(sigs)})")
+    dt = np.dtype(_DTYPES[encoding])
+    nb = x.size * dt.itemsize
+    buf = np.full(nb + 2 * guard, 0xA5, np.uint8)
+    check(_lib.lib().sbv2_debug_pcm_cast(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(sigs),
+                                         _f64p(g), ENCODINGS[encoding], buf[guard:].ctypes.data_as(C.c_void_p)))
+    if not (np.all(buf[:guard] == 0xA5) and np.all(buf[guard + nb:] == 0xA5)):
+        raise Sbv2Error("sbv2_debug_pcm_cast wrote outside its destination")
+    out = buf[guard:guard + nb].copy().view(dt)
+    return np.split(out, np.cumsum(lens)[:-1])
 
 
 def pcm_format_taps(sample_rate: int):
@@ -297,8 +348,10 @@ class StreamLevel:
 
 
 def stream_level_lookahead(fmt: PcmFormat) -> int:
-    """A: the delivered samples a level stream runs behind, sample_rate // 100 + 11 (host only)."""
-    n = _lib.lib().sbv2_stream_level_lookahead(C.byref(fmt.c))
+    """A: the delivered samples a level stream runs behind, sample_rate // 100 + 11 (host only).  A depends on the rate alone; the C query
+    takes f32 / s16 formats only, so a G.711 format asks with the s16 format of its rate."""
+    c = PcmFormat(fmt.sample_rate, "s16").c if fmt.encoding in G711 else fmt.c
+    n = _lib.lib().sbv2_stream_level_lookahead(C.byref(c))
     if n < 0:
         raise Sbv2Error(_lib.lib().sbv2_last_error().decode(errors="replace"))
     return n
@@ -352,11 +405,16 @@ class Marks:
         return [a for a in (self.start, self.end, self.sumsq, self.peak, self.env_sumsq, self.env_peak) if a is not None]
 
 
+def full_scale(encoding: str) -> float:
+    """Full scale of the delivered samples' levels: 32767 for s16 and for G.711 (levels of the decoded integers), 1 for f32."""
+    return 1.0 if encoding == "f32" else 32767.0
+
+
 def level_dbfs(sumsq, n, encoding: str = "f32"):
-    """10 log10(sumsq / n) re full scale (s16: 32767) of a span of n delivered samples; None for an empty or all-zero one."""
+    """10 log10(sumsq / n) re full scale (s16, mulaw, alaw: 32767) of a span of n delivered samples; None for an empty or all-zero one."""
     if n <= 0 or sumsq <= 0:
         return None
-    return float(10.0 * np.log10(float(sumsq) / n / (32767.0 ** 2 if encoding == "s16" else 1.0)))
+    return float(10.0 * np.log10(float(sumsq) / n / full_scale(encoding) ** 2))
 
 
 def marks_spans(durations, hop: int, place: int, fmt: PcmFormat):
@@ -369,14 +427,18 @@ def marks_spans(durations, hop: int, place: int, fmt: PcmFormat):
     return st, en
 
 
-def debug_segment_levels(x, starts, ends, device: int = 0):
-    """Test hook: the device level reduction on host samples x (int16 or float32) -> (sumsq, peak) per segment [starts[i], ends[i])."""
+def debug_segment_levels(x, starts, ends, device: int = 0, encoding: str | None = None):
+    """Test hook: the device level reduction on host samples x (int16 or float32; uint8 G.711 codes with encoding "mulaw" / "alaw") ->
+    (sumsq, peak) per segment [starts[i], ends[i])."""
     x = np.ascontiguousarray(x).reshape(-1)
-    if x.dtype not in (np.int16, np.float32):
+    if encoding is None and x.dtype not in (np.int16, np.float32):
         raise Sbv2Error(f"levels are taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"levels of {encoding!r} samples are not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
     st, en = (np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1)) for a in (starts, ends))
     ss, pk = np.zeros(st.size, np.float64), np.zeros(st.size, np.float64)
-    check(_lib.lib().sbv2_debug_segment_levels(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, int(x.dtype == np.int16), x.size,
+    check(_lib.lib().sbv2_debug_segment_levels(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size,
                                                st.ctypes.data_as(i64p), en.ctypes.data_as(i64p), st.size, _f64p(ss), _f64p(pk)))
     return ss, pk
 
@@ -552,7 +614,7 @@ class Pipeline:
         return (_split_bytes(dst, got), stats) if nstats else _split_bytes(dst, got)
 
     def fetch_format(self, b, fmt: PcmFormat, place=None, joined_len=None):
-        """PCM of the run `b` in the output format `fmt` (resampled / normalised / quantised on the device; int16 or float32 arrays).
+        """PCM of the run `b` in the output format `fmt` (resampled / normalised / quantised on the device; int16 or float32 arrays, uint8 G.711 codes).
         place None: one array per utterance.  place [n] native-sample offsets + joined_len: ONE array, the utterances laid on a silent
         timeline of joined_len native samples."""
         return self._fetch_pcm("sbv2_pipeline_fetch_pcm_format", b, fmt, (), place, joined_len)
@@ -654,7 +716,7 @@ class StreamHandle:
     total_samples is then counted at fmt.sample_rate.  flac=True (fmt must be s16): the chunks' samples are encoded on the device as ONE FLAC
     stream; next() returns the bytes of the frames the chunk completed (b"" when it completed none: FLAC frames hold 4096 samples), the
     42-byte stream header in front of the first ones; samples_taken counts the s16 samples consumed so far.
-    level (StreamLevel; needs fmt, f32 or s16, with or without flac): the samples pass a fixed gain and the look-ahead limiter on the device,
+    level (StreamLevel; needs fmt, any encoding; flac with s16 only): the samples pass a fixed gain and the look-ahead limiter on the device,
     carried from chunk to chunk.  Delivery runs stream_level_lookahead(fmt) samples behind the chunks: next() returns what the chunk
     completed (possibly an empty array or b""), the last chunk everything; samples_taken counts the chunks' samples; level_stats() after
     the end."""
@@ -668,7 +730,7 @@ class StreamHandle:
         if flac and fmt is None:
             raise Sbv2Error("a FLAC stream needs a format: fmt=PcmFormat(rate, \"s16\")")
         if level is not None and fmt is None:
-            raise Sbv2Error("a level stream needs a format: fmt=PcmFormat(rate, \"f32\" or \"s16\")")
+            raise Sbv2Error("a level stream needs a format: fmt=PcmFormat(rate, encoding), any encoding")
         tot = C.c_int64()
         args = (bert.handle, vits.handle, C.byref(self.b.c), self.b.ids.ctypes.data_as(i64p), self.b.s_lens.ctypes.data_as(i64p),
                 self.b.w2p.ctypes.data_as(i64p), chunk_frames)

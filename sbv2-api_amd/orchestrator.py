@@ -33,6 +33,8 @@ class SynthesizeOptions:
     """tts.rs:359-375 (same defaults).  sample_rate / encoding / normalize are new (the reference writes 44.1 kHz f32 only): when any of
     them differs from its default the request's WAV signal is resampled / normalised / quantised on the device (model.PcmFormat).
     encoding "flac": the same signal as s16, returned as a FLAC stream encoded on the device instead of a WAV.
+    encoding "mulaw" / "alaw" (new): the same signal as G.711 codes, one byte per sample, encoded on the device from the s16 samples and
+    returned as a WAV with format tag 7 / 6 (g711_wav); what telephony links carry, usually at sample_rate 8000.
     loudness (target LUFS) / true_peak_max (dBTP) are new as well: the signal's integrated loudness is brought to the target, capped by the
     true-peak ceiling (model.Loudness); it replaces peak normalisation, so normalize=True with a loudness is refused.  That gain is one
     scale, so a target is missed whenever the signal's peak-to-loudness ratio exceeds true_peak_max - loudness (speech: about 20 dB, which
@@ -107,6 +109,32 @@ def pcm16_wav(samples: np.ndarray, rate: int) -> bytes:
     channels, bits = 1, 16
     block = channels * bits // 8
     return _riff(struct.pack("<HHIIHH", 0x0001, channels, rate, rate * block, block, bits), data)
+
+
+G711_TAGS = {"mulaw": 7, "alaw": 6}   # WAVE_FORMAT_MULAW / WAVE_FORMAT_ALAW
+
+
+def _g711_header(rate: int, encoding: str, n: int) -> bytes:
+    if encoding not in G711_TAGS:
+        raise model.Sbv2Error(f"unsupported G.711 encoding {encoding!r} (mulaw, alaw)")
+    n = int(n)
+    fmt = struct.pack("<HHIIHHH", G711_TAGS[encoding], 1, rate, rate, 1, 8, 0)   # 18 bytes: the non-PCM form, cbSize 0
+    return (b"RIFF" + struct.pack("<I", 50 + n + (n & 1)) + b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt +
+            b"fact" + struct.pack("<II", 4, n) + b"data" + struct.pack("<I", n))
+
+
+def g711_wav(codes, rate: int, encoding: str) -> bytes:
+    """Mono G.711 WAV ("mulaw": format tag 7, "alaw": 6) at any rate: the 18-byte fmt chunk of a non-PCM format (8 bits, block align 1, byte
+    rate = rate, cbSize 0), a fact chunk with the sample count, then the codes; 58 bytes of header, one zero pad byte after an odd count."""
+    data = np.ascontiguousarray(np.frombuffer(codes, np.uint8) if isinstance(codes, (bytes, bytearray, memoryview)) else codes, dtype=np.uint8).tobytes()
+    return _g711_header(rate, encoding, len(data)) + data + b"\0" * (len(data) & 1)
+
+
+def _pcm_wav(out, fmt) -> bytes:
+    """The WAV of delivered samples `out` in the PcmFormat fmt."""
+    if fmt.encoding in G711_TAGS:
+        return g711_wav(out, fmt.sample_rate, fmt.encoding)
+    return pcm16_wav(out, fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out, fmt.sample_rate)
 
 
 def joined_placement(lens, live_index, n_lines, split_sentences=True):
@@ -191,7 +219,7 @@ def marks_dict(utts, live, fmt, m) -> dict:
     square of its delivered samples re full scale; None for an empty or silent span) and peak (largest |sample| re full scale), and `envelope`
     {hop, level_dbfs [n], peak [n]} when the marks hold one.  The gaps between sentences belong to no token."""
     d = token_marks(utts, live, fmt.sample_rate, m.start, m.end)
-    full = 32767.0 if fmt.encoding == "s16" else 1.0
+    full = model.full_scale(fmt.encoding)
     if m.sumsq is not None:
         for t, ss, pk in zip(d["tokens"], m.sumsq, m.peak):
             t["level_dbfs"] = model.level_dbfs(ss, t["end"] - t["start"], fmt.encoding)
@@ -224,7 +252,7 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
             loudness_stats.append([float(v) for v in stats])
         if plan.flac:
             return out
-        return pcm16_wav(out, fmt.sample_rate) if fmt.encoding == "s16" else float_wav(out, fmt.sample_rate)
+        return _pcm_wav(out, fmt)
     if pcm is None:
         pcm = pipe.fetch(b)
     parts = []
@@ -270,8 +298,10 @@ def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, styl
 
 
 def wav_stream_header(rate: int, encoding: str, n_samples: int) -> bytes:
-    """The header of pcm16_wav ("s16") / float_wav ("f32") for a signal of n_samples whose samples follow later: the same bytes as the header
-    of the finished file."""
+    """The header of pcm16_wav ("s16") / float_wav ("f32") / g711_wav ("mulaw", "alaw") for a signal of n_samples whose samples follow later:
+    the same bytes as the header of the finished file (after an odd number of G.711 codes the file ends with one zero pad byte)."""
+    if encoding in G711_TAGS:
+        return _g711_header(rate, encoding, n_samples)
     empty = pcm16_wav(np.zeros(0, np.int16), rate) if encoding == "s16" else float_wav(np.zeros(0, np.float32), rate)
     data = int(n_samples) * (2 if encoding == "s16" else 4)
     riff = struct.unpack("<I", empty[4:8])[0] + data
@@ -283,8 +313,8 @@ class SynthesisStream:
     the pieces run out, when one fails, by close(), and when the object is dropped, iterated or not: the replays of a stream are already
     enqueued when this object is returned, so its end cannot hang on a generator's `finally`, which never runs for a generator nobody started."""
 
-    def __init__(self, st, head, to_bytes, marks=None):
-        self._st, self._head, self._to_bytes = st, head, to_bytes
+    def __init__(self, st, head, to_bytes, marks=None, tail=None):
+        self._st, self._head, self._to_bytes, self._tail = st, head, to_bytes, tail   # tail: bytes that follow the last chunk (a pad byte)
         self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece (streams carry no levels)
         self.level_stats = None   # a level stream's (deepest reduction in dB, max |x|), once its last piece has been handed out
 
@@ -301,19 +331,24 @@ class SynthesisStream:
                 if c is None:
                     if getattr(self._st, "level", None) is not None:
                         self.level_stats = self._st.level_stats()
+                    st, self._st = self._st, None
+                    st.close()      # the device side is done; on_close waits until the last byte has been handed out
                     break
                 if len(c):
                     return self._to_bytes(c)
         except BaseException:
             self.close()
             raise
+        tail, self._tail = self._tail, None
+        if tail:
+            return tail     # close(), and on_close with it, follows on the next call: the holder's lock is held until the last byte
         self.close()
         raise StopIteration
 
     on_close = None   # optional callable, run once when the stream is closed (the holder resumes the model's batcher with it)
 
     def close(self):
-        st, self._st, self._head = self._st, None, None
+        st, self._st, self._head, self._tail = self._st, None, None, None
         try:
             if st is not None:
                 st.close()
@@ -336,9 +371,10 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     takes ONE utterance (model.StreamHandle: whole-sequence DeBERTa / text / flow, then the decoder chunk by chunk), so `sentences` must hold
     one parsed text: the request's lines joined, as options.split_sentences = False passes them (empty entries are skipped, a second live one
     is refused).  encoding "flac": the pieces of one FLAC stream encoded on the device, as its frames complete (chunks that complete none
-    yield nothing); "s16" / "f32": the WAV header of pcm16_wav / float_wav written with the known total length, then the chunks' samples.
+    yield nothing); "s16" / "f32": the WAV header of pcm16_wav / float_wav written with the known total length, then the chunks' samples;
+    "mulaw" / "alaw": the header of g711_wav, the chunks' codes, and one zero pad byte after the last chunk when the total is odd.
     normalize, loudness and limiter are refused: they need the whole signal before the first sample can leave.
-    options.gain_db: the level stream (model.StreamLevel(gain_db, true_peak_max)) for "f32", "s16" and "flac" alike: a fixed gain, no sample above
+    options.gain_db: the level stream (model.StreamLevel(gain_db, true_peak_max)) for every encoding alike: a fixed gain, no sample above
     the ceiling; the pieces run stream_level_lookahead samples behind the decoder, the total length is unchanged, and after the last piece
     the iterator's `.level_stats` holds (deepest reduction in dB, max |x|).
     Everything up to the first replay (options, DeBERTa, flow, the header) runs before the iterator is returned.
@@ -372,6 +408,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
         raise
     if flac:
         return SynthesisStream(st, None, lambda c: c, marks)
-    dtype = "<i2" if fmt.encoding == "s16" else "<f4"
+    dtype = {"s16": "<i2", "f32": "<f4"}.get(fmt.encoding, "u1")
+    pad = b"\0" if fmt.encoding in G711_TAGS and st.total_samples & 1 else None
     return SynthesisStream(st, wav_stream_header(fmt.sample_rate, fmt.encoding, st.total_samples),
-                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks)
+                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad)

@@ -4,14 +4,14 @@ and error mapping, so that a client of the reference's server cannot tell the di
   GET  /            "Hello, World!"                                              main.rs:193
   GET  /models      JSON list of idents                                          main.rs:24-33
   POST /synthesize  {text, ident, sdp_ratio = 0.0, length_scale = 1.0, style_id = 0, speaker_id = 0} -> audio/wav     main.rs:51-100
-                    (+ sample_rate = 44100, encoding = "f32" | "s16" | "flac", normalize = false: new output formats, defaults = the
-                    reference's; "flac" -> audio/flac; loudness = null (target LUFS), true_peak_max = -1.0 (dBTP): loudness
+                    (+ sample_rate = 44100, encoding = "f32" | "s16" | "flac" | "mulaw" | "alaw", normalize = false: new output formats, defaults = the
+                    reference's; "flac" -> audio/flac; "mulaw" / "alaw" -> audio/wav holding G.711 codes, format tag 7 / 6; loudness = null (target LUFS), true_peak_max = -1.0 (dBTP): loudness
                     normalisation, exclusive with normalize.  The loudness gain is one scale: a target louder than the signal's
                     true_peak_max - (TP - L), about -21 LUFS for speech under -1 dBTP, is missed unless limiter = true (default false;
                     max_reduction = 6.0 dB): a look-ahead true-peak limiter that reaches it; limiter needs loudness)
   POST /synthesize_stream  new: the same request, answered while it is synthesised (chunked transfer): the text as ONE utterance (joined, as
                     split_sentences = false does), encoding "flac" -> audio/flac, one FLAC stream encoded on the device chunk by chunk;
-                    "s16" / "f32" -> audio/wav, the header written with the known length, then the chunks.  normalize / loudness / limiter
+                    "s16" / "f32" / "mulaw" / "alaw" -> audio/wav, the header written with the known length, then the chunks.  normalize / loudness / limiter
                     are refused (they need the whole signal).  gain_db = null (new): a fixed gain in dB with the limiter's look-ahead gain
                     curve holding every sample under true_peak_max, carried from chunk to chunk on the device; same length, same header;
                     the other routes refuse it.  Errors before the first byte map as below; the lock is held until the last byte
@@ -100,7 +100,7 @@ def make_app(holder, batching=None):
         style_id: int = 0
         speaker_id: int = 0
         sample_rate: int = 44100            # new: output format of the WAV (the reference's is 44.1 kHz f32)
-        encoding: str = "f32"               # "f32" | "s16" | "flac"
+        encoding: str = "f32"               # "f32" | "s16" | "flac" | "mulaw" | "alaw" (G.711 in a WAV, tag 7 / 6)
         normalize: bool = False             # peak of the signal -> full scale
         loudness: Optional[float] = None    # integrated loudness target (LUFS, BS.1770-4); exclusive with normalize
         true_peak_max: float = -1.0         # true-peak ceiling (dBTP) of the loudness gain
