@@ -516,11 +516,64 @@ int sbv2_debug_limiter_fixed(int device, const double* x, const int64_t* lens, i
 int sbv2_debug_limiter_stream(int device, const double* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
                               const sbv2_stream_level* level, double* out_x, int64_t* out_per_push, double* stats);
 /* ---- new: speech marks of a stream.  Host only, valid from sbv2_stream_begin* onwards: the token spans (see sbv2_marks) of the stream's one
- * utterance at place 0 and at the stream's delivered rate (native for sbv2_stream_begin).  Every duration is known before the first replay, so
+ * utterance at place 0 (a request stream, sbv2_stream_begin_request: of all its rows, row i at place[i], row order then token order) and at
+ * the stream's delivered rate (native for sbv2_stream_begin).  Every duration is known before the first replay, so
  * the client has the full timing before the first audio byte; the samples of all chunks sum to the last token's end (durations summing to >= 1).
  * Levels and the envelope are NOT built on streams: they would need partial sums carried across chunks, and a streaming client decodes the
  * audio anyway.  Refused: capacity below the token count. */
 int sbv2_stream_marks(sbv2_stream* s, int64_t* tok_start, int64_t* tok_end, int64_t capacity, int64_t* n_tokens);
+/* ---- new: a stream over the n rows of ONE batched forward: a multi-sentence request as one signal, sentence by sentence.
+ * Forward.  batch->n >= 1 rows run through one forward with the decoder left out: the forward sbv2_pipeline_run_opts runs for that batch and
+ *   opts (which may be NULL), so durations and noise keys are those of the run.
+ * Timeline.  With len[i] the native (44.1 kHz) samples of row i: place[0] = 0, place[i + 1] = place[i] + len[i] + gap_after[i],
+ *   joined_len = place[n - 1] + len[n - 1] + gap_after[n - 1]; *total_samples = J(joined_len), J(a) = ceil(a L / M) at the stream's rate.
+ * Output.  The concatenation of everything the stream delivers is the signal sbv2_pipeline_fetch_pcm_format(..., place, joined_len, ...)
+ *   delivers for a pipeline run of the same batch and options in the same format; with flac its s16 samples as one FLAC stream in the
+ *   convention of sbv2_stream_begin_flac; with level the x of sbv2_stream_level for the whole joined y.
+ * Calls.  Row i is cut on its own frame grid into ceil(frames[i] / chunk_frames) chunks (a gap is no multiple of the hop: there is no joined
+ *   frame grid); the stream's calls are those chunks in row order, then chunk order.  With m_i = place[i] + len[i] + gap_after[i] / 2 (integer
+ *   division) for i < n - 1, m_{-1} = 0 and m_{n-1} = joined_len, the call for chunk [a, b) (native positions of the timeline) of row i delivers
+ *   the output samples [J(a'), J(b')): a' = m_{i-1} for the row's first chunk, else a; b' = m_i for its last chunk, else b.  The calls tile
+ *   [0, J(joined_len)): each gap leaves half with the sentence before it and half with the one after it, trailing silence with the last call.
+ * Minimum gap.  For i < n - 1, gap_after[i] >= 2 ceil(half / L) of the format (sbv2_stream_min_gap): 354 at 8 kHz, 178 at 16 kHz, 128 at
+ *   22.05 kHz, 118 at 24 kHz, 90 at 32 kHz, 64 at 48 kHz, 0 at 44.1 kHz (sentences may abut).  Then no output sample on one side of m_i has a
+ *   filter tap on the other side's sentence, and every call needs its own window's PCM only.  A shorter gap is refused with the minimum named;
+ *   every gap_after[i] must lie in [0, 441000] (10 s).  The halo check of sbv2_stream_begin_format (reach <= exact) stays as it is: the
+ *   exact part of the halo grows with the hop, so the full-size model (hop 512) streams 16 kHz and 8 kHz, and only a model with a small hop
+ *   (the tiny test models, hop 16) is refused 16 kHz by it.
+ * Taking chunks.  A request stream is always a formatted stream, also at the identity format: sbv2_stream_next_format, or sbv2_stream_next_flac
+ *   with flac, or sbv2_stream_next_level with level; sbv2_stream_next is refused.  n_consumed / n_samples of call c = call_samples[c] of
+ *   sbv2_stream_timeline; the end marker and "too small a buffer: nothing written, nothing consumed, repeat" are those of the single-utterance
+ *   streams.  sbv2_stream_marks gives the tokens of all rows, row order then token order, row i at place[i]: the spans of
+ *   sbv2_pipeline_fetch_request_marks for the joined fetch; the silence belongs to no token.
+ * Refused before any GPU work: NULL rq or gap_after, n < 1, a gap out of range or below the minimum, a non-zero reserved, normalize, flac without
+ *   s16, and whatever the options, the format and the level are refused for elsewhere.
+ * Not built: gaps below the minimum at resampled rates (they would need a call to see two windows), levels / an envelope in the marks, a
+ *   loudness target, sbv2_node_*.  The four calls above are the n = 1, gap_after = {0} case of the same code and keep their bytes. */
+typedef struct sbv2_stream_request {
+    const int64_t* gap_after;         /* [batch->n] native (44.1 kHz) samples of silence after row i; the last entry is trailing silence */
+    const sbv2_pcm_format* fmt;       /* NULL = 44100 Hz f32, not normalised (the identity format) */
+    const sbv2_stream_level* level;   /* NULL = none */
+    int32_t flac;                     /* 1 = one FLAC stream (fmt s16) */
+    int32_t reserved;                 /* must be 0 */
+} sbv2_stream_request;
+int sbv2_stream_begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                              const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                              const sbv2_stream_request* rq, sbv2_stream** out, int64_t* total_samples);
+/* Host only: the minimum gap above in native samples (fmt NULL = the identity format = 0); -1 for a bad fmt. */
+int64_t sbv2_stream_min_gap(const sbv2_pcm_format* fmt);
+/* Host only: the arithmetic above in one place (the library calls it itself).  frames[n] = the rows' lengths in frames (>= 1), hop =
+ * sbv2_vits_hop, fmt NULL = the identity format.  Outputs (each may be NULL): place[n], *joined_len, call_samples[c] = the samples call c covers
+ * (a level stream DELIVERS them by its delivery rule, A samples late), *n_calls (also written when capacity is refused).  Refused: what
+ * sbv2_stream_begin_request refuses in the gaps, n < 1, a row without frames, hop or chunk_frames < 1, capacity < n_calls with call_samples given. */
+int sbv2_stream_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int32_t hop, int64_t chunk_frames, const sbv2_pcm_format* fmt,
+                         int64_t* place, int64_t* joined_len, int64_t* call_samples, int64_t capacity, int64_t* n_calls);
+/* Host only, valid from any sbv2_stream_begin* onwards: the rows' placement and native lengths (capacity entries each; either may be NULL), *n
+ * rows, *joined_len. */
+int sbv2_stream_layout(const sbv2_stream* s, int64_t* place, int64_t* pcm_lens, int64_t capacity, int64_t* n, int64_t* joined_len);
+/* Host only: bytes that suffice for any sbv2_stream_next* call of THIS stream: its largest call, plus A samples with a level, or the FLAC push
+ * bound of that many samples.  (sbv2_flac_stream_bound / sbv2_stream_level_bound bound a plain chunk, not a call that carries half a gap.) */
+int64_t sbv2_stream_call_bound(const sbv2_stream* s);
 int sbv2_stream_uses_graph(const sbv2_stream* s);
 int64_t sbv2_stream_workspace_bytes(const sbv2_stream* s);
 void sbv2_stream_end(sbv2_stream* s);
@@ -714,10 +767,16 @@ int sbv2_debug_text_embed(int device, const int32_t* phones, const int32_t* tone
    tok_mask [sum lens] (may be null) is the layout's extra mask; use_mask = 0 passes no mask to the kernel */
 int sbv2_debug_add_segvec(int device, const float* x, const float* vec, int64_t C, const int64_t* lens, int nutt, int kind, int64_t div,
                           const uint8_t* tok_mask, int use_mask, int cl, float* y, int64_t* stray);
-/* op 0 = gather_cols (map [a], y [C][a]); 1 = transpose_out (col0 = a, T = b, y [T][C]); 2 = window_cols (col0 = a, width b, y [C][b], mask_out [b]);
-   3 = flip_channels; 4 = swap_rows (C = 2) */
+/* op 0 = gather_cols (map [a], y [C][a]); 1 = transpose_out (col0 = a, T = b, y [T][C]); 2 = one window of stream_windows over the whole plane
+   (first column a, width b, y [C][b], mask_out [b]); 3 = flip_channels; 4 = swap_rows (C = 2) */
 int sbv2_debug_plane_op(int device, int op, const float* x, int64_t C, int64_t L, const int32_t* map, int64_t a, int64_t b, float* y, uint8_t* mask_out,
                         int64_t* stray);
+/* stream_windows (ops.h), the one launch in front of a replay of the streaming decoder: z [C][L] = a plane holding several rows (the caller
+   puts NaN between and around them), table [nwin][4] = {first z column of the window's row, row length in frames, first frame of the window
+   within the row (any sign), row index}, cond_vecs [n_rows][cond_dim].  Outputs: z_out [nwin][C][W], mask_out [nwin][W], cond_out
+   [nwin][cond_dim].  On the device the three outputs lie between guard bands; a byte written outside them fails the call.  nwin <= 16. */
+int sbv2_debug_stream_windows(int device, const float* z, int64_t C, int64_t L, const int32_t* table, int64_t W, int64_t nwin, const float* cond_vecs,
+                              int64_t n_rows, int64_t cond_dim, float* z_out, uint8_t* mask_out, float* cond_out);
 /* copy_segments: table [nseg][3] = (source offset, destination offset, length); dst is read and written (what no segment covers stays) */
 int sbv2_debug_copy_segments(int device, const float* src, int64_t nsrc, const int64_t* table, int nseg, float* dst, int64_t ndst);
 

@@ -39,6 +39,12 @@ class Sbv2StreamLevel(C.Structure):
     _fields_ = [("gain_db", C.c_double), ("true_peak_max_dbtp", C.c_double), ("reserved", C.c_double * 2)]
 
 
+class Sbv2StreamRequest(C.Structure):
+    """struct sbv2_stream_request (include/sbv2_hip.h)."""
+    _fields_ = [("gap_after", i64p), ("fmt", C.POINTER(Sbv2PcmFormat)), ("level", C.POINTER(Sbv2StreamLevel)), ("flac", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class Sbv2UttOptions(C.Structure):
     """struct sbv2_utt_options (include/sbv2_hip.h)."""
     _fields_ = [("sdp_ratio", f32p), ("length_scale", f32p), ("noise_scale", f32p), ("noise_scale_w", f32p),
@@ -163,6 +169,14 @@ SYMBOLS = {
                                            C.POINTER(C.c_double)]),
     "sbv2_debug_limiter_stream": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2StreamLevel), C.c_void_p, i64p,
                                             C.POINTER(C.c_double)]),
+    "sbv2_stream_begin_request": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p, i64p, i64p, C.c_int64,
+                                            C.POINTER(Sbv2StreamRequest), C.POINTER(C.c_void_p), i64p]),
+    "sbv2_stream_min_gap": (C.c_int64, [C.POINTER(Sbv2PcmFormat)]),
+    "sbv2_stream_timeline": (C.c_int, [i64p, i64p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, i64p, i64p, C.c_int64, i64p]),
+    "sbv2_stream_layout": (C.c_int, [C.c_void_p, i64p, i64p, C.c_int64, i64p, i64p]),
+    "sbv2_stream_call_bound": (C.c_int64, [C.c_void_p]),
+    "sbv2_debug_stream_windows": (C.c_int, [C.c_int, f32p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64, f32p, C.c_int64, C.c_int64,
+                                            f32p, C.c_void_p, f32p]),
     "sbv2_stream_uses_graph": (C.c_int, [C.c_void_p]),
     "sbv2_stream_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "sbv2_stream_end": (None, [C.c_void_p]),

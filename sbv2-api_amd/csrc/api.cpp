@@ -29,7 +29,7 @@ VitsBatch to_batch(const sbv2_batch* b) {
 }
 
 // The per-row arrays of sbv2_utt_options onto the batch (host pointers, read by forward()); every check here, before any GPU work.
-static void apply_utt_options(VitsBatch* v, const sbv2_utt_options* o) {
+void apply_utt_options(VitsBatch* v, const sbv2_utt_options* o) {
     if (!o) return;
     const auto row = [](int u) { return " of row " + std::to_string(u); };
     for (int u = 0; u < v->n; ++u) {

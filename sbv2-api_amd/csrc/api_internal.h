@@ -68,6 +68,8 @@ struct sbv2_pipeline {
     }
 
 VitsBatch to_batch(const sbv2_batch* b);
+// The per-row arrays of sbv2_utt_options onto the batch (NULL: nothing); throws for an option out of range, before any GPU work
+void apply_utt_options(sbv2::VitsBatch* v, const sbv2_utt_options* o);
 // One batch on one execution context: bert::predict -> word2ph repeat (tts_util.rs:129-154) -> model::synthesize; returns once enqueued
 void pipeline_run_one(sbv2::BertModel& bm, sbv2::VitsModel& vm, sbv2::VitsBatch v, const int64_t* token_ids, const int64_t* s_lens,
                       const int64_t* word2ph);

@@ -274,6 +274,24 @@ struct VitsConfig {
 };
 
 constexpr int kStreamBurst = 8;   // windows per graph replay of the streaming decoder after an utterance's first chunk
+// The timeline of a stream over the n rows of one forward (the contract above sbv2_stream_begin_request, include/sbv2_hip.h): row i of
+// len[i] = frames[i] * hop native samples lies at place[i] of a silent timeline of `joined` samples; the calls are the rows' chunks in row
+// order, then chunk order, call c delivering the output samples [j0, j1) of the timeline.  The library's one place for this arithmetic
+// (sbv2_stream_timeline and VitsModel::stream_begin both call it); every check before any device call, refusals as exceptions.
+constexpr int64_t kStreamMaxGap = 441000;   // 10 s of silence after a row
+struct StreamCall {
+    int row;
+    int64_t f0;       // the chunk's first frame within its row
+    int64_t j0, j1;
+};
+struct StreamTimeline {
+    std::vector<int64_t> place, len;
+    int64_t joined = 0;
+    std::vector<StreamCall> calls;
+};
+int64_t stream_min_gap(const PcmFmtSpec& spec);   // 2 ceil(half / L): no output sample on one side of a cut has a filter tap on the other side's row
+void stream_check_gaps(const int64_t* gap_after, int64_t n, const PcmFmtSpec& spec);
+StreamTimeline stream_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int hop, int64_t chunk_frames, const PcmFmtSpec& spec);
 struct VitsBatch {
     int n = 0;
     const int64_t* t_lens = nullptr;   // [n]
@@ -311,10 +329,11 @@ class VitsModel {
     int device() const { return device_; }
     const VitsConfig& cfg() const { return cfg_; }
     void forward(const VitsBatch& b);
-    // Streaming long-form decode (BASELINE configs[4]) of the utterance of the last forward(skip_decoder = true, n = 1): the HiFi-GAN
-    // decoder runs on windows of chunk_frames + 2 * kStreamHalo frames, ONE hipGraph captured for that fixed shape and replayed per
-    // chunk; the workspace is bounded by the window.  stream_begin returns the number of frames; stream_chunk decodes frames
-    // [f0, f0 + chunk_frames) into dst (host) and returns the number of samples written.
+    // Streaming decode (BASELINE configs[4]) of the rows of the last forward(skip_decoder = true): the HiFi-GAN decoder runs on windows of
+    // chunk_frames + 2 * stream_halo() frames, ONE hipGraph captured for that fixed shape and replayed per burst of windows; the workspace is
+    // bounded by the window.  The stream's state is a global chunk list (stream_layout().calls): every row cut on its own frame grid, row after
+    // row; a replay takes the next windows of that list whatever rows they belong to.  stream_begin returns the number of calls; stream_chunk*
+    // deliver call ci (in order) into dst (host).  gap_after == nullptr: ONE row without gaps (the single-utterance streams).
     // halo frames per side = the generator's receptive field (from the config: 13.4 frames -> 16 for JP-Extra, SURVEY.md §5 "Long-context")
     int stream_halo() const;
     double stream_receptive_field() const;   // frames per side, before the margin and rounding of stream_halo
@@ -323,16 +342,20 @@ class VitsModel {
     // flac (fmt must be s16): the chunks' samples are not delivered but pushed into a FlacStreamEncoder (flac_encode.h) behind each replay
     // level (needs fmt): the formatter stops at y (f64), a StreamLimiter (limiter.h) takes it replay by replay at the fixed gain and holds the
     // ceiling; what it emits is cast / quantised and delivered (or, with flac, pushed into the encoder): delivery runs A samples behind
-    int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false, const StreamLevelSpec* level = nullptr);
-    int64_t stream_chunk(int64_t f0, float* dst_host, int64_t capacity);
-    // formatted stream: output samples of the chunk at f0 -> dst_host (capacity_bytes); returns the samples written
-    int64_t stream_chunk_format(int64_t f0, void* dst_host, int64_t capacity_bytes);
-    // FLAC stream: the bytes of every frame the chunk at f0 completes (the stream header before the first) -> dst_host, *n_bytes of them
+    // gap_after (needs fmt): [n] native samples of silence after each row of the forward, the rows joined as stream_timeline lays them out
+    int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false, const StreamLevelSpec* level = nullptr,
+                         const int64_t* gap_after = nullptr);
+    const StreamTimeline& stream_layout() const { return stl_; }
+    int64_t stream_call_bound() const;   // bytes that suffice for any one call of the running stream
+    int64_t stream_chunk(int64_t ci, float* dst_host, int64_t capacity);
+    // formatted stream: output samples of call ci -> dst_host (capacity_bytes); returns the samples written
+    int64_t stream_chunk_format(int64_t ci, void* dst_host, int64_t capacity_bytes);
+    // FLAC stream: the bytes of every frame call ci completes (the stream header before the first) -> dst_host, *n_bytes of them
     // (possibly 0); returns the s16 samples the chunk consumed.  Chunks in order only.
-    int64_t stream_chunk_flac(int64_t f0, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes);
-    // level stream: what the chunk at f0 completes -> dst_host; *n_out = samples written (bytes when FLAC; possibly 0); returns the samples
+    int64_t stream_chunk_flac(int64_t ci, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes);
+    // level stream: what call ci completes -> dst_host; *n_out = samples written (bytes when FLAC; possibly 0); returns the samples
     // of the chunk taken.  Chunks in order only.
-    int64_t stream_chunk_level(int64_t f0, void* dst_host, int64_t capacity_bytes, int64_t* n_out);
+    int64_t stream_chunk_level(int64_t ci, void* dst_host, int64_t capacity_bytes, int64_t* n_out);
     // level stream, after its last chunk was taken: 20 log10 min s and max |x| over the utterance
     void stream_level_stats(double* out) const;
     bool stream_graph_captured() const { return chunk_ && chunk_->exec != nullptr; }
@@ -446,8 +469,9 @@ class VitsModel {
         // chunk c + 1 is enqueued before the host waits for chunk c: two pinned host slots + events
         float* host[2] = {nullptr, nullptr};
         hipEvent_t ev[2] = {nullptr, nullptr};
-        int64_t slot_f0[2] = {-1, -1}, slot_n[2] = {0, 0};
+        int64_t slot_ci[2] = {-1, -1}, slot_n[2] = {0, 0};   // the first call of the replay a slot holds (-1: none), its samples
         size_t host_bytes = 0;                      // capacity of each pinned slot
+        int64_t fmt_cap = 0;                        // formatted stream: samples the running stream's largest replay of this plan delivers (+ A)
         std::vector<int64_t> fmt_off[2], fmt_n[2];  // formatted stream: each window's output samples in its slot (offset, count)
         FlacStreamEncoder::Push flac_push[2];       // FLAC stream: the slot's push (its pinned region is host[slot]) and, per window, the
         std::vector<int> flac_fr[2];                // frames of the push it completes: [flac_fr[w], flac_fr[w + 1])
@@ -462,11 +486,10 @@ class VitsModel {
         }
     };
     void ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, int nwin);
-    void stream_enqueue(ChunkPlan& c, int64_t f0, int slot);
+    void stream_enqueue(ChunkPlan& c, int64_t c0, int slot);   // the replay of calls c0 .. c0 + nwin - 1
     // flac_bytes: FLAC delivery; taken (level stream): receives the samples the chunk fed, the return value being what was delivered
-    int64_t stream_take(int64_t f0, void* dst_host, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes, int64_t* taken = nullptr);
-    int64_t stream_fmt_samples(const ChunkPlan& c) const;   // formatted output of one replay of c, upper bound
-    size_t stream_fmt_bytes(const ChunkPlan& c) const;
+    int64_t stream_take(int64_t ci, void* dst_host, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes, int64_t* taken = nullptr);
+    StreamTimeline stl_;                         // rows, placement and calls of the running stream
     bool sfmt_on_ = false;                       // the running stream is formatted (stream_begin with fmt)
     PcmFmtSpec sfmt_;
     std::shared_ptr<PcmFormatter> sfmtr_;          // its launches: slots 0 / 1 = chunk_'s, 2 / 3 = burst_'s

@@ -87,8 +87,23 @@ void noise_fill(float* out, int ld, int rows, const int* seg_of, const int* seg_
                 int stream_id, hipStream_t s);   // scaled by the row's noise_scale_w
 void expand_frames(Plane m_p, Plane logs_p, const int* tok_of_frame, const int* seg_of, const int* seg_start,
                    const int* seg_len, const RowOpts* opts, Plane out, hipStream_t s);   // prior noise scaled by the row's noise_scale
-// out[c][j] = in[c][col0 + j] or 0 outside the plane; mask[j] = 1 where the column exists (the chunk window of the streaming decoder)
-void window_cols(Plane in, int col0, Plane out, unsigned char* mask, hipStream_t s);
+// The windows of one replay of the streaming decoder, ONE launch.  Window w < nwin is described by tab.w[w]: its row's first column z0 in the
+// plane z, the row's length len in frames, the window's first frame `first` within the row (negative, or past the end, where the window
+// overhangs the row) and the row's index.  For j < W: out[c][out_start[w] + j] = z[c][z0 + first + j] where 0 <= first + j < len, else 0;
+// mask[out_start[w] + j] = that condition; cond[w][i] = cond_vec[row][i] for i < cond_dim (cond may be null: nothing is gathered).  A window
+// with len == 0 (past the end of the request) is all-zero with mask 0 and a zero cond.  The table travels BY VALUE as a kernel argument: no
+// pinned table is rewritten while an earlier replay may still read it.  out_start: device array [nwin] (the plan layout's d_start).
+constexpr int kStreamWinMax = 16;
+struct StreamWin {
+    int z0, len, first, row;
+};
+struct StreamWinTable {
+    StreamWin w[kStreamWinMax];
+};
+static_assert(sizeof(StreamWinTable) == 256, "the window table is a 256-byte kernel argument");
+// h_start: the same [nwin] starts on the host; every window must lie inside out (h_start[w] + W <= out.L, checked before the launch).
+void stream_windows(Plane z, const StreamWinTable& tab, int nwin, int W, const int* out_start, const int* h_start, Plane out, unsigned char* mask,
+                    const float* cond_vec, int cond_dim, float* cond, hipStream_t s);
 // dst[tab[3i + 1] + e] = src[tab[3i] + e] for e < tab[3i + 2], i < n (device table)
 void copy_segments(const float* src, float* dst, const int64_t* d_table, int n, hipStream_t s);
 void conv_post_tanh(Plane x, const float* w, int k, float slope, const int* seg_start, const int* seg_len,

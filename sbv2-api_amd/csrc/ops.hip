@@ -990,19 +990,28 @@ void conv_post_tanh_cl(const float* x, int C, int64_t L, const float* w, int k, 
 void fill_zero(void* p, size_t bytes, hipStream_t s) { HIP_CHECK(hipMemsetAsync(p, 0, bytes, s)); }
 
 // ------------------------------------------------------------------------------------------------
-// Streaming decode: out[c][j] = in[c][col0 + j] (0 outside [0, in.L)), mask[j] = column col0 + j exists; out.L columns
+// Streaming decode: the windows of one replay (ops.h stream_windows).  grid = (ceil(W / 256), C, nwin); the first block of every window
+// also gathers its conditioning vector
 // ------------------------------------------------------------------------------------------------
-__global__ void k_window_cols(Plane in, int col0, Plane out, unsigned char* mask) {
+__global__ __launch_bounds__(256) void k_stream_windows(Plane z, StreamWinTable tab, int W, const int* out_start, Plane out, unsigned char* mask,
+                                                       const float* cond_vec, int cond_dim, float* cond) {
+    const int w = blockIdx.z, c = blockIdx.y;
+    const StreamWin t = tab.w[w];
+    if (cond && blockIdx.x == 0 && c == 0)
+        for (int i = threadIdx.x; i < cond_dim; i += 256) cond[(size_t)w * cond_dim + i] = t.len > 0 ? cond_vec[(size_t)t.row * cond_dim + i] : 0.f;
     const int j = blockIdx.x * 256 + threadIdx.x;
-    const int c = blockIdx.y;
-    if (j >= out.L) return;
-    const int q = col0 + j;
-    const bool ok = q >= 0 && q < in.L;
-    out.p[(size_t)c * out.ld + j] = ok ? in.p[(size_t)c * in.ld + q] : 0.f;
-    if (c == 0 && mask) mask[j] = ok ? 1 : 0;
+    if (j >= W) return;
+    const int q = t.first + j, o = out_start[w] + j;
+    const bool ok = q >= 0 && q < t.len;
+    out.p[(size_t)c * out.ld + o] = ok ? z.p[(size_t)c * z.ld + t.z0 + q] : 0.f;
+    if (c == 0) mask[o] = ok ? 1 : 0;
 }
-void window_cols(Plane in, int col0, Plane out, unsigned char* mask, hipStream_t s) {
-    hipLaunchKernelGGL(k_window_cols, dim3((out.L + 255) / 256, out.C), dim3(256), 0, s, in, col0, out, mask);
+void stream_windows(Plane z, const StreamWinTable& tab, int nwin, int W, const int* out_start, const int* h_start, Plane out, unsigned char* mask,
+                    const float* cond_vec, int cond_dim, float* cond, hipStream_t s) {
+    SBV2_REQUIRE(nwin >= 1 && nwin <= kStreamWinMax && W >= 1 && out.C == z.C && h_start, "stream_windows: bad window plan");
+    for (int w = 0; w < nwin; ++w)   // the kernel writes out and mask at [h_start[w], h_start[w] + W) unchecked
+        SBV2_REQUIRE(h_start[w] >= 0 && (int64_t)h_start[w] + W <= out.L, "stream_windows: window " + std::to_string(w) + " lies outside the output plane");
+    hipLaunchKernelGGL(k_stream_windows, dim3((W + 255) / 256, out.C, nwin), dim3(256), 0, s, z, tab, W, out_start, out, mask, cond_vec, cond_dim, cond);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -5,15 +5,18 @@
 // of the work and all of the output bytes, is purely convolutional and runs on fixed-size frame windows (chunk + 16-frame halo per side),
 // one hipGraph captured per window shape and replayed per chunk (VitsModel::stream_begin / stream_chunk, vits.cpp).  The first PCM is
 // available after the flow + ONE chunk instead of after the whole decoder, and the decoder workspace is bounded by the window.
+// A request stream (sbv2_stream_begin_request) is the same over the n rows of ONE batched forward: the rows on a silent timeline, each cut into
+// chunks on its own frame grid, delivered row after row; the single-utterance streams are its n = 1 case (begin_stream below).
 #include "api_internal.h"
 
 struct sbv2_stream {
     sbv2_bert* bert = nullptr;
     sbv2_vits* vits = nullptr;
-    int64_t frames = 0, next = 0, chunk = 0;
+    int64_t calls = 0, next = 0;   // the stream's calls (its rows' chunks, row after row) and the next one to deliver
     bool formatted = false, flac = false, level = false;
-    // speech marks (sbv2_stream_marks): the utterance's expanded durations, on the host since the forward's one sync, and the delivered format
-    std::vector<int64_t> durations;
+    // speech marks (sbv2_stream_marks): the rows' expanded durations (row i's tokens are [offs[i], offs[i + 1])), on the host since the forward's
+    // one sync, and the delivered format
+    std::vector<int64_t> durations, offs;
     PcmFmtSpec spec;
 };
 
@@ -24,6 +27,28 @@ PcmFmtSpec flac_stream_spec(const sbv2_pcm_format* fmt) {
     SBV2_REQUIRE(spec.encoding == kEncS16, "FLAC needs encoding = 1 (s16): f32 samples and G.711 codes have no FLAC form");
     SBV2_REQUIRE(!spec.normalize, "a FLAC stream cannot normalise (normalize must be 0): the peak of the utterance is not known ahead");
     return spec;
+}
+
+// The one path behind every sbv2_stream_begin*: the forward of the batch's rows with skip_decoder, then the stream over them.  spec == nullptr:
+// a plain stream (native f32, one row); gap_after == nullptr: one row without gaps.  Every check of the arguments has happened before.
+void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
+                  int64_t chunk_frames, const PcmFmtSpec* spec, bool flac, const StreamLevelSpec* level, const int64_t* gap_after, sbv2_stream** out,
+                  int64_t* total_samples) {
+    VitsBatch run = v;
+    run.skip_decoder = true;
+    pipeline_run_one(*bert->m, *vits->m, run, token_ids, s_lens, word2ph);
+    std::unique_ptr<sbv2_stream> s(new sbv2_stream);
+    s->bert = bert;
+    s->vits = vits;
+    s->durations = vits->m->used_durations();
+    s->offs = vits->m->used_offs();
+    if (spec) s->spec = *spec;
+    s->formatted = spec != nullptr;
+    s->flac = flac;
+    s->level = level != nullptr;
+    s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after);
+    if (total_samples) *total_samples = pcm_format_out_len(s->spec, vits->m->stream_layout().joined);
+    *out = s.release();
 }
 }  // namespace
 
@@ -38,17 +63,7 @@ int sbv2_stream_begin(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch,
     SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
     SBV2_REQUIRE(batch->n == 1, "sbv2_stream_begin takes one utterance");
     SBV2_REQUIRE(bert->m->device() == vits->m->device(), "bert and vits handles live on different devices");
-    VitsBatch v = to_batch(batch);
-    v.skip_decoder = true;
-    pipeline_run_one(*bert->m, *vits->m, v, token_ids, s_lens, word2ph);
-    std::unique_ptr<sbv2_stream> s(new sbv2_stream);
-    s->bert = bert;
-    s->vits = vits;
-    s->chunk = chunk_frames;
-    s->durations = vits->m->used_durations();
-    s->frames = vits->m->stream_begin((int)chunk_frames);
-    if (total_samples) *total_samples = s->frames * vits->m->cfg().hop();
-    *out = s.release();
+    begin_stream(bert, vits, to_batch(batch), token_ids, s_lens, word2ph, chunk_frames, nullptr, false, nullptr, nullptr, out, total_samples);
     API_END
 }
 
@@ -61,9 +76,9 @@ int sbv2_stream_next(sbv2_stream* s, float* dst, int64_t capacity, int64_t* n) {
     SBV2_REQUIRE(!s->flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
     SBV2_REQUIRE(!s->formatted, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
     *n = 0;
-    if (s->next < s->frames) {
+    if (s->next < s->calls) {
         *n = s->vits->m->stream_chunk(s->next, dst, capacity);
-        s->next += s->chunk;
+        s->next += 1;
     }
     API_END
 }
@@ -77,19 +92,7 @@ int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch*
     SBV2_REQUIRE(bert->m->device() == vits->m->device(), "bert and vits handles live on different devices");
     const PcmFmtSpec spec = pcm_format_spec(fmt);
     SBV2_REQUIRE(!spec.normalize, "a formatted stream cannot normalise (normalize must be 0): the peak of the utterance is not known ahead");
-    VitsBatch v = to_batch(batch);
-    v.skip_decoder = true;
-    pipeline_run_one(*bert->m, *vits->m, v, token_ids, s_lens, word2ph);
-    std::unique_ptr<sbv2_stream> s(new sbv2_stream);
-    s->bert = bert;
-    s->vits = vits;
-    s->chunk = chunk_frames;
-    s->durations = vits->m->used_durations();
-    s->spec = spec;
-    s->formatted = true;
-    s->frames = vits->m->stream_begin((int)chunk_frames, &spec);
-    if (total_samples) *total_samples = pcm_format_out_len(spec, s->frames * vits->m->cfg().hop());
-    *out = s.release();
+    begin_stream(bert, vits, to_batch(batch), token_ids, s_lens, word2ph, chunk_frames, &spec, false, nullptr, nullptr, out, total_samples);
     API_END
 }
 
@@ -100,9 +103,9 @@ int sbv2_stream_next_format(sbv2_stream* s, void* dst, int64_t capacity_bytes, i
     SBV2_REQUIRE(!s->flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
     SBV2_REQUIRE(s->formatted, "this stream has no output format: take its chunks with sbv2_stream_next");
     *n = 0;
-    if (s->next < s->frames) {
+    if (s->next < s->calls) {
         *n = s->vits->m->stream_chunk_format(s->next, dst, capacity_bytes);
-        s->next += s->chunk;
+        s->next += 1;
     }
     API_END
 }
@@ -128,19 +131,7 @@ int sbv2_stream_begin_flac(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* b
     SBV2_REQUIRE(batch->n == 1, "sbv2_stream_begin_flac takes one utterance");
     SBV2_REQUIRE(bert->m->device() == vits->m->device(), "bert and vits handles live on different devices");
     const PcmFmtSpec spec = flac_stream_spec(fmt);
-    VitsBatch v = to_batch(batch);
-    v.skip_decoder = true;
-    pipeline_run_one(*bert->m, *vits->m, v, token_ids, s_lens, word2ph);
-    std::unique_ptr<sbv2_stream> s(new sbv2_stream);
-    s->bert = bert;
-    s->vits = vits;
-    s->chunk = chunk_frames;
-    s->durations = vits->m->used_durations();
-    s->spec = spec;
-    s->formatted = s->flac = true;
-    s->frames = vits->m->stream_begin((int)chunk_frames, &spec, true);
-    if (total_samples) *total_samples = pcm_format_out_len(spec, s->frames * vits->m->cfg().hop());
-    *out = s.release();
+    begin_stream(bert, vits, to_batch(batch), token_ids, s_lens, word2ph, chunk_frames, &spec, true, nullptr, nullptr, out, total_samples);
     API_END
 }
 
@@ -152,9 +143,9 @@ int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, 
     SBV2_REQUIRE(!s->level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
     SBV2_REQUIRE(s->flac, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
     *n_bytes = *n_samples = 0;
-    if (s->next < s->frames) {
+    if (s->next < s->calls) {
         *n_samples = s->vits->m->stream_chunk_flac(s->next, dst, capacity_bytes, n_bytes);
-        s->next += s->chunk;
+        s->next += 1;
     }
     API_END
 }
@@ -199,20 +190,7 @@ int sbv2_stream_begin_level(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* 
     const PcmFmtSpec spec = flac ? flac_stream_spec(fmt) : pcm_format_spec(fmt);
     SBV2_REQUIRE(!spec.normalize, "a level stream cannot normalise (normalize must be 0): the peak of the utterance is not known ahead");
     const StreamLevelSpec lv = stream_level_spec(level);
-    VitsBatch v = to_batch(batch);
-    v.skip_decoder = true;
-    pipeline_run_one(*bert->m, *vits->m, v, token_ids, s_lens, word2ph);
-    std::unique_ptr<sbv2_stream> s(new sbv2_stream);
-    s->bert = bert;
-    s->vits = vits;
-    s->chunk = chunk_frames;
-    s->durations = vits->m->used_durations();
-    s->spec = spec;
-    s->formatted = s->level = true;
-    s->flac = flac != 0;
-    s->frames = vits->m->stream_begin((int)chunk_frames, &spec, flac != 0, &lv);
-    if (total_samples) *total_samples = pcm_format_out_len(spec, s->frames * vits->m->cfg().hop());
-    *out = s.release();
+    begin_stream(bert, vits, to_batch(batch), token_ids, s_lens, word2ph, chunk_frames, &spec, flac != 0, &lv, nullptr, out, total_samples);
     API_END
 }
 
@@ -223,12 +201,12 @@ int sbv2_stream_next_level(sbv2_stream* s, void* dst, int64_t capacity_bytes, in
     API_BEGIN
     SBV2_REQUIRE(s && dst && n_out && n_consumed, "bad arguments");
     SBV2_REQUIRE(s->level, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
-    if (s->next < s->frames) {
+    if (s->next < s->calls) {
         int64_t out = 0;
         const int64_t taken = s->vits->m->stream_chunk_level(s->next, dst, capacity_bytes, &out);
         *n_out = out;
         *n_consumed = taken;
-        s->next += s->chunk;
+        s->next += 1;
     } else {
         *n_out = *n_consumed = 0;
     }
@@ -240,23 +218,96 @@ int sbv2_stream_level_stats(sbv2_stream* s, double* stats) {
     API_BEGIN
     SBV2_REQUIRE(s && stats, "bad arguments");
     SBV2_REQUIRE(s->level, "this stream was not begun with a level");
-    SBV2_REQUIRE(s->next >= s->frames, "the level stats exist once the stream is complete: take its chunks to the end first");
+    SBV2_REQUIRE(s->next >= s->calls, "the level stats exist once the stream is complete: take its chunks to the end first");
     s->vits->m->stream_level_stats(stats);
     API_END
 }
 
-// Host only: the token spans of the stream's utterance at its delivered rate (marks.h; place 0).  Every duration is known once _begin* has
-// returned, so the whole timing is there before the first chunk is decoded.
+// Host only: the token spans of the stream's rows at its delivered rate (marks.h), row i at place[i] of the stream's timeline, in row order
+// then token order: what sbv2_pipeline_fetch_request_marks gives for the joined fetch.  Every duration is known once _begin* has returned, so
+// the whole timing is there before the first chunk is decoded.
 int sbv2_stream_marks(sbv2_stream* s, int64_t* tok_start, int64_t* tok_end, int64_t capacity, int64_t* n_tokens) {
     API_BEGIN
     SBV2_REQUIRE(s && n_tokens, "bad arguments");
     const int64_t n = (int64_t)s->durations.size();
     SBV2_REQUIRE(capacity >= n, "token arrays too small: " + std::to_string(capacity) + " < " + std::to_string(n) + " tokens");
     SBV2_REQUIRE(n == 0 || (tok_start && tok_end), "bad arguments");
-    marks_spans(s->durations.data(), n, s->vits->m->cfg().hop(), 0, s->spec, tok_start, tok_end);
+    const StreamTimeline& t = s->vits->m->stream_layout();
+    for (size_t i = 0; i + 1 < s->offs.size(); ++i) {
+        const int64_t o = s->offs[i];
+        marks_spans(s->durations.data() + o, s->offs[i + 1] - o, s->vits->m->cfg().hop(), t.place[i], s->spec, tok_start + o, tok_end + o);
+    }
     *n_tokens = n;
     API_END
 }
+
+// ---- a stream over the n rows of ONE batched forward (the contract above sbv2_stream_begin_request, include/sbv2_hip.h) ----
+// Host only: the smallest gap between two rows at fmt's rate, 2 ceil(half / L) native samples (NULL = the identity format = 0; -1: bad fmt)
+int64_t sbv2_stream_min_gap(const sbv2_pcm_format* fmt) {
+    try {
+        return fmt ? stream_min_gap(pcm_format_spec(fmt)) : 0;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// Host only: placement, joined length and per-call sample counts of a request stream (stream_timeline, vits.cpp: the library's own arithmetic)
+int sbv2_stream_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int32_t hop, int64_t chunk_frames, const sbv2_pcm_format* fmt,
+                         int64_t* place, int64_t* joined_len, int64_t* call_samples, int64_t capacity, int64_t* n_calls) {
+    API_BEGIN
+    const PcmFmtSpec spec = fmt ? pcm_format_spec(fmt) : PcmFmtSpec();
+    const StreamTimeline t = stream_timeline(frames, gap_after, n, hop, chunk_frames, spec);
+    const int64_t calls = (int64_t)t.calls.size();
+    if (n_calls) *n_calls = calls;
+    SBV2_REQUIRE(!call_samples || capacity >= calls, "call_samples too small: " + std::to_string(capacity) + " < " + std::to_string(calls) + " calls");
+    if (place) std::copy(t.place.begin(), t.place.end(), place);
+    if (joined_len) *joined_len = t.joined;
+    if (call_samples)
+        for (int64_t c = 0; c < calls; ++c) call_samples[c] = t.calls[c].j1 - t.calls[c].j0;
+    API_END
+}
+
+int sbv2_stream_begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids,
+                              const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq, sbv2_stream** out,
+                              int64_t* total_samples) {
+    API_BEGIN
+    SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
+    SBV2_REQUIRE(rq, "no sbv2_stream_request given");
+    SBV2_REQUIRE(rq->gap_after, "sbv2_stream_request.gap_after must not be NULL (one entry per row, the last one = trailing silence)");
+    SBV2_REQUIRE(batch->n >= 1, "sbv2_stream_begin_request takes at least one row");
+    SBV2_REQUIRE(rq->reserved == 0, "sbv2_stream_request.reserved must be 0");
+    SBV2_REQUIRE(rq->flac == 0 || rq->flac == 1, "sbv2_stream_request.flac must be 0 or 1");
+    SBV2_REQUIRE(bert->m->device() == vits->m->device(), "bert and vits handles live on different devices");
+    SBV2_REQUIRE(!rq->flac || rq->fmt, "FLAC needs encoding = 1 (s16): the identity format (fmt NULL) is f32");
+    const PcmFmtSpec spec = rq->flac ? flac_stream_spec(rq->fmt) : rq->fmt ? pcm_format_spec(rq->fmt) : PcmFmtSpec();
+    SBV2_REQUIRE(!spec.normalize, "a request stream cannot normalise (normalize must be 0): the peak of the signal is not known ahead");
+    StreamLevelSpec lv;
+    if (rq->level) lv = stream_level_spec(rq->level);
+    VitsBatch v = to_batch(batch);
+    apply_utt_options(&v, opts);
+    stream_check_gaps(rq->gap_after, batch->n, spec);
+    begin_stream(bert, vits, v, token_ids, s_lens, word2ph, chunk_frames, &spec, rq->flac != 0, rq->level ? &lv : nullptr, rq->gap_after, out,
+                 total_samples);
+    API_END
+}
+
+// Host only, valid from begin onwards: where the stream's rows lie (place[i], pcm_lens[i] native samples) and the timeline's length
+int sbv2_stream_layout(const sbv2_stream* s, int64_t* place, int64_t* pcm_lens, int64_t capacity, int64_t* n, int64_t* joined_len) {
+    API_BEGIN
+    SBV2_REQUIRE(s, "bad arguments");
+    const StreamTimeline& t = s->vits->m->stream_layout();
+    const int64_t rows = (int64_t)t.place.size();
+    if (n) *n = rows;
+    SBV2_REQUIRE((!place && !pcm_lens) || capacity >= rows, "row arrays too small: " + std::to_string(capacity) + " < " + std::to_string(rows) + " rows");
+    if (place) std::copy(t.place.begin(), t.place.end(), place);
+    if (pcm_lens) std::copy(t.len.begin(), t.len.end(), pcm_lens);
+    if (joined_len) *joined_len = t.joined;
+    API_END
+}
+
+// Host only: bytes that suffice for any one sbv2_stream_next* call of THIS stream (-1: no stream)
+int64_t sbv2_stream_call_bound(const sbv2_stream* s) { return s ? s->vits->m->stream_call_bound() : -1; }
 
 // 1 when the decoder of this stream replays a captured hipGraph (0: eager launches, SBV2_STREAM_GRAPH=0)
 int sbv2_stream_uses_graph(const sbv2_stream* s) { return s && s->vits->m->stream_graph_captured() ? 1 : 0; }

@@ -1458,13 +1458,17 @@ int sbv2_debug_plane_op(int device, int op, const float* x, int64_t C, int64_t L
         HIP_CHECK(hipMemcpy(h.data(), dy.p, 4 * h.size(), hipMemcpyDeviceToHost));
         std::memcpy(y, h.data(), 4 * (size_t)(b * C));
         for (int64_t e = b * C; e < b * C + kGuard; ++e) bad += h[e] != kSentinelWord;
-    } else if (op == 2) {   // window_cols: col0 = a (any sign), width = b, y [C][b], mask_out [b]
+    } else if (op == 2) {   // one window of stream_windows over the whole plane: first column a (any sign), width = b, y [C][b], mask_out [b]
         SBV2_REQUIRE(b >= 1 && mask_out && a > -(1 << 28) && a < (1 << 28), "bad arguments");
         DevPlane Y(C, b);
         Y.fill(true);
-        DevMem dm((size_t)round_up((int)b, 64));
+        DevMem dm((size_t)round_up((int)b, 64)), d0(sizeof(int));
         HIP_CHECK(hipMemset(dm.p, kCtxSentinel, (size_t)round_up((int)b, 64)));
-        window_cols(X.P, (int)a, Y.P, dm.u8(), nullptr);
+        HIP_CHECK(hipMemset(d0.p, 0, sizeof(int)));
+        StreamWinTable tab{};
+        tab.w[0] = StreamWin{0, (int)L, (int)a, 0};
+        const int h0 = 0;
+        stream_windows(X.P, tab, 1, (int)b, static_cast<const int*>(d0.p), &h0, Y.P, dm.u8(), nullptr, 0, nullptr, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
         bad = Y.get(y, kSentinelWord);
         std::vector<unsigned char> hm((size_t)round_up((int)b, 64));
@@ -1484,6 +1488,58 @@ int sbv2_debug_plane_op(int device, int op, const float* x, int64_t C, int64_t L
         bad = X.get(y, kNanWord);
     }
     if (stray) *stray = bad;
+    API_END
+}
+
+int sbv2_debug_stream_windows(int device, const float* z, int64_t C, int64_t L, const int32_t* table, int64_t W, int64_t nwin, const float* cond_vecs,
+                              int64_t n_rows, int64_t cond_dim, float* z_out, uint8_t* mask_out, float* cond_out) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(z && table && cond_vecs && z_out && mask_out && cond_out, "bad arguments");
+    SBV2_REQUIRE(nwin >= 1 && nwin <= kStreamWinMax && W >= 1 && W < (1 << 20) && n_rows >= 1 && cond_dim >= 1 && cond_dim < (1 << 16), "bad window plan");
+    StreamWinTable tab{};
+    for (int64_t w = 0; w < nwin; ++w) {   // every read the launch can make lies inside the plane and the cond table
+        const int32_t *t = table + 4 * w, z0 = t[0], len = t[1], first = t[2], row = t[3];
+        SBV2_REQUIRE(z0 >= 0 && len >= 0 && (int64_t)z0 + len <= L && first > -(1 << 28) && first < (1 << 28) && row >= 0 && row < n_rows,
+                     "window " + std::to_string(w) + " of the table lies outside the plane");
+        tab.w[w] = StreamWin{z0, len, first, row};
+    }
+    DevPlane X(C, L);
+    X.put(z, true);
+    // the windows lie kGuard columns apart in one output plane; everything else holds the sentinel and must still hold it afterwards
+    constexpr int kGuard = 64;
+    const int pitch = round_up((int)W, 4) + kGuard;
+    const int64_t Lo = kGuard + (int64_t)nwin * pitch;
+    std::vector<int> start((size_t)nwin);
+    for (int64_t w = 0; w < nwin; ++w) start[w] = kGuard + (int)w * pitch;
+    DevPlane Y(C, Lo);
+    Y.fill(true);
+    const size_t ncond = (size_t)(nwin * cond_dim);
+    DevMem dstart(start.data(), sizeof(int) * (size_t)nwin), dm((size_t)Lo), dc(sizeof(float) * (ncond + 2 * kGuard)),
+        dv(cond_vecs, sizeof(float) * (size_t)(n_rows * cond_dim));
+    HIP_CHECK(hipMemset(dm.p, kCtxSentinel, (size_t)Lo));
+    HIP_CHECK(hipMemset(dc.p, kCtxSentinel, sizeof(float) * (ncond + 2 * kGuard)));
+    stream_windows(X.P, tab, (int)nwin, (int)W, static_cast<const int*>(dstart.p), start.data(), Y.P, dm.u8(), dv.f(), (int)cond_dim, dc.f() + kGuard, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<uint32_t> hy((size_t)C * Lo), hc(ncond + 2 * kGuard);
+    std::vector<unsigned char> hm((size_t)Lo);
+    int64_t bad = Y.get(hy.data(), kSentinelWord);
+    HIP_CHECK(hipMemcpy(hm.data(), dm.p, hm.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(hc.data(), dc.p, 4 * hc.size(), hipMemcpyDeviceToHost));
+    std::vector<unsigned char> inside((size_t)Lo, 0);
+    for (int64_t w = 0; w < nwin; ++w) std::memset(&inside[(size_t)start[w]], 1, (size_t)W);
+    for (int64_t n = 0; n < Lo; ++n) {
+        if (inside[n]) continue;
+        bad += hm[n] != kCtxSentinel;
+        for (int64_t c = 0; c < C; ++c) bad += hy[(size_t)c * Lo + n] != kSentinelWord;
+    }
+    for (int i = 0; i < kGuard; ++i) bad += (hc[i] != kSentinelWord) + (hc[kGuard + ncond + i] != kSentinelWord);
+    SBV2_REQUIRE(bad == 0, "stream_windows wrote " + std::to_string(bad) + " words or bytes outside its output");
+    for (int64_t w = 0; w < nwin; ++w) {
+        for (int64_t c = 0; c < C; ++c) std::memcpy(z_out + (size_t)((w * C + c) * W), &hy[(size_t)c * Lo + start[w]], 4 * (size_t)W);
+        std::memcpy(mask_out + (size_t)(w * W), &hm[(size_t)start[w]], (size_t)W);
+    }
+    std::memcpy(cond_out, hc.data() + kGuard, 4 * ncond);
     API_END
 }
 

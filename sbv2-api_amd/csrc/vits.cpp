@@ -889,6 +889,7 @@ void VitsModel::ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, 
         c.zin = c.ar.plane(cfg_.inter, c.lay.L);
         fill_zero(c.zin.p, sizeof(float) * (size_t)c.zin.C * c.zin.ld, stream_);
         c.cond = c.ar.array<float>((size_t)cfg_.up_initial * nwin);
+        fill_zero(c.cond, sizeof(float) * (size_t)cfg_.up_initial * nwin, stream_);
         c.mark = c.ar.mark();
         for (int i = 0; i < 2; ++i) {
             HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.host[i]), sizeof(float) * (size_t)nwin * chunk_frames * cfg_.hop(), hipHostMallocDefault));
@@ -897,9 +898,8 @@ void VitsModel::ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, 
         }
     }
     ChunkPlan& c = *slot;
-    // the speaker conditioning vector of THIS utterance goes into the plan's persistent buffer (the captured launches read it there), once per window
-    for (int w = 0; w < nwin; ++w)
-        HIP_CHECK(hipMemcpyAsync(c.cond + (size_t)w * cfg_.up_initial, dec_cond_vec_, sizeof(float) * (size_t)cfg_.up_initial, hipMemcpyDeviceToDevice, stream_));
+    // (the conditioning vectors of the windows' rows reach c.cond with every replay's stream_windows launch: the captured launches read them there;
+    // the warm-up and the capture below run on whatever the buffers hold, their output is never used)
     if (!c.exec && !no_graph) {
         // warm-up pass (sizes the arena: no hipMalloc may happen under capture), then the same launch sequence under capture
         auto decode = [&]() {
@@ -930,12 +930,55 @@ void VitsModel::ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, 
         HIP_CHECK(hipStreamSynchronize(stream_));
         c.ar.reset_pinned();
     }
-    c.slot_f0[0] = c.slot_f0[1] = -1;
+    c.slot_ci[0] = c.slot_ci[1] = -1;
 }
 
-int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac, const StreamLevelSpec* level) {
+// ---- the timeline of a stream over the n rows of one forward (sbv2_stream_timeline, include/sbv2_hip.h) ----
+int64_t stream_min_gap(const PcmFmtSpec& spec) { return 2 * (((int64_t)spec.half + spec.L - 1) / spec.L); }
+
+void stream_check_gaps(const int64_t* gap_after, int64_t n, const PcmFmtSpec& spec) {
+    SBV2_REQUIRE(gap_after, "no gap_after given (one entry per row, the last one = trailing silence)");
+    SBV2_REQUIRE(n >= 1, "a stream needs at least one row");
+    const int64_t need = stream_min_gap(spec);
+    for (int64_t i = 0; i < n; ++i) {
+        SBV2_REQUIRE(gap_after[i] >= 0 && gap_after[i] <= kStreamMaxGap, "gap_after[" + std::to_string(i) + "] = " + std::to_string(gap_after[i]) +
+                                                                              " is outside [0, " + std::to_string(kStreamMaxGap) + "] native samples");
+        SBV2_REQUIRE(i == n - 1 || gap_after[i] >= need, "gap_after[" + std::to_string(i) + "] = " + std::to_string(gap_after[i]) +
+                                                             " is below the minimum gap of " + std::to_string(need) + " native samples at " +
+                                                             std::to_string(spec.rate) + " Hz (the resampling filter must not reach across a cut)");
+    }
+}
+
+StreamTimeline stream_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int hop, int64_t chunk_frames, const PcmFmtSpec& spec) {
+    stream_check_gaps(gap_after, n, spec);
+    SBV2_REQUIRE(frames && hop >= 1 && chunk_frames >= 1 && n < (1 << 20), "bad timeline arguments");
+    StreamTimeline t;
+    int64_t pos = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        SBV2_REQUIRE(frames[i] >= 1 && frames[i] < (1 << 28), "row " + std::to_string(i) + " has " + std::to_string(frames[i]) + " frames");
+        t.place.push_back(pos);
+        t.len.push_back(frames[i] * hop);
+        pos += frames[i] * hop + gap_after[i];
+    }
+    t.joined = pos;
+    int64_t cut = 0;   // m_{i-1}: where the previous row's last call ended
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t end = i == n - 1 ? t.joined : t.place[i] + t.len[i] + gap_after[i] / 2;
+        for (int64_t f0 = 0; f0 < frames[i]; f0 += chunk_frames) {
+            const bool last = f0 + chunk_frames >= frames[i];
+            const int64_t a = f0 == 0 ? cut : t.place[i] + f0 * hop, b = last ? end : t.place[i] + (f0 + chunk_frames) * hop;
+            t.calls.push_back(StreamCall{(int)i, f0, pcm_format_out_len(spec, a), pcm_format_out_len(spec, b)});
+        }
+        cut = end;
+    }
+    return t;
+}
+
+int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac, const StreamLevelSpec* level, const int64_t* gap_after) {
     HIP_CHECK(hipSetDevice(device_));
-    SBV2_REQUIRE(fl_.n == 1 && z_.p, "stream_begin needs a preceding forward of ONE utterance with skip_decoder");
+    SBV2_REQUIRE(fl_.n >= 1 && z_.p, "stream_begin needs a preceding forward with skip_decoder");
+    SBV2_REQUIRE(gap_after || fl_.n == 1, "stream_begin without gaps needs a preceding forward of ONE utterance");
+    SBV2_REQUIRE(!gap_after || fmt, "a stream over several rows is a formatted stream");
     SBV2_REQUIRE(chunk_frames >= 16 && chunk_frames <= (1 << 20), "chunk_frames must be in [16, 2^20]");
     sfmt_on_ = sflac_on_ = slevel_on_ = false;
     slevel_A_ = 0;
@@ -949,19 +992,26 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
         const double exact = (stream_halo() - stream_receptive_field()) * cfg_.hop();
         SBV2_REQUIRE((double)reach <= exact, "the " + std::to_string(fmt->rate) + " Hz filter reaches " + std::to_string(reach) +
                                                  " samples past a chunk edge, the stream halo holds only " + std::to_string((int64_t)exact) + " exact samples");
+    }
+    // the global chunk list: every row cut on its own frame grid, the calls in row order then chunk order (a single utterance: one row, no gap)
+    const int64_t no_gap = 0;
+    const std::vector<int64_t> frames(fl_.len.begin(), fl_.len.end());
+    stl_ = stream_timeline(frames.data(), gap_after ? gap_after : &no_gap, fl_.n, cfg_.hop(), chunk_frames, fmt ? *fmt : PcmFmtSpec());
+    if (fmt) {
         sfmt_ = *fmt;
         if (!sfmtr_) sfmtr_ = std::make_shared<PcmFormatter>();
         if (level) slevel_A_ = stream_level_lookahead(fmt->rate);   // (sizes the slots below: a replay may hand back A samples more than it fed)
     }
     constexpr int burst = kStreamBurst;   // (1 / 2 / 4 / 8 / 12 / 16 windows per replay measured in round 3: 2.62 / 1.88 / 1.64 / 1.41 / 1.39 / 1.47 ms per chunk)
-    const int64_t Tf = fl_.len[0];
+    static_assert(kStreamBurst <= kStreamWinMax, "a replay's window table holds kStreamWinMax windows");
+    const int64_t ncalls = (int64_t)stl_.calls.size();
     ensure_plan(chunk_, chunk_frames, 1);
-    const bool want_burst = burst > 1 && Tf > chunk_frames;   // an utterance of one chunk never needs it
+    const bool want_burst = burst > 1 && ncalls > 1;   // a request of one chunk never needs it
     if (want_burst) {
         // windows per replay: no more than the chunks that follow the first one (a 2-chunk utterance does not decode 7 all-zero windows, nor pay
         // their workspace: 256 MiB per window at 256-frame chunks), from {2, 4, 8, 16} so that utterances of different lengths share few captures;
         // a larger plan of the same chunk size that this handle already holds is reused as it is
-        const int64_t rest = (Tf - 1) / chunk_frames;
+        const int64_t rest = ncalls - 1;
         int nw = 2;
         while (nw < burst && nw < rest) nw *= 2;
         nw = std::min(nw, burst);
@@ -969,12 +1019,17 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
         ensure_plan(burst_, chunk_frames, nw);
     }
     stream_bursts_ = want_burst;
-    if (fmt) {   // pinned slots and the device output sized for the format (f32 at 48 kHz is larger than native)
+    if (fmt) {   // pinned slots and the device output sized from the timeline: the largest replay of each plan, gaps included (+ A with a level)
         size_t dev = 0;
         for (ChunkPlan* c : {chunk_.get(), want_burst ? burst_.get() : nullptr}) {
             if (!c) continue;
-            const size_t need = flac ? FlacStreamEncoder::host_bytes(stream_fmt_samples(*c)) : stream_fmt_bytes(*c);
-            dev = std::max(dev, stream_fmt_bytes(*c));
+            const bool is_burst = want_burst && c == burst_.get();   // (with bursts the single-window plan decodes call 0 only)
+            int64_t most = 0;
+            for (int64_t c0 = is_burst ? 1 : 0; c0 < (want_burst && !is_burst ? 1 : ncalls); c0 += c->nwin)
+                most = std::max(most, stl_.calls[std::min<int64_t>(c0 + c->nwin, ncalls) - 1].j1 - stl_.calls[c0].j0);
+            c->fmt_cap = most + slevel_A_;
+            const size_t need = flac ? FlacStreamEncoder::host_bytes(c->fmt_cap) : (size_t)c->fmt_cap * sfmt_.bytes();
+            dev = std::max(dev, (size_t)c->fmt_cap * sfmt_.bytes());
             if (need > c->host_bytes) {
                 HIP_CHECK(hipStreamSynchronize(stream_));
                 for (int i = 0; i < 2; ++i) {
@@ -986,38 +1041,42 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
                 c->host_bytes = need;
             }
         }
+        const int64_t total_out = pcm_format_out_len(sfmt_, stl_.joined);
         if (flac) {   // the replays' s16 samples go straight behind the encoder's carried tail instead (stream_enqueue)
             if (!sflac_) sflac_ = std::make_shared<FlacStreamEncoder>();
-            sflac_->begin(sfmt_.rate, pcm_format_out_len(sfmt_, Tf * cfg_.hop()), (int64_t)(dev / sfmt_.bytes()), stream_);
+            sflac_->begin(sfmt_.rate, total_out, (int64_t)(dev / sfmt_.bytes()), stream_);
             sflac_on_ = true;
         } else {
             sfmtr_->out_buffer(dev, stream_);
         }
         if (level) {   // the formatter's y goes behind the limiter's carried tail, what the limiter emits to one of the two sinks above
             if (!slim_) slim_ = std::make_shared<StreamLimiter>();
-            slim_->begin(sfmt_.rate, pcm_format_out_len(sfmt_, Tf * cfg_.hop()), (int64_t)(dev / sfmt_.bytes()), *level, stream_);
+            slim_->begin(sfmt_.rate, total_out, (int64_t)(dev / sfmt_.bytes()), *level, stream_);
             slevel_on_ = true;
         }
         sfmt_on_ = true;
     }
-    stream_enqueue(*chunk_, 0, 0);                            // the first chunk starts right behind the flow ...
-    if (want_burst) stream_enqueue(*burst_, chunk_frames, 0); // ... and the first burst right behind it
-    return Tf;
+    stream_enqueue(*chunk_, 0, 0);                 // the first chunk starts right behind the flow ...
+    if (want_burst) stream_enqueue(*burst_, 1, 0); // ... and the first burst right behind it
+    return ncalls;
 }
 
 // windows + decoder (graph replay) + device -> pinned-host copies of the windows' centres, all asynchronous on the model's stream.
-// The plan's windows are the chunks starting at f0, f0 + chunk, ... (windows past the end of the utterance decode zeros and are not copied).
-void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
-    const int64_t Tf = fl_.len[0];
+// The plan's windows are the calls c0, c0 + 1, ... of the global chunk list, whatever rows they belong to (windows past the end of the
+// request decode zeros and are not copied).
+void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
     const int hop = cfg_.hop(), halo = stream_halo();
-    // window w = frames [f0_w - halo, f0_w - halo + W) of this utterance (fl_.start[0] is its first column in the packed plane)
-    Plane zu = z_;
-    zu.p = z_.p + fl_.start[0];
-    zu.L = (int)Tf;
-    for (int w = 0; w < c.nwin; ++w) {
-        const int64_t fw = std::min<int64_t>(f0 + (int64_t)w * c.chunk, Tf + c.W);   // (past the end: an all-zero window)
-        window_cols(zu, (int)(fw - halo), Plane{c.zin.p + c.lay.start[w], c.zin.C, c.W, c.zin.ld}, c.lay.d_mask + c.lay.start[w], stream_);
+    const int64_t ncalls = (int64_t)stl_.calls.size();
+    const int live = (int)std::min<int64_t>(c.nwin, ncalls - c0);
+    // window w = frames [f0 - halo, f0 - halo + W) of its call's row (fl_.start[row] is the row's first column in the packed plane); ONE launch
+    // writes every window's z columns, column mask and conditioning vector, from a table passed by value
+    StreamWinTable tab{};
+    for (int w = 0; w < live; ++w) {
+        const StreamCall& k = stl_.calls[c0 + w];
+        tab.w[w] = StreamWin{fl_.start[k.row], fl_.len[k.row], (int)(k.f0 - halo), k.row};
     }
+    SBV2_REQUIRE((int)c.lay.start.size() >= c.nwin, "stream plan: fewer windows in the layout than in the plan");
+    stream_windows(z_, tab, c.nwin, c.W, c.lay.d_start, c.lay.start.data(), c.zin, c.lay.d_mask, dec_cond_vec_, cfg_.up_initial, c.cond, stream_);
     if (c.exec) {
         HIP_CHECK(hipGraphLaunch(c.exec, stream_));
     } else {
@@ -1027,30 +1086,32 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
         c.pcm = pcm_;
     }
     int64_t total = 0;
+    const bool last = c0 + c.nwin >= ncalls;
     if (sfmt_on_) {
-        // ONE formatting launch over the replay's windows: window w holds native samples [(fw - halo) hop, (fw - halo + W) hop) of the utterance,
-        // clipped to [0, N) (the decoder's output outside the utterance is not silence); its chunk [a, b) emits [ceil(a L / M), ceil(b L / M))
-        const int64_t N = Tf * hop;
+        // ONE formatting launch over the replay's windows: window w holds native samples [(f0 - halo) hop, (f0 - halo + W) hop) of its row, which
+        // lies at place[row] of the joined timeline; the piece is that PCM clipped to the row (the decoder's output outside a row is not silence);
+        // the call emits the output samples [j0, j1) of the timeline (stream_timeline: its chunk, and with a row's first / last chunk the half gaps)
         std::vector<FmtPiece> pieces;
         std::vector<FmtSignal> sig;
         c.fmt_off[slot].clear();
         c.fmt_n[slot].clear();
-        for (int w = 0; w < c.nwin; ++w) {
-            const int64_t fw = f0 + (int64_t)w * c.chunk;
-            if (fw >= Tf) break;
-            const int64_t ws = (fw - halo) * hop, lo = std::max<int64_t>(0, ws), hi = std::min<int64_t>(N, ws + (int64_t)c.W * hop);
+        for (int w = 0; w < live; ++w) {
+            const StreamCall& k = stl_.calls[c0 + w];
+            const int64_t r0 = stl_.place[k.row], r1 = r0 + stl_.len[k.row];
+            const int64_t ws = r0 + (k.f0 - halo) * hop, lo = std::max<int64_t>(r0, ws), hi = std::min<int64_t>(r1, ws + (int64_t)c.W * hop);
             pieces.push_back(FmtPiece{c.pcm + (size_t)w * c.W * hop + (lo - ws), lo, hi - lo});
-            const int64_t j0 = pcm_format_out_len(sfmt_, fw * hop), j1 = pcm_format_out_len(sfmt_, std::min<int64_t>(fw + c.chunk, Tf) * hop);
-            sig.push_back(FmtSignal{j0, j1, total, w, w + 1});
+            sig.push_back(FmtSignal{k.j0, k.j1, total, w, w + 1});
             c.fmt_off[slot].push_back(total);
-            c.fmt_n[slot].push_back(j1 - j0);
-            total += j1 - j0;
+            c.fmt_n[slot].push_back(k.j1 - k.j0);
+            total += k.j1 - k.j0;
         }
+        SBV2_REQUIRE(total + (slevel_on_ ? slevel_A_ : 0) <= c.fmt_cap, "internal: a replay of " + std::to_string(total) + " samples exceeds the slot sized for " +
+                                                                            std::to_string(c.fmt_cap));
+        const size_t dev_bytes = (size_t)c.fmt_cap * sfmt_.bytes();
         if (slevel_on_) {
             // ONE level push per replay: y (f64) behind the limiter's carried tail, then the samples the push completes through the cast /
-            // quantiser.  With S samples fed up to a window's end the stream has emitted max(0, S - A), the utterance's last window
+            // quantiser.  With S samples fed up to a window's end the stream has emitted max(0, S - A), the request's last window
             // everything: window w is handed the samples between its predecessor's count and its own.
-            const bool last = f0 + (int64_t)c.nwin * c.chunk >= Tf;
             const int64_t fed0 = sig.empty() ? 0 : sig[0].j0, e0 = slim_->emitted_after(fed0, false);
             SBV2_REQUIRE(fed0 == slim_->fed(), "internal: a level replay out of stream order (" + std::to_string(fed0) + " samples before it, " +
                                                    std::to_string(slim_->fed()) + " fed)");
@@ -1066,7 +1127,7 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
             }
             SBV2_REQUIRE(at - e0 == em, "internal: the level stream's counts disagree");
             total = em;
-            void* dev = sflac_on_ ? static_cast<void*>(sflac_->dst()) : sfmtr_->out_buffer(stream_fmt_bytes(c), stream_);
+            void* dev = sflac_on_ ? static_cast<void*>(sflac_->dst()) : sfmtr_->out_buffer(dev_bytes, stream_);
             pcm_cast(slim_->out_buffer(), em, slim_->unit(), sfmt_.encoding, dev, stream_);
             if (sflac_on_) {
                 const int64_t t0 = sflac_->tail();
@@ -1081,9 +1142,8 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
             }
         } else if (sflac_on_) {
             // ONE push per replay: the formatter writes behind the carried tail, the encoder packs every block that completes (with the
-            // utterance's last chunk also the short final frame).  Window w completes frames [flac_fr[w], flac_fr[w + 1]) of the push.
+            // request's last chunk also the short final frame).  Window w completes frames [flac_fr[w], flac_fr[w + 1]) of the push.
             const int64_t t0 = sflac_->tail();
-            const bool last = f0 + (int64_t)c.nwin * c.chunk >= Tf;
             sfmtr_->run(sfmt_, pieces, sig, total, sflac_->dst(), (&c == burst_.get() ? 2 : 0) + slot, stream_);
             c.flac_push[slot] = sflac_->push(total, last, c.host[slot], stream_);
             c.flac_fr[slot].assign(1, 0);
@@ -1092,55 +1152,49 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t f0, int slot) {
                 c.flac_fr[slot].push_back(w + 1 == c.fmt_n[slot].size() ? c.flac_push[slot].frames : (int)(upto / kFlacBlock));
             }
         } else {
-            void* dev = sfmtr_->out_buffer(stream_fmt_bytes(c), stream_);
+            void* dev = sfmtr_->out_buffer(dev_bytes, stream_);
             sfmtr_->run(sfmt_, pieces, sig, total, dev, (&c == burst_.get() ? 2 : 0) + slot, stream_);
             if (total) HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)total * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
         }
         HIP_CHECK(hipEventRecord(c.ev[slot], stream_));
-        c.slot_f0[slot] = f0;
+        c.slot_ci[slot] = c0;
         c.slot_n[slot] = total;
         return;
     }
-    for (int w = 0; w < c.nwin; ++w) {
-        const int64_t fw = f0 + (int64_t)w * c.chunk;
-        if (fw >= Tf) break;
-        const int64_t nsamp = std::min<int64_t>(c.chunk, Tf - fw) * hop;
+    for (int w = 0; w < live; ++w) {   // a plain stream: one row at place 0, the windows' centres as they are
+        const StreamCall& k = stl_.calls[c0 + w];
+        const int64_t nsamp = k.j1 - k.j0;
         HIP_CHECK(hipMemcpyAsync(c.host[slot] + (size_t)w * c.chunk * hop, c.pcm + ((size_t)w * c.W + halo) * hop, sizeof(float) * (size_t)nsamp,
                                  hipMemcpyDeviceToHost, stream_));
         total += nsamp;
     }
     HIP_CHECK(hipEventRecord(c.ev[slot], stream_));
-    c.slot_f0[slot] = f0;
+    c.slot_ci[slot] = c0;
     c.slot_n[slot] = total;
 }
 
-int64_t VitsModel::stream_fmt_samples(const ChunkPlan& c) const {
-    return (int64_t)c.nwin * (pcm_format_out_len(sfmt_, (int64_t)c.chunk * cfg_.hop()) + 1) + slevel_A_;
-}
-size_t VitsModel::stream_fmt_bytes(const ChunkPlan& c) const { return (size_t)stream_fmt_samples(c) * sfmt_.bytes(); }
-
-int64_t VitsModel::stream_chunk(int64_t f0, float* dst_host, int64_t capacity) {
+int64_t VitsModel::stream_chunk(int64_t ci, float* dst_host, int64_t capacity) {
     SBV2_REQUIRE(!sfmt_on_, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
-    return stream_take(f0, dst_host, capacity * (int64_t)sizeof(float), false, nullptr);
+    return stream_take(ci, dst_host, capacity * (int64_t)sizeof(float), false, nullptr);
 }
 
-int64_t VitsModel::stream_chunk_format(int64_t f0, void* dst_host, int64_t capacity_bytes) {
+int64_t VitsModel::stream_chunk_format(int64_t ci, void* dst_host, int64_t capacity_bytes) {
     SBV2_REQUIRE(sfmt_on_, "this stream has no output format: take its chunks with sbv2_stream_next");
     SBV2_REQUIRE(!slevel_on_, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
     SBV2_REQUIRE(!sflac_on_, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
-    return stream_take(f0, dst_host, capacity_bytes, true, nullptr);
+    return stream_take(ci, dst_host, capacity_bytes, true, nullptr);
 }
 
-int64_t VitsModel::stream_chunk_flac(int64_t f0, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes) {
+int64_t VitsModel::stream_chunk_flac(int64_t ci, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes) {
     SBV2_REQUIRE(!slevel_on_, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
     SBV2_REQUIRE(sflac_on_, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
-    return stream_take(f0, dst_host, capacity_bytes, true, n_bytes);
+    return stream_take(ci, dst_host, capacity_bytes, true, n_bytes);
 }
 
-int64_t VitsModel::stream_chunk_level(int64_t f0, void* dst_host, int64_t capacity_bytes, int64_t* n_out) {
+int64_t VitsModel::stream_chunk_level(int64_t ci, void* dst_host, int64_t capacity_bytes, int64_t* n_out) {
     SBV2_REQUIRE(slevel_on_, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
     int64_t taken = 0, bytes = 0;
-    const int64_t n = stream_take(f0, dst_host, capacity_bytes, true, sflac_on_ ? &bytes : nullptr, &taken);
+    const int64_t n = stream_take(ci, dst_host, capacity_bytes, true, sflac_on_ ? &bytes : nullptr, &taken);
     *n_out = sflac_on_ ? bytes : n;
     return taken;
 }
@@ -1151,14 +1205,22 @@ void VitsModel::stream_level_stats(double* out) const {
     slim_->stats(out);
 }
 
-int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes, int64_t* taken) {
+int64_t VitsModel::stream_call_bound() const {
+    int64_t most = 0;
+    for (const StreamCall& k : stl_.calls) most = std::max(most, k.j1 - k.j0);
+    if (!sfmt_on_) return most * (int64_t)sizeof(float);
+    most += slevel_on_ ? slevel_A_ : 0;
+    return sflac_on_ ? flac_stream_bound(most) : most * sfmt_.bytes();
+}
+
+int64_t VitsModel::stream_take(int64_t ci, void* dst, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes, int64_t* taken) {
     HIP_CHECK(hipSetDevice(device_));
-    SBV2_REQUIRE(chunk_ && z_.p && fl_.n == 1, "stream_chunk without stream_begin");
+    const int64_t ncalls = (int64_t)stl_.calls.size();
+    SBV2_REQUIRE(chunk_ && z_.p && ncalls > 0, "stream_chunk without stream_begin");
     ChunkPlan& c1 = *chunk_;
-    const int64_t Tf = fl_.len[0];
-    SBV2_REQUIRE(f0 >= 0 && f0 < Tf && f0 % c1.chunk == 0, "chunk start out of range");
+    SBV2_REQUIRE(ci >= 0 && ci < ncalls, "chunk out of range");
     const int hop = cfg_.hop();
-    const int64_t nsamp = std::min<int64_t>(c1.chunk, Tf - f0) * hop;
+    const int64_t nsamp = stl_.calls[ci].j1 - stl_.calls[ci].j0;
     const int64_t esz = formatted ? sfmt_.bytes() : (int64_t)sizeof(float);
     SBV2_REQUIRE(formatted || capacity_bytes >= nsamp * esz, "PCM buffer too small for the chunk");
     char* dst_host = static_cast<char*>(dst);
@@ -1171,11 +1233,11 @@ int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bo
         SBV2_REQUIRE(w < (int64_t)c.fmt_n[slot].size(), "formatted chunk missing from its replay");
         const int64_t n = c.fmt_n[slot][w];
         if (flac_bytes) {
-            // the frames this window completed, the stream header in front of the utterance's first ones.  Too small a buffer is refused before
+            // the frames this window completed, the stream header in front of the request's first ones.  Too small a buffer is refused before
             // anything is written or marked as taken: the call can be repeated.
             const FlacStreamEncoder::Push& p = c.flac_push[slot];
             const int fa = c.flac_fr[slot][w], fb = c.flac_fr[slot][w + 1];
-            const int64_t head = f0 == 0 ? kFlacStreamHeader : 0, nb = p.size(fa, fb);
+            const int64_t head = ci == 0 ? kFlacStreamHeader : 0, nb = p.size(fa, fb);
             SBV2_REQUIRE(capacity_bytes >= head + nb, "FLAC buffer too small for the chunk: " + std::to_string(capacity_bytes) + " < " +
                                                           std::to_string(head + nb) + " bytes (sbv2_flac_stream_bound always suffices)");
             uint8_t* o = reinterpret_cast<uint8_t*>(dst_host);
@@ -1190,30 +1252,29 @@ int64_t VitsModel::stream_take(int64_t f0, void* dst, int64_t capacity_bytes, bo
         if (taken) *taken = c.lvl_taken[slot][w];
         return n;
     };
-    const int64_t ci = f0 / c1.chunk;
     const bool bursts = stream_bursts_ && burst_ && burst_->chunk == c1.chunk;
     if (ci == 0 || !bursts) {
-        // the single-window plan: the utterance's first chunk (and everything when bursts are off); the next chunk runs while this one is delivered
+        // the single-window plan: the request's first chunk (and everything when bursts are off); the next chunk runs while this one is delivered
         const int slot = (int)(ci & 1);
-        SBV2_REQUIRE(!slevel_on_ || c1.slot_f0[slot] == f0, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
-        SBV2_REQUIRE(!flac_bytes || c1.slot_f0[slot] == f0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
-        if (c1.slot_f0[slot] != f0) stream_enqueue(c1, f0, slot);                                  // (random access: not the streaming order)
-        if (!bursts && f0 + c1.chunk < Tf && c1.slot_f0[slot ^ 1] != f0 + c1.chunk) stream_enqueue(c1, f0 + c1.chunk, slot ^ 1);
+        SBV2_REQUIRE(!slevel_on_ || c1.slot_ci[slot] == ci, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
+        SBV2_REQUIRE(!flac_bytes || c1.slot_ci[slot] == ci, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
+        if (c1.slot_ci[slot] != ci) stream_enqueue(c1, ci, slot);                                  // (random access: not the streaming order)
+        if (!bursts && ci + 1 < ncalls && c1.slot_ci[slot ^ 1] != ci + 1) stream_enqueue(c1, ci + 1, slot ^ 1);
         HIP_CHECK(hipEventSynchronize(c1.ev[slot]));
         const int64_t n = deliver(c1, slot, 0);
-        c1.slot_f0[slot] = -1;
+        c1.slot_ci[slot] = -1;
         return n;
     }
     ChunkPlan& cb = *burst_;
     const int64_t bi = (ci - 1) / cb.nwin, within = (ci - 1) % cb.nwin;
-    const int64_t bf0 = (1 + bi * cb.nwin) * c1.chunk;      // first frame of this chunk's burst
+    const int64_t b0 = 1 + bi * cb.nwin;      // first call of this chunk's burst
     const int slot = (int)(bi & 1);
-    SBV2_REQUIRE(!slevel_on_ || cb.slot_f0[slot] == bf0, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
-    SBV2_REQUIRE(!flac_bytes || cb.slot_f0[slot] == bf0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
-    if (cb.slot_f0[slot] != bf0) stream_enqueue(cb, bf0, slot);                                    // (random access)
+    SBV2_REQUIRE(!slevel_on_ || cb.slot_ci[slot] == b0, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
+    SBV2_REQUIRE(!flac_bytes || cb.slot_ci[slot] == b0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
+    if (cb.slot_ci[slot] != b0) stream_enqueue(cb, b0, slot);                                    // (random access)
     // the following burst is decoded while this one is delivered (its slot was drained one burst ago)
-    const int64_t nf0 = bf0 + (int64_t)cb.nwin * c1.chunk;
-    if (within == 0 && nf0 < Tf && cb.slot_f0[slot ^ 1] != nf0) stream_enqueue(cb, nf0, slot ^ 1);
+    const int64_t n0 = b0 + cb.nwin;
+    if (within == 0 && n0 < ncalls && cb.slot_ci[slot ^ 1] != n0) stream_enqueue(cb, n0, slot ^ 1);
     HIP_CHECK(hipEventSynchronize(cb.ev[slot]));
     return deliver(cb, slot, within);
 }

@@ -206,18 +206,26 @@ class TTSModelHolder:
         lines = text.split("\n") if options.split_sentences else [text]
         return [self.parse_text(t) if t else None for t in lines]
 
-    def easy_synthesize_stream(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, chunk_frames=256):
-        """The request as ONE utterance, delivered while it is synthesised (orchestrator.easy_synthesize_stream): a generator over the bytes of
-        the FLAC stream or WAV (an orchestrator.SynthesisStream: close() it when it is abandoned before its end).  `text`: a str, parsed as a whole (as split_sentences = False does), or the already parsed text as a one-entry
-        list.  Errors of the request are raised here, before the first piece.  The stream's `.marks` holds the token and word timing of the whole
-        utterance from the start (no levels: see orchestrator.easy_synthesize_stream)."""
+    def easy_synthesize_stream(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, chunk_frames=256,
+                               split=False):
+        """The request delivered while it is synthesised (orchestrator.easy_synthesize_stream): a generator over the bytes of the FLAC stream or
+        WAV (an orchestrator.SynthesisStream: close() it when it is abandoned before its end).  Errors of the request are raised here, before
+        the first piece.  The stream's `.marks` holds the token and word timing of the whole answer from the start (no levels: see
+        orchestrator.easy_synthesize_stream).
+
+        split=False (the default): the request as ONE utterance.  `text` is a str, parsed as a whole (as split_sentences = False does), or the
+        already parsed text as a one-entry list; a second live sentence is refused.
+
+        split=True: the request's lines as the rows of one batched forward, delivered as one signal sentence by sentence, with the pauses and
+        the bytes of easy_synthesize.  `text` is a str, split on '\\n' and parsed per line as _sentences does, or the list of parsed lines with
+        None for an empty line."""
         options = options or orchestrator.SynthesizeOptions()
         self.find_and_load_model(ident)
         m = self._find(ident)
         if isinstance(text, str):
             if self.parse_text is None:
                 raise model.Sbv2Error("no text front end configured (parse_text): pass parsed sentences instead")
-            sentences = [self.parse_text(text) if text else None]
+            sentences = [self.parse_text(t) if t else None for t in (text.split("\n") if split else [text])]
         else:
             sentences = list(text)
         # The stream runs on the two sessions themselves, which are the first execution context of the model's pipeline (same stream, arena and
@@ -236,7 +244,7 @@ class TTSModelHolder:
 
         try:
             st = orchestrator.easy_synthesize_stream(self.bert, m.vits2, sentences, m.style_vectors, style_id, speaker_id, options,
-                                                     noise_seed=noise_seed, chunk_frames=chunk_frames)
+                                                     noise_seed=noise_seed, chunk_frames=chunk_frames, split=split)
         except BaseException:
             release()
             raise

@@ -711,8 +711,34 @@ def stream_synthesize(bert: Session, vits: Session, utt, chunk_frames=256, **kw)
         st.close()
 
 
+def stream_min_gap(fmt: PcmFormat | None) -> int:
+    """The smallest gap (native samples) between two utterances of a request stream at fmt's rate: 2 ceil(half / L); 0 at 44.1 kHz (host only)."""
+    n = _lib.lib().sbv2_stream_min_gap(C.byref(fmt.c) if fmt is not None else None)
+    if n < 0:
+        raise Sbv2Error(_lib.lib().sbv2_last_error().decode(errors="replace"))
+    return int(n)
+
+
+def stream_timeline(frames, gaps, hop: int, chunk_frames: int, fmt: PcmFormat | None = None):
+    """(place, joined_len, call_samples): the timeline of a request stream over rows of `frames` frames with `gaps` native samples of silence
+    after each (sbv2_stream_timeline; host only): where the rows lie, the length of the timeline, and the samples every call covers."""
+    fr, fp = _i64(frames)
+    gp_a, gp = _i64(gaps)
+    n = int(fr.size)
+    cap = int(sum(-(-int(f) // max(int(chunk_frames), 1)) for f in fr if f > 0)) + 1
+    place, joined, calls, ncalls = np.zeros(max(n, 1), np.int64), C.c_int64(), np.zeros(cap, np.int64), C.c_int64()
+    if gp_a.size != n:
+        raise Sbv2Error(f"gaps must hold one entry per row ({n})")
+    check(_lib.lib().sbv2_stream_timeline(fp, gp, n, int(hop), int(chunk_frames), C.byref(fmt.c) if fmt is not None else None,
+                                          place.ctypes.data_as(i64p), C.byref(joined), calls.ctypes.data_as(i64p), cap, C.byref(ncalls)))
+    return place[:n], joined.value, calls[:ncalls.value]
+
+
 class StreamHandle:
-    """fmt (PcmFormat, optional): the chunks leave the device in that format (normalize is refused: a stream cannot know the peak ahead);
+    """utt: one utterance dict, or a LIST of them with gaps= (native samples of silence after each entry, the last one trailing): the rows of
+    one batched forward delivered as one signal, sentence by sentence (sbv2_stream_begin_request; fmt None = 44.1 kHz f32; next() returns one
+    piece per chunk of a row, the half gaps with a row's first and last piece; layout() tells where the rows lie, marks() covers all rows).
+    fmt (PcmFormat, optional): the chunks leave the device in that format (normalize is refused: a stream cannot know the peak ahead);
     total_samples is then counted at fmt.sample_rate.  flac=True (fmt must be s16): the chunks' samples are encoded on the device as ONE FLAC
     stream; next() returns the bytes of the frames the chunk completed (b"" when it completed none: FLAC frames hold 4096 samples), the
     42-byte stream header in front of the first ones; samples_taken counts the s16 samples consumed so far.
@@ -722,18 +748,39 @@ class StreamHandle:
     the end."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
-                 level: "StreamLevel | None" = None, **kw):
+                 level: "StreamLevel | None" = None, gaps=None, **kw):
         l = _lib.lib()
-        self.b = Pipeline.prepare(None, [utt], **kw)
+        self.request = isinstance(utt, (list, tuple))
+        self.b = Pipeline.prepare(None, list(utt) if self.request else [utt], **kw)
         self.h = C.c_void_p()
         self.fmt, self.flac, self.level, self.samples_taken = fmt, bool(flac), level, 0
         if flac and fmt is None:
             raise Sbv2Error("a FLAC stream needs a format: fmt=PcmFormat(rate, \"s16\")")
-        if level is not None and fmt is None:
-            raise Sbv2Error("a level stream needs a format: fmt=PcmFormat(rate, encoding), any encoding")
         tot = C.c_int64()
         args = (bert.handle, vits.handle, C.byref(self.b.c), self.b.ids.ctypes.data_as(i64p), self.b.s_lens.ctypes.data_as(i64p),
                 self.b.w2p.ctypes.data_as(i64p), chunk_frames)
+        if self.request:
+            # the rows of ONE batched forward as one signal (sbv2_stream_begin_request): always a formatted stream, fmt None = the identity format
+            if gaps is None:
+                raise Sbv2Error("a stream over several utterances needs gaps= (native samples of silence after each, the last one trailing)")
+            self.gaps, gp = _i64(gaps)
+            if self.gaps.shape != (len(utt),):
+                raise Sbv2Error(f"gaps must hold one entry per utterance ({len(utt)})")
+            rq = _lib.Sbv2StreamRequest(gp, C.pointer(fmt.c) if fmt is not None else None, C.pointer(level.c) if level is not None else None,
+                                        int(self.flac), 0)
+            check(l.sbv2_stream_begin_request(args[0], args[1], args[2], C.byref(self.b.opts) if self.b.opts is not None else None, *args[3:],
+                                              C.byref(rq), C.byref(self.h), C.byref(tot)))
+            if fmt is None:
+                self.fmt = PcmFormat(44100, "f32")
+            self.buf = np.empty(max(int(l.sbv2_stream_call_bound(self.h)), 1), np.uint8)
+            self.total_samples = tot.value
+            self.uses_graph = bool(l.sbv2_stream_uses_graph(self.h))
+            self.workspace_bytes = l.sbv2_stream_workspace_bytes(self.h)
+            return
+        if gaps is not None:
+            raise Sbv2Error("gaps= belongs to a stream over a list of utterances")
+        if level is not None and fmt is None:
+            raise Sbv2Error("a level stream needs a format: fmt=PcmFormat(rate, encoding), any encoding")
         if fmt is None:
             check(l.sbv2_stream_begin(*args, C.byref(self.h), C.byref(tot)))
             self.buf = np.empty(chunk_frames * l.sbv2_vits_hop(vits.handle), np.float32)
@@ -768,6 +815,8 @@ class StreamHandle:
             check(_lib.lib().sbv2_stream_next(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.size, C.byref(n)))
         else:
             check(_lib.lib().sbv2_stream_next_format(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.nbytes, C.byref(n)))
+        if self.request:   # (the request stream's buffer is sized in bytes: sbv2_stream_call_bound)
+            return None if n.value == 0 else self.buf[:n.value * np.dtype(self.fmt.dtype).itemsize].view(self.fmt.dtype).copy()
         return None if n.value == 0 else self.buf[:n.value].copy()
 
     def level_stats(self):
@@ -779,10 +828,17 @@ class StreamHandle:
     def marks(self):
         """(start, end): the spans of the utterance's tokens in delivered samples of this stream (sbv2_stream_marks; host only, complete from
         the moment the stream exists).  Streams carry no levels."""
-        n = int(self.b.t_lens[0])
+        n = int(np.asarray(self.b.t_lens).sum())   # (a request stream: the tokens of all rows, row after row)
         st, en, got = np.zeros(n, np.int64), np.zeros(n, np.int64), C.c_int64()
         check(_lib.lib().sbv2_stream_marks(self.h, st.ctypes.data_as(i64p), en.ctypes.data_as(i64p), n, C.byref(got)))
         return st[:got.value], en[:got.value]
+
+    def layout(self):
+        """(place, lens, joined_len) in native samples: where the stream's rows lie on its timeline (sbv2_stream_layout; host only)."""
+        n = len(self.b.t_lens)
+        place, lens, got, joined = np.zeros(n, np.int64), np.zeros(n, np.int64), C.c_int64(), C.c_int64()
+        check(_lib.lib().sbv2_stream_layout(self.h, place.ctypes.data_as(i64p), lens.ctypes.data_as(i64p), n, C.byref(got), C.byref(joined)))
+        return place[:got.value], lens[:got.value], joined.value
 
     def close(self):
         if self.h:

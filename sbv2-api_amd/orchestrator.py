@@ -365,12 +365,21 @@ class SynthesisStream:
 
 
 def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
-                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256):
-    """easy_synthesize for long text, delivered while it is synthesised: an iterator (SynthesisStream; close() it when it is abandoned early)
-    over the pieces of the request's container.  A stream
-    takes ONE utterance (model.StreamHandle: whole-sequence DeBERTa / text / flow, then the decoder chunk by chunk), so `sentences` must hold
-    one parsed text: the request's lines joined, as options.split_sentences = False passes them (empty entries are skipped, a second live one
-    is refused).  encoding "flac": the pieces of one FLAC stream encoded on the device, as its frames complete (chunks that complete none
+                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False):
+    """easy_synthesize delivered while it is synthesised: an iterator (SynthesisStream; close() it when it is abandoned early) over the pieces
+    of the request's container.  The forward (DeBERTa / text / flow) runs once over the whole request, then the decoder runs chunk by chunk
+    (model.StreamHandle).
+
+    split=False (the default): the stream takes ONE utterance, so `sentences` must hold one parsed text: the request's lines joined, as
+    options.split_sentences = False passes them (empty entries are skipped, a second live one is refused).
+
+    split=True: `sentences` is the request's line list as easy_synthesize takes it (None for an empty line).  The live sentences become the rows
+    of ONE batched forward (the request's seed, the row number as noise key: what easy_synthesize prepares) and leave as one signal, sentence
+    by sentence (a model.StreamHandle over a list): SENTENCE_GAP native samples of silence after every live sentence that is not the last
+    line, joined_placement's rule.  With the same seed and options the streamed bytes are easy_synthesize's (at the default format the WAV
+    headers differ in form, the samples do not).
+
+    Either way.  encoding "flac": the pieces of one FLAC stream encoded on the device, as its frames complete (chunks that complete none
     yield nothing); "s16" / "f32": the WAV header of pcm16_wav / float_wav written with the known total length, then the chunks' samples;
     "mulaw" / "alaw": the header of g711_wav, the chunks' codes, and one zero pad byte after the last chunk when the total is odd.
     normalize, loudness and limiter are refused: they need the whole signal before the first sample can leave.
@@ -378,7 +387,8 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     the ceiling; the pieces run stream_level_lookahead samples behind the decoder, the total length is unchanged, and after the last piece
     the iterator's `.level_stats` holds (deepest reduction in dB, max |x|).
     Everything up to the first replay (options, DeBERTa, flow, the header) runs before the iterator is returned.
-    The iterator's `.marks` holds the utterance's token and word timing (token_marks: every duration is known before the first replay)."""
+    The iterator's `.marks` holds the token and word timing of every row with its line number (token_marks: every duration is known before
+    the first replay)."""
     options = options or SynthesizeOptions()
     if options.normalize:
         raise model.Sbv2Error("a stream cannot normalise: the peak needs the whole signal (use /synthesize)")
@@ -390,19 +400,24 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     live = [s for s in sentences if s]
     if not live:
         raise model.Sbv2Error("nothing to synthesize (the reference's concatenate fails on an empty list)")
-    if len(live) != 1:
+    if not split and len(live) != 1:
         raise model.Sbv2Error(f"a stream takes one utterance, not {len(live)} sentences: pass the text parsed as a whole (split_sentences = False)")
     flac = options.encoding == "flac"
     fmt = model.PcmFormat(options.sample_rate, "s16" if flac else options.encoding, False)
     model.pcm_format_length(fmt, 0)   # a bad rate is refused before any GPU work
     # (with a level the default format is an explicit one: the level stream always formats)
     level = model.StreamLevel(options.gain_db, options.true_peak_max) if options.gain_db is not None else None
-    st = model.StreamHandle(bert, vits, dict(live[0], style=style, sid=speaker_id), chunk_frames,
-                            fmt=None if fmt.is_default and level is None else fmt, flac=flac, level=level,
-                            sdp_ratio=options.sdp_ratio, length_scale=options.length_scale, noise_scale=noise_scale,
-                            noise_scale_w=noise_scale_w, noise_seed=noise_seed)
+    kw = dict(fmt=None if fmt.is_default and level is None else fmt, flac=flac, level=level, sdp_ratio=options.sdp_ratio,
+              length_scale=options.length_scale, noise_scale=noise_scale, noise_scale_w=noise_scale_w, noise_seed=noise_seed)
+    if split:
+        lines = [i for i, s in enumerate(sentences) if s]
+        gaps = [SENTENCE_GAP if i != len(sentences) - 1 else 0 for i in lines]
+        st = model.StreamHandle(bert, vits, [dict(s, style=style, sid=speaker_id) for s in live], chunk_frames, gaps=gaps, **kw)
+    else:
+        lines = [sentences.index(live[0])]
+        st = model.StreamHandle(bert, vits, dict(live[0], style=style, sid=speaker_id), chunk_frames, **kw)
     try:
-        marks = token_marks([live[0]], [sentences.index(live[0])], fmt.sample_rate, *st.marks())
+        marks = token_marks(live, lines, fmt.sample_rate, *st.marks())
     except BaseException:
         st.close()
         raise

@@ -113,6 +113,7 @@ def make_app(holder, batching=None):
 
     class SynthesizeStreamRequest(SynthesizeRequest):
         marks: bool = False                 # the utterance's timing in the X-Speech-Marks response header
+        split_sentences: bool = False       # the text's lines as sentences of one batched run, streamed one after the other with /synthesize's pauses
 
     class _ClosingStream(StreamingResponse):
         """A StreamingResponse that closes its _HeldPieces when the response is over, however it ends: sent to the end, cut by the client's
@@ -196,7 +197,11 @@ def make_app(holder, batching=None):
     def synthesize_stream(req: SynthesizeStreamRequest):
         lock.acquire()                        # one request at a time: given back by _HeldPieces.close when the response is over
         try:
-            pieces = holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
+            # split_sentences = False is the holder's own default (split=False), and it is sent by leaving the keyword out, on purpose: a holder
+            # written before request streams takes five arguments and keeps serving every request that does not ask for a split.  Asked of such
+            # a holder, a split is a TypeError, answered as the error below, never a silent unsplit stream.
+            pieces = holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req),
+                                                   **({"split": True} if req.split_sentences else {}))
             held = _HeldPieces(lock, pieces)
             headers = {"X-Speech-Marks": stream_marks_header(pieces.marks)} if req.marks else None
         except BaseException as e:            # before the first byte: the same mapping
