@@ -519,8 +519,8 @@ int sbv2_debug_limiter_stream(int device, const double* x, int64_t n, const int6
  * utterance at place 0 (a request stream, sbv2_stream_begin_request: of all its rows, row i at place[i], row order then token order) and at
  * the stream's delivered rate (native for sbv2_stream_begin).  Every duration is known before the first replay, so
  * the client has the full timing before the first audio byte; the samples of all chunks sum to the last token's end (durations summing to >= 1).
- * Levels and the envelope are NOT built on streams: they would need partial sums carried across chunks, and a streaming client decodes the
- * audio anyway.  Refused: capacity below the token count. */
+ * Levels and the envelope of a stream come from sbv2_stream_begin_request_levels / sbv2_stream_next_marks below (partial sums carried across
+ * the chunks on the device); this call stays host arithmetic and is the same on every stream.  Refused: capacity below the token count. */
 int sbv2_stream_marks(sbv2_stream* s, int64_t* tok_start, int64_t* tok_end, int64_t capacity, int64_t* n_tokens);
 /* ---- new: a stream over the n rows of ONE batched forward: a multi-sentence request as one signal, sentence by sentence.
  * Forward.  batch->n >= 1 rows run through one forward with the decoder left out: the forward sbv2_pipeline_run_opts runs for that batch and
@@ -548,8 +548,8 @@ int sbv2_stream_marks(sbv2_stream* s, int64_t* tok_start, int64_t* tok_end, int6
  *   sbv2_pipeline_fetch_request_marks for the joined fetch; the silence belongs to no token.
  * Refused before any GPU work: NULL rq or gap_after, n < 1, a gap out of range or below the minimum, a non-zero reserved, normalize, flac without
  *   s16, and whatever the options, the format and the level are refused for elsewhere.
- * Not built: gaps below the minimum at resampled rates (they would need a call to see two windows), levels / an envelope in the marks, a
- *   loudness target, sbv2_node_*.  The four calls above are the n = 1, gap_after = {0} case of the same code and keep their bytes. */
+ * Not built: gaps below the minimum at resampled rates (they would need a call to see two windows), a loudness target, sbv2_node_*.  Levels
+ *   and an envelope: sbv2_stream_begin_request_levels below.  The four calls above are the n = 1, gap_after = {0} case of the same code and keep their bytes. */
 typedef struct sbv2_stream_request {
     const int64_t* gap_after;         /* [batch->n] native (44.1 kHz) samples of silence after row i; the last entry is trailing silence */
     const sbv2_pcm_format* fmt;       /* NULL = 44100 Hz f32, not normalised (the identity format) */
@@ -560,6 +560,53 @@ typedef struct sbv2_stream_request {
 int sbv2_stream_begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
                               const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
                               const sbv2_stream_request* rq, sbv2_stream** out, int64_t* total_samples);
+/* ---- new: the levels and the envelope of a stream's marks, reduced chunk by chunk ON THE DEVICE.
+ * sbv2_stream_begin_request with, besides, a level reduction of the DELIVERED samples behind every decoder replay: sumsq / peak (see sbv2_marks:
+ *   the same values of the same samples, "exactly what crosses PCIe or enters the FLAC encoder", G.711 codes as the integers they decode to) per
+ *   token span of sbv2_stream_marks (tokens = 1) and / or per envelope frame [f env_hop, min((f + 1) env_hop, total_samples)) (env_hop > 0,
+ *   *n_env = ceil(total_samples / env_hop) frames).  On a level stream (rq->level) the samples are those the limiter emits, at their own
+ *   positions: time is not shifted, delivery only runs A samples late.
+ * Bits.  A segment's sum is formed in the order of the one-shot reduction (sbv2_debug_segment_levels, sbv2_pipeline_fetch_request_marks): lane
+ *   o mod stride adds offset o, stride by the segment's total length; a segment open at a replay's end keeps its lanes' partial sums on the
+ *   device (16 KB in all, whatever the stream's length).  So the values do not depend on chunk_frames, and where the stream's bytes equal a
+ *   fetch's (sbv2_stream_begin_request, "Output") they equal the fetch's marks bit for bit.  No sample is read more often than in the fetch.
+ * lv == NULL, or tokens == 0 and env_hop == 0: exactly sbv2_stream_begin_request (*n_tokens = *n_env = 0, no new launch, sbv2_stream_next_marks
+ *   refused).  Otherwise the stream is taken with the sbv2_stream_next_* call of its kind, unchanged, its audio bytes are those of the same
+ *   stream without levels, and it delivers in order only.  The single-utterance streams are the n = 1, gap_after = {0} case.
+ * Refused before any GPU work: a non-zero reserved, tokens outside {0, 1}, a negative env_hop (these three before the handles are looked at),
+ *   and everything sbv2_stream_begin_request refuses.  n_env >= 2^30 is refused once the forward has named the length
+ *   (with predicted durations nothing names it earlier), before the stream has set up anything: no replay, no buffer, no level work.
+ * Not built: levels on the plain sbv2_stream_begin stream (begin a request stream with fmt NULL, the identity format, instead), sbv2_node_*,
+ *   a loudness target on a stream. */
+typedef struct sbv2_stream_levels {
+    int32_t tokens;        /* 0 / 1: levels per token */
+    int32_t env_hop;       /* 0 = no envelope, else delivered samples per frame */
+    int32_t reserved[2];   /* must be 0 */
+} sbv2_stream_levels;
+int sbv2_stream_begin_request_levels(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                                     const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                     const sbv2_stream_request* rq, const sbv2_stream_levels* lv, sbv2_stream** out, int64_t* total_samples,
+                                     int64_t* n_tokens, int64_t* n_env);
+/* Host only: the entries completed since the previous call.  With D the samples the stream has delivered or consumed so far (the sum of *n of
+ * sbv2_stream_next_format, of *n_samples of sbv2_stream_next_flac; on a level stream the samples EMITTED by its delivery rule, max(0, S - A),
+ * and everything with the last chunk): token t is complete once end[t] <= D, frame f once min((f + 1) env_hop, total) <= D; after the last
+ * chunk everything is.  A call hands out the contiguous ranges [tok_first, tok_first + n_tok) (numbering of sbv2_stream_marks) and
+ * [env_first, env_first + n_env) that became complete since the previous call, and delivered = D.  A capacity below the pending entries, or
+ * NULL arrays with entries pending, is refused with nothing handed out: repeat with more room.  Not calling it loses nothing: the next call
+ * returns everything pending.  Refused on a stream begun without levels. */
+typedef struct sbv2_stream_marks_part {
+    int64_t tok_capacity; double* tok_sumsq; double* tok_peak; int64_t tok_first, n_tok;
+    int64_t env_capacity; double* env_sumsq; double* env_peak; int64_t env_first, n_env;
+    int64_t delivered;
+} sbv2_stream_marks_part;
+int sbv2_stream_next_marks(sbv2_stream* s, sbv2_stream_marks_part* part);
+/* Test hook: the fed reduction on its own.  x[n] (host; encoding as sbv2_debug_segment_levels) is cut at the ascending positions cuts[ncuts] into
+ * ncuts + 1 pushes (empty ones allowed); segments [starts[i], ends[i]) must be monotone and disjoint within [0, n] (empty ones and holes allowed),
+ * env_hop as above (0 = none).  seg_* [nseg] and env_* [ceil(n / env_hop)] receive the results, seg_per_push / env_per_push [ncuts + 1] the
+ * entries each push completed.  Segments, env_hop and cuts are checked before any device call. */
+int sbv2_debug_stream_levels(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, const int64_t* starts,
+                             const int64_t* ends, int64_t nseg, int32_t env_hop, double* seg_sumsq, double* seg_peak, double* env_sumsq,
+                             double* env_peak, int64_t* seg_per_push, int64_t* env_per_push);
 /* Host only: the minimum gap above in native samples (fmt NULL = the identity format = 0); -1 for a bad fmt. */
 int64_t sbv2_stream_min_gap(const sbv2_pcm_format* fmt);
 /* Host only: the arithmetic above in one place (the library calls it itself).  frames[n] = the rows' lengths in frames (>= 1), hop =

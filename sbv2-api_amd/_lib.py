@@ -45,6 +45,18 @@ class Sbv2StreamRequest(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class Sbv2StreamLevels(C.Structure):
+    """struct sbv2_stream_levels (include/sbv2_hip.h)."""
+    _fields_ = [("tokens", C.c_int32), ("env_hop", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class Sbv2StreamMarksPart(C.Structure):
+    """struct sbv2_stream_marks_part (include/sbv2_hip.h)."""
+    _fields_ = [("tok_capacity", C.c_int64), ("tok_sumsq", C.POINTER(C.c_double)), ("tok_peak", C.POINTER(C.c_double)), ("tok_first", C.c_int64),
+                ("n_tok", C.c_int64), ("env_capacity", C.c_int64), ("env_sumsq", C.POINTER(C.c_double)), ("env_peak", C.POINTER(C.c_double)),
+                ("env_first", C.c_int64), ("n_env", C.c_int64), ("delivered", C.c_int64)]
+
+
 class Sbv2UttOptions(C.Structure):
     """struct sbv2_utt_options (include/sbv2_hip.h)."""
     _fields_ = [("sdp_ratio", f32p), ("length_scale", f32p), ("noise_scale", f32p), ("noise_scale_w", f32p),
@@ -171,6 +183,11 @@ SYMBOLS = {
                                             C.POINTER(C.c_double)]),
     "sbv2_stream_begin_request": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p, i64p, i64p, C.c_int64,
                                             C.POINTER(Sbv2StreamRequest), C.POINTER(C.c_void_p), i64p]),
+    "sbv2_stream_begin_request_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p, i64p, i64p, C.c_int64,
+                                                   C.POINTER(Sbv2StreamRequest), C.POINTER(Sbv2StreamLevels), C.POINTER(C.c_void_p), i64p, i64p, i64p]),
+    "sbv2_stream_next_marks": (C.c_int, [C.c_void_p, C.POINTER(Sbv2StreamMarksPart)]),
+    "sbv2_debug_stream_levels": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, i64p, C.c_int, i64p, i64p, C.c_int64, C.c_int32,
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i64p, i64p]),
     "sbv2_stream_min_gap": (C.c_int64, [C.POINTER(Sbv2PcmFormat)]),
     "sbv2_stream_timeline": (C.c_int, [i64p, i64p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, i64p, i64p, C.c_int64, i64p]),
     "sbv2_stream_layout": (C.c_int, [C.c_void_p, i64p, i64p, C.c_int64, i64p, i64p]),

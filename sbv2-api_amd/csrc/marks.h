@@ -38,4 +38,51 @@ class Marks {
     int64_t nseg_ = 0;
 };
 
+// The same reduction FED piece by piece (a stream's replays): two segment tables fixed at begin, the token spans (monotone, disjoint, empty
+// ones and unowned holes allowed) and the envelope frames [f hop, min((f + 1) hop, total)); a push covers the delivered samples [D0, D0 + n)
+// that have just been written on the device.  Lane (o mod stride) of a segment adds the squares at offsets o in increasing order, stride by
+// the segment's TOTAL length (64 up to Marks::kLongSegment, 256 above), exactly as k_segment_levels does; a segment that a push leaves open
+// keeps its lanes' (ss, pk) on the device and the next push goes on from them, the push that ends it runs the same tree.  So the results
+// have the bits of Marks::run over the whole signal, whatever the pushes.  At most one segment per table is open between two pushes: the
+// carry is 2 tables x 256 lanes x 2 doubles, held twice (a push reads one copy and writes the other: the segment it continues and the
+// segment it leaves open may differ and run in different workgroups of one launch) = 16 KB whatever the stream's length.  No atomics.
+// A push passes scalars by value only; nothing is allocated and no table is copied after begin.  Results: one device array of pairs
+// {sumsq, peak}, tokens then frames, zero at begin (an empty segment stays 0, 0), with a pinned mirror; a push copies the slots it completed.
+class StreamLevels {
+  public:
+    StreamLevels() = default;
+    StreamLevels(const StreamLevels&) = delete;
+    StreamLevels& operator=(const StreamLevels&) = delete;
+    struct Done {
+        int64_t tok, env;   // entries the push completed: tokens with end <= D0 + n, frames likewise, that no earlier push completed
+    };
+    // Host only, throws: spans within [0, total], start <= end, end[i] <= start[i + 1]; env_hop >= 0 with fewer than 2^30 frames
+    static void check(const int64_t* seg, int64_t nseg, int64_t env_hop, int64_t total);
+    static int64_t env_frames(int64_t env_hop, int64_t total) { return env_hop > 0 ? (total + env_hop - 1) / env_hop : 0; }
+    // seg = [nseg][2] (nseg = 0: no token levels), env_hop = 0: no envelope.  Waits for s once (the buffers of an earlier stream are reused).
+    void begin(const int64_t* seg, int64_t nseg, int64_t env_hop, int64_t total, hipStream_t s);
+    // x = the sample at delivered position D0 (device), D0 = fed(); n = 0 enqueues nothing
+    Done push(const void* x, int encoding, int64_t D0, int64_t n, hipStream_t s);
+    int64_t fed() const { return fed_; }
+    int64_t total() const { return total_; }
+    int64_t env_hop() const { return env_hop_; }
+    int64_t n_tok() const { return ntok_; }
+    int64_t n_env() const { return nenv_; }
+    // the completion rule: entries complete once D samples are out (tokens: end <= D; frames: min((f + 1) hop, total) <= D)
+    int64_t tok_complete(int64_t D) const;
+    int64_t env_complete(int64_t D) const { return nenv_ == 0 ? 0 : D >= total_ ? nenv_ : D / env_hop_; }
+    // pairs {sumsq, peak}; entry i is valid once the push that completed it has run on s
+    const double* tok_host() const { return res_host_; }
+    const double* env_host() const { return res_host_ + 2 * ntok_; }
+
+  private:
+    std::vector<int64_t> seg_;   // the token table (host copy: which segments a push meets and completes)
+    PinnedBuffer host_;          // the token table for its upload, then the results' mirror
+    DeviceBuffer dev_;           // token table | carry (2 copies) | results
+    int64_t* d_seg_ = nullptr;
+    double *d_carry_ = nullptr, *d_res_ = nullptr, *res_host_ = nullptr;
+    int64_t ntok_ = 0, nenv_ = 0, env_hop_ = 0, total_ = 0, fed_ = 0, tok_done_ = 0, env_done_ = 0;
+    int parity_ = 0;
+};
+
 }  // namespace sbv2

@@ -161,4 +161,204 @@ void Marks::run(const void* x, int encoding, int64_t n, const int64_t* seg, int6
     HIP_CHECK(hipMemcpyAsync(res_host_, a.sumsq, 16 * (size_t)nseg, hipMemcpyDeviceToHost, s));
 }
 
+// ---- the fed reduction (StreamLevels, marks.h) ----
+namespace {
+
+constexpr int kCarryTable = 2 * kBlock;   // doubles per table in one copy of the carry: {ss, pk} per lane
+
+struct StreamLevelArgs {
+    const void* x;             // the sample at delivered position d0
+    int64_t d0, d1;            // the push
+    const int64_t* seg;        // the token table [ntok][2]
+    int64_t ntok;
+    int32_t tok_first, tok_count;   // the tokens this push may meet: one workgroup each
+    int64_t env_hop, total, env_first;
+    int32_t env_count, env_packed;   // the frames it meets; packed: four (short) frames per workgroup, one per wave
+    const double* carry_in;    // [2 tables][256 lanes][2]
+    double* carry_out;
+    double* res;               // [ntok + nenv][2]
+};
+
+// One segment per wave (stride 64) or per workgroup (stride 256), by the segment's total length.  The piece [max(s, d0), min(e, d1)): the lane
+// of offset o is o mod stride, so a lane goes on with the offsets k_segment_levels gives it, in the same order, from the carried partials.
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_stream_levels(const StreamLevelArgs a) {
+    __shared__ double sh_ss[kWavesPerBlock], sh_pk[kWavesPerBlock];
+    const T* x = static_cast<const T*>(a.x);
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    int table;
+    bool packed = false;
+    int64_t slot, s, e;
+    if ((int)blockIdx.x < a.tok_count) {
+        table = 0;
+        slot = a.tok_first + (int)blockIdx.x;
+        s = a.seg[2 * slot];
+        e = a.seg[2 * slot + 1];
+    } else {
+        table = 1;
+        const int eb = (int)blockIdx.x - a.tok_count;
+        packed = a.env_packed != 0;
+        const int64_t k = packed ? (int64_t)eb * kWavesPerBlock + wave : eb;
+        if (k >= a.env_count) return;   // (packed only: no barrier on that path)
+        const int64_t f = a.env_first + k;
+        s = f * a.env_hop;
+        e = min(s + a.env_hop, a.total);
+        slot = a.ntok + f;
+    }
+    const bool whole_block = e - s > Marks::kLongSegment;   // uniform over the workgroup (never with packed frames)
+    if (!whole_block && !packed && wave) return;            // a short segment alone in its workgroup: wave 0
+    const int64_t lo = max(s, a.d0), hi = min(e, a.d1);
+    if (lo >= hi) return;   // (uniform over the segment's lanes: an empty span, or a segment this push does not reach)
+    const int stride = whole_block ? kBlock : kWave, me = whole_block ? (int)threadIdx.x : lane;
+    double ss = 0.0, pk = 0.0;
+    if (lo > s) {
+        const double* c = a.carry_in + table * kCarryTable + 2 * me;
+        ss = c[0];
+        pk = c[1];
+    }
+    const int64_t o0 = lo - s, len = hi - s, base = s - a.d0;   // x[base + o] is offset o of the segment; base + o >= lo - d0 >= 0
+    int64_t i = o0 + ((me - (int)(o0 & (stride - 1))) & (stride - 1));
+    for (; i + 3 * stride < len; i += 4 * stride) {
+        const double v0 = level_load(x, base + i), v1 = level_load(x, base + i + stride), v2 = level_load(x, base + i + 2 * stride),
+                     v3 = level_load(x, base + i + 3 * stride);
+        ss += v0 * v0;
+        ss += v1 * v1;
+        ss += v2 * v2;
+        ss += v3 * v3;
+        pk = fmax(fmax(pk, fabs(v0)), fmax(fabs(v1), fmax(fabs(v2), fabs(v3))));
+    }
+    for (; i < len; i += stride) {
+        const double v = level_load(x, base + i);
+        ss += v * v;
+        pk = fmax(pk, fabs(v));
+    }
+    if (hi < e) {   // the segment stays open: the lanes' partials wait for the next push
+        double* c = a.carry_out + table * kCarryTable + 2 * me;
+        c[0] = ss;
+        c[1] = pk;
+        return;
+    }
+    wave_reduce(ss, pk);
+    if (!whole_block) {
+        if (lane == 0) a.res[2 * slot] = ss, a.res[2 * slot + 1] = pk;
+        return;
+    }
+    if (lane == 0) sh_ss[wave] = ss, sh_pk[wave] = pk;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = sh_ss[0], m = sh_pk[0];
+        for (int w = 1; w < kWavesPerBlock; ++w) t += sh_ss[w], m = fmax(m, sh_pk[w]);
+        a.res[2 * slot] = t;
+        a.res[2 * slot + 1] = m;
+    }
+}
+
+}  // namespace
+
+void StreamLevels::check(const int64_t* seg, int64_t nseg, int64_t env_hop, int64_t total) {
+    SBV2_REQUIRE(total >= 0 && nseg >= 0 && nseg < (1 << 30) && (nseg == 0 || seg), "bad segment table");
+    SBV2_REQUIRE(env_hop >= 0, "env_hop must be >= 0");
+    SBV2_REQUIRE(env_frames(env_hop, total) < (1 << 30), "too many envelope frames: " + std::to_string(env_frames(env_hop, total)) + " >= 2^30");
+    int64_t at = 0;
+    for (int64_t i = 0; i < nseg; ++i) {
+        const int64_t s0 = seg[2 * i], e0 = seg[2 * i + 1];
+        SBV2_REQUIRE(s0 >= 0 && s0 <= e0 && e0 <= total, "segment " + std::to_string(i) + " [" + std::to_string(s0) + ", " + std::to_string(e0) +
+                                                             ") is outside the " + std::to_string(total) + " delivered samples");
+        SBV2_REQUIRE(s0 >= at, "segment " + std::to_string(i) + " [" + std::to_string(s0) + ", " + std::to_string(e0) +
+                                   ") starts before its predecessor ends: a stream's segments must be monotone and disjoint");
+        at = e0;
+    }
+}
+
+void StreamLevels::begin(const int64_t* seg, int64_t nseg, int64_t env_hop, int64_t total, hipStream_t s) {
+    check(seg, nseg, env_hop, total);
+    ntok_ = nseg;
+    env_hop_ = env_hop;
+    total_ = total;
+    nenv_ = env_frames(env_hop, total);
+    fed_ = tok_done_ = env_done_ = 0;
+    parity_ = 0;
+    seg_.assign(seg, seg + 2 * nseg);
+    const int64_t nres = ntok_ + nenv_;
+    // device: table | carry (two copies) | results; pinned: table | results
+    const size_t o_carry = round_up64(16 * (size_t)ntok_, 64), carry_bytes = 2 * 2 * kCarryTable * sizeof(double), o_res = o_carry + carry_bytes,
+                 bytes = o_res + 16 * (size_t)nres, h_res = o_carry, h_bytes = h_res + 16 * (size_t)nres;
+    char* d = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes * 2, 32768), s));
+    char* h = static_cast<char*>(host_.reserve(h_bytes, std::max<size_t>(h_bytes * 2, 4096), s));
+    HIP_CHECK(hipStreamSynchronize(s));   // (an earlier stream's copies into the mirror are done)
+    d_seg_ = reinterpret_cast<int64_t*>(d);
+    d_carry_ = reinterpret_cast<double*>(d + o_carry);
+    d_res_ = reinterpret_cast<double*>(d + o_res);
+    res_host_ = reinterpret_cast<double*>(h + h_res);
+    std::memset(res_host_, 0, 16 * (size_t)nres);
+    if (ntok_) {
+        std::memcpy(h, seg, 16 * (size_t)ntok_);
+        HIP_CHECK(hipMemcpyAsync(d_seg_, h, 16 * (size_t)ntok_, hipMemcpyHostToDevice, s));
+    }
+    HIP_CHECK(hipMemsetAsync(d_carry_, 0, carry_bytes + 16 * (size_t)nres, s));
+}
+
+int64_t StreamLevels::tok_complete(int64_t D) const {
+    int64_t lo = 0, hi = ntok_;   // ends ascend: the first token with end > D
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) / 2;
+        if (seg_[2 * mid + 1] <= D) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+StreamLevels::Done StreamLevels::push(const void* x, int encoding, int64_t D0, int64_t n, hipStream_t s) {
+    SBV2_REQUIRE(pcm_encoding_known(encoding), "internal: levels of an unknown encoding");
+    SBV2_REQUIRE(n >= 0 && D0 == fed_ && D0 + n <= total_, "internal: a levels push of [" + std::to_string(D0) + ", " + std::to_string(D0 + n) +
+                                                               ") out of stream order (" + std::to_string(fed_) + " of " + std::to_string(total_) + " fed)");
+    const int64_t D1 = D0 + n;
+    fed_ = D1;
+    const int64_t tok_new = tok_complete(D1), env_new = env_complete(D1);
+    const Done done{tok_new - tok_done_, env_new - env_done_};
+    if (n > 0 && ntok_ + nenv_ > 0) {
+        SBV2_REQUIRE(x, "internal: no samples to push");
+        StreamLevelArgs a{};
+        a.x = x;
+        a.d0 = D0;
+        a.d1 = D1;
+        a.seg = d_seg_;
+        a.ntok = ntok_;
+        // tokens: every one before tok_done_ ended at or before D0; the push meets those that start before D1 (empty ones among them do nothing)
+        int64_t t1 = tok_done_;
+        while (t1 < ntok_ && seg_[2 * t1] < D1) ++t1;
+        a.tok_first = (int32_t)tok_done_;
+        a.tok_count = (int32_t)(t1 - tok_done_);
+        a.env_hop = env_hop_;
+        a.total = total_;
+        int64_t env_blocks = 0;
+        if (nenv_) {
+            a.env_first = D0 / env_hop_;
+            a.env_count = (int32_t)((D1 - 1) / env_hop_ - a.env_first + 1);
+            a.env_packed = env_hop_ <= Marks::kLongSegment;
+            env_blocks = a.env_packed ? (a.env_count + kWavesPerBlock - 1) / kWavesPerBlock : a.env_count;
+        }
+        a.carry_in = d_carry_ + (size_t)parity_ * 2 * kCarryTable;
+        a.carry_out = d_carry_ + (size_t)(parity_ ^ 1) * 2 * kCarryTable;
+        a.res = d_res_;
+        const int64_t blocks = a.tok_count + env_blocks;
+        if (blocks > 0) {
+            const dim3 grid((unsigned)blocks), blk(kBlock);
+            if (encoding == kEncS16) hipLaunchKernelGGL(k_stream_levels<int16_t>, grid, blk, 0, s, a);
+            else if (encoding == kEncMulaw) hipLaunchKernelGGL(k_stream_levels<MulawCode>, grid, blk, 0, s, a);
+            else if (encoding == kEncAlaw) hipLaunchKernelGGL(k_stream_levels<AlawCode>, grid, blk, 0, s, a);
+            else hipLaunchKernelGGL(k_stream_levels<float>, grid, blk, 0, s, a);
+            HIP_CHECK(hipGetLastError());
+            parity_ ^= 1;
+        }
+        // the slots this push completed -> the mirror (tokens and frames are two contiguous ranges of the one array)
+        if (done.tok) HIP_CHECK(hipMemcpyAsync(res_host_ + 2 * tok_done_, d_res_ + 2 * tok_done_, 16 * (size_t)done.tok, hipMemcpyDeviceToHost, s));
+        if (done.env)
+            HIP_CHECK(hipMemcpyAsync(res_host_ + 2 * (ntok_ + env_done_), d_res_ + 2 * (ntok_ + env_done_), 16 * (size_t)done.env, hipMemcpyDeviceToHost, s));
+    }
+    tok_done_ = tok_new;
+    env_done_ = env_new;
+    return done;
+}
+
 }  // namespace sbv2

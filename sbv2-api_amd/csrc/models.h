@@ -4,6 +4,7 @@
 #include "common.h"
 #include "flac_encode.h"
 #include "limiter.h"
+#include "marks.h"
 #include "ops.h"
 #include "pcm_format.h"
 
@@ -292,6 +293,11 @@ struct StreamTimeline {
 int64_t stream_min_gap(const PcmFmtSpec& spec);   // 2 ceil(half / L): no output sample on one side of a cut has a filter tap on the other side's row
 void stream_check_gaps(const int64_t* gap_after, int64_t n, const PcmFmtSpec& spec);
 StreamTimeline stream_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int hop, int64_t chunk_frames, const PcmFmtSpec& spec);
+// levels on a stream (sbv2_stream_levels, include/sbv2_hip.h)
+struct StreamMarksSpec {
+    bool tokens = false;
+    int64_t env_hop = 0;
+};
 struct VitsBatch {
     int n = 0;
     const int64_t* t_lens = nullptr;   // [n]
@@ -343,8 +349,13 @@ class VitsModel {
     // level (needs fmt): the formatter stops at y (f64), a StreamLimiter (limiter.h) takes it replay by replay at the fixed gain and holds the
     // ceiling; what it emits is cast / quantised and delivered (or, with flac, pushed into the encoder): delivery runs A samples behind
     // gap_after (needs fmt): [n] native samples of silence after each row of the forward, the rows joined as stream_timeline lays them out
+    // marks (needs fmt): levels per token and / or per envelope frame of the DELIVERED samples, reduced replay by replay (StreamLevels, marks.h):
+    // one push per replay on what crosses PCIe or enters the FLAC encoder; such a stream delivers in order only
     int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false, const StreamLevelSpec* level = nullptr,
-                         const int64_t* gap_after = nullptr);
+                         const int64_t* gap_after = nullptr, const StreamMarksSpec* marks = nullptr);
+    // a stream begun with marks: its reduction (nullptr otherwise) and the samples delivered so far (what the taken calls handed out)
+    const StreamLevels* stream_marks_levels() const { return smarks_on_ ? smarks_.get() : nullptr; }
+    int64_t stream_delivered() const { return sdelivered_; }
     const StreamTimeline& stream_layout() const { return stl_; }
     int64_t stream_call_bound() const;   // bytes that suffice for any one call of the running stream
     int64_t stream_chunk(int64_t ci, float* dst_host, int64_t capacity);
@@ -498,6 +509,9 @@ class VitsModel {
     bool slevel_on_ = false;                     // ... and level-controlled replay by replay (stream_begin with level; implies sfmt_on_)
     int64_t slevel_A_ = 0;                       // its look-ahead in delivered samples (0 without a level)
     std::shared_ptr<StreamLimiter> slim_;
+    bool smarks_on_ = false;                     // ... and its delivered samples are reduced to levels replay by replay (stream_begin with marks)
+    std::shared_ptr<StreamLevels> smarks_;
+    int64_t sdelivered_ = 0;                     // delivered samples the taken calls of a formatted stream handed out
     bool stream_bursts_ = false;                 // the running stream uses burst_ behind its first chunk
     std::shared_ptr<ChunkPlan> chunk_, burst_;   // one window (an utterance's first chunk) / kStreamBurst windows per replay (every later one)
     Plane z_{};              // flow output of the last forward (frame-rate plane, packed layout fl_)

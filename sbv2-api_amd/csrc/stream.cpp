@@ -18,6 +18,9 @@ struct sbv2_stream {
     // one sync, and the delivered format
     std::vector<int64_t> durations, offs;
     PcmFmtSpec spec;
+    // levels (sbv2_stream_begin_request_levels): the entries sbv2_stream_next_marks has handed out so far
+    bool levels = false;
+    int64_t tok_out = 0, env_out = 0;
 };
 
 namespace {
@@ -33,7 +36,7 @@ PcmFmtSpec flac_stream_spec(const sbv2_pcm_format* fmt) {
 // a plain stream (native f32, one row); gap_after == nullptr: one row without gaps.  Every check of the arguments has happened before.
 void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
                   int64_t chunk_frames, const PcmFmtSpec* spec, bool flac, const StreamLevelSpec* level, const int64_t* gap_after, sbv2_stream** out,
-                  int64_t* total_samples) {
+                  int64_t* total_samples, const StreamMarksSpec* marks = nullptr) {
     VitsBatch run = v;
     run.skip_decoder = true;
     pipeline_run_one(*bert->m, *vits->m, run, token_ids, s_lens, word2ph);
@@ -46,7 +49,8 @@ void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const in
     s->formatted = spec != nullptr;
     s->flac = flac;
     s->level = level != nullptr;
-    s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after);
+    s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after, marks);
+    s->levels = vits->m->stream_marks_levels() != nullptr;
     if (total_samples) *total_samples = pcm_format_out_len(s->spec, vits->m->stream_layout().joined);
     *out = s.release();
 }
@@ -268,10 +272,11 @@ int sbv2_stream_timeline(const int64_t* frames, const int64_t* gap_after, int64_
     API_END
 }
 
-int sbv2_stream_begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids,
-                              const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq, sbv2_stream** out,
-                              int64_t* total_samples) {
-    API_BEGIN
+namespace {
+// sbv2_stream_begin_request, with or without levels: every check before any GPU work
+void begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids, const int64_t* s_lens,
+                   const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq, const StreamMarksSpec* marks, sbv2_stream** out,
+                   int64_t* total_samples) {
     SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
     SBV2_REQUIRE(rq, "no sbv2_stream_request given");
     SBV2_REQUIRE(rq->gap_after, "sbv2_stream_request.gap_after must not be NULL (one entry per row, the last one = trailing silence)");
@@ -288,7 +293,69 @@ int sbv2_stream_begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch
     apply_utt_options(&v, opts);
     stream_check_gaps(rq->gap_after, batch->n, spec);
     begin_stream(bert, vits, v, token_ids, s_lens, word2ph, chunk_frames, &spec, rq->flac != 0, rq->level ? &lv : nullptr, rq->gap_after, out,
-                 total_samples);
+                 total_samples, marks);
+}
+}  // namespace
+
+int sbv2_stream_begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids,
+                              const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq, sbv2_stream** out,
+                              int64_t* total_samples) {
+    API_BEGIN
+    begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, nullptr, out, total_samples);
+    API_END
+}
+
+// The same stream with the levels of its delivered samples reduced replay by replay (StreamLevels, marks.hip).  lv NULL or all off: exactly the
+// call above.  The levels' fields are checked first, before the handles are looked at.
+int sbv2_stream_begin_request_levels(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids,
+                                     const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
+                                     const sbv2_stream_levels* lv, sbv2_stream** out, int64_t* total_samples, int64_t* n_tokens, int64_t* n_env) {
+    API_BEGIN
+    StreamMarksSpec marks;
+    if (lv) {
+        SBV2_REQUIRE(lv->reserved[0] == 0 && lv->reserved[1] == 0, "sbv2_stream_levels.reserved must be 0");
+        SBV2_REQUIRE(lv->tokens == 0 || lv->tokens == 1, "sbv2_stream_levels.tokens must be 0 or 1");
+        SBV2_REQUIRE(lv->env_hop >= 0, "sbv2_stream_levels.env_hop must be >= 0 (0 = no envelope)");
+        marks.tokens = lv->tokens == 1;
+        marks.env_hop = lv->env_hop;
+    }
+    const bool on = marks.tokens || marks.env_hop > 0;
+    begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples);
+    const StreamLevels* l = (*out)->vits->m->stream_marks_levels();
+    if (n_tokens) *n_tokens = l ? l->n_tok() : 0;
+    if (n_env) *n_env = l ? l->n_env() : 0;
+    API_END
+}
+
+// The levels completed since the previous call (the delivery rule above sbv2_stream_next_marks, include/sbv2_hip.h).  Host only: every entry
+// handed out was copied to the pinned mirror before the event of a replay whose samples the stream has already delivered.
+int sbv2_stream_next_marks(sbv2_stream* s, sbv2_stream_marks_part* part) {
+    API_BEGIN
+    SBV2_REQUIRE(s && part, "bad arguments");
+    SBV2_REQUIRE(s->levels, "this stream was begun without levels: begin it with sbv2_stream_begin_request_levels");
+    const StreamLevels* l = s->vits->m->stream_marks_levels();
+    SBV2_REQUIRE(l, "internal: the stream's level reduction is gone");
+    const int64_t D = s->next >= s->calls ? l->total() : s->vits->m->stream_delivered();
+    const int64_t nt = l->tok_complete(D) - s->tok_out, ne = l->env_complete(D) - s->env_out;
+    SBV2_REQUIRE(part->tok_capacity >= nt, "token arrays too small: " + std::to_string(part->tok_capacity) + " < " + std::to_string(nt) + " pending tokens");
+    SBV2_REQUIRE(part->env_capacity >= ne, "envelope arrays too small: " + std::to_string(part->env_capacity) + " < " + std::to_string(ne) + " pending frames");
+    SBV2_REQUIRE(nt == 0 || (part->tok_sumsq && part->tok_peak), "NULL token arrays with " + std::to_string(nt) + " pending tokens");
+    SBV2_REQUIRE(ne == 0 || (part->env_sumsq && part->env_peak), "NULL envelope arrays with " + std::to_string(ne) + " pending frames");
+    for (int64_t i = 0; i < nt; ++i) {
+        part->tok_sumsq[i] = l->tok_host()[2 * (s->tok_out + i)];
+        part->tok_peak[i] = l->tok_host()[2 * (s->tok_out + i) + 1];
+    }
+    for (int64_t i = 0; i < ne; ++i) {
+        part->env_sumsq[i] = l->env_host()[2 * (s->env_out + i)];
+        part->env_peak[i] = l->env_host()[2 * (s->env_out + i) + 1];
+    }
+    part->tok_first = s->tok_out;
+    part->n_tok = nt;
+    part->env_first = s->env_out;
+    part->n_env = ne;
+    part->delivered = D;
+    s->tok_out += nt;
+    s->env_out += ne;
     API_END
 }
 

@@ -1604,4 +1604,39 @@ int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n
     API_END
 }
 
+// The fed level reduction (StreamLevels, marks.hip) on its own: x cut at cuts[ncuts] into ncuts + 1 pushes, each handed the samples of its
+// piece only.  Segments, envelope and cuts are checked before any device call.
+int sbv2_debug_stream_levels(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, const int64_t* starts,
+                             const int64_t* ends, int64_t nseg, int32_t env_hop, double* seg_sumsq, double* seg_peak, double* env_sumsq,
+                             double* env_peak, int64_t* seg_per_push, int64_t* env_per_push) {
+    API_BEGIN
+    SBV2_REQUIRE(pcm_encoding_known(encoding) && n >= 0 && nseg >= 0 && ncuts >= 0 && (x || n == 0) && (ncuts == 0 || cuts), "bad arguments");
+    SBV2_REQUIRE(nseg == 0 || (starts && ends && seg_sumsq && seg_peak), "bad arguments");
+    SBV2_REQUIRE(seg_per_push && env_per_push, "bad arguments");
+    std::vector<int64_t> seg((size_t)(2 * nseg));
+    for (int64_t i = 0; i < nseg; ++i) seg[2 * i] = starts[i], seg[2 * i + 1] = ends[i];
+    StreamLevels::check(seg.data(), nseg, env_hop, n);
+    const int64_t nenv = StreamLevels::env_frames(env_hop, n);
+    SBV2_REQUIRE(nenv == 0 || (env_sumsq && env_peak), "bad arguments");
+    std::vector<int64_t> edge(1, 0);
+    for (int i = 0; i < ncuts; ++i) {
+        SBV2_REQUIRE(cuts[i] >= edge.back() && cuts[i] <= n, "cuts must ascend within [0, n]");
+        edge.push_back(cuts[i]);
+    }
+    edge.push_back(n);
+    const size_t esz = pcm_encoding_bytes(encoding);
+    AudioScratch r(device, x, (size_t)n * esz);
+    StreamLevels lv;
+    lv.begin(seg.data(), nseg, env_hop, n, r.s);
+    for (int i = 0; i <= ncuts; ++i) {
+        const StreamLevels::Done d = lv.push(r.x.as<char>() + (size_t)edge[i] * esz, encoding, edge[i], edge[i + 1] - edge[i], r.s);
+        seg_per_push[i] = d.tok;
+        env_per_push[i] = d.env;
+    }
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    for (int64_t i = 0; i < nseg; ++i) seg_sumsq[i] = lv.tok_host()[2 * i], seg_peak[i] = lv.tok_host()[2 * i + 1];
+    for (int64_t i = 0; i < nenv; ++i) env_sumsq[i] = lv.env_host()[2 * i], env_peak[i] = lv.env_host()[2 * i + 1];
+    API_END
+}
+
 }  // extern "C"

@@ -974,14 +974,17 @@ StreamTimeline stream_timeline(const int64_t* frames, const int64_t* gap_after, 
     return t;
 }
 
-int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac, const StreamLevelSpec* level, const int64_t* gap_after) {
+int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac, const StreamLevelSpec* level, const int64_t* gap_after,
+                                const StreamMarksSpec* marks) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(fl_.n >= 1 && z_.p, "stream_begin needs a preceding forward with skip_decoder");
     SBV2_REQUIRE(gap_after || fl_.n == 1, "stream_begin without gaps needs a preceding forward of ONE utterance");
     SBV2_REQUIRE(!gap_after || fmt, "a stream over several rows is a formatted stream");
     SBV2_REQUIRE(chunk_frames >= 16 && chunk_frames <= (1 << 20), "chunk_frames must be in [16, 2^20]");
-    sfmt_on_ = sflac_on_ = slevel_on_ = false;
+    sfmt_on_ = sflac_on_ = slevel_on_ = smarks_on_ = false;
     slevel_A_ = 0;
+    sdelivered_ = 0;
+    SBV2_REQUIRE(!marks || fmt, "levels on a stream need an output format: begin it with the identity format (44100 Hz f32) instead of none");
     SBV2_REQUIRE(!flac || (fmt && fmt->encoding == kEncS16), "a FLAC stream needs encoding = 1 (s16): f32 samples and G.711 codes have no FLAC form");
     SBV2_REQUIRE(!level || fmt, "a level stream needs an output format");
     if (fmt) {
@@ -997,6 +1000,8 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     const int64_t no_gap = 0;
     const std::vector<int64_t> frames(fl_.len.begin(), fl_.len.end());
     stl_ = stream_timeline(frames.data(), gap_after ? gap_after : &no_gap, fl_.n, cfg_.hop(), chunk_frames, fmt ? *fmt : PcmFmtSpec());
+    // (the envelope's frame count is refused here, before the stream has set up anything of its own)
+    if (marks && fmt) StreamLevels::check(nullptr, 0, marks->env_hop, pcm_format_out_len(*fmt, stl_.joined));
     if (fmt) {
         sfmt_ = *fmt;
         if (!sfmtr_) sfmtr_ = std::make_shared<PcmFormatter>();
@@ -1053,6 +1058,23 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
             if (!slim_) slim_ = std::make_shared<StreamLimiter>();
             slim_->begin(sfmt_.rate, total_out, (int64_t)(dev / sfmt_.bytes()), *level, stream_);
             slevel_on_ = true;
+        }
+        if (marks && (marks->tokens || marks->env_hop > 0)) {
+            // the token spans of all rows on the delivered timeline (what sbv2_stream_marks answers) and the frames, fixed before the first replay
+            std::vector<int64_t> seg;
+            if (marks->tokens) {
+                const int64_t ntok = (int64_t)used_host_.size();
+                std::vector<int64_t> st((size_t)ntok), en((size_t)ntok);
+                for (size_t i = 0; i + 1 < used_offs_.size(); ++i) {
+                    const int64_t o = used_offs_[i];
+                    marks_spans(used_host_.data() + o, used_offs_[i + 1] - o, cfg_.hop(), stl_.place[i], sfmt_, st.data() + o, en.data() + o);
+                }
+                seg.resize((size_t)(2 * ntok));
+                for (int64_t i = 0; i < ntok; ++i) seg[2 * i] = st[i], seg[2 * i + 1] = en[i];
+            }
+            if (!smarks_) smarks_ = std::make_shared<StreamLevels>();
+            smarks_->begin(seg.data(), (int64_t)seg.size() / 2, marks->env_hop, total_out, stream_);
+            smarks_on_ = true;
         }
         sfmt_on_ = true;
     }
@@ -1129,6 +1151,7 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
             total = em;
             void* dev = sflac_on_ ? static_cast<void*>(sflac_->dst()) : sfmtr_->out_buffer(dev_bytes, stream_);
             pcm_cast(slim_->out_buffer(), em, slim_->unit(), sfmt_.encoding, dev, stream_);
+            if (smarks_on_) smarks_->push(dev, sfmt_.encoding, e0, em, stream_);   // (before the encoder's push moves its tail)
             if (sflac_on_) {
                 const int64_t t0 = sflac_->tail();
                 c.flac_push[slot] = sflac_->push(em, last, c.host[slot], stream_);
@@ -1145,6 +1168,7 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
             // request's last chunk also the short final frame).  Window w completes frames [flac_fr[w], flac_fr[w + 1]) of the push.
             const int64_t t0 = sflac_->tail();
             sfmtr_->run(sfmt_, pieces, sig, total, sflac_->dst(), (&c == burst_.get() ? 2 : 0) + slot, stream_);
+            if (smarks_on_) smarks_->push(sflac_->dst(), sfmt_.encoding, sig.empty() ? smarks_->fed() : sig[0].j0, total, stream_);   // (before the push moves the tail)
             c.flac_push[slot] = sflac_->push(total, last, c.host[slot], stream_);
             c.flac_fr[slot].assign(1, 0);
             for (size_t w = 0; w < c.fmt_n[slot].size(); ++w) {
@@ -1154,6 +1178,7 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
         } else {
             void* dev = sfmtr_->out_buffer(dev_bytes, stream_);
             sfmtr_->run(sfmt_, pieces, sig, total, dev, (&c == burst_.get() ? 2 : 0) + slot, stream_);
+            if (smarks_on_) smarks_->push(dev, sfmt_.encoding, sig.empty() ? smarks_->fed() : sig[0].j0, total, stream_);
             if (total) HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)total * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
         }
         HIP_CHECK(hipEventRecord(c.ev[slot], stream_));
@@ -1258,11 +1283,13 @@ int64_t VitsModel::stream_take(int64_t ci, void* dst, int64_t capacity_bytes, bo
         const int slot = (int)(ci & 1);
         SBV2_REQUIRE(!slevel_on_ || c1.slot_ci[slot] == ci, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
         SBV2_REQUIRE(!flac_bytes || c1.slot_ci[slot] == ci, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
+        SBV2_REQUIRE(!smarks_on_ || c1.slot_ci[slot] == ci, "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk");
         if (c1.slot_ci[slot] != ci) stream_enqueue(c1, ci, slot);                                  // (random access: not the streaming order)
         if (!bursts && ci + 1 < ncalls && c1.slot_ci[slot ^ 1] != ci + 1) stream_enqueue(c1, ci + 1, slot ^ 1);
         HIP_CHECK(hipEventSynchronize(c1.ev[slot]));
         const int64_t n = deliver(c1, slot, 0);
         c1.slot_ci[slot] = -1;
+        if (formatted) sdelivered_ += n;
         return n;
     }
     ChunkPlan& cb = *burst_;
@@ -1271,12 +1298,15 @@ int64_t VitsModel::stream_take(int64_t ci, void* dst, int64_t capacity_bytes, bo
     const int slot = (int)(bi & 1);
     SBV2_REQUIRE(!slevel_on_ || cb.slot_ci[slot] == b0, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
     SBV2_REQUIRE(!flac_bytes || cb.slot_ci[slot] == b0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
+    SBV2_REQUIRE(!smarks_on_ || cb.slot_ci[slot] == b0, "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk");
     if (cb.slot_ci[slot] != b0) stream_enqueue(cb, b0, slot);                                    // (random access)
     // the following burst is decoded while this one is delivered (its slot was drained one burst ago)
     const int64_t n0 = b0 + cb.nwin;
     if (within == 0 && n0 < ncalls && cb.slot_ci[slot ^ 1] != n0) stream_enqueue(cb, n0, slot ^ 1);
     HIP_CHECK(hipEventSynchronize(cb.ev[slot]));
-    return deliver(cb, slot, within);
+    const int64_t n = deliver(cb, slot, within);
+    if (formatted) sdelivered_ += n;
+    return n;
 }
 
 void VitsModel::copy_pcm(float* host) {

@@ -427,6 +427,26 @@ def marks_spans(durations, hop: int, place: int, fmt: PcmFormat):
     return st, en
 
 
+def debug_stream_levels(x, cuts, starts, ends, env_hop: int = 0, device: int = 0, encoding: str | None = None):
+    """Test hook: the fed level reduction on its own (sbv2_debug_stream_levels).  x as for debug_segment_levels, cut at the ascending positions
+    `cuts` into len(cuts) + 1 pushes; segments monotone and disjoint -> (sumsq, peak, env_sumsq, env_peak, seg_per_push, env_per_push)."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if encoding is None and x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"levels are taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"levels of {encoding!r} samples are not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
+    st, en, cuts = (np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1)) for a in (starts, ends, cuts))
+    nenv = -(-x.size // int(env_hop)) if env_hop > 0 else 0
+    ss, pk, es, ep = (np.zeros(max(n, 1), np.float64) for n in (st.size, st.size, nenv, nenv))
+    sp, epp = np.zeros(cuts.size + 1, np.int64), np.zeros(cuts.size + 1, np.int64)
+    check(_lib.lib().sbv2_debug_stream_levels(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size,
+                                              cuts.ctypes.data_as(i64p) if cuts.size else None, cuts.size, st.ctypes.data_as(i64p),
+                                              en.ctypes.data_as(i64p), st.size, int(env_hop), _f64p(ss), _f64p(pk), _f64p(es), _f64p(ep),
+                                              sp.ctypes.data_as(i64p), epp.ctypes.data_as(i64p)))
+    return ss[:st.size], pk[:st.size], es[:nenv], ep[:nenv], sp, epp
+
+
 def debug_segment_levels(x, starts, ends, device: int = 0, encoding: str | None = None):
     """Test hook: the device level reduction on host samples x (int16 or float32; uint8 G.711 codes with encoding "mulaw" / "alaw") ->
     (sumsq, peak) per segment [starts[i], ends[i])."""
@@ -745,12 +765,20 @@ class StreamHandle:
     level (StreamLevel; needs fmt, any encoding; flac with s16 only): the samples pass a fixed gain and the look-ahead limiter on the device,
     carried from chunk to chunk.  Delivery runs stream_level_lookahead(fmt) samples behind the chunks: next() returns what the chunk
     completed (possibly an empty array or b""), the last chunk everything; samples_taken counts the chunks' samples; level_stats() after
-    the end."""
+    the end.
+    levels=True / env_hop > 0 (delivered samples per envelope frame): the levels of the delivered samples per token / per frame are reduced on
+    the device chunk by chunk (sbv2_stream_begin_request_levels); next_marks() hands out what the pieces taken so far completed.  A single
+    utterance then runs as the request stream with gaps=[0] (the same code, the same bytes; fmt None = 44.1 kHz f32)."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
-                 level: "StreamLevel | None" = None, gaps=None, **kw):
+                 level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, **kw):
         l = _lib.lib()
         self.request = isinstance(utt, (list, tuple))
+        self.levels, self.env_hop, self.n_tokens, self.n_env, self._marks_buf = bool(levels), int(env_hop), 0, 0, None
+        if (self.levels or self.env_hop) and not self.request:
+            if gaps is not None:
+                raise Sbv2Error("gaps= belongs to a stream over a list of utterances")
+            utt, gaps, self.request = [utt], [0], True
         self.b = Pipeline.prepare(None, list(utt) if self.request else [utt], **kw)
         self.h = C.c_void_p()
         self.fmt, self.flac, self.level, self.samples_taken = fmt, bool(flac), level, 0
@@ -768,8 +796,14 @@ class StreamHandle:
                 raise Sbv2Error(f"gaps must hold one entry per utterance ({len(utt)})")
             rq = _lib.Sbv2StreamRequest(gp, C.pointer(fmt.c) if fmt is not None else None, C.pointer(level.c) if level is not None else None,
                                         int(self.flac), 0)
-            check(l.sbv2_stream_begin_request(args[0], args[1], args[2], C.byref(self.b.opts) if self.b.opts is not None else None, *args[3:],
-                                              C.byref(rq), C.byref(self.h), C.byref(tot)))
+            opts = C.byref(self.b.opts) if self.b.opts is not None else None
+            if self.levels or self.env_hop:
+                lv, nt, ne = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)), C.c_int64(), C.c_int64()
+                check(l.sbv2_stream_begin_request_levels(args[0], args[1], args[2], opts, *args[3:], C.byref(rq), C.byref(lv), C.byref(self.h),
+                                                         C.byref(tot), C.byref(nt), C.byref(ne)))
+                self.n_tokens, self.n_env = nt.value, ne.value
+            else:
+                check(l.sbv2_stream_begin_request(args[0], args[1], args[2], opts, *args[3:], C.byref(rq), C.byref(self.h), C.byref(tot)))
             if fmt is None:
                 self.fmt = PcmFormat(44100, "f32")
             self.buf = np.empty(max(int(l.sbv2_stream_call_bound(self.h)), 1), np.uint8)
@@ -825,9 +859,21 @@ class StreamHandle:
         check(_lib.lib().sbv2_stream_level_stats(self.h, _f64p(st)))
         return float(st[0]), float(st[1])
 
+    def next_marks(self):
+        """(tok_first, sumsq, peak, env_first, env_sumsq, env_peak, delivered): the levels that the pieces taken since the previous call completed
+        (sbv2_stream_next_marks; host only).  Tokens [tok_first, tok_first + len(sumsq)) in the numbering of marks(), frames likewise; delivered =
+        the samples the stream has handed out so far.  Refused on a stream begun without levels=True / env_hop."""
+        if self._marks_buf is None:   # (sized for the whole stream once: a call hands out what is pending, at most everything)
+            self._marks_buf = [np.zeros(max(n, 1), np.float64) for n in (self.n_tokens, self.n_tokens, self.n_env, self.n_env)]
+        ts, tp, es, ep = self._marks_buf
+        part = _lib.Sbv2StreamMarksPart(self.n_tokens, _f64p(ts), _f64p(tp), 0, 0, self.n_env, _f64p(es), _f64p(ep), 0, 0, 0)
+        check(_lib.lib().sbv2_stream_next_marks(self.h, C.byref(part)))
+        return (int(part.tok_first), ts[:part.n_tok].copy(), tp[:part.n_tok].copy(), int(part.env_first), es[:part.n_env].copy(),
+                ep[:part.n_env].copy(), int(part.delivered))
+
     def marks(self):
         """(start, end): the spans of the utterance's tokens in delivered samples of this stream (sbv2_stream_marks; host only, complete from
-        the moment the stream exists).  Streams carry no levels."""
+        the moment the stream exists).  The levels come piece by piece: next_marks()."""
         n = int(np.asarray(self.b.t_lens).sum())   # (a request stream: the tokens of all rows, row after row)
         st, en, got = np.zeros(n, np.int64), np.zeros(n, np.int64), C.c_int64()
         check(_lib.lib().sbv2_stream_marks(self.h, st.ctypes.data_as(i64p), en.ctypes.data_as(i64p), n, C.byref(got)))

@@ -313,10 +313,48 @@ class SynthesisStream:
     the pieces run out, when one fails, by close(), and when the object is dropped, iterated or not: the replays of a stream are already
     enqueued when this object is returned, so its end cannot hang on a generator's `finally`, which never runs for a generator nobody started."""
 
-    def __init__(self, st, head, to_bytes, marks=None, tail=None):
+    def __init__(self, st, head, to_bytes, marks=None, tail=None, levels=None):
         self._st, self._head, self._to_bytes, self._tail = st, head, to_bytes, tail   # tail: bytes that follow the last chunk (a pad byte)
-        self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece (streams carry no levels)
+        self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece
         self.level_stats = None   # a level stream's (deepest reduction in dB, max |x|), once its last piece has been handed out
+        # levels=(fmt, env_hop, total_samples): the stream was begun with levels (easy_synthesize_stream(levels=True)); take_marks() hands out
+        # what the pieces so far completed, and once the last piece is out `.marks` holds them all, in marks_dict's shape
+        self._levels, self.delivered = levels, 0
+        self.total_samples = int(getattr(st, "total_samples", 0))   # delivered samples of the whole answer
+        self._new_tokens, self._new_env, self._env_first = [], ([], []), 0
+        if levels is not None and levels[1] > 0:
+            self.marks["envelope"] = {"hop": int(levels[1]), "level_dbfs": [], "peak": []}
+
+    def _collect(self):
+        """The levels the handle has completed since the last look -> `.marks` and the lists take_marks() hands out next."""
+        if self._levels is None or self._st is None:
+            return
+        fmt, hop, total = self._levels
+        full = model.full_scale(fmt.encoding)
+        t0, ss, pk, f0, es, ep, self.delivered = self._st.next_marks()
+        for i, (s, p) in enumerate(zip(ss, pk)):
+            tok = self.marks["tokens"][t0 + i]
+            tok["level_dbfs"], tok["peak"] = model.level_dbfs(s, tok["end"] - tok["start"], fmt.encoding), float(p) / full
+            self._new_tokens.append({"token": t0 + i, "level_dbfs": tok["level_dbfs"], "peak": tok["peak"]})
+        for i, (s, p) in enumerate(zip(es, ep)):
+            db = model.level_dbfs(s, min(hop, total - (f0 + i) * hop), fmt.encoding)   # (the last frame may be short)
+            for lst, v in ((self.marks["envelope"]["level_dbfs"], db), (self.marks["envelope"]["peak"], float(p) / full),
+                           (self._new_env[0], db), (self._new_env[1], float(p) / full)):
+                lst.append(v)
+
+    def take_marks(self) -> dict:
+        """JSON-ready: the levels that the pieces handed out so far have completed and that no earlier call returned.  {"delivered": samples out
+        so far, "tokens": [{"token": its index in .marks["tokens"], "level_dbfs", "peak"}, ...], "envelope": {"first", "hop", "level_dbfs" [n],
+        "peak" [n]} (with an envelope)}.  A token is complete once its last sample has been delivered, a frame likewise."""
+        if self._levels is None:
+            raise model.Sbv2Error("this stream was begun without levels (easy_synthesize_stream(levels=True))")
+        self._collect()
+        d = {"delivered": int(self.delivered), "tokens": self._new_tokens}
+        if self._levels[1] > 0:
+            d["envelope"] = {"first": self._env_first, "hop": int(self._levels[1]), "level_dbfs": self._new_env[0], "peak": self._new_env[1]}
+            self._env_first += len(self._new_env[0])
+        self._new_tokens, self._new_env = [], ([], [])
+        return d
 
     def __iter__(self):
         return self
@@ -329,6 +367,7 @@ class SynthesisStream:
             while self._st is not None:
                 c = self._st.next()
                 if c is None:
+                    self._collect()     # (everything is complete now: what take_marks() has not seen yet waits for its next call)
                     if getattr(self._st, "level", None) is not None:
                         self.level_stats = self._st.level_stats()
                     st, self._st = self._st, None
@@ -365,7 +404,7 @@ class SynthesisStream:
 
 
 def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
-                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False):
+                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False, levels=False):
     """easy_synthesize delivered while it is synthesised: an iterator (SynthesisStream; close() it when it is abandoned early) over the pieces
     of the request's container.  The forward (DeBERTa / text / flow) runs once over the whole request, then the decoder runs chunk by chunk
     (model.StreamHandle).
@@ -388,7 +427,11 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     the iterator's `.level_stats` holds (deepest reduction in dB, max |x|).
     Everything up to the first replay (options, DeBERTa, flow, the header) runs before the iterator is returned.
     The iterator's `.marks` holds the token and word timing of every row with its line number (token_marks: every duration is known before
-    the first replay)."""
+    the first replay).
+    levels=True: the levels of the delivered samples per token, and with options.envelope_hz per envelope frame, are reduced on the device
+    chunk by chunk (model.StreamHandle(levels=True, env_hop=...)): the iterator's take_marks() returns what the pieces so far completed, and
+    once the last piece is out `.marks` has marks_dict's shape.  The audio bytes are those of the same call without levels (the default,
+    which ignores envelope_hz).  On a level stream (gain_db) the levels are those of the samples the limiter emits."""
     options = options or SynthesizeOptions()
     if options.normalize:
         raise model.Sbv2Error("a stream cannot normalise: the peak needs the whole signal (use /synthesize)")
@@ -409,6 +452,8 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     level = model.StreamLevel(options.gain_db, options.true_peak_max) if options.gain_db is not None else None
     kw = dict(fmt=None if fmt.is_default and level is None else fmt, flac=flac, level=level, sdp_ratio=options.sdp_ratio,
               length_scale=options.length_scale, noise_scale=noise_scale, noise_scale_w=noise_scale_w, noise_seed=noise_seed)
+    if levels:
+        kw.update(levels=True, env_hop=envelope_hop(options, fmt.sample_rate))   # (a bad envelope_hz is refused before any GPU work)
     if split:
         lines = [i for i, s in enumerate(sentences) if s]
         gaps = [SENTENCE_GAP if i != len(sentences) - 1 else 0 for i in lines]
@@ -421,9 +466,10 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     except BaseException:
         st.close()
         raise
+    lv = (fmt, kw["env_hop"], st.total_samples) if levels else None
     if flac:
-        return SynthesisStream(st, None, lambda c: c, marks)
+        return SynthesisStream(st, None, lambda c: c, marks, levels=lv)
     dtype = {"s16": "<i2", "f32": "<f4"}.get(fmt.encoding, "u1")
     pad = b"\0" if fmt.encoding in G711_TAGS and st.total_samples & 1 else None
     return SynthesisStream(st, wav_stream_header(fmt.sample_rate, fmt.encoding, st.total_samples),
-                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad)
+                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad, levels=lv)

@@ -19,7 +19,15 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     marks = true (new, default false): the response carries the header X-Speech-Marks, compact JSON {"sample_rate", "tokens":
                     [[line, index, phone, start, end], ...], "words": [[line, index, start, end], ...]} in delivered samples: the timing of the
                     whole utterance, known before the first audio byte (a header rather than a leading body part: the body stays the audio alone).
-                    No levels on a stream.  A server in front may cap header sizes: very long texts should ask /synthesize_marks instead.
+                    No levels on this route (the body stays the audio alone): /synthesize_stream_marks.  A server in front may cap header
+                    sizes: very long texts should ask /synthesize_marks or /synthesize_stream_marks instead.
+  POST /synthesize_stream_marks  new: the body of /synthesize_stream (its marks field is ignored) plus envelope_hz = null -> application/x-ndjson,
+                    one JSON object per line while the request is synthesised.  First line {"media_type", "sample_rate", "total_samples",
+                    "marks": the timing of the whole answer (orchestrator.token_marks)}.  Then one line per piece of /synthesize_stream's body
+                    {"audio": base64 of that piece, "delivered": samples out so far, "tokens": [{"token", "level_dbfs", "peak"}, ...],
+                    "envelope": {"first", "hop", "level_dbfs", "peak"} (with envelope_hz)}: the levels of the tokens and envelope frames whose
+                    last sample that piece delivered, reduced on the device chunk by chunk.  The pieces' audio concatenates to /synthesize_stream's
+                    body; the last line's delivered equals total_samples.  Same lock and closing discipline as /synthesize_stream.
   POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
@@ -81,6 +89,28 @@ class _HeldPieces:
             pass
 
 
+class _MarksLines:
+    """The NDJSON lines of /synthesize_stream_marks over an orchestrator.SynthesisStream begun with levels: the opening line, then one line per
+    piece with the levels that piece completed.  close() closes the stream (_HeldPieces calls it, once, however the response ends)."""
+
+    def __init__(self, pieces, media_type, sample_rate, total_samples):
+        self._pieces, self.close = pieces, pieces.close
+        self._first = {"media_type": media_type, "sample_rate": sample_rate, "total_samples": total_samples,
+                       "marks": {k: pieces.marks[k] for k in ("sample_rate", "tokens", "words")}}
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._first is not None:
+            # (the timing as it stands before the first piece: the levels follow line by line)
+            line, self._first = json.dumps(self._first), None
+            return (line + "\n").encode()
+        audio = next(self._pieces)
+        d = self._pieces.take_marks()
+        return (json.dumps({"audio": base64.b64encode(audio).decode("ascii"), **d}) + "\n").encode()
+
+
 def make_app(holder, batching=None):
     """batching None: one request at a time, as the reference.  A dict of batcher.RequestBatcher keyword arguments (max_utts, max_symbols,
     max_wait_ms; {} = the defaults): /synthesize holds the lock only while the request is parsed and queued, then awaits its answer, so
@@ -114,6 +144,9 @@ def make_app(holder, batching=None):
     class SynthesizeStreamRequest(SynthesizeRequest):
         marks: bool = False                 # the utterance's timing in the X-Speech-Marks response header
         split_sentences: bool = False       # the text's lines as sentences of one batched run, streamed one after the other with /synthesize's pauses
+
+    class SynthesizeStreamMarksRequest(SynthesizeStreamRequest):
+        envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
 
     class _ClosingStream(StreamingResponse):
         """A StreamingResponse that closes its _HeldPieces when the response is over, however it ends: sent to the end, cut by the client's
@@ -210,5 +243,25 @@ def make_app(holder, batching=None):
                 raise
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
         return _ClosingStream(held, media_type="audio/flac" if req.encoding == "flac" else "audio/wav", headers=headers)
+
+    @app.post("/synthesize_stream_marks")
+    def synthesize_stream_marks(req: SynthesizeStreamMarksRequest):
+        lock.acquire()                        # as /synthesize_stream: given back by _HeldPieces.close when the response is over
+        try:
+            pieces = holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), levels=True,
+                                                   **({"split": True} if req.split_sentences else {}))
+            try:
+                lines = _MarksLines(pieces, "audio/flac" if req.encoding == "flac" else "audio/wav", pieces.marks["sample_rate"],
+                                    pieces.total_samples)
+            except BaseException:
+                pieces.close()
+                raise
+            held = _HeldPieces(lock, lines)
+        except BaseException as e:            # before the first byte: the same mapping
+            lock.release()
+            if not isinstance(e, Exception):
+                raise
+            return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
+        return _ClosingStream(held, media_type="application/x-ndjson")
 
     return app
