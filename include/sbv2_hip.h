@@ -363,6 +363,48 @@ int sbv2_marks_spans(const int64_t* durations, int64_t n_tokens, int32_t hop, in
 int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n, const int64_t* starts, const int64_t* ends, int64_t nseg,
                               double* sumsq, double* peak);
 
+/* ---- new: the pitch contour of a delivered signal.  How high the voice is, frame by frame, estimated on the device from the samples the
+ * speech marks are taken of: YIN (de Cheveigne & Kawahara 2002, steps 2 - 5), stated so that it is reproducible.
+ * Input.  The delivered samples v[0 .. n) of ONE signal at rate sr, read as the levels read them (f32 values, s16 integers, or the integers
+ *   that G.711 codes decode to); positions outside [0, n) read as 0.  Parameters hop >= 1, f0_min, f0_max, threshold with
+ *   40 <= f0_min < f0_max <= sr / 4 and 0 < threshold < 1 (everything else is refused).
+ * Frames.  tau_min = floor(sr / f0_max), tau_max = ceil(sr / f0_min), W = tau_max; n_frames = ceil(n / hop) (0 for n = 0); frame f has its
+ *   centre at f hop + hop / 2 (integer division) and its window starts at b = centre - tau_max.
+ * Per frame.  d(tau) = sum_{j < W} (v[b + j] - v[b + j + tau])^2 for tau = 1 .. tau_max; S(tau) = sum_{k <= tau} d(k);
+ *   c(tau) = double(d(tau)) double(tau) / double(S(tau)), and c(tau) = 1 where S(tau) = 0.
+ * Decision.  The smallest tau in [tau_min, tau_max] with c(tau) < threshold, then tau is increased while tau + 1 <= tau_max and
+ *   c(tau + 1) < c(tau): that is the lag, and the frame is voiced.  If no tau qualifies the frame is unvoiced and its lag is the smallest tau
+ *   in range that attains min c.
+ * Result.  The device gives lag, voiced and c- = c(lag - 1), c0 = c(lag), c+ = c(lag + 1) (a neighbour outside [1, tau_max] is replaced by
+ *   c0); the HOST computes in plain f64 arithmetic, never contracted: den = c- - 2 c0 + c+; delta = 0.5 (c- - c+) / den if den > 0 and both
+ *   neighbours exist, else 0; f0 = voiced ? sr / (lag + delta) : 0; ap = c0 (the aperiodicity: near 0 for a clean periodic frame).
+ * Bits.  For the integer encodings d and S are formed in 64-bit integers.  With |v| <= 32768 and tau_max <= 1200 (the 40 Hz floor at 48 kHz)
+ *   d tau and S stay below 2^53 (6.2e15 < 9.0e15), so c has exactly one rounding, its division: lag, voiced and the three c values do not
+ *   depend on the order of any sum and equal a restatement in int64 / f64 bit for bit.  For f32 samples differences and squares are taken in
+ *   f64 in an order the library fixes; only that order is its own (f32 samples that are s16 integers / 32768 still give the s16 bits).
+ * Not done: smoothing across frames (octave errors are the caller's to treat, with ap), pitch on a stream. */
+typedef struct sbv2_pitch {
+    int32_t hop; int32_t reserved;        /* in: delivered samples per frame (>= 1); reserved must be 0 */
+    double f0_min, f0_max, threshold;     /* in: Hz, Hz, (0, 1); usual values 70, 600, 0.15 */
+    int64_t capacity;                     /* in: entries each given array holds */
+    double* f0;                           /* out: Hz, 0 for an unvoiced frame; must not be NULL */
+    double* ap;                           /* out, may be NULL: c(lag) */
+    int32_t* lag;                         /* out, may be NULL */
+    int64_t n_frames;                     /* out: ceil(out_len / hop) */
+} sbv2_pitch;
+/* sbv2_pipeline_fetch_request_marks that also fills *pitch: the contour of the delivered signal of the request (every gain / sink combination,
+ * FLAC included), one more launch before the fetch's only synchronisation.  pitch == NULL is exactly sbv2_pipeline_fetch_request_marks (marks
+ * may be NULL either way); with pitch the audio bytes, out_count, stats and marks are those of the same call without, and two fetches of one
+ * ticket give identical bits.  The caller's arrays are written only after everything else has succeeded.  Refused with nothing written,
+ * besides everything that call refuses: parameters outside the ranges above, capacity < n_frames, a NULL f0, a non-zero reserved. */
+int sbv2_pipeline_fetch_request_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
+                                      int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch);
+/* Host only: tau_min and tau_max of a rate and a range, under the checks above (0 < sample_rate <= 48000). */
+int sbv2_pitch_lags(int32_t sample_rate, double f0_min, double f0_max, int32_t* tau_min, int32_t* tau_max);
+/* Test hook: the estimator on host samples x[n] (encoding as sbv2_debug_segment_levels).  pitch: parameters in, f0 / ap / lag / n_frames out as
+ * in the fetch; cmnd3 [n_frames][3] (c-, c0, c+) and voiced [n_frames] may be NULL. */
+int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, double* cmnd3, int32_t* voiced);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,

@@ -76,6 +76,13 @@ class Sbv2Marks(C.Structure):
                 ("env_capacity", C.c_int64), ("env_sumsq", C.POINTER(C.c_double)), ("env_peak", C.POINTER(C.c_double)), ("n_env", C.c_int64)]
 
 
+class Sbv2Pitch(C.Structure):
+    """struct sbv2_pitch (include/sbv2_hip.h)."""
+    _fields_ = [("hop", C.c_int32), ("reserved", C.c_int32), ("f0_min", C.c_double), ("f0_max", C.c_double), ("threshold", C.c_double),
+                ("capacity", C.c_int64), ("f0", C.POINTER(C.c_double)), ("ap", C.POINTER(C.c_double)), ("lag", C.POINTER(C.c_int32)),
+                ("n_frames", C.c_int64)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -114,6 +121,11 @@ SYMBOLS = {
     "sbv2_pipeline_fetch_request": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double)]),
     "sbv2_pipeline_fetch_request_marks": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.c_void_p, C.c_int64, i64p,
                                                     C.POINTER(C.c_double), C.POINTER(Sbv2Marks)]),
+    "sbv2_pipeline_fetch_request_pitch": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.c_void_p, C.c_int64, i64p,
+                                                    C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_pitch_lags": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sbv2_debug_pitch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2Pitch), C.POINTER(C.c_double),
+                                   C.POINTER(C.c_int32)]),
     "sbv2_marks_spans": (C.c_int, [i64p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, i64p]),
     "sbv2_debug_segment_levels": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, i64p, i64p, C.c_int64, C.POINTER(C.c_double),
                                             C.POINTER(C.c_double)]),

@@ -95,6 +95,9 @@ class RequestBatcher:
             self._check(plan.options)
             if req.marks:
                 orchestrator.envelope_hop(plan.options, plan.fmt.sample_rate)
+                orchestrator.pitch_options(plan.options, plan.fmt.sample_rate)
+            else:
+                orchestrator.refuse_pitch(plan.options, "a request without marks (/synthesize)")
             seed = model.fresh_noise_seed() if seed is None else seed
             for j, u in enumerate(plan.utts):   # noise_index restarts per request: the keys of the request run alone
                 u.update(sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=orchestrator.NOISE_SCALE,

@@ -509,6 +509,15 @@ static MarksPlan plan_marks(const sbv2_marks* m, const PcmFmtSpec& spec, const V
     return mp;
 }
 
+// The checks of sbv2_pitch that need no run: the parameters at the delivered rate (marks.h states the bounds), the arrays.
+static PitchSpec check_pitch_static(const sbv2_pitch* q, int rate) {
+    SBV2_REQUIRE(q->reserved == 0, "sbv2_pitch.reserved must be 0");
+    const PitchSpec sp = pitch_spec(rate, q->hop, q->f0_min, q->f0_max, q->threshold);
+    SBV2_REQUIRE(q->capacity >= 0, "negative sbv2_pitch capacity");
+    SBV2_REQUIRE(q->f0, "sbv2_pitch.f0 must not be NULL");
+    return sp;
+}
+
 // The run's packed PCM (pcm_device + pcm_offs / pcm_lens) is formatted on the run's own stream and crosses PCIe in the format: every
 // check first (format, gain options, ticket, placement, PCM capacity), then the formatter's launches with the gain stage between the
 // resampler and the quantiser, then the sink.  out_counts: samples (PCM) or bytes (FLAC) of each signal; stats (may be NULL): the gain
@@ -516,9 +525,10 @@ static MarksPlan plan_marks(const sbv2_marks* m, const PcmFmtSpec& spec, const V
 // utts (with place): the one signal of those rows only.
 // marks (with utts): the speech marks of that signal; their reduction reads the delivered samples in HBM, on the same stream, before the one
 // synchronisation of the fetch, and the caller's arrays are written only once everything else has succeeded.
+// pitch (with utts): the pitch contour of the same delivered samples (Pitch, marks.h), enqueued and written under the same two rules.
 static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
                             int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats,
-                            const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr) {
+                            const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr) {
     const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
     const LoudnessSpec ln = gain.kind == FetchGain::kLoudness ? loudness_spec(gain.ln) : LoudnessSpec();
     const LimiterSpec lim = gain.kind == FetchGain::kLimiter ? limiter_spec(gain.lim) : LimiterSpec();
@@ -536,6 +546,15 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
     const MarksPlan mp = marks ? plan_marks(marks, spec, vm, utts, n_utts, place, total) : MarksPlan();
     const int64_t nseg = (int64_t)mp.seg.size() / 2;
     bool marks_ran = false;
+    PitchSpec ps;
+    int64_t n_pitch = 0;
+    if (pitch) {
+        SBV2_REQUIRE(utts && place, "internal: pitch needs a request's rows");
+        ps = check_pitch_static(pitch, spec.rate);
+        n_pitch = pitch_frames(total, ps.hop);
+        SBV2_REQUIRE(pitch->capacity >= n_pitch,
+                     "pitch arrays too small: " + std::to_string(pitch->capacity) + " < " + std::to_string(n_pitch) + " frames");
+    }
     HIP_CHECK(hipSetDevice(vm.device()));
     OutputChain& c = p->chains[ctx];
     const hipStream_t s = vm.stream();
@@ -551,6 +570,7 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
             c.marks.run(dev, spec.encoding, total, mp.seg.data(), nseg, s);
             marks_ran = true;
         }
+        if (n_pitch > 0) c.pitch.run(dev, spec.encoding, total, ps, s);
         if (sink == Sink::kFlac) {   // the signals stay in HBM; the encoder reads the stream sizes back, then exactly the encoded bytes cross PCIe
             std::vector<int64_t> offs(outs.size());
             for (size_t i = 1; i < outs.size(); ++i) offs[i] = offs[i - 1] + outs[i - 1];
@@ -583,6 +603,14 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         }
         marks->n_tokens = mp.n_tok;
         marks->n_env = mp.n_env;
+    }
+    if (pitch) {   // (an empty signal has no frames and ran nothing)
+        for (int64_t f = 0; f < n_pitch; ++f) {
+            const int32_t lag = c.pitch.lag_host()[f];
+            pitch_finish(ps, lag, c.pitch.voiced_host()[f], c.pitch.c3_host() + 3 * f, pitch->f0 + f, pitch->ap ? pitch->ap + f : nullptr);
+            if (pitch->lag) pitch->lag[f] = lag;
+        }
+        pitch->n_frames = n_pitch;
     }
 }
 
@@ -654,8 +682,8 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
     API_END
 }
 
-int sbv2_pipeline_fetch_request_marks(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
-                                      int64_t* out_count, double* stats, sbv2_marks* marks) {
+int sbv2_pipeline_fetch_request_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
+                                      int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch) {
     API_BEGIN
     SBV2_REQUIRE(req && req->n_utts >= 0 && (req->n_utts == 0 || (req->utts && req->place)), "bad fetch request");
     SBV2_REQUIRE(!(req->loudness && req->limiter), "a fetch request takes a loudness target or a limiter, not both");
@@ -663,6 +691,7 @@ int sbv2_pipeline_fetch_request_marks(sbv2_pipeline* p, int64_t ticket, const sb
         check_marks_static(marks);
         (void)pcm_format_spec(req->fmt);
     }
+    if (pitch) (void)check_pitch_static(pitch, pcm_format_spec(req->fmt).rate);
     SBV2_REQUIRE(p && dst && out_count, "bad arguments");
     const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter}
                            : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr}
@@ -670,12 +699,25 @@ int sbv2_pipeline_fetch_request_marks(sbv2_pipeline* p, int64_t ticket, const sb
     static const int32_t no_rows[1] = {0};
     static const int64_t no_place[1] = {0};
     fetch_formatted(p, ticket, req->fmt, gain, req->n_utts ? req->place : no_place, req->joined_len, req->flac ? Sink::kFlac : Sink::kPcm, dst,
-                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks);
+                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch);
     API_END
+}
+int sbv2_pipeline_fetch_request_marks(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
+                                      int64_t* out_count, double* stats, sbv2_marks* marks) {
+    return sbv2_pipeline_fetch_request_pitch(p, ticket, req, dst, capacity_bytes, out_count, stats, marks, nullptr);
 }
 int sbv2_pipeline_fetch_request(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes, int64_t* out_count,
                                 double* stats) {
     return sbv2_pipeline_fetch_request_marks(p, ticket, req, dst, capacity_bytes, out_count, stats, nullptr);
+}
+
+int sbv2_pitch_lags(int32_t sample_rate, double f0_min, double f0_max, int32_t* tau_min, int32_t* tau_max) {
+    API_BEGIN
+    SBV2_REQUIRE(tau_min && tau_max, "bad arguments");
+    const PitchSpec sp = pitch_spec(sample_rate, 1, f0_min, f0_max, 0.5);   // (hop and threshold have no part in the lags)
+    *tau_min = sp.tau_min;
+    *tau_max = sp.tau_max;
+    API_END
 }
 
 int sbv2_marks_spans(const int64_t* durations, int64_t n_tokens, int32_t hop, int64_t place, const sbv2_pcm_format* fmt, int64_t* start, int64_t* end) {

@@ -34,6 +34,7 @@ struct OutputChain {
     LoudnessMeter meter;
     Limiter limiter;   // (owns a second meter, for its evaluations)
     Marks marks;       // speech marks: levels of token spans and envelope frames (fetch_request_marks only)
+    Pitch pitch;       // ... and the pitch contour of the same samples (fetch_request_pitch only)
 };
 struct sbv2_pipeline {
     sbv2_bert* bert;

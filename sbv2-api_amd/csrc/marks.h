@@ -1,6 +1,7 @@
 // Speech marks (marks.hip): where each token lies in a delivered signal (host arithmetic, marks_spans) and how loud it is there (one
 // segmented reduction over the samples a formatted fetch leaves in HBM: sum of squares and peak per [start, end) segment).  Used by
 // sbv2_pipeline_fetch_request_marks (fetch_formatted, api.cpp), sbv2_stream_marks (stream.cpp) and the test hook sbv2_debug_segment_levels.
+// Beside them the pitch contour of the same samples (Pitch: YIN per frame; sbv2_pipeline_fetch_request_pitch, sbv2_debug_pitch).
 #pragma once
 #include "common.h"
 #include "pcm_format.h"
@@ -36,6 +37,49 @@ class Marks {
     DeviceBuffer dev_;    // the same
     double* res_host_ = nullptr;
     int64_t nseg_ = 0;
+};
+
+// The pitch contour of a delivered signal: YIN (de Cheveigne & Kawahara 2002, steps 2 - 5) per frame of `hop` delivered samples, as
+// include/sbv2_hip.h states it above sbv2_pitch.  Checked parameters and the lag range they give:
+struct PitchSpec {
+    int sample_rate = 0;
+    int64_t hop = 0;
+    int tau_min = 0, tau_max = 0;   // floor(sr / f0_max), ceil(sr / f0_min); the window W = tau_max
+    double threshold = 0.0;
+};
+// The exactness bound of the integer encodings rests on tau_max <= kPitchMaxTau: with |v| <= 32768 a difference is at most 65535, so
+// d(tau) <= 1200 * 65535^2 < 2^43, d(tau) tau and S(tau) <= 1200 * 1200 * 65535^2 = 6.2e15 < 2^53 = 9.0e15: both convert to f64 unrounded and
+// c(tau) has ONE rounding, its division.  40 Hz at 48 kHz gives exactly 1200; anything that would exceed it is refused.
+constexpr int kPitchMaxTau = 1200;
+constexpr double kPitchMinF0 = 40.0;
+constexpr int kPitchMaxRate = 48000;
+// throws: 40 <= f0_min < f0_max <= sr / 4, 0 < threshold < 1, hop >= 1, 0 < sr <= 48000 (NaNs fail every comparison and are refused)
+PitchSpec pitch_spec(int sample_rate, int64_t hop, double f0_min, double f0_max, double threshold);
+inline int64_t pitch_frames(int64_t n, int64_t hop) { return n > 0 ? (n + hop - 1) / hop : 0; }
+// What the host makes of a frame's device results (plain f64 arithmetic, never contracted): the parabolic refinement of the lag through
+// c(lag - 1), c(lag), c(lag + 1), f0 = sr / (lag + delta) for a voiced frame and 0 otherwise, ap = c(lag).
+void pitch_finish(const PitchSpec& sp, int32_t lag, int32_t voiced, const double* c3, double* f0, double* ap);
+
+// Device state of the pitch estimator of one execution context (k_pitch_yin, marks.hip): results on the device and their pinned mirror, grown
+// on demand; nothing is allocated before the first run.  One launch per run, one workgroup per frame, no atomics.
+class Pitch {
+  public:
+    Pitch() = default;
+    Pitch(const Pitch&) = delete;
+    Pitch& operator=(const Pitch&) = delete;
+    // Enqueues on s the estimator over x = n delivered samples on the device (encoding as Marks::run) and the copy of its results to the
+    // host: lag_host()[f], voiced_host()[f] and c3_host()[3 f ..] = c(lag - 1), c(lag), c(lag + 1) (a neighbour outside [1, tau_max] replaced
+    // by c(lag)) hold frame f < n_frames() once s has been synchronised.  n = 0 enqueues nothing.
+    void run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hipStream_t s);
+    int64_t n_frames() const { return nf_; }
+    const double* c3_host() const { return static_cast<const double*>(host_.get()); }
+    const int32_t* lag_host() const { return reinterpret_cast<const int32_t*>(c3_host() + 3 * nf_); }
+    const int32_t* voiced_host() const { return lag_host() + nf_; }
+
+  private:
+    PinnedBuffer host_;   // c3 [nf][3] | lag [nf] | voiced [nf]
+    DeviceBuffer dev_;    // the same
+    int64_t nf_ = 0;
 };
 
 // The same reduction FED piece by piece (a stream's replays): two segment tables fixed at begin, the token spans (monotone, disjoint, empty

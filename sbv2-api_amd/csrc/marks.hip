@@ -11,8 +11,11 @@
 // on the segment's length alone: no atomics, equal samples give equal bits wherever the segment lies.  s16 samples are squared as integers
 // (exact in f64, as are their sums below 2^53), and so are the integers that G.711 codes decode to (one byte per sample, any start); an f32 sample's square is exact in f64 too, so only the order of the sum is this kernel's own.
 // Each sample is read once per table it appears in (tokens, frames): the launch is bound by its few MB of HBM reads.
+// The pitch contour of the same samples (k_pitch_yin) is at the end of the file.
 #include "marks.h"
 
+#include <climits>
+#include <cmath>
 #include <cstring>
 
 namespace sbv2 {
@@ -359,6 +362,211 @@ StreamLevels::Done StreamLevels::push(const void* x, int encoding, int64_t D0, i
     tok_done_ = tok_new;
     env_done_ = env_new;
     return done;
+}
+
+// ---- the pitch contour (Pitch, marks.h) ----
+// YIN per frame as include/sbv2_hip.h states it: one workgroup per frame.  The 2 tau_max samples of the frame's window are staged once in LDS
+// (integers for s16 and the G.711 codes, f64 for f32; positions outside [0, n) are zeros written there, nothing outside is addressed).  Lane
+// l owns the lags l + 1, l + 1 + nt, ... (P of them, in registers) and walks j over the window: a[j] is one broadcast read for all of them,
+// a[j + tau] is consecutive across lanes.  Integer differences are 32-bit, their squares are accumulated in 64 bits; f32 differences and
+// squares are taken in f64, j ascending.  d(tau) goes to LDS, a chunked scan gives S(tau) (each thread sums its run of consecutive lags, one
+// lane scans the runs' totals: exact for integers, one fixed order per tau_max for f32), every thread divides for its own lags, and the
+// decision is two index minima over the workgroup and a short walk by one lane.  No atomics.
+namespace {
+
+struct PitchArgs {
+    const void* x;
+    int64_t n, hop;
+    int32_t tau_min, tau_max;
+    double threshold;
+    double* c3;        // [nf][3]
+    int32_t* lag;      // [nf]
+    int32_t* voiced;   // [nf]
+};
+
+template <class T>
+struct PitchTypes {   // staged sample, accumulator
+    using S = int32_t;
+    using D = int64_t;
+};
+template <>
+struct PitchTypes<float> {
+    using S = double;
+    using D = double;
+};
+
+constexpr int kPitchMaxP = (kPitchMaxTau + kBlock - 1) / kBlock;   // lags per lane at the largest window
+
+template <class T, int P>
+__global__ __launch_bounds__(kBlock) void k_pitch_yin(const PitchArgs a) {
+    using S = typename PitchTypes<T>::S;
+    using D = typename PitchTypes<T>::D;
+    __shared__ S win[2 * kPitchMaxTau];
+    __shared__ D dd[kPitchMaxTau + 1];
+    __shared__ double cc[kPitchMaxTau + 1];
+    __shared__ D part[kBlock];
+    __shared__ int sh_first[kWavesPerBlock], sh_arg[kWavesPerBlock];
+    __shared__ double sh_min[kWavesPerBlock];
+    const T* x = static_cast<const T*>(a.x);
+    const int nt = blockDim.x, tid = threadIdx.x, W = a.tau_max;   // nt P >= W (Pitch::run)
+    const int64_t b = (int64_t)blockIdx.x * a.hop + a.hop / 2 - W;
+    for (int k = tid; k < 2 * W; k += nt) {
+        const int64_t i = b + k;
+        win[k] = i >= 0 && i < a.n ? static_cast<S>(level_load(x, i)) : S(0);
+    }
+    __syncthreads();
+    int tau[P];
+    D acc[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        tau[p] = 1 + tid + p * nt;
+        if (tau[p] > W) tau[p] = 0;   // a lane without a lag in this round reads inside the window and its sum is dropped
+        acc[p] = D(0);
+    }
+#pragma unroll 4
+    for (int j = 0; j < W; ++j) {   // j + tau <= 2 W - 1
+        const S v = win[j];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            const S e = v - win[j + tau[p]];   // |e| <= 65535 for the integer encodings
+            acc[p] += (D)e * (D)e;
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+        if (tau[p]) dd[tau[p]] = acc[p];
+    __syncthreads();
+    // S(tau): thread t owns the lags [lo, hi], K consecutive ones
+    const int K = (W + nt - 1) / nt, lo = 1 + tid * K, hi = min(lo + K - 1, W);
+    D run = D(0);
+    for (int t = lo; t <= hi; ++t) run += dd[t];
+    part[tid] = run;
+    __syncthreads();
+    if (tid == 0) {
+        D before = D(0);
+        for (int t = 0; t < nt; ++t) {
+            const D v = part[t];
+            part[t] = before;
+            before += v;
+        }
+    }
+    __syncthreads();
+    run = part[tid];
+    int first = INT_MAX, arg = INT_MAX;   // the smallest lag in range under the threshold; the smallest lag in range that attains min c
+    double cmin = INFINITY;
+    for (int t = lo; t <= hi; ++t) {
+        const D d = dd[t];
+        run += d;
+        const double c = run == D(0) ? 1.0 : (double)d * (double)t / (double)run;   // both exact below 2^53 for integers: one rounding
+        cc[t] = c;
+        if (t >= a.tau_min) {
+            if (c < a.threshold && first == INT_MAX) first = t;
+            if (c < cmin) cmin = c, arg = t;
+        }
+    }
+#pragma unroll
+    for (int s = kWave / 2; s >= 1; s >>= 1) {
+        first = min(first, __shfl_down(first, s, kWave));
+        const double oc = __shfl_down(cmin, s, kWave);
+        const int oa = __shfl_down(arg, s, kWave);
+        if (oc < cmin || (oc == cmin && oa < arg)) cmin = oc, arg = oa;
+    }
+    const int lane = tid & (kWave - 1), wave = tid / kWave;
+    if (lane == 0) sh_first[wave] = first, sh_min[wave] = cmin, sh_arg[wave] = arg;
+    __syncthreads();   // (also: every cc[] is written)
+    if (tid == 0) {
+        for (int w = 1; w < nt / kWave; ++w) {
+            first = min(first, sh_first[w]);
+            if (sh_min[w] < cmin || (sh_min[w] == cmin && sh_arg[w] < arg)) cmin = sh_min[w], arg = sh_arg[w];
+        }
+        const bool voiced = first != INT_MAX;
+        int lag = voiced ? first : arg != INT_MAX ? arg : a.tau_min;   // (no minimum: every c is a NaN, from non-finite f32 samples)
+        if (voiced)
+            while (lag + 1 <= W && cc[lag + 1] < cc[lag]) ++lag;
+        const double c0 = cc[lag];
+        double* o = a.c3 + 3 * (int64_t)blockIdx.x;
+        o[0] = lag - 1 >= 1 ? cc[lag - 1] : c0;
+        o[1] = c0;
+        o[2] = lag + 1 <= W ? cc[lag + 1] : c0;
+        a.lag[blockIdx.x] = lag;
+        a.voiced[blockIdx.x] = voiced;
+    }
+}
+
+template <class T>
+void launch_pitch(int P, dim3 grid, dim3 blk, hipStream_t s, const PitchArgs& a) {
+    static_assert(kPitchMaxP == 5, "one case per lag count");
+    switch (P) {
+        case 1: hipLaunchKernelGGL((k_pitch_yin<T, 1>), grid, blk, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((k_pitch_yin<T, 2>), grid, blk, 0, s, a); break;
+        case 3: hipLaunchKernelGGL((k_pitch_yin<T, 3>), grid, blk, 0, s, a); break;
+        case 4: hipLaunchKernelGGL((k_pitch_yin<T, 4>), grid, blk, 0, s, a); break;
+        default: hipLaunchKernelGGL((k_pitch_yin<T, 5>), grid, blk, 0, s, a); break;
+    }
+}
+
+}  // namespace
+
+PitchSpec pitch_spec(int sample_rate, int64_t hop, double f0_min, double f0_max, double threshold) {
+    SBV2_REQUIRE(sample_rate > 0 && sample_rate <= kPitchMaxRate,
+                 "pitch: sample rate must be in [1, " + std::to_string(kPitchMaxRate) + "]: " + std::to_string(sample_rate));
+    SBV2_REQUIRE(hop >= 1, "pitch: hop must be >= 1: " + std::to_string(hop));
+    SBV2_REQUIRE(f0_min >= kPitchMinF0, "pitch: f0_min must be >= 40 Hz (the window of tau_max samples stays within " + std::to_string(kPitchMaxTau) +
+                                            ", the bound that keeps integer samples exact): " + std::to_string(f0_min));
+    SBV2_REQUIRE(f0_min < f0_max, "pitch: f0_min must be below f0_max: " + std::to_string(f0_min) + " >= " + std::to_string(f0_max));
+    SBV2_REQUIRE(f0_max <= sample_rate / 4.0,
+                 "pitch: f0_max must be <= sample_rate / 4 = " + std::to_string(sample_rate / 4.0) + ": " + std::to_string(f0_max));
+    SBV2_REQUIRE(threshold > 0.0 && threshold < 1.0, "pitch: threshold must be in (0, 1): " + std::to_string(threshold));
+    PitchSpec sp;
+    sp.sample_rate = sample_rate;
+    sp.hop = hop;
+    sp.tau_min = (int)std::floor(sample_rate / f0_max);
+    sp.tau_max = (int)std::ceil(sample_rate / f0_min);
+    sp.threshold = threshold;
+    SBV2_REQUIRE(sp.tau_min >= 4 && sp.tau_min <= sp.tau_max && sp.tau_max <= kPitchMaxTau, "internal: pitch lags out of range");
+    return sp;
+}
+
+void pitch_finish(const PitchSpec& sp, int32_t lag, int32_t voiced, const double* c3, double* f0, double* ap) {
+#pragma clang fp contract(off)
+    const double cm = c3[0], c0 = c3[1], cp = c3[2];
+    const double den = cm - 2.0 * c0 + cp;
+    const bool both = lag - 1 >= 1 && lag + 1 <= sp.tau_max;
+    const double delta = den > 0.0 && both ? 0.5 * (cm - cp) / den : 0.0;
+    *f0 = voiced ? (double)sp.sample_rate / ((double)lag + delta) : 0.0;
+    if (ap) *ap = c0;
+}
+
+void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hipStream_t s) {
+    SBV2_REQUIRE(pcm_encoding_known(encoding), "internal: pitch of an unknown encoding");
+    SBV2_REQUIRE(n >= 0 && sp.hop >= 1 && sp.tau_min >= 1 && sp.tau_min <= sp.tau_max && sp.tau_max <= kPitchMaxTau, "internal: bad pitch spec");
+    const int64_t nf = pitch_frames(n, sp.hop);
+    SBV2_REQUIRE(nf < (1 << 30), "too many pitch frames: " + std::to_string(nf) + " >= 2^30");
+    nf_ = nf;
+    if (nf == 0) return;
+    SBV2_REQUIRE(x, "internal: no samples");
+    const size_t bytes = 32 * (size_t)nf;   // c3 (24) | lag (4) | voiced (4) per frame
+    char* h = static_cast<char*>(host_.reserve(bytes, std::max<size_t>(bytes * 2, 4096), s));
+    char* d = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes * 2, 4096), s));
+    PitchArgs a;
+    a.x = x;
+    a.n = n;
+    a.hop = sp.hop;
+    a.tau_min = sp.tau_min;
+    a.tau_max = sp.tau_max;
+    a.threshold = sp.threshold;
+    a.c3 = reinterpret_cast<double*>(d);
+    a.lag = reinterpret_cast<int32_t*>(d + 24 * (size_t)nf);
+    a.voiced = a.lag + nf;
+    // a small window (8 or 16 kHz) takes one or two waves per frame instead of four; a large one several lags per lane
+    const int nt = sp.tau_max <= kWave ? kWave : sp.tau_max <= 2 * kWave ? 2 * kWave : kBlock, P = (sp.tau_max + nt - 1) / nt;
+    const dim3 grid((unsigned)nf), blk(nt);
+    if (encoding == kEncS16) launch_pitch<int16_t>(P, grid, blk, s, a);
+    else if (encoding == kEncMulaw) launch_pitch<MulawCode>(P, grid, blk, s, a);
+    else if (encoding == kEncAlaw) launch_pitch<AlawCode>(P, grid, blk, s, a);
+    else launch_pitch<float>(P, grid, blk, s, a);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s));
 }
 
 }  // namespace sbv2

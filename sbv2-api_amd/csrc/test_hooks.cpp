@@ -1604,6 +1604,32 @@ int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n
     API_END
 }
 
+// The pitch estimator (Pitch, marks.hip) on host samples, finished on the host as the fetch finishes it.  Parameters and capacity are checked
+// before any device call; nothing is written when the call fails.
+int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, double* cmnd3, int32_t* voiced) {
+    API_BEGIN
+    SBV2_REQUIRE(pitch && pcm_encoding_known(encoding) && n >= 0 && (x || n == 0), "bad arguments");
+    SBV2_REQUIRE(pitch->reserved == 0, "sbv2_pitch.reserved must be 0");
+    const PitchSpec sp = pitch_spec(sample_rate, pitch->hop, pitch->f0_min, pitch->f0_max, pitch->threshold);
+    const int64_t nf = pitch_frames(n, sp.hop);
+    SBV2_REQUIRE(pitch->capacity >= nf, "pitch arrays too small: " + std::to_string(pitch->capacity) + " < " + std::to_string(nf) + " frames");
+    SBV2_REQUIRE(pitch->f0, "sbv2_pitch.f0 must not be NULL");
+    HIP_CHECK(hipSetDevice(device));
+    DevMem dx(x, (size_t)n * pcm_encoding_bytes(encoding));
+    Pitch est;
+    est.run(dx.p, encoding, n, sp, nullptr);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    for (int64_t f = 0; f < nf; ++f) {
+        const int32_t lag = est.lag_host()[f];
+        pitch_finish(sp, lag, est.voiced_host()[f], est.c3_host() + 3 * f, pitch->f0 + f, pitch->ap ? pitch->ap + f : nullptr);
+        if (pitch->lag) pitch->lag[f] = lag;
+        if (cmnd3) std::memcpy(cmnd3 + 3 * f, est.c3_host() + 3 * f, 3 * sizeof(double));
+        if (voiced) voiced[f] = est.voiced_host()[f];
+    }
+    pitch->n_frames = nf;
+    API_END
+}
+
 // The fed level reduction (StreamLevels, marks.hip) on its own: x cut at cuts[ncuts] into ncuts + 1 pushes, each handed the samples of its
 // piece only.  Segments, envelope and cuts are checked before any device call.
 int sbv2_debug_stream_levels(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, const int64_t* starts,

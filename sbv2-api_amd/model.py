@@ -405,6 +405,59 @@ class Marks:
         return [a for a in (self.start, self.end, self.sumsq, self.peak, self.env_sumsq, self.env_peak) if a is not None]
 
 
+PITCH_THRESHOLD = 0.15   # YIN's usual absolute threshold
+
+
+class Pitch:
+    """Options and, once a call has filled it, results of the pitch estimator (struct sbv2_pitch: YIN per frame of `hop` delivered samples,
+    include/sbv2_hip.h states it).  Results: f0 [n] in Hz (0 for an unvoiced frame), ap [n] = c(lag), the aperiodicity, lag [n] in samples;
+    frame f has its centre at f hop + hop // 2.  None before a call."""
+
+    def __init__(self, hop: int, f0_min: float = 70.0, f0_max: float = 600.0, threshold: float = PITCH_THRESHOLD):
+        self.hop, self.f0_min, self.f0_max, self.threshold = int(hop), float(f0_min), float(f0_max), float(threshold)
+        self.f0 = self.ap = self.lag = None
+
+    def n_frames(self, n: int) -> int:
+        return -(-int(n) // self.hop) if n > 0 and self.hop > 0 else 0
+
+    def c_struct(self, n: int):
+        """A sbv2_pitch over fresh arrays for a signal of n delivered samples; take() keeps them once the call has succeeded."""
+        nf = self.n_frames(n)
+        arrays = np.zeros(max(nf, 1), np.float64), np.zeros(max(nf, 1), np.float64), np.zeros(max(nf, 1), np.int32)
+        c = _lib.Sbv2Pitch(self.hop if -2 ** 31 <= self.hop < 2 ** 31 else 0, 0, self.f0_min, self.f0_max, self.threshold, nf, _f64p(arrays[0]),
+                           _f64p(arrays[1]), arrays[2].ctypes.data_as(C.POINTER(C.c_int32)), 0)
+        return c, arrays
+
+    def take(self, c, arrays):
+        assert c.n_frames == c.capacity, (c.n_frames, c.capacity)
+        self.f0, self.ap, self.lag = (a[:c.n_frames] for a in arrays)
+        return self
+
+
+def pitch_lags(sample_rate: int, f0_min: float, f0_max: float):
+    """(tau_min, tau_max) = (floor(sr / f0_max), ceil(sr / f0_min)) under the library's checks: 40 <= f0_min < f0_max <= sr / 4
+    (sbv2_pitch_lags; host only)."""
+    a, b = C.c_int32(0), C.c_int32(0)
+    check(_lib.lib().sbv2_pitch_lags(int(sample_rate), float(f0_min), float(f0_max), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def debug_pitch(x, sample_rate: int, pitch: Pitch, device: int = 0, encoding: str | None = None):
+    """Test hook: the pitch estimator on host samples (sbv2_debug_pitch).  x: int16 or float32 samples, or with encoding "mulaw" / "alaw"
+    uint8 codes -> (pitch with f0 / ap / lag filled, cmnd3 [n][3] = c(lag - 1), c(lag), c(lag + 1), voiced [n])."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if encoding is None and x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"pitch is taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"pitch of {encoding!r} samples is not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
+    c, arrays = pitch.c_struct(x.size)
+    c3, voiced = np.zeros((len(arrays[0]), 3), np.float64), np.zeros(len(arrays[0]), np.int32)   # (at least one entry: never a NULL)
+    check(_lib.lib().sbv2_debug_pitch(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size, int(sample_rate), C.byref(c),
+                                      _f64p(c3), voiced.ctypes.data_as(C.POINTER(C.c_int32))))
+    return pitch.take(c, arrays), c3[:c.n_frames], voiced[:c.n_frames]
+
+
 def full_scale(encoding: str) -> float:
     """Full scale of the delivered samples' levels: 32767 for s16 and for G.711 (levels of the decoded integers), 1 for f32."""
     return 1.0 if encoding == "f32" else 32767.0
@@ -669,14 +722,16 @@ class Pipeline:
         """The signals of fetch_format(b, fmt, place, joined_len), each as one FLAC stream (bytes) encoded on the device; fmt must be s16."""
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
-    def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True):
+    def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
         read: the requests that share a run are fetched one by one from the same ticket.
         marks=True: (signal, stats, Marks) through sbv2_pipeline_fetch_request_marks: the listed rows' token spans on the delivered timeline, with
         their levels (levels=False: timing only, no kernel) and, with env_hop > 0 delivered samples, the envelope.  The signal and stats are
-        those of the same call without marks."""
+        those of the same call without marks.
+        pitch: a Pitch -> a fourth element, that Pitch with the contour of the delivered signal (sbv2_pipeline_fetch_request_pitch); the third is
+        None without marks.  Signal, stats and marks are those of the same call without pitch."""
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
         rw = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
@@ -691,23 +746,33 @@ class Pipeline:
         dst = np.empty(max(size, 1), np.uint8 if flac else fmt.dtype)
         got = C.c_int64(0)
         stats = np.zeros(nstats, np.float64) if nstats else None
-        if not marks:
+        if pitch is not None:
+            cp, parr = pitch.c_struct(pcm_format_length(fmt, int(joined_len)))
+        if not marks and pitch is None:
             check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
                                                          _f64p(stats) if nstats else None))
             return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        ntok = int(sum(int(b.t_lens[r]) for r in rw))
-        out_len = pcm_format_length(fmt, int(joined_len))
-        nenv = -(-out_len // int(env_hop)) if env_hop > 0 else 0
-        m = Marks(np.zeros(ntok, np.int64), np.zeros(ntok, np.int64), np.zeros(ntok, np.float64) if levels else None,
-                  np.zeros(ntok, np.float64) if levels else None, env_hop, np.zeros(nenv, np.float64) if env_hop > 0 else None,
-                  np.zeros(nenv, np.float64) if env_hop > 0 else None, out_len)
-        cm = _lib.Sbv2Marks(ntok, m.start.ctypes.data_as(i64p), m.end.ctypes.data_as(i64p), _f64p(m.sumsq) if levels else None,
-                            _f64p(m.peak) if levels else None, 0, int(env_hop), 0, nenv, _f64p(m.env_sumsq) if env_hop > 0 else None,
-                            _f64p(m.env_peak) if env_hop > 0 else None, 0)
-        check(_lib.lib().sbv2_pipeline_fetch_request_marks(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
-                                                           _f64p(stats) if nstats else None, C.byref(cm)))
-        assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
-        return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats, m
+        m = cm = None
+        if marks:
+            ntok = int(sum(int(b.t_lens[r]) for r in rw))
+            out_len = pcm_format_length(fmt, int(joined_len))
+            nenv = -(-out_len // int(env_hop)) if env_hop > 0 else 0
+            m = Marks(np.zeros(ntok, np.int64), np.zeros(ntok, np.int64), np.zeros(ntok, np.float64) if levels else None,
+                      np.zeros(ntok, np.float64) if levels else None, env_hop, np.zeros(nenv, np.float64) if env_hop > 0 else None,
+                      np.zeros(nenv, np.float64) if env_hop > 0 else None, out_len)
+            cm = _lib.Sbv2Marks(ntok, m.start.ctypes.data_as(i64p), m.end.ctypes.data_as(i64p), _f64p(m.sumsq) if levels else None,
+                                _f64p(m.peak) if levels else None, 0, int(env_hop), 0, nenv, _f64p(m.env_sumsq) if env_hop > 0 else None,
+                                _f64p(m.env_peak) if env_hop > 0 else None, 0)
+        args = (self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
+                C.byref(cm) if marks else None)
+        if pitch is None:
+            check(_lib.lib().sbv2_pipeline_fetch_request_marks(*args))
+        else:
+            check(_lib.lib().sbv2_pipeline_fetch_request_pitch(*args, C.byref(cp)))
+        if marks:
+            assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
+        out = dst[:got.value].tobytes() if flac else dst[:got.value]
+        return (out, stats, m) if pitch is None else (out, stats, m, pitch.take(cp, parr))
 
     def close(self):
         if self.h:

@@ -44,10 +44,14 @@ class SynthesizeOptions:
     samples per frame.
     gain_db (new; read by easy_synthesize_stream only, refused everywhere else): a fixed gain in dB on a stream, with the limiter's gain curve
     holding the samples under true_peak_max (model.StreamLevel).  A stream cannot measure its loudness; the caller names the gain, for
-    example target - L from the loudness stats of an earlier answer of the same voice."""
+    example target - L from the loudness stats of an earlier answer of the same voice.
+    pitch_hz (new; easy_synthesize_marks only, refused everywhere else): the speech marks carry a pitch contour of pitch_hz frames per second
+    (an integer in [1, 1000]; sample_rate // pitch_hz delivered samples per frame), estimated on the device from the delivered samples within
+    [pitch_min_hz, pitch_max_hz] (model.Pitch)."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
-                 normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None):
+                 normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
+                 pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0):
         if loudness is not None and normalize:
             raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
         if limiter and loudness is None:
@@ -58,6 +62,7 @@ class SynthesizeOptions:
         self.loudness, self.true_peak_max = loudness, true_peak_max
         self.envelope_hz = envelope_hz
         self.gain_db = gain_db
+        self.pitch_hz, self.pitch_min_hz, self.pitch_max_hz = pitch_hz, pitch_min_hz, pitch_max_hz
 
 
 def load_style(data: bytes) -> np.ndarray:
@@ -188,6 +193,29 @@ def envelope_hop(options, rate: int) -> int:
     return rate // hz
 
 
+def pitch_options(options, rate: int):
+    """The model.Pitch of a request with marks (None without pitch_hz): rate // pitch_hz delivered samples per frame.  A bad pitch_hz or
+    range is refused here, before any GPU work (the range by the library's own host check)."""
+    hz = getattr(options, "pitch_hz", None)
+    if hz is None:
+        return None
+    if not (isinstance(hz, int) and not isinstance(hz, bool) and 1 <= hz <= 1000):
+        raise model.Sbv2Error(f"pitch_hz must be an integer in [1, 1000]: {hz!r}")
+    lo, hi = getattr(options, "pitch_min_hz", 70.0), getattr(options, "pitch_max_hz", 600.0)
+    for name, v in (("pitch_min_hz", lo), ("pitch_max_hz", hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise model.Sbv2Error(f"{name} must be a number: {v!r}")
+    model.pitch_lags(rate, lo, hi)
+    return model.Pitch(rate // hz, lo, hi)
+
+
+def refuse_pitch(options, what: str):
+    """pitch_hz where no marks are returned: refused, with the route that carries a contour."""
+    if getattr(options, "pitch_hz", None) is not None:
+        raise model.Sbv2Error(f"pitch_hz needs the speech marks of a whole signal: {what} carries none, ask /synthesize_marks "
+                              "(easy_synthesize_marks) instead")
+
+
 def token_marks(utts, live, rate: int, start, end):
     """The timing part of the marks dict: utts = the request's live sentences (phones, word2ph), live = their line numbers, start / end = the
     delivered-sample spans of their tokens, sentence after sentence.  tokens: one entry per phone id (blanks included); words: one entry per
@@ -214,10 +242,13 @@ def token_marks(utts, live, rate: int, start, end):
     return {"sample_rate": int(rate), "tokens": tokens, "words": words}
 
 
-def marks_dict(utts, live, fmt, m) -> dict:
+def marks_dict(utts, live, fmt, m, pitch=None) -> dict:
     """The JSON-ready speech marks of one request from a model.Marks of its rows: token_marks plus, per token, level_dbfs (10 log10 of the mean
     square of its delivered samples re full scale; None for an empty or silent span) and peak (largest |sample| re full scale), and `envelope`
-    {hop, level_dbfs [n], peak [n]} when the marks hold one.  The gaps between sentences belong to no token."""
+    {hop, level_dbfs [n], peak [n]} when the marks hold one.  The gaps between sentences belong to no token.
+    pitch (a filled model.Pitch): `pitch` {hop, f0_hz [n] (None for an unvoiced frame), aperiodicity [n]}, and per token f0_hz (the mean over
+    the voiced frames whose centre f hop + hop // 2 lies in its span; None when there is none) and voiced (the share of the frames centred in
+    its span that are voiced; 0.0 when none is centred there).  Without pitch the dict has none of these keys."""
     d = token_marks(utts, live, fmt.sample_rate, m.start, m.end)
     full = model.full_scale(fmt.encoding)
     if m.sumsq is not None:
@@ -228,6 +259,15 @@ def marks_dict(utts, live, fmt, m) -> dict:
         n = [min(m.env_hop, m.out_len - f * m.env_hop) for f in range(len(m.env_sumsq))]   # (the last frame may be short)
         d["envelope"] = {"hop": int(m.env_hop), "level_dbfs": [model.level_dbfs(ss, k, fmt.encoding) for ss, k in zip(m.env_sumsq, n)],
                          "peak": [float(pk) / full for pk in m.env_peak]}
+    if pitch is not None:
+        f0 = np.asarray(pitch.f0, np.float64)
+        d["pitch"] = {"hop": int(pitch.hop), "f0_hz": [float(v) if v > 0 else None for v in f0], "aperiodicity": [float(v) for v in pitch.ap]}
+        centre = np.arange(f0.size, dtype=np.int64) * pitch.hop + pitch.hop // 2
+        for t in d["tokens"]:
+            k0, k1 = np.searchsorted(centre, [t["start"], t["end"]])   # the frames with start <= centre < end
+            v = f0[k0:k1][f0[k0:k1] > 0]
+            t["f0_hz"] = float(v.mean()) if v.size else None
+            t["voiced"] = float(v.size) / (k1 - k0) if k1 > k0 else 0.0
     return d
 
 
@@ -243,9 +283,13 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
         if marks is not None:
-            out, stats, m = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, marks=True,
-                                               env_hop=envelope_hop(options, fmt.sample_rate))
-            marks.append(marks_dict(plan.utts, plan.live, fmt, m))
+            kw = dict(gain=ln, flac=plan.flac, marks=True, env_hop=envelope_hop(options, fmt.sample_rate))
+            pitch = pitch_options(options, fmt.sample_rate)
+            if pitch is None:   # (the call of a request without a contour is the call it always was)
+                out, stats, m = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw)
+            else:
+                out, stats, m, pitch = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, pitch=pitch, **kw)
+            marks.append(marks_dict(plan.utts, plan.live, fmt, m, pitch))
         else:
             out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac)
         if stats is not None and loudness_stats is not None:
@@ -271,6 +315,7 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     loudness_stats: an optional list that receives [L, TP, G] of the signal when options.loudness is set, or the limiter's 6 values
     [L, TP, G, L_out, TP_out, deepest reduction] when options.limiter is set as well.
     = finish_request over all rows of a run that holds this request alone (batcher.RequestBatcher: the same, several requests to a run)."""
+    refuse_pitch(options, "easy_synthesize (/synthesize)")
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
     if noise_seed is None:      # the reference draws fresh noise per request; tests pass an explicit seed
         noise_seed = model.fresh_noise_seed()
@@ -287,6 +332,7 @@ def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, styl
     options.envelope_hz a level envelope.  Levels are computed on the device from the delivered samples (also behind the FLAC sink)."""
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
     envelope_hop(plan.options, plan.fmt.sample_rate)   # a bad envelope_hz is refused before any GPU work
+    pitch_options(plan.options, plan.fmt.sample_rate)  # ... and so is a bad pitch_hz or range
     if noise_seed is None:
         noise_seed = model.fresh_noise_seed()
     b = pipe.prepare(plan.utts, sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=noise_scale,
@@ -433,6 +479,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     once the last piece is out `.marks` has marks_dict's shape.  The audio bytes are those of the same call without levels (the default,
     which ignores envelope_hz).  On a level stream (gain_db) the levels are those of the samples the limiter emits."""
     options = options or SynthesizeOptions()
+    refuse_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")   # (a contour on a stream needs a carried window: DESIGN.md)
     if options.normalize:
         raise model.Sbv2Error("a stream cannot normalise: the peak needs the whole signal (use /synthesize)")
     if options.loudness is not None or options.limiter:

@@ -32,6 +32,9 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
                     samples per frame.  With batching the request shares runs like /synthesize.
+                    pitch_hz = null (new; with pitch_min_hz = 70, pitch_max_hz = 600): the marks also carry "pitch" {"hop", "f0_hz" (null for an
+                    unvoiced frame), "aperiodicity"}, pitch_hz frames per second estimated on the device from the delivered samples, and every
+                    token "f0_hz" and "voiced".  The field is refused on every other route.
   any error         500 text/plain "Something went wrong: <message>"            sbv2_api/src/error.rs:10-18
   one request at a time (Arc<Mutex<TTSModelHolder>>, main.rs:86,104)             -> a lock around the holder
   make_app(holder, batching={...})  new, off by default: concurrent /synthesize requests share pipeline runs (batcher.py)
@@ -137,6 +140,9 @@ def make_app(holder, batching=None):
         limiter: bool = False               # look-ahead true-peak limiter for targets the plain gain misses; needs loudness
         max_reduction: float = 6.0          # the limiter's deepest gain reduction (dB)
         gain_db: Optional[float] = None     # /synthesize_stream only: fixed gain (dB) under the true_peak_max ceiling; refused elsewhere
+        pitch_hz: Optional[int] = None      # /synthesize_marks only: frames per second of the pitch contour in the marks; refused elsewhere
+        pitch_min_hz: float = 70.0          # the contour's search range (Hz)
+        pitch_max_hz: float = 600.0
 
     class SynthesizeMarksRequest(SynthesizeRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
@@ -182,7 +188,8 @@ def make_app(holder, batching=None):
         return orchestrator.SynthesizeOptions(sdp_ratio=req.sdp_ratio, length_scale=req.length_scale, sample_rate=req.sample_rate,
                                               encoding=req.encoding, normalize=req.normalize, loudness=req.loudness,
                                               true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction,
-                                              envelope_hz=getattr(req, "envelope_hz", None), gain_db=req.gain_db)
+                                              envelope_hz=getattr(req, "envelope_hz", None), gain_db=req.gain_db, pitch_hz=req.pitch_hz,
+                                              pitch_min_hz=req.pitch_min_hz, pitch_max_hz=req.pitch_max_hz)
 
     def synthesize(req: SynthesizeRequest):
         try:
