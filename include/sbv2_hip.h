@@ -758,6 +758,49 @@ int sbv2_debug_gemm_bfs(int device, const float* x, const float* w, const float*
    wrong result: the race screen of gemm_bfs.hip's cross-workgroup K split.  parts as above. */
 int sbv2_debug_gemm_bfs_alt(int device, const float* xa, const float* xb, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
                             int parts, int64_t iters, float* ya, float* yb);
+/* ---- the repeated-launch screen of the inline-asm MFMA kernels (tests/test_mfma_repeatability.py) ----
+   One launch of the named kernel is enqueued `reps` (2 .. 4096) times on one stream with no host synchronisation in between, alternately on the two inputs
+   xa / xb (repetition i: input and output plane i % 2).  Before each repetition a device-to-device copy restores the output (prev when it is given: the launch
+   accumulates onto it; NaN otherwise: every row must be written), after it a comparison kernel counts the 32-bit words of everything the launch writes that
+   differ from the FIRST result of the same input: mismatch[i] = that count, first_bad[i] = the index of the first such word (-1: none), both [reps].
+   ya / yb = the first result of each input.  neighbour != 0: a second stream receives one launch per repetition from the same host loop, alternately a
+   LayerNorm [1024][8192] and a gemm_bfs f16x3 product 1024 x 1024 x 2048 (nothing polls or waits; no graphs).  flip_at >= 0: one bit of word flip_word of
+   repetition flip_at's output is flipped before its comparison (the screen's self-check; -1: off).  A HIP error of any launch is returned; nothing is
+   retried.  Operands as in sbv2_debug_respair (variant 1 / 2; 3 = respair_x16.hip or an error), sbv2_debug_resbranch (variant 1) and sbv2_debug_conv1d_clx; the latter's words are the f32
+   plane [L][cout] and, with want_ys, the bf16 parts planes behind it (ysa / ysb = hi + lo of the first results). */
+int sbv2_debug_repeat_respair(int device, const float* xa, const float* xb, const float* w1, const float* w2, const float* b1, const float* b2, int64_t C,
+                              int64_t N, int64_t k, int64_t dilation, const uint8_t* mask, int64_t mask_div, float beta, const float* prev, int variant,
+                              int reps, int neighbour, int flip_at, int64_t flip_word, float* ya, float* yb, int64_t* mismatch, int64_t* first_bad);
+int sbv2_debug_repeat_resbranch(int device, const float* xa, const float* xb, const float* w, const float* bias, int64_t C, int64_t N, int64_t k,
+                                const int64_t* dilations, const uint8_t* mask, int64_t mask_div, float beta, const float* prev, int reps, int neighbour,
+                                int flip_at, int64_t flip_word, float* ya, float* yb, int64_t* mismatch, int64_t* first_bad);
+int sbv2_debug_repeat_conv1d_clx(int device, const float* xa, const float* xb, const float* w, const float* bias, const float* res, int64_t cin, int64_t cout,
+                                 int64_t k, int64_t L, int64_t dilation, float pre_slope, float beta, int want_ys, int reps, int neighbour, int flip_at,
+                                 int64_t flip_word, float* ya, float* yb, float* ysa, float* ysb, int64_t* mismatch, int64_t* first_bad);
+/* ... the phased transposed convolution of the wide decoder stages (operands as sbv2_debug_conv_transpose1d_clx; y [cout][L * stride], the mask on input
+   positions), and y[M][N] = w[M][K] x[K][N] + bias (+ res) through gemm_bfs.hip as conv_bfs launches it (parts code 2 / 3 / 4 as sbv2_debug_gemm_bfs, with the
+   K-split scratch DeBERTa's forward provides; split_out = parts: the parts copy is written and compared as well).  gemm_bfs' words are the f32 plane at its
+   device pitch [M][round_up(N, 64)], then the parts planes. */
+int sbv2_debug_repeat_conv_transpose1d_clx(int device, const float* xa, const float* xb, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k,
+                                           int64_t L, int64_t stride, float pre_slope, const uint8_t* mask, int64_t mask_div, int want_ys, int reps,
+                                           int neighbour, int flip_at, int64_t flip_word, float* ya, float* yb, float* ysa, float* ysb, int64_t* mismatch,
+                                           int64_t* first_bad);
+int sbv2_debug_repeat_gemm_bfs(int device, const float* xa, const float* xb, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
+                               int parts, int split_out, int reps, int neighbour, int flip_at, int64_t flip_word, float* ya, float* yb, float* ysa, float* ysb,
+                               int64_t* mismatch, int64_t* first_bad);
+/* ... and k_vits_flash_x3q (attn_flash.hip) on the flow's frame layout as sbv2_debug_vits_attention's variants 4 / 5 build it, the launcher choosing the 4- or
+   8-wave shape by the grid as in the model: q / k / v packed [heads * dk][sum lens] in two sets, ctx cleared before every repetition.  The words are the ctx
+   plane at its device pitch [heads * dk][*ld], gaps and pad columns included. */
+int sbv2_debug_repeat_vits_attention(int device, const float* qa, const float* ka, const float* va, const float* qb, const float* kb, const float* vb,
+                                     const float* erk, const float* erv, const int64_t* lens, int nutt, int64_t heads, int64_t dk, int64_t window, int reps,
+                                     int neighbour, int flip_at, int64_t flip_word, float* ctxa, float* ctxb, int64_t* ld, int64_t* mismatch,
+                                     int64_t* first_bad);
+/* ... and the flow FFN pair as VitsModel::run_encoder launches it on conv_clx.hip (weights through sbv2_debug_conv_ffn_cl's builders): conv_1 writes relu(.) as
+   conv_2's operand parts, conv_2 the k-major plane y = conv + b + x, mask [L] at both; one repetition = both launches; x / y [H][L].  The words are the
+   intermediate's parts planes, then y at its device pitch [H][round_up(L, 64)]. */
+int sbv2_debug_repeat_conv_ffn_clx(int device, const float* xa, const float* xb, const float* w1, const float* b1, const float* w2, const float* b2, int64_t H,
+                                   int64_t F, int64_t k, int64_t L, const uint8_t* mask, int reps, int neighbour, int flip_at, int64_t flip_word, float* ya,
+                                   float* yb, int64_t* mismatch, int64_t* first_bad);
 /* ---- conv_plain, conv_bfs, the encoders' FFN pair and linear_tokmajor with every argument the models pass (tests/test_gemm_conv_kernels.py) ----
    Host planes [C][L] without pitch; on the device every plane sits at the library's pitch, every input holds NaN in the columns L .. pitch, outputs are
    pre-filled with a sentinel (0x5A bytes) and *stray (optional) = the number of pad words of the outputs that the launch changed.

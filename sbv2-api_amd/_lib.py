@@ -239,6 +239,21 @@ SYMBOLS = {
     "sbv2_debug_resbranch": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, i64p, C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_int,
                                        C.c_int64, f32p, f32p]),
     "sbv2_debug_gemm_bfs_alt": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, f32p, f32p]),
+    "sbv2_debug_repeat_respair": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_float, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, f32p, f32p, i64p, i64p]),
+    "sbv2_debug_repeat_resbranch": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, i64p, C.c_void_p, C.c_int64, C.c_float, f32p,
+                                              C.c_int, C.c_int, C.c_int, C.c_int64, f32p, f32p, i64p, i64p]),
+    "sbv2_debug_repeat_conv1d_clx": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float,
+                                               C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, f32p, f32p, f32p, f32p, i64p, i64p]),
+    "sbv2_debug_repeat_conv_transpose1d_clx": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_float,
+                                                         C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, f32p, f32p, f32p, f32p, i64p,
+                                                         i64p]),
+    "sbv2_debug_repeat_gemm_bfs": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int64, f32p, f32p, f32p, f32p, i64p, i64p]),
+    "sbv2_debug_repeat_vits_attention": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, i64p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                                   C.c_int, C.c_int, C.c_int, C.c_int64, f32p, f32p, i64p, i64p, i64p]),
+    "sbv2_debug_repeat_conv_ffn_clx": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int64, f32p, f32p, i64p, i64p]),
     "sbv2_debug_gemm_bfs": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64,
                                       f32p, f32p]),
     "sbv2_debug_conv_plain": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p,

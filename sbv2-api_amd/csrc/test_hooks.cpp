@@ -5,6 +5,7 @@
 // make_layout, with the attention hooks' poison / sentinel / stray-count convention (tests/test_ops_kernels.py).
 #include <cstring>
 #include <limits>
+#include <memory>
 
 #include "api_internal.h"
 
@@ -243,6 +244,219 @@ RowOpts* upload_rows(Arena& ar, int n, const uint64_t* seed, uint64_t seed1, con
     RowOpts* d = ar.array<RowOpts>(r.size());
     HIP_CHECK(hipMemcpy(d, r.data(), sizeof(RowOpts) * r.size(), hipMemcpyHostToDevice));
     return d;
+}
+
+// ---- the repeated-launch screen of the inline-asm MFMA kernels (tests/test_mfma_repeatability.py) -------------------------------------------------------
+// One launch is enqueued `reps` times on one stream without a host synchronisation in between, alternately on two inputs (repetition i: input and output
+// plane i % 2).  Before each repetition the output is restored by a device-to-device copy (the previous contents under accumulate, else NaN: every row must be
+// written); after it a comparison kernel counts the 32-bit words that differ from the FIRST result of the same input.  These kernels have no floating-point
+// atomics and no order-dependent reduction, so any difference is a defect.  Optionally a second stream receives one launch per repetition from
+// the same host loop, alternately a LayerNorm over a plane that reaches every CU and one gemm_bfs f16x3 product of DeBERTa's batch shape class: nothing polls,
+// nothing waits for a condition, no graphs.
+__global__ __launch_bounds__(256) void k_rep_compare(const uint32_t* __restrict__ got, const uint32_t* __restrict__ ref, size_t n, unsigned long long word0,
+                                                     unsigned long long* mismatch, unsigned long long* first_bad) {
+    const size_t n4 = n / 4, stride = (size_t)gridDim.x * blockDim.x, t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long cnt = 0, first = ~0ull;
+    auto note = [&](size_t i) {
+        ++cnt;
+        if (i < first) first = i;
+    };
+    for (size_t i = t; i < n4; i += stride) {
+        const uint4 a = reinterpret_cast<const uint4*>(got)[i], b = reinterpret_cast<const uint4*>(ref)[i];
+        if (a.x != b.x) note(4 * i);
+        if (a.y != b.y) note(4 * i + 1);
+        if (a.z != b.z) note(4 * i + 2);
+        if (a.w != b.w) note(4 * i + 3);
+    }
+    for (size_t i = 4 * n4 + t; i < n; i += stride)
+        if (got[i] != ref[i]) note(i);
+    if (cnt) {
+        atomicAdd(mismatch, cnt);
+        atomicMin(first_bad, word0 + first);
+    }
+}
+__global__ void k_rep_flip(uint32_t* p, size_t word) { p[word] ^= 0x1000u; }
+
+struct RepRegion {          // one buffer a launch writes: the two output planes, the first result of each input, what a repetition starts from (null: nothing)
+    void* out[2];
+    void* ref[2];
+    const void* init;
+    size_t words;
+};
+struct RepOpts {
+    int reps, neighbour, flip_at;
+    int64_t flip_word;
+};
+struct HookStream {
+    hipStream_t s = nullptr;
+    HookStream() { HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    ~HookStream() {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    }
+    HookStream(const HookStream&) = delete;
+    HookStream& operator=(const HookStream&) = delete;
+};
+// the other execution context's work: LayerNorm [1024][8192] (8192 columns: waves on every CU; little LDS, few registers) and W[1024][1024] x X[1024][2048]
+// in f16x3 (128 tiles of 128 x 128: the batch instantiation)
+struct RepNeighbour {
+    static constexpr int kC = 1024, kL = 8192, kN = 2048;
+    std::vector<float> w, bias;
+    Blob blob;
+    WeightStore ws;
+    PackedConv pc;
+    DevMem x, y, g, b, xs_mem, sk_mem;
+    Plane X, Y, GX, GY;
+    SplitPlanes xs;
+    BfsSplitK sk;
+    static std::vector<float> noise(size_t n, float scale, uint32_t st) {
+        std::vector<float> v(n);
+        for (auto& e : v) {
+            st = st * 1664525u + 1013904223u;
+            e = ((st >> 8) * (1.0f / 16777216.0f) - 0.5f) * scale;
+        }
+        return v;
+    }
+    static constexpr size_t kWs = (size_t)48 << 20;
+    RepNeighbour()
+        : w(noise((size_t)kC * kC, 0.1f, 1u)), bias(noise(kC, 1.f, 2u)), blob(one_conv_blob(w.data(), bias.data(), {kC, kC, 1}, kC)), ws(blob),
+          x(sizeof(float) * kC * kL), y(sizeof(float) * kC * kL), g(sizeof(float) * kC), b(sizeof(float) * kC), xs_mem((size_t)2 * kC * kN * 2 + 64),
+          sk_mem(kWs + 1024 * sizeof(float)) {
+        ws.set_bfs_parts(kPartsF16x3);
+        pc = ws.conv("c");
+        const std::vector<float> hx = noise((size_t)kC * kL, 2.f, 3u);
+        HIP_CHECK(hipMemcpy(x.p, hx.data(), sizeof(float) * hx.size(), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(g.p, bias.data(), sizeof(float) * kC, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(b.p, bias.data(), sizeof(float) * kC, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemset(sk_mem.p, 0, kWs + 1024 * sizeof(float)));
+        X = Plane{x.f(), kC, kL, kL};
+        Y = Plane{y.f(), kC, kL, kL};
+        GX = Plane{x.f(), kC, kN, kL};   // the product reads the first 2048 columns of the same plane and writes the LayerNorm's output plane
+        GY = Plane{y.f(), kC, kN, kL};
+        xs.p = xs_mem.p;
+        xs.parts = 2;
+        xs.f16 = 1;
+        xs.sat = f16x3_sat_counter();
+        xs.C = kC;
+        xs.L = kN;
+        xs.ld = kN;
+        xs.pstride = (int64_t)kC * kN;
+        split_planes(GX, xs, nullptr);
+        sk.ws = sk_mem.f();
+        sk.ws_bytes = kWs;
+        sk.counters = reinterpret_cast<unsigned*>(sk_mem.f() + kWs / sizeof(float));
+        sk.ncounters = 1024;
+    }
+    void launch(int i, hipStream_t s) {
+        if (i & 1) conv_bfs(pc, xs, &GY, nullptr, nullptr, 1, s, ACT_NONE, nullptr, 1.0f, 1.0f, -1, 0, &sk);
+        else layernorm_ch(X, Y, g.f(), b.f(), 1e-5f, ACT_NONE, nullptr, 0, nullptr, s);
+    }
+};
+
+// launch(which, stream) enqueues the launch under test on input / output plane `which`
+template <class F>
+void run_repeated(const std::vector<RepRegion>& regs, const RepOpts& o, F&& launch, int64_t* mismatch, int64_t* first_bad) {
+    SBV2_REQUIRE(o.reps >= 2 && o.reps <= 4096 && mismatch && first_bad && o.flip_at >= -1 && o.flip_at < o.reps, "bad repetition arguments");
+    size_t total = 0;
+    for (const RepRegion& r : regs) total += r.words;
+    SBV2_REQUIRE(o.flip_at < 0 || (o.flip_word >= 0 && (size_t)o.flip_word < total), "flip_word lies outside what the launch writes");
+    std::unique_ptr<RepNeighbour> nb;
+    if (o.neighbour) nb.reset(new RepNeighbour());
+    std::vector<unsigned long long> h((size_t)2 * o.reps, 0);
+    for (int i = 0; i < o.reps; ++i) h[(size_t)o.reps + i] = ~0ull;
+    DevMem dc(h.data(), sizeof(unsigned long long) * h.size());
+    unsigned long long* cnt = static_cast<unsigned long long*>(dc.p);
+    HIP_CHECK(hipDeviceSynchronize());   // (the uploads ran on the null stream, which the two streams below do not wait for)
+    {
+        HookStream A, B;
+        for (int i = 0; i < o.reps; ++i) {
+            const int w = i & 1;
+            for (const RepRegion& r : regs)
+                if (r.init) HIP_CHECK(hipMemcpyAsync(r.out[w], r.init, r.words * 4, hipMemcpyDeviceToDevice, A.s));
+            launch(w, A.s);
+            if (i < 2)
+                for (const RepRegion& r : regs) HIP_CHECK(hipMemcpyAsync(r.ref[w], r.out[w], r.words * 4, hipMemcpyDeviceToDevice, A.s));
+            size_t word0 = 0;
+            for (const RepRegion& r : regs) {
+                if (i == o.flip_at && (size_t)o.flip_word >= word0 && (size_t)o.flip_word < word0 + r.words)
+                    hipLaunchKernelGGL(k_rep_flip, dim3(1), dim3(1), 0, A.s, static_cast<uint32_t*>(r.out[w]), (size_t)o.flip_word - word0);
+                const unsigned grid = (unsigned)std::min<size_t>((r.words / 4 + 255) / 256 + 1, 2048);
+                hipLaunchKernelGGL(k_rep_compare, dim3(grid), dim3(256), 0, A.s, static_cast<const uint32_t*>(r.out[w]), static_cast<const uint32_t*>(r.ref[w]),
+                                   r.words, (unsigned long long)word0, cnt + i, cnt + o.reps + i);
+                HIP_CHECK(hipGetLastError());
+                word0 += r.words;
+            }
+            if (nb) nb->launch(i, B.s);
+        }
+        HIP_CHECK(hipStreamSynchronize(A.s));
+        HIP_CHECK(hipStreamSynchronize(B.s));
+    }
+    HIP_CHECK(hipMemcpy(h.data(), dc.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < o.reps; ++i) {
+        mismatch[i] = (int64_t)h[i];
+        first_bad[i] = h[(size_t)o.reps + i] == ~0ull ? -1 : (int64_t)h[(size_t)o.reps + i];
+    }
+}
+
+// 0xFF bytes: NaN as f32 and as bf16
+void fill_nan(DevMem& m, size_t bytes) { HIP_CHECK(hipMemset(m.p, 0xFF, bytes)); }
+
+// the two inputs of a conv_clx launch as bf16 parts of lrelu(x, pre_slope): x channel-major [cin][L] on the host
+struct ClxInputs {
+    DevMem ma, mb;
+    SplitClPlanes xs[2];
+    ClxInputs(const float* xa, const float* xb, int64_t cin, int64_t L, float pre_slope) : ma(split_cl_bytes((int)cin, L) + 16), mb(split_cl_bytes((int)cin, L) + 16) {
+        const float* hx[2] = {xa, xb};
+        void* mem[2] = {ma.p, mb.p};
+        for (int i = 0; i < 2; ++i) {
+            DevMem dx = upload_cl(hx[i], cin, L);
+            xs[i] = make_split_cl(mem[i], (int)cin, L, nullptr);
+            split_cl(dx.f(), (int)cin, L, (int)cin, pre_slope, xs[i], nullptr);
+            HIP_CHECK(hipDeviceSynchronize());
+        }
+    }
+};
+// p0 (everything but X, Y, Ys) repeated on in.xs[which]: the f32 plane [rows][C] starts every repetition as NaN, the parts planes (want_ys) as NaN between
+// zeroed halo rows (make_split_cl's contract); the parts are compared word by word, halo rows included, behind the f32 plane's rows * C words
+void repeat_clx(ConvClxParams p0, const ClxInputs& in, int64_t C, int64_t rows, int want_ys, const RepOpts& o, float* ya, float* yb, float* ysa, float* ysb,
+                int64_t* mismatch, int64_t* first_bad) {
+    const size_t ybytes = sizeof(float) * rows * C, ysbytes = want_ys ? split_cl_bytes((int)C, rows) + 16 : 0;
+    DevMem dya(ybytes), dyb(ybytes), ra(ybytes), rb(ybytes), nan(ybytes), dysa(ysbytes), dysb(ysbytes), rsa(ysbytes), rsb(ysbytes), ysinit(ysbytes);
+    fill_nan(nan, ybytes);
+    SplitClPlanes ys[2], ysr[2];
+    if (want_ys) {
+        DevMem* mem[2] = {&dysa, &dysb};
+        void* rmem[2] = {rsa.p, rsb.p};
+        fill_nan(ysinit, ysbytes);
+        (void)make_split_cl(ysinit.p, (int)C, rows, nullptr);
+        for (int i = 0; i < 2; ++i) {
+            fill_nan(*mem[i], ysbytes);
+            ys[i] = make_split_cl(mem[i]->p, (int)C, rows, nullptr);
+            ysr[i] = ys[i];
+            ysr[i].p = rmem[i];
+        }
+    }
+    p0.X = in.xs[0];
+    p0.Y = dya.f();
+    p0.Ys = want_ys ? ys[0] : SplitClPlanes();
+    SBV2_REQUIRE(p0.W && conv_clx_usable(p0), "shape not supported by conv_clx");
+    std::vector<RepRegion> regs{{{dya.p, dyb.p}, {ra.p, rb.p}, nan.p, (size_t)rows * C}};
+    if (want_ys) regs.push_back(RepRegion{{dysa.p, dysb.p}, {rsa.p, rsb.p}, ysinit.p, split_cl_bytes((int)C, rows) / 4});
+    run_repeated(regs, o,
+                 [&](int which, hipStream_t s) {
+                     ConvClxParams p = p0;
+                     p.X = in.xs[which];
+                     p.Y = static_cast<float*>(regs[0].out[which]);
+                     if (want_ys) p.Ys = ys[which];
+                     launch_conv_clx(p, s);
+                 },
+                 mismatch, first_bad);
+    download_cl(ra.f(), C, rows, ya);
+    download_cl(rb.f(), C, rows, yb);
+    if (want_ys) {
+        read_parts(ysr[0], ysa);
+        read_parts(ysr[1], ysb);
+    }
 }
 
 }  // namespace
@@ -1662,6 +1876,377 @@ int sbv2_debug_stream_levels(int device, const void* x, int encoding, int64_t n,
     HIP_CHECK(hipStreamSynchronize(r.s));
     for (int64_t i = 0; i < nseg; ++i) seg_sumsq[i] = lv.tok_host()[2 * i], seg_peak[i] = lv.tok_host()[2 * i + 1];
     for (int64_t i = 0; i < nenv; ++i) env_sumsq[i] = lv.env_host()[2 * i], env_peak[i] = lv.env_host()[2 * i + 1];
+    API_END
+}
+
+// ---- the repeated-launch hooks (run_repeated above): operands as in the one-launch hook of the same kernel, two inputs xa / xb, ya / yb = the first result of
+// each; prev (may be null) = what every repetition accumulates onto
+int sbv2_debug_repeat_respair(int device, const float* xa, const float* xb, const float* w1, const float* w2, const float* b1, const float* b2, int64_t C,
+                              int64_t N, int64_t k, int64_t dilation, const uint8_t* mask, int64_t mask_div, float beta, const float* prev, int variant,
+                              int reps, int neighbour, int flip_at, int64_t flip_word, float* ya, float* yb, int64_t* mismatch, int64_t* first_bad) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(xa && xb && w1 && w2 && b1 && b2 && ya && yb && (C == 16 || C == 32 || C == 64) && N >= 1 && N * C < ((int64_t)1 << 31) && k >= 1 &&
+                     k <= kMaxTaps && (k & 1) && mask_div >= 1 && (mask_div & (mask_div - 1)) == 0 && variant >= 1 && variant <= 3,
+                 "bad arguments");
+    Blob b = one_conv_blob(w1, b1, {C, C, k}, C);
+    WeightStore ws(b);
+    ClConv c1 = pack_decoder_conv(ws, w1, (int)C, (int)C, (int)k, 1, b1);
+    ClConv c2 = pack_decoder_conv(ws, w2, (int)C, (int)C, (int)k, 1, b2);
+    const size_t bytes = sizeof(float) * N * C;
+    DevMem dxa(xa, bytes), dxb(xb, bytes), dya(bytes), dyb(bytes), ra(bytes), rb(bytes), init(prev, prev ? bytes : 0), nan(prev ? 0 : bytes);
+    if (!prev) fill_nan(nan, bytes);
+    DevMem dm(mask, mask ? (size_t)((N + mask_div - 1) / mask_div) : 0);
+    int shift = 0;
+    while ((1 << shift) < mask_div) ++shift;
+    ResPairParams rp = step_params(c1, c2, (int)k, (int)dilation, 1, (int)C, N, mask ? dm.u8() : nullptr, (int)mask_div, shift);
+    rp.beta = beta;
+    rp.accumulate = prev != nullptr;
+    // 1 = the default dispatch's kernel, 2 = respair_clx, 3 = respair_x16 (launch_respair_x16 refuses what that kernel does not take: no silent fall-back)
+    const BranchKernel kern = variant == 3 ? BranchKernel::respair_x16 : (variant == 2 ? BranchKernel::respair_clx : respair_default(rp));
+    const float* X[2] = {dxa.f(), dxb.f()};
+    const std::vector<RepRegion> regs{{{dya.p, dyb.p}, {ra.p, rb.p}, prev ? init.p : nan.p, (size_t)N * C}};
+    run_repeated(regs, RepOpts{reps, neighbour, flip_at, flip_word},
+                 [&](int which, hipStream_t s) {
+                     ResPairParams p = rp;
+                     p.X = X[which];
+                     p.Y = static_cast<float*>(regs[0].out[which]);
+                     launch_respair(p, kern, s);
+                 },
+                 mismatch, first_bad);
+    HIP_CHECK(hipMemcpy(ya, ra.p, bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(yb, rb.p, bytes, hipMemcpyDeviceToHost));
+    API_END
+}
+
+int sbv2_debug_repeat_resbranch(int device, const float* xa, const float* xb, const float* w, const float* bias, int64_t C, int64_t N, int64_t k,
+                                const int64_t* dilations, const uint8_t* mask, int64_t mask_div, float beta, const float* prev, int reps, int neighbour,
+                                int flip_at, int64_t flip_word, float* ya, float* yb, int64_t* mismatch, int64_t* first_bad) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(xa && xb && w && bias && ya && yb && dilations && (C == 16 || C == 32 || C == 64 || C == 128) && N >= 1 && N * C < ((int64_t)1 << 31) &&
+                     k >= 1 && k <= kMaxTaps && (k & 1) && mask_div >= 1 && (mask_div & (mask_div - 1)) == 0,
+                 "bad arguments");
+    const size_t wsz = (size_t)C * C * k;
+    Blob b = one_conv_blob(w, bias, {C, C, k}, C);
+    WeightStore ws(b);
+    std::vector<ClConv> c1, c2;   // conv1 / conv2 of each step
+    std::vector<int> dil;
+    for (int q = 0; q < kResBranchSteps; ++q) {
+        c1.push_back(pack_decoder_conv(ws, w + 2 * q * wsz, (int)C, (int)C, (int)k, 1, bias + (size_t)2 * q * C));
+        c2.push_back(pack_decoder_conv(ws, w + (2 * q + 1) * wsz, (int)C, (int)C, (int)k, 1, bias + (size_t)(2 * q + 1) * C));
+        dil.push_back((int)dilations[q]);
+    }
+    const size_t bytes = sizeof(float) * N * C;
+    DevMem dxa(xa, bytes), dxb(xb, bytes), dya(bytes), dyb(bytes), ra(bytes), rb(bytes), init(prev, prev ? bytes : 0), nan(prev ? 0 : bytes);
+    if (!prev) fill_nan(nan, bytes);
+    DevMem dm(mask, mask ? (size_t)((N + mask_div - 1) / mask_div) : 0);
+    int shift = 0;
+    while ((1 << shift) < mask_div) ++shift;
+    ResBranchParams rb0 = branch_params(c1, c2, dil, (int)k, (int)C, N, mask ? dm.u8() : nullptr, shift);
+    rb0.beta = beta;
+    rb0.accumulate = prev != nullptr;
+    const float* X[2] = {dxa.f(), dxb.f()};
+    const std::vector<RepRegion> regs{{{dya.p, dyb.p}, {ra.p, rb.p}, prev ? init.p : nan.p, (size_t)N * C}};
+    run_repeated(regs, RepOpts{reps, neighbour, flip_at, flip_word},
+                 [&](int which, hipStream_t s) {
+                     ResBranchParams p = rb0;
+                     p.X = X[which];
+                     p.Y = static_cast<float*>(regs[0].out[which]);
+                     launch_resbranch(p, s);
+                 },
+                 mismatch, first_bad);
+    HIP_CHECK(hipMemcpy(ya, ra.p, bytes, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(yb, rb.p, bytes, hipMemcpyDeviceToHost));
+    API_END
+}
+
+// x / res / y channel-major [C][L] as sbv2_debug_conv1d_clx; want_ys: the launch also writes the bf16 parts of lrelu(y, 0.1), which are compared word by word
+// (halo rows included) behind the f32 plane's L * cout words, and ysa / ysb return hi + lo of the first results
+int sbv2_debug_repeat_conv1d_clx(int device, const float* xa, const float* xb, const float* w, const float* bias, const float* res, int64_t cin, int64_t cout,
+                                 int64_t k, int64_t L, int64_t dilation, float pre_slope, float beta, int want_ys, int reps, int neighbour, int flip_at,
+                                 int64_t flip_word, float* ya, float* yb, float* ysa, float* ysb, int64_t* mismatch, int64_t* first_bad) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(xa && xb && w && ya && yb && (!want_ys || (ysa && ysb)) && L >= 1 && L * std::max(cin, cout) < ((int64_t)1 << 31), "bad arguments");
+    Blob b = one_conv_blob(w, bias, {cout, cin, k}, cout);
+    WeightStore ws(b);
+    ClConv c = pack_decoder_conv(ws, w, (int)cout, (int)cin, (int)k, 1, bias);
+    DevMem dr = res ? upload_cl(res, cout, L) : DevMem(0);
+    ClxInputs in(xa, xb, cin, L, pre_slope);
+    ConvClxParams p;
+    p.W = c.wx;
+    p.nmt = c.nmt;
+    p.M = (int)cout;
+    p.N = (int)L;
+    p.K = (int)cin;
+    p.ntaps = (int)k;
+    p.shift0 = (int)(-dilation * (k - 1) / 2);
+    p.shift_step = (int)dilation;
+    p.ldy = (int)cout;
+    p.ys_slope = 0.1f;
+    p.bias = c.bias;
+    if (res) {
+        p.R = dr.f();
+        p.ldr = (int)cout;
+    }
+    p.beta = beta;
+    repeat_clx(p, in, cout, L, want_ys, RepOpts{reps, neighbour, flip_at, flip_word}, ya, yb, ysa, ysb, mismatch, first_bad);
+    API_END
+}
+
+// the phased transposed convolution of the wide decoder stages, operands as sbv2_debug_conv_transpose1d_clx; y [cout][L * stride]
+int sbv2_debug_repeat_conv_transpose1d_clx(int device, const float* xa, const float* xb, const float* w, const float* bias, int64_t cin, int64_t cout, int64_t k,
+                                           int64_t L, int64_t stride, float pre_slope, const uint8_t* mask, int64_t mask_div, int want_ys, int reps,
+                                           int neighbour, int flip_at, int64_t flip_word, float* ya, float* yb, float* ysa, float* ysb, int64_t* mismatch,
+                                           int64_t* first_bad) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(xa && xb && w && bias && ya && yb && (!want_ys || (ysa && ysb)) && mask_div >= 1 && (mask_div & (mask_div - 1)) == 0 && L >= 1 && stride >= 1 &&
+                     L * stride * cout < ((int64_t)1 << 31) && L * cin < ((int64_t)1 << 31),
+                 "bad arguments");
+    Blob b = one_conv_blob(w, bias, {cin, cout, k}, cout);
+    WeightStore ws(b);
+    ClUpX u = build_upx(ws, w, bias, (int)cin, (int)cout, (int)k, (int)stride, /*parts_out=*/want_ys != 0);
+    SBV2_REQUIRE(u.wx, "shape not supported by the phased conv_clx transposed convolution");
+    ClxInputs in(xa, xb, cin, L, pre_slope);
+    DevMem dm(mask, mask ? (size_t)((L + mask_div - 1) / mask_div) : 0);
+    int shift = 0;
+    while ((1 << shift) < mask_div) ++shift;
+    ConvClxParams p;
+    p.W = u.wx;
+    p.nmt = u.M / 32;
+    p.M = u.M;
+    p.N = (int)L;
+    p.K = (int)cin;
+    p.ntaps = u.ntaps;
+    p.shift0 = u.shift0;
+    p.shift_step = -1;
+    p.ldy = (int)cout;
+    p.ys_slope = 0.1f;
+    p.bias = u.bias;
+    p.mask = mask ? dm.u8() : nullptr;   // indexed by the INPUT position >> shift
+    p.mask_shift = shift;
+    p.out_stride = (int)stride;
+    p.phase_rows = (int)cout;
+    p.phase_group = u.group;
+    for (int q = 0; q < kMaxPhases; ++q) {
+        p.phase_off[q] = u.phase_off[q];
+        p.phase_tap0[q] = u.phase_tap0[q];
+    }
+    repeat_clx(p, in, cout, L * stride, want_ys, RepOpts{reps, neighbour, flip_at, flip_word}, ya, yb, ysa, ysb, mismatch, first_bad);
+    API_END
+}
+
+// y[M][N] = w[M][K] x[K][N] + bias (+ res) through gemm_bfs.hip as conv_bfs launches it (parts code as sbv2_debug_gemm_bfs), with the K-split scratch of the
+// other gemm_bfs hooks; split_out: the parts copy is written and compared too (ysa / ysb = the parts' sum).  Words: the f32 plane [M][round_up(N, 64)], pad
+// columns included, then the parts planes.
+int sbv2_debug_repeat_gemm_bfs(int device, const float* xa, const float* xb, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,
+                               int parts, int split_out, int reps, int neighbour, int flip_at, int64_t flip_word, float* ya, float* yb, float* ysa, float* ysb,
+                               int64_t* mismatch, int64_t* first_bad) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE((parts == 2 || parts == 3 || parts == kPartsF16x3) && (split_out == 0 || split_out == parts) && xa && xb && w && ya && yb &&
+                     (!split_out || (ysa && ysb)) && M >= 1 && N >= 4 && (N & 3) == 0 && (K & 15) == 0 && M * (N + 64) < ((int64_t)1 << 30),
+                 "bad arguments");
+    Blob b = one_conv_blob(w, bias, {M, K, 1}, M);
+    WeightStore ws(b);
+    ws.set_bfs_parts(parts);
+    PackedConv pc = ws.conv("c");
+    const int ld = round_up((int)N, 64), np_ = split_nplanes(parts);
+    const size_t ybytes = sizeof(float) * M * ld, xbytes = sizeof(float) * K * ld, xs_bytes = (size_t)np_ * K * ld * 2 + 64,
+                 ys_bytes = split_out ? (size_t)np_ * M * ld * 2 : 0;
+    DevMem dx(xbytes), dr(res ? ybytes : 0), dxsa(xs_bytes), dxsb(xs_bytes), dya(ybytes), dyb(ybytes), ra(ybytes), rb(ybytes), nan(ybytes), dysa(ys_bytes),
+        dysb(ys_bytes), rsa(ys_bytes), rsb(ys_bytes), ysnan(ys_bytes);
+    fill_nan(nan, ybytes);
+    if (split_out) fill_nan(ysnan, ys_bytes);
+    Plane X{dx.f(), (int)K, (int)N, ld}, R{dr.f(), (int)M, (int)N, ld};
+    if (res) {
+        HIP_CHECK(hipMemset(R.p, 0, ybytes));
+        HIP_CHECK(hipMemcpy2D(R.p, sizeof(float) * ld, res, sizeof(float) * N, sizeof(float) * N, M, hipMemcpyHostToDevice));
+    }
+    SplitPlanes xs[2], ys[2];
+    for (int i = 0; i < 2; ++i) {
+        HIP_CHECK(hipMemset(X.p, 0, xbytes));
+        HIP_CHECK(hipMemcpy2D(X.p, sizeof(float) * ld, i ? xb : xa, sizeof(float) * N, sizeof(float) * N, K, hipMemcpyHostToDevice));
+        xs[i].p = i ? dxsb.p : dxsa.p;
+        xs[i].parts = np_;
+        xs[i].f16 = parts == kPartsF16x3;
+        xs[i].sat = xs[i].f16 ? f16x3_sat_counter() : nullptr;
+        xs[i].C = (int)K;
+        xs[i].L = (int)N;
+        xs[i].ld = ld;
+        xs[i].pstride = (int64_t)K * ld;
+        split_planes(X, xs[i], nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        ys[i] = xs[i];
+        ys[i].p = i ? dysb.p : dysa.p;
+        ys[i].sat = nullptr;
+        ys[i].C = (int)M;
+        ys[i].pstride = (int64_t)M * ld;
+    }
+    constexpr size_t kWs = (size_t)48 << 20;   // (as BertModel::kSkWsBytes / kSkCounters)
+    DevMem dsk(kWs + 1024 * sizeof(float));
+    HIP_CHECK(hipMemset(dsk.p, 0, kWs + 1024 * sizeof(float)));
+    BfsSplitK sk;
+    sk.ws = dsk.f();
+    sk.ws_bytes = kWs;
+    sk.counters = reinterpret_cast<unsigned*>(dsk.f() + (kWs / sizeof(float)));
+    sk.ncounters = 1024;
+    std::vector<RepRegion> regs{{{dya.p, dyb.p}, {ra.p, rb.p}, nan.p, (size_t)M * ld}};
+    if (split_out) regs.push_back(RepRegion{{dysa.p, dysb.p}, {rsa.p, rsb.p}, ysnan.p, ys_bytes / 4});
+    run_repeated(regs, RepOpts{reps, neighbour, flip_at, flip_word},
+                 [&](int which, hipStream_t s) {
+                     Plane Y{static_cast<float*>(regs[0].out[which]), (int)M, (int)N, ld};
+                     conv_bfs(pc, xs[which], &Y, split_out ? &ys[which] : nullptr, nullptr, 1, s, ACT_NONE, res ? &R : nullptr, 1.0f, 1.0f, -1, 0, &sk);
+                 },
+                 mismatch, first_bad);
+    for (int i = 0; i < 2; ++i) {
+        HIP_CHECK(hipMemcpy2D(i ? yb : ya, sizeof(float) * N, i ? rb.p : ra.p, sizeof(float) * ld, sizeof(float) * N, M, hipMemcpyDeviceToHost));
+        if (!split_out) continue;
+        std::vector<uint16_t> hs(ys_bytes / 2);
+        HIP_CHECK(hipMemcpy(hs.data(), i ? rsb.p : rsa.p, ys_bytes, hipMemcpyDeviceToHost));
+        float* out = i ? ysb : ysa;
+        for (int64_t m = 0; m < M; ++m)
+            for (int64_t n = 0; n < N; ++n) {
+                if (parts == kPartsF16x3) {
+                    _Float16 hi, lo;
+                    memcpy(&hi, &hs[(size_t)m * ld + n], 2);
+                    memcpy(&lo, &hs[((size_t)M + m) * ld + n], 2);
+                    out[(size_t)m * N + n] = (float)hi + (float)lo * (1.0f / kF16LoScale);
+                    continue;
+                }
+                float acc = 0.f;
+                for (int pp = np_ - 1; pp >= 0; --pp) {
+                    const uint32_t u = (uint32_t)hs[((size_t)pp * M + m) * ld + n] << 16;
+                    float f;
+                    memcpy(&f, &u, 4);
+                    acc += f;
+                }
+                out[(size_t)m * N + n] = acc;
+            }
+    }
+    API_END
+}
+
+// k_vits_flash_x3q on the flow's frame layout as sbv2_debug_vits_attention (variant 4 / 5) builds it, the launcher choosing the 4- or 8-wave shape by the grid
+// as in the model; q / k / v packed [heads * dk][sum lens], two sets; ctx starts every repetition as zeros (as the models clear it).  Words: the ctx plane at
+// its device pitch [heads * dk][ld], gaps and pad columns included.
+int sbv2_debug_repeat_vits_attention(int device, const float* qa, const float* ka, const float* va, const float* qb, const float* kb, const float* vb,
+                                     const float* erk, const float* erv, const int64_t* lens, int nutt, int64_t heads, int64_t dk, int64_t window, int reps,
+                                     int neighbour, int flip_at, int64_t flip_word, float* ctxa, float* ctxb, int64_t* ld_out, int64_t* mismatch,
+                                     int64_t* first_bad) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(qa && ka && va && qb && kb && vb && erk && erv && lens && ctxa && ctxb && nutt >= 1 && heads >= 1 && window >= 0 && flash_pipelined_usable((int)dk),
+                 "bad arguments");
+    std::vector<int> L(nutt);
+    for (int i = 0; i < nutt; ++i) {
+        SBV2_REQUIRE(lens[i] >= 1 && lens[i] < (1 << 20), "bad sequence length");
+        L[i] = (int)lens[i];
+    }
+    const int H = (int)(heads * dk), nw = 2 * (int)window + 1;
+    Arena ar;
+    const SegLayout lay = make_layout(L, kFrameGap, ar, nullptr, nullptr, 32);
+    const int N = lay.L;
+    Plane QKV[2] = {ar.plane(3 * H, N), ar.plane(3 * H, N)}, Cx[4] = {ar.plane(H, N), ar.plane(H, N), ar.plane(H, N), ar.plane(H, N)}, Z = ar.plane(H, N);
+    SplitPlanes kv[2];
+    const float* hq[2][3] = {{qa, ka, va}, {qb, kb, vb}};
+    for (int i = 0; i < 2; ++i) {
+        for (int j = 0; j < 3; ++j) upload_packed(hq[i][j], lay, QKV[i].rows(j * H, H), false);
+        kv[i] = alloc_split(ar, 2, 3 * H, N);
+        HIP_CHECK(hipMemset(kv[i].p, 0, (size_t)2 * kv[i].pstride * 2));
+        split_planes(QKV[i].rows(H, 2 * H), kv[i].rows(H, 2 * H), nullptr);
+    }
+    DevMem d_erk(erk, sizeof(float) * nw * dk), d_erv(erv, sizeof(float) * nw * dk);
+    const AttnPlan pl = make_attn_plan(lay, H, (int)heads, QKV[0].ld, (int)window, ar, nullptr, false);
+    const size_t words = (size_t)H * Cx[0].ld;
+    HIP_CHECK(hipMemset(Z.p, 0, words * 4));
+    const float qscale = 1.0f / std::sqrt((float)dk);   // as run_encoder
+    const std::vector<RepRegion> regs{{{Cx[0].p, Cx[1].p}, {Cx[2].p, Cx[3].p}, Z.p, words}};
+    run_repeated(regs, RepOpts{reps, neighbour, flip_at, flip_word},
+                 [&](int which, hipStream_t s) {
+                     vits_flash_attention_parts(pl.d_ag, pl.ng, pl.maxT, QKV[which].p, QKV[which].ld, kv[which], H, 2 * H, Cx[which].p, Cx[which].ld, (int)dk,
+                                                d_erk.f(), d_erv.f(), (int)window, qscale, s, 1);
+                 },
+                 mismatch, first_bad);
+    download_packed(Cx[2], lay, false, ctxa, nullptr);
+    download_packed(Cx[3], lay, false, ctxb, nullptr);
+    if (ld_out) *ld_out = Cx[0].ld;
+    API_END
+}
+
+// The flow FFN pair as VitsModel::run_encoder launches it on conv_clx.hip (weights through the builders of sbv2_debug_conv_ffn_cl: split-bf16 fragments):
+// conv_1 reads the parts of x (split_cl_km, once per input) and writes relu(.) as conv_2's operand parts, conv_2 writes the k-major plane y = conv + b + x;
+// mask [L] at both.  One repetition = both launches.  Words: the intermediate's parts planes (halo rows included), then y at its pitch [H][round_up(L, 64)].
+int sbv2_debug_repeat_conv_ffn_clx(int device, const float* xa, const float* xb, const float* w1, const float* b1, const float* w2, const float* b2, int64_t H,
+                                   int64_t F, int64_t k, int64_t L, const uint8_t* mask, int reps, int neighbour, int flip_at, int64_t flip_word, float* ya,
+                                   float* yb, int64_t* mismatch, int64_t* first_bad) {
+    API_BEGIN
+    HIP_CHECK(hipSetDevice(device));
+    SBV2_REQUIRE(xa && xb && w1 && w2 && ya && yb && H >= 1 && F >= 1 && k >= 1 && k <= kMaxTaps && (k & 1) && L >= 1 && L * F < ((int64_t)1 << 31), "bad arguments");
+    Blob bl1 = one_conv_blob(w1, b1, {F, H, k}, F), bl2 = one_conv_blob(w2, b2, {H, F, k}, H);
+    WeightStore ws1(bl1, 2), ws2(bl2, 2);
+    PackedConv c1 = ws1.conv("c"), c2 = ws2.conv("c");
+    SBV2_REQUIRE(c1.cl.wx && c2.cl.wx, "shape not supported by conv_clx");
+    DevPlane Xa(H, L), Xb(H, L), Ya(H, L), Yb(H, L), Ra(H, L), Rb(H, L), Yn(H, L);
+    Xa.put(xa, false);
+    Xb.put(xb, false);
+    const size_t ywords = (size_t)H * Xa.P.ld, xsb = split_cl_bytes((int)H, L) + 16, fsb = split_cl_bytes((int)F, L) + 16;
+    HIP_CHECK(hipMemset(Yn.P.p, 0xFF, ywords * 4));
+    DevMem mxa(xsb), mxb(xsb), mfa(fsb), mfb(fsb), rfa(fsb), rfb(fsb), finit(fsb), dm(mask, mask ? (size_t)L : 0);
+    SplitClPlanes xs[2], fs[2];
+    DevMem* fm[2] = {&mfa, &mfb};
+    fill_nan(finit, fsb);
+    (void)make_split_cl(finit.p, (int)F, L, nullptr);
+    for (int i = 0; i < 2; ++i) {
+        xs[i] = make_split_cl(i ? mxb.p : mxa.p, (int)H, L, nullptr);
+        split_cl_km(i ? Xb.P : Xa.P, 1.0f, xs[i], nullptr);
+        fill_nan(*fm[i], fsb);
+        fs[i] = make_split_cl(fm[i]->p, (int)F, L, nullptr);
+    }
+    const Plane X[2] = {Xa.P, Xb.P};
+    const std::vector<RepRegion> regs{{{mfa.p, mfb.p}, {rfa.p, rfb.p}, finit.p, split_cl_bytes((int)F, L) / 4}, {{Ya.P.p, Yb.P.p}, {Ra.P.p, Rb.P.p}, Yn.P.p, ywords}};
+    run_repeated(regs, RepOpts{reps, neighbour, flip_at, flip_word},
+                 [&](int which, hipStream_t s) {
+                     ConvClxParams p1;
+                     p1.X = xs[which];
+                     p1.W = c1.cl.wx;
+                     p1.nmt = c1.cl.nmt;
+                     p1.M = (int)F;
+                     p1.N = (int)L;
+                     p1.K = (int)H;
+                     p1.ntaps = (int)k;
+                     p1.shift0 = -(int)(k - 1) / 2;
+                     p1.shift_step = 1;
+                     p1.Ys = fs[which];
+                     p1.ys_slope = 0.0f;     // ReLU
+                     p1.bias = c1.cl.bias;
+                     p1.mask = mask ? dm.u8() : nullptr;
+                     p1.mask_shift = mask ? 0 : -1;
+                     launch_conv_clx(p1, s);
+                     ConvClxParams p2;
+                     p2.X = fs[which];
+                     p2.W = c2.cl.wx;
+                     p2.nmt = c2.cl.nmt;
+                     p2.M = (int)H;
+                     p2.N = (int)L;
+                     p2.K = (int)F;
+                     p2.ntaps = (int)k;
+                     p2.shift0 = -(int)(k - 1) / 2;
+                     p2.shift_step = 1;
+                     p2.Ykm = static_cast<float*>(regs[1].out[which]);
+                     p2.ldykm = X[which].ld;
+                     p2.Rkm = X[which].p;
+                     p2.ldrkm = X[which].ld;
+                     p2.bias = c2.cl.bias;
+                     p2.mask = p1.mask;
+                     p2.mask_shift = p1.mask_shift;
+                     launch_conv_clx(p2, s);
+                 },
+                 mismatch, first_bad);
+    (void)Ra.get(ya, kNanWord);
+    (void)Rb.get(yb, kNanWord);
     API_END
 }
 
