@@ -382,7 +382,8 @@ int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n
  *   d tau and S stay below 2^53 (6.2e15 < 9.0e15), so c has exactly one rounding, its division: lag, voiced and the three c values do not
  *   depend on the order of any sum and equal a restatement in int64 / f64 bit for bit.  For f32 samples differences and squares are taken in
  *   f64 in an order the library fixes; only that order is its own (f32 samples that are s16 integers / 32768 still give the s16 bits).
- * Not done: smoothing across frames (octave errors are the caller's to treat, with ap), pitch on a stream. */
+ * On a stream the same contour comes frame by frame: sbv2_stream_begin_request_pitch / sbv2_stream_next_pitch below.
+ * Not done: smoothing across frames (octave errors are the caller's to treat, with ap). */
 typedef struct sbv2_pitch {
     int32_t hop; int32_t reserved;        /* in: delivered samples per frame (>= 1); reserved must be 0 */
     double f0_min, f0_max, threshold;     /* in: Hz, Hz, (0, 1); usual values 70, 600, 0.15 */
@@ -642,6 +643,45 @@ typedef struct sbv2_stream_marks_part {
     int64_t delivered;
 } sbv2_stream_marks_part;
 int sbv2_stream_next_marks(sbv2_stream* s, sbv2_stream_marks_part* part);
+/* ---- new: the pitch contour of a stream, estimated chunk by chunk ON THE DEVICE.
+ * sbv2_stream_begin_request_levels with, besides, the contour of sbv2_pitch over the DELIVERED samples of the stream (the samples the levels
+ *   are taken of; on a level stream those the limiter emits), by sbv2_pitch's convention unchanged: the rate is the format's (fmt NULL = the
+ *   identity format, 44100 Hz), frame f has its centre at f hop + hop / 2 and its window [centre - tau_max, centre + tau_max), positions outside
+ *   [0, total_samples) read as 0, *n_pitch = ceil(total_samples / hop).
+ * Completion.  Frame f is complete once min(f hop + hop / 2 + tau_max, total_samples) <= D, D as for sbv2_stream_next_marks (delivered or
+ *   consumed samples; emitted ones on a level stream): frames complete in order and about tau_max samples late, everything with the last chunk.
+ * Bits.  The device keeps the last 2 tau_max delivered samples from replay to replay (19 KB in all, whatever the stream's length); a frame's
+ *   window is staged from them and from the replay's samples and then takes the one-shot kernel's own per-frame arithmetic.  So lag, ap and f0
+ *   equal sbv2_debug_pitch / sbv2_pipeline_fetch_request_pitch over the same samples bit for bit, for every encoding, f32 included, whatever
+ *   chunk_frames is.  One launch and one device-to-host copy more per replay.
+ * sp == NULL: exactly sbv2_stream_begin_request_levels (*n_pitch = 0, sbv2_stream_next_pitch refused).  Pitch may be on without levels (lv NULL)
+ *   and levels without pitch.  With pitch the audio bytes, sbv2_stream_marks and sbv2_stream_next_marks are those of the same stream without,
+ *   and the stream delivers in order only.
+ * Refused before the handles are looked at: a non-zero reserved and everything sbv2_pitch's parameters refuse at the format's rate (so rates
+ *   above 48000 Hz); besides, everything sbv2_stream_begin_request_levels refuses.  n_pitch >= 2^30 is refused where n_env >= 2^30 is.
+ * Not built: pitch on the plain sbv2_stream_begin stream (begin a request stream with fmt NULL instead), sbv2_node_*, smoothing across frames. */
+typedef struct sbv2_stream_pitch {
+    int32_t hop; int32_t reserved;        /* delivered samples per frame (>= 1); reserved must be 0 */
+    double f0_min, f0_max, threshold;     /* Hz, Hz, (0, 1); usual values 70, 600, 0.15 */
+} sbv2_stream_pitch;
+int sbv2_stream_begin_request_pitch(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                                    const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                    const sbv2_stream_request* rq, const sbv2_stream_levels* lv /* may be NULL */,
+                                    const sbv2_stream_pitch* sp /* may be NULL */, sbv2_stream** out, int64_t* total_samples, int64_t* n_tokens,
+                                    int64_t* n_env, int64_t* n_pitch);
+/* Host only: the frames [first, first + n) that became complete since the previous call, f0 / ap / lag as sbv2_pitch gives them (ap and lag may
+ * be NULL), and delivered = D.  A capacity below the pending frames, or a NULL f0 with frames pending, is refused with nothing written and
+ * nothing lost: repeat with more room.  Not calling it loses nothing.  Refused on a stream begun without pitch. */
+typedef struct sbv2_stream_pitch_part {
+    int64_t capacity; double* f0; double* ap; int32_t* lag; int64_t first, n;
+    int64_t delivered;
+} sbv2_stream_pitch_part;
+int sbv2_stream_next_pitch(sbv2_stream* s, sbv2_stream_pitch_part* part);
+/* Test hook: the fed estimator on its own.  x[n] (host; encoding and pitch as sbv2_debug_pitch) is cut at the ascending positions cuts[ncuts]
+ * into ncuts + 1 pushes (empty ones allowed), each handed a copy of its own samples only; outputs as sbv2_debug_pitch, and per_push [ncuts + 1]
+ * the frames each push completed.  Parameters, capacity and cuts are checked before any device call. */
+int sbv2_debug_stream_pitch(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, sbv2_pitch* pitch,
+                            double* cmnd3, int32_t* voiced, int64_t* per_push);
 /* Test hook: the fed reduction on its own.  x[n] (host; encoding as sbv2_debug_segment_levels) is cut at the ascending positions cuts[ncuts] into
  * ncuts + 1 pushes (empty ones allowed); segments [starts[i], ends[i]) must be monotone and disjoint within [0, n] (empty ones and holes allowed),
  * env_hop as above (0 = none).  seg_* [nseg] and env_* [ceil(n / env_hop)] receive the results, seg_per_push / env_per_push [ncuts + 1] the

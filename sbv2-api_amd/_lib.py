@@ -57,6 +57,17 @@ class Sbv2StreamMarksPart(C.Structure):
                 ("env_first", C.c_int64), ("n_env", C.c_int64), ("delivered", C.c_int64)]
 
 
+class Sbv2StreamPitch(C.Structure):
+    """struct sbv2_stream_pitch (include/sbv2_hip.h)."""
+    _fields_ = [("hop", C.c_int32), ("reserved", C.c_int32), ("f0_min", C.c_double), ("f0_max", C.c_double), ("threshold", C.c_double)]
+
+
+class Sbv2StreamPitchPart(C.Structure):
+    """struct sbv2_stream_pitch_part (include/sbv2_hip.h)."""
+    _fields_ = [("capacity", C.c_int64), ("f0", C.POINTER(C.c_double)), ("ap", C.POINTER(C.c_double)), ("lag", C.POINTER(C.c_int32)),
+                ("first", C.c_int64), ("n", C.c_int64), ("delivered", C.c_int64)]
+
+
 class Sbv2UttOptions(C.Structure):
     """struct sbv2_utt_options (include/sbv2_hip.h)."""
     _fields_ = [("sdp_ratio", f32p), ("length_scale", f32p), ("noise_scale", f32p), ("noise_scale_w", f32p),
@@ -200,6 +211,12 @@ SYMBOLS = {
     "sbv2_stream_next_marks": (C.c_int, [C.c_void_p, C.POINTER(Sbv2StreamMarksPart)]),
     "sbv2_debug_stream_levels": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, i64p, C.c_int, i64p, i64p, C.c_int64, C.c_int32,
                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i64p, i64p]),
+    "sbv2_stream_begin_request_pitch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p, i64p, i64p, C.c_int64,
+                                                  C.POINTER(Sbv2StreamRequest), C.POINTER(Sbv2StreamLevels), C.POINTER(Sbv2StreamPitch),
+                                                  C.POINTER(C.c_void_p), i64p, i64p, i64p, i64p]),
+    "sbv2_stream_next_pitch": (C.c_int, [C.c_void_p, C.POINTER(Sbv2StreamPitchPart)]),
+    "sbv2_debug_stream_pitch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Pitch),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_int32), i64p]),
     "sbv2_stream_min_gap": (C.c_int64, [C.POINTER(Sbv2PcmFormat)]),
     "sbv2_stream_timeline": (C.c_int, [i64p, i64p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, i64p, i64p, C.c_int64, i64p]),
     "sbv2_stream_layout": (C.c_int, [C.c_void_p, i64p, i64p, C.c_int64, i64p, i64p]),

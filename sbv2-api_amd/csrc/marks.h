@@ -1,7 +1,8 @@
 // Speech marks (marks.hip): where each token lies in a delivered signal (host arithmetic, marks_spans) and how loud it is there (one
 // segmented reduction over the samples a formatted fetch leaves in HBM: sum of squares and peak per [start, end) segment).  Used by
 // sbv2_pipeline_fetch_request_marks (fetch_formatted, api.cpp), sbv2_stream_marks (stream.cpp) and the test hook sbv2_debug_segment_levels.
-// Beside them the pitch contour of the same samples (Pitch: YIN per frame; sbv2_pipeline_fetch_request_pitch, sbv2_debug_pitch).
+// Beside them the pitch contour of the same samples (Pitch: YIN per frame; sbv2_pipeline_fetch_request_pitch, sbv2_debug_pitch) and the same
+// contour fed replay by replay (StreamPitch; sbv2_stream_begin_request_pitch, sbv2_debug_stream_pitch).
 #pragma once
 #include "common.h"
 #include "pcm_format.h"
@@ -127,6 +128,56 @@ class StreamLevels {
     double *d_carry_ = nullptr, *d_res_ = nullptr, *res_host_ = nullptr;
     int64_t ntok_ = 0, nenv_ = 0, env_hop_ = 0, total_ = 0, fed_ = 0, tok_done_ = 0, env_done_ = 0;
     int parity_ = 0;
+};
+
+// The same estimator FED piece by piece (a stream's replays), by sbv2_pitch's convention unchanged: frame f has its centre at f hop + hop / 2,
+// its window is [centre - tau_max, centre + tau_max), positions outside [0, total) read as 0, n_frames = ceil(total / hop).
+// The completion rule: frame f is complete once min(f hop + hop / 2 + tau_max, total) <= D, D the samples fed (or, for what a stream hands out,
+// delivered) so far.  Frames complete in order and about tau_max samples late; after the last push everything is complete.
+// The carry: the last min(D, 2 tau_max) fed samples, in the sample's own type (float, int16_t, one-byte G.711 code), on the device.  That is
+// enough: the first incomplete frame has centre + tau_max > D, so its window starts after D - 2 tau_max.  Sized once for 2 kPitchMaxTau
+// elements and held twice (a push reads one copy and writes the other: a push shorter than the carry keeps part of the old one, and no workgroup
+// reads what another one of the same launch overwrites) = 19 KB whatever the stream's length.
+// A push is ONE launch (k_stream_pitch: one workgroup per frame it completed, staging the window from the carry and from x and then running
+// k_pitch_yin's own per-frame body, and behind them the workgroups that write the next carry) and one copy of the completed slots to the pinned
+// mirror; a push that completes no frame still updates the carry, n = 0 enqueues nothing.  Scalars by value, nothing allocated after begin, no
+// atomics.
+// Bits: a frame's sums depend on its window and on tau_max only, so lag, voiced and the three c values of every frame equal Pitch::run over the
+// whole signal bit for bit, for every encoding (f32 included), whatever the pushes.
+struct PitchFrame {   // one frame's device results (32 bytes): what Pitch keeps as c3 | lag | voiced, side by side so that a push copies one range
+    double c3[3];
+    int32_t lag, voiced;
+};
+class StreamPitch {
+  public:
+    StreamPitch() = default;
+    StreamPitch(const StreamPitch&) = delete;
+    StreamPitch& operator=(const StreamPitch&) = delete;
+    // Host only, throws: the spec's lags within kPitchMaxTau, fewer than 2^30 frames
+    static void check(const PitchSpec& sp, int64_t total);
+    // Waits for s once (the buffers of an earlier stream are reused).
+    void begin(const PitchSpec& sp, int encoding, int64_t total, hipStream_t s);
+    // x = the sample at delivered position D0 (device), D0 = fed(); returns the frames this push completed; n = 0 enqueues nothing
+    int64_t push(const void* x, int64_t D0, int64_t n, hipStream_t s);
+    int64_t fed() const { return fed_; }
+    int64_t total() const { return total_; }
+    int64_t n_frames() const { return nf_; }
+    const PitchSpec& spec() const { return sp_; }
+    int64_t complete(int64_t D) const;   // the completion rule: frames complete once D samples are in
+    // frame f is valid once the push that completed it has run on s
+    const double* c3_host(int64_t f) const { return res_host_[f].c3; }
+    int32_t lag_host(int64_t f) const { return res_host_[f].lag; }
+    int32_t voiced_host(int64_t f) const { return res_host_[f].voiced; }
+
+  private:
+    static constexpr size_t kCarryBytes = 2 * (size_t)kPitchMaxTau * sizeof(float);   // one copy, in the widest sample type
+    PinnedBuffer host_;   // the results' mirror
+    DeviceBuffer dev_;    // carry (2 copies) | results
+    PitchSpec sp_;
+    char* d_carry_ = nullptr;
+    PitchFrame *d_res_ = nullptr, *res_host_ = nullptr;
+    int64_t total_ = 0, nf_ = 0, fed_ = 0, done_ = 0;
+    int encoding_ = 0, parity_ = 0;
 };
 
 }  // namespace sbv2

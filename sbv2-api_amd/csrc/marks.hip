@@ -11,7 +11,7 @@
 // on the segment's length alone: no atomics, equal samples give equal bits wherever the segment lies.  s16 samples are squared as integers
 // (exact in f64, as are their sums below 2^53), and so are the integers that G.711 codes decode to (one byte per sample, any start); an f32 sample's square is exact in f64 too, so only the order of the sum is this kernel's own.
 // Each sample is read once per table it appears in (tokens, frames): the launch is bound by its few MB of HBM reads.
-// The pitch contour of the same samples (k_pitch_yin) is at the end of the file.
+// The pitch contour of the same samples (k_pitch_yin, and k_stream_pitch for a stream's replays) is at the end of the file.
 #include "marks.h"
 
 #include <climits>
@@ -397,8 +397,10 @@ struct PitchTypes<float> {
 
 constexpr int kPitchMaxP = (kPitchMaxTau + kBlock - 1) / kBlock;   // lags per lane at the largest window
 
-template <class T, int P>
-__global__ __launch_bounds__(kBlock) void k_pitch_yin(const PitchArgs a) {
+// One frame, by the workgroup that owns it: `at(i)` gives the sample at delivered position i (zero outside the signal) and is the only thing
+// the one-shot kernel and the fed one (k_stream_pitch) do differently; everything behind the staging is this one body.
+template <class T, int P, class At>
+__device__ inline void pitch_frame(const At& at, int64_t b, int tau_min, int W, double threshold, double* o, int32_t* o_lag, int32_t* o_voiced) {
     using S = typename PitchTypes<T>::S;
     using D = typename PitchTypes<T>::D;
     __shared__ S win[2 * kPitchMaxTau];
@@ -407,13 +409,8 @@ __global__ __launch_bounds__(kBlock) void k_pitch_yin(const PitchArgs a) {
     __shared__ D part[kBlock];
     __shared__ int sh_first[kWavesPerBlock], sh_arg[kWavesPerBlock];
     __shared__ double sh_min[kWavesPerBlock];
-    const T* x = static_cast<const T*>(a.x);
-    const int nt = blockDim.x, tid = threadIdx.x, W = a.tau_max;   // nt P >= W (Pitch::run)
-    const int64_t b = (int64_t)blockIdx.x * a.hop + a.hop / 2 - W;
-    for (int k = tid; k < 2 * W; k += nt) {
-        const int64_t i = b + k;
-        win[k] = i >= 0 && i < a.n ? static_cast<S>(level_load(x, i)) : S(0);
-    }
+    const int nt = blockDim.x, tid = threadIdx.x;   // nt P >= W (pitch_lanes)
+    for (int k = tid; k < 2 * W; k += nt) win[k] = at(b + k);
     __syncthreads();
     int tau[P];
     D acc[P];
@@ -459,8 +456,8 @@ __global__ __launch_bounds__(kBlock) void k_pitch_yin(const PitchArgs a) {
         run += d;
         const double c = run == D(0) ? 1.0 : (double)d * (double)t / (double)run;   // both exact below 2^53 for integers: one rounding
         cc[t] = c;
-        if (t >= a.tau_min) {
-            if (c < a.threshold && first == INT_MAX) first = t;
+        if (t >= tau_min) {
+            if (c < threshold && first == INT_MAX) first = t;
             if (c < cmin) cmin = c, arg = t;
         }
     }
@@ -480,30 +477,90 @@ __global__ __launch_bounds__(kBlock) void k_pitch_yin(const PitchArgs a) {
             if (sh_min[w] < cmin || (sh_min[w] == cmin && sh_arg[w] < arg)) cmin = sh_min[w], arg = sh_arg[w];
         }
         const bool voiced = first != INT_MAX;
-        int lag = voiced ? first : arg != INT_MAX ? arg : a.tau_min;   // (no minimum: every c is a NaN, from non-finite f32 samples)
+        int lag = voiced ? first : arg != INT_MAX ? arg : tau_min;   // (no minimum: every c is a NaN, from non-finite f32 samples)
         if (voiced)
             while (lag + 1 <= W && cc[lag + 1] < cc[lag]) ++lag;
         const double c0 = cc[lag];
-        double* o = a.c3 + 3 * (int64_t)blockIdx.x;
         o[0] = lag - 1 >= 1 ? cc[lag - 1] : c0;
         o[1] = c0;
         o[2] = lag + 1 <= W ? cc[lag + 1] : c0;
-        a.lag[blockIdx.x] = lag;
-        a.voiced[blockIdx.x] = voiced;
+        *o_lag = lag;
+        *o_voiced = voiced;
     }
 }
 
+template <class T, int P>
+__global__ __launch_bounds__(kBlock) void k_pitch_yin(const PitchArgs a) {
+    using S = typename PitchTypes<T>::S;
+    const T* x = static_cast<const T*>(a.x);
+    const int64_t n = a.n;
+    const auto at = [x, n](int64_t i) -> S { return i >= 0 && i < n ? static_cast<S>(level_load(x, i)) : S(0); };
+    const int64_t f = blockIdx.x;
+    pitch_frame<T, P>(at, f * a.hop + a.hop / 2 - a.tau_max, a.tau_min, a.tau_max, a.threshold, a.c3 + 3 * f, a.lag + f, a.voiced + f);
+}
+
+// The fed estimator (StreamPitch, marks.h): the workgroups [0, count) take the frames first, first + 1, ... that this push completed, the
+// workgroups behind them write the next carry.  A frame's window lies in [d0 - cl, d1): positions below d0 come from the carry (the cl
+// samples before d0, in the sample's own type), the rest from x (the sample at d0 onwards); nothing outside carry_in[0, cl) and x[0, d1 - d0)
+// is addressed, whatever the arguments.
+struct StreamPitchArgs {
+    const void* x;
+    const void* carry_in;   // positions [d0 - cl, d0)
+    void* carry_out;        // positions [d1 - cl_out, d1)
+    int64_t d0, d1, total, hop, first;
+    int32_t count, cl, cl_out;
+    int32_t tau_min, tau_max;
+    double threshold;
+    PitchFrame* res;        // [nf]
+};
+
+template <class T, int P>
+__global__ __launch_bounds__(kBlock) void k_stream_pitch(const StreamPitchArgs a) {
+    using S = typename PitchTypes<T>::S;
+    const T* x = static_cast<const T*>(a.x);
+    const T* cin = static_cast<const T*>(a.carry_in);
+    const int64_t d0 = a.d0, d1 = a.d1, c0 = a.d0 - a.cl;
+    if ((int)blockIdx.x >= a.count) {   // the carry: a push shorter than it keeps the end of the old one in front of x (uniform: no barrier here)
+        T* cout = static_cast<T*>(a.carry_out);
+        const int j = ((int)blockIdx.x - a.count) * (int)blockDim.x + (int)threadIdx.x;
+        if (j >= a.cl_out) return;
+        const int64_t i = d1 - a.cl_out + j;
+        if (i >= d0) cout[j] = x[i - d0];
+        else if (i >= c0) cout[j] = cin[i - c0];
+        return;
+    }
+    const int64_t total = a.total;
+    const auto at = [x, cin, d0, d1, c0, total](int64_t i) -> S {
+        if (i < 0 || i >= total) return S(0);
+        if (i >= d0) return i < d1 ? static_cast<S>(level_load(x, i - d0)) : S(0);
+        return i >= c0 ? static_cast<S>(level_load(cin, i - c0)) : S(0);
+    };
+    const int64_t f = a.first + (int)blockIdx.x;
+    PitchFrame* r = a.res + f;
+    pitch_frame<T, P>(at, f * a.hop + a.hop / 2 - a.tau_max, a.tau_min, a.tau_max, a.threshold, r->c3, &r->lag, &r->voiced);
+}
+
+#define SBV2_PITCH_LAUNCH(KERNEL)                                                             \
+    static_assert(kPitchMaxP == 5, "one case per lag count");                                 \
+    switch (P) {                                                                              \
+        case 1: hipLaunchKernelGGL((KERNEL<T, 1>), grid, blk, 0, s, a); break;                \
+        case 2: hipLaunchKernelGGL((KERNEL<T, 2>), grid, blk, 0, s, a); break;                \
+        case 3: hipLaunchKernelGGL((KERNEL<T, 3>), grid, blk, 0, s, a); break;                \
+        case 4: hipLaunchKernelGGL((KERNEL<T, 4>), grid, blk, 0, s, a); break;                \
+        default: hipLaunchKernelGGL((KERNEL<T, 5>), grid, blk, 0, s, a); break;               \
+    }
 template <class T>
 void launch_pitch(int P, dim3 grid, dim3 blk, hipStream_t s, const PitchArgs& a) {
-    static_assert(kPitchMaxP == 5, "one case per lag count");
-    switch (P) {
-        case 1: hipLaunchKernelGGL((k_pitch_yin<T, 1>), grid, blk, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((k_pitch_yin<T, 2>), grid, blk, 0, s, a); break;
-        case 3: hipLaunchKernelGGL((k_pitch_yin<T, 3>), grid, blk, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((k_pitch_yin<T, 4>), grid, blk, 0, s, a); break;
-        default: hipLaunchKernelGGL((k_pitch_yin<T, 5>), grid, blk, 0, s, a); break;
-    }
+    SBV2_PITCH_LAUNCH(k_pitch_yin)
 }
+template <class T>
+void launch_stream_pitch(int P, dim3 grid, dim3 blk, hipStream_t s, const StreamPitchArgs& a) {
+    SBV2_PITCH_LAUNCH(k_stream_pitch)
+}
+#undef SBV2_PITCH_LAUNCH
+
+// a small window (8 or 16 kHz) takes one or two waves per frame instead of four; a large one several lags per lane
+inline int pitch_lanes(int tau_max) { return tau_max <= kWave ? kWave : tau_max <= 2 * kWave ? 2 * kWave : kBlock; }
 
 }  // namespace
 
@@ -558,8 +615,7 @@ void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hip
     a.c3 = reinterpret_cast<double*>(d);
     a.lag = reinterpret_cast<int32_t*>(d + 24 * (size_t)nf);
     a.voiced = a.lag + nf;
-    // a small window (8 or 16 kHz) takes one or two waves per frame instead of four; a large one several lags per lane
-    const int nt = sp.tau_max <= kWave ? kWave : sp.tau_max <= 2 * kWave ? 2 * kWave : kBlock, P = (sp.tau_max + nt - 1) / nt;
+    const int nt = pitch_lanes(sp.tau_max), P = (sp.tau_max + nt - 1) / nt;
     const dim3 grid((unsigned)nf), blk(nt);
     if (encoding == kEncS16) launch_pitch<int16_t>(P, grid, blk, s, a);
     else if (encoding == kEncMulaw) launch_pitch<MulawCode>(P, grid, blk, s, a);
@@ -567,6 +623,77 @@ void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hip
     else launch_pitch<float>(P, grid, blk, s, a);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s));
+}
+
+// ---- the fed estimator (StreamPitch, marks.h) ----
+void StreamPitch::check(const PitchSpec& sp, int64_t total) {
+    SBV2_REQUIRE(total >= 0 && sp.hop >= 1 && sp.tau_min >= 1 && sp.tau_min <= sp.tau_max && sp.tau_max <= kPitchMaxTau, "internal: bad pitch spec");
+    const int64_t nf = pitch_frames(total, sp.hop);
+    SBV2_REQUIRE(nf < (1 << 30), "too many pitch frames: " + std::to_string(nf) + " >= 2^30");
+}
+
+int64_t StreamPitch::complete(int64_t D) const {
+    if (nf_ == 0 || D >= total_) return nf_;
+    const int64_t r = D - sp_.tau_max - sp_.hop / 2;   // frame f: f hop + hop / 2 + tau_max <= D
+    return r < 0 ? 0 : std::min(nf_, r / sp_.hop + 1);
+}
+
+void StreamPitch::begin(const PitchSpec& sp, int encoding, int64_t total, hipStream_t s) {
+    SBV2_REQUIRE(pcm_encoding_known(encoding), "internal: pitch of an unknown encoding");
+    check(sp, total);
+    sp_ = sp;
+    encoding_ = encoding;
+    total_ = total;
+    nf_ = pitch_frames(total, sp.hop);
+    fed_ = done_ = 0;
+    parity_ = 0;
+    // device: carry (two copies, each 2 kPitchMaxTau elements of the widest sample type) | results; pinned: the results
+    const size_t o_res = 2 * kCarryBytes, bytes = o_res + sizeof(PitchFrame) * (size_t)nf_, h_bytes = sizeof(PitchFrame) * (size_t)nf_;
+    char* d = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes * 2, 32768), s));
+    char* h = static_cast<char*>(host_.reserve(std::max<size_t>(h_bytes, 64), std::max<size_t>(h_bytes * 2, 4096), s));
+    HIP_CHECK(hipStreamSynchronize(s));   // (an earlier stream's copies into the mirror are done)
+    d_carry_ = d;
+    d_res_ = reinterpret_cast<PitchFrame*>(d + o_res);
+    res_host_ = reinterpret_cast<PitchFrame*>(h);
+    HIP_CHECK(hipMemsetAsync(d_carry_, 0, 2 * kCarryBytes, s));
+}
+
+int64_t StreamPitch::push(const void* x, int64_t D0, int64_t n, hipStream_t s) {
+    SBV2_REQUIRE(n >= 0 && D0 == fed_ && D0 + n <= total_, "internal: a pitch push of [" + std::to_string(D0) + ", " + std::to_string(D0 + n) +
+                                                               ") out of stream order (" + std::to_string(fed_) + " of " + std::to_string(total_) + " fed)");
+    const int64_t D1 = D0 + n, now = complete(D1), done = now - done_;
+    fed_ = D1;
+    if (n > 0) {
+        SBV2_REQUIRE(x, "internal: no samples to push");
+        const int64_t keep = 2 * (int64_t)sp_.tau_max;
+        StreamPitchArgs a{};
+        a.x = x;
+        a.carry_in = d_carry_ + (size_t)parity_ * kCarryBytes;
+        a.carry_out = d_carry_ + (size_t)(parity_ ^ 1) * kCarryBytes;
+        a.d0 = D0;
+        a.d1 = D1;
+        a.total = total_;
+        a.hop = sp_.hop;
+        a.first = done_;
+        a.count = (int32_t)done;
+        a.cl = (int32_t)std::min(D0, keep);
+        a.cl_out = (int32_t)std::min(D1, keep);
+        a.tau_min = sp_.tau_min;
+        a.tau_max = sp_.tau_max;
+        a.threshold = sp_.threshold;
+        a.res = d_res_;
+        const int nt = pitch_lanes(sp_.tau_max), P = (sp_.tau_max + nt - 1) / nt;
+        const dim3 grid((unsigned)(done + (a.cl_out + nt - 1) / nt)), blk(nt);
+        if (encoding_ == kEncS16) launch_stream_pitch<int16_t>(P, grid, blk, s, a);
+        else if (encoding_ == kEncMulaw) launch_stream_pitch<MulawCode>(P, grid, blk, s, a);
+        else if (encoding_ == kEncAlaw) launch_stream_pitch<AlawCode>(P, grid, blk, s, a);
+        else launch_stream_pitch<float>(P, grid, blk, s, a);
+        HIP_CHECK(hipGetLastError());
+        parity_ ^= 1;
+        if (done) HIP_CHECK(hipMemcpyAsync(res_host_ + done_, d_res_ + done_, sizeof(PitchFrame) * (size_t)done, hipMemcpyDeviceToHost, s));
+    }
+    done_ = now;
+    return done;
 }
 
 }  // namespace sbv2

@@ -297,6 +297,9 @@ StreamTimeline stream_timeline(const int64_t* frames, const int64_t* gap_after, 
 struct StreamMarksSpec {
     bool tokens = false;
     int64_t env_hop = 0;
+    // the pitch contour of the delivered samples (sbv2_stream_pitch): on or off independently of the levels; the spec at the stream's delivered rate
+    bool pitch = false;
+    PitchSpec pitch_spec;
 };
 struct VitsBatch {
     int n = 0;
@@ -350,11 +353,13 @@ class VitsModel {
     // ceiling; what it emits is cast / quantised and delivered (or, with flac, pushed into the encoder): delivery runs A samples behind
     // gap_after (needs fmt): [n] native samples of silence after each row of the forward, the rows joined as stream_timeline lays them out
     // marks (needs fmt): levels per token and / or per envelope frame of the DELIVERED samples, reduced replay by replay (StreamLevels, marks.h):
-    // one push per replay on what crosses PCIe or enters the FLAC encoder; such a stream delivers in order only
+    // one push per replay on what crosses PCIe or enters the FLAC encoder; such a stream delivers in order only.  marks->pitch: the pitch contour
+    // of the same samples, fed by the same pushes (StreamPitch, marks.h), with or without the levels; in order only as well
     int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false, const StreamLevelSpec* level = nullptr,
                          const int64_t* gap_after = nullptr, const StreamMarksSpec* marks = nullptr);
     // a stream begun with marks: its reduction (nullptr otherwise) and the samples delivered so far (what the taken calls handed out)
     const StreamLevels* stream_marks_levels() const { return smarks_on_ ? smarks_.get() : nullptr; }
+    const StreamPitch* stream_marks_pitch() const { return spitch_on_ ? spitch_.get() : nullptr; }
     int64_t stream_delivered() const { return sdelivered_; }
     const StreamTimeline& stream_layout() const { return stl_; }
     int64_t stream_call_bound() const;   // bytes that suffice for any one call of the running stream
@@ -511,6 +516,8 @@ class VitsModel {
     std::shared_ptr<StreamLimiter> slim_;
     bool smarks_on_ = false;                     // ... and its delivered samples are reduced to levels replay by replay (stream_begin with marks)
     std::shared_ptr<StreamLevels> smarks_;
+    bool spitch_on_ = false;                     // ... and / or to a pitch contour (stream_begin with marks->pitch)
+    std::shared_ptr<StreamPitch> spitch_;
     int64_t sdelivered_ = 0;                     // delivered samples the taken calls of a formatted stream handed out
     bool stream_bursts_ = false;                 // the running stream uses burst_ behind its first chunk
     std::shared_ptr<ChunkPlan> chunk_, burst_;   // one window (an utterance's first chunk) / kStreamBurst windows per replay (every later one)

@@ -21,6 +21,9 @@ struct sbv2_stream {
     // levels (sbv2_stream_begin_request_levels): the entries sbv2_stream_next_marks has handed out so far
     bool levels = false;
     int64_t tok_out = 0, env_out = 0;
+    // pitch (sbv2_stream_begin_request_pitch): the frames sbv2_stream_next_pitch has handed out so far
+    bool pitch = false;
+    int64_t pitch_out = 0;
 };
 
 namespace {
@@ -51,6 +54,7 @@ void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const in
     s->level = level != nullptr;
     s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after, marks);
     s->levels = vits->m->stream_marks_levels() != nullptr;
+    s->pitch = vits->m->stream_marks_pitch() != nullptr;
     if (total_samples) *total_samples = pcm_format_out_len(s->spec, vits->m->stream_layout().joined);
     *out = s.release();
 }
@@ -305,6 +309,20 @@ int sbv2_stream_begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch
     API_END
 }
 
+namespace {
+// sbv2_stream_levels' fields, checked before the handles are looked at; true when anything is on
+bool levels_spec(const sbv2_stream_levels* lv, StreamMarksSpec* marks) {
+    if (lv) {
+        SBV2_REQUIRE(lv->reserved[0] == 0 && lv->reserved[1] == 0, "sbv2_stream_levels.reserved must be 0");
+        SBV2_REQUIRE(lv->tokens == 0 || lv->tokens == 1, "sbv2_stream_levels.tokens must be 0 or 1");
+        SBV2_REQUIRE(lv->env_hop >= 0, "sbv2_stream_levels.env_hop must be >= 0 (0 = no envelope)");
+        marks->tokens = lv->tokens == 1;
+        marks->env_hop = lv->env_hop;
+    }
+    return marks->tokens || marks->env_hop > 0;
+}
+}  // namespace
+
 // The same stream with the levels of its delivered samples reduced replay by replay (StreamLevels, marks.hip).  lv NULL or all off: exactly the
 // call above.  The levels' fields are checked first, before the handles are looked at.
 int sbv2_stream_begin_request_levels(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids,
@@ -312,18 +330,35 @@ int sbv2_stream_begin_request_levels(sbv2_bert* bert, sbv2_vits* vits, const sbv
                                      const sbv2_stream_levels* lv, sbv2_stream** out, int64_t* total_samples, int64_t* n_tokens, int64_t* n_env) {
     API_BEGIN
     StreamMarksSpec marks;
-    if (lv) {
-        SBV2_REQUIRE(lv->reserved[0] == 0 && lv->reserved[1] == 0, "sbv2_stream_levels.reserved must be 0");
-        SBV2_REQUIRE(lv->tokens == 0 || lv->tokens == 1, "sbv2_stream_levels.tokens must be 0 or 1");
-        SBV2_REQUIRE(lv->env_hop >= 0, "sbv2_stream_levels.env_hop must be >= 0 (0 = no envelope)");
-        marks.tokens = lv->tokens == 1;
-        marks.env_hop = lv->env_hop;
-    }
-    const bool on = marks.tokens || marks.env_hop > 0;
+    const bool on = levels_spec(lv, &marks);
     begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples);
     const StreamLevels* l = (*out)->vits->m->stream_marks_levels();
     if (n_tokens) *n_tokens = l ? l->n_tok() : 0;
     if (n_env) *n_env = l ? l->n_env() : 0;
+    API_END
+}
+
+// ... and with the pitch contour of the same samples, fed by the same pushes (StreamPitch, marks.hip).  sp NULL: exactly the call above.  The
+// levels' and the pitch's fields are checked first, before the handles are looked at: the rate is the format's, a NULL fmt = 44100 Hz.
+int sbv2_stream_begin_request_pitch(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids,
+                                    const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
+                                    const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp, sbv2_stream** out, int64_t* total_samples,
+                                    int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch) {
+    API_BEGIN
+    StreamMarksSpec marks;
+    bool on = levels_spec(lv, &marks);
+    if (sp) {
+        SBV2_REQUIRE(sp->reserved == 0, "sbv2_stream_pitch.reserved must be 0");
+        const int rate = rq && rq->fmt ? pcm_format_spec(rq->fmt).rate : PcmFmtSpec().rate;
+        marks.pitch_spec = pitch_spec(rate, sp->hop, sp->f0_min, sp->f0_max, sp->threshold);
+        marks.pitch = on = true;
+    }
+    begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples);
+    const StreamLevels* l = (*out)->vits->m->stream_marks_levels();
+    const StreamPitch* q = (*out)->vits->m->stream_marks_pitch();
+    if (n_tokens) *n_tokens = l ? l->n_tok() : 0;
+    if (n_env) *n_env = l ? l->n_env() : 0;
+    if (n_pitch) *n_pitch = q ? q->n_frames() : 0;
     API_END
 }
 
@@ -356,6 +391,30 @@ int sbv2_stream_next_marks(sbv2_stream* s, sbv2_stream_marks_part* part) {
     part->delivered = D;
     s->tok_out += nt;
     s->env_out += ne;
+    API_END
+}
+
+// The pitch frames completed since the previous call (the rule above sbv2_stream_next_pitch, include/sbv2_hip.h), finished on the host as the
+// fetch finishes them.  Host only, for the reason given above sbv2_stream_next_marks.
+int sbv2_stream_next_pitch(sbv2_stream* s, sbv2_stream_pitch_part* part) {
+    API_BEGIN
+    SBV2_REQUIRE(s && part, "bad arguments");
+    SBV2_REQUIRE(s->pitch, "this stream was begun without pitch: begin it with sbv2_stream_begin_request_pitch");
+    const StreamPitch* q = s->vits->m->stream_marks_pitch();
+    SBV2_REQUIRE(q, "internal: the stream's pitch estimator is gone");
+    const int64_t D = s->next >= s->calls ? q->total() : s->vits->m->stream_delivered();
+    const int64_t n = q->complete(D) - s->pitch_out;
+    SBV2_REQUIRE(part->capacity >= n, "pitch arrays too small: " + std::to_string(part->capacity) + " < " + std::to_string(n) + " pending frames");
+    SBV2_REQUIRE(n == 0 || part->f0, "NULL f0 with " + std::to_string(n) + " pending frames");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t f = s->pitch_out + i;
+        pitch_finish(q->spec(), q->lag_host(f), q->voiced_host(f), q->c3_host(f), part->f0 + i, part->ap ? part->ap + i : nullptr);
+        if (part->lag) part->lag[i] = q->lag_host(f);
+    }
+    part->first = s->pitch_out;
+    part->n = n;
+    part->delivered = D;
+    s->pitch_out += n;
     API_END
 }
 

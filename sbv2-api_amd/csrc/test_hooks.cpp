@@ -1879,6 +1879,53 @@ int sbv2_debug_stream_levels(int device, const void* x, int encoding, int64_t n,
     API_END
 }
 
+// The fed pitch estimator (StreamPitch, marks.hip) on its own: x cut at cuts[ncuts] into ncuts + 1 pushes.  Each push is handed a COPY of its
+// piece, between two guards of a fill pattern, never a pointer into the whole signal: a kernel that looked for earlier samples in front of x
+// instead of in its carry would not find them.  Parameters, capacity and cuts are checked before any device call.
+int sbv2_debug_stream_pitch(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, sbv2_pitch* pitch,
+                            double* cmnd3, int32_t* voiced, int64_t* per_push) {
+    API_BEGIN
+    SBV2_REQUIRE(pitch && per_push && pcm_encoding_known(encoding) && n >= 0 && ncuts >= 0 && (x || n == 0) && (ncuts == 0 || cuts), "bad arguments");
+    SBV2_REQUIRE(pitch->reserved == 0, "sbv2_pitch.reserved must be 0");
+    const PitchSpec sp = pitch_spec(sample_rate, pitch->hop, pitch->f0_min, pitch->f0_max, pitch->threshold);
+    StreamPitch::check(sp, n);
+    const int64_t nf = pitch_frames(n, sp.hop);
+    SBV2_REQUIRE(pitch->capacity >= nf, "pitch arrays too small: " + std::to_string(pitch->capacity) + " < " + std::to_string(nf) + " frames");
+    SBV2_REQUIRE(pitch->f0, "sbv2_pitch.f0 must not be NULL");
+    std::vector<int64_t> edge(1, 0);
+    int64_t longest = 0;
+    for (int i = 0; i < ncuts; ++i) {
+        SBV2_REQUIRE(cuts[i] >= edge.back() && cuts[i] <= n, "cuts must ascend within [0, n]");
+        edge.push_back(cuts[i]);
+    }
+    edge.push_back(n);
+    for (size_t i = 0; i + 1 < edge.size(); ++i) longest = std::max(longest, edge[i + 1] - edge[i]);
+    const size_t esz = pcm_encoding_bytes(encoding), guard = 4096;
+    AudioScratch r(device, x, (size_t)n * esz);
+    DeviceBuffer piece;
+    char* pc = static_cast<char*>(piece.reserve((size_t)longest * esz + 2 * guard, (size_t)longest * esz + 2 * guard, r.s));
+    HIP_CHECK(hipMemsetAsync(pc, 0x5A, (size_t)longest * esz + 2 * guard, r.s));
+    StreamPitch est;
+    est.begin(sp, encoding, n, r.s);
+    for (int i = 0; i <= ncuts; ++i) {
+        const int64_t len = edge[i + 1] - edge[i];
+        // (stream order: the previous push's launch has read the piece before this copy overwrites it)
+        if (len) HIP_CHECK(hipMemcpyAsync(pc + guard, r.x.as<char>() + (size_t)edge[i] * esz, (size_t)len * esz, hipMemcpyDeviceToDevice, r.s));
+        per_push[i] = est.push(pc + guard, edge[i], len, r.s);
+    }
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    SBV2_REQUIRE(est.complete(est.fed()) == nf, "internal: frames left incomplete after the last push");
+    for (int64_t f = 0; f < nf; ++f) {
+        const int32_t lag = est.lag_host(f);
+        pitch_finish(sp, lag, est.voiced_host(f), est.c3_host(f), pitch->f0 + f, pitch->ap ? pitch->ap + f : nullptr);
+        if (pitch->lag) pitch->lag[f] = lag;
+        if (cmnd3) std::memcpy(cmnd3 + 3 * f, est.c3_host(f), 3 * sizeof(double));
+        if (voiced) voiced[f] = est.voiced_host(f);
+    }
+    pitch->n_frames = nf;
+    API_END
+}
+
 // ---- the repeated-launch hooks (run_repeated above): operands as in the one-launch hook of the same kernel, two inputs xa / xb, ya / yb = the first result of
 // each; prev (may be null) = what every repetition accumulates onto
 int sbv2_debug_repeat_respair(int device, const float* xa, const float* xb, const float* w1, const float* w2, const float* b1, const float* b2, int64_t C,

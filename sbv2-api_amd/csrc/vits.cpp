@@ -981,10 +981,10 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     SBV2_REQUIRE(gap_after || fl_.n == 1, "stream_begin without gaps needs a preceding forward of ONE utterance");
     SBV2_REQUIRE(!gap_after || fmt, "a stream over several rows is a formatted stream");
     SBV2_REQUIRE(chunk_frames >= 16 && chunk_frames <= (1 << 20), "chunk_frames must be in [16, 2^20]");
-    sfmt_on_ = sflac_on_ = slevel_on_ = smarks_on_ = false;
+    sfmt_on_ = sflac_on_ = slevel_on_ = smarks_on_ = spitch_on_ = false;
     slevel_A_ = 0;
     sdelivered_ = 0;
-    SBV2_REQUIRE(!marks || fmt, "levels on a stream need an output format: begin it with the identity format (44100 Hz f32) instead of none");
+    SBV2_REQUIRE(!marks || fmt, "levels and pitch on a stream need an output format: begin it with the identity format (44100 Hz f32) instead of none");
     SBV2_REQUIRE(!flac || (fmt && fmt->encoding == kEncS16), "a FLAC stream needs encoding = 1 (s16): f32 samples and G.711 codes have no FLAC form");
     SBV2_REQUIRE(!level || fmt, "a level stream needs an output format");
     if (fmt) {
@@ -1002,6 +1002,7 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     stl_ = stream_timeline(frames.data(), gap_after ? gap_after : &no_gap, fl_.n, cfg_.hop(), chunk_frames, fmt ? *fmt : PcmFmtSpec());
     // (the envelope's frame count is refused here, before the stream has set up anything of its own)
     if (marks && fmt) StreamLevels::check(nullptr, 0, marks->env_hop, pcm_format_out_len(*fmt, stl_.joined));
+    if (marks && fmt && marks->pitch) StreamPitch::check(marks->pitch_spec, pcm_format_out_len(*fmt, stl_.joined));   // (and the contour's likewise)
     if (fmt) {
         sfmt_ = *fmt;
         if (!sfmtr_) sfmtr_ = std::make_shared<PcmFormatter>();
@@ -1075,6 +1076,11 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
             if (!smarks_) smarks_ = std::make_shared<StreamLevels>();
             smarks_->begin(seg.data(), (int64_t)seg.size() / 2, marks->env_hop, total_out, stream_);
             smarks_on_ = true;
+        }
+        if (marks && marks->pitch) {   // the contour of the same delivered samples: the format's rate (in the spec) and encoding
+            if (!spitch_) spitch_ = std::make_shared<StreamPitch>();
+            spitch_->begin(marks->pitch_spec, sfmt_.encoding, total_out, stream_);
+            spitch_on_ = true;
         }
         sfmt_on_ = true;
     }
@@ -1152,6 +1158,7 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
             void* dev = sflac_on_ ? static_cast<void*>(sflac_->dst()) : sfmtr_->out_buffer(dev_bytes, stream_);
             pcm_cast(slim_->out_buffer(), em, slim_->unit(), sfmt_.encoding, dev, stream_);
             if (smarks_on_) smarks_->push(dev, sfmt_.encoding, e0, em, stream_);   // (before the encoder's push moves its tail)
+            if (spitch_on_) spitch_->push(dev, e0, em, stream_);                    // (likewise)
             if (sflac_on_) {
                 const int64_t t0 = sflac_->tail();
                 c.flac_push[slot] = sflac_->push(em, last, c.host[slot], stream_);
@@ -1169,6 +1176,7 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
             const int64_t t0 = sflac_->tail();
             sfmtr_->run(sfmt_, pieces, sig, total, sflac_->dst(), (&c == burst_.get() ? 2 : 0) + slot, stream_);
             if (smarks_on_) smarks_->push(sflac_->dst(), sfmt_.encoding, sig.empty() ? smarks_->fed() : sig[0].j0, total, stream_);   // (before the push moves the tail)
+            if (spitch_on_) spitch_->push(sflac_->dst(), sig.empty() ? spitch_->fed() : sig[0].j0, total, stream_);                  // (likewise)
             c.flac_push[slot] = sflac_->push(total, last, c.host[slot], stream_);
             c.flac_fr[slot].assign(1, 0);
             for (size_t w = 0; w < c.fmt_n[slot].size(); ++w) {
@@ -1179,6 +1187,7 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
             void* dev = sfmtr_->out_buffer(dev_bytes, stream_);
             sfmtr_->run(sfmt_, pieces, sig, total, dev, (&c == burst_.get() ? 2 : 0) + slot, stream_);
             if (smarks_on_) smarks_->push(dev, sfmt_.encoding, sig.empty() ? smarks_->fed() : sig[0].j0, total, stream_);
+            if (spitch_on_) spitch_->push(dev, sig.empty() ? spitch_->fed() : sig[0].j0, total, stream_);
             if (total) HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)total * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
         }
         HIP_CHECK(hipEventRecord(c.ev[slot], stream_));
@@ -1284,6 +1293,7 @@ int64_t VitsModel::stream_take(int64_t ci, void* dst, int64_t capacity_bytes, bo
         SBV2_REQUIRE(!slevel_on_ || c1.slot_ci[slot] == ci, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
         SBV2_REQUIRE(!flac_bytes || c1.slot_ci[slot] == ci, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
         SBV2_REQUIRE(!smarks_on_ || c1.slot_ci[slot] == ci, "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk");
+        SBV2_REQUIRE(!spitch_on_ || c1.slot_ci[slot] == ci, "a stream with pitch delivers its chunks in order only: the estimator carries the last samples from chunk to chunk");
         if (c1.slot_ci[slot] != ci) stream_enqueue(c1, ci, slot);                                  // (random access: not the streaming order)
         if (!bursts && ci + 1 < ncalls && c1.slot_ci[slot ^ 1] != ci + 1) stream_enqueue(c1, ci + 1, slot ^ 1);
         HIP_CHECK(hipEventSynchronize(c1.ev[slot]));
@@ -1299,6 +1309,7 @@ int64_t VitsModel::stream_take(int64_t ci, void* dst, int64_t capacity_bytes, bo
     SBV2_REQUIRE(!slevel_on_ || cb.slot_ci[slot] == b0, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
     SBV2_REQUIRE(!flac_bytes || cb.slot_ci[slot] == b0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
     SBV2_REQUIRE(!smarks_on_ || cb.slot_ci[slot] == b0, "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk");
+    SBV2_REQUIRE(!spitch_on_ || cb.slot_ci[slot] == b0, "a stream with pitch delivers its chunks in order only: the estimator carries the last samples from chunk to chunk");
     if (cb.slot_ci[slot] != b0) stream_enqueue(cb, b0, slot);                                    // (random access)
     // the following burst is decoded while this one is delivered (its slot was drained one burst ago)
     const int64_t n0 = b0 + cb.nwin;

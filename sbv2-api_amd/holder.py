@@ -207,11 +207,12 @@ class TTSModelHolder:
         return [self.parse_text(t) if t else None for t in lines]
 
     def easy_synthesize_stream(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, chunk_frames=256,
-                               split=False, levels=False):
+                               split=False, levels=False, pitch=False):
         """The request delivered while it is synthesised (orchestrator.easy_synthesize_stream): a generator over the bytes of the FLAC stream or
         WAV (an orchestrator.SynthesisStream: close() it when it is abandoned before its end).  Errors of the request are raised here, before
         the first piece.  The stream's `.marks` holds the token and word timing of the whole answer from the start; levels=True adds the levels
-        piece by piece (take_marks(): see orchestrator.easy_synthesize_stream).
+        piece by piece (take_marks(): see orchestrator.easy_synthesize_stream), pitch=True (with levels=True and options.pitch_hz) the pitch
+        contour as well.
 
         split=False (the default): the request as ONE utterance.  `text` is a str, parsed as a whole (as split_sentences = False does), or the
         already parsed text as a one-entry list; a second live sentence is refused.
@@ -245,7 +246,7 @@ class TTSModelHolder:
         try:
             st = orchestrator.easy_synthesize_stream(self.bert, m.vits2, sentences, m.style_vectors, style_id, speaker_id, options,
                                                      noise_seed=noise_seed, chunk_frames=chunk_frames, split=split,
-                                                     **({"levels": True} if levels else {}))
+                                                     **({"levels": True} if levels else {}), **({"pitch": True} if pitch else {}))
         except BaseException:
             release()
             raise

@@ -458,6 +458,36 @@ def debug_pitch(x, sample_rate: int, pitch: Pitch, device: int = 0, encoding: st
     return pitch.take(c, arrays), c3[:c.n_frames], voiced[:c.n_frames]
 
 
+def debug_stream_pitch(x, cuts, sample_rate: int, pitch: Pitch, device: int = 0, encoding: str | None = None):
+    """Test hook: the fed pitch estimator on its own (sbv2_debug_stream_pitch).  x as for debug_pitch, cut at the ascending positions `cuts`
+    into len(cuts) + 1 pushes -> debug_pitch's results and per_push [len(cuts) + 1], the frames each push completed."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if encoding is None and x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"pitch is taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"pitch of {encoding!r} samples is not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
+    cuts = np.ascontiguousarray(np.asarray(cuts, np.int64).reshape(-1))
+    c, arrays = pitch.c_struct(x.size)
+    c3, voiced = np.zeros((len(arrays[0]), 3), np.float64), np.zeros(len(arrays[0]), np.int32)
+    per_push = np.zeros(cuts.size + 1, np.int64)
+    check(_lib.lib().sbv2_debug_stream_pitch(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size,
+                                             cuts.ctypes.data_as(i64p) if cuts.size else None, cuts.size, int(sample_rate), C.byref(c), _f64p(c3),
+                                             voiced.ctypes.data_as(C.POINTER(C.c_int32)), per_push.ctypes.data_as(i64p)))
+    return pitch.take(c, arrays), c3[:c.n_frames], voiced[:c.n_frames], per_push
+
+
+def stream_pitch_complete(D: int, hop: int, tau_max: int, total: int) -> int:
+    """The completion rule of a stream's pitch contour (above sbv2_stream_next_pitch): the number of frames f < ceil(total / hop) with
+    min(f hop + hop // 2 + tau_max, total) <= D.  They are the first ones: frames complete in order."""
+    D, hop, tau_max, total = int(D), int(hop), int(tau_max), int(total)
+    nf = -(-total // hop) if total > 0 else 0
+    if D >= total:
+        return nf
+    r = D - tau_max - hop // 2
+    return 0 if r < 0 else min(nf, r // hop + 1)
+
+
 def full_scale(encoding: str) -> float:
     """Full scale of the delivered samples' levels: 32767 for s16 and for G.711 (levels of the decoded integers), 1 for f32."""
     return 1.0 if encoding == "f32" else 32767.0
@@ -833,14 +863,18 @@ class StreamHandle:
     the end.
     levels=True / env_hop > 0 (delivered samples per envelope frame): the levels of the delivered samples per token / per frame are reduced on
     the device chunk by chunk (sbv2_stream_begin_request_levels); next_marks() hands out what the pieces taken so far completed.  A single
-    utterance then runs as the request stream with gaps=[0] (the same code, the same bytes; fmt None = 44.1 kHz f32)."""
+    utterance then runs as the request stream with gaps=[0] (the same code, the same bytes; fmt None = 44.1 kHz f32).
+    pitch (a Pitch: hop, range, threshold at the stream's delivered rate; with or without levels): the pitch contour of the delivered samples is
+    estimated on the device chunk by chunk as well (sbv2_stream_begin_request_pitch): n_pitch frames in all, next_pitch() hands out the ones the
+    pieces taken so far completed, with the bits of debug_pitch over the whole delivered signal."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
-                 level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, **kw):
+                 level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, **kw):
         l = _lib.lib()
         self.request = isinstance(utt, (list, tuple))
         self.levels, self.env_hop, self.n_tokens, self.n_env, self._marks_buf = bool(levels), int(env_hop), 0, 0, None
-        if (self.levels or self.env_hop) and not self.request:
+        self.pitch, self.n_pitch, self._pitch_buf = pitch, 0, None
+        if (self.levels or self.env_hop or pitch is not None) and not self.request:
             if gaps is not None:
                 raise Sbv2Error("gaps= belongs to a stream over a list of utterances")
             utt, gaps, self.request = [utt], [0], True
@@ -862,7 +896,13 @@ class StreamHandle:
             rq = _lib.Sbv2StreamRequest(gp, C.pointer(fmt.c) if fmt is not None else None, C.pointer(level.c) if level is not None else None,
                                         int(self.flac), 0)
             opts = C.byref(self.b.opts) if self.b.opts is not None else None
-            if self.levels or self.env_hop:
+            if pitch is not None:
+                lv, nt, ne, nq = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)), C.c_int64(), C.c_int64(), C.c_int64()
+                sp = _lib.Sbv2StreamPitch(pitch.hop if -2 ** 31 <= pitch.hop < 2 ** 31 else 0, 0, pitch.f0_min, pitch.f0_max, pitch.threshold)
+                check(l.sbv2_stream_begin_request_pitch(args[0], args[1], args[2], opts, *args[3:], C.byref(rq), C.byref(lv), C.byref(sp),
+                                                        C.byref(self.h), C.byref(tot), C.byref(nt), C.byref(ne), C.byref(nq)))
+                self.n_tokens, self.n_env, self.n_pitch = nt.value, ne.value, nq.value
+            elif self.levels or self.env_hop:
                 lv, nt, ne = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)), C.c_int64(), C.c_int64()
                 check(l.sbv2_stream_begin_request_levels(args[0], args[1], args[2], opts, *args[3:], C.byref(rq), C.byref(lv), C.byref(self.h),
                                                          C.byref(tot), C.byref(nt), C.byref(ne)))
@@ -935,6 +975,18 @@ class StreamHandle:
         check(_lib.lib().sbv2_stream_next_marks(self.h, C.byref(part)))
         return (int(part.tok_first), ts[:part.n_tok].copy(), tp[:part.n_tok].copy(), int(part.env_first), es[:part.n_env].copy(),
                 ep[:part.n_env].copy(), int(part.delivered))
+
+    def next_pitch(self):
+        """(first, f0, ap, lag, delivered): the frames of the pitch contour that the pieces taken since the previous call completed
+        (sbv2_stream_next_pitch; host only; the rule: stream_pitch_complete).  Frames [first, first + len(f0)); f0 in Hz, 0 for an unvoiced
+        frame.  Refused on a stream begun without pitch=."""
+        if self._pitch_buf is None:   # (sized for the whole stream once)
+            n = max(self.n_pitch, 1)
+            self._pitch_buf = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.int32)
+        f0, ap, lag = self._pitch_buf
+        part = _lib.Sbv2StreamPitchPart(self.n_pitch, _f64p(f0), _f64p(ap), lag.ctypes.data_as(C.POINTER(C.c_int32)), 0, 0, 0)
+        check(_lib.lib().sbv2_stream_next_pitch(self.h, C.byref(part)))
+        return int(part.first), f0[:part.n].copy(), ap[:part.n].copy(), lag[:part.n].copy(), int(part.delivered)
 
     def marks(self):
         """(start, end): the spans of the utterance's tokens in delivered samples of this stream (sbv2_stream_marks; host only, complete from

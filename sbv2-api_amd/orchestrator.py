@@ -262,13 +262,20 @@ def marks_dict(utts, live, fmt, m, pitch=None) -> dict:
     if pitch is not None:
         f0 = np.asarray(pitch.f0, np.float64)
         d["pitch"] = {"hop": int(pitch.hop), "f0_hz": [float(v) if v > 0 else None for v in f0], "aperiodicity": [float(v) for v in pitch.ap]}
-        centre = np.arange(f0.size, dtype=np.int64) * pitch.hop + pitch.hop // 2
-        for t in d["tokens"]:
-            k0, k1 = np.searchsorted(centre, [t["start"], t["end"]])   # the frames with start <= centre < end
-            v = f0[k0:k1][f0[k0:k1] > 0]
-            t["f0_hz"] = float(v.mean()) if v.size else None
-            t["voiced"] = float(v.size) / (k1 - k0) if k1 > k0 else 0.0
+        token_pitch(d["tokens"], f0, pitch.hop)
     return d
+
+
+def token_pitch(tokens, f0, hop: int):
+    """Per token of a marks dict, from the contour f0 [n] (0 = unvoiced) of frames with their centres at f hop + hop // 2: f0_hz and voiced as
+    marks_dict states them."""
+    f0 = np.asarray(f0, np.float64)
+    centre = np.arange(f0.size, dtype=np.int64) * hop + hop // 2
+    for t in tokens:
+        k0, k1 = np.searchsorted(centre, [t["start"], t["end"]])   # the frames with start <= centre < end
+        v = f0[k0:k1][f0[k0:k1] > 0]
+        t["f0_hz"] = float(v.mean()) if v.size else None
+        t["voiced"] = float(v.size) / (k1 - k0) if k1 > k0 else 0.0
 
 
 def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPlan, loudness_stats=None, pcm=None, marks=None) -> bytes:
@@ -359,7 +366,7 @@ class SynthesisStream:
     the pieces run out, when one fails, by close(), and when the object is dropped, iterated or not: the replays of a stream are already
     enqueued when this object is returned, so its end cannot hang on a generator's `finally`, which never runs for a generator nobody started."""
 
-    def __init__(self, st, head, to_bytes, marks=None, tail=None, levels=None):
+    def __init__(self, st, head, to_bytes, marks=None, tail=None, levels=None, pitch=None):
         self._st, self._head, self._to_bytes, self._tail = st, head, to_bytes, tail   # tail: bytes that follow the last chunk (a pad byte)
         self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece
         self.level_stats = None   # a level stream's (deepest reduction in dB, max |x|), once its last piece has been handed out
@@ -370,6 +377,11 @@ class SynthesisStream:
         self._new_tokens, self._new_env, self._env_first = [], ([], []), 0
         if levels is not None and levels[1] > 0:
             self.marks["envelope"] = {"hop": int(levels[1]), "level_dbfs": [], "peak": []}
+        # pitch (a model.Pitch, with levels): the stream was begun with a contour; take_marks() hands out the frames the pieces so far completed
+        # too, and once the last piece is out `.marks` has the "pitch" block and the tokens' f0_hz / voiced of marks_dict
+        self._pitch, self._f0, self._new_pitch, self._pitch_first = pitch, [], ([], []), 0
+        if pitch is not None:
+            self.marks["pitch"] = {"hop": int(pitch.hop), "f0_hz": [], "aperiodicity": []}
 
     def _collect(self):
         """The levels the handle has completed since the last look -> `.marks` and the lists take_marks() hands out next."""
@@ -387,11 +399,20 @@ class SynthesisStream:
             for lst, v in ((self.marks["envelope"]["level_dbfs"], db), (self.marks["envelope"]["peak"], float(p) / full),
                            (self._new_env[0], db), (self._new_env[1], float(p) / full)):
                 lst.append(v)
+        if self._pitch is not None:
+            _, f0, ap, _, _ = self._st.next_pitch()
+            self._f0.extend(float(v) for v in f0)
+            for lst, vals in ((self.marks["pitch"]["f0_hz"], f0), (self._new_pitch[0], f0)):
+                lst.extend(float(v) if v > 0 else None for v in vals)
+            for lst in (self.marks["pitch"]["aperiodicity"], self._new_pitch[1]):
+                lst.extend(float(v) for v in ap)
 
     def take_marks(self) -> dict:
         """JSON-ready: the levels that the pieces handed out so far have completed and that no earlier call returned.  {"delivered": samples out
         so far, "tokens": [{"token": its index in .marks["tokens"], "level_dbfs", "peak"}, ...], "envelope": {"first", "hop", "level_dbfs" [n],
-        "peak" [n]} (with an envelope)}.  A token is complete once its last sample has been delivered, a frame likewise."""
+        "peak" [n]} (with an envelope), "pitch": {"first", "hop", "f0_hz" [n] (None = unvoiced), "aperiodicity" [n]} (with pitch)}.  A token is
+        complete once its last sample has been delivered, an envelope frame likewise, a pitch frame once its window has been
+        (model.stream_pitch_complete)."""
         if self._levels is None:
             raise model.Sbv2Error("this stream was begun without levels (easy_synthesize_stream(levels=True))")
         self._collect()
@@ -399,7 +420,10 @@ class SynthesisStream:
         if self._levels[1] > 0:
             d["envelope"] = {"first": self._env_first, "hop": int(self._levels[1]), "level_dbfs": self._new_env[0], "peak": self._new_env[1]}
             self._env_first += len(self._new_env[0])
-        self._new_tokens, self._new_env = [], ([], [])
+        if self._pitch is not None:
+            d["pitch"] = {"first": self._pitch_first, "hop": int(self._pitch.hop), "f0_hz": self._new_pitch[0], "aperiodicity": self._new_pitch[1]}
+            self._pitch_first += len(self._new_pitch[0])
+        self._new_tokens, self._new_env, self._new_pitch = [], ([], []), ([], [])
         return d
 
     def __iter__(self):
@@ -414,6 +438,8 @@ class SynthesisStream:
                 c = self._st.next()
                 if c is None:
                     self._collect()     # (everything is complete now: what take_marks() has not seen yet waits for its next call)
+                    if self._pitch is not None:
+                        token_pitch(self.marks["tokens"], self._f0, self._pitch.hop)
                     if getattr(self._st, "level", None) is not None:
                         self.level_stats = self._st.level_stats()
                     st, self._st = self._st, None
@@ -450,7 +476,7 @@ class SynthesisStream:
 
 
 def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
-                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False, levels=False):
+                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False, levels=False, pitch=False):
     """easy_synthesize delivered while it is synthesised: an iterator (SynthesisStream; close() it when it is abandoned early) over the pieces
     of the request's container.  The forward (DeBERTa / text / flow) runs once over the whole request, then the decoder runs chunk by chunk
     (model.StreamHandle).
@@ -477,9 +503,18 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     levels=True: the levels of the delivered samples per token, and with options.envelope_hz per envelope frame, are reduced on the device
     chunk by chunk (model.StreamHandle(levels=True, env_hop=...)): the iterator's take_marks() returns what the pieces so far completed, and
     once the last piece is out `.marks` has marks_dict's shape.  The audio bytes are those of the same call without levels (the default,
-    which ignores envelope_hz).  On a level stream (gain_db) the levels are those of the samples the limiter emits."""
+    which ignores envelope_hz).  On a level stream (gain_db) the levels are those of the samples the limiter emits.
+    pitch=True (needs levels=True and options.pitch_hz; hop and range as pitch_options reads them): the pitch contour of the delivered samples
+    is estimated on the device chunk by chunk as well (model.StreamHandle(pitch=...)): take_marks() pieces gain a "pitch" block, and once the
+    last piece is out `.marks` has marks_dict's "pitch" block and the tokens' f0_hz / voiced.  Without pitch=True, pitch_hz is refused."""
     options = options or SynthesizeOptions()
-    refuse_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")   # (a contour on a stream needs a carried window: DESIGN.md)
+    if pitch:
+        if not levels:
+            raise model.Sbv2Error("pitch=True on a stream comes with its speech marks: pass levels=True as well")
+        if getattr(options, "pitch_hz", None) is None:
+            raise model.Sbv2Error("pitch=True needs options.pitch_hz (frames per second of the contour)")
+    else:
+        refuse_pitch(options, "a stream without pitch=True (/synthesize_stream)")
     if options.normalize:
         raise model.Sbv2Error("a stream cannot normalise: the peak needs the whole signal (use /synthesize)")
     if options.loudness is not None or options.limiter:
@@ -501,6 +536,9 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
               length_scale=options.length_scale, noise_scale=noise_scale, noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     if levels:
         kw.update(levels=True, env_hop=envelope_hop(options, fmt.sample_rate))   # (a bad envelope_hz is refused before any GPU work)
+    contour = pitch_options(options, fmt.sample_rate) if pitch else None   # (a bad pitch_hz or range likewise)
+    if contour is not None:
+        kw.update(pitch=contour)
     if split:
         lines = [i for i, s in enumerate(sentences) if s]
         gaps = [SENTENCE_GAP if i != len(sentences) - 1 else 0 for i in lines]
@@ -515,8 +553,8 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
         raise
     lv = (fmt, kw["env_hop"], st.total_samples) if levels else None
     if flac:
-        return SynthesisStream(st, None, lambda c: c, marks, levels=lv)
+        return SynthesisStream(st, None, lambda c: c, marks, levels=lv, pitch=contour)
     dtype = {"s16": "<i2", "f32": "<f4"}.get(fmt.encoding, "u1")
     pad = b"\0" if fmt.encoding in G711_TAGS and st.total_samples & 1 else None
     return SynthesisStream(st, wav_stream_header(fmt.sample_rate, fmt.encoding, st.total_samples),
-                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad, levels=lv)
+                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad, levels=lv, pitch=contour)

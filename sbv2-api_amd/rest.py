@@ -28,13 +28,16 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     "envelope": {"first", "hop", "level_dbfs", "peak"} (with envelope_hz)}: the levels of the tokens and envelope frames whose
                     last sample that piece delivered, reduced on the device chunk by chunk.  The pieces' audio concatenates to /synthesize_stream's
                     body; the last line's delivered equals total_samples.  Same lock and closing discipline as /synthesize_stream.
+                    pitch_hz = null (new; range as for /synthesize_marks): the first line gains "pitch": {"hop", "n_frames"} and every later
+                    line "pitch": {"first", "hop", "f0_hz", "aperiodicity"}, the frames of the contour whose window that piece completed
+                    (about 1 / pitch_min_hz seconds behind the audio), estimated on the device chunk by chunk with the one-shot contour's bits.
   POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
                     samples per frame.  With batching the request shares runs like /synthesize.
                     pitch_hz = null (new; with pitch_min_hz = 70, pitch_max_hz = 600): the marks also carry "pitch" {"hop", "f0_hz" (null for an
                     unvoiced frame), "aperiodicity"}, pitch_hz frames per second estimated on the device from the delivered samples, and every
-                    token "f0_hz" and "voiced".  The field is refused on every other route.
+                    token "f0_hz" and "voiced".  /synthesize_stream_marks carries the field too; every other route refuses it.
   any error         500 text/plain "Something went wrong: <message>"            sbv2_api/src/error.rs:10-18
   one request at a time (Arc<Mutex<TTSModelHolder>>, main.rs:86,104)             -> a lock around the holder
   make_app(holder, batching={...})  new, off by default: concurrent /synthesize requests share pipeline runs (batcher.py)
@@ -100,6 +103,9 @@ class _MarksLines:
         self._pieces, self.close = pieces, pieces.close
         self._first = {"media_type": media_type, "sample_rate": sample_rate, "total_samples": total_samples,
                        "marks": {k: pieces.marks[k] for k in ("sample_rate", "tokens", "words")}}
+        if "pitch" in pieces.marks:   # (a stream begun with pitch: what the contour will hold, before its first frame)
+            hop = int(pieces.marks["pitch"]["hop"])
+            self._first["pitch"] = {"hop": hop, "n_frames": -(-int(total_samples) // hop)}
 
     def __iter__(self):
         return self
@@ -140,7 +146,7 @@ def make_app(holder, batching=None):
         limiter: bool = False               # look-ahead true-peak limiter for targets the plain gain misses; needs loudness
         max_reduction: float = 6.0          # the limiter's deepest gain reduction (dB)
         gain_db: Optional[float] = None     # /synthesize_stream only: fixed gain (dB) under the true_peak_max ceiling; refused elsewhere
-        pitch_hz: Optional[int] = None      # /synthesize_marks only: frames per second of the pitch contour in the marks; refused elsewhere
+        pitch_hz: Optional[int] = None      # /synthesize_marks, /synthesize_stream_marks: frames per second of the pitch contour in the marks; refused elsewhere
         pitch_min_hz: float = 70.0          # the contour's search range (Hz)
         pitch_max_hz: float = 600.0
 
@@ -255,8 +261,10 @@ def make_app(holder, batching=None):
     def synthesize_stream_marks(req: SynthesizeStreamMarksRequest):
         lock.acquire()                        # as /synthesize_stream: given back by _HeldPieces.close when the response is over
         try:
+            # (pitch is sent like split: named only when the request asks for it, so a request without pitch_hz is the call it always was)
             pieces = holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), levels=True,
-                                                   **({"split": True} if req.split_sentences else {}))
+                                                   **({"split": True} if req.split_sentences else {}),
+                                                   **({"pitch": True} if req.pitch_hz is not None else {}))
             try:
                 lines = _MarksLines(pieces, "audio/flac" if req.encoding == "flac" else "audio/wav", pieces.marks["sample_rate"],
                                     pieces.total_samples)
