@@ -190,6 +190,17 @@ int sbv2_g711_decode(int32_t encoding, const uint8_t* codes, int64_t n, int16_t*
  * times gains[i], delivered in `encoding` (0, 1, 7, 6) -> dst (host; sum of lens samples, back to back as well: a G.711 signal starts at any
  * byte offset).  The device output lies between guard bands; a byte written outside it fails the call. */
 int sbv2_debug_pcm_cast(int device, const double* x, const int64_t* lens, int nsig, const double* gains, int32_t encoding, void* dst);
+/* Test hook: the formatting launches themselves (resampler, and peak normalisation when fmt asks for it) on a host table of pieces and signals.
+ * x = nx native samples.  pieces [npieces][3] = offset into x, t0, len: x[offset, offset + len) lies at [t0, t0 + len) of a silent timeline.
+ * sigs [nsig][4] = j0, j1, p0, p1: the output samples [j0, j1) of the timeline whose pieces are [p0, p1) (sorted by t0, disjoint; pieces of
+ * different signals may overlap), delivered back to back in signal order -> dst (host; sum of j1 - j0 samples in fmt's encoding).
+ * expose_y != 0: the run ends before the gain stage and dst receives the resampler's f64 samples (fmt->normalize must be 0).  peaks (may be
+ * NULL): when fmt normalises, max |y| of each signal, the value whose reciprocal is the gain.  Refused with a message before any device call,
+ * nothing written: a bad fmt, ranges that are no ranges (j1 < j0, p1 < p0, outside the table or x), unsorted or overlapping pieces of a
+ * signal.  On the device every piece is a copy of its own between NaN words and the output lies between guard bands; a byte written outside
+ * it fails the call. */
+int sbv2_debug_pcm_format(int device, const float* x, int64_t nx, const int64_t* pieces, int npieces, const int64_t* sigs, int nsig,
+                          const sbv2_pcm_format* fmt, int expose_y, void* dst, double* peaks);
 /* Host-only test hook: the prototype h of a rate (*len = 2 half + 1 taps at 44100 L Hz) and L, M.  h may be NULL (query); else cap >= *len. */
 int sbv2_pcm_format_taps(int32_t sample_rate, float* h, int64_t cap, int64_t* len, int32_t* L, int32_t* M);
 /* Formats run `ticket` on its context's stream (waits for it) and copies the result into HOST memory dst (capacity_bytes; a longer result is refused

@@ -150,6 +150,8 @@ SYMBOLS = {
     "sbv2_g711_encode": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "sbv2_g711_decode": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "sbv2_debug_pcm_cast": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.POINTER(C.c_double), C.c_int32, C.c_void_p]),
+    "sbv2_debug_pcm_format": (C.c_int, [C.c_int, f32p, C.c_int64, i64p, C.c_int, i64p, C.c_int, C.POINTER(Sbv2PcmFormat), C.c_int, C.c_void_p,
+                                        C.POINTER(C.c_double)]),
     "sbv2_pcm_format_taps": (C.c_int, [C.c_int32, f32p, C.c_int64, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sbv2_pipeline_fetch_pcm_format": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, C.c_int64, C.c_void_p, C.c_int64, i64p]),
     "sbv2_flac_bound": (C.c_int64, [C.POINTER(Sbv2PcmFormat), C.c_int64]),

@@ -112,6 +112,9 @@ class PcmFormatter {
     // and its x as it is; the stage runs also when every signal is empty, so that its stats are written.  kExposeY: y to gain.y_out, dst_dev unused.
     void run(const PcmFmtSpec& spec, const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, void* dst_dev,
              int slot, hipStream_t s, const GainStage& gain = GainStage());
+    // max |y| of each signal of the last peak-normalised run that had samples (device, valid once that run's launches have completed; the
+    // test hook's view of the gain k_pcm_gain applies)
+    const double* peaks_device() const { return peak_.as<double>(); }
 
   private:
     struct Slot {

@@ -1800,6 +1800,78 @@ int sbv2_debug_pcm_cast(int device, const double* x, const int64_t* lens, int ns
     API_END
 }
 
+// The formatting launches of the output chain (PcmFormatter::run, pcm_format.hip: k_pcm_resample and, when fmt normalises, k_pcm_gain) on a host
+// table of pieces and signals.  x = nx native samples; piece q = x[pieces[3q], + pieces[3q + 2]) lying at position pieces[3q + 1] of its signal's
+// timeline; signal i = outputs [sigs[4i], sigs[4i + 1]) of the timeline whose pieces are [sigs[4i + 2], sigs[4i + 3]), written back to back in
+// signal order (out_off = the running sum of j1 - j0, as format_layout and the streaming replay lay them).  expose_y: the run ends at the gain
+// stage's input and dst receives f64.  The tables are checked before any device call.  On the device every piece is a copy of its own between
+// NaN words (a read outside a piece poisons the output) and the output lies between two guard bands; a byte written there fails the call.
+// peaks (may be NULL): max |y| of each signal when fmt normalises.
+int sbv2_debug_pcm_format(int device, const float* x, int64_t nx, const int64_t* pieces, int npieces, const int64_t* sigs, int nsig,
+                          const sbv2_pcm_format* fmt, int expose_y, void* dst, double* peaks) {
+    API_BEGIN
+    const PcmFmtSpec spec = pcm_format_spec(fmt);
+    SBV2_REQUIRE(nx >= 0 && npieces >= 0 && nsig >= 1 && sigs && (x || nx == 0) && (pieces || npieces == 0), "bad arguments");
+    SBV2_REQUIRE(expose_y == 0 || expose_y == 1, "expose_y must be 0 or 1");
+    SBV2_REQUIRE(!(expose_y && spec.normalize), "expose_y with a peak-normalised format");
+    constexpr int64_t kMaxPos = (int64_t)1 << 44, kMaxTotal = (int64_t)1 << 26;   // j M + half and t0 + len stay far inside int64
+    constexpr size_t kPad = 64, kGuard = 64;
+    constexpr unsigned char kFill = 0xA5;
+    std::vector<size_t> at((size_t)npieces);   // piece q's first word in the poisoned source
+    size_t words = kPad;
+    for (int q = 0; q < npieces; ++q) {
+        const int64_t off = pieces[3 * q], t0 = pieces[3 * q + 1], len = pieces[3 * q + 2];
+        SBV2_REQUIRE(len >= 0 && off >= 0 && off <= nx && len <= nx - off, "piece " + std::to_string(q) + " lies outside the " + std::to_string(nx) + " samples");
+        SBV2_REQUIRE(t0 >= 0 && t0 <= kMaxPos, "piece " + std::to_string(q) + " starts at a position outside [0, 2^44]");
+        at[q] = words;
+        words += (size_t)len + kPad;
+    }
+    std::vector<FmtSignal> sig((size_t)nsig);
+    int64_t total = 0;
+    for (int i = 0; i < nsig; ++i) {
+        const int64_t j0 = sigs[4 * i], j1 = sigs[4 * i + 1], p0 = sigs[4 * i + 2], p1 = sigs[4 * i + 3];
+        SBV2_REQUIRE(0 <= j0 && j0 <= j1 && j1 <= kMaxPos, "signal " + std::to_string(i) + ": outputs [" + std::to_string(j0) + ", " + std::to_string(j1) +
+                                                               ") are no range within [0, 2^44]");
+        SBV2_REQUIRE(0 <= p0 && p0 <= p1 && p1 <= npieces, "signal " + std::to_string(i) + ": pieces [" + std::to_string(p0) + ", " + std::to_string(p1) +
+                                                               ") are no range of the table's " + std::to_string(npieces));
+        for (int64_t q = p0; q + 1 < p1; ++q) {
+            SBV2_REQUIRE(pieces[3 * q + 1] <= pieces[3 * q + 4], "signal " + std::to_string(i) + ": its pieces are not sorted by position");
+            SBV2_REQUIRE(pieces[3 * q + 1] + pieces[3 * q + 2] <= pieces[3 * q + 4], "signal " + std::to_string(i) + ": pieces " + std::to_string(q) + " and " +
+                                                                                        std::to_string(q + 1) + " overlap");
+        }
+        sig[i] = FmtSignal{j0, j1, total, (int32_t)p0, (int32_t)p1};
+        total += j1 - j0;
+        SBV2_REQUIRE(total <= kMaxTotal, "more than 2^26 output samples");
+    }
+    SBV2_REQUIRE(total == 0 || dst, "bad arguments");
+    std::vector<uint32_t> src(words, kNanWord);
+    for (int q = 0; q < npieces; ++q)
+        if (pieces[3 * q + 2]) std::memcpy(&src[at[q]], x + pieces[3 * q], sizeof(float) * (size_t)pieces[3 * q + 2]);
+    AudioScratch r(device, src.data(), sizeof(uint32_t) * words);
+    std::vector<FmtPiece> pc((size_t)npieces);
+    for (int q = 0; q < npieces; ++q) pc[q] = FmtPiece{r.x.as<float>() + at[q], pieces[3 * q + 1], pieces[3 * q + 2]};
+    const size_t nb = (size_t)total * (expose_y ? sizeof(double) : (size_t)spec.bytes());
+    DevMem dout(nb + 2 * kGuard);
+    HIP_CHECK(hipMemsetAsync(dout.p, kFill, nb + 2 * kGuard, r.s));
+    PcmFormatter f;
+    if (expose_y) f.run(spec, pc, sig, total, nullptr, 0, r.s, GainStage(reinterpret_cast<double*>(dout.u8() + kGuard)));
+    else f.run(spec, pc, sig, total, dout.u8() + kGuard, 0, r.s);
+    std::vector<unsigned char> h(nb + 2 * kGuard);
+    HIP_CHECK(hipMemcpyAsync(h.data(), dout.p, h.size(), hipMemcpyDeviceToHost, r.s));
+    std::vector<double> pk;
+    if (peaks && spec.normalize && total) {
+        pk.resize((size_t)nsig);
+        HIP_CHECK(hipMemcpyAsync(pk.data(), f.peaks_device(), sizeof(double) * (size_t)nsig, hipMemcpyDeviceToHost, r.s));
+    }
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    for (size_t i = 0; i < kGuard; ++i)
+        SBV2_REQUIRE(h[i] == kFill && h[kGuard + nb + i] == kFill, "the formatter wrote outside its " + std::to_string(nb) + " bytes");
+    if (nb) std::memcpy(dst, h.data() + kGuard, nb);
+    if (peaks && spec.normalize)
+        for (int i = 0; i < nsig; ++i) peaks[i] = pk.empty() ? 0.0 : pk[i];
+    API_END
+}
+
 // The level reduction of the speech marks (marks.hip) on host samples: x = n samples (encoding 0 = f32, 1 = s16, 7 / 6 = G.711 codes), segments
 // [starts[i], ends[i]).
 int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n, const int64_t* starts, const int64_t* ends, int64_t nseg, double* sumsq,

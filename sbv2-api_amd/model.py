@@ -195,6 +195,30 @@ def debug_pcm_cast(signals, gains, encoding: str, device: int = 0, guard: int = 
     return np.split(out, np.cumsum(lens)[:-1])
 
 
+def debug_pcm_format(x, pieces, sigs, fmt: PcmFormat, expose_y: bool = False, peaks: bool = False, device: int = 0, guard: int = 64):
+    """Test hook: the formatting launches (resampler, peak normalisation) on a table of pieces and signals.  x = native float32 samples;
+    pieces = rows (offset into x, t0, len); sigs = rows (j0, j1, p0, p1): outputs [j0, j1) of the timeline that holds pieces [p0, p1).
+    Returns one array per signal in fmt's encoding, or float64 with expose_y (the resampler's sum before the gain stage); with peaks also
+    max |y| of every signal (fmt must normalise).  The host destination lies between two `guard`-byte bands of 0xA5, checked here."""
+    x = np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1))
+    pc = np.ascontiguousarray(np.asarray(pieces, np.int64).reshape(-1, 3))
+    sg = np.ascontiguousarray(np.asarray(sigs, np.int64).reshape(-1, 4))
+    dt = np.dtype(np.float64 if expose_y else fmt.dtype)
+    lens = sg[:, 1] - sg[:, 0]
+    n_out = int(np.clip(lens, 0, None).sum())
+    nb = n_out * dt.itemsize if n_out <= 1 << 26 else 0   # (a table with j1 < j0 or more samples than that is refused by the hook)
+    buf = np.full(nb + 2 * guard, 0xA5, np.uint8)
+    pk = np.full(len(sg), np.nan) if peaks else None
+    rc = _lib.lib().sbv2_debug_pcm_format(int(device), x.ctypes.data_as(f32p) if x.size else None, x.size, pc.ctypes.data_as(i64p) if pc.size else None,
+                                          len(pc), sg.ctypes.data_as(i64p), len(sg), C.byref(fmt.c), int(bool(expose_y)),
+                                          buf[guard:].ctypes.data_as(C.c_void_p), _f64p(pk) if peaks else None)
+    if not (np.all(buf[:guard] == 0xA5) and np.all(buf[guard + nb:] == 0xA5)) or (rc != 0 and not np.all(buf == 0xA5)):
+        raise Sbv2Error("sbv2_debug_pcm_format wrote outside its destination, or wrote although it failed")
+    check(rc)
+    out = np.split(buf[guard:guard + nb].copy().view(dt), np.cumsum(lens)[:-1])
+    return (out, pk) if peaks else out
+
+
 def pcm_format_taps(sample_rate: int):
     """(h, L, M): the library's resampling prototype for a rate (host only; test hook)."""
     l = _lib.lib()
