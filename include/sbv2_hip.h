@@ -417,6 +417,64 @@ int sbv2_pitch_lags(int32_t sample_rate, double f0_min, double f0_max, int32_t* 
  * in the fetch; cmnd3 [n_frames][3] (c-, c0, c+) and voiced [n_frames] may be NULL. */
 int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, double* cmnd3, int32_t* voiced);
 
+/* ---- new: pitch and intonation scale.  Raise or lower a voice (pitch_scale) and flatten or exaggerate its melody (intonation_scale).  The model
+ * gives no handle on f0, so both are a transform of the synthesized signal: a length-preserving pitch-synchronous overlap-add (TD-PSOLA) of the
+ * run's native f32 rows, on the device, BEFORE the formatter.  Every row keeps its length, so placement, delivered lengths, token spans and every
+ * later stage (resampler, gain stage, quantiser, FLAC, the marks' levels and their own pitch contour) work unchanged on the shifted voice.
+ * Input.  One row x[0 .. n) of f32 at rate sr (the model's rate in the pipeline; the hook takes 1000 <= sr <= 48000); reads outside [0, n) are 0.
+ * Parameters (anything else is refused): pitch_scale p in [0.5, 2]; intonation_scale s in [0, 2]; hop H in [sr / 1000, sr / 50] (integer
+ *   divisions), 0 = sr / 200; f0_min, f0_max, threshold under the rules of sbv2_pitch, 0 = 70, 600, 0.15.
+ * Contour.  YIN exactly as sbv2_pitch states it on x (encoding f32) with hop H, and the parabolic refinement on the device, the same f64
+ *   expression as there, never contracted: delta = 0.5 (c- - c+) / den if den > 0 and both neighbours exist, else 0, here limited to [-1, 1] (a
+ *   parabola whose vertex lies farther off has not been fitted to a minimum; the limit is what bounds the windows below).  Per frame
+ *   T_f = lag + delta (f64) and voiced_f; frame f owns the samples [f H, min((f + 1) H, n)).
+ * Target.  f0_f = sr / T_f for voiced frames; their mean m = double(sum llrint(f0_f 65536)) / (65536.0 count), an integer sum, so any order of
+ *   reduction gives the same bits; g_f = p (m + s (f0_f - m)) clamped to [f0_min / 2, 2 f0_max]; T'_f = sr / g_f.
+ * Phase increments (Q32, int64).  inc_a(f) = llrint(4294967296.0 / T_f) and inc_s(f) = llrint(4294967296.0 / T'_f) for voiced frames; both are
+ *   inc_u = llrint(4294967296.0 / (sr / 200)) (integer division) for unvoiced frames.
+ * Analysis marks.  phi_a(k) = sum_{i <= k} inc_a(frame(i)), phi_a(-1) = 0; sample k is an analysis mark iff phi_a(k) >> 32 != phi_a(k - 1) >> 32.
+ * Synthesis marks.  In an unvoiced frame k is a synthesis mark iff it is an analysis mark.  A voiced run starts at the first sample k0 of a
+ *   voiced frame whose predecessor is unvoiced or absent; there phi_s(k0 - 1) = phi_a(k0 - 1); inside the run phi_s(k) = phi_s(k - 1) +
+ *   inc_s(frame(k)) and k is a mark iff the integer part changes.  (The increment is constant within a frame: the marks of a frame follow from a
+ *   prefix sum over FRAMES and a division, nothing walks the samples.)
+ * Mapping.  With the ascending lists ta[0 .. Na) and ts[0 .. Ns): synthesis mark j uses the analysis mark m(j) nearest to ts_j, a tie going to
+ *   the earlier one.
+ * Window of analysis mark m.  L = ta_m - ta_{m-1} (ta_0 + 1 for m = 0), R = ta_{m+1} - ta_m (n - ta_m for the last).  For integer offsets
+ *   -L < u < R: v = double(|u|) / double(u < 0 ? L : R), S = (v v) (3.0 - 2.0 v), w(u) = 1.0 - S, except w = 1 on the left side of mark 0 and on
+ *   the right side of the last mark.  Adjacent windows are complementary: the analysis grains partition the row.
+ * Output.  In ascending j, in f64, never contracted: num(k) = sum_j w_{m(j)}(k - ts_j) double(x[ta_{m(j)} + k - ts_j]),
+ *   den(k) = sum_j w_{m(j)}(k - ts_j); y[k] = float(num / max(den, 1.0)).  A row with no analysis mark is copied.
+ * Hence: the length is unchanged; |y[k]| <= max |x| (where den >= 1 y is a convex combination of input samples, elsewhere a sub-unit one), so
+ *   the stage cannot create clipping; with p = 1 and s = 1 the two mark lists coincide and y == x bit for bit, and the same holds in any stretch
+ *   of unvoiced frames farther than tau_max + H + 2 samples from a voiced one; no half-width exceeds max(tau_max + 1, sr / 200) + 2, which bounds
+ *   the gather.  Dividing by den trades level for the peak bound; the loudness stage downstream restores level.
+ * Not built: epoch (glottal) alignment of the marks, contour smoothing and octave-error repair, formant shifting, energy compensation.  No
+ *   stream entry point either: sbv2_stream_* and sbv2_node_* do not take a sbv2_voice. */
+typedef struct sbv2_voice {
+    double pitch_scale;          /* [0.5, 2] */
+    double intonation_scale;     /* [0, 2] */
+    double f0_min, f0_max;       /* Hz; 0 = 70, 600 */
+    double threshold;            /* (0, 1); 0 = 0.15 */
+    int32_t hop; int32_t reserved;   /* native samples per contour frame, 0 = rate / 200; reserved must be 0 */
+} sbv2_voice;
+/* sbv2_pipeline_fetch_request_pitch of the listed rows SHIFTED.  voice == NULL, or pitch_scale == 1 and intonation_scale == 1, is exactly that
+ * call: no launch, the same bytes.  Otherwise the listed rows are shifted into a scratch buffer laid out like the run's packed PCM and the
+ * formatter reads them there; everything else (gain stage, sink, stats, marks, pitch: all of the delivered, shifted signal) is that call.  The
+ * run's PCM is only read: a ticket can be fetched any number of times, with and without voice, and two equal fetches give identical bytes.
+ * Refused with nothing written: a non-zero reserved, parameters outside the ranges above, and everything that call refuses. */
+int sbv2_pipeline_fetch_request_voice(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice, void* dst,
+                                      int64_t capacity_bytes, int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch);
+/* Output samples per workgroup of the overlap-add gather (tests place row lengths around it). */
+int32_t sbv2_voice_tile(void);
+/* Test hook: the shifter on host rows x laid back to back (lens[nrows] samples each, f32), always through the kernels (p = s = 1 included).
+ * period_in / voiced_in (both or neither; one entry per frame, ceil(len / hop) frames per row, rows back to back): the contour to use instead of
+ * the estimated one; a voiced period outside [tau_min - 1, tau_max + 1] is refused.  Outputs: y laid out as x; period_out / voiced_out per
+ * frame (may be NULL); ta, ts, map [sum(lens) + nrows] each, row i's lists starting at entry sum_{r < i} (lens[r] + 1), and n_marks
+ * [nrows][2] = (Na, Ns) per row (all four may be NULL together). */
+int sbv2_debug_voice_shift(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
+                           const double* period_in, const int32_t* voiced_in, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts,
+                           int32_t* map, int64_t* n_marks, float* y);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,

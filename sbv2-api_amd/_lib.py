@@ -94,6 +94,12 @@ class Sbv2Pitch(C.Structure):
                 ("n_frames", C.c_int64)]
 
 
+class Sbv2Voice(C.Structure):
+    """struct sbv2_voice (include/sbv2_hip.h)."""
+    _fields_ = [("pitch_scale", C.c_double), ("intonation_scale", C.c_double), ("f0_min", C.c_double), ("f0_max", C.c_double),
+                ("threshold", C.c_double), ("hop", C.c_int32), ("reserved", C.c_int32)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -135,6 +141,12 @@ SYMBOLS = {
     "sbv2_pipeline_fetch_request_pitch": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.c_void_p, C.c_int64, i64p,
                                                     C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
     "sbv2_pitch_lags": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "sbv2_pipeline_fetch_request_voice": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice), C.c_void_p, C.c_int64, i64p,
+                                                    C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_voice_tile": (C.c_int32, []),
+    "sbv2_debug_voice_shift": (C.c_int, [C.c_int, f32p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Voice), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), i64p, f32p]),
     "sbv2_debug_pitch": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2Pitch), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int32)]),
     "sbv2_marks_spans": (C.c_int, [i64p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sbv2PcmFormat), i64p, i64p]),

@@ -518,6 +518,12 @@ static PitchSpec check_pitch_static(const sbv2_pitch* q, int rate) {
     return sp;
 }
 
+// The checks of sbv2_voice that need no run: the parameters at the rate of the rows (voice.h states the bounds).
+static VoiceSpec check_voice_static(const sbv2_voice* v, int rate) {
+    SBV2_REQUIRE(v->reserved == 0, "sbv2_voice.reserved must be 0");
+    return voice_spec(rate, v->pitch_scale, v->intonation_scale, v->hop, v->f0_min, v->f0_max, v->threshold);
+}
+
 // The run's packed PCM (pcm_device + pcm_offs / pcm_lens) is formatted on the run's own stream and crosses PCIe in the format: every
 // check first (format, gain options, ticket, placement, PCM capacity), then the formatter's launches with the gain stage between the
 // resampler and the quantiser, then the sink.  out_counts: samples (PCM) or bytes (FLAC) of each signal; stats (may be NULL): the gain
@@ -526,9 +532,12 @@ static PitchSpec check_pitch_static(const sbv2_pitch* q, int rate) {
 // marks (with utts): the speech marks of that signal; their reduction reads the delivered samples in HBM, on the same stream, before the one
 // synchronisation of the fetch, and the caller's arrays are written only once everything else has succeeded.
 // pitch (with utts): the pitch contour of the same delivered samples (Pitch, marks.h), enqueued and written under the same two rules.
+// voice (with utts; NULL or the identity: nothing): the listed rows are shifted first (Voice, voice.h) into the chain's scratch buffer, laid out
+// like the run's packed PCM, and the pieces point there; the run's PCM is only read.
 static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
                             int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats,
-                            const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr) {
+                            const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr,
+                            const sbv2_voice* voice = nullptr) {
     const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
     const LoudnessSpec ln = gain.kind == FetchGain::kLoudness ? loudness_spec(gain.ln) : LoudnessSpec();
     const LimiterSpec lim = gain.kind == FetchGain::kLimiter ? limiter_spec(gain.lim) : LimiterSpec();
@@ -555,9 +564,22 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         SBV2_REQUIRE(pitch->capacity >= n_pitch,
                      "pitch arrays too small: " + std::to_string(pitch->capacity) + " < " + std::to_string(n_pitch) + " frames");
     }
+    VoiceSpec vs;
+    if (voice) {
+        SBV2_REQUIRE(utts && place, "internal: voice needs a request's rows");
+        vs = check_voice_static(voice, kNativeRate);
+    }
+    const bool shift = voice && !vs.identity() && n_utts > 0;
     HIP_CHECK(hipSetDevice(vm.device()));
     OutputChain& c = p->chains[ctx];
     const hipStream_t s = vm.stream();
+    if (shift) {   // the listed rows, shifted, where the formatter will read them
+        std::vector<VoiceRow> rows((size_t)n_utts);
+        for (int k = 0; k < n_utts; ++k) rows[k] = VoiceRow{vm.pcm_offs()[utts[k]], vm.pcm_lens()[utts[k]]};
+        const float* pcm = vm.pcm_device();
+        const float* shifted = c.voice.run(pcm, vm.pcm_total(), rows.data(), n_utts, vs, s);
+        for (FmtPiece& pc : pieces) pc.src = shifted + (pc.src - pcm);
+    }
     if (sink == Sink::kPcm && gain.kind == FetchGain::kNone && spec.identity() && !place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
         HIP_CHECK(hipMemcpyAsync(dst, vm.pcm_device(), sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, s));
     } else if (total > 0 || gain.kind != FetchGain::kNone || sink == Sink::kFlac) {   // a gain stage and the encoder run on empty signals too
@@ -583,6 +605,8 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         }
     }
     HIP_CHECK(hipStreamSynchronize(s));
+    if (shift)
+        for (int k = 0; k < n_utts; ++k) SBV2_REQUIRE(c.voice.status(k) == 0, "internal: the shifter found more marks than it planned for");
     for (size_t i = 0; i < outs.size(); ++i) out_counts[i] = sink == Sink::kFlac ? flac_bytes[i] : outs[i];
     if (stats) {   // written by the stage's last copy on s
         const double* from = gain.kind == FetchGain::kLimiter ? c.limiter.stats_host() : c.meter.stats_host();
@@ -682,9 +706,12 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
     API_END
 }
 
-int sbv2_pipeline_fetch_request_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
-                                      int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch) {
+int32_t sbv2_voice_tile(void) { return Voice::kTile; }
+
+int sbv2_pipeline_fetch_request_voice(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice, void* dst,
+                                      int64_t capacity_bytes, int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch) {
     API_BEGIN
+    if (voice) (void)check_voice_static(voice, kNativeRate);   // what needs no run is refused before the handle is looked at
     SBV2_REQUIRE(req && req->n_utts >= 0 && (req->n_utts == 0 || (req->utts && req->place)), "bad fetch request");
     SBV2_REQUIRE(!(req->loudness && req->limiter), "a fetch request takes a loudness target or a limiter, not both");
     if (marks) {   // what needs no run is refused before the handle is looked at
@@ -699,8 +726,12 @@ int sbv2_pipeline_fetch_request_pitch(sbv2_pipeline* p, int64_t ticket, const sb
     static const int32_t no_rows[1] = {0};
     static const int64_t no_place[1] = {0};
     fetch_formatted(p, ticket, req->fmt, gain, req->n_utts ? req->place : no_place, req->joined_len, req->flac ? Sink::kFlac : Sink::kPcm, dst,
-                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch);
+                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch, voice);
     API_END
+}
+int sbv2_pipeline_fetch_request_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
+                                      int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch) {
+    return sbv2_pipeline_fetch_request_voice(p, ticket, req, nullptr, dst, capacity_bytes, out_count, stats, marks, pitch);
 }
 int sbv2_pipeline_fetch_request_marks(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
                                       int64_t* out_count, double* stats, sbv2_marks* marks) {

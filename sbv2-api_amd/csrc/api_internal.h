@@ -13,6 +13,7 @@
 #include "marks.h"
 #include "models.h"
 #include "pcm_format.h"
+#include "voice.h"
 
 namespace sbv2 {
 const char* last_error_cstr();
@@ -35,6 +36,7 @@ struct OutputChain {
     Limiter limiter;   // (owns a second meter, for its evaluations)
     Marks marks;       // speech marks: levels of token spans and envelope frames (fetch_request_marks only)
     Pitch pitch;       // ... and the pitch contour of the same samples (fetch_request_pitch only)
+    Voice voice;       // pitch / intonation scale of the listed rows, in front of the formatter (fetch_request_voice only)
 };
 struct sbv2_pipeline {
     sbv2_bert* bert;

@@ -61,6 +61,10 @@ inline int64_t pitch_frames(int64_t n, int64_t hop) { return n > 0 ? (n + hop - 
 // c(lag - 1), c(lag), c(lag + 1), f0 = sr / (lag + delta) for a voiced frame and 0 otherwise, ap = c(lag).
 void pitch_finish(const PitchSpec& sp, int32_t lag, int32_t voiced, const double* c3, double* f0, double* ap);
 
+// The estimator's one launch (k_pitch_yin) into the caller's device arrays c3 [nf][3], lag [nf], voiced [nf], nf = pitch_frames(n, sp.hop);
+// x = n samples on the device (encoding as Marks::run).  n = 0 enqueues nothing.  Pitch::run and the shifter's contour (voice.hip) go through it.
+void pitch_launch(const void* x, int encoding, int64_t n, const PitchSpec& sp, double* c3, int32_t* lag, int32_t* voiced, hipStream_t s);
+
 // Device state of the pitch estimator of one execution context (k_pitch_yin, marks.hip): results on the device and their pinned mirror, grown
 // on demand; nothing is allocated before the first run.  One launch per run, one workgroup per frame, no atomics.
 class Pitch {

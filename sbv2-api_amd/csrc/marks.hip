@@ -594,17 +594,13 @@ void pitch_finish(const PitchSpec& sp, int32_t lag, int32_t voiced, const double
     if (ap) *ap = c0;
 }
 
-void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hipStream_t s) {
+void pitch_launch(const void* x, int encoding, int64_t n, const PitchSpec& sp, double* c3, int32_t* lag, int32_t* voiced, hipStream_t s) {
     SBV2_REQUIRE(pcm_encoding_known(encoding), "internal: pitch of an unknown encoding");
     SBV2_REQUIRE(n >= 0 && sp.hop >= 1 && sp.tau_min >= 1 && sp.tau_min <= sp.tau_max && sp.tau_max <= kPitchMaxTau, "internal: bad pitch spec");
     const int64_t nf = pitch_frames(n, sp.hop);
     SBV2_REQUIRE(nf < (1 << 30), "too many pitch frames: " + std::to_string(nf) + " >= 2^30");
-    nf_ = nf;
     if (nf == 0) return;
-    SBV2_REQUIRE(x, "internal: no samples");
-    const size_t bytes = 32 * (size_t)nf;   // c3 (24) | lag (4) | voiced (4) per frame
-    char* h = static_cast<char*>(host_.reserve(bytes, std::max<size_t>(bytes * 2, 4096), s));
-    char* d = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes * 2, 4096), s));
+    SBV2_REQUIRE(x && c3 && lag && voiced, "internal: no samples");
     PitchArgs a;
     a.x = x;
     a.n = n;
@@ -612,9 +608,9 @@ void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hip
     a.tau_min = sp.tau_min;
     a.tau_max = sp.tau_max;
     a.threshold = sp.threshold;
-    a.c3 = reinterpret_cast<double*>(d);
-    a.lag = reinterpret_cast<int32_t*>(d + 24 * (size_t)nf);
-    a.voiced = a.lag + nf;
+    a.c3 = c3;
+    a.lag = lag;
+    a.voiced = voiced;
     const int nt = pitch_lanes(sp.tau_max), P = (sp.tau_max + nt - 1) / nt;
     const dim3 grid((unsigned)nf), blk(nt);
     if (encoding == kEncS16) launch_pitch<int16_t>(P, grid, blk, s, a);
@@ -622,6 +618,19 @@ void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hip
     else if (encoding == kEncAlaw) launch_pitch<AlawCode>(P, grid, blk, s, a);
     else launch_pitch<float>(P, grid, blk, s, a);
     HIP_CHECK(hipGetLastError());
+}
+
+void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hipStream_t s) {
+    SBV2_REQUIRE(n >= 0 && sp.hop >= 1, "internal: bad pitch spec");
+    const int64_t nf = pitch_frames(n, sp.hop);
+    SBV2_REQUIRE(nf < (1 << 30), "too many pitch frames: " + std::to_string(nf) + " >= 2^30");
+    nf_ = nf;
+    if (nf == 0) return;
+    const size_t bytes = 32 * (size_t)nf;   // c3 (24) | lag (4) | voiced (4) per frame
+    char* h = static_cast<char*>(host_.reserve(bytes, std::max<size_t>(bytes * 2, 4096), s));
+    char* d = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes * 2, 4096), s));
+    int32_t* lag = reinterpret_cast<int32_t*>(d + 24 * (size_t)nf);
+    pitch_launch(x, encoding, n, sp, reinterpret_cast<double*>(d), lag, lag + nf, s);
     HIP_CHECK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s));
 }
 

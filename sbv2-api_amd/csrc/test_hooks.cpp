@@ -1916,6 +1916,50 @@ int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t
     API_END
 }
 
+// The shifter (Voice, voice.hip) on host rows laid back to back, always through its kernels; everything is checked before any device call.
+int sbv2_debug_voice_shift(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
+                           const double* period_in, const int32_t* voiced_in, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts,
+                           int32_t* map, int64_t* n_marks, float* y) {
+    API_BEGIN
+    SBV2_REQUIRE(voice && nrows >= 0 && (nrows == 0 || lens), "bad arguments");
+    SBV2_REQUIRE(voice->reserved == 0, "sbv2_voice.reserved must be 0");
+    const VoiceSpec sp = voice_spec(sample_rate, voice->pitch_scale, voice->intonation_scale, voice->hop, voice->f0_min, voice->f0_max, voice->threshold);
+    SBV2_REQUIRE(!period_in == !voiced_in, "period_in and voiced_in are given together or not at all");
+    SBV2_REQUIRE((!ta == !ts) && (!ta == !map) && (!ta == !n_marks), "ta, ts, map and n_marks are given together or not at all");
+    std::vector<VoiceRow> rows((size_t)nrows);
+    int64_t total = 0;
+    for (int i = 0; i < nrows; ++i) {
+        SBV2_REQUIRE(lens[i] >= 0 && lens[i] < (1 << 30), "bad length of row " + std::to_string(i));
+        rows[i] = VoiceRow{total, lens[i]};
+        total += lens[i];
+    }
+    SBV2_REQUIRE(total == 0 || (x && y), "bad arguments");
+    HIP_CHECK(hipSetDevice(device));
+    DevMem dx(x, sizeof(float) * (size_t)total);
+    Voice v;
+    const float* dy = v.run(dx.f(), total, rows.data(), nrows, sp, nullptr, period_in, voiced_in);
+    v.results_to_host(nullptr);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    for (int i = 0; i < nrows; ++i) SBV2_REQUIRE(v.status(i) == 0, "internal: the shifter found more marks than it planned for in row " + std::to_string(i));
+    if (total) HIP_CHECK(hipMemcpy(y, dy, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost));
+    if (period_out) std::memcpy(period_out, v.period_host(), sizeof(double) * (size_t)v.n_frames());
+    if (voiced_out) std::memcpy(voiced_out, v.voiced_host(), sizeof(int32_t) * (size_t)v.n_frames());
+    if (ta) {
+        int64_t at = 0;   // row i's lists start at sum of (lens + 1) of the rows before it
+        for (int i = 0; i < nrows; ++i) {
+            const int64_t na = v.n_a(i), ns = v.n_s(i);
+            SBV2_REQUIRE(na <= lens[i] + 1 && ns <= lens[i] + 1, "internal: more marks than samples");
+            std::memcpy(ta + at, v.ta_host(i), sizeof(int32_t) * (size_t)na);
+            std::memcpy(ts + at, v.ts_host(i), sizeof(int32_t) * (size_t)ns);
+            std::memcpy(map + at, v.map_host(i), sizeof(int32_t) * (size_t)ns);
+            n_marks[2 * i] = na;
+            n_marks[2 * i + 1] = ns;
+            at += lens[i] + 1;
+        }
+    }
+    API_END
+}
+
 // The fed level reduction (StreamLevels, marks.hip) on its own: x cut at cuts[ncuts] into ncuts + 1 pushes, each handed the samples of its
 // piece only.  Segments, envelope and cuts are checked before any device call.
 int sbv2_debug_stream_levels(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, const int64_t* starts,

@@ -1,0 +1,401 @@
+// Pitch and intonation scale: TD-PSOLA of the run's native f32 rows on gfx950, as include/sbv2_hip.h states it above sbv2_voice.
+//
+// Three steps on one stream, no atomics, every f64 expression in the header's order (this file is built with -ffp-contract=off and says so
+// itself below: bit equality with the numpy restatement depends on it).
+//   * The contour: k_pitch_yin on f32 (marks.hip, pitch_launch), one launch per row, into this file's frame arrays.
+//   * k_voice_marks, one workgroup per row.  Lanes take frames: the parabolic refinement (the f64 expression of pitch_finish), the integer sum of
+//     f0 (int64, so the tree's order does not matter), the two Q32 increments.  One lane walks the frames once for the phases at the frames'
+//     starts and the running mark counts: the increment is constant within a frame, so nothing walks the samples.  Lanes take frames again and
+//     place each frame's marks by one division per mark, then take synthesis marks and find each one's nearest analysis mark by bisection.
+//   * k_voice_gather, the hot path: a workgroup owns kTile consecutive output samples of one row, one per lane.  The synthesis marks whose
+//     window can reach the tile are those with ts in [tile - half, tile + half): two bisections by one lane.  They are staged in LDS 256 at a
+//     time with their analysis mark's position and its two half-widths, and every lane walks them in ascending j, adding w and w x in f64 where
+//     the window covers its sample.  A staged mark is a broadcast read; x[ta + u] is consecutive across lanes.  Reads stay inside the row:
+//     ta - L >= -1 and ta + R <= n by the definition of L and R, and the index is checked besides.
+#include "voice.h"
+
+#include <cmath>
+#include <cstring>
+
+#pragma clang fp contract(off)
+
+namespace sbv2 {
+
+namespace {
+
+constexpr int kBlock = 256;
+static_assert(Voice::kTile == kBlock, "one output sample per lane");
+
+struct VoiceRowDev {   // one row of a call, on the device
+    int64_t off, n;    // samples [off, off + n) of x and y
+    int64_t f_off, nf; // its frames in the frame arrays
+    int64_t m_off, cap;   // its marks in ta / ts / map, and how many each may hold
+};
+
+struct VoiceMarkArgs {
+    const VoiceRowDev* rows;
+    const double* c3;        // the YIN results (not read with a given contour)
+    const int32_t* lag;
+    const int32_t* yvoiced;
+    int32_t given;           // period / voiced hold the caller's contour
+    double* period;          // [NF] T_f
+    int32_t* voiced;         // [NF] 0 / 1
+    int64_t *inc_a, *inc_s, *phi_a, *phi_s;   // [NF] increments; phases at the sample before the frame's first
+    int32_t *off_a, *off_s;                   // [NF] marks before the frame
+    int32_t *ta, *ts, *map;
+    int32_t* count;          // [nrows][4]: n_a, n_s, status, 0
+    double sr, p, s, g_lo, g_hi;
+    int64_t inc_u, hop;
+    int32_t tau_max;
+};
+
+constexpr double kTwo32 = 4294967296.0;
+
+// the marks of one frame: positions k = first + c - 1 for the c at which phi + c inc reaches the next integers (0 < inc <= 2^32: at most one a sample)
+__device__ inline void place_marks(int64_t phi, int64_t inc, int64_t len, int64_t first, int32_t* out) {
+    const int64_t B = phi >> 32, E = (phi + len * inc) >> 32;
+    for (int64_t q = 1; q <= E - B; ++q) {
+        const int64_t D = ((B + q) << 32) - phi;   // > 0
+        out[q - 1] = (int32_t)(first + (D + inc - 1) / inc - 1);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_voice_marks(const VoiceMarkArgs a) {
+    __shared__ int64_t sh_sum[kBlock];
+    __shared__ int32_t sh_cnt[kBlock];
+    __shared__ int32_t sh_n[2];
+    const VoiceRowDev r = a.rows[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int64_t nf = r.nf;
+    // the contour and the integer sum of f0
+    int64_t sum = 0;
+    int32_t cnt = 0;
+    for (int64_t f = tid; f < nf; f += kBlock) {
+        const int64_t F = r.f_off + f;
+        double T;
+        int32_t v;
+        if (a.given) {
+            T = a.period[F];
+            v = a.voiced[F] != 0;
+        } else {
+            const double cm = a.c3[3 * F], c0 = a.c3[3 * F + 1], cp = a.c3[3 * F + 2];
+            const int32_t lag = a.lag[F];
+            const double den = cm - 2.0 * c0 + cp;
+            const bool both = lag - 1 >= 1 && lag + 1 <= a.tau_max;
+            double delta = den > 0.0 && both ? 0.5 * (cm - cp) / den : 0.0;
+            delta = fmin(fmax(delta, -1.0), 1.0);
+            T = (double)lag + delta;
+            v = a.yvoiced[F] != 0;
+            a.period[F] = T;
+        }
+        a.voiced[F] = v;
+        if (v) {
+            sum += llrint((a.sr / T) * 65536.0);
+            ++cnt;
+        }
+    }
+    sh_sum[tid] = sum;
+    sh_cnt[tid] = cnt;
+    __syncthreads();
+    for (int d = kBlock / 2; d >= 1; d >>= 1) {
+        if (tid < d) sh_sum[tid] += sh_sum[tid + d], sh_cnt[tid] += sh_cnt[tid + d];
+        __syncthreads();
+    }
+    const int32_t nv = sh_cnt[0];
+    const double m = nv ? (double)sh_sum[0] / (65536.0 * (double)nv) : 0.0;
+    // the increments
+    for (int64_t f = tid; f < nf; f += kBlock) {
+        const int64_t F = r.f_off + f;
+        int64_t ia = a.inc_u, is = a.inc_u;
+        if (a.voiced[F]) {
+            const double T = a.period[F], f0 = a.sr / T;
+            double g = a.p * (m + a.s * (f0 - m));
+            g = fmin(fmax(g, a.g_lo), a.g_hi);
+            const double Tp = a.sr / g;
+            ia = llrint(kTwo32 / T);
+            is = llrint(kTwo32 / Tp);
+        }
+        a.inc_a[F] = ia;
+        a.inc_s[F] = is;
+    }
+    __syncthreads();
+    // the phases at the frames' starts and the marks before each frame: one lane, once over the frames
+    if (tid == 0) {
+        int64_t pa = 0, ps = 0, ca = 0, cs = 0;
+        bool prev = false;
+        for (int64_t f = 0; f < nf; ++f) {
+            const int64_t F = r.f_off + f, len = min(a.hop, r.n - f * a.hop), ia = a.inc_a[F], is = a.inc_s[F];
+            const bool v = a.voiced[F] != 0;
+            if (!v || !prev) ps = pa;   // an unvoiced frame has the analysis marks; a voiced run starts from the analysis phase
+            a.phi_a[F] = pa;
+            a.phi_s[F] = ps;
+            a.off_a[F] = (int32_t)min(ca, r.cap);
+            a.off_s[F] = (int32_t)min(cs, r.cap);
+            ca += ((pa + len * ia) >> 32) - (pa >> 32);
+            cs += ((ps + len * is) >> 32) - (ps >> 32);
+            pa += len * ia;
+            ps += len * is;
+            prev = v;
+        }
+        const bool fits = ca <= r.cap && cs <= r.cap;
+        sh_n[0] = fits ? (int32_t)ca : 0;
+        sh_n[1] = fits ? (int32_t)cs : 0;
+        int32_t* c = a.count + 4 * blockIdx.x;
+        c[0] = sh_n[0];
+        c[1] = sh_n[1];
+        c[2] = fits ? 0 : 1;
+        c[3] = 0;
+    }
+    __syncthreads();
+    const int32_t na = sh_n[0], ns = sh_n[1];
+    if (na == 0 && ns == 0) return;   // (uniform) no marks, or more than planned: nothing is written
+    int32_t* ta = a.ta + r.m_off;
+    int32_t* ts = a.ts + r.m_off;
+    int32_t* mp = a.map + r.m_off;
+    for (int64_t f = tid; f < nf; f += kBlock) {
+        const int64_t F = r.f_off + f, len = min(a.hop, r.n - f * a.hop);
+        place_marks(a.phi_a[F], a.inc_a[F], len, f * a.hop, ta + a.off_a[F]);
+        place_marks(a.phi_s[F], a.inc_s[F], len, f * a.hop, ts + a.off_s[F]);
+    }
+    __syncthreads();
+    if (na == 0) return;
+    // the nearest analysis mark of every synthesis mark, a tie to the earlier
+    for (int32_t j = tid; j < ns; j += kBlock) {
+        const int32_t t = ts[j];
+        int32_t lo = 0, hi = na;   // the first analysis mark at or after t
+        while (lo < hi) {
+            const int32_t mid = (lo + hi) / 2;
+            if (ta[mid] < t) lo = mid + 1;
+            else hi = mid;
+        }
+        int32_t m1;
+        if (lo == 0) m1 = 0;
+        else if (lo == na) m1 = na - 1;
+        else m1 = t - ta[lo - 1] <= ta[lo] - t ? lo - 1 : lo;
+        mp[j] = m1;
+    }
+}
+
+struct VoiceGatherArgs {
+    const VoiceRowDev* rows;
+    const float* x;
+    float* y;
+    const int32_t *ta, *ts, *map, *count;
+    int32_t half;
+};
+
+// the first j in [0, n) with v[j] >= t (n if none)
+__device__ inline int32_t first_at_or_after(const int32_t* v, int32_t n, int64_t t) {
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) / 2;
+        if (v[mid] < t) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void k_voice_gather(const VoiceGatherArgs a) {
+    __shared__ int32_t s_ts[kBlock], s_ta[kBlock], s_L[kBlock], s_R[kBlock], s_edge[kBlock];
+    __shared__ int32_t s_range[2];
+    const VoiceRowDev r = a.rows[blockIdx.y];
+    const int64_t t0 = (int64_t)blockIdx.x * Voice::kTile;
+    if (t0 >= r.n) return;   // (uniform: this row has fewer tiles than the longest)
+    const int tid = threadIdx.x;
+    const int64_t n = r.n, k = t0 + tid, t1 = min(t0 + Voice::kTile, n);
+    const bool mine = k < n;
+    const float* x = a.x + r.off;
+    float* y = a.y + r.off;
+    const int32_t na = a.count[4 * blockIdx.y], ns = a.count[4 * blockIdx.y + 1];
+    if (na == 0) {   // (uniform) a row without an analysis mark is copied
+        if (mine) y[k] = x[k];
+        return;
+    }
+    const int32_t* ta = a.ta + r.m_off;
+    const int32_t* ts = a.ts + r.m_off;
+    const int32_t* mp = a.map + r.m_off;
+    if (tid == 0) {
+        s_range[0] = first_at_or_after(ts, ns, t0 - a.half);
+        s_range[1] = first_at_or_after(ts, ns, t1 + a.half);
+    }
+    __syncthreads();
+    const int32_t j0 = s_range[0], j1 = s_range[1];
+    double num = 0.0, den = 0.0;
+    for (int32_t c = j0; c < j1; c += kBlock) {
+        const int32_t j = c + tid;
+        if (j < j1) {
+            const int32_t m = mp[j], am = ta[m];
+            s_ts[tid] = ts[j];
+            s_ta[tid] = am;
+            s_L[tid] = m > 0 ? am - ta[m - 1] : am + 1;
+            s_R[tid] = m + 1 < na ? ta[m + 1] - am : (int32_t)(n - am);
+            s_edge[tid] = (m == 0 ? 1 : 0) | (m == na - 1 ? 2 : 0);
+        }
+        __syncthreads();
+        const int32_t cn = min(kBlock, j1 - c);
+        if (mine) {
+            for (int32_t i = 0; i < cn; ++i) {   // ascending j
+                const int64_t u = k - s_ts[i];
+                const int32_t L = s_L[i], R = s_R[i];
+                if (u <= -(int64_t)L || u >= R) continue;
+                const int64_t src = s_ta[i] + u;
+                if (src < 0 || src >= n) continue;   // (never, by the definition of L and R)
+                const double v = (double)(u < 0 ? -u : u) / (double)(u < 0 ? L : R);
+                double w = 1.0 - (v * v) * (3.0 - 2.0 * v);
+                const int32_t e = s_edge[i];
+                if ((u < 0 && (e & 1)) || (u > 0 && (e & 2))) w = 1.0;
+                num += w * (double)x[src];
+                den += w;
+            }
+        }
+        __syncthreads();
+    }
+    if (mine) y[k] = (float)(num / fmax(den, 1.0));
+}
+
+}  // namespace
+
+VoiceSpec voice_spec(int sample_rate, double pitch_scale, double intonation_scale, int64_t hop, double f0_min, double f0_max, double threshold) {
+    SBV2_REQUIRE(pitch_scale >= 0.5 && pitch_scale <= 2.0, "voice: pitch_scale must be in [0.5, 2]: " + std::to_string(pitch_scale));
+    SBV2_REQUIRE(intonation_scale >= 0.0 && intonation_scale <= 2.0, "voice: intonation_scale must be in [0, 2]: " + std::to_string(intonation_scale));
+    SBV2_REQUIRE(sample_rate >= kVoiceMinRate && sample_rate <= kPitchMaxRate,
+                 "voice: sample rate must be in [" + std::to_string(kVoiceMinRate) + ", " + std::to_string(kPitchMaxRate) + "]: " + std::to_string(sample_rate));
+    if (hop == 0) hop = sample_rate / 200;
+    SBV2_REQUIRE(hop >= sample_rate / 1000 && hop <= sample_rate / 50, "voice: hop must be in [sample_rate / 1000, sample_rate / 50] = [" +
+                                                                            std::to_string(sample_rate / 1000) + ", " + std::to_string(sample_rate / 50) +
+                                                                            "] (0 = sample_rate / 200): " + std::to_string(hop));
+    VoiceSpec v;
+    v.pitch = pitch_spec(sample_rate, hop, f0_min == 0.0 ? 70.0 : f0_min, f0_max == 0.0 ? 600.0 : f0_max, threshold == 0.0 ? 0.15 : threshold);
+    v.pitch_scale = pitch_scale;
+    v.intonation_scale = intonation_scale;
+    const double lo = f0_min == 0.0 ? 70.0 : f0_min, hi = f0_max == 0.0 ? 600.0 : f0_max;
+    v.g_lo = lo / 2.0;
+    v.g_hi = 2.0 * hi;
+    const int tu = sample_rate / 200;
+    v.inc_u = std::llrint(kTwo32 / (double)tu);
+    v.half = std::max(v.pitch.tau_max + 1, tu) + 2;
+    // the shortest synthesis period is sr / (2 f0_max) >= 2, the shortest analysis period tau_min - 1 is longer; a rounded increment may bring two
+    // marks one sample closer than the period's floor
+    v.min_s = std::max(1, std::min((int)std::floor(sample_rate / v.g_hi), tu) - 1);
+    v.min_a = std::max(1, std::min(v.pitch.tau_min - 1, tu) - 1);
+    return v;
+}
+
+float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows, const VoiceSpec& sp, hipStream_t s, const double* period_in,
+                  const int32_t* voiced_in) {
+    SBV2_REQUIRE(nrows >= 0 && nrows <= 65535 && span >= 0 && (nrows == 0 || rows), "voice: bad rows");
+    SBV2_REQUIRE(!period_in == !voiced_in, "voice: period_in and voiced_in are given together or not at all");
+    const int64_t hop = sp.pitch.hop;
+    std::vector<VoiceRowDev> rd((size_t)nrows);
+    int64_t NF = 0, NCAP = 0, longest = 0;
+    cap_off_.assign((size_t)nrows, 0);
+    for (int i = 0; i < nrows; ++i) {
+        SBV2_REQUIRE(rows[i].n >= 0 && rows[i].n < (1 << 30) && rows[i].off >= 0 && rows[i].off + rows[i].n <= span,
+                     "voice: row " + std::to_string(i) + " is outside the buffer or longer than 2^30 samples");
+        rd[i].off = rows[i].off;
+        rd[i].n = rows[i].n;
+        rd[i].f_off = NF;
+        rd[i].nf = pitch_frames(rows[i].n, hop);
+        rd[i].m_off = NCAP;
+        rd[i].cap = rows[i].n / std::min(sp.min_a, sp.min_s) + rd[i].nf + 2;
+        cap_off_[i] = NCAP;
+        NF += rd[i].nf;
+        NCAP += rd[i].cap;
+        longest = std::max(longest, rows[i].n);
+    }
+    SBV2_REQUIRE(NF < (1 << 30) && NCAP < (int64_t(1) << 31), "voice: too many frames or marks in one call");
+    if (period_in)
+        for (int64_t f = 0; f < NF; ++f)
+            SBV2_REQUIRE(!voiced_in[f] || (period_in[f] >= sp.pitch.tau_min - 1 && period_in[f] <= sp.pitch.tau_max + 1),
+                         "voice: period_in of voiced frame " + std::to_string(f) + " is outside [tau_min - 1, tau_max + 1]: " + std::to_string(period_in[f]));
+    nrows_ = nrows;
+    nf_ = NF;
+    ncap_ = NCAP;
+    float* y = static_cast<float*>(out_.reserve(sizeof(float) * (size_t)std::max<int64_t>(span, 16), s));
+    if (nrows == 0) return y;
+    // device: rows | c3 | period | inc_a inc_s phi_a phi_s | lag yvoiced voiced off_a off_s | count | ta ts map   (8-byte parts first)
+    const size_t nF = (size_t)NF, nC = (size_t)NCAP;
+    const size_t o_c3 = round_up64(sizeof(VoiceRowDev) * nrows, 64), o_period = o_c3 + 24 * nF, o_i64 = o_period + 8 * nF, o_i32 = o_i64 + 32 * nF,
+                 o_count = round_up64(o_i32 + 20 * nF, 64), o_marks = o_count + round_up64(16 * (size_t)nrows, 64), bytes = o_marks + 12 * nC;
+    // pinned: rows | period | voiced (the upload) ; period | voiced | count | ta ts map (the mirror)
+    const size_t h_period_in = round_up64(sizeof(VoiceRowDev) * nrows, 64), h_voiced_in = h_period_in + 8 * nF, h_mirror = round_up64(h_voiced_in + 4 * nF, 64),
+                 h_voiced = h_mirror + 8 * nF, h_count = round_up64(h_voiced + 4 * nF, 64), h_marks = h_count + round_up64(16 * (size_t)nrows, 64),
+                 h_bytes = h_marks + 12 * nC;
+    char* d = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes * 2, 65536), s));
+    char* h = static_cast<char*>(host_.reserve(h_bytes, std::max<size_t>(h_bytes * 2, 65536), s));
+    VoiceMarkArgs m{};
+    m.rows = reinterpret_cast<const VoiceRowDev*>(d);
+    double* c3 = reinterpret_cast<double*>(d + o_c3);
+    m.c3 = c3;
+    m.period = d_period_ = reinterpret_cast<double*>(d + o_period);
+    m.inc_a = reinterpret_cast<int64_t*>(d + o_i64);
+    m.inc_s = m.inc_a + nF;
+    m.phi_a = m.inc_s + nF;
+    m.phi_s = m.phi_a + nF;
+    int32_t* lag = reinterpret_cast<int32_t*>(d + o_i32);
+    int32_t* yvoiced = lag + nF;
+    m.lag = lag;
+    m.yvoiced = yvoiced;
+    m.voiced = d_voiced_ = yvoiced + nF;
+    m.off_a = m.voiced + nF;
+    m.off_s = m.off_a + nF;
+    m.count = d_count_ = reinterpret_cast<int32_t*>(d + o_count);
+    m.ta = d_ta_ = reinterpret_cast<int32_t*>(d + o_marks);
+    m.ts = d_ts_ = d_ta_ + nC;
+    m.map = d_map_ = d_ts_ + nC;
+    h_period_ = reinterpret_cast<double*>(h + h_mirror);
+    h_voiced_ = reinterpret_cast<int32_t*>(h + h_voiced);
+    h_count_ = reinterpret_cast<int32_t*>(h + h_count);
+    h_ta_ = reinterpret_cast<int32_t*>(h + h_marks);
+    h_ts_ = h_ta_ + nC;
+    h_map_ = h_ts_ + nC;
+    std::memcpy(h, rd.data(), sizeof(VoiceRowDev) * (size_t)nrows);
+    HIP_CHECK(hipMemcpyAsync(d, h, sizeof(VoiceRowDev) * (size_t)nrows, hipMemcpyHostToDevice, s));
+    m.given = period_in != nullptr;
+    if (m.given && NF > 0) {
+        std::memcpy(h + h_period_in, period_in, 8 * nF);
+        std::memcpy(h + h_voiced_in, voiced_in, 4 * nF);
+        HIP_CHECK(hipMemcpyAsync(m.period, h + h_period_in, 8 * nF, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(m.voiced, h + h_voiced_in, 4 * nF, hipMemcpyHostToDevice, s));
+    } else {
+        for (int i = 0; i < nrows; ++i)
+            pitch_launch(x + rd[i].off, kEncF32, rd[i].n, sp.pitch, c3 + 3 * rd[i].f_off, lag + rd[i].f_off, yvoiced + rd[i].f_off, s);
+    }
+    m.sr = (double)sp.pitch.sample_rate;
+    m.p = sp.pitch_scale;
+    m.s = sp.intonation_scale;
+    m.g_lo = sp.g_lo;
+    m.g_hi = sp.g_hi;
+    m.inc_u = sp.inc_u;
+    m.hop = hop;
+    m.tau_max = sp.pitch.tau_max;
+    hipLaunchKernelGGL(k_voice_marks, dim3((unsigned)nrows), dim3(kBlock), 0, s, m);
+    HIP_CHECK(hipGetLastError());
+    if (longest > 0) {
+        VoiceGatherArgs g{};
+        g.rows = m.rows;
+        g.x = x;
+        g.y = y;
+        g.ta = m.ta;
+        g.ts = m.ts;
+        g.map = m.map;
+        g.count = m.count;
+        g.half = sp.half;
+        hipLaunchKernelGGL(k_voice_gather, dim3((unsigned)((longest + kTile - 1) / kTile), (unsigned)nrows), dim3(kBlock), 0, s, g);
+        HIP_CHECK(hipGetLastError());
+    }
+    // (the status of every row is looked at by the caller after its synchronisation)
+    HIP_CHECK(hipMemcpyAsync(h_count_, d_count_, 16 * (size_t)nrows, hipMemcpyDeviceToHost, s));
+    return y;
+}
+
+void Voice::results_to_host(hipStream_t s) {
+    if (nrows_ == 0) return;
+    if (nf_) {
+        HIP_CHECK(hipMemcpyAsync(h_period_, d_period_, 8 * (size_t)nf_, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(h_voiced_, d_voiced_, 4 * (size_t)nf_, hipMemcpyDeviceToHost, s));
+    }
+    if (ncap_) HIP_CHECK(hipMemcpyAsync(h_ta_, d_ta_, 12 * (size_t)ncap_, hipMemcpyDeviceToHost, s));
+}
+
+}  // namespace sbv2

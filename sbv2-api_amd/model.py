@@ -482,6 +482,81 @@ def debug_pitch(x, sample_rate: int, pitch: Pitch, device: int = 0, encoding: st
     return pitch.take(c, arrays), c3[:c.n_frames], voiced[:c.n_frames]
 
 
+class Voice:
+    """Pitch and intonation scale of a fetched request (struct sbv2_voice: a length-preserving TD-PSOLA of the run's native rows on the device,
+    include/sbv2_hip.h states it).  pitch_scale in [0.5, 2] multiplies f0, intonation_scale in [0, 2] scales its excursions about the rows' mean;
+    hop = native samples per contour frame (0 = rate // 200); f0_min / f0_max / threshold as Pitch has them (0 = 70, 600, 0.15).  Ranges are
+    checked by the library."""
+
+    def __init__(self, pitch_scale: float = 1.0, intonation_scale: float = 1.0, hop: int = 0, f0_min: float = 0.0, f0_max: float = 0.0,
+                 threshold: float = 0.0):
+        self.pitch_scale, self.intonation_scale, self.hop = float(pitch_scale), float(intonation_scale), int(hop)
+        self.f0_min, self.f0_max, self.threshold = float(f0_min), float(f0_max), float(threshold)
+
+    @property
+    def c(self):
+        return _lib.Sbv2Voice(self.pitch_scale, self.intonation_scale, self.f0_min, self.f0_max, self.threshold,
+                              self.hop if -2 ** 31 <= self.hop < 2 ** 31 else -1, 0)
+
+    def is_identity(self) -> bool:
+        return self.pitch_scale == 1.0 and self.intonation_scale == 1.0
+
+    def __repr__(self):
+        return f"Voice({self.pitch_scale}, {self.intonation_scale}, hop={self.hop})"
+
+
+def voice_tile() -> int:
+    """Output samples per workgroup of the shifter's overlap-add gather (sbv2_voice_tile)."""
+    return int(_lib.lib().sbv2_voice_tile())
+
+
+def debug_voice_shift(rows, sample_rate: int, voice: Voice, period=None, voiced=None, device: int = 0):
+    """Test hook: the shifter on host rows (sbv2_debug_voice_shift), always through its kernels.  rows: float32 arrays (one array = one row);
+    period / voiced: per row, the contour to use instead of the estimated one (both or neither) -> a list of namespaces, one per row: y, period
+    and voiced (per frame, as used), ta, ts, map."""
+    import types
+    if isinstance(rows, np.ndarray):
+        rows = [rows]
+    rows = [np.ascontiguousarray(r).reshape(-1) for r in rows]
+    for r in rows:
+        if r.dtype != np.float32:
+            raise Sbv2Error(f"the shifter takes float32 rows, not {r.dtype}")
+    lens = np.array([r.size for r in rows], np.int64)
+    x = np.ascontiguousarray(np.concatenate(rows + [np.zeros(0, np.float32)]))
+    c = voice.c
+    hop = voice.hop if voice.hop else int(sample_rate) // 200
+    nfs = [-(-int(n) // hop) if n and hop > 0 else 0 for n in lens]
+    nf, total = int(sum(nfs)), int(lens.sum())
+    i32p = C.POINTER(C.c_int32)
+    pin = vin = None
+    if (period is None) != (voiced is None):
+        raise Sbv2Error("period and voiced are given together or not at all")
+    if period is not None:
+        if isinstance(period, np.ndarray):
+            period, voiced = [period], [voiced]
+        pin = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in period] + [np.zeros(0)]))
+        vin = np.ascontiguousarray(np.concatenate([np.asarray(a).reshape(-1) for a in voiced] + [np.zeros(0)]).astype(np.int32))
+        if pin.size != nf or vin.size != nf:
+            raise Sbv2Error(f"the contour must hold one entry per frame ({nf})")
+        pin, vin = np.concatenate([pin, [0.0]]), np.concatenate([vin, [0]]).astype(np.int32)   # (never a NULL for an empty contour)
+    pout, vout = np.zeros(nf + 1, np.float64), np.zeros(nf + 1, np.int32)
+    ta, ts, mp = (np.zeros(total + len(rows) + 1, np.int32) for _ in range(3))
+    nm = np.zeros((len(rows) + 1, 2), np.int64)
+    y = np.zeros(total + 1, np.float32)
+    check(_lib.lib().sbv2_debug_voice_shift(int(device), x.ctypes.data_as(_lib.f32p) if total else None, lens.ctypes.data_as(i64p) if len(rows) else None,
+                                            len(rows), int(sample_rate), C.byref(c), _f64p(pin) if pin is not None else None,
+                                            vin.ctypes.data_as(i32p) if vin is not None else None, _f64p(pout), vout.ctypes.data_as(i32p),
+                                            ta.ctypes.data_as(i32p), ts.ctypes.data_as(i32p), mp.ctypes.data_as(i32p), nm.ctypes.data_as(i64p),
+                                            y.ctypes.data_as(_lib.f32p)))
+    out, at, fa, ma = [], 0, 0, 0
+    for i, n in enumerate(lens):
+        n, na, ns = int(n), int(nm[i, 0]), int(nm[i, 1])
+        out.append(types.SimpleNamespace(y=y[at:at + n].copy(), period=pout[fa:fa + nfs[i]].copy(), voiced=vout[fa:fa + nfs[i]].copy(),
+                                         ta=ta[ma:ma + na].astype(np.int64), ts=ts[ma:ma + ns].astype(np.int64), map=mp[ma:ma + ns].astype(np.int64)))
+        at, fa, ma = at + n, fa + nfs[i], ma + n + 1
+    return out
+
+
 def debug_stream_pitch(x, cuts, sample_rate: int, pitch: Pitch, device: int = 0, encoding: str | None = None):
     """Test hook: the fed pitch estimator on its own (sbv2_debug_stream_pitch).  x as for debug_pitch, cut at the ascending positions `cuts`
     into len(cuts) + 1 pushes -> debug_pitch's results and per_push [len(cuts) + 1], the frames each push completed."""
@@ -776,7 +851,8 @@ class Pipeline:
         """The signals of fetch_format(b, fmt, place, joined_len), each as one FLAC stream (bytes) encoded on the device; fmt must be s16."""
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
-    def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None):
+    def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
+                      voice=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
@@ -785,7 +861,9 @@ class Pipeline:
         their levels (levels=False: timing only, no kernel) and, with env_hop > 0 delivered samples, the envelope.  The signal and stats are
         those of the same call without marks.
         pitch: a Pitch -> a fourth element, that Pitch with the contour of the delivered signal (sbv2_pipeline_fetch_request_pitch); the third is
-        None without marks.  Signal, stats and marks are those of the same call without pitch."""
+        None without marks.  Signal, stats and marks are those of the same call without pitch.
+        voice: a Voice -> the listed rows are shifted on the device before the formatter (sbv2_pipeline_fetch_request_voice); everything else,
+        the returned shape included, is the same call on the shifted rows.  None or Voice(1, 1): exactly the call without."""
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
         rw = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
@@ -802,9 +880,14 @@ class Pipeline:
         stats = np.zeros(nstats, np.float64) if nstats else None
         if pitch is not None:
             cp, parr = pitch.c_struct(pcm_format_length(fmt, int(joined_len)))
-        if not marks and pitch is None:
+        if not marks and pitch is None and voice is None:
             check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
                                                          _f64p(stats) if nstats else None))
+            return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
+        if not marks and pitch is None:
+            cv = voice.c
+            check(_lib.lib().sbv2_pipeline_fetch_request_voice(self.h, b.ticket, C.byref(req), C.byref(cv), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
+                                                               C.byref(got), _f64p(stats) if nstats else None, None, None))
             return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
         m = cm = None
         if marks:
@@ -819,7 +902,10 @@ class Pipeline:
                                 _f64p(m.env_peak) if env_hop > 0 else None, 0)
         args = (self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
                 C.byref(cm) if marks else None)
-        if pitch is None:
+        if voice is not None:
+            cv = voice.c
+            check(_lib.lib().sbv2_pipeline_fetch_request_voice(*args[:3], C.byref(cv), *args[3:], C.byref(cp) if pitch is not None else None))
+        elif pitch is None:
             check(_lib.lib().sbv2_pipeline_fetch_request_marks(*args))
         else:
             check(_lib.lib().sbv2_pipeline_fetch_request_pitch(*args, C.byref(cp)))

@@ -47,11 +47,19 @@ class SynthesizeOptions:
     example target - L from the loudness stats of an earlier answer of the same voice.
     pitch_hz (new; easy_synthesize_marks only, refused everywhere else): the speech marks carry a pitch contour of pitch_hz frames per second
     (an integer in [1, 1000]; sample_rate // pitch_hz delivered samples per frame), estimated on the device from the delivered samples within
-    [pitch_min_hz, pitch_max_hz] (model.Pitch)."""
+    [pitch_min_hz, pitch_max_hz] (model.Pitch).
+    pitch_scale in [0.5, 2] / intonation_scale in [0, 2] (new; checked here): the voice is raised or lowered, its melody flattened or
+    exaggerated about its mean, by a length-preserving overlap-add of the synthesized rows on the device before anything else of the output
+    chain (model.Voice); whole-signal routes only (easy_synthesize, easy_synthesize_marks, the batcher), refused on streams.  The defaults
+    1.0 / 1.0 are the calls and the bytes there always were."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
                  normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
-                 pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0):
+                 pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0):
+        for name, v, lo, hi in (("pitch_scale", pitch_scale, 0.5, 2.0), ("intonation_scale", intonation_scale, 0.0, 2.0)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= v <= hi:   # (a NaN fails the comparison)
+                raise model.Sbv2Error(f"{name} must be a number in [{lo}, {hi}]: {v!r}")
+        self.pitch_scale, self.intonation_scale = float(pitch_scale), float(intonation_scale)
         if loudness is not None and normalize:
             raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
         if limiter and loudness is None:
@@ -216,6 +224,19 @@ def refuse_pitch(options, what: str):
                               "(easy_synthesize_marks) instead")
 
 
+def voice_options(options):
+    """The model.Voice of a request (None at the defaults: the request is then the call it always was)."""
+    p, s = float(getattr(options, "pitch_scale", 1.0)), float(getattr(options, "intonation_scale", 1.0))
+    return None if p == 1.0 and s == 1.0 else model.Voice(p, s)
+
+
+def refuse_voice(options, what: str):
+    """pitch_scale / intonation_scale where rows leave chunk by chunk: refused, with the routes that shift a whole signal."""
+    if voice_options(options) is not None:
+        raise model.Sbv2Error(f"pitch_scale / intonation_scale shift a whole signal: {what} hands out chunks before the rows are complete, ask "
+                              "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
+
+
 def token_marks(utts, live, rate: int, start, end):
     """The timing part of the marks dict: utts = the request's live sentences (phones, word2ph), live = their line numbers, start / end = the
     delivered-sample spans of their tokens, sentence after sentence.  tokens: one entry per phone id (blanks included); words: one entry per
@@ -285,12 +306,14 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
     request's rows with marks (at the identity format for the default output: the same samples, hence the same bytes)."""
     options, fmt, ln = plan.options, plan.fmt, plan.gain
     lens = b.lens[r0:r1]
-    if ln is not None or not fmt.is_default or marks is not None:
+    voice = voice_options(options)
+    vkw = {} if voice is None else {"voice": voice}   # (named only when asked for: a request at the defaults is the call it always was)
+    if ln is not None or not fmt.is_default or marks is not None or voice is not None:
         # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
         if marks is not None:
-            kw = dict(gain=ln, flac=plan.flac, marks=True, env_hop=envelope_hop(options, fmt.sample_rate))
+            kw = dict(gain=ln, flac=plan.flac, marks=True, env_hop=envelope_hop(options, fmt.sample_rate), **vkw)
             pitch = pitch_options(options, fmt.sample_rate)
             if pitch is None:   # (the call of a request without a contour is the call it always was)
                 out, stats, m = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw)
@@ -298,7 +321,7 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
                 out, stats, m, pitch = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, pitch=pitch, **kw)
             marks.append(marks_dict(plan.utts, plan.live, fmt, m, pitch))
         else:
-            out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac)
+            out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, **vkw)
         if stats is not None and loudness_stats is not None:
             loudness_stats.append([float(v) for v in stats])
         if plan.flac:
@@ -508,6 +531,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     is estimated on the device chunk by chunk as well (model.StreamHandle(pitch=...)): take_marks() pieces gain a "pitch" block, and once the
     last piece is out `.marks` has marks_dict's "pitch" block and the tokens' f0_hz / voiced.  Without pitch=True, pitch_hz is refused."""
     options = options or SynthesizeOptions()
+    refuse_voice(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if pitch:
         if not levels:
             raise model.Sbv2Error("pitch=True on a stream comes with its speech marks: pass levels=True as well")

@@ -31,6 +31,9 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     pitch_hz = null (new; range as for /synthesize_marks): the first line gains "pitch": {"hop", "n_frames"} and every later
                     line "pitch": {"first", "hop", "f0_hz", "aperiodicity"}, the frames of the contour whose window that piece completed
                     (about 1 / pitch_min_hz seconds behind the audio), estimated on the device chunk by chunk with the one-shot contour's bits.
+  pitch_scale = 1.0, intonation_scale = 1.0 (new; /synthesize and /synthesize_marks, batched or not): the voice's f0 multiplied by pitch_scale
+                    ([0.5, 2]) and its excursions about the mean scaled by intonation_scale ([0, 2]), by an overlap-add of the synthesized signal
+                    on the device; the signal keeps its length, so marks keep their spans.  The stream routes answer 400 for other values.
   POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
@@ -149,6 +152,8 @@ def make_app(holder, batching=None):
         pitch_hz: Optional[int] = None      # /synthesize_marks, /synthesize_stream_marks: frames per second of the pitch contour in the marks; refused elsewhere
         pitch_min_hz: float = 70.0          # the contour's search range (Hz)
         pitch_max_hz: float = 600.0
+        pitch_scale: float = 1.0            # new: multiplies the voice's f0, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); refused on the stream routes
+        intonation_scale: float = 1.0       # new: scales f0's excursions about its mean, [0, 2]; the same routes
 
     class SynthesizeMarksRequest(SynthesizeRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
@@ -195,7 +200,8 @@ def make_app(holder, batching=None):
                                               encoding=req.encoding, normalize=req.normalize, loudness=req.loudness,
                                               true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction,
                                               envelope_hz=getattr(req, "envelope_hz", None), gain_db=req.gain_db, pitch_hz=req.pitch_hz,
-                                              pitch_min_hz=req.pitch_min_hz, pitch_max_hz=req.pitch_max_hz)
+                                              pitch_min_hz=req.pitch_min_hz, pitch_max_hz=req.pitch_max_hz, pitch_scale=req.pitch_scale,
+                                              intonation_scale=req.intonation_scale)
 
     def synthesize(req: SynthesizeRequest):
         try:
@@ -239,8 +245,19 @@ def make_app(holder, batching=None):
                            "tokens": [[t["line"], t["index"], t["phone"], t["start"], t["end"]] for t in marks["tokens"]],
                            "words": [[w["line"], w["index"], w["start"], w["end"]] for w in marks["words"]]}, separators=(",", ":"))
 
+    def refuse_stream_voice(req):
+        """A 400 for pitch_scale / intonation_scale on a stream route (the request is at fault, nothing was tried), None at the defaults."""
+        try:
+            orchestrator.refuse_voice(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+        except Exception as e:
+            return PlainTextResponse(f"Something went wrong: {e}", status_code=400)
+        return None
+
     @app.post("/synthesize_stream")
     def synthesize_stream(req: SynthesizeStreamRequest):
+        refused = refuse_stream_voice(req)
+        if refused is not None:
+            return refused
         lock.acquire()                        # one request at a time: given back by _HeldPieces.close when the response is over
         try:
             # split_sentences = False is the holder's own default (split=False), and it is sent by leaving the keyword out, on purpose: a holder
@@ -259,6 +276,9 @@ def make_app(holder, batching=None):
 
     @app.post("/synthesize_stream_marks")
     def synthesize_stream_marks(req: SynthesizeStreamMarksRequest):
+        refused = refuse_stream_voice(req)
+        if refused is not None:
+            return refused
         lock.acquire()                        # as /synthesize_stream: given back by _HeldPieces.close when the response is over
         try:
             # (pitch is sent like split: named only when the request asks for it, so a request without pitch_hz is the call it always was)
