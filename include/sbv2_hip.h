@@ -394,7 +394,8 @@ int sbv2_debug_segment_levels(int device, const void* x, int encoding, int64_t n
  *   depend on the order of any sum and equal a restatement in int64 / f64 bit for bit.  For f32 samples differences and squares are taken in
  *   f64 in an order the library fixes; only that order is its own (f32 samples that are s16 integers / 32768 still give the s16 bits).
  * On a stream the same contour comes frame by frame: sbv2_stream_begin_request_pitch / sbv2_stream_next_pitch below.
- * Not done: smoothing across frames (octave errors are the caller's to treat, with ap). */
+ * Not done here: anything across frames.  Octave-error repair is sbv2_pitch_track below (one best path through the frames' candidates, opt-in);
+ *   smoothing of the f0 values is not built. */
 typedef struct sbv2_pitch {
     int32_t hop; int32_t reserved;        /* in: delivered samples per frame (>= 1); reserved must be 0 */
     double f0_min, f0_max, threshold;     /* in: Hz, Hz, (0, 1); usual values 70, 600, 0.15 */
@@ -448,7 +449,8 @@ int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t
  *   the stage cannot create clipping; with p = 1 and s = 1 the two mark lists coincide and y == x bit for bit, and the same holds in any stretch
  *   of unvoiced frames farther than tau_max + H + 2 samples from a voiced one; no half-width exceeds max(tau_max + 1, sr / 200) + 2, which bounds
  *   the gather.  Dividing by den trades level for the peak bound; the loudness stage downstream restores level.
- * Not built: epoch (glottal) alignment of the marks, contour smoothing and octave-error repair, formant shifting, energy compensation.  No
+ * Not built: epoch (glottal) alignment of the marks, contour smoothing, formant shifting, energy compensation (octave-error repair of the
+ *   contour is opt-in: sbv2_pitch_track and sbv2_pipeline_fetch_request_tracked below).  No
  *   stream entry point either: sbv2_stream_* and sbv2_node_* do not take a sbv2_voice. */
 typedef struct sbv2_voice {
     double pitch_scale;          /* [0.5, 2] */
@@ -474,6 +476,51 @@ int32_t sbv2_voice_tile(void);
 int sbv2_debug_voice_shift(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
                            const double* period_in, const int32_t* voiced_in, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts,
                            int32_t* map, int64_t* n_marks, float* y);
+
+/* ---- new: the pitch contour TRACKED across frames (octave-error repair).  sbv2_pitch decides every frame on its own, and "the first lag under
+ * the threshold" answers T / 2 or 2 T on single frames whenever a harmonic or subharmonic dips under the threshold first.  Here every frame
+ * keeps its candidates and ONE path is chosen through them (the last step of pYIN, RAPT and Praat).  Everything after the c values is integer
+ * arithmetic, so the path does not depend on any order of evaluation and equals a sequential restatement bit for bit.
+ * Parameters (anything else, a NaN included, is refused; 0 never means "default"): cand_max in (0, 1]; unvoiced_cost and switch_cost in [0, 4];
+ *   jump_cost in [0, 16]; reserved = {0, 0}.  The host forms U, Sw, J = llrint(value * 65536) once.  Usual values 0.5, 0.30, 0.20, 1.0.
+ * Candidates of a frame.  c(1 .. tau_max) exactly as sbv2_pitch defines it.  tau in [tau_min, tau_max] is a dip iff c(tau) < c(tau - 1) and
+ *   c(tau) <= c(tau + 1) (c(tau_max + 1) read as +infinity) and c(tau) < cand_max.  The candidates are the 7 dips with the smallest c (ties: the
+ *   smaller tau), or all dips when there are fewer, listed in ascending tau; each carries tau, q = llrint(c(tau) * 65536) and c-, c0, c+ under
+ *   the neighbour rule of sbv2_pitch.  A frame may have no candidate (digital silence: S = 0, c = 1).
+ * States.  0 .. 6 are the frame's candidates, 7 is "unvoiced" and is always present; absent candidate slots take no part in any minimum.
+ * Costs (int64).  local(k) = q_k for a candidate, local(7) = U.  trans(j -> k) = (J |tau_k - tau_j|) / max(tau_k, tau_j) (integer division)
+ *   between two candidates, Sw between a candidate and state 7 either way, 0 from 7 to 7.  cost(0, k) = local(k);
+ *   cost(f, k) = local(k) + min_j (cost(f - 1, j) + trans(j -> k)), bp(f, k) = the smallest j that attains the minimum.  The last frame takes
+ *   the smallest k that attains min cost; the path is the backtrace.  With n_frames < 2^30 the costs stay below 2^52.
+ * Result per frame.  On a candidate the frame is voiced, lag = tau and c-, c0, c+ are the candidate's; on state 7 voiced = 0 and lag and the
+ *   three c values stay what sbv2_pitch gives for that frame.  f0, ap and the refinement are sbv2_pitch's, unchanged.
+ * Hence: a frame with no candidate (a "cut") has a single state, so the frames before and after it do not influence each other's choices and
+ *   the path of a signal is the concatenation of the paths of the runs between cuts; the last state before a cut is the smallest j attaining
+ *   min (cost_j + trans(j -> 7)).  The library walks those runs side by side on the device.
+ * Not built: smoothing of the f0 values (a median and the like), tracking on streams (a best path needs the future; a fixed-lag variant would
+ *   be another definition) and on sbv2_node_*, probabilistic voicing (pYIN's several thresholds). */
+typedef struct sbv2_pitch_track {
+    double cand_max;              /* (0, 1]: a dip at or above it is no candidate */
+    double unvoiced_cost;         /* [0, 4]: a frame on state 7 */
+    double switch_cost;           /* [0, 4]: between a candidate and state 7 */
+    double jump_cost;             /* [0, 16]: times the relative change of the lag between two candidates */
+    int32_t reserved[2];          /* must be 0 */
+} sbv2_pitch_track;
+/* sbv2_pipeline_fetch_request_voice with the contours tracked.  track == NULL is exactly that call.  With track and pitch the delivered contour
+ * is the tracked one; with track and a voice that is not the identity the shifter's own contour (native f32, per row, hop H) is tracked with
+ * the same parameters before the marks are placed.  The audio bytes of a tracked fetch without a shifting voice are those of the untracked
+ * fetch; two fetches of one ticket give identical bits.  Refused with nothing written: track with neither a pitch nor a non-identity voice,
+ * parameters outside the ranges above, a non-zero reserved, and everything that call refuses. */
+int sbv2_pipeline_fetch_request_tracked(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                        const sbv2_pitch_track* track, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                        sbv2_marks* marks, sbv2_pitch* pitch);
+/* Test hook: the tracker on host samples x[n] (as sbv2_debug_pitch): pitch receives the TRACKED f0 / ap / lag; cand_out [n_frames][15] (ncand,
+ * 7 tau, 7 q; 0 in absent slots), c3_out [n_frames][7][3] and state_out [n_frames] (0 .. 6 the candidate, 7 unvoiced) may each be NULL.
+ * With cand_in [nf_in][15] the extraction is skipped and the path alone is found on the caller's table: x and pitch may be NULL, c3_in is not
+ * read (the path depends on tau and q alone) and only state_out [nf_in], which must be given, is written.  Refused besides everything
+ * sbv2_debug_pitch refuses: a table with ncand outside [0, 7], tau not ascending or outside [1, 1200], q outside [0, 65536]. */
+int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, const sbv2_pitch_track* track,
+                           const int32_t* cand_in, const double* c3_in, int64_t nf_in, int32_t* cand_out, double* c3_out, int32_t* state_out);
 
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */

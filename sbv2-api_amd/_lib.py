@@ -100,6 +100,12 @@ class Sbv2Voice(C.Structure):
                 ("threshold", C.c_double), ("hop", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Sbv2PitchTrack(C.Structure):
+    """struct sbv2_pitch_track (include/sbv2_hip.h)."""
+    _fields_ = [("cand_max", C.c_double), ("unvoiced_cost", C.c_double), ("switch_cost", C.c_double), ("jump_cost", C.c_double),
+                ("reserved", C.c_int32 * 2)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -143,6 +149,12 @@ SYMBOLS = {
     "sbv2_pitch_lags": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "sbv2_pipeline_fetch_request_voice": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice), C.c_void_p, C.c_int64, i64p,
                                                     C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_pipeline_fetch_request_tracked": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                      C.POINTER(Sbv2PitchTrack), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
+                                                      C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_debug_pitch_track": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2Pitch), C.POINTER(Sbv2PitchTrack),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_int32)]),
     "sbv2_voice_tile": (C.c_int32, []),
     "sbv2_debug_voice_shift": (C.c_int, [C.c_int, f32p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Voice), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),

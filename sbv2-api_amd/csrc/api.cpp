@@ -524,6 +524,12 @@ static VoiceSpec check_voice_static(const sbv2_voice* v, int rate) {
     return voice_spec(rate, v->pitch_scale, v->intonation_scale, v->hop, v->f0_min, v->f0_max, v->threshold);
 }
 
+// The checks of sbv2_pitch_track (track.h states the bounds).
+static TrackSpec check_track_static(const sbv2_pitch_track* t) {
+    SBV2_REQUIRE(t->reserved[0] == 0 && t->reserved[1] == 0, "sbv2_pitch_track.reserved must be 0");
+    return track_spec(t->cand_max, t->unvoiced_cost, t->switch_cost, t->jump_cost);
+}
+
 // The run's packed PCM (pcm_device + pcm_offs / pcm_lens) is formatted on the run's own stream and crosses PCIe in the format: every
 // check first (format, gain options, ticket, placement, PCM capacity), then the formatter's launches with the gain stage between the
 // resampler and the quantiser, then the sink.  out_counts: samples (PCM) or bytes (FLAC) of each signal; stats (may be NULL): the gain
@@ -534,10 +540,11 @@ static VoiceSpec check_voice_static(const sbv2_voice* v, int rate) {
 // pitch (with utts): the pitch contour of the same delivered samples (Pitch, marks.h), enqueued and written under the same two rules.
 // voice (with utts; NULL or the identity: nothing): the listed rows are shifted first (Voice, voice.h) into the chain's scratch buffer, laid out
 // like the run's packed PCM, and the pieces point there; the run's PCM is only read.
+// track (with pitch, or with a voice that shifts): both contours are tracked (Track, track.h) before they are used.
 static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
                             int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats,
                             const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr,
-                            const sbv2_voice* voice = nullptr) {
+                            const sbv2_voice* voice = nullptr, const sbv2_pitch_track* track = nullptr) {
     const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
     const LoudnessSpec ln = gain.kind == FetchGain::kLoudness ? loudness_spec(gain.ln) : LoudnessSpec();
     const LimiterSpec lim = gain.kind == FetchGain::kLimiter ? limiter_spec(gain.lim) : LimiterSpec();
@@ -570,6 +577,11 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         vs = check_voice_static(voice, kNativeRate);
     }
     const bool shift = voice && !vs.identity() && n_utts > 0;
+    TrackSpec ts;
+    if (track) {
+        ts = check_track_static(track);
+        SBV2_REQUIRE(pitch || (voice && !vs.identity()), "pitch tracking needs a pitch contour or a voice that is not the identity");
+    }
     HIP_CHECK(hipSetDevice(vm.device()));
     OutputChain& c = p->chains[ctx];
     const hipStream_t s = vm.stream();
@@ -577,7 +589,7 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         std::vector<VoiceRow> rows((size_t)n_utts);
         for (int k = 0; k < n_utts; ++k) rows[k] = VoiceRow{vm.pcm_offs()[utts[k]], vm.pcm_lens()[utts[k]]};
         const float* pcm = vm.pcm_device();
-        const float* shifted = c.voice.run(pcm, vm.pcm_total(), rows.data(), n_utts, vs, s);
+        const float* shifted = c.voice.run(pcm, vm.pcm_total(), rows.data(), n_utts, vs, s, nullptr, nullptr, track ? &ts : nullptr);
         for (FmtPiece& pc : pieces) pc.src = shifted + (pc.src - pcm);
     }
     if (sink == Sink::kPcm && gain.kind == FetchGain::kNone && spec.identity() && !place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
@@ -592,7 +604,7 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
             c.marks.run(dev, spec.encoding, total, mp.seg.data(), nseg, s);
             marks_ran = true;
         }
-        if (n_pitch > 0) c.pitch.run(dev, spec.encoding, total, ps, s);
+        if (n_pitch > 0) c.pitch.run(dev, spec.encoding, total, ps, s, track ? &ts : nullptr, track ? &c.track : nullptr);
         if (sink == Sink::kFlac) {   // the signals stay in HBM; the encoder reads the stream sizes back, then exactly the encoded bytes cross PCIe
             std::vector<int64_t> offs(outs.size());
             for (size_t i = 1; i < outs.size(); ++i) offs[i] = offs[i - 1] + outs[i - 1];
@@ -708,10 +720,16 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
 
 int32_t sbv2_voice_tile(void) { return Voice::kTile; }
 
-int sbv2_pipeline_fetch_request_voice(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice, void* dst,
-                                      int64_t capacity_bytes, int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch) {
+int sbv2_pipeline_fetch_request_tracked(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                        const sbv2_pitch_track* track, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                        sbv2_marks* marks, sbv2_pitch* pitch) {
     API_BEGIN
-    if (voice) (void)check_voice_static(voice, kNativeRate);   // what needs no run is refused before the handle is looked at
+    VoiceSpec vs;
+    if (voice) vs = check_voice_static(voice, kNativeRate);   // what needs no run is refused before the handle is looked at
+    if (track) {
+        (void)check_track_static(track);
+        SBV2_REQUIRE(pitch || (voice && !vs.identity()), "pitch tracking needs a pitch contour or a voice that is not the identity");
+    }
     SBV2_REQUIRE(req && req->n_utts >= 0 && (req->n_utts == 0 || (req->utts && req->place)), "bad fetch request");
     SBV2_REQUIRE(!(req->loudness && req->limiter), "a fetch request takes a loudness target or a limiter, not both");
     if (marks) {   // what needs no run is refused before the handle is looked at
@@ -726,8 +744,12 @@ int sbv2_pipeline_fetch_request_voice(sbv2_pipeline* p, int64_t ticket, const sb
     static const int32_t no_rows[1] = {0};
     static const int64_t no_place[1] = {0};
     fetch_formatted(p, ticket, req->fmt, gain, req->n_utts ? req->place : no_place, req->joined_len, req->flac ? Sink::kFlac : Sink::kPcm, dst,
-                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch, voice);
+                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch, voice, track);
     API_END
+}
+int sbv2_pipeline_fetch_request_voice(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice, void* dst,
+                                      int64_t capacity_bytes, int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch) {
+    return sbv2_pipeline_fetch_request_tracked(p, ticket, req, voice, nullptr, dst, capacity_bytes, out_count, stats, marks, pitch);
 }
 int sbv2_pipeline_fetch_request_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, void* dst, int64_t capacity_bytes,
                                       int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch) {

@@ -13,6 +13,7 @@
 #include "marks.h"
 #include "models.h"
 #include "pcm_format.h"
+#include "track.h"
 #include "voice.h"
 
 namespace sbv2 {
@@ -37,6 +38,7 @@ struct OutputChain {
     Marks marks;       // speech marks: levels of token spans and envelope frames (fetch_request_marks only)
     Pitch pitch;       // ... and the pitch contour of the same samples (fetch_request_pitch only)
     Voice voice;       // pitch / intonation scale of the listed rows, in front of the formatter (fetch_request_voice only)
+    Track track;       // the best path through the delivered contour's candidates (fetch_request_tracked only; the shifter has its own)
 };
 struct sbv2_pipeline {
     sbv2_bert* bert;

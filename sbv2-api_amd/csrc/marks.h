@@ -63,7 +63,15 @@ void pitch_finish(const PitchSpec& sp, int32_t lag, int32_t voiced, const double
 
 // The estimator's one launch (k_pitch_yin) into the caller's device arrays c3 [nf][3], lag [nf], voiced [nf], nf = pitch_frames(n, sp.hop);
 // x = n samples on the device (encoding as Marks::run).  n = 0 enqueues nothing.  Pitch::run and the shifter's contour (voice.hip) go through it.
-void pitch_launch(const void* x, int encoding, int64_t n, const PitchSpec& sp, double* c3, int32_t* lag, int32_t* voiced, hipStream_t s);
+// With cand (k_pitch_yin_cand): besides, every frame's candidates for the tracker (track.h) as include/sbv2_hip.h states them above
+// sbv2_pitch_track: cand [nf][kTrackRec] = ncand, 7 tau (ascending; 0 in absent slots), 7 q = llrint(c 65536); cand_c3 [nf][7][3] = c-, c0, c+
+// under the neighbour rule.  c3 / lag / voiced are the plain kernel's bits either way.
+constexpr int kTrackCand = 7, kTrackRec = 1 + 2 * kTrackCand;
+void pitch_launch(const void* x, int encoding, int64_t n, const PitchSpec& sp, double* c3, int32_t* lag, int32_t* voiced, hipStream_t s,
+                  double cand_max = 0.0, int32_t* cand = nullptr, double* cand_c3 = nullptr);
+
+struct TrackSpec;   // track.h
+class Track;
 
 // Device state of the pitch estimator of one execution context (k_pitch_yin, marks.hip): results on the device and their pinned mirror, grown
 // on demand; nothing is allocated before the first run.  One launch per run, one workgroup per frame, no atomics.
@@ -75,7 +83,9 @@ class Pitch {
     // Enqueues on s the estimator over x = n delivered samples on the device (encoding as Marks::run) and the copy of its results to the
     // host: lag_host()[f], voiced_host()[f] and c3_host()[3 f ..] = c(lag - 1), c(lag), c(lag + 1) (a neighbour outside [1, tau_max] replaced
     // by c(lag)) hold frame f < n_frames() once s has been synchronised.  n = 0 enqueues nothing.
-    void run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hipStream_t s);
+    // With tr (and tk, the tracker's state): the contour is TRACKED before the copy (track.h): two more launches, k_pitch_yin_cand instead of
+    // k_pitch_yin; lag / voiced / c3 of the frames on the path's candidates are the candidates'.
+    void run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hipStream_t s, const TrackSpec* tr = nullptr, Track* tk = nullptr);
     int64_t n_frames() const { return nf_; }
     const double* c3_host() const { return static_cast<const double*>(host_.get()); }
     const int32_t* lag_host() const { return reinterpret_cast<const int32_t*>(c3_host() + 3 * nf_); }

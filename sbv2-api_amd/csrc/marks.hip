@@ -13,6 +13,7 @@
 // Each sample is read once per table it appears in (tokens, frames): the launch is bound by its few MB of HBM reads.
 // The pitch contour of the same samples (k_pitch_yin, and k_stream_pitch for a stream's replays) is at the end of the file.
 #include "marks.h"
+#include "track.h"
 
 #include <climits>
 #include <cmath>
@@ -399,8 +400,11 @@ constexpr int kPitchMaxP = (kPitchMaxTau + kBlock - 1) / kBlock;   // lags per l
 
 // One frame, by the workgroup that owns it: `at(i)` gives the sample at delivered position i (zero outside the signal) and is the only thing
 // the one-shot kernel and the fed one (k_stream_pitch) do differently; everything behind the staging is this one body.
-template <class T, int P, class At>
-__device__ inline void pitch_frame(const At& at, int64_t b, int tau_min, int W, double threshold, double* o, int32_t* o_lag, int32_t* o_voiced) {
+// cand (CAND only): besides, the frame's candidates for the tracker (track.h), as include/sbv2_hip.h states them above sbv2_pitch_track.  Without
+// CAND nothing below exists: the body, its LDS and its results are the plain kernel's.
+template <class T, int P, class At, bool CAND = false>
+__device__ inline void pitch_frame(const At& at, int64_t b, int tau_min, int W, double threshold, double* o, int32_t* o_lag, int32_t* o_voiced,
+                                   double cand_max = 0.0, int32_t* o_cand = nullptr, double* o_cand_c3 = nullptr) {
     using S = typename PitchTypes<T>::S;
     using D = typename PitchTypes<T>::D;
     __shared__ S win[2 * kPitchMaxTau];
@@ -487,6 +491,59 @@ __device__ inline void pitch_frame(const At& at, int64_t b, int tau_min, int W, 
         *o_lag = lag;
         *o_voiced = voiced;
     }
+    if constexpr (CAND) {
+        // The dips among this thread's lags [lo, hi] (every cc[] is complete).  Round r takes the smallest (c, tau) above round r - 1's pick:
+        // nothing is marked, a thread looks at its few lags again.  The index minimum is the one of `arg` above, with every lane given the result.
+        __shared__ double sh_cc[kWavesPerBlock];
+        __shared__ int sh_ct[kWavesPerBlock];
+        __shared__ int sh_pick[kTrackCand];
+        double last_c = -1.0;
+        int last_t = 0, npick = 0;
+        for (int r = 0; r < kTrackCand; ++r) {
+            double bc = INFINITY;
+            int bt = INT_MAX;
+            for (int t = max(lo, max(tau_min, 2)); t <= hi; ++t) {   // (c(tau - 1) exists)
+                const double c = cc[t];
+                const bool dip = c < cc[t - 1] && (t + 1 > W || c <= cc[t + 1]) && c < cand_max;
+                if (dip && (c > last_c || (c == last_c && t > last_t)) && (c < bc || (c == bc && t < bt))) bc = c, bt = t;
+            }
+#pragma unroll
+            for (int s = kWave / 2; s >= 1; s >>= 1) {
+                const double oc = __shfl_xor(bc, s, kWave);
+                const int ot = __shfl_xor(bt, s, kWave);
+                if (oc < bc || (oc == bc && ot < bt)) bc = oc, bt = ot;
+            }
+            if (lane == 0) sh_cc[wave] = bc, sh_ct[wave] = bt;
+            __syncthreads();
+            for (int w = 0; w < nt / kWave; ++w)
+                if (sh_cc[w] < bc || (sh_cc[w] == bc && sh_ct[w] < bt)) bc = sh_cc[w], bt = sh_ct[w];
+            __syncthreads();   // (the next round writes sh_cc / sh_ct again)
+            if (bt == INT_MAX) break;   // (uniform) no dip is left
+            if (tid == 0) sh_pick[r] = bt;
+            last_c = bc;
+            last_t = bt;
+            npick = r + 1;
+        }
+        if (tid == 0) {   // (its own writes to sh_pick) the picks in ascending tau
+            int pick[kTrackCand];
+            for (int i = 0; i < npick; ++i) {
+                const int t = sh_pick[i];
+                int k = i;
+                for (; k > 0 && pick[k - 1] > t; --k) pick[k] = pick[k - 1];
+                pick[k] = t;
+            }
+            o_cand[0] = npick;
+            for (int i = 0; i < kTrackCand; ++i) {
+                const int t = i < npick ? pick[i] : 0;
+                const double c0 = i < npick ? cc[t] : 0.0;
+                o_cand[1 + i] = t;
+                o_cand[1 + kTrackCand + i] = i < npick ? (int32_t)llrint(c0 * 65536.0) : 0;
+                o_cand_c3[3 * i] = i < npick ? (t - 1 >= 1 ? cc[t - 1] : c0) : 0.0;
+                o_cand_c3[3 * i + 1] = c0;
+                o_cand_c3[3 * i + 2] = i < npick ? (t + 1 <= W ? cc[t + 1] : c0) : 0.0;
+            }
+        }
+    }
 }
 
 template <class T, int P>
@@ -497,6 +554,25 @@ __global__ __launch_bounds__(kBlock) void k_pitch_yin(const PitchArgs a) {
     const auto at = [x, n](int64_t i) -> S { return i >= 0 && i < n ? static_cast<S>(level_load(x, i)) : S(0); };
     const int64_t f = blockIdx.x;
     pitch_frame<T, P>(at, f * a.hop + a.hop / 2 - a.tau_max, a.tau_min, a.tau_max, a.threshold, a.c3 + 3 * f, a.lag + f, a.voiced + f);
+}
+
+// k_pitch_yin with the candidate record of every frame besides (cand [nf][15] = ncand, 7 tau, 7 q; cand_c3 [nf][7][3])
+struct PitchCandArgs {
+    PitchArgs a;
+    double cand_max;
+    int32_t* cand;
+    double* cand_c3;
+};
+template <class T, int P>
+__global__ __launch_bounds__(kBlock) void k_pitch_yin_cand(const PitchCandArgs ca) {
+    using S = typename PitchTypes<T>::S;
+    const PitchArgs& a = ca.a;
+    const T* x = static_cast<const T*>(a.x);
+    const int64_t n = a.n;
+    const auto at = [x, n](int64_t i) -> S { return i >= 0 && i < n ? static_cast<S>(level_load(x, i)) : S(0); };
+    const int64_t f = blockIdx.x;
+    pitch_frame<T, P, decltype(at), true>(at, f * a.hop + a.hop / 2 - a.tau_max, a.tau_min, a.tau_max, a.threshold, a.c3 + 3 * f, a.lag + f,
+                                          a.voiced + f, ca.cand_max, ca.cand + kTrackRec * f, ca.cand_c3 + 3 * kTrackCand * f);
 }
 
 // The fed estimator (StreamPitch, marks.h): the workgroups [0, count) take the frames first, first + 1, ... that this push completed, the
@@ -554,6 +630,10 @@ void launch_pitch(int P, dim3 grid, dim3 blk, hipStream_t s, const PitchArgs& a)
     SBV2_PITCH_LAUNCH(k_pitch_yin)
 }
 template <class T>
+void launch_pitch_cand(int P, dim3 grid, dim3 blk, hipStream_t s, const PitchCandArgs& a) {
+    SBV2_PITCH_LAUNCH(k_pitch_yin_cand)
+}
+template <class T>
 void launch_stream_pitch(int P, dim3 grid, dim3 blk, hipStream_t s, const StreamPitchArgs& a) {
     SBV2_PITCH_LAUNCH(k_stream_pitch)
 }
@@ -594,7 +674,8 @@ void pitch_finish(const PitchSpec& sp, int32_t lag, int32_t voiced, const double
     if (ap) *ap = c0;
 }
 
-void pitch_launch(const void* x, int encoding, int64_t n, const PitchSpec& sp, double* c3, int32_t* lag, int32_t* voiced, hipStream_t s) {
+void pitch_launch(const void* x, int encoding, int64_t n, const PitchSpec& sp, double* c3, int32_t* lag, int32_t* voiced, hipStream_t s,
+                  double cand_max, int32_t* cand, double* cand_c3) {
     SBV2_REQUIRE(pcm_encoding_known(encoding), "internal: pitch of an unknown encoding");
     SBV2_REQUIRE(n >= 0 && sp.hop >= 1 && sp.tau_min >= 1 && sp.tau_min <= sp.tau_max && sp.tau_max <= kPitchMaxTau, "internal: bad pitch spec");
     const int64_t nf = pitch_frames(n, sp.hop);
@@ -613,6 +694,16 @@ void pitch_launch(const void* x, int encoding, int64_t n, const PitchSpec& sp, d
     a.voiced = voiced;
     const int nt = pitch_lanes(sp.tau_max), P = (sp.tau_max + nt - 1) / nt;
     const dim3 grid((unsigned)nf), blk(nt);
+    if (cand) {   // the same frames with their candidates besides
+        SBV2_REQUIRE(cand_c3 && cand_max > 0.0 && cand_max <= 1.0, "internal: bad candidate output");
+        const PitchCandArgs ca{a, cand_max, cand, cand_c3};
+        if (encoding == kEncS16) launch_pitch_cand<int16_t>(P, grid, blk, s, ca);
+        else if (encoding == kEncMulaw) launch_pitch_cand<MulawCode>(P, grid, blk, s, ca);
+        else if (encoding == kEncAlaw) launch_pitch_cand<AlawCode>(P, grid, blk, s, ca);
+        else launch_pitch_cand<float>(P, grid, blk, s, ca);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
     if (encoding == kEncS16) launch_pitch<int16_t>(P, grid, blk, s, a);
     else if (encoding == kEncMulaw) launch_pitch<MulawCode>(P, grid, blk, s, a);
     else if (encoding == kEncAlaw) launch_pitch<AlawCode>(P, grid, blk, s, a);
@@ -620,17 +711,28 @@ void pitch_launch(const void* x, int encoding, int64_t n, const PitchSpec& sp, d
     HIP_CHECK(hipGetLastError());
 }
 
-void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hipStream_t s) {
+void Pitch::run(const void* x, int encoding, int64_t n, const PitchSpec& sp, hipStream_t s, const TrackSpec* tr, Track* tk) {
     SBV2_REQUIRE(n >= 0 && sp.hop >= 1, "internal: bad pitch spec");
+    SBV2_REQUIRE(!tr == !tk, "internal: a tracked contour needs the tracker's state");
     const int64_t nf = pitch_frames(n, sp.hop);
     SBV2_REQUIRE(nf < (1 << 30), "too many pitch frames: " + std::to_string(nf) + " >= 2^30");
     nf_ = nf;
     if (nf == 0) return;
     const size_t bytes = 32 * (size_t)nf;   // c3 (24) | lag (4) | voiced (4) per frame
+    // tracked: behind them, on the device only, the candidates' c3 (168) | their records (60) per frame
+    const size_t d_bytes = bytes + (tr ? (24 * kTrackCand + 4 * kTrackRec) * (size_t)nf : 0);
     char* h = static_cast<char*>(host_.reserve(bytes, std::max<size_t>(bytes * 2, 4096), s));
-    char* d = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes * 2, 4096), s));
+    char* d = static_cast<char*>(dev_.reserve(d_bytes, std::max<size_t>(d_bytes * 2, 4096), s));
+    double* c3 = reinterpret_cast<double*>(d);
     int32_t* lag = reinterpret_cast<int32_t*>(d + 24 * (size_t)nf);
-    pitch_launch(x, encoding, n, sp, reinterpret_cast<double*>(d), lag, lag + nf, s);
+    if (tr) {
+        double* cand_c3 = reinterpret_cast<double*>(d + bytes);
+        int32_t* cand = reinterpret_cast<int32_t*>(d + bytes + 24 * kTrackCand * (size_t)nf);
+        pitch_launch(x, encoding, n, sp, c3, lag, lag + nf, s, tr->cand_max, cand, cand_c3);
+        tk->run(cand, cand_c3, nf, *tr, c3, lag, lag + nf, s);
+    } else {
+        pitch_launch(x, encoding, n, sp, c3, lag, lag + nf, s);
+    }
     HIP_CHECK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s));
 }
 

@@ -1916,6 +1916,66 @@ int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t
     API_END
 }
 
+// The tracker (Track, track.hip) on host samples, or on the caller's candidate table alone.  Everything is checked before any device call;
+// nothing is written when the call fails.
+int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, const sbv2_pitch_track* track,
+                           const int32_t* cand_in, const double* c3_in, int64_t nf_in, int32_t* cand_out, double* c3_out, int32_t* state_out) {
+    API_BEGIN
+    (void)c3_in;   // (the path depends on tau and q alone)
+    SBV2_REQUIRE(track, "bad arguments");
+    SBV2_REQUIRE(track->reserved[0] == 0 && track->reserved[1] == 0, "sbv2_pitch_track.reserved must be 0");
+    const TrackSpec ts = track_spec(track->cand_max, track->unvoiced_cost, track->switch_cost, track->jump_cost);
+    if (cand_in) {   // the path alone
+        SBV2_REQUIRE(nf_in >= 0 && nf_in < (1 << 30) && (state_out || nf_in == 0), "bad arguments");
+        track_check_table(cand_in, nf_in);
+        HIP_CHECK(hipSetDevice(device));
+        if (nf_in == 0) return 0;
+        DevMem dc(cand_in, sizeof(int32_t) * kTrackRec * (size_t)nf_in);
+        Track tk;
+        tk.run(static_cast<const int32_t*>(dc.p), nullptr, nf_in, ts, nullptr, nullptr, nullptr, nullptr);
+        std::vector<int32_t> st((size_t)nf_in);
+        HIP_CHECK(hipMemcpyAsync(st.data(), tk.state_device(), sizeof(int32_t) * (size_t)nf_in, hipMemcpyDeviceToHost, nullptr));
+        HIP_CHECK(hipStreamSynchronize(nullptr));
+        std::memcpy(state_out, st.data(), sizeof(int32_t) * (size_t)nf_in);
+        return 0;
+    }
+    SBV2_REQUIRE(pitch && pcm_encoding_known(encoding) && n >= 0 && (x || n == 0), "bad arguments");
+    SBV2_REQUIRE(pitch->reserved == 0, "sbv2_pitch.reserved must be 0");
+    const PitchSpec sp = pitch_spec(sample_rate, pitch->hop, pitch->f0_min, pitch->f0_max, pitch->threshold);
+    const int64_t nf = pitch_frames(n, sp.hop);
+    SBV2_REQUIRE(nf < (1 << 30), "too many pitch frames: " + std::to_string(nf) + " >= 2^30");
+    SBV2_REQUIRE(pitch->capacity >= nf, "pitch arrays too small: " + std::to_string(pitch->capacity) + " < " + std::to_string(nf) + " frames");
+    SBV2_REQUIRE(pitch->f0, "sbv2_pitch.f0 must not be NULL");
+    HIP_CHECK(hipSetDevice(device));
+    if (nf > 0) {
+        const size_t F = (size_t)nf;
+        DevMem dx(x, (size_t)n * pcm_encoding_bytes(encoding));
+        DevMem dc3(24 * F), dlag(8 * F), dcc3(24 * kTrackCand * F), dcand(4 * kTrackRec * F);
+        double* c3 = static_cast<double*>(dc3.p);
+        int32_t* lag = static_cast<int32_t*>(dlag.p);
+        pitch_launch(dx.p, encoding, n, sp, c3, lag, lag + nf, nullptr, ts.cand_max, static_cast<int32_t*>(dcand.p), static_cast<double*>(dcc3.p));
+        Track tk;
+        tk.run(static_cast<const int32_t*>(dcand.p), static_cast<const double*>(dcc3.p), nf, ts, c3, lag, lag + nf, nullptr);
+        std::vector<double> hc3(3 * F), hcc3(3 * kTrackCand * F);
+        std::vector<int32_t> hlag(2 * F), hcand(kTrackRec * F), hst(F);
+        HIP_CHECK(hipMemcpyAsync(hc3.data(), c3, 24 * F, hipMemcpyDeviceToHost, nullptr));
+        HIP_CHECK(hipMemcpyAsync(hlag.data(), lag, 8 * F, hipMemcpyDeviceToHost, nullptr));
+        HIP_CHECK(hipMemcpyAsync(hcc3.data(), dcc3.p, 24 * kTrackCand * F, hipMemcpyDeviceToHost, nullptr));
+        HIP_CHECK(hipMemcpyAsync(hcand.data(), dcand.p, 4 * kTrackRec * F, hipMemcpyDeviceToHost, nullptr));
+        HIP_CHECK(hipMemcpyAsync(hst.data(), tk.state_device(), 4 * F, hipMemcpyDeviceToHost, nullptr));
+        HIP_CHECK(hipStreamSynchronize(nullptr));
+        for (int64_t f = 0; f < nf; ++f) {
+            pitch_finish(sp, hlag[f], hlag[F + f], hc3.data() + 3 * f, pitch->f0 + f, pitch->ap ? pitch->ap + f : nullptr);
+            if (pitch->lag) pitch->lag[f] = hlag[f];
+        }
+        if (cand_out) std::memcpy(cand_out, hcand.data(), 4 * kTrackRec * F);
+        if (c3_out) std::memcpy(c3_out, hcc3.data(), 24 * kTrackCand * F);
+        if (state_out) std::memcpy(state_out, hst.data(), 4 * F);
+    }
+    pitch->n_frames = nf;
+    API_END
+}
+
 // The shifter (Voice, voice.hip) on host rows laid back to back, always through its kernels; everything is checked before any device call.
 int sbv2_debug_voice_shift(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
                            const double* period_in, const int32_t* voiced_in, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts,

@@ -5,6 +5,7 @@
 #pragma once
 #include "common.h"
 #include "marks.h"
+#include "track.h"
 
 namespace sbv2 {
 
@@ -40,8 +41,9 @@ class Voice {
     // off + n) and is returned.  period_in / voiced_in (HOST, one entry per frame, rows back to back; both or neither): the contour to use
     // instead of the estimated one; a voiced entry outside [tau_min - 1, tau_max + 1] is refused.  Rows and parameters are checked before
     // anything is enqueued (throws).
+    // tr (not with a given contour): the estimated contour is tracked, every row apart from the others, before the marks are placed (track.h).
     float* run(const float* x, int64_t span, const VoiceRow* rows, int nrows, const VoiceSpec& sp, hipStream_t s, const double* period_in = nullptr,
-               const int32_t* voiced_in = nullptr);
+               const int32_t* voiced_in = nullptr, const TrackSpec* tr = nullptr);
     // Results of the last run for the test hook, valid once results_to_host() has been enqueued and s synchronised: per frame (rows back to
     // back) the period T_f and voiced; per row the marks at mark_off(i), n_a(i) analysis and n_s(i) synthesis ones.
     void results_to_host(hipStream_t s);
@@ -56,7 +58,8 @@ class Voice {
     const int32_t* map_host(int i) const { return h_map_ + cap_off_[i]; }
 
   private:
-    DeviceBuffer dev_, out_;   // tables | contour | phases | marks ; the shifted rows
+    DeviceBuffer dev_, out_;   // tables | contour | phases | marks (| the candidates of a tracked contour) ; the shifted rows
+    Track track_;
     PinnedBuffer host_;
     std::vector<int64_t> cap_off_;
     int64_t nf_ = 0, ncap_ = 0;

@@ -15,6 +15,7 @@
 #include "voice.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #pragma clang fp contract(off)
@@ -282,7 +283,7 @@ VoiceSpec voice_spec(int sample_rate, double pitch_scale, double intonation_scal
 }
 
 float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows, const VoiceSpec& sp, hipStream_t s, const double* period_in,
-                  const int32_t* voiced_in) {
+                  const int32_t* voiced_in, const TrackSpec* tr) {
     SBV2_REQUIRE(nrows >= 0 && nrows <= 65535 && span >= 0 && (nrows == 0 || rows), "voice: bad rows");
     SBV2_REQUIRE(!period_in == !voiced_in, "voice: period_in and voiced_in are given together or not at all");
     const int64_t hop = sp.pitch.hop;
@@ -316,7 +317,9 @@ float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows,
     // device: rows | c3 | period | inc_a inc_s phi_a phi_s | lag yvoiced voiced off_a off_s | count | ta ts map   (8-byte parts first)
     const size_t nF = (size_t)NF, nC = (size_t)NCAP;
     const size_t o_c3 = round_up64(sizeof(VoiceRowDev) * nrows, 64), o_period = o_c3 + 24 * nF, o_i64 = o_period + 8 * nF, o_i32 = o_i64 + 32 * nF,
-                 o_count = round_up64(o_i32 + 20 * nF, 64), o_marks = o_count + round_up64(16 * (size_t)nrows, 64), bytes = o_marks + 12 * nC;
+                 o_count = round_up64(o_i32 + 20 * nF, 64), o_marks = o_count + round_up64(16 * (size_t)nrows, 64),
+                 o_cand_c3 = round_up64(o_marks + 12 * nC, 64), o_cand = o_cand_c3 + 24 * kTrackCand * nF,
+                 bytes = tr && !period_in ? o_cand + 4 * kTrackRec * nF : o_marks + 12 * nC;
     // pinned: rows | period | voiced (the upload) ; period | voiced | count | ta ts map (the mirror)
     const size_t h_period_in = round_up64(sizeof(VoiceRowDev) * nrows, 64), h_voiced_in = h_period_in + 8 * nF, h_mirror = round_up64(h_voiced_in + 4 * nF, 64),
                  h_voiced = h_mirror + 8 * nF, h_count = round_up64(h_voiced + 4 * nF, 64), h_marks = h_count + round_up64(16 * (size_t)nrows, 64),
@@ -357,6 +360,15 @@ float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows,
         std::memcpy(h + h_voiced_in, voiced_in, 4 * nF);
         HIP_CHECK(hipMemcpyAsync(m.period, h + h_period_in, 8 * nF, hipMemcpyHostToDevice, s));
         HIP_CHECK(hipMemcpyAsync(m.voiced, h + h_voiced_in, 4 * nF, hipMemcpyHostToDevice, s));
+    } else if (tr) {   // every row's candidates besides, then one path per row through them (the rows' runs side by side)
+        double* cand_c3 = reinterpret_cast<double*>(d + o_cand_c3);
+        int32_t* cand = reinterpret_cast<int32_t*>(d + o_cand);
+        for (int i = 0; i < nrows; ++i)
+            pitch_launch(x + rd[i].off, kEncF32, rd[i].n, sp.pitch, c3 + 3 * rd[i].f_off, lag + rd[i].f_off, yvoiced + rd[i].f_off, s, tr->cand_max,
+                         cand + kTrackRec * rd[i].f_off, cand_c3 + 3 * kTrackCand * rd[i].f_off);
+        static_assert(sizeof(VoiceRowDev) % sizeof(int64_t) == 0 && offsetof(VoiceRowDev, f_off) % sizeof(int64_t) == 0, "the rows' first frames are read in place");
+        track_.run(cand, cand_c3, NF, *tr, c3, lag, yvoiced, s, reinterpret_cast<const int64_t*>(d + offsetof(VoiceRowDev, f_off)),
+                   (int)(sizeof(VoiceRowDev) / sizeof(int64_t)), nrows);
     } else {
         for (int i = 0; i < nrows; ++i)
             pitch_launch(x + rd[i].off, kEncF32, rd[i].n, sp.pitch, c3 + 3 * rd[i].f_off, lag + rd[i].f_off, yvoiced + rd[i].f_off, s);

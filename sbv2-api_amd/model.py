@@ -482,6 +482,55 @@ def debug_pitch(x, sample_rate: int, pitch: Pitch, device: int = 0, encoding: st
     return pitch.take(c, arrays), c3[:c.n_frames], voiced[:c.n_frames]
 
 
+class PitchTrack:
+    """Octave-error repair of a pitch contour (struct sbv2_pitch_track: one best path through the frames' candidates, include/sbv2_hip.h states
+    it).  cand_max in (0, 1]: a dip of c at or above it is no candidate; unvoiced_cost and switch_cost in [0, 4], jump_cost in [0, 16], all in
+    units of c.  The defaults live here only: the library takes every value as given (0 is 0) and checks the ranges."""
+
+    def __init__(self, cand_max: float = 0.5, unvoiced_cost: float = 0.30, switch_cost: float = 0.20, jump_cost: float = 1.0):
+        self.cand_max, self.unvoiced_cost = float(cand_max), float(unvoiced_cost)
+        self.switch_cost, self.jump_cost = float(switch_cost), float(jump_cost)
+
+    @property
+    def c(self):
+        return _lib.Sbv2PitchTrack(self.cand_max, self.unvoiced_cost, self.switch_cost, self.jump_cost, (C.c_int32 * 2)(0, 0))
+
+    def __repr__(self):
+        return f"PitchTrack({self.cand_max}, {self.unvoiced_cost}, {self.switch_cost}, {self.jump_cost})"
+
+
+TRACK_CAND = 7   # candidates a frame keeps; a record is (ncand, 7 tau, 7 q)
+
+
+def debug_pitch_track(x, sample_rate: int, pitch, track: PitchTrack, device: int = 0, encoding: str | None = None, cand=None):
+    """Test hook: the tracker (sbv2_debug_pitch_track).  x as for debug_pitch -> a namespace: pitch (f0 / ap / lag of the TRACKED contour), cand
+    [n][15] int32 (ncand, 7 tau, 7 q), c3 [n][7][3] (c-, c0, c+ of every candidate), state [n] (0 .. 6 the candidate, 7 unvoiced).
+    With cand (an int32 table [n][15]) the path alone is found on that table: x, sample_rate and pitch are not looked at -> state [n]."""
+    import types
+    i32p = C.POINTER(C.c_int32)
+    ct = track.c
+    if cand is not None:
+        tab = np.ascontiguousarray(np.asarray(cand, np.int32).reshape(-1, 2 * TRACK_CAND + 1))
+        state = np.zeros(max(len(tab), 1), np.int32)
+        pad = tab if len(tab) else np.zeros((1, 2 * TRACK_CAND + 1), np.int32)   # (never a NULL: NULL means "extract")
+        check(_lib.lib().sbv2_debug_pitch_track(int(device), None, 0, 0, 0, None, C.byref(ct), pad.ctypes.data_as(i32p), None, len(tab), None, None,
+                                                state.ctypes.data_as(i32p)))
+        return state[:len(tab)]
+    x = np.ascontiguousarray(x).reshape(-1)
+    if encoding is None and x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"pitch is taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"pitch of {encoding!r} samples is not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
+    c, arrays = pitch.c_struct(x.size)
+    nf = len(arrays[0])   # (at least one entry: never a NULL)
+    tab, c3, state = np.zeros((nf, 2 * TRACK_CAND + 1), np.int32), np.zeros((nf, TRACK_CAND, 3), np.float64), np.zeros(nf, np.int32)
+    check(_lib.lib().sbv2_debug_pitch_track(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size, int(sample_rate), C.byref(c),
+                                            C.byref(ct), None, None, 0, tab.ctypes.data_as(i32p), _f64p(c3), state.ctypes.data_as(i32p)))
+    n = c.n_frames
+    return types.SimpleNamespace(pitch=pitch.take(c, arrays), cand=tab[:n], c3=c3[:n], state=state[:n])
+
+
 class Voice:
     """Pitch and intonation scale of a fetched request (struct sbv2_voice: a length-preserving TD-PSOLA of the run's native rows on the device,
     include/sbv2_hip.h states it).  pitch_scale in [0.5, 2] multiplies f0, intonation_scale in [0, 2] scales its excursions about the rows' mean;
@@ -852,7 +901,7 @@ class Pipeline:
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
-                      voice=None):
+                      voice=None, track=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
@@ -863,7 +912,9 @@ class Pipeline:
         pitch: a Pitch -> a fourth element, that Pitch with the contour of the delivered signal (sbv2_pipeline_fetch_request_pitch); the third is
         None without marks.  Signal, stats and marks are those of the same call without pitch.
         voice: a Voice -> the listed rows are shifted on the device before the formatter (sbv2_pipeline_fetch_request_voice); everything else,
-        the returned shape included, is the same call on the shifted rows.  None or Voice(1, 1): exactly the call without."""
+        the returned shape included, is the same call on the shifted rows.  None or Voice(1, 1): exactly the call without.
+        track: a PitchTrack -> the contours are tracked (sbv2_pipeline_fetch_request_tracked): the delivered one (pitch) and the shifter's own
+        (a voice that shifts); it needs one of the two.  None: exactly the call without."""
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
         rw = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
@@ -880,6 +931,13 @@ class Pipeline:
         stats = np.zeros(nstats, np.float64) if nstats else None
         if pitch is not None:
             cp, parr = pitch.c_struct(pcm_format_length(fmt, int(joined_len)))
+        if track is not None:
+            ct = track.c
+            tracked = lambda *a: _lib.lib().sbv2_pipeline_fetch_request_tracked(*a[:3], C.byref(voice.c) if voice is not None else None, C.byref(ct), *a[3:])
+        if track is not None and not marks and pitch is None:
+            check(tracked(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
+                          None, None))
+            return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
         if not marks and pitch is None and voice is None:
             check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
                                                          _f64p(stats) if nstats else None))
@@ -902,7 +960,9 @@ class Pipeline:
                                 _f64p(m.env_peak) if env_hop > 0 else None, 0)
         args = (self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
                 C.byref(cm) if marks else None)
-        if voice is not None:
+        if track is not None:
+            check(tracked(*args, C.byref(cp) if pitch is not None else None))
+        elif voice is not None:
             cv = voice.c
             check(_lib.lib().sbv2_pipeline_fetch_request_voice(*args[:3], C.byref(cv), *args[3:], C.byref(cp) if pitch is not None else None))
         elif pitch is None:
@@ -979,7 +1039,11 @@ class StreamHandle:
     pieces taken so far completed, with the bits of debug_pitch over the whole delivered signal."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
-                 level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, **kw):
+                 level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, track=None,
+                 **kw):
+        if track is not None:
+            raise Sbv2Error("a stream's contour is not tracked: one best path needs every frame of the signal, and a stream hands its frames out "
+                            "as they complete; fetch the whole signal instead (Pipeline.fetch_request(track=), /synthesize, /synthesize_marks)")
         l = _lib.lib()
         self.request = isinstance(utt, (list, tuple))
         self.levels, self.env_hop, self.n_tokens, self.n_env, self._marks_buf = bool(levels), int(env_hop), 0, 0, None

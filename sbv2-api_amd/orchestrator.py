@@ -51,15 +51,27 @@ class SynthesizeOptions:
     pitch_scale in [0.5, 2] / intonation_scale in [0, 2] (new; checked here): the voice is raised or lowered, its melody flattened or
     exaggerated about its mean, by a length-preserving overlap-add of the synthesized rows on the device before anything else of the output
     chain (model.Voice); whole-signal routes only (easy_synthesize, easy_synthesize_marks, the batcher), refused on streams.  The defaults
-    1.0 / 1.0 are the calls and the bytes there always were."""
+    1.0 / 1.0 are the calls and the bytes there always were.
+    pitch_track (new; checked here): octave-error repair.  The contours the request uses (the marks' pitch_hz contour, the shifter's own) are
+    tracked across frames on the device: one best path through every frame's candidate lags (model.PitchTrack at its defaults) instead of a
+    decision per frame.  It needs pitch_hz or a pitch_scale / intonation_scale away from 1; whole-signal routes only, refused on streams (a best
+    path needs the future).  pitch_hz counts on the routes that carry a contour only: without marks (easy_synthesize, /synthesize, the batcher
+    without marks) pitch_hz itself is refused, with or without pitch_track, so tracking is never dropped in silence; there a scale away from 1 is
+    what pitch_track needs.  False is the calls and the bytes there always were."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
                  normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
-                 pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0):
+                 pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False):
         for name, v, lo, hi in (("pitch_scale", pitch_scale, 0.5, 2.0), ("intonation_scale", intonation_scale, 0.0, 2.0)):
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= v <= hi:   # (a NaN fails the comparison)
                 raise model.Sbv2Error(f"{name} must be a number in [{lo}, {hi}]: {v!r}")
         self.pitch_scale, self.intonation_scale = float(pitch_scale), float(intonation_scale)
+        if not isinstance(pitch_track, bool):
+            raise model.Sbv2Error(f"pitch_track must be true or false: {pitch_track!r}")
+        if pitch_track and pitch_hz is None and self.pitch_scale == 1.0 and self.intonation_scale == 1.0:
+            raise model.Sbv2Error("pitch_track tracks a pitch contour: it needs pitch_hz (the marks' contour) or a pitch_scale / intonation_scale "
+                                  "away from 1 (the shifter's)")
+        self.pitch_track = pitch_track
         if loudness is not None and normalize:
             raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
         if limiter and loudness is None:
@@ -237,6 +249,19 @@ def refuse_voice(options, what: str):
                               "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
 
 
+def track_options(options):
+    """The model.PitchTrack of a request (None without pitch_track: the request is then the call it always was)."""
+    return model.PitchTrack() if getattr(options, "pitch_track", False) else None
+
+
+def refuse_track(options, what: str):
+    """pitch_track where the signal leaves chunk by chunk: refused, with the routes that fetch a whole signal."""
+    if getattr(options, "pitch_track", False):
+        raise model.Sbv2Error(f"pitch_track chooses one path through all frames of a signal: {what} hands out chunks before the signal is complete, "
+                              "ask /synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks, Pipeline.fetch_request) or the batcher "
+                              "instead")
+
+
 def token_marks(utts, live, rate: int, start, end):
     """The timing part of the marks dict: utts = the request's live sentences (phones, word2ph), live = their line numbers, start / end = the
     delivered-sample spans of their tokens, sentence after sentence.  tokens: one entry per phone id (blanks included); words: one entry per
@@ -263,13 +288,14 @@ def token_marks(utts, live, rate: int, start, end):
     return {"sample_rate": int(rate), "tokens": tokens, "words": words}
 
 
-def marks_dict(utts, live, fmt, m, pitch=None) -> dict:
+def marks_dict(utts, live, fmt, m, pitch=None, tracked=False) -> dict:
     """The JSON-ready speech marks of one request from a model.Marks of its rows: token_marks plus, per token, level_dbfs (10 log10 of the mean
     square of its delivered samples re full scale; None for an empty or silent span) and peak (largest |sample| re full scale), and `envelope`
     {hop, level_dbfs [n], peak [n]} when the marks hold one.  The gaps between sentences belong to no token.
     pitch (a filled model.Pitch): `pitch` {hop, f0_hz [n] (None for an unvoiced frame), aperiodicity [n]}, and per token f0_hz (the mean over
     the voiced frames whose centre f hop + hop // 2 lies in its span; None when there is none) and voiced (the share of the frames centred in
-    its span that are voiced; 0.0 when none is centred there).  Without pitch the dict has none of these keys."""
+    its span that are voiced; 0.0 when none is centred there).  Without pitch the dict has none of these keys.
+    tracked: the contour is a tracked one (options.pitch_track): the `pitch` block says "tracked": true (the key is absent otherwise)."""
     d = token_marks(utts, live, fmt.sample_rate, m.start, m.end)
     full = model.full_scale(fmt.encoding)
     if m.sumsq is not None:
@@ -283,6 +309,8 @@ def marks_dict(utts, live, fmt, m, pitch=None) -> dict:
     if pitch is not None:
         f0 = np.asarray(pitch.f0, np.float64)
         d["pitch"] = {"hop": int(pitch.hop), "f0_hz": [float(v) if v > 0 else None for v in f0], "aperiodicity": [float(v) for v in pitch.ap]}
+        if tracked:
+            d["pitch"]["tracked"] = True
         token_pitch(d["tokens"], f0, pitch.hop)
     return d
 
@@ -308,6 +336,7 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
     lens = b.lens[r0:r1]
     voice = voice_options(options)
     vkw = {} if voice is None else {"voice": voice}   # (named only when asked for: a request at the defaults is the call it always was)
+    track = track_options(options)
     if ln is not None or not fmt.is_default or marks is not None or voice is not None:
         # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
@@ -315,13 +344,16 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
         if marks is not None:
             kw = dict(gain=ln, flac=plan.flac, marks=True, env_hop=envelope_hop(options, fmt.sample_rate), **vkw)
             pitch = pitch_options(options, fmt.sample_rate)
+            if track is not None and (pitch is not None or voice is not None):   # (likewise named only when asked for)
+                kw["track"] = track
             if pitch is None:   # (the call of a request without a contour is the call it always was)
                 out, stats, m = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw)
             else:
                 out, stats, m, pitch = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, pitch=pitch, **kw)
-            marks.append(marks_dict(plan.utts, plan.live, fmt, m, pitch))
+            marks.append(marks_dict(plan.utts, plan.live, fmt, m, pitch, **({"tracked": True} if "track" in kw and pitch is not None else {})))
         else:
-            out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, **vkw)
+            tkw = {"track": track} if track is not None and voice is not None else {}
+            out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, **vkw, **tkw)
         if stats is not None and loudness_stats is not None:
             loudness_stats.append([float(v) for v in stats])
         if plan.flac:
@@ -532,6 +564,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     last piece is out `.marks` has marks_dict's "pitch" block and the tokens' f0_hz / voiced.  Without pitch=True, pitch_hz is refused."""
     options = options or SynthesizeOptions()
     refuse_voice(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if pitch:
         if not levels:
             raise model.Sbv2Error("pitch=True on a stream comes with its speech marks: pass levels=True as well")

@@ -34,6 +34,9 @@ and error mapping, so that a client of the reference's server cannot tell the di
   pitch_scale = 1.0, intonation_scale = 1.0 (new; /synthesize and /synthesize_marks, batched or not): the voice's f0 multiplied by pitch_scale
                     ([0.5, 2]) and its excursions about the mean scaled by intonation_scale ([0, 2]), by an overlap-add of the synthesized signal
                     on the device; the signal keeps its length, so marks keep their spans.  The stream routes answer 400 for other values.
+  pitch_track = false (new; the same routes): octave-error repair.  The contours the request uses (pitch_hz's in the marks, the shifter's own)
+                    are tracked across frames on the device, one best path through every frame's candidate lags; the marks' "pitch" block then
+                    says "tracked": true.  It needs pitch_hz or a scale away from 1.  The stream routes answer 400 for true.
   POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
@@ -154,6 +157,7 @@ def make_app(holder, batching=None):
         pitch_max_hz: float = 600.0
         pitch_scale: float = 1.0            # new: multiplies the voice's f0, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); refused on the stream routes
         intonation_scale: float = 1.0       # new: scales f0's excursions about its mean, [0, 2]; the same routes
+        pitch_track: bool = False           # new: octave-error repair of the contours in use (needs pitch_hz or a scale away from 1); the same routes
 
     class SynthesizeMarksRequest(SynthesizeRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
@@ -201,7 +205,7 @@ def make_app(holder, batching=None):
                                               true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction,
                                               envelope_hz=getattr(req, "envelope_hz", None), gain_db=req.gain_db, pitch_hz=req.pitch_hz,
                                               pitch_min_hz=req.pitch_min_hz, pitch_max_hz=req.pitch_max_hz, pitch_scale=req.pitch_scale,
-                                              intonation_scale=req.intonation_scale)
+                                              intonation_scale=req.intonation_scale, **({"pitch_track": True} if getattr(req, "pitch_track", False) else {}))
 
     def synthesize(req: SynthesizeRequest):
         try:
@@ -246,9 +250,11 @@ def make_app(holder, batching=None):
                            "words": [[w["line"], w["index"], w["start"], w["end"]] for w in marks["words"]]}, separators=(",", ":"))
 
     def refuse_stream_voice(req):
-        """A 400 for pitch_scale / intonation_scale on a stream route (the request is at fault, nothing was tried), None at the defaults."""
+        """A 400 for pitch_scale / intonation_scale / pitch_track on a stream route (the request is at fault, nothing was tried), None at the
+        defaults."""
         try:
             orchestrator.refuse_voice(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=400)
         return None
