@@ -674,6 +674,21 @@ int sbv2_debug_limiter_fixed(int device, const double* x, const int64_t* lens, i
  * counts (the delivery rule), stats the 2 doubles.  level, rate and cuts are checked before any device call. */
 int sbv2_debug_limiter_stream(int device, const double* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
                               const sbv2_stream_level* level, double* out_x, int64_t* out_per_push, double* stats);
+/* Test hooks: what every launch of the meter / of the fixed-gain limiter leaves on the device, on host f64 signals laid out as for
+ * sbv2_debug_loudness.  On the device the packed input lies between NaN words (a read outside [0, total) poisons a result) and every array
+ * returned is pre-filled with the byte 0x5A (a slot no launch wrote still holds 0x5A5A5A5A5A5A5A5A); the meter / limiter runs as it is.
+ * Refused without writing anything: an unsupported rate, a bad level, a negative length, a NULL output, too small a capacity.
+ * sbv2_debug_loudness_parts (measure only): stats [nsig][3]; e and st [nseg][4] (zero-start end state and true start state of every
+ * K-weighting segment), part [nseg] (its sum of w^2), nseg <= cap_seg; bmax [ceil(total / 256)] <= cap_blk (the true-peak workgroups' maxima,
+ * 0 for one that straddles signals); peak [nsig] (the atomic maxima of the straddling workgroups, as doubles); taps [3][24] (the
+ * interpolator's phases 1..3 as the kernels get them); counts[4] = the segment length m, nseg, workgroups, pad words behind the arrays that a
+ * launch changed.
+ * sbv2_debug_limiter_parts: out_t and out_x [total] (the interpolated magnitudes and the limited signal), smin [tiles] <= cap_tiles (min s of
+ * every 1024-sample tile), taps [K] and *hsum (the Hann taps and their sum as uploaded); counts[3] = K, tiles, pad words changed. */
+int sbv2_debug_loudness_parts(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, double* stats, int64_t cap_seg,
+                              int64_t cap_blk, double* e, double* st, double* part, double* bmax, double* peak, double* taps, int64_t* counts);
+int sbv2_debug_limiter_parts(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_stream_level* level,
+                             int64_t cap_tiles, double* out_t, double* out_x, double* smin, double* taps, double* hsum, int64_t* counts);
 /* ---- new: speech marks of a stream.  Host only, valid from sbv2_stream_begin* onwards: the token spans (see sbv2_marks) of the stream's one
  * utterance at place 0 (a request stream, sbv2_stream_begin_request: of all its rows, row i at place[i], row order then token order) and at
  * the stream's delivered rate (native for sbv2_stream_begin).  Every duration is known before the first replay, so

@@ -230,6 +230,10 @@ SYMBOLS = {
                                            C.POINTER(C.c_double)]),
     "sbv2_debug_limiter_stream": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2StreamLevel), C.c_void_p, i64p,
                                             C.POINTER(C.c_double)]),
+    "sbv2_debug_loudness_parts": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.POINTER(C.c_double), C.c_int64, C.c_int64] +
+                                  [C.POINTER(C.c_double)] * 6 + [i64p]),
+    "sbv2_debug_limiter_parts": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2StreamLevel), C.c_int64] +
+                                 [C.POINTER(C.c_double)] * 5 + [i64p]),
     "sbv2_stream_begin_request": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p, i64p, i64p, C.c_int64,
                                             C.POINTER(Sbv2StreamRequest), C.POINTER(C.c_void_p), i64p]),
     "sbv2_stream_begin_request_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), i64p, i64p, i64p, C.c_int64,

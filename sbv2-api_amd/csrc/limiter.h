@@ -47,8 +47,19 @@ class Limiter {
     // (20 log10 min s, max |x|) once s has been synchronised.
     const double* run_fixed(const double* y, const std::vector<FmtSignal>& sig, int rate, const StreamLevelSpec& lv, hipStream_t s);
     const double* stats_host() const { return stats_host_; }
+    // Where the last run left what its launches read and write (device; read only; valid on its stream until the next run): the Hann taps
+    // h [K] with their sum as the kernel gets it, t and x [total], smin [tiles], each of the three followed by pad words up to the next array
+    // (smin up to `end`).  For the test hook sbv2_debug_limiter_parts.
+    struct Parts {
+        const double *h = nullptr, *t = nullptr, *x = nullptr, *smin = nullptr, *end = nullptr;
+        int64_t total = 0, tiles = 0;
+        int K = 0;
+        double hsum = 0.0;
+    };
+    const Parts& parts() const { return parts_; }
 
   private:
+    Parts parts_;
     LoudnessMeter xmeter_;   // the meter of x (its own scratch: the stats of y stay in the caller's meter)
     PinnedBuffer host_;      // signal table, Hann taps, then the stats
     DeviceBuffer dev_;

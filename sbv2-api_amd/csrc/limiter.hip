@@ -427,7 +427,9 @@ struct LimWork {
     LimState* st = nullptr;
     double *stats = nullptr, *unit = nullptr, *t = nullptr, *x = nullptr, *smin = nullptr, *stats_host = nullptr;
     const double* h = nullptr;
+    const double* end = nullptr;   // behind the per-tile minima and their pad words
 
+    Limiter::Parts parts() const { return Limiter::Parts{h, t, x, smin, end, total, tiles, K, hsum}; }
     void interp(hipStream_t s) const {
         if (total <= 0) return;
         InterpArgs a;
@@ -497,6 +499,7 @@ LimWork lim_setup(const double* y, const std::vector<FmtSignal>& sig, int rate, 
     w.t = reinterpret_cast<double*>(d + o_t);
     w.x = reinterpret_cast<double*>(d + o_x);
     w.smin = reinterpret_cast<double*>(d + o_smin);
+    w.end = reinterpret_cast<const double*>(d + dbytes);
     return w;
 }
 
@@ -512,6 +515,7 @@ const double* Limiter::run(const double* y, const std::vector<FmtSignal>& sig, i
     const double* ygain = meter.measure(y, sig, rate, scale, s);   // refuses unsupported rates
     const LimWork w = lim_setup(y, sig, rate, dev_, host_, s);
     stats_host_ = w.stats_host;
+    parts_ = w.parts();
     const double* ystats = meter.stats_dev();
     w.interp(s);
     {
@@ -568,6 +572,7 @@ int64_t stream_level_lookahead(int rate) { return window_of(rate) - 1 + kTpBack;
 const double* Limiter::run_fixed(const double* y, const std::vector<FmtSignal>& sig, int rate, const StreamLevelSpec& lv, hipStream_t s) {
     const LimWork w = lim_setup(y, sig, rate, dev_, host_, s);
     stats_host_ = w.stats_host;
+    parts_ = w.parts();
     hipLaunchKernelGGL(k_lim_fixed_init, dim3((unsigned)((w.nsig + kLanes - 1) / kLanes)), dim3(kLanes), 0, s, w.st, w.nsig, lv.gain_db,
                        std::pow(10.0, lv.gain_db / 20.0));
     w.interp(s);

@@ -38,6 +38,16 @@ class LoudnessMeter {
     const double* stats_host() const { return stats_host_; }
     // the device copy of the last measure()'s stats (valid on its stream, until the next measure())
     const double* stats_dev() const { return stats_dev_; }
+    // Where the last measure() left what its launches write (device; read only; valid like stats_dev()): e and st [nseg][4], part [nseg],
+    // bmax [nblk], peak [nsig], each followed by pad words up to the next array (the last one up to `end`), and the segment length m.  For
+    // the test hook sbv2_debug_loudness_parts.
+    struct Parts {
+        const double *e = nullptr, *st = nullptr, *part = nullptr, *bmax = nullptr, *end = nullptr;
+        const unsigned long long* peak = nullptr;
+        int64_t nseg = 0, nblk = 0;
+        int m = 0;
+    };
+    const Parts& parts() const { return parts_; }
 
   private:
     const std::vector<double>& tables(int rate);
@@ -46,6 +56,7 @@ class LoudnessMeter {
     DeviceBuffer dev_;    // signal table, peaks, stats, gains, then the per-segment states and partial sums
     double* stats_host_ = nullptr;
     double* stats_dev_ = nullptr;
+    Parts parts_;
 };
 
 }  // namespace sbv2

@@ -497,6 +497,8 @@ const double* LoudnessMeter::measure(const double* y, const std::vector<FmtSigna
     auto* stats = reinterpret_cast<double*>(d + o_stats);
     stats_dev_ = stats;
     auto* gain = reinterpret_cast<double*>(d + o_gain);
+    parts_ = Parts{reinterpret_cast<const double*>(d + o_e),    reinterpret_cast<const double*>(d + o_st), reinterpret_cast<const double*>(d + o_part),
+                   reinterpret_cast<const double*>(d + o_bmax), reinterpret_cast<const double*>(d + dbytes), peak, nseg, (total + 255) / 256, m};
     if (total > 0) {
         KwArgs a;
         a.y = y;

@@ -178,6 +178,29 @@ struct AudioScratch {
     AudioScratch& operator=(const AudioScratch&) = delete;
 };
 
+// The packed f64 input of the *_parts hooks (tests/test_loudness_limiter_kernels.py): kPad NaN words (all bits set), the total samples, kPad NaN
+// words.  The signal starts at words[kPad]; a read outside [0, total) poisons what it feeds.
+struct PoisonedSignal {
+    static constexpr size_t kPad = 64;
+    std::vector<double> words;
+    PoisonedSignal(const double* x, int64_t total) : words((size_t)total + 2 * kPad) {
+        std::memset(words.data(), 0xFF, sizeof(double) * words.size());
+        if (total) std::memcpy(words.data() + kPad, x, sizeof(double) * (size_t)total);
+    }
+};
+// the words of [a, b) that no longer hold the sentinel fill (kCtxSentinel in every byte)
+int64_t sentinel_strays(const double* a, const double* b) {
+    uint64_t sent;
+    std::memset(&sent, kCtxSentinel, 8);
+    int64_t bad = 0;
+    for (; a < b; ++a) {
+        uint64_t v;
+        std::memcpy(&v, a, 8);
+        bad += v != sent;
+    }
+    return bad;
+}
+
 // ---- the hooks of ops.h's launchers (tests/test_ops_kernels.py) ----------------------------------------------------------------------------------------
 // A host plane [C][L] on the device at the library's pitch (Arena::plane's rule: a multiple of 64 floats).  poison: the columns between L and the pitch,
 // and every column where inside[n] == 0 (inside may be null), hold NaN (all bits set) instead of zero.  Outputs are pre-filled with the sentinel; after
@@ -580,6 +603,89 @@ int sbv2_debug_limiter_fixed(int device, const double* x, const int64_t* lens, i
     if (total) HIP_CHECK(hipMemcpyAsync(out_x, lx, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, r.s));
     HIP_CHECK(hipStreamSynchronize(r.s));
     std::memcpy(stats, limiter.stats_host(), sizeof(double) * 2 * nsig);
+    API_END
+}
+
+int sbv2_debug_loudness_parts(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, double* stats, int64_t cap_seg,
+                              int64_t cap_blk, double* e, double* st, double* part, double* bmax, double* peak, double* taps, int64_t* counts) {
+    API_BEGIN
+    SBV2_REQUIRE(nsig >= 1 && lens && stats && e && st && part && bmax && peak && taps && counts, "bad arguments");
+    double coef[10];
+    loudness_kweight(sample_rate, coef);   // refuses unsupported rates
+    int64_t total = 0;
+    const std::vector<FmtSignal> sig = packed_signals(lens, nsig, &total);
+    SBV2_REQUIRE(total == 0 || x, "bad arguments");
+    SBV2_REQUIRE(cap_blk >= (total + 255) / 256, "bmax too small: " + std::to_string(cap_blk) + " < " + std::to_string((total + 255) / 256) + " workgroups");
+    PoisonedSignal src(x, total);
+    AudioScratch r(device, src.words.data(), sizeof(double) * src.words.size());
+    const double* y = r.x.as<double>() + PoisonedSignal::kPad;
+    const LoudnessSpec spec;
+    LoudnessMeter meter;
+    meter.measure(y, sig, sample_rate, spec, r.s);   // places the buffers; the run reported is the next one, at the same places
+    const LoudnessMeter::Parts p = meter.parts();
+    SBV2_REQUIRE(cap_seg >= p.nseg, "e / st / part too small: " + std::to_string(cap_seg) + " < " + std::to_string(p.nseg) + " segments");
+    HIP_CHECK(hipMemsetAsync(const_cast<double*>(p.e), kCtxSentinel, sizeof(double) * (size_t)(p.end - p.e), r.s));
+    meter.measure(y, sig, sample_rate, spec, r.s);
+    const LoudnessMeter::Parts q = meter.parts();
+    SBV2_REQUIRE(q.e == p.e && q.end == p.end && q.nseg == p.nseg && q.nblk == p.nblk, "internal: the meter moved its buffers between two equal runs");
+    std::vector<double> h((size_t)(p.end - p.e));
+    std::vector<unsigned long long> pk((size_t)nsig);
+    HIP_CHECK(hipMemcpyAsync(h.data(), p.e, sizeof(double) * h.size(), hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipMemcpyAsync(pk.data(), p.peak, 8 * (size_t)nsig, hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    const double *he = h.data(), *hst = he + (p.st - p.e), *hpart = he + (p.part - p.e), *hbmax = he + (p.bmax - p.e), *hend = he + h.size();
+    std::memcpy(stats, meter.stats_host(), sizeof(double) * 3 * nsig);
+    std::memcpy(e, he, sizeof(double) * 4 * (size_t)p.nseg);
+    std::memcpy(st, hst, sizeof(double) * 4 * (size_t)p.nseg);
+    std::memcpy(part, hpart, sizeof(double) * (size_t)p.nseg);
+    std::memcpy(bmax, hbmax, sizeof(double) * (size_t)p.nblk);
+    for (int i = 0; i < nsig; ++i) std::memcpy(peak + i, &pk[i], 8);
+    loudness_true_peak_taps(reinterpret_cast<double(*)[kTruePeakTaps]>(taps));
+    counts[0] = p.m;
+    counts[1] = p.nseg;
+    counts[2] = p.nblk;
+    counts[3] = sentinel_strays(he + 4 * p.nseg, hst) + sentinel_strays(hst + 4 * p.nseg, hpart) + sentinel_strays(hpart + p.nseg, hbmax) +
+                sentinel_strays(hbmax + p.nblk, hend);
+    API_END
+}
+
+int sbv2_debug_limiter_parts(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_stream_level* level,
+                             int64_t cap_tiles, double* out_t, double* out_x, double* smin, double* taps, double* hsum, int64_t* counts) {
+    API_BEGIN
+    SBV2_REQUIRE(nsig >= 1 && lens && out_t && out_x && smin && taps && hsum && counts, "bad arguments");
+    const StreamLevelSpec spec = stream_level_spec(level);
+    double coef[10];
+    loudness_kweight(sample_rate, coef);   // refuses unsupported rates
+    int64_t total = 0;
+    const std::vector<FmtSignal> sig = packed_signals(lens, nsig, &total);
+    SBV2_REQUIRE(total == 0 || x, "bad arguments");
+    int64_t tiles = 0;
+    for (int i = 0; i < nsig; ++i) tiles += (lens[i] + 1023) / 1024;
+    SBV2_REQUIRE(cap_tiles >= tiles, "smin too small: " + std::to_string(cap_tiles) + " < " + std::to_string(tiles) + " tiles");
+    PoisonedSignal src(x, total);
+    AudioScratch r(device, src.words.data(), sizeof(double) * src.words.size());
+    const double* y = r.x.as<double>() + PoisonedSignal::kPad;
+    Limiter limiter;
+    limiter.run_fixed(y, sig, sample_rate, spec, r.s);   // places the buffers; the run reported is the next one, at the same places
+    const Limiter::Parts p = limiter.parts();
+    SBV2_REQUIRE(p.tiles == tiles && p.total == total, "internal: the limiter's tile count");
+    HIP_CHECK(hipMemsetAsync(const_cast<double*>(p.t), kCtxSentinel, sizeof(double) * (size_t)(p.end - p.t), r.s));
+    limiter.run_fixed(y, sig, sample_rate, spec, r.s);
+    const Limiter::Parts q = limiter.parts();
+    SBV2_REQUIRE(q.t == p.t && q.end == p.end && q.h == p.h && q.K == p.K, "internal: the limiter moved its buffers between two equal runs");
+    std::vector<double> h((size_t)(p.end - p.t)), hh((size_t)p.K);
+    HIP_CHECK(hipMemcpyAsync(h.data(), p.t, sizeof(double) * h.size(), hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipMemcpyAsync(hh.data(), p.h, sizeof(double) * hh.size(), hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    const double *ht = h.data(), *hx = ht + (p.x - p.t), *hsm = ht + (p.smin - p.t), *hend = ht + h.size();
+    std::memcpy(out_t, ht, sizeof(double) * (size_t)total);
+    std::memcpy(out_x, hx, sizeof(double) * (size_t)total);
+    std::memcpy(smin, hsm, sizeof(double) * (size_t)tiles);
+    std::memcpy(taps, hh.data(), sizeof(double) * hh.size());
+    *hsum = q.hsum;
+    counts[0] = p.K;
+    counts[1] = tiles;
+    counts[2] = sentinel_strays(ht + total, hx) + sentinel_strays(hx + total, hsm) + sentinel_strays(hsm + tiles, hend);
     API_END
 }
 

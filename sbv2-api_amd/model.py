@@ -402,6 +402,44 @@ def debug_limiter_fixed(signals, sample_rate: int, level: StreamLevel, device: i
     return np.split(out[:x.size], np.cumsum(lens)[:-1]), stats
 
 
+PARTS_SENTINEL = np.frombuffer(b"\x5a" * 8, np.float64)[0]   # what the *_parts hooks fill every returned device array with before the run
+
+
+def _packed(signals):
+    sigs = [np.ascontiguousarray(np.asarray(x, np.float64)).reshape(-1) for x in signals]
+    x = np.concatenate(sigs) if sigs else np.zeros(0, np.float64)
+    return x, np.array([s.size for s in sigs], np.int64)
+
+
+def debug_loudness_parts(signals, sample_rate: int, device: int = 0):
+    """Test hook: what each launch of the device meter leaves, on host float64 signals -> dict: stats [n, 3], m (segment length), e and st
+    [nseg, 4], part [nseg], bmax [ceil(total / 256)], peak [n], taps [3, 24], strays (pad words a launch changed).  A slot of a device array
+    that no launch wrote holds PARTS_SENTINEL."""
+    x, lens = _packed(signals)
+    cap_seg, cap_blk = int(np.sum(-(-lens // 200))) + 1, -(-x.size // 256) + 1
+    stats, peak, taps, counts = np.zeros((len(lens), 3)), np.zeros(len(lens)), np.zeros((3, 24)), np.zeros(4, np.int64)
+    e, st, part, bmax = np.zeros((cap_seg, 4)), np.zeros((cap_seg, 4)), np.zeros(cap_seg), np.zeros(cap_blk)
+    check(_lib.lib().sbv2_debug_loudness_parts(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(lens),
+                                               int(sample_rate), _f64p(stats), cap_seg, cap_blk, _f64p(e), _f64p(st), _f64p(part), _f64p(bmax),
+                                               _f64p(peak), _f64p(taps), counts.ctypes.data_as(i64p)))
+    m, nseg, nblk, strays = (int(v) for v in counts)
+    return {"stats": stats, "m": m, "e": e[:nseg], "st": st[:nseg], "part": part[:nseg], "bmax": bmax[:nblk], "peak": peak, "taps": taps,
+            "strays": strays}
+
+
+def debug_limiter_parts(signals, sample_rate: int, level: StreamLevel, device: int = 0):
+    """Test hook: what each launch of the fixed-gain limiter leaves, on host float64 signals -> dict: t and x [total], smin [tiles], taps [K],
+    hsum, K, strays (pad words a launch changed).  A slot of a device array that no launch wrote holds PARTS_SENTINEL."""
+    x, lens = _packed(signals)
+    cap = int(np.sum(-(-lens // 1024))) + 1
+    t, out, smin, taps, hsum, counts = np.zeros(x.size + 1), np.zeros(x.size + 1), np.zeros(cap), np.zeros(480), np.zeros(1), np.zeros(3, np.int64)
+    check(_lib.lib().sbv2_debug_limiter_parts(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(lens),
+                                              int(sample_rate), C.byref(level.c), cap, _f64p(t), _f64p(out), _f64p(smin), _f64p(taps), _f64p(hsum),
+                                              counts.ctypes.data_as(i64p)))
+    K, tiles, strays = (int(v) for v in counts)
+    return {"t": t[:x.size], "x": out[:x.size], "smin": smin[:tiles], "taps": taps[:K], "hsum": float(hsum[0]), "K": K, "strays": strays}
+
+
 def debug_limiter_stream(x, cuts, sample_rate: int, level: StreamLevel, device: int = 0):
     """Test hook: the same limiter fed piece by piece.  The host float64 signal x is cut at the ascending sample positions `cuts` into
     len(cuts) + 1 pushes (empty ones allowed) -> (the samples each push emitted, in order; stats [2])."""
