@@ -496,12 +496,7 @@ static MarksPlan plan_marks(const sbv2_marks* m, const PcmFmtSpec& spec, const V
     mp.levels = m->tok_sumsq != nullptr;
     mp.start.resize((size_t)mp.n_tok);
     mp.end.resize((size_t)mp.n_tok);
-    int64_t e = 0;
-    for (int k = 0; k < n_utts; ++k) {
-        const int64_t o = offs[utts[k]], nt = offs[utts[k] + 1] - o;
-        marks_spans(used.data() + o, nt, vm.cfg().hop(), place[k], spec, mp.start.data() + e, mp.end.data() + e);
-        e += nt;
-    }
+    marks_spans_rows(used, offs, utts, n_utts, place, vm.cfg().hop(), spec, mp.start.data(), mp.end.data());
     mp.seg.reserve((size_t)(2 * ((mp.levels ? mp.n_tok : 0) + mp.n_env)));
     if (mp.levels)
         for (int64_t t = 0; t < mp.n_tok; ++t) mp.seg.push_back(mp.start[t]), mp.seg.push_back(mp.end[t]);

@@ -2,7 +2,7 @@
 // sbv2_pipeline_fetch_pcm_limited / _fetch_flac_limited (the limiter GainStage of PcmFormatter::run), and of the test hook
 // sbv2_debug_limiter.  The convention is the header comment of struct sbv2_limiter (include/sbv2_hip.h).  Its step 2 alone, at a gain the
 // caller fixes, is the level control of a stream (struct sbv2_stream_level): in one shot (Limiter::run_fixed) or fed piece by piece with an
-// O(K) tail carried on the device (StreamLimiter; vits.cpp stream_enqueue and the sbv2_debug_limiter_fixed / _stream hooks).
+// O(K) tail carried on the device (StreamLimiter; StreamOutput::push, stream_output.cpp, and the sbv2_debug_limiter_fixed / _stream hooks).
 #pragma once
 #include "common.h"
 #include "loudness.h"

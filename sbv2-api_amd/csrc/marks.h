@@ -15,6 +15,16 @@ inline int64_t marks_delivered(const PcmFmtSpec& s, int64_t a) { return (a * s.L
 // [start[t], end[t]) = [J(place + hop c[t]), J(place + hop c[t + 1])), c the exclusive prefix sum of d.  Throws for a negative duration,
 // hop < 1, place < 0 and positions that leave the int64 range of a L.
 void marks_spans(const int64_t* d, int64_t n, int64_t hop, int64_t place, const PcmFmtSpec& s, int64_t* start, int64_t* end);
+// The span table of n_rows rows of one forward, packed in the order given: row rows[k] (rows == nullptr: row k), whose durations are
+// used[offs[r], offs[r + 1]), placed at place[k].  The fetch's marks, sbv2_stream_marks and a stream's token levels all read this table.
+inline void marks_spans_rows(const std::vector<int64_t>& used, const std::vector<int64_t>& offs, const int32_t* rows, int64_t n_rows,
+                             const int64_t* place, int64_t hop, const PcmFmtSpec& s, int64_t* start, int64_t* end) {
+    for (int64_t k = 0, e = 0; k < n_rows; ++k) {
+        const int64_t r = rows ? rows[k] : k, nt = offs[r + 1] - offs[r];
+        marks_spans(used.data() + offs[r], nt, hop, place[k], s, start + e, end + e);
+        e += nt;
+    }
+}
 
 // Device state of the level reduction of one execution context: the segment table (pinned + device) and the results (device + pinned), grown
 // on demand; nothing is allocated before the first run.  One launch per run, no atomics: a segment's sum is formed in an order that depends

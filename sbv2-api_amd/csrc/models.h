@@ -7,6 +7,7 @@
 #include "marks.h"
 #include "ops.h"
 #include "pcm_format.h"
+#include "stream_output.h"
 
 #include <memory>
 
@@ -293,14 +294,6 @@ struct StreamTimeline {
 int64_t stream_min_gap(const PcmFmtSpec& spec);   // 2 ceil(half / L): no output sample on one side of a cut has a filter tap on the other side's row
 void stream_check_gaps(const int64_t* gap_after, int64_t n, const PcmFmtSpec& spec);
 StreamTimeline stream_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int hop, int64_t chunk_frames, const PcmFmtSpec& spec);
-// levels on a stream (sbv2_stream_levels, include/sbv2_hip.h)
-struct StreamMarksSpec {
-    bool tokens = false;
-    int64_t env_hop = 0;
-    // the pitch contour of the delivered samples (sbv2_stream_pitch): on or off independently of the levels; the spec at the stream's delivered rate
-    bool pitch = false;
-    PitchSpec pitch_spec;
-};
 struct VitsBatch {
     int n = 0;
     const int64_t* t_lens = nullptr;   // [n]
@@ -341,8 +334,8 @@ class VitsModel {
     // Streaming decode (BASELINE configs[4]) of the rows of the last forward(skip_decoder = true): the HiFi-GAN decoder runs on windows of
     // chunk_frames + 2 * stream_halo() frames, ONE hipGraph captured for that fixed shape and replayed per burst of windows; the workspace is
     // bounded by the window.  The stream's state is a global chunk list (stream_layout().calls): every row cut on its own frame grid, row after
-    // row; a replay takes the next windows of that list whatever rows they belong to.  stream_begin returns the number of calls; stream_chunk*
-    // deliver call ci (in order) into dst (host).  gap_after == nullptr: ONE row without gaps (the single-utterance streams).
+    // row; a replay takes the next windows of that list whatever rows they belong to.  stream_begin returns the number of calls; stream_next
+    // delivers call ci (in order) into dst (host).  gap_after == nullptr: ONE row without gaps (the single-utterance streams).
     // halo frames per side = the generator's receptive field (from the config: 13.4 frames -> 16 for JP-Extra, SURVEY.md §5 "Long-context")
     int stream_halo() const;
     double stream_receptive_field() const;   // frames per side, before the margin and rounding of stream_halo
@@ -357,23 +350,14 @@ class VitsModel {
     // of the same samples, fed by the same pushes (StreamPitch, marks.h), with or without the levels; in order only as well
     int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false, const StreamLevelSpec* level = nullptr,
                          const int64_t* gap_after = nullptr, const StreamMarksSpec* marks = nullptr);
-    // a stream begun with marks: its reduction (nullptr otherwise) and the samples delivered so far (what the taken calls handed out)
-    const StreamLevels* stream_marks_levels() const { return smarks_on_ ? smarks_.get() : nullptr; }
-    const StreamPitch* stream_marks_pitch() const { return spitch_on_ ? spitch_.get() : nullptr; }
-    int64_t stream_delivered() const { return sdelivered_; }
+    // the output side of the running stream when it is formatted (stream_output.h: its kind, reductions, delivered count), else nullptr
+    const StreamOutput* stream_output() const { return sformatted_ ? sout_.get() : nullptr; }
     const StreamTimeline& stream_layout() const { return stl_; }
     int64_t stream_call_bound() const;   // bytes that suffice for any one call of the running stream
-    int64_t stream_chunk(int64_t ci, float* dst_host, int64_t capacity);
-    // formatted stream: output samples of call ci -> dst_host (capacity_bytes); returns the samples written
-    int64_t stream_chunk_format(int64_t ci, void* dst_host, int64_t capacity_bytes);
-    // FLAC stream: the bytes of every frame call ci completes (the stream header before the first) -> dst_host, *n_bytes of them
-    // (possibly 0); returns the s16 samples the chunk consumed.  Chunks in order only.
-    int64_t stream_chunk_flac(int64_t ci, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes);
-    // level stream: what call ci completes -> dst_host; *n_out = samples written (bytes when FLAC; possibly 0); returns the samples
-    // of the chunk taken.  Chunks in order only.
-    int64_t stream_chunk_level(int64_t ci, void* dst_host, int64_t capacity_bytes, int64_t* n_out);
-    // level stream, after its last chunk was taken: 20 log10 min s and max |x| over the utterance
-    void stream_level_stats(double* out) const;
+    // What call ci completes -> dst_host: the chunk's f32 samples (plain), its output samples (formatted), what the limiter hands back
+    // (level: possibly nothing; `fed` = the samples of the chunk taken) or the bytes of the FLAC frames those samples complete (the stream
+    // header before the first; possibly none).  A stream that carries state from replay to replay delivers in order only.
+    StreamOutput::Taken stream_next(int64_t ci, void* dst_host, int64_t capacity_bytes);
     bool stream_graph_captured() const { return chunk_ && chunk_->exec != nullptr; }
     size_t stream_workspace_bytes() const { return (chunk_ ? chunk_->ar.capacity() : 0) + (burst_ ? burst_->ar.capacity() : 0); }
     // results of the last forward
@@ -485,13 +469,10 @@ class VitsModel {
         // chunk c + 1 is enqueued before the host waits for chunk c: two pinned host slots + events
         float* host[2] = {nullptr, nullptr};
         hipEvent_t ev[2] = {nullptr, nullptr};
-        int64_t slot_ci[2] = {-1, -1}, slot_n[2] = {0, 0};   // the first call of the replay a slot holds (-1: none), its samples
+        int64_t slot_ci[2] = {-1, -1};              // the first call of the replay a slot holds (-1: none)
         size_t host_bytes = 0;                      // capacity of each pinned slot
         int64_t fmt_cap = 0;                        // formatted stream: samples the running stream's largest replay of this plan delivers (+ A)
-        std::vector<int64_t> fmt_off[2], fmt_n[2];  // formatted stream: each window's output samples in its slot (offset, count)
-        FlacStreamEncoder::Push flac_push[2];       // FLAC stream: the slot's push (its pinned region is host[slot]) and, per window, the
-        std::vector<int> flac_fr[2];                // frames of the push it completes: [flac_fr[w], flac_fr[w + 1])
-        std::vector<int64_t> lvl_taken[2];          // level stream: the samples each window fed (fmt_off / fmt_n then hold what it was handed back)
+        StreamOutput::Slot out[2];                  // formatted stream: what each slot's replay left there, window by window
         ~ChunkPlan() {
             if (exec) (void)hipGraphExecDestroy(exec);
             if (graph) (void)hipGraphDestroy(graph);
@@ -503,22 +484,9 @@ class VitsModel {
     };
     void ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, int nwin);
     void stream_enqueue(ChunkPlan& c, int64_t c0, int slot);   // the replay of calls c0 .. c0 + nwin - 1
-    // flac_bytes: FLAC delivery; taken (level stream): receives the samples the chunk fed, the return value being what was delivered
-    int64_t stream_take(int64_t ci, void* dst_host, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes, int64_t* taken = nullptr);
     StreamTimeline stl_;                         // rows, placement and calls of the running stream
-    bool sfmt_on_ = false;                       // the running stream is formatted (stream_begin with fmt)
-    PcmFmtSpec sfmt_;
-    std::shared_ptr<PcmFormatter> sfmtr_;          // its launches: slots 0 / 1 = chunk_'s, 2 / 3 = burst_'s
-    bool sflac_on_ = false;                      // ... and encoded as FLAC replay by replay (stream_begin with flac; implies sfmt_on_)
-    std::shared_ptr<FlacStreamEncoder> sflac_;
-    bool slevel_on_ = false;                     // ... and level-controlled replay by replay (stream_begin with level; implies sfmt_on_)
-    int64_t slevel_A_ = 0;                       // its look-ahead in delivered samples (0 without a level)
-    std::shared_ptr<StreamLimiter> slim_;
-    bool smarks_on_ = false;                     // ... and its delivered samples are reduced to levels replay by replay (stream_begin with marks)
-    std::shared_ptr<StreamLevels> smarks_;
-    bool spitch_on_ = false;                     // ... and / or to a pitch contour (stream_begin with marks->pitch)
-    std::shared_ptr<StreamPitch> spitch_;
-    int64_t sdelivered_ = 0;                     // delivered samples the taken calls of a formatted stream handed out
+    bool sformatted_ = false;                    // the running stream is formatted (stream_begin with fmt) ...
+    std::shared_ptr<StreamOutput> sout_;         // ... and this is everything behind its decoder (made by the first such stream; a clone makes its own)
     bool stream_bursts_ = false;                 // the running stream uses burst_ behind its first chunk
     std::shared_ptr<ChunkPlan> chunk_, burst_;   // one window (an utterance's first chunk) / kStreamBurst windows per replay (every later one)
     Plane z_{};              // flow output of the last forward (frame-rate plane, packed layout fl_)

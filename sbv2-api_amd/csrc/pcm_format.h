@@ -82,7 +82,7 @@ struct LimiterSpec;
 
 // The gain stage of a formatting run, between the resampler and the quantiser: none (peak-normalise or not, as spec.normalize says), a
 // loudness gain from `meter` (loudness.hip), or the look-ahead limiter (limiter.hip).  A fourth kind ends the run at the stage's input: y
-// (f64) is written to a caller-given address and nothing else happens (the level control of a stream takes it from there, vits.cpp).
+// (f64) is written to a caller-given address and nothing else happens (the level control of a stream takes it from there, stream_output.cpp).
 struct GainStage {
     enum Kind { kNone, kLoudness, kLimiter, kExposeY };
     GainStage() = default;

@@ -3,7 +3,7 @@
 //
 // DeBERTa, the text encoder, the duration predictors and the flow use global attention and run whole-sequence; the HiFi-GAN decoder, 82 %
 // of the work and all of the output bytes, is purely convolutional and runs on fixed-size frame windows (chunk + 16-frame halo per side),
-// one hipGraph captured per window shape and replayed per chunk (VitsModel::stream_begin / stream_chunk, vits.cpp).  The first PCM is
+// one hipGraph captured per window shape and replayed per chunk (VitsModel::stream_begin / stream_next, vits.cpp).  The first PCM is
 // available after the flow + ONE chunk instead of after the whole decoder, and the decoder workspace is bounded by the window.
 // A request stream (sbv2_stream_begin_request) is the same over the n rows of ONE batched forward: the rows on a silent timeline, each cut into
 // chunks on its own frame grid, delivered row after row; the single-utterance streams are its n = 1 case (begin_stream below).
@@ -13,17 +13,14 @@ struct sbv2_stream {
     sbv2_bert* bert = nullptr;
     sbv2_vits* vits = nullptr;
     int64_t calls = 0, next = 0;   // the stream's calls (its rows' chunks, row after row) and the next one to deliver
-    bool formatted = false, flac = false, level = false;
     // speech marks (sbv2_stream_marks): the rows' expanded durations (row i's tokens are [offs[i], offs[i + 1])), on the host since the forward's
     // one sync, and the delivered format
     std::vector<int64_t> durations, offs;
     PcmFmtSpec spec;
-    // levels (sbv2_stream_begin_request_levels): the entries sbv2_stream_next_marks has handed out so far
-    bool levels = false;
-    int64_t tok_out = 0, env_out = 0;
-    // pitch (sbv2_stream_begin_request_pitch): the frames sbv2_stream_next_pitch has handed out so far
-    bool pitch = false;
-    int64_t pitch_out = 0;
+    // the entries sbv2_stream_next_marks and the frames sbv2_stream_next_pitch have handed out so far
+    int64_t tok_out = 0, env_out = 0, pitch_out = 0;
+    // what the stream was begun with is the model's to say: its output side, nullptr for a plain stream (native f32)
+    const StreamOutput* output() const { return vits->m->stream_output(); }
 };
 
 namespace {
@@ -49,14 +46,29 @@ void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const in
     s->durations = vits->m->used_durations();
     s->offs = vits->m->used_offs();
     if (spec) s->spec = *spec;
-    s->formatted = spec != nullptr;
-    s->flac = flac;
-    s->level = level != nullptr;
     s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after, marks);
-    s->levels = vits->m->stream_marks_levels() != nullptr;
-    s->pitch = vits->m->stream_marks_pitch() != nullptr;
     if (total_samples) *total_samples = pcm_format_out_len(s->spec, vits->m->stream_layout().joined);
     *out = s.release();
+}
+
+// The one place that refuses the wrong kind of sbv2_stream_next* call for a stream, in each call's own words and order
+enum NextKind { kNextPlain, kNextFormat, kNextFlac, kNextLevel };
+void require_kind(const sbv2_stream* s, NextKind want) {
+    const StreamOutput* o = s->output();
+    const bool level = o && o->level(), flac = o && o->flac();
+    if (want == kNextLevel) SBV2_REQUIRE(level, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
+    else SBV2_REQUIRE(!level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
+    if (want == kNextFlac) SBV2_REQUIRE(flac, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
+    else if (want != kNextLevel) SBV2_REQUIRE(!flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
+    if (want == kNextFormat) SBV2_REQUIRE(o, "this stream has no output format: take its chunks with sbv2_stream_next");
+    else if (want == kNextPlain) SBV2_REQUIRE(!o, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
+}
+// the stream's next call -> dst; all zero once the stream is complete
+StreamOutput::Taken take_next(sbv2_stream* s, void* dst, int64_t capacity_bytes) {
+    if (s->next >= s->calls) return StreamOutput::Taken{};
+    const StreamOutput::Taken t = s->vits->m->stream_next(s->next, dst, capacity_bytes);
+    s->next += 1;
+    return t;
 }
 }  // namespace
 
@@ -80,18 +92,13 @@ int sbv2_stream_begin(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch,
 int sbv2_stream_next(sbv2_stream* s, float* dst, int64_t capacity, int64_t* n) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n, "bad arguments");
-    SBV2_REQUIRE(!s->level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
-    SBV2_REQUIRE(!s->flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
-    SBV2_REQUIRE(!s->formatted, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
-    *n = 0;
-    if (s->next < s->calls) {
-        *n = s->vits->m->stream_chunk(s->next, dst, capacity);
-        s->next += 1;
-    }
+    require_kind(s, kNextPlain);
+    *n = 0;   // (also when the call below is refused)
+    *n = take_next(s, dst, capacity * (int64_t)sizeof(float)).samples;
     API_END
 }
 
-// Same as sbv2_stream_begin with the chunks leaving the device in `fmt` (formatted by one launch per decoder replay, vits.cpp stream_enqueue).
+// Same as sbv2_stream_begin with the chunks leaving the device in `fmt` (formatted by one launch per decoder replay, StreamOutput::push, stream_output.cpp).
 int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
                              const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, sbv2_stream** out, int64_t* total_samples) {
     API_BEGIN
@@ -107,14 +114,9 @@ int sbv2_stream_begin_format(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch*
 int sbv2_stream_next_format(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n, "bad arguments");
-    SBV2_REQUIRE(!s->level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
-    SBV2_REQUIRE(!s->flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
-    SBV2_REQUIRE(s->formatted, "this stream has no output format: take its chunks with sbv2_stream_next");
+    require_kind(s, kNextFormat);
     *n = 0;
-    if (s->next < s->calls) {
-        *n = s->vits->m->stream_chunk_format(s->next, dst, capacity_bytes);
-        s->next += 1;
-    }
+    *n = take_next(s, dst, capacity_bytes).samples;
     API_END
 }
 
@@ -131,7 +133,7 @@ int64_t sbv2_flac_stream_bound(const sbv2_pcm_format* fmt, int64_t chunk_native_
 }
 
 // Same as sbv2_stream_begin_format (fmt: s16, normalize 0) with the chunks' samples encoded as ONE FLAC stream on the device, replay by
-// replay (vits.cpp stream_enqueue, flac_encode.hip FlacStreamEncoder).
+// replay (StreamOutput::push, stream_output.cpp, flac_encode.hip FlacStreamEncoder).
 int sbv2_stream_begin_flac(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
                            const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, sbv2_stream** out, int64_t* total_samples) {
     API_BEGIN
@@ -148,13 +150,11 @@ int sbv2_stream_begin_flac(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* b
 int sbv2_stream_next_flac(sbv2_stream* s, uint8_t* dst, int64_t capacity_bytes, int64_t* n_bytes, int64_t* n_samples) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n_bytes && n_samples, "bad arguments");
-    SBV2_REQUIRE(!s->level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
-    SBV2_REQUIRE(s->flac, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
+    require_kind(s, kNextFlac);
     *n_bytes = *n_samples = 0;
-    if (s->next < s->calls) {
-        *n_samples = s->vits->m->stream_chunk_flac(s->next, dst, capacity_bytes, n_bytes);
-        s->next += 1;
-    }
+    const StreamOutput::Taken t = take_next(s, dst, capacity_bytes);
+    *n_bytes = t.bytes;
+    *n_samples = t.samples;
     API_END
 }
 
@@ -187,7 +187,7 @@ int64_t sbv2_stream_level_bound(const sbv2_pcm_format* fmt, int64_t chunk_native
 }
 
 // Same as sbv2_stream_begin_format (or, with flac, sbv2_stream_begin_flac) with the fixed-gain limiter of `level` between the resampler and
-// the cast / quantiser (vits.cpp stream_enqueue, limiter.hip StreamLimiter).
+// the cast / quantiser (StreamOutput::push, stream_output.cpp, limiter.hip StreamLimiter).
 int sbv2_stream_begin_level(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens,
                             const int64_t* word2ph, int64_t chunk_frames, const sbv2_pcm_format* fmt, const sbv2_stream_level* level, int flac,
                             sbv2_stream** out, int64_t* total_samples) {
@@ -208,16 +208,10 @@ int sbv2_stream_begin_level(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* 
 int sbv2_stream_next_level(sbv2_stream* s, void* dst, int64_t capacity_bytes, int64_t* n_out, int64_t* n_consumed) {
     API_BEGIN
     SBV2_REQUIRE(s && dst && n_out && n_consumed, "bad arguments");
-    SBV2_REQUIRE(s->level, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
-    if (s->next < s->calls) {
-        int64_t out = 0;
-        const int64_t taken = s->vits->m->stream_chunk_level(s->next, dst, capacity_bytes, &out);
-        *n_out = out;
-        *n_consumed = taken;
-        s->next += 1;
-    } else {
-        *n_out = *n_consumed = 0;
-    }
+    require_kind(s, kNextLevel);
+    const StreamOutput::Taken t = take_next(s, dst, capacity_bytes);
+    *n_out = s->output()->flac() ? t.bytes : t.samples;
+    *n_consumed = t.fed;
     API_END
 }
 
@@ -225,9 +219,9 @@ int sbv2_stream_next_level(sbv2_stream* s, void* dst, int64_t capacity_bytes, in
 int sbv2_stream_level_stats(sbv2_stream* s, double* stats) {
     API_BEGIN
     SBV2_REQUIRE(s && stats, "bad arguments");
-    SBV2_REQUIRE(s->level, "this stream was not begun with a level");
+    SBV2_REQUIRE(s->output() && s->output()->level(), "this stream was not begun with a level");
     SBV2_REQUIRE(s->next >= s->calls, "the level stats exist once the stream is complete: take its chunks to the end first");
-    s->vits->m->stream_level_stats(stats);
+    s->output()->level_stats(stats, s->vits->m->stream());
     API_END
 }
 
@@ -240,11 +234,8 @@ int sbv2_stream_marks(sbv2_stream* s, int64_t* tok_start, int64_t* tok_end, int6
     const int64_t n = (int64_t)s->durations.size();
     SBV2_REQUIRE(capacity >= n, "token arrays too small: " + std::to_string(capacity) + " < " + std::to_string(n) + " tokens");
     SBV2_REQUIRE(n == 0 || (tok_start && tok_end), "bad arguments");
-    const StreamTimeline& t = s->vits->m->stream_layout();
-    for (size_t i = 0; i + 1 < s->offs.size(); ++i) {
-        const int64_t o = s->offs[i];
-        marks_spans(s->durations.data() + o, s->offs[i + 1] - o, s->vits->m->cfg().hop(), t.place[i], s->spec, tok_start + o, tok_end + o);
-    }
+    marks_spans_rows(s->durations, s->offs, nullptr, (int64_t)s->offs.size() - 1, s->vits->m->stream_layout().place.data(), s->vits->m->cfg().hop(),
+                     s->spec, tok_start, tok_end);
     *n_tokens = n;
     API_END
 }
@@ -332,7 +323,7 @@ int sbv2_stream_begin_request_levels(sbv2_bert* bert, sbv2_vits* vits, const sbv
     StreamMarksSpec marks;
     const bool on = levels_spec(lv, &marks);
     begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples);
-    const StreamLevels* l = (*out)->vits->m->stream_marks_levels();
+    const StreamLevels* l = (*out)->output()->levels();
     if (n_tokens) *n_tokens = l ? l->n_tok() : 0;
     if (n_env) *n_env = l ? l->n_env() : 0;
     API_END
@@ -354,8 +345,8 @@ int sbv2_stream_begin_request_pitch(sbv2_bert* bert, sbv2_vits* vits, const sbv2
         marks.pitch = on = true;
     }
     begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples);
-    const StreamLevels* l = (*out)->vits->m->stream_marks_levels();
-    const StreamPitch* q = (*out)->vits->m->stream_marks_pitch();
+    const StreamLevels* l = (*out)->output()->levels();
+    const StreamPitch* q = (*out)->output()->pitch();
     if (n_tokens) *n_tokens = l ? l->n_tok() : 0;
     if (n_env) *n_env = l ? l->n_env() : 0;
     if (n_pitch) *n_pitch = q ? q->n_frames() : 0;
@@ -367,10 +358,9 @@ int sbv2_stream_begin_request_pitch(sbv2_bert* bert, sbv2_vits* vits, const sbv2
 int sbv2_stream_next_marks(sbv2_stream* s, sbv2_stream_marks_part* part) {
     API_BEGIN
     SBV2_REQUIRE(s && part, "bad arguments");
-    SBV2_REQUIRE(s->levels, "this stream was begun without levels: begin it with sbv2_stream_begin_request_levels");
-    const StreamLevels* l = s->vits->m->stream_marks_levels();
-    SBV2_REQUIRE(l, "internal: the stream's level reduction is gone");
-    const int64_t D = s->next >= s->calls ? l->total() : s->vits->m->stream_delivered();
+    const StreamLevels* l = s->output() ? s->output()->levels() : nullptr;
+    SBV2_REQUIRE(l, "this stream was begun without levels: begin it with sbv2_stream_begin_request_levels");
+    const int64_t D = s->next >= s->calls ? l->total() : s->output()->delivered();
     const int64_t nt = l->tok_complete(D) - s->tok_out, ne = l->env_complete(D) - s->env_out;
     SBV2_REQUIRE(part->tok_capacity >= nt, "token arrays too small: " + std::to_string(part->tok_capacity) + " < " + std::to_string(nt) + " pending tokens");
     SBV2_REQUIRE(part->env_capacity >= ne, "envelope arrays too small: " + std::to_string(part->env_capacity) + " < " + std::to_string(ne) + " pending frames");
@@ -399,10 +389,9 @@ int sbv2_stream_next_marks(sbv2_stream* s, sbv2_stream_marks_part* part) {
 int sbv2_stream_next_pitch(sbv2_stream* s, sbv2_stream_pitch_part* part) {
     API_BEGIN
     SBV2_REQUIRE(s && part, "bad arguments");
-    SBV2_REQUIRE(s->pitch, "this stream was begun without pitch: begin it with sbv2_stream_begin_request_pitch");
-    const StreamPitch* q = s->vits->m->stream_marks_pitch();
-    SBV2_REQUIRE(q, "internal: the stream's pitch estimator is gone");
-    const int64_t D = s->next >= s->calls ? q->total() : s->vits->m->stream_delivered();
+    const StreamPitch* q = s->output() ? s->output()->pitch() : nullptr;
+    SBV2_REQUIRE(q, "this stream was begun without pitch: begin it with sbv2_stream_begin_request_pitch");
+    const int64_t D = s->next >= s->calls ? q->total() : s->output()->delivered();
     const int64_t n = q->complete(D) - s->pitch_out;
     SBV2_REQUIRE(part->capacity >= n, "pitch arrays too small: " + std::to_string(part->capacity) + " < " + std::to_string(n) + " pending frames");
     SBV2_REQUIRE(n == 0 || part->f0, "NULL f0 with " + std::to_string(n) + " pending frames");

@@ -338,8 +338,8 @@ VitsModel* VitsModel::clone() const {
     c->traces_.clear();
     c->chunk_.reset();
     c->burst_.reset();
-    c->sfmtr_.reset();
-    c->sfmt_on_ = false;
+    c->sout_.reset();   // (with it the carried limiter, encoder tail and reductions: a clone's stream shares none of them)
+    c->sformatted_ = false;
     c->z_ = Plane{};
     c->trace_ = false;
     return c;
@@ -829,7 +829,7 @@ void VitsModel::forward(const VitsBatch& b) {
     trace("z", ZA, fl);
     tr.reset();
     z_ = ZA;
-    if (b.skip_decoder) {   // streaming: the caller decodes chunk by chunk (stream_begin / stream_chunk)
+    if (b.skip_decoder) {   // streaming: the caller decodes chunk by chunk (stream_begin / stream_next)
         pcm_ = nullptr;
         pcm_total_ = 0;
         pcm_lens_.assign(n, 0);
@@ -981,9 +981,7 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     SBV2_REQUIRE(gap_after || fl_.n == 1, "stream_begin without gaps needs a preceding forward of ONE utterance");
     SBV2_REQUIRE(!gap_after || fmt, "a stream over several rows is a formatted stream");
     SBV2_REQUIRE(chunk_frames >= 16 && chunk_frames <= (1 << 20), "chunk_frames must be in [16, 2^20]");
-    sfmt_on_ = sflac_on_ = slevel_on_ = smarks_on_ = spitch_on_ = false;
-    slevel_A_ = 0;
-    sdelivered_ = 0;
+    sformatted_ = false;
     SBV2_REQUIRE(!marks || fmt, "levels and pitch on a stream need an output format: begin it with the identity format (44100 Hz f32) instead of none");
     SBV2_REQUIRE(!flac || (fmt && fmt->encoding == kEncS16), "a FLAC stream needs encoding = 1 (s16): f32 samples and G.711 codes have no FLAC form");
     SBV2_REQUIRE(!level || fmt, "a level stream needs an output format");
@@ -1000,14 +998,8 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     const int64_t no_gap = 0;
     const std::vector<int64_t> frames(fl_.len.begin(), fl_.len.end());
     stl_ = stream_timeline(frames.data(), gap_after ? gap_after : &no_gap, fl_.n, cfg_.hop(), chunk_frames, fmt ? *fmt : PcmFmtSpec());
-    // (the envelope's frame count is refused here, before the stream has set up anything of its own)
-    if (marks && fmt) StreamLevels::check(nullptr, 0, marks->env_hop, pcm_format_out_len(*fmt, stl_.joined));
-    if (marks && fmt && marks->pitch) StreamPitch::check(marks->pitch_spec, pcm_format_out_len(*fmt, stl_.joined));   // (and the contour's likewise)
-    if (fmt) {
-        sfmt_ = *fmt;
-        if (!sfmtr_) sfmtr_ = std::make_shared<PcmFormatter>();
-        if (level) slevel_A_ = stream_level_lookahead(fmt->rate);   // (sizes the slots below: a replay may hand back A samples more than it fed)
-    }
+    // (the envelope's and the contour's frame counts are refused here, before the stream has set up anything of its own)
+    const int64_t A = fmt ? StreamOutput::check(*fmt, level, marks, stl_.joined) : 0;
     constexpr int burst = kStreamBurst;   // (1 / 2 / 4 / 8 / 12 / 16 windows per replay measured in round 3: 2.62 / 1.88 / 1.64 / 1.41 / 1.39 / 1.47 ms per chunk)
     static_assert(kStreamBurst <= kStreamWinMax, "a replay's window table holds kStreamWinMax windows");
     const int64_t ncalls = (int64_t)stl_.calls.size();
@@ -1026,16 +1018,16 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     }
     stream_bursts_ = want_burst;
     if (fmt) {   // pinned slots and the device output sized from the timeline: the largest replay of each plan, gaps included (+ A with a level)
-        size_t dev = 0;
+        int64_t cap = 0;
         for (ChunkPlan* c : {chunk_.get(), want_burst ? burst_.get() : nullptr}) {
             if (!c) continue;
             const bool is_burst = want_burst && c == burst_.get();   // (with bursts the single-window plan decodes call 0 only)
             int64_t most = 0;
             for (int64_t c0 = is_burst ? 1 : 0; c0 < (want_burst && !is_burst ? 1 : ncalls); c0 += c->nwin)
                 most = std::max(most, stl_.calls[std::min<int64_t>(c0 + c->nwin, ncalls) - 1].j1 - stl_.calls[c0].j0);
-            c->fmt_cap = most + slevel_A_;
-            const size_t need = flac ? FlacStreamEncoder::host_bytes(c->fmt_cap) : (size_t)c->fmt_cap * sfmt_.bytes();
-            dev = std::max(dev, (size_t)c->fmt_cap * sfmt_.bytes());
+            c->fmt_cap = most + A;
+            const size_t need = StreamOutput::slot_bytes(*fmt, flac, c->fmt_cap);
+            cap = std::max(cap, c->fmt_cap);
             if (need > c->host_bytes) {
                 HIP_CHECK(hipStreamSynchronize(stream_));
                 for (int i = 0; i < 2; ++i) {
@@ -1047,42 +1039,9 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
                 c->host_bytes = need;
             }
         }
-        const int64_t total_out = pcm_format_out_len(sfmt_, stl_.joined);
-        if (flac) {   // the replays' s16 samples go straight behind the encoder's carried tail instead (stream_enqueue)
-            if (!sflac_) sflac_ = std::make_shared<FlacStreamEncoder>();
-            sflac_->begin(sfmt_.rate, total_out, (int64_t)(dev / sfmt_.bytes()), stream_);
-            sflac_on_ = true;
-        } else {
-            sfmtr_->out_buffer(dev, stream_);
-        }
-        if (level) {   // the formatter's y goes behind the limiter's carried tail, what the limiter emits to one of the two sinks above
-            if (!slim_) slim_ = std::make_shared<StreamLimiter>();
-            slim_->begin(sfmt_.rate, total_out, (int64_t)(dev / sfmt_.bytes()), *level, stream_);
-            slevel_on_ = true;
-        }
-        if (marks && (marks->tokens || marks->env_hop > 0)) {
-            // the token spans of all rows on the delivered timeline (what sbv2_stream_marks answers) and the frames, fixed before the first replay
-            std::vector<int64_t> seg;
-            if (marks->tokens) {
-                const int64_t ntok = (int64_t)used_host_.size();
-                std::vector<int64_t> st((size_t)ntok), en((size_t)ntok);
-                for (size_t i = 0; i + 1 < used_offs_.size(); ++i) {
-                    const int64_t o = used_offs_[i];
-                    marks_spans(used_host_.data() + o, used_offs_[i + 1] - o, cfg_.hop(), stl_.place[i], sfmt_, st.data() + o, en.data() + o);
-                }
-                seg.resize((size_t)(2 * ntok));
-                for (int64_t i = 0; i < ntok; ++i) seg[2 * i] = st[i], seg[2 * i + 1] = en[i];
-            }
-            if (!smarks_) smarks_ = std::make_shared<StreamLevels>();
-            smarks_->begin(seg.data(), (int64_t)seg.size() / 2, marks->env_hop, total_out, stream_);
-            smarks_on_ = true;
-        }
-        if (marks && marks->pitch) {   // the contour of the same delivered samples: the format's rate (in the spec) and encoding
-            if (!spitch_) spitch_ = std::make_shared<StreamPitch>();
-            spitch_->begin(marks->pitch_spec, sfmt_.encoding, total_out, stream_);
-            spitch_on_ = true;
-        }
-        sfmt_on_ = true;
+        if (!sout_) sout_ = std::make_shared<StreamOutput>();
+        sout_->begin(*fmt, flac, level, marks, used_host_, used_offs_, stl_.place.data(), cfg_.hop(), stl_.joined, cap, stream_);
+        sformatted_ = true;
     }
     stream_enqueue(*chunk_, 0, 0);                 // the first chunk starts right behind the flow ...
     if (want_burst) stream_enqueue(*burst_, 1, 0); // ... and the first burst right behind it
@@ -1113,211 +1072,67 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
         else run_decoder(c.ar, c.zin, c.lay, c.cond);
         c.pcm = pcm_;
     }
-    int64_t total = 0;
-    const bool last = c0 + c.nwin >= ncalls;
-    if (sfmt_on_) {
+    if (sformatted_) {
         // ONE formatting launch over the replay's windows: window w holds native samples [(f0 - halo) hop, (f0 - halo + W) hop) of its row, which
         // lies at place[row] of the joined timeline; the piece is that PCM clipped to the row (the decoder's output outside a row is not silence);
         // the call emits the output samples [j0, j1) of the timeline (stream_timeline: its chunk, and with a row's first / last chunk the half gaps)
         std::vector<FmtPiece> pieces;
         std::vector<FmtSignal> sig;
-        c.fmt_off[slot].clear();
-        c.fmt_n[slot].clear();
+        int64_t total = 0;
         for (int w = 0; w < live; ++w) {
             const StreamCall& k = stl_.calls[c0 + w];
             const int64_t r0 = stl_.place[k.row], r1 = r0 + stl_.len[k.row];
             const int64_t ws = r0 + (k.f0 - halo) * hop, lo = std::max<int64_t>(r0, ws), hi = std::min<int64_t>(r1, ws + (int64_t)c.W * hop);
             pieces.push_back(FmtPiece{c.pcm + (size_t)w * c.W * hop + (lo - ws), lo, hi - lo});
             sig.push_back(FmtSignal{k.j0, k.j1, total, w, w + 1});
-            c.fmt_off[slot].push_back(total);
-            c.fmt_n[slot].push_back(k.j1 - k.j0);
             total += k.j1 - k.j0;
         }
-        SBV2_REQUIRE(total + (slevel_on_ ? slevel_A_ : 0) <= c.fmt_cap, "internal: a replay of " + std::to_string(total) + " samples exceeds the slot sized for " +
-                                                                            std::to_string(c.fmt_cap));
-        const size_t dev_bytes = (size_t)c.fmt_cap * sfmt_.bytes();
-        if (slevel_on_) {
-            // ONE level push per replay: y (f64) behind the limiter's carried tail, then the samples the push completes through the cast /
-            // quantiser.  With S samples fed up to a window's end the stream has emitted max(0, S - A), the request's last window
-            // everything: window w is handed the samples between its predecessor's count and its own.
-            const int64_t fed0 = sig.empty() ? 0 : sig[0].j0, e0 = slim_->emitted_after(fed0, false);
-            SBV2_REQUIRE(fed0 == slim_->fed(), "internal: a level replay out of stream order (" + std::to_string(fed0) + " samples before it, " +
-                                                   std::to_string(slim_->fed()) + " fed)");
-            sfmtr_->run(sfmt_, pieces, sig, total, nullptr, (&c == burst_.get() ? 2 : 0) + slot, stream_, GainStage(slim_->dst()));
-            const int64_t em = slim_->push(total, last, slim_->out_buffer(), stream_);
-            c.lvl_taken[slot] = c.fmt_n[slot];
-            int64_t at = e0;
-            for (size_t w = 0; w < sig.size(); ++w) {
-                const int64_t upto = slim_->emitted_after(sig[w].j1, last && w + 1 == sig.size());
-                c.fmt_off[slot][w] = at - e0;
-                c.fmt_n[slot][w] = upto - at;
-                at = upto;
-            }
-            SBV2_REQUIRE(at - e0 == em, "internal: the level stream's counts disagree");
-            total = em;
-            void* dev = sflac_on_ ? static_cast<void*>(sflac_->dst()) : sfmtr_->out_buffer(dev_bytes, stream_);
-            pcm_cast(slim_->out_buffer(), em, slim_->unit(), sfmt_.encoding, dev, stream_);
-            if (smarks_on_) smarks_->push(dev, sfmt_.encoding, e0, em, stream_);   // (before the encoder's push moves its tail)
-            if (spitch_on_) spitch_->push(dev, e0, em, stream_);                    // (likewise)
-            if (sflac_on_) {
-                const int64_t t0 = sflac_->tail();
-                c.flac_push[slot] = sflac_->push(em, last, c.host[slot], stream_);
-                c.flac_fr[slot].assign(1, 0);
-                for (size_t w = 0; w < c.fmt_n[slot].size(); ++w) {
-                    const int64_t upto = t0 + c.fmt_off[slot][w] + c.fmt_n[slot][w];
-                    c.flac_fr[slot].push_back(w + 1 == c.fmt_n[slot].size() ? c.flac_push[slot].frames : (int)(upto / kFlacBlock));
-                }
-            } else if (em) {
-                HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)em * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
-            }
-        } else if (sflac_on_) {
-            // ONE push per replay: the formatter writes behind the carried tail, the encoder packs every block that completes (with the
-            // request's last chunk also the short final frame).  Window w completes frames [flac_fr[w], flac_fr[w + 1]) of the push.
-            const int64_t t0 = sflac_->tail();
-            sfmtr_->run(sfmt_, pieces, sig, total, sflac_->dst(), (&c == burst_.get() ? 2 : 0) + slot, stream_);
-            if (smarks_on_) smarks_->push(sflac_->dst(), sfmt_.encoding, sig.empty() ? smarks_->fed() : sig[0].j0, total, stream_);   // (before the push moves the tail)
-            if (spitch_on_) spitch_->push(sflac_->dst(), sig.empty() ? spitch_->fed() : sig[0].j0, total, stream_);                  // (likewise)
-            c.flac_push[slot] = sflac_->push(total, last, c.host[slot], stream_);
-            c.flac_fr[slot].assign(1, 0);
-            for (size_t w = 0; w < c.fmt_n[slot].size(); ++w) {
-                const int64_t upto = t0 + c.fmt_off[slot][w] + c.fmt_n[slot][w];
-                c.flac_fr[slot].push_back(w + 1 == c.fmt_n[slot].size() ? c.flac_push[slot].frames : (int)(upto / kFlacBlock));
-            }
-        } else {
-            void* dev = sfmtr_->out_buffer(dev_bytes, stream_);
-            sfmtr_->run(sfmt_, pieces, sig, total, dev, (&c == burst_.get() ? 2 : 0) + slot, stream_);
-            if (smarks_on_) smarks_->push(dev, sfmt_.encoding, sig.empty() ? smarks_->fed() : sig[0].j0, total, stream_);
-            if (spitch_on_) spitch_->push(dev, sig.empty() ? spitch_->fed() : sig[0].j0, total, stream_);
-            if (total) HIP_CHECK(hipMemcpyAsync(c.host[slot], dev, (size_t)total * sfmt_.bytes(), hipMemcpyDeviceToHost, stream_));
+        // ... and everything behind it, sink included (StreamOutput::push); the formatter's table slots: 0 / 1 = chunk_'s, 2 / 3 = burst_'s
+        sout_->push(pieces, sig, total, c0 + c.nwin >= ncalls, (&c == burst_.get() ? 2 : 0) + slot, c.host[slot], c.fmt_cap, c.out[slot], stream_);
+    } else {
+        for (int w = 0; w < live; ++w) {   // a plain stream: one row at place 0, the windows' centres as they are
+            const StreamCall& k = stl_.calls[c0 + w];
+            HIP_CHECK(hipMemcpyAsync(c.host[slot] + (size_t)w * c.chunk * hop, c.pcm + ((size_t)w * c.W + halo) * hop, sizeof(float) * (size_t)(k.j1 - k.j0),
+                                     hipMemcpyDeviceToHost, stream_));
         }
-        HIP_CHECK(hipEventRecord(c.ev[slot], stream_));
-        c.slot_ci[slot] = c0;
-        c.slot_n[slot] = total;
-        return;
-    }
-    for (int w = 0; w < live; ++w) {   // a plain stream: one row at place 0, the windows' centres as they are
-        const StreamCall& k = stl_.calls[c0 + w];
-        const int64_t nsamp = k.j1 - k.j0;
-        HIP_CHECK(hipMemcpyAsync(c.host[slot] + (size_t)w * c.chunk * hop, c.pcm + ((size_t)w * c.W + halo) * hop, sizeof(float) * (size_t)nsamp,
-                                 hipMemcpyDeviceToHost, stream_));
-        total += nsamp;
     }
     HIP_CHECK(hipEventRecord(c.ev[slot], stream_));
     c.slot_ci[slot] = c0;
-    c.slot_n[slot] = total;
-}
-
-int64_t VitsModel::stream_chunk(int64_t ci, float* dst_host, int64_t capacity) {
-    SBV2_REQUIRE(!sfmt_on_, "this stream was begun with an output format: take its chunks with sbv2_stream_next_format");
-    return stream_take(ci, dst_host, capacity * (int64_t)sizeof(float), false, nullptr);
-}
-
-int64_t VitsModel::stream_chunk_format(int64_t ci, void* dst_host, int64_t capacity_bytes) {
-    SBV2_REQUIRE(sfmt_on_, "this stream has no output format: take its chunks with sbv2_stream_next");
-    SBV2_REQUIRE(!slevel_on_, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
-    SBV2_REQUIRE(!sflac_on_, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
-    return stream_take(ci, dst_host, capacity_bytes, true, nullptr);
-}
-
-int64_t VitsModel::stream_chunk_flac(int64_t ci, uint8_t* dst_host, int64_t capacity_bytes, int64_t* n_bytes) {
-    SBV2_REQUIRE(!slevel_on_, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
-    SBV2_REQUIRE(sflac_on_, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
-    return stream_take(ci, dst_host, capacity_bytes, true, n_bytes);
-}
-
-int64_t VitsModel::stream_chunk_level(int64_t ci, void* dst_host, int64_t capacity_bytes, int64_t* n_out) {
-    SBV2_REQUIRE(slevel_on_, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
-    int64_t taken = 0, bytes = 0;
-    const int64_t n = stream_take(ci, dst_host, capacity_bytes, true, sflac_on_ ? &bytes : nullptr, &taken);
-    *n_out = sflac_on_ ? bytes : n;
-    return taken;
-}
-
-void VitsModel::stream_level_stats(double* out) const {
-    SBV2_REQUIRE(slevel_on_ && slim_, "this stream was not begun with a level");
-    HIP_CHECK(hipStreamSynchronize(stream_));
-    slim_->stats(out);
 }
 
 int64_t VitsModel::stream_call_bound() const {
     int64_t most = 0;
     for (const StreamCall& k : stl_.calls) most = std::max(most, k.j1 - k.j0);
-    if (!sfmt_on_) return most * (int64_t)sizeof(float);
-    most += slevel_on_ ? slevel_A_ : 0;
-    return sflac_on_ ? flac_stream_bound(most) : most * sfmt_.bytes();
+    return sformatted_ ? sout_->call_bound(most) : most * (int64_t)sizeof(float);
 }
 
-int64_t VitsModel::stream_take(int64_t ci, void* dst, int64_t capacity_bytes, bool formatted, int64_t* flac_bytes, int64_t* taken) {
+StreamOutput::Taken VitsModel::stream_next(int64_t ci, void* dst, int64_t capacity_bytes) {
     HIP_CHECK(hipSetDevice(device_));
     const int64_t ncalls = (int64_t)stl_.calls.size();
     SBV2_REQUIRE(chunk_ && z_.p && ncalls > 0, "stream_chunk without stream_begin");
-    ChunkPlan& c1 = *chunk_;
     SBV2_REQUIRE(ci >= 0 && ci < ncalls, "chunk out of range");
-    const int hop = cfg_.hop();
-    const int64_t nsamp = stl_.calls[ci].j1 - stl_.calls[ci].j0;
-    const int64_t esz = formatted ? sfmt_.bytes() : (int64_t)sizeof(float);
-    SBV2_REQUIRE(formatted || capacity_bytes >= nsamp * esz, "PCM buffer too small for the chunk");
-    char* dst_host = static_cast<char*>(dst);
-    // formatted: window w of the slot's replay -> its recorded output range
-    auto deliver = [&](ChunkPlan& c, int slot, int64_t w) -> int64_t {
-        if (!formatted) {
-            std::memcpy(dst_host, c.host[slot] + (size_t)w * c1.chunk * hop, sizeof(float) * (size_t)nsamp);
-            return nsamp;
-        }
-        SBV2_REQUIRE(w < (int64_t)c.fmt_n[slot].size(), "formatted chunk missing from its replay");
-        const int64_t n = c.fmt_n[slot][w];
-        if (flac_bytes) {
-            // the frames this window completed, the stream header in front of the request's first ones.  Too small a buffer is refused before
-            // anything is written or marked as taken: the call can be repeated.
-            const FlacStreamEncoder::Push& p = c.flac_push[slot];
-            const int fa = c.flac_fr[slot][w], fb = c.flac_fr[slot][w + 1];
-            const int64_t head = ci == 0 ? kFlacStreamHeader : 0, nb = p.size(fa, fb);
-            SBV2_REQUIRE(capacity_bytes >= head + nb, "FLAC buffer too small for the chunk: " + std::to_string(capacity_bytes) + " < " +
-                                                          std::to_string(head + nb) + " bytes (sbv2_flac_stream_bound always suffices)");
-            uint8_t* o = reinterpret_cast<uint8_t*>(dst_host);
-            if (head) sflac_->header(o);
-            if (nb) std::memcpy(o + head, p.bytes + p.pre[fa], (size_t)nb);
-            *flac_bytes = head + nb;
-            if (taken) *taken = c.lvl_taken[slot][w];
-            return n;
-        }
-        SBV2_REQUIRE(capacity_bytes >= n * esz, "PCM buffer too small for the chunk: " + std::to_string(capacity_bytes) + " < " + std::to_string(n * esz) + " bytes");
-        if (n) std::memcpy(dst_host, reinterpret_cast<const char*>(c.host[slot]) + (size_t)c.fmt_off[slot][w] * esz, (size_t)(n * esz));
-        if (taken) *taken = c.lvl_taken[slot][w];
-        return n;
-    };
-    const bool bursts = stream_bursts_ && burst_ && burst_->chunk == c1.chunk;
-    if (ci == 0 || !bursts) {
-        // the single-window plan: the request's first chunk (and everything when bursts are off); the next chunk runs while this one is delivered
-        const int slot = (int)(ci & 1);
-        SBV2_REQUIRE(!slevel_on_ || c1.slot_ci[slot] == ci, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
-        SBV2_REQUIRE(!flac_bytes || c1.slot_ci[slot] == ci, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
-        SBV2_REQUIRE(!smarks_on_ || c1.slot_ci[slot] == ci, "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk");
-        SBV2_REQUIRE(!spitch_on_ || c1.slot_ci[slot] == ci, "a stream with pitch delivers its chunks in order only: the estimator carries the last samples from chunk to chunk");
-        if (c1.slot_ci[slot] != ci) stream_enqueue(c1, ci, slot);                                  // (random access: not the streaming order)
-        if (!bursts && ci + 1 < ncalls && c1.slot_ci[slot ^ 1] != ci + 1) stream_enqueue(c1, ci + 1, slot ^ 1);
-        HIP_CHECK(hipEventSynchronize(c1.ev[slot]));
-        const int64_t n = deliver(c1, slot, 0);
-        c1.slot_ci[slot] = -1;
-        if (formatted) sdelivered_ += n;
-        return n;
+    const int64_t nsamp = stl_.calls[ci].j1 - stl_.calls[ci].j0, nbytes = nsamp * (int64_t)sizeof(float);
+    SBV2_REQUIRE(sformatted_ || capacity_bytes >= nbytes, "PCM buffer too small for the chunk");
+    // The replay that holds call ci: window w of the replay of calls c0 .. on plan c.  The single-window plan has the request's first chunk
+    // (and everything when bursts are off) and runs the next chunk while this one is delivered; the burst plan has every later chunk and
+    // decodes the following burst while the first window of this one is delivered (that burst's slot was drained one burst ago).
+    const bool bursts = stream_bursts_ && burst_ && burst_->chunk == chunk_->chunk;
+    const bool single = ci == 0 || !bursts;
+    ChunkPlan& c = single ? *chunk_ : *burst_;
+    const int64_t w = single ? 0 : (ci - 1) % c.nwin, c0 = ci - w, next = c0 + c.nwin;
+    const int slot = (int)((c0 / c.nwin) & 1);
+    if (c.slot_ci[slot] != c0) {   // random access, not the streaming order: refused where anything is carried from replay to replay
+        const char* carried = sformatted_ ? sout_->ordered() : nullptr;
+        SBV2_REQUIRE(!carried, carried);
+        stream_enqueue(c, c0, slot);
     }
-    ChunkPlan& cb = *burst_;
-    const int64_t bi = (ci - 1) / cb.nwin, within = (ci - 1) % cb.nwin;
-    const int64_t b0 = 1 + bi * cb.nwin;      // first call of this chunk's burst
-    const int slot = (int)(bi & 1);
-    SBV2_REQUIRE(!slevel_on_ || cb.slot_ci[slot] == b0, "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk");
-    SBV2_REQUIRE(!flac_bytes || cb.slot_ci[slot] == b0, "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk");
-    SBV2_REQUIRE(!smarks_on_ || cb.slot_ci[slot] == b0, "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk");
-    SBV2_REQUIRE(!spitch_on_ || cb.slot_ci[slot] == b0, "a stream with pitch delivers its chunks in order only: the estimator carries the last samples from chunk to chunk");
-    if (cb.slot_ci[slot] != b0) stream_enqueue(cb, b0, slot);                                    // (random access)
-    // the following burst is decoded while this one is delivered (its slot was drained one burst ago)
-    const int64_t n0 = b0 + cb.nwin;
-    if (within == 0 && n0 < ncalls && cb.slot_ci[slot ^ 1] != n0) stream_enqueue(cb, n0, slot ^ 1);
-    HIP_CHECK(hipEventSynchronize(cb.ev[slot]));
-    const int64_t n = deliver(cb, slot, within);
-    if (formatted) sdelivered_ += n;
-    return n;
+    if ((single ? !bursts : w == 0) && next < ncalls && c.slot_ci[slot ^ 1] != next) stream_enqueue(c, next, slot ^ 1);
+    HIP_CHECK(hipEventSynchronize(c.ev[slot]));
+    StreamOutput::Taken t{nsamp, nbytes, nsamp};
+    if (sformatted_) t = sout_->deliver(c.out[slot], w, ci, dst, capacity_bytes);
+    else std::memcpy(dst, c.host[slot] + (size_t)w * c.chunk * cfg_.hop(), (size_t)nbytes);
+    if (single) c.slot_ci[slot] = -1;
+    return t;
 }
 
 void VitsModel::copy_pcm(float* host) {
