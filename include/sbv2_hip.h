@@ -522,6 +522,57 @@ int sbv2_pipeline_fetch_request_tracked(sbv2_pipeline* p, int64_t ticket, const 
 int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, const sbv2_pitch_track* track,
                            const int32_t* cand_in, const double* c3_in, int64_t nf_in, int32_t* cand_out, double* c3_out, int32_t* state_out);
 
+/* ---- new: a speech compressor in front of the loudness stage.  Speech cannot always reach the loudness target it is asked for: its
+ * peak-to-loudness ratio is near 20 dB, and the limiter's depth is used up before a loud target is met.  The compressor evens out the level
+ * differences between syllables and between the sentences of a joined request, so that the limiter behind it is left with the crest only.
+ * Per output signal y[0 .. N) at fs, all in f64: the formatter's y before any gain, the array the limiter reads.
+ *   L = the integrated loudness of y (the meter of sbv2_loudness).  If L = -inf, N = 0 or ratio == 1 the signal is idle: yc = y bit for bit.
+ *   e[n] = the envelope of sbv2_limiter step 1 (computed by the limiter's own code).
+ *   Static curve.  T = L + threshold_lu, k = 1 - 1 / ratio; d[n] = k (20 log10 e[n] - T) where e[n] > 0 and that value is > 0, else 0;
+ *     dq[n] = llrint(65536 d[n]) (int64; the unit is 1 / 65536 dB, as in sbv2_pitch_track).
+ *   Ballistics, in integers, so that no order of evaluation matters.  rho = max(1, llrint(65536 release_db_per_s / fs)),
+ *     alpha = max(1, llrint(65536 attack_db_per_s / fs));
+ *     p[n] = max_{i <= n} (dq[i] - rho (n - i)): hold, then a release that is linear in dB (sequentially p[n] = max(dq[n], p[n - 1] - rho));
+ *     a[n] = max_{i >= n} (dq[i] - alpha (i - n)): the attack ramp AHEAD of a peak (the whole signal is at hand: the stage is not causal);
+ *     u[n] = max(p[n], a[n]).  Hence p[n] = prefixmax(dq[i] + rho i)[n] - rho n and a[n] = suffixmax(dq[i] - alpha i)[n] + alpha n: two
+ *     plain maximum scans of int64 keys below 2^46.
+ *   Smoothing with the limiter's window.  K = fs div 100, h[k] = sin^2(pi (k + 0.5) / K) scaled to sum to 1, c0 = K - 1 - K div 2;
+ *     ut[n] = sum_{k < K} h[k] double(u[clamp(n + c0 - k, 0, N - 1)]) / 65536, summed in ascending k and never contracted;
+ *     s[n] = 10^(-ut[n] / 20); yc[n] = y[n] s[n].
+ *   Hence: 0 < s <= 1, so |yc| <= |y| and the stage cannot create clipping; scans and windows never cross a signal edge; the smoothed
+ *   curve may sit below d at an isolated peak, by about alpha K / 4 units: the stage LEVELS the signal, it does not bound it (the limiter
+ *   behind it bounds); the knee is hard and the detector reads peaks (the envelope), not a mean square.  The crest factor stays: on
+ *   speech-like signals the peak-to-loudness ratio falls from about 21 to about 17 dB, not further.
+ *   stats, 3 doubles per signal: L of y, T, and -max ut (the deepest compression in dB; <= 0, 0 when idle).  The 3 or 6 stats of the
+ *   loudness or limiter stage behind are then those of yc: everything behind the stage (meter, gain, limiter, cast, quantisers, FLAC, the
+ *   marks' levels and pitch) runs unchanged on the compressed signal.
+ * Parameters: 0 never means "default" and a NaN is refused.  Usual values 8, 4, 600, 60.
+ * Not built: the stage on streams (the threshold needs the whole signal's loudness and the attack looks ahead without bound), on sbv2_node_*
+ *   and on the six older formatted fetches; a soft knee, an RMS detector, several bands. */
+typedef struct sbv2_dynamics {
+    double threshold_lu;        /* [0, 30]: dB above the signal's own integrated loudness */
+    double ratio;               /* [1, 20]; 1 = identity */
+    double attack_db_per_s;     /* [10, 10000] */
+    double release_db_per_s;    /* [1, 1000] */
+    double reserved;            /* must be 0 */
+} sbv2_dynamics;
+/* sbv2_pipeline_fetch_request_tracked with the compressor in front of req's loudness gain or limiter.  dynamics == NULL or ratio == 1 is
+ * exactly that call: no launch, the same bytes, and dyn_stats is not written.  Otherwise dyn_stats (may be NULL) receives the 3 doubles above
+ * and stats (NULL, or 3 / 6 doubles) those of the stage behind, of yc.  The run's PCM is only read: two fetches of one ticket give identical
+ * bytes and stats.  Refused with nothing written: a compressing dynamics with neither req->loudness nor req->limiter (without make-up the
+ * stage only makes the signal quieter) or with fmt->normalize, fields out of range or non-finite (ratio == 1 included), a non-zero
+ * reserved, and everything that call refuses. */
+int sbv2_pipeline_fetch_request_dynamics(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                         const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, void* dst, int64_t capacity_bytes,
+                                         int64_t* out_count, double* stats, double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch);
+/* Samples per workgroup of the compressor's scans (tests place signal lengths around it). */
+int32_t sbv2_dynamics_tile(void);
+/* Test hook: the compressor on host f64 signals laid back to back (as sbv2_debug_limiter), always through the kernels (ratio == 1
+ * included).  Outputs, each laid out as the input and each may be NULL: e_out, dq_out (int64), u_out (int64), s_out, y_out (yc); stats 3
+ * doubles per signal. */
+int sbv2_debug_dynamics(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_dynamics* dynamics,
+                        double* e_out, int64_t* dq_out, int64_t* u_out, double* s_out, double* y_out, double* stats);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,

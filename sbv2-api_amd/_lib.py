@@ -34,6 +34,12 @@ class Sbv2Limiter(C.Structure):
     _fields_ = [("target_lufs", C.c_double), ("true_peak_max_dbtp", C.c_double), ("max_reduction_db", C.c_double), ("reserved", C.c_double)]
 
 
+class Sbv2Dynamics(C.Structure):
+    """struct sbv2_dynamics (include/sbv2_hip.h)."""
+    _fields_ = [("threshold_lu", C.c_double), ("ratio", C.c_double), ("attack_db_per_s", C.c_double), ("release_db_per_s", C.c_double),
+                ("reserved", C.c_double)]
+
+
 class Sbv2StreamLevel(C.Structure):
     """struct sbv2_stream_level (include/sbv2_hip.h)."""
     _fields_ = [("gain_db", C.c_double), ("true_peak_max_dbtp", C.c_double), ("reserved", C.c_double * 2)]
@@ -152,6 +158,12 @@ SYMBOLS = {
     "sbv2_pipeline_fetch_request_tracked": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
                                                       C.POINTER(Sbv2PitchTrack), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
                                                       C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_pipeline_fetch_request_dynamics": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                       C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.c_void_p, C.c_int64, i64p,
+                                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_dynamics_tile": (C.c_int32, []),
+    "sbv2_debug_dynamics": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Dynamics), C.POINTER(C.c_double), i64p, i64p,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "sbv2_debug_pitch_track": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2Pitch), C.POINTER(Sbv2PitchTrack),
                                          C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                          C.POINTER(C.c_int32)]),

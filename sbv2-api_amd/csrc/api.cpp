@@ -449,6 +449,7 @@ struct FetchGain {
     enum Kind { kNone, kLoudness, kLimiter } kind = kNone;
     const sbv2_loudness* ln = nullptr;
     const sbv2_limiter* lim = nullptr;
+    const sbv2_dynamics* dyn = nullptr;   // the compressor in front of either stage (NULL or ratio == 1: none)
     int stats_per_signal() const { return kind == kLimiter ? 6 : kind == kLoudness ? 3 : 0; }
 };
 enum class Sink { kPcm, kFlac };
@@ -536,10 +537,13 @@ static TrackSpec check_track_static(const sbv2_pitch_track* t) {
 // voice (with utts; NULL or the identity: nothing): the listed rows are shifted first (Voice, voice.h) into the chain's scratch buffer, laid out
 // like the run's packed PCM, and the pieces point there; the run's PCM is only read.
 // track (with pitch, or with a voice that shifts): both contours are tracked (Track, track.h) before they are used.
+// gain.dyn (with a loudness or limiter stage): the compressor runs on y first (Dynamics, dynamics.h); dyn_stats (may be NULL): its 3 doubles.
 static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
                             int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats,
                             const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr,
-                            const sbv2_voice* voice = nullptr, const sbv2_pitch_track* track = nullptr) {
+                            const sbv2_voice* voice = nullptr, const sbv2_pitch_track* track = nullptr, double* dyn_stats = nullptr) {
+    const DynamicsSpec dyn = gain.dyn ? dynamics_spec(gain.dyn) : DynamicsSpec();
+    const bool compress = gain.dyn && !dyn.identity();
     const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
     const LoudnessSpec ln = gain.kind == FetchGain::kLoudness ? loudness_spec(gain.ln) : LoudnessSpec();
     const LimiterSpec lim = gain.kind == FetchGain::kLimiter ? limiter_spec(gain.lim) : LimiterSpec();
@@ -591,8 +595,9 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         HIP_CHECK(hipMemcpyAsync(dst, vm.pcm_device(), sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, s));
     } else if (total > 0 || gain.kind != FetchGain::kNone || sink == Sink::kFlac) {   // a gain stage and the encoder run on empty signals too
         void* dev = c.formatter.out_buffer((size_t)std::max<int64_t>(pcm_bytes, spec.bytes()), s);
-        const GainStage stage = gain.kind == FetchGain::kLimiter    ? GainStage(c.meter, c.limiter, lim)
-                                : gain.kind == FetchGain::kLoudness ? GainStage(c.meter, ln)
+        Dynamics* const dy = compress ? &c.dynamics : nullptr;
+        const GainStage stage = gain.kind == FetchGain::kLimiter    ? GainStage(c.meter, c.limiter, lim, dy, &dyn)
+                                : gain.kind == FetchGain::kLoudness ? GainStage(c.meter, ln, dy, &dyn)
                                                                     : GainStage();
         c.formatter.run(spec, pieces, sig, total, dev, 0, s, stage);
         if (nseg > 0 && total > 0) {   // the delivered samples, as they cross PCIe or enter the encoder
@@ -619,6 +624,7 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         const double* from = gain.kind == FetchGain::kLimiter ? c.limiter.stats_host() : c.meter.stats_host();
         std::memcpy(stats, from, sizeof(double) * gain.stats_per_signal() * sig.size());
     }
+    if (dyn_stats && compress) std::memcpy(dyn_stats, c.dynamics.stats_host(), sizeof(double) * 3 * sig.size());
     if (marks) {
         std::copy(mp.start.begin(), mp.start.end(), marks->tok_start);
         std::copy(mp.end.begin(), mp.end.end(), marks->tok_end);
@@ -715,10 +721,14 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
 
 int32_t sbv2_voice_tile(void) { return Voice::kTile; }
 
-int sbv2_pipeline_fetch_request_tracked(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
-                                        const sbv2_pitch_track* track, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
-                                        sbv2_marks* marks, sbv2_pitch* pitch) {
+int32_t sbv2_dynamics_tile(void) { return Dynamics::kTile; }
+
+int sbv2_pipeline_fetch_request_dynamics(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                         const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, void* dst, int64_t capacity_bytes,
+                                         int64_t* out_count, double* stats, double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch) {
     API_BEGIN
+    DynamicsSpec ds;
+    if (dynamics) ds = dynamics_spec(dynamics);   // what needs no run is refused before the handle is looked at
     VoiceSpec vs;
     if (voice) vs = check_voice_static(voice, kNativeRate);   // what needs no run is refused before the handle is looked at
     if (track) {
@@ -727,20 +737,28 @@ int sbv2_pipeline_fetch_request_tracked(sbv2_pipeline* p, int64_t ticket, const 
     }
     SBV2_REQUIRE(req && req->n_utts >= 0 && (req->n_utts == 0 || (req->utts && req->place)), "bad fetch request");
     SBV2_REQUIRE(!(req->loudness && req->limiter), "a fetch request takes a loudness target or a limiter, not both");
+    if (dynamics && !ds.identity())   // (fmt->normalize is then refused with the gain stage it needs)
+        SBV2_REQUIRE(req->loudness || req->limiter,
+                     "a compressor needs a loudness target or a limiter behind it: without make-up it only makes the signal quieter");
     if (marks) {   // what needs no run is refused before the handle is looked at
         check_marks_static(marks);
         (void)pcm_format_spec(req->fmt);
     }
     if (pitch) (void)check_pitch_static(pitch, pcm_format_spec(req->fmt).rate);
     SBV2_REQUIRE(p && dst && out_count, "bad arguments");
-    const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter}
-                           : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr}
-                                           : FetchGain();
+    const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter, dynamics}
+                           : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr, dynamics}
+                                           : FetchGain{FetchGain::kNone, nullptr, nullptr, dynamics};
     static const int32_t no_rows[1] = {0};
     static const int64_t no_place[1] = {0};
     fetch_formatted(p, ticket, req->fmt, gain, req->n_utts ? req->place : no_place, req->joined_len, req->flac ? Sink::kFlac : Sink::kPcm, dst,
-                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch, voice, track);
+                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch, voice, track, dyn_stats);
     API_END
+}
+int sbv2_pipeline_fetch_request_tracked(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                        const sbv2_pitch_track* track, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                        sbv2_marks* marks, sbv2_pitch* pitch) {
+    return sbv2_pipeline_fetch_request_dynamics(p, ticket, req, voice, track, nullptr, dst, capacity_bytes, out_count, stats, nullptr, marks, pitch);
 }
 int sbv2_pipeline_fetch_request_voice(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice, void* dst,
                                       int64_t capacity_bytes, int64_t* out_count, double* stats, sbv2_marks* marks, sbv2_pitch* pitch) {

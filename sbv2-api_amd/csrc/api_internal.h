@@ -7,6 +7,7 @@
 #include <new>
 
 #include "../../include/sbv2_hip.h"
+#include "dynamics.h"
 #include "flac_encode.h"
 #include "limiter.h"
 #include "loudness.h"
@@ -35,6 +36,7 @@ struct OutputChain {
     FlacEncoder flac;
     LoudnessMeter meter;
     Limiter limiter;   // (owns a second meter, for its evaluations)
+    Dynamics dynamics; // the speech compressor in front of the loudness gain or the limiter (fetch_request_dynamics only)
     Marks marks;       // speech marks: levels of token spans and envelope frames (fetch_request_marks only)
     Pitch pitch;       // ... and the pitch contour of the same samples (fetch_request_pitch only)
     Voice voice;       // pitch / intonation scale of the listed rows, in front of the formatter (fetch_request_voice only)

@@ -29,6 +29,33 @@ StreamLevelSpec stream_level_spec(const sbv2_stream_level* lv);
 // A = K - 1 + 12 at `rate`: the samples that must follow a sample before its gain is final (throws for a rate the limiter has no window for)
 int64_t stream_level_lookahead(int rate);
 
+// What the limiter shares with the compressor in front of it (dynamics.hip), so that both read ONE envelope and ONE window: the signal table,
+// step 1 of sbv2_limiter and the taps of its smoothing window.
+constexpr int kLimTile = 1024;   // samples per workgroup of the curve kernels; a tile never straddles a signal edge
+struct LimSig {
+    int64_t off, n, tile0;   // samples y[off, off + n); its tiles are [tile0, tile0 + ceil(n / kLimTile))
+};
+__device__ __forceinline__ int lim_find_tile(const LimSig* sig, int nsig, int64_t k) {   // last signal with tile0 <= k
+    int lo = 0, hi = nsig - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (sig[mid].tile0 <= k) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// e[p] of step 1 from the interpolated magnitudes t (limiter_interp) of ONE signal, 0 <= p < n: y and t are indexed by the position in it
+__device__ __forceinline__ double lim_envelope_at(const double* y, const double* t, int64_t p) {
+    return fmax(fmax(p > 0 ? t[p - 1] : 0.0, fabs(y[p])), t[p]);
+}
+// t[o] = max |z[4 o + 1 .. 4 o + 3]| of the `total` samples y of the signals in sig (device table), one launch on s
+void limiter_interp(const double* y, const LimSig* sig, int nsig, int64_t total, double* t, hipStream_t s);
+// K = rate / 100 (throws for a rate the window does not cover); sin^2(pi (k + 0.5) / K) scaled to sum to 1 into h[K], returns their sum
+// in ascending k
+constexpr int kLimMaxK = 480;   // 10 ms at 48 kHz
+int limiter_window(int rate);
+double limiter_hann_taps(int K, double* h);
+
 // Device state of the limiter of one execution context, beside the LoudnessMeter and outside the activation arena: the signal table, the
 // per-signal gains and stats, the interpolated magnitudes, the evaluated signal x and the per-tile minima (grown on demand; growing
 // synchronises the stream), and a second meter for the evaluations of x.

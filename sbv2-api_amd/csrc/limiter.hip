@@ -50,13 +50,10 @@ namespace {
 constexpr int kTile = 1024;
 constexpr int kLanes = 256;
 constexpr int kMaxK = 480;                        // 10 ms at 48 kHz
+static_assert(kTile == kLimTile && kMaxK == kLimMaxK, "limiter.h states the same two for the compressor");
 constexpr int kLdsLen = kTile + 2 * kMaxK - 2;   // r of a tile and its halo
 constexpr int kTpBack = 12;                       // the interpolator's window is y[o - 11, o + 12] (loudness.hip)
 static_assert(kLdsLen <= 8 * kLanes && kTile + kMaxK - 1 <= 6 * kLanes && kTile == 4 * kLanes, "k_lim_curve's per-lane counts");
-
-struct LimSig {
-    int64_t off, n, tile0;   // samples y[off, off + n); its tiles are [tile0, tile0 + ceil(n / kTile))
-};
 
 struct LimState {
     double G, g0, Gcap;   // the pre-gain in dB and linear, its cap
@@ -68,16 +65,6 @@ __device__ __forceinline__ int find_off(const LimSig* sig, int nsig, int64_t o) 
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (sig[mid].off <= o) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ int find_tile(const LimSig* sig, int nsig, int64_t k) {   // last signal with tile0 <= k
-    int lo = 0, hi = nsig - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (sig[mid].tile0 <= k) lo = mid;
         else hi = mid - 1;
     }
     return lo;
@@ -176,7 +163,7 @@ struct CurveArgs {
 };
 
 __device__ __forceinline__ double ratio_at(const double* y, const double* t, int64_t p, double c, double g0) {   // r[p], 0 <= p < n
-    const double e = fmax(fmax(p > 0 ? t[p - 1] : 0.0, fabs(y[p])), t[p]);
+    const double e = lim_envelope_at(y, t, p);
     return e > 0.0 ? fmin(1.0, c / (g0 * e)) : 1.0;
 }
 
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(kLanes) void k_lim_curve(CurveArgs a) {
     __shared__ double red[kLanes / 64];
     __shared__ int active;
     const int t = threadIdx.x;
-    const int si = kStream ? 0 : find_tile(a.sig, a.nsig, blockIdx.x);
+    const int si = kStream ? 0 : lim_find_tile(a.sig, a.nsig, blockIdx.x);
     const LimSig g = kStream ? LimSig{0, a.win_n, 0} : a.sig[si];
     const LimState st = kStream ? LimState{0.0, a.g0, 0.0, 0} : a.st[si];
     const int64_t n0 = kStream ? a.lo + (int64_t)blockIdx.x * kTile : ((int64_t)blockIdx.x - g.tile0) * kTile;
@@ -323,21 +310,6 @@ __global__ __launch_bounds__(64) void k_lim_update(UpdateArgs a) {
     }
 }
 
-// sin^2(pi (k + 0.5) / K), scaled to sum to 1, into h[K]; returns their sum in the kernel's order
-double hann_taps(int K, double* h) {
-    double sum = 0.0, hsum = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const double v = std::sin(M_PI * (k + 0.5) / K);
-        h[k] = v * v;
-        sum += h[k];
-    }
-    for (int k = 0; k < K; ++k) {
-        h[k] /= sum;
-        hsum += h[k];   // = fma(h[k], 1, acc): the kernel's sum over a window of ones
-    }
-    return hsum;
-}
-
 // ---- fixed gain ----
 
 __global__ __launch_bounds__(kLanes) void k_lim_fixed_init(LimState* st, int nsig, double G, double g0) {
@@ -390,13 +362,40 @@ __global__ __launch_bounds__(64) void k_lim_stream_fold(const double* smin, cons
     }
 }
 
-int window_of(int rate) {
+}  // namespace
+
+// sin^2(pi (k + 0.5) / K), scaled to sum to 1, into h[K]; returns their sum in the kernel's order
+double limiter_hann_taps(int K, double* h) {
+    double sum = 0.0, hsum = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double v = std::sin(M_PI * (k + 0.5) / K);
+        h[k] = v * v;
+        sum += h[k];
+    }
+    for (int k = 0; k < K; ++k) {
+        h[k] /= sum;
+        hsum += h[k];   // = fma(h[k], 1, acc): the kernel's sum over a window of ones
+    }
+    return hsum;
+}
+
+int limiter_window(int rate) {
     const int K = rate / 100;
     SBV2_REQUIRE(K >= 2 && K <= kMaxK, "internal: limiter window");
     return K;
 }
 
-}  // namespace
+void limiter_interp(const double* y, const LimSig* sig, int nsig, int64_t total, double* t, hipStream_t s) {
+    if (total <= 0) return;
+    InterpArgs a;
+    a.y = y;
+    a.sig = sig;
+    a.nsig = nsig;
+    a.total = total;
+    loudness_true_peak_taps(a.h);
+    a.t = t;
+    hipLaunchKernelGGL(k_lim_interp<false>, dim3((unsigned)((total + kLanes - 1) / kLanes)), dim3(kLanes), 0, s, a);
+}
 
 LimiterSpec limiter_spec(const sbv2_limiter* lim) {
     SBV2_REQUIRE(lim, "no limiter given");
@@ -430,17 +429,7 @@ struct LimWork {
     const double* end = nullptr;   // behind the per-tile minima and their pad words
 
     Limiter::Parts parts() const { return Limiter::Parts{h, t, x, smin, end, total, tiles, K, hsum}; }
-    void interp(hipStream_t s) const {
-        if (total <= 0) return;
-        InterpArgs a;
-        a.y = y;
-        a.sig = sig;
-        a.nsig = nsig;
-        a.total = total;
-        loudness_true_peak_taps(a.h);
-        a.t = t;
-        hipLaunchKernelGGL(k_lim_interp<false>, dim3((unsigned)((total + kLanes - 1) / kLanes)), dim3(kLanes), 0, s, a);
-    }
+    void interp(hipStream_t s) const { limiter_interp(y, sig, nsig, total, t, s); }
     void curve(double ceiling_db, bool first, hipStream_t s) const {
         if (tiles <= 0) return;
         CurveArgs a{};
@@ -466,7 +455,7 @@ LimWork lim_setup(const double* y, const std::vector<FmtSignal>& sig, int rate, 
     w.y = y;
     w.nsig = (int)sig.size();
     SBV2_REQUIRE(w.nsig >= 1, "internal: no signal to limit");
-    w.K = window_of(rate);
+    w.K = limiter_window(rate);
     const int nsig = w.nsig;
     std::vector<LimSig> tab(nsig);
     for (int i = 0; i < nsig; ++i) {
@@ -487,7 +476,7 @@ LimWork lim_setup(const double* y, const std::vector<FmtSignal>& sig, int rate, 
     char* h = static_cast<char*>(host.reserve(hbytes, std::max<size_t>(hbytes * 2, 8192), s));
     std::memcpy(h, tab.data(), sizeof(LimSig) * nsig);
     double* hann = reinterpret_cast<double*>(h + tb);   // sin^2(pi (k + 0.5) / K), scaled to sum to 1
-    w.hsum = hann_taps(w.K, hann);
+    w.hsum = limiter_hann_taps(w.K, hann);
     w.stats_host = reinterpret_cast<double*>(h + tb + hb);
     HIP_CHECK(hipMemcpyAsync(d, h, sizeof(LimSig) * nsig, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d + o_h, hann, sizeof(double) * w.K, hipMemcpyHostToDevice, s));
@@ -567,7 +556,7 @@ StreamLevelSpec stream_level_spec(const sbv2_stream_level* lv) {
 
 // The interpolator's window of t[o] is y[o - 11, o + 12] (kTpBack; k_lim_interp stages [base - 11, base + 268) for 256 samples: 11 back,
 // 12 ahead), and s[n] needs r, hence t, up to n + K - 1: y up to n + K - 1 + 12.
-int64_t stream_level_lookahead(int rate) { return window_of(rate) - 1 + kTpBack; }
+int64_t stream_level_lookahead(int rate) { return limiter_window(rate) - 1 + kTpBack; }
 
 const double* Limiter::run_fixed(const double* y, const std::vector<FmtSignal>& sig, int rate, const StreamLevelSpec& lv, hipStream_t s) {
     const LimWork w = lim_setup(y, sig, rate, dev_, host_, s);
@@ -591,7 +580,7 @@ const double* Limiter::run_fixed(const double* y, const std::vector<FmtSignal>& 
 // push was, and the buffers swap.  Which samples a push emits follows from the counts alone: nothing here waits for the GPU after begin.
 
 void StreamLimiter::begin(int rate, int64_t total_samples, int64_t max_push, const StreamLevelSpec& lv, hipStream_t s) {
-    K_ = window_of(rate);
+    K_ = limiter_window(rate);
     A_ = stream_level_lookahead(rate);
     SBV2_REQUIRE(total_samples >= 0 && max_push >= 0, "stream level: length out of range");
     total_ = total_samples;
@@ -608,7 +597,7 @@ void StreamLimiter::begin(int rate, int64_t total_samples, int64_t max_push, con
     // [running min s, max |x|, the unit gain | Hann taps | per-tile min s | per-tile max |x|]
     aux_.reserve(64 + 8 * kMaxK + 16 * tiles, s);
     double* hann = static_cast<double*>(host_.reserve(8 * kMaxK + 64, s));
-    hsum_ = hann_taps(K_, hann);
+    hsum_ = limiter_hann_taps(K_, hann);
     HIP_CHECK(hipMemcpyAsync(aux_.as<char>() + 64, hann, sizeof(double) * K_, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_lim_stream_init, dim3(1), dim3(1), 0, s, aux_.as<double>());
     HIP_CHECK(hipGetLastError());

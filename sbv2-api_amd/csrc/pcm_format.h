@@ -79,21 +79,28 @@ class LoudnessMeter;   // loudness.h
 struct LoudnessSpec;
 class Limiter;   // limiter.h
 struct LimiterSpec;
+class Dynamics;   // dynamics.h
+struct DynamicsSpec;
 
 // The gain stage of a formatting run, between the resampler and the quantiser: none (peak-normalise or not, as spec.normalize says), a
 // loudness gain from `meter` (loudness.hip), or the look-ahead limiter (limiter.hip).  A fourth kind ends the run at the stage's input: y
 // (f64) is written to a caller-given address and nothing else happens (the level control of a stream takes it from there, stream_output.cpp).
+// A loudness or limiter stage may have the speech compressor (dynamics.hip) in front of it: the stage then works on its output yc in place of y.
 struct GainStage {
     enum Kind { kNone, kLoudness, kLimiter, kExposeY };
     GainStage() = default;
     explicit GainStage(double* y_dev) : kind(kExposeY), y_out(y_dev) {}
-    GainStage(LoudnessMeter& m, const LoudnessSpec& l) : kind(kLoudness), meter(&m), ln(&l) {}
-    GainStage(LoudnessMeter& m, Limiter& li, const LimiterSpec& l) : kind(kLimiter), meter(&m), limiter(&li), lim(&l) {}
+    GainStage(LoudnessMeter& m, const LoudnessSpec& l, Dynamics* dy = nullptr, const DynamicsSpec* ds = nullptr)
+        : kind(kLoudness), meter(&m), ln(&l), dynamics(dy), dyn(ds) {}
+    GainStage(LoudnessMeter& m, Limiter& li, const LimiterSpec& l, Dynamics* dy = nullptr, const DynamicsSpec* ds = nullptr)
+        : kind(kLimiter), meter(&m), limiter(&li), lim(&l), dynamics(dy), dyn(ds) {}
     const Kind kind = kNone;
     LoudnessMeter* const meter = nullptr;   // the meter of y (both stages)
     const LoudnessSpec* const ln = nullptr;
     Limiter* const limiter = nullptr;
     const LimiterSpec* const lim = nullptr;
+    Dynamics* const dynamics = nullptr;     // the compressor in front of the stage (both stages), or none
+    const DynamicsSpec* const dyn = nullptr;
     double* const y_out = nullptr;          // kExposeY: total doubles on the device
 };
 

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "../../include/sbv2_hip.h"
+#include "dynamics.h"
 #include "limiter.h"
 #include "loudness.h"
 #include "pcm_format.h"
@@ -262,6 +263,7 @@ const float* PcmFormatter::taps(const PcmFmtSpec& spec, hipStream_t s) {
 // the stage on the f64 signal y (null when there is no sample): returns the signal to deliver, *gain = one gain per signal for it
 static const double* apply_gain(const GainStage& g, const double* y, const std::vector<FmtSignal>& sig, int rate, hipStream_t s,
                                 const double** gain) {
+    if (g.dynamics) y = g.dynamics->run(y, sig, rate, *g.dyn, *g.meter, s);   // yc takes y's place; the meter is free again behind it
     if (g.kind == GainStage::kLimiter) return g.limiter->run(y, sig, rate, *g.lim, *g.meter, s, gain);   // its own x and unit gains
     *gain = g.meter->measure(y, sig, rate, *g.ln, s);
     return y;

@@ -587,6 +587,34 @@ int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsi
     API_END
 }
 
+int sbv2_debug_dynamics(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_dynamics* dynamics,
+                        double* e_out, int64_t* dq_out, int64_t* u_out, double* s_out, double* y_out, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(nsig >= 1 && lens && stats, "bad arguments");
+    const DynamicsSpec spec = dynamics_spec(dynamics);
+    double coef[10];
+    loudness_kweight(sample_rate, coef);   // refuses unsupported rates
+    int64_t total = 0;
+    const std::vector<FmtSignal> sig = packed_signals(lens, nsig, &total);
+    SBV2_REQUIRE(total == 0 || x, "bad arguments");
+    AudioScratch r(device, x, sizeof(double) * (size_t)total);
+    LoudnessMeter meter;
+    Dynamics dyn;
+    dyn.run(r.x.as<double>(), sig, sample_rate, spec, meter, r.s, true);   // (the kernels run also at ratio == 1: d = 0 throughout)
+    const Dynamics::Parts& pt = dyn.parts();
+    const size_t bytes = sizeof(double) * (size_t)total;
+    if (total) {
+        if (e_out) HIP_CHECK(hipMemcpyAsync(e_out, pt.e, bytes, hipMemcpyDeviceToHost, r.s));
+        if (dq_out) HIP_CHECK(hipMemcpyAsync(dq_out, pt.dq, bytes, hipMemcpyDeviceToHost, r.s));
+        if (u_out) HIP_CHECK(hipMemcpyAsync(u_out, pt.u, bytes, hipMemcpyDeviceToHost, r.s));
+        if (s_out) HIP_CHECK(hipMemcpyAsync(s_out, pt.s, bytes, hipMemcpyDeviceToHost, r.s));
+        if (y_out) HIP_CHECK(hipMemcpyAsync(y_out, pt.yc, bytes, hipMemcpyDeviceToHost, r.s));
+    }
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    std::memcpy(stats, dyn.stats_host(), sizeof(double) * 3 * nsig);
+    API_END
+}
+
 int sbv2_debug_limiter_fixed(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_stream_level* level,
                              double* out_x, double* stats) {
     API_BEGIN

@@ -354,6 +354,56 @@ def debug_limiter(signals, sample_rate: int, limiter: Limiter, device: int = 0):
     return np.split(out[:x.size], np.cumsum(lens)[:-1]), stats
 
 
+class Dynamics:
+    """Speech compressor in front of a Loudness or a Limiter (struct sbv2_dynamics): what lies more than threshold_lu in [0, 30] dB above
+    the signal's own integrated loudness is taken down by ratio in [1, 20] (1: nothing happens), the gain moving by attack in [10, 10000]
+    dB/s ahead of a peak and by release in [1, 1000] dB/s behind it.  It evens out syllables and sentences so that the limiter is left with
+    the crest only; it does not bound the signal and does not remove the crest factor.  Runs on the device."""
+
+    def __init__(self, threshold_lu: float = 8.0, ratio: float = 4.0, attack: float = 600.0, release: float = 60.0):
+        self.threshold_lu, self.ratio, self.attack, self.release = float(threshold_lu), float(ratio), float(attack), float(release)
+        if not (np.isfinite(self.threshold_lu) and 0.0 <= self.threshold_lu <= 30.0):
+            raise Sbv2Error(f"compressor threshold {threshold_lu} LU is outside [0, 30]")
+        if not (np.isfinite(self.ratio) and 1.0 <= self.ratio <= 20.0):
+            raise Sbv2Error(f"compressor ratio {ratio} is outside [1, 20]")
+        if not (np.isfinite(self.attack) and 10.0 <= self.attack <= 10000.0):
+            raise Sbv2Error(f"compressor attack {attack} dB/s is outside [10, 10000]")
+        if not (np.isfinite(self.release) and 1.0 <= self.release <= 1000.0):
+            raise Sbv2Error(f"compressor release {release} dB/s is outside [1, 1000]")
+        self.c = _lib.Sbv2Dynamics(self.threshold_lu, self.ratio, self.attack, self.release, 0.0)
+
+    def is_identity(self) -> bool:
+        return self.ratio == 1.0
+
+    def __repr__(self):
+        return f"Dynamics({self.threshold_lu}, ratio={self.ratio}, attack={self.attack}, release={self.release})"
+
+
+def dynamics_tile() -> int:
+    """Samples per workgroup of the compressor's scans."""
+    return int(_lib.lib().sbv2_dynamics_tile())
+
+
+def debug_dynamics(signals, sample_rate: int, dynamics: Dynamics, device: int = 0):
+    """Test hook: the device compressor on host float64 signals at sample_rate, always through the kernels -> (parts, stats [n, 3]: L LUFS,
+    T, deepest compression dB); parts[i] has e, dq (int64), u (int64), s and y (the compressed signal) of signal i."""
+    import types
+    sigs = [np.ascontiguousarray(np.asarray(x, np.float64)).reshape(-1) for x in signals]
+    x = np.concatenate(sigs) if sigs else np.zeros(0, np.float64)
+    lens = np.array([s.size for s in sigs], np.int64)
+    n = max(x.size, 1)
+    e, s_, y = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.float64)
+    dq, u = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    stats = np.zeros((len(sigs), 3), np.float64)
+    check(_lib.lib().sbv2_debug_dynamics(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, lens.ctypes.data_as(i64p), len(sigs),
+                                         int(sample_rate), C.byref(dynamics.c), _f64p(e), dq.ctypes.data_as(i64p), u.ctypes.data_as(i64p),
+                                         _f64p(s_), _f64p(y), _f64p(stats)))
+    cuts = np.cumsum(lens)[:-1]
+    parts = [types.SimpleNamespace(e=a, dq=b, u=c, s=d, y=f)
+             for a, b, c, d, f in zip(*(np.split(v[:x.size], cuts) for v in (e, dq, u, s_, y)))]
+    return parts, stats
+
+
 class StreamLevel:
     """Level control of a stream (struct sbv2_stream_level): a fixed gain of gain_db in [-40, 40] and the look-ahead gain curve of Limiter at
     that gain, which holds every sample at or below true_peak_max dBTP in [-20, 0].  No loudness target and no depth bound: the gain is the
@@ -939,7 +989,7 @@ class Pipeline:
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
-                      voice=None, track=None):
+                      voice=None, track=None, dynamics=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
@@ -952,7 +1002,10 @@ class Pipeline:
         voice: a Voice -> the listed rows are shifted on the device before the formatter (sbv2_pipeline_fetch_request_voice); everything else,
         the returned shape included, is the same call on the shifted rows.  None or Voice(1, 1): exactly the call without.
         track: a PitchTrack -> the contours are tracked (sbv2_pipeline_fetch_request_tracked): the delivered one (pitch) and the shifter's own
-        (a voice that shifts); it needs one of the two.  None: exactly the call without."""
+        (a voice that shifts); it needs one of the two.  None: exactly the call without.
+        dynamics: a Dynamics -> the compressor runs in front of `gain`, which must be given (sbv2_pipeline_fetch_request_dynamics), and the
+        returned tuple gains a last element: the stage's stats [3] (L of the uncompressed signal, the threshold T, the deepest compression
+        in dB), or None at ratio 1, which is exactly the call without.  `stats` are then those of the compressed signal."""
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
         rw = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
@@ -972,15 +1025,25 @@ class Pipeline:
         if track is not None:
             ct = track.c
             tracked = lambda *a: _lib.lib().sbv2_pipeline_fetch_request_tracked(*a[:3], C.byref(voice.c) if voice is not None else None, C.byref(ct), *a[3:])
-        if track is not None and not marks and pitch is None:
+        if dynamics is not None:
+            dst_stats = None if dynamics.is_identity() else np.zeros(3, np.float64)
+            cd = dynamics.c
+            compressed = lambda *a: _lib.lib().sbv2_pipeline_fetch_request_dynamics(
+                *a[:3], C.byref(voice.c) if voice is not None else None, C.byref(track.c) if track is not None else None, C.byref(cd), *a[3:7],
+                _f64p(dst_stats) if dst_stats is not None else None, *a[7:])
+            if not marks and pitch is None:
+                check(compressed(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
+                                 _f64p(stats) if nstats else None, None, None))
+                return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats, dst_stats
+        if dynamics is None and track is not None and not marks and pitch is None:
             check(tracked(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
                           None, None))
             return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        if not marks and pitch is None and voice is None:
+        if dynamics is None and not marks and pitch is None and voice is None:
             check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
                                                          _f64p(stats) if nstats else None))
             return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        if not marks and pitch is None:
+        if dynamics is None and not marks and pitch is None:
             cv = voice.c
             check(_lib.lib().sbv2_pipeline_fetch_request_voice(self.h, b.ticket, C.byref(req), C.byref(cv), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
                                                                C.byref(got), _f64p(stats) if nstats else None, None, None))
@@ -998,7 +1061,9 @@ class Pipeline:
                                 _f64p(m.env_peak) if env_hop > 0 else None, 0)
         args = (self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
                 C.byref(cm) if marks else None)
-        if track is not None:
+        if dynamics is not None:
+            check(compressed(*args, C.byref(cp) if pitch is not None else None))
+        elif track is not None:
             check(tracked(*args, C.byref(cp) if pitch is not None else None))
         elif voice is not None:
             cv = voice.c
@@ -1010,7 +1075,8 @@ class Pipeline:
         if marks:
             assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
         out = dst[:got.value].tobytes() if flac else dst[:got.value]
-        return (out, stats, m) if pitch is None else (out, stats, m, pitch.take(cp, parr))
+        res = (out, stats, m) if pitch is None else (out, stats, m, pitch.take(cp, parr))
+        return res if dynamics is None else res + (dst_stats,)
 
     def close(self):
         if self.h:

@@ -57,11 +57,27 @@ class SynthesizeOptions:
     decision per frame.  It needs pitch_hz or a pitch_scale / intonation_scale away from 1; whole-signal routes only, refused on streams (a best
     path needs the future).  pitch_hz counts on the routes that carry a contour only: without marks (easy_synthesize, /synthesize, the batcher
     without marks) pitch_hz itself is refused, with or without pitch_track, so tracking is never dropped in silence; there a scale away from 1 is
-    what pitch_track needs.  False is the calls and the bytes there always were."""
+    what pitch_track needs.  False is the calls and the bytes there always were.
+    compressor (new; checked here) with comp_threshold (LU above the signal's own loudness, [0, 30]), comp_ratio ([1, 20]), comp_attack
+    ([10, 10000] dB/s) and comp_release ([1, 1000] dB/s): a speech compressor in front of the loudness gain or the limiter (model.Dynamics),
+    which evens out syllables and sentences so that a loud target comes nearer; it needs a loudness target, as limiter does.  Whole-signal
+    routes only (easy_synthesize, easy_synthesize_marks, the batcher), refused on streams.  False is the calls and the bytes there always were."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
                  normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
-                 pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False):
+                 pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False,
+                 compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0):
+        if not isinstance(compressor, bool):
+            raise model.Sbv2Error(f"compressor must be true or false: {compressor!r}")
+        for name, v in (("comp_threshold", comp_threshold), ("comp_ratio", comp_ratio), ("comp_attack", comp_attack), ("comp_release", comp_release)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise model.Sbv2Error(f"{name} must be a number: {v!r}")
+        if compressor and loudness is None:
+            raise model.Sbv2Error("compressor needs a loudness target: set loudness (LUFS); without make-up it only makes the signal quieter")
+        self.compressor = compressor
+        self.comp_threshold, self.comp_ratio, self.comp_attack, self.comp_release = comp_threshold, comp_ratio, comp_attack, comp_release
+        if compressor:
+            dynamics_options(self)   # the ranges, by model.Dynamics
         for name, v, lo, hi in (("pitch_scale", pitch_scale, 0.5, 2.0), ("intonation_scale", intonation_scale, 0.0, 2.0)):
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= v <= hi:   # (a NaN fails the comparison)
                 raise model.Sbv2Error(f"{name} must be a number in [{lo}, {hi}]: {v!r}")
@@ -191,6 +207,9 @@ class RequestPlan:
             self.gain = model.Limiter(options.loudness, options.true_peak_max, options.max_reduction)
         else:
             self.gain = model.Loudness(options.loudness, options.true_peak_max) if options.loudness is not None else None
+        self.dynamics = dynamics_options(options)
+        if self.dynamics is not None and self.gain is None:
+            raise model.Sbv2Error("compressor needs a loudness target: set loudness (LUFS); without make-up it only makes the signal quieter")
         style = get_style_vector(style_vectors, style_id, options.style_weight)
         live = [(i, s) for i, s in enumerate(sentences) if s]
         if not live:
@@ -262,6 +281,28 @@ def refuse_track(options, what: str):
                               "instead")
 
 
+def dynamics_options(options):
+    """The model.Dynamics of a request (None without compressor: the request is then the call it always was)."""
+    if not getattr(options, "compressor", False):
+        return None
+    return model.Dynamics(getattr(options, "comp_threshold", 8.0), getattr(options, "comp_ratio", 4.0), getattr(options, "comp_attack", 600.0),
+                          getattr(options, "comp_release", 60.0))
+
+
+def refuse_dynamics(options, what: str):
+    """compressor where the signal leaves chunk by chunk: refused, with the reason and the routes that fetch a whole signal."""
+    if getattr(options, "compressor", False):
+        raise model.Sbv2Error(f"compressor works on a whole signal: its threshold needs the whole signal's loudness and its attack looks ahead "
+                              f"without bound, and {what} hands out chunks before the signal is complete; ask /synthesize, /synthesize_marks "
+                              "(easy_synthesize, easy_synthesize_marks) or the batcher instead")
+
+
+def dynamics_dict(stats) -> dict:
+    """The "dynamics" block of a marks dict from the compressor's three stats."""
+    L, T, deepest = (float(v) for v in stats)
+    return {"loudness_lufs": L if np.isfinite(L) else None, "threshold_lufs": T if np.isfinite(T) else None, "deepest_db": deepest}
+
+
 def token_marks(utts, live, rate: int, start, end):
     """The timing part of the marks dict: utts = the request's live sentences (phones, word2ph), live = their line numbers, start / end = the
     delivered-sample spans of their tokens, sentence after sentence.  tokens: one entry per phone id (blanks included); words: one entry per
@@ -327,12 +368,18 @@ def token_pitch(tokens, f0, hop: int):
         t["voiced"] = float(v.size) / (k1 - k0) if k1 > k0 else 0.0
 
 
-def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPlan, loudness_stats=None, pcm=None, marks=None) -> bytes:
+def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPlan, loudness_stats=None, pcm=None, marks=None,
+                   dynamics_stats=None) -> bytes:
     """The answer of one request from rows r0 .. r1 - 1 of run `b` (plan.utts were prepared as those rows): the request's WAV or FLAC bytes,
     whatever else the run holds.  pcm: the run's plain fetch (pipe.fetch(b)) when the caller already has it.
     marks: an optional list that receives the request's speech marks (marks_dict); the signal then always comes from ONE fetch of the
-    request's rows with marks (at the identity format for the default output: the same samples, hence the same bytes)."""
+    request's rows with marks (at the identity format for the default output: the same samples, hence the same bytes).
+    dynamics_stats: an optional list that receives the compressor's [L, T, deepest compression] when plan.dynamics compresses; the marks then
+    carry them as a "dynamics" block (dynamics_dict), and loudness_stats are those of the compressed signal."""
     options, fmt, ln = plan.options, plan.fmt, plan.gain
+    dyn = getattr(plan, "dynamics", None)
+    dkw = {} if dyn is None else {"dynamics": dyn}   # (named only when asked for, like voice)
+    dstats = None
     lens = b.lens[r0:r1]
     voice = voice_options(options)
     vkw = {} if voice is None else {"voice": voice}   # (named only when asked for: a request at the defaults is the call it always was)
@@ -347,13 +394,19 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
             if track is not None and (pitch is not None or voice is not None):   # (likewise named only when asked for)
                 kw["track"] = track
             if pitch is None:   # (the call of a request without a contour is the call it always was)
-                out, stats, m = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw)
+                out, stats, m, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw, **dkw)
             else:
-                out, stats, m, pitch = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, pitch=pitch, **kw)
+                out, stats, m, pitch, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, pitch=pitch, **kw, **dkw)
+            dstats = rest[0] if dyn is not None else None
             marks.append(marks_dict(plan.utts, plan.live, fmt, m, pitch, **({"tracked": True} if "track" in kw and pitch is not None else {})))
+            if dstats is not None:
+                marks[-1]["dynamics"] = dynamics_dict(dstats)
         else:
             tkw = {"track": track} if track is not None and voice is not None else {}
-            out, stats = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, **vkw, **tkw)
+            out, stats, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, **vkw, **tkw, **dkw)
+            dstats = rest[0] if dyn is not None else None
+        if dstats is not None and dynamics_stats is not None:
+            dynamics_stats.append([float(v) for v in dstats])
         if stats is not None and loudness_stats is not None:
             loudness_stats.append([float(v) for v in stats])
         if plan.flac:
@@ -370,12 +423,14 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
 
 
 def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
-                    noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, loudness_stats=None) -> bytes:
+                    noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, loudness_stats=None, dynamics_stats=None) -> bytes:
     """tts.rs:280-349 for one request whose lines are already parsed: `sentences` is the list obtained from text.split('\\n'),
     each entry a dict {input_ids, word2ph, phones, tones, langs} (parse_text's products) or None / {} for an empty line.
     With options.split_sentences False the caller passes the single parsed text as a one-element list.
     loudness_stats: an optional list that receives [L, TP, G] of the signal when options.loudness is set, or the limiter's 6 values
     [L, TP, G, L_out, TP_out, deepest reduction] when options.limiter is set as well.
+    dynamics_stats: an optional list that receives the compressor's [L, T, deepest compression] when options.compressor is set; the
+    loudness_stats are then those of the compressed signal.
     = finish_request over all rows of a run that holds this request alone (batcher.RequestBatcher: the same, several requests to a run)."""
     refuse_pitch(options, "easy_synthesize (/synthesize)")
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
@@ -384,11 +439,11 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     b = pipe.prepare(plan.utts, sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=noise_scale,
                      noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     pipe.run(b)
-    return finish_request(pipe, b, 0, len(plan.utts), plan, loudness_stats)
+    return finish_request(pipe, b, 0, len(plan.utts), plan, loudness_stats, **({} if dynamics_stats is None else {"dynamics_stats": dynamics_stats}))
 
 
 def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
-                          noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, loudness_stats=None):
+                          noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, loudness_stats=None, dynamics_stats=None):
     """(audio_bytes, marks): easy_synthesize's bytes for the same arguments, and the speech marks of that signal (marks_dict): when each
     phone id and each word (word2ph entry) is spoken, in samples and seconds of the delivered signal, how loud it is there, and with
     options.envelope_hz a level envelope.  Levels are computed on the device from the delivered samples (also behind the FLAC sink)."""
@@ -401,7 +456,8 @@ def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, styl
                      noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     pipe.run(b)
     got = []
-    audio = finish_request(pipe, b, 0, len(plan.utts), plan, loudness_stats, marks=got)
+    audio = finish_request(pipe, b, 0, len(plan.utts), plan, loudness_stats, marks=got,
+                           **({} if dynamics_stats is None else {"dynamics_stats": dynamics_stats}))
     return audio, got[0]
 
 
@@ -565,6 +621,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     options = options or SynthesizeOptions()
     refuse_voice(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    refuse_dynamics(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if pitch:
         if not levels:
             raise model.Sbv2Error("pitch=True on a stream comes with its speech marks: pass levels=True as well")

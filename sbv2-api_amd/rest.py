@@ -37,6 +37,11 @@ and error mapping, so that a client of the reference's server cannot tell the di
   pitch_track = false (new; the same routes): octave-error repair.  The contours the request uses (pitch_hz's in the marks, the shifter's own)
                     are tracked across frames on the device, one best path through every frame's candidate lags; the marks' "pitch" block then
                     says "tracked": true.  It needs pitch_hz or a scale away from 1.  The stream routes answer 400 for true.
+  compressor = false (new; the same routes; comp_threshold = 8.0, comp_ratio = 4.0, comp_attack = 600.0, comp_release = 60.0): a speech compressor
+                    in front of the loudness gain or the limiter, on the device: what lies more than comp_threshold dB above the signal's own
+                    loudness is taken down by comp_ratio, at comp_attack / comp_release dB per second.  It needs loudness, as limiter does.  The
+                    marks of /synthesize_marks then carry "dynamics": {"loudness_lufs", "threshold_lufs", "deepest_db"}.  The stream routes answer
+                    400 for true: the threshold needs the whole signal's loudness and the attack looks ahead without bound.
   POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
@@ -158,6 +163,11 @@ def make_app(holder, batching=None):
         pitch_scale: float = 1.0            # new: multiplies the voice's f0, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); refused on the stream routes
         intonation_scale: float = 1.0       # new: scales f0's excursions about its mean, [0, 2]; the same routes
         pitch_track: bool = False           # new: octave-error repair of the contours in use (needs pitch_hz or a scale away from 1); the same routes
+        compressor: bool = False            # new: speech compressor in front of the loudness stage; needs loudness; the same routes
+        comp_threshold: float = 8.0         # dB above the signal's own integrated loudness, [0, 30]
+        comp_ratio: float = 4.0             # [1, 20]
+        comp_attack: float = 600.0          # dB per second, [10, 10000]
+        comp_release: float = 60.0          # dB per second, [1, 1000]
 
     class SynthesizeMarksRequest(SynthesizeRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
@@ -205,7 +215,10 @@ def make_app(holder, batching=None):
                                               true_peak_max=req.true_peak_max, limiter=req.limiter, max_reduction=req.max_reduction,
                                               envelope_hz=getattr(req, "envelope_hz", None), gain_db=req.gain_db, pitch_hz=req.pitch_hz,
                                               pitch_min_hz=req.pitch_min_hz, pitch_max_hz=req.pitch_max_hz, pitch_scale=req.pitch_scale,
-                                              intonation_scale=req.intonation_scale, **({"pitch_track": True} if getattr(req, "pitch_track", False) else {}))
+                                              intonation_scale=req.intonation_scale, **({"pitch_track": True} if getattr(req, "pitch_track", False) else {}),
+                                              **({"compressor": True, "comp_threshold": req.comp_threshold, "comp_ratio": req.comp_ratio,
+                                                  "comp_attack": req.comp_attack, "comp_release": req.comp_release}
+                                                 if getattr(req, "compressor", False) else {}))
 
     def synthesize(req: SynthesizeRequest):
         try:
@@ -250,9 +263,10 @@ def make_app(holder, batching=None):
                            "words": [[w["line"], w["index"], w["start"], w["end"]] for w in marks["words"]]}, separators=(",", ":"))
 
     def refuse_stream_voice(req):
-        """A 400 for pitch_scale / intonation_scale / pitch_track on a stream route (the request is at fault, nothing was tried), None at the
-        defaults."""
+        """A 400 for pitch_scale / intonation_scale / pitch_track / compressor on a stream route (the request is at fault, nothing was tried), None
+        at the defaults."""
         try:
+            orchestrator.refuse_dynamics(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_voice(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
         except Exception as e:
