@@ -129,6 +129,27 @@ inline Array3f synthesize(Session& session, const Array2f& bert_ori, const std::
     return out;
 }
 
+// Not in the reference: per-token pitch targets of a fetched request (sbv2_token_pitch in sbv2_hip.h states them).  values: one per token of the
+// listed rows in marks order, 0 = not edited; hz: targets in Hz, else ratios; smooth: contour frames to each side.  applied / src_f0 are filled
+// by fetch_request_token_pitch.
+struct TokenPitch {
+    std::vector<double> values;
+    bool hz = true;
+    int smooth = 2;
+    std::vector<double> applied, src_f0;
+};
+// sbv2_pipeline_fetch_request_token_pitch with owned arrays: voice, track, dynamics, marks and pitch may each be NULL as there.
+inline void fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,
+                                      const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, TokenPitch& tp, void* dst, int64_t capacity_bytes,
+                                      int64_t* out_count, double* stats = nullptr, double* dyn_stats = nullptr, sbv2_marks* marks = nullptr,
+                                      sbv2_pitch* pitch = nullptr) {
+    tp.applied.assign(tp.values.size(), 1.0);
+    tp.src_f0.assign(tp.values.size(), 0.0);
+    const sbv2_token_pitch c{tp.values.data(), (int64_t)tp.values.size(), tp.hz ? 1 : 0, tp.smooth, tp.applied.data(), tp.src_f0.data(), 0};
+    check(sbv2_pipeline_fetch_request_token_pitch(p, ticket, &req, voice, track, dynamics, &c, dst, capacity_bytes, out_count, stats, dyn_stats, marks,
+                                                  pitch));
+}
+
 }  // namespace sbv2_core
 
 #endif

@@ -450,7 +450,8 @@ int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t
  *   of unvoiced frames farther than tau_max + H + 2 samples from a voiced one; no half-width exceeds max(tau_max + 1, sr / 200) + 2, which bounds
  *   the gather.  Dividing by den trades level for the peak bound; the loudness stage downstream restores level.
  * Not built: epoch (glottal) alignment of the marks, contour smoothing, formant shifting, energy compensation (octave-error repair of the
- *   contour is opt-in: sbv2_pitch_track and sbv2_pipeline_fetch_request_tracked below).  No
+ *   contour is opt-in: sbv2_pitch_track and sbv2_pipeline_fetch_request_tracked below; a target per token instead of one pair of scales is
+ *   sbv2_token_pitch and sbv2_pipeline_fetch_request_token_pitch below).  No
  *   stream entry point either: sbv2_stream_* and sbv2_node_* do not take a sbv2_voice. */
 typedef struct sbv2_voice {
     double pitch_scale;          /* [0.5, 2] */
@@ -572,6 +573,64 @@ int32_t sbv2_dynamics_tile(void);
  * doubles per signal. */
 int sbv2_debug_dynamics(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_dynamics* dynamics,
                         double* e_out, int64_t* dq_out, int64_t* u_out, double* s_out, double* y_out, double* stats);
+
+/* ---- new: per-token pitch targets.  The speech marks say that token 17 sits at 212 Hz; this says "make it 180": query, edit the pitch per
+ * token, fetch again.  It is the shifter of sbv2_voice with ONE more factor in the target f0 of a frame; everything not named here is that
+ * section, unchanged.  Targets are per token and not per time, so they survive a re-run whose predicted durations differ.
+ * Tokens of a frame.  Token t of a row owns the native samples [hop c[t], hop c[t + 1]) (c = the running sum of the row's used durations: the
+ *   span rule of sbv2_marks).  Contour frame f (H samples, the voice's hop) belongs to the token whose span holds its centre sample
+ *   min(f H + H / 2, n - 1).  A zero-duration token owns no frame; a row whose durations sum to 0 has one frame that belongs to no token; a
+ *   frame without a token has rho = 65536 (ratio 1).  The frames of a token are consecutive.
+ * Measured mean.  Over the voiced frames of token t: M_t = double(sum llrint(f0_f 65536)) / (65536.0 count_t), an integer sum as the row mean m
+ *   is; f0_f = sr / T_f of the contour the marks are placed by (the tracked one when a sbv2_pitch_track is given).  src_f0_t = M_t, 0 where
+ *   count_t = 0.
+ * Token ratio.  kind 0: r_t = value_t.  kind 1: G_t = p (m + s (M_t - m)) (where the two scales alone would put the token's mean) and
+ *   r_t = min(max(value_t / G_t, 0.5), 2.0), f64, never contracted.  Both: rho_t = llrint(r_t 65536) (int64), and rho_t = 65536 where
+ *   value_t == 0 or (kind 1) count_t == 0; applied_t = double(rho_t) / 65536.0.
+ * Frame ratio.  rho(f) = the rho of the frame's token; with K = smooth and nf the row's frames
+ *   R_f = double(sum_{i = max(f - K, 0)}^{min(f + K, nf - 1)} rho(i)) / (65536.0 double(count)), an integer sum inside the row: nothing crosses
+ *   rows, and any order of summation gives the same bits.  K is taken as given, 0 = steps at the token boundaries.
+ * Target.  g_f = R_f (p (m + s (f0_f - m))), then the clamp to [f0_min / 2, 2 f0_max].  Everything behind g_f is sbv2_voice: T'_f, the
+ *   increments, the marks, the mapping, the windows and the gather.
+ * Hence: the length is unchanged and |y[k]| <= max |x|; where every rho is 65536, R_f = 1.0 exactly, the product is exact and the result is the
+ *   call without the struct, bit for bit; a kind 1 target is honoured in the token's MEAN, before the clamp of g_f and before smoothing (both
+ *   move it: a smoothed edge shares the ratio with the neighbours); what the clamp of r_t did is visible in applied.
+ * Why Q16 ratios averaged linearly and not in the log domain: an integer sum has no order, so R_f has the same bits on any device and in the
+ *   restatement; the arithmetic and the geometric mean of two neighbouring ratios a, b differ by the factor (a + b) / (2 sqrt(a b)), 0.9 % for
+ *   1 next to 1.3 and 6 % for 1 next to 2, and only on the K frames of an edge.  Why the centre rule: a frame is decided by the samples about its centre, and it gives every frame at most one token.
+ * Not built: token pitch on streams (sbv2_stream_*) and on sbv2_node_*, a per-token intonation scale, per-token duration edits, energy
+ *   compensation. */
+typedef struct sbv2_token_pitch {
+    const double* value;      /* [n_tokens]: tokens of the rows in the order of req->utts, token order within a row (the order of sbv2_marks); 0 = token not edited */
+    int64_t n_tokens;         /* must equal the sum of t_lens over the listed rows */
+    int32_t kind;             /* 0 = value is a ratio in [0.5, 2]; 1 = value is the token's target mean f0 in Hz, in [f0_min / 2, 2 f0_max] */
+    int32_t smooth;           /* K in [0, 20] contour frames to each side; taken as given, 0 = steps */
+    double* applied;          /* out, NULL or [n_tokens]: the ratio used for the token (1.0 where not edited) */
+    double* src_f0;           /* out, NULL or [n_tokens]: the token's measured mean f0 before any shift, 0 where it has no voiced frame */
+    int64_t reserved;         /* must be 0 */
+} sbv2_token_pitch;
+/* sbv2_pipeline_fetch_request_dynamics with the listed rows' tokens edited.  token_pitch == NULL, or a value array of all zeros, is exactly that
+ * call: no new launch, the same bytes (with all zeros applied is 1.0 and src_f0 is 0 throughout: nothing was measured).  Otherwise the rows
+ * are shifted as sbv2_voice shifts them, with R_f in the target, also when voice is NULL or the identity (voice == NULL: p = s = 1 and the
+ * voice's defaults); track then tracks the shifter's contour.  The token stage is one phase of the marks kernel: no further launch, no
+ * atomics, no synchronisation beyond the fetch's one; applied and src_f0 reach pinned memory before it and the caller's arrays only after
+ * everything else has succeeded.  The run's PCM is only read: two equal fetches give identical bytes and identical applied / src_f0.
+ * Refused with nothing written: n_tokens different from the rows' token count, a NULL value (with n_tokens > 0), kind outside {0, 1}, smooth
+ * outside [0, 20], a value that is negative, non-finite or outside the kind's range (0 excepted), a non-zero reserved, and everything that
+ * call refuses. */
+int sbv2_pipeline_fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                            const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                            void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats, double* dyn_stats,
+                                            sbv2_marks* marks, sbv2_pitch* pitch);
+/* Test hook: sbv2_debug_voice_shift with a token table, always through the kernels (all zeros included).  tok_counts [nrows]: tokens of every
+ * row; tok_ends [sum tok_counts]: the end position of every token in samples of its row, ascending within a row from 0 (token t owns
+ * [end[t - 1], end[t]), the first from 0; arbitrary positions, also beyond the row: the hook needs no model); token_pitch as in the fetch, its
+ * n_tokens = sum tok_counts.  Outputs besides sbv2_debug_voice_shift's: ratio_out [frames] = R_f (may be NULL), token_pitch->applied and
+ * ->src_f0. */
+int sbv2_debug_voice_tokens(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
+                            const double* period_in, const int32_t* voiced_in, const int64_t* tok_counts, const int64_t* tok_ends,
+                            const sbv2_token_pitch* token_pitch, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts, int32_t* map,
+                            int64_t* n_marks, float* y, double* ratio_out);
 
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */

@@ -112,6 +112,12 @@ class Sbv2PitchTrack(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class Sbv2TokenPitch(C.Structure):
+    """struct sbv2_token_pitch (include/sbv2_hip.h)."""
+    _fields_ = [("value", C.POINTER(C.c_double)), ("n_tokens", C.c_int64), ("kind", C.c_int32), ("smooth", C.c_int32),
+                ("applied", C.POINTER(C.c_double)), ("src_f0", C.POINTER(C.c_double)), ("reserved", C.c_int64)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -161,6 +167,13 @@ SYMBOLS = {
     "sbv2_pipeline_fetch_request_dynamics": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
                                                        C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.c_void_p, C.c_int64, i64p,
                                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_pipeline_fetch_request_token_pitch": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                          C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch), C.c_void_p,
+                                                          C.c_int64, i64p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Sbv2Marks),
+                                                          C.POINTER(Sbv2Pitch)]),
+    "sbv2_debug_voice_tokens": (C.c_int, [C.c_int, f32p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Voice), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                          i64p, i64p, C.POINTER(Sbv2TokenPitch), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64p, f32p, C.POINTER(C.c_double)]),
     "sbv2_dynamics_tile": (C.c_int32, []),
     "sbv2_debug_dynamics": (C.c_int, [C.c_int, C.c_void_p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Dynamics), C.POINTER(C.c_double), i64p, i64p,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -180,7 +180,8 @@ class RequestBatcher:
                         audio = orchestrator.finish_request(self.pipe, b, r0, r1, req.plan, marks=got)
                         req.future.set_result((audio, got[0]))
                         continue
-                    if pcm is None and req.plan.gain is None and req.plan.fmt.is_default and orchestrator.voice_options(req.plan.options) is None:
+                    if (pcm is None and req.plan.gain is None and req.plan.fmt.is_default and orchestrator.voice_options(req.plan.options) is None
+                            and getattr(req.plan, "token_pitch", None) is None):
                         pcm = self.pipe.fetch(b)   # the plain f32 requests of a run share one fetch
                     req.future.set_result(orchestrator.finish_request(self.pipe, b, r0, r1, req.plan, pcm=pcm))
                 except Exception as e:

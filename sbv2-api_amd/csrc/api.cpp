@@ -520,6 +520,19 @@ static VoiceSpec check_voice_static(const sbv2_voice* v, int rate) {
     return voice_spec(rate, v->pitch_scale, v->intonation_scale, v->hop, v->f0_min, v->f0_max, v->threshold);
 }
 
+// The checks of sbv2_token_pitch that need no run (voice.h states the bounds; vs: the voice's checked parameters, the defaults without a voice)
+// -> whether any token is edited.
+static VoiceSpec default_voice_spec() { return voice_spec(kNativeRate, 1.0, 1.0, 0, 0.0, 0.0, 0.0); }
+static bool check_token_pitch_static(const sbv2_token_pitch* t, const VoiceSpec& vs) {
+    SBV2_REQUIRE(t->reserved == 0, "sbv2_token_pitch.reserved must be 0");
+    SBV2_REQUIRE(t->n_tokens >= 0, "sbv2_token_pitch.n_tokens must be >= 0: " + std::to_string(t->n_tokens));
+    SBV2_REQUIRE(t->value || t->n_tokens == 0, "sbv2_token_pitch.value must not be NULL");
+    voice_tokens_check(t->value, t->n_tokens, t->kind, t->smooth, vs);
+    for (int64_t i = 0; i < t->n_tokens; ++i)
+        if (t->value[i] != 0.0) return true;
+    return false;
+}
+
 // The checks of sbv2_pitch_track (track.h states the bounds).
 static TrackSpec check_track_static(const sbv2_pitch_track* t) {
     SBV2_REQUIRE(t->reserved[0] == 0 && t->reserved[1] == 0, "sbv2_pitch_track.reserved must be 0");
@@ -538,10 +551,13 @@ static TrackSpec check_track_static(const sbv2_pitch_track* t) {
 // like the run's packed PCM, and the pieces point there; the run's PCM is only read.
 // track (with pitch, or with a voice that shifts): both contours are tracked (Track, track.h) before they are used.
 // gain.dyn (with a loudness or limiter stage): the compressor runs on y first (Dynamics, dynamics.h); dyn_stats (may be NULL): its 3 doubles.
+// tp (with utts; NULL or all zeros: nothing): the listed rows' tokens are edited in the shifter (its token phase, voice.h), which then runs
+// whatever the voice is; applied / src_f0 reach the caller's arrays only once everything else has succeeded.
 static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
                             int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats,
                             const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr,
-                            const sbv2_voice* voice = nullptr, const sbv2_pitch_track* track = nullptr, double* dyn_stats = nullptr) {
+                            const sbv2_voice* voice = nullptr, const sbv2_pitch_track* track = nullptr, double* dyn_stats = nullptr,
+                            const sbv2_token_pitch* tp = nullptr) {
     const DynamicsSpec dyn = gain.dyn ? dynamics_spec(gain.dyn) : DynamicsSpec();
     const bool compress = gain.dyn && !dyn.identity();
     const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
@@ -574,12 +590,36 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
     if (voice) {
         SBV2_REQUIRE(utts && place, "internal: voice needs a request's rows");
         vs = check_voice_static(voice, kNativeRate);
+    } else if (tp) {
+        vs = default_voice_spec();
     }
-    const bool shift = voice && !vs.identity() && n_utts > 0;
+    bool edit = false;
+    std::vector<int64_t> tok_counts, tok_ends;
+    if (tp) {
+        SBV2_REQUIRE(utts && place, "internal: token pitch needs a request's rows");
+        edit = check_token_pitch_static(tp, vs);
+        const std::vector<int64_t>& offs = vm.used_offs();
+        const std::vector<int64_t>& used = vm.used_durations();
+        SBV2_REQUIRE(offs.size() == vm.pcm_lens().size() + 1, "internal: the run kept no durations");
+        int64_t n_tok = 0;
+        for (int k = 0; k < n_utts; ++k) n_tok += offs[utts[k] + 1] - offs[utts[k]];
+        SBV2_REQUIRE(tp->n_tokens == n_tok, "sbv2_token_pitch.n_tokens is " + std::to_string(tp->n_tokens) + " but the listed rows have " +
+                                                std::to_string(n_tok) + " tokens");
+        if (edit) {   // token t of a row ends at hop c[t + 1]
+            tok_ends.reserve((size_t)n_tok);
+            for (int k = 0; k < n_utts; ++k) {
+                tok_counts.push_back(offs[utts[k] + 1] - offs[utts[k]]);
+                int64_t c = 0;
+                for (int64_t e = offs[utts[k]]; e < offs[utts[k] + 1]; ++e) tok_ends.push_back((c += used[(size_t)e]) * vm.cfg().hop());
+            }
+        }
+    }
+    const bool shift = ((voice && !vs.identity()) || edit) && n_utts > 0;
     TrackSpec ts;
     if (track) {
         ts = check_track_static(track);
-        SBV2_REQUIRE(pitch || (voice && !vs.identity()), "pitch tracking needs a pitch contour or a voice that is not the identity");
+        SBV2_REQUIRE(pitch || (voice && !vs.identity()) || edit,
+                     "pitch tracking needs a pitch contour or a voice that is not the identity");
     }
     HIP_CHECK(hipSetDevice(vm.device()));
     OutputChain& c = p->chains[ctx];
@@ -588,7 +628,8 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         std::vector<VoiceRow> rows((size_t)n_utts);
         for (int k = 0; k < n_utts; ++k) rows[k] = VoiceRow{vm.pcm_offs()[utts[k]], vm.pcm_lens()[utts[k]]};
         const float* pcm = vm.pcm_device();
-        const float* shifted = c.voice.run(pcm, vm.pcm_total(), rows.data(), n_utts, vs, s, nullptr, nullptr, track ? &ts : nullptr);
+        const VoiceTokens vt{tok_counts.data(), tok_ends.data(), edit ? tp->value : nullptr, edit ? tp->kind : 0, edit ? tp->smooth : 0};
+        const float* shifted = c.voice.run(pcm, vm.pcm_total(), rows.data(), n_utts, vs, s, nullptr, nullptr, track ? &ts : nullptr, edit ? &vt : nullptr);
         for (FmtPiece& pc : pieces) pc.src = shifted + (pc.src - pcm);
     }
     if (sink == Sink::kPcm && gain.kind == FetchGain::kNone && spec.identity() && !place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
@@ -640,6 +681,12 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         }
         marks->n_tokens = mp.n_tok;
         marks->n_env = mp.n_env;
+    }
+    if (tp) {   // (all zeros: nothing was measured)
+        for (int64_t t = 0; t < tp->n_tokens; ++t) {
+            if (tp->applied) tp->applied[t] = edit && shift ? c.voice.applied_host()[t] : 1.0;
+            if (tp->src_f0) tp->src_f0[t] = edit && shift ? c.voice.src_f0_host()[t] : 0.0;
+        }
     }
     if (pitch) {   // (an empty signal has no frames and ran nothing)
         for (int64_t f = 0; f < n_pitch; ++f) {
@@ -723,17 +770,19 @@ int32_t sbv2_voice_tile(void) { return Voice::kTile; }
 
 int32_t sbv2_dynamics_tile(void) { return Dynamics::kTile; }
 
-int sbv2_pipeline_fetch_request_dynamics(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
-                                         const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, void* dst, int64_t capacity_bytes,
-                                         int64_t* out_count, double* stats, double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch) {
+int sbv2_pipeline_fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                            const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                            void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats, double* dyn_stats,
+                                            sbv2_marks* marks, sbv2_pitch* pitch) {
     API_BEGIN
     DynamicsSpec ds;
     if (dynamics) ds = dynamics_spec(dynamics);   // what needs no run is refused before the handle is looked at
     VoiceSpec vs;
     if (voice) vs = check_voice_static(voice, kNativeRate);   // what needs no run is refused before the handle is looked at
+    const bool edit = token_pitch && check_token_pitch_static(token_pitch, voice ? vs : default_voice_spec());
     if (track) {
         (void)check_track_static(track);
-        SBV2_REQUIRE(pitch || (voice && !vs.identity()), "pitch tracking needs a pitch contour or a voice that is not the identity");
+        SBV2_REQUIRE(pitch || (voice && !vs.identity()) || edit, "pitch tracking needs a pitch contour or a voice that is not the identity");
     }
     SBV2_REQUIRE(req && req->n_utts >= 0 && (req->n_utts == 0 || (req->utts && req->place)), "bad fetch request");
     SBV2_REQUIRE(!(req->loudness && req->limiter), "a fetch request takes a loudness target or a limiter, not both");
@@ -752,8 +801,15 @@ int sbv2_pipeline_fetch_request_dynamics(sbv2_pipeline* p, int64_t ticket, const
     static const int32_t no_rows[1] = {0};
     static const int64_t no_place[1] = {0};
     fetch_formatted(p, ticket, req->fmt, gain, req->n_utts ? req->place : no_place, req->joined_len, req->flac ? Sink::kFlac : Sink::kPcm, dst,
-                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch, voice, track, dyn_stats);
+                    capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch, voice, track, dyn_stats,
+                    token_pitch);
     API_END
+}
+int sbv2_pipeline_fetch_request_dynamics(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                         const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, void* dst, int64_t capacity_bytes,
+                                         int64_t* out_count, double* stats, double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch) {
+    return sbv2_pipeline_fetch_request_token_pitch(p, ticket, req, voice, track, dynamics, nullptr, dst, capacity_bytes, out_count, stats, dyn_stats,
+                                                   marks, pitch);
 }
 int sbv2_pipeline_fetch_request_tracked(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
                                         const sbv2_pitch_track* track, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,

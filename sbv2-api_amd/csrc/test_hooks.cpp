@@ -2111,9 +2111,11 @@ int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, i
 }
 
 // The shifter (Voice, voice.hip) on host rows laid back to back, always through its kernels; everything is checked before any device call.
-int sbv2_debug_voice_shift(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
-                           const double* period_in, const int32_t* voiced_in, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts,
-                           int32_t* map, int64_t* n_marks, float* y) {
+// tp (with tok_counts / tok_ends): the per-token edits, through k_voice_marks_tok whatever the values are.
+static int debug_voice(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
+                       const double* period_in, const int32_t* voiced_in, const int64_t* tok_counts, const int64_t* tok_ends,
+                       const sbv2_token_pitch* tp, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts, int32_t* map, int64_t* n_marks,
+                       float* y, double* ratio_out) {
     API_BEGIN
     SBV2_REQUIRE(voice && nrows >= 0 && (nrows == 0 || lens), "bad arguments");
     SBV2_REQUIRE(voice->reserved == 0, "sbv2_voice.reserved must be 0");
@@ -2128,10 +2130,30 @@ int sbv2_debug_voice_shift(int device, const float* x, const int64_t* lens, int 
         total += lens[i];
     }
     SBV2_REQUIRE(total == 0 || (x && y), "bad arguments");
+    VoiceTokens vt{};
+    if (tp) {
+        SBV2_REQUIRE(nrows == 0 || tok_counts, "bad arguments");
+        SBV2_REQUIRE(tp->reserved == 0, "sbv2_token_pitch.reserved must be 0");
+        int64_t n_tok = 0;
+        for (int i = 0; i < nrows; ++i) {
+            SBV2_REQUIRE(tok_counts[i] >= 0 && tok_counts[i] < (1 << 30), "bad token count of row " + std::to_string(i));
+            n_tok += tok_counts[i];
+        }
+        SBV2_REQUIRE(tp->n_tokens == n_tok, "sbv2_token_pitch.n_tokens is " + std::to_string(tp->n_tokens) + " but the listed rows have " +
+                                                std::to_string(n_tok) + " tokens");
+        SBV2_REQUIRE(n_tok == 0 || (tp->value && tok_ends), "sbv2_token_pitch.value must not be NULL");
+        voice_tokens_check(tp->value, n_tok, tp->kind, tp->smooth, sp);
+        for (int i = 0, e = 0; i < nrows; ++i)
+            for (int64_t t = 0, prev = 0; t < tok_counts[i]; ++t, ++e) {
+                SBV2_REQUIRE(tok_ends[e] >= prev, "the token ends of row " + std::to_string(i) + " must ascend from 0");
+                prev = tok_ends[e];
+            }
+        vt = VoiceTokens{tok_counts, tok_ends, tp->value, tp->kind, tp->smooth};
+    }
     HIP_CHECK(hipSetDevice(device));
     DevMem dx(x, sizeof(float) * (size_t)total);
     Voice v;
-    const float* dy = v.run(dx.f(), total, rows.data(), nrows, sp, nullptr, period_in, voiced_in);
+    const float* dy = v.run(dx.f(), total, rows.data(), nrows, sp, nullptr, period_in, voiced_in, nullptr, tp ? &vt : nullptr);
     v.results_to_host(nullptr);
     HIP_CHECK(hipStreamSynchronize(nullptr));
     for (int i = 0; i < nrows; ++i) SBV2_REQUIRE(v.status(i) == 0, "internal: the shifter found more marks than it planned for in row " + std::to_string(i));
@@ -2151,7 +2173,29 @@ int sbv2_debug_voice_shift(int device, const float* x, const int64_t* lens, int 
             at += lens[i] + 1;
         }
     }
+    if (tp) {
+        if (ratio_out) std::memcpy(ratio_out, v.ratio_host(), sizeof(double) * (size_t)v.n_frames());
+        if (tp->applied) std::memcpy(tp->applied, v.applied_host(), sizeof(double) * (size_t)v.n_tokens());
+        if (tp->src_f0) std::memcpy(tp->src_f0, v.src_f0_host(), sizeof(double) * (size_t)v.n_tokens());
+    }
     API_END
+}
+int sbv2_debug_voice_shift(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
+                           const double* period_in, const int32_t* voiced_in, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts,
+                           int32_t* map, int64_t* n_marks, float* y) {
+    return debug_voice(device, x, lens, nrows, sample_rate, voice, period_in, voiced_in, nullptr, nullptr, nullptr, period_out, voiced_out, ta, ts, map,
+                       n_marks, y, nullptr);
+}
+int sbv2_debug_voice_tokens(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
+                            const double* period_in, const int32_t* voiced_in, const int64_t* tok_counts, const int64_t* tok_ends,
+                            const sbv2_token_pitch* token_pitch, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts, int32_t* map,
+                            int64_t* n_marks, float* y, double* ratio_out) {
+    if (!token_pitch) {
+        set_last_error("bad arguments");
+        return 1;
+    }
+    return debug_voice(device, x, lens, nrows, sample_rate, voice, period_in, voiced_in, tok_counts, tok_ends, token_pitch, period_out, voiced_out, ta,
+                       ts, map, n_marks, y, ratio_out);
 }
 
 // The fed level reduction (StreamLevels, marks.hip) on its own: x cut at cuts[ncuts] into ncuts + 1 pushes, each handed the samples of its

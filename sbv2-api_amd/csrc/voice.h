@@ -2,6 +2,8 @@
 // api.cpp), as include/sbv2_hip.h states it above sbv2_voice.  Used by sbv2_pipeline_fetch_request_voice and the test hook sbv2_debug_voice_shift.
 // Three steps on one stream: the YIN contour of every listed row (k_pitch_yin of marks.hip on f32, one launch per row), the marks of every row
 // (k_voice_marks, one workgroup per row: mean f0, phase increments, ta / ts / map) and the overlap-add gather (k_voice_gather, the hot path).
+// Per-token pitch targets (sbv2_token_pitch, sbv2_pipeline_fetch_request_token_pitch, sbv2_debug_voice_tokens) are one more phase of the marks
+// kernel, launched as k_voice_marks_tok only by a call that brings a token table.
 #pragma once
 #include "common.h"
 #include "marks.h"
@@ -29,6 +31,18 @@ struct VoiceRow {
     int64_t off, n;
 };
 
+// Per-token pitch edits of a call, as include/sbv2_hip.h states them above sbv2_token_pitch.  HOST arrays, the rows' tokens back to back: token t
+// of a row owns the samples [ends[t - 1], ends[t]) of that row (the first from 0); ends ascend within a row and may lie beyond its length.
+struct VoiceTokens {
+    const int64_t* counts;   // [nrows] tokens of every row
+    const int64_t* ends;     // [sum counts]
+    const double* value;     // [sum counts] 0 = not edited
+    int kind, smooth;        // 0 = ratio, 1 = Hz; K contour frames to each side
+};
+constexpr int kVoiceMaxSmooth = 20;
+// throws: kind in {0, 1}, smooth in [0, 20], every value 0 or in [0.5, 2] (kind 0) / [f0_min / 2, 2 f0_max] (kind 1); a NaN is refused
+void voice_tokens_check(const double* value, int64_t n_tokens, int kind, int smooth, const VoiceSpec& sp);
+
 // Device state of the shifter of one execution context: the contour, the per-frame phases, the marks and the shifted rows, grown on demand;
 // nothing is allocated before the first run.  No atomics; every sum's order is fixed, so equal rows give equal bits.
 class Voice {
@@ -42,8 +56,11 @@ class Voice {
     // instead of the estimated one; a voiced entry outside [tau_min - 1, tau_max + 1] is refused.  Rows and parameters are checked before
     // anything is enqueued (throws).
     // tr (not with a given contour): the estimated contour is tracked, every row apart from the others, before the marks are placed (track.h).
+    // tok: the per-token edits (checked here, throws); k_voice_marks_tok then forms M_t, rho_t and R_f between the contour and the marks, and
+    // applied / src_f0 are on their way to pinned memory when run returns.  Without tok every launch, argument and byte is that of a call
+    // from before token edits existed.
     float* run(const float* x, int64_t span, const VoiceRow* rows, int nrows, const VoiceSpec& sp, hipStream_t s, const double* period_in = nullptr,
-               const int32_t* voiced_in = nullptr, const TrackSpec* tr = nullptr);
+               const int32_t* voiced_in = nullptr, const TrackSpec* tr = nullptr, const VoiceTokens* tok = nullptr);
     // Results of the last run for the test hook, valid once results_to_host() has been enqueued and s synchronised: per frame (rows back to
     // back) the period T_f and voiced; per row the marks at mark_off(i), n_a(i) analysis and n_s(i) synthesis ones.
     void results_to_host(hipStream_t s);
@@ -56,19 +73,25 @@ class Voice {
     const int32_t* ta_host(int i) const { return h_ta_ + cap_off_[i]; }
     const int32_t* ts_host(int i) const { return h_ts_ + cap_off_[i]; }
     const int32_t* map_host(int i) const { return h_map_ + cap_off_[i]; }
+    // Of a run with a token table, valid once s is synchronised: per token applied and src_f0; per frame R_f (after results_to_host()).
+    int64_t n_tokens() const { return nt_ > 0 ? nt_ : 0; }
+    const double* applied_host() const { return h_tout_; }
+    const double* src_f0_host() const { return h_tout_ + n_tokens(); }
+    const double* ratio_host() const { return h_ratio_; }
 
   private:
     DeviceBuffer dev_, out_;   // tables | contour | phases | marks (| the candidates of a tracked contour) ; the shifted rows
     Track track_;
     PinnedBuffer host_;
     std::vector<int64_t> cap_off_;
-    int64_t nf_ = 0, ncap_ = 0;
+    int64_t nf_ = 0, ncap_ = 0, nt_ = -1;   // nt_ < 0: the last run had no token table
     int nrows_ = 0;
     // the layout of the last run (device pointers and the pinned mirror's)
     double* d_period_ = nullptr;
     int32_t *d_voiced_ = nullptr, *d_count_ = nullptr, *d_ta_ = nullptr, *d_ts_ = nullptr, *d_map_ = nullptr;
     double* h_period_ = nullptr;
     int32_t *h_voiced_ = nullptr, *h_count_ = nullptr, *h_ta_ = nullptr, *h_ts_ = nullptr, *h_map_ = nullptr;
+    double *d_tout_ = nullptr, *d_ratio_ = nullptr, *h_tout_ = nullptr, *h_ratio_ = nullptr;
 };
 
 }  // namespace sbv2

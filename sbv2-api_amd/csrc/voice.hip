@@ -12,6 +12,11 @@
 //     time with their analysis mark's position and its two half-widths, and every lane walks them in ascending j, adding w and w x in f64 where
 //     the window covers its sample.  A staged mark is a broadcast read; x[ta + u] is consecutive across lanes.  Reads stay inside the row:
 //     ta - L >= -1 and ta + R <= n by the definition of L and R, and the index is checked besides.
+// Per-token pitch edits (sbv2_token_pitch) are one more phase of k_voice_marks, in a second instantiation of it (k_voice_marks_tok) that only a call
+// with a token table launches: between the row's mean and the increments, where T_f and m are at hand.  The frames' llrint(f0 65536) and voiced
+// flags are prefix-summed over the row (an LDS scan, kBlock frames at a time), lanes take tokens (M_t from two prefix entries, rho_t, applied,
+// src_f0), lanes take frames (the frame's token by bisection of the tokens' frame ends, then the integer window sum R_f).  Nothing loops over a
+// token's frames or a frame's tokens, so a token that is the whole row and a row of a thousand empty tokens cost the same.
 #include "voice.h"
 
 #include <cmath>
@@ -50,6 +55,23 @@ struct VoiceMarkArgs {
     int32_t tau_max;
 };
 
+struct VoiceTokRowDev {   // the tokens of one row in the token arrays
+    int64_t t_off, nt;
+};
+
+struct VoiceTokArgs {
+    const VoiceTokRowDev* rows;
+    const double* value;      // [NT] the edit of every token, 0 = none
+    const int32_t* fend;      // [NT] frames of the row whose centre lies before the token's end (ascending within a row)
+    double *applied, *src;    // [NT] out
+    int64_t* fq;              // [NF] llrint(f0 65536) of a voiced frame, 0 otherwise; then its inclusive prefix sum within the row
+    int32_t* fc;              // [NF] the inclusive prefix count of voiced frames within the row
+    int32_t* rho_t;           // [NT]
+    int32_t* rho_f;           // [NF] the rho of the frame's token, 65536 where it has none
+    double* ratio;            // [NF] R_f
+    int32_t kind, smooth;
+};
+
 constexpr double kTwo32 = 4294967296.0;
 
 // the marks of one frame: positions k = first + c - 1 for the c at which phi + c inc reaches the next integers (0 < inc <= 2^32: at most one a sample)
@@ -61,7 +83,84 @@ __device__ inline void place_marks(int64_t phi, int64_t inc, int64_t len, int64_
     }
 }
 
-__global__ __launch_bounds__(kBlock) void k_voice_marks(const VoiceMarkArgs a) {
+// The per-token phase of k_voice_marks_tok: fq / voiced of the row are written, m is its mean.  sh_q / sh_c are the kernel's reduction arrays.
+__device__ inline void token_ratios(const VoiceMarkArgs& a, const VoiceTokArgs& t, const VoiceRowDev& r, double m, int64_t* sh_q, int32_t* sh_c) {
+    const int tid = threadIdx.x;
+    const int64_t nf = r.nf;
+    const VoiceTokRowDev tr = t.rows[blockIdx.x];
+    __syncthreads();   // every lane has read the row's sums
+    // inclusive prefix sums of q and voiced over the row's frames (integers: any order gives these values)
+    int64_t carry_q = 0;
+    int32_t carry_c = 0;
+    for (int64_t base = 0; base < nf; base += kBlock) {
+        const int64_t f = base + tid, F = r.f_off + f;
+        sh_q[tid] = f < nf ? t.fq[F] : 0;
+        sh_c[tid] = f < nf ? a.voiced[F] : 0;
+        __syncthreads();
+        for (int d = 1; d < kBlock; d <<= 1) {
+            const int64_t q = tid >= d ? sh_q[tid - d] : 0;
+            const int32_t c = tid >= d ? sh_c[tid - d] : 0;
+            __syncthreads();
+            sh_q[tid] += q;
+            sh_c[tid] += c;
+            __syncthreads();
+        }
+        if (f < nf) {
+            t.fq[F] = carry_q + sh_q[tid];
+            t.fc[F] = carry_c + sh_c[tid];
+        }
+        carry_q += sh_q[kBlock - 1];
+        carry_c += sh_c[kBlock - 1];
+        __syncthreads();
+    }
+    // lanes take tokens: the measured mean, the ratio
+    for (int64_t i = tid; i < tr.nt; i += kBlock) {
+        const int64_t I = tr.t_off + i;
+        const int64_t fb = min((int64_t)(i ? t.fend[I - 1] : 0), nf), fe = min((int64_t)t.fend[I], nf);
+        int64_t q = 0;
+        int32_t c = 0;
+        if (fe > fb) {
+            q = t.fq[r.f_off + fe - 1] - (fb ? t.fq[r.f_off + fb - 1] : 0);
+            c = t.fc[r.f_off + fe - 1] - (fb ? t.fc[r.f_off + fb - 1] : 0);
+        }
+        const double M = c ? (double)q / (65536.0 * (double)c) : 0.0;
+        const double val = t.value[I];
+        int64_t rho = 65536;
+        if (val != 0.0) {
+            if (t.kind == 0) {
+                rho = llrint(val * 65536.0);
+            } else if (c) {
+                const double G = a.p * (m + a.s * (M - m));
+                rho = llrint(fmin(fmax(val / G, 0.5), 2.0) * 65536.0);
+            }
+        }
+        t.rho_t[I] = (int32_t)rho;
+        t.applied[I] = (double)rho / 65536.0;
+        t.src[I] = M;
+    }
+    __syncthreads();
+    // lanes take frames: the frame's token is the first whose frames end behind it
+    for (int64_t f = tid; f < nf; f += kBlock) {
+        int64_t lo = 0, hi = tr.nt;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) / 2;
+            if (t.fend[tr.t_off + mid] <= f) lo = mid + 1;
+            else hi = mid;
+        }
+        t.rho_f[r.f_off + f] = lo < tr.nt ? t.rho_t[tr.t_off + lo] : 65536;
+    }
+    __syncthreads();
+    for (int64_t f = tid; f < nf; f += kBlock) {
+        const int64_t i0 = max(f - t.smooth, (int64_t)0), i1 = min(f + t.smooth, nf - 1);
+        int64_t sum = 0;
+        for (int64_t i = i0; i <= i1; ++i) sum += t.rho_f[r.f_off + i];
+        t.ratio[r.f_off + f] = (double)sum / (65536.0 * (double)(i1 - i0 + 1));
+    }
+}
+
+// kTok: with the per-token phase and R_f in the target; without, t is not looked at and the code is what it was before token edits existed
+template <bool kTok>
+__device__ __forceinline__ void voice_marks_body(const VoiceMarkArgs& a, const VoiceTokArgs* t) {
     __shared__ int64_t sh_sum[kBlock];
     __shared__ int32_t sh_cnt[kBlock];
     __shared__ int32_t sh_n[2];
@@ -91,8 +190,12 @@ __global__ __launch_bounds__(kBlock) void k_voice_marks(const VoiceMarkArgs a) {
         }
         a.voiced[F] = v;
         if (v) {
-            sum += llrint((a.sr / T) * 65536.0);
+            const int64_t q = llrint((a.sr / T) * 65536.0);
+            sum += q;
             ++cnt;
+            if constexpr (kTok) t->fq[F] = q;
+        } else if constexpr (kTok) {
+            t->fq[F] = 0;
         }
     }
     sh_sum[tid] = sum;
@@ -104,6 +207,7 @@ __global__ __launch_bounds__(kBlock) void k_voice_marks(const VoiceMarkArgs a) {
     }
     const int32_t nv = sh_cnt[0];
     const double m = nv ? (double)sh_sum[0] / (65536.0 * (double)nv) : 0.0;
+    if constexpr (kTok) token_ratios(a, *t, r, m, sh_sum, sh_cnt);
     // the increments
     for (int64_t f = tid; f < nf; f += kBlock) {
         const int64_t F = r.f_off + f;
@@ -111,6 +215,7 @@ __global__ __launch_bounds__(kBlock) void k_voice_marks(const VoiceMarkArgs a) {
         if (a.voiced[F]) {
             const double T = a.period[F], f0 = a.sr / T;
             double g = a.p * (m + a.s * (f0 - m));
+            if constexpr (kTok) g = t->ratio[F] * g;
             g = fmin(fmax(g, a.g_lo), a.g_hi);
             const double Tp = a.sr / g;
             ia = llrint(kTwo32 / T);
@@ -176,6 +281,9 @@ __global__ __launch_bounds__(kBlock) void k_voice_marks(const VoiceMarkArgs a) {
         mp[j] = m1;
     }
 }
+
+__global__ __launch_bounds__(kBlock) void k_voice_marks(const VoiceMarkArgs a) { voice_marks_body<false>(a, nullptr); }
+__global__ __launch_bounds__(kBlock) void k_voice_marks_tok(const VoiceMarkArgs a, const VoiceTokArgs t) { voice_marks_body<true>(a, &t); }
 
 struct VoiceGatherArgs {
     const VoiceRowDev* rows;
@@ -282,8 +390,19 @@ VoiceSpec voice_spec(int sample_rate, double pitch_scale, double intonation_scal
     return v;
 }
 
+void voice_tokens_check(const double* value, int64_t n_tokens, int kind, int smooth, const VoiceSpec& sp) {
+    SBV2_REQUIRE(n_tokens >= 0 && (value || n_tokens == 0), "token pitch: value must not be NULL");
+    SBV2_REQUIRE(kind == 0 || kind == 1, "token pitch: kind must be 0 (ratio) or 1 (Hz): " + std::to_string(kind));
+    SBV2_REQUIRE(smooth >= 0 && smooth <= kVoiceMaxSmooth, "token pitch: smooth must be in [0, " + std::to_string(kVoiceMaxSmooth) + "]: " + std::to_string(smooth));
+    const double lo = kind == 0 ? 0.5 : sp.g_lo, hi = kind == 0 ? 2.0 : sp.g_hi;
+    for (int64_t t = 0; t < n_tokens; ++t)   // (a NaN fails both comparisons)
+        SBV2_REQUIRE(value[t] == 0.0 || (value[t] >= lo && value[t] <= hi),
+                     "token pitch: value of token " + std::to_string(t) + " must be 0 or in [" + std::to_string(lo) + ", " + std::to_string(hi) + "] (" +
+                         (kind == 0 ? "a ratio" : "Hz") + "): " + std::to_string(value[t]));
+}
+
 float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows, const VoiceSpec& sp, hipStream_t s, const double* period_in,
-                  const int32_t* voiced_in, const TrackSpec* tr) {
+                  const int32_t* voiced_in, const TrackSpec* tr, const VoiceTokens* tok) {
     SBV2_REQUIRE(nrows >= 0 && nrows <= 65535 && span >= 0 && (nrows == 0 || rows), "voice: bad rows");
     SBV2_REQUIRE(!period_in == !voiced_in, "voice: period_in and voiced_in are given together or not at all");
     const int64_t hop = sp.pitch.hop;
@@ -309,9 +428,37 @@ float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows,
         for (int64_t f = 0; f < NF; ++f)
             SBV2_REQUIRE(!voiced_in[f] || (period_in[f] >= sp.pitch.tau_min - 1 && period_in[f] <= sp.pitch.tau_max + 1),
                          "voice: period_in of voiced frame " + std::to_string(f) + " is outside [tau_min - 1, tau_max + 1]: " + std::to_string(period_in[f]));
+    // the token table: every token's frames by the centre rule, a running frame index per row (the centres ascend, and so do the ends)
+    std::vector<VoiceTokRowDev> trd;
+    std::vector<int32_t> fend;
+    int64_t NT = 0;
+    if (tok) {
+        SBV2_REQUIRE(nrows == 0 || tok->counts, "voice: the token table needs the rows' token counts");
+        trd.resize((size_t)nrows);
+        for (int i = 0; i < nrows; ++i) {
+            SBV2_REQUIRE(tok->counts[i] >= 0 && tok->counts[i] < (1 << 30), "voice: bad token count of row " + std::to_string(i));
+            trd[i] = VoiceTokRowDev{NT, tok->counts[i]};
+            NT += tok->counts[i];
+            SBV2_REQUIRE(NT < (1 << 30), "voice: too many tokens in one call");
+        }
+        SBV2_REQUIRE(NT == 0 || tok->ends, "voice: the token table needs the tokens' ends");
+        voice_tokens_check(tok->value, NT, tok->kind, tok->smooth, sp);
+        fend.resize((size_t)NT);
+        for (int i = 0; i < nrows; ++i) {
+            int64_t f = 0, prev = 0;
+            for (int64_t t = 0; t < trd[i].nt; ++t) {
+                const int64_t e = tok->ends[trd[i].t_off + t];
+                SBV2_REQUIRE(e >= prev, "voice: the token ends of row " + std::to_string(i) + " must ascend from 0");
+                while (f < rd[i].nf && std::min(f * hop + hop / 2, rd[i].n - 1) < e) ++f;
+                fend[(size_t)(trd[i].t_off + t)] = (int32_t)f;
+                prev = e;
+            }
+        }
+    }
     nrows_ = nrows;
     nf_ = NF;
     ncap_ = NCAP;
+    nt_ = tok ? NT : -1;
     float* y = static_cast<float*>(out_.reserve(sizeof(float) * (size_t)std::max<int64_t>(span, 16), s));
     if (nrows == 0) return y;
     // device: rows | c3 | period | inc_a inc_s phi_a phi_s | lag yvoiced voiced off_a off_s | count | ta ts map   (8-byte parts first)
@@ -319,11 +466,18 @@ float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows,
     const size_t o_c3 = round_up64(sizeof(VoiceRowDev) * nrows, 64), o_period = o_c3 + 24 * nF, o_i64 = o_period + 8 * nF, o_i32 = o_i64 + 32 * nF,
                  o_count = round_up64(o_i32 + 20 * nF, 64), o_marks = o_count + round_up64(16 * (size_t)nrows, 64),
                  o_cand_c3 = round_up64(o_marks + 12 * nC, 64), o_cand = o_cand_c3 + 24 * kTrackCand * nF,
-                 bytes = tr && !period_in ? o_cand + 4 * kTrackRec * nF : o_marks + 12 * nC;
+                 bytes0 = tr && !period_in ? o_cand + 4 * kTrackRec * nF : o_marks + 12 * nC;
+    // with a token table, behind everything else: token rows | value | fend (the upload) ; applied | src ; fq | ratio ; rho_t | fc | rho_f
+    const size_t nT = (size_t)std::max<int64_t>(NT, 0), up_bytes = sizeof(VoiceTokRowDev) * (size_t)nrows + 12 * nT, o_up = round_up64(bytes0, 64),
+                 o_tout = round_up64(o_up + up_bytes, 64), o_fq = o_tout + 16 * nT, o_ratio = o_fq + 8 * nF, o_rho_t = o_ratio + 8 * nF,
+                 o_fc = o_rho_t + 4 * nT, o_rho_f = o_fc + 4 * nF, bytes = tok ? o_rho_f + 4 * nF : bytes0;
     // pinned: rows | period | voiced (the upload) ; period | voiced | count | ta ts map (the mirror)
     const size_t h_period_in = round_up64(sizeof(VoiceRowDev) * nrows, 64), h_voiced_in = h_period_in + 8 * nF, h_mirror = round_up64(h_voiced_in + 4 * nF, 64),
                  h_voiced = h_mirror + 8 * nF, h_count = round_up64(h_voiced + 4 * nF, 64), h_marks = h_count + round_up64(16 * (size_t)nrows, 64),
-                 h_bytes = h_marks + 12 * nC;
+                 h_bytes0 = h_marks + 12 * nC;
+    // ... ; token rows | value | fend (the upload) ; applied | src | ratio (the mirror)
+    const size_t h_up = round_up64(h_bytes0, 64), h_tout = round_up64(h_up + up_bytes, 64), h_ratio = h_tout + 16 * nT,
+                 h_bytes = tok ? h_ratio + 8 * nF : h_bytes0;
     char* d = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes * 2, 65536), s));
     char* h = static_cast<char*>(host_.reserve(h_bytes, std::max<size_t>(h_bytes * 2, 65536), s));
     VoiceMarkArgs m{};
@@ -381,8 +535,36 @@ float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows,
     m.inc_u = sp.inc_u;
     m.hop = hop;
     m.tau_max = sp.pitch.tau_max;
-    hipLaunchKernelGGL(k_voice_marks, dim3((unsigned)nrows), dim3(kBlock), 0, s, m);
-    HIP_CHECK(hipGetLastError());
+    if (tok) {
+        VoiceTokArgs t{};
+        char* up = h + h_up;
+        std::memcpy(up, trd.data(), sizeof(VoiceTokRowDev) * (size_t)nrows);
+        if (nT) {
+            std::memcpy(up + sizeof(VoiceTokRowDev) * (size_t)nrows, tok->value, 8 * nT);
+            std::memcpy(up + sizeof(VoiceTokRowDev) * (size_t)nrows + 8 * nT, fend.data(), 4 * nT);
+        }
+        HIP_CHECK(hipMemcpyAsync(d + o_up, up, up_bytes, hipMemcpyHostToDevice, s));
+        t.rows = reinterpret_cast<const VoiceTokRowDev*>(d + o_up);
+        t.value = reinterpret_cast<const double*>(d + o_up + sizeof(VoiceTokRowDev) * (size_t)nrows);
+        t.fend = reinterpret_cast<const int32_t*>(t.value + nT);
+        t.applied = d_tout_ = reinterpret_cast<double*>(d + o_tout);
+        t.src = t.applied + nT;
+        t.fq = reinterpret_cast<int64_t*>(d + o_fq);
+        t.ratio = d_ratio_ = reinterpret_cast<double*>(d + o_ratio);
+        t.rho_t = reinterpret_cast<int32_t*>(d + o_rho_t);
+        t.fc = reinterpret_cast<int32_t*>(d + o_fc);
+        t.rho_f = reinterpret_cast<int32_t*>(d + o_rho_f);
+        t.kind = tok->kind;
+        t.smooth = tok->smooth;
+        h_tout_ = reinterpret_cast<double*>(h + h_tout);
+        h_ratio_ = reinterpret_cast<double*>(h + h_ratio);
+        hipLaunchKernelGGL(k_voice_marks_tok, dim3((unsigned)nrows), dim3(kBlock), 0, s, m, t);
+        HIP_CHECK(hipGetLastError());
+        if (nT) HIP_CHECK(hipMemcpyAsync(h_tout_, d_tout_, 16 * nT, hipMemcpyDeviceToHost, s));   // applied | src: in pinned memory by the caller's synchronisation
+    } else {
+        hipLaunchKernelGGL(k_voice_marks, dim3((unsigned)nrows), dim3(kBlock), 0, s, m);
+        HIP_CHECK(hipGetLastError());
+    }
     if (longest > 0) {
         VoiceGatherArgs g{};
         g.rows = m.rows;
@@ -408,6 +590,7 @@ void Voice::results_to_host(hipStream_t s) {
         HIP_CHECK(hipMemcpyAsync(h_voiced_, d_voiced_, 4 * (size_t)nf_, hipMemcpyDeviceToHost, s));
     }
     if (ncap_) HIP_CHECK(hipMemcpyAsync(h_ta_, d_ta_, 12 * (size_t)ncap_, hipMemcpyDeviceToHost, s));
+    if (nt_ >= 0 && nf_) HIP_CHECK(hipMemcpyAsync(h_ratio_, d_ratio_, 8 * (size_t)nf_, hipMemcpyDeviceToHost, s));
 }
 
 }  // namespace sbv2

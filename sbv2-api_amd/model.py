@@ -642,6 +642,37 @@ class Voice:
         return f"Voice({self.pitch_scale}, {self.intonation_scale}, hop={self.hop})"
 
 
+class TokenPitch:
+    """Per-token pitch targets of a fetched request (struct sbv2_token_pitch, include/sbv2_hip.h states it): values, one per token of the listed
+    rows in marks order, 0 = not edited; kind "hz" (the token's target mean f0) or "ratio" (in [0.5, 2]); smooth = contour frames to each side
+    over which the ratio changes (0 = steps).  Ranges are checked by the library.  Once a call has filled it: applied [n] (the ratio used, 1.0
+    where not edited) and src_f0 [n] (the token's measured mean f0 before any shift, 0 where it has no voiced frame); None before."""
+    KINDS = {"ratio": 0, "hz": 1}
+
+    def __init__(self, values, kind: str = "hz", smooth: int = 2):
+        if kind not in self.KINDS:
+            raise Sbv2Error(f"token pitch kind must be \"hz\" or \"ratio\", not {kind!r}")
+        self.values = np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1))
+        self.kind, self.smooth = kind, int(smooth)
+        self.applied = self.src_f0 = None
+
+    def c_struct(self):
+        """A sbv2_token_pitch over fresh output arrays; take() keeps them once the call has succeeded."""
+        n = self.values.size
+        arrays = np.ones(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+        pad = self.values if n else np.zeros(1, np.float64)   # (never a NULL for an empty table)
+        c = _lib.Sbv2TokenPitch(_f64p(pad), n, self.KINDS[self.kind], self.smooth if -2 ** 31 <= self.smooth < 2 ** 31 else -1, _f64p(arrays[0]),
+                                _f64p(arrays[1]), 0)
+        return c, arrays + (pad,)
+
+    def take(self, arrays):
+        self.applied, self.src_f0 = arrays[0][:self.values.size], arrays[1][:self.values.size]
+        return self
+
+    def __repr__(self):
+        return f"TokenPitch({self.values.size} tokens, {self.kind!r}, smooth={self.smooth})"
+
+
 def voice_tile() -> int:
     """Output samples per workgroup of the shifter's overlap-add gather (sbv2_voice_tile)."""
     return int(_lib.lib().sbv2_voice_tile())
@@ -692,6 +723,65 @@ def debug_voice_shift(rows, sample_rate: int, voice: Voice, period=None, voiced=
                                          ta=ta[ma:ma + na].astype(np.int64), ts=ts[ma:ma + ns].astype(np.int64), map=mp[ma:ma + ns].astype(np.int64)))
         at, fa, ma = at + n, fa + nfs[i], ma + n + 1
     return out
+
+
+def debug_voice_tokens(rows, sample_rate: int, voice: Voice, tok_ends, token_pitch: TokenPitch, period=None, voiced=None, device: int = 0):
+    """Test hook: the shifter with a token table on host rows (sbv2_debug_voice_tokens), always through its kernels.  rows, period, voiced as
+    for debug_voice_shift; tok_ends: per row the ascending end positions of its tokens in samples (one array = one row); token_pitch: the
+    values of all rows' tokens back to back -> (a list of namespaces as debug_voice_shift gives, each with ratio [frames] = R_f, applied and
+    src_f0 [the row's tokens] besides; token_pitch with applied / src_f0 of all tokens filled)."""
+    import types
+    if isinstance(rows, np.ndarray):
+        rows = [rows]
+        tok_ends = [tok_ends]
+    rows = [np.ascontiguousarray(r).reshape(-1) for r in rows]
+    for r in rows:
+        if r.dtype != np.float32:
+            raise Sbv2Error(f"the shifter takes float32 rows, not {r.dtype}")
+    ends = [np.asarray(e, np.int64).reshape(-1) for e in tok_ends]
+    if len(ends) != len(rows):
+        raise Sbv2Error(f"tok_ends must hold one array per row ({len(rows)})")
+    counts = np.array([e.size for e in ends] + [0], np.int64)
+    ends_all = np.ascontiguousarray(np.concatenate(ends + [np.zeros(1, np.int64)]))
+    lens = np.array([r.size for r in rows], np.int64)
+    x = np.ascontiguousarray(np.concatenate(rows + [np.zeros(0, np.float32)]))
+    c = voice.c
+    hop = voice.hop if voice.hop else int(sample_rate) // 200
+    nfs = [-(-int(n) // hop) if n and hop > 0 else 0 for n in lens]
+    nf, total = int(sum(nfs)), int(lens.sum())
+    i32p = C.POINTER(C.c_int32)
+    pin = vin = None
+    if (period is None) != (voiced is None):
+        raise Sbv2Error("period and voiced are given together or not at all")
+    if period is not None:
+        if isinstance(period, np.ndarray):
+            period, voiced = [period], [voiced]
+        pin = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in period] + [np.zeros(0)]))
+        vin = np.ascontiguousarray(np.concatenate([np.asarray(a).reshape(-1) for a in voiced] + [np.zeros(0)]).astype(np.int32))
+        if pin.size != nf or vin.size != nf:
+            raise Sbv2Error(f"the contour must hold one entry per frame ({nf})")
+        pin, vin = np.concatenate([pin, [0.0]]), np.concatenate([vin, [0]]).astype(np.int32)
+    pout, vout, rout = np.zeros(nf + 1, np.float64), np.zeros(nf + 1, np.int32), np.zeros(nf + 1, np.float64)
+    ta, ts, mp = (np.zeros(total + len(rows) + 1, np.int32) for _ in range(3))
+    nm = np.zeros((len(rows) + 1, 2), np.int64)
+    y = np.zeros(total + 1, np.float32)
+    ctp, tparr = token_pitch.c_struct()
+    check(_lib.lib().sbv2_debug_voice_tokens(int(device), x.ctypes.data_as(_lib.f32p) if total else None, lens.ctypes.data_as(i64p) if len(rows) else None,
+                                             len(rows), int(sample_rate), C.byref(c), _f64p(pin) if pin is not None else None,
+                                             vin.ctypes.data_as(i32p) if vin is not None else None, counts.ctypes.data_as(i64p),
+                                             ends_all.ctypes.data_as(i64p), C.byref(ctp), _f64p(pout), vout.ctypes.data_as(i32p),
+                                             ta.ctypes.data_as(i32p), ts.ctypes.data_as(i32p), mp.ctypes.data_as(i32p), nm.ctypes.data_as(i64p),
+                                             y.ctypes.data_as(_lib.f32p), _f64p(rout)))
+    token_pitch.take(tparr)
+    out, at, fa, ma, tk = [], 0, 0, 0, 0
+    for i, n in enumerate(lens):
+        n, na, ns, nt = int(n), int(nm[i, 0]), int(nm[i, 1]), int(counts[i])
+        out.append(types.SimpleNamespace(y=y[at:at + n].copy(), period=pout[fa:fa + nfs[i]].copy(), voiced=vout[fa:fa + nfs[i]].copy(),
+                                         ta=ta[ma:ma + na].astype(np.int64), ts=ts[ma:ma + ns].astype(np.int64), map=mp[ma:ma + ns].astype(np.int64),
+                                         ratio=rout[fa:fa + nfs[i]].copy(), applied=token_pitch.applied[tk:tk + nt].copy(),
+                                         src_f0=token_pitch.src_f0[tk:tk + nt].copy()))
+        at, fa, ma, tk = at + n, fa + nfs[i], ma + n + 1, tk + nt
+    return out, token_pitch
 
 
 def debug_stream_pitch(x, cuts, sample_rate: int, pitch: Pitch, device: int = 0, encoding: str | None = None):
@@ -989,7 +1079,7 @@ class Pipeline:
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
-                      voice=None, track=None, dynamics=None):
+                      voice=None, track=None, dynamics=None, token_pitch=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
@@ -1005,7 +1095,10 @@ class Pipeline:
         (a voice that shifts); it needs one of the two.  None: exactly the call without.
         dynamics: a Dynamics -> the compressor runs in front of `gain`, which must be given (sbv2_pipeline_fetch_request_dynamics), and the
         returned tuple gains a last element: the stage's stats [3] (L of the uncompressed signal, the threshold T, the deepest compression
-        in dB), or None at ratio 1, which is exactly the call without.  `stats` are then those of the compressed signal."""
+        in dB), or None at ratio 1, which is exactly the call without.  `stats` are then those of the compressed signal.
+        token_pitch: a TokenPitch -> the listed rows' tokens are edited in the shifter (sbv2_pipeline_fetch_request_token_pitch), whatever the
+        voice is, and the returned tuple gains a last element: that TokenPitch with applied [n] (the ratio used per token) and src_f0 [n]
+        (the token's measured mean f0, 0 without a voiced frame) filled.  All zeros: the bytes of the call without."""
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
         rw = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
@@ -1031,19 +1124,21 @@ class Pipeline:
             compressed = lambda *a: _lib.lib().sbv2_pipeline_fetch_request_dynamics(
                 *a[:3], C.byref(voice.c) if voice is not None else None, C.byref(track.c) if track is not None else None, C.byref(cd), *a[3:7],
                 _f64p(dst_stats) if dst_stats is not None else None, *a[7:])
-            if not marks and pitch is None:
+            if not marks and pitch is None and token_pitch is None:
                 check(compressed(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
                                  _f64p(stats) if nstats else None, None, None))
                 return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats, dst_stats
-        if dynamics is None and track is not None and not marks and pitch is None:
+        if token_pitch is not None:
+            ctp, tparr = token_pitch.c_struct()
+        if token_pitch is None and dynamics is None and track is not None and not marks and pitch is None:
             check(tracked(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
                           None, None))
             return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        if dynamics is None and not marks and pitch is None and voice is None:
+        if token_pitch is None and dynamics is None and not marks and pitch is None and voice is None:
             check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
                                                          _f64p(stats) if nstats else None))
             return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        if dynamics is None and not marks and pitch is None:
+        if token_pitch is None and dynamics is None and not marks and pitch is None:
             cv = voice.c
             check(_lib.lib().sbv2_pipeline_fetch_request_voice(self.h, b.ticket, C.byref(req), C.byref(cv), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
                                                                C.byref(got), _f64p(stats) if nstats else None, None, None))
@@ -1061,7 +1156,12 @@ class Pipeline:
                                 _f64p(m.env_peak) if env_hop > 0 else None, 0)
         args = (self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
                 C.byref(cm) if marks else None)
-        if dynamics is not None:
+        if token_pitch is not None:
+            none = lambda o: C.byref(o.c) if o is not None else None   # (every struct is read during the call only)
+            check(_lib.lib().sbv2_pipeline_fetch_request_token_pitch(
+                *args[:3], none(voice), none(track), none(dynamics), C.byref(ctp), *args[3:7],
+                _f64p(dst_stats) if dynamics is not None and dst_stats is not None else None, args[7], C.byref(cp) if pitch is not None else None))
+        elif dynamics is not None:
             check(compressed(*args, C.byref(cp) if pitch is not None else None))
         elif track is not None:
             check(tracked(*args, C.byref(cp) if pitch is not None else None))
@@ -1076,7 +1176,10 @@ class Pipeline:
             assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
         out = dst[:got.value].tobytes() if flac else dst[:got.value]
         res = (out, stats, m) if pitch is None else (out, stats, m, pitch.take(cp, parr))
-        return res if dynamics is None else res + (dst_stats,)
+        if token_pitch is not None and not marks and pitch is None:
+            res = res[:2]
+        res = res if dynamics is None else res + (dst_stats,)
+        return res if token_pitch is None else res + (token_pitch.take(tparr),)
 
     def close(self):
         if self.h:

@@ -61,12 +61,20 @@ class SynthesizeOptions:
     compressor (new; checked here) with comp_threshold (LU above the signal's own loudness, [0, 30]), comp_ratio ([1, 20]), comp_attack
     ([10, 10000] dB/s) and comp_release ([1, 1000] dB/s): a speech compressor in front of the loudness gain or the limiter (model.Dynamics),
     which evens out syllables and sentences so that a loud target comes nearer; it needs a loudness target, as limiter does.  Whole-signal
-    routes only (easy_synthesize, easy_synthesize_marks, the batcher), refused on streams.  False is the calls and the bytes there always were."""
+    routes only (easy_synthesize, easy_synthesize_marks, the batcher), refused on streams.  False is the calls and the bytes there always were.
+    token_pitch (new; checked here) with token_pitch_kind ("hz" | "ratio") and token_pitch_smooth ([0, 20] contour frames): one value per token
+    of the request's live sentences, in the order of the speech marks; 0 leaves the token alone, "hz" asks for that mean f0 of the token
+    (within [35, 1200] Hz: the shifter's clamp at its default range), "ratio" multiplies its f0 (within [0.5, 2]); the edit is made by the
+    shifter of pitch_scale on the device (model.TokenPitch) and composes with the two scales.  A list of another length than the request's token
+    count is refused with the expected count (TokenPitchError), before any GPU work.  Whole-signal routes only, refused on streams.  The marks
+    then carry "pitch_edit": {"applied", "src_f0_hz"}.  None, or all zeros, is the calls and the bytes there always were."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
                  normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
                  pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False,
-                 compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0):
+                 compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0, token_pitch=None, token_pitch_kind="hz",
+                 token_pitch_smooth=2):
+        self.token_pitch, self.token_pitch_kind, self.token_pitch_smooth = check_token_pitch(token_pitch, token_pitch_kind, token_pitch_smooth)
         if not isinstance(compressor, bool):
             raise model.Sbv2Error(f"compressor must be true or false: {compressor!r}")
         for name, v in (("comp_threshold", comp_threshold), ("comp_ratio", comp_ratio), ("comp_attack", comp_attack), ("comp_release", comp_release)):
@@ -84,7 +92,7 @@ class SynthesizeOptions:
         self.pitch_scale, self.intonation_scale = float(pitch_scale), float(intonation_scale)
         if not isinstance(pitch_track, bool):
             raise model.Sbv2Error(f"pitch_track must be true or false: {pitch_track!r}")
-        if pitch_track and pitch_hz is None and self.pitch_scale == 1.0 and self.intonation_scale == 1.0:
+        if pitch_track and pitch_hz is None and self.pitch_scale == 1.0 and self.intonation_scale == 1.0 and not edits_tokens(self):
             raise model.Sbv2Error("pitch_track tracks a pitch contour: it needs pitch_hz (the marks' contour) or a pitch_scale / intonation_scale "
                                   "away from 1 (the shifter's)")
         self.pitch_track = pitch_track
@@ -99,6 +107,66 @@ class SynthesizeOptions:
         self.envelope_hz = envelope_hz
         self.gain_db = gain_db
         self.pitch_hz, self.pitch_min_hz, self.pitch_max_hz = pitch_hz, pitch_min_hz, pitch_max_hz
+
+
+class TokenPitchError(model.Sbv2Error):
+    """A token_pitch the request itself is at fault for: a bad value, kind or smoothing, or a list that does not match the text's token count."""
+
+
+TOKEN_PITCH_RANGES = {"hz": (35.0, 1200.0), "ratio": (0.5, 2.0)}   # the library's, at the shifter's default range of 70 .. 600 Hz
+
+
+def check_token_pitch(values, kind, smooth):
+    """(values as a list of floats or None, kind, smooth) under the checks SynthesizeOptions states; TokenPitchError otherwise."""
+    if kind not in TOKEN_PITCH_RANGES:
+        raise TokenPitchError(f"token_pitch_kind must be \"hz\" or \"ratio\": {kind!r}")
+    if isinstance(smooth, bool) or not isinstance(smooth, int) or not 0 <= smooth <= 20:
+        raise TokenPitchError(f"token_pitch_smooth must be an integer in [0, 20]: {smooth!r}")
+    if values is None:
+        return None, kind, smooth
+    if isinstance(values, (str, bytes)) or not isinstance(values, (list, tuple, np.ndarray)):
+        raise TokenPitchError(f"token_pitch must be a list of numbers, one per token: {values!r}")
+    lo, hi = TOKEN_PITCH_RANGES[kind]
+    out = []
+    for t, v in enumerate(values):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not (v == 0 or lo <= v <= hi):   # (a NaN fails)
+            raise TokenPitchError(f"token_pitch[{t}] must be 0 (not edited) or a number in [{lo}, {hi}] ({kind}): {v!r}")
+        out.append(float(v))
+    return out, kind, smooth
+
+
+def edits_tokens(options) -> bool:
+    """Whether the request edits any token (None and all zeros do not: the request is then the call it always was)."""
+    v = getattr(options, "token_pitch", None)
+    return v is not None and any(x != 0.0 for x in v)
+
+
+def token_pitch_options(options, utts):
+    """The model.TokenPitch of a request over its live sentences `utts` (None when no token is edited).  A list of another length than the
+    request's token count is refused with the expected count, edited or not."""
+    v = getattr(options, "token_pitch", None)
+    if v is None:
+        return None
+    n = sum(int(np.asarray(u["phones"]).size) for u in utts)
+    if len(v) != n:
+        raise TokenPitchError(f"token_pitch holds {len(v)} values but the text has {n} tokens: expected {n}, one per token of the speech marks")
+    if not edits_tokens(options):
+        return None
+    return model.TokenPitch(v, getattr(options, "token_pitch_kind", "hz"), getattr(options, "token_pitch_smooth", 2))
+
+
+def refuse_token_pitch(options, what: str):
+    """token_pitch where rows leave chunk by chunk: refused, with the routes that edit a whole signal."""
+    if getattr(options, "token_pitch", None) is not None:
+        raise TokenPitchError(f"token_pitch edits a whole signal: {what} hands out chunks before the rows are complete, ask /synthesize, "
+                              "/synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
+
+
+def pitch_edit_dict(tp) -> dict:
+    """The "pitch_edit" block of a marks dict from a filled model.TokenPitch: per token the ratio used and its measured mean f0 before any shift
+    (None where it has no voiced frame)."""
+    return {"kind": tp.kind, "smooth": int(tp.smooth), "applied": [float(v) for v in tp.applied],
+            "src_f0_hz": [float(v) if v > 0 else None for v in tp.src_f0]}
 
 
 def load_style(data: bytes) -> np.ndarray:
@@ -220,6 +288,7 @@ class RequestPlan:
         self.options, self.n_lines = options, len(sentences)
         self.live = [i for i, _ in live]
         self.utts = [dict(s, style=style, sid=speaker_id) for _, s in live]
+        self.token_pitch = token_pitch_options(options, self.utts)   # (a list of the wrong length is refused before any GPU work)
 
 
 def envelope_hop(options, rate: int) -> int:
@@ -384,14 +453,18 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
     voice = voice_options(options)
     vkw = {} if voice is None else {"voice": voice}   # (named only when asked for: a request at the defaults is the call it always was)
     track = track_options(options)
-    if ln is not None or not fmt.is_default or marks is not None or voice is not None:
+    tp = getattr(plan, "token_pitch", None)
+    if tp is not None:   # (named only when asked for; the fetch's tuple then ends with the filled TokenPitch)
+        dkw = dict(dkw, token_pitch=tp)
+    shifts = voice is not None or tp is not None
+    if ln is not None or not fmt.is_default or marks is not None or shifts:
         # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
         if marks is not None:
             kw = dict(gain=ln, flac=plan.flac, marks=True, env_hop=envelope_hop(options, fmt.sample_rate), **vkw)
             pitch = pitch_options(options, fmt.sample_rate)
-            if track is not None and (pitch is not None or voice is not None):   # (likewise named only when asked for)
+            if track is not None and (pitch is not None or shifts):   # (likewise named only when asked for)
                 kw["track"] = track
             if pitch is None:   # (the call of a request without a contour is the call it always was)
                 out, stats, m, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw, **dkw)
@@ -401,8 +474,10 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
             marks.append(marks_dict(plan.utts, plan.live, fmt, m, pitch, **({"tracked": True} if "track" in kw and pitch is not None else {})))
             if dstats is not None:
                 marks[-1]["dynamics"] = dynamics_dict(dstats)
+            if tp is not None:
+                marks[-1]["pitch_edit"] = pitch_edit_dict(rest[-1])
         else:
-            tkw = {"track": track} if track is not None and voice is not None else {}
+            tkw = {"track": track} if track is not None and shifts else {}
             out, stats, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, **vkw, **tkw, **dkw)
             dstats = rest[0] if dyn is not None else None
         if dstats is not None and dynamics_stats is not None:
@@ -620,6 +695,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     last piece is out `.marks` has marks_dict's "pitch" block and the tokens' f0_hz / voiced.  Without pitch=True, pitch_hz is refused."""
     options = options or SynthesizeOptions()
     refuse_voice(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    refuse_token_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_dynamics(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if pitch:

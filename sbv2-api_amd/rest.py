@@ -42,6 +42,14 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     loudness is taken down by comp_ratio, at comp_attack / comp_release dB per second.  It needs loudness, as limiter does.  The
                     marks of /synthesize_marks then carry "dynamics": {"loudness_lufs", "threshold_lufs", "deepest_db"}.  The stream routes answer
                     400 for true: the threshold needs the whole signal's loudness and the attack looks ahead without bound.
+  token_pitch = null (new; the same routes; token_pitch_kind = "hz", token_pitch_smooth = 2): one value per token of the speech marks, 0 = leave
+                    the token alone; "hz": the mean f0 the token shall have ([35, 1200]), "ratio": a factor on its f0 ([0.5, 2]); the ratio changes
+                    over token_pitch_smooth contour frames ([0, 20]) to each side of a token boundary.  Query /synthesize_marks with pitch_hz, edit
+                    the tokens' f0_hz, ask again with the same text: the edit is made by the shifter of pitch_scale on the device and composes
+                    with the scales.  The marks of /synthesize_marks then carry "pitch_edit": {"kind", "smooth", "applied" (the ratio used per
+                    token), "src_f0_hz" (the token's measured mean, null without a voiced frame)}.  A bad value, kind or smoothing and a list of
+                    another length than the text's token count (the message names the expected count) answer 400, and so do the stream routes
+                    for any list.
   POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
@@ -58,7 +66,7 @@ FastAPI / starlette are plumbing here; `python -m sbv2_api_amd.rest` is not prov
 import base64
 import json
 import threading
-from typing import Optional
+from typing import List, Optional
 
 
 class _HeldPieces:
@@ -168,6 +176,9 @@ def make_app(holder, batching=None):
         comp_ratio: float = 4.0             # [1, 20]
         comp_attack: float = 600.0          # dB per second, [10, 10000]
         comp_release: float = 60.0          # dB per second, [1, 1000]
+        token_pitch: Optional[List[float]] = None   # new: per token of the speech marks, 0 = not edited; /synthesize, /synthesize_marks; 400 on the stream routes
+        token_pitch_kind: str = "hz"        # "hz": the token's target mean f0, [35, 1200]; "ratio": a factor on its f0, [0.5, 2]
+        token_pitch_smooth: int = 2         # contour frames to each side over which the ratio changes, [0, 20]
 
     class SynthesizeMarksRequest(SynthesizeRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
@@ -218,12 +229,21 @@ def make_app(holder, batching=None):
                                               intonation_scale=req.intonation_scale, **({"pitch_track": True} if getattr(req, "pitch_track", False) else {}),
                                               **({"compressor": True, "comp_threshold": req.comp_threshold, "comp_ratio": req.comp_ratio,
                                                   "comp_attack": req.comp_attack, "comp_release": req.comp_release}
-                                                 if getattr(req, "compressor", False) else {}))
+                                                 if getattr(req, "compressor", False) else {}),
+                                              **({"token_pitch": req.token_pitch, "token_pitch_kind": req.token_pitch_kind,
+                                                  "token_pitch_smooth": req.token_pitch_smooth}
+                                                 if getattr(req, "token_pitch", None) is not None else {}))
+
+    def bad_request(e):
+        """400 for what the request itself is at fault for in token_pitch (a bad value, a count that does not match the text)."""
+        return PlainTextResponse(f"Something went wrong: {e}", status_code=400)
 
     def synthesize(req: SynthesizeRequest):
         try:
             with lock:
                 wav = holder.easy_synthesize(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
+        except orchestrator.TokenPitchError as e:
+            return bad_request(e)
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
         return Response(content=wav, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
@@ -235,6 +255,8 @@ def make_app(holder, batching=None):
             with lock:                        # parse and queue only: the answer is awaited without it
                 fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching)
             wav = fut.result()
+        except orchestrator.TokenPitchError as e:
+            return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
         return Response(content=wav, media_type="audio/flac" if req.encoding == "flac" else "audio/wav")
@@ -252,6 +274,8 @@ def make_app(holder, batching=None):
                     fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching,
                                                          marks=True)
                 audio, marks = fut.result()
+        except orchestrator.TokenPitchError as e:
+            return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
         return JSONResponse({"audio": base64.b64encode(audio).decode("ascii"), "media_type": "audio/flac" if req.encoding == "flac" else "audio/wav",
@@ -268,6 +292,7 @@ def make_app(holder, batching=None):
         try:
             orchestrator.refuse_dynamics(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_voice(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=400)
