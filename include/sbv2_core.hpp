@@ -150,6 +150,23 @@ inline void fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, const sb
                                                   pitch));
 }
 
+// Not in the reference: the formant scale of a fetched request (sbv2_formant in sbv2_hip.h states it).  sbv2_pipeline_fetch_request_formant with
+// owned arrays: fetch_request_token_pitch with formant_scale behind the table; 1 is exactly that call.
+inline void fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,
+                                  const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, TokenPitch* tp, double formant_scale, void* dst,
+                                  int64_t capacity_bytes, int64_t* out_count, double* stats = nullptr, double* dyn_stats = nullptr,
+                                  sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr) {
+    sbv2_token_pitch c{};
+    if (tp) {
+        tp->applied.assign(tp->values.size(), 1.0);
+        tp->src_f0.assign(tp->values.size(), 0.0);
+        c = sbv2_token_pitch{tp->values.data(), (int64_t)tp->values.size(), tp->hz ? 1 : 0, tp->smooth, tp->applied.data(), tp->src_f0.data(), 0};
+    }
+    const sbv2_formant f{formant_scale, 0.0};
+    check(sbv2_pipeline_fetch_request_formant(p, ticket, &req, voice, track, dynamics, tp ? &c : nullptr, &f, dst, capacity_bytes, out_count, stats,
+                                              dyn_stats, marks, pitch));
+}
+
 }  // namespace sbv2_core
 
 #endif

@@ -449,9 +449,10 @@ int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t
  *   the stage cannot create clipping; with p = 1 and s = 1 the two mark lists coincide and y == x bit for bit, and the same holds in any stretch
  *   of unvoiced frames farther than tau_max + H + 2 samples from a voiced one; no half-width exceeds max(tau_max + 1, sr / 200) + 2, which bounds
  *   the gather.  Dividing by den trades level for the peak bound; the loudness stage downstream restores level.
- * Not built: epoch (glottal) alignment of the marks, contour smoothing, formant shifting, energy compensation (octave-error repair of the
+ * Not built: epoch (glottal) alignment of the marks, contour smoothing, energy compensation (octave-error repair of the
  *   contour is opt-in: sbv2_pitch_track and sbv2_pipeline_fetch_request_tracked below; a target per token instead of one pair of scales is
- *   sbv2_token_pitch and sbv2_pipeline_fetch_request_token_pitch below).  No
+ *   sbv2_token_pitch and sbv2_pipeline_fetch_request_token_pitch below; moving the formants is sbv2_formant and
+ *   sbv2_pipeline_fetch_request_formant below).  No
  *   stream entry point either: sbv2_stream_* and sbv2_node_* do not take a sbv2_voice. */
 typedef struct sbv2_voice {
     double pitch_scale;          /* [0.5, 2] */
@@ -631,6 +632,50 @@ int sbv2_debug_voice_tokens(int device, const float* x, const int64_t* lens, int
                             const double* period_in, const int32_t* voiced_in, const int64_t* tok_counts, const int64_t* tok_ends,
                             const sbv2_token_pitch* token_pitch, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts, int32_t* map,
                             int64_t* n_marks, float* y, double* ratio_out);
+
+/* ---- new: formant scale.  TD-PSOLA keeps the spectral envelope: a voice raised by 1.3 is the same vocal tract at a higher pitch.  The perceived
+ * size, age and character of a speaker sit in the formants; this moves them, by the factor q, and leaves f0 alone.  It is the shifter of
+ * sbv2_voice with every grain READ at a scaled offset; everything up to and including the mapping m(j) is that section, unchanged.
+ * Parameter: q = formant_scale in [0.5, 2]; 1 is the identity; anything else, a NaN included, is refused.
+ * Voiced marks.  Analysis mark m is voiced iff frame ta_m / H (integer division) of the contour the marks were placed by (the given, the
+ *   estimated or the tracked one) is voiced.
+ * Output.  For synthesis mark j with a = ta_{m(j)}, L, R and the edge rule of sbv2_voice, every integer offset u = k - ts_j, in f64, never
+ *   contracted: the read position p = q double(u); the window argument pw = p for a voiced mark and pw = double(u) for an unvoiced one; the
+ *   grain contributes iff -L < pw < R; v = |pw| / (pw < 0 ? L : R), w = 1.0 - (v v) (3.0 - 2.0 v), and w = 1 on the left side of mark 0 and
+ *   on the right side of the last mark, the side decided by the sign of pw; i0 = floor(p), fr = p - i0,
+ *   val = (1.0 - fr) X(a + i0) + fr X(a + i0 + 1) with X = x inside [0, n) and 0 outside (64-bit indices); num += w val, den += w in
+ *   ascending j; y[k] = float(num / max(den, 1.0)).  A row without an analysis mark is copied.
+ * Why two window rules.  A voiced grain is the vocal tract's response to one pulse: compressing it together with its window is the classical
+ *   grain resampling.  Unvoiced marks sit sr / 200 samples apart; compressed windows would no longer sum to 1 between them (den falls to 0.70
+ *   at q = 1.2: a 200 Hz amplitude dip on every fricative), so an unvoiced grain keeps its complementary output-domain window (den = 1) and
+ *   only its read index is scaled.
+ * Hence: the length is unchanged; |y[k]| <= max |x| still holds, because val is a convex combination of two samples (or of a sample and 0):
+ *   that is why the interpolation is linear and not cubic, the stage must stay unable to create clipping; with q = 1, fr = 0 and the result
+ *   equals sbv2_voice's gather bit for bit; the marks, the contour, and applied / src_f0 of a token table are those of the call without; a
+ *   voiced grain reaches |u| < max(L, R) / q, so the gather looks ceil(half / min(q, 1)) + 1 samples to each side of a tile for marks
+ *   (half = max(tau_max + 1, sr / 200) + 2).
+ * The level drops (RMS ratio 0.73 .. 0.91 on the synthetic vowel of tests/test_formant.py for q in 0.8 .. 1.3; the overlapping grains of noise
+ *   are incoherent and lose level too): energy compensation stays not built, and the loudness stage behind restores level, as it does for pitch.
+ * Not built: formant scale on streams (sbv2_stream_*) and on sbv2_node_*, a per-token or time-varying scale, energy compensation, an
+ *   envelope-based (LPC / cepstral) shifter that would move single formants. */
+typedef struct sbv2_formant {
+    double formant_scale;     /* [0.5, 2]; 1 = the identity */
+    double reserved;          /* must be 0 */
+} sbv2_formant;
+/* sbv2_pipeline_fetch_request_token_pitch with the listed rows' formants scaled.  formant == NULL, or formant_scale == 1, is exactly that call:
+ * no new launch, the same bytes.  Otherwise the listed rows go through the shifter with k_voice_gather_fmt in place of its gather, also when
+ * voice is NULL or the identity and no token is edited (voice == NULL: p = s = 1 and the voice's defaults); track then tracks the shifter's
+ * contour.  Everything else (token table, compressor, gain stage, sink, stats, marks, pitch: all of the delivered signal) is that call, and
+ * token_pitch's applied / src_f0 are those of the call without formant.  The run's PCM is only read: two equal fetches give identical bytes.
+ * Refused with nothing written: a formant_scale outside [0.5, 2] or NaN, a non-zero reserved, and everything that call refuses. */
+int sbv2_pipeline_fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                        const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                        const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                        double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch);
+/* Test hook: sbv2_debug_voice_shift with a formant scale, always through k_voice_gather_fmt (formant_scale = 1 included). */
+int sbv2_debug_voice_formant(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
+                             const sbv2_formant* formant, const double* period_in, const int32_t* voiced_in, double* period_out,
+                             int32_t* voiced_out, int32_t* ta, int32_t* ts, int32_t* map, int64_t* n_marks, float* y);
 
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */

@@ -118,6 +118,11 @@ class Sbv2TokenPitch(C.Structure):
                 ("applied", C.POINTER(C.c_double)), ("src_f0", C.POINTER(C.c_double)), ("reserved", C.c_int64)]
 
 
+class Sbv2Formant(C.Structure):
+    """struct sbv2_formant (include/sbv2_hip.h)."""
+    _fields_ = [("formant_scale", C.c_double), ("reserved", C.c_double)]
+
+
 #: every symbol include/sbv2_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "sbv2_last_error": (C.c_char_p, []),
@@ -171,6 +176,13 @@ SYMBOLS = {
                                                           C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch), C.c_void_p,
                                                           C.c_int64, i64p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Sbv2Marks),
                                                           C.POINTER(Sbv2Pitch)]),
+    "sbv2_pipeline_fetch_request_formant": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                      C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch),
+                                                      C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_debug_voice_formant": (C.c_int, [C.c_int, f32p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Voice), C.POINTER(Sbv2Formant),
+                                           C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64p, f32p]),
     "sbv2_debug_voice_tokens": (C.c_int, [C.c_int, f32p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Voice), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                           i64p, i64p, C.POINTER(Sbv2TokenPitch), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64p, f32p, C.POINTER(C.c_double)]),

@@ -93,6 +93,7 @@ class RequestBatcher:
             sentences, style_vectors, style_id, speaker_id, options, seed = req.args
             plan = orchestrator.RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
             self._check(plan.options)
+            orchestrator.require_formant(self.pipe, plan.options)
             if req.marks:
                 orchestrator.envelope_hop(plan.options, plan.fmt.sample_rate)
                 orchestrator.pitch_options(plan.options, plan.fmt.sample_rate)
@@ -181,7 +182,7 @@ class RequestBatcher:
                         req.future.set_result((audio, got[0]))
                         continue
                     if (pcm is None and req.plan.gain is None and req.plan.fmt.is_default and orchestrator.voice_options(req.plan.options) is None
-                            and getattr(req.plan, "token_pitch", None) is None):
+                            and getattr(req.plan, "token_pitch", None) is None and orchestrator.formant_options(req.plan.options) is None):
                         pcm = self.pipe.fetch(b)   # the plain f32 requests of a run share one fetch
                     req.future.set_result(orchestrator.finish_request(self.pipe, b, r0, r1, req.plan, pcm=pcm))
                 except Exception as e:

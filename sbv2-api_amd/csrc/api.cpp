@@ -533,6 +533,9 @@ static bool check_token_pitch_static(const sbv2_token_pitch* t, const VoiceSpec&
     return false;
 }
 
+// The checks of sbv2_formant that need no run (formant_spec of voice.h holds them; vs as above) -> the scale and the gather's widened range.
+static FormantSpec check_formant_static(const sbv2_formant* f, const VoiceSpec& vs) { return formant_spec(f->formant_scale, f->reserved, vs); }
+
 // The checks of sbv2_pitch_track (track.h states the bounds).
 static TrackSpec check_track_static(const sbv2_pitch_track* t) {
     SBV2_REQUIRE(t->reserved[0] == 0 && t->reserved[1] == 0, "sbv2_pitch_track.reserved must be 0");
@@ -553,11 +556,12 @@ static TrackSpec check_track_static(const sbv2_pitch_track* t) {
 // gain.dyn (with a loudness or limiter stage): the compressor runs on y first (Dynamics, dynamics.h); dyn_stats (may be NULL): its 3 doubles.
 // tp (with utts; NULL or all zeros: nothing): the listed rows' tokens are edited in the shifter (its token phase, voice.h), which then runs
 // whatever the voice is; applied / src_f0 reach the caller's arrays only once everything else has succeeded.
+// fmnt (with utts; NULL or scale 1: nothing): the shifter runs whatever the voice is, its gather reading every grain at the scaled offset.
 static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_format* fmt, const FetchGain& gain, const int64_t* place,
                             int64_t joined_len, Sink sink, void* dst, int64_t capacity_bytes, int64_t* out_counts, double* stats,
                             const int32_t* utts = nullptr, int n_utts = 0, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr,
                             const sbv2_voice* voice = nullptr, const sbv2_pitch_track* track = nullptr, double* dyn_stats = nullptr,
-                            const sbv2_token_pitch* tp = nullptr) {
+                            const sbv2_token_pitch* tp = nullptr, const sbv2_formant* fmnt = nullptr) {
     const DynamicsSpec dyn = gain.dyn ? dynamics_spec(gain.dyn) : DynamicsSpec();
     const bool compress = gain.dyn && !dyn.identity();
     const PcmFmtSpec spec = fetch_spec(fmt, gain.kind != FetchGain::kNone, sink);
@@ -590,9 +594,15 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
     if (voice) {
         SBV2_REQUIRE(utts && place, "internal: voice needs a request's rows");
         vs = check_voice_static(voice, kNativeRate);
-    } else if (tp) {
+    } else if (tp || fmnt) {
         vs = default_voice_spec();
     }
+    FormantSpec fs;
+    if (fmnt) {
+        SBV2_REQUIRE(utts && place, "internal: formant needs a request's rows");
+        fs = check_formant_static(fmnt, vs);
+    }
+    const bool scale = fmnt && !fs.identity();
     bool edit = false;
     std::vector<int64_t> tok_counts, tok_ends;
     if (tp) {
@@ -614,11 +624,11 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
             }
         }
     }
-    const bool shift = ((voice && !vs.identity()) || edit) && n_utts > 0;
+    const bool shift = ((voice && !vs.identity()) || edit || scale) && n_utts > 0;
     TrackSpec ts;
     if (track) {
         ts = check_track_static(track);
-        SBV2_REQUIRE(pitch || (voice && !vs.identity()) || edit,
+        SBV2_REQUIRE(pitch || (voice && !vs.identity()) || edit || scale,
                      "pitch tracking needs a pitch contour or a voice that is not the identity");
     }
     HIP_CHECK(hipSetDevice(vm.device()));
@@ -629,7 +639,8 @@ static void fetch_formatted(sbv2_pipeline* p, int64_t ticket, const sbv2_pcm_for
         for (int k = 0; k < n_utts; ++k) rows[k] = VoiceRow{vm.pcm_offs()[utts[k]], vm.pcm_lens()[utts[k]]};
         const float* pcm = vm.pcm_device();
         const VoiceTokens vt{tok_counts.data(), tok_ends.data(), edit ? tp->value : nullptr, edit ? tp->kind : 0, edit ? tp->smooth : 0};
-        const float* shifted = c.voice.run(pcm, vm.pcm_total(), rows.data(), n_utts, vs, s, nullptr, nullptr, track ? &ts : nullptr, edit ? &vt : nullptr);
+        const float* shifted = c.voice.run(pcm, vm.pcm_total(), rows.data(), n_utts, vs, s, nullptr, nullptr, track ? &ts : nullptr, edit ? &vt : nullptr,
+                                           scale ? &fs : nullptr);
         for (FmtPiece& pc : pieces) pc.src = shifted + (pc.src - pcm);
     }
     if (sink == Sink::kPcm && gain.kind == FetchGain::kNone && spec.identity() && !place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
@@ -770,19 +781,20 @@ int32_t sbv2_voice_tile(void) { return Voice::kTile; }
 
 int32_t sbv2_dynamics_tile(void) { return Dynamics::kTile; }
 
-int sbv2_pipeline_fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
-                                            const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
-                                            void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats, double* dyn_stats,
-                                            sbv2_marks* marks, sbv2_pitch* pitch) {
+int sbv2_pipeline_fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                        const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                        const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                        double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch) {
     API_BEGIN
     DynamicsSpec ds;
     if (dynamics) ds = dynamics_spec(dynamics);   // what needs no run is refused before the handle is looked at
     VoiceSpec vs;
     if (voice) vs = check_voice_static(voice, kNativeRate);   // what needs no run is refused before the handle is looked at
     const bool edit = token_pitch && check_token_pitch_static(token_pitch, voice ? vs : default_voice_spec());
+    const bool scale = formant && !check_formant_static(formant, voice ? vs : default_voice_spec()).identity();
     if (track) {
         (void)check_track_static(track);
-        SBV2_REQUIRE(pitch || (voice && !vs.identity()) || edit, "pitch tracking needs a pitch contour or a voice that is not the identity");
+        SBV2_REQUIRE(pitch || (voice && !vs.identity()) || edit || scale, "pitch tracking needs a pitch contour or a voice that is not the identity");
     }
     SBV2_REQUIRE(req && req->n_utts >= 0 && (req->n_utts == 0 || (req->utts && req->place)), "bad fetch request");
     SBV2_REQUIRE(!(req->loudness && req->limiter), "a fetch request takes a loudness target or a limiter, not both");
@@ -802,8 +814,15 @@ int sbv2_pipeline_fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, co
     static const int64_t no_place[1] = {0};
     fetch_formatted(p, ticket, req->fmt, gain, req->n_utts ? req->place : no_place, req->joined_len, req->flac ? Sink::kFlac : Sink::kPcm, dst,
                     capacity_bytes, out_count, stats, req->n_utts ? req->utts : no_rows, req->n_utts, marks, pitch, voice, track, dyn_stats,
-                    token_pitch);
+                    token_pitch, formant);
     API_END
+}
+int sbv2_pipeline_fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                            const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                            void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats, double* dyn_stats,
+                                            sbv2_marks* marks, sbv2_pitch* pitch) {
+    return sbv2_pipeline_fetch_request_formant(p, ticket, req, voice, track, dynamics, token_pitch, nullptr, dst, capacity_bytes, out_count, stats,
+                                               dyn_stats, marks, pitch);
 }
 int sbv2_pipeline_fetch_request_dynamics(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
                                          const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, void* dst, int64_t capacity_bytes,

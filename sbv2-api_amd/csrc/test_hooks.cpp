@@ -2112,10 +2112,11 @@ int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, i
 
 // The shifter (Voice, voice.hip) on host rows laid back to back, always through its kernels; everything is checked before any device call.
 // tp (with tok_counts / tok_ends): the per-token edits, through k_voice_marks_tok whatever the values are.
+// fmnt: the formant scale, through k_voice_gather_fmt whatever the value is.
 static int debug_voice(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
                        const double* period_in, const int32_t* voiced_in, const int64_t* tok_counts, const int64_t* tok_ends,
                        const sbv2_token_pitch* tp, double* period_out, int32_t* voiced_out, int32_t* ta, int32_t* ts, int32_t* map, int64_t* n_marks,
-                       float* y, double* ratio_out) {
+                       float* y, double* ratio_out, const sbv2_formant* fmnt = nullptr) {
     API_BEGIN
     SBV2_REQUIRE(voice && nrows >= 0 && (nrows == 0 || lens), "bad arguments");
     SBV2_REQUIRE(voice->reserved == 0, "sbv2_voice.reserved must be 0");
@@ -2130,6 +2131,8 @@ static int debug_voice(int device, const float* x, const int64_t* lens, int nrow
         total += lens[i];
     }
     SBV2_REQUIRE(total == 0 || (x && y), "bad arguments");
+    FormantSpec fs;
+    if (fmnt) fs = formant_spec(fmnt->formant_scale, fmnt->reserved, sp);
     VoiceTokens vt{};
     if (tp) {
         SBV2_REQUIRE(nrows == 0 || tok_counts, "bad arguments");
@@ -2153,7 +2156,7 @@ static int debug_voice(int device, const float* x, const int64_t* lens, int nrow
     HIP_CHECK(hipSetDevice(device));
     DevMem dx(x, sizeof(float) * (size_t)total);
     Voice v;
-    const float* dy = v.run(dx.f(), total, rows.data(), nrows, sp, nullptr, period_in, voiced_in, nullptr, tp ? &vt : nullptr);
+    const float* dy = v.run(dx.f(), total, rows.data(), nrows, sp, nullptr, period_in, voiced_in, nullptr, tp ? &vt : nullptr, fmnt ? &fs : nullptr);
     v.results_to_host(nullptr);
     HIP_CHECK(hipStreamSynchronize(nullptr));
     for (int i = 0; i < nrows; ++i) SBV2_REQUIRE(v.status(i) == 0, "internal: the shifter found more marks than it planned for in row " + std::to_string(i));
@@ -2196,6 +2199,16 @@ int sbv2_debug_voice_tokens(int device, const float* x, const int64_t* lens, int
     }
     return debug_voice(device, x, lens, nrows, sample_rate, voice, period_in, voiced_in, tok_counts, tok_ends, token_pitch, period_out, voiced_out, ta,
                        ts, map, n_marks, y, ratio_out);
+}
+int sbv2_debug_voice_formant(int device, const float* x, const int64_t* lens, int nrows, int32_t sample_rate, const sbv2_voice* voice,
+                             const sbv2_formant* formant, const double* period_in, const int32_t* voiced_in, double* period_out,
+                             int32_t* voiced_out, int32_t* ta, int32_t* ts, int32_t* map, int64_t* n_marks, float* y) {
+    if (!formant) {
+        set_last_error("bad arguments");
+        return 1;
+    }
+    return debug_voice(device, x, lens, nrows, sample_rate, voice, period_in, voiced_in, nullptr, nullptr, nullptr, period_out, voiced_out, ta, ts, map,
+                       n_marks, y, nullptr, formant);
 }
 
 // The fed level reduction (StreamLevels, marks.hip) on its own: x cut at cuts[ncuts] into ncuts + 1 pushes, each handed the samples of its

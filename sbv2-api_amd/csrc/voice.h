@@ -3,7 +3,8 @@
 // Three steps on one stream: the YIN contour of every listed row (k_pitch_yin of marks.hip on f32, one launch per row), the marks of every row
 // (k_voice_marks, one workgroup per row: mean f0, phase increments, ta / ts / map) and the overlap-add gather (k_voice_gather, the hot path).
 // Per-token pitch targets (sbv2_token_pitch, sbv2_pipeline_fetch_request_token_pitch, sbv2_debug_voice_tokens) are one more phase of the marks
-// kernel, launched as k_voice_marks_tok only by a call that brings a token table.
+// kernel, launched as k_voice_marks_tok only by a call that brings a token table.  A formant scale (sbv2_formant, sbv2_pipeline_fetch_request_formant,
+// sbv2_debug_voice_formant) is a second instantiation of the gather, launched as k_voice_gather_fmt only by a call that brings one.
 #pragma once
 #include "common.h"
 #include "marks.h"
@@ -25,6 +26,17 @@ constexpr int kVoiceMinRate = 1000;
 // throws: pitch_scale in [0.5, 2], intonation_scale in [0, 2], 1000 <= sr <= 48000, hop in [sr / 1000, sr / 50] (0 = sr / 200), f0_min / f0_max /
 // threshold as pitch_spec has them (0 = 70, 600, 0.15); NaNs fail every comparison and are refused
 VoiceSpec voice_spec(int sample_rate, double pitch_scale, double intonation_scale, int64_t hop, double f0_min, double f0_max, double threshold);
+
+// Formant scale (sbv2_formant in include/sbv2_hip.h): the factor q by which every grain is read, and the range of synthesis marks that can reach
+// an output sample, which grows as a voiced grain widens by 1 / q.
+struct FormantSpec {
+    double scale = 1.0;
+    int half = 0;   // ceil(VoiceSpec::half / min(q, 1)) + 1
+    bool identity() const { return scale == 1.0; }
+};
+// The checks of a sbv2_formant's two fields, in one place for the fetch and the test hook.  throws: reserved == 0, formant_scale in [0.5, 2];
+// a NaN fails the comparisons and is refused
+FormantSpec formant_spec(double formant_scale, double reserved, const VoiceSpec& v);
 
 // One row of a call: x[x_off .. x_off + n) -> y[x_off .. x_off + n)
 struct VoiceRow {
@@ -59,8 +71,10 @@ class Voice {
     // tok: the per-token edits (checked here, throws); k_voice_marks_tok then forms M_t, rho_t and R_f between the contour and the marks, and
     // applied / src_f0 are on their way to pinned memory when run returns.  Without tok every launch, argument and byte is that of a call
     // from before token edits existed.
+    // fm: the gather is k_voice_gather_fmt with this scale, 1 included (the test hook); without fm it is k_voice_gather as it always was.
+    // Contour, marks and token results do not depend on it.
     float* run(const float* x, int64_t span, const VoiceRow* rows, int nrows, const VoiceSpec& sp, hipStream_t s, const double* period_in = nullptr,
-               const int32_t* voiced_in = nullptr, const TrackSpec* tr = nullptr, const VoiceTokens* tok = nullptr);
+               const int32_t* voiced_in = nullptr, const TrackSpec* tr = nullptr, const VoiceTokens* tok = nullptr, const FormantSpec* fm = nullptr);
     // Results of the last run for the test hook, valid once results_to_host() has been enqueued and s synchronised: per frame (rows back to
     // back) the period T_f and voiced; per row the marks at mark_off(i), n_a(i) analysis and n_s(i) synthesis ones.
     void results_to_host(hipStream_t s);

@@ -12,6 +12,11 @@
 //     time with their analysis mark's position and its two half-widths, and every lane walks them in ascending j, adding w and w x in f64 where
 //     the window covers its sample.  A staged mark is a broadcast read; x[ta + u] is consecutive across lanes.  Reads stay inside the row:
 //     ta - L >= -1 and ta + R <= n by the definition of L and R, and the index is checked besides.
+// Formant scaling (sbv2_formant) is a second instantiation of the gather (k_voice_gather_fmt) that only a call with a formant scale launches: a
+// staged mark carries its voiced bit besides, the range of marks that may reach a tile is wider by 1 / min(q, 1), and every lane reads its grain
+// at q u: two adjacent floats, interpolated in f64, each checked against the row (an unvoiced grain keeps its window and reads up to q times as
+// far).  Lanes hold consecutive k, so their addresses advance by q: a wavefront touches 64 q floats of one grain, one to four cache lines
+// a load.  LDS, the launch shape and the ascending order of the sum are the plain gather's.
 // Per-token pitch edits (sbv2_token_pitch) are one more phase of k_voice_marks, in a second instantiation of it (k_voice_marks_tok) that only a call
 // with a token table launches: between the row's mean and the increments, where T_f and m are at hand.  The frames' llrint(f0 65536) and voiced
 // flags are prefix-summed over the row (an LDS scan, kBlock frames at a time), lanes take tokens (M_t from two prefix entries, rho_t, applied,
@@ -304,7 +309,17 @@ __device__ inline int32_t first_at_or_after(const int32_t* v, int32_t n, int64_t
     return lo;
 }
 
-__global__ __launch_bounds__(kBlock) void k_voice_gather(const VoiceGatherArgs a) {
+struct VoiceFmtArgs {   // what k_voice_gather_fmt needs besides
+    const int32_t* voiced;   // [NF] the contour the marks were placed by
+    double q;                // formant_scale
+    int64_t hop;
+    int32_t half;            // the widened search range: ceil(half / min(q, 1)) + 1
+};
+
+// kFmt: every grain is read at q u by linear interpolation (sbv2_formant); without, f is not looked at and the code is what it was before
+// formant scaling existed
+template <bool kFmt>
+__device__ __forceinline__ void voice_gather_body(const VoiceGatherArgs& a, const VoiceFmtArgs* f) {
     __shared__ int32_t s_ts[kBlock], s_ta[kBlock], s_L[kBlock], s_R[kBlock], s_edge[kBlock];
     __shared__ int32_t s_range[2];
     const VoiceRowDev r = a.rows[blockIdx.y];
@@ -323,9 +338,11 @@ __global__ __launch_bounds__(kBlock) void k_voice_gather(const VoiceGatherArgs a
     const int32_t* ta = a.ta + r.m_off;
     const int32_t* ts = a.ts + r.m_off;
     const int32_t* mp = a.map + r.m_off;
+    int32_t half = a.half;
+    if constexpr (kFmt) half = f->half;
     if (tid == 0) {
-        s_range[0] = first_at_or_after(ts, ns, t0 - a.half);
-        s_range[1] = first_at_or_after(ts, ns, t1 + a.half);
+        s_range[0] = first_at_or_after(ts, ns, t0 - half);
+        s_range[1] = first_at_or_after(ts, ns, t1 + half);
     }
     __syncthreads();
     const int32_t j0 = s_range[0], j1 = s_range[1];
@@ -338,7 +355,9 @@ __global__ __launch_bounds__(kBlock) void k_voice_gather(const VoiceGatherArgs a
             s_ta[tid] = am;
             s_L[tid] = m > 0 ? am - ta[m - 1] : am + 1;
             s_R[tid] = m + 1 < na ? ta[m + 1] - am : (int32_t)(n - am);
-            s_edge[tid] = (m == 0 ? 1 : 0) | (m == na - 1 ? 2 : 0);
+            int32_t e = (m == 0 ? 1 : 0) | (m == na - 1 ? 2 : 0);
+            if constexpr (kFmt) e |= f->voiced[r.f_off + am / f->hop] ? 4 : 0;   // (am < n: a frame of the row)
+            s_edge[tid] = e;
         }
         __syncthreads();
         const int32_t cn = min(kBlock, j1 - c);
@@ -346,21 +365,40 @@ __global__ __launch_bounds__(kBlock) void k_voice_gather(const VoiceGatherArgs a
             for (int32_t i = 0; i < cn; ++i) {   // ascending j
                 const int64_t u = k - s_ts[i];
                 const int32_t L = s_L[i], R = s_R[i];
-                if (u <= -(int64_t)L || u >= R) continue;
-                const int64_t src = s_ta[i] + u;
-                if (src < 0 || src >= n) continue;   // (never, by the definition of L and R)
-                const double v = (double)(u < 0 ? -u : u) / (double)(u < 0 ? L : R);
-                double w = 1.0 - (v * v) * (3.0 - 2.0 * v);
-                const int32_t e = s_edge[i];
-                if ((u < 0 && (e & 1)) || (u > 0 && (e & 2))) w = 1.0;
-                num += w * (double)x[src];
-                den += w;
+                if constexpr (kFmt) {
+                    const int32_t e = s_edge[i];
+                    const double du = (double)u, p = f->q * du, pw = (e & 4) ? p : du;
+                    if (!(pw > -(double)L && pw < (double)R)) continue;
+                    const double v = fabs(pw) / (double)(pw < 0.0 ? L : R);
+                    double w = 1.0 - (v * v) * (3.0 - 2.0 * v);
+                    if ((pw < 0.0 && (e & 1)) || (pw > 0.0 && (e & 2))) w = 1.0;
+                    const double fl = floor(p), fr = p - fl;
+                    const int64_t src = s_ta[i] + (int64_t)fl;   // X is 0 outside the row: an unvoiced grain reads up to q times its width
+                    const double x0 = src >= 0 && src < n ? (double)x[src] : 0.0;
+                    const double x1 = src + 1 >= 0 && src + 1 < n ? (double)x[src + 1] : 0.0;
+                    const double val = (1.0 - fr) * x0 + fr * x1;
+                    num += w * val;
+                    den += w;
+                } else {
+                    if (u <= -(int64_t)L || u >= R) continue;
+                    const int64_t src = s_ta[i] + u;
+                    if (src < 0 || src >= n) continue;   // (never, by the definition of L and R)
+                    const double v = (double)(u < 0 ? -u : u) / (double)(u < 0 ? L : R);
+                    double w = 1.0 - (v * v) * (3.0 - 2.0 * v);
+                    const int32_t e = s_edge[i];
+                    if ((u < 0 && (e & 1)) || (u > 0 && (e & 2))) w = 1.0;
+                    num += w * (double)x[src];
+                    den += w;
+                }
             }
         }
         __syncthreads();
     }
     if (mine) y[k] = (float)(num / fmax(den, 1.0));
 }
+
+__global__ __launch_bounds__(kBlock) void k_voice_gather(const VoiceGatherArgs a) { voice_gather_body<false>(a, nullptr); }
+__global__ __launch_bounds__(kBlock) void k_voice_gather_fmt(const VoiceGatherArgs a, const VoiceFmtArgs f) { voice_gather_body<true>(a, &f); }
 
 }  // namespace
 
@@ -390,6 +428,15 @@ VoiceSpec voice_spec(int sample_rate, double pitch_scale, double intonation_scal
     return v;
 }
 
+FormantSpec formant_spec(double formant_scale, double reserved, const VoiceSpec& v) {
+    SBV2_REQUIRE(reserved == 0.0, "sbv2_formant.reserved must be 0");   // (a NaN fails)
+    SBV2_REQUIRE(formant_scale >= 0.5 && formant_scale <= 2.0, "voice: formant_scale must be in [0.5, 2]: " + std::to_string(formant_scale));   // (a NaN fails)
+    FormantSpec f;
+    f.scale = formant_scale;
+    f.half = (int)std::ceil((double)v.half / std::min(formant_scale, 1.0)) + 1;
+    return f;
+}
+
 void voice_tokens_check(const double* value, int64_t n_tokens, int kind, int smooth, const VoiceSpec& sp) {
     SBV2_REQUIRE(n_tokens >= 0 && (value || n_tokens == 0), "token pitch: value must not be NULL");
     SBV2_REQUIRE(kind == 0 || kind == 1, "token pitch: kind must be 0 (ratio) or 1 (Hz): " + std::to_string(kind));
@@ -402,7 +449,7 @@ void voice_tokens_check(const double* value, int64_t n_tokens, int kind, int smo
 }
 
 float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows, const VoiceSpec& sp, hipStream_t s, const double* period_in,
-                  const int32_t* voiced_in, const TrackSpec* tr, const VoiceTokens* tok) {
+                  const int32_t* voiced_in, const TrackSpec* tr, const VoiceTokens* tok, const FormantSpec* fm) {
     SBV2_REQUIRE(nrows >= 0 && nrows <= 65535 && span >= 0 && (nrows == 0 || rows), "voice: bad rows");
     SBV2_REQUIRE(!period_in == !voiced_in, "voice: period_in and voiced_in are given together or not at all");
     const int64_t hop = sp.pitch.hop;
@@ -575,7 +622,17 @@ float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows,
         g.map = m.map;
         g.count = m.count;
         g.half = sp.half;
-        hipLaunchKernelGGL(k_voice_gather, dim3((unsigned)((longest + kTile - 1) / kTile), (unsigned)nrows), dim3(kBlock), 0, s, g);
+        const dim3 grid((unsigned)((longest + kTile - 1) / kTile), (unsigned)nrows);
+        if (fm) {
+            VoiceFmtArgs f{};
+            f.voiced = m.voiced;
+            f.q = fm->scale;
+            f.hop = hop;
+            f.half = fm->half;
+            hipLaunchKernelGGL(k_voice_gather_fmt, grid, dim3(kBlock), 0, s, g, f);
+        } else {
+            hipLaunchKernelGGL(k_voice_gather, grid, dim3(kBlock), 0, s, g);
+        }
         HIP_CHECK(hipGetLastError());
     }
     // (the status of every row is looked at by the caller after its synchronisation)

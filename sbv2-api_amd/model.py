@@ -673,15 +673,34 @@ class TokenPitch:
         return f"TokenPitch({self.values.size} tokens, {self.kind!r}, smooth={self.smooth})"
 
 
+class Formant:
+    """Formant scale of a fetched request (struct sbv2_formant, include/sbv2_hip.h states it): every grain of the shifter is read at
+    formant_scale times its offset, which moves the spectral envelope by that factor and leaves f0, the marks and the length alone.
+    formant_scale in [0.5, 2], 1 = the identity; checked by the library."""
+
+    def __init__(self, formant_scale: float = 1.0):
+        self.formant_scale = float(formant_scale)
+
+    @property
+    def c(self):
+        return _lib.Sbv2Formant(self.formant_scale, 0.0)
+
+    def is_identity(self) -> bool:
+        return self.formant_scale == 1.0
+
+    def __repr__(self):
+        return f"Formant({self.formant_scale})"
+
+
 def voice_tile() -> int:
     """Output samples per workgroup of the shifter's overlap-add gather (sbv2_voice_tile)."""
     return int(_lib.lib().sbv2_voice_tile())
 
 
-def debug_voice_shift(rows, sample_rate: int, voice: Voice, period=None, voiced=None, device: int = 0):
+def debug_voice_shift(rows, sample_rate: int, voice: Voice, period=None, voiced=None, device: int = 0, formant=None):
     """Test hook: the shifter on host rows (sbv2_debug_voice_shift), always through its kernels.  rows: float32 arrays (one array = one row);
     period / voiced: per row, the contour to use instead of the estimated one (both or neither) -> a list of namespaces, one per row: y, period
-    and voiced (per frame, as used), ta, ts, map."""
+    and voiced (per frame, as used), ta, ts, map.  formant: a Formant -> sbv2_debug_voice_formant, always through the formant gather."""
     import types
     if isinstance(rows, np.ndarray):
         rows = [rows]
@@ -711,11 +730,15 @@ def debug_voice_shift(rows, sample_rate: int, voice: Voice, period=None, voiced=
     ta, ts, mp = (np.zeros(total + len(rows) + 1, np.int32) for _ in range(3))
     nm = np.zeros((len(rows) + 1, 2), np.int64)
     y = np.zeros(total + 1, np.float32)
-    check(_lib.lib().sbv2_debug_voice_shift(int(device), x.ctypes.data_as(_lib.f32p) if total else None, lens.ctypes.data_as(i64p) if len(rows) else None,
-                                            len(rows), int(sample_rate), C.byref(c), _f64p(pin) if pin is not None else None,
-                                            vin.ctypes.data_as(i32p) if vin is not None else None, _f64p(pout), vout.ctypes.data_as(i32p),
-                                            ta.ctypes.data_as(i32p), ts.ctypes.data_as(i32p), mp.ctypes.data_as(i32p), nm.ctypes.data_as(i64p),
-                                            y.ctypes.data_as(_lib.f32p)))
+    head = (int(device), x.ctypes.data_as(_lib.f32p) if total else None, lens.ctypes.data_as(i64p) if len(rows) else None, len(rows), int(sample_rate),
+            C.byref(c))
+    tail = (_f64p(pin) if pin is not None else None, vin.ctypes.data_as(i32p) if vin is not None else None, _f64p(pout), vout.ctypes.data_as(i32p),
+            ta.ctypes.data_as(i32p), ts.ctypes.data_as(i32p), mp.ctypes.data_as(i32p), nm.ctypes.data_as(i64p), y.ctypes.data_as(_lib.f32p))
+    if formant is not None:
+        cf = formant.c
+        check(_lib.lib().sbv2_debug_voice_formant(*head, C.byref(cf), *tail))
+    else:
+        check(_lib.lib().sbv2_debug_voice_shift(*head, *tail))
     out, at, fa, ma = [], 0, 0, 0
     for i, n in enumerate(lens):
         n, na, ns = int(n), int(nm[i, 0]), int(nm[i, 1])
@@ -723,6 +746,12 @@ def debug_voice_shift(rows, sample_rate: int, voice: Voice, period=None, voiced=
                                          ta=ta[ma:ma + na].astype(np.int64), ts=ts[ma:ma + ns].astype(np.int64), map=mp[ma:ma + ns].astype(np.int64)))
         at, fa, ma = at + n, fa + nfs[i], ma + n + 1
     return out
+
+
+def debug_voice_formant(rows, sample_rate: int, voice: Voice, formant: Formant, period=None, voiced=None, device: int = 0):
+    """Test hook: the shifter with a formant scale on host rows (sbv2_debug_voice_formant), always through k_voice_gather_fmt (scale 1
+    included); arguments and results as debug_voice_shift has them."""
+    return debug_voice_shift(rows, sample_rate, voice, period, voiced, device, formant=formant)
 
 
 def debug_voice_tokens(rows, sample_rate: int, voice: Voice, tok_ends, token_pitch: TokenPitch, period=None, voiced=None, device: int = 0):
@@ -1079,7 +1108,7 @@ class Pipeline:
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
-                      voice=None, track=None, dynamics=None, token_pitch=None):
+                      voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
@@ -1098,7 +1127,10 @@ class Pipeline:
         in dB), or None at ratio 1, which is exactly the call without.  `stats` are then those of the compressed signal.
         token_pitch: a TokenPitch -> the listed rows' tokens are edited in the shifter (sbv2_pipeline_fetch_request_token_pitch), whatever the
         voice is, and the returned tuple gains a last element: that TokenPitch with applied [n] (the ratio used per token) and src_f0 [n]
-        (the token's measured mean f0, 0 without a voiced frame) filled.  All zeros: the bytes of the call without."""
+        (the token's measured mean f0, 0 without a voiced frame) filled.  All zeros: the bytes of the call without.
+        formant_scale: in [0.5, 2] -> the listed rows' formants are moved by that factor in the shifter's gather, whatever the voice is
+        (sbv2_pipeline_fetch_request_formant; model.Formant states it); the returned tuple is that of the call without.  1.0: exactly that call."""
+        fm = None if formant_scale == 1.0 else Formant(formant_scale)   # (a NaN is carried on and refused by the library)
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
         rw = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1))
@@ -1124,21 +1156,21 @@ class Pipeline:
             compressed = lambda *a: _lib.lib().sbv2_pipeline_fetch_request_dynamics(
                 *a[:3], C.byref(voice.c) if voice is not None else None, C.byref(track.c) if track is not None else None, C.byref(cd), *a[3:7],
                 _f64p(dst_stats) if dst_stats is not None else None, *a[7:])
-            if not marks and pitch is None and token_pitch is None:
+            if not marks and pitch is None and token_pitch is None and fm is None:
                 check(compressed(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
                                  _f64p(stats) if nstats else None, None, None))
                 return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats, dst_stats
         if token_pitch is not None:
             ctp, tparr = token_pitch.c_struct()
-        if token_pitch is None and dynamics is None and track is not None and not marks and pitch is None:
+        if fm is None and token_pitch is None and dynamics is None and track is not None and not marks and pitch is None:
             check(tracked(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
                           None, None))
             return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        if token_pitch is None and dynamics is None and not marks and pitch is None and voice is None:
+        if fm is None and token_pitch is None and dynamics is None and not marks and pitch is None and voice is None:
             check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
                                                          _f64p(stats) if nstats else None))
             return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        if token_pitch is None and dynamics is None and not marks and pitch is None:
+        if fm is None and token_pitch is None and dynamics is None and not marks and pitch is None:
             cv = voice.c
             check(_lib.lib().sbv2_pipeline_fetch_request_voice(self.h, b.ticket, C.byref(req), C.byref(cv), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
                                                                C.byref(got), _f64p(stats) if nstats else None, None, None))
@@ -1156,7 +1188,12 @@ class Pipeline:
                                 _f64p(m.env_peak) if env_hop > 0 else None, 0)
         args = (self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
                 C.byref(cm) if marks else None)
-        if token_pitch is not None:
+        if fm is not None:
+            none = lambda o: C.byref(o.c) if o is not None else None   # (every struct is read during the call only)
+            check(_lib.lib().sbv2_pipeline_fetch_request_formant(
+                *args[:3], none(voice), none(track), none(dynamics), C.byref(ctp) if token_pitch is not None else None, none(fm), *args[3:7],
+                _f64p(dst_stats) if dynamics is not None and dst_stats is not None else None, args[7], C.byref(cp) if pitch is not None else None))
+        elif token_pitch is not None:
             none = lambda o: C.byref(o.c) if o is not None else None   # (every struct is read during the call only)
             check(_lib.lib().sbv2_pipeline_fetch_request_token_pitch(
                 *args[:3], none(voice), none(track), none(dynamics), C.byref(ctp), *args[3:7],
@@ -1176,7 +1213,7 @@ class Pipeline:
             assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
         out = dst[:got.value].tobytes() if flac else dst[:got.value]
         res = (out, stats, m) if pitch is None else (out, stats, m, pitch.take(cp, parr))
-        if token_pitch is not None and not marks and pitch is None:
+        if (token_pitch is not None or fm is not None) and not marks and pitch is None:
             res = res[:2]
         res = res if dynamics is None else res + (dst_stats,)
         return res if token_pitch is None else res + (token_pitch.take(tparr),)

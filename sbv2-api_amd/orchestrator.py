@@ -67,13 +67,21 @@ class SynthesizeOptions:
     (within [35, 1200] Hz: the shifter's clamp at its default range), "ratio" multiplies its f0 (within [0.5, 2]); the edit is made by the
     shifter of pitch_scale on the device (model.TokenPitch) and composes with the two scales.  A list of another length than the request's token
     count is refused with the expected count (TokenPitchError), before any GPU work.  Whole-signal routes only, refused on streams.  The marks
-    then carry "pitch_edit": {"applied", "src_f0_hz"}.  None, or all zeros, is the calls and the bytes there always were."""
+    then carry "pitch_edit": {"applied", "src_f0_hz"}.  None, or all zeros, is the calls and the bytes there always were.
+    formant_scale in [0.5, 2] (new; checked here): the voice's formants are moved by that factor, which changes the perceived size, age and
+    character of the speaker and leaves f0, the length and the token spans alone; it is made by the shifter of pitch_scale on the device
+    (model.Formant: every grain is read at the scaled offset) and composes with pitch_scale, intonation_scale, pitch_track and token_pitch.
+    The level drops somewhat (set loudness to restore it).  Whole-signal routes only, refused on streams.  The marks then carry
+    "formant_scale".  1.0 is the calls and the bytes there always were."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
                  normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
                  pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False,
                  compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0, token_pitch=None, token_pitch_kind="hz",
-                 token_pitch_smooth=2):
+                 token_pitch_smooth=2, formant_scale=1.0):
+        if isinstance(formant_scale, bool) or not isinstance(formant_scale, (int, float)) or not 0.5 <= formant_scale <= 2.0:   # (a NaN fails)
+            raise model.Sbv2Error(f"formant_scale must be a number in [0.5, 2.0]: {formant_scale!r}")
+        self.formant_scale = float(formant_scale)
         self.token_pitch, self.token_pitch_kind, self.token_pitch_smooth = check_token_pitch(token_pitch, token_pitch_kind, token_pitch_smooth)
         if not isinstance(compressor, bool):
             raise model.Sbv2Error(f"compressor must be true or false: {compressor!r}")
@@ -92,7 +100,8 @@ class SynthesizeOptions:
         self.pitch_scale, self.intonation_scale = float(pitch_scale), float(intonation_scale)
         if not isinstance(pitch_track, bool):
             raise model.Sbv2Error(f"pitch_track must be true or false: {pitch_track!r}")
-        if pitch_track and pitch_hz is None and self.pitch_scale == 1.0 and self.intonation_scale == 1.0 and not edits_tokens(self):
+        if (pitch_track and pitch_hz is None and self.pitch_scale == 1.0 and self.intonation_scale == 1.0 and not edits_tokens(self)
+                and self.formant_scale == 1.0):
             raise model.Sbv2Error("pitch_track tracks a pitch contour: it needs pitch_hz (the marks' contour) or a pitch_scale / intonation_scale "
                                   "away from 1 (the shifter's)")
         self.pitch_track = pitch_track
@@ -330,8 +339,32 @@ def voice_options(options):
     return None if p == 1.0 and s == 1.0 else model.Voice(p, s)
 
 
+def formant_options(options):
+    """The formant_scale of a request (None at 1: the request is then the call it always was)."""
+    q = float(getattr(options, "formant_scale", 1.0))
+    return None if q == 1.0 else q
+
+
+def require_formant(pipe, options):
+    """A request with a formant_scale needs a pipeline whose fetch_request takes it: an older one is refused, not served unshifted."""
+    if formant_options(options) is None:
+        return
+    import inspect
+    try:
+        params = inspect.signature(pipe.fetch_request).parameters
+    except (AttributeError, TypeError, ValueError):   # no fetch_request, or one whose parameters cannot be read: not known to take it
+        raise model.Sbv2Error(f"formant_scale needs a pipeline whose fetch_request is known to take formant_scale: that of {type(pipe).__name__} "
+                              "cannot be inspected, and the request is not served with its formants unmoved")
+    if "formant_scale" not in params and not any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
+        raise model.Sbv2Error(f"formant_scale needs a pipeline whose fetch_request takes formant_scale: {type(pipe).__name__} does not, "
+                              "and the request is not served with its formants unmoved")
+
+
 def refuse_voice(options, what: str):
-    """pitch_scale / intonation_scale where rows leave chunk by chunk: refused, with the routes that shift a whole signal."""
+    """pitch_scale / intonation_scale / formant_scale where rows leave chunk by chunk: refused, with the routes that shift a whole signal."""
+    if formant_options(options) is not None:
+        raise model.Sbv2Error(f"formant_scale shifts a whole signal: {what} hands out chunks before the rows are complete, ask "
+                              "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
     if voice_options(options) is not None:
         raise model.Sbv2Error(f"pitch_scale / intonation_scale shift a whole signal: {what} hands out chunks before the rows are complete, ask "
                               "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
@@ -456,7 +489,11 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
     tp = getattr(plan, "token_pitch", None)
     if tp is not None:   # (named only when asked for; the fetch's tuple then ends with the filled TokenPitch)
         dkw = dict(dkw, token_pitch=tp)
-    shifts = voice is not None or tp is not None
+    fq = formant_options(options)
+    if fq is not None:   # (named only when asked for; the fetch's tuple is that of the call without)
+        require_formant(pipe, options)
+        dkw = dict(dkw, formant_scale=fq)
+    shifts = voice is not None or tp is not None or fq is not None
     if ln is not None or not fmt.is_default or marks is not None or shifts:
         # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
@@ -476,6 +513,8 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
                 marks[-1]["dynamics"] = dynamics_dict(dstats)
             if tp is not None:
                 marks[-1]["pitch_edit"] = pitch_edit_dict(rest[-1])
+            if fq is not None:
+                marks[-1]["formant_scale"] = fq
         else:
             tkw = {"track": track} if track is not None and shifts else {}
             out, stats, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, **vkw, **tkw, **dkw)
@@ -509,6 +548,7 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     = finish_request over all rows of a run that holds this request alone (batcher.RequestBatcher: the same, several requests to a run)."""
     refuse_pitch(options, "easy_synthesize (/synthesize)")
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
+    require_formant(pipe, plan.options)   # (before any GPU work)
     if noise_seed is None:      # the reference draws fresh noise per request; tests pass an explicit seed
         noise_seed = model.fresh_noise_seed()
     b = pipe.prepare(plan.utts, sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=noise_scale,
@@ -523,6 +563,7 @@ def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, styl
     phone id and each word (word2ph entry) is spoken, in samples and seconds of the delivered signal, how loud it is there, and with
     options.envelope_hz a level envelope.  Levels are computed on the device from the delivered samples (also behind the FLAC sink)."""
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
+    require_formant(pipe, plan.options)   # (before any GPU work)
     envelope_hop(plan.options, plan.fmt.sample_rate)   # a bad envelope_hz is refused before any GPU work
     pitch_options(plan.options, plan.fmt.sample_rate)  # ... and so is a bad pitch_hz or range
     if noise_seed is None:

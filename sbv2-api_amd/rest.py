@@ -50,6 +50,10 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     token), "src_f0_hz" (the token's measured mean, null without a voiced frame)}.  A bad value, kind or smoothing and a list of
                     another length than the text's token count (the message names the expected count) answer 400, and so do the stream routes
                     for any list.
+  formant_scale = 1.0 (new; the same routes): the voice's formants moved by that factor in [0.5, 2], f0 and the length left alone (below 1 a
+                    larger, darker speaker, above 1 a smaller, brighter one); made by the shifter of pitch_scale on the device, it composes with
+                    pitch_scale, intonation_scale, pitch_track and token_pitch.  The marks of /synthesize_marks then carry "formant_scale".  The
+                    stream routes answer 400 for a value other than 1.
   POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
@@ -179,6 +183,7 @@ def make_app(holder, batching=None):
         token_pitch: Optional[List[float]] = None   # new: per token of the speech marks, 0 = not edited; /synthesize, /synthesize_marks; 400 on the stream routes
         token_pitch_kind: str = "hz"        # "hz": the token's target mean f0, [35, 1200]; "ratio": a factor on its f0, [0.5, 2]
         token_pitch_smooth: int = 2         # contour frames to each side over which the ratio changes, [0, 20]
+        formant_scale: float = 1.0          # new: moves the voice's formants, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); 400 on the stream routes
 
     class SynthesizeMarksRequest(SynthesizeRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
@@ -232,7 +237,8 @@ def make_app(holder, batching=None):
                                                  if getattr(req, "compressor", False) else {}),
                                               **({"token_pitch": req.token_pitch, "token_pitch_kind": req.token_pitch_kind,
                                                   "token_pitch_smooth": req.token_pitch_smooth}
-                                                 if getattr(req, "token_pitch", None) is not None else {}))
+                                                 if getattr(req, "token_pitch", None) is not None else {}),
+                                              **({"formant_scale": req.formant_scale} if getattr(req, "formant_scale", 1.0) != 1.0 else {}))
 
     def bad_request(e):
         """400 for what the request itself is at fault for in token_pitch (a bad value, a count that does not match the text)."""
