@@ -2,7 +2,8 @@
 
 It parses STREAMINFO and every frame, checks each frame header's CRC-8 and each frame's CRC-16, checks the streamable-subset limits the
 encoder promises (block size <= 4608 and 4096 here, LPC order <= 12, Rice partition order <= 8, rate and bit depth coded in the frame header),
-and decodes CONSTANT, VERBATIM, FIXED and LPC subframes with Rice-coded partitioned residuals.  numpy + Python only."""
+and decodes CONSTANT, VERBATIM, FIXED and LPC subframes with Rice-coded partitioned residuals; the bits between a subframe's end and the
+byte boundary must be zero (RFC 9639, 9.3).  numpy + Python only."""
 import numpy as np
 
 RATE_CODES = {8000: 0b0100, 16000: 0b0101, 22050: 0b0110, 24000: 0b0111, 32000: 0b1000, 44100: 0b1001, 48000: 0b1010}
@@ -117,6 +118,7 @@ def _residual(r: _Bits, n, order, info):
             u = (q << k) | r.u(k) if k else q
             res.append((u >> 1) ^ -(u & 1))
     info["k"] = ks
+    info["res"] = np.asarray(res, np.int64)
     return res
 
 
@@ -164,7 +166,9 @@ def _subframe(r: _Bits, n):
 
 
 def read(data: bytes):
-    """-> dict(rate, total, min_block, max_block, min_frame, max_frame, md5, samples (int16), frames = [dict(size, n, number, type, ...)])."""
+    """-> dict(rate, total, min_block, max_block, min_frame, max_frame, md5, samples (int16), frames = [dict(size, n, number, header, type,
+    bits = the subframe's length in bits from its first bit to the end of its last residual code; FIXED and LPC: order, p, k = [per
+    partition], res = the decoded residuals (int64 array); LPC: precision, shift, coef)])."""
     data = bytes(data)
     if data[:4] != b"fLaC":
         raise FlacError("no fLaC marker")
@@ -203,8 +207,11 @@ def read(data: bytes):
         hlen = r.pos // 8 - pos
         if crc8(data[pos:pos + hlen]) != r.u(8):
             raise FlacError(f"frame {number}: header CRC-8 mismatch")
+        sub = r.pos
         x, info = _subframe(r, n)
-        r.pos = (r.pos + 7) // 8 * 8
+        info["bits"] = r.pos - sub
+        if r.u(-r.pos % 8):
+            raise FlacError(f"frame {number}: a padding bit before the byte boundary is set")
         end = r.pos // 8
         if end + 2 > len(data):
             raise FlacError("truncated frame")

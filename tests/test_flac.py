@@ -43,29 +43,38 @@ class BitWriter:
         return bytes(np.packbits(np.array(self.bits, np.uint8)))
 
 
-def hand_frame(number, x, kind, coef=(), shift=0):
-    """One frame of a 16 kHz stream: VERBATIM, FIXED (order len(coef)) or LPC (coefficients coef, first = the sample right before x[i])."""
+def hand_frame(number, x, kind, coef=(), shift=0, p=0, k=3):
+    """One frame of a 16 kHz stream: CONSTANT, VERBATIM, FIXED (order len(coef)) or LPC (coefficients coef, first = the sample right before
+    x[i]); 2^p Rice partitions with parameter k, or k[i] for partition i."""
     n = len(x)
+    ks = [k] * (1 << p) if np.isscalar(k) else list(k)
+    assert len(ks) == 1 << p and n % (1 << p) == 0
     w = BitWriter()
     w.put(0xFFF8, 16)
-    w.put(0b0110, 4)          # block size: 8 bits of n - 1 follow
+    w.put(0b1100 if n == 4096 else 0b0110 if n <= 256 else 0b0111, 4)   # block size: 4096, or 8 / 16 bits of n - 1 after the number
     w.put(0b0101, 4)          # 16 kHz
     w.put(0b0000, 4)
     w.put(0b100, 3)
     w.put(0, 1)
-    w.put(number, 8)          # frame number < 128: one byte
-    w.put(n - 1, 8)
+    for b in chr(number).encode("utf-8"):   # the frame number, coded like a code point
+        w.put(b, 8)
+    if n != 4096:
+        w.put(n - 1, 8 if n <= 256 else 16)
     w.put(R.crc8(w.bytes()), 8)
     order = len(coef)
     w.put(0, 1)
-    if kind == "VERBATIM":
+    if kind == "CONSTANT":
+        w.put(0, 6)
+    elif kind == "VERBATIM":
         w.put(1, 6)
     elif kind == "FIXED":
         w.put(8 + order, 6)
     else:
         w.put(31 + order, 6)
     w.put(0, 1)
-    if kind == "VERBATIM":
+    if kind == "CONSTANT":
+        w.signed(int(x[0]), 16)
+    elif kind == "VERBATIM":
         for v in x:
             w.signed(int(v), 16)
     else:
@@ -77,11 +86,13 @@ def hand_frame(number, x, kind, coef=(), shift=0):
             for c in coef:
                 w.signed(c, 15)
         w.put(0, 2)
-        w.put(0, 4)           # one partition
-        w.put(3, 4)           # k = 3
+        w.put(p, 4)
+        P = n >> p
         for i in range(order, n):
+            if i % P == 0 or i == order:
+                w.put(ks[i // P], 4)
             acc = sum(c * int(x[i - 1 - j]) for j, c in enumerate(coef))
-            w.rice(int(x[i]) - (acc >> shift), 3)
+            w.rice(int(x[i]) - (acc >> shift), ks[i // P])
     w.pad()
     b = w.bytes()
     return b + R.crc16(b).to_bytes(2, "big")
@@ -193,48 +204,56 @@ def voiced_signal(rate, seconds=4.0, seed=2024):
 
 
 def _rice_bits(e, order, n):
-    u = np.where(e >= 0, 2 * e, -2 * e - 1).astype(np.int64)
+    """Method + partition order (6 bits) and the cheapest partitioned Rice coding of the residuals e of a block of n, over every valid p <= 8."""
+    u = np.concatenate([np.zeros(order, np.int64), np.where(e >= 0, 2 * e, -2 * e - 1).astype(np.int64)])
+    ks = np.arange(15, dtype=np.int64)[:, None]
+    hi = u[None, :] >> ks                  # (the warm-up samples count as zeros and are taken out of partition 0's count below)
     best = None
     for p in range(9):
         if n % (1 << p) or (n >> p) <= order:
             continue
-        P = n >> p
-        full = np.concatenate([np.zeros(order, np.int64), u])
-        bits = 6
-        for q in range(1 << p):
-            seg = full[q * P + (order if q == 0 else 0):(q + 1) * P]
-            bits += 4 + min(int((seg >> k).sum()) + seg.size * (k + 1) for k in range(15))
+        count = np.full(1 << p, n >> p, np.int64)
+        count[0] -= order
+        cost = hi.reshape(15, 1 << p, n >> p).sum(2) + count[None, :] * (ks + 1)
+        bits = 6 + 4 * (1 << p) + int(cost.min(0).sum())
         best = bits if best is None else min(best, bits)
     return best
 
 
-def _lpc_coefs(x, order):
+def _lpc_all(x, maxorder):
+    """[(quantised coefficients, shift)] for LPC orders 1, 2, ... up to maxorder from one Levinson-Durbin pass (Tukey 0.5 window, libFLAC's
+    precision-15 quantiser); the pass stops, as the encoder's does, where the error or a coefficient stops being a positive / finite number."""
     import scipy.signal.windows as SW
     n = x.size
     w = SW.tukey(n, 0.5)
     xw = x * w
-    R_ = np.array([np.dot(xw[l:], xw[:n - l]) for l in range(order + 1)])
+    R_ = np.array([np.dot(xw[l:], xw[:n - l]) for l in range(maxorder + 1)])
     a, err = np.zeros(0), R_[0]
-    if err <= 0:
-        return None
-    for o in range(order):
+    out = []
+    for o in range(maxorder):
+        if not err > 0:
+            break
         k = -(R_[o + 1] + np.dot(a, R_[o:0:-1][:o])) / err
         a = np.concatenate([a + k * a[::-1], [k]])
         err *= 1 - k * k
-    lp = -a
-    cmax = np.abs(lp).max()
-    shift = int(min(max(13 - np.floor(np.log2(cmax)), 0), 15)) if cmax > 0 else 0
-    q, acc = [], 0.0
-    for c in lp:
-        acc += c * 2.0 ** shift
-        v = int(min(max(np.floor(acc + 0.5) if acc >= 0 else -np.floor(-acc + 0.5), -16384), 16383))
-        acc -= v
-        q.append(v)
-    return q, shift
+        if not np.isfinite(a).all():
+            break
+        lp = -a
+        cmax = np.abs(lp).max()
+        shift = int(min(max(13 - np.floor(np.log2(cmax)), 0), 15)) if cmax > 0 else 0
+        q, acc = [], 0.0
+        for c in lp:
+            acc += c * 2.0 ** shift
+            v = int(min(max(np.floor(acc + 0.5) if acc >= 0 else -np.floor(-acc + 0.5), -16384), 16383))
+            acc -= v
+            q.append(v)
+        out.append((q, shift))
+    return out
 
 
 def restated_frame_bytes(x, lpc_orders=(8, 12)):
-    """Sum of frame sizes of the best of FIXED 0-4 and LPC 8 / 12 (Tukey 0.5, precision 15, p <= 8) per 4096-sample block."""
+    """Sum of frame sizes of the best of FIXED 0-4 and the LPC orders asked for (8 and 12, or any of 1..12; Tukey 0.5, precision 15, p <= 8)
+    per 4096-sample block."""
     total = 0
     for f0 in range(0, x.size, 4096):
         b = x[f0:f0 + 4096].astype(np.int64)
@@ -244,10 +263,10 @@ def restated_frame_bytes(x, lpc_orders=(8, 12)):
             if order < n:
                 pred = sum(c * b[order - 1 - j:n - 1 - j] for j, c in enumerate(coef)) if coef else 0
                 cands.append(8 + 16 * order + _rice_bits(b[order:] - pred, order, n))
+        lpc = _lpc_all(b.astype(np.float64), min(max(lpc_orders, default=0), n - 1))
         for order in lpc_orders:
-            qs = _lpc_coefs(b.astype(np.float64), order) if n > order else None
-            if qs:
-                q, sh = qs
+            if order <= len(lpc):
+                q, sh = lpc[order - 1]
                 acc = sum(c * b[order - 1 - j:n - 1 - j] for j, c in enumerate(q))
                 cands.append(8 + 16 * order + 9 + 15 * order + _rice_bits(b[order:] - (acc >> sh), order, n))
         cands.append(8 + 16 * n)
