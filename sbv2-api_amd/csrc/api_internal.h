@@ -1,4 +1,4 @@
-// Shared by the translation units behind the C ABI (api.cpp, test_hooks.cpp, node.cpp, stream.cpp): handle structs and the exception -> return-code
+// Shared by the translation units behind the C ABI (api.cpp, fetch.cpp, test_hooks.cpp, node.cpp, stream.cpp): handle structs and the exception -> return-code
 // convention.  Not installed; include/sbv2_hip.h is the public contract.
 #pragma once
 #include <cstdlib>
@@ -28,7 +28,7 @@ struct sbv2_bert {
 struct sbv2_vits {
     std::unique_ptr<VitsModel> m;
 };
-// The output chain of one execution context: what the formatted fetches (fetch_formatted, api.cpp) launch on that context's stream.  Every
+// The output chain of one execution context: what the formatted fetches (fetch_formatted, fetch.cpp) launch on that context's stream.  Every
 // member grows its device and pinned buffers on first use and holds none before: a pipeline that never asks for FLAC or a limiter pays
 // nothing for them, and creating the pipeline allocates nothing here.
 struct OutputChain {

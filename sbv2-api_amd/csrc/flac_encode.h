@@ -1,5 +1,5 @@
 // FLAC encoder on the device (flac_encode.hip): mono 16-bit streams of the s16 samples PcmFormatter::run leaves in HBM, encoded before the
-// copy to the host.  Used by the FLAC sink of the formatted fetches (fetch_formatted, api.cpp), the FLAC stream (StreamOutput::push, stream_output.cpp) and the
+// copy to the host.  Used by the FLAC sink of the formatted fetches (fetch_formatted, fetch.cpp), the FLAC stream (StreamOutput::push, stream_output.cpp) and the
 // sbv2_debug_flac_* hooks (test_hooks.cpp).
 #pragma once
 #include "common.h"

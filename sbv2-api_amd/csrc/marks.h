@@ -1,6 +1,6 @@
 // Speech marks (marks.hip): where each token lies in a delivered signal (host arithmetic, marks_spans) and how loud it is there (one
 // segmented reduction over the samples a formatted fetch leaves in HBM: sum of squares and peak per [start, end) segment).  Used by
-// sbv2_pipeline_fetch_request_marks (fetch_formatted, api.cpp), sbv2_stream_marks (stream.cpp) and the test hook sbv2_debug_segment_levels.
+// sbv2_pipeline_fetch_request_marks (fetch_formatted, fetch.cpp), sbv2_stream_marks (stream.cpp) and the test hook sbv2_debug_segment_levels.
 // Beside them the pitch contour of the same samples (Pitch: YIN per frame; sbv2_pipeline_fetch_request_pitch, sbv2_debug_pitch) and the same
 // contour fed replay by replay (StreamPitch; sbv2_stream_begin_request_pitch, sbv2_debug_stream_pitch).
 #pragma once

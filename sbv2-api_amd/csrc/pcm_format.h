@@ -1,5 +1,5 @@
 // Output formats of the PCM (pcm_format.hip): rational polyphase resampling from 44.1 kHz, optional peak normalisation and the f32 -> s16
-// quantiser (with the G.711 mu-law / A-law codes of its integers as two more deliveries), on the device, next to the PCM a run leaves in HBM.  Used by the formatted fetches (fetch_formatted, api.cpp) and the streaming decoder (vits.cpp).
+// quantiser (with the G.711 mu-law / A-law codes of its integers as two more deliveries), on the device, next to the PCM a run leaves in HBM.  Used by the formatted fetches (fetch_formatted, fetch.cpp) and the streaming decoder (vits.cpp).
 #pragma once
 #include "common.h"
 

@@ -1,5 +1,5 @@
 // Pitch and intonation scale (voice.hip): a length-preserving TD-PSOLA of the run's native f32 rows, in front of the formatter (fetch_formatted,
-// api.cpp), as include/sbv2_hip.h states it above sbv2_voice.  Used by sbv2_pipeline_fetch_request_voice and the test hook sbv2_debug_voice_shift.
+// fetch.cpp), as include/sbv2_hip.h states it above sbv2_voice.  Used by sbv2_pipeline_fetch_request_voice and the test hook sbv2_debug_voice_shift.
 // Three steps on one stream: the YIN contour of every listed row (k_pitch_yin of marks.hip on f32, one launch per row), the marks of every row
 // (k_voice_marks, one workgroup per row: mean f0, phase increments, ta / ts / map) and the overlap-add gather (k_voice_gather, the hot path).
 // Per-token pitch targets (sbv2_token_pitch, sbv2_pipeline_fetch_request_token_pitch, sbv2_debug_voice_tokens) are one more phase of the marks

@@ -5,6 +5,7 @@ pipeline entry points are the new capabilities (the reference is 
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -990,6 +991,28 @@ def get_trace(session: Session, name: str, utt: int = 0) -> np.ndarray:
     return out
 
 
+# What a Pipeline.fetch_request result holds, by name (None: not there, or there and None)
+FetchResult = namedtuple("FetchResult", "signal stats marks pitch dyn_stats token_pitch", defaults=(None,) * 4)
+
+
+def _fetch_fields(marks=False, pitch=False, dynamics=False, token_pitch=False):
+    """THE rule of the shape of a Pipeline.fetch_request result, from which of these four options were given: (signal, stats); then
+    marks-or-None if marks or pitch was; then the filled Pitch if pitch was; then the compressor's stats-or-None if dynamics was; then the
+    filled TokenPitch if token_pitch was."""
+    there = (True, True, marks or pitch, pitch, dynamics, token_pitch)
+    return [name for name, t in zip(FetchResult._fields, there) if t]
+
+
+def fetch_result(r: FetchResult, **given) -> tuple:
+    """The tuple Pipeline.fetch_request returns when the options `given` were (_fetch_fields), from its named fields."""
+    return tuple(getattr(r, name) for name in _fetch_fields(**given))
+
+
+def split_fetch_result(res, **given) -> FetchResult:
+    """... and such a tuple taken apart again, for the same options."""
+    return FetchResult(**dict(zip(_fetch_fields(**given), res, strict=True)))   # (ValueError for a tuple of another length)
+
+
 class Pipeline:
     """New capability: bert::predict -> word2ph feature repeat (tts_util.rs:129-154) -> model::synthesize for a batch,
     device resident between the stages."""
@@ -1110,26 +1133,28 @@ class Pipeline:
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
                       voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
-        joined_len native samples, through the same output chain as the fetches above (sbv2_pipeline_fetch_request).  gain: None, a Loudness
+        joined_len native samples, through the same output chain as the fetches above.  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
         read: the requests that share a run are fetched one by one from the same ticket.
-        marks=True: (signal, stats, Marks) through sbv2_pipeline_fetch_request_marks: the listed rows' token spans on the delivered timeline, with
+        Whatever is asked for, this is ONE call of sbv2_pipeline_fetch_request_formant, the widest of the C symbols, with NULL for every stage
+        that is not; the shape of the result follows _fetch_fields.
+        marks=True: (signal, stats, Marks): the listed rows' token spans on the delivered timeline, with
         their levels (levels=False: timing only, no kernel) and, with env_hop > 0 delivered samples, the envelope.  The signal and stats are
         those of the same call without marks.
-        pitch: a Pitch -> a fourth element, that Pitch with the contour of the delivered signal (sbv2_pipeline_fetch_request_pitch); the third is
+        pitch: a Pitch -> a fourth element, that Pitch with the contour of the delivered signal; the third is
         None without marks.  Signal, stats and marks are those of the same call without pitch.
-        voice: a Voice -> the listed rows are shifted on the device before the formatter (sbv2_pipeline_fetch_request_voice); everything else,
+        voice: a Voice -> the listed rows are shifted on the device before the formatter; everything else,
         the returned shape included, is the same call on the shifted rows.  None or Voice(1, 1): exactly the call without.
-        track: a PitchTrack -> the contours are tracked (sbv2_pipeline_fetch_request_tracked): the delivered one (pitch) and the shifter's own
+        track: a PitchTrack -> the contours are tracked: the delivered one (pitch) and the shifter's own
         (a voice that shifts); it needs one of the two.  None: exactly the call without.
-        dynamics: a Dynamics -> the compressor runs in front of `gain`, which must be given (sbv2_pipeline_fetch_request_dynamics), and the
+        dynamics: a Dynamics -> the compressor runs in front of `gain`, which must be given, and the
         returned tuple gains a last element: the stage's stats [3] (L of the uncompressed signal, the threshold T, the deepest compression
         in dB), or None at ratio 1, which is exactly the call without.  `stats` are then those of the compressed signal.
-        token_pitch: a TokenPitch -> the listed rows' tokens are edited in the shifter (sbv2_pipeline_fetch_request_token_pitch), whatever the
+        token_pitch: a TokenPitch -> the listed rows' tokens are edited in the shifter, whatever the
         voice is, and the returned tuple gains a last element: that TokenPitch with applied [n] (the ratio used per token) and src_f0 [n]
         (the token's measured mean f0, 0 without a voiced frame) filled.  All zeros: the bytes of the call without.
         formant_scale: in [0.5, 2] -> the listed rows' formants are moved by that factor in the shifter's gather, whatever the voice is
-        (sbv2_pipeline_fetch_request_formant; model.Formant states it); the returned tuple is that of the call without.  1.0: exactly that call."""
+        (model.Formant states it); the returned tuple is that of the call without.  1.0: exactly that call."""
         fm = None if formant_scale == 1.0 else Formant(formant_scale)   # (a NaN is carried on and refused by the library)
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
@@ -1141,44 +1166,16 @@ class Pipeline:
         nstats = 0 if gain is None else 6 if limited else 3
         req = Sbv2FetchRequest(rw.ctypes.data_as(C.POINTER(C.c_int32)), rw.size, pp, int(joined_len), C.pointer(fmt.c),
                                None if gain is None or limited else C.pointer(gain.c), C.pointer(gain.c) if limited else None, int(bool(flac)))
-        size = (flac_bound if flac else pcm_format_length)(fmt, int(joined_len))
-        dst = np.empty(max(size, 1), np.uint8 if flac else fmt.dtype)
+        out_len = pcm_format_length(fmt, int(joined_len))
+        dst = np.empty(max(flac_bound(fmt, int(joined_len)) if flac else out_len, 1), np.uint8 if flac else fmt.dtype)
         got = C.c_int64(0)
         stats = np.zeros(nstats, np.float64) if nstats else None
-        if pitch is not None:
-            cp, parr = pitch.c_struct(pcm_format_length(fmt, int(joined_len)))
-        if track is not None:
-            ct = track.c
-            tracked = lambda *a: _lib.lib().sbv2_pipeline_fetch_request_tracked(*a[:3], C.byref(voice.c) if voice is not None else None, C.byref(ct), *a[3:])
-        if dynamics is not None:
-            dst_stats = None if dynamics.is_identity() else np.zeros(3, np.float64)
-            cd = dynamics.c
-            compressed = lambda *a: _lib.lib().sbv2_pipeline_fetch_request_dynamics(
-                *a[:3], C.byref(voice.c) if voice is not None else None, C.byref(track.c) if track is not None else None, C.byref(cd), *a[3:7],
-                _f64p(dst_stats) if dst_stats is not None else None, *a[7:])
-            if not marks and pitch is None and token_pitch is None and fm is None:
-                check(compressed(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
-                                 _f64p(stats) if nstats else None, None, None))
-                return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats, dst_stats
-        if token_pitch is not None:
-            ctp, tparr = token_pitch.c_struct()
-        if fm is None and token_pitch is None and dynamics is None and track is not None and not marks and pitch is None:
-            check(tracked(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
-                          None, None))
-            return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        if fm is None and token_pitch is None and dynamics is None and not marks and pitch is None and voice is None:
-            check(_lib.lib().sbv2_pipeline_fetch_request(self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got),
-                                                         _f64p(stats) if nstats else None))
-            return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
-        if fm is None and token_pitch is None and dynamics is None and not marks and pitch is None:
-            cv = voice.c
-            check(_lib.lib().sbv2_pipeline_fetch_request_voice(self.h, b.ticket, C.byref(req), C.byref(cv), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
-                                                               C.byref(got), _f64p(stats) if nstats else None, None, None))
-            return (dst[:got.value].tobytes() if flac else dst[:got.value]), stats
+        dst_stats = None if dynamics is None or dynamics.is_identity() else np.zeros(3, np.float64)
+        cp, parr = pitch.c_struct(out_len) if pitch is not None else (None, None)
+        ctp, tparr = token_pitch.c_struct() if token_pitch is not None else (None, None)
         m = cm = None
         if marks:
             ntok = int(sum(int(b.t_lens[r]) for r in rw))
-            out_len = pcm_format_length(fmt, int(joined_len))
             nenv = -(-out_len // int(env_hop)) if env_hop > 0 else 0
             m = Marks(np.zeros(ntok, np.int64), np.zeros(ntok, np.int64), np.zeros(ntok, np.float64) if levels else None,
                       np.zeros(ntok, np.float64) if levels else None, env_hop, np.zeros(nenv, np.float64) if env_hop > 0 else None,
@@ -1186,37 +1183,16 @@ class Pipeline:
             cm = _lib.Sbv2Marks(ntok, m.start.ctypes.data_as(i64p), m.end.ctypes.data_as(i64p), _f64p(m.sumsq) if levels else None,
                                 _f64p(m.peak) if levels else None, 0, int(env_hop), 0, nenv, _f64p(m.env_sumsq) if env_hop > 0 else None,
                                 _f64p(m.env_peak) if env_hop > 0 else None, 0)
-        args = (self.h, b.ticket, C.byref(req), dst.ctypes.data_as(C.c_void_p), dst.nbytes, C.byref(got), _f64p(stats) if nstats else None,
-                C.byref(cm) if marks else None)
-        if fm is not None:
-            none = lambda o: C.byref(o.c) if o is not None else None   # (every struct is read during the call only)
-            check(_lib.lib().sbv2_pipeline_fetch_request_formant(
-                *args[:3], none(voice), none(track), none(dynamics), C.byref(ctp) if token_pitch is not None else None, none(fm), *args[3:7],
-                _f64p(dst_stats) if dynamics is not None and dst_stats is not None else None, args[7], C.byref(cp) if pitch is not None else None))
-        elif token_pitch is not None:
-            none = lambda o: C.byref(o.c) if o is not None else None   # (every struct is read during the call only)
-            check(_lib.lib().sbv2_pipeline_fetch_request_token_pitch(
-                *args[:3], none(voice), none(track), none(dynamics), C.byref(ctp), *args[3:7],
-                _f64p(dst_stats) if dynamics is not None and dst_stats is not None else None, args[7], C.byref(cp) if pitch is not None else None))
-        elif dynamics is not None:
-            check(compressed(*args, C.byref(cp) if pitch is not None else None))
-        elif track is not None:
-            check(tracked(*args, C.byref(cp) if pitch is not None else None))
-        elif voice is not None:
-            cv = voice.c
-            check(_lib.lib().sbv2_pipeline_fetch_request_voice(*args[:3], C.byref(cv), *args[3:], C.byref(cp) if pitch is not None else None))
-        elif pitch is None:
-            check(_lib.lib().sbv2_pipeline_fetch_request_marks(*args))
-        else:
-            check(_lib.lib().sbv2_pipeline_fetch_request_pitch(*args, C.byref(cp)))
+        ref = lambda c: C.byref(c) if c is not None else None   # (NULL for every stage not asked for; a struct is read during the call only)
+        opt = lambda o: ref(o.c if o is not None else None)
+        check(_lib.lib().sbv2_pipeline_fetch_request_formant(
+            self.h, b.ticket, C.byref(req), opt(voice), opt(track), opt(dynamics), ref(ctp), opt(fm), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
+            C.byref(got), _f64p(stats) if nstats else None, _f64p(dst_stats) if dst_stats is not None else None, ref(cm), ref(cp)))
         if marks:
             assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
-        out = dst[:got.value].tobytes() if flac else dst[:got.value]
-        res = (out, stats, m) if pitch is None else (out, stats, m, pitch.take(cp, parr))
-        if (token_pitch is not None or fm is not None) and not marks and pitch is None:
-            res = res[:2]
-        res = res if dynamics is None else res + (dst_stats,)
-        return res if token_pitch is None else res + (token_pitch.take(tparr),)
+        res = FetchResult(dst[:got.value].tobytes() if flac else dst[:got.value], stats, m, pitch.take(cp, parr) if pitch is not None else None,
+                          dst_stats, token_pitch.take(tparr) if token_pitch is not None else None)
+        return fetch_result(res, marks=bool(marks), pitch=pitch is not None, dynamics=dynamics is not None, token_pitch=token_pitch is not None)
 
     def close(self):
         if self.h:

@@ -479,53 +479,43 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
     dynamics_stats: an optional list that receives the compressor's [L, T, deepest compression] when plan.dynamics compresses; the marks then
     carry them as a "dynamics" block (dynamics_dict), and loudness_stats are those of the compressed signal."""
     options, fmt, ln = plan.options, plan.fmt, plan.gain
-    dyn = getattr(plan, "dynamics", None)
-    dkw = {} if dyn is None else {"dynamics": dyn}   # (named only when asked for, like voice)
-    dstats = None
     lens = b.lens[r0:r1]
-    voice = voice_options(options)
-    vkw = {} if voice is None else {"voice": voice}   # (named only when asked for: a request at the defaults is the call it always was)
-    track = track_options(options)
-    tp = getattr(plan, "token_pitch", None)
-    if tp is not None:   # (named only when asked for; the fetch's tuple then ends with the filled TokenPitch)
-        dkw = dict(dkw, token_pitch=tp)
-    fq = formant_options(options)
-    if fq is not None:   # (named only when asked for; the fetch's tuple is that of the call without)
+    # every option is named only when asked for: a request at the defaults is the call it always was
+    dyn, voice, tp, fq = getattr(plan, "dynamics", None), voice_options(options), getattr(plan, "token_pitch", None), formant_options(options)
+    if fq is not None:
         require_formant(pipe, options)
-        dkw = dict(dkw, formant_scale=fq)
+    kw = {k: v for k, v in (("voice", voice), ("dynamics", dyn), ("token_pitch", tp), ("formant_scale", fq)) if v is not None}
     shifts = voice is not None or tp is not None or fq is not None
     if ln is not None or not fmt.is_default or marks is not None or shifts:
         # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
+        kw.update(gain=ln, flac=plan.flac)
+        pitch = None
         if marks is not None:
-            kw = dict(gain=ln, flac=plan.flac, marks=True, env_hop=envelope_hop(options, fmt.sample_rate), **vkw)
+            kw.update(marks=True, env_hop=envelope_hop(options, fmt.sample_rate))
             pitch = pitch_options(options, fmt.sample_rate)
-            if track is not None and (pitch is not None or shifts):   # (likewise named only when asked for)
-                kw["track"] = track
-            if pitch is None:   # (the call of a request without a contour is the call it always was)
-                out, stats, m, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw, **dkw)
-            else:
-                out, stats, m, pitch, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, pitch=pitch, **kw, **dkw)
-            dstats = rest[0] if dyn is not None else None
-            marks.append(marks_dict(plan.utts, plan.live, fmt, m, pitch, **({"tracked": True} if "track" in kw and pitch is not None else {})))
+            if pitch is not None:
+                kw["pitch"] = pitch
+        track = track_options(options)
+        if track is not None and (pitch is not None or shifts):   # (it needs a contour or a shift)
+            kw["track"] = track
+        got = model.split_fetch_result(pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw), marks=marks is not None,
+                                       pitch=pitch is not None, dynamics=dyn is not None, token_pitch=tp is not None)
+        out, stats, dstats = got.signal, got.stats, got.dyn_stats
+        if marks is not None:
+            marks.append(marks_dict(plan.utts, plan.live, fmt, got.marks, got.pitch, **({"tracked": True} if "track" in kw and pitch is not None else {})))
             if dstats is not None:
                 marks[-1]["dynamics"] = dynamics_dict(dstats)
             if tp is not None:
-                marks[-1]["pitch_edit"] = pitch_edit_dict(rest[-1])
+                marks[-1]["pitch_edit"] = pitch_edit_dict(got.token_pitch)
             if fq is not None:
                 marks[-1]["formant_scale"] = fq
-        else:
-            tkw = {"track": track} if track is not None and shifts else {}
-            out, stats, *rest = pipe.fetch_request(b, range(r0, r1), fmt, place, joined, gain=ln, flac=plan.flac, **vkw, **tkw, **dkw)
-            dstats = rest[0] if dyn is not None else None
         if dstats is not None and dynamics_stats is not None:
             dynamics_stats.append([float(v) for v in dstats])
         if stats is not None and loudness_stats is not None:
             loudness_stats.append([float(v) for v in stats])
-        if plan.flac:
-            return out
-        return _pcm_wav(out, fmt)
+        return out if plan.flac else _pcm_wav(out, fmt)
     if pcm is None:
         pcm = pipe.fetch(b)
     parts = []

@@ -694,6 +694,60 @@ def test_pipeline_formant_with_table_tracking_compressor_loudness_and_flac(five_
     assert [x.tobytes() for x in pipe.fetch(b)] == [x.tobytes() for x in c.native]
 
 
+# the fetch-request ladder, narrowest first: each symbol takes what the one before takes and one stage more
+RUNGS = ["", "_marks", "_pitch", "_voice", "_tracked", "_dynamics", "_token_pitch", "_formant"]
+
+
+@gpu
+@pytest.mark.parametrize("rung", RUNGS)
+def test_every_rung_of_the_fetch_request_ladder_is_the_widest_call(five_rows, edits, rung):
+    """include/sbv2_hip.h states each narrower sbv2_pipeline_fetch_request* symbol as exactly the next wider call with NULL.  Python reaches the
+    widest only, so each symbol is called raw here with the richest arguments it can carry (marks with levels and an envelope, a Pitch,
+    Voice(1.3, 0.8), a PitchTrack, a Dynamics in front of a loudness target, the token table, a scale), into s16 at 48 kHz so that the resampler
+    and the quantiser run, and compared bit for bit with sbv2_pipeline_fetch_request_formant given the same arguments and NULL for the rest."""
+    c, e, l = five_rows, edits, _lib.lib()
+    k = RUNGS.index(rung)
+    f = model.PcmFormat(48000, "s16")
+    n_out = model.pcm_format_length(f, c.joined)
+    rw, pl, gain = np.asarray(c.rows, np.int32), np.asarray(c.place, np.int64), model.Loudness(-23.0)
+    req = _lib.Sbv2FetchRequest(rw.ctypes.data_as(i32p), rw.size, pl.ctypes.data_as(i64p), c.joined, C.pointer(f.c), C.pointer(gain.c), None, 0)
+    ntok, env_hop = sum(e.counts), 480
+    nenv = -(-n_out // env_hop)
+
+    def fetch(widest):
+        dst, got, stats, dyn = np.zeros(n_out, np.int16), C.c_int64(-1), np.full(3, np.nan), np.full(3, np.nan)
+        mi = [np.full(ntok, -1, np.int64) for _ in range(2)]
+        mf = [np.full(n, np.nan) for n in (ntok, ntok, nenv, nenv)]
+        cm = _lib.Sbv2Marks(ntok, mi[0].ctypes.data_as(i64p), mi[1].ctypes.data_as(i64p), mf[0].ctypes.data_as(f64p), mf[1].ctypes.data_as(f64p), -1,
+                            env_hop, 0, nenv, mf[2].ctypes.data_as(f64p), mf[3].ctypes.data_as(f64p), -1)
+        cp, parr = model.Pitch(240).c_struct(n_out)
+        ctp, tparr = e.tp().c_struct()
+        stages = [model.Voice(*VOICE).c, model.PitchTrack().c, model.Dynamics().c, ctp, _lib.Sbv2Formant(1.2, 0.0)]
+        n_stages = max(0, k - 2)                                                  # voice .. formant: what this rung can name
+        stages = [C.byref(s) if i < n_stages else None for i, s in enumerate(stages)]
+        tail = [C.byref(cm) if k >= 1 else None, C.byref(cp) if k >= 2 else None]
+        out = [dst.ctypes.data, dst.nbytes, C.byref(got), stats.ctypes.data_as(f64p)]
+        dyn_p = dyn.ctypes.data_as(f64p) if k >= 5 else None
+        if widest:
+            model.check(l.sbv2_pipeline_fetch_request_formant(c.pipe.h, c.b.ticket, C.byref(req), *stages, *out, dyn_p, *tail))
+        else:
+            fn = getattr(l, "sbv2_pipeline_fetch_request" + rung)
+            model.check(fn(c.pipe.h, c.b.ticket, C.byref(req), *stages[:n_stages], *out, *([dyn_p] if k >= 5 else []), *tail[:min(k, 2)]))
+        return dict(dst=dst.tobytes(), got=got.value, stats=stats.tobytes(), dyn=dyn.tobytes(), marks=[a.tobytes() for a in mi + mf],
+                    marks_n=(cm.n_tokens, cm.n_env), pitch=[a.tobytes() for a in parr], pitch_n=cp.n_frames, tokens=[a.tobytes() for a in tparr])
+
+    mine, widest = fetch(False), fetch(True)
+    assert mine == widest, [name for name in mine if mine[name] != widest[name]]
+    # ... and the arguments did reach the routine: whatever this rung names was filled, whatever it cannot name was left alone
+    assert mine["got"] == n_out and not np.isnan(np.frombuffer(mine["stats"])).any()
+    assert mine["marks_n"] == ((ntok, nenv) if k >= 1 else (-1, -1)) and np.isfinite(np.frombuffer(mine["marks"][2])).all() == (k >= 1)
+    assert mine["pitch_n"] == (-(-n_out // 240) if k >= 2 else 0)
+    assert (not np.isnan(np.frombuffer(mine["dyn"])).any()) == (k >= 5)
+    assert (np.frombuffer(mine["tokens"][1]) > 0).any() == (k >= 6)                 # src_f0: measured where the table is given
+    plain = c.pipe.fetch_request(c.b, c.rows, f, c.place, c.joined, gain=gain)[0].tobytes()
+    assert (mine["dst"] == plain) == (k < 3)                                        # from the voice on, the signal is another
+
+
 @gpu
 def test_batcher_and_rest_carry_the_scale(monkeypatch):
     """Two concurrent requests with different scales each get the bytes of the request run alone, through the batcher and through REST (without

@@ -336,3 +336,51 @@ def test_rest_contract():
     r = c.post("/synthesize", json={"text": "x", "ident": "nope"})
     assert r.status_code == 500 and r.text == "Something went wrong: model not found: nope"
     assert c.post("/synthesize", json={"ident": "tsukuyomi"}).status_code == 422        # missing field (axum answers 422 as well)
+
+
+# The shape of a Pipeline.fetch_request result for every combination of (marks, pitch, dynamics, token_pitch), written out by hand from the
+# method's docstring: the names of the elements behind (signal, stats), in order.
+FETCH_RESULT_SHAPES = {
+    (0, 0, 0, 0): (),
+    (0, 0, 0, 1): ("token_pitch",),
+    (0, 0, 1, 0): ("dyn_stats",),
+    (0, 0, 1, 1): ("dyn_stats", "token_pitch"),
+    (0, 1, 0, 0): ("marks", "pitch"),
+    (0, 1, 0, 1): ("marks", "pitch", "token_pitch"),
+    (0, 1, 1, 0): ("marks", "pitch", "dyn_stats"),
+    (0, 1, 1, 1): ("marks", "pitch", "dyn_stats", "token_pitch"),
+    (1, 0, 0, 0): ("marks",),
+    (1, 0, 0, 1): ("marks", "token_pitch"),
+    (1, 0, 1, 0): ("marks", "dyn_stats"),
+    (1, 0, 1, 1): ("marks", "dyn_stats", "token_pitch"),
+    (1, 1, 0, 0): ("marks", "pitch"),
+    (1, 1, 0, 1): ("marks", "pitch", "token_pitch"),
+    (1, 1, 1, 0): ("marks", "pitch", "dyn_stats"),
+    (1, 1, 1, 1): ("marks", "pitch", "dyn_stats", "token_pitch"),
+}
+
+
+@pytest.mark.parametrize("given", sorted(FETCH_RESULT_SHAPES))
+def test_fetch_result_shape_rule(given):
+    """model.fetch_result / model.split_fetch_result, the one statement of the shape of a fetch_request result: the tuple's length and the place
+    of every element equal the table above, and taking a built tuple apart gives the fields back.  Also with an element that is there and None:
+    the marks of a call with pitch and without marks, the compressor's stats at ratio 1."""
+    from sbv2_api_amd import model
+    has = dict(zip(("marks", "pitch", "dynamics", "token_pitch"), map(bool, given)))
+    want = ("signal", "stats") + FETCH_RESULT_SHAPES[given]
+    full = model.FetchResult(*(object() for _ in model.FetchResult._fields))
+    cases = [full]
+    if has["pitch"] and not has["marks"]:
+        cases.append(full._replace(marks=None))
+    if has["dynamics"]:
+        cases.append(full._replace(dyn_stats=None))
+    for r in cases:
+        t = model.fetch_result(r, **has)
+        assert isinstance(t, tuple) and len(t) == len(want)
+        for k, name in enumerate(want):
+            assert t[k] is getattr(r, name), (given, k, name)
+        back = model.split_fetch_result(t, **has)
+        for name in model.FetchResult._fields:   # what is not in the tuple comes back as None
+            assert getattr(back, name) is (getattr(r, name) if name in want else None), (given, name)
+    with pytest.raises(ValueError):
+        model.split_fetch_result(model.fetch_result(full, **has) + (None,), **has)
