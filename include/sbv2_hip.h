@@ -1071,10 +1071,18 @@ int sbv2_debug_conv_transpose1d_clx(int device, const float* x, const float* w, 
 /* A whole ResBlock1 branch (HifiGanResidualBlock.forward, modeling_vits.py:455-463; the graph of scripts/convert/convert_model.py:97-110): three steps
    y_q = conv2_q(lrelu(conv1_q(lrelu(y_{q-1}), dilations[q]) + b1_q)) + b2_q + y_{q-1}, result beta * y_3 [+ y when accumulate], masked by mask[n / mask_div]
    (a power of two; mask may be null) at every layer; channels-last x / y [N][C], w [6][C][C][k] and bias [6][C] in the order conv1_0, conv2_0, conv1_1, ...,
-   split-bf16, C in {16, 32, 64, 128}; variant 0 = three launches of the fused step (respair_clx.hip, C <= 64), 1 = one launch (resbranch_clx.hip), 2 = six
-   launches of conv_cl.hip (any C).  iters > 0: *ms = average duration of `iters` further runs.  Test / measurement hook. */
+   split-bf16, C in {16, 32, 64, 128, 256}; variant 0 = three launches of the fused step (respair_clx.hip, C <= 64), 1 = one launch (resbranch_clx.hip,
+   C <= 128), 2 = six launches of conv_cl.hip (any C), 3 = six launches of conv_clx.hip as the decoder's wide stages make them (C >= 128: the input's bf16
+   parts by one split_cl pass, conv1 writes parts only, conv2 reads them and adds the residual plane; beta and accumulate on the last launch).
+   iters > 0: *ms = average duration of `iters` further runs.  Test / measurement hook. */
 int sbv2_debug_resbranch(int device, const float* x, const float* w, const float* bias, int64_t C, int64_t N, int64_t k, const int64_t* dilations,
                          const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, int64_t iters, float* y, float* ms);
+/* Variant 3 of sbv2_debug_resbranch whose last launch also writes the bf16 parts of lrelu(y, 0.1), as the last branch of a stage does for the next
+   transposed convolution: ys (may be null) [N][C] = hi + lo of those parts.  y_steps, ys_steps (may be null) [2][N][C]: the planes the first two steps
+   returned and hi + lo of the parts their conv2 launches wrote for the next step's conv1, so a test can hold the chain step by step. */
+int sbv2_debug_resbranch_ys(int device, const float* x, const float* w, const float* bias, int64_t C, int64_t N, int64_t k, const int64_t* dilations,
+                            const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int64_t iters, float* y, float* ys, float* y_steps, float* ys_steps,
+                            float* ms);
 /* y[M][N] = act(w[M][K] x[K][N] + bias) (+ res) through the split-bf16 1x1 GEMM (gemm_bfs.hip; parts 2 = bf16x3, 3 = bf16x6).  split_out != 0:
    the result is also emitted as that many bf16 parts and y returns their sum.  iters > 0: average launch time in *ms.  Test hook. */
 int sbv2_debug_gemm_bfs(int device, const float* x, const float* w, const float* bias, const float* res, int64_t M, int64_t N, int64_t K,

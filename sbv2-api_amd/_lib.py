@@ -322,6 +322,8 @@ SYMBOLS = {
                                                   C.c_int64, C.c_int64, f32p, f32p, f32p]),
     "sbv2_debug_resbranch": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, i64p, C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_int,
                                        C.c_int64, f32p, f32p]),
+    "sbv2_debug_resbranch_ys": (C.c_int, [C.c_int, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, i64p, C.c_void_p, C.c_int64, C.c_float, C.c_int,
+                                          C.c_int64, f32p, f32p, f32p, f32p, f32p]),
     "sbv2_debug_gemm_bfs_alt": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, f32p, f32p]),
     "sbv2_debug_repeat_respair": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                             C.c_float, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, f32p, f32p, i64p, i64p]),

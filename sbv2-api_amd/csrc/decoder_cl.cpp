@@ -402,6 +402,54 @@ ResPairParams step_params(const ClConv& c1, const ClConv& c2, int k, int dil, in
     return rp;
 }
 
+ConvClxParams clx_conv1_params(const ClConv& c1, const SplitClPlanes& X, const SplitClPlanes& T, int C, int64_t N, int k, int dil, const unsigned char* mask,
+                               int mask_shift) {
+    ConvClxParams p;
+    p.X = X;
+    p.W = c1.wx;
+    p.nmt = c1.nmt;
+    p.M = C;
+    p.N = (int)N;
+    p.K = C;
+    p.ntaps = k;
+    p.shift0 = -dil * (k - 1) / 2;
+    p.shift_step = dil;
+    p.Ys = T;                  // conv1's result is only ever read as conv2's operand
+    p.ys_slope = 0.1f;
+    p.bias = c1.bias;
+    p.mask = mask;
+    p.mask_shift = mask_shift;
+    return p;
+}
+
+ConvClxParams clx_conv2_params(const ClConv& c2, const SplitClPlanes& T, int C, int64_t N, int k, const float* R, float* Y, const SplitClPlanes* Ys, float beta,
+                               int accumulate, const unsigned char* mask, int mask_shift) {
+    ConvClxParams p;
+    p.X = T;
+    p.W = c2.wx;
+    p.nmt = c2.nmt;
+    p.M = C;
+    p.N = (int)N;
+    p.K = C;
+    p.ntaps = k;
+    p.shift0 = -(k - 1) / 2;
+    p.shift_step = 1;
+    p.Y = Y;
+    p.ldy = C;
+    if (Ys) {
+        p.Ys = *Ys;
+        p.ys_slope = 0.1f;
+    }
+    p.bias = c2.bias;
+    p.R = R;
+    p.ldr = C;
+    p.beta = beta;
+    p.accumulate = accumulate;
+    p.mask = mask;
+    p.mask_shift = mask_shift;
+    return p;
+}
+
 // Which kernels one decoder run launches, per upsampling stage: filled by plan_decoder_cl, carried out by run_decoder_cl, which decides nothing itself
 struct VitsModel::ClStagePlan {
     bool upx = false;           // the transposed convolution as ONE phased conv_clx launch (else conv_cl's phase groups)
@@ -618,50 +666,12 @@ void VitsModel::run_decoder_cl(Arena& ar, Plane z, const SegLayout& fl, const fl
                 const bool last = q + 1 == nd;
                 float* yn = last ? XS : ((y == YA) ? YB : YA);
                 if (kern == BranchKernel::clx_steps) {
-                    ConvClxParams p1;
-                    p1.X = *ys;
-                    p1.W = rb.c1[q].wx;
-                    p1.nmt = rb.c1[q].nmt;
-                    p1.M = C;
-                    p1.N = (int)Lo;
-                    p1.K = C;
-                    p1.ntaps = rb.k;
-                    p1.shift0 = -d * (rb.k - 1) / 2;
-                    p1.shift_step = d;
-                    p1.Ys = T1s;               // conv1's result is only ever read as conv2's operand
-                    p1.ys_slope = 0.1f;
-                    p1.bias = rb.c1[q].bias;
-                    p1.mask = fl.d_mask;
-                    p1.mask_shift = ushift;
-                    launch_conv_clx(p1, stream_);
-                    ConvClxParams p2;
-                    p2.X = T1s;
-                    p2.W = rb.c2[q].wx;
-                    p2.nmt = rb.c2[q].nmt;
-                    p2.M = C;
-                    p2.N = (int)Lo;
-                    p2.K = C;
-                    p2.ntaps = rb.k;
-                    p2.shift0 = -(rb.k - 1) / 2;
-                    p2.shift_step = 1;
-                    p2.Y = yn;
-                    p2.ldy = C;
+                    launch_conv_clx(clx_conv1_params(rb.c1[q], *ys, T1s, C, Lo, rb.k, d, fl.d_mask, ushift), stream_);
                     const SplitClPlanes* yns = (ys == &YsA) ? &YsB : &YsA;
-                    if (!last) {
-                        p2.Ys = *yns;
-                        p2.ys_slope = 0.1f;
-                    } else if (sp.next_parts && j + 1 == nk) {   // the stage's finished sum: lrelu(XS, 0.1) as the next transposed convolution's operand
-                        p2.Ys = XSs;
-                        p2.ys_slope = 0.1f;
-                    }
-                    p2.bias = rb.c2[q].bias;
-                    p2.R = y;
-                    p2.ldr = C;
-                    p2.beta = last ? 1.0f / nk : 1.0f;
-                    p2.accumulate = last && j > 0;
-                    p2.mask = fl.d_mask;
-                    p2.mask_shift = ushift;
-                    launch_conv_clx(p2, stream_);
+                    // the parts of lrelu(result): the next step's operand, or (the stage's finished sum) the next transposed convolution's
+                    const SplitClPlanes* out_parts = !last ? yns : (sp.next_parts && j + 1 == nk ? &XSs : nullptr);
+                    launch_conv_clx(clx_conv2_params(rb.c2[q], T1s, C, Lo, rb.k, y, yn, out_parts, last ? 1.0f / nk : 1.0f, last && j > 0, fl.d_mask, ushift),
+                                    stream_);
                     ys = yns;
                 } else if (kern == BranchKernel::conv_cl_steps) {
                     conv_cl(rb.c1[q], y, C, (int)Lo, T1, C, (int)Lo, d, d * (rb.k - 1) / 2, fl.d_mask, U, 0.1f, nullptr, 0, 1.0f, 0);

@@ -92,6 +92,12 @@ ResPairParams step_params(const ClConv& c1, const ClConv& c2, int k, int dil, in
 // The operands of a fused ResBlock branch (resbranch_clx.hip); X, Y, beta and accumulate are the caller's
 ResBranchParams branch_params(const std::vector<ClConv>& c1, const std::vector<ClConv>& c2, const std::vector<int>& dil, int k, int C, int64_t N,
                               const unsigned char* mask, int mask_shift);
+// The two conv_clx launches of one ResBlock step of the wide stages (run_decoder_cl's clx_steps arm): conv1 reads the parts X of lrelu(y) and writes ONLY the
+// parts T of lrelu(its result); conv2 reads T, adds the residual plane R = y and writes the f32 plane Y and, when Ys is given, the parts of lrelu(Y)
+ConvClxParams clx_conv1_params(const ClConv& c1, const SplitClPlanes& X, const SplitClPlanes& T, int C, int64_t N, int k, int dil, const unsigned char* mask,
+                               int mask_shift);
+ConvClxParams clx_conv2_params(const ClConv& c2, const SplitClPlanes& T, int C, int64_t N, int k, const float* R, float* Y, const SplitClPlanes* Ys, float beta,
+                               int accumulate, const unsigned char* mask, int mask_shift);
 // w is [M][K] (Linear / 1x1 conv): bf16 parts (2 = hi + lo, 3 = hi + mid + lo) as MFMA A fragments; K must be a multiple of 16
 BfsWeights pack_bfs(WeightStore& ws, const float* w, int M, int K, int parts);
 

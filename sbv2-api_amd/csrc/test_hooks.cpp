@@ -1,8 +1,8 @@
 // The test hooks of libsbv2_hip.so (the sbv2_debug_* entry points of include/sbv2_hip.h): one kernel or launcher at a time on host data, for the tests
 // and the probe tools.  The decoder's kernels get their parameters from the decoder's own builders (decoder_cl.cpp: pack_decoder_conv, conv_cl_params,
-// step_params, branch_params), so a test of a kernel also tests what the decoder launches.  The launchers of ops.h (LayerNorm, the duration flow's pieces,
-// noise, the generator tail, the movers) have one hook per launcher or family, on planes at the library's pitches and layouts built by the models' own
-// make_layout, with the attention hooks' poison / sentinel / stray-count convention (tests/test_ops_kernels.py).
+// step_params, branch_params, clx_conv1_params, clx_conv2_params), so a test of a kernel also tests what the decoder launches.  The launchers of ops.h
+// (LayerNorm, the duration flow's pieces, noise, the generator tail, the movers) have one hook per launcher or family, on planes at the library's pitches
+// and layouts built by the models' own make_layout, with the attention hooks' poison / sentinel / stray-count convention (tests/test_ops_kernels.py).
 #include <cstring>
 #include <limits>
 #include <memory>
@@ -1067,13 +1067,19 @@ int sbv2_debug_respair(int device, const float* x, const float* w1, const float*
     API_END
 }
 
-int sbv2_debug_resbranch(int device, const float* x, const float* w, const float* bias, int64_t C, int64_t N, int64_t k, const int64_t* dilations,
-                         const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, int64_t iters, float* y, float* ms) {
+// ys (variant 3 only, may be null): hi + lo of the bf16 parts of lrelu(y, 0.1) the last launch writes, [N][C] as y
+// y_steps, ys_steps (variant 3 only, may be null): [2][N][C], the planes the first two steps' conv2 launches wrote, and hi + lo of the parts they wrote
+static int debug_resbranch_impl(int device, const float* x, const float* w, const float* bias, int64_t C, int64_t N, int64_t k, const int64_t* dilations,
+                                const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, int64_t iters, float* y, float* ms, float* ys,
+                                float* y_steps, float* ys_steps) {
     API_BEGIN
     HIP_CHECK(hipSetDevice(device));
-    SBV2_REQUIRE(x && w && bias && y && dilations && (C == 16 || C == 32 || C == 64 || C == 128) && N >= 1 && k >= 1 && k <= kMaxTaps && (k & 1) && mask_div >= 1 &&
-                     (mask_div & (mask_div - 1)) == 0, "bad arguments");
+    SBV2_REQUIRE(x && w && bias && y && dilations && (C == 16 || C == 32 || C == 64 || C == 128 || C == 256) && N >= 1 && k >= 1 && k <= kMaxTaps && (k & 1) &&
+                     mask_div >= 1 && (mask_div & (mask_div - 1)) == 0 && variant >= 0 && variant <= 3,
+                 "bad arguments");
     SBV2_REQUIRE(variant != 0 || C <= 64, "the fused step exists for C <= 64 (variant 2 = the two-launch conv_cl path at any C)");
+    SBV2_REQUIRE(variant != 3 || C >= 128, "the conv_clx step chain is the path of the >= 128-channel stages");
+    SBV2_REQUIRE(variant == 3 || (!ys && !y_steps && !ys_steps), "only the conv_clx step chain returns parts and its steps' planes");
     const size_t wsz = (size_t)C * C * k;
     Blob b = one_conv_blob(w, bias, {C, C, k}, C);
     WeightStore ws(b);
@@ -1090,7 +1096,37 @@ int sbv2_debug_resbranch(int device, const float* x, const float* w, const float
     const unsigned char* m = mask ? dm.u8() : nullptr;
     int shift = 0;
     while ((1 << shift) < mask_div) ++shift;
+    // 3 = six launches of conv_clx.hip as run_decoder_cl's clx_steps arm makes them: the input's parts by one split_cl pass, conv1 writes parts only, conv2
+    // reads them and adds the residual plane; the parts of the last result (ys) as the stage's last branch writes them for the next transposed convolution
+    const size_t sb = variant == 3 ? split_cl_bytes((int)C, N) + 16 : 0;
+    DevMem mxu(sb), mt1(sb), mya(sb), myb(sb), mys(ys ? sb : 0);
+    SplitClPlanes XUs, T1s, YsA, YsB, YSs;
+    if (variant == 3) {
+        for (int q = 0; q < kResBranchSteps; ++q) SBV2_REQUIRE(c1[q].wx && c2[q].wx, "shape not supported by conv_clx");
+        XUs = make_split_cl(mxu.p, (int)C, N, nullptr);
+        T1s = make_split_cl(mt1.p, (int)C, N, nullptr);
+        YsA = make_split_cl(mya.p, (int)C, N, nullptr);
+        YsB = make_split_cl(myb.p, (int)C, N, nullptr);
+        if (ys) YSs = make_split_cl(mys.p, (int)C, N, nullptr);
+        split_cl(dx.f(), (int)C, N, (int)C, 0.1f, XUs, nullptr);
+    }
     auto run = [&]() {
+        if (variant == 3) {
+            const float* cur = dx.f();
+            const SplitClPlanes* cs = &XUs;   // bf16 parts of lrelu(cur)
+            for (int q = 0; q < kResBranchSteps; ++q) {
+                const bool last = q + 1 == kResBranchSteps;
+                float* yn = last ? dy.f() : (q & 1 ? db.f() : da.f());
+                const SplitClPlanes* yns = (cs == &YsA) ? &YsB : &YsA;
+                launch_conv_clx(clx_conv1_params(c1[q], *cs, T1s, (int)C, N, (int)k, dil[q], m, shift), nullptr);
+                launch_conv_clx(clx_conv2_params(c2[q], T1s, (int)C, N, (int)k, cur, yn, !last ? yns : (ys ? &YSs : nullptr), last ? beta : 1.0f,
+                                                 last ? accumulate : 0, m, shift),
+                                nullptr);
+                cs = yns;
+                cur = yn;
+            }
+            return;
+        }
         if (variant == 1) {     // 1 = the fused branch (resbranch_clx.hip)
             ResBranchParams rb = branch_params(c1, c2, dil, (int)k, (int)C, N, m, shift);
             rb.X = dx.f();
@@ -1126,8 +1162,32 @@ int sbv2_debug_resbranch(int device, const float* x, const float* w, const float
     run();
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(y, dy.p, bytes, hipMemcpyDeviceToHost));
+    auto parts_cl = [&](const SplitClPlanes& s, float* out) {   // hi + lo of a parts plane, channels-last
+        std::vector<float> t((size_t)N * C);
+        read_parts(s, t.data());
+        for (int64_t c = 0; c < C; ++c)
+            for (int64_t n = 0; n < N; ++n) out[(size_t)n * C + c] = t[(size_t)c * N + n];
+    };
+    if (ys) parts_cl(YSs, ys);
+    if (y_steps) {    // (step 0 wrote da and YsA, step 1 db and YsB)
+        HIP_CHECK(hipMemcpy(y_steps, da.p, bytes, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(y_steps + (size_t)N * C, db.p, bytes, hipMemcpyDeviceToHost));
+    }
+    if (ys_steps) {
+        parts_cl(YsA, ys_steps);
+        parts_cl(YsB, ys_steps + (size_t)N * C);
+    }
     if (iters > 0 && ms) *ms = time_ms(iters, run);
     API_END
+}
+int sbv2_debug_resbranch(int device, const float* x, const float* w, const float* bias, int64_t C, int64_t N, int64_t k, const int64_t* dilations,
+                         const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int variant, int64_t iters, float* y, float* ms) {
+    return debug_resbranch_impl(device, x, w, bias, C, N, k, dilations, mask, mask_div, beta, accumulate, variant, iters, y, ms, nullptr, nullptr, nullptr);
+}
+int sbv2_debug_resbranch_ys(int device, const float* x, const float* w, const float* bias, int64_t C, int64_t N, int64_t k, const int64_t* dilations,
+                            const uint8_t* mask, int64_t mask_div, float beta, int accumulate, int64_t iters, float* y, float* ys, float* y_steps, float* ys_steps,
+                            float* ms) {
+    return debug_resbranch_impl(device, x, w, bias, C, N, k, dilations, mask, mask_div, beta, accumulate, 3, iters, y, ms, ys, y_steps, ys_steps);
 }
 int sbv2_debug_set_resbranch(int on) { return set_resbranch(on); }
 

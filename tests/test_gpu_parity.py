@@ -139,8 +139,10 @@ def _resbranch(x, w, b, k, dils, mask, mask_div, beta, prev, variant):
 def test_resbranch_kernel_same_bits_as_three_respair_steps(C, N, k):
     """resbranch_clx.hip (round 6): the three steps of a k = 3 ResBlock1 branch (dilations 1, 3, 5) in ONE launch, the residual stream in registers and the
     operand windows in LDS, gives the SAME bits as three launches of the fused step (respair_clx.hip): plain, with a column mask (edges of packed utterances:
-    mask_div 4) and with beta + accumulate (the branch's last step), at lengths around the tile sizes (232 / 104 outputs per workgroup); and both agree with
-    the numpy oracle's three resblock steps (O.conv1d_same: the checker).  The 16-channel stage's k = 7 / 11 branches run the same kernel on 512-row windows."""
+    mask_div 4) and with beta + accumulate (the branch's last step); and both agree with the numpy oracle's three resblock steps (O.conv1d_same: the checker).
+    Outputs per workgroup today (launch_resbranch: window rows - 24 at k = 3): 232 at C = 16 / 32 (256 rows), 360 at C = 64 (384 rows), 168 at C = 128 (192
+    rows); the lengths listed for C = 64 and C = 128 date from 128-row windows (104 outputs) and no longer sit on a tile edge: tests/test_decoder_kernels.py
+    runs the edges of every window.  The 16-channel stage's k = 7 / 11 branches run the same kernel on 512-row windows."""
     dils = (1, 3, 5)
     RV = 0 if C <= 64 else 2      # the reference chain: three fused steps (respair_clx, C <= 64) or six conv_cl launches (any C; same bits as the fused step)
     rng = np.random.default_rng(C * 1000 + N + k)
