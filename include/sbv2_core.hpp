@@ -167,6 +167,46 @@ inline void fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_f
                                               dyn_stats, marks, pitch));
 }
 
+// Not in the reference (upstream Style-Bert-VITS2's assist_text / assist_text_weight; sbv2_assist in sbv2_hip.h states it): assist texts of a run
+// with owned arrays.  texts: the distinct assist sequences' token ids; text_of / weight: one entry per row of the batch (-1 = none).
+struct Assist {
+    std::vector<std::vector<int64_t>> texts;
+    std::vector<int32_t> text_of;
+    std::vector<double> weight;
+    // the C struct over flat copies that live as long as this object is not changed
+    const sbv2_assist* c_struct() {
+        ids_.clear();
+        lens_.clear();
+        for (const auto& t : texts) {
+            ids_.insert(ids_.end(), t.begin(), t.end());
+            lens_.push_back((int64_t)t.size());
+        }
+        c_ = sbv2_assist{(int64_t)texts.size(), ids_.data(), lens_.data(), text_of.data(), weight.data(), 0};
+        return &c_;
+    }
+
+  private:
+    std::vector<int64_t> ids_, lens_;
+    sbv2_assist c_{};
+};
+// sbv2_pipeline_run_assist: sbv2_pipeline_run_opts with the rows' assist texts; assist == nullptr is exactly that call.
+inline void pipeline_run_assist(sbv2_pipeline* p, const sbv2_batch& batch, const sbv2_utt_options* opts, Assist* assist, const int64_t* token_ids,
+                                const int64_t* s_lens, const int64_t* word2ph, int64_t* pcm_lens) {
+    check(sbv2_pipeline_run_assist(p, &batch, opts, assist ? assist->c_struct() : nullptr, token_ids, s_lens, word2ph, pcm_lens));
+}
+// sbv2_stream_begin_request_assist: sbv2_stream_begin_request_pitch with the rows' assist texts; assist == nullptr is exactly that call.
+inline sbv2_stream* stream_begin_request_assist(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch& batch, const sbv2_utt_options* opts, Assist* assist,
+                                                const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                                const sbv2_stream_request& rq, const sbv2_stream_levels* lv = nullptr,
+                                                const sbv2_stream_pitch* sp = nullptr, int64_t* total_samples = nullptr, int64_t* n_tokens = nullptr,
+                                                int64_t* n_env = nullptr, int64_t* n_pitch = nullptr) {
+    sbv2_stream* s = nullptr;
+    check(sbv2_stream_begin_request_assist(bert, vits, &batch, opts, assist ? assist->c_struct() : nullptr, token_ids, s_lens, word2ph, chunk_frames, &rq,
+                                           lv, sp, &s, total_samples, n_tokens, n_env, n_pitch));
+    return s;
+}
+// (the kernels on their own are the test hook sbv2_debug_assist_blend of sbv2_hip.h: plain arrays in, plain arrays out, nothing to own here)
+
 }  // namespace sbv2_core
 
 #endif

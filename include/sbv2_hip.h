@@ -993,6 +993,60 @@ int sbv2_stream_uses_graph(const sbv2_stream* s);
 int64_t sbv2_stream_workspace_bytes(const sbv2_stream* s);
 void sbv2_stream_end(sbv2_stream* s);
 
+/* ---- new: assist text.  Steer HOW a sentence is spoken with a second text ("I am so happy!"): upstream Style-Bert-VITS2's assist_text /
+ * assist_text_weight.  The second text goes through the same DeBERTa; the mean of its hidden states over its tokens is mixed into every
+ * token's feature of the spoken text before the word2ph repeat: res[i] * (1 - w) + style_res_mean * w.  It is the one inference knob that acts
+ * BEFORE the model; durations, PCM, every fetch, sink, mark, voice edit and stream work unchanged on what an assisted run produces.
+ * A run of n rows also carries A >= 1 assist sequences of token ids, each of its own length S_a >= 1 with the limits of a sequence of
+ *   sbv2_pipeline_run (1 <= S_a < 2^20, ids inside the vocabulary).  Row u names one of them, text_of[u] in [0, A), or none (-1), and carries a
+ *   weight w_u, a double in [0, 1].  An assist text that no row names is allowed (a caller may hand in a deduplicated table); it is still run.
+ * Forward.  ONE DeBERTa forward over the n sequences of the batch followed by the A assist sequences (n + A rows); the packed layout puts the
+ *   batch's rows where they are without an assist.  F[c][q] below is that forward's output plane (channel-major), s_a the first column of
+ *   assist sequence a in it.
+ * Mean of assist sequence a (k_assist_mean, one 64-lane wavefront per (a, channel c), no atomics), over ALL S_a columns, [CLS] and [SEP]
+ *   included, as upstream's mean(0): lane l adds double(F[c][s_a + i]) for i = l, l + 64, l + 128, ... < S_a in ascending i, in f64, starting
+ *   from 0.0; then the lanes are folded pairwise, for h = 32, 16, 8, 4, 2, 1 in that order: acc[l] = acc[l] + acc[l + h] for every l < h;
+ *   mean_a[c] = float(acc[0] / double(S_a)).  The result depends on nothing but that sequence's own columns.
+ * Blend, fused into the word2ph gather (k_gather_cols_assist in place of the plain gather).  For text column t of row u with source column
+ *   q = map[t]: wf = float(w_u), omw = float(1.0 - w_u) (the subtraction in f64: what torch does with a Python scalar), and
+ *   out[c][t] = F[c][q] * omw + mean[c] * wf, two f32 products and one f32 sum, never contracted into a fused multiply-add.  A row with
+ *   text_of = -1 or w_u == 0 is gathered plainly, out[c][t] = F[c][q], the expression and the bits of a run without an assist.  A padding
+ *   column (map < 0) stays 0 whatever the row's weight.  The text encoder reads the blended plane where it read the gathered one; nothing
+ *   else changes.
+ * assist == NULL, or every text_of[u] == -1: exactly sbv2_pipeline_run_opts / sbv2_stream_begin_request_pitch: no assist sequence is run, the
+ *   same launches, the same bytes.  (sbv2_utt_options is not extended: it is passed by pointer and older callers hand in the shorter struct.)
+ * Co-batching.  Appended sequences change the forward's column count, and DeBERTa's small-grid summation order moves with it: a row keeps its
+ *   integer durations and its PCM to f32 rounding (2e-4 on the tiny models), and bit for bit under sbv2_debug_set_ksplit(0).
+ * Refused before any GPU work and before the handles are looked at, with the row or text named in sbv2_last_error: n_texts < 1, a NULL array,
+ *   an s_lens entry below 1 or >= 2^20, a text_of outside [-1, A), a weight that is NaN or outside [0, 1] (not read where text_of is -1), a
+ *   non-zero reserved.
+ * Not built: an assist on sbv2_node_*; on the plain single-utterance sbv2_stream_begin* entries (a request stream with one row serves them);
+ *   a per-token weight; caching an assist text's mean across runs; sbv2_bert_predict / sbv2_vits_synthesize, where the host has the features
+ *   and can blend them itself; a text front end for the assist text (the caller parses it as it parses the spoken text). */
+typedef struct sbv2_assist {
+    int64_t n_texts;            /* A >= 1 */
+    const int64_t* token_ids;   /* the A sequences back to back */
+    const int64_t* s_lens;      /* [A] */
+    const int32_t* text_of;     /* [batch->n], -1 = none */
+    const double* weight;       /* [batch->n], in [0, 1]; not read where text_of is -1 */
+    int64_t reserved;           /* must be 0 */
+} sbv2_assist;
+int sbv2_pipeline_run_assist(sbv2_pipeline* p, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                             const sbv2_assist* assist /* may be NULL */, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
+                             int64_t* pcm_lens);
+int sbv2_stream_begin_request_assist(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                                     const sbv2_assist* assist /* may be NULL */, const int64_t* token_ids, const int64_t* s_lens,
+                                     const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
+                                     const sbv2_stream_levels* lv /* may be NULL */, const sbv2_stream_pitch* sp /* may be NULL */, sbv2_stream** out,
+                                     int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch);
+/* Test hook: the two kernels on a host plane F [C][ld] (pitch ld, any value >= 1; on the device it lies between NaN words).  Assist sequence a
+ * is the columns [a_start[a], a_start[a] + a_len[a]) of F; text column t < L reads source column map[t] (< 0: padding) and belongs to row
+ * row_of[t] in [0, n_rows) (read where map[t] >= 0); text_of / weight [n_rows] as in sbv2_assist, checked the same way.  mean [A][C] and
+ * out [C][L] are pre-filled with 0x5A on the device and lie between guard words; *stray = the guard and pitch-pad words no longer 0x5A. */
+int sbv2_debug_assist_blend(int device, const float* F, int64_t C, int64_t ld, const int32_t* map, const int32_t* row_of, int64_t L, int64_t A,
+                            const int32_t* a_start, const int32_t* a_len, int64_t n_rows, const int32_t* text_of, const double* weight, float* mean,
+                            float* out, int64_t* stray);
+
 /* ---- test hooks (no reference counterpart) ------------------------------------------------------------------------ */
 /* bucket(rel) for rel in [-(max_s-1), max_s-1] (transformers modeling_deberta_v2.py:57-69); host only, no GPU needed. */
 int sbv2_debug_bucket_table(int64_t max_s, int64_t buckets, int64_t max_rel, int32_t* out);

@@ -4,6 +4,9 @@ A run of the pipeline costs about the same for one utterance as for a few dozen 
 sentences share a run get close to N times the audio of N runs in a row.  Two things make a shared run safe:
   - options per row (sbv2_pipeline_run_opts): a request's sdp_ratio / length_scale / noise scales, and its noise key (seed, sentence number
     WITHIN the request), travel with its rows, so its durations and noise are those of the request run alone;
+  - an assist text per request (options.assist): it travels on the request's rows as well (assist_ids / assist_weight); the run holds every
+    distinct assist sequence once (model._Batch.set_assist), each row blends the mean of its own, and a sequence's mean depends on nothing but
+    that sequence's columns;
   - a fetch per request (sbv2_pipeline_fetch_request, orchestrator.finish_request): each request's rows are joined, resampled, gain-staged and
     encoded as its own signal, from the run's PCM, which is only read.
 
@@ -94,6 +97,7 @@ class RequestBatcher:
             plan = orchestrator.RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
             self._check(plan.options)
             orchestrator.require_formant(self.pipe, plan.options)
+            orchestrator.require_assist(self.pipe, plan.options)   # (its rows carry the pair: equal assist ids of a run share one sequence)
             if req.marks:
                 orchestrator.envelope_hop(plan.options, plan.fmt.sample_rate)
                 orchestrator.pitch_options(plan.options, plan.fmt.sample_rate)

@@ -55,6 +55,42 @@ void apply_utt_options(VitsBatch* v, const sbv2_utt_options* o) {
     v->row_index = o->noise_index;
 }
 
+// sbv2_assist onto the run's tables (the contract above the struct, include/sbv2_hip.h); every check here, before any GPU work
+AssistSpec assist_spec(const sbv2_assist* a, int64_t n) {
+    AssistSpec s;
+    if (!a) return s;
+    SBV2_REQUIRE(a->reserved == 0, "sbv2_assist.reserved must be 0");
+    SBV2_REQUIRE(a->n_texts >= 1 && a->n_texts < (1 << 20), "sbv2_assist.n_texts must be >= 1: " + std::to_string(a->n_texts));
+    SBV2_REQUIRE(a->token_ids && a->s_lens && a->text_of && a->weight, "sbv2_assist has null fields (token_ids, s_lens, text_of, weight)");
+    const int A = (int)a->n_texts;
+    for (int t = 0; t < A; ++t) {
+        SBV2_REQUIRE(a->s_lens[t] >= 1 && a->s_lens[t] < (1 << 20),
+                     "s_lens of assist text " + std::to_string(t) + " must be in [1, 2^20): " + std::to_string(a->s_lens[t]));
+        s.total += a->s_lens[t];
+    }
+    s.rows = assist_row_table(n, A, a->text_of, a->weight);
+    bool used = false;
+    for (int64_t u = 0; u < n; ++u) used = used || a->text_of[u] >= 0;
+    if (!used) return AssistSpec();   // every text_of is -1: the run without an assist
+    s.A = A;
+    s.ids = a->token_ids;
+    s.lens = a->s_lens;
+    return s;
+}
+std::vector<AssistRow> assist_row_table(int64_t n, int A, const int32_t* text_of, const double* weight) {
+    std::vector<AssistRow> rows((size_t)n, AssistRow{-1, 0.f, 1.f, 0});
+    for (int64_t u = 0; u < n; ++u) {
+        const int32_t t = text_of[u];
+        SBV2_REQUIRE(t >= -1 && t < A, "text_of of row " + std::to_string(u) + " must be in [-1, " + std::to_string(A) + "): " + std::to_string(t));
+        if (t < 0) continue;
+        const double w = weight[u];
+        SBV2_REQUIRE(w >= 0.0 && w <= 1.0, "assist weight of row " + std::to_string(u) + " must be in [0, 1]: " + std::to_string(w));   // (a NaN fails both)
+        if (w == 0.0) continue;   // the plain gather, bit for bit
+        rows[u] = AssistRow{t, (float)w, (float)(1.0 - w), 0};
+    }
+    return rows;
+}
+
 extern "C" {
 
 const char* sbv2_last_error(void) { return last_error_cstr(); }
@@ -258,9 +294,31 @@ void sbv2_pipeline_destroy(sbv2_pipeline* p) { delete p; }
 
 // One micro-batch on one context: bert::predict -> word2ph repeat (tts_util.rs:129-154) -> model::synthesize
 void pipeline_run_one(BertModel& bm, VitsModel& vm, VitsBatch v, const int64_t* token_ids, const int64_t* s_lens,
-                      const int64_t* word2ph) {
+                      const int64_t* word2ph, const AssistSpec* assist) {
     HIP_CHECK(hipStreamSynchronize(vm.stream()));  // this context's previous batch may still be reading the DeBERTa output plane
-    bm.forward(v.n, token_ids, nullptr, s_lens);
+    std::vector<int> a_start, a_len;
+    if (assist && assist->A > 0) {
+        // the assist sequences ride behind the batch's in ONE forward: the batch's rows lie where they lie without them
+        int64_t total = 0;
+        for (int u = 0; u < v.n; ++u) {
+            SBV2_REQUIRE(s_lens[u] >= 1 && s_lens[u] < (1 << 20), "bad sequence length");
+            total += s_lens[u];
+        }
+        std::vector<int64_t> ids(token_ids, token_ids + total), lens(s_lens, s_lens + v.n);
+        ids.insert(ids.end(), assist->ids, assist->ids + assist->total);
+        lens.insert(lens.end(), assist->lens, assist->lens + assist->A);
+        bm.forward(v.n + assist->A, ids.data(), nullptr, lens.data());
+        for (int a = 0; a < assist->A; ++a) {
+            a_start.push_back(bm.layout().start[v.n + a]);
+            a_len.push_back(bm.layout().len[v.n + a]);
+        }
+        v.assist_n = assist->A;
+        v.assist_start = a_start.data();
+        v.assist_len = a_len.data();
+        v.assist_rows = assist->rows.data();
+    } else {
+        bm.forward(v.n, token_ids, nullptr, s_lens);
+    }
     const SegLayout& bl = bm.layout();
     std::vector<int> map;
     int64_t e = 0;
@@ -288,17 +346,23 @@ extern "C" {
 // latency-bound part of batch n+1 (DeBERTa, text encoder, duration predictors, flow: ~1300 small launches, ~55 ms whatever the
 // batch size) executes beside the throughput-bound HiFi-GAN kernels of batch n.  A call returns once its kernels are enqueued (the
 // host only waits for the batch's own integer durations); results are collected with sbv2_pipeline_wait / _fetch_pcm by ticket.
-int sbv2_pipeline_run_opts(sbv2_pipeline* p, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids, const int64_t* s_lens,
-                           const int64_t* word2ph, int64_t* pcm_lens) {
+// (assist == NULL, or an assist no row names: sbv2_pipeline_run_opts itself, launch for launch)
+int sbv2_pipeline_run_assist(sbv2_pipeline* p, const sbv2_batch* batch, const sbv2_utt_options* opts, const sbv2_assist* assist, const int64_t* token_ids,
+                             const int64_t* s_lens, const int64_t* word2ph, int64_t* pcm_lens) {
     API_BEGIN
     VitsBatch v = to_batch(batch);
     apply_utt_options(&v, opts);
+    const AssistSpec as = assist_spec(assist, v.n);
     SBV2_REQUIRE(p && token_ids && s_lens && word2ph && pcm_lens, "bad arguments");
     const int ctx = (int)(p->calls % p->contexts());
     ++p->calls;
-    pipeline_run_one(p->bm(ctx), p->vm(ctx), v, token_ids, s_lens, word2ph);
+    pipeline_run_one(p->bm(ctx), p->vm(ctx), v, token_ids, s_lens, word2ph, &as);
     for (int i = 0; i < v.n; ++i) pcm_lens[i] = p->vm(ctx).pcm_lens()[i];
     API_END
+}
+int sbv2_pipeline_run_opts(sbv2_pipeline* p, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids, const int64_t* s_lens,
+                           const int64_t* word2ph, int64_t* pcm_lens) {
+    return sbv2_pipeline_run_assist(p, batch, opts, nullptr, token_ids, s_lens, word2ph, pcm_lens);
 }
 int sbv2_pipeline_run(sbv2_pipeline* p, const sbv2_batch* batch, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
                       int64_t* pcm_lens) {

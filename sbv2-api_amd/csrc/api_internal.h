@@ -78,5 +78,17 @@ VitsBatch to_batch(const sbv2_batch* b);
 // The per-row arrays of sbv2_utt_options onto the batch (NULL: nothing); throws for an option out of range, before any GPU work
 void apply_utt_options(sbv2::VitsBatch* v, const sbv2_utt_options* o);
 // One batch on one execution context: bert::predict -> word2ph repeat (tts_util.rs:129-154) -> model::synthesize; returns once enqueued
+// What a run carries of an sbv2_assist (the contract above the struct, include/sbv2_hip.h): A = 0 when there is none or no row names a text
+struct AssistSpec {
+    int A = 0;
+    const int64_t* ids = nullptr;    // the A sequences back to back, `total` ids
+    const int64_t* lens = nullptr;   // [A]
+    int64_t total = 0;
+    std::vector<sbv2::AssistRow> rows;   // [n]: the row's text and f32 weights (mean_row -1: none, or a weight of 0)
+};
+// every check of the struct's fields, the row or text named; throws before any GPU work
+AssistSpec assist_spec(const sbv2_assist* a, int64_t n);
+std::vector<sbv2::AssistRow> assist_row_table(int64_t n, int A, const int32_t* text_of, const double* weight);
+// ... assist (may be null): its sequences ride behind the batch's in the one DeBERTa forward and the gather blends their means in
 void pipeline_run_one(sbv2::BertModel& bm, sbv2::VitsModel& vm, sbv2::VitsBatch v, const int64_t* token_ids, const int64_t* s_lens,
-                      const int64_t* word2ph);
+                      const int64_t* word2ph, const AssistSpec* assist = nullptr);

@@ -311,6 +311,13 @@ struct VitsBatch {
     const float* bert_host = nullptr;  // concatenated [bert_dim][T_i] blocks, or null when bert_dev is given
     const Plane* bert_dev = nullptr;   // device plane [bert_dim][*] ...
     const int* bert_map = nullptr;     // ... with HOST map: text column (packed, no gaps, utterance-major) -> source column
+    // Assist text (bert_dev only; the contract above sbv2_assist, include/sbv2_hip.h): assist_n > 0 sequences lie in bert_dev at the columns
+    // [assist_start[a], assist_start[a] + assist_len[a]) (host arrays); assist_rows [n] (host) names each row's mean and weights.  assist_n == 0:
+    // the plain gather, the launches of a batch without an assist.
+    int assist_n = 0;
+    const int* assist_start = nullptr;
+    const int* assist_len = nullptr;
+    const AssistRow* assist_rows = nullptr;
     float sdp_ratio = 0.f, length_scale = 1.f, noise_scale = 0.f, noise_scale_w = 0.f;
     uint64_t seed = 0;
     const int64_t* forced_durations = nullptr;  // concatenated, optional

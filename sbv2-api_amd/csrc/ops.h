@@ -110,6 +110,18 @@ void conv_post_tanh(Plane x, const float* w, int k, float slope, const int* seg_
                     const int64_t* pcm_off, int nseg, int up, int64_t max_samples, float* pcm, hipStream_t s);
 void transpose_out(Plane in, int col0, int T, float* out, hipStream_t s);  // out[t][c] = in[c][col0+t]
 void gather_cols(Plane in, const int* map, Plane out, hipStream_t s);       // out[c][n] = map[n]>=0 ? in[c][map[n]] : 0
+// Assist text (assist.hip; the contract above sbv2_assist, include/sbv2_hip.h).  One record per row of the batch, [n] on the device: the row of
+// `mean` blended into the row's columns (-1: none, the plain gather) and the two f32 weights wf = float(w), omw = float(1.0 - w).
+struct AssistRow {
+    int mean_row;
+    float wf, omw;
+    int pad_;
+};
+static_assert(sizeof(AssistRow) == 16, "AssistRow is one 16-byte record");
+// mean[a][c] = float(sum_i double(F[c][a_start[a] + i]) / a_len[a]) in the header's order; a_start / a_len: device arrays [A], mean [A][F.C]
+void assist_mean(Plane F, const int* a_start, const int* a_len, int A, float* mean, hipStream_t s);
+// gather_cols with out[c][n] = in[c][map[n]] * omw + mean[mean_row][c] * wf for the columns of a row that has an assist (rows[seg_of[n]])
+void gather_cols_assist(Plane in, const int* map, const int* seg_of, const AssistRow* rows, const float* mean, Plane out, hipStream_t s);
 void fill_zero(void* p, size_t bytes, hipStream_t s);
 // channels-last helpers: x[L][C]
 void add_segvec_cl(float* x, int L, int C, const float* vec, int vec_ld, const int* seg_of, const unsigned char* mask, hipStream_t s);

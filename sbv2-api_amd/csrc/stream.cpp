@@ -36,10 +36,10 @@ PcmFmtSpec flac_stream_spec(const sbv2_pcm_format* fmt) {
 // a plain stream (native f32, one row); gap_after == nullptr: one row without gaps.  Every check of the arguments has happened before.
 void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
                   int64_t chunk_frames, const PcmFmtSpec* spec, bool flac, const StreamLevelSpec* level, const int64_t* gap_after, sbv2_stream** out,
-                  int64_t* total_samples, const StreamMarksSpec* marks = nullptr) {
+                  int64_t* total_samples, const StreamMarksSpec* marks = nullptr, const AssistSpec* assist = nullptr) {
     VitsBatch run = v;
     run.skip_decoder = true;
-    pipeline_run_one(*bert->m, *vits->m, run, token_ids, s_lens, word2ph);
+    pipeline_run_one(*bert->m, *vits->m, run, token_ids, s_lens, word2ph, assist);
     std::unique_ptr<sbv2_stream> s(new sbv2_stream);
     s->bert = bert;
     s->vits = vits;
@@ -271,7 +271,7 @@ namespace {
 // sbv2_stream_begin_request, with or without levels: every check before any GPU work
 void begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids, const int64_t* s_lens,
                    const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq, const StreamMarksSpec* marks, sbv2_stream** out,
-                   int64_t* total_samples) {
+                   int64_t* total_samples, const AssistSpec* assist = nullptr) {
     SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
     SBV2_REQUIRE(rq, "no sbv2_stream_request given");
     SBV2_REQUIRE(rq->gap_after, "sbv2_stream_request.gap_after must not be NULL (one entry per row, the last one = trailing silence)");
@@ -288,7 +288,7 @@ void begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, co
     apply_utt_options(&v, opts);
     stream_check_gaps(rq->gap_after, batch->n, spec);
     begin_stream(bert, vits, v, token_ids, s_lens, word2ph, chunk_frames, &spec, rq->flac != 0, rq->level ? &lv : nullptr, rq->gap_after, out,
-                 total_samples, marks);
+                 total_samples, marks, assist);
 }
 }  // namespace
 
@@ -335,6 +335,17 @@ int sbv2_stream_begin_request_pitch(sbv2_bert* bert, sbv2_vits* vits, const sbv2
                                     const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
                                     const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp, sbv2_stream** out, int64_t* total_samples,
                                     int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch) {
+    return sbv2_stream_begin_request_assist(bert, vits, batch, opts, nullptr, token_ids, s_lens, word2ph, chunk_frames, rq, lv, sp, out, total_samples,
+                                            n_tokens, n_env, n_pitch);
+}
+
+// ... and with an assist text steering the rows' delivery (the contract above sbv2_assist, include/sbv2_hip.h): the stream gets it from the one
+// function the pipeline gets it from (pipeline_run_one).  assist NULL, or no row naming a text: exactly the call above.  The assist's fields are
+// checked with the levels' and the pitch's, before the handles are looked at.
+int sbv2_stream_begin_request_assist(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const sbv2_assist* assist,
+                                     const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                     const sbv2_stream_request* rq, const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp, sbv2_stream** out,
+                                     int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch) {
     API_BEGIN
     StreamMarksSpec marks;
     bool on = levels_spec(lv, &marks);
@@ -344,7 +355,12 @@ int sbv2_stream_begin_request_pitch(sbv2_bert* bert, sbv2_vits* vits, const sbv2
         marks.pitch_spec = pitch_spec(rate, sp->hop, sp->f0_min, sp->f0_max, sp->threshold);
         marks.pitch = on = true;
     }
-    begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples);
+    AssistSpec as;
+    if (assist) {
+        SBV2_REQUIRE(batch && batch->n >= 1, "sbv2_stream_begin_request takes at least one row");
+        as = assist_spec(assist, batch->n);
+    }
+    begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples, &as);
     const StreamLevels* l = (*out)->output()->levels();
     const StreamPitch* q = (*out)->output()->pitch();
     if (n_tokens) *n_tokens = l ? l->n_tok() : 0;

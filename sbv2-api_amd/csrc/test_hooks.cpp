@@ -1838,6 +1838,46 @@ int sbv2_debug_add_segvec(int device, const float* x, const float* vec, int64_t 
     API_END
 }
 
+// The two kernels of assist.hip on a host plane at the caller's pitch, between NaN words; the row table is the one pipeline_run_one builds
+int sbv2_debug_assist_blend(int device, const float* F, int64_t C, int64_t ld, const int32_t* map, const int32_t* row_of, int64_t L, int64_t A,
+                            const int32_t* a_start, const int32_t* a_len, int64_t n_rows, const int32_t* text_of, const double* weight, float* mean,
+                            float* out, int64_t* stray) {
+    API_BEGIN
+    SBV2_REQUIRE(F && map && row_of && a_start && a_len && text_of && weight && mean && out, "bad arguments");
+    SBV2_REQUIRE(C >= 1 && C < (1 << 20) && ld >= 1 && ld < (1 << 28) && L >= 1 && L < (1 << 28) && A >= 1 && A < (1 << 20) && n_rows >= 1 && n_rows < (1 << 20),
+                 "bad shapes");
+    for (int64_t a = 0; a < A; ++a)
+        SBV2_REQUIRE(a_len[a] >= 1 && a_start[a] >= 0 && (int64_t)a_start[a] + a_len[a] <= ld, "assist sequence " + std::to_string(a) + " outside the plane");
+    for (int64_t t = 0; t < L; ++t) {
+        SBV2_REQUIRE(map[t] < ld, "column map outside the plane");
+        SBV2_REQUIRE(map[t] < 0 || (row_of[t] >= 0 && row_of[t] < n_rows), "row_of outside the rows at column " + std::to_string(t));
+    }
+    const std::vector<AssistRow> rows = assist_row_table(n_rows, (int)A, text_of, weight);
+    HIP_CHECK(hipSetDevice(device));
+    constexpr size_t kPad = 64;
+    const size_t nF = (size_t)C * ld, nM = (size_t)A * C;
+    std::vector<uint32_t> hF(nF + 2 * kPad, kNanWord);
+    std::memcpy(hF.data() + kPad, F, sizeof(float) * nF);
+    DevMem dF(hF.data(), 4 * hF.size()), dM(4 * (nM + 2 * kPad));
+    HIP_CHECK(hipMemset(dM.p, kCtxSentinel, 4 * (nM + 2 * kPad)));
+    DevPlane Y(C, L);
+    Y.fill(true);
+    DevMem dmap(map, sizeof(int) * L), drow(row_of, sizeof(int) * L), das(a_start, sizeof(int) * A), dal(a_len, sizeof(int) * A),
+        drows(rows.data(), sizeof(AssistRow) * rows.size());
+    const Plane P{dF.f() + kPad, (int)C, (int)ld, (int)ld};
+    assist_mean(P, static_cast<const int*>(das.p), static_cast<const int*>(dal.p), (int)A, dM.f() + kPad, nullptr);
+    gather_cols_assist(P, static_cast<const int*>(dmap.p), static_cast<const int*>(drow.p), static_cast<const AssistRow*>(drows.p), dM.f() + kPad, Y.P,
+                       nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    int64_t bad = Y.get(out, kSentinelWord);
+    std::vector<uint32_t> hM(nM + 2 * kPad);
+    HIP_CHECK(hipMemcpy(hM.data(), dM.p, 4 * hM.size(), hipMemcpyDeviceToHost));
+    std::memcpy(mean, hM.data() + kPad, 4 * nM);
+    for (size_t e = 0; e < kPad; ++e) bad += (hM[e] != kSentinelWord) + (hM[kPad + nM + e] != kSentinelWord);
+    if (stray) *stray = bad;
+    API_END
+}
+
 int sbv2_debug_plane_op(int device, int op, const float* x, int64_t C, int64_t L, const int32_t* map, int64_t a, int64_t b, float* y, uint8_t* mask_out,
                         int64_t* stray) {
     API_BEGIN

@@ -684,7 +684,26 @@ void VitsModel::forward(const VitsBatch& b) {
             for (int t = 0; t < T[u]; ++t, ++e) map[tl.start[u] + t] = b.bert_map[e];
         int* d_map = ar.array<int>(Lt);
         ar.upload(d_map, map.data(), sizeof(int) * Lt, stream_);
-        gather_cols(*b.bert_dev, d_map, bert, stream_);
+        if (b.assist_n > 0) {
+            // assist text: every sequence's mean over its own columns, then the gather with the rows' blends (assist.hip)
+            SBV2_REQUIRE(b.assist_start && b.assist_len && b.assist_rows, "internal: assist tables missing");
+            const int A = b.assist_n;
+            for (int a = 0; a < A; ++a)
+                SBV2_REQUIRE(b.assist_len[a] >= 1 && b.assist_start[a] >= 0 && b.assist_start[a] + b.assist_len[a] <= b.bert_dev->L,
+                             "internal: assist sequence outside the feature plane");
+            for (int u = 0; u < n; ++u) SBV2_REQUIRE(b.assist_rows[u].mean_row < A, "internal: assist row outside the table");
+            int* d_as = ar.array<int>(A);
+            int* d_al = ar.array<int>(A);
+            AssistRow* d_ar = ar.array<AssistRow>(n);
+            float* d_mean = ar.array<float>((size_t)A * cfg_.bert_dim);
+            ar.upload(d_as, b.assist_start, sizeof(int) * A, stream_);
+            ar.upload(d_al, b.assist_len, sizeof(int) * A, stream_);
+            ar.upload(d_ar, b.assist_rows, sizeof(AssistRow) * n, stream_);
+            assist_mean(*b.bert_dev, d_as, d_al, A, d_mean, stream_);
+            gather_cols_assist(*b.bert_dev, d_map, tl.d_seg_of, d_ar, d_mean, bert, stream_);
+        } else {
+            gather_cols(*b.bert_dev, d_map, bert, stream_);
+        }
     }
 
     // ---- per-utterance vectors: g = emb_g(sid) and every Linear / 1x1 conv applied to it ---------------

@@ -157,7 +157,7 @@ class TTSModelHolder:
     # ---- tts.rs:280-349
     def easy_synthesize(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None) -> bytes:
         """`text`: a str (needs parse_text) or the already parsed list of sentence dicts / None for empty lines."""
-        options = options or orchestrator.SynthesizeOptions()
+        options = orchestrator.parsed_assist(options or orchestrator.SynthesizeOptions(), self.parse_text)   # (options.assist as a str: parsed here)
         self.find_and_load_model(ident)
         m = self._find(ident)
         sentences = self._sentences(text, options)
@@ -167,7 +167,7 @@ class TTSModelHolder:
 
     def easy_synthesize_marks(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None):
         """easy_synthesize with speech marks: (bytes, marks) (orchestrator.easy_synthesize_marks)."""
-        options = options or orchestrator.SynthesizeOptions()
+        options = orchestrator.parsed_assist(options or orchestrator.SynthesizeOptions(), self.parse_text)   # (options.assist as a str: parsed here)
         self.find_and_load_model(ident)
         m = self._find(ident)
         sentences = self._sentences(text, options)
@@ -183,7 +183,7 @@ class TTSModelHolder:
         when the model's batcher is created.  The caller serialises calls of this method (rest.py: under its lock); waiting for the
         Future needs no lock.  A model with a batcher is served through it alone: easy_synthesize on the same ident would share its pipeline.
         marks=True: the Future holds (bytes, marks), as easy_synthesize_marks returns them."""
-        options = options or orchestrator.SynthesizeOptions()
+        options = orchestrator.parsed_assist(options or orchestrator.SynthesizeOptions(), self.parse_text)   # (options.assist as a str: parsed here)
         self.find_and_load_model(ident)
         m = self._find(ident)
         sentences = self._sentences(text, options)
@@ -220,7 +220,7 @@ class TTSModelHolder:
         split=True: the request's lines as the rows of one batched forward, delivered as one signal sentence by sentence, with the pauses and
         the bytes of easy_synthesize.  `text` is a str, split on '\\n' and parsed per line as _sentences does, or the list of parsed lines with
         None for an empty line."""
-        options = options or orchestrator.SynthesizeOptions()
+        options = orchestrator.parsed_assist(options or orchestrator.SynthesizeOptions(), self.parse_text)   # (options.assist as a str: parsed here)
         self.find_and_load_model(ident)
         m = self._find(ident)
         if isinstance(text, str):

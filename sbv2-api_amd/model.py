@@ -902,6 +902,23 @@ def debug_segment_levels(x, starts, ends, device: int = 0, encoding: str | None 
     return ss, pk
 
 
+def debug_assist_blend(F, col_map, row_of, a_start, a_len, text_of, weight, device: int = 0):
+    """(mean [A][C], out [C][L], stray, raw) of the two assist kernels on the host plane F [C][ld] (sbv2_debug_assist_blend): assist sequence a
+    is F's columns [a_start[a], a_start[a] + a_len[a]), text column t reads column col_map[t] (< 0: padding) and belongs to row row_of[t];
+    text_of / weight per row as in sbv2_assist.  mean and out come back as uint32 words too (raw), so that a word the kernels never wrote
+    (0x5A5A5A5A) can be told from a value."""
+    F = np.ascontiguousarray(F, np.float32)
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
+    m, r, st, ln, to = i32(col_map), i32(row_of), i32(a_start), i32(a_len), i32(text_of)
+    w = np.ascontiguousarray(np.asarray(weight, np.float64).reshape(-1))
+    Cn, ld = F.shape
+    mean, out, stray = np.zeros((st.size, Cn), np.float32), np.zeros((Cn, m.size), np.float32), C.c_int64(-1)
+    p32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    check(_lib.lib().sbv2_debug_assist_blend(int(device), F.ctypes.data_as(f32p), Cn, ld, p32(m), p32(r), m.size, st.size, p32(st), p32(ln), to.size,
+                                             p32(to), _f64p(w), mean.ctypes.data_as(f32p), out.ctypes.data_as(f32p), C.byref(stray)))
+    return mean, out, stray.value, (mean.view(np.uint32), out.view(np.uint32))
+
+
 class _Batch:
     """Keeps the numpy buffers of one sbv2_batch alive."""
 
@@ -919,6 +936,7 @@ class _Batch:
                            p(self.styles, f32p), p(self.bert, f32p), sdp_ratio, length_scale, noise_scale, noise_scale_w, noise_seed,
                            p(self.forced, i64p))
         self.opts = None   # Sbv2UttOptions when an utterance overrides an option (set_row_options)
+        self.assist = None   # Sbv2Assist when an utterance carries an assist text (set_assist)
 
     ROW_KEYS = ("sdp_ratio", "length_scale", "noise_scale", "noise_scale_w", "noise_seed", "noise_index")
 
@@ -932,6 +950,41 @@ class _Batch:
         self.rows.append(np.array([int(u.get("noise_seed", self.c.noise_seed)) & (2 ** 64 - 1) for u in utts], np.uint64))
         self.rows.append(col("noise_index", np.int64, lambda i: i))
         self.opts = Sbv2UttOptions(*[a.ctypes.data_as(t) for a, t in zip(self.rows, [f32p] * 4 + [C.POINTER(C.c_uint64), i64p])])
+
+
+    def set_assist(self, utts):
+        """Assist texts (struct sbv2_assist): an utterance dict may carry assist_ids (the token ids of a second text whose mean DeBERTa feature
+        is mixed into the utterance's own) with assist_weight in [0, 1].  Equal id sequences become ONE assist text of the run.  An utterance
+        without assist_ids, or with a weight of 0, has none; nothing is built when no utterance has one: the run is then the call without."""
+        texts, text_of, weight = {}, [], []
+        for i, u in enumerate(utts):
+            ids = u.get("assist_ids")
+            if ids is None:
+                text_of.append(-1)
+                weight.append(0.0)
+                continue
+            if u.get("assist_weight") is None:
+                raise Sbv2Error(f"utterance {i} carries assist_ids without an assist_weight")
+            ids = tuple(int(t) for t in np.asarray(ids).reshape(-1))
+            w = float(u["assist_weight"])
+            if not ids:
+                raise Sbv2Error(f"assist_ids of utterance {i} is empty")
+            if not 0.0 <= w <= 1.0:   # (a NaN fails both)
+                raise Sbv2Error(f"assist_weight of utterance {i} must be in [0, 1]: {w}")
+            if w == 0.0:
+                text_of.append(-1)
+                weight.append(0.0)
+                continue
+            text_of.append(texts.setdefault(ids, len(texts)))
+            weight.append(w)
+        if not texts:
+            return
+        self.assist_ids = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int64) for t in texts]))
+        self.assist_lens = np.array([len(t) for t in texts], np.int64)
+        self.assist_of = np.array(text_of, np.int32)
+        self.assist_w = np.array(weight, np.float64)
+        self.assist = _lib.Sbv2Assist(len(texts), self.assist_ids.ctypes.data_as(i64p), self.assist_lens.ctypes.data_as(i64p),
+                                      self.assist_of.ctypes.data_as(C.POINTER(C.c_int32)), self.assist_w.ctypes.data_as(C.POINTER(C.c_double)), 0)
 
 
 def synthesize_batch(session: Session, utts, sdp_ratio=0.0, length_scale=1.0, noise_scale=0.0, noise_scale_w=0.0, noise_seed=0,
@@ -1017,6 +1070,9 @@ class Pipeline:
     """New capability: bert::predict -> word2ph feature repeat (tts_util.rs:129-154) -> model::synthesize for a batch,
     device resident between the stages."""
 
+    #: the run entry points this pipeline calls (orchestrator.require_assist looks for the last one before it hands over an assisted request)
+    entry_points = ("sbv2_pipeline_run", "sbv2_pipeline_run_opts", "sbv2_pipeline_run_assist")
+
     def __init__(self, bert: Session, vits: Session):
         self.bert, self.vits = bert, vits
         self.h = C.c_void_p()
@@ -1030,11 +1086,14 @@ class Pipeline:
         b.w2p = np.ascontiguousarray(np.concatenate([np.asarray(u["word2ph"], np.int64) for u in utts]))
         b.lens = np.zeros(len(utts), np.int64)
         b.set_row_options(utts)   # keys sdp_ratio / length_scale / noise_scale / noise_scale_w / noise_seed / noise_index of an utterance win
+        b.set_assist(utts)        # keys assist_ids / assist_weight of an utterance: equal id sequences are one assist text of the run
         return b
 
     def run(self, b):
         tail = (b.ids.ctypes.data_as(i64p), b.s_lens.ctypes.data_as(i64p), b.w2p.ctypes.data_as(i64p), b.lens.ctypes.data_as(i64p))
-        if b.opts is not None:
+        if b.assist is not None:   # (only then: a run without an assist is the call it always was)
+            check(_lib.lib().sbv2_pipeline_run_assist(self.h, C.byref(b.c), C.byref(b.opts) if b.opts is not None else None, C.byref(b.assist), *tail))
+        elif b.opts is not None:
             check(_lib.lib().sbv2_pipeline_run_opts(self.h, C.byref(b.c), C.byref(b.opts), *tail))
         else:
             check(_lib.lib().sbv2_pipeline_run(self.h, C.byref(b.c), *tail))
@@ -1256,7 +1315,9 @@ class StreamHandle:
     utterance then runs as the request stream with gaps=[0] (the same code, the same bytes; fmt None = 44.1 kHz f32).
     pitch (a Pitch: hop, range, threshold at the stream's delivered rate; with or without levels): the pitch contour of the delivered samples is
     estimated on the device chunk by chunk as well (sbv2_stream_begin_request_pitch): n_pitch frames in all, next_pitch() hands out the ones the
-    pieces taken so far completed, with the bits of debug_pitch over the whole delivered signal."""
+    pieces taken so far completed, with the bits of debug_pitch over the whole delivered signal.
+    assist: an utterance of a LIST may carry assist_ids / assist_weight (sbv2_stream_begin_request_assist, as Pipeline.run takes them); a single
+    utterance dict that carries them is refused, gaps= named: a request of one row serves it."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
                  level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, track=None,
@@ -1290,7 +1351,19 @@ class StreamHandle:
             rq = _lib.Sbv2StreamRequest(gp, C.pointer(fmt.c) if fmt is not None else None, C.pointer(level.c) if level is not None else None,
                                         int(self.flac), 0)
             opts = C.byref(self.b.opts) if self.b.opts is not None else None
-            if pitch is not None:
+            if self.b.assist is not None:
+                # an assisted row: the one entry that takes it, with the levels and the pitch it may carry (NULL: without)
+                on = self.levels or self.env_hop
+                lv = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)) if on or pitch is not None else None
+                sp = None
+                if pitch is not None:
+                    sp = _lib.Sbv2StreamPitch(pitch.hop if -2 ** 31 <= pitch.hop < 2 ** 31 else 0, 0, pitch.f0_min, pitch.f0_max, pitch.threshold)
+                nt, ne, nq = C.c_int64(), C.c_int64(), C.c_int64()
+                check(l.sbv2_stream_begin_request_assist(args[0], args[1], args[2], opts, C.byref(self.b.assist), *args[3:], C.byref(rq),
+                                                         C.byref(lv) if lv is not None else None, C.byref(sp) if sp is not None else None,
+                                                         C.byref(self.h), C.byref(tot), C.byref(nt), C.byref(ne), C.byref(nq)))
+                self.n_tokens, self.n_env, self.n_pitch = nt.value, ne.value, nq.value
+            elif pitch is not None:
                 lv, nt, ne, nq = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)), C.c_int64(), C.c_int64(), C.c_int64()
                 sp = _lib.Sbv2StreamPitch(pitch.hop if -2 ** 31 <= pitch.hop < 2 ** 31 else 0, 0, pitch.f0_min, pitch.f0_max, pitch.threshold)
                 check(l.sbv2_stream_begin_request_pitch(args[0], args[1], args[2], opts, *args[3:], C.byref(rq), C.byref(lv), C.byref(sp),
@@ -1312,6 +1385,9 @@ class StreamHandle:
             return
         if gaps is not None:
             raise Sbv2Error("gaps= belongs to a stream over a list of utterances")
+        if self.b.assist is not None:
+            raise Sbv2Error("a single-utterance stream cannot carry an assist text: stream it as a request of one row, "
+                            "StreamHandle(bert, vits, [utt], gaps=[0])")
         if level is not None and fmt is None:
             raise Sbv2Error("a level stream needs a format: fmt=PcmFormat(rate, encoding), any encoding")
         if fmt is None:

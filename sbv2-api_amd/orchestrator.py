@@ -16,6 +16,7 @@ tests/test_gpu_parity.py), so the WAV is the same as the sequential loop's given
 The text front-end (G2P, tokenizer: tts_util.rs:14-155) is out of scope: callers pass per-sentence
 dicts {input_ids, word2ph, phones, tones, langs} exactly as parse_text produces them, or None for an empty line.
 """
+import copy
 import json
 import struct
 
@@ -72,13 +73,23 @@ class SynthesizeOptions:
     character of the speaker and leaves f0, the length and the token spans alone; it is made by the shifter of pitch_scale on the device
     (model.Formant: every grain is read at the scaled offset) and composes with pitch_scale, intonation_scale, pitch_track and token_pitch.
     The level drops somewhat (set loudness to restore it).  Whole-signal routes only, refused on streams.  The marks then carry
-    "formant_scale".  1.0 is the calls and the bytes there always were."""
+    "formant_scale".  1.0 is the calls and the bytes there always were.
+    assist (new; checked here) with assist_weight in [0, 1]: upstream Style-Bert-VITS2's assist_text / assist_text_weight.  assist is a second
+    text, parsed (a sentence dict, of which only input_ids is read) or as a list of token ids (a str is taken by a holder only, which parses it
+    with its parse_text); it goes through the same DeBERTa in the same
+    run, and the mean of its features is mixed into every token's feature of every sentence of the request, feature * (1 - w) + mean * w, on
+    the device (model._Batch.set_assist, sbv2_assist): it steers HOW the text is spoken (towards "I am so happy!") and leaves the style vector
+    alone.  0.7 is this layer's default, chosen to match upstream's.  It acts before the model, so every route takes it, streams included.
+    None, or a weight of 0, is the calls and the bytes there always were."""
 
     def __init__(self, sdp_ratio=0.0, length_scale=1.0, style_weight=1.0, split_sentences=True, sample_rate=SAMPLE_RATE, encoding="f32",
                  normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
                  pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False,
                  compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0, token_pitch=None, token_pitch_kind="hz",
-                 token_pitch_smooth=2, formant_scale=1.0):
+                 token_pitch_smooth=2, formant_scale=1.0, assist=None, assist_weight=0.7):
+        # (a str is a text still to be parsed: holder.TTSModelHolder does that with its parse_text; the routes below refuse it as it is)
+        self.assist_text = assist if isinstance(assist, str) and assist else None
+        self.assist_ids, self.assist_weight = check_assist(None if isinstance(assist, str) else assist, assist_weight)
         if isinstance(formant_scale, bool) or not isinstance(formant_scale, (int, float)) or not 0.5 <= formant_scale <= 2.0:   # (a NaN fails)
             raise model.Sbv2Error(f"formant_scale must be a number in [0.5, 2.0]: {formant_scale!r}")
         self.formant_scale = float(formant_scale)
@@ -116,6 +127,61 @@ class SynthesizeOptions:
         self.envelope_hz = envelope_hz
         self.gain_db = gain_db
         self.pitch_hz, self.pitch_min_hz, self.pitch_max_hz = pitch_hz, pitch_min_hz, pitch_max_hz
+
+
+def check_assist(assist, weight):
+    """(the assist text's token ids as a list of ints or None, the weight as a float) under the checks SynthesizeOptions states."""
+    if isinstance(weight, (bool, np.bool_)) or not isinstance(weight, (int, float, np.integer, np.floating)) or not 0.0 <= weight <= 1.0:   # (a NaN fails)
+        raise model.Sbv2Error(f"assist_weight must be a number in [0, 1]: {weight!r}")
+    if assist is None:
+        return None, float(weight)
+    ids = assist.get("input_ids") if isinstance(assist, dict) else assist
+    if ids is None or isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple, np.ndarray)):
+        raise model.Sbv2Error("assist must be a parsed sentence (a dict with input_ids) or a list of token ids")
+    out = []
+    for t, v in enumerate(np.asarray(ids, object).reshape(-1)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise model.Sbv2Error(f"assist token id {t} must be an integer >= 0: {v!r}")
+        out.append(int(v))
+    if not out:
+        raise model.Sbv2Error("assist holds no token ids")
+    return out, float(weight)
+
+
+def assist_options(options):
+    """(token ids, weight) of a request's assist text, or None without one or at a weight of 0: the request is then the call it always was."""
+    ids, w = getattr(options, "assist_ids", None), float(getattr(options, "assist_weight", 0.0))
+    if ids is None and getattr(options, "assist_text", None) is not None and w != 0.0:
+        raise model.Sbv2Error("the assist text is not parsed: a holder parses it with its parse_text (TTSModelHolder), or pass the parsed "
+                              "sentence or its token ids as assist")
+    return None if ids is None or w == 0.0 else (list(ids), w)
+
+
+def parsed_assist(options, parse_text):
+    """`options` with its assist text parsed by parse_text (a copy; `options` itself when there is nothing to parse or the weight is 0).  No
+    front end is a refusal, as for the spoken text."""
+    if getattr(options, "assist_text", None) is None or getattr(options, "assist_ids", None) is not None or options.assist_weight == 0.0:
+        return options
+    if parse_text is None:
+        raise model.Sbv2Error("no text front end configured (parse_text): pass the assist as a parsed sentence or token ids instead")
+    out = copy.copy(options)
+    out.assist_ids, _ = check_assist(parse_text(options.assist_text), options.assist_weight)
+    return out
+
+
+def with_assist(utts, options):
+    """The request's rows with its assist on every one of them (the keys model._Batch.set_assist reads); the rows as they are without one."""
+    a = assist_options(options)
+    return utts if a is None else [dict(u, assist_ids=a[0], assist_weight=a[1]) for u in utts]
+
+
+def require_assist(pipe, options):
+    """A request with an assist needs a pipeline that runs sbv2_pipeline_run_assist (it says so in `entry_points`, as model.Pipeline does): any
+    other is refused, not served unassisted."""
+    names = getattr(pipe, "entry_points", None)
+    if assist_options(options) is not None and not (isinstance(names, (tuple, list, set, frozenset)) and "sbv2_pipeline_run_assist" in names):
+        raise model.Sbv2Error(f"assist needs a pipeline that runs sbv2_pipeline_run_assist: {type(pipe).__name__} does not name it in its "
+                              "entry_points, and the request is not served unassisted")
 
 
 class TokenPitchError(model.Sbv2Error):
@@ -296,7 +362,7 @@ class RequestPlan:
         model.pcm_format_length(self.fmt, 0)   # a bad rate is refused before any GPU work
         self.options, self.n_lines = options, len(sentences)
         self.live = [i for i, _ in live]
-        self.utts = [dict(s, style=style, sid=speaker_id) for _, s in live]
+        self.utts = with_assist([dict(s, style=style, sid=speaker_id) for _, s in live], options)   # (the pair on every row of the request)
         self.token_pitch = token_pitch_options(options, self.utts)   # (a list of the wrong length is refused before any GPU work)
 
 
@@ -539,6 +605,7 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     refuse_pitch(options, "easy_synthesize (/synthesize)")
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
     require_formant(pipe, plan.options)   # (before any GPU work)
+    require_assist(pipe, plan.options)
     if noise_seed is None:      # the reference draws fresh noise per request; tests pass an explicit seed
         noise_seed = model.fresh_noise_seed()
     b = pipe.prepare(plan.utts, sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=noise_scale,
@@ -554,6 +621,7 @@ def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, styl
     options.envelope_hz a level envelope.  Levels are computed on the device from the delivered samples (also behind the FLAC sink)."""
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
     require_formant(pipe, plan.options)   # (before any GPU work)
+    require_assist(pipe, plan.options)
     envelope_hop(plan.options, plan.fmt.sample_rate)   # a bad envelope_hz is refused before any GPU work
     pitch_options(plan.options, plan.fmt.sample_rate)  # ... and so is a bad pitch_hz or range
     if noise_seed is None:
@@ -723,7 +791,9 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     which ignores envelope_hz).  On a level stream (gain_db) the levels are those of the samples the limiter emits.
     pitch=True (needs levels=True and options.pitch_hz; hop and range as pitch_options reads them): the pitch contour of the delivered samples
     is estimated on the device chunk by chunk as well (model.StreamHandle(pitch=...)): take_marks() pieces gain a "pitch" block, and once the
-    last piece is out `.marks` has marks_dict's "pitch" block and the tokens' f0_hz / voiced.  Without pitch=True, pitch_hz is refused."""
+    last piece is out `.marks` has marks_dict's "pitch" block and the tokens' f0_hz / voiced.  Without pitch=True, pitch_hz is refused.
+    options.assist: every row carries the assist (sbv2_stream_begin_request_assist); with split=False the utterance then runs as a request of
+    one row without a gap, the only stream kind that takes one."""
     options = options or SynthesizeOptions()
     refuse_voice(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_token_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
@@ -763,10 +833,14 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     if split:
         lines = [i for i, s in enumerate(sentences) if s]
         gaps = [SENTENCE_GAP if i != len(sentences) - 1 else 0 for i in lines]
-        st = model.StreamHandle(bert, vits, [dict(s, style=style, sid=speaker_id) for s in live], chunk_frames, gaps=gaps, **kw)
+        st = model.StreamHandle(bert, vits, with_assist([dict(s, style=style, sid=speaker_id) for s in live], options), chunk_frames, gaps=gaps, **kw)
     else:
         lines = [sentences.index(live[0])]
-        st = model.StreamHandle(bert, vits, dict(live[0], style=style, sid=speaker_id), chunk_frames, **kw)
+        if assist_options(options) is not None:
+            # the plain single-utterance entries take no assist: the same utterance as a request of one row without a gap (the same samples)
+            st = model.StreamHandle(bert, vits, with_assist([dict(live[0], style=style, sid=speaker_id)], options), chunk_frames, gaps=[0], **kw)
+        else:
+            st = model.StreamHandle(bert, vits, dict(live[0], style=style, sid=speaker_id), chunk_frames, **kw)
     try:
         marks = token_marks(live, lines, fmt.sample_rate, *st.marks())
     except BaseException:

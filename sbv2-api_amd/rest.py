@@ -54,6 +54,11 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     larger, darker speaker, above 1 a smaller, brighter one); made by the shifter of pitch_scale on the device, it composes with
                     pitch_scale, intonation_scale, pitch_track and token_pitch.  The marks of /synthesize_marks then carry "formant_scale".  The
                     stream routes answer 400 for a value other than 1.
+  assist_text = null (new; all four synthesis routes, streams included; assist_text_weight = 0.7): a second text ("I am so happy!") that steers
+                    HOW the text is spoken, upstream Style-Bert-VITS2's assist_text: it is parsed by the holder's parse_text, runs through the
+                    same DeBERTa in the same run, and the mean of its features is mixed into every token's feature with that weight in [0, 1] on
+                    the device.  A weight outside [0, 1] answers 500 on /synthesize and /synthesize_marks and 400 on the stream routes, before
+                    the holder is asked; null, "" or a weight of 0 is the request it always was.
   POST /synthesize_marks  new: the body of /synthesize plus envelope_hz = null -> application/json {"audio": base64 of the bytes /synthesize
                     answers with, "media_type", "sample_rate", "marks"}: when each phone id and word is spoken in that audio and how loud
                     (orchestrator.marks_dict; levels computed on the device), with envelope_hz a level envelope of sample_rate // envelope_hz
@@ -183,6 +188,8 @@ def make_app(holder, batching=None):
         token_pitch: Optional[List[float]] = None   # new: per token of the speech marks, 0 = not edited; /synthesize, /synthesize_marks; 400 on the stream routes
         token_pitch_kind: str = "hz"        # "hz": the token's target mean f0, [35, 1200]; "ratio": a factor on its f0, [0.5, 2]
         token_pitch_smooth: int = 2         # contour frames to each side over which the ratio changes, [0, 20]
+        assist_text: Optional[str] = None   # new: a second text whose DeBERTa features steer the delivery (upstream's assist_text); all four routes
+        assist_text_weight: float = 0.7     # its weight, [0, 1] (upstream's default); 0 = none
         formant_scale: float = 1.0          # new: moves the voice's formants, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); 400 on the stream routes
 
     class SynthesizeMarksRequest(SynthesizeRequest):
@@ -238,7 +245,9 @@ def make_app(holder, batching=None):
                                               **({"token_pitch": req.token_pitch, "token_pitch_kind": req.token_pitch_kind,
                                                   "token_pitch_smooth": req.token_pitch_smooth}
                                                  if getattr(req, "token_pitch", None) is not None else {}),
-                                              **({"formant_scale": req.formant_scale} if getattr(req, "formant_scale", 1.0) != 1.0 else {}))
+                                              **({"formant_scale": req.formant_scale} if getattr(req, "formant_scale", 1.0) != 1.0 else {}),
+                                              **({"assist": req.assist_text or None, "assist_weight": req.assist_text_weight}
+                                                 if getattr(req, "assist_text", None) or getattr(req, "assist_text_weight", 0.7) != 0.7 else {}))
 
     def bad_request(e):
         """400 for what the request itself is at fault for in token_pitch (a bad value, a count that does not match the text)."""
@@ -293,13 +302,14 @@ def make_app(holder, batching=None):
                            "words": [[w["line"], w["index"], w["start"], w["end"]] for w in marks["words"]]}, separators=(",", ":"))
 
     def refuse_stream_voice(req):
-        """A 400 for pitch_scale / intonation_scale / pitch_track / compressor on a stream route (the request is at fault, nothing was tried), None
-        at the defaults."""
+        """A 400 for pitch_scale / intonation_scale / pitch_track / compressor on a stream route, and for an assist_text_weight outside [0, 1] (the
+        request is at fault, nothing was tried), None at the defaults."""
         try:
             orchestrator.refuse_dynamics(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_voice(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            orchestrator.check_assist(None, getattr(req, "assist_text_weight", 0.7))   # (a stream takes an assist; a bad weight is the request's fault)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=400)
         return None
