@@ -1089,6 +1089,13 @@ int sbv2_debug_set_ksplit(int on);
    of 8), 4 at every length on the pipelined kernel's 8-wave shape (the batch shape, forced for the test), 0 never (converted per key tile inside the
    attention kernel); bit-identical; returns the previous setting */
 int sbv2_debug_set_flash_parts(int on);
+/* 0 (default): the stochastic duration predictor runs only for the rows of a call whose sdp_ratio is not exactly 0: not at all when there is none, on a
+   second text layout over those rows when there are some, on the text layout when all need it.  1: for every row of every call on the text layout, as the
+   exported graph does.  The two agree bit for bit in durations, logw (up to the sign of an exact zero at ratio 0) and PCM wherever the predictor's value is
+   finite (on the second layout the predictor's LayerNorm launches take the kernels the text layout's column count selects, so this holds whichever side of
+   the small-grid threshold of sbv2_debug_set_ksplit either layout falls on); the tests compare them in one process.  Process-wide, atomic; returns the
+   previous value. */
+int sbv2_debug_set_sdp_all(int on);
 /* Same contract as sbv2_debug_conv1d_cl (mode 1) through conv_clx.hip: x is split into bf16 parts of lrelu(x, pre_slope) first (split_cl), the
    convolution reads the parts; y = (conv + bias + res) * beta; ys_sum (optional) = hi + lo of the parts of lrelu(y, 0.1) the epilogue emits. */
 int sbv2_debug_conv1d_clx(int device, const float* x, const float* w, const float* bias, const float* res, int64_t cin, int64_t cout, int64_t k,

@@ -151,6 +151,8 @@ void linear_tokmajor(const PackedConv& w, Plane x, float* y, int ldy, hipStream_
 int default_bert_bfs_parts();
 bool flash_parts_enabled();   // vits.cpp: the flow's attention reads pre-split keys / values
 int set_flash_parts(int on);
+bool sdp_all();               // vits.cpp: every row goes through the stochastic duration predictor (sbv2_debug_set_sdp_all)
+int set_sdp_all(int on);      // returns the previous value
 
 // The VITS encoders' attention (vits.cpp; built here for run_encoder and sbv2_debug_vits_attention alike)
 constexpr int kTextGap = 16;   // >= 9: DDSConv depthwise dilation 3^2 with k=3
@@ -439,7 +441,7 @@ class VitsModel {
     Encoder load_encoder(const std::string& prefix, int n_layers);
     DDS load_dds(const std::string& prefix, int channels);
     void run_encoder(const Encoder& e, Plane x, const SegLayout& lay, const float* spk_vec, Arena& ar);
-    void run_dds(const DDS& d, Plane x, const SegLayout& lay, Arena& ar);
+    void run_dds(const DDS& d, Plane x, const SegLayout& lay, Arena& ar, int shape_L = 0);
     void run_decoder(Arena& ar, Plane z, const SegLayout& fl, const float* cond_vec);
     // channels-last bf16 / split-bf16 MFMA decoder (decoder_cl.cpp)
     struct ClUpGroup {

@@ -20,11 +20,12 @@ void deberta_embed_ln(const int* ids, const float* emb, int H, const float* gamm
                       Plane out, hipStream_t s);
 // out = mask * ( act(LN_c(in)) + res )   (act: ACT_NONE / ACT_GELU; res optional; in == out allowed)
 // split != null: the result is also written as bf16 parts (the operand format of gemm_bfs.hip)
+// shape_L > 0: the kernel is chosen as for a plane of shape_L columns (the choice fixes the order of the per-column sums, i.e. the f32 rounding)
 void layernorm_ch(Plane in, Plane out, const float* gamma, const float* beta, float eps, int act, const float* res,
-                  int ldr, const unsigned char* mask, hipStream_t s, const SplitPlanes* split = nullptr);
+                  int ldr, const unsigned char* mask, hipStream_t s, const SplitPlanes* split = nullptr, int shape_L = 0);
 // out = mask * gelu(LN_c(depthwise_conv_k3(in, dilation) + b))
 void dds_dw_ln_gelu(Plane in, Plane out, const float* w, const float* b, int dil, const float* gamma,
-                    const float* beta, const unsigned char* mask, hipStream_t s);
+                    const float* beta, const unsigned char* mask, hipStream_t s, int shape_L = 0);
 
 // fused disentangled attention for short sequences (attn_deberta.hip); deberta_attention_fits says whether a batch qualifies
 bool deberta_attention_fits(int maxT, int wlen, int dh);
@@ -57,7 +58,7 @@ void vits_relv_add(const AttnGroup* groups, int ngroups, int maxT, float* ctx, i
                    int window, const float* pwin, hipStream_t s);
 
 void add_segvec(Plane x, const float* vec, int vec_ld, const int* seg_of, int div, const unsigned char* mask,
-                hipStream_t s);
+                hipStream_t s, const Plane* src = nullptr);   // x = (src ? *src : x) + vec of the column's segment, 0 outside the mask
 void linear_vec(const float* W, const float* bias, int M, int K, const float* v, int ldv, float* out, int ldo, int B,
                 hipStream_t s);
 void gather_rows(const float* table, int K, const int* idx, float* out, int B, hipStream_t s);
@@ -81,8 +82,10 @@ struct RowOpts {
     int pad_;
 };
 static_assert(sizeof(RowOpts) == 32, "RowOpts is one 32-byte record");
+// sdp: the stochastic predictor's plane, or null when no row of the batch uses it; sdp_col (may be null: column n of sdp is column n): the column of sdp
+// that holds column n's value, -1 where it has none (a row whose sdp_ratio is 0 when only some rows went through the predictor).
 void durations(const float* sdp, const float* dp, const int* seg_of, const RowOpts* rows, const unsigned char* mask, int L,
-               float* logw, int* dur, hipStream_t s);
+               float* logw, int* dur, hipStream_t s, const int* sdp_col = nullptr);
 void noise_fill(float* out, int ld, int rows, const int* seg_of, const int* seg_start, const int* seg_len, const RowOpts* opts, int L,
                 int stream_id, hipStream_t s);   // scaled by the row's noise_scale_w
 void expand_frames(Plane m_p, Plane logs_p, const int* tok_of_frame, const int* seg_of, const int* seg_start,
@@ -109,7 +112,7 @@ void copy_segments(const float* src, float* dst, const int64_t* d_table, int n, 
 void conv_post_tanh(Plane x, const float* w, int k, float slope, const int* seg_start, const int* seg_len,
                     const int64_t* pcm_off, int nseg, int up, int64_t max_samples, float* pcm, hipStream_t s);
 void transpose_out(Plane in, int col0, int T, float* out, hipStream_t s);  // out[t][c] = in[c][col0+t]
-void gather_cols(Plane in, const int* map, Plane out, hipStream_t s);       // out[c][n] = map[n]>=0 ? in[c][map[n]] : 0
+void gather_cols(Plane in, const int* map, Plane out, hipStream_t s, const float* fill = nullptr);   // out[c][n] = map[n]>=0 ? in[c][map[n]] : fill ? 0 + fill[c] : 0
 // Assist text (assist.hip; the contract above sbv2_assist, include/sbv2_hip.h).  One record per row of the batch, [n] on the device: the row of
 // `mean` blended into the row's columns (-1: none, the plain gather) and the two f32 weights wf = float(w), omw = float(1.0 - w).
 struct AssistRow {

@@ -281,17 +281,22 @@ __global__ __launch_bounds__(256) void k_layernorm_q4(Plane in, Plane out, const
 
 template <bool DW>
 static void launch_layernorm(Plane in, Plane out, const float* gamma, const float* beta, float eps, int act, const float* res, int ldr,
-                             const unsigned char* mask, const float* w, const float* b, int dil, hipStream_t s, SplitPlanes sp = SplitPlanes{}) {
+                             const unsigned char* mask, const float* w, const float* b, int dil, hipStream_t s, SplitPlanes sp = SplitPlanes{},
+                             int shape_L = 0) {
     SBV2_REQUIRE(!sp.parts || (sp.C == out.C && sp.ld >= out.L), "layernorm: split output shape");
     const dim3 block(256);
+    // The kernels below group the per-column sums differently (f32 rounding apart), and which one runs depends on the column count.  shape_L > 0: choose
+    // as for a plane of that many columns, so that a plane holding some of a batch's rows gets, per column, the bits the whole batch's plane gets (the
+    // stochastic duration predictor's sub-layout, vits.cpp).  Grids still follow the plane's own width.
+    const int Ls = shape_L > 0 ? shape_L : in.L;
     // A single utterance (66 tokens x 1024 channels, 897 frames or 257 symbols x 192): few columns per workgroup and few channels per thread, i.e. more
     // workgroups and a shorter chain of dependent loads per thread (12.4 -> ~7 us and 7.8 -> ~5 us per launch, 129 launches per call).  Another grouping of the
     // per-column sums than the batch's launch shape: f32-rounding apart from it, so it belongs to the small-grid dispatch that sbv2_debug_set_ksplit(0) turns off.
-    if (ksplit_enabled() && in.C >= 512 && in.C <= 8 * 128 && in.L <= 256) {
+    if (ksplit_enabled() && in.C >= 512 && in.C <= 8 * 128 && Ls <= 256) {
         hipLaunchKernelGGL((k_layernorm_ch<DW, 8, 2>), dim3((in.L + 1) / 2), block, 0, s, in, out, gamma, beta, eps, act, res, ldr, mask, w, b, dil, sp);
         return;
     }
-    if (ksplit_enabled() && in.C < 512 && in.C <= 6 * 32 && in.L <= 1024) {
+    if (ksplit_enabled() && in.C < 512 && in.C <= 6 * 32 && Ls <= 1024) {
         hipLaunchKernelGGL((k_layernorm_ch<DW, 6, 8>), dim3((in.L + 7) / 8), block, 0, s, in, out, gamma, beta, eps, act, res, ldr, mask, w, b, dil, sp);
         return;
     }
@@ -307,7 +312,7 @@ static void launch_layernorm(Plane in, Plane out, const float* gamma, const floa
         }
     }
     // few, wide columns (DeBERTa: 1024 channels x ~2k tokens): 8 columns x 32 channel groups per workgroup, or the grid is 64 workgroups
-    if (!DW && in.C >= 512 && in.L <= 8192 && in.C <= 32 * 32) {
+    if (!DW && in.C >= 512 && Ls <= 8192 && in.C <= 32 * 32) {
         hipLaunchKernelGGL((k_layernorm_ch<DW, 32, 8>), dim3((in.L + 7) / 8), block, 0, s, in, out, gamma, beta, eps, act, res, ldr, mask, w, b, dil, sp);
         return;
     }
@@ -320,13 +325,13 @@ static void launch_layernorm(Plane in, Plane out, const float* gamma, const floa
     else hipLaunchKernelGGL((k_layernorm_ch<DW, 0, 32>), grid, block, 0, s, in, out, gamma, beta, eps, act, res, ldr, mask, w, b, dil, sp);
 }
 void layernorm_ch(Plane in, Plane out, const float* gamma, const float* beta, float eps, int act, const float* res, int ldr,
-                  const unsigned char* mask, hipStream_t s, const SplitPlanes* split) {
-    launch_layernorm<false>(in, out, gamma, beta, eps, act, res, ldr, mask, nullptr, nullptr, 1, s, split ? *split : SplitPlanes{});
+                  const unsigned char* mask, hipStream_t s, const SplitPlanes* split, int shape_L) {
+    launch_layernorm<false>(in, out, gamma, beta, eps, act, res, ldr, mask, nullptr, nullptr, 1, s, split ? *split : SplitPlanes{}, shape_L);
 }
 void dds_dw_ln_gelu(Plane in, Plane out, const float* w, const float* b, int dil, const float* gamma, const float* beta,
-                    const unsigned char* mask, hipStream_t s) {
+                    const unsigned char* mask, hipStream_t s, int shape_L) {
     SBV2_REQUIRE(in.p != out.p, "depthwise conv cannot run in place");
-    launch_layernorm<true>(in, out, gamma, beta, 1e-5f, (int)ACT_GELU, nullptr, 0, mask, w, b, dil, s);
+    launch_layernorm<true>(in, out, gamma, beta, 1e-5f, (int)ACT_GELU, nullptr, 0, mask, w, b, dil, s, SplitPlanes{}, shape_L);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -549,18 +554,20 @@ void vits_relv_add(const AttnGroup* groups, int ngroups, int maxT, float* ctx, i
 // ------------------------------------------------------------------------------------------------
 // small per-utterance vector ops
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_add_segvec(Plane x, const float* vec, int vec_ld, const int* seg_of, int div,
+// (src, src_ld: the plane the sum starts from; x's own for the in-place form)
+__global__ __launch_bounds__(256) void k_add_segvec(Plane x, const float* src, int src_ld, const float* vec, int vec_ld, const int* seg_of, int div,
                                                      const unsigned char* mask) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     const int c = blockIdx.y;
     if (n >= x.L) return;
     const int q = n / div;
     const int sg = seg_of[q];
-    float* p = x.p + (size_t)c * x.ld + n;
-    *p = (sg >= 0 && (!mask || mask[q])) ? *p + vec[(size_t)sg * vec_ld + c] : 0.f;
+    x.p[(size_t)c * x.ld + n] = (sg >= 0 && (!mask || mask[q])) ? src[(size_t)c * src_ld + n] + vec[(size_t)sg * vec_ld + c] : 0.f;
 }
-void add_segvec(Plane x, const float* vec, int vec_ld, const int* seg_of, int div, const unsigned char* mask, hipStream_t s) {
-    hipLaunchKernelGGL(k_add_segvec, dim3((x.L + 255) / 256, x.C), dim3(256), 0, s, x, vec, vec_ld, seg_of, div, mask);
+void add_segvec(Plane x, const float* vec, int vec_ld, const int* seg_of, int div, const unsigned char* mask, hipStream_t s, const Plane* src) {
+    SBV2_REQUIRE(!src || (src->C >= x.C && src->L >= x.L), "add_segvec: source plane smaller than the destination");
+    hipLaunchKernelGGL(k_add_segvec, dim3((x.L + 255) / 256, x.C), dim3(256), 0, s, x, src ? src->p : x.p, src ? src->ld : x.ld, vec, vec_ld, seg_of, div,
+                       mask);
 }
 
 __global__ __launch_bounds__(256) void k_linear_vec(const float* W, const float* bias, int M, int K, const float* v, int ldv,
@@ -740,7 +747,14 @@ void affine_reverse(float* z0, float* z1, const float* m, const float* logs, con
 
 // w_ceil = ceil(exp(logw) * mask * length_scale)   (SynthesizerTrn.infer), with the sdp / dp mix and the length scale of the column's own row:
 // rows[seg_of[n]], read once per thread.  A wave's columns lie in one segment unless it straddles a gap, so the address is wave-uniform.
-__global__ void k_durations(const float* sdp, const float* dp, const int* seg_of, const RowOpts* rows, const unsigned char* mask, int L,
+// The stochastic predictor runs only for rows whose sdp_ratio is not 0 (VitsModel::forward): sdp is null when no row used it, and sdp_col (when given)
+// names the column of sdp that holds column n's value, -1 for none.  A column without a value takes s = 0.0f in the SAME expression, s * ratio +
+// dp * (1 - ratio), so fma contraction cannot differ between the two cases.  Against the predictor's value v multiplied by ratio == 0:
+//   - v finite: v * 0 is +-0 and dp * 1 is dp, so logw and dur are the same, except that dp == -0.0f gives logw +0.0f where v < 0 gave -0.0f
+//     (the one representable difference: the sign of an exact zero of logw; exp of either is 1, so dur cannot change);
+//   - v not finite: v * 0 was NaN and poisoned the row's logw and dur; it is now ignored.  Deliberate: a row that does not use the predictor does not
+//     depend on it.
+__global__ void k_durations(const float* sdp, const int* sdp_col, const float* dp, const int* seg_of, const RowOpts* rows, const unsigned char* mask, int L,
                             float* logw, int* dur) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= L) return;
@@ -752,13 +766,15 @@ __global__ void k_durations(const float* sdp, const float* dp, const int* seg_of
     }
     const RowOpts o = rows[sg];   // the record, once
     const float ratio = o.sdp_ratio, length_scale = o.length_scale;
-    const float lw = sdp[n] * ratio + dp[n] * (1.0f - ratio);
+    const int q = !sdp ? -1 : sdp_col ? sdp_col[n] : n;
+    const float s = q >= 0 ? sdp[q] : 0.0f;
+    const float lw = s * ratio + dp[n] * (1.0f - ratio);
     logw[n] = lw;
     dur[n] = (int)ceilf(expf(lw) * length_scale);
 }
 void durations(const float* sdp, const float* dp, const int* seg_of, const RowOpts* rows, const unsigned char* mask, int L, float* logw,
-               int* dur, hipStream_t s) {
-    hipLaunchKernelGGL(k_durations, dim3((L + 255) / 256), dim3(256), 0, s, sdp, dp, seg_of, rows, mask, L, logw, dur);
+               int* dur, hipStream_t s, const int* sdp_col) {
+    hipLaunchKernelGGL(k_durations, dim3((L + 255) / 256), dim3(256), 0, s, sdp, sdp_col, dp, seg_of, rows, mask, L, logw, dur);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -884,15 +900,17 @@ void transpose_out(Plane in, int col0, int T, float* out, hipStream_t s) {
     hipLaunchKernelGGL(k_transpose_out, dim3((T + 31) / 32, (in.C + 31) / 32), dim3(256), 0, s, in, col0, T, out);
 }
 
-__global__ void k_gather_cols(Plane in, const int* map, Plane out) {
+// fill (may be null): row c of a column with no source holds 0.f + fill[c], what a biased 1x1 product gives an all-zero column (its accumulator is +0 there),
+// so a product taken BEFORE the gather leaves the plane the product AFTER the gather left.
+__global__ void k_gather_cols(Plane in, const int* map, Plane out, const float* fill) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     const int c = blockIdx.y;
     if (n >= out.L) return;
     const int q = map[n];
-    out.p[(size_t)c * out.ld + n] = q >= 0 ? in.p[(size_t)c * in.ld + q] : 0.f;
+    out.p[(size_t)c * out.ld + n] = q >= 0 ? in.p[(size_t)c * in.ld + q] : fill ? 0.f + fill[c] : 0.f;
 }
-void gather_cols(Plane in, const int* map, Plane out, hipStream_t s) {
-    hipLaunchKernelGGL(k_gather_cols, dim3((out.L + 255) / 256, out.C), dim3(256), 0, s, in, map, out);
+void gather_cols(Plane in, const int* map, Plane out, hipStream_t s, const float* fill) {
+    hipLaunchKernelGGL(k_gather_cols, dim3((out.L + 255) / 256, out.C), dim3(256), 0, s, in, map, out, fill);
 }
 
 __global__ void k_add_segvec_cl(float* x, int L, int C, const float* vec, int vec_ld, const int* seg_of, const unsigned char* mask) {

@@ -24,6 +24,12 @@ bool flash_parts_enabled() { return g_flash_parts.load(std::memory_order_relaxed
 static int flash_parts_mode() { return g_flash_parts.load(std::memory_order_relaxed); }
 int set_flash_parts(int on) { return g_flash_parts.exchange(on); }
 
+// sbv2_debug_set_sdp_all: 1 = every row of every call goes through the stochastic duration predictor on the full text layout, whatever its sdp_ratio
+// (what the exported graph does); 0 (default) = only the rows whose ratio is not 0 (VitsModel::forward).  For tests and same-process A/B.
+static std::atomic<int> g_sdp_all{0};
+bool sdp_all() { return g_sdp_all.load(std::memory_order_relaxed) != 0; }
+int set_sdp_all(int on) { return g_sdp_all.exchange(on != 0); }
+
 AttnPlan make_attn_plan(const SegLayout& lay, int H, int heads, int ld, int window, Arena& ar, hipStream_t stream, bool scores) {
     AttnPlan pl;
     const int dk = H / heads;
@@ -504,14 +510,15 @@ void VitsModel::run_encoder(const Encoder& e, Plane x, const SegLayout& lay, con
 }
 
 // modules.DDSConv: x += gelu(LN(1x1(gelu(LN(depthwise(x * mask))))))  x 3, dilation 3^i
-void VitsModel::run_dds(const DDS& d, Plane x, const SegLayout& lay, Arena& ar) {
+// (shape_L: the column count the LayerNorm kernels are chosen for, see layernorm_ch; 0 = the plane's own)
+void VitsModel::run_dds(const DDS& d, Plane x, const SegLayout& lay, Arena& ar, int shape_L) {
     const Arena::Mark mk = ar.mark();
     Plane a = ar.plane(x.C, x.L), b = ar.plane(x.C, x.L);
     int dil = 1;
     for (size_t i = 0; i < d.pw.size(); ++i) {
-        dds_dw_ln_gelu(x, a, d.sep_w[i], d.sep_b[i], dil, d.n1g[i], d.n1b[i], lay.d_mask, stream_);
+        dds_dw_ln_gelu(x, a, d.sep_w[i], d.sep_b[i], dil, d.n1g[i], d.n1b[i], lay.d_mask, stream_, shape_L);
         conv_plain(d.pw[i], a, b, 1, 0, nullptr, 1, stream_);
-        layernorm_ch(b, x, d.n2g[i], d.n2b[i], 1e-5f, ACT_GELU, x.p, x.ld, lay.d_mask, stream_);
+        layernorm_ch(b, x, d.n2g[i], d.n2b[i], 1e-5f, ACT_GELU, x.p, x.ld, lay.d_mask, stream_, nullptr, shape_L);
         dil *= cfg_.sdp_kernel;
     }
     ar.rewind(mk);
@@ -644,29 +651,71 @@ void VitsModel::forward(const VitsBatch& b) {
     int* d_sid = ar.array<int>(n);
     RowOpts* d_rows = ar.array<RowOpts>(n);   // every row's options and noise key (seed, index of the utterance in the caller's batch)
     float* d_style = ar.array<float>((size_t)n * cfg_.style_dim);
+    std::vector<RowOpts> rows(n);
+    for (int u = 0; u < n; ++u) {
+        RowOpts& r = rows[u];
+        r.seed = b.row_seed ? b.row_seed[u] : b.seed;
+        r.index = b.row_index ? (int)b.row_index[u] : b.utt_ids ? (int)b.utt_ids[u] : b.utt0 + u;
+        r.sdp_ratio = b.row_sdp_ratio ? b.row_sdp_ratio[u] : b.sdp_ratio;
+        r.length_scale = b.row_length_scale ? b.row_length_scale[u] : b.length_scale;
+        r.noise_scale = b.row_noise_scale ? b.row_noise_scale[u] : b.noise_scale;
+        r.noise_scale_w = b.row_noise_scale_w ? b.row_noise_scale_w[u] : b.noise_scale_w;
+        r.pad_ = 0;
+    }
+    // The stochastic duration predictor's only consumer is k_durations, which multiplies its value by the row's sdp_ratio: a row needs it iff that
+    // ratio is not exactly 0 (a denormal ratio counts as needing it).  Decided here, on the host, before anything is enqueued: no row -> the
+    // predictor is not run at all; every row -> it runs on the text layout; some rows -> it runs on a second text layout over those rows only, in
+    // batch order (sl), fed by gathers, and k_durations reads its plane through a column map.  (sbv2_debug_set_sdp_all(1): every row, always.)
+    std::vector<int> sdp_rows;   // the batch rows that go through the predictor
+    for (int u = 0; u < n; ++u)
+        if (rows[u].sdp_ratio != 0.0f || sdp_all()) sdp_rows.push_back(u);
+    const int n_sdp = (int)sdp_rows.size();
+    const bool sdp_sub = n_sdp > 0 && n_sdp < n;
+    SegLayout sl;                  // the sub-layout (sdp_sub only)
+    RowOpts* d_sub_rows = nullptr; // its rows' options, compacted: noise_fill keys by (seed, index, position within the segment), so a row draws its own noise
+    int* d_sub_idx = nullptr;      // [n_sdp] batch row of each of its rows
+    int* d_sub_src = nullptr;      // [sl.L] column of tl behind each of its columns, -1 in its gaps
+    int* d_sdp_col = nullptr;      // [Lt] its column for each column of tl, -1 for none
     {
-        // six neighbours in the arena, uploaded in allocation order: one copy (Arena::begin_uploads)
+        // six neighbours in the arena, uploaded in allocation order: one copy (Arena::begin_uploads); the sub-layout's tables ride along
         UploadBatch ub(ar);
-        std::vector<RowOpts> rows(n);
-        for (int u = 0; u < n; ++u) {
-            RowOpts& r = rows[u];
-            r.seed = b.row_seed ? b.row_seed[u] : b.seed;
-            r.index = b.row_index ? (int)b.row_index[u] : b.utt_ids ? (int)b.utt_ids[u] : b.utt0 + u;
-            r.sdp_ratio = b.row_sdp_ratio ? b.row_sdp_ratio[u] : b.sdp_ratio;
-            r.length_scale = b.row_length_scale ? b.row_length_scale[u] : b.length_scale;
-            r.noise_scale = b.row_noise_scale ? b.row_noise_scale[u] : b.noise_scale;
-            r.noise_scale_w = b.row_noise_scale_w ? b.row_noise_scale_w[u] : b.noise_scale_w;
-            r.pad_ = 0;
-        }
         ar.upload(d_ph, ph.data(), sizeof(int) * Lt, stream_);
         ar.upload(d_tn, tn.data(), sizeof(int) * Lt, stream_);
         ar.upload(d_lg, lg.data(), sizeof(int) * Lt, stream_);
         ar.upload(d_sid, sid.data(), sizeof(int) * n, stream_);
         ar.upload(d_rows, rows.data(), sizeof(RowOpts) * n, stream_);
         ar.upload(d_style, b.styles, sizeof(float) * (size_t)n * cfg_.style_dim, stream_);
+        if (sdp_sub) {
+            std::vector<int> T_sub(n_sdp);
+            std::vector<RowOpts> sub_rows(n_sdp);
+            for (int j = 0; j < n_sdp; ++j) {
+                T_sub[j] = T[sdp_rows[j]];
+                sub_rows[j] = rows[sdp_rows[j]];
+            }
+            sl = make_layout(T_sub, kTextGap, ar, stream_);
+            std::vector<int> src(sl.L, -1), col(Lt, -1);
+            for (int j = 0; j < n_sdp; ++j)
+                for (int t = 0; t < T_sub[j]; ++t) {
+                    src[sl.start[j] + t] = tl.start[sdp_rows[j]] + t;
+                    col[tl.start[sdp_rows[j]] + t] = sl.start[j] + t;
+                }
+            d_sub_rows = ar.array<RowOpts>(n_sdp);
+            d_sub_idx = ar.array<int>(n_sdp);
+            d_sub_src = ar.array<int>(sl.L);
+            d_sdp_col = ar.array<int>(Lt);
+            ar.upload(d_sub_rows, sub_rows.data(), sizeof(RowOpts) * n_sdp, stream_);
+            ar.upload(d_sub_idx, sdp_rows.data(), sizeof(int) * n_sdp, stream_);
+            ar.upload(d_sub_src, src.data(), sizeof(int) * sl.L, stream_);
+            ar.upload(d_sdp_col, col.data(), sizeof(int) * Lt, stream_);
+        }
     }
 
-    Plane bert = ar.plane(cfg_.bert_dim, Lt);
+    // Device-resident features without an assist text: bert_proj is a 1x1 product, so it commutes with the word2ph column gather.  It runs over
+    // DeBERTa's own token columns and the gather then moves H rows; the [bert_dim x Lt] plane is never built (see the TextEncoder block).
+    const bool proj_first = !b.bert_host && b.bert_dev && b.assist_n == 0;
+    Plane bert = proj_first ? Plane() : ar.plane(cfg_.bert_dim, Lt);
+    Plane BP = ar.plane(H, Lt);   // bert_proj's output on the text layout
+    int* d_map = nullptr;         // [Lt] DeBERTa's column behind each text column, -1 for none (device-resident features)
     if (b.bert_host) {
         fill_zero(bert.p, sizeof(float) * (size_t)bert.C * bert.ld, stream_);
         HIP_CHECK(hipStreamSynchronize(stream_));
@@ -681,8 +730,11 @@ void VitsModel::forward(const VitsBatch& b) {
         std::vector<int> map(Lt, -1);
         int64_t e = 0;
         for (int u = 0; u < n; ++u)
-            for (int t = 0; t < T[u]; ++t, ++e) map[tl.start[u] + t] = b.bert_map[e];
-        int* d_map = ar.array<int>(Lt);
+            for (int t = 0; t < T[u]; ++t, ++e) {
+                SBV2_REQUIRE(b.bert_map[e] < b.bert_dev->L, "internal: feature map outside the feature plane");
+                map[tl.start[u] + t] = b.bert_map[e];
+            }
+        d_map = ar.array<int>(Lt);
         ar.upload(d_map, map.data(), sizeof(int) * Lt, stream_);
         if (b.assist_n > 0) {
             // assist text: every sequence's mean over its own columns, then the gather with the rows' blends (assist.hip)
@@ -701,8 +753,6 @@ void VitsModel::forward(const VitsBatch& b) {
             ar.upload(d_ar, b.assist_rows, sizeof(AssistRow) * n, stream_);
             assist_mean(*b.bert_dev, d_as, d_al, A, d_mean, stream_);
             gather_cols_assist(*b.bert_dev, d_map, tl.d_seg_of, d_ar, d_mean, bert, stream_);
-        } else {
-            gather_cols(*b.bert_dev, d_map, bert, stream_);
         }
     }
 
@@ -718,15 +768,28 @@ void VitsModel::forward(const VitsBatch& b) {
     linear_vec(style_w_, style_b_, H, cfg_.style_dim, d_style, cfg_.style_dim, v_style, H, n, stream_);
     float* v_encp = gvec(enc_p_.spk_w, enc_p_.spk_b, H);
     float* v_dp = gvec(dp_cond_w_, dp_cond_b_, H);
-    float* v_sdp = gvec(sdp_cond_w_, sdp_cond_b_, H);
+    float* v_sdp = n_sdp > 0 ? gvec(sdp_cond_w_, sdp_cond_b_, H) : nullptr;
+    if (sdp_sub) {   // the sub-layout's segments are numbered 0 .. n_sdp - 1: its rows' vectors, compacted
+        float* v_sub = ar.array<float>((size_t)n_sdp * H);
+        gather_rows(v_sdp, H, d_sub_idx, v_sub, n_sdp, stream_);
+        v_sdp = v_sub;
+    }
     dec_cond_vec_ = gvec(dec_cond_w_, dec_cond_b_, cfg_.up_initial);
     std::vector<float*> v_flow;
     for (auto& c : flows_) v_flow.push_back(gvec(c.enc.spk_w, c.enc.spk_b, H));
 
     // ---- TextEncoder ----------------------------------------------------------------------------------
     std::unique_ptr<TraceRange> tr(new TraceRange("text_encoder"));
-    Plane BP = ar.plane(H, Lt);
-    conv_plain(bert_proj_, bert, BP, 1, 0, nullptr, 1, stream_);
+    if (proj_first) {
+        // Same bits as gather-then-project: the exact-f32 product is one fma chain per column whatever the launch shape, the bias is per row, and
+        // a column with no source gets 0 + bias, what the product gave the gather's zero column.
+        SBV2_REQUIRE(b.bert_dev->C >= cfg_.bert_dim, "internal: feature plane narrower than bert_dim");
+        Plane P = ar.plane(H, b.bert_dev->L);
+        conv_plain(bert_proj_, b.bert_dev->rows(0, cfg_.bert_dim), P, 1, 0, nullptr, 1, stream_);
+        gather_cols(P, d_map, BP, stream_, bert_proj_.bias);
+    } else {
+        conv_plain(bert_proj_, bert, BP, 1, 0, nullptr, 1, stream_);
+    }
     Plane X = ar.plane(H, Lt);
     text_embed(d_ph, d_tn, d_lg, tl.d_seg_of, emb_, tone_emb_, lang_emb_, BP.p, BP.ld, v_style, H, std::sqrt((float)H), X, stream_);
     trace("x_emb", X, tl);
@@ -741,8 +804,7 @@ void VitsModel::forward(const VitsBatch& b) {
     tr.reset();
     tr.reset(new TraceRange("durations"));
     Plane XD = ar.plane(H, Lt);
-    HIP_CHECK(hipMemcpyAsync(XD.p, X.p, sizeof(float) * (size_t)H * X.ld, hipMemcpyDeviceToDevice, stream_));
-    add_segvec(XD, v_dp, H, tl.d_seg_of, 1, tl.d_mask, stream_);
+    add_segvec(XD, v_dp, H, tl.d_seg_of, 1, tl.d_mask, stream_, &X);   // XD = X + v_dp, out of place: no copy of X first
     Plane D1 = ar.plane(cfg_.dp_filter, Lt), D2 = ar.plane(cfg_.dp_filter, Lt), DPO = ar.plane(1, Lt);
     conv_plain(dp_c1_, XD, D1, 1, cfg_.dp_kernel / 2, tl.d_mask, 1, stream_, ACT_RELU);
     layernorm_ch(D1, D1, dp_n1g_, dp_n1b_, 1e-5f, ACT_NONE, nullptr, 0, tl.d_mask, stream_);
@@ -750,32 +812,46 @@ void VitsModel::forward(const VitsBatch& b) {
     layernorm_ch(D2, D2, dp_n2g_, dp_n2b_, 1e-5f, ACT_NONE, nullptr, 0, tl.d_mask, stream_);
     conv_plain(dp_proj_, D2, DPO, 1, 0, tl.d_mask, 1, stream_);
 
-    // ---- StochasticDurationPredictor, reverse (executed even when sdp_ratio == 0, like the exported graph) ----
-    Plane XSd = ar.plane(H, Lt), COND = ar.plane(H, Lt), HH = ar.plane(H, Lt);
-    Plane PR = ar.plane(3 * cfg_.sdp_bins - 1, Lt), Z = ar.plane(2, Lt);
-    conv_plain(sdp_pre_, X, XSd, 1, 0, nullptr, 1, stream_);
-    add_segvec(XSd, v_sdp, H, tl.d_seg_of, 1, tl.d_mask, stream_);
-    run_dds(sdp_dds_, XSd, tl, ar);
-    conv_plain(sdp_proj_, XSd, COND, 1, 0, tl.d_mask, 1, stream_);
-    float* z0 = Z.p;
-    float* z1 = Z.p + Z.ld;
-    noise_fill(Z.p, Z.ld, 2, tl.d_seg_of, tl.d_start, tl.d_len, d_rows, Lt, 0, stream_);
-    const float inv_sqrt_f = 1.0f / std::sqrt((float)H);
-    for (int i = (int)sdp_cf_.size() - 1; i >= 0; --i) {
-        const ConvFlow& cf = sdp_cf_[i];
-        swap_rows(z0, z1, Lt, stream_);  // Flip
-        convflow_pre(z0, cf.pre_w, cf.pre_b, COND, HH, tl.d_mask, stream_);
-        run_dds(cf.dds, HH, tl, ar);
-        conv_plain(cf.proj, HH, PR, 1, 0, tl.d_mask, 1, stream_);
-        spline_inverse(PR, z0, z1, cfg_.sdp_bins, cfg_.sdp_tail, inv_sqrt_f, tl.d_mask, Lt, stream_);
+    // ---- StochasticDurationPredictor, reverse: only for the rows whose sdp_ratio is not 0 (decided above).  The exported graph runs it for every row
+    // and multiplies by the ratio; no row at a non-zero ratio is the default of every server path, and then nothing of it is launched or allocated. ----
+    // Every kernel of the chain is column-local or segment-local (the exact-f32 products are one fma chain per column whatever the launch shape,
+    // the depthwise convolutions see their own segment and the zero gap), so a row gets the same bits on sl as on tl.  LayerNorm is per column too, but
+    // its kernels differ in the order of the per-column sums and are chosen by column count: on sl they are chosen for Lt columns, as on tl.
+    float* z0 = nullptr;   // the predictor's output row, on sl when sdp_sub, else on tl; null: no row uses it
+    if (n_sdp > 0) {
+        const SegLayout& pl = sdp_sub ? sl : tl;
+        const int Lp = pl.L;
+        Plane XS = X;
+        if (sdp_sub) {
+            XS = ar.plane(H, Lp);
+            gather_cols(X, d_sub_src, XS, stream_);
+        }
+        Plane XSd = ar.plane(H, Lp), COND = ar.plane(H, Lp), HH = ar.plane(H, Lp);
+        Plane PR = ar.plane(3 * cfg_.sdp_bins - 1, Lp), Z = ar.plane(2, Lp);
+        conv_plain(sdp_pre_, XS, XSd, 1, 0, nullptr, 1, stream_);
+        add_segvec(XSd, v_sdp, H, pl.d_seg_of, 1, pl.d_mask, stream_);
+        run_dds(sdp_dds_, XSd, pl, ar, Lt);
+        conv_plain(sdp_proj_, XSd, COND, 1, 0, pl.d_mask, 1, stream_);
+        z0 = Z.p;
+        float* z1 = Z.p + Z.ld;
+        noise_fill(Z.p, Z.ld, 2, pl.d_seg_of, pl.d_start, pl.d_len, sdp_sub ? d_sub_rows : d_rows, Lp, 0, stream_);
+        const float inv_sqrt_f = 1.0f / std::sqrt((float)H);
+        for (int i = (int)sdp_cf_.size() - 1; i >= 0; --i) {
+            const ConvFlow& cf = sdp_cf_[i];
+            swap_rows(z0, z1, Lp, stream_);  // Flip
+            convflow_pre(z0, cf.pre_w, cf.pre_b, COND, HH, pl.d_mask, stream_);
+            run_dds(cf.dds, HH, pl, ar, Lt);
+            conv_plain(cf.proj, HH, PR, 1, 0, pl.d_mask, 1, stream_);
+            spline_inverse(PR, z0, z1, cfg_.sdp_bins, cfg_.sdp_tail, inv_sqrt_f, pl.d_mask, Lp, stream_);
+        }
+        swap_rows(z0, z1, Lp, stream_);
+        affine_reverse(z0, z1, sdp_ea_m_, sdp_ea_logs_, sdp_ea_scale_, pl.d_mask, Lp, stream_);
     }
-    swap_rows(z0, z1, Lt, stream_);
-    affine_reverse(z0, z1, sdp_ea_m_, sdp_ea_logs_, sdp_ea_scale_, tl.d_mask, Lt, stream_);
 
     // ---- durations (the one device -> host sync of the batch: T_frames is data dependent) ----------------
     float* d_logw = ar.array<float>(Lt);
     int* d_dur = ar.array<int>(Lt);
-    sbv2::durations(z0, DPO.p, tl.d_seg_of, d_rows, tl.d_mask, Lt, d_logw, d_dur, stream_);
+    sbv2::durations(z0, DPO.p, tl.d_seg_of, d_rows, tl.d_mask, Lt, d_logw, d_dur, stream_, sdp_sub ? d_sdp_col : nullptr);
     std::vector<int> dur_p(Lt);
     std::vector<float> logw_p(Lt);
     HIP_CHECK(hipMemcpyAsync(dur_p.data(), d_dur, sizeof(int) * Lt, hipMemcpyDeviceToHost, stream_));
