@@ -207,6 +207,52 @@ inline sbv2_stream* stream_begin_request_assist(sbv2_bert* bert, sbv2_vits* vits
 }
 // (the kernels on their own are the test hook sbv2_debug_assist_blend of sbv2_hip.h: plain arrays in, plain arrays out, nothing to own here)
 
+// Not in the reference (sbv2_stream_voice in sbv2_hip.h states it): pitch, intonation and formant scale of a request STREAM about the pivots the
+// caller names, with the pivots owned.  pivot_hz: one entry per row of the batch.
+struct StreamVoice {
+    double pitch_scale = 1.0, intonation_scale = 1.0, formant_scale = 1.0;
+    std::vector<double> pivot_hz;
+    double f0_min = 0.0, f0_max = 0.0, threshold = 0.0;   // 0 = 70, 600, 0.15
+    int32_t hop = 0;                                       // 0 = rate / 200
+    // the C struct over this object's pivots, valid as long as it is not changed
+    const sbv2_stream_voice* c_struct() {
+        c_ = sbv2_stream_voice{sbv2_voice{pitch_scale, intonation_scale, f0_min, f0_max, threshold, hop, 0}, formant_scale,
+                               pivot_hz.empty() ? nullptr : pivot_hz.data(), {0.0, 0.0}};
+        return &c_;
+    }
+    // A_v at a rate (sbv2_stream_voice_lookahead; throws on parameters the begin call refuses)
+    int64_t lookahead(int32_t sample_rate = 44100) {
+        const int64_t a = sbv2_stream_voice_lookahead(c_struct(), sample_rate);
+        if (a < 0) check(1);
+        return a;
+    }
+
+  private:
+    sbv2_stream_voice c_{};
+};
+// sbv2_stream_begin_request_voice: sbv2_stream_begin_request_assist with the voice shifted on the way; voice == nullptr is exactly that call.
+// The chunks of a voice stream are taken with sbv2_stream_next_level (delivery runs behind them).
+inline sbv2_stream* stream_begin_request_voice(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch& batch, const sbv2_utt_options* opts, Assist* assist,
+                                               const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                               const sbv2_stream_request& rq, StreamVoice* voice, const sbv2_stream_levels* lv = nullptr,
+                                               const sbv2_stream_pitch* sp = nullptr, int64_t* total_samples = nullptr, int64_t* n_tokens = nullptr,
+                                               int64_t* n_env = nullptr, int64_t* n_pitch = nullptr) {
+    sbv2_stream* s = nullptr;
+    check(sbv2_stream_begin_request_voice(bert, vits, &batch, opts, assist ? assist->c_struct() : nullptr, token_ids, s_lens, word2ph, chunk_frames, &rq,
+                                          lv, sp, voice ? voice->c_struct() : nullptr, &s, total_samples, n_tokens, n_env, n_pitch));
+    return s;
+}
+// every call's delivered count of a voice stream without a level (sbv2_stream_voice_timeline)
+inline std::vector<int64_t> stream_voice_timeline(const std::vector<int64_t>& frames, const std::vector<int64_t>& gap_after, int32_t hop,
+                                                  int64_t chunk_frames, const sbv2_pcm_format* fmt, StreamVoice& voice) {
+    int64_t calls = 0;
+    check(sbv2_stream_voice_timeline(frames.data(), gap_after.data(), (int64_t)frames.size(), hop, chunk_frames, fmt, voice.c_struct(), nullptr, 0, &calls));
+    std::vector<int64_t> out((size_t)calls);
+    check(sbv2_stream_voice_timeline(frames.data(), gap_after.data(), (int64_t)frames.size(), hop, chunk_frames, fmt, voice.c_struct(), out.data(), calls,
+                                     &calls));
+    return out;
+}
+
 }  // namespace sbv2_core
 
 #endif

@@ -452,8 +452,9 @@ int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t
  * Not built: epoch (glottal) alignment of the marks, contour smoothing, energy compensation (octave-error repair of the
  *   contour is opt-in: sbv2_pitch_track and sbv2_pipeline_fetch_request_tracked below; a target per token instead of one pair of scales is
  *   sbv2_token_pitch and sbv2_pipeline_fetch_request_token_pitch below; moving the formants is sbv2_formant and
- *   sbv2_pipeline_fetch_request_formant below).  No
- *   stream entry point either: sbv2_stream_* and sbv2_node_* do not take a sbv2_voice. */
+ *   sbv2_pipeline_fetch_request_formant below).  On a
+ *   request stream the same shifter runs chunk by chunk about a pivot the caller names: sbv2_stream_voice and
+ *   sbv2_stream_begin_request_voice below; sbv2_node_* and the plain sbv2_stream_begin* entries do not take a sbv2_voice. */
 typedef struct sbv2_voice {
     double pitch_scale;          /* [0.5, 2] */
     double intonation_scale;     /* [0, 2] */
@@ -1039,6 +1040,65 @@ int sbv2_stream_begin_request_assist(sbv2_bert* bert, sbv2_vits* vits, const sbv
                                      const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
                                      const sbv2_stream_levels* lv /* may be NULL */, const sbv2_stream_pitch* sp /* may be NULL */, sbv2_stream** out,
                                      int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch);
+/* ---- new: pitch, intonation and formant scale on a request stream.  Nothing in sbv2_voice / sbv2_formant needs the whole signal except ONE
+ * number, the mean f0 m that the intonation scale pivots about; the contour, the Q32 phases (a prefix sum over frames), the mapping and the
+ * windows (one mark ahead) and the gather (a bounded half-width) are local.  A stream cannot know m ahead, as it cannot know its loudness, so
+ * the caller names the pivot (as sbv2_stream_level's caller names the gain) and everything else is carried from chunk to chunk ON THE DEVICE.
+ * Signal.  Row i of the stream is transformed exactly as sbv2_voice and sbv2_formant state it, with m := pivot_hz[i] and nothing else changed:
+ *   the contour on the row's native f32 samples at hop H, the increments, both mark lists, the mapping, the windows with their edge rules (the
+ *   row's length n is known at begin), the gather in f64 in ascending j, y = float(num / max(den, 1)).  formant_scale == 1 is the plain gather.
+ *   Hence: if pivot_hz[i] holds the bits of the row's own m, the shifted row equals the one-shot shifter's bit for bit whatever the chunk size;
+ *   |y| <= max |x| and the unchanged length come with it.
+ * Pivot.  Required for every stream voice, s == 1 included (ONE formula for the target): finite and in [f0_min, f0_max] after the 0-defaults.
+ *   Read it from any /synthesize_marks answer of the same voice (the mean f0_hz of its pitch block) or from src_f0.
+ * Look-ahead.  With W = max(tau_max + 1, sr / 200) + 2 (no half-width and no distance of two neighbouring analysis marks exceeds it),
+ *   G = ceil(W / min(q, 1)) + 1 and X = ceil((max(q, 1) - 1) W):  output k sums over the synthesis marks t within G of it, t <= k + G - 1; t
+ *   needs the first analysis mark at or after it, which lies before t + W; the nearer of that mark and its predecessor needs ITS successor
+ *   for its right half-width, before t + 2 W; an unvoiced grain is read up to q times as far as its window reaches, X samples more (samples,
+ *   not marks).  So marks are needed at positions below k + G - 1 + 2 W and samples at or below k + G - 1 + 2 W + X.  The marks below
+ *   position F H are known once the contour frames 0 .. F - 1 are, and frame f is complete where sbv2_pitch says: once f H + H div 2 + tau_max
+ *   samples are in.  With S samples fed the complete frames reach beyond S - tau_max - H div 2.  Output k is therefore final once
+ *       A_v = G + 2 W + X + tau_max + H div 2
+ *   native samples of the row follow it: 2640 at 44.1 kHz, 70 Hz, H = 220, q = 1 (60 ms); 3273 at q = 0.5, 3273 at q = 2.  A higher f0_min
+ *   shortens it (tau_max = ceil(sr / f0_min) enters four times).
+ * Delivery rule (deterministic, no host wait): after S native samples of a row have been fed and the row has not ended, max(0, S - A_v) of
+ *   its shifted samples are final; the window that feeds the row's last sample makes all n final.  A call then delivers the timeline's
+ *   output samples j whose filter reads final samples only (floor((j M + half) / L) below place + final), never fewer than the calls
+ *   before it delivered and nothing while no sample of the row is final; a row's last call delivers up to where it always ended (the
+ *   row's end and half its gap).  Time is not shifted: sbv2_stream_marks and sbv2_stream_timeline stay valid, only delivery runs late.
+ *   sbv2_stream_voice_timeline gives every call's delivered count ahead.  A level's own A adds behind.
+ * Taking the chunks: with sbv2_stream_next_level, whatever else the stream carries: *n_consumed = the chunk's samples (0 = the end),
+ *   *n_out = what the call delivers (bytes for FLAC), possibly 0.  The other sbv2_stream_next* calls are refused on a voice stream.
+ * Composition: every encoding, FLAC, sbv2_stream_level, levels / env_hop / stream pitch (all of the delivered, shifted samples), assist,
+ *   n rows with gaps.  voice == NULL is exactly sbv2_stream_begin_request_assist: the same launches, the same bytes.
+ * Refused before any GPU work: a NULL or non-finite pivot or one outside [f0_min, f0_max], the identity (p = s = q = 1: begin the stream
+ *   without the struct), non-zero reserved fields, everything sbv2_voice and sbv2_formant refuse.
+ * Not built: pitch_track and token_pitch on a stream (Viterbi and token means need unbounded look-ahead), the plain sbv2_stream_begin*
+ *   entries (a request stream of one row serves them), sbv2_node_*, estimating the pivot on the fly. */
+typedef struct sbv2_stream_voice {
+    sbv2_voice voice;            /* p, s, f0_min, f0_max, threshold, hop: the rules of sbv2_voice */
+    double formant_scale;        /* [0.5, 2], the rules of sbv2_formant; 1 = plain gather */
+    const double* pivot_hz;      /* [batch->n]: replaces the row mean m in g_f = p (m + s (f0_f - m)) */
+    double reserved[2];          /* must be 0 */
+} sbv2_stream_voice;
+int sbv2_stream_begin_request_voice(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                                    const sbv2_assist* assist /* may be NULL */, const int64_t* token_ids, const int64_t* s_lens,
+                                    const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
+                                    const sbv2_stream_levels* lv /* may be NULL */, const sbv2_stream_pitch* sp /* may be NULL */,
+                                    const sbv2_stream_voice* voice /* may be NULL */, sbv2_stream** out, int64_t* total_samples,
+                                    int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch);
+/* Host only: A_v at sample_rate (v->pivot_hz is not looked at); -1 for parameters the begin call refuses. */
+int64_t sbv2_stream_voice_lookahead(const sbv2_stream_voice* v, int32_t sample_rate);
+/* Host only: sbv2_stream_timeline's arguments and the voice (pivot_hz not looked at; the rate is the model's, 44100) -> call_delivered[c] = the
+ * samples call c of a voice stream WITHOUT a level delivers by the delivery rule (they sum to the stream's total), *n_calls. */
+int sbv2_stream_voice_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int32_t hop, int64_t chunk_frames,
+                               const sbv2_pcm_format* fmt, const sbv2_stream_voice* v, int64_t* call_delivered, int64_t capacity, int64_t* n_calls);
+/* Test hook: the fed shifter on one host row x[n] at sample_rate, cut at the ascending positions cuts[ncuts] into ncuts + 1 pushes (empty ones
+ * allowed, the last one ends the row); v carries ONE pivot.  period_in / voiced_in as sbv2_debug_voice_shift takes them.  y receives the
+ * pushes' final samples back to back (n in all), out_per_push[ncuts + 1] their counts (the delivery rule). */
+int sbv2_debug_voice_stream(int device, const float* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, const sbv2_stream_voice* v,
+                            const double* period_in, const int32_t* voiced_in, float* y, int64_t* out_per_push);
+
 /* Test hook: the two kernels on a host plane F [C][ld] (pitch ld, any value >= 1; on the device it lies between NaN words).  Assist sequence a
  * is the columns [a_start[a], a_start[a] + a_len[a]) of F; text column t < L reads source column map[t] (< 0: padding) and belongs to row
  * row_of[t] in [0, n_rows) (read where map[t] >= 0); text_of / weight [n_rows] as in sbv2_assist, checked the same way.  mean [A][C] and

@@ -123,6 +123,11 @@ class Sbv2Formant(C.Structure):
     _fields_ = [("formant_scale", C.c_double), ("reserved", C.c_double)]
 
 
+class Sbv2StreamVoice(C.Structure):
+    """struct sbv2_stream_voice (include/sbv2_hip.h)."""
+    _fields_ = [("voice", Sbv2Voice), ("formant_scale", C.c_double), ("pivot_hz", C.POINTER(C.c_double)), ("reserved", C.c_double * 2)]
+
+
 class Sbv2Assist(C.Structure):
     """struct sbv2_assist (include/sbv2_hip.h)."""
     _fields_ = [("n_texts", C.c_int64), ("token_ids", i64p), ("s_lens", i64p), ("text_of", C.POINTER(C.c_int32)), ("weight", C.POINTER(C.c_double)),
@@ -291,6 +296,14 @@ SYMBOLS = {
     "sbv2_stream_begin_request_assist": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), C.POINTER(Sbv2Assist), i64p, i64p,
                                                    i64p, C.c_int64, C.POINTER(Sbv2StreamRequest), C.POINTER(Sbv2StreamLevels), C.POINTER(Sbv2StreamPitch),
                                                    C.POINTER(C.c_void_p), i64p, i64p, i64p, i64p]),
+    "sbv2_stream_begin_request_voice": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), C.POINTER(Sbv2Assist), i64p, i64p,
+                                                  i64p, C.c_int64, C.POINTER(Sbv2StreamRequest), C.POINTER(Sbv2StreamLevels), C.POINTER(Sbv2StreamPitch),
+                                                  C.POINTER(Sbv2StreamVoice), C.POINTER(C.c_void_p), i64p, i64p, i64p, i64p]),
+    "sbv2_stream_voice_lookahead": (C.c_int64, [C.POINTER(Sbv2StreamVoice), C.c_int32]),
+    "sbv2_stream_voice_timeline": (C.c_int, [i64p, i64p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sbv2PcmFormat), C.POINTER(Sbv2StreamVoice), i64p,
+                                             C.c_int64, i64p]),
+    "sbv2_debug_voice_stream": (C.c_int, [C.c_int, f32p, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2StreamVoice), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_int32), f32p, i64p]),
     "sbv2_debug_assist_blend": (C.c_int, [C.c_int, f32p, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int64,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_double), f32p, f32p,
                                           i64p]),

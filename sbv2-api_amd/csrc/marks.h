@@ -172,6 +172,12 @@ struct PitchFrame {   // one frame's device results (32 bytes): what Pitch keeps
     double c3[3];
     int32_t lag, voiced;
 };
+// the completion rule on its own: the frames of a signal of `total` samples that are complete once D of them are in
+int64_t pitch_frames_complete(const PitchSpec& sp, int64_t total, int64_t D);
+// k_stream_pitch over a signal that is fed into ONE device buffer (the stream form of the shifter, voice.hip): x holds the first `fed` of its
+// `total` f32 samples; the complete frames [first, first + count) go to res[first ...] with the bits of pitch_launch over the whole signal.
+// No carry is read or written.  count = 0 enqueues nothing; frames that are not complete are refused (throws).
+void pitch_launch_fed(const float* x, int64_t fed, int64_t total, const PitchSpec& sp, int64_t first, int64_t count, PitchFrame* res, hipStream_t s);
 class StreamPitch {
   public:
     StreamPitch() = default;

@@ -743,10 +743,36 @@ void StreamPitch::check(const PitchSpec& sp, int64_t total) {
     SBV2_REQUIRE(nf < (1 << 30), "too many pitch frames: " + std::to_string(nf) + " >= 2^30");
 }
 
-int64_t StreamPitch::complete(int64_t D) const {
-    if (nf_ == 0 || D >= total_) return nf_;
-    const int64_t r = D - sp_.tau_max - sp_.hop / 2;   // frame f: f hop + hop / 2 + tau_max <= D
-    return r < 0 ? 0 : std::min(nf_, r / sp_.hop + 1);
+int64_t pitch_frames_complete(const PitchSpec& sp, int64_t total, int64_t D) {
+    const int64_t nf = pitch_frames(total, sp.hop);
+    if (nf == 0 || D >= total) return nf;
+    const int64_t r = D - sp.tau_max - sp.hop / 2;   // frame f: f hop + hop / 2 + tau_max <= D
+    return r < 0 ? 0 : std::min(nf, r / sp.hop + 1);
+}
+
+int64_t StreamPitch::complete(int64_t D) const { return pitch_frames_complete(sp_, total_, D); }
+
+void pitch_launch_fed(const float* x, int64_t fed, int64_t total, const PitchSpec& sp, int64_t first, int64_t count, PitchFrame* res, hipStream_t s) {
+    SBV2_REQUIRE(fed >= 0 && fed <= total && sp.hop >= 1 && sp.tau_min >= 1 && sp.tau_min <= sp.tau_max && sp.tau_max <= kPitchMaxTau,
+                 "internal: bad pitch spec");
+    SBV2_REQUIRE(first >= 0 && count >= 0 && first + count <= pitch_frames_complete(sp, total, fed), "internal: pitch frames that are not complete yet");
+    if (count == 0) return;
+    SBV2_REQUIRE(x && res, "internal: no samples");
+    StreamPitchArgs a{};   // no carry: every fed sample lies at x
+    a.x = x;
+    a.d0 = 0;
+    a.d1 = fed;
+    a.total = total;
+    a.hop = sp.hop;
+    a.first = first;
+    a.count = (int32_t)count;
+    a.tau_min = sp.tau_min;
+    a.tau_max = sp.tau_max;
+    a.threshold = sp.threshold;
+    a.res = res;
+    const int nt = pitch_lanes(sp.tau_max), P = (sp.tau_max + nt - 1) / nt;
+    launch_stream_pitch<float>(P, dim3((unsigned)count), dim3(nt), s, a);
+    HIP_CHECK(hipGetLastError());
 }
 
 void StreamPitch::begin(const PitchSpec& sp, int encoding, int64_t total, hipStream_t s) {

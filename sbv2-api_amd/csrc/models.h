@@ -302,6 +302,9 @@ struct StreamTimeline {
 int64_t stream_min_gap(const PcmFmtSpec& spec);   // 2 ceil(half / L): no output sample on one side of a cut has a filter tap on the other side's row
 void stream_check_gaps(const int64_t* gap_after, int64_t n, const PcmFmtSpec& spec);
 StreamTimeline stream_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int hop, int64_t chunk_frames, const PcmFmtSpec& spec);
+// The delivery rule of a voice stream (above sbv2_stream_voice, include/sbv2_hip.h) over timeline t: entry c = the output samples delivered
+// once call c has been taken, without a level; `lookahead` = A_v.  Host only; the stream's pushes and sbv2_stream_voice_timeline both read it here.
+std::vector<int64_t> stream_voice_upto(const StreamTimeline& t, int hop, int64_t chunk_frames, const PcmFmtSpec& spec, int64_t lookahead);
 struct VitsBatch {
     int n = 0;
     const int64_t* t_lens = nullptr;   // [n]
@@ -363,8 +366,10 @@ class VitsModel {
     // marks (needs fmt): levels per token and / or per envelope frame of the DELIVERED samples, reduced replay by replay (StreamLevels, marks.h):
     // one push per replay on what crosses PCIe or enters the FLAC encoder; such a stream delivers in order only.  marks->pitch: the pitch contour
     // of the same samples, fed by the same pushes (StreamPitch, marks.h), with or without the levels; in order only as well
+    // voice (needs fmt; its pivots one per row): every window's central samples pass the fed shifter (StreamVoice, voice.h) ahead of the
+    // formatter, which then reads the shifted rows; delivery runs A_v native samples behind within a row (stream_voice_upto); in order only
     int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false, const StreamLevelSpec* level = nullptr,
-                         const int64_t* gap_after = nullptr, const StreamMarksSpec* marks = nullptr);
+                         const int64_t* gap_after = nullptr, const StreamMarksSpec* marks = nullptr, const StreamVoiceSpec* voice = nullptr);
     // the output side of the running stream when it is formatted (stream_output.h: its kind, reductions, delivered count), else nullptr
     const StreamOutput* stream_output() const { return sformatted_ ? sout_.get() : nullptr; }
     const StreamTimeline& stream_layout() const { return stl_; }
@@ -500,6 +505,7 @@ class VitsModel {
     void ensure_plan(std::shared_ptr<ChunkPlan>& slot, int chunk_frames, int nwin);
     void stream_enqueue(ChunkPlan& c, int64_t c0, int slot);   // the replay of calls c0 .. c0 + nwin - 1
     StreamTimeline stl_;                         // rows, placement and calls of the running stream
+    std::vector<int64_t> svoice_upto_;           // a voice stream: the calls' cumulative delivered samples (empty otherwise)
     bool sformatted_ = false;                    // the running stream is formatted (stream_begin with fmt) ...
     std::shared_ptr<StreamOutput> sout_;         // ... and this is everything behind its decoder (made by the first such stream; a clone makes its own)
     bool stream_bursts_ = false;                 // the running stream uses burst_ behind its first chunk

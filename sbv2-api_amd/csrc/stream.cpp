@@ -36,7 +36,8 @@ PcmFmtSpec flac_stream_spec(const sbv2_pcm_format* fmt) {
 // a plain stream (native f32, one row); gap_after == nullptr: one row without gaps.  Every check of the arguments has happened before.
 void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
                   int64_t chunk_frames, const PcmFmtSpec* spec, bool flac, const StreamLevelSpec* level, const int64_t* gap_after, sbv2_stream** out,
-                  int64_t* total_samples, const StreamMarksSpec* marks = nullptr, const AssistSpec* assist = nullptr) {
+                  int64_t* total_samples, const StreamMarksSpec* marks = nullptr, const AssistSpec* assist = nullptr,
+                  const StreamVoiceSpec* voice = nullptr) {
     VitsBatch run = v;
     run.skip_decoder = true;
     pipeline_run_one(*bert->m, *vits->m, run, token_ids, s_lens, word2ph, assist);
@@ -46,7 +47,7 @@ void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const in
     s->durations = vits->m->used_durations();
     s->offs = vits->m->used_offs();
     if (spec) s->spec = *spec;
-    s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after, marks);
+    s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after, marks, voice);
     if (total_samples) *total_samples = pcm_format_out_len(s->spec, vits->m->stream_layout().joined);
     *out = s.release();
 }
@@ -55,9 +56,13 @@ void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const in
 enum NextKind { kNextPlain, kNextFormat, kNextFlac, kNextLevel };
 void require_kind(const sbv2_stream* s, NextKind want) {
     const StreamOutput* o = s->output();
-    const bool level = o && o->level(), flac = o && o->flac();
-    if (want == kNextLevel) SBV2_REQUIRE(level, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
-    else SBV2_REQUIRE(!level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
+    const bool level = o && o->level(), flac = o && o->flac(), voice = o && o->voice();
+    if (want == kNextLevel) {
+        SBV2_REQUIRE(level || voice, "this stream was not begun with a level: take its chunks with the sbv2_stream_next call of its kind");
+    } else {
+        SBV2_REQUIRE(!level, "this stream was begun with a level: take its chunks with sbv2_stream_next_level");
+        SBV2_REQUIRE(!voice, "this stream was begun with a voice, and delivery runs behind its chunks: take them with sbv2_stream_next_level");
+    }
     if (want == kNextFlac) SBV2_REQUIRE(flac, "this stream was not begun as FLAC: take its chunks with sbv2_stream_next or sbv2_stream_next_format");
     else if (want != kNextLevel) SBV2_REQUIRE(!flac, "this stream was begun as FLAC: take its chunks with sbv2_stream_next_flac");
     if (want == kNextFormat) SBV2_REQUIRE(o, "this stream has no output format: take its chunks with sbv2_stream_next");
@@ -271,7 +276,7 @@ namespace {
 // sbv2_stream_begin_request, with or without levels: every check before any GPU work
 void begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids, const int64_t* s_lens,
                    const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq, const StreamMarksSpec* marks, sbv2_stream** out,
-                   int64_t* total_samples, const AssistSpec* assist = nullptr) {
+                   int64_t* total_samples, const AssistSpec* assist = nullptr, const StreamVoiceSpec* voice = nullptr) {
     SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
     SBV2_REQUIRE(rq, "no sbv2_stream_request given");
     SBV2_REQUIRE(rq->gap_after, "sbv2_stream_request.gap_after must not be NULL (one entry per row, the last one = trailing silence)");
@@ -288,7 +293,7 @@ void begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, co
     apply_utt_options(&v, opts);
     stream_check_gaps(rq->gap_after, batch->n, spec);
     begin_stream(bert, vits, v, token_ids, s_lens, word2ph, chunk_frames, &spec, rq->flac != 0, rq->level ? &lv : nullptr, rq->gap_after, out,
-                 total_samples, marks, assist);
+                 total_samples, marks, assist, voice);
 }
 }  // namespace
 
@@ -346,9 +351,60 @@ int sbv2_stream_begin_request_assist(sbv2_bert* bert, sbv2_vits* vits, const sbv
                                      const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
                                      const sbv2_stream_request* rq, const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp, sbv2_stream** out,
                                      int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch) {
+    return sbv2_stream_begin_request_voice(bert, vits, batch, opts, assist, token_ids, s_lens, word2ph, chunk_frames, rq, lv, sp, nullptr, out,
+                                           total_samples, n_tokens, n_env, n_pitch);
+}
+
+// Host only: A_v of a stream voice at a rate (-1: what the begin call refuses; the pivot is not looked at)
+int64_t sbv2_stream_voice_lookahead(const sbv2_stream_voice* v, int32_t sample_rate) {
+    try {
+        SBV2_REQUIRE(v, "no sbv2_stream_voice given");
+        SBV2_REQUIRE(v->voice.reserved == 0, "sbv2_voice.reserved must be 0");
+        return stream_voice_spec(sample_rate, v->voice.pitch_scale, v->voice.intonation_scale, v->voice.hop, v->voice.f0_min, v->voice.f0_max,
+                                 v->voice.threshold, v->formant_scale, nullptr, 0, v->reserved[0], v->reserved[1])
+            .lookahead;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// Host only: what every call of a voice stream without a level delivers (stream_voice_upto, vits.cpp: the library's own arithmetic)
+int sbv2_stream_voice_timeline(const int64_t* frames, const int64_t* gap_after, int64_t n, int32_t hop, int64_t chunk_frames, const sbv2_pcm_format* fmt,
+                               const sbv2_stream_voice* v, int64_t* call_delivered, int64_t capacity, int64_t* n_calls) {
+    API_BEGIN
+    const int64_t A = sbv2_stream_voice_lookahead(v, kNativeRate);
+    SBV2_REQUIRE(A >= 0, sbv2_last_error());
+    const PcmFmtSpec spec = fmt ? pcm_format_spec(fmt) : PcmFmtSpec();
+    const StreamTimeline t = stream_timeline(frames, gap_after, n, hop, chunk_frames, spec);
+    const std::vector<int64_t> upto = stream_voice_upto(t, hop, chunk_frames, spec, A);
+    const int64_t calls = (int64_t)upto.size();
+    if (n_calls) *n_calls = calls;
+    SBV2_REQUIRE(!call_delivered || capacity >= calls, "call_delivered too small: " + std::to_string(capacity) + " < " + std::to_string(calls) + " calls");
+    if (call_delivered)
+        for (int64_t c = 0; c < calls; ++c) call_delivered[c] = upto[(size_t)c] - (c ? upto[(size_t)(c - 1)] : 0);
+    API_END
+}
+
+// ... and with the voice shifted on the way (the contract above sbv2_stream_voice, include/sbv2_hip.h): the fed shifter ahead of the formatter
+// (StreamVoice, voice.hip; StreamOutput::push).  voice NULL: exactly the call above.  Its fields are checked with the others', before the
+// handles are looked at.
+int sbv2_stream_begin_request_voice(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const sbv2_assist* assist,
+                                    const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                    const sbv2_stream_request* rq, const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp,
+                                    const sbv2_stream_voice* voice, sbv2_stream** out, int64_t* total_samples, int64_t* n_tokens, int64_t* n_env,
+                                    int64_t* n_pitch) {
     API_BEGIN
     StreamMarksSpec marks;
     bool on = levels_spec(lv, &marks);
+    StreamVoiceSpec vs;
+    if (voice) {
+        SBV2_REQUIRE(batch && batch->n >= 1, "sbv2_stream_begin_request takes at least one row");
+        SBV2_REQUIRE(voice->voice.reserved == 0, "sbv2_voice.reserved must be 0");
+        vs = stream_voice_spec(kNativeRate, voice->voice.pitch_scale, voice->voice.intonation_scale, voice->voice.hop, voice->voice.f0_min,
+                               voice->voice.f0_max, voice->voice.threshold, voice->formant_scale, voice->pivot_hz, batch->n, voice->reserved[0],
+                               voice->reserved[1]);
+    }
     if (sp) {
         SBV2_REQUIRE(sp->reserved == 0, "sbv2_stream_pitch.reserved must be 0");
         const int rate = rq && rq->fmt ? pcm_format_spec(rq->fmt).rate : PcmFmtSpec().rate;
@@ -360,7 +416,8 @@ int sbv2_stream_begin_request_assist(sbv2_bert* bert, sbv2_vits* vits, const sbv
         SBV2_REQUIRE(batch && batch->n >= 1, "sbv2_stream_begin_request takes at least one row");
         as = assist_spec(assist, batch->n);
     }
-    begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples, &as);
+    begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples, &as,
+                  voice ? &vs : nullptr);
     const StreamLevels* l = (*out)->output()->levels();
     const StreamPitch* q = (*out)->output()->pitch();
     if (n_tokens) *n_tokens = l ? l->n_tok() : 0;

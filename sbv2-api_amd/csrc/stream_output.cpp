@@ -13,7 +13,7 @@ int64_t StreamOutput::check(const PcmFmtSpec& spec, const StreamLevelSpec* level
 
 void StreamOutput::begin(const PcmFmtSpec& spec, bool flac, const StreamLevelSpec* level, const StreamMarksSpec* marks, const std::vector<int64_t>& used,
                          const std::vector<int64_t>& offs, const int64_t* place, int hop, int64_t joined, int64_t cap, hipStream_t s) {
-    flac_on_ = level_on_ = levels_on_ = pitch_on_ = false;
+    flac_on_ = level_on_ = levels_on_ = pitch_on_ = voice_on_ = false;
     spec_ = spec;
     A_ = level ? stream_level_lookahead(spec.rate) : 0;
     delivered_ = 0;
@@ -51,12 +51,49 @@ void StreamOutput::begin(const PcmFmtSpec& spec, bool flac, const StreamLevelSpe
     }
 }
 
-void StreamOutput::push(const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, bool last, int fmt_slot, void* host,
-                        int64_t cap, Slot& rec, hipStream_t s) {
+void StreamOutput::begin_voice(const StreamVoiceSpec& voice, const std::vector<int64_t>& place, const std::vector<int64_t>& len,
+                               std::vector<int64_t> upto, hipStream_t s) {
+    // the rows back to back in the stage's two buffers; the formatter finds row i's shifted samples at place[i] of the timeline
+    const int nrows = (int)place.size();
+    std::vector<VoiceRow> rows((size_t)nrows);
+    int64_t span = 0;
+    for (int i = 0; i < nrows; ++i) {
+        rows[(size_t)i] = VoiceRow{span, len[(size_t)i]};
+        span += len[(size_t)i];
+    }
+    if (!voice_) voice_.reset(new StreamVoice);
+    voice_->begin(voice, rows.data(), nrows, span, s);
+    vpieces_.clear();
+    for (int i = 0; i < nrows; ++i) vpieces_.push_back(FmtPiece{voice_->out(i), place[(size_t)i], len[(size_t)i]});
+    vupto_ = std::move(upto);
+    voice_on_ = true;
+}
+
+void StreamOutput::push(const std::vector<FmtPiece>& pieces_in, const std::vector<FmtSignal>& sig_in, int64_t total, bool last, int fmt_slot,
+                        void* host, int64_t cap, Slot& rec, hipStream_t s, const std::vector<StreamVoiceFeed>* feed, int64_t c0) {
+    std::vector<FmtSignal> vsig;
+    if (voice_on_) {
+        // every window's native samples go through the shifter first; the window then delivers the outputs the delivery rule makes final
+        // (vupto_, worked out at begin: nothing here waits for the device), read from the shifted rows
+        SBV2_REQUIRE(feed && feed->size() == sig_in.size() && c0 >= 0 && c0 + (int64_t)feed->size() <= (int64_t)vupto_.size(),
+                     "internal: a voice stream's replay without its windows' samples");
+        total = 0;
+        for (size_t w = 0; w < feed->size(); ++w) {
+            const StreamVoiceFeed& f = (*feed)[w];
+            SBV2_REQUIRE(f.s0 == voice_->fed(f.row), "internal: a voice replay out of stream order (row " + std::to_string(f.row) + ": sample " +
+                                                         std::to_string(f.s0) + " after " + std::to_string(voice_->fed(f.row)) + " fed)");
+            voice_->push(f.row, f.src, f.s1 - f.s0, s);
+            const int64_t c = c0 + (int64_t)w, j0 = c ? vupto_[(size_t)(c - 1)] : 0, j1 = vupto_[(size_t)c];
+            vsig.push_back(FmtSignal{j0, j1, total, 0, (int32_t)vpieces_.size()});
+            total += j1 - j0;
+        }
+    }
+    const std::vector<FmtPiece>& pieces = voice_on_ ? vpieces_ : pieces_in;
+    const std::vector<FmtSignal>& sig = voice_on_ ? vsig : sig_in;
     SBV2_REQUIRE(total + A_ <= cap, "internal: a replay of " + std::to_string(total) + " samples exceeds the slot sized for " + std::to_string(cap));
     rec.host = static_cast<const char*>(host);
     rec.win.clear();
-    for (const FmtSignal& g : sig) rec.win.push_back(Slot::Win{g.out_off, g.j1 - g.j0, g.j1 - g.j0, 0, 0});
+    for (size_t w = 0; w < sig.size(); ++w) rec.win.push_back(Slot::Win{sig[w].out_off, sig[w].j1 - sig[w].j0, sig_in[w].j1 - sig_in[w].j0, 0, 0});
     // the replay's delivered samples are [d0, d0 + n) of the stream; on the device they lie behind the encoder's carried tail or in the formatter's buffer
     void* dev = flac_on_ ? static_cast<void*>(flac_->dst()) : fmtr_.out_buffer((size_t)cap * spec_.bytes(), s);
     const int64_t fed0 = sig.empty() ? 0 : sig[0].j0;
@@ -101,7 +138,8 @@ void StreamOutput::push(const std::vector<FmtPiece>& pieces, const std::vector<F
 }
 
 const char* StreamOutput::ordered() const {
-    return level_on_    ? "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk"
+    return voice_on_    ? "a voice stream delivers its chunks in order only: the shifter carries its phases and marks from chunk to chunk"
+           : level_on_  ? "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk"
            : flac_on_   ? "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk"
            : levels_on_ ? "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk"
            : pitch_on_  ? "a stream with pitch delivers its chunks in order only: the estimator carries the last samples from chunk to chunk"

@@ -6,6 +6,7 @@
 #include "limiter.h"
 #include "marks.h"
 #include "pcm_format.h"
+#include "voice.h"
 
 #include <memory>
 
@@ -18,6 +19,14 @@ struct StreamMarksSpec {
     // the pitch contour of the delivered samples (sbv2_stream_pitch): on or off independently of the levels; the spec at the stream's delivered rate
     bool pitch = false;
     PitchSpec pitch_spec;
+};
+
+// One window of a replay as the voice stage is fed it (sbv2_stream_voice): the window's central native samples clipped to its row, the
+// samples [s0, s1) of row `row`, at src on the device.
+struct StreamVoiceFeed {
+    int row;
+    int64_t s0, s1;
+    const float* src;
 };
 
 class StreamOutput {
@@ -37,6 +46,12 @@ class StreamOutput {
     // Host only, throws: the frame counts of the envelope and of the contour over the `joined` native samples of the timeline, then the
     // look-ahead A of the level (0 without one), which it returns.  Called before a stream sets up anything.
     static int64_t check(const PcmFmtSpec& spec, const StreamLevelSpec* level, const StreamMarksSpec* marks, int64_t joined);
+    // A voice stream (sbv2_stream_voice) over rows of len[i] native samples at place[i] of the timeline, begun right after begin(): the
+    // shifter's stage is made on first use; upto = the calls' cumulative delivered samples (stream_voice_upto, models.h).  From then on push()
+    // is given the windows' feeds and formats the SHIFTED rows.
+    void begin_voice(const StreamVoiceSpec& voice, const std::vector<int64_t>& place, const std::vector<int64_t>& len, std::vector<int64_t> upto,
+                     hipStream_t s);
+    bool voice() const { return voice_on_; }
     // pinned bytes of a slot whose replays deliver up to cap samples (A included)
     static size_t slot_bytes(const PcmFmtSpec& spec, bool flac, int64_t cap) { return flac ? FlacStreamEncoder::host_bytes(cap) : (size_t)cap * spec.bytes(); }
     // A stream of `joined` native samples whose largest replay delivers cap samples (A included).  Each optional stage is made on first use
@@ -47,8 +62,10 @@ class StreamOutput {
     // One replay, enqueued on s: the formatter over its windows (sig[w] = window w), with a level the limiter's push and the cast, the levels
     // and pitch pushes on the delivered samples, then the sink: the encoder's push into `host` or the copy there.  fmt_slot: the formatter's
     // table slot; cap: what `host` was sized for; rec: filled for deliver.
+    // A voice stream: feed[w] = window w's native samples and c0 = the replay's first call; the pieces and signals are then made here, from
+    // the shifted rows and the delivery rule, and the caller's are not looked at (sig[w].j1 - sig[w].j0 stays what window w fed).
     void push(const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, bool last, int fmt_slot, void* host,
-              int64_t cap, Slot& rec, hipStream_t s);
+              int64_t cap, Slot& rec, hipStream_t s, const std::vector<StreamVoiceFeed>* feed = nullptr, int64_t c0 = 0);
     // Why this stream delivers in order only (something is carried from replay to replay), or nullptr: replays may be enqueued again
     const char* ordered() const;
     // Window w of a replay that has completed -> dst, the stream header in front for call ci = 0 of a FLAC stream.  Too small a buffer is
@@ -70,6 +87,10 @@ class StreamOutput {
     std::unique_ptr<StreamLimiter> lim_;
     std::unique_ptr<StreamLevels> levels_;
     std::unique_ptr<StreamPitch> pitch_;
+    std::unique_ptr<StreamVoice> voice_;
+    std::vector<FmtPiece> vpieces_;   // a voice stream's pieces: every row's shifted samples at its place
+    std::vector<int64_t> vupto_;      // ... and its calls' cumulative delivered samples
+    bool voice_on_ = false;
     bool flac_on_ = false, level_on_ = false, levels_on_ = false, pitch_on_ = false;   // what the running stream uses of them
     int64_t A_ = 0;           // the level's look-ahead in delivered samples (0 without a level)
     int64_t delivered_ = 0;

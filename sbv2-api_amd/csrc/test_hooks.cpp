@@ -2312,6 +2312,53 @@ int sbv2_debug_voice_formant(int device, const float* x, const int64_t* lens, in
                        n_marks, y, nullptr, formant);
 }
 
+// The fed shifter (StreamVoice, voice.hip) on its own: one row x cut at cuts[ncuts] into ncuts + 1 pushes, each handed a COPY of its piece
+// between two guards of a fill pattern (the stage keeps the fed samples itself; nothing in front of or behind a piece is its to read).  The
+// shifted samples each push made final go to y back to back.  Everything is checked before any device call.
+int sbv2_debug_voice_stream(int device, const float* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, const sbv2_stream_voice* v,
+                            const double* period_in, const int32_t* voiced_in, float* y, int64_t* out_per_push) {
+    API_BEGIN
+    SBV2_REQUIRE(v && out_per_push && n >= 0 && n < (1 << 30) && ncuts >= 0 && (ncuts == 0 || cuts) && (n == 0 || (x && y)), "bad arguments");
+    SBV2_REQUIRE(v->voice.reserved == 0, "sbv2_voice.reserved must be 0");
+    SBV2_REQUIRE(!period_in == !voiced_in, "period_in and voiced_in are given together or not at all");
+    const StreamVoiceSpec sp = stream_voice_spec(sample_rate, v->voice.pitch_scale, v->voice.intonation_scale, v->voice.hop, v->voice.f0_min,
+                                                 v->voice.f0_max, v->voice.threshold, v->formant_scale, v->pivot_hz, 1, v->reserved[0], v->reserved[1]);
+    std::vector<int64_t> edge(1, 0);
+    int64_t longest = 0;
+    for (int i = 0; i < ncuts; ++i) {
+        SBV2_REQUIRE(cuts[i] >= edge.back() && cuts[i] <= n, "cuts must ascend within [0, n]");
+        edge.push_back(cuts[i]);
+    }
+    edge.push_back(n);
+    for (size_t i = 0; i + 1 < edge.size(); ++i) longest = std::max(longest, edge[i + 1] - edge[i]);
+    const size_t guard = 4096;
+    AudioScratch r(device, x, sizeof(float) * (size_t)n);
+    DeviceBuffer piece;
+    char* pc = static_cast<char*>(piece.reserve(sizeof(float) * (size_t)longest + 2 * guard, r.s));
+    HIP_CHECK(hipMemsetAsync(pc, 0x5A, sizeof(float) * (size_t)longest + 2 * guard, r.s));
+    const VoiceRow row{0, n};
+    StreamVoice sv;
+    sv.begin(sp, &row, 1, n, r.s, period_in, voiced_in);
+    std::vector<float> out((size_t)std::max<int64_t>(n, 1));
+    int64_t at = 0;
+    for (int i = 0; i <= ncuts; ++i) {
+        const int64_t len = edge[i + 1] - edge[i];
+        // (stream order: the previous push has copied the piece before this copy overwrites it)
+        if (len) HIP_CHECK(hipMemcpyAsync(pc + guard, r.x.as<float>() + edge[i], sizeof(float) * (size_t)len, hipMemcpyDeviceToDevice, r.s));
+        const int64_t fin = sv.push(0, reinterpret_cast<const float*>(pc + guard), len, r.s);
+        out_per_push[i] = fin - at;
+        // the samples this push made final, read before a later push could write them again (it never does)
+        if (fin > at) HIP_CHECK(hipMemcpyAsync(out.data() + at, sv.out(0) + at, sizeof(float) * (size_t)(fin - at), hipMemcpyDeviceToHost, r.s));
+        at = fin;
+    }
+    sv.status_to_host(r.s);
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    SBV2_REQUIRE(at == n, "internal: the fed shifter made " + std::to_string(at) + " of " + std::to_string(n) + " samples final");
+    SBV2_REQUIRE(sv.status(0) == 0, "internal: the shifter found more marks than it planned for");
+    if (n) std::memcpy(y, out.data(), sizeof(float) * (size_t)n);
+    API_END
+}
+
 // The fed level reduction (StreamLevels, marks.hip) on its own: x cut at cuts[ncuts] into ncuts + 1 pushes, each handed the samples of its
 // piece only.  Segments, envelope and cuts are checked before any device call.
 int sbv2_debug_stream_levels(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, const int64_t* starts,

@@ -1069,8 +1069,28 @@ StreamTimeline stream_timeline(const int64_t* frames, const int64_t* gap_after, 
     return t;
 }
 
+std::vector<int64_t> stream_voice_upto(const StreamTimeline& t, int hop, int64_t chunk_frames, const PcmFmtSpec& spec, int64_t lookahead) {
+    SBV2_REQUIRE(hop >= 1 && chunk_frames >= 1 && lookahead >= 0, "bad timeline arguments");
+    std::vector<int64_t> upto;
+    int64_t prev = 0;
+    for (const StreamCall& k : t.calls) {
+        const int64_t len = t.len[(size_t)k.row], S = std::min((k.f0 + chunk_frames) * (int64_t)hop, len);
+        int64_t now = prev;
+        if (S >= len) {
+            now = k.j1;   // the row's last call: where it always ended
+        } else if (S > lookahead) {
+            // the outputs j whose newest tap, floor((j M + half) / L), lies below P = place + final: j M + half <= P L - 1
+            const int64_t P = t.place[(size_t)k.row] + (S - lookahead), top = P * spec.L - 1 - spec.half;
+            if (top >= 0) now = std::max(prev, std::min(top / spec.M + 1, k.j1));
+        }
+        upto.push_back(now);
+        prev = now;
+    }
+    return upto;
+}
+
 int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac, const StreamLevelSpec* level, const int64_t* gap_after,
-                                const StreamMarksSpec* marks) {
+                                const StreamMarksSpec* marks, const StreamVoiceSpec* voice) {
     HIP_CHECK(hipSetDevice(device_));
     SBV2_REQUIRE(fl_.n >= 1 && z_.p, "stream_begin needs a preceding forward with skip_decoder");
     SBV2_REQUIRE(gap_after || fl_.n == 1, "stream_begin without gaps needs a preceding forward of ONE utterance");
@@ -1080,8 +1100,8 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     SBV2_REQUIRE(!marks || fmt, "levels and pitch on a stream need an output format: begin it with the identity format (44100 Hz f32) instead of none");
     SBV2_REQUIRE(!flac || (fmt && fmt->encoding == kEncS16), "a FLAC stream needs encoding = 1 (s16): f32 samples and G.711 codes have no FLAC form");
     SBV2_REQUIRE(!level || fmt, "a level stream needs an output format");
-    if (fmt) {
-        SBV2_REQUIRE(!fmt->normalize, "a formatted stream cannot normalise: the peak of the utterance is not known ahead");
+    if (fmt) SBV2_REQUIRE(!fmt->normalize, "a formatted stream cannot normalise: the peak of the utterance is not known ahead");
+    if (fmt && !voice) {   // (a voice stream formats the shifted rows, whole on the device: no filter tap reads a window's halo)
         // the filter of an output sample at a chunk edge reaches ceil(half / L) native samples past the window centre; they must lie in the
         // part of the halo that the decoder computes exactly (halo minus the generator's receptive field)
         const int64_t reach = (fmt->half + fmt->L - 1) / fmt->L;
@@ -1095,6 +1115,10 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
     stl_ = stream_timeline(frames.data(), gap_after ? gap_after : &no_gap, fl_.n, cfg_.hop(), chunk_frames, fmt ? *fmt : PcmFmtSpec());
     // (the envelope's and the contour's frame counts are refused here, before the stream has set up anything of its own)
     const int64_t A = fmt ? StreamOutput::check(*fmt, level, marks, stl_.joined) : 0;
+    SBV2_REQUIRE(!voice || fmt, "a voice stream needs an output format: begin it with the identity format (44100 Hz f32) instead of none");
+    SBV2_REQUIRE(!voice || (int64_t)voice->pivot.size() == fl_.n, "a voice stream needs one pivot per row");
+    svoice_upto_.clear();
+    if (voice) svoice_upto_ = stream_voice_upto(stl_, cfg_.hop(), chunk_frames, *fmt, voice->lookahead);
     constexpr int burst = kStreamBurst;   // (1 / 2 / 4 / 8 / 12 / 16 windows per replay measured in round 3: 2.62 / 1.88 / 1.64 / 1.41 / 1.39 / 1.47 ms per chunk)
     static_assert(kStreamBurst <= kStreamWinMax, "a replay's window table holds kStreamWinMax windows");
     const int64_t ncalls = (int64_t)stl_.calls.size();
@@ -1118,8 +1142,11 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
             if (!c) continue;
             const bool is_burst = want_burst && c == burst_.get();   // (with bursts the single-window plan decodes call 0 only)
             int64_t most = 0;
-            for (int64_t c0 = is_burst ? 1 : 0; c0 < (want_burst && !is_burst ? 1 : ncalls); c0 += c->nwin)
-                most = std::max(most, stl_.calls[std::min<int64_t>(c0 + c->nwin, ncalls) - 1].j1 - stl_.calls[c0].j0);
+            for (int64_t c0 = is_burst ? 1 : 0; c0 < (want_burst && !is_burst ? 1 : ncalls); c0 += c->nwin) {
+                const int64_t ce = std::min<int64_t>(c0 + c->nwin, ncalls) - 1;
+                if (voice) most = std::max(most, svoice_upto_[(size_t)ce] - (c0 ? svoice_upto_[(size_t)(c0 - 1)] : 0));   // (what the replay delivers)
+                else most = std::max(most, stl_.calls[ce].j1 - stl_.calls[c0].j0);
+            }
             c->fmt_cap = most + A;
             const size_t need = StreamOutput::slot_bytes(*fmt, flac, c->fmt_cap);
             cap = std::max(cap, c->fmt_cap);
@@ -1136,6 +1163,7 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
         }
         if (!sout_) sout_ = std::make_shared<StreamOutput>();
         sout_->begin(*fmt, flac, level, marks, used_host_, used_offs_, stl_.place.data(), cfg_.hop(), stl_.joined, cap, stream_);
+        if (voice) sout_->begin_voice(*voice, stl_.place, stl_.len, svoice_upto_, stream_);
         sformatted_ = true;
     }
     stream_enqueue(*chunk_, 0, 0);                 // the first chunk starts right behind the flow ...
@@ -1182,8 +1210,17 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
             sig.push_back(FmtSignal{k.j0, k.j1, total, w, w + 1});
             total += k.j1 - k.j0;
         }
+        // a voice stream: the shifter is fed every window's central samples clipped to the row, the samples the fetch's packed PCM holds
+        std::vector<StreamVoiceFeed> feed;
+        if (sout_->voice())
+            for (int w = 0; w < live; ++w) {
+                const StreamCall& k = stl_.calls[c0 + w];
+                const int64_t s0 = k.f0 * hop, s1 = std::min<int64_t>((k.f0 + c.chunk) * hop, stl_.len[k.row]);
+                feed.push_back(StreamVoiceFeed{k.row, s0, s1, c.pcm + ((size_t)w * c.W + halo) * hop});
+            }
         // ... and everything behind it, sink included (StreamOutput::push); the formatter's table slots: 0 / 1 = chunk_'s, 2 / 3 = burst_'s
-        sout_->push(pieces, sig, total, c0 + c.nwin >= ncalls, (&c == burst_.get() ? 2 : 0) + slot, c.host[slot], c.fmt_cap, c.out[slot], stream_);
+        sout_->push(pieces, sig, total, c0 + c.nwin >= ncalls, (&c == burst_.get() ? 2 : 0) + slot, c.host[slot], c.fmt_cap, c.out[slot], stream_,
+                    sout_->voice() ? &feed : nullptr, c0);
     } else {
         for (int w = 0; w < live; ++w) {   // a plain stream: one row at place 0, the windows' centres as they are
             const StreamCall& k = stl_.calls[c0 + w];
@@ -1198,6 +1235,8 @@ void VitsModel::stream_enqueue(ChunkPlan& c, int64_t c0, int slot) {
 int64_t VitsModel::stream_call_bound() const {
     int64_t most = 0;
     for (const StreamCall& k : stl_.calls) most = std::max(most, k.j1 - k.j0);
+    for (size_t c = 0; c < svoice_upto_.size(); ++c)   // (a voice stream: a row's last call also delivers what the look-ahead held back)
+        most = std::max(most, svoice_upto_[c] - (c ? svoice_upto_[c - 1] : 0));
     return sformatted_ ? sout_->call_bound(most) : most * (int64_t)sizeof(float);
 }
 

@@ -108,4 +108,68 @@ class Voice {
     double *d_tout_ = nullptr, *d_ratio_ = nullptr, *h_tout_ = nullptr, *h_ratio_ = nullptr;
 };
 
+// The shifter on a stream (sbv2_stream_voice in include/sbv2_hip.h): the two scales, the formant scale and the pivot the caller names for
+// every row in place of the row's mean f0.  Checked by stream_voice_spec.
+struct StreamVoiceSpec {
+    VoiceSpec voice;
+    FormantSpec formant;          // identity(): the plain gather
+    std::vector<double> pivot;    // [rows] Hz, each in [f0_min, f0_max]
+    int64_t lookahead = 0;        // A_v (stream_voice_lookahead)
+};
+// A_v = G + 2 W + X + tau_max + H div 2 with W = VoiceSpec::half, G = ceil(W / min(q, 1)) + 1 and X = ceil((max(q, 1) - 1) W), as
+// include/sbv2_hip.h derives it
+int64_t stream_voice_lookahead(const VoiceSpec& v, double formant_scale);
+// throws: everything voice_spec and formant_spec refuse, the identity (p = s = q = 1), a non-zero reserved, a NULL pivot with rows > 0, a pivot
+// that is not finite or lies outside [f0_min, f0_max]
+StreamVoiceSpec stream_voice_spec(int sample_rate, double pitch_scale, double intonation_scale, int64_t hop, double f0_min, double f0_max, double threshold,
+                                  double formant_scale, const double* pivot, int64_t rows, double reserved0, double reserved1);
+
+// The same shifter FED piece by piece (a stream's replays).  The rows' lengths are known at begin, and the fed samples and the shifted ones
+// are kept whole on the device (two buffers of the joined length), so no sample is carried; what a row carries from push to push is its two
+// Q32 phases, the voiced-run bit, its mark counts and how many synthesis marks are mapped (k_voice_marks_fed), besides the frame cursor the
+// host keeps by the estimator's completion rule.
+// A push is up to three launches on the caller's stream: the contour of the frames it completed (pitch_launch_fed: k_stream_pitch's frames,
+// the per-frame body of every estimator here), k_voice_marks_fed over them, and k_voice_gather / k_voice_gather_fmt over the outputs that
+// became final.  The delivery rule: with S samples of a row fed and the row not ended, max(0, S - A_v) of its outputs are final; the push
+// that feeds its last sample makes all of them final.  No atomics, nothing read back, nothing allocated after begin.
+// Bits: with the row's own mean as the pivot, Voice::run's, whatever the pushes.
+class StreamVoice {
+  public:
+    StreamVoice() = default;
+    ~StreamVoice();
+    StreamVoice(const StreamVoice&) = delete;
+    StreamVoice& operator=(const StreamVoice&) = delete;
+    // rows[i] = where row i lies in the two buffers of `span` floats; sp.pivot holds one entry per row.  period_in / voiced_in (HOST, as
+    // Voice::run takes them): the contour to use instead of the estimated one (the test hook).  Waits for s once (an earlier stream's buffers
+    // are reused) only if its uploads are still in flight or a buffer grows.  throws on rows outside the span, a pivot count that differs, a bad given contour.
+    void begin(const StreamVoiceSpec& sp, const VoiceRow* rows, int nrows, int64_t span, hipStream_t s, const double* period_in = nullptr,
+               const int32_t* voiced_in = nullptr);
+    // The next n samples of row `row` (device, f32; n = 0 allowed), rows in any order, each row's samples in order.  Returns how many of the
+    // row's outputs are final after it (final_after).
+    int64_t push(int row, const float* x, int64_t n, hipStream_t s);
+    int64_t final_after(int row, int64_t fed) const;   // the delivery rule
+    int64_t fed(int row) const { return rows_[(size_t)row].fed; }
+    int64_t lookahead() const { return sp_.lookahead; }
+    const float* out(int row) const { return y_ + rows_[(size_t)row].off; }   // the row's shifted samples, final ones valid
+    // status of every row -> the pinned mirror (0, or 1 = more marks than planned); valid once s is synchronised
+    void status_to_host(hipStream_t s);
+    int32_t status(int row) const { return h_count_[4 * row + 2]; }
+
+  private:
+    struct Row {
+        int64_t off, n, f_off, nf, fed, frames, done;   // samples fed, frames placed, outputs final
+    };
+    StreamVoiceSpec sp_;
+    std::vector<Row> rows_;
+    DeviceBuffer dev_;
+    PinnedBuffer host_;
+    char* d_ = nullptr;
+    size_t o_res_ = 0, o_period_ = 0, o_i64_ = 0, o_i32_ = 0, o_count_ = 0, o_state_ = 0, o_marks_ = 0;
+    int64_t nf_ = 0, ncap_ = 0;
+    float *x_ = nullptr, *y_ = nullptr;
+    int32_t* h_count_ = nullptr;
+    bool given_ = false;
+    hipEvent_t uploaded_ = nullptr;   // behind the last begin's uploads from the pinned buffer
+};
+
 }  // namespace sbv2

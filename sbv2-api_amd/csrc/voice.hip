@@ -88,6 +88,36 @@ __device__ inline void place_marks(int64_t phi, int64_t inc, int64_t len, int64_
     }
 }
 
+// T_f of a frame from the estimator's results: the parabolic refinement (the f64 expression of pitch_finish), limited to one sample
+__device__ inline double refined_period(double cm, double c0, double cp, int32_t lag, int32_t tau_max) {
+    const double den = cm - 2.0 * c0 + cp;
+    const bool both = lag - 1 >= 1 && lag + 1 <= tau_max;
+    double delta = den > 0.0 && both ? 0.5 * (cm - cp) / den : 0.0;
+    delta = fmin(fmax(delta, -1.0), 1.0);
+    return (double)lag + delta;
+}
+
+// the two increments of a voiced frame of period T whose target is g (before the clamp)
+__device__ inline void voiced_increments(double sr, double g_lo, double g_hi, double T, double g, int64_t* ia, int64_t* is) {
+    g = fmin(fmax(g, g_lo), g_hi);
+    const double Tp = sr / g;
+    *ia = llrint(kTwo32 / T);
+    *is = llrint(kTwo32 / Tp);
+}
+
+// the analysis mark nearest to t among ta[0, na), na >= 1, a tie to the earlier
+__device__ inline int32_t nearest_mark(const int32_t* ta, int32_t na, int32_t t) {
+    int32_t lo = 0, hi = na;   // the first analysis mark at or after t
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) / 2;
+        if (ta[mid] < t) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == 0) return 0;
+    if (lo == na) return na - 1;
+    return t - ta[lo - 1] <= ta[lo] - t ? lo - 1 : lo;
+}
+
 // The per-token phase of k_voice_marks_tok: fq / voiced of the row are written, m is its mean.  sh_q / sh_c are the kernel's reduction arrays.
 __device__ inline void token_ratios(const VoiceMarkArgs& a, const VoiceTokArgs& t, const VoiceRowDev& r, double m, int64_t* sh_q, int32_t* sh_c) {
     const int tid = threadIdx.x;
@@ -183,13 +213,7 @@ __device__ __forceinline__ void voice_marks_body(const VoiceMarkArgs& a, const V
             T = a.period[F];
             v = a.voiced[F] != 0;
         } else {
-            const double cm = a.c3[3 * F], c0 = a.c3[3 * F + 1], cp = a.c3[3 * F + 2];
-            const int32_t lag = a.lag[F];
-            const double den = cm - 2.0 * c0 + cp;
-            const bool both = lag - 1 >= 1 && lag + 1 <= a.tau_max;
-            double delta = den > 0.0 && both ? 0.5 * (cm - cp) / den : 0.0;
-            delta = fmin(fmax(delta, -1.0), 1.0);
-            T = (double)lag + delta;
+            T = refined_period(a.c3[3 * F], a.c3[3 * F + 1], a.c3[3 * F + 2], a.lag[F], a.tau_max);
             v = a.yvoiced[F] != 0;
             a.period[F] = T;
         }
@@ -221,10 +245,7 @@ __device__ __forceinline__ void voice_marks_body(const VoiceMarkArgs& a, const V
             const double T = a.period[F], f0 = a.sr / T;
             double g = a.p * (m + a.s * (f0 - m));
             if constexpr (kTok) g = t->ratio[F] * g;
-            g = fmin(fmax(g, a.g_lo), a.g_hi);
-            const double Tp = a.sr / g;
-            ia = llrint(kTwo32 / T);
-            is = llrint(kTwo32 / Tp);
+            voiced_increments(a.sr, a.g_lo, a.g_hi, T, g, &ia, &is);
         }
         a.inc_a[F] = ia;
         a.inc_s[F] = is;
@@ -271,32 +292,11 @@ __device__ __forceinline__ void voice_marks_body(const VoiceMarkArgs& a, const V
     __syncthreads();
     if (na == 0) return;
     // the nearest analysis mark of every synthesis mark, a tie to the earlier
-    for (int32_t j = tid; j < ns; j += kBlock) {
-        const int32_t t = ts[j];
-        int32_t lo = 0, hi = na;   // the first analysis mark at or after t
-        while (lo < hi) {
-            const int32_t mid = (lo + hi) / 2;
-            if (ta[mid] < t) lo = mid + 1;
-            else hi = mid;
-        }
-        int32_t m1;
-        if (lo == 0) m1 = 0;
-        else if (lo == na) m1 = na - 1;
-        else m1 = t - ta[lo - 1] <= ta[lo] - t ? lo - 1 : lo;
-        mp[j] = m1;
-    }
+    for (int32_t j = tid; j < ns; j += kBlock) mp[j] = nearest_mark(ta, na, ts[j]);
 }
 
 __global__ __launch_bounds__(kBlock) void k_voice_marks(const VoiceMarkArgs a) { voice_marks_body<false>(a, nullptr); }
 __global__ __launch_bounds__(kBlock) void k_voice_marks_tok(const VoiceMarkArgs a, const VoiceTokArgs t) { voice_marks_body<true>(a, &t); }
-
-struct VoiceGatherArgs {
-    const VoiceRowDev* rows;
-    const float* x;
-    float* y;
-    const int32_t *ta, *ts, *map, *count;
-    int32_t half;
-};
 
 // the first j in [0, n) with v[j] >= t (n if none)
 __device__ inline int32_t first_at_or_after(const int32_t* v, int32_t n, int64_t t) {
@@ -308,6 +308,141 @@ __device__ inline int32_t first_at_or_after(const int32_t* v, int32_t n, int64_t
     }
     return lo;
 }
+
+// The fed marks kernel (StreamVoice::push): ONE workgroup takes the frames [f0, f1) of one row that a push completed and goes on from the
+// row's carried state: the phases and the voiced-run bit behind frame f0 - 1 (state[0 .. 3)), the mark counts and the number of mapped
+// synthesis marks (count[0], [1], [3]).  a.rows / a.count point at THAT row's entries.  The target pivots about d.pivot, the caller's, where
+// k_voice_marks has the row's mean; every other expression is that kernel's (the helpers above), so with the mean's bits as the pivot the
+// lists are its lists.  The prefix over the frames is latency-bound, as k_track_path is: lanes stage kBlock frames' increments in LDS,
+// one lane walks them there and leaves phases and offsets in LDS, lanes write them out: the walk waits for LDS, never for memory.
+// Mapping: a synthesis mark is mapped once the first analysis mark at or after it is known, which is when it lies at or before the last
+// known analysis mark, or when the row's last frame is in (d.last): the bisection over the known list then answers what it answers over
+// the whole one.  More marks than planned: status is set, nothing more is written by this or any later push.
+struct VoiceFedArgs {
+    const PitchFrame* res;   // [NF] the estimator's results (not read with a given contour)
+    int64_t* state;          // [3] phi_a, phi_s at the last sample before frame f0; 1 if frame f0 - 1 is voiced
+    double pivot;
+    int64_t f0, f1;
+    int32_t last;            // f1 is the row's frame count
+};
+
+__global__ __launch_bounds__(kBlock) void k_voice_marks_fed(const VoiceMarkArgs a, const VoiceFedArgs d) {
+    __shared__ int64_t s_ia[kBlock], s_is[kBlock], s_pa[kBlock], s_ps[kBlock];
+    __shared__ int32_t s_v[kBlock], s_oa[kBlock], s_os[kBlock];
+    __shared__ int64_t s_st[5];   // phi_a, phi_s, voiced before, n_a, n_s
+    __shared__ int32_t s_n[3];    // status, mapped before, mapped after
+    const VoiceRowDev r = a.rows[0];
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        s_st[0] = d.state[0];
+        s_st[1] = d.state[1];
+        s_st[2] = d.state[2];
+        s_st[3] = a.count[0];
+        s_st[4] = a.count[1];
+        s_n[0] = a.count[2];
+        s_n[1] = a.count[3];
+    }
+    __syncthreads();
+    if (s_n[0]) return;   // (uniform) an earlier push found more marks than planned
+    for (int64_t base = d.f0; base < d.f1; base += kBlock) {
+        const int64_t f = base + tid, F = r.f_off + f;
+        if (f < d.f1) {
+            double T;
+            int32_t v;
+            if (a.given) {
+                T = a.period[F];
+                v = a.voiced[F] != 0;
+            } else {
+                const PitchFrame pf = d.res[F];
+                T = refined_period(pf.c3[0], pf.c3[1], pf.c3[2], pf.lag, a.tau_max);
+                v = pf.voiced != 0;
+                a.period[F] = T;
+            }
+            a.voiced[F] = v;
+            int64_t ia = a.inc_u, is = a.inc_u;
+            if (v) voiced_increments(a.sr, a.g_lo, a.g_hi, T, a.p * (d.pivot + a.s * (a.sr / T - d.pivot)), &ia, &is);
+            a.inc_a[F] = ia;
+            a.inc_s[F] = is;
+            s_ia[tid] = ia;
+            s_is[tid] = is;
+            s_v[tid] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {   // k_voice_marks' walk, from the carried state
+            int64_t pa = s_st[0], ps = s_st[1], ca = s_st[3], cs = s_st[4];
+            bool prev = s_st[2] != 0;
+            const int cn = (int)min((int64_t)kBlock, d.f1 - base);
+            for (int i = 0; i < cn; ++i) {
+                const int64_t len = min(a.hop, r.n - (base + i) * a.hop), ia = s_ia[i], is = s_is[i];
+                const bool v = s_v[i] != 0;
+                if (!v || !prev) ps = pa;
+                s_pa[i] = pa;
+                s_ps[i] = ps;
+                s_oa[i] = (int32_t)min(ca, r.cap);
+                s_os[i] = (int32_t)min(cs, r.cap);
+                ca += ((pa + len * ia) >> 32) - (pa >> 32);
+                cs += ((ps + len * is) >> 32) - (ps >> 32);
+                pa += len * ia;
+                ps += len * is;
+                prev = v;
+            }
+            s_st[0] = pa;
+            s_st[1] = ps;
+            s_st[2] = prev;
+            s_st[3] = ca;
+            s_st[4] = cs;
+        }
+        __syncthreads();
+        if (f < d.f1) {
+            a.phi_a[F] = s_pa[tid];
+            a.phi_s[F] = s_ps[tid];
+            a.off_a[F] = s_oa[tid];
+            a.off_s[F] = s_os[tid];
+        }
+        __syncthreads();   // (the next round writes the staged frames again)
+    }
+    const int64_t ca = s_st[3], cs = s_st[4];
+    if (ca > r.cap || cs > r.cap) {   // (uniform) the counts stay where they were: the gather reads nothing beyond them
+        if (tid == 0) a.count[2] = 1;
+        return;
+    }
+    const int32_t na = (int32_t)ca, ns = (int32_t)cs;
+    int32_t* ta = a.ta + r.m_off;
+    int32_t* ts = a.ts + r.m_off;
+    int32_t* mp = a.map + r.m_off;
+    for (int64_t f = d.f0 + tid; f < d.f1; f += kBlock) {   // (frame f's phases were written by this lane)
+        const int64_t F = r.f_off + f, len = min(a.hop, r.n - f * a.hop);
+        place_marks(a.phi_a[F], a.inc_a[F], len, f * a.hop, ta + a.off_a[F]);
+        place_marks(a.phi_s[F], a.inc_s[F], len, f * a.hop, ts + a.off_s[F]);
+    }
+    __syncthreads();
+    const int32_t mapped = s_n[1];
+    if (tid == 0) {
+        int32_t upto = mapped;
+        if (na > 0) upto = d.last ? ns : max(mapped, first_at_or_after(ts, ns, (int64_t)ta[na - 1] + 1));
+        s_n[2] = upto;
+    }
+    __syncthreads();
+    const int32_t upto = s_n[2];
+    for (int32_t j = mapped + tid; j < upto; j += kBlock) mp[j] = nearest_mark(ta, na, ts[j]);
+    if (tid == 0) {
+        d.state[0] = s_st[0];
+        d.state[1] = s_st[1];
+        d.state[2] = s_st[2];
+        a.count[0] = na;
+        a.count[1] = ns;
+        a.count[3] = upto;
+    }
+}
+
+struct VoiceGatherArgs {
+    const VoiceRowDev* rows;
+    const float* x;
+    float* y;
+    const int32_t *ta, *ts, *map, *count;
+    int32_t half;
+    int64_t k0, k1;   // the launch covers the outputs [k0, min(k1, n)) of every row (a whole row: 0 and any k1 >= n)
+};
 
 struct VoiceFmtArgs {   // what k_voice_gather_fmt needs besides
     const int32_t* voiced;   // [NF] the contour the marks were placed by
@@ -323,11 +458,11 @@ __device__ __forceinline__ void voice_gather_body(const VoiceGatherArgs& a, cons
     __shared__ int32_t s_ts[kBlock], s_ta[kBlock], s_L[kBlock], s_R[kBlock], s_edge[kBlock];
     __shared__ int32_t s_range[2];
     const VoiceRowDev r = a.rows[blockIdx.y];
-    const int64_t t0 = (int64_t)blockIdx.x * Voice::kTile;
-    if (t0 >= r.n) return;   // (uniform: this row has fewer tiles than the longest)
+    const int64_t t0 = a.k0 + (int64_t)blockIdx.x * Voice::kTile, end = min(r.n, a.k1);
+    if (t0 >= end) return;   // (uniform: this row has fewer tiles than the longest)
     const int tid = threadIdx.x;
-    const int64_t n = r.n, k = t0 + tid, t1 = min(t0 + Voice::kTile, n);
-    const bool mine = k < n;
+    const int64_t n = r.n, k = t0 + tid, t1 = min(t0 + Voice::kTile, end);
+    const bool mine = k < end;
     const float* x = a.x + r.off;
     float* y = a.y + r.off;
     const int32_t na = a.count[4 * blockIdx.y], ns = a.count[4 * blockIdx.y + 1];
@@ -622,6 +757,8 @@ float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows,
         g.map = m.map;
         g.count = m.count;
         g.half = sp.half;
+        g.k0 = 0;
+        g.k1 = longest;
         const dim3 grid((unsigned)((longest + kTile - 1) / kTile), (unsigned)nrows);
         if (fm) {
             VoiceFmtArgs f{};
@@ -638,6 +775,194 @@ float* Voice::run(const float* x, int64_t span, const VoiceRow* rows, int nrows,
     // (the status of every row is looked at by the caller after its synchronisation)
     HIP_CHECK(hipMemcpyAsync(h_count_, d_count_, 16 * (size_t)nrows, hipMemcpyDeviceToHost, s));
     return y;
+}
+
+// ---- the fed shifter (StreamVoice, voice.h) ----
+int64_t stream_voice_lookahead(const VoiceSpec& v, double formant_scale) {
+    const int64_t W = v.half, G = (int64_t)std::ceil((double)W / std::min(formant_scale, 1.0)) + 1;
+    const int64_t X = (int64_t)std::ceil((std::max(formant_scale, 1.0) - 1.0) * (double)W);   // an unvoiced grain is read up to q times as far
+    return G + 2 * W + X + v.pitch.tau_max + v.pitch.hop / 2;
+}
+
+StreamVoiceSpec stream_voice_spec(int sample_rate, double pitch_scale, double intonation_scale, int64_t hop, double f0_min, double f0_max, double threshold,
+                                  double formant_scale, const double* pivot, int64_t rows, double reserved0, double reserved1) {
+    SBV2_REQUIRE(reserved0 == 0.0 && reserved1 == 0.0, "sbv2_stream_voice.reserved must be 0");   // (a NaN fails)
+    StreamVoiceSpec sp;
+    sp.voice = voice_spec(sample_rate, pitch_scale, intonation_scale, hop, f0_min, f0_max, threshold);
+    sp.formant = formant_spec(formant_scale, 0.0, sp.voice);
+    SBV2_REQUIRE(!(sp.voice.identity() && sp.formant.identity()),
+                 "a stream voice with pitch_scale = intonation_scale = formant_scale = 1 shifts nothing: begin the stream without a voice");
+    SBV2_REQUIRE(rows >= 0 && (pivot || rows == 0), "sbv2_stream_voice.pivot_hz must not be NULL (one entry per row: the f0 the intonation scale pivots about)");
+    const double lo = 2.0 * sp.voice.g_lo, hi = sp.voice.g_hi / 2.0;   // (f0_min, f0_max after the defaults: halving and doubling are exact)
+    for (int64_t i = 0; i < rows; ++i)   // (a NaN fails both comparisons)
+        SBV2_REQUIRE(pivot[i] >= lo && pivot[i] <= hi, "sbv2_stream_voice.pivot_hz[" + std::to_string(i) + "] must be finite and in [f0_min, f0_max] = [" +
+                                                           std::to_string(lo) + ", " + std::to_string(hi) + "] Hz: " + std::to_string(pivot[i]));
+    sp.pivot.assign(pivot, pivot + rows);
+    sp.lookahead = stream_voice_lookahead(sp.voice, formant_scale);
+    return sp;
+}
+
+void StreamVoice::begin(const StreamVoiceSpec& sp, const VoiceRow* rows, int nrows, int64_t span, hipStream_t s, const double* period_in,
+                        const int32_t* voiced_in) {
+    SBV2_REQUIRE(nrows >= 0 && nrows <= 65535 && span >= 0 && (nrows == 0 || rows), "stream voice: bad rows");
+    SBV2_REQUIRE((int64_t)sp.pivot.size() == nrows, "stream voice: one pivot per row");
+    SBV2_REQUIRE(!period_in == !voiced_in, "stream voice: period_in and voiced_in are given together or not at all");
+    sp_ = sp;
+    const VoiceSpec& v = sp_.voice;
+    const int64_t hop = v.pitch.hop;
+    std::vector<VoiceRowDev> rd((size_t)nrows);
+    rows_.assign((size_t)nrows, Row{});
+    int64_t NF = 0, NCAP = 0;
+    for (int i = 0; i < nrows; ++i) {
+        SBV2_REQUIRE(rows[i].n >= 0 && rows[i].n < (1 << 30) && rows[i].off >= 0 && rows[i].off + rows[i].n <= span,
+                     "stream voice: row " + std::to_string(i) + " is outside the buffer or longer than 2^30 samples");
+        rd[i].off = rows[i].off;
+        rd[i].n = rows[i].n;
+        rd[i].f_off = NF;
+        rd[i].nf = pitch_frames(rows[i].n, hop);
+        rd[i].m_off = NCAP;
+        rd[i].cap = rows[i].n / std::min(v.min_a, v.min_s) + rd[i].nf + 2;
+        rows_[(size_t)i] = Row{rd[i].off, rd[i].n, NF, rd[i].nf, 0, 0, 0};
+        NF += rd[i].nf;
+        NCAP += rd[i].cap;
+    }
+    SBV2_REQUIRE(NF < (1 << 30) && NCAP < (int64_t(1) << 31), "stream voice: too many frames or marks in one stream");
+    if (period_in)
+        for (int64_t f = 0; f < NF; ++f)
+            SBV2_REQUIRE(!voiced_in[f] || (period_in[f] >= v.pitch.tau_min - 1 && period_in[f] <= v.pitch.tau_max + 1),
+                         "voice: period_in of voiced frame " + std::to_string(f) + " is outside [tau_min - 1, tau_max + 1]: " + std::to_string(period_in[f]));
+    nf_ = NF;
+    ncap_ = NCAP;
+    given_ = period_in != nullptr;
+    // device: rows | results | period | inc_a inc_s phi_a phi_s | voiced off_a off_s | count | state | ta ts map | x | y   (8-byte parts first)
+    const size_t nF = (size_t)NF, nC = (size_t)NCAP, nR = (size_t)nrows, nS = (size_t)std::max<int64_t>(span, 16);
+    o_res_ = round_up64(sizeof(VoiceRowDev) * nR, 64);
+    o_period_ = o_res_ + sizeof(PitchFrame) * nF;
+    o_i64_ = o_period_ + 8 * nF;
+    o_i32_ = o_i64_ + 32 * nF;
+    o_count_ = round_up64(o_i32_ + 12 * nF, 64);
+    o_state_ = o_count_ + round_up64(16 * nR, 64);
+    o_marks_ = o_state_ + round_up64(24 * nR, 64);
+    const size_t o_x = round_up64(o_marks_ + 12 * nC, 64), o_y = o_x + round_up64(4 * nS, 64), bytes = o_y + 4 * nS;
+    // pinned: rows | period | voiced (the upload) ; count (the mirror)
+    const size_t h_period = round_up64(sizeof(VoiceRowDev) * nR, 64), h_voiced = h_period + 8 * nF, h_count = round_up64(h_voiced + 4 * nF, 64),
+                 h_bytes = h_count + std::max<size_t>(16 * nR, 64);
+    d_ = static_cast<char*>(dev_.reserve(bytes, std::max<size_t>(bytes + bytes / 4, 65536), s));
+    char* h = static_cast<char*>(host_.reserve(h_bytes, std::max<size_t>(h_bytes * 2, 4096), s));
+    // an earlier stream's uploads out of the pinned buffer are done (its event has long fired: no wait on the path to the first chunk)
+    if (uploaded_) HIP_CHECK(hipEventSynchronize(uploaded_));
+    x_ = reinterpret_cast<float*>(d_ + o_x);
+    y_ = reinterpret_cast<float*>(d_ + o_y);
+    h_count_ = reinterpret_cast<int32_t*>(h + h_count);
+    if (nrows == 0) return;
+    std::memcpy(h, rd.data(), sizeof(VoiceRowDev) * nR);
+    HIP_CHECK(hipMemcpyAsync(d_, h, sizeof(VoiceRowDev) * nR, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(d_ + o_count_, 0, o_marks_ - o_count_, s));   // counts, status and every row's carried state
+    if (given_ && NF > 0) {
+        std::memcpy(h + h_period, period_in, 8 * nF);
+        std::memcpy(h + h_voiced, voiced_in, 4 * nF);
+        HIP_CHECK(hipMemcpyAsync(d_ + o_period_, h + h_period, 8 * nF, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(d_ + o_i32_, h + h_voiced, 4 * nF, hipMemcpyHostToDevice, s));
+    }
+    if (!uploaded_) HIP_CHECK(hipEventCreateWithFlags(&uploaded_, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(uploaded_, s));
+}
+
+StreamVoice::~StreamVoice() {
+    if (uploaded_) (void)hipEventDestroy(uploaded_);
+}
+
+int64_t StreamVoice::final_after(int row, int64_t fed) const {
+    const Row& r = rows_[(size_t)row];
+    return fed >= r.n ? r.n : std::max<int64_t>(0, fed - sp_.lookahead);
+}
+
+int64_t StreamVoice::push(int row, const float* x, int64_t n, hipStream_t s) {
+    SBV2_REQUIRE(row >= 0 && row < (int)rows_.size(), "internal: a voice push of a row the stream does not have");
+    Row& r = rows_[(size_t)row];
+    SBV2_REQUIRE(n >= 0 && r.fed + n <= r.n, "internal: a voice push of " + std::to_string(n) + " samples behind " + std::to_string(r.fed) + " of " +
+                                                 std::to_string(r.n) + " of row " + std::to_string(row));
+    const VoiceSpec& v = sp_.voice;
+    if (n > 0) {
+        SBV2_REQUIRE(x, "internal: no samples to push");
+        HIP_CHECK(hipMemcpyAsync(x_ + r.off + r.fed, x, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    }
+    r.fed += n;
+    const int64_t frames = pitch_frames_complete(v.pitch, r.n, r.fed);
+    const size_t nF = (size_t)nf_, nC = (size_t)ncap_;
+    const VoiceRowDev* d_rows = reinterpret_cast<const VoiceRowDev*>(d_) + row;
+    int32_t* count = reinterpret_cast<int32_t*>(d_ + o_count_) + 4 * row;
+    int32_t* ta = reinterpret_cast<int32_t*>(d_ + o_marks_);
+    int32_t* voiced = reinterpret_cast<int32_t*>(d_ + o_i32_);
+    if (frames > r.frames) {
+        PitchFrame* res = reinterpret_cast<PitchFrame*>(d_ + o_res_);
+        if (!given_) pitch_launch_fed(x_ + r.off, r.fed, r.n, v.pitch, r.frames, frames - r.frames, res + r.f_off, s);
+        VoiceMarkArgs m{};
+        m.rows = d_rows;
+        m.given = given_;
+        m.period = reinterpret_cast<double*>(d_ + o_period_);
+        m.voiced = voiced;
+        m.inc_a = reinterpret_cast<int64_t*>(d_ + o_i64_);
+        m.inc_s = m.inc_a + nF;
+        m.phi_a = m.inc_s + nF;
+        m.phi_s = m.phi_a + nF;
+        m.off_a = voiced + nF;
+        m.off_s = m.off_a + nF;
+        m.ta = ta;
+        m.ts = ta + nC;
+        m.map = m.ts + nC;
+        m.count = count;
+        m.sr = (double)v.pitch.sample_rate;
+        m.p = v.pitch_scale;
+        m.s = v.intonation_scale;
+        m.g_lo = v.g_lo;
+        m.g_hi = v.g_hi;
+        m.inc_u = v.inc_u;
+        m.hop = v.pitch.hop;
+        m.tau_max = v.pitch.tau_max;
+        VoiceFedArgs d{};
+        d.res = res;
+        d.state = reinterpret_cast<int64_t*>(d_ + o_state_) + 3 * row;
+        d.pivot = sp_.pivot[(size_t)row];
+        d.f0 = r.frames;
+        d.f1 = frames;
+        d.last = frames == r.nf;
+        hipLaunchKernelGGL(k_voice_marks_fed, dim3(1), dim3(kBlock), 0, s, m, d);
+        HIP_CHECK(hipGetLastError());
+        r.frames = frames;
+    }
+    const int64_t fin = final_after(row, r.fed);
+    if (fin > r.done) {
+        VoiceGatherArgs g{};
+        g.rows = d_rows;
+        g.x = x_;
+        g.y = y_;
+        g.ta = ta;
+        g.ts = ta + nC;
+        g.map = g.ts + nC;
+        g.count = count;
+        g.half = v.half;
+        g.k0 = r.done;
+        g.k1 = fin;
+        const dim3 grid((unsigned)((fin - r.done + Voice::kTile - 1) / Voice::kTile), 1);
+        if (!sp_.formant.identity()) {
+            VoiceFmtArgs f{};
+            f.voiced = voiced;
+            f.q = sp_.formant.scale;
+            f.hop = v.pitch.hop;
+            f.half = sp_.formant.half;
+            hipLaunchKernelGGL(k_voice_gather_fmt, grid, dim3(kBlock), 0, s, g, f);
+        } else {
+            hipLaunchKernelGGL(k_voice_gather, grid, dim3(kBlock), 0, s, g);
+        }
+        HIP_CHECK(hipGetLastError());
+        r.done = fin;
+    }
+    return fin;
+}
+
+void StreamVoice::status_to_host(hipStream_t s) {
+    if (!rows_.empty()) HIP_CHECK(hipMemcpyAsync(h_count_, d_ + o_count_, 16 * rows_.size(), hipMemcpyDeviceToHost, s));
 }
 
 void Voice::results_to_host(hipStream_t s) {

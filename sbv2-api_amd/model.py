@@ -755,6 +755,77 @@ def debug_voice_formant(rows, sample_rate: int, voice: Voice, formant: Formant, 
     return debug_voice_shift(rows, sample_rate, voice, period, voiced, device, formant=formant)
 
 
+class StreamVoice:
+    """Pitch, intonation and formant scale of a request STREAM (struct sbv2_stream_voice, include/sbv2_hip.h states it): the shifter of Voice
+    and Formant fed chunk by chunk on the device.  pivot_hz: the f0 the intonation scale pivots about in place of the row's mean, which a stream
+    cannot know ahead: one value for every row or one per row, each in [f0_min, f0_max]; read it from a /synthesize_marks answer of the same
+    voice.  The identity (all three scales 1) is refused by the library: begin the stream without a voice."""
+
+    def __init__(self, pitch_scale: float = 1.0, intonation_scale: float = 1.0, formant_scale: float = 1.0, pivot_hz=None, hop: int = 0,
+                 f0_min: float = 0.0, f0_max: float = 0.0, threshold: float = 0.0):
+        self.voice = Voice(pitch_scale, intonation_scale, hop, f0_min, f0_max, threshold)
+        self.formant_scale = float(formant_scale)
+        self.pivot_hz = None if pivot_hz is None else np.ascontiguousarray(np.asarray(pivot_hz, np.float64).reshape(-1))
+
+    def c_struct(self, rows: int):
+        """(sbv2_stream_voice, the pivot array it points to) for a stream of `rows` rows: a scalar pivot is repeated, None stays NULL."""
+        piv = self.pivot_hz
+        if piv is not None:
+            if piv.size == 1 and rows != 1:
+                piv = np.ascontiguousarray(np.repeat(piv, max(rows, 1)))
+            if piv.size != rows:
+                raise Sbv2Error(f"pivot_hz must be one value or one per row ({rows}), not {piv.size}")
+        return _lib.Sbv2StreamVoice(self.voice.c, self.formant_scale, _f64p(piv) if piv is not None else None, (C.c_double * 2)(0.0, 0.0)), piv
+
+    def __repr__(self):
+        return f"StreamVoice({self.voice.pitch_scale}, {self.voice.intonation_scale}, {self.formant_scale}, pivot_hz={self.pivot_hz})"
+
+
+def stream_voice_lookahead(voice: StreamVoice, sample_rate: int = 44100) -> int:
+    """A_v: the native samples of a row that must follow a shifted sample before it is final (sbv2_stream_voice_lookahead; host only)."""
+    c, _keep = voice.c_struct(0 if voice.pivot_hz is None else voice.pivot_hz.size)
+    a = int(_lib.lib().sbv2_stream_voice_lookahead(C.byref(c), int(sample_rate)))
+    if a < 0:
+        raise Sbv2Error(_lib.lib().sbv2_last_error().decode())
+    return a
+
+
+def stream_voice_timeline(frames, gaps, hop: int, chunk_frames: int, voice: StreamVoice, fmt: PcmFormat | None = None):
+    """The samples every call of a voice stream without a level delivers (sbv2_stream_voice_timeline; host only)."""
+    fr, fp = _i64(frames)
+    gp_a, gp = _i64(gaps)
+    n = int(fr.size)
+    cap = int(sum(-(-int(f) // max(int(chunk_frames), 1)) for f in fr if f > 0)) + 1
+    calls, ncalls = np.zeros(cap, np.int64), C.c_int64()
+    c, _keep = voice.c_struct(0 if voice.pivot_hz is None else voice.pivot_hz.size)
+    check(_lib.lib().sbv2_stream_voice_timeline(fp, gp, n, int(hop), int(chunk_frames), C.byref(fmt.c) if fmt is not None else None, C.byref(c),
+                                                calls.ctypes.data_as(i64p), cap, C.byref(ncalls)))
+    return calls[:ncalls.value]
+
+
+def debug_voice_stream(x, cuts, sample_rate: int, voice: StreamVoice, period=None, voiced=None, device: int = 0):
+    """Test hook: the fed shifter on one float32 row cut at `cuts` into len(cuts) + 1 pushes (sbv2_debug_voice_stream) -> (y, per_push): the
+    pushes' final samples back to back and their counts.  period / voiced: the contour to use instead of the estimated one."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if x.dtype != np.float32:
+        raise Sbv2Error(f"the shifter takes float32 rows, not {x.dtype}")
+    ct, cp = _i64(cuts)
+    i32p = C.POINTER(C.c_int32)
+    pin = vin = None
+    if (period is None) != (voiced is None):
+        raise Sbv2Error("period and voiced are given together or not at all")
+    if period is not None:
+        pin = np.concatenate([np.asarray(period, np.float64).reshape(-1), [0.0]])
+        vin = np.concatenate([np.asarray(voiced).reshape(-1), [0]]).astype(np.int32)
+    c, _keep = voice.c_struct(1)
+    y, per = np.zeros(x.size + 1, np.float32), np.zeros(ct.size + 1, np.int64)
+    check(_lib.lib().sbv2_debug_voice_stream(int(device), x.ctypes.data_as(_lib.f32p) if x.size else None, x.size, cp if ct.size else None, ct.size,
+                                             int(sample_rate), C.byref(c), _f64p(pin) if pin is not None else None,
+                                             vin.ctypes.data_as(i32p) if vin is not None else None, y.ctypes.data_as(_lib.f32p),
+                                             per.ctypes.data_as(i64p)))
+    return y[:x.size].copy(), per
+
+
 def debug_voice_tokens(rows, sample_rate: int, voice: Voice, tok_ends, token_pitch: TokenPitch, period=None, voiced=None, device: int = 0):
     """Test hook: the shifter with a token table on host rows (sbv2_debug_voice_tokens), always through its kernels.  rows, period, voiced as
     for debug_voice_shift; tok_ends: per row the ascending end positions of its tokens in samples (one array = one row); token_pitch: the
@@ -1317,11 +1388,21 @@ class StreamHandle:
     estimated on the device chunk by chunk as well (sbv2_stream_begin_request_pitch): n_pitch frames in all, next_pitch() hands out the ones the
     pieces taken so far completed, with the bits of debug_pitch over the whole delivered signal.
     assist: an utterance of a LIST may carry assist_ids / assist_weight (sbv2_stream_begin_request_assist, as Pipeline.run takes them); a single
-    utterance dict that carries them is refused, gaps= named: a request of one row serves it."""
+    utterance dict that carries them is refused, gaps= named: a request of one row serves it.
+    voice (a StreamVoice: the three scales and the pivot): the voice is shifted on the device ahead of the formatter, carried chunk by chunk
+    (sbv2_stream_begin_request_voice); delivery runs stream_voice_lookahead native samples behind within a row, so next() returns what the
+    chunk completed, possibly nothing, and a row's last chunk the rest; stream_voice_timeline gives the counts ahead.  A single utterance
+    runs as the request stream with gaps=[0]."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
                  level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, track=None,
-                 **kw):
+                 voice: "StreamVoice | None" = None, token_pitch=None, **kw):
+        if token_pitch is not None:
+            raise Sbv2Error("a stream takes no token_pitch: a token's mean f0 needs all of the token's frames and the row's mean, and a stream hands "
+                            "its samples out before they exist; fetch the whole signal instead (Pipeline.fetch_request(token_pitch=), /synthesize, "
+                            "/synthesize_marks)")
+        if voice is not None and not hasattr(_lib.lib(), "sbv2_stream_begin_request_voice"):
+            raise Sbv2Error("this library has no sbv2_stream_begin_request_voice: a stream cannot shift the voice (it is never served unshifted)")
         if track is not None:
             raise Sbv2Error("a stream's contour is not tracked: one best path needs every frame of the signal, and a stream hands its frames out "
                             "as they complete; fetch the whole signal instead (Pipeline.fetch_request(track=), /synthesize, /synthesize_marks)")
@@ -1329,7 +1410,8 @@ class StreamHandle:
         self.request = isinstance(utt, (list, tuple))
         self.levels, self.env_hop, self.n_tokens, self.n_env, self._marks_buf = bool(levels), int(env_hop), 0, 0, None
         self.pitch, self.n_pitch, self._pitch_buf = pitch, 0, None
-        if (self.levels or self.env_hop or pitch is not None) and not self.request:
+        self.voice = voice
+        if (self.levels or self.env_hop or pitch is not None or voice is not None) and not self.request:
             if gaps is not None:
                 raise Sbv2Error("gaps= belongs to a stream over a list of utterances")
             utt, gaps, self.request = [utt], [0], True
@@ -1351,17 +1433,22 @@ class StreamHandle:
             rq = _lib.Sbv2StreamRequest(gp, C.pointer(fmt.c) if fmt is not None else None, C.pointer(level.c) if level is not None else None,
                                         int(self.flac), 0)
             opts = C.byref(self.b.opts) if self.b.opts is not None else None
-            if self.b.assist is not None:
-                # an assisted row: the one entry that takes it, with the levels and the pitch it may carry (NULL: without)
+            if self.b.assist is not None or voice is not None:
+                # an assisted row or a shifted voice: the one entry that takes them, with the levels and the pitch the stream may carry (NULL: without)
                 on = self.levels or self.env_hop
                 lv = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)) if on or pitch is not None else None
                 sp = None
                 if pitch is not None:
                     sp = _lib.Sbv2StreamPitch(pitch.hop if -2 ** 31 <= pitch.hop < 2 ** 31 else 0, 0, pitch.f0_min, pitch.f0_max, pitch.threshold)
                 nt, ne, nq = C.c_int64(), C.c_int64(), C.c_int64()
-                check(l.sbv2_stream_begin_request_assist(args[0], args[1], args[2], opts, C.byref(self.b.assist), *args[3:], C.byref(rq),
-                                                         C.byref(lv) if lv is not None else None, C.byref(sp) if sp is not None else None,
-                                                         C.byref(self.h), C.byref(tot), C.byref(nt), C.byref(ne), C.byref(nq)))
+                head = (args[0], args[1], args[2], opts, C.byref(self.b.assist) if self.b.assist is not None else None, *args[3:], C.byref(rq),
+                        C.byref(lv) if lv is not None else None, C.byref(sp) if sp is not None else None)
+                tail = (C.byref(self.h), C.byref(tot), C.byref(nt), C.byref(ne), C.byref(nq))
+                if voice is not None:
+                    cv, _keep = voice.c_struct(len(utt))
+                    check(l.sbv2_stream_begin_request_voice(*head, C.byref(cv), *tail))
+                else:
+                    check(l.sbv2_stream_begin_request_assist(*head, *tail))
                 self.n_tokens, self.n_env, self.n_pitch = nt.value, ne.value, nq.value
             elif pitch is not None:
                 lv, nt, ne, nq = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)), C.c_int64(), C.c_int64(), C.c_int64()
@@ -1408,7 +1495,7 @@ class StreamHandle:
 
     def next(self):
         n = C.c_int64()
-        if self.level is not None:
+        if self.level is not None or self.voice is not None:   # (delivery runs behind the chunks: what the call delivers, what it consumed)
             out = C.c_int64()
             check(_lib.lib().sbv2_stream_next_level(self.h, self.buf.ctypes.data_as(C.c_void_p), self.buf.nbytes, C.byref(out), C.byref(n)))
             self.samples_taken += n.value

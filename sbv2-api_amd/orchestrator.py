@@ -86,7 +86,8 @@ class SynthesizeOptions:
                  normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
                  pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False,
                  compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0, token_pitch=None, token_pitch_kind="hz",
-                 token_pitch_smooth=2, formant_scale=1.0, assist=None, assist_weight=0.7):
+                 token_pitch_smooth=2, formant_scale=1.0, assist=None, assist_weight=0.7, voice_pivot_hz=None):
+        self.voice_pivot_hz = check_voice_pivot(voice_pivot_hz)
         # (a str is a text still to be parsed: holder.TTSModelHolder does that with its parse_text; the routes below refuse it as it is)
         self.assist_text = assist if isinstance(assist, str) and assist else None
         self.assist_ids, self.assist_weight = check_assist(None if isinstance(assist, str) else assist, assist_weight)
@@ -127,6 +128,42 @@ class SynthesizeOptions:
         self.envelope_hz = envelope_hz
         self.gain_db = gain_db
         self.pitch_hz, self.pitch_min_hz, self.pitch_max_hz = pitch_hz, pitch_min_hz, pitch_max_hz
+
+
+def check_voice_pivot(pivot):
+    """voice_pivot_hz of a request: None, or the f0 in Hz that intonation_scale pivots about on a STREAM in place of the mean a stream cannot
+    know (model.StreamVoice): one number for every sentence or a list with one per live sentence, each finite and in [70, 600], the shifter's
+    range.  It is what opens pitch_scale / intonation_scale / formant_scale on the stream routes; the whole-signal routes refuse it.  Returns
+    None, a float or a list of floats."""
+    if pivot is None:
+        return None
+    many = isinstance(pivot, (list, tuple))
+    values = list(pivot) if many else [pivot]
+    if many and not values:
+        raise model.Sbv2Error("voice_pivot_hz must be a number or a non-empty list of numbers (Hz)")
+    for v in values:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 70.0 <= v <= 600.0:   # (a NaN fails the comparison)
+            raise model.Sbv2Error(f"voice_pivot_hz must be finite and in [70, 600] Hz (the shifter's f0 range): {v!r}")
+    return [float(v) for v in values] if many else float(pivot)
+
+
+def refuse_voice_pivot(options, what: str):
+    """voice_pivot_hz where a whole signal is shifted: refused, the row's own mean f0 is the pivot there; the stream routes take it."""
+    if getattr(options, "voice_pivot_hz", None) is not None:
+        raise model.Sbv2Error(f"voice_pivot_hz names the pivot of a STREAM's intonation_scale: {what} shifts a whole signal about its own mean f0; "
+                              "leave it out here, or ask /synthesize_stream, /synthesize_stream_marks (easy_synthesize_stream)")
+
+
+def stream_voice_options(options, rows: int):
+    """The model.StreamVoice of a stream request: None when no scale is away from 1 (the stream is then the call it always was, pivot or not);
+    otherwise the three scales about options.voice_pivot_hz, a list holding one pivot per live sentence."""
+    p, s, q = (float(getattr(options, k, 1.0)) for k in ("pitch_scale", "intonation_scale", "formant_scale"))
+    if p == 1.0 and s == 1.0 and q == 1.0:
+        return None
+    pivot = getattr(options, "voice_pivot_hz", None)
+    if isinstance(pivot, list) and len(pivot) != rows:
+        raise model.Sbv2Error(f"voice_pivot_hz holds {len(pivot)} pivots, the stream has {rows} sentence(s): name one number, or one per live sentence")
+    return model.StreamVoice(p, s, q, pivot)
 
 
 def check_assist(assist, weight):
@@ -339,6 +376,7 @@ class RequestPlan:
 
     def __init__(self, sentences, style_vectors, style_id, speaker_id, options):
         options = options or SynthesizeOptions()
+        refuse_voice_pivot(options, "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks, the batcher)")
         if options.gain_db is not None:
             raise model.Sbv2Error("gain_db is the level control of a stream (/synthesize_stream): a whole signal is measured, set loudness (LUFS) instead")
         if options.loudness is not None and options.normalize:
@@ -427,13 +465,16 @@ def require_formant(pipe, options):
 
 
 def refuse_voice(options, what: str):
-    """pitch_scale / intonation_scale / formant_scale where rows leave chunk by chunk: refused, with the routes that shift a whole signal."""
+    """pitch_scale / intonation_scale / formant_scale where rows leave chunk by chunk, WITHOUT voice_pivot_hz: refused, with the routes that
+    shift a whole signal.  With the pivot named the stream shifts them itself (stream_voice_options)."""
+    if getattr(options, "voice_pivot_hz", None) is not None:
+        return
     if formant_options(options) is not None:
         raise model.Sbv2Error(f"formant_scale shifts a whole signal: {what} hands out chunks before the rows are complete, ask "
-                              "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
+                              "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead, or name voice_pivot_hz")
     if voice_options(options) is not None:
         raise model.Sbv2Error(f"pitch_scale / intonation_scale shift a whole signal: {what} hands out chunks before the rows are complete, ask "
-                              "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
+                              "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead, or name voice_pivot_hz")
 
 
 def track_options(options):
@@ -830,6 +871,15 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     contour = pitch_options(options, fmt.sample_rate) if pitch else None   # (a bad pitch_hz or range likewise)
     if contour is not None:
         kw.update(pitch=contour)
+    sv = stream_voice_options(options, len(live))   # (pitch_scale / intonation_scale / formant_scale about voice_pivot_hz: refused above without it)
+    if sv is not None:
+        # a handle class without the entry point is refused, never served unshifted (the formant_scale rule)
+        import inspect
+        params = inspect.signature(model.StreamHandle.__init__).parameters
+        if "voice" not in params:
+            raise model.Sbv2Error("pitch_scale / intonation_scale / formant_scale on a stream need a StreamHandle that takes voice=: this one does "
+                                  "not, and the request is not served unshifted")
+        kw.update(voice=sv, fmt=fmt)   # (a voice stream always formats: the identity format is an explicit one)
     if split:
         lines = [i for i, s in enumerate(sentences) if s]
         gaps = [SENTENCE_GAP if i != len(sentences) - 1 else 0 for i in lines]

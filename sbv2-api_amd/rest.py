@@ -53,7 +53,14 @@ and error mapping, so that a client of the reference's server cannot tell the di
   formant_scale = 1.0 (new; the same routes): the voice's formants moved by that factor in [0.5, 2], f0 and the length left alone (below 1 a
                     larger, darker speaker, above 1 a smaller, brighter one); made by the shifter of pitch_scale on the device, it composes with
                     pitch_scale, intonation_scale, pitch_track and token_pitch.  The marks of /synthesize_marks then carry "formant_scale".  The
-                    stream routes answer 400 for a value other than 1.
+                    stream routes answer 400 for a value other than 1 unless voice_pivot_hz is named.
+  voice_pivot_hz = null (new; /synthesize_stream and /synthesize_stream_marks): the f0 in Hz, in [70, 600], that intonation_scale pivots about on a
+                    stream, in place of the mean f0 a stream cannot know ahead: one number, or with split_sentences one per non-empty line.
+                    With it the stream routes take pitch_scale, intonation_scale and formant_scale and shift the voice on the device chunk by
+                    chunk; audio then runs about 60 ms further behind the synthesis within a sentence.  Read it from the "pitch" block of a
+                    /synthesize_marks answer of the same voice (the mean of its voiced f0_hz); with that value the stream's samples are those of
+                    /synthesize.  A value outside the range answers 400 there; /synthesize and /synthesize_marks refuse the field and name the
+                    stream routes.  pitch_track and token_pitch stay refused on streams.
   assist_text = null (new; all four synthesis routes, streams included; assist_text_weight = 0.7): a second text ("I am so happy!") that steers
                     HOW the text is spoken, upstream Style-Bert-VITS2's assist_text: it is parsed by the holder's parse_text, runs through the
                     same DeBERTa in the same run, and the mean of its features is mixed into every token's feature with that weight in [0, 1] on
@@ -75,7 +82,7 @@ FastAPI / starlette are plumbing here; `python -m sbv2_api_amd.rest` is not prov
 import base64
 import json
 import threading
-from typing import List, Optional
+from typing import List, Optional, Union
 
 
 class _HeldPieces:
@@ -190,7 +197,8 @@ def make_app(holder, batching=None):
         token_pitch_smooth: int = 2         # contour frames to each side over which the ratio changes, [0, 20]
         assist_text: Optional[str] = None   # new: a second text whose DeBERTa features steer the delivery (upstream's assist_text); all four routes
         assist_text_weight: float = 0.7     # its weight, [0, 1] (upstream's default); 0 = none
-        formant_scale: float = 1.0          # new: moves the voice's formants, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); 400 on the stream routes
+        formant_scale: float = 1.0          # new: moves the voice's formants, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); 400 on the stream routes without voice_pivot_hz
+        voice_pivot_hz: Optional[Union[float, List[float]]] = None   # new: /synthesize_stream, /synthesize_stream_marks: the f0 (Hz, [70, 600]) that intonation_scale pivots about, one number or one per sentence; it opens the three scales on the stream routes; 400 elsewhere
 
     class SynthesizeMarksRequest(SynthesizeRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
@@ -246,6 +254,7 @@ def make_app(holder, batching=None):
                                                   "token_pitch_smooth": req.token_pitch_smooth}
                                                  if getattr(req, "token_pitch", None) is not None else {}),
                                               **({"formant_scale": req.formant_scale} if getattr(req, "formant_scale", 1.0) != 1.0 else {}),
+                                              **({"voice_pivot_hz": req.voice_pivot_hz} if getattr(req, "voice_pivot_hz", None) is not None else {}),
                                               **({"assist": req.assist_text or None, "assist_weight": req.assist_text_weight}
                                                  if getattr(req, "assist_text", None) or getattr(req, "assist_text_weight", 0.7) != 0.7 else {}))
 
@@ -306,6 +315,7 @@ def make_app(holder, batching=None):
         request is at fault, nothing was tried), None at the defaults."""
         try:
             orchestrator.refuse_dynamics(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            orchestrator.check_voice_pivot(getattr(req, "voice_pivot_hz", None))   # (a bad pivot is the request's fault)
             orchestrator.refuse_voice(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
