@@ -253,6 +253,36 @@ inline std::vector<int64_t> stream_voice_timeline(const std::vector<int64_t>& fr
     return out;
 }
 
+// Not in the reference (sbv2_stream_leveler in sbv2_hip.h states it): a loudness target followed on a request STREAM, from the gain_db of the
+// request's level towards target_lufs - (the gated loudness heard so far).  The defaults are the usual values.
+struct StreamLeveler {
+    double target_lufs = -16.0, range_db = 12.0, slew_db_per_s = 3.0;
+    int32_t hold_blocks = 10;
+    sbv2_stream_leveler c_struct() const { return sbv2_stream_leveler{target_lufs, range_db, slew_db_per_s, hold_blocks, 0}; }
+};
+// sbv2_stream_begin_request_leveler: sbv2_stream_begin_request_voice with the leveler in front of the level's limiter (rq.level must be set);
+// leveler == nullptr is exactly that call.  The chunks are taken with sbv2_stream_next_level.
+inline sbv2_stream* stream_begin_request_leveler(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch& batch, const sbv2_utt_options* opts, Assist* assist,
+                                                 const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                                 const sbv2_stream_request& rq, StreamVoice* voice, const StreamLeveler* leveler,
+                                                 const sbv2_stream_levels* lv = nullptr, const sbv2_stream_pitch* sp = nullptr,
+                                                 int64_t* total_samples = nullptr, int64_t* n_tokens = nullptr, int64_t* n_env = nullptr,
+                                                 int64_t* n_pitch = nullptr) {
+    sbv2_stream* s = nullptr;
+    sbv2_stream_leveler c{};
+    if (leveler) c = leveler->c_struct();
+    check(sbv2_stream_begin_request_leveler(bert, vits, &batch, opts, assist ? assist->c_struct() : nullptr, token_ids, s_lens, word2ph, chunk_frames, &rq,
+                                            lv, sp, voice ? voice->c_struct() : nullptr, leveler ? &c : nullptr, &s, total_samples, n_tokens, n_env,
+                                            n_pitch));
+    return s;
+}
+// (L_in, last g, min g, max g, deepest reduction in dB, max |x|) of a levelled stream, once its last chunk was taken
+inline std::vector<double> stream_leveler_stats(sbv2_stream* s) {
+    std::vector<double> st(6);
+    check(sbv2_stream_leveler_stats(s, st.data()));
+    return st;
+}
+
 }  // namespace sbv2_core
 
 #endif

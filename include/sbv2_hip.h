@@ -878,8 +878,9 @@ int sbv2_stream_marks(sbv2_stream* s, int64_t* tok_start, int64_t* tok_end, int6
  *   sbv2_pipeline_fetch_request_marks for the joined fetch; the silence belongs to no token.
  * Refused before any GPU work: NULL rq or gap_after, n < 1, a gap out of range or below the minimum, a non-zero reserved, normalize, flac without
  *   s16, and whatever the options, the format and the level are refused for elsewhere.
- * Not built: gaps below the minimum at resampled rates (they would need a call to see two windows), a loudness target, sbv2_node_*.  Levels
- *   and an envelope: sbv2_stream_begin_request_levels below.  The four calls above are the n = 1, gap_after = {0} case of the same code and keep their bytes. */
+ * Not built: gaps below the minimum at resampled rates (they would need a call to see two windows), sbv2_node_*.  Levels and an envelope:
+ *   sbv2_stream_begin_request_levels below; a loudness target: sbv2_stream_begin_request_leveler below.  The four calls above are the n = 1,
+ *   gap_after = {0} case of the same code and keep their bytes. */
 typedef struct sbv2_stream_request {
     const int64_t* gap_after;         /* [batch->n] native (44.1 kHz) samples of silence after row i; the last entry is trailing silence */
     const sbv2_pcm_format* fmt;       /* NULL = 44100 Hz f32, not normalised (the identity format) */
@@ -906,8 +907,7 @@ int sbv2_stream_begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch
  * Refused before any GPU work: a non-zero reserved, tokens outside {0, 1}, a negative env_hop (these three before the handles are looked at),
  *   and everything sbv2_stream_begin_request refuses.  n_env >= 2^30 is refused once the forward has named the length
  *   (with predicted durations nothing names it earlier), before the stream has set up anything: no replay, no buffer, no level work.
- * Not built: levels on the plain sbv2_stream_begin stream (begin a request stream with fmt NULL, the identity format, instead), sbv2_node_*,
- *   a loudness target on a stream. */
+ * Not built: levels on the plain sbv2_stream_begin stream (begin a request stream with fmt NULL, the identity format, instead), sbv2_node_*. */
 typedef struct sbv2_stream_levels {
     int32_t tokens;        /* 0 / 1: levels per token */
     int32_t env_hop;       /* 0 = no envelope, else delivered samples per frame */
@@ -1098,6 +1098,69 @@ int sbv2_stream_voice_timeline(const int64_t* frames, const int64_t* gap_after, 
  * pushes' final samples back to back (n in all), out_per_push[ncuts + 1] their counts (the delivery rule). */
 int sbv2_debug_voice_stream(int device, const float* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate, const sbv2_stream_voice* v,
                             const double* period_in, const int32_t* voiced_in, float* y, int64_t* out_per_push);
+
+/* ---- new: a loudness target on a request stream: a gated leveler carried from chunk to chunk ON THE DEVICE.
+ * An exact integrated-loudness target needs the end of the signal; a follower does not.  The BS.1770 meter of sbv2_loudness is a linear
+ * recurrence over segments and its gated mean can be kept as a running quantity, so a gain that tracks "target - loudness of everything heard so
+ * far" needs no look-ahead beyond the limiter's own A samples.  The leveler starts from the caller's gain_db (sbv2_stream_level: the guess),
+ * walks to the right gain at a bounded rate, ends at target - L_in and reports L_in, so the next request of the same voice can start right.
+ * Signal.  y = the stream's delivered signal: f64, at the format's rate fs, before any cast: the signal the limiter of a level stream reads.
+ *   S = fs div 10.  m = the K-weighting segment length of the meter at that rate: 200 at 8 / 16 / 32 kHz, 245 at 22.05 / 44.1 kHz, 240 at 24 /
+ *   48 kHz (m divides S).
+ * Meter.  w = y through the K-weighting cascade of sbv2_loudness: the same coefficients, transposed direct form II, zero state at the stream's
+ *   start.  Segment s covers samples [s m, (s + 1) m); its start state is st_{s+1} = A^m st_s + e_s with st_0 = 0, A the cascade's transition
+ *   over one sample of zero input and e_s the segment's end state from a zero start, folded in ascending segment order (a sequential fold, not
+ *   a scan tree: each row of A^m st is 4 fused multiply-adds in ascending column order onto e_s); its partial p_s = the sum of w^2 in sample
+ *   order from st_s (acc = fma(w, w, acc)).  Quarter k = samples [k S, (k + 1) S), complete quarters only; E_k = the sum of its S / m partials
+ *   in ascending order.  Block j >= 3: z_j = (((E_{j-3} + E_{j-2}) + E_{j-1}) + E_j) / (4 S), l_j = -0.691 + 10 log10 z_j.
+ * Running gated loudness.  Once quarter k is complete, Lambda_k = the BS.1770-4 integrated loudness over the blocks 3 .. k: absolute gate
+ *   l_j > -70, relative gate l_j > (-0.691 + 10 log10 of the mean z of the blocks that passed the absolute gate) - 10, Lambda_k = -0.691 +
+ *   10 log10 of the mean z of the blocks that pass both; -inf when no block passes (always for k < 3).  n_k = the number of blocks that pass the
+ *   absolute gate.  Every mean over blocks runs in an order that depends on the block indices alone (block j - 3 is added by lane (j - 3) mod
+ *   256 in ascending order, the lanes by a fixed tree), so the values agree with a sequential float64 sum to its rounding, not bit for bit.
+ * Gain schedule, in dB.  g_k = the gain reached at the end of quarter k, decided from quarters < k only.  g_0 = gain_db of the stream's
+ *   sbv2_stream_level.  For k >= 1: if n_{k-1} >= hold_blocks and Lambda_{k-1} is finite, want = clamp(target_lufs - Lambda_{k-1},
+ *   gain_db - range_db, gain_db + range_db) and g_k = g_{k-1} + clamp(want - g_{k-1}, -slew_db_per_s / 10, +slew_db_per_s / 10); otherwise
+ *   g_k = g_{k-1}.
+ * Gain applied.  a_k = 10^(g_k / 20).  Sample i (0 <= i < S) of quarter k becomes v = y (a_{k-1} + (a_k - a_{k-1}) (i + 1) / S), a_{-1} = a_0;
+ *   the trailing partial quarter is ramped like a whole one.
+ * Behind the leveler.  v goes through the stream limiter of sbv2_stream_level begun at gain 0 dB under the level's ceiling: x = v s, |x| <= c as
+ *   on any level stream.  Delivery runs A samples late and not one more: the gain of a sample depends only on quarters that end before that
+ *   sample's quarter begins.  The delivery rule, sbv2_stream_level_lookahead, sbv2_stream_call_bound, the timelines, sbv2_stream_marks, the
+ *   stream levels and the stream pitch (all of the delivered x) stay as they are; such a stream is taken with sbv2_stream_next_level.
+ * Chunk invariance.  x, the schedule g_k and the stats do not depend on how the stream is cut into chunks.
+ * Carried on the device: the 4-double filter state, the < m samples of the unfinished segment, the < S / m partials of the unfinished quarter,
+ *   the last three E, the block history z_j and g_k, a_k (ceil(total / S) doubles each), the running stats.  Five launches per replay.
+ * leveler == NULL: exactly sbv2_stream_begin_request_voice: the same launches, the same bytes.
+ * Refused before any GPU work and before the handles are looked at: non-finite or out-of-range fields, a non-zero reserved, a leveler without
+ *   rq->level (it needs the ceiling and the starting gain).
+ * Not built: a bound on the limiter's depth on a stream (reported, as on any level stream), the compressor on a stream, the plain
+ *   sbv2_stream_begin_level entry (a request stream of one row serves it), sbv2_node_*, a short-term (per-sentence) leveler. */
+typedef struct sbv2_stream_leveler {
+    double target_lufs;      /* [-70, -5], as sbv2_loudness.target_lufs */
+    double range_db;         /* [0, 20]: g stays within gain_db +- range_db; usual value 12 */
+    double slew_db_per_s;    /* (0, 20]: g moves at most slew / 10 dB per quarter; usual value 3 */
+    int32_t hold_blocks;     /* [1, 100]: blocks above the absolute gate before g moves; usual value 10 */
+    int32_t reserved;        /* must be 0 */
+} sbv2_stream_leveler;
+int sbv2_stream_begin_request_leveler(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                                      const sbv2_assist* assist /* may be NULL */, const int64_t* token_ids, const int64_t* s_lens,
+                                      const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
+                                      const sbv2_stream_levels* lv /* may be NULL */, const sbv2_stream_pitch* sp /* may be NULL */,
+                                      const sbv2_stream_voice* voice /* may be NULL */, const sbv2_stream_leveler* leveler /* may be NULL */,
+                                      sbv2_stream** out, int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch);
+/* stats[0] = L_in = Lambda of the last complete quarter (-inf when none passed the gates), stats[1] = the last g (g_K, K = the complete
+ * quarters: the gain to begin the next request of the voice with), stats[2] / stats[3] = the lowest / highest g_k, k = 0 .. K, stats[4] /
+ * stats[5] = the two of sbv2_stream_level_stats (20 log10 min s, max |x|).  Refused before the stream is complete, as that call is. */
+int sbv2_stream_leveler_stats(sbv2_stream* s, double* stats /* [6] */);
+/* Test hook: the fed leveler and the stream limiter behind it on a host f64 signal, as StreamOutput runs them.  On the device the input lies
+ * between NaN words (a read outside [0, n) poisons a result).  x[n] is cut at the ascending positions cuts[ncuts] into ncuts + 1 pushes (empty
+ * ones allowed, the last one ends the stream; ncuts = 0 is the one shot); out_x receives the pushes' samples back to back (n in all),
+ * out_per_push[ncuts + 1] their counts (the delivery rule), out_gain_db[k] = g_k for k = 0 .. n div S (gain_capacity must hold them), stats the
+ * 6 doubles.  level, leveler, rate, cuts and the capacity are checked before any device call. */
+int sbv2_debug_leveler_stream(int device, const double* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
+                              const sbv2_stream_level* level, const sbv2_stream_leveler* leveler, double* out_x, int64_t* out_per_push,
+                              double* out_gain_db, int64_t gain_capacity, double* stats);
 
 /* Test hook: the two kernels on a host plane F [C][ld] (pitch ld, any value >= 1; on the device it lies between NaN words).  Assist sequence a
  * is the columns [a_start[a], a_start[a] + a_len[a]) of F; text column t < L reads source column map[t] (< 0: padding) and belongs to row

@@ -45,6 +45,12 @@ class Sbv2StreamLevel(C.Structure):
     _fields_ = [("gain_db", C.c_double), ("true_peak_max_dbtp", C.c_double), ("reserved", C.c_double * 2)]
 
 
+class Sbv2StreamLeveler(C.Structure):
+    """struct sbv2_stream_leveler (include/sbv2_hip.h)."""
+    _fields_ = [("target_lufs", C.c_double), ("range_db", C.c_double), ("slew_db_per_s", C.c_double), ("hold_blocks", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class Sbv2StreamRequest(C.Structure):
     """struct sbv2_stream_request (include/sbv2_hip.h)."""
     _fields_ = [("gap_after", i64p), ("fmt", C.POINTER(Sbv2PcmFormat)), ("level", C.POINTER(Sbv2StreamLevel)), ("flac", C.c_int32),
@@ -299,6 +305,13 @@ SYMBOLS = {
     "sbv2_stream_begin_request_voice": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), C.POINTER(Sbv2Assist), i64p, i64p,
                                                   i64p, C.c_int64, C.POINTER(Sbv2StreamRequest), C.POINTER(Sbv2StreamLevels), C.POINTER(Sbv2StreamPitch),
                                                   C.POINTER(Sbv2StreamVoice), C.POINTER(C.c_void_p), i64p, i64p, i64p, i64p]),
+    "sbv2_stream_begin_request_leveler": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions), C.POINTER(Sbv2Assist), i64p,
+                                                    i64p, i64p, C.c_int64, C.POINTER(Sbv2StreamRequest), C.POINTER(Sbv2StreamLevels),
+                                                    C.POINTER(Sbv2StreamPitch), C.POINTER(Sbv2StreamVoice), C.POINTER(Sbv2StreamLeveler),
+                                                    C.POINTER(C.c_void_p), i64p, i64p, i64p, i64p]),
+    "sbv2_stream_leveler_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "sbv2_debug_leveler_stream": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2StreamLevel),
+                                            C.POINTER(Sbv2StreamLeveler), C.c_void_p, i64p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double)]),
     "sbv2_stream_voice_lookahead": (C.c_int64, [C.POINTER(Sbv2StreamVoice), C.c_int32]),
     "sbv2_stream_voice_timeline": (C.c_int, [i64p, i64p, C.c_int64, C.c_int32, C.c_int64, C.POINTER(Sbv2PcmFormat), C.POINTER(Sbv2StreamVoice), i64p,
                                              C.c_int64, i64p]),

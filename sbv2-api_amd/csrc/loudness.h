@@ -18,6 +18,8 @@ struct LoudnessSpec {
 LoudnessSpec loudness_spec(const sbv2_loudness* ln);
 // the K-weighting at a supported rate (libebur128 form): coef = shelf b0 b1 b2 a1 a2, then high-pass b0 b1 b2 a1 a2; throws for other rates
 void loudness_kweight(int rate, double coef[10]);
+// samples per K-weighting segment at a supported rate, a divisor of rate / 10 (the meter's and the stream leveler's); throws for other rates
+int loudness_segment_len(int rate);
 // the true-peak interpolator's phases 1..3 (the kernel arguments of k_true_peak): h[p][d] = h4(p + 1 + 4 (d - 12)), d in [0, 24)
 constexpr int kTruePeakTaps = 24;
 void loudness_true_peak_taps(double h[3][kTruePeakTaps]);

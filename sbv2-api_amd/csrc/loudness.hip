@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "../../include/sbv2_hip.h"
+#include "kweight.h"
 #include "loudness.h"
 
 namespace sbv2 {
@@ -82,28 +83,6 @@ __device__ __forceinline__ int find_sig_off(const LSig* sig, int nsig, int64_t o
         else hi = mid - 1;
     }
     return lo;
-}
-
-// one sample through the cascade (transposed direct form II, as scipy.signal.lfilter): returns w, updates the state
-__device__ __forceinline__ double kw_step(const double* c, double* s, double x) {
-    const double u = fma(c[0], x, s[0]);
-    s[0] = fma(c[1], x, fma(-c[3], u, s[1]));
-    s[1] = fma(c[2], x, -c[4] * u);
-    const double w = fma(c[5], u, s[2]);
-    s[2] = fma(c[6], u, fma(-c[8], w, s[3]));
-    s[3] = fma(c[7], u, -c[9] * w);
-    return w;
-}
-
-// r = M v (+ r0)
-__device__ __forceinline__ void matvec(const double* M, const double* v, const double* r0, double* r) {
-    double t[4];
-    for (int i = 0; i < 4; ++i) {
-        double a = r0 ? r0[i] : 0.0;
-        for (int j = 0; j < 4; ++j) a = fma(M[4 * i + j], v[j], a);
-        t[i] = a;
-    }
-    for (int i = 0; i < 4; ++i) r[i] = t[i];
 }
 
 __device__ __forceinline__ void matmul(const double* X, const double* Y, double* R) {
@@ -184,13 +163,13 @@ __global__ __launch_bounds__(kScanLanes) void k_kw_carry(KwArgs a) {
     }
     const int64_t lo = g.seg0 + min(nseg, t * c), hi = g.seg0 + min(nseg, (t + 1) * c);
     double f[4] = {0.0, 0.0, 0.0, 0.0};   // the chunk's end state from a zero start
-    for (int64_t k = lo; k < hi; ++k) matvec(a.A, f, a.e + 4 * k, f);
+    for (int64_t k = lo; k < hi; ++k) kw_matvec(a.A, f, a.e + 4 * k, f);
     for (int i = 0; i < 4; ++i) Q[t][i] = f[i];
     __syncthreads();
     for (int d = 0; d < kScanLevels; ++d) {   // Q[t] = end state of chunk t from the signal's zero start
         const int sh = 1 << d;
         double v[4] = {0.0, 0.0, 0.0, 0.0};
-        if (t >= sh) matvec(P[d], Q[t - sh], Q[t], v);
+        if (t >= sh) kw_matvec(P[d], Q[t - sh], Q[t], v);
         __syncthreads();
         if (t >= sh)
             for (int i = 0; i < 4; ++i) Q[t][i] = v[i];
@@ -200,7 +179,7 @@ __global__ __launch_bounds__(kScanLanes) void k_kw_carry(KwArgs a) {
     for (int i = 0; i < 4; ++i) s[i] = t == 0 ? 0.0 : Q[t - 1][i];
     for (int64_t k = lo; k < hi; ++k) {
         for (int i = 0; i < 4; ++i) a.st[4 * k + i] = s[i];
-        matvec(a.A, s, a.e + 4 * k, s);
+        kw_matvec(a.A, s, a.e + 4 * k, s);
     }
 }
 
@@ -373,30 +352,11 @@ __global__ __launch_bounds__(256) void k_gate(GateArgs a) {
     }
 }
 
-// the cascade's state transition over one sample with zero input (state = shelf s1 s2, high-pass s1 s2)
-void transition(const double* c, double* A) {
-    const double a1 = c[3], a2 = c[4], h0 = c[5], h1 = c[6], h2 = c[7], d1 = c[8], d2 = c[9];
-    const double T[16] = {-a1, 1, 0, 0,
-                          -a2, 0, 0, 0,
-                          h1 - d1 * h0, 0, -d1, 1,
-                          h2 - d2 * h0, 0, -d2, 0};
-    std::memcpy(A, T, sizeof(T));
-}
-
-void host_matmul(const double* X, const double* Y, double* R) {
-    double t[16];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < 4; ++k) s += X[4 * i + k] * Y[4 * k + j];
-            t[4 * i + j] = s;
-        }
-    std::memcpy(R, t, sizeof(t));
-}
-
 }  // namespace
 
 static_assert(kTpTaps == kTruePeakTaps, "loudness.h states the tap count");
+
+int loudness_segment_len(int rate) { return segment_len(rate); }
 
 // the 4x interpolator's phases 1..3: h[p][d] = h4(p + 1 + 4 (d - 12)), every phase of h4 scaled to sum to 1
 void loudness_true_peak_taps(double h[3][kTruePeakTaps]) {
@@ -457,11 +417,7 @@ const std::vector<double>& LoudnessMeter::tables(int rate) {
     auto it = tables_.find(rate);
     if (it != tables_.end()) return it->second;
     std::vector<double> v(10 + 16 + 3 * kTpTaps);
-    loudness_kweight(rate, v.data());
-    double A1[16];
-    transition(v.data(), A1);
-    std::memcpy(v.data() + 10, A1, sizeof(A1));
-    for (int i = 1, m = segment_len(rate); i < m; ++i) host_matmul(A1, v.data() + 10, v.data() + 10);
+    kw_table(rate, v.data());
     loudness_true_peak_taps(reinterpret_cast<double(*)[kTpTaps]>(v.data() + 26));
     return tables_[rate] = std::move(v);
 }

@@ -362,6 +362,7 @@ class VitsModel {
     // flac (fmt must be s16): the chunks' samples are not delivered but pushed into a FlacStreamEncoder (flac_encode.h) behind each replay
     // level (needs fmt): the formatter stops at y (f64), a StreamLimiter (limiter.h) takes it replay by replay at the fixed gain and holds the
     // ceiling; what it emits is cast / quantised and delivered (or, with flac, pushed into the encoder): delivery runs A samples behind
+    // leveler (needs level): a StreamLeveler (leveler.h) scales y in place ahead of the limiter, from the level's gain towards its loudness target
     // gap_after (needs fmt): [n] native samples of silence after each row of the forward, the rows joined as stream_timeline lays them out
     // marks (needs fmt): levels per token and / or per envelope frame of the DELIVERED samples, reduced replay by replay (StreamLevels, marks.h):
     // one push per replay on what crosses PCIe or enters the FLAC encoder; such a stream delivers in order only.  marks->pitch: the pitch contour
@@ -369,7 +370,8 @@ class VitsModel {
     // voice (needs fmt; its pivots one per row): every window's central samples pass the fed shifter (StreamVoice, voice.h) ahead of the
     // formatter, which then reads the shifted rows; delivery runs A_v native samples behind within a row (stream_voice_upto); in order only
     int64_t stream_begin(int chunk_frames, const PcmFmtSpec* fmt = nullptr, bool flac = false, const StreamLevelSpec* level = nullptr,
-                         const int64_t* gap_after = nullptr, const StreamMarksSpec* marks = nullptr, const StreamVoiceSpec* voice = nullptr);
+                         const int64_t* gap_after = nullptr, const StreamMarksSpec* marks = nullptr, const StreamVoiceSpec* voice = nullptr,
+                         const StreamLevelerSpec* leveler = nullptr);
     // the output side of the running stream when it is formatted (stream_output.h: its kind, reductions, delivered count), else nullptr
     const StreamOutput* stream_output() const { return sformatted_ ? sout_.get() : nullptr; }
     const StreamTimeline& stream_layout() const { return stl_; }

@@ -37,7 +37,7 @@ PcmFmtSpec flac_stream_spec(const sbv2_pcm_format* fmt) {
 void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
                   int64_t chunk_frames, const PcmFmtSpec* spec, bool flac, const StreamLevelSpec* level, const int64_t* gap_after, sbv2_stream** out,
                   int64_t* total_samples, const StreamMarksSpec* marks = nullptr, const AssistSpec* assist = nullptr,
-                  const StreamVoiceSpec* voice = nullptr) {
+                  const StreamVoiceSpec* voice = nullptr, const StreamLevelerSpec* leveler = nullptr) {
     VitsBatch run = v;
     run.skip_decoder = true;
     pipeline_run_one(*bert->m, *vits->m, run, token_ids, s_lens, word2ph, assist);
@@ -47,7 +47,7 @@ void begin_stream(sbv2_bert* bert, sbv2_vits* vits, const VitsBatch& v, const in
     s->durations = vits->m->used_durations();
     s->offs = vits->m->used_offs();
     if (spec) s->spec = *spec;
-    s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after, marks, voice);
+    s->calls = vits->m->stream_begin((int)chunk_frames, spec, flac, level, gap_after, marks, voice, leveler);
     if (total_samples) *total_samples = pcm_format_out_len(s->spec, vits->m->stream_layout().joined);
     *out = s.release();
 }
@@ -230,6 +230,16 @@ int sbv2_stream_level_stats(sbv2_stream* s, double* stats) {
     API_END
 }
 
+// L_in, the last, the lowest and the highest g in dB, then the two of sbv2_stream_level_stats, once the last chunk of a levelled stream was taken
+int sbv2_stream_leveler_stats(sbv2_stream* s, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(s && stats, "bad arguments");
+    SBV2_REQUIRE(s->output() && s->output()->leveler(), "this stream was not begun with a leveler");
+    SBV2_REQUIRE(s->next >= s->calls, "the leveler stats exist once the stream is complete: take its chunks to the end first");
+    s->output()->leveler_stats(stats, s->vits->m->stream());
+    API_END
+}
+
 // Host only: the token spans of the stream's rows at its delivered rate (marks.h), row i at place[i] of the stream's timeline, in row order
 // then token order: what sbv2_pipeline_fetch_request_marks gives for the joined fetch.  Every duration is known once _begin* has returned, so
 // the whole timing is there before the first chunk is decoded.
@@ -276,7 +286,8 @@ namespace {
 // sbv2_stream_begin_request, with or without levels: every check before any GPU work
 void begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const int64_t* token_ids, const int64_t* s_lens,
                    const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq, const StreamMarksSpec* marks, sbv2_stream** out,
-                   int64_t* total_samples, const AssistSpec* assist = nullptr, const StreamVoiceSpec* voice = nullptr) {
+                   int64_t* total_samples, const AssistSpec* assist = nullptr, const StreamVoiceSpec* voice = nullptr,
+                   const StreamLevelerSpec* leveler = nullptr) {
     SBV2_REQUIRE(bert && vits && batch && token_ids && s_lens && word2ph && out, "bad arguments");
     SBV2_REQUIRE(rq, "no sbv2_stream_request given");
     SBV2_REQUIRE(rq->gap_after, "sbv2_stream_request.gap_after must not be NULL (one entry per row, the last one = trailing silence)");
@@ -289,11 +300,12 @@ void begin_request(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, co
     SBV2_REQUIRE(!spec.normalize, "a request stream cannot normalise (normalize must be 0): the peak of the signal is not known ahead");
     StreamLevelSpec lv;
     if (rq->level) lv = stream_level_spec(rq->level);
+    SBV2_REQUIRE(!leveler || rq->level, "a stream leveler needs sbv2_stream_request.level: its true_peak_max_dbtp is the ceiling, its gain_db the starting gain");
     VitsBatch v = to_batch(batch);
     apply_utt_options(&v, opts);
     stream_check_gaps(rq->gap_after, batch->n, spec);
     begin_stream(bert, vits, v, token_ids, s_lens, word2ph, chunk_frames, &spec, rq->flac != 0, rq->level ? &lv : nullptr, rq->gap_after, out,
-                 total_samples, marks, assist, voice);
+                 total_samples, marks, assist, voice, leveler);
 }
 }  // namespace
 
@@ -394,9 +406,26 @@ int sbv2_stream_begin_request_voice(sbv2_bert* bert, sbv2_vits* vits, const sbv2
                                     const sbv2_stream_request* rq, const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp,
                                     const sbv2_stream_voice* voice, sbv2_stream** out, int64_t* total_samples, int64_t* n_tokens, int64_t* n_env,
                                     int64_t* n_pitch) {
+    return sbv2_stream_begin_request_leveler(bert, vits, batch, opts, assist, token_ids, s_lens, word2ph, chunk_frames, rq, lv, sp, voice, nullptr, out,
+                                             total_samples, n_tokens, n_env, n_pitch);
+}
+
+// ... and with a loudness target followed on the way (the contract above sbv2_stream_leveler, include/sbv2_hip.h): the fed leveler between the
+// formatter and the stream limiter (StreamLeveler, leveler.hip; StreamOutput::push).  leveler NULL: exactly the call above.  Its fields are
+// checked with the others', before the handles are looked at; it needs rq->level.
+int sbv2_stream_begin_request_leveler(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const sbv2_assist* assist,
+                                      const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                      const sbv2_stream_request* rq, const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp,
+                                      const sbv2_stream_voice* voice, const sbv2_stream_leveler* leveler, sbv2_stream** out, int64_t* total_samples,
+                                      int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch) {
     API_BEGIN
     StreamMarksSpec marks;
     bool on = levels_spec(lv, &marks);
+    StreamLevelerSpec ls;
+    if (leveler) {
+        ls = stream_leveler_spec(leveler);
+        SBV2_REQUIRE(rq && rq->level, "a stream leveler needs sbv2_stream_request.level: its true_peak_max_dbtp is the ceiling, its gain_db the starting gain");
+    }
     StreamVoiceSpec vs;
     if (voice) {
         SBV2_REQUIRE(batch && batch->n >= 1, "sbv2_stream_begin_request takes at least one row");
@@ -417,7 +446,7 @@ int sbv2_stream_begin_request_voice(sbv2_bert* bert, sbv2_vits* vits, const sbv2
         as = assist_spec(assist, batch->n);
     }
     begin_request(bert, vits, batch, opts, token_ids, s_lens, word2ph, chunk_frames, rq, on ? &marks : nullptr, out, total_samples, &as,
-                  voice ? &vs : nullptr);
+                  voice ? &vs : nullptr, leveler ? &ls : nullptr);
     const StreamLevels* l = (*out)->output()->levels();
     const StreamPitch* q = (*out)->output()->pitch();
     if (n_tokens) *n_tokens = l ? l->n_tok() : 0;

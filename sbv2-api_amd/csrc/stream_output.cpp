@@ -12,8 +12,10 @@ int64_t StreamOutput::check(const PcmFmtSpec& spec, const StreamLevelSpec* level
 }
 
 void StreamOutput::begin(const PcmFmtSpec& spec, bool flac, const StreamLevelSpec* level, const StreamMarksSpec* marks, const std::vector<int64_t>& used,
-                         const std::vector<int64_t>& offs, const int64_t* place, int hop, int64_t joined, int64_t cap, hipStream_t s) {
-    flac_on_ = level_on_ = levels_on_ = pitch_on_ = voice_on_ = false;
+                         const std::vector<int64_t>& offs, const int64_t* place, int hop, int64_t joined, int64_t cap, hipStream_t s,
+                         const StreamLevelerSpec* leveler) {
+    flac_on_ = level_on_ = leveler_on_ = levels_on_ = pitch_on_ = voice_on_ = false;
+    SBV2_REQUIRE(!leveler || level, "a stream leveler needs a level: its ceiling and its starting gain");
     spec_ = spec;
     A_ = level ? stream_level_lookahead(spec.rate) : 0;
     delivered_ = 0;
@@ -27,7 +29,14 @@ void StreamOutput::begin(const PcmFmtSpec& spec, bool flac, const StreamLevelSpe
     }
     if (level) {   // the formatter's y goes behind the limiter's carried tail, what the limiter emits to one of the two sinks above
         if (!lim_) lim_.reset(new StreamLimiter);
-        lim_->begin(spec_.rate, total_out, cap, *level, s);
+        StreamLevelSpec lv = *level;
+        if (leveler) {   // the follower starts at the level's gain and owns it from there: the limiter behind it runs at 0 dB under the same ceiling
+            if (!lev_) lev_.reset(new StreamLeveler);
+            lev_->begin(spec_.rate, total_out, cap, *leveler, level->gain_db, s);
+            leveler_on_ = true;
+            lv.gain_db = 0.0;
+        }
+        lim_->begin(spec_.rate, total_out, cap, lv, s);
         level_on_ = true;
     }
     if (marks && (marks->tokens || marks->env_hop > 0)) {
@@ -106,6 +115,7 @@ void StreamOutput::push(const std::vector<FmtPiece>& pieces_in, const std::vecto
                                               std::to_string(lim_->fed()) + " fed)");
         d0 = lim_->emitted_after(fed0, false);
         fmtr_.run(spec_, pieces, sig, total, nullptr, fmt_slot, s, GainStage(lim_->dst()));
+        if (leveler_on_) lev_->push(lim_->dst(), total, last, s);   // in place, before the limiter reads it
         n = lim_->push(total, last, lim_->out_buffer(), s);
         int64_t at = d0;
         for (size_t w = 0; w < sig.size(); ++w) {
@@ -139,6 +149,7 @@ void StreamOutput::push(const std::vector<FmtPiece>& pieces_in, const std::vecto
 
 const char* StreamOutput::ordered() const {
     return voice_on_    ? "a voice stream delivers its chunks in order only: the shifter carries its phases and marks from chunk to chunk"
+           : leveler_on_ ? "a levelled stream delivers its chunks in order only: the leveler carries its meter and its gain from chunk to chunk"
            : level_on_  ? "a level stream delivers its chunks in order only: the limiter carries a tail from chunk to chunk"
            : flac_on_   ? "a FLAC stream delivers its chunks in order only: the encoder carries a tail from chunk to chunk"
            : levels_on_ ? "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk"
@@ -173,6 +184,13 @@ void StreamOutput::level_stats(double* out, hipStream_t s) const {
     SBV2_REQUIRE(level_on_ && lim_, "this stream was not begun with a level");
     HIP_CHECK(hipStreamSynchronize(s));
     lim_->stats(out);
+}
+
+void StreamOutput::leveler_stats(double* out, hipStream_t s) const {
+    SBV2_REQUIRE(leveler_on_ && lev_ && lim_, "this stream was not begun with a leveler");
+    HIP_CHECK(hipStreamSynchronize(s));
+    lev_->stats(out);
+    lim_->stats(out + 4);
 }
 
 }  // namespace sbv2

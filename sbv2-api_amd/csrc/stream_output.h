@@ -3,6 +3,7 @@
 // is behind the formatted fetches; the decoder's replays, their pinned slots and the prefetch stay in VitsModel.
 #pragma once
 #include "flac_encode.h"
+#include "leveler.h"
 #include "limiter.h"
 #include "marks.h"
 #include "pcm_format.h"
@@ -56,9 +57,11 @@ class StreamOutput {
     static size_t slot_bytes(const PcmFmtSpec& spec, bool flac, int64_t cap) { return flac ? FlacStreamEncoder::host_bytes(cap) : (size_t)cap * spec.bytes(); }
     // A stream of `joined` native samples whose largest replay delivers cap samples (A included).  Each optional stage is made on first use
     // and reused by later streams; a stage's begin may grow its buffers (synchronises s).  used / offs / place / hop: the rows' token
-    // durations and places (marks_spans_rows), read for token levels only.
+    // durations and places (marks_spans_rows), read for token levels only.  leveler (needs level): the loudness follower (StreamLeveler,
+    // leveler.h) works on y in place between the formatter and the limiter, which then runs at 0 dB under the level's ceiling.
     void begin(const PcmFmtSpec& spec, bool flac, const StreamLevelSpec* level, const StreamMarksSpec* marks, const std::vector<int64_t>& used,
-               const std::vector<int64_t>& offs, const int64_t* place, int hop, int64_t joined, int64_t cap, hipStream_t s);
+               const std::vector<int64_t>& offs, const int64_t* place, int hop, int64_t joined, int64_t cap, hipStream_t s,
+               const StreamLevelerSpec* leveler = nullptr);
     // One replay, enqueued on s: the formatter over its windows (sig[w] = window w), with a level the limiter's push and the cast, the levels
     // and pitch pushes on the delivered samples, then the sink: the encoder's push into `host` or the copy there.  fmt_slot: the formatter's
     // table slot; cap: what `host` was sized for; rec: filled for deliver.
@@ -73,6 +76,9 @@ class StreamOutput {
     Taken deliver(const Slot& rec, int64_t w, int64_t ci, void* dst, int64_t capacity_bytes);
     int64_t call_bound(int64_t most) const;   // bytes that suffice for a call of up to `most` fed samples
     void level_stats(double* out, hipStream_t s) const;   // level stream, after its last chunk: 20 log10 min s and max |x| (synchronises s)
+    // levelled stream, after its last chunk: L_in, the last / min / max g in dB, then the two of level_stats (synchronises s)
+    void leveler_stats(double* out, hipStream_t s) const;
+    bool leveler() const { return leveler_on_; }
     bool flac() const { return flac_on_; }
     bool level() const { return level_on_; }
     // the reductions of a stream begun with marks (nullptr otherwise) and the samples the taken calls handed out
@@ -85,13 +91,14 @@ class StreamOutput {
     PcmFormatter fmtr_;   // its table slots: 0 / 1 = the single-window plan's, 2 / 3 = the burst plan's
     std::unique_ptr<FlacStreamEncoder> flac_;
     std::unique_ptr<StreamLimiter> lim_;
+    std::unique_ptr<StreamLeveler> lev_;
     std::unique_ptr<StreamLevels> levels_;
     std::unique_ptr<StreamPitch> pitch_;
     std::unique_ptr<StreamVoice> voice_;
     std::vector<FmtPiece> vpieces_;   // a voice stream's pieces: every row's shifted samples at its place
     std::vector<int64_t> vupto_;      // ... and its calls' cumulative delivered samples
     bool voice_on_ = false;
-    bool flac_on_ = false, level_on_ = false, levels_on_ = false, pitch_on_ = false;   // what the running stream uses of them
+    bool flac_on_ = false, level_on_ = false, leveler_on_ = false, levels_on_ = false, pitch_on_ = false;   // what the running stream uses of them
     int64_t A_ = 0;           // the level's look-ahead in delivered samples (0 without a level)
     int64_t delivered_ = 0;
 };

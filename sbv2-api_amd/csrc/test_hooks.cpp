@@ -753,6 +753,56 @@ int sbv2_debug_limiter_stream(int device, const double* x, int64_t n, const int6
     API_END
 }
 
+// The fed leveler with the stream limiter behind it, as StreamOutput::push runs them: every push's samples are copied behind the limiter's
+// carried tail, scaled there in place, then pushed.  The input lies between NaN words on the device.
+int sbv2_debug_leveler_stream(int device, const double* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
+                              const sbv2_stream_level* level, const sbv2_stream_leveler* leveler, double* out_x, int64_t* out_per_push,
+                              double* out_gain_db, int64_t gain_capacity, double* stats) {
+    API_BEGIN
+    SBV2_REQUIRE(n >= 0 && ncuts >= 0 && (ncuts == 0 || cuts) && out_per_push && out_gain_db && stats && (n == 0 || (x && out_x)), "bad arguments");
+    const StreamLevelSpec spec = stream_level_spec(level);
+    const StreamLevelerSpec lspec = stream_leveler_spec(leveler);
+    double coef[10];
+    loudness_kweight(sample_rate, coef);   // refuses unsupported rates
+    const int64_t ngain = n / (sample_rate / 10) + 1;
+    SBV2_REQUIRE(gain_capacity >= ngain, "out_gain_db too small: " + std::to_string(gain_capacity) + " < " + std::to_string(ngain) + " gains");
+    std::vector<int64_t> edge(1, 0);   // push i = samples [edge[i], edge[i + 1])
+    for (int i = 0; i < ncuts; ++i) {
+        SBV2_REQUIRE(cuts[i] >= edge.back() && cuts[i] <= n, "cuts must ascend within [0, n]");
+        edge.push_back(cuts[i]);
+    }
+    edge.push_back(n);
+    const int npush = ncuts + 1;
+    int64_t longest = 0;
+    for (int i = 0; i < npush; ++i) longest = std::max(longest, edge[i + 1] - edge[i]);
+    PoisonedSignal src(x, n);
+    AudioScratch r(device, src.words.data(), sizeof(double) * src.words.size());
+    const double* y = r.x.as<double>() + PoisonedSignal::kPad;
+    DeviceBuffer out;   // every push is enqueued before the host waits once: the pushes' samples back to back
+    out.reserve(sizeof(double) * (size_t)std::max<int64_t>(n, 1), r.s);
+    StreamLevelSpec unity = spec;
+    unity.gain_db = 0.0;
+    StreamLimiter lim;
+    StreamLeveler lev;
+    lim.begin(sample_rate, n, longest, unity, r.s);
+    lev.begin(sample_rate, n, longest, lspec, spec.gain_db, r.s);
+    int64_t at = 0;
+    for (int i = 0; i < npush; ++i) {
+        const int64_t len = edge[i + 1] - edge[i];
+        if (len) HIP_CHECK(hipMemcpyAsync(lim.dst(), y + edge[i], sizeof(double) * (size_t)len, hipMemcpyDeviceToDevice, r.s));
+        lev.push(lim.dst(), len, i + 1 == npush, r.s);
+        out_per_push[i] = lim.push(len, i + 1 == npush, out.as<double>() + at, r.s);
+        at += out_per_push[i];
+    }
+    SBV2_REQUIRE(at == n, "internal: the fed limiter emitted " + std::to_string(at) + " of " + std::to_string(n) + " samples");
+    if (n) HIP_CHECK(hipMemcpyAsync(out_x, out.get(), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipMemcpyAsync(out_gain_db, lev.gains_dev(), sizeof(double) * (size_t)ngain, hipMemcpyDeviceToHost, r.s));
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    lev.stats(stats);
+    lim.stats(stats + 4);
+    API_END
+}
+
 int sbv2_debug_bucket_table(int64_t max_s, int64_t buckets, int64_t max_rel, int32_t* out) {
     API_BEGIN
     SBV2_REQUIRE(max_s >= 1 && out, "bad arguments");

@@ -1090,8 +1090,9 @@ std::vector<int64_t> stream_voice_upto(const StreamTimeline& t, int hop, int64_t
 }
 
 int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool flac, const StreamLevelSpec* level, const int64_t* gap_after,
-                                const StreamMarksSpec* marks, const StreamVoiceSpec* voice) {
+                                const StreamMarksSpec* marks, const StreamVoiceSpec* voice, const StreamLevelerSpec* leveler) {
     HIP_CHECK(hipSetDevice(device_));
+    SBV2_REQUIRE(!leveler || level, "a stream leveler needs a level: its ceiling and its starting gain");
     SBV2_REQUIRE(fl_.n >= 1 && z_.p, "stream_begin needs a preceding forward with skip_decoder");
     SBV2_REQUIRE(gap_after || fl_.n == 1, "stream_begin without gaps needs a preceding forward of ONE utterance");
     SBV2_REQUIRE(!gap_after || fmt, "a stream over several rows is a formatted stream");
@@ -1162,7 +1163,7 @@ int64_t VitsModel::stream_begin(int chunk_frames, const PcmFmtSpec* fmt, bool fl
             }
         }
         if (!sout_) sout_ = std::make_shared<StreamOutput>();
-        sout_->begin(*fmt, flac, level, marks, used_host_, used_offs_, stl_.place.data(), cfg_.hop(), stl_.joined, cap, stream_);
+        sout_->begin(*fmt, flac, level, marks, used_host_, used_offs_, stl_.place.data(), cfg_.hop(), stl_.joined, cap, stream_, leveler);
         if (voice) sout_->begin_voice(*voice, stl_.place, stl_.len, svoice_upto_, stream_);
         sformatted_ = true;
     }

@@ -505,6 +505,46 @@ def debug_limiter_stream(x, cuts, sample_rate: int, level: StreamLevel, device: 
     return np.split(out[:x.size], np.cumsum(got)[:-1]), stats
 
 
+class StreamLeveler:
+    """Loudness target of a level stream (struct sbv2_stream_leveler): the gain starts at the StreamLevel's gain_db (the guess) and follows
+    target_lufs - (the gated BS.1770 loudness of everything heard so far), within gain_db +- range_db, at most slew_db_per_s, and not before
+    hold_blocks 400 ms blocks have passed the absolute gate.  The StreamLevel's limiter runs behind it under its ceiling.  The loudness
+    heard and the gain reached are reported by StreamHandle.leveler_stats: the next request of the voice can begin there."""
+
+    def __init__(self, target_lufs: float, range_db: float = 12.0, slew_db_per_s: float = 3.0, hold_blocks: int = 10):
+        self.target_lufs, self.range_db, self.slew_db_per_s = float(target_lufs), float(range_db), float(slew_db_per_s)
+        if not (np.isfinite(self.target_lufs) and -70.0 <= self.target_lufs <= -5.0):
+            raise Sbv2Error(f"leveler target {target_lufs} LUFS is outside [-70, -5]")
+        if not (np.isfinite(self.range_db) and 0.0 <= self.range_db <= 20.0):
+            raise Sbv2Error(f"leveler range {range_db} dB is outside [0, 20]")
+        if not (np.isfinite(self.slew_db_per_s) and 0.0 < self.slew_db_per_s <= 20.0):
+            raise Sbv2Error(f"leveler slew {slew_db_per_s} dB/s is outside (0, 20]")
+        if isinstance(hold_blocks, bool) or not isinstance(hold_blocks, (int, np.integer)) or not 1 <= hold_blocks <= 100:
+            raise Sbv2Error(f"leveler hold of {hold_blocks} blocks is outside [1, 100]")
+        self.hold_blocks = int(hold_blocks)
+        self.c = _lib.Sbv2StreamLeveler(self.target_lufs, self.range_db, self.slew_db_per_s, self.hold_blocks, 0)
+
+    def __repr__(self):
+        return f"StreamLeveler({self.target_lufs}, range_db={self.range_db}, slew_db_per_s={self.slew_db_per_s}, hold_blocks={self.hold_blocks})"
+
+
+def debug_leveler_stream(x, cuts, sample_rate: int, level: StreamLevel, leveler: StreamLeveler, device: int = 0):
+    """Test hook: the fed leveler and the stream limiter behind it.  The host float64 signal x is cut at the ascending sample positions `cuts`
+    into len(cuts) + 1 pushes (empty ones allowed; none = the one shot) -> (the samples each push emitted, in order; g_k in dB for
+    k = 0 .. len(x) // (sample_rate // 10); stats [6]: L_in, last g, min g, max g, deepest reduction dB, max |x|)."""
+    x = np.ascontiguousarray(np.asarray(x, np.float64)).reshape(-1)
+    cuts = np.ascontiguousarray(np.asarray(cuts, np.int64)).reshape(-1)
+    out = np.zeros(max(x.size, 1), np.float64)
+    got = np.zeros(cuts.size + 1, np.int64)
+    gains = np.zeros(x.size // (int(sample_rate) // 10 or 1) + 1, np.float64)
+    stats = np.zeros(6, np.float64)
+    check(_lib.lib().sbv2_debug_leveler_stream(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, x.size,
+                                               cuts.ctypes.data_as(i64p) if cuts.size else None, cuts.size, int(sample_rate), C.byref(level.c),
+                                               C.byref(leveler.c), out.ctypes.data_as(C.c_void_p), got.ctypes.data_as(i64p), _f64p(gains), gains.size,
+                                               _f64p(stats)))
+    return np.split(out[:x.size], np.cumsum(got)[:-1]), gains, stats
+
+
 class Marks:
     """Speech marks of one fetched signal (struct sbv2_marks): per token of the listed rows, in row then token order, the delivered-sample span
     [start, end) and, when levels were asked for, sumsq / peak of the delivered samples in it (s16 as integers; None otherwise); env_sumsq /
@@ -1392,11 +1432,19 @@ class StreamHandle:
     voice (a StreamVoice: the three scales and the pivot): the voice is shifted on the device ahead of the formatter, carried chunk by chunk
     (sbv2_stream_begin_request_voice); delivery runs stream_voice_lookahead native samples behind within a row, so next() returns what the
     chunk completed, possibly nothing, and a row's last chunk the rest; stream_voice_timeline gives the counts ahead.  A single utterance
-    runs as the request stream with gaps=[0]."""
+    runs as the request stream with gaps=[0].
+    leveler (a StreamLeveler; needs level): the level's gain_db becomes the starting gain of a loudness follower carried chunk by chunk
+    (sbv2_stream_begin_request_leveler) in front of the level's limiter; the delivery rule is the level stream's; leveler_stats() after the
+    end.  A single utterance runs as the request stream with gaps=[0]."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
                  level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, track=None,
-                 voice: "StreamVoice | None" = None, token_pitch=None, **kw):
+                 voice: "StreamVoice | None" = None, token_pitch=None, leveler: "StreamLeveler | None" = None, **kw):
+        if leveler is not None and not hasattr(_lib.lib(), "sbv2_stream_begin_request_leveler"):
+            raise Sbv2Error("this library has no sbv2_stream_begin_request_leveler: a stream cannot follow a loudness target (it is never served "
+                            "unlevelled)")
+        if leveler is not None and level is None:
+            raise Sbv2Error("a stream leveler needs level=StreamLevel(gain_db, true_peak_max): the starting gain and the ceiling")
         if token_pitch is not None:
             raise Sbv2Error("a stream takes no token_pitch: a token's mean f0 needs all of the token's frames and the row's mean, and a stream hands "
                             "its samples out before they exist; fetch the whole signal instead (Pipeline.fetch_request(token_pitch=), /synthesize, "
@@ -1410,8 +1458,8 @@ class StreamHandle:
         self.request = isinstance(utt, (list, tuple))
         self.levels, self.env_hop, self.n_tokens, self.n_env, self._marks_buf = bool(levels), int(env_hop), 0, 0, None
         self.pitch, self.n_pitch, self._pitch_buf = pitch, 0, None
-        self.voice = voice
-        if (self.levels or self.env_hop or pitch is not None or voice is not None) and not self.request:
+        self.voice, self.leveler = voice, leveler
+        if (self.levels or self.env_hop or pitch is not None or voice is not None or leveler is not None) and not self.request:
             if gaps is not None:
                 raise Sbv2Error("gaps= belongs to a stream over a list of utterances")
             utt, gaps, self.request = [utt], [0], True
@@ -1433,8 +1481,8 @@ class StreamHandle:
             rq = _lib.Sbv2StreamRequest(gp, C.pointer(fmt.c) if fmt is not None else None, C.pointer(level.c) if level is not None else None,
                                         int(self.flac), 0)
             opts = C.byref(self.b.opts) if self.b.opts is not None else None
-            if self.b.assist is not None or voice is not None:
-                # an assisted row or a shifted voice: the one entry that takes them, with the levels and the pitch the stream may carry (NULL: without)
+            if self.b.assist is not None or voice is not None or leveler is not None:
+                # an assisted row, a shifted voice or a leveler: the one entry that takes them, with the levels and the pitch the stream may carry (NULL: without)
                 on = self.levels or self.env_hop
                 lv = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)) if on or pitch is not None else None
                 sp = None
@@ -1444,8 +1492,10 @@ class StreamHandle:
                 head = (args[0], args[1], args[2], opts, C.byref(self.b.assist) if self.b.assist is not None else None, *args[3:], C.byref(rq),
                         C.byref(lv) if lv is not None else None, C.byref(sp) if sp is not None else None)
                 tail = (C.byref(self.h), C.byref(tot), C.byref(nt), C.byref(ne), C.byref(nq))
-                if voice is not None:
-                    cv, _keep = voice.c_struct(len(utt))
+                cv, _keep = voice.c_struct(len(utt)) if voice is not None else (None, None)
+                if leveler is not None:
+                    check(l.sbv2_stream_begin_request_leveler(*head, C.byref(cv) if cv is not None else None, C.byref(leveler.c), *tail))
+                elif voice is not None:
                     check(l.sbv2_stream_begin_request_voice(*head, C.byref(cv), *tail))
                 else:
                     check(l.sbv2_stream_begin_request_assist(*head, *tail))
@@ -1520,6 +1570,13 @@ class StreamHandle:
         st = np.zeros(2, np.float64)
         check(_lib.lib().sbv2_stream_level_stats(self.h, _f64p(st)))
         return float(st[0]), float(st[1])
+
+    def leveler_stats(self):
+        """(L_in LUFS, last g, min g, max g in dB, deepest reduction in dB, max |x|) of a levelled stream, once next() has returned None or the
+        last chunk (sbv2_stream_leveler_stats)."""
+        st = np.zeros(6, np.float64)
+        check(_lib.lib().sbv2_stream_leveler_stats(self.h, _f64p(st)))
+        return tuple(float(v) for v in st)
 
     def next_marks(self):
         """(tok_first, sumsq, peak, env_first, env_sumsq, env_peak, delivered): the levels that the pieces taken since the previous call completed

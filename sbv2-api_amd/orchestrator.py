@@ -46,6 +46,10 @@ class SynthesizeOptions:
     gain_db (new; read by easy_synthesize_stream only, refused everywhere else): a fixed gain in dB on a stream, with the limiter's gain curve
     holding the samples under true_peak_max (model.StreamLevel).  A stream cannot measure its loudness; the caller names the gain, for
     example target - L from the loudness stats of an earlier answer of the same voice.
+    level_target (new; read by easy_synthesize_stream only, refused everywhere else) with level_range ([0, 20] dB), level_slew ((0, 20] dB/s) and
+    level_hold ([1, 100] blocks): a loudness target in LUFS followed on a stream (model.StreamLeveler).  gain_db is then the STARTING gain (0
+    when absent), true_peak_max the ceiling; the gain walks towards level_target - (the gated loudness of everything heard so far), and the
+    iterator's `.leveler_stats` reports the loudness heard and the gain reached, so the next request of the voice can begin there.
     pitch_hz (new; easy_synthesize_marks only, refused everywhere else): the speech marks carry a pitch contour of pitch_hz frames per second
     (an integer in [1, 1000]; sample_rate // pitch_hz delivered samples per frame), estimated on the device from the delivered samples within
     [pitch_min_hz, pitch_max_hz] (model.Pitch).
@@ -86,8 +90,12 @@ class SynthesizeOptions:
                  normalize=False, loudness=None, true_peak_max=-1.0, limiter=False, max_reduction=6.0, envelope_hz=None, gain_db=None,
                  pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False,
                  compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0, token_pitch=None, token_pitch_kind="hz",
-                 token_pitch_smooth=2, formant_scale=1.0, assist=None, assist_weight=0.7, voice_pivot_hz=None):
+                 token_pitch_smooth=2, formant_scale=1.0, assist=None, assist_weight=0.7, voice_pivot_hz=None, level_target=None,
+                 level_range=12.0, level_slew=3.0, level_hold=10):
         self.voice_pivot_hz = check_voice_pivot(voice_pivot_hz)
+        self.level_target, self.level_range, self.level_slew, self.level_hold = level_target, level_range, level_slew, level_hold
+        if level_target is not None:
+            stream_leveler_options(self)   # the ranges, by model.StreamLeveler
         # (a str is a text still to be parsed: holder.TTSModelHolder does that with its parse_text; the routes below refuse it as it is)
         self.assist_text = assist if isinstance(assist, str) and assist else None
         self.assist_ids, self.assist_weight = check_assist(None if isinstance(assist, str) else assist, assist_weight)
@@ -128,6 +136,23 @@ class SynthesizeOptions:
         self.envelope_hz = envelope_hz
         self.gain_db = gain_db
         self.pitch_hz, self.pitch_min_hz, self.pitch_max_hz = pitch_hz, pitch_min_hz, pitch_max_hz
+
+
+def stream_leveler_options(options):
+    """The model.StreamLeveler of a request's options, or None without a level_target (options of an older shape have none)."""
+    if getattr(options, "level_target", None) is None:
+        return None
+    for name in ("level_target", "level_range", "level_slew"):
+        v = getattr(options, name)
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise model.Sbv2Error(f"{name} must be a number: {v!r}")
+    return model.StreamLeveler(options.level_target, options.level_range, options.level_slew, options.level_hold)
+
+
+def refuse_level_target(options, where):
+    if getattr(options, "level_target", None) is not None:
+        raise model.Sbv2Error(f"level_target is the loudness follower of a stream (/synthesize_stream), not of {where}: a whole signal is measured, "
+                              "set loudness (LUFS) instead")
 
 
 def check_voice_pivot(pivot):
@@ -379,6 +404,7 @@ class RequestPlan:
         refuse_voice_pivot(options, "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks, the batcher)")
         if options.gain_db is not None:
             raise model.Sbv2Error("gain_db is the level control of a stream (/synthesize_stream): a whole signal is measured, set loudness (LUFS) instead")
+        refuse_level_target(options, "/synthesize, /synthesize_marks (easy_synthesize, easy_synthesize_marks, the batcher)")
         if options.loudness is not None and options.normalize:
             raise model.Sbv2Error("normalize (peak) and loudness are exclusive: choose one")
         self.limited = bool(options.limiter)
@@ -696,6 +722,7 @@ class SynthesisStream:
         self._st, self._head, self._to_bytes, self._tail = st, head, to_bytes, tail   # tail: bytes that follow the last chunk (a pad byte)
         self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece
         self.level_stats = None   # a level stream's (deepest reduction in dB, max |x|), once its last piece has been handed out
+        self.leveler_stats = None   # a levelled stream's (L_in, last g, min g, max g, deepest reduction, max |x|), likewise
         # levels=(fmt, env_hop, total_samples): the stream was begun with levels (easy_synthesize_stream(levels=True)); take_marks() hands out
         # what the pieces so far completed, and once the last piece is out `.marks` holds them all, in marks_dict's shape
         self._levels, self.delivered = levels, 0
@@ -768,6 +795,8 @@ class SynthesisStream:
                         token_pitch(self.marks["tokens"], self._f0, self._pitch.hop)
                     if getattr(self._st, "level", None) is not None:
                         self.level_stats = self._st.level_stats()
+                    if getattr(self._st, "leveler", None) is not None:
+                        self.leveler_stats = self._st.leveler_stats()
                     st, self._st = self._st, None
                     st.close()      # the device side is done; on_close waits until the last byte has been handed out
                     break
@@ -823,6 +852,9 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     options.gain_db: the level stream (model.StreamLevel(gain_db, true_peak_max)) for every encoding alike: a fixed gain, no sample above
     the ceiling; the pieces run stream_level_lookahead samples behind the decoder, the total length is unchanged, and after the last piece
     the iterator's `.level_stats` holds (deepest reduction in dB, max |x|).
+    options.level_target (with level_range / level_slew / level_hold): the same level stream with a loudness follower in front of its limiter
+    (model.StreamLeveler): gain_db is then the starting gain, 0 when absent; after the last piece `.leveler_stats` holds (L_in LUFS, last g, min
+    g, max g in dB, deepest reduction in dB, max |x|).  A handle class that takes no leveler= is refused, never served unlevelled.
     Everything up to the first replay (options, DeBERTa, flow, the header) runs before the iterator is returned.
     The iterator's `.marks` holds the token and word timing of every row with its line number (token_marks: every duration is known before
     the first replay).
@@ -863,7 +895,9 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     fmt = model.PcmFormat(options.sample_rate, "s16" if flac else options.encoding, False)
     model.pcm_format_length(fmt, 0)   # a bad rate is refused before any GPU work
     # (with a level the default format is an explicit one: the level stream always formats)
-    level = model.StreamLevel(options.gain_db, options.true_peak_max) if options.gain_db is not None else None
+    leveler = stream_leveler_options(options)
+    start_db = options.gain_db if options.gain_db is not None else (0.0 if leveler is not None else None)
+    level = model.StreamLevel(start_db, options.true_peak_max) if start_db is not None else None
     kw = dict(fmt=None if fmt.is_default and level is None else fmt, flac=flac, level=level, sdp_ratio=options.sdp_ratio,
               length_scale=options.length_scale, noise_scale=noise_scale, noise_scale_w=noise_scale_w, noise_seed=noise_seed)
     if levels:
@@ -871,6 +905,12 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     contour = pitch_options(options, fmt.sample_rate) if pitch else None   # (a bad pitch_hz or range likewise)
     if contour is not None:
         kw.update(pitch=contour)
+    if leveler is not None:
+        import inspect
+        if "leveler" not in inspect.signature(model.StreamHandle.__init__).parameters:
+            raise model.Sbv2Error("level_target on a stream needs a StreamHandle that takes leveler=: this one does not, and the request is not "
+                                  "served unlevelled")
+        kw.update(leveler=leveler)
     sv = stream_voice_options(options, len(live))   # (pitch_scale / intonation_scale / formant_scale about voice_pivot_hz: refused above without it)
     if sv is not None:
         # a handle class without the entry point is refused, never served unshifted (the formant_scale rule)

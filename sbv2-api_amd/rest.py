@@ -14,7 +14,9 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     "s16" / "f32" / "mulaw" / "alaw" -> audio/wav, the header written with the known length, then the chunks.  normalize / loudness / limiter
                     are refused (they need the whole signal).  gain_db = null (new): a fixed gain in dB with the limiter's look-ahead gain
                     curve holding every sample under true_peak_max, carried from chunk to chunk on the device; same length, same header;
-                    the other routes refuse it.  Errors before the first byte map as below; the lock is held until the last byte
+                    the other routes refuse it.  level_target = null (new; with level_range = 12, level_slew = 3, level_hold = 10): a loudness
+                    target in LUFS that a follower on the device walks towards from gain_db (the starting gain, 0 when absent) while the
+                    stream runs, under the same ceiling; the other routes refuse it and point to loudness.  Errors before the first byte map as below; the lock is held until the last byte
                     has left or the client has gone, whichever comes first (_HeldPieces, _ClosingStream).
                     marks = true (new, default false): the response carries the header X-Speech-Marks, compact JSON {"sample_rate", "tokens":
                     [[line, index, phone, start, end], ...], "words": [[line, index, start, end], ...]} in delivered samples: the timing of the
@@ -181,6 +183,10 @@ def make_app(holder, batching=None):
         limiter: bool = False               # look-ahead true-peak limiter for targets the plain gain misses; needs loudness
         max_reduction: float = 6.0          # the limiter's deepest gain reduction (dB)
         gain_db: Optional[float] = None     # /synthesize_stream only: fixed gain (dB) under the true_peak_max ceiling; refused elsewhere
+        level_target: Optional[float] = None   # new: /synthesize_stream, /synthesize_stream_marks: loudness target (LUFS) followed on the stream, gain_db the starting gain; refused elsewhere
+        level_range: float = 12.0           # how far the follower may move from gain_db (dB), [0, 20]
+        level_slew: float = 3.0             # its fastest move (dB per second), (0, 20]
+        level_hold: int = 10                # 400 ms blocks above the absolute gate before it moves, [1, 100]
         pitch_hz: Optional[int] = None      # /synthesize_marks, /synthesize_stream_marks: frames per second of the pitch contour in the marks; refused elsewhere
         pitch_min_hz: float = 70.0          # the contour's search range (Hz)
         pitch_max_hz: float = 600.0
@@ -255,6 +261,8 @@ def make_app(holder, batching=None):
                                                  if getattr(req, "token_pitch", None) is not None else {}),
                                               **({"formant_scale": req.formant_scale} if getattr(req, "formant_scale", 1.0) != 1.0 else {}),
                                               **({"voice_pivot_hz": req.voice_pivot_hz} if getattr(req, "voice_pivot_hz", None) is not None else {}),
+                                              **({"level_target": req.level_target, "level_range": req.level_range, "level_slew": req.level_slew,
+                                                  "level_hold": req.level_hold} if getattr(req, "level_target", None) is not None else {}),
                                               **({"assist": req.assist_text or None, "assist_weight": req.assist_text_weight}
                                                  if getattr(req, "assist_text", None) or getattr(req, "assist_text_weight", 0.7) != 0.7 else {}))
 
