@@ -167,6 +167,43 @@ inline void fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_f
                                               dyn_stats, marks, pitch));
 }
 
+// Not in the reference: the spectrum of a fetched request (sbv2_spectrum in sbv2_hip.h states it).  n_mels = 0: the n_fft / 2 + 1 bins; f_max
+// <= 0: half the delivered rate.  power [n_frames][n_bands] is filled by fetch_request_spectrum.
+struct Spectrum {
+    int n_fft = 400, hop = 160, n_mels = 80;
+    double f_min = 0.0, f_max = 0.0;
+    std::vector<float> power;
+    int64_t n_frames = 0;
+    int n_bands = 0;
+};
+// sbv2_pipeline_fetch_request_spectrum with owned arrays: fetch_request_formant with the spectrum of the delivered signal behind it.  out_len =
+// the delivered samples of the request (sbv2_pcm_format_length of its joined_len), which sizes the array.
+inline void fetch_request_spectrum(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,
+                                   const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, TokenPitch* tp, double formant_scale, Spectrum& sp,
+                                   void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats = nullptr, double* dyn_stats = nullptr,
+                                   sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr) {
+    sbv2_token_pitch c{};
+    if (tp) {
+        tp->applied.assign(tp->values.size(), 1.0);
+        tp->src_f0.assign(tp->values.size(), 0.0);
+        c = sbv2_token_pitch{tp->values.data(), (int64_t)tp->values.size(), tp->hz ? 1 : 0, tp->smooth, tp->applied.data(), tp->src_f0.data(), 0};
+    }
+    const sbv2_formant f{formant_scale, 0.0};
+    const int rate = req.fmt ? req.fmt->sample_rate : 44100;
+    sbv2_spectrum s{sp.n_fft, sp.hop, sp.n_mels, 0, sp.f_min, sp.f_max > 0.0 ? sp.f_max : rate / 2.0, 0, nullptr, 0, 0};
+    check(sbv2_spectrum_bands(rate, &s, nullptr));   // the ranges, and n_bands
+    const int64_t out_len = sbv2_pcm_format_length(req.fmt, req.joined_len);
+    if (out_len < 0) throw Error(sbv2_last_error());
+    sp.power.assign((size_t)((out_len + sp.hop - 1) / sp.hop) * s.n_bands + 1, 0.0f);
+    s.capacity = (int64_t)sp.power.size();
+    s.power = sp.power.data();
+    check(sbv2_pipeline_fetch_request_spectrum(p, ticket, &req, voice, track, dynamics, tp ? &c : nullptr, &f, dst, capacity_bytes, out_count, stats,
+                                               dyn_stats, marks, pitch, &s));
+    sp.n_frames = s.n_frames;
+    sp.n_bands = s.n_bands;
+    sp.power.resize((size_t)(s.n_frames * s.n_bands));
+}
+
 // Not in the reference (upstream Style-Bert-VITS2's assist_text / assist_text_weight; sbv2_assist in sbv2_hip.h states it): assist texts of a run
 // with owned arrays.  texts: the distinct assist sequences' token ids; text_of / weight: one entry per row of the batch (-1 = none).
 struct Assist {

@@ -678,6 +678,57 @@ int sbv2_debug_voice_formant(int device, const float* x, const int64_t* lens, in
                              const sbv2_formant* formant, const double* period_in, const int32_t* voiced_in, double* period_out,
                              int32_t* voiced_out, int32_t* ta, int32_t* ts, int32_t* map, int64_t* n_marks, float* y);
 
+/* ---- new: the spectrum of a delivered signal.  Power per STFT bin, or per Slaney mel band, frame by frame, reduced on the device from the samples
+ * the speech marks are taken of (behind every sink, FLAC and G.711 included), stated so that it is reproducible.
+ * Input.  The delivered samples v[0 .. n) of ONE signal at rate sr, read as levels and pitch read them: u[j] = v[j] for f32, u[j] = v[j] / 32768
+ *   for s16 and for the integers that G.711 codes decode to (exact in f32); positions outside [0, n) read as 0.
+ * Parameters.  n_fft a multiple of 16 in [64, 2048] (16 samples are one step of the matrix cores; 400 is served); 1 <= hop <= n_fft; n_mels in
+ *   [0, 128]; 0 <= f_min < f_max <= sr / 2; sr <= 48000.  NaNs fail every comparison and are refused.
+ * Frames.  The time axis of sbv2_pitch and of the envelope: n_frames = ceil(n / hop) (0 for n = 0); frame f has its centre at f hop + hop / 2
+ *   (integer division) and its window starts at b = centre - n_fft / 2.
+ * Per frame.  a[i] = u[b + i] w[i] in f32 (one rounding), w[i] = 0.5 - 0.5 cos(2 pi i / n_fft) the periodic Hann window, formed in f64 and
+ *   rounded to f32; X[k] = sum_i a[i] exp(-2 pi sqrt(-1) i k / n_fft) for k = 0 .. n_fft / 2; P[k] = Re^2 + Im^2.
+ * Bands.  n_mels = 0: B = P, n_bands = n_fft / 2 + 1.  Otherwise n_bands = n_mels and B[m] = sum_k W[m][k] P[k] over ascending k, W the Slaney
+ *   mel bank: the mel scale is linear below 1000 Hz at 200 / 3 Hz per mel and logarithmic above with step log(6.4) / 27; n_mels + 2 edges
+ *   equally spaced in mel between f_min and f_max (edge i at mel(f_min) + (mel(f_max) - mel(f_min)) i / (n_mels + 1)); triangles over the bin
+ *   frequencies k sr / n_fft, W[m][k] = max(0, min((f_k - e_m) / (e_m+1 - e_m), (e_m+2 - f_k) / (e_m+2 - e_m+1))) (2 / (e_m+2 - e_m)); built on
+ *   the host in f64 and rounded to f32 (sbv2_spectrum_bands gives it).  A triangle that holds no bin gives a zero row: allowed, not refused.
+ * Result.  power [n_frames][n_bands], f32, linear; decibels are the caller's arithmetic, as dBFS is for the levels.  An all-zero signal gives
+ *   exact zeros.
+ * Bits.  No atomics; every sum is in an order the library fixes: two fetches of one ticket give identical bits, and a fetch gives the bits of
+ *   sbv2_debug_spectrum on the same samples.  Only that order and the operands of the transform are the library's own: a[i] and the basis
+ *   (cos / sin of 2 pi ((i k) mod n_fft) / n_fft, from f64) enter the matrix cores as an f16 pair hi + 2^-11 lo' of 22 mantissa bits, products
+ *   and sums in f32; P is f32 and a band's sum is a compensated (Kahan) f32 sum over ascending k.  Measured against the f64 definition, E = max over frames of max_band |B - B_ref| / max_band
+ *   B_ref, next to E32, the same for an f32 restatement in numpy (f32 operands, f32 matmul): see DESIGN.md (8w) for the figures.
+ * Range.  The pair has f16's exponent range and a[i] is split times 2^10 (so that quiet signals keep the 22 bits): an f32 value with |a[i]|
+ *   beyond 63.97 is clamped there by the split (a NaN sample likewise); delivered samples are within [-1, 1].
+ * Not built: the spectrum on streams (sbv2_stream_*) and on sbv2_node_*, the HTK mel scale, reflect padding, phase output, MFCCs, an
+ *   envelope-based formant shifter. */
+typedef struct sbv2_spectrum {
+    int32_t n_fft, hop, n_mels, reserved; /* in; reserved must be 0 */
+    double f_min, f_max;                  /* in: Hz (looked at with n_mels = 0 too) */
+    int64_t capacity;                     /* in: floats `power` holds */
+    float* power;                         /* out: [n_frames][n_bands]; must not be NULL */
+    int64_t n_frames;                     /* out: ceil(out_len / hop) */
+    int32_t n_bands;                      /* out: n_mels, or n_fft / 2 + 1 */
+} sbv2_spectrum;
+/* sbv2_pipeline_fetch_request_formant that also fills *spectrum: the spectrum of the delivered signal of the request (every gain / sink
+ * combination, FLAC included), one more launch before the fetch's only synchronisation.  spectrum == NULL is exactly that call: nothing new is
+ * launched or allocated.  The first fetch of a context with an n_fft, or with a mel bank, also forms that table on the host and uploads it (up to
+ * 17.3 MB at n_fft 2048) with one more synchronisation of the stream; the tables are cached per context (4 bases, 8 banks).  With it the audio bytes, out_count, stats, marks and pitch are those of the same call without.  The caller's array is
+ * written only after everything else has succeeded.  Refused with nothing written, besides everything that call refuses: parameters outside the
+ * ranges above (at the format's rate), capacity < n_frames n_bands, a NULL power, a non-zero reserved. */
+int sbv2_pipeline_fetch_request_spectrum(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                         const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                         const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                         double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum);
+/* Host only: checks the parameters of *spectrum at sample_rate (capacity and power are not looked at) and sets its n_bands; bank (may be NULL)
+ * receives W [n_mels][n_fft / 2 + 1] as f32 (nothing for n_mels = 0), so that a client can reproduce or invert the bands. */
+int sbv2_spectrum_bands(int32_t sample_rate, sbv2_spectrum* spectrum, float* bank);
+/* Test hook: the stage on host samples x[n] (encoding as sbv2_debug_segment_levels); spectrum: parameters in, power / n_frames / n_bands out as
+ * in the fetch. */
+int sbv2_debug_spectrum(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_spectrum* spectrum);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,

@@ -129,6 +129,12 @@ class Sbv2Formant(C.Structure):
     _fields_ = [("formant_scale", C.c_double), ("reserved", C.c_double)]
 
 
+class Sbv2Spectrum(C.Structure):
+    """struct sbv2_spectrum (include/sbv2_hip.h)."""
+    _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("reserved", C.c_int32), ("f_min", C.c_double),
+                ("f_max", C.c_double), ("capacity", C.c_int64), ("power", f32p), ("n_frames", C.c_int64), ("n_bands", C.c_int32)]
+
+
 class Sbv2StreamVoice(C.Structure):
     """struct sbv2_stream_voice (include/sbv2_hip.h)."""
     _fields_ = [("voice", Sbv2Voice), ("formant_scale", C.c_double), ("pivot_hz", C.POINTER(C.c_double)), ("reserved", C.c_double * 2)]
@@ -197,6 +203,12 @@ SYMBOLS = {
                                                       C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch),
                                                       C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
                                                       C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch)]),
+    "sbv2_pipeline_fetch_request_spectrum": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                       C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch),
+                                                       C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
+                                                       C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch), C.POINTER(Sbv2Spectrum)]),
+    "sbv2_spectrum_bands": (C.c_int, [C.c_int32, C.POINTER(Sbv2Spectrum), f32p]),
+    "sbv2_debug_spectrum": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2Spectrum)]),
     "sbv2_debug_voice_formant": (C.c_int, [C.c_int, f32p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Voice), C.POINTER(Sbv2Formant),
                                            C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64p, f32p]),

@@ -474,6 +474,20 @@ int sbv2_pitch_lags(int32_t sample_rate, double f0_min, double f0_max, int32_t* 
     API_END
 }
 
+int sbv2_spectrum_bands(int32_t sample_rate, sbv2_spectrum* spectrum, float* bank) {
+    API_BEGIN
+    SBV2_REQUIRE(spectrum, "bad arguments");
+    SBV2_REQUIRE(spectrum->reserved == 0, "sbv2_spectrum.reserved must be 0");
+    const SpectrumSpec sp = spectrum_spec(sample_rate, spectrum->n_fft, spectrum->hop, spectrum->n_mels, spectrum->f_min, spectrum->f_max);
+    if (bank && sp.n_mels) {
+        std::vector<float> W;
+        spectrum_mel_bank(sp, &W, nullptr);
+        std::memcpy(bank, W.data(), sizeof(float) * W.size());
+    }
+    spectrum->n_bands = sp.n_bands();
+    API_END
+}
+
 int sbv2_marks_spans(const int64_t* durations, int64_t n_tokens, int32_t hop, int64_t place, const sbv2_pcm_format* fmt, int64_t* start, int64_t* end) {
     API_BEGIN
     const PcmFmtSpec spec = pcm_format_spec(fmt);

@@ -14,6 +14,7 @@
 #include "marks.h"
 #include "models.h"
 #include "pcm_format.h"
+#include "spectrum.h"
 #include "track.h"
 #include "voice.h"
 
@@ -39,6 +40,7 @@ struct OutputChain {
     Dynamics dynamics; // the speech compressor in front of the loudness gain or the limiter (fetch_request_dynamics only)
     Marks marks;       // speech marks: levels of token spans and envelope frames (fetch_request_marks only)
     Pitch pitch;       // ... and the pitch contour of the same samples (fetch_request_pitch only)
+    Spectrum spectrum; // ... and their power spectrum or mel bands (fetch_request_spectrum only)
     Voice voice;       // pitch / intonation scale of the listed rows, in front of the formatter (fetch_request_voice only)
     Track track;       // the best path through the delivered contour's candidates (fetch_request_tracked only; the shifter has its own)
 };

@@ -40,6 +40,7 @@ struct FetchArgs {
 // the voice is, editing the rows' tokens (its token phase) and reading every grain at the scaled offset.
 // track (with pitch, or with a shifter that runs): both contours are tracked (Track, track.h) before they are used.
 // dynamics (with a loudness or limiter stage; ratio 1: nothing): the compressor runs on y first (dynamics.h); dyn_stats (may be NULL): its 3 doubles.
+// spectrum: the power spectrum or mel bands (spectrum.h) of the same delivered samples as marks and pitch, one more launch beside theirs.
 struct FetchStages {
     const int32_t* utts = nullptr;   // the rows of the one signal (with place[k] belonging to row utts[k]); NULL: no request, all of the run
     int n_utts = 0;
@@ -51,6 +52,7 @@ struct FetchStages {
     const sbv2_formant* formant = nullptr;
     sbv2_marks* marks = nullptr;
     sbv2_pitch* pitch = nullptr;
+    sbv2_spectrum* spectrum = nullptr;
 };
 // ... and once everything about them that needs no run has been checked (check_stages).  Default: no stage.
 struct CheckedStages : FetchStages {
@@ -59,6 +61,7 @@ struct CheckedStages : FetchStages {
     FormantSpec fs;
     TrackSpec ts;
     PitchSpec ps;
+    SpectrumSpec ss;
     bool edit = false, scale = false, compress = false;   // a token is edited; the formants move; the compressor is not the identity
     bool shifts() const { return (voice && !vs.identity()) || edit || scale; }   // the shifter has something to do
 };
@@ -85,6 +88,15 @@ PitchSpec check_pitch_static(const sbv2_pitch* q, int rate) {
     const PitchSpec sp = pitch_spec(rate, q->hop, q->f0_min, q->f0_max, q->threshold);
     SBV2_REQUIRE(q->capacity >= 0, "negative sbv2_pitch capacity");
     SBV2_REQUIRE(q->f0, "sbv2_pitch.f0 must not be NULL");
+    return sp;
+}
+
+// The checks of sbv2_spectrum that need no run: the parameters at the delivered rate (spectrum.h states the bounds), the array.
+SpectrumSpec check_spectrum_static(const sbv2_spectrum* q, int rate) {
+    SBV2_REQUIRE(q->reserved == 0, "sbv2_spectrum.reserved must be 0");
+    const SpectrumSpec sp = spectrum_spec(rate, q->n_fft, q->hop, q->n_mels, q->f_min, q->f_max);
+    SBV2_REQUIRE(q->capacity >= 0, "negative sbv2_spectrum capacity");
+    SBV2_REQUIRE(q->power, "sbv2_spectrum.power must not be NULL");
     return sp;
 }
 
@@ -139,6 +151,7 @@ CheckedStages check_stages(const sbv2_fetch_request* req, const FetchStages& st)
         (void)pcm_format_spec(req->fmt);
     }
     if (st.pitch) cs.ps = check_pitch_static(st.pitch, pcm_format_spec(req->fmt).rate);
+    if (st.spectrum) cs.ss = check_spectrum_static(st.spectrum, pcm_format_spec(req->fmt).rate);
     return cs;
 }
 
@@ -224,7 +237,7 @@ MarksPlan plan_marks(const sbv2_marks* m, const PcmFmtSpec& spec, const VitsMode
 }
 
 // Phase 1 of a fetch, host only: what will run, on what, into how many bytes.  Every refusal that needs the run is here (the format against the
-// gain stage and the sink, the gain's parameters, the ticket, the layout, PCM capacity, the marks' and the contour's capacity, the token count), so
+// gain stage and the sink, the gain's parameters, the ticket, the layout, PCM capacity, the marks', the contour's and the spectrum's capacity, the token count), so
 // nothing is enqueued before every check has passed.  (The FLAC sink alone checks its capacity after encoding, when the sizes are known.)
 struct FetchPlan {
     PcmFmtSpec spec;
@@ -235,6 +248,7 @@ struct FetchPlan {
     std::vector<FmtSignal> sig;
     std::vector<int64_t> outs;   // per signal: samples
     int64_t total = 0, pcm_bytes = 0, n_pitch = 0;   // delivered samples and their bytes; frames of the contour
+    int64_t n_spec = 0;                              // frames of the spectrum
     MarksPlan marks;
     std::vector<int64_t> tok_counts, tok_ends;   // (an edit only) per listed row: its tokens; per token: the native sample it ends at
     bool shift = false;                          // the shifter runs
@@ -262,6 +276,12 @@ FetchPlan plan_fetch(const FetchArgs& a, const CheckedStages& cs) {
         pl.n_pitch = pitch_frames(pl.total, cs.ps.hop);
         SBV2_REQUIRE(cs.pitch->capacity >= pl.n_pitch,
                      "pitch arrays too small: " + std::to_string(cs.pitch->capacity) + " < " + std::to_string(pl.n_pitch) + " frames");
+    }
+    if (cs.spectrum) {
+        pl.n_spec = spectrum_frames(pl.total, cs.ss.hop);
+        SBV2_REQUIRE(cs.spectrum->capacity >= pl.n_spec * cs.ss.n_bands(),
+                     "spectrum array too small: " + std::to_string(cs.spectrum->capacity) + " < " + std::to_string(pl.n_spec) + " frames of " +
+                         std::to_string(cs.ss.n_bands()) + " bands");
     }
     if (cs.token_pitch)
         SBV2_REQUIRE(cs.token_pitch->n_tokens == n_tok, "sbv2_token_pitch.n_tokens is " + std::to_string(cs.token_pitch->n_tokens) +
@@ -312,6 +332,7 @@ std::vector<int64_t> enqueue_fetch(const FetchArgs& a, const CheckedStages& cs, 
         // marks and pitch read the delivered samples, as they cross PCIe or enter the encoder
         if (pl.marks.reduce) c.marks.run(dev, spec.encoding, pl.total, pl.marks.seg.data(), (int64_t)pl.marks.seg.size() / 2, s);
         if (pl.n_pitch > 0) c.pitch.run(dev, spec.encoding, pl.total, cs.ps, s, ts, cs.track ? &c.track : nullptr);
+        if (pl.n_spec > 0) c.spectrum.run(dev, spec.encoding, pl.total, cs.ss, s);
         if (a.sink == Sink::kFlac) {   // the signals stay in HBM; the encoder reads the stream sizes back, then exactly the encoded bytes cross PCIe
             std::vector<int64_t> offs(pl.outs.size());
             for (size_t i = 1; i < pl.outs.size(); ++i) offs[i] = offs[i - 1] + pl.outs[i - 1];
@@ -329,7 +350,7 @@ std::vector<int64_t> enqueue_fetch(const FetchArgs& a, const CheckedStages& cs, 
     return flac_bytes;
 }
 
-// Phase 3, once everything else has succeeded: the counts, the stats, and the caller's marks, pitch and token-pitch arrays, from the chain's pinned
+// Phase 3, once everything else has succeeded: the counts, the stats, and the caller's marks, pitch, spectrum and token-pitch arrays, from the chain's pinned
 // buffers.  Nothing here can fail.
 void deliver_fetch(const FetchArgs& a, const CheckedStages& cs, const FetchPlan& pl, const std::vector<int64_t>& flac_bytes) {
     OutputChain& c = a.p->chains[pl.ctx];
@@ -364,6 +385,11 @@ void deliver_fetch(const FetchArgs& a, const CheckedStages& cs, const FetchPlan&
             if (pitch->lag) pitch->lag[f] = lag;
         }
         pitch->n_frames = pl.n_pitch;
+    }
+    if (sbv2_spectrum* sp = cs.spectrum) {   // (an empty signal has no frames and ran nothing)
+        if (pl.n_spec > 0) std::memcpy(sp->power, c.spectrum.power_host(), sizeof(float) * (size_t)(pl.n_spec * cs.ss.n_bands()));
+        sp->n_frames = pl.n_spec;
+        sp->n_bands = cs.ss.n_bands();
     }
 }
 
@@ -427,22 +453,30 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
 }
 
 // The widest request fetch; each narrower symbol below is exactly this call with NULL for what it lacks.
-int sbv2_pipeline_fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
-                                        const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
-                                        const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
-                                        double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch) {
+int sbv2_pipeline_fetch_request_spectrum(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                         const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                         const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                         double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum) {
     API_BEGIN
     static const int32_t no_rows[1] = {0};   // (a request of no rows is still a request: one empty joined signal)
     static const int64_t no_place[1] = {0};
     const bool rows = req && req->n_utts > 0;   // (what is wrong with req is refused in its turn, by check_stages)
     const CheckedStages cs = check_stages(
-        req, FetchStages{rows ? req->utts : no_rows, rows ? req->n_utts : 0, voice, track, dynamics, dyn_stats, token_pitch, formant, marks, pitch});
+        req, FetchStages{rows ? req->utts : no_rows, rows ? req->n_utts : 0, voice, track, dynamics, dyn_stats, token_pitch, formant, marks, pitch,
+                         spectrum});
     const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter}
                            : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr}
                                            : FetchGain();
     const Sink sink = req->flac ? Sink::kFlac : Sink::kPcm;
     fetch_formatted({p, ticket, req->fmt, gain, rows ? req->place : no_place, req->joined_len, sink, dst, capacity_bytes, out_count, stats}, cs);
     API_END
+}
+int sbv2_pipeline_fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                        const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                        const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                        double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch) {
+    return sbv2_pipeline_fetch_request_spectrum(p, ticket, req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count, stats,
+                                                dyn_stats, marks, pitch, nullptr);
 }
 int sbv2_pipeline_fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
                                             const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,

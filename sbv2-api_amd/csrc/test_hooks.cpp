@@ -2201,6 +2201,28 @@ int sbv2_debug_pitch(int device, const void* x, int encoding, int64_t n, int32_t
     API_END
 }
 
+// The spectrum stage (Spectrum, spectrum.hip) on host samples.  Everything is checked before any device call; nothing is written when the
+// call fails.
+int sbv2_debug_spectrum(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_spectrum* spectrum) {
+    API_BEGIN
+    SBV2_REQUIRE(spectrum && pcm_encoding_known(encoding) && n >= 0 && (x || n == 0), "bad arguments");
+    SBV2_REQUIRE(spectrum->reserved == 0, "sbv2_spectrum.reserved must be 0");
+    const SpectrumSpec sp = spectrum_spec(sample_rate, spectrum->n_fft, spectrum->hop, spectrum->n_mels, spectrum->f_min, spectrum->f_max);
+    const int64_t nf = spectrum_frames(n, sp.hop);
+    SBV2_REQUIRE(spectrum->capacity >= nf * sp.n_bands(), "spectrum array too small: " + std::to_string(spectrum->capacity) + " < " +
+                                                              std::to_string(nf) + " frames of " + std::to_string(sp.n_bands()) + " bands");
+    SBV2_REQUIRE(spectrum->power, "sbv2_spectrum.power must not be NULL");
+    HIP_CHECK(hipSetDevice(device));
+    DevMem dx(x, (size_t)n * pcm_encoding_bytes(encoding));
+    Spectrum st;
+    st.run(dx.p, encoding, n, sp, nullptr);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    if (nf > 0) std::memcpy(spectrum->power, st.power_host(), sizeof(float) * (size_t)(nf * sp.n_bands()));
+    spectrum->n_frames = nf;
+    spectrum->n_bands = sp.n_bands();
+    API_END
+}
+
 // The tracker (Track, track.hip) on host samples, or on the caller's candidate table alone.  Everything is checked before any device call;
 // nothing is written when the call fails.
 int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, const sbv2_pitch_track* track,

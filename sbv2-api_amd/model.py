@@ -611,6 +611,67 @@ def debug_pitch(x, sample_rate: int, pitch: Pitch, device: int = 0, encoding: st
     return pitch.take(c, arrays), c3[:c.n_frames], voiced[:c.n_frames]
 
 
+class Spectrum:
+    """Options and, once a call has filled it, results of the spectrum stage (struct sbv2_spectrum, include/sbv2_hip.h states it): per frame of
+    `hop` delivered samples the power of a Hann-windowed DFT of n_fft samples (n_mels = 0: n_fft // 2 + 1 bins) or of n_mels Slaney mel bands
+    between f_min and f_max (None: half the delivered rate); frame f has its centre at f hop + hop // 2, as Pitch has.  Result: power
+    [n_frames][n_bands] float32, linear; None before a call.  Ranges are checked by the library."""
+
+    def __init__(self, n_fft: int, hop: int, n_mels: int = 80, f_min: float = 0.0, f_max: float | None = None):
+        self.n_fft, self.hop, self.n_mels = int(n_fft), int(hop), int(n_mels)
+        self.f_min, self.f_max = float(f_min), None if f_max is None else float(f_max)
+        self.power = self.used_f_max = None   # (used_f_max: f_max as the call that filled power resolved it)
+
+    def n_bands(self) -> int:
+        return self.n_mels if self.n_mels > 0 else self.n_fft // 2 + 1
+
+    def n_frames(self, n: int) -> int:
+        return -(-int(n) // self.hop) if n > 0 and self.hop > 0 else 0
+
+    def c_struct(self, n: int, sample_rate: int):
+        """A sbv2_spectrum over a fresh array for a signal of n delivered samples at sample_rate; take() keeps it once the call has succeeded."""
+        i32 = lambda v: v if -2 ** 31 <= v < 2 ** 31 else -1
+        size = self.n_frames(n) * max(self.n_bands(), 0)
+        power = np.zeros(max(size, 1), np.float32)
+        c = _lib.Sbv2Spectrum(i32(self.n_fft), i32(self.hop), i32(self.n_mels), 0, self.f_min,
+                              sample_rate / 2.0 if self.f_max is None else self.f_max, size, power.ctypes.data_as(f32p), 0, 0)
+        return c, power
+
+    def take(self, c, power):
+        assert c.n_frames * c.n_bands == c.capacity, (c.n_frames, c.n_bands, c.capacity)
+        self.power, self.used_f_max = power[:c.capacity].reshape(c.n_frames, c.n_bands), float(c.f_max)
+        return self
+
+    def __repr__(self):
+        return f"Spectrum({self.n_fft}, {self.hop}, n_mels={self.n_mels}, f_min={self.f_min}, f_max={self.f_max})"
+
+
+def spectrum_bands(sample_rate: int, spectrum: Spectrum):
+    """(n_bands, bank): the library's checks of a Spectrum at sample_rate and its mel bank W [n_mels][n_fft // 2 + 1] float32, None for
+    n_mels = 0 (sbv2_spectrum_bands; host only)."""
+    c, _ = spectrum.c_struct(0, int(sample_rate))
+    check(_lib.lib().sbv2_spectrum_bands(int(sample_rate), C.byref(c), None))   # (the ranges, before the bank is sized by them)
+    if spectrum.n_mels == 0:
+        return c.n_bands, None
+    bank = np.zeros((spectrum.n_mels, spectrum.n_fft // 2 + 1), np.float32)
+    check(_lib.lib().sbv2_spectrum_bands(int(sample_rate), C.byref(c), bank.ctypes.data_as(f32p)))
+    return c.n_bands, bank
+
+
+def debug_spectrum(x, sample_rate: int, spectrum: Spectrum, device: int = 0, encoding: str | None = None):
+    """Test hook: the spectrum stage on host samples (sbv2_debug_spectrum).  x: int16 or float32 samples, or with encoding "mulaw" / "alaw"
+    uint8 codes -> spectrum with power [n_frames][n_bands] filled."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if encoding is None and x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"the spectrum is taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"the spectrum of {encoding!r} samples is not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
+    c, power = spectrum.c_struct(x.size, int(sample_rate))
+    check(_lib.lib().sbv2_debug_spectrum(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size, int(sample_rate), C.byref(c)))
+    return spectrum.take(c, power)
+
+
 class PitchTrack:
     """Octave-error repair of a pitch contour (struct sbv2_pitch_track: one best path through the frames' candidates, include/sbv2_hip.h states
     it).  cand_max in (0, 1]: a dip of c at or above it is no candidate; unvoiced_cost and switch_cost in [0, 4], jump_cost in [0, 16], all in
@@ -1156,14 +1217,14 @@ def get_trace(session: Session, name: str, utt: int = 0) -> np.ndarray:
 
 
 # What a Pipeline.fetch_request result holds, by name (None: not there, or there and None)
-FetchResult = namedtuple("FetchResult", "signal stats marks pitch dyn_stats token_pitch", defaults=(None,) * 4)
+FetchResult = namedtuple("FetchResult", "signal stats marks pitch dyn_stats token_pitch spectrum", defaults=(None,) * 5)
 
 
-def _fetch_fields(marks=False, pitch=False, dynamics=False, token_pitch=False):
-    """THE rule of the shape of a Pipeline.fetch_request result, from which of these four options were given: (signal, stats); then
+def _fetch_fields(marks=False, pitch=False, dynamics=False, token_pitch=False, spectrum=False):
+    """THE rule of the shape of a Pipeline.fetch_request result, from which of these five options were given: (signal, stats); then
     marks-or-None if marks or pitch was; then the filled Pitch if pitch was; then the compressor's stats-or-None if dynamics was; then the
-    filled TokenPitch if token_pitch was."""
-    there = (True, True, marks or pitch, pitch, dynamics, token_pitch)
+    filled TokenPitch if token_pitch was; then the filled Spectrum if spectrum was."""
+    there = (True, True, marks or pitch, pitch, dynamics, token_pitch, spectrum)
     return [name for name, t in zip(FetchResult._fields, there) if t]
 
 
@@ -1301,13 +1362,14 @@ class Pipeline:
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
-                      voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0):
+                      voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0, spectrum=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above.  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
         read: the requests that share a run are fetched one by one from the same ticket.
-        Whatever is asked for, this is ONE call of sbv2_pipeline_fetch_request_formant, the widest of the C symbols, with NULL for every stage
-        that is not; the shape of the result follows _fetch_fields.
+        Whatever is asked for short of a spectrum, this is ONE call of sbv2_pipeline_fetch_request_formant with NULL for every stage that is
+        not; with a spectrum it is the same call of sbv2_pipeline_fetch_request_spectrum, the widest of the C symbols.  The shape of the result
+        follows _fetch_fields.
         marks=True: (signal, stats, Marks): the listed rows' token spans on the delivered timeline, with
         their levels (levels=False: timing only, no kernel) and, with env_hop > 0 delivered samples, the envelope.  The signal and stats are
         those of the same call without marks.
@@ -1324,7 +1386,9 @@ class Pipeline:
         voice is, and the returned tuple gains a last element: that TokenPitch with applied [n] (the ratio used per token) and src_f0 [n]
         (the token's measured mean f0, 0 without a voiced frame) filled.  All zeros: the bytes of the call without.
         formant_scale: in [0.5, 2] -> the listed rows' formants are moved by that factor in the shifter's gather, whatever the voice is
-        (model.Formant states it); the returned tuple is that of the call without.  1.0: exactly that call."""
+        (model.Formant states it); the returned tuple is that of the call without.  1.0: exactly that call.
+        spectrum: a Spectrum -> the returned tuple gains a last element: that Spectrum with power [n_frames][n_bands] of the delivered signal
+        filled.  Everything else is that of the same call without.  A library without the symbol is refused, never served without."""
         fm = None if formant_scale == 1.0 else Formant(formant_scale)   # (a NaN is carried on and refused by the library)
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
@@ -1343,6 +1407,7 @@ class Pipeline:
         dst_stats = None if dynamics is None or dynamics.is_identity() else np.zeros(3, np.float64)
         cp, parr = pitch.c_struct(out_len) if pitch is not None else (None, None)
         ctp, tparr = token_pitch.c_struct() if token_pitch is not None else (None, None)
+        csp, sparr = spectrum.c_struct(out_len, fmt.sample_rate) if spectrum is not None else (None, None)
         m = cm = None
         if marks:
             ntok = int(sum(int(b.t_lens[r]) for r in rw))
@@ -1355,14 +1420,22 @@ class Pipeline:
                                 _f64p(m.env_peak) if env_hop > 0 else None, 0)
         ref = lambda c: C.byref(c) if c is not None else None   # (NULL for every stage not asked for; a struct is read during the call only)
         opt = lambda o: ref(o.c if o is not None else None)
-        check(_lib.lib().sbv2_pipeline_fetch_request_formant(
-            self.h, b.ticket, C.byref(req), opt(voice), opt(track), opt(dynamics), ref(ctp), opt(fm), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
-            C.byref(got), _f64p(stats) if nstats else None, _f64p(dst_stats) if dst_stats is not None else None, ref(cm), ref(cp)))
+        args = (self.h, b.ticket, C.byref(req), opt(voice), opt(track), opt(dynamics), ref(ctp), opt(fm), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
+                C.byref(got), _f64p(stats) if nstats else None, _f64p(dst_stats) if dst_stats is not None else None, ref(cm), ref(cp))
+        if spectrum is None:
+            check(_lib.lib().sbv2_pipeline_fetch_request_formant(*args))
+        else:
+            fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_spectrum", None)
+            if fn is None:
+                raise Sbv2Error("a spectrum needs a library with sbv2_pipeline_fetch_request_spectrum: the request is not served without it")
+            check(fn(*args, C.byref(csp)))
         if marks:
             assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
         res = FetchResult(dst[:got.value].tobytes() if flac else dst[:got.value], stats, m, pitch.take(cp, parr) if pitch is not None else None,
-                          dst_stats, token_pitch.take(tparr) if token_pitch is not None else None)
-        return fetch_result(res, marks=bool(marks), pitch=pitch is not None, dynamics=dynamics is not None, token_pitch=token_pitch is not None)
+                          dst_stats, token_pitch.take(tparr) if token_pitch is not None else None,
+                          spectrum.take(csp, sparr) if spectrum is not None else None)
+        return fetch_result(res, marks=bool(marks), pitch=pitch is not None, dynamics=dynamics is not None, token_pitch=token_pitch is not None,
+                            spectrum=spectrum is not None)
 
     def close(self):
         if self.h:

@@ -16,6 +16,7 @@ tests/test_gpu_parity.py), so the WAV is the same as the sequential loop's given
 The text front-end (G2P, tokenizer: tts_util.rs:14-155) is out of scope: callers pass per-sentence
 dicts {input_ids, word2ph, phones, tones, langs} exactly as parse_text produces them, or None for an empty line.
 """
+import base64
 import copy
 import json
 import struct
@@ -53,6 +54,10 @@ class SynthesizeOptions:
     pitch_hz (new; easy_synthesize_marks only, refused everywhere else): the speech marks carry a pitch contour of pitch_hz frames per second
     (an integer in [1, 1000]; sample_rate // pitch_hz delivered samples per frame), estimated on the device from the delivered samples within
     [pitch_min_hz, pitch_max_hz] (model.Pitch).
+    spectrum_mels (new; easy_synthesize_marks and the batcher with marks only, refused everywhere else): the speech marks carry the spectrum of
+    the delivered samples (model.Spectrum): spectrum_mels Slaney mel bands in [1, 128] between spectrum_fmin (0) and spectrum_fmax (half the
+    rate), or with 0 the spectrum_fft // 2 + 1 bins; spectrum_fft (a multiple of 16 in [64, 2048]; default: the multiple of 32 nearest to 25 ms, a tie going up)
+    and spectrum_hop (delivered samples per frame; default sample_rate // 100).  The other four fields need spectrum_mels.
     pitch_scale in [0.5, 2] / intonation_scale in [0, 2] (new; checked here): the voice is raised or lowered, its melody flattened or
     exaggerated about its mean, by a length-preserving overlap-add of the synthesized rows on the device before anything else of the output
     chain (model.Voice); whole-signal routes only (easy_synthesize, easy_synthesize_marks, the batcher), refused on streams.  The defaults
@@ -91,7 +96,11 @@ class SynthesizeOptions:
                  pitch_hz=None, pitch_min_hz=70.0, pitch_max_hz=600.0, pitch_scale=1.0, intonation_scale=1.0, pitch_track=False,
                  compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0, token_pitch=None, token_pitch_kind="hz",
                  token_pitch_smooth=2, formant_scale=1.0, assist=None, assist_weight=0.7, voice_pivot_hz=None, level_target=None,
-                 level_range=12.0, level_slew=3.0, level_hold=10):
+                 level_range=12.0, level_slew=3.0, level_hold=10, spectrum_mels=None, spectrum_fft=None, spectrum_hop=None, spectrum_fmin=0.0,
+                 spectrum_fmax=None):
+        self.spectrum_mels, self.spectrum_fft, self.spectrum_hop = spectrum_mels, spectrum_fft, spectrum_hop
+        self.spectrum_fmin, self.spectrum_fmax = spectrum_fmin, spectrum_fmax
+        spectrum_options(self, None)   # (the fields' types; the ranges need the rate)
         self.voice_pivot_hz = check_voice_pivot(voice_pivot_hz)
         self.level_target, self.level_range, self.level_slew, self.level_hold = level_target, level_range, level_slew, level_hold
         if level_target is not None:
@@ -463,6 +472,70 @@ def refuse_pitch(options, what: str):
                               "(easy_synthesize_marks) instead")
 
 
+class SpectrumError(model.Sbv2Error):
+    """A spectrum field the request itself is at fault for (a bad value, a route that carries no spectrum): REST answers 400."""
+
+
+SPECTRUM_FIELDS = ("spectrum_mels", "spectrum_fft", "spectrum_hop", "spectrum_fmin", "spectrum_fmax")
+
+
+def spectrum_options(options, rate):
+    """The model.Spectrum of a request with marks (None without spectrum_mels).  Bad types are refused always, the ranges once the delivered
+    rate is known (rate None: the types alone), by the library's own host check, before any GPU work."""
+    mels, fft, hop = (getattr(options, k, None) for k in SPECTRUM_FIELDS[:3])
+    fmin, fmax = getattr(options, "spectrum_fmin", 0.0), getattr(options, "spectrum_fmax", None)
+    for name, v in (("spectrum_mels", mels), ("spectrum_fft", fft), ("spectrum_hop", hop)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+            raise SpectrumError(f"{name} must be an integer: {v!r}")
+    for name, v in (("spectrum_fmin", fmin), ("spectrum_fmax", fmax)):
+        if (v is not None or name == "spectrum_fmin") and (isinstance(v, bool) or not isinstance(v, (int, float))):
+            raise SpectrumError(f"{name} must be a number: {v!r}")
+    if mels is None:
+        if fft is not None or hop is not None or fmin != 0.0 or fmax is not None:
+            raise SpectrumError("spectrum_fft / spectrum_hop / spectrum_fmin / spectrum_fmax describe a spectrum: name spectrum_mels (0 = the bins) as well")
+        return None
+    if rate is None:
+        return None
+    if fft is None:   # the multiple of 32 nearest to 25 ms
+        fft = min(max(32 * int(rate * 0.025 / 32 + 0.5), 64), 2048)
+    sp = model.Spectrum(fft, rate // 100 if hop is None else hop, mels, fmin, fmax)
+    try:
+        model.spectrum_bands(rate, sp)
+    except SpectrumError:
+        raise
+    except model.Sbv2Error as e:
+        raise SpectrumError(str(e)) from None
+    return sp
+
+
+def refuse_spectrum(options, what: str):
+    """The spectrum fields where no marks are returned: refused, with the route that carries a spectrum."""
+    if any(getattr(options, k, d) != d for k, d in zip(SPECTRUM_FIELDS, (None, None, None, 0.0, None))):
+        raise SpectrumError(f"spectrum_mels and its fields need the speech marks of a whole signal: {what} carries none, ask /synthesize_marks "
+                            "(easy_synthesize_marks) instead")
+
+
+def require_spectrum(pipe, options):
+    """A request with a spectrum needs a pipeline whose fetch_request takes it: an older one is refused, not served without."""
+    if getattr(options, "spectrum_mels", None) is None:
+        return
+    import inspect
+    try:
+        params = inspect.signature(pipe.fetch_request).parameters
+    except (TypeError, ValueError):
+        params = {}
+    if "spectrum" not in params and not any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
+        raise model.Sbv2Error(f"spectrum_mels needs a pipeline whose fetch_request takes spectrum: {type(pipe).__name__} does not, and the "
+                              "request is not served without its spectrum")
+
+
+def spectrum_dict(sp) -> dict:
+    """The "spectrum" block of a marks dict from a filled model.Spectrum: db = 10 log10(max(power, 1e-10)) in f64, as little-endian float32."""
+    db = (10.0 * np.log10(np.maximum(np.asarray(sp.power, np.float64), 1e-10))).astype("<f4")
+    return {"n_fft": int(sp.n_fft), "hop": int(sp.hop), "n_bands": int(db.shape[1]), "f_min": float(sp.f_min), "f_max": float(sp.used_f_max),
+            "shape": [int(db.shape[0]), int(db.shape[1])], "db": base64.b64encode(db.tobytes()).decode("ascii")}
+
+
 def voice_options(options):
     """The model.Voice of a request (None at the defaults: the request is then the call it always was)."""
     p, s = float(getattr(options, "pitch_scale", 1.0)), float(getattr(options, "intonation_scale", 1.0))
@@ -624,17 +697,22 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
         kw.update(gain=ln, flac=plan.flac)
-        pitch = None
+        pitch = spec = None
         if marks is not None:
             kw.update(marks=True, env_hop=envelope_hop(options, fmt.sample_rate))
             pitch = pitch_options(options, fmt.sample_rate)
             if pitch is not None:
                 kw["pitch"] = pitch
+            spec = spectrum_options(options, fmt.sample_rate)
+            if spec is not None:
+                require_spectrum(pipe, options)
+                kw["spectrum"] = spec
         track = track_options(options)
         if track is not None and (pitch is not None or shifts):   # (it needs a contour or a shift)
             kw["track"] = track
         got = model.split_fetch_result(pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw), marks=marks is not None,
-                                       pitch=pitch is not None, dynamics=dyn is not None, token_pitch=tp is not None)
+                                       pitch=pitch is not None, dynamics=dyn is not None, token_pitch=tp is not None,
+                                       **({"spectrum": True} if spec is not None else {}))
         out, stats, dstats = got.signal, got.stats, got.dyn_stats
         if marks is not None:
             marks.append(marks_dict(plan.utts, plan.live, fmt, got.marks, got.pitch, **({"tracked": True} if "track" in kw and pitch is not None else {})))
@@ -644,6 +722,8 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
                 marks[-1]["pitch_edit"] = pitch_edit_dict(got.token_pitch)
             if fq is not None:
                 marks[-1]["formant_scale"] = fq
+            if spec is not None:
+                marks[-1]["spectrum"] = spectrum_dict(got.spectrum)
         if dstats is not None and dynamics_stats is not None:
             dynamics_stats.append([float(v) for v in dstats])
         if stats is not None and loudness_stats is not None:
@@ -670,6 +750,7 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     loudness_stats are then those of the compressed signal.
     = finish_request over all rows of a run that holds this request alone (batcher.RequestBatcher: the same, several requests to a run)."""
     refuse_pitch(options, "easy_synthesize (/synthesize)")
+    refuse_spectrum(options, "easy_synthesize (/synthesize)")
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
     require_formant(pipe, plan.options)   # (before any GPU work)
     require_assist(pipe, plan.options)
@@ -691,6 +772,8 @@ def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, styl
     require_assist(pipe, plan.options)
     envelope_hop(plan.options, plan.fmt.sample_rate)   # a bad envelope_hz is refused before any GPU work
     pitch_options(plan.options, plan.fmt.sample_rate)  # ... and so is a bad pitch_hz or range
+    spectrum_options(plan.options, plan.fmt.sample_rate)   # ... and a bad spectrum
+    require_spectrum(pipe, plan.options)
     if noise_seed is None:
         noise_seed = model.fresh_noise_seed()
     b = pipe.prepare(plan.utts, sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=noise_scale,
@@ -872,6 +955,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     refuse_token_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_dynamics(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    refuse_spectrum(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if pitch:
         if not levels:
             raise model.Sbv2Error("pitch=True on a stream comes with its speech marks: pass levels=True as well")

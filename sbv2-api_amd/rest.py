@@ -52,6 +52,11 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     token), "src_f0_hz" (the token's measured mean, null without a voiced frame)}.  A bad value, kind or smoothing and a list of
                     another length than the text's token count (the message names the expected count) answer 400, and so do the stream routes
                     for any list.
+  spectrum_mels = null (new; /synthesize_marks only, batched or not): the marks carry "spectrum": {"n_fft", "hop", "n_bands", "f_min", "f_max",
+                    "shape": [n_frames, n_bands], "db": base64 of little-endian float32, 10 log10(max(power, 1e-10))}, the Slaney mel bands (0:
+                    the spectrum_fft // 2 + 1 bins) of the delivered samples, reduced on the device.  spectrum_fft (null: the multiple of 32
+                    nearest to 25 ms), spectrum_hop (null: sample_rate // 100), spectrum_fmin = 0, spectrum_fmax (null: half the rate).  A bad
+                    value answers 400; so does any of the five fields on every other route, naming /synthesize_marks.
   formant_scale = 1.0 (new; the same routes): the voice's formants moved by that factor in [0.5, 2], f0 and the length left alone (below 1 a
                     larger, darker speaker, above 1 a smaller, brighter one); made by the shifter of pitch_scale on the device, it composes with
                     pitch_scale, intonation_scale, pitch_track and token_pitch.  The marks of /synthesize_marks then carry "formant_scale".  The
@@ -204,6 +209,11 @@ def make_app(holder, batching=None):
         assist_text: Optional[str] = None   # new: a second text whose DeBERTa features steer the delivery (upstream's assist_text); all four routes
         assist_text_weight: float = 0.7     # its weight, [0, 1] (upstream's default); 0 = none
         formant_scale: float = 1.0          # new: moves the voice's formants, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); 400 on the stream routes without voice_pivot_hz
+        spectrum_mels: Optional[int] = None   # new: /synthesize_marks only (400 elsewhere): the marks carry "spectrum"; mel bands in [1, 128], 0 = the bins
+        spectrum_fft: Optional[int] = None    # window (delivered samples), a multiple of 16 in [64, 2048]; null = the multiple of 32 nearest to 25 ms
+        spectrum_hop: Optional[int] = None    # delivered samples per frame; null = sample_rate // 100
+        spectrum_fmin: float = 0.0            # the mel bank's range (Hz)
+        spectrum_fmax: Optional[float] = None # null = sample_rate / 2
         voice_pivot_hz: Optional[Union[float, List[float]]] = None   # new: /synthesize_stream, /synthesize_stream_marks: the f0 (Hz, [70, 600]) that intonation_scale pivots about, one number or one per sentence; it opens the three scales on the stream routes; 400 elsewhere
 
     class SynthesizeMarksRequest(SynthesizeRequest):
@@ -261,6 +271,9 @@ def make_app(holder, batching=None):
                                                  if getattr(req, "token_pitch", None) is not None else {}),
                                               **({"formant_scale": req.formant_scale} if getattr(req, "formant_scale", 1.0) != 1.0 else {}),
                                               **({"voice_pivot_hz": req.voice_pivot_hz} if getattr(req, "voice_pivot_hz", None) is not None else {}),
+                                              **({k: getattr(req, k) for k in orchestrator.SPECTRUM_FIELDS}
+                                                 if any(getattr(req, k, d) != d for k, d in zip(orchestrator.SPECTRUM_FIELDS, (None, None, None, 0.0, None)))
+                                                 else {}),
                                               **({"level_target": req.level_target, "level_range": req.level_range, "level_slew": req.level_slew,
                                                   "level_hold": req.level_hold} if getattr(req, "level_target", None) is not None else {}),
                                               **({"assist": req.assist_text or None, "assist_weight": req.assist_text_weight}
@@ -272,9 +285,10 @@ def make_app(holder, batching=None):
 
     def synthesize(req: SynthesizeRequest):
         try:
+            orchestrator.refuse_spectrum(req, "/synthesize")   # (the route first: it is what the client has to change)
             with lock:
                 wav = holder.easy_synthesize(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
-        except orchestrator.TokenPitchError as e:
+        except (orchestrator.TokenPitchError, orchestrator.SpectrumError) as e:
             return bad_request(e)
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -284,10 +298,11 @@ def make_app(holder, batching=None):
         # a plain function: it runs on a worker thread, so neither the lock (which a stream holds until its last byte has left, and gives back
         # only with the event loop's help) nor parse_text, a model load or an eviction's drain inside the holder ever stall the event loop
         try:
+            orchestrator.refuse_spectrum(req, "/synthesize")
             with lock:                        # parse and queue only: the answer is awaited without it
                 fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching)
             wav = fut.result()
-        except orchestrator.TokenPitchError as e:
+        except (orchestrator.TokenPitchError, orchestrator.SpectrumError) as e:
             return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -306,7 +321,7 @@ def make_app(holder, batching=None):
                     fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching,
                                                          marks=True)
                 audio, marks = fut.result()
-        except orchestrator.TokenPitchError as e:
+        except (orchestrator.TokenPitchError, orchestrator.SpectrumError) as e:
             return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -328,6 +343,7 @@ def make_app(holder, batching=None):
             orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.check_assist(None, getattr(req, "assist_text_weight", 0.7))   # (a stream takes an assist; a bad weight is the request's fault)
+            orchestrator.refuse_spectrum(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=400)
         return None
