@@ -320,6 +320,46 @@ inline std::vector<double> stream_leveler_stats(sbv2_stream* s) {
     return st;
 }
 
+// Not in the reference (sbv2_stream_spectrum in sbv2_hip.h states it): the spectrum of a request STREAM's delivered samples, frame by frame.
+struct StreamSpectrum {
+    int32_t n_fft = 400, hop = 160, n_mels = 80;
+    double f_min = 0.0, f_max = 8000.0;
+    int64_t n_frames = 0;   // out, set by stream_begin_request_spectrum: ceil(total_samples / hop)
+    int32_t n_bands = 0;    // out: n_mels, or n_fft / 2 + 1
+    sbv2_stream_spectrum c_struct() const { return sbv2_stream_spectrum{n_fft, hop, n_mels, 0, f_min, f_max}; }
+};
+// sbv2_stream_begin_request_spectrum: sbv2_stream_begin_request_leveler with the spectrum of the delivered samples; spectrum == nullptr is
+// exactly that call.
+inline sbv2_stream* stream_begin_request_spectrum(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch& batch, const sbv2_utt_options* opts, Assist* assist,
+                                                  const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                                  const sbv2_stream_request& rq, StreamVoice* voice, const StreamLeveler* leveler,
+                                                  StreamSpectrum* spectrum, const sbv2_stream_levels* lv = nullptr,
+                                                  const sbv2_stream_pitch* sp = nullptr, int64_t* total_samples = nullptr, int64_t* n_tokens = nullptr,
+                                                  int64_t* n_env = nullptr, int64_t* n_pitch = nullptr) {
+    sbv2_stream* s = nullptr;
+    sbv2_stream_leveler c{};
+    sbv2_stream_spectrum q{};
+    if (leveler) c = leveler->c_struct();
+    if (spectrum) q = spectrum->c_struct();
+    int64_t n_spec = 0;
+    int32_t n_bands = 0;
+    check(sbv2_stream_begin_request_spectrum(bert, vits, &batch, opts, assist ? assist->c_struct() : nullptr, token_ids, s_lens, word2ph, chunk_frames,
+                                             &rq, lv, sp, voice ? voice->c_struct() : nullptr, leveler ? &c : nullptr, spectrum ? &q : nullptr, &s,
+                                             total_samples, n_tokens, n_env, n_pitch, &n_spec, &n_bands));
+    if (spectrum) spectrum->n_frames = n_spec, spectrum->n_bands = n_bands;
+    return s;
+}
+// sbv2_stream_next_spectrum: the frames completed since the previous call, appended to power ([frames][n_bands]); returns how many
+inline int64_t stream_next_spectrum(sbv2_stream* s, const StreamSpectrum& spectrum, std::vector<float>* power) {
+    const size_t at = power->size();
+    power->resize(at + (size_t)(spectrum.n_frames * spectrum.n_bands));   // (room for everything that can be pending)
+    sbv2_stream_spectrum_part part{spectrum.n_frames * spectrum.n_bands, power->data() + at, 0, 0, 0};
+    const int rc = sbv2_stream_next_spectrum(s, &part);
+    power->resize(at + (rc == 0 ? (size_t)(part.n * spectrum.n_bands) : 0));
+    check(rc);
+    return part.n;
+}
+
 }  // namespace sbv2_core
 
 #endif

@@ -702,8 +702,8 @@ int sbv2_debug_voice_formant(int device, const float* x, const int64_t* lens, in
  *   B_ref, next to E32, the same for an f32 restatement in numpy (f32 operands, f32 matmul): see DESIGN.md (8w) for the figures.
  * Range.  The pair has f16's exponent range and a[i] is split times 2^10 (so that quiet signals keep the 22 bits): an f32 value with |a[i]|
  *   beyond 63.97 is clamped there by the split (a NaN sample likewise); delivered samples are within [-1, 1].
- * Not built: the spectrum on streams (sbv2_stream_*) and on sbv2_node_*, the HTK mel scale, reflect padding, phase output, MFCCs, an
- *   envelope-based formant shifter. */
+ * On a stream the same spectrum comes frame by frame: sbv2_stream_begin_request_spectrum / sbv2_stream_next_spectrum below.
+ * Not built: the spectrum on sbv2_node_*, the HTK mel scale, reflect padding, phase output, MFCCs, an envelope-based formant shifter. */
 typedef struct sbv2_spectrum {
     int32_t n_fft, hop, n_mels, reserved; /* in; reserved must be 0 */
     double f_min, f_max;                  /* in: Hz (looked at with n_mels = 0 too) */
@@ -1212,6 +1212,53 @@ int sbv2_stream_leveler_stats(sbv2_stream* s, double* stats /* [6] */);
 int sbv2_debug_leveler_stream(int device, const double* x, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
                               const sbv2_stream_level* level, const sbv2_stream_leveler* leveler, double* out_x, int64_t* out_per_push,
                               double* out_gain_db, int64_t gain_capacity, double* stats);
+
+/* ---- new: the spectrum of a stream, computed chunk by chunk ON THE DEVICE.
+ * sbv2_stream_begin_request_leveler with, besides, the spectrum of sbv2_spectrum over the DELIVERED samples of the stream (the samples the
+ *   levels and the pitch are taken of; on a level stream those the limiter emits), by sbv2_spectrum's convention unchanged: the rate is the
+ *   format's (fmt NULL = the identity format, 44100 Hz), frame f has its centre at f hop + hop / 2 and its window [centre - n_fft / 2, centre +
+ *   n_fft / 2), positions outside [0, total_samples) read as 0, *n_spec = ceil(total_samples / hop), *n_bands = n_mels or n_fft / 2 + 1.
+ * Completion.  Frame f is complete once min(f hop + hop / 2 + n_fft / 2, total_samples) <= D, D as for sbv2_stream_next_marks: frames complete
+ *   in order and about n_fft / 2 samples late, everything that remains with the last chunk.
+ * Bits.  The device keeps the last n_fft delivered samples from replay to replay, in the sample's own type (two copies of at most 8 KB, used
+ *   alternately); a frame's window is read from them and from the replay's samples and then takes the one-shot kernel's own tile arithmetic.
+ *   So power equals sbv2_debug_spectrum / sbv2_pipeline_fetch_request_spectrum over the same samples bit for bit, for every encoding (f32, s16,
+ *   mu-law, A-law), behind FLAC and behind a level, whatever chunk_frames is.  One launch and one device-to-host copy more per replay; the
+ *   launch splits a replay's frames x the bins (or the mel bands) into groups so that a few hundred frames fill the chip (csrc/spectrum.h
+ *   states the rule; the bits do not depend on it).  Basis, window and bank are formed and uploaded by the begin call, not behind the first
+ *   chunk.  The frames stay on the host (pinned, n_spec n_bands floats) until the stream is freed or the handle begins another.
+ * spectrum == NULL: exactly sbv2_stream_begin_request_leveler: the same launches, the same bytes, *n_spec = 0, sbv2_stream_next_spectrum
+ *   refused.  With a spectrum the audio bytes, sbv2_stream_marks, the stream levels and the stream pitch are those of the same stream without,
+ *   and the stream delivers in order only.
+ * Refused before the handles are looked at: a non-zero reserved and everything sbv2_spectrum's parameters refuse at the format's rate;
+ *   besides, everything sbv2_stream_begin_request_leveler refuses.  n_spec >= 2^30 is refused where n_pitch >= 2^30 is.
+ * Not built: the spectrum on sbv2_node_*; on the plain single-utterance sbv2_stream_begin* entries (a request stream of one row serves them);
+ *   the HTK mel scale, reflect padding, phase output, MFCCs. */
+typedef struct sbv2_stream_spectrum {
+    int32_t n_fft, hop, n_mels, reserved; /* as sbv2_spectrum; reserved must be 0 */
+    double f_min, f_max;                  /* Hz (looked at with n_mels = 0 too) */
+} sbv2_stream_spectrum;
+int sbv2_stream_begin_request_spectrum(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                                       const sbv2_assist* assist /* may be NULL */, const int64_t* token_ids, const int64_t* s_lens,
+                                       const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
+                                       const sbv2_stream_levels* lv /* may be NULL */, const sbv2_stream_pitch* sp /* may be NULL */,
+                                       const sbv2_stream_voice* voice /* may be NULL */, const sbv2_stream_leveler* leveler /* may be NULL */,
+                                       const sbv2_stream_spectrum* spectrum /* may be NULL */, sbv2_stream** out, int64_t* total_samples,
+                                       int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch, int64_t* n_spec, int32_t* n_bands);
+/* Host only: the frames [first, first + n) that became complete since the previous call, power [n][n_bands] as sbv2_spectrum gives it, and
+ * delivered = D.  A capacity (in floats) below n n_bands, or a NULL power with frames pending, is refused with nothing written and nothing
+ * lost: repeat with more room.  Not calling it loses nothing.  Refused on a stream begun without a spectrum. */
+typedef struct sbv2_stream_spectrum_part {
+    int64_t capacity; float* power; int64_t first, n;
+    int64_t delivered;
+} sbv2_stream_spectrum_part;
+int sbv2_stream_next_spectrum(sbv2_stream* s, sbv2_stream_spectrum_part* part);
+/* Test hook: the fed stage on its own.  x[n] (host; encoding and spectrum as sbv2_debug_spectrum) is cut at the ascending positions
+ * cuts[ncuts] into ncuts + 1 pushes (empty ones allowed), each handed a copy of its own samples only; outputs as sbv2_debug_spectrum, and
+ * per_push [ncuts + 1] the frames each push completed.  groups: 0 = the rule of csrc/spectrum.h, 1 .. 8 = that many groups in every launch
+ * (more than the spec allows: the most it allows).  Parameters, capacity and cuts are checked before any device call. */
+int sbv2_debug_stream_spectrum(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
+                               sbv2_spectrum* spectrum, int groups, int64_t* per_push);
 
 /* Test hook: the two kernels on a host plane F [C][ld] (pitch ld, any value >= 1; on the device it lies between NaN words).  Assist sequence a
  * is the columns [a_start[a], a_start[a] + a_len[a]) of F; text column t < L reads source column map[t] (< 0: padding) and belongs to row

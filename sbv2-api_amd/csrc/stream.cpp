@@ -17,8 +17,8 @@ struct sbv2_stream {
     // one sync, and the delivered format
     std::vector<int64_t> durations, offs;
     PcmFmtSpec spec;
-    // the entries sbv2_stream_next_marks and the frames sbv2_stream_next_pitch have handed out so far
-    int64_t tok_out = 0, env_out = 0, pitch_out = 0;
+    // the entries sbv2_stream_next_marks and the frames sbv2_stream_next_pitch / sbv2_stream_next_spectrum have handed out so far
+    int64_t tok_out = 0, env_out = 0, pitch_out = 0, spec_out = 0;
     // what the stream was begun with is the model's to say: its output side, nullptr for a plain stream (native f32)
     const StreamOutput* output() const { return vits->m->stream_output(); }
 };
@@ -418,9 +418,28 @@ int sbv2_stream_begin_request_leveler(sbv2_bert* bert, sbv2_vits* vits, const sb
                                       const sbv2_stream_request* rq, const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp,
                                       const sbv2_stream_voice* voice, const sbv2_stream_leveler* leveler, sbv2_stream** out, int64_t* total_samples,
                                       int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch) {
+    return sbv2_stream_begin_request_spectrum(bert, vits, batch, opts, assist, token_ids, s_lens, word2ph, chunk_frames, rq, lv, sp, voice, leveler,
+                                              nullptr, out, total_samples, n_tokens, n_env, n_pitch, nullptr, nullptr);
+}
+
+// ... and with the spectrum of the same delivered samples, fed by the same pushes (the contract above sbv2_stream_spectrum, include/sbv2_hip.h;
+// StreamSpectrum, spectrum.hip).  spectrum NULL: exactly the call above.  Its fields are checked with the others', before the handles are
+// looked at, at the format's rate.
+int sbv2_stream_begin_request_spectrum(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts, const sbv2_assist* assist,
+                                       const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph, int64_t chunk_frames,
+                                       const sbv2_stream_request* rq, const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp,
+                                       const sbv2_stream_voice* voice, const sbv2_stream_leveler* leveler, const sbv2_stream_spectrum* spectrum,
+                                       sbv2_stream** out, int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch, int64_t* n_spec,
+                                       int32_t* n_bands) {
     API_BEGIN
     StreamMarksSpec marks;
     bool on = levels_spec(lv, &marks);
+    if (spectrum) {
+        SBV2_REQUIRE(spectrum->reserved == 0, "sbv2_stream_spectrum.reserved must be 0");
+        const int rate = rq && rq->fmt ? pcm_format_spec(rq->fmt).rate : PcmFmtSpec().rate;
+        marks.spectrum_spec = spectrum_spec(rate, spectrum->n_fft, spectrum->hop, spectrum->n_mels, spectrum->f_min, spectrum->f_max);
+        marks.spectrum = on = true;
+    }
     StreamLevelerSpec ls;
     if (leveler) {
         ls = stream_leveler_spec(leveler);
@@ -452,6 +471,9 @@ int sbv2_stream_begin_request_leveler(sbv2_bert* bert, sbv2_vits* vits, const sb
     if (n_tokens) *n_tokens = l ? l->n_tok() : 0;
     if (n_env) *n_env = l ? l->n_env() : 0;
     if (n_pitch) *n_pitch = q ? q->n_frames() : 0;
+    const StreamSpectrum* sq = (*out)->output()->spectrum();
+    if (n_spec) *n_spec = sq ? sq->n_frames() : 0;
+    if (n_bands) *n_bands = sq ? sq->spec().n_bands() : 0;
     API_END
 }
 
@@ -506,6 +528,26 @@ int sbv2_stream_next_pitch(sbv2_stream* s, sbv2_stream_pitch_part* part) {
     part->n = n;
     part->delivered = D;
     s->pitch_out += n;
+    API_END
+}
+
+// The spectrum frames completed since the previous call (the rule above sbv2_stream_next_spectrum, include/sbv2_hip.h).  Host only, for the
+// reason given above sbv2_stream_next_marks.
+int sbv2_stream_next_spectrum(sbv2_stream* s, sbv2_stream_spectrum_part* part) {
+    API_BEGIN
+    SBV2_REQUIRE(s && part, "bad arguments");
+    const StreamSpectrum* q = s->output() ? s->output()->spectrum() : nullptr;
+    SBV2_REQUIRE(q, "this stream was begun without a spectrum: begin it with sbv2_stream_begin_request_spectrum");
+    const int64_t D = s->next >= s->calls ? q->total() : s->output()->delivered();
+    const int64_t n = q->complete(D) - s->spec_out, nb = q->spec().n_bands();
+    SBV2_REQUIRE(part->capacity >= n * nb, "spectrum array too small: " + std::to_string(part->capacity) + " < " + std::to_string(n) +
+                                               " pending frames of " + std::to_string(nb) + " bands");
+    SBV2_REQUIRE(n == 0 || part->power, "NULL power with " + std::to_string(n) + " pending frames");
+    if (n) std::memcpy(part->power, q->power_host(s->spec_out), sizeof(float) * (size_t)(n * nb));
+    part->first = s->spec_out;
+    part->n = n;
+    part->delivered = D;
+    s->spec_out += n;
     API_END
 }
 

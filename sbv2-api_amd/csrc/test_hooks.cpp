@@ -2513,6 +2513,49 @@ int sbv2_debug_stream_pitch(int device, const void* x, int encoding, int64_t n, 
     API_END
 }
 
+// The fed spectrum stage (StreamSpectrum, spectrum.hip) on its own, as the hook above feeds the estimator: every push is a COPY of its piece
+// between two guards of a fill pattern.  Parameters, capacity and cuts are checked before any device call.
+int sbv2_debug_stream_spectrum(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
+                               sbv2_spectrum* spectrum, int groups, int64_t* per_push) {
+    API_BEGIN
+    SBV2_REQUIRE(spectrum && per_push && pcm_encoding_known(encoding) && n >= 0 && ncuts >= 0 && (x || n == 0) && (ncuts == 0 || cuts), "bad arguments");
+    SBV2_REQUIRE(groups >= 0 && groups <= kSpectrumMaxGroups, "groups must be in [0, " + std::to_string(kSpectrumMaxGroups) + "]: " + std::to_string(groups));
+    SBV2_REQUIRE(spectrum->reserved == 0, "sbv2_spectrum.reserved must be 0");
+    const SpectrumSpec sp = spectrum_spec(sample_rate, spectrum->n_fft, spectrum->hop, spectrum->n_mels, spectrum->f_min, spectrum->f_max);
+    StreamSpectrum::check(sp, n);
+    const int64_t nf = spectrum_frames(n, sp.hop);
+    SBV2_REQUIRE(spectrum->capacity >= nf * sp.n_bands(), "spectrum array too small: " + std::to_string(spectrum->capacity) + " < " +
+                                                              std::to_string(nf) + " frames of " + std::to_string(sp.n_bands()) + " bands");
+    SBV2_REQUIRE(spectrum->power, "sbv2_spectrum.power must not be NULL");
+    std::vector<int64_t> edge(1, 0);
+    int64_t longest = 0;
+    for (int i = 0; i < ncuts; ++i) {
+        SBV2_REQUIRE(cuts[i] >= edge.back() && cuts[i] <= n, "cuts must ascend within [0, n]");
+        edge.push_back(cuts[i]);
+    }
+    edge.push_back(n);
+    for (size_t i = 0; i + 1 < edge.size(); ++i) longest = std::max(longest, edge[i + 1] - edge[i]);
+    const size_t esz = pcm_encoding_bytes(encoding), guard = 4096;
+    AudioScratch r(device, x, (size_t)n * esz);
+    DeviceBuffer piece;
+    char* pc = static_cast<char*>(piece.reserve((size_t)longest * esz + 2 * guard, (size_t)longest * esz + 2 * guard, r.s));
+    HIP_CHECK(hipMemsetAsync(pc, 0x5A, (size_t)longest * esz + 2 * guard, r.s));
+    StreamSpectrum st;
+    st.begin(sp, encoding, n, longest, r.s, groups);
+    for (int i = 0; i <= ncuts; ++i) {
+        const int64_t len = edge[i + 1] - edge[i];
+        // (stream order: the previous push's launch has read the piece before this copy overwrites it)
+        if (len) HIP_CHECK(hipMemcpyAsync(pc + guard, r.x.as<char>() + (size_t)edge[i] * esz, (size_t)len * esz, hipMemcpyDeviceToDevice, r.s));
+        per_push[i] = st.push(pc + guard, edge[i], len, r.s);
+    }
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    SBV2_REQUIRE(st.complete(st.fed()) == nf, "internal: frames left incomplete after the last push");
+    if (nf > 0) std::memcpy(spectrum->power, st.power_host(0), sizeof(float) * (size_t)(nf * sp.n_bands()));
+    spectrum->n_frames = nf;
+    spectrum->n_bands = sp.n_bands();
+    API_END
+}
+
 // ---- the repeated-launch hooks (run_repeated above): operands as in the one-launch hook of the same kernel, two inputs xa / xb, ya / yb = the first result of
 // each; prev (may be null) = what every repetition accumulates onto
 int sbv2_debug_repeat_respair(int device, const float* xa, const float* xb, const float* w1, const float* w2, const float* b1, const float* b2, int64_t C,

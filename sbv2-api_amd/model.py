@@ -1005,6 +1005,31 @@ def debug_stream_pitch(x, cuts, sample_rate: int, pitch: Pitch, device: int = 0,
     return pitch.take(c, arrays), c3[:c.n_frames], voiced[:c.n_frames], per_push
 
 
+def debug_stream_spectrum(x, cuts, sample_rate: int, spectrum: Spectrum, device: int = 0, encoding: str | None = None, groups: int = 0):
+    """Test hook: the fed spectrum stage on its own (sbv2_debug_stream_spectrum).  x as for debug_spectrum, cut at the ascending positions
+    `cuts` into len(cuts) + 1 pushes; groups: 0 = the library's rule, 1 .. 8 = that many groups in every launch (at most what the spec allows)
+    -> (spectrum with power filled, per_push [len(cuts) + 1], the frames each push completed)."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if encoding is None and x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"the spectrum is taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"the spectrum of {encoding!r} samples is not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
+    cuts = np.ascontiguousarray(np.asarray(cuts, np.int64).reshape(-1))
+    c, power = spectrum.c_struct(x.size, int(sample_rate))
+    per_push = np.zeros(cuts.size + 1, np.int64)
+    check(_lib.lib().sbv2_debug_stream_spectrum(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size,
+                                                cuts.ctypes.data_as(i64p) if cuts.size else None, cuts.size, int(sample_rate), C.byref(c), int(groups),
+                                                per_push.ctypes.data_as(i64p)))
+    return spectrum.take(c, power), per_push
+
+
+def stream_spectrum_complete(D: int, hop: int, n_fft: int, total: int) -> int:
+    """The completion rule of a stream's spectrum (above sbv2_stream_next_spectrum): the rule of stream_pitch_complete with n_fft // 2 in the
+    place of tau_max."""
+    return stream_pitch_complete(D, hop, int(n_fft) // 2, total)
+
+
 def stream_pitch_complete(D: int, hop: int, tau_max: int, total: int) -> int:
     """The completion rule of a stream's pitch contour (above sbv2_stream_next_pitch): the number of frames f < ceil(total / hop) with
     min(f hop + hop // 2 + tau_max, total) <= D.  They are the first ones: frames complete in order."""
@@ -1508,11 +1533,18 @@ class StreamHandle:
     runs as the request stream with gaps=[0].
     leveler (a StreamLeveler; needs level): the level's gain_db becomes the starting gain of a loudness follower carried chunk by chunk
     (sbv2_stream_begin_request_leveler) in front of the level's limiter; the delivery rule is the level stream's; leveler_stats() after the
-    end.  A single utterance runs as the request stream with gaps=[0]."""
+    end.  A single utterance runs as the request stream with gaps=[0].
+    spectrum (a Spectrum: n_fft, hop, n_mels, f_min, f_max at the stream's delivered rate): the spectrum of the delivered samples is computed on
+    the device chunk by chunk (sbv2_stream_begin_request_spectrum): n_spec frames of n_bands in all, next_spectrum() hands out the ones the
+    pieces taken so far completed, with the bits of debug_spectrum over the whole delivered signal.  A single utterance runs as the request
+    stream with gaps=[0]."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
                  level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, track=None,
-                 voice: "StreamVoice | None" = None, token_pitch=None, leveler: "StreamLeveler | None" = None, **kw):
+                 voice: "StreamVoice | None" = None, token_pitch=None, leveler: "StreamLeveler | None" = None,
+                 spectrum: "Spectrum | None" = None, **kw):
+        if spectrum is not None and not hasattr(_lib.lib(), "sbv2_stream_begin_request_spectrum"):
+            raise Sbv2Error("this library has no sbv2_stream_begin_request_spectrum: a stream cannot carry a spectrum (it is never served without)")
         if leveler is not None and not hasattr(_lib.lib(), "sbv2_stream_begin_request_leveler"):
             raise Sbv2Error("this library has no sbv2_stream_begin_request_leveler: a stream cannot follow a loudness target (it is never served "
                             "unlevelled)")
@@ -1532,7 +1564,8 @@ class StreamHandle:
         self.levels, self.env_hop, self.n_tokens, self.n_env, self._marks_buf = bool(levels), int(env_hop), 0, 0, None
         self.pitch, self.n_pitch, self._pitch_buf = pitch, 0, None
         self.voice, self.leveler = voice, leveler
-        if (self.levels or self.env_hop or pitch is not None or voice is not None or leveler is not None) and not self.request:
+        self.spectrum, self.n_spec, self.n_bands, self._spec_buf = spectrum, 0, 0, None
+        if (self.levels or self.env_hop or pitch is not None or voice is not None or leveler is not None or spectrum is not None) and not self.request:
             if gaps is not None:
                 raise Sbv2Error("gaps= belongs to a stream over a list of utterances")
             utt, gaps, self.request = [utt], [0], True
@@ -1554,8 +1587,8 @@ class StreamHandle:
             rq = _lib.Sbv2StreamRequest(gp, C.pointer(fmt.c) if fmt is not None else None, C.pointer(level.c) if level is not None else None,
                                         int(self.flac), 0)
             opts = C.byref(self.b.opts) if self.b.opts is not None else None
-            if self.b.assist is not None or voice is not None or leveler is not None:
-                # an assisted row, a shifted voice or a leveler: the one entry that takes them, with the levels and the pitch the stream may carry (NULL: without)
+            if self.b.assist is not None or voice is not None or leveler is not None or spectrum is not None:
+                # an assisted row, a shifted voice, a leveler or a spectrum: the one entry that takes them, with the levels and the pitch the stream may carry (NULL: without)
                 on = self.levels or self.env_hop
                 lv = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)) if on or pitch is not None else None
                 sp = None
@@ -1566,7 +1599,17 @@ class StreamHandle:
                         C.byref(lv) if lv is not None else None, C.byref(sp) if sp is not None else None)
                 tail = (C.byref(self.h), C.byref(tot), C.byref(nt), C.byref(ne), C.byref(nq))
                 cv, _keep = voice.c_struct(len(utt)) if voice is not None else (None, None)
-                if leveler is not None:
+                if spectrum is not None:
+                    i32 = lambda v: v if -2 ** 31 <= v < 2 ** 31 else -1
+                    rate = fmt.sample_rate if fmt is not None else 44100
+                    cs = _lib.Sbv2StreamSpectrum(i32(spectrum.n_fft), i32(spectrum.hop), i32(spectrum.n_mels), 0, spectrum.f_min,
+                                                 rate / 2.0 if spectrum.f_max is None else spectrum.f_max)
+                    ns, nb = C.c_int64(), C.c_int32()
+                    check(l.sbv2_stream_begin_request_spectrum(*head, C.byref(cv) if cv is not None else None,
+                                                               C.byref(leveler.c) if leveler is not None else None, C.byref(cs), *tail, C.byref(ns),
+                                                               C.byref(nb)))
+                    self.n_spec, self.n_bands = ns.value, nb.value
+                elif leveler is not None:
                     check(l.sbv2_stream_begin_request_leveler(*head, C.byref(cv) if cv is not None else None, C.byref(leveler.c), *tail))
                 elif voice is not None:
                     check(l.sbv2_stream_begin_request_voice(*head, C.byref(cv), *tail))
@@ -1674,6 +1717,16 @@ class StreamHandle:
         part = _lib.Sbv2StreamPitchPart(self.n_pitch, _f64p(f0), _f64p(ap), lag.ctypes.data_as(C.POINTER(C.c_int32)), 0, 0, 0)
         check(_lib.lib().sbv2_stream_next_pitch(self.h, C.byref(part)))
         return int(part.first), f0[:part.n].copy(), ap[:part.n].copy(), lag[:part.n].copy(), int(part.delivered)
+
+    def next_spectrum(self):
+        """(first, power, delivered): the frames of the spectrum that the pieces taken since the previous call completed
+        (sbv2_stream_next_spectrum; host only; the rule: stream_spectrum_complete).  power [n][n_bands] float32, linear, the frames [first,
+        first + n).  Refused on a stream begun without spectrum=."""
+        if self._spec_buf is None:   # (sized for the whole stream once)
+            self._spec_buf = np.zeros(max(self.n_spec * self.n_bands, 1), np.float32)
+        part = _lib.Sbv2StreamSpectrumPart(self.n_spec * self.n_bands, self._spec_buf.ctypes.data_as(f32p), 0, 0, 0)
+        check(_lib.lib().sbv2_stream_next_spectrum(self.h, C.byref(part)))
+        return int(part.first), self._spec_buf[:part.n * self.n_bands].reshape(part.n, self.n_bands).copy(), int(part.delivered)
 
     def marks(self):
         """(start, end): the spans of the utterance's tokens in delivered samples of this stream (sbv2_stream_marks; host only, complete from

@@ -529,11 +529,16 @@ def require_spectrum(pipe, options):
                               "request is not served without its spectrum")
 
 
+def spectrum_db(power) -> dict:
+    """{"shape", "db"} of power [n_frames][n_bands]: db = 10 log10(max(power, 1e-10)) in f64, as base64 of little-endian float32."""
+    db = (10.0 * np.log10(np.maximum(np.asarray(power, np.float64), 1e-10))).astype("<f4")
+    return {"shape": [int(db.shape[0]), int(db.shape[1])], "db": base64.b64encode(db.tobytes()).decode("ascii")}
+
+
 def spectrum_dict(sp) -> dict:
-    """The "spectrum" block of a marks dict from a filled model.Spectrum: db = 10 log10(max(power, 1e-10)) in f64, as little-endian float32."""
-    db = (10.0 * np.log10(np.maximum(np.asarray(sp.power, np.float64), 1e-10))).astype("<f4")
-    return {"n_fft": int(sp.n_fft), "hop": int(sp.hop), "n_bands": int(db.shape[1]), "f_min": float(sp.f_min), "f_max": float(sp.used_f_max),
-            "shape": [int(db.shape[0]), int(db.shape[1])], "db": base64.b64encode(db.tobytes()).decode("ascii")}
+    """The "spectrum" block of a marks dict from a filled model.Spectrum (spectrum_db's decibels)."""
+    return {"n_fft": int(sp.n_fft), "hop": int(sp.hop), "n_bands": int(np.shape(sp.power)[1]), "f_min": float(sp.f_min),
+            "f_max": float(sp.used_f_max), **spectrum_db(sp.power)}
 
 
 def voice_options(options):
@@ -801,7 +806,7 @@ class SynthesisStream:
     the pieces run out, when one fails, by close(), and when the object is dropped, iterated or not: the replays of a stream are already
     enqueued when this object is returned, so its end cannot hang on a generator's `finally`, which never runs for a generator nobody started."""
 
-    def __init__(self, st, head, to_bytes, marks=None, tail=None, levels=None, pitch=None):
+    def __init__(self, st, head, to_bytes, marks=None, tail=None, levels=None, pitch=None, spectrum=None):
         self._st, self._head, self._to_bytes, self._tail = st, head, to_bytes, tail   # tail: bytes that follow the last chunk (a pad byte)
         self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece
         self.level_stats = None   # a level stream's (deepest reduction in dB, max |x|), once its last piece has been handed out
@@ -818,6 +823,14 @@ class SynthesisStream:
         self._pitch, self._f0, self._new_pitch, self._pitch_first = pitch, [], ([], []), 0
         if pitch is not None:
             self.marks["pitch"] = {"hop": int(pitch.hop), "f0_hz": [], "aperiodicity": []}
+        # spectrum (a model.Spectrum, with levels): the stream was begun with a spectrum; take_marks() hands out the frames the pieces so far
+        # completed.  `.marks` names what the spectrum holds and never the frames themselves: a caller keeps the blocks it wants
+        self._spectrum, self._new_spec, self._spec_first = spectrum, [], 0
+        if spectrum is not None:
+            rate = float(levels[0].sample_rate)
+            self.marks["spectrum"] = {"n_fft": int(spectrum.n_fft), "hop": int(spectrum.hop), "n_bands": int(spectrum.n_bands()),
+                                      "n_frames": int(spectrum.n_frames(self.total_samples)), "f_min": float(spectrum.f_min),
+                                      "f_max": rate / 2.0 if spectrum.f_max is None else float(spectrum.f_max)}
 
     def _collect(self):
         """The levels the handle has completed since the last look -> `.marks` and the lists take_marks() hands out next."""
@@ -842,11 +855,13 @@ class SynthesisStream:
                 lst.extend(float(v) if v > 0 else None for v in vals)
             for lst in (self.marks["pitch"]["aperiodicity"], self._new_pitch[1]):
                 lst.extend(float(v) for v in ap)
+        if self._spectrum is not None:
+            self._new_spec.append(self._st.next_spectrum()[1])
 
     def take_marks(self) -> dict:
         """JSON-ready: the levels that the pieces handed out so far have completed and that no earlier call returned.  {"delivered": samples out
         so far, "tokens": [{"token": its index in .marks["tokens"], "level_dbfs", "peak"}, ...], "envelope": {"first", "hop", "level_dbfs" [n],
-        "peak" [n]} (with an envelope), "pitch": {"first", "hop", "f0_hz" [n] (None = unvoiced), "aperiodicity" [n]} (with pitch)}.  A token is
+        "peak" [n]} (with an envelope), "pitch": {"first", "hop", "f0_hz" [n] (None = unvoiced), "aperiodicity" [n]} (with pitch), "spectrum": {"first", "shape": [n, n_bands], "db": spectrum_db's} (with a spectrum)}.  A token is
         complete once its last sample has been delivered, an envelope frame likewise, a pitch frame once its window has been
         (model.stream_pitch_complete)."""
         if self._levels is None:
@@ -859,6 +874,11 @@ class SynthesisStream:
         if self._pitch is not None:
             d["pitch"] = {"first": self._pitch_first, "hop": int(self._pitch.hop), "f0_hz": self._new_pitch[0], "aperiodicity": self._new_pitch[1]}
             self._pitch_first += len(self._new_pitch[0])
+        if self._spectrum is not None:
+            power = np.concatenate(self._new_spec) if self._new_spec else np.zeros((0, self._spectrum.n_bands()), np.float32)
+            d["spectrum"] = {"first": self._spec_first, **spectrum_db(power)}
+            self._spec_first += len(power)
+            self._new_spec = []
         self._new_tokens, self._new_env, self._new_pitch = [], ([], []), ([], [])
         return d
 
@@ -914,7 +934,7 @@ class SynthesisStream:
 
 
 def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
-                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False, levels=False, pitch=False):
+                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False, levels=False, pitch=False, spectrum=False):
     """easy_synthesize delivered while it is synthesised: an iterator (SynthesisStream; close() it when it is abandoned early) over the pieces
     of the request's container.  The forward (DeBERTa / text / flow) runs once over the whole request, then the decoder runs chunk by chunk
     (model.StreamHandle).
@@ -948,6 +968,10 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     pitch=True (needs levels=True and options.pitch_hz; hop and range as pitch_options reads them): the pitch contour of the delivered samples
     is estimated on the device chunk by chunk as well (model.StreamHandle(pitch=...)): take_marks() pieces gain a "pitch" block, and once the
     last piece is out `.marks` has marks_dict's "pitch" block and the tokens' f0_hz / voiced.  Without pitch=True, pitch_hz is refused.
+    spectrum=True (needs levels=True and options.spectrum_mels; the spectrum_* options as spectrum_options reads them at the stream's rate):
+    the spectrum of the delivered samples is computed on the device chunk by chunk (model.StreamHandle(spectrum=...)): `.marks` gains
+    "spectrum": {n_fft, hop, n_bands, n_frames, f_min, f_max} and take_marks() pieces a "spectrum" block.  Without spectrum=True the spectrum_*
+    options are refused as before.
     options.assist: every row carries the assist (sbv2_stream_begin_request_assist); with split=False the utterance then runs as a request of
     one row without a gap, the only stream kind that takes one."""
     options = options or SynthesizeOptions()
@@ -955,7 +979,13 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     refuse_token_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_dynamics(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
-    refuse_spectrum(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    if spectrum:
+        if not levels:
+            raise SpectrumError("spectrum=True on a stream comes with its speech marks: pass levels=True as well")
+        if getattr(options, "spectrum_mels", None) is None:
+            raise SpectrumError("spectrum=True needs options.spectrum_mels (mel bands, 0 = the bins)")
+    else:
+        refuse_spectrum(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if pitch:
         if not levels:
             raise model.Sbv2Error("pitch=True on a stream comes with its speech marks: pass levels=True as well")
@@ -989,6 +1019,13 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     contour = pitch_options(options, fmt.sample_rate) if pitch else None   # (a bad pitch_hz or range likewise)
     if contour is not None:
         kw.update(pitch=contour)
+    spec = spectrum_options(options, fmt.sample_rate) if spectrum else None   # (a bad field is refused before any GPU work)
+    if spec is not None:
+        import inspect
+        if "spectrum" not in inspect.signature(model.StreamHandle.__init__).parameters:
+            raise model.Sbv2Error("spectrum=True on a stream needs a StreamHandle that takes spectrum=: this one does not, and the request is not "
+                                  "served without its spectrum")
+        kw.update(spectrum=spec)
     if leveler is not None:
         import inspect
         if "leveler" not in inspect.signature(model.StreamHandle.__init__).parameters:
@@ -1022,8 +1059,8 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
         raise
     lv = (fmt, kw["env_hop"], st.total_samples) if levels else None
     if flac:
-        return SynthesisStream(st, None, lambda c: c, marks, levels=lv, pitch=contour)
+        return SynthesisStream(st, None, lambda c: c, marks, levels=lv, pitch=contour, spectrum=spec)
     dtype = {"s16": "<i2", "f32": "<f4"}.get(fmt.encoding, "u1")
     pad = b"\0" if fmt.encoding in G711_TAGS and st.total_samples & 1 else None
     return SynthesisStream(st, wav_stream_header(fmt.sample_rate, fmt.encoding, st.total_samples),
-                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad, levels=lv, pitch=contour)
+                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad, levels=lv, pitch=contour, spectrum=spec)

@@ -52,6 +52,9 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     token), "src_f0_hz" (the token's measured mean, null without a voiced frame)}.  A bad value, kind or smoothing and a list of
                     another length than the text's token count (the message names the expected count) answer 400, and so do the stream routes
                     for any list.
+  spectrum_stream = false (new; /synthesize_stream_marks only, with spectrum_mels and its fields): the first line gains "spectrum": {"n_fft",
+                    "hop", "n_bands", "n_frames", "f_min", "f_max"} and every later line "spectrum": {"first", "shape": [n, n_bands], "db"}, the
+                    frames that piece completed, decibels as below.  Without it the stream routes keep answering 400 for spectrum_mels.
   spectrum_mels = null (new; /synthesize_marks only, batched or not): the marks carry "spectrum": {"n_fft", "hop", "n_bands", "f_min", "f_max",
                     "shape": [n_frames, n_bands], "db": base64 of little-endian float32, 10 log10(max(power, 1e-10))}, the Slaney mel bands (0:
                     the spectrum_fft // 2 + 1 bins) of the delivered samples, reduced on the device.  spectrum_fft (null: the multiple of 32
@@ -148,6 +151,8 @@ class _MarksLines:
         if "pitch" in pieces.marks:   # (a stream begun with pitch: what the contour will hold, before its first frame)
             hop = int(pieces.marks["pitch"]["hop"])
             self._first["pitch"] = {"hop": hop, "n_frames": -(-int(total_samples) // hop)}
+        if "spectrum" in pieces.marks:   # (a stream begun with a spectrum: what its frames will hold)
+            self._first["spectrum"] = dict(pieces.marks["spectrum"])
 
     def __iter__(self):
         return self
@@ -225,6 +230,7 @@ def make_app(holder, batching=None):
 
     class SynthesizeStreamMarksRequest(SynthesizeStreamRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
+        spectrum_stream: bool = False       # new: with spectrum_mels, every piece carries the spectrum frames it completed; without it spectrum_mels stays a 400
 
     class _ClosingStream(StreamingResponse):
         """A StreamingResponse that closes its _HeldPieces when the response is over, however it ends: sent to the end, cut by the client's
@@ -333,7 +339,7 @@ def make_app(holder, batching=None):
                            "tokens": [[t["line"], t["index"], t["phone"], t["start"], t["end"]] for t in marks["tokens"]],
                            "words": [[w["line"], w["index"], w["start"], w["end"]] for w in marks["words"]]}, separators=(",", ":"))
 
-    def refuse_stream_voice(req):
+    def refuse_stream_voice(req, spectrum=False):
         """A 400 for pitch_scale / intonation_scale / pitch_track / compressor on a stream route, and for an assist_text_weight outside [0, 1] (the
         request is at fault, nothing was tried), None at the defaults."""
         try:
@@ -343,7 +349,12 @@ def make_app(holder, batching=None):
             orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.check_assist(None, getattr(req, "assist_text_weight", 0.7))   # (a stream takes an assist; a bad weight is the request's fault)
-            orchestrator.refuse_spectrum(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            if not spectrum:
+                orchestrator.refuse_spectrum(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            elif req.spectrum_mels is None:
+                raise orchestrator.SpectrumError("spectrum_stream needs spectrum_mels (mel bands, 0 = the bins)")
+            else:
+                orchestrator.spectrum_options(req, req.sample_rate)   # (a bad field is the request's fault)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=400)
         return None
@@ -371,7 +382,7 @@ def make_app(holder, batching=None):
 
     @app.post("/synthesize_stream_marks")
     def synthesize_stream_marks(req: SynthesizeStreamMarksRequest):
-        refused = refuse_stream_voice(req)
+        refused = refuse_stream_voice(req, spectrum=req.spectrum_stream)
         if refused is not None:
             return refused
         lock.acquire()                        # as /synthesize_stream: given back by _HeldPieces.close when the response is over
@@ -379,7 +390,8 @@ def make_app(holder, batching=None):
             # (pitch is sent like split: named only when the request asks for it, so a request without pitch_hz is the call it always was)
             pieces = holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), levels=True,
                                                    **({"split": True} if req.split_sentences else {}),
-                                                   **({"pitch": True} if req.pitch_hz is not None else {}))
+                                                   **({"pitch": True} if req.pitch_hz is not None else {}),
+                                                   **({"spectrum": True} if req.spectrum_stream else {}))
             try:
                 lines = _MarksLines(pieces, "audio/flac" if req.encoding == "flac" else "audio/wav", pieces.marks["sample_rate"],
                                     pieces.total_samples)
