@@ -204,6 +204,41 @@ inline void fetch_request_spectrum(sbv2_pipeline* p, int64_t ticket, const sbv2_
     sp.power.resize((size_t)(s.n_frames * s.n_bands));
 }
 
+// Not in the reference: the formant contour of a fetched request (sbv2_formant_contour in sbv2_hip.h states it).  window / order / f_lo / f_hi /
+// bw_max 0: the defaults at the delivered rate, which fetch_request_formant_contour writes back.  f_hz / bw_hz [n_frames][n_formants] and
+// status [n_frames] are filled by it.
+struct FormantContour {
+    int hop = 160, window = 0, order = 0, n_formants = 4;
+    double f_lo = 0.0, f_hi = 0.0, bw_max = 0.0;
+    std::vector<double> f_hz, bw_hz;
+    std::vector<int32_t> status;
+    int64_t n_frames = 0;
+};
+// sbv2_pipeline_fetch_request_formant_contour with owned arrays: sbv2_pipeline_fetch_request_formant (no spectrum) with the formant contour of
+// the delivered signal behind it.
+inline void fetch_request_formant_contour(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,
+                                          const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                          const sbv2_formant* formant, FormantContour& fc, void* dst, int64_t capacity_bytes, int64_t* out_count,
+                                          double* stats = nullptr, double* dyn_stats = nullptr, sbv2_marks* marks = nullptr,
+                                          sbv2_pitch* pitch = nullptr, sbv2_spectrum* spectrum = nullptr) {
+    const int rate = req.fmt ? req.fmt->sample_rate : 44100;
+    const int64_t out_len = sbv2_pcm_format_length(req.fmt, req.joined_len);
+    if (out_len < 0) throw Error(sbv2_last_error());
+    sbv2_formant_contour c{fc.hop, fc.window, fc.order, fc.n_formants, fc.f_lo, fc.f_hi, fc.bw_max, 0, 0, nullptr, nullptr, nullptr, out_len};
+    check(sbv2_formant_contour_defaults(rate, &c));   // the ranges, the defaults, and n_frames of out_len
+    fc.window = c.window, fc.order = c.order, fc.f_lo = c.f_lo, fc.f_hi = c.f_hi, fc.bw_max = c.bw_max;
+    const size_t nf = (size_t)c.n_frames;
+    fc.f_hz.assign(nf * fc.n_formants + 1, 0.0);
+    fc.bw_hz.assign(nf * fc.n_formants + 1, 0.0);
+    fc.status.assign(nf + 1, 0);
+    c.capacity = (int64_t)nf;
+    c.f_hz = fc.f_hz.data(), c.bw_hz = fc.bw_hz.data(), c.status = fc.status.data();
+    check(sbv2_pipeline_fetch_request_formant_contour(p, ticket, &req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count,
+                                                      stats, dyn_stats, marks, pitch, spectrum, &c));
+    fc.n_frames = c.n_frames;
+    fc.f_hz.resize(nf * fc.n_formants), fc.bw_hz.resize(nf * fc.n_formants), fc.status.resize(nf);
+}
+
 // Not in the reference (upstream Style-Bert-VITS2's assist_text / assist_text_weight; sbv2_assist in sbv2_hip.h states it): assist texts of a run
 // with owned arrays.  texts: the distinct assist sequences' token ids; text_of / weight: one entry per row of the batch (-1 = none).
 struct Assist {

@@ -729,6 +729,67 @@ int sbv2_spectrum_bands(int32_t sample_rate, sbv2_spectrum* spectrum, float* ban
  * in the fetch. */
 int sbv2_debug_spectrum(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_spectrum* spectrum);
 
+/* ---- new: the formant contour of a delivered signal.  The vowel's resonances F1, F2, ... and their bandwidths, frame by frame, by linear
+ * prediction on the device from the samples the speech marks are taken of (behind every sink, FLAC and G.711 included), stated so that it is
+ * reproducible.  (sbv2_formant above MOVES the formants; this measures them.)
+ * Input.  The delivered samples v[0 .. n) of ONE signal at rate sr <= 48000, read as the spectrum reads them: u[j] = v[j] for f32, u[j] = v[j] /
+ *   32768 for s16 and for the integers that G.711 codes decode to; positions outside [0, n) read as 0.
+ * Parameters (0 = the default, where there is one).  hop >= 1 delivered samples per frame; window in [64, 2048] samples (0: sr / 40, 25 ms,
+ *   integer division); order p even, in [4, 50] and p < window / 4 (integer division) (0: 2 + sr / 1000, integer division, rounded up to even);
+ *   n_formants in [1, 8] and <= p / 2; 0 < f_lo < f_hi < sr / 2 in Hz (0: 50 and min(5500, sr / 2 - 50)); bw_max > 0 in Hz (0: sr / 2);
+ *   reserved = 0.  Everything else is refused, NaNs included (they fail every comparison).
+ * Frames.  The time axis of sbv2_pitch: n_frames = ceil(n / hop) (0 for n = 0); frame f has its centre at f hop + hop / 2 (integer division)
+ *   and its window starts at b = centre - window / 2.
+ * Per frame, in f64.  e[i] = u[b + i] - alpha u[b + i - 1], alpha = exp(-2 pi 50 / sr) (pre-emphasis from 50 Hz); w[i] = (exp(-12 ((i - c) /
+ *   (window + 1))^2) - exp(-12)) / (1 - exp(-12)), c = (window - 1) / 2, i - c in f64 (a Gaussian window, formed on the host in f64 and
+ *   uploaded); s = e w; r[k] = sum_i s[i] s[i + k] over the i with i + k < window, for k = 0 .. p.  Levinson-Durbin on r gives a[0 .. p], a[0] =
+ *   1: E = r[0]; for m = 1 .. p: k = -(r[m] + sum_{j=1}^{m-1} a[j] r[m - j]) / E, a[j] += k a[m - j] for 0 < j < m (from the old values), a[m] =
+ *   k, E *= 1 - k^2; once E is no longer positive the recursion stops (status bit 1, value 2), the higher coefficients staying 0.  A frame with
+ *   r[0] = 0 (digital silence) has no formants: F = B = 0, a = (1, 0, ...), status 0.
+ * Roots.  The p roots of A(z) = z^p + a[1] z^(p-1) + ... + a[p] by Aberth-Ehrlich iteration from z_i = 0.9 exp(sqrt(-1) (2 pi i + 0.5) / p),
+ *   i = 0 .. p - 1: every iteration corrects every root at once from the previous iteration's roots, z_i -= w_i, w_i = q / (1 - q sum_{j != i}
+ *   1 / (z_i - z_j)), q = A(z_i) / A'(z_i) by Horner's rule.  It stops once |w_i| < 1e-14 max(1, |z_i|) (the corrected z_i) holds for every i,
+ *   and after 64 iterations at the latest; a frame that was stopped by the cap has status bit 0 (value 1) set: flagged, not hidden.
+ * Selection.  Per root F = arg(z) sr / (2 pi) and B = -ln|z| sr / pi; the roots with f_lo <= F <= f_hi and 0 < B <= bw_max are kept, sorted by
+ *   ascending F (equal F: ascending i), and the first n_formants are delivered as f_hz / bw_hz [n_frames][n_formants]; 0 where a frame has fewer.
+ * Bits.  No atomics; every sum is in an order the library fixes (lag k: 64 strided partial sums over ascending i, met in an xor butterfly; the
+ *   Levinson sum: one term per lane, the same butterfly; the sums over roots and coefficients: ascending index): two fetches of one ticket give
+ *   identical bits, and a fetch gives the bits of sbv2_debug_formant_contour on the same samples.  Nothing claims equality with numpy: what is
+ *   measured against a longdouble restatement, and against numpy's own roots, is in DESIGN.md (8y).
+ * Not built: the contour on streams (sbv2_stream_*) and on sbv2_node_*, Burg's method, resampling to 2 f_hi before the analysis (the caller picks
+ *   the delivered rate; 16 kHz is the phonetician's), tracking the formants across frames. */
+typedef struct sbv2_formant_contour {
+    int32_t hop, window, order, n_formants; /* in; window / order 0: the defaults */
+    double f_lo, f_hi, bw_max;              /* in: Hz; 0: the defaults */
+    int32_t reserved;                       /* in: must be 0 */
+    int64_t capacity;                       /* in: FRAMES that f_hz / bw_hz (times n_formants) and status hold */
+    double* f_hz;                           /* out: [n_frames][n_formants]; must not be NULL */
+    double* bw_hz;                          /* out: likewise */
+    int32_t* status;                        /* out: [n_frames], 0 = converged, bit 0 = iteration cap hit, bit 1 = Levinson stopped; may be NULL */
+    int64_t n_frames;                       /* out: ceil(out_len / hop) */
+} sbv2_formant_contour;
+/* sbv2_pipeline_fetch_request_spectrum that also fills *contour: the formant contour of the delivered signal of the request (every gain / sink
+ * combination, FLAC included), one more launch (k_formant_lpc) before the fetch's only synchronisation.  contour == NULL is exactly that call:
+ * nothing new is launched or allocated.  The first fetch of a context with a window length also forms the window table (at most 16 KB) on the
+ * host and uploads it with one more synchronisation of the stream; the tables are cached per context (8).  With it the audio bytes, out_count,
+ * stats, marks, pitch and spectrum are those of the same call without.  The caller's arrays are written only after everything else has
+ * succeeded; the zero parameters are left as they were given.  Refused with nothing written, besides everything that call refuses: parameters
+ * outside the ranges above (at the format's rate), capacity < n_frames, a NULL f_hz or bw_hz, a non-zero reserved. */
+int sbv2_pipeline_fetch_request_formant_contour(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                                const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                                const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                                double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                                sbv2_formant_contour* contour);
+/* Host only: checks the parameters of *contour at sample_rate (capacity and the arrays are not looked at) and replaces the zeros among window,
+ * order, f_lo, f_hi and bw_max by their defaults.  n_frames is read as well as written: on entry a count n >= 0 of delivered samples, on return
+ * the frames of a signal of n samples. */
+int sbv2_formant_contour_defaults(int32_t sample_rate, sbv2_formant_contour* contour);
+/* Test hook: the stage on host samples x[n] (encoding as sbv2_debug_segment_levels); contour: parameters in, f_hz / bw_hz / status / n_frames
+ * out as in the fetch.  lpc (may be NULL) receives every frame's polynomial a[0 .. p], [n_frames][p + 1]; status (may be NULL) the status words
+ * [n_frames] as well. */
+int sbv2_debug_formant_contour(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_formant_contour* contour, double* lpc,
+                               int32_t* status);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,

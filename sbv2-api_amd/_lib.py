@@ -135,6 +135,13 @@ class Sbv2Spectrum(C.Structure):
                 ("f_max", C.c_double), ("capacity", C.c_int64), ("power", f32p), ("n_frames", C.c_int64), ("n_bands", C.c_int32)]
 
 
+class Sbv2FormantContour(C.Structure):
+    """struct sbv2_formant_contour (include/sbv2_hip.h)."""
+    _fields_ = [("hop", C.c_int32), ("window", C.c_int32), ("order", C.c_int32), ("n_formants", C.c_int32), ("f_lo", C.c_double),
+                ("f_hi", C.c_double), ("bw_max", C.c_double), ("reserved", C.c_int32), ("capacity", C.c_int64), ("f_hz", C.POINTER(C.c_double)),
+                ("bw_hz", C.POINTER(C.c_double)), ("status", C.POINTER(C.c_int32)), ("n_frames", C.c_int64)]
+
+
 class Sbv2StreamSpectrum(C.Structure):
     """struct sbv2_stream_spectrum (include/sbv2_hip.h)."""
     _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("reserved", C.c_int32), ("f_min", C.c_double),
@@ -218,6 +225,14 @@ SYMBOLS = {
                                                        C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch),
                                                        C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
                                                        C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch), C.POINTER(Sbv2Spectrum)]),
+    "sbv2_pipeline_fetch_request_formant_contour": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                              C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch),
+                                                              C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
+                                                              C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch),
+                                                              C.POINTER(Sbv2Spectrum), C.POINTER(Sbv2FormantContour)]),
+    "sbv2_formant_contour_defaults": (C.c_int, [C.c_int32, C.POINTER(Sbv2FormantContour)]),
+    "sbv2_debug_formant_contour": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2FormantContour),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "sbv2_spectrum_bands": (C.c_int, [C.c_int32, C.POINTER(Sbv2Spectrum), f32p]),
     "sbv2_debug_spectrum": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2Spectrum)]),
     "sbv2_debug_voice_formant": (C.c_int, [C.c_int, f32p, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Voice), C.POINTER(Sbv2Formant),

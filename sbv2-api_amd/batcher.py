@@ -103,9 +103,12 @@ class RequestBatcher:
                 orchestrator.pitch_options(plan.options, plan.fmt.sample_rate)
                 orchestrator.spectrum_options(plan.options, plan.fmt.sample_rate)
                 orchestrator.require_spectrum(self.pipe, plan.options)
+                orchestrator.formants_options(plan.options, plan.fmt.sample_rate)
+                orchestrator.require_formants(self.pipe, plan.options)
             else:
                 orchestrator.refuse_pitch(plan.options, "a request without marks (/synthesize)")
                 orchestrator.refuse_spectrum(plan.options, "a request without marks (/synthesize)")
+                orchestrator.refuse_formants(plan.options, "a request without marks (/synthesize)")
             seed = model.fresh_noise_seed() if seed is None else seed
             for j, u in enumerate(plan.utts):   # noise_index restarts per request: the keys of the request run alone
                 u.update(sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=orchestrator.NOISE_SCALE,

@@ -488,6 +488,20 @@ int sbv2_spectrum_bands(int32_t sample_rate, sbv2_spectrum* spectrum, float* ban
     API_END
 }
 
+int sbv2_formant_contour_defaults(int32_t sample_rate, sbv2_formant_contour* contour) {
+    API_BEGIN
+    SBV2_REQUIRE(contour, "bad arguments");
+    const FormantContourSpec sp = check_formant_contour(sample_rate, contour);
+    SBV2_REQUIRE(contour->n_frames >= 0, "sbv2_formant_contour.n_frames must hold a sample count >= 0 on entry");
+    contour->window = sp.window;
+    contour->order = sp.order;
+    contour->f_lo = sp.f_lo;
+    contour->f_hi = sp.f_hi;
+    contour->bw_max = sp.bw_max;
+    contour->n_frames = formant_frames(contour->n_frames, sp.hop);
+    API_END
+}
+
 int sbv2_marks_spans(const int64_t* durations, int64_t n_tokens, int32_t hop, int64_t place, const sbv2_pcm_format* fmt, int64_t* start, int64_t* end) {
     API_BEGIN
     const PcmFmtSpec spec = pcm_format_spec(fmt);

@@ -9,6 +9,7 @@
 #include "../../include/sbv2_hip.h"
 #include "dynamics.h"
 #include "flac_encode.h"
+#include "formants.h"
 #include "limiter.h"
 #include "loudness.h"
 #include "marks.h"
@@ -41,6 +42,7 @@ struct OutputChain {
     Marks marks;       // speech marks: levels of token spans and envelope frames (fetch_request_marks only)
     Pitch pitch;       // ... and the pitch contour of the same samples (fetch_request_pitch only)
     Spectrum spectrum; // ... and their power spectrum or mel bands (fetch_request_spectrum only)
+    Formants formants; // ... and their formant contour (fetch_request_formant_contour only)
     Voice voice;       // pitch / intonation scale of the listed rows, in front of the formatter (fetch_request_voice only)
     Track track;       // the best path through the delivered contour's candidates (fetch_request_tracked only; the shifter has its own)
 };
@@ -77,6 +79,12 @@ struct sbv2_pipeline {
     }
 
 VitsBatch to_batch(const sbv2_batch* b);
+// THE parameter check of an sbv2_formant_contour at a rate (the fetch, sbv2_formant_contour_defaults and the hook): reserved, then
+// formant_contour_spec (formants.h); capacity and the arrays are the caller's to look at
+inline FormantContourSpec check_formant_contour(int rate, const sbv2_formant_contour* q) {
+    SBV2_REQUIRE(q->reserved == 0, "sbv2_formant_contour.reserved must be 0");
+    return formant_contour_spec(rate, q->hop, q->window, q->order, q->n_formants, q->f_lo, q->f_hi, q->bw_max);
+}
 // The per-row arrays of sbv2_utt_options onto the batch (NULL: nothing); throws for an option out of range, before any GPU work
 void apply_utt_options(sbv2::VitsBatch* v, const sbv2_utt_options* o);
 // One batch on one execution context: bert::predict -> word2ph repeat (tts_util.rs:129-154) -> model::synthesize; returns once enqueued

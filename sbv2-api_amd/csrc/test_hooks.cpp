@@ -2223,6 +2223,34 @@ int sbv2_debug_spectrum(int device, const void* x, int encoding, int64_t n, int3
     API_END
 }
 
+// The formant contour stage (Formants, formants.hip) on host samples.  Everything is checked before any device call; nothing is written when
+// the call fails.
+int sbv2_debug_formant_contour(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_formant_contour* contour, double* lpc,
+                               int32_t* status) {
+    API_BEGIN
+    SBV2_REQUIRE(contour && pcm_encoding_known(encoding) && n >= 0 && (x || n == 0), "bad arguments");
+    const FormantContourSpec sp = check_formant_contour(sample_rate, contour);
+    const int64_t nf = formant_frames(n, sp.hop);
+    SBV2_REQUIRE(contour->capacity >= nf,
+                 "formant contour arrays too small: " + std::to_string(contour->capacity) + " < " + std::to_string(nf) + " frames");
+    SBV2_REQUIRE(contour->f_hz && contour->bw_hz, "sbv2_formant_contour.f_hz and bw_hz must not be NULL");
+    HIP_CHECK(hipSetDevice(device));
+    DevMem dx(x, (size_t)n * pcm_encoding_bytes(encoding));
+    Formants st;
+    st.run(dx.p, encoding, n, sp, nullptr, lpc != nullptr);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    if (nf > 0) {
+        const size_t cnt = (size_t)(nf * sp.n_formants);
+        std::memcpy(contour->f_hz, st.f_host(), sizeof(double) * cnt);
+        std::memcpy(contour->bw_hz, st.bw_host(), sizeof(double) * cnt);
+        if (lpc) std::memcpy(lpc, st.lpc_host(), sizeof(double) * (size_t)(nf * (sp.order + 1)));
+        if (contour->status) std::memcpy(contour->status, st.status_host(), sizeof(int32_t) * (size_t)nf);
+        if (status) std::memcpy(status, st.status_host(), sizeof(int32_t) * (size_t)nf);
+    }
+    contour->n_frames = nf;
+    API_END
+}
+
 // The tracker (Track, track.hip) on host samples, or on the caller's candidate table alone.  Everything is checked before any device call;
 // nothing is written when the call fails.
 int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, const sbv2_pitch_track* track,

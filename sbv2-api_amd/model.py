@@ -3,6 +3,7 @@
 Same names, argument order and meaning as the reference; numpy arrays stand in for ndarray.  The batched /
 pipeline entry points are the new capabilities (the reference is strictly batch 1).
 """
+import copy
 import ctypes as C
 import os
 from collections import namedtuple
@@ -672,6 +673,77 @@ def debug_spectrum(x, sample_rate: int, spectrum: Spectrum, device: int = 0, enc
     return spectrum.take(c, power)
 
 
+class FormantContour:
+    """Options and, once a call has filled it, results of the formant contour stage (struct sbv2_formant_contour, include/sbv2_hip.h states it):
+    per frame of `hop` delivered samples the first n_formants resonances of an LPC fit of order `order` to `window` pre-emphasised,
+    Gauss-windowed samples: the roots of the polynomial with f_lo <= F <= f_hi and 0 < B <= bw_max, by ascending F; frame f has its centre at
+    f hop + hop // 2, as Pitch has.  None (or 0) for window / order / f_lo / f_hi / bw_max: the library's defaults at the delivered rate (25 ms,
+    2 + rate // 1000 rounded up to even, 50 Hz, min(5500, rate / 2 - 50), rate / 2), which a call writes back.  Results: f_hz and bw_hz
+    [n_frames][n_formants] float64 (0 where a frame has fewer), status [n_frames] int32 (0 = converged, bit 0 = the root iteration hit its cap,
+    bit 1 = the Levinson recursion stopped early); None before a call.  Ranges are checked by the library.
+    (Formant MOVES the formants; this measures them.)"""
+
+    def __init__(self, hop: int, n_formants: int = 4, order: int | None = None, window: int | None = None, f_lo: float | None = None,
+                 f_hi: float | None = None, bw_max: float | None = None):
+        self.hop, self.n_formants, self.order, self.window = int(hop), int(n_formants), int(order or 0), int(window or 0)
+        self.f_lo, self.f_hi, self.bw_max = float(f_lo or 0.0), float(f_hi or 0.0), float(bw_max or 0.0)
+        self.f_hz = self.bw_hz = self.status = None
+
+    def c_struct(self, n: int, sample_rate: int):
+        """A sbv2_formant_contour over fresh arrays for a signal of n delivered samples; take() keeps them once the call has succeeded."""
+        i32 = lambda v: v if -2 ** 31 <= v < 2 ** 31 else -1
+        nf = -(-int(n) // self.hop) if n > 0 and self.hop > 0 else 0
+        k = min(max(self.n_formants, 0), 8)
+        arrays = np.zeros(max(nf * k, 1), np.float64), np.zeros(max(nf * k, 1), np.float64), np.zeros(max(nf, 1), np.int32)
+        c = _lib.Sbv2FormantContour(i32(self.hop), i32(self.window), i32(self.order), i32(self.n_formants), self.f_lo, self.f_hi, self.bw_max, 0,
+                                    nf, _f64p(arrays[0]), _f64p(arrays[1]), arrays[2].ctypes.data_as(C.POINTER(C.c_int32)), 0)
+        return c, arrays
+
+    def take(self, c, arrays, sample_rate: int):
+        assert c.n_frames == c.capacity, (c.n_frames, c.capacity)
+        nf, k = int(c.n_frames), self.n_formants
+        self.f_hz, self.bw_hz, self.status = arrays[0][:nf * k].reshape(nf, k), arrays[1][:nf * k].reshape(nf, k), arrays[2][:nf]
+        formant_contour_defaults(sample_rate, self)   # (the defaults the call used, written back)
+        return self
+
+    def __repr__(self):
+        return (f"FormantContour({self.hop}, n_formants={self.n_formants}, order={self.order}, window={self.window}, f_lo={self.f_lo}, "
+                f"f_hi={self.f_hi}, bw_max={self.bw_max})")
+
+
+def formant_contour_defaults(sample_rate: int, contour: FormantContour, n: int = 0) -> int:
+    """The library's checks of a FormantContour at sample_rate, its zeros replaced by the defaults there (sbv2_formant_contour_defaults; host
+    only) -> the frames of a signal of n delivered samples."""
+    fn = getattr(_lib.lib(), "sbv2_formant_contour_defaults", None)
+    if fn is None:
+        raise Sbv2Error("this library has no sbv2_formant_contour_defaults: it computes no formant contour")
+    c, _ = contour.c_struct(0, int(sample_rate))
+    c.n_frames = int(n)
+    check(fn(int(sample_rate), C.byref(c)))
+    contour.window, contour.order, contour.f_lo, contour.f_hi, contour.bw_max = c.window, c.order, c.f_lo, c.f_hi, c.bw_max
+    return int(c.n_frames)
+
+
+def debug_formant_contour(x, sample_rate: int, contour: FormantContour, device: int = 0, encoding: str | None = None):
+    """Test hook: the formant contour stage on host samples (sbv2_debug_formant_contour).  x: int16 or float32 samples, or with encoding
+    "mulaw" / "alaw" uint8 codes -> (contour with f_hz / bw_hz / status filled, lpc [n_frames][order + 1] float64, every frame's polynomial)."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if encoding is None and x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"the formant contour is taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"the formant contour of {encoding!r} samples is not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
+    probe = copy.copy(contour)
+    nf = formant_contour_defaults(sample_rate, probe, x.size)   # (the order sizes lpc)
+    c, arrays = contour.c_struct(x.size, int(sample_rate))
+    lpc, status = np.zeros((nf, probe.order + 1), np.float64), np.zeros(max(nf, 1), np.int32)
+    check(_lib.lib().sbv2_debug_formant_contour(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size, int(sample_rate),
+                                                C.byref(c), _f64p(lpc) if nf else None, status.ctypes.data_as(C.POINTER(C.c_int32))))
+    contour.take(c, arrays, int(sample_rate))
+    assert np.array_equal(status[:nf], contour.status)
+    return contour, lpc
+
+
 class PitchTrack:
     """Octave-error repair of a pitch contour (struct sbv2_pitch_track: one best path through the frames' candidates, include/sbv2_hip.h states
     it).  cand_max in (0, 1]: a dip of c at or above it is no candidate; unvoiced_cost and switch_cost in [0, 4], jump_cost in [0, 16], all in
@@ -1242,14 +1314,14 @@ def get_trace(session: Session, name: str, utt: int = 0) -> np.ndarray:
 
 
 # What a Pipeline.fetch_request result holds, by name (None: not there, or there and None)
-FetchResult = namedtuple("FetchResult", "signal stats marks pitch dyn_stats token_pitch spectrum", defaults=(None,) * 5)
+FetchResult = namedtuple("FetchResult", "signal stats marks pitch dyn_stats token_pitch spectrum formants", defaults=(None,) * 6)
 
 
-def _fetch_fields(marks=False, pitch=False, dynamics=False, token_pitch=False, spectrum=False):
-    """THE rule of the shape of a Pipeline.fetch_request result, from which of these five options were given: (signal, stats); then
+def _fetch_fields(marks=False, pitch=False, dynamics=False, token_pitch=False, spectrum=False, formants=False):
+    """THE rule of the shape of a Pipeline.fetch_request result, from which of these six options were given: (signal, stats); then
     marks-or-None if marks or pitch was; then the filled Pitch if pitch was; then the compressor's stats-or-None if dynamics was; then the
-    filled TokenPitch if token_pitch was; then the filled Spectrum if spectrum was."""
-    there = (True, True, marks or pitch, pitch, dynamics, token_pitch, spectrum)
+    filled TokenPitch if token_pitch was; then the filled Spectrum if spectrum was; then the filled FormantContour if formants was."""
+    there = (True, True, marks or pitch, pitch, dynamics, token_pitch, spectrum, formants)
     return [name for name, t in zip(FetchResult._fields, there) if t]
 
 
@@ -1387,13 +1459,13 @@ class Pipeline:
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
-                      voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0, spectrum=None):
+                      voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0, spectrum=None, formants=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above.  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
         read: the requests that share a run are fetched one by one from the same ticket.
         Whatever is asked for short of a spectrum, this is ONE call of sbv2_pipeline_fetch_request_formant with NULL for every stage that is
-        not; with a spectrum it is the same call of sbv2_pipeline_fetch_request_spectrum, the widest of the C symbols.  The shape of the result
+        not; with a spectrum it is the same call of sbv2_pipeline_fetch_request_spectrum, with formants of _formant_contour.  The shape of the result
         follows _fetch_fields.
         marks=True: (signal, stats, Marks): the listed rows' token spans on the delivered timeline, with
         their levels (levels=False: timing only, no kernel) and, with env_hop > 0 delivered samples, the envelope.  The signal and stats are
@@ -1413,7 +1485,10 @@ class Pipeline:
         formant_scale: in [0.5, 2] -> the listed rows' formants are moved by that factor in the shifter's gather, whatever the voice is
         (model.Formant states it); the returned tuple is that of the call without.  1.0: exactly that call.
         spectrum: a Spectrum -> the returned tuple gains a last element: that Spectrum with power [n_frames][n_bands] of the delivered signal
-        filled.  Everything else is that of the same call without.  A library without the symbol is refused, never served without."""
+        filled.  Everything else is that of the same call without.  A library without the symbol is refused, never served without.
+        formants: a FormantContour -> the returned tuple gains a last element: that FormantContour with f_hz / bw_hz [n_frames][n_formants] and
+        status [n_frames] of the delivered signal filled (one call of sbv2_pipeline_fetch_request_formant_contour, the widest of the C symbols).
+        Everything else is that of the same call without.  A library without the symbol is refused, never served without."""
         fm = None if formant_scale == 1.0 else Formant(formant_scale)   # (a NaN is carried on and refused by the library)
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
@@ -1433,6 +1508,7 @@ class Pipeline:
         cp, parr = pitch.c_struct(out_len) if pitch is not None else (None, None)
         ctp, tparr = token_pitch.c_struct() if token_pitch is not None else (None, None)
         csp, sparr = spectrum.c_struct(out_len, fmt.sample_rate) if spectrum is not None else (None, None)
+        cfc, fcarr = formants.c_struct(out_len, fmt.sample_rate) if formants is not None else (None, None)
         m = cm = None
         if marks:
             ntok = int(sum(int(b.t_lens[r]) for r in rw))
@@ -1447,7 +1523,13 @@ class Pipeline:
         opt = lambda o: ref(o.c if o is not None else None)
         args = (self.h, b.ticket, C.byref(req), opt(voice), opt(track), opt(dynamics), ref(ctp), opt(fm), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
                 C.byref(got), _f64p(stats) if nstats else None, _f64p(dst_stats) if dst_stats is not None else None, ref(cm), ref(cp))
-        if spectrum is None:
+        if formants is not None:
+            fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_formant_contour", None)
+            if fn is None:
+                raise Sbv2Error("a formant contour needs a library with sbv2_pipeline_fetch_request_formant_contour: the request is not served "
+                                "without it")
+            check(fn(*args, ref(csp), C.byref(cfc)))
+        elif spectrum is None:
             check(_lib.lib().sbv2_pipeline_fetch_request_formant(*args))
         else:
             fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_spectrum", None)
@@ -1458,9 +1540,10 @@ class Pipeline:
             assert cm.n_tokens == ntok and cm.n_env == nenv, (cm.n_tokens, ntok, cm.n_env, nenv)
         res = FetchResult(dst[:got.value].tobytes() if flac else dst[:got.value], stats, m, pitch.take(cp, parr) if pitch is not None else None,
                           dst_stats, token_pitch.take(tparr) if token_pitch is not None else None,
-                          spectrum.take(csp, sparr) if spectrum is not None else None)
+                          spectrum.take(csp, sparr) if spectrum is not None else None,
+                          formants.take(cfc, fcarr, fmt.sample_rate) if formants is not None else None)
         return fetch_result(res, marks=bool(marks), pitch=pitch is not None, dynamics=dynamics is not None, token_pitch=token_pitch is not None,
-                            spectrum=spectrum is not None)
+                            spectrum=spectrum is not None, formants=formants is not None)
 
     def close(self):
         if self.h:

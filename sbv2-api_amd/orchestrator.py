@@ -58,6 +58,11 @@ class SynthesizeOptions:
     the delivered samples (model.Spectrum): spectrum_mels Slaney mel bands in [1, 128] between spectrum_fmin (0) and spectrum_fmax (half the
     rate), or with 0 the spectrum_fft // 2 + 1 bins; spectrum_fft (a multiple of 16 in [64, 2048]; default: the multiple of 32 nearest to 25 ms, a tie going up)
     and spectrum_hop (delivered samples per frame; default sample_rate // 100).  The other four fields need spectrum_mels.
+    formants (new; easy_synthesize_marks and the batcher with marks only, refused everywhere else, the streams included): the speech marks
+    carry the formant contour of the delivered samples (model.FormantContour): the first `formants` (in [1, 8]) resonances F1, F2, ... and
+    their bandwidths per frame, formants_hz frames per second (an integer in [1, 1000]; sample_rate // formants_hz delivered samples per
+    frame), by an LPC fit of formants_order (default 2 + sample_rate // 1000, rounded up to even) to formants_window samples (default 25 ms),
+    resonances up to formants_max_hz (default min(5500, sample_rate / 2 - 50)) accepted.  The other four fields need formants.
     pitch_scale in [0.5, 2] / intonation_scale in [0, 2] (new; checked here): the voice is raised or lowered, its melody flattened or
     exaggerated about its mean, by a length-preserving overlap-add of the synthesized rows on the device before anything else of the output
     chain (model.Voice); whole-signal routes only (easy_synthesize, easy_synthesize_marks, the batcher), refused on streams.  The defaults
@@ -97,7 +102,10 @@ class SynthesizeOptions:
                  compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0, token_pitch=None, token_pitch_kind="hz",
                  token_pitch_smooth=2, formant_scale=1.0, assist=None, assist_weight=0.7, voice_pivot_hz=None, level_target=None,
                  level_range=12.0, level_slew=3.0, level_hold=10, spectrum_mels=None, spectrum_fft=None, spectrum_hop=None, spectrum_fmin=0.0,
-                 spectrum_fmax=None):
+                 spectrum_fmax=None, formants=None, formants_hz=100, formants_max_hz=None, formants_order=None, formants_window=None):
+        self.formants, self.formants_hz, self.formants_max_hz = formants, formants_hz, formants_max_hz
+        self.formants_order, self.formants_window = formants_order, formants_window
+        formants_options(self, None)   # (the fields' types; the ranges need the rate)
         self.spectrum_mels, self.spectrum_fft, self.spectrum_hop = spectrum_mels, spectrum_fft, spectrum_hop
         self.spectrum_fmin, self.spectrum_fmax = spectrum_fmin, spectrum_fmax
         spectrum_options(self, None)   # (the fields' types; the ranges need the rate)
@@ -529,6 +537,81 @@ def require_spectrum(pipe, options):
                               "request is not served without its spectrum")
 
 
+class FormantsError(model.Sbv2Error):
+    """A formants field the request itself is at fault for (a bad value, a route that carries no formant contour): REST answers 400."""
+
+
+FORMANTS_FIELDS = ("formants", "formants_hz", "formants_max_hz", "formants_order", "formants_window")
+FORMANTS_DEFAULTS = (None, 100, None, None, None)
+
+
+def formants_options(options, rate):
+    """The model.FormantContour of a request with marks (None without formants).  Bad types are refused always, the ranges once the delivered
+    rate is known (rate None: the types alone), by the library's own host check, before any GPU work."""
+    n, hz, fmax, order, window = (getattr(options, k, d) for k, d in zip(FORMANTS_FIELDS, FORMANTS_DEFAULTS))
+    for name, v in (("formants", n), ("formants_order", order), ("formants_window", window)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+            raise FormantsError(f"{name} must be an integer: {v!r}")
+    if isinstance(hz, bool) or not isinstance(hz, int) or not 1 <= hz <= 1000:
+        raise FormantsError(f"formants_hz must be an integer in [1, 1000]: {hz!r}")
+    if fmax is not None and (isinstance(fmax, bool) or not isinstance(fmax, (int, float)) or not fmax > 0):
+        raise FormantsError(f"formants_max_hz must be a number above 0: {fmax!r}")
+    if n is None:
+        if (hz, fmax, order, window) != FORMANTS_DEFAULTS[1:]:
+            raise FormantsError("formants_hz / formants_max_hz / formants_order / formants_window describe a formant contour: name formants (how "
+                                "many, 1 to 8) as well")
+        return None
+    for name, v in (("formants", n), ("formants_order", order), ("formants_window", window)):
+        if v is not None and v < 1:   # (0 is the library's "default": here None is)
+            raise FormantsError(f"{name} must be at least 1: {v!r}")
+    if rate is None:
+        return None
+    if rate // hz < 1:
+        raise FormantsError(f"formants_hz must be at most the delivered rate {rate}: {hz!r}")
+    fc = model.FormantContour(rate // hz, n, order, window, f_hi=fmax)
+    try:
+        model.formant_contour_defaults(rate, fc)
+    except model.Sbv2Error as e:
+        raise FormantsError(str(e).replace("formant contour:", "formants:")) from None
+    return fc
+
+
+def refuse_formants(options, what: str):
+    """The formants fields where no marks of a whole signal are returned: refused, with the route that carries a formant contour."""
+    if any(getattr(options, k, d) != d for k, d in zip(FORMANTS_FIELDS, FORMANTS_DEFAULTS)):
+        raise FormantsError(f"formants and its fields need the speech marks of a whole signal: {what} carries none, ask /synthesize_marks "
+                            "(easy_synthesize_marks) instead")
+
+
+def require_formants(pipe, options):
+    """A request with a formant contour needs a pipeline whose fetch_request takes it: an older one is refused, not served without."""
+    if getattr(options, "formants", None) is None:
+        return
+    import inspect
+    try:
+        params = inspect.signature(pipe.fetch_request).parameters
+    except (TypeError, ValueError):
+        params = {}
+    if "formants" not in params and not any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
+        raise model.Sbv2Error(f"formants needs a pipeline whose fetch_request takes formants: {type(pipe).__name__} does not, and the "
+                              "request is not served without its formant contour")
+
+
+def formants_dict(fc, tokens) -> dict:
+    """The "formants" block of a marks dict from a filled model.FormantContour: {hop, order, f_hz [n][k], bw_hz [n][k]} (0 = the frame has no
+    such formant).  Besides, every token of `tokens` gains f1_hz and f2_hz: the mean of the non-zero F1 / F2 of the frames whose centre f hop +
+    hop // 2 lies in its span (None when there is none)."""
+    f = np.asarray(fc.f_hz, np.float64)
+    centre = np.arange(f.shape[0], dtype=np.int64) * fc.hop + fc.hop // 2
+    for t in tokens:
+        k0, k1 = np.searchsorted(centre, [t["start"], t["end"]])   # the frames with start <= centre < end
+        for q, name in enumerate(("f1_hz", "f2_hz")):
+            v = f[k0:k1, q][f[k0:k1, q] > 0] if q < f.shape[1] else f[:0, 0]
+            t[name] = float(v.mean()) if v.size else None
+    return {"hop": int(fc.hop), "order": int(fc.order), "f_hz": [[float(v) for v in row] for row in f],
+            "bw_hz": [[float(v) for v in row] for row in np.asarray(fc.bw_hz, np.float64)]}
+
+
 def spectrum_db(power) -> dict:
     """{"shape", "db"} of power [n_frames][n_bands]: db = 10 log10(max(power, 1e-10)) in f64, as base64 of little-endian float32."""
     db = (10.0 * np.log10(np.maximum(np.asarray(power, np.float64), 1e-10))).astype("<f4")
@@ -702,7 +785,7 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
         kw.update(gain=ln, flac=plan.flac)
-        pitch = spec = None
+        pitch = spec = fcon = None
         if marks is not None:
             kw.update(marks=True, env_hop=envelope_hop(options, fmt.sample_rate))
             pitch = pitch_options(options, fmt.sample_rate)
@@ -712,12 +795,16 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
             if spec is not None:
                 require_spectrum(pipe, options)
                 kw["spectrum"] = spec
+            fcon = formants_options(options, fmt.sample_rate)
+            if fcon is not None:
+                require_formants(pipe, options)
+                kw["formants"] = fcon
         track = track_options(options)
         if track is not None and (pitch is not None or shifts):   # (it needs a contour or a shift)
             kw["track"] = track
         got = model.split_fetch_result(pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw), marks=marks is not None,
                                        pitch=pitch is not None, dynamics=dyn is not None, token_pitch=tp is not None,
-                                       **({"spectrum": True} if spec is not None else {}))
+                                       **({"spectrum": True} if spec is not None else {}), **({"formants": True} if fcon is not None else {}))
         out, stats, dstats = got.signal, got.stats, got.dyn_stats
         if marks is not None:
             marks.append(marks_dict(plan.utts, plan.live, fmt, got.marks, got.pitch, **({"tracked": True} if "track" in kw and pitch is not None else {})))
@@ -729,6 +816,8 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
                 marks[-1]["formant_scale"] = fq
             if spec is not None:
                 marks[-1]["spectrum"] = spectrum_dict(got.spectrum)
+            if fcon is not None:
+                marks[-1]["formants"] = formants_dict(got.formants, marks[-1]["tokens"])
         if dstats is not None and dynamics_stats is not None:
             dynamics_stats.append([float(v) for v in dstats])
         if stats is not None and loudness_stats is not None:
@@ -756,6 +845,7 @@ def easy_synthesize(pipe: "model.Pipeline", sentences, style_vectors, style_id=0
     = finish_request over all rows of a run that holds this request alone (batcher.RequestBatcher: the same, several requests to a run)."""
     refuse_pitch(options, "easy_synthesize (/synthesize)")
     refuse_spectrum(options, "easy_synthesize (/synthesize)")
+    refuse_formants(options, "easy_synthesize (/synthesize)")
     plan = RequestPlan(sentences, style_vectors, style_id, speaker_id, options)
     require_formant(pipe, plan.options)   # (before any GPU work)
     require_assist(pipe, plan.options)
@@ -779,6 +869,8 @@ def easy_synthesize_marks(pipe: "model.Pipeline", sentences, style_vectors, styl
     pitch_options(plan.options, plan.fmt.sample_rate)  # ... and so is a bad pitch_hz or range
     spectrum_options(plan.options, plan.fmt.sample_rate)   # ... and a bad spectrum
     require_spectrum(pipe, plan.options)
+    formants_options(plan.options, plan.fmt.sample_rate)   # ... and a bad formant contour
+    require_formants(pipe, plan.options)
     if noise_seed is None:
         noise_seed = model.fresh_noise_seed()
     b = pipe.prepare(plan.utts, sdp_ratio=plan.options.sdp_ratio, length_scale=plan.options.length_scale, noise_scale=noise_scale,
@@ -979,6 +1071,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     refuse_token_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_dynamics(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    refuse_formants(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if spectrum:
         if not levels:
             raise SpectrumError("spectrum=True on a stream comes with its speech marks: pass levels=True as well")

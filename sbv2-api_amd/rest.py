@@ -55,6 +55,12 @@ and error mapping, so that a client of the reference's server cannot tell the di
   spectrum_stream = false (new; /synthesize_stream_marks only, with spectrum_mels and its fields): the first line gains "spectrum": {"n_fft",
                     "hop", "n_bands", "n_frames", "f_min", "f_max"} and every later line "spectrum": {"first", "shape": [n, n_bands], "db"}, the
                     frames that piece completed, decibels as below.  Without it the stream routes keep answering 400 for spectrum_mels.
+  formants = null (new; /synthesize_marks only, batched or not): the marks carry "formants": {"hop", "order", "f_hz": [[F1, F2, ...] per frame],
+                    "bw_hz": likewise} (0 = the frame has no such formant), the first `formants` (1 to 8) resonances of an LPC fit to the
+                    delivered samples, found on the device, and every token "f1_hz" / "f2_hz" (the mean over its frames, null without one).
+                    formants_hz = 100 (frames per second), formants_max_hz (null: min(5500, sample_rate / 2 - 50)), formants_order (null: 2 +
+                    sample_rate // 1000, rounded up to even), formants_window (null: 25 ms).  A bad value answers 400; so does any of the five
+                    fields on every other route, the stream routes included, naming /synthesize_marks.
   spectrum_mels = null (new; /synthesize_marks only, batched or not): the marks carry "spectrum": {"n_fft", "hop", "n_bands", "f_min", "f_max",
                     "shape": [n_frames, n_bands], "db": base64 of little-endian float32, 10 log10(max(power, 1e-10))}, the Slaney mel bands (0:
                     the spectrum_fft // 2 + 1 bins) of the delivered samples, reduced on the device.  spectrum_fft (null: the multiple of 32
@@ -219,6 +225,11 @@ def make_app(holder, batching=None):
         spectrum_hop: Optional[int] = None    # delivered samples per frame; null = sample_rate // 100
         spectrum_fmin: float = 0.0            # the mel bank's range (Hz)
         spectrum_fmax: Optional[float] = None # null = sample_rate / 2
+        formants: Optional[int] = None        # new: /synthesize_marks only (400 elsewhere): the marks carry "formants"; how many, [1, 8]
+        formants_hz: int = 100                # frames per second
+        formants_max_hz: Optional[float] = None   # resonances accepted up to here; null = min(5500, sample_rate / 2 - 50)
+        formants_order: Optional[int] = None  # LPC order, even, [4, 50]; null = 2 + sample_rate // 1000 rounded up to even
+        formants_window: Optional[int] = None # delivered samples, [64, 2048]; null = 25 ms
         voice_pivot_hz: Optional[Union[float, List[float]]] = None   # new: /synthesize_stream, /synthesize_stream_marks: the f0 (Hz, [70, 600]) that intonation_scale pivots about, one number or one per sentence; it opens the three scales on the stream routes; 400 elsewhere
 
     class SynthesizeMarksRequest(SynthesizeRequest):
@@ -280,6 +291,9 @@ def make_app(holder, batching=None):
                                               **({k: getattr(req, k) for k in orchestrator.SPECTRUM_FIELDS}
                                                  if any(getattr(req, k, d) != d for k, d in zip(orchestrator.SPECTRUM_FIELDS, (None, None, None, 0.0, None)))
                                                  else {}),
+                                              **({k: getattr(req, k) for k in orchestrator.FORMANTS_FIELDS}
+                                                 if any(getattr(req, k, d) != d
+                                                        for k, d in zip(orchestrator.FORMANTS_FIELDS, orchestrator.FORMANTS_DEFAULTS)) else {}),
                                               **({"level_target": req.level_target, "level_range": req.level_range, "level_slew": req.level_slew,
                                                   "level_hold": req.level_hold} if getattr(req, "level_target", None) is not None else {}),
                                               **({"assist": req.assist_text or None, "assist_weight": req.assist_text_weight}
@@ -292,9 +306,10 @@ def make_app(holder, batching=None):
     def synthesize(req: SynthesizeRequest):
         try:
             orchestrator.refuse_spectrum(req, "/synthesize")   # (the route first: it is what the client has to change)
+            orchestrator.refuse_formants(req, "/synthesize")
             with lock:
                 wav = holder.easy_synthesize(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
-        except (orchestrator.TokenPitchError, orchestrator.SpectrumError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -305,10 +320,11 @@ def make_app(holder, batching=None):
         # only with the event loop's help) nor parse_text, a model load or an eviction's drain inside the holder ever stall the event loop
         try:
             orchestrator.refuse_spectrum(req, "/synthesize")
+            orchestrator.refuse_formants(req, "/synthesize")
             with lock:                        # parse and queue only: the answer is awaited without it
                 fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching)
             wav = fut.result()
-        except (orchestrator.TokenPitchError, orchestrator.SpectrumError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -327,7 +343,7 @@ def make_app(holder, batching=None):
                     fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching,
                                                          marks=True)
                 audio, marks = fut.result()
-        except (orchestrator.TokenPitchError, orchestrator.SpectrumError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -349,6 +365,7 @@ def make_app(holder, batching=None):
             orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.check_assist(None, getattr(req, "assist_text_weight", 0.7))   # (a stream takes an assist; a bad weight is the request's fault)
+            orchestrator.refuse_formants(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             if not spectrum:
                 orchestrator.refuse_spectrum(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             elif req.spectrum_mels is None:
