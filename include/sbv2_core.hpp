@@ -395,6 +395,58 @@ inline int64_t stream_next_spectrum(sbv2_stream* s, const StreamSpectrum& spectr
     return part.n;
 }
 
+// Not in the reference (sbv2_stream_formant_contour in sbv2_hip.h states it): the formant contour of a request STREAM's delivered samples,
+// frame by frame.
+struct StreamFormantContour {
+    int32_t hop = 160, window = 0, order = 0, n_formants = 4;
+    double f_lo = 0.0, f_hi = 0.0, bw_max = 0.0;
+    int64_t n_frames = 0;   // out, set by stream_begin_request_formant_contour: ceil(total_samples / hop)
+    sbv2_stream_formant_contour c_struct() const { return sbv2_stream_formant_contour{hop, window, order, n_formants, f_lo, f_hi, bw_max, 0}; }
+};
+// sbv2_stream_begin_request_formant_contour: stream_begin_request_spectrum with the formant contour of the delivered samples; contour ==
+// nullptr is exactly that call.
+inline sbv2_stream* stream_begin_request_formant_contour(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch& batch, const sbv2_utt_options* opts,
+                                                         Assist* assist, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
+                                                         int64_t chunk_frames, const sbv2_stream_request& rq, StreamVoice* voice,
+                                                         const StreamLeveler* leveler, StreamSpectrum* spectrum, StreamFormantContour* contour,
+                                                         const sbv2_stream_levels* lv = nullptr, const sbv2_stream_pitch* sp = nullptr,
+                                                         int64_t* total_samples = nullptr, int64_t* n_tokens = nullptr, int64_t* n_env = nullptr,
+                                                         int64_t* n_pitch = nullptr) {
+    sbv2_stream* s = nullptr;
+    sbv2_stream_leveler c{};
+    sbv2_stream_spectrum q{};
+    sbv2_stream_formant_contour fc{};
+    if (leveler) c = leveler->c_struct();
+    if (spectrum) q = spectrum->c_struct();
+    if (contour) fc = contour->c_struct();
+    int64_t n_spec = 0, n_formant = 0;
+    int32_t n_bands = 0;
+    check(sbv2_stream_begin_request_formant_contour(bert, vits, &batch, opts, assist ? assist->c_struct() : nullptr, token_ids, s_lens, word2ph,
+                                                    chunk_frames, &rq, lv, sp, voice ? voice->c_struct() : nullptr, leveler ? &c : nullptr,
+                                                    spectrum ? &q : nullptr, contour ? &fc : nullptr, &s, total_samples, n_tokens, n_env, n_pitch,
+                                                    &n_spec, &n_bands, &n_formant));
+    if (spectrum) spectrum->n_frames = n_spec, spectrum->n_bands = n_bands;
+    if (contour) contour->n_frames = n_formant;
+    return s;
+}
+// sbv2_stream_next_formant_contour: the frames completed since the previous call, appended to f_hz / bw_hz ([frames][n_formants]) and status
+// ([frames]); returns how many
+inline int64_t stream_next_formant_contour(sbv2_stream* s, const StreamFormantContour& contour, std::vector<double>* f_hz, std::vector<double>* bw_hz,
+                                           std::vector<int32_t>* status) {
+    const size_t at = f_hz->size(), at_b = bw_hz->size(), at_s = status->size(), nk = (size_t)contour.n_formants;
+    f_hz->resize(at + (size_t)contour.n_frames * nk);   // (room for everything that can be pending)
+    bw_hz->resize(at_b + (size_t)contour.n_frames * nk);
+    status->resize(at_s + (size_t)contour.n_frames);
+    sbv2_stream_formant_part part{contour.n_frames, f_hz->data() + at, bw_hz->data() + at_b, status->data() + at_s, 0, 0, 0};
+    const int rc = sbv2_stream_next_formant_contour(s, &part);
+    const size_t n = rc == 0 ? (size_t)part.n : 0;
+    f_hz->resize(at + n * nk);
+    bw_hz->resize(at_b + n * nk);
+    status->resize(at_s + n);
+    check(rc);
+    return part.n;
+}
+
 }  // namespace sbv2_core
 
 #endif

@@ -756,7 +756,8 @@ int sbv2_debug_spectrum(int device, const void* x, int encoding, int64_t n, int3
  *   Levinson sum: one term per lane, the same butterfly; the sums over roots and coefficients: ascending index): two fetches of one ticket give
  *   identical bits, and a fetch gives the bits of sbv2_debug_formant_contour on the same samples.  Nothing claims equality with numpy: what is
  *   measured against a longdouble restatement, and against numpy's own roots, is in DESIGN.md (8y).
- * Not built: the contour on streams (sbv2_stream_*) and on sbv2_node_*, Burg's method, resampling to 2 f_hi before the analysis (the caller picks
+ * On a stream the same contour comes frame by frame: sbv2_stream_begin_request_formant_contour / sbv2_stream_next_formant_contour below.
+ * Not built: the contour on sbv2_node_*, Burg's method, resampling to 2 f_hi before the analysis (the caller picks
  *   the delivered rate; 16 kHz is the phonetician's), tracking the formants across frames. */
 typedef struct sbv2_formant_contour {
     int32_t hop, window, order, n_formants; /* in; window / order 0: the defaults */
@@ -1320,6 +1321,58 @@ int sbv2_stream_next_spectrum(sbv2_stream* s, sbv2_stream_spectrum_part* part);
  * (more than the spec allows: the most it allows).  Parameters, capacity and cuts are checked before any device call. */
 int sbv2_debug_stream_spectrum(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
                                sbv2_spectrum* spectrum, int groups, int64_t* per_push);
+
+/* ---- new: the formant contour of a stream, computed chunk by chunk ON THE DEVICE.
+ * sbv2_stream_begin_request_spectrum with, besides, the formant contour of sbv2_formant_contour over the DELIVERED samples of the stream (the
+ *   samples the levels, the pitch and the spectrum are taken of; on a level stream those the limiter emits), by that definition unchanged: the
+ *   rate is the format's (fmt NULL = the identity format, 44100 Hz), the parameters, defaults and refusals are sbv2_formant_contour's at that
+ *   rate, frame f has its window at b = f hop + hop / 2 - window / 2 and reads u[b - 1 .. b + window), positions outside [0, total_samples)
+ *   read as 0, *n_formant_frames = ceil(total_samples / hop).  A stream may carry the spectrum, the pitch and the formants together.
+ * Completion.  Frame f is complete once min(b + window, total_samples) <= D, D as for sbv2_stream_next_marks: frames complete in order and
+ *   about window / 2 samples late, everything that remains with the last chunk.
+ * Bits.  The device keeps the last min(D, window) delivered samples from replay to replay, in the sample's own type (two copies of at most
+ *   8 KB, used alternately); a frame's samples are read from them and from the replay's and then take the one-shot kernel's own frame body.
+ *   So f_hz, bw_hz and status equal sbv2_debug_formant_contour / sbv2_pipeline_fetch_request_formant_contour over the same samples bit for
+ *   bit, for every encoding (f32, s16, mu-law, A-law), behind FLAC and behind a level, whatever chunk_frames is.  One launch
+ *   (k_stream_formant) and one device-to-host copy more per replay.  A replay that completes no more frames than the device has compute
+ *   units gives every frame a workgroup of its own (csrc/formants.h states the rule; the bits do not depend on it).  The window table is
+ *   uploaded by the begin call.  The frames stay on the host (pinned) until the stream is freed or the handle begins another.
+ * contour == NULL: exactly sbv2_stream_begin_request_spectrum: the same launches, the same bytes, *n_formant_frames = 0,
+ *   sbv2_stream_next_formant_contour refused.  With a contour the audio bytes, sbv2_stream_marks, the stream levels, pitch and spectrum are
+ *   those of the same stream without, and the stream delivers in order only.
+ * Refused before the handles are looked at, with nothing written: a non-zero reserved and everything sbv2_formant_contour's parameters
+ *   refuse at the format's rate; besides, everything sbv2_stream_begin_request_spectrum refuses.  2^30 frames or more are refused.
+ * Not built: per-token f1_hz / f2_hz on streams; the contour on sbv2_node_*; on the plain sbv2_stream_begin* entries (a request stream of one
+ *   row serves them); tracking the formants across frames. */
+typedef struct sbv2_stream_formant_contour {
+    int32_t hop, window, order, n_formants; /* as sbv2_formant_contour; window / order 0: the defaults */
+    double f_lo, f_hi, bw_max;              /* Hz; 0: the defaults */
+    int32_t reserved;                       /* must be 0 */
+} sbv2_stream_formant_contour;
+int sbv2_stream_begin_request_formant_contour(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                                              const sbv2_assist* assist /* may be NULL */, const int64_t* token_ids, const int64_t* s_lens,
+                                              const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
+                                              const sbv2_stream_levels* lv /* may be NULL */, const sbv2_stream_pitch* sp /* may be NULL */,
+                                              const sbv2_stream_voice* voice /* may be NULL */, const sbv2_stream_leveler* leveler /* may be NULL */,
+                                              const sbv2_stream_spectrum* spectrum /* may be NULL */,
+                                              const sbv2_stream_formant_contour* contour /* may be NULL */, sbv2_stream** out, int64_t* total_samples,
+                                              int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch, int64_t* n_spec, int32_t* n_bands,
+                                              int64_t* n_formant_frames);
+/* Host only: the frames [first, first + n) that became complete since the previous call, f_hz / bw_hz [n][n_formants] and status [n] (may be
+ * NULL) as sbv2_formant_contour gives them, and delivered = D.  A capacity (in FRAMES) below n, or a NULL f_hz / bw_hz with frames pending, is
+ * refused with nothing written and nothing lost: repeat with more room.  Not calling it loses nothing.  Refused on a stream begun without
+ * a contour. */
+typedef struct sbv2_stream_formant_part {
+    int64_t capacity; double* f_hz; double* bw_hz; int32_t* status; int64_t first, n;
+    int64_t delivered;
+} sbv2_stream_formant_part;
+int sbv2_stream_next_formant_contour(sbv2_stream* s, sbv2_stream_formant_part* part);
+/* Test hook: the fed stage on its own.  x[n] (host; encoding, contour, lpc and status as sbv2_debug_formant_contour) is cut at the ascending
+ * positions cuts[ncuts] into ncuts + 1 pushes (empty ones allowed), each handed a copy of its own samples only; per_push [ncuts + 1] receives
+ * the frames each push completed.  pack: 0 = the rule of csrc/formants.h, 1 or 4 = that many frames per workgroup in every launch (4 with a
+ * window above 512 runs as 1).  Parameters, capacity and cuts are checked before any device call. */
+int sbv2_debug_stream_formant_contour(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
+                                      sbv2_formant_contour* contour, double* lpc, int32_t* status, int pack, int64_t* per_push);
 
 /* Test hook: the two kernels on a host plane F [C][ld] (pitch ld, any value >= 1; on the device it lies between NaN words).  Assist sequence a
  * is the columns [a_start[a], a_start[a] + a_len[a]) of F; text column t < L reads source column map[t] (< 0: padding) and belongs to row

@@ -153,6 +153,18 @@ class Sbv2StreamSpectrumPart(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("power", f32p), ("first", C.c_int64), ("n", C.c_int64), ("delivered", C.c_int64)]
 
 
+class Sbv2StreamFormantContour(C.Structure):
+    """struct sbv2_stream_formant_contour (include/sbv2_hip.h)."""
+    _fields_ = [("hop", C.c_int32), ("window", C.c_int32), ("order", C.c_int32), ("n_formants", C.c_int32), ("f_lo", C.c_double),
+                ("f_hi", C.c_double), ("bw_max", C.c_double), ("reserved", C.c_int32)]
+
+
+class Sbv2StreamFormantPart(C.Structure):
+    """struct sbv2_stream_formant_part (include/sbv2_hip.h)."""
+    _fields_ = [("capacity", C.c_int64), ("f_hz", C.POINTER(C.c_double)), ("bw_hz", C.POINTER(C.c_double)), ("status", C.POINTER(C.c_int32)),
+                ("first", C.c_int64), ("n", C.c_int64), ("delivered", C.c_int64)]
+
+
 class Sbv2StreamVoice(C.Structure):
     """struct sbv2_stream_voice (include/sbv2_hip.h)."""
     _fields_ = [("voice", Sbv2Voice), ("formant_scale", C.c_double), ("pivot_hz", C.POINTER(C.c_double)), ("reserved", C.c_double * 2)]
@@ -355,6 +367,15 @@ SYMBOLS = {
     "sbv2_stream_next_spectrum": (C.c_int, [C.c_void_p, C.POINTER(Sbv2StreamSpectrumPart)]),
     "sbv2_debug_stream_spectrum": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2Spectrum), C.c_int,
                                              i64p]),
+    "sbv2_stream_begin_request_formant_contour": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions),
+                                                            C.POINTER(Sbv2Assist), i64p, i64p, i64p, C.c_int64, C.POINTER(Sbv2StreamRequest),
+                                                            C.POINTER(Sbv2StreamLevels), C.POINTER(Sbv2StreamPitch), C.POINTER(Sbv2StreamVoice),
+                                                            C.POINTER(Sbv2StreamLeveler), C.POINTER(Sbv2StreamSpectrum),
+                                                            C.POINTER(Sbv2StreamFormantContour), C.POINTER(C.c_void_p), i64p, i64p, i64p, i64p, i64p,
+                                                            C.POINTER(C.c_int32), i64p]),
+    "sbv2_stream_next_formant_contour": (C.c_int, [C.c_void_p, C.POINTER(Sbv2StreamFormantPart)]),
+    "sbv2_debug_stream_formant_contour": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2FormantContour),
+                                                    C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, i64p]),
     "sbv2_stream_leveler_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "sbv2_debug_leveler_stream": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2StreamLevel),
                                             C.POINTER(Sbv2StreamLeveler), C.c_void_p, i64p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double)]),

@@ -2,7 +2,8 @@
 // samples a formatted fetch leaves in HBM, its roots, and the first n_formants resonances (frequency, bandwidth) among them, as
 // include/sbv2_hip.h states it above sbv2_formant_contour.  The time axis is that of the pitch contour and of the spectrum (marks.h).
 // Used by sbv2_pipeline_fetch_request_formant_contour (fetch.cpp), sbv2_formant_contour_defaults (api.cpp) and the test hook
-// sbv2_debug_formant_contour.  (The formant SCALE, which moves the formants, is voice.h's.)
+// sbv2_debug_formant_contour; fed replay by replay (StreamFormants below) by sbv2_stream_begin_request_formant_contour (stream_output.cpp) and
+// the test hook sbv2_debug_stream_formant_contour.  (The formant SCALE, which moves the formants, is voice.h's.)
 #pragma once
 #include <map>
 
@@ -65,6 +66,63 @@ class Formants {
     DeviceBuffer dev_;                      // F [nf][nk] | B [nf][nk] | lpc [nf][p + 1] (asked for only) | status [nf]
     PinnedBuffer host_;
     int64_t nf_ = 0, nk_ = 0, nlpc_ = 0;
+};
+
+// The same stage FED piece by piece (a stream's replays), by sbv2_formant_contour's convention unchanged: frame f reads the window
+// [b, b + window) and the sample at b - 1, b = f hop + hop / 2 - window / 2; positions outside [0, total) read as 0; n_frames = ceil(total / hop).
+// The completion rule: frame f is complete once min(b + window, total) <= D, D the samples fed (or, for what a stream hands out, delivered)
+// so far.  Frames complete in order (b ascends with f); after the last push everything is complete.
+// The carry: the last min(D, window) fed samples, in the sample's own type, on the device.  That is enough: the first incomplete frame has
+// b + window > D, so its earliest read b - 1 is >= D - window.  Sized once for kFormantMaxWindow elements of the widest type and held twice (a
+// push reads one copy and writes the other: a push shorter than the carry keeps part of the old one, and no workgroup reads what another
+// one of the same launch overwrites) = 16 KB whatever the stream's length.
+// A push is ONE launch (k_stream_formant) and one copy of the frames it completed from the push's device records to the pinned mirror, which
+// holds every frame of the stream as a record {F [n_formants] | B [n_formants] | lpc [order + 1] (asked for only) | status} until the next
+// begin; a push that completes no frame still updates the carry, n = 0 enqueues nothing.  The window table is uploaded in begin.  No atomics.
+//
+// Ownership on a stream.  formant_frames_per_block is tuned for tens of thousands of frames; a push completes a few hundred at most and the
+// first chunk far fewer, fewer than the device has compute units, and four frames to a workgroup then leave most of the chip idle while one
+// wave computes all order + 1 lags of its frame.  So a push that completes no more frames than the device has compute units (read once in
+// begin) takes ONE frame per workgroup whatever the window, the head dealt over four waves and wave 0 running the tail; above that count it
+// takes formant_frames_per_block(window).  The bits do not depend on the choice (above: a lag is one wave's lane-strided sum and one
+// butterfly under either).  Measured (DESIGN.md 8z, 16 kHz, window 400): a first push of 147 frames takes 46 us against 58 us with four frames
+// to a workgroup.  One frame per workgroup was also the faster one above the count (1.10 - 1.20 times at 296 to 2378 frames): the threshold
+// is where the rule stops, not where the other ownership starts to win, and has not been swept.
+inline int formant_stream_frames_per_block(int64_t frames, int window, int cus) { return frames <= cus ? 1 : formant_frames_per_block(window); }
+// the completion rule on its own: the frames of a signal of `total` samples that are complete once D of them are in
+int64_t formant_frames_complete(const FormantContourSpec& sp, int64_t total, int64_t D);
+class StreamFormants {
+  public:
+    StreamFormants() = default;
+    StreamFormants(const StreamFormants&) = delete;
+    StreamFormants& operator=(const StreamFormants&) = delete;
+    // Host only, throws: the spec within the stage's limits, fewer than 2^30 frames
+    static void check(const FormantContourSpec& sp, int64_t total);
+    // Uploads the window table the previous stream did not leave, sizes the push's records for pushes of up to `most` samples (a longer one
+    // grows them, which waits for s) and waits for s once.  pack: 0 = the rule above; 1 / 4 = that many frames per workgroup in every push
+    // (4 with window > kFormantPackWindow runs as 1).  lpc: the records keep the polynomial (the hook's).
+    void begin(const FormantContourSpec& sp, int encoding, int64_t total, int64_t most, hipStream_t s, int pack = 0, bool lpc = false);
+    // x = the sample at delivered position D0 (device), D0 = fed(); returns the frames this push completed; n = 0 enqueues nothing
+    int64_t push(const void* x, int64_t D0, int64_t n, hipStream_t s);
+    int64_t fed() const { return fed_; }
+    int64_t total() const { return total_; }
+    int64_t n_frames() const { return nf_; }
+    const FormantContourSpec& spec() const { return sp_; }
+    int64_t complete(int64_t D) const { return formant_frames_complete(sp_, total_, D); }
+    // frame f is valid once the push that completed it has run on s: n_formants values each, order + 1 for the polynomial
+    const double* f_host(int64_t f) const { return host_.as<double>() + f * rec_; }
+    const double* bw_host(int64_t f) const { return f_host(f) + sp_.n_formants; }
+    const double* lpc_host(int64_t f) const { return f_host(f) + 2 * sp_.n_formants; }
+    int32_t status_host(int64_t f) const { return *reinterpret_cast<const int32_t*>(f_host(f) + rec_ - 1); }
+
+  private:
+    static constexpr size_t kCarryBytes = (size_t)kFormantMaxWindow * sizeof(float);   // one copy, in the widest sample type
+    PinnedBuffer host_, stage_;   // the records' mirror; upload staging of the window
+    DeviceBuffer window_, carry_, out_;
+    FormantContourSpec sp_;
+    int64_t total_ = 0, nf_ = 0, fed_ = 0, done_ = 0, rec_ = 0;   // rec_: f64 words per record (the status takes the last one)
+    int encoding_ = 0, parity_ = 0, forced_ = 0, cus_ = 0, window_len_ = 0;
+    bool lpc_ = false;
 };
 
 }  // namespace sbv2

@@ -17,8 +17,9 @@ struct sbv2_stream {
     // one sync, and the delivered format
     std::vector<int64_t> durations, offs;
     PcmFmtSpec spec;
-    // the entries sbv2_stream_next_marks and the frames sbv2_stream_next_pitch / sbv2_stream_next_spectrum have handed out so far
-    int64_t tok_out = 0, env_out = 0, pitch_out = 0, spec_out = 0;
+    // the entries sbv2_stream_next_marks and the frames sbv2_stream_next_pitch / sbv2_stream_next_spectrum / sbv2_stream_next_formant_contour have
+    // handed out so far
+    int64_t tok_out = 0, env_out = 0, pitch_out = 0, spec_out = 0, formant_out = 0;
     // what the stream was begun with is the model's to say: its output side, nullptr for a plain stream (native f32)
     const StreamOutput* output() const { return vits->m->stream_output(); }
 };
@@ -431,9 +432,30 @@ int sbv2_stream_begin_request_spectrum(sbv2_bert* bert, sbv2_vits* vits, const s
                                        const sbv2_stream_voice* voice, const sbv2_stream_leveler* leveler, const sbv2_stream_spectrum* spectrum,
                                        sbv2_stream** out, int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch, int64_t* n_spec,
                                        int32_t* n_bands) {
+    return sbv2_stream_begin_request_formant_contour(bert, vits, batch, opts, assist, token_ids, s_lens, word2ph, chunk_frames, rq, lv, sp, voice,
+                                                     leveler, spectrum, nullptr, out, total_samples, n_tokens, n_env, n_pitch, n_spec, n_bands, nullptr);
+}
+
+// ... and with the formant contour of the same delivered samples, fed by the same pushes (the contract above sbv2_stream_formant_contour,
+// include/sbv2_hip.h; StreamFormants, formants.hip).  contour NULL: exactly the call above.  Its fields are checked with the others', before
+// the handles are looked at, at the format's rate, by formant_contour_spec as sbv2_formant_contour's are.
+int sbv2_stream_begin_request_formant_contour(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts,
+                                              const sbv2_assist* assist, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
+                                              int64_t chunk_frames, const sbv2_stream_request* rq, const sbv2_stream_levels* lv,
+                                              const sbv2_stream_pitch* sp, const sbv2_stream_voice* voice, const sbv2_stream_leveler* leveler,
+                                              const sbv2_stream_spectrum* spectrum, const sbv2_stream_formant_contour* contour, sbv2_stream** out,
+                                              int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch, int64_t* n_spec,
+                                              int32_t* n_bands, int64_t* n_formant_frames) {
     API_BEGIN
     StreamMarksSpec marks;
     bool on = levels_spec(lv, &marks);
+    if (contour) {
+        SBV2_REQUIRE(contour->reserved == 0, "sbv2_stream_formant_contour.reserved must be 0");
+        const int rate = rq && rq->fmt ? pcm_format_spec(rq->fmt).rate : PcmFmtSpec().rate;
+        marks.formant_spec = formant_contour_spec(rate, contour->hop, contour->window, contour->order, contour->n_formants, contour->f_lo,
+                                                  contour->f_hi, contour->bw_max);
+        marks.formants = on = true;
+    }
     if (spectrum) {
         SBV2_REQUIRE(spectrum->reserved == 0, "sbv2_stream_spectrum.reserved must be 0");
         const int rate = rq && rq->fmt ? pcm_format_spec(rq->fmt).rate : PcmFmtSpec().rate;
@@ -474,6 +496,8 @@ int sbv2_stream_begin_request_spectrum(sbv2_bert* bert, sbv2_vits* vits, const s
     const StreamSpectrum* sq = (*out)->output()->spectrum();
     if (n_spec) *n_spec = sq ? sq->n_frames() : 0;
     if (n_bands) *n_bands = sq ? sq->spec().n_bands() : 0;
+    const StreamFormants* fq = (*out)->output()->formants();
+    if (n_formant_frames) *n_formant_frames = fq ? fq->n_frames() : 0;
     API_END
 }
 
@@ -548,6 +572,31 @@ int sbv2_stream_next_spectrum(sbv2_stream* s, sbv2_stream_spectrum_part* part) {
     part->n = n;
     part->delivered = D;
     s->spec_out += n;
+    API_END
+}
+
+// The formant frames completed since the previous call (the rule above sbv2_stream_next_formant_contour, include/sbv2_hip.h).  Host only, for
+// the reason given above sbv2_stream_next_marks.
+int sbv2_stream_next_formant_contour(sbv2_stream* s, sbv2_stream_formant_part* part) {
+    API_BEGIN
+    SBV2_REQUIRE(s && part, "bad arguments");
+    const StreamFormants* q = s->output() ? s->output()->formants() : nullptr;
+    SBV2_REQUIRE(q, "this stream was begun without a formant contour: begin it with sbv2_stream_begin_request_formant_contour");
+    const int64_t D = s->next >= s->calls ? q->total() : s->output()->delivered();
+    const int64_t n = q->complete(D) - s->formant_out, nk = q->spec().n_formants;
+    SBV2_REQUIRE(part->capacity >= n, "formant contour arrays too small: " + std::to_string(part->capacity) + " < " + std::to_string(n) +
+                                          " pending frames");
+    SBV2_REQUIRE(n == 0 || (part->f_hz && part->bw_hz), "NULL f_hz / bw_hz with " + std::to_string(n) + " pending frames");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t f = s->formant_out + i;
+        std::memcpy(part->f_hz + i * nk, q->f_host(f), sizeof(double) * (size_t)nk);
+        std::memcpy(part->bw_hz + i * nk, q->bw_host(f), sizeof(double) * (size_t)nk);
+        if (part->status) part->status[i] = q->status_host(f);
+    }
+    part->first = s->formant_out;
+    part->n = n;
+    part->delivered = D;
+    s->formant_out += n;
     API_END
 }
 

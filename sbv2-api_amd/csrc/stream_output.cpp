@@ -9,13 +9,14 @@ int64_t StreamOutput::check(const PcmFmtSpec& spec, const StreamLevelSpec* level
     if (marks) StreamLevels::check(nullptr, 0, marks->env_hop, pcm_format_out_len(spec, joined));
     if (marks && marks->pitch) StreamPitch::check(marks->pitch_spec, pcm_format_out_len(spec, joined));
     if (marks && marks->spectrum) StreamSpectrum::check(marks->spectrum_spec, pcm_format_out_len(spec, joined));
+    if (marks && marks->formants) StreamFormants::check(marks->formant_spec, pcm_format_out_len(spec, joined));
     return level ? stream_level_lookahead(spec.rate) : 0;   // (sizes the slots: a replay may hand back A samples more than it fed)
 }
 
 void StreamOutput::begin(const PcmFmtSpec& spec, bool flac, const StreamLevelSpec* level, const StreamMarksSpec* marks, const std::vector<int64_t>& used,
                          const std::vector<int64_t>& offs, const int64_t* place, int hop, int64_t joined, int64_t cap, hipStream_t s,
                          const StreamLevelerSpec* leveler) {
-    flac_on_ = level_on_ = leveler_on_ = levels_on_ = pitch_on_ = spectrum_on_ = voice_on_ = false;
+    flac_on_ = level_on_ = leveler_on_ = levels_on_ = pitch_on_ = spectrum_on_ = formants_on_ = voice_on_ = false;
     SBV2_REQUIRE(!leveler || level, "a stream leveler needs a level: its ceiling and its starting gain");
     spec_ = spec;
     A_ = level ? stream_level_lookahead(spec.rate) : 0;
@@ -63,6 +64,11 @@ void StreamOutput::begin(const PcmFmtSpec& spec, bool flac, const StreamLevelSpe
         if (!spectrum_) spectrum_.reset(new StreamSpectrum);
         spectrum_->begin(marks->spectrum_spec, spec_.encoding, total_out, cap, s);
         spectrum_on_ = true;
+    }
+    if (marks && marks->formants) {   // ... and their formant contour; its window is uploaded here
+        if (!formants_) formants_.reset(new StreamFormants);
+        formants_->begin(marks->formant_spec, spec_.encoding, total_out, cap, s);
+        formants_on_ = true;
     }
 }
 
@@ -139,6 +145,7 @@ void StreamOutput::push(const std::vector<FmtPiece>& pieces_in, const std::vecto
     if (levels_on_) levels_->push(dev, spec_.encoding, d0, n, s);
     if (pitch_on_) pitch_->push(dev, d0, n, s);
     if (spectrum_on_) spectrum_->push(dev, d0, n, s);
+    if (formants_on_) formants_->push(dev, d0, n, s);
     if (flac_on_) {
         // ONE push per replay: the encoder packs every block that completes (with the request's last chunk also the short final frame);
         // window w completes the frames of the push up to the block its last sample lies in
@@ -162,6 +169,7 @@ const char* StreamOutput::ordered() const {
            : levels_on_ ? "a stream with levels delivers its chunks in order only: the reduction carries partial sums from chunk to chunk"
            : pitch_on_  ? "a stream with pitch delivers its chunks in order only: the estimator carries the last samples from chunk to chunk"
            : spectrum_on_ ? "a stream with a spectrum delivers its chunks in order only: the stage carries the last samples from chunk to chunk"
+           : formants_on_ ? "a stream with a formant contour delivers its chunks in order only: the stage carries the last samples from chunk to chunk"
                         : nullptr;
 }
 

@@ -1,8 +1,9 @@
 // What a running stream does to decoded PCM after the decoder (stream_output.cpp): the formatter, the optional level control, level reduction,
-// pitch estimator, spectrum stage and FLAC encoder, and the sink.  One object per execution context, behind VitsModel::stream_* as OutputChain (api_internal.h)
+// pitch estimator, spectrum stage, formant stage and FLAC encoder, and the sink.  One object per execution context, behind VitsModel::stream_* as OutputChain (api_internal.h)
 // is behind the formatted fetches; the decoder's replays, their pinned slots and the prefetch stay in VitsModel.
 #pragma once
 #include "flac_encode.h"
+#include "formants.h"
 #include "leveler.h"
 #include "limiter.h"
 #include "marks.h"
@@ -24,6 +25,9 @@ struct StreamMarksSpec {
     // the spectrum of the delivered samples (sbv2_stream_spectrum): likewise
     bool spectrum = false;
     SpectrumSpec spectrum_spec;
+    // the formant contour of the delivered samples (sbv2_stream_formant_contour): likewise
+    bool formants = false;
+    FormantContourSpec formant_spec;
 };
 
 // One window of a replay as the voice stage is fed it (sbv2_stream_voice): the window's central native samples clipped to its row, the
@@ -68,7 +72,7 @@ class StreamOutput {
                const StreamLevelerSpec* leveler = nullptr);
     // One replay, enqueued on s: the formatter over its windows (sig[w] = window w), with a level the limiter's push and the cast, the levels
     // and pitch pushes on the delivered samples, then the sink: the encoder's push into `host` or the copy there.  fmt_slot: the formatter's
-    // table slot; cap: what `host` was sized for; rec: filled for deliver.  A stream begun with a spectrum pushes that stage where the pitch is.
+    // table slot; cap: what `host` was sized for; rec: filled for deliver.  A stream begun with a spectrum or a formant contour pushes those stages where the pitch is.
     // A voice stream: feed[w] = window w's native samples and c0 = the replay's first call; the pieces and signals are then made here, from
     // the shifted rows and the delivery rule, and the caller's are not looked at (sig[w].j1 - sig[w].j0 stays what window w fed).
     void push(const std::vector<FmtPiece>& pieces, const std::vector<FmtSignal>& sig, int64_t total, bool last, int fmt_slot, void* host,
@@ -89,6 +93,7 @@ class StreamOutput {
     const StreamLevels* levels() const { return levels_on_ ? levels_.get() : nullptr; }
     const StreamPitch* pitch() const { return pitch_on_ ? pitch_.get() : nullptr; }
     const StreamSpectrum* spectrum() const { return spectrum_on_ ? spectrum_.get() : nullptr; }
+    const StreamFormants* formants() const { return formants_on_ ? formants_.get() : nullptr; }
     int64_t delivered() const { return delivered_; }
 
   private:
@@ -100,11 +105,12 @@ class StreamOutput {
     std::unique_ptr<StreamLevels> levels_;
     std::unique_ptr<StreamPitch> pitch_;
     std::unique_ptr<StreamSpectrum> spectrum_;
+    std::unique_ptr<StreamFormants> formants_;
     std::unique_ptr<StreamVoice> voice_;
     std::vector<FmtPiece> vpieces_;   // a voice stream's pieces: every row's shifted samples at its place
     std::vector<int64_t> vupto_;      // ... and its calls' cumulative delivered samples
     bool voice_on_ = false;
-    bool flac_on_ = false, level_on_ = false, leveler_on_ = false, levels_on_ = false, pitch_on_ = false, spectrum_on_ = false;   // what the running stream uses of them
+    bool flac_on_ = false, level_on_ = false, leveler_on_ = false, levels_on_ = false, pitch_on_ = false, spectrum_on_ = false, formants_on_ = false;   // what the running stream uses of them
     int64_t A_ = 0;           // the level's look-ahead in delivered samples (0 without a level)
     int64_t delivered_ = 0;
 };

@@ -2584,6 +2584,54 @@ int sbv2_debug_stream_spectrum(int device, const void* x, int encoding, int64_t 
     API_END
 }
 
+// The fed formant stage (StreamFormants, formants.hip) on its own, as the hook above feeds the spectrum: every push is a COPY of its piece
+// between two guards of a fill pattern.  Parameters, capacity and cuts are checked before any device call.
+int sbv2_debug_stream_formant_contour(int device, const void* x, int encoding, int64_t n, const int64_t* cuts, int ncuts, int32_t sample_rate,
+                                      sbv2_formant_contour* contour, double* lpc, int32_t* status, int pack, int64_t* per_push) {
+    API_BEGIN
+    SBV2_REQUIRE(contour && per_push && pcm_encoding_known(encoding) && n >= 0 && ncuts >= 0 && (x || n == 0) && (ncuts == 0 || cuts), "bad arguments");
+    SBV2_REQUIRE(pack == 0 || pack == 1 || pack == 4, "pack must be 0, 1 or 4: " + std::to_string(pack));
+    const FormantContourSpec sp = check_formant_contour(sample_rate, contour);
+    StreamFormants::check(sp, n);
+    const int64_t nf = formant_frames(n, sp.hop);
+    SBV2_REQUIRE(contour->capacity >= nf,
+                 "formant contour arrays too small: " + std::to_string(contour->capacity) + " < " + std::to_string(nf) + " frames");
+    SBV2_REQUIRE(contour->f_hz && contour->bw_hz, "sbv2_formant_contour.f_hz and bw_hz must not be NULL");
+    std::vector<int64_t> edge(1, 0);
+    int64_t longest = 0;
+    for (int i = 0; i < ncuts; ++i) {
+        SBV2_REQUIRE(cuts[i] >= edge.back() && cuts[i] <= n, "cuts must ascend within [0, n]");
+        edge.push_back(cuts[i]);
+    }
+    edge.push_back(n);
+    for (size_t i = 0; i + 1 < edge.size(); ++i) longest = std::max(longest, edge[i + 1] - edge[i]);
+    const size_t esz = pcm_encoding_bytes(encoding), guard = 4096;
+    AudioScratch r(device, x, (size_t)n * esz);
+    DeviceBuffer piece;
+    char* pc = static_cast<char*>(piece.reserve((size_t)longest * esz + 2 * guard, (size_t)longest * esz + 2 * guard, r.s));
+    HIP_CHECK(hipMemsetAsync(pc, 0x5A, (size_t)longest * esz + 2 * guard, r.s));
+    StreamFormants st;
+    st.begin(sp, encoding, n, longest, r.s, pack, lpc != nullptr);
+    for (int i = 0; i <= ncuts; ++i) {
+        const int64_t len = edge[i + 1] - edge[i];
+        // (stream order: the previous push's launch has read the piece before this copy overwrites it)
+        if (len) HIP_CHECK(hipMemcpyAsync(pc + guard, r.x.as<char>() + (size_t)edge[i] * esz, (size_t)len * esz, hipMemcpyDeviceToDevice, r.s));
+        per_push[i] = st.push(pc + guard, edge[i], len, r.s);
+    }
+    HIP_CHECK(hipStreamSynchronize(r.s));
+    SBV2_REQUIRE(st.complete(st.fed()) == nf, "internal: frames left incomplete after the last push");
+    const int nk = sp.n_formants;
+    for (int64_t f = 0; f < nf; ++f) {
+        std::memcpy(contour->f_hz + f * nk, st.f_host(f), sizeof(double) * (size_t)nk);
+        std::memcpy(contour->bw_hz + f * nk, st.bw_host(f), sizeof(double) * (size_t)nk);
+        if (lpc) std::memcpy(lpc + f * (sp.order + 1), st.lpc_host(f), sizeof(double) * (size_t)(sp.order + 1));
+        if (contour->status) contour->status[f] = st.status_host(f);
+        if (status) status[f] = st.status_host(f);
+    }
+    contour->n_frames = nf;
+    API_END
+}
+
 // ---- the repeated-launch hooks (run_repeated above): operands as in the one-launch hook of the same kernel, two inputs xa / xb, ya / yb = the first result of
 // each; prev (may be null) = what every repetition accumulates onto
 int sbv2_debug_repeat_respair(int device, const float* xa, const float* xb, const float* w1, const float* w2, const float* b1, const float* b2, int64_t C,

@@ -209,12 +209,13 @@ class TTSModelHolder:
         return [self.parse_text(t) if t else None for t in lines]
 
     def easy_synthesize_stream(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None, chunk_frames=256,
-                               split=False, levels=False, pitch=False, spectrum=False):
+                               split=False, levels=False, pitch=False, spectrum=False, formants=False):
         """The request delivered while it is synthesised (orchestrator.easy_synthesize_stream): a generator over the bytes of the FLAC stream or
         WAV (an orchestrator.SynthesisStream: close() it when it is abandoned before its end).  Errors of the request are raised here, before
         the first piece.  The stream's `.marks` holds the token and word timing of the whole answer from the start; levels=True adds the levels
         piece by piece (take_marks(): see orchestrator.easy_synthesize_stream), pitch=True (with levels=True and options.pitch_hz) the pitch
-        contour as well, spectrum=True (with levels=True and options.spectrum_mels) the spectrum's frames.
+        contour as well, spectrum=True (with levels=True and options.spectrum_mels) the spectrum's frames, formants=True (with levels=True and
+        options.formants) the formant contour's.
 
         split=False (the default): the request as ONE utterance.  `text` is a str, parsed as a whole (as split_sentences = False does), or the
         already parsed text as a one-entry list; a second live sentence is refused.
@@ -249,7 +250,7 @@ class TTSModelHolder:
             st = orchestrator.easy_synthesize_stream(self.bert, m.vits2, sentences, m.style_vectors, style_id, speaker_id, options,
                                                      noise_seed=noise_seed, chunk_frames=chunk_frames, split=split,
                                                      **({"levels": True} if levels else {}), **({"pitch": True} if pitch else {}),
-                                                     **({"spectrum": True} if spectrum else {}))
+                                                     **({"spectrum": True} if spectrum else {}), **({"formants": True} if formants else {}))
         except BaseException:
             release()
             raise

@@ -1096,6 +1096,42 @@ def debug_stream_spectrum(x, cuts, sample_rate: int, spectrum: Spectrum, device:
     return spectrum.take(c, power), per_push
 
 
+def debug_stream_formant_contour(x, cuts, sample_rate: int, contour: FormantContour, device: int = 0, encoding: str | None = None, pack: int = 0):
+    """Test hook: the fed formant stage on its own (sbv2_debug_stream_formant_contour).  x as for debug_formant_contour, cut at the ascending
+    positions `cuts` into len(cuts) + 1 pushes; pack: 0 = the library's rule, 1 / 4 = that many frames per workgroup in every launch
+    -> (contour with f_hz / bw_hz / status filled, lpc [n_frames][order + 1], per_push [len(cuts) + 1], the frames each push completed)."""
+    x = np.ascontiguousarray(x).reshape(-1)
+    if encoding is None and x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"the formant contour is taken of int16 or float32 samples, not {x.dtype}")
+    if encoding is not None and (encoding not in ENCODINGS or x.dtype != _DTYPES[encoding]):
+        raise Sbv2Error(f"the formant contour of {encoding!r} samples is not taken of {x.dtype}")
+    enc = ENCODINGS[encoding] if encoding is not None else int(x.dtype == np.int16)
+    cuts = np.ascontiguousarray(np.asarray(cuts, np.int64).reshape(-1))
+    probe = copy.copy(contour)
+    nf = formant_contour_defaults(sample_rate, probe, x.size)   # (the order sizes lpc)
+    c, arrays = contour.c_struct(x.size, int(sample_rate))
+    lpc, status = np.zeros((max(nf, 1), probe.order + 1), np.float64), np.zeros(max(nf, 1), np.int32)
+    per_push = np.zeros(cuts.size + 1, np.int64)
+    check(_lib.lib().sbv2_debug_stream_formant_contour(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, enc, x.size,
+                                                       cuts.ctypes.data_as(i64p) if cuts.size else None, cuts.size, int(sample_rate), C.byref(c),
+                                                       _f64p(lpc), status.ctypes.data_as(C.POINTER(C.c_int32)), int(pack),
+                                                       per_push.ctypes.data_as(i64p)))
+    contour.take(c, arrays, int(sample_rate))
+    assert np.array_equal(status[:nf], contour.status)
+    return contour, lpc[:nf], per_push
+
+
+def stream_formants_complete(D: int, hop: int, window: int, total: int) -> int:
+    """The completion rule of a stream's formant contour (above sbv2_stream_next_formant_contour): the number of frames f < ceil(total / hop)
+    with min(b + window, total) <= D, b = f hop + hop // 2 - window // 2.  They are the first ones: frames complete in order."""
+    D, hop, window, total = int(D), int(hop), int(window), int(total)
+    nf = -(-total // hop) if total > 0 else 0
+    if nf == 0 or D >= total:
+        return nf
+    r = D - (hop // 2 - window // 2 + window)
+    return 0 if r < 0 else min(nf, r // hop + 1)
+
+
 def stream_spectrum_complete(D: int, hop: int, n_fft: int, total: int) -> int:
     """The completion rule of a stream's spectrum (above sbv2_stream_next_spectrum): the rule of stream_pitch_complete with n_fft // 2 in the
     place of tau_max."""
@@ -1620,12 +1656,19 @@ class StreamHandle:
     spectrum (a Spectrum: n_fft, hop, n_mels, f_min, f_max at the stream's delivered rate): the spectrum of the delivered samples is computed on
     the device chunk by chunk (sbv2_stream_begin_request_spectrum): n_spec frames of n_bands in all, next_spectrum() hands out the ones the
     pieces taken so far completed, with the bits of debug_spectrum over the whole delivered signal.  A single utterance runs as the request
-    stream with gaps=[0]."""
+    stream with gaps=[0].
+    formants (a FormantContour at the stream's delivered rate; with or without a spectrum and pitch): the formant contour of the delivered
+    samples is computed on the device chunk by chunk (sbv2_stream_begin_request_formant_contour): n_formant_frames frames in all,
+    next_formants() hands out the ones the pieces taken so far completed, with the bits of debug_formant_contour over the whole delivered
+    signal.  A single utterance runs as the request stream with gaps=[0]."""
 
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
                  level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, track=None,
                  voice: "StreamVoice | None" = None, token_pitch=None, leveler: "StreamLeveler | None" = None,
-                 spectrum: "Spectrum | None" = None, **kw):
+                 spectrum: "Spectrum | None" = None, formants: "FormantContour | None" = None, **kw):
+        if formants is not None and not hasattr(_lib.lib(), "sbv2_stream_begin_request_formant_contour"):
+            raise Sbv2Error("this library has no sbv2_stream_begin_request_formant_contour: a stream cannot carry a formant contour (it is never "
+                            "served without)")
         if spectrum is not None and not hasattr(_lib.lib(), "sbv2_stream_begin_request_spectrum"):
             raise Sbv2Error("this library has no sbv2_stream_begin_request_spectrum: a stream cannot carry a spectrum (it is never served without)")
         if leveler is not None and not hasattr(_lib.lib(), "sbv2_stream_begin_request_leveler"):
@@ -1648,7 +1691,9 @@ class StreamHandle:
         self.pitch, self.n_pitch, self._pitch_buf = pitch, 0, None
         self.voice, self.leveler = voice, leveler
         self.spectrum, self.n_spec, self.n_bands, self._spec_buf = spectrum, 0, 0, None
-        if (self.levels or self.env_hop or pitch is not None or voice is not None or leveler is not None or spectrum is not None) and not self.request:
+        self.formants, self.n_formant_frames, self._formant_buf = formants, 0, None
+        if (self.levels or self.env_hop or pitch is not None or voice is not None or leveler is not None or spectrum is not None or
+                formants is not None) and not self.request:
             if gaps is not None:
                 raise Sbv2Error("gaps= belongs to a stream over a list of utterances")
             utt, gaps, self.request = [utt], [0], True
@@ -1670,8 +1715,8 @@ class StreamHandle:
             rq = _lib.Sbv2StreamRequest(gp, C.pointer(fmt.c) if fmt is not None else None, C.pointer(level.c) if level is not None else None,
                                         int(self.flac), 0)
             opts = C.byref(self.b.opts) if self.b.opts is not None else None
-            if self.b.assist is not None or voice is not None or leveler is not None or spectrum is not None:
-                # an assisted row, a shifted voice, a leveler or a spectrum: the one entry that takes them, with the levels and the pitch the stream may carry (NULL: without)
+            if self.b.assist is not None or voice is not None or leveler is not None or spectrum is not None or formants is not None:
+                # an assisted row, a shifted voice, a leveler, a spectrum or a formant contour: the one entry that takes them, with the levels and the pitch the stream may carry (NULL: without)
                 on = self.levels or self.env_hop
                 lv = _lib.Sbv2StreamLevels(int(self.levels), self.env_hop, (C.c_int32 * 2)(0, 0)) if on or pitch is not None else None
                 sp = None
@@ -1682,12 +1727,23 @@ class StreamHandle:
                         C.byref(lv) if lv is not None else None, C.byref(sp) if sp is not None else None)
                 tail = (C.byref(self.h), C.byref(tot), C.byref(nt), C.byref(ne), C.byref(nq))
                 cv, _keep = voice.c_struct(len(utt)) if voice is not None else (None, None)
+                i32 = lambda v: v if -2 ** 31 <= v < 2 ** 31 else -1
+                cs = None
                 if spectrum is not None:
-                    i32 = lambda v: v if -2 ** 31 <= v < 2 ** 31 else -1
                     rate = fmt.sample_rate if fmt is not None else 44100
                     cs = _lib.Sbv2StreamSpectrum(i32(spectrum.n_fft), i32(spectrum.hop), i32(spectrum.n_mels), 0, spectrum.f_min,
                                                  rate / 2.0 if spectrum.f_max is None else spectrum.f_max)
-                    ns, nb = C.c_int64(), C.c_int32()
+                ns, nb = C.c_int64(), C.c_int32()
+                if formants is not None:
+                    cf = _lib.Sbv2StreamFormantContour(i32(formants.hop), i32(formants.window), i32(formants.order), i32(formants.n_formants),
+                                                       formants.f_lo, formants.f_hi, formants.bw_max, 0)
+                    nff = C.c_int64()
+                    check(l.sbv2_stream_begin_request_formant_contour(*head, C.byref(cv) if cv is not None else None,
+                                                                      C.byref(leveler.c) if leveler is not None else None,
+                                                                      C.byref(cs) if cs is not None else None, C.byref(cf), *tail, C.byref(ns),
+                                                                      C.byref(nb), C.byref(nff)))
+                    self.n_spec, self.n_bands, self.n_formant_frames = ns.value, nb.value, nff.value
+                elif spectrum is not None:
                     check(l.sbv2_stream_begin_request_spectrum(*head, C.byref(cv) if cv is not None else None,
                                                                C.byref(leveler.c) if leveler is not None else None, C.byref(cs), *tail, C.byref(ns),
                                                                C.byref(nb)))
@@ -1810,6 +1866,20 @@ class StreamHandle:
         part = _lib.Sbv2StreamSpectrumPart(self.n_spec * self.n_bands, self._spec_buf.ctypes.data_as(f32p), 0, 0, 0)
         check(_lib.lib().sbv2_stream_next_spectrum(self.h, C.byref(part)))
         return int(part.first), self._spec_buf[:part.n * self.n_bands].reshape(part.n, self.n_bands).copy(), int(part.delivered)
+
+    def next_formants(self):
+        """(first, f_hz, bw_hz, status, delivered): the frames of the formant contour that the pieces taken since the previous call completed
+        (sbv2_stream_next_formant_contour; host only; the rule: stream_formants_complete).  f_hz / bw_hz [n][n_formants] float64 and status
+        [n] int32, the frames [first, first + n).  Refused on a stream begun without formants=."""
+        k = self.formants.n_formants if self.formants is not None else 1
+        if self._formant_buf is None:   # (sized for the whole stream once)
+            nf = max(self.n_formant_frames, 1)
+            self._formant_buf = np.zeros(nf * k, np.float64), np.zeros(nf * k, np.float64), np.zeros(nf, np.int32)
+        f, b, st = self._formant_buf
+        part = _lib.Sbv2StreamFormantPart(self.n_formant_frames, _f64p(f), _f64p(b), st.ctypes.data_as(C.POINTER(C.c_int32)), 0, 0, 0)
+        check(_lib.lib().sbv2_stream_next_formant_contour(self.h, C.byref(part)))
+        n = int(part.n)
+        return int(part.first), f[:n * k].reshape(n, k).copy(), b[:n * k].reshape(n, k).copy(), st[:n].copy(), int(part.delivered)
 
     def marks(self):
         """(start, end): the spans of the utterance's tokens in delivered samples of this stream (sbv2_stream_marks; host only, complete from

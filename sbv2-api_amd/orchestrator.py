@@ -898,7 +898,7 @@ class SynthesisStream:
     the pieces run out, when one fails, by close(), and when the object is dropped, iterated or not: the replays of a stream are already
     enqueued when this object is returned, so its end cannot hang on a generator's `finally`, which never runs for a generator nobody started."""
 
-    def __init__(self, st, head, to_bytes, marks=None, tail=None, levels=None, pitch=None, spectrum=None):
+    def __init__(self, st, head, to_bytes, marks=None, tail=None, levels=None, pitch=None, spectrum=None, formants=None):
         self._st, self._head, self._to_bytes, self._tail = st, head, to_bytes, tail   # tail: bytes that follow the last chunk (a pad byte)
         self.marks = marks   # token_marks of the utterance at the stream's rate: complete before the first piece
         self.level_stats = None   # a level stream's (deepest reduction in dB, max |x|), once its last piece has been handed out
@@ -923,6 +923,13 @@ class SynthesisStream:
             self.marks["spectrum"] = {"n_fft": int(spectrum.n_fft), "hop": int(spectrum.hop), "n_bands": int(spectrum.n_bands()),
                                       "n_frames": int(spectrum.n_frames(self.total_samples)), "f_min": float(spectrum.f_min),
                                       "f_max": rate / 2.0 if spectrum.f_max is None else float(spectrum.f_max)}
+
+        # formants (a model.FormantContour, with levels): the stream was begun with a formant contour; take_marks() hands out the frames the
+        # pieces so far completed.  As with the spectrum, `.marks` names what the contour holds and never the frames themselves
+        self._formants, self._new_formants, self._formants_first = formants, [], 0
+        if formants is not None:
+            self.marks["formants"] = {"hop": int(formants.hop), "order": int(formants.order), "n_formants": int(formants.n_formants),
+                                      "n_frames": -(-self.total_samples // int(formants.hop))}
 
     def _collect(self):
         """The levels the handle has completed since the last look -> `.marks` and the lists take_marks() hands out next."""
@@ -949,11 +956,14 @@ class SynthesisStream:
                 lst.extend(float(v) for v in ap)
         if self._spectrum is not None:
             self._new_spec.append(self._st.next_spectrum()[1])
+        if self._formants is not None:
+            self._new_formants.append(self._st.next_formants()[1:3])
 
     def take_marks(self) -> dict:
         """JSON-ready: the levels that the pieces handed out so far have completed and that no earlier call returned.  {"delivered": samples out
         so far, "tokens": [{"token": its index in .marks["tokens"], "level_dbfs", "peak"}, ...], "envelope": {"first", "hop", "level_dbfs" [n],
-        "peak" [n]} (with an envelope), "pitch": {"first", "hop", "f0_hz" [n] (None = unvoiced), "aperiodicity" [n]} (with pitch), "spectrum": {"first", "shape": [n, n_bands], "db": spectrum_db's} (with a spectrum)}.  A token is
+        "peak" [n]} (with an envelope), "pitch": {"first", "hop", "f0_hz" [n] (None = unvoiced), "aperiodicity" [n]} (with pitch), "spectrum": {"first", "shape": [n, n_bands], "db": spectrum_db's} (with a spectrum),
+        "formants": {"first", "f_hz" [n][n_formants], "bw_hz" likewise (0 = the frame has no such formant)} (with formants)}.  A token is
         complete once its last sample has been delivered, an envelope frame likewise, a pitch frame once its window has been
         (model.stream_pitch_complete)."""
         if self._levels is None:
@@ -971,6 +981,11 @@ class SynthesisStream:
             d["spectrum"] = {"first": self._spec_first, **spectrum_db(power)}
             self._spec_first += len(power)
             self._new_spec = []
+        if self._formants is not None:
+            rows = lambda q: [[float(v) for v in row] for part in self._new_formants for row in part[q]]
+            d["formants"] = {"first": self._formants_first, "f_hz": rows(0), "bw_hz": rows(1)}
+            self._formants_first += len(d["formants"]["f_hz"])
+            self._new_formants = []
         self._new_tokens, self._new_env, self._new_pitch = [], ([], []), ([], [])
         return d
 
@@ -1026,7 +1041,8 @@ class SynthesisStream:
 
 
 def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, speaker_id=0, options=None, noise_seed=None,
-                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False, levels=False, pitch=False, spectrum=False):
+                           noise_scale=NOISE_SCALE, noise_scale_w=NOISE_SCALE_W, chunk_frames=256, split=False, levels=False, pitch=False, spectrum=False,
+                           formants=False):
     """easy_synthesize delivered while it is synthesised: an iterator (SynthesisStream; close() it when it is abandoned early) over the pieces
     of the request's container.  The forward (DeBERTa / text / flow) runs once over the whole request, then the decoder runs chunk by chunk
     (model.StreamHandle).
@@ -1064,6 +1080,10 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     the spectrum of the delivered samples is computed on the device chunk by chunk (model.StreamHandle(spectrum=...)): `.marks` gains
     "spectrum": {n_fft, hop, n_bands, n_frames, f_min, f_max} and take_marks() pieces a "spectrum" block.  Without spectrum=True the spectrum_*
     options are refused as before.
+    formants=True (needs levels=True and options.formants; the formants_* options as formants_options reads them at the stream's rate): the
+    formant contour of the delivered samples is computed on the device chunk by chunk (model.StreamHandle(formants=...)): `.marks` gains
+    "formants": {hop, order, n_formants, n_frames} and take_marks() pieces a "formants" block {first, f_hz, bw_hz}.  The tokens gain no f1_hz /
+    f2_hz on a stream.  Without formants=True the formants* options are refused as before.
     options.assist: every row carries the assist (sbv2_stream_begin_request_assist); with split=False the utterance then runs as a request of
     one row without a gap, the only stream kind that takes one."""
     options = options or SynthesizeOptions()
@@ -1071,7 +1091,13 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     refuse_token_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_dynamics(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
-    refuse_formants(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    if formants:
+        if not levels:
+            raise FormantsError("formants=True on a stream comes with its speech marks: pass levels=True as well")
+        if getattr(options, "formants", None) is None:
+            raise FormantsError("formants=True needs options.formants (how many, 1 to 8)")
+    else:
+        refuse_formants(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if spectrum:
         if not levels:
             raise SpectrumError("spectrum=True on a stream comes with its speech marks: pass levels=True as well")
@@ -1119,6 +1145,13 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
             raise model.Sbv2Error("spectrum=True on a stream needs a StreamHandle that takes spectrum=: this one does not, and the request is not "
                                   "served without its spectrum")
         kw.update(spectrum=spec)
+    fc = formants_options(options, fmt.sample_rate) if formants else None   # (a bad field is refused before any GPU work)
+    if fc is not None:
+        import inspect
+        if "formants" not in inspect.signature(model.StreamHandle.__init__).parameters:
+            raise model.Sbv2Error("formants=True on a stream needs a StreamHandle that takes formants=: this one does not, and the request is not "
+                                  "served without its formant contour")
+        kw.update(formants=fc)
     if leveler is not None:
         import inspect
         if "leveler" not in inspect.signature(model.StreamHandle.__init__).parameters:
@@ -1152,8 +1185,9 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
         raise
     lv = (fmt, kw["env_hop"], st.total_samples) if levels else None
     if flac:
-        return SynthesisStream(st, None, lambda c: c, marks, levels=lv, pitch=contour, spectrum=spec)
+        return SynthesisStream(st, None, lambda c: c, marks, levels=lv, pitch=contour, spectrum=spec, formants=fc)
     dtype = {"s16": "<i2", "f32": "<f4"}.get(fmt.encoding, "u1")
     pad = b"\0" if fmt.encoding in G711_TAGS and st.total_samples & 1 else None
     return SynthesisStream(st, wav_stream_header(fmt.sample_rate, fmt.encoding, st.total_samples),
-                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad, levels=lv, pitch=contour, spectrum=spec)
+                           lambda c: np.ascontiguousarray(c, dtype).tobytes(), marks, tail=pad, levels=lv, pitch=contour, spectrum=spec,
+                           formants=fc)

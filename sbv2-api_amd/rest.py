@@ -61,6 +61,10 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     formants_hz = 100 (frames per second), formants_max_hz (null: min(5500, sample_rate / 2 - 50)), formants_order (null: 2 +
                     sample_rate // 1000, rounded up to even), formants_window (null: 25 ms).  A bad value answers 400; so does any of the five
                     fields on every other route, the stream routes included, naming /synthesize_marks.
+  formants_stream = false (new; /synthesize_stream_marks only, with formants and its fields): the first line gains "formants": {"hop",
+                    "order", "n_formants", "n_frames"} and every later line "formants": {"first", "f_hz": [[F1, ...] per frame], "bw_hz": likewise},
+                    the frames that piece completed.  The tokens gain no f1_hz / f2_hz.  Without it the stream routes keep answering 400 for
+                    formants.
   spectrum_mels = null (new; /synthesize_marks only, batched or not): the marks carry "spectrum": {"n_fft", "hop", "n_bands", "f_min", "f_max",
                     "shape": [n_frames, n_bands], "db": base64 of little-endian float32, 10 log10(max(power, 1e-10))}, the Slaney mel bands (0:
                     the spectrum_fft // 2 + 1 bins) of the delivered samples, reduced on the device.  spectrum_fft (null: the multiple of 32
@@ -159,6 +163,8 @@ class _MarksLines:
             self._first["pitch"] = {"hop": hop, "n_frames": -(-int(total_samples) // hop)}
         if "spectrum" in pieces.marks:   # (a stream begun with a spectrum: what its frames will hold)
             self._first["spectrum"] = dict(pieces.marks["spectrum"])
+        if "formants" in pieces.marks:   # (a stream begun with a formant contour: likewise)
+            self._first["formants"] = dict(pieces.marks["formants"])
 
     def __iter__(self):
         return self
@@ -242,6 +248,7 @@ def make_app(holder, batching=None):
     class SynthesizeStreamMarksRequest(SynthesizeStreamRequest):
         envelope_hz: Optional[int] = None   # frames per second of the level envelope; null = none
         spectrum_stream: bool = False       # new: with spectrum_mels, every piece carries the spectrum frames it completed; without it spectrum_mels stays a 400
+        formants_stream: bool = False       # new: with formants, every piece carries the formant frames it completed; without it formants stays a 400
 
     class _ClosingStream(StreamingResponse):
         """A StreamingResponse that closes its _HeldPieces when the response is over, however it ends: sent to the end, cut by the client's
@@ -355,7 +362,7 @@ def make_app(holder, batching=None):
                            "tokens": [[t["line"], t["index"], t["phone"], t["start"], t["end"]] for t in marks["tokens"]],
                            "words": [[w["line"], w["index"], w["start"], w["end"]] for w in marks["words"]]}, separators=(",", ":"))
 
-    def refuse_stream_voice(req, spectrum=False):
+    def refuse_stream_voice(req, spectrum=False, formants=False):
         """A 400 for pitch_scale / intonation_scale / pitch_track / compressor on a stream route, and for an assist_text_weight outside [0, 1] (the
         request is at fault, nothing was tried), None at the defaults."""
         try:
@@ -365,7 +372,12 @@ def make_app(holder, batching=None):
             orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.check_assist(None, getattr(req, "assist_text_weight", 0.7))   # (a stream takes an assist; a bad weight is the request's fault)
-            orchestrator.refuse_formants(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            if not formants:
+                orchestrator.refuse_formants(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            elif req.formants is None:
+                raise orchestrator.FormantsError("formants_stream needs formants (how many, 1 to 8)")
+            else:
+                orchestrator.formants_options(req, req.sample_rate)   # (a bad field is the request's fault)
             if not spectrum:
                 orchestrator.refuse_spectrum(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             elif req.spectrum_mels is None:
@@ -399,7 +411,7 @@ def make_app(holder, batching=None):
 
     @app.post("/synthesize_stream_marks")
     def synthesize_stream_marks(req: SynthesizeStreamMarksRequest):
-        refused = refuse_stream_voice(req, spectrum=req.spectrum_stream)
+        refused = refuse_stream_voice(req, spectrum=req.spectrum_stream, formants=req.formants_stream)
         if refused is not None:
             return refused
         lock.acquire()                        # as /synthesize_stream: given back by _HeldPieces.close when the response is over
@@ -408,7 +420,8 @@ def make_app(holder, batching=None):
             pieces = holder.easy_synthesize_stream(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), levels=True,
                                                    **({"split": True} if req.split_sentences else {}),
                                                    **({"pitch": True} if req.pitch_hz is not None else {}),
-                                                   **({"spectrum": True} if req.spectrum_stream else {}))
+                                                   **({"spectrum": True} if req.spectrum_stream else {}),
+                                                   **({"formants": True} if req.formants_stream else {}))
             try:
                 lines = _MarksLines(pieces, "audio/flac" if req.encoding == "flac" else "audio/wav", pieces.marks["sample_rate"],
                                     pieces.total_samples)
