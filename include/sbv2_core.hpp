@@ -214,6 +214,26 @@ struct FormantContour {
     std::vector<int32_t> status;
     int64_t n_frames = 0;
 };
+// Not in the reference: tracking of that contour across frames (sbv2_formant_track in sbv2_hip.h states it).  ref_hz holds one reference per track
+// (1 to 5, strictly ascending); FormantContour::n_formants must equal their number.
+struct FormantTrack {
+    std::vector<double> ref_hz{500.0, 1500.0, 2500.0};
+    int candidates = 6;
+    double freq_cost = 1.0, bw_cost = 1.0, jump_cost = 4.0;
+    sbv2_formant_track c_struct() const {
+        sbv2_formant_track t{};
+        t.n_tracks = (int32_t)ref_hz.size(), t.candidates = candidates;
+        for (size_t i = 0; i < ref_hz.size() && i < 5; ++i) t.ref_hz[i] = ref_hz[i];
+        t.freq_cost = freq_cost, t.bw_cost = bw_cost, t.jump_cost = jump_cost;
+        return t;
+    }
+};
+// sbv2_pipeline_fetch_request_formant_track with owned arrays: the call below with the contour tracked (ft == nullptr: exactly the call below).
+inline void fetch_request_formant_track(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,
+                                        const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                        const sbv2_formant* formant, FormantContour& fc, const FormantTrack* ft, void* dst, int64_t capacity_bytes,
+                                        int64_t* out_count, double* stats = nullptr, double* dyn_stats = nullptr, sbv2_marks* marks = nullptr,
+                                        sbv2_pitch* pitch = nullptr, sbv2_spectrum* spectrum = nullptr);
 // sbv2_pipeline_fetch_request_formant_contour with owned arrays: sbv2_pipeline_fetch_request_formant (no spectrum) with the formant contour of
 // the delivered signal behind it.
 inline void fetch_request_formant_contour(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,
@@ -221,6 +241,14 @@ inline void fetch_request_formant_contour(sbv2_pipeline* p, int64_t ticket, cons
                                           const sbv2_formant* formant, FormantContour& fc, void* dst, int64_t capacity_bytes, int64_t* out_count,
                                           double* stats = nullptr, double* dyn_stats = nullptr, sbv2_marks* marks = nullptr,
                                           sbv2_pitch* pitch = nullptr, sbv2_spectrum* spectrum = nullptr) {
+    fetch_request_formant_track(p, ticket, req, voice, track, dynamics, token_pitch, formant, fc, nullptr, dst, capacity_bytes, out_count, stats, dyn_stats,
+                                marks, pitch, spectrum);
+}
+inline void fetch_request_formant_track(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,
+                                        const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                        const sbv2_formant* formant, FormantContour& fc, const FormantTrack* ft, void* dst, int64_t capacity_bytes,
+                                        int64_t* out_count, double* stats, double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch,
+                                        sbv2_spectrum* spectrum) {
     const int rate = req.fmt ? req.fmt->sample_rate : 44100;
     const int64_t out_len = sbv2_pcm_format_length(req.fmt, req.joined_len);
     if (out_len < 0) throw Error(sbv2_last_error());
@@ -233,8 +261,10 @@ inline void fetch_request_formant_contour(sbv2_pipeline* p, int64_t ticket, cons
     fc.status.assign(nf + 1, 0);
     c.capacity = (int64_t)nf;
     c.f_hz = fc.f_hz.data(), c.bw_hz = fc.bw_hz.data(), c.status = fc.status.data();
-    check(sbv2_pipeline_fetch_request_formant_contour(p, ticket, &req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count,
-                                                      stats, dyn_stats, marks, pitch, spectrum, &c));
+    sbv2_formant_track t{};
+    if (ft) t = ft->c_struct();
+    check(sbv2_pipeline_fetch_request_formant_track(p, ticket, &req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count, stats,
+                                                    dyn_stats, marks, pitch, spectrum, &c, ft ? &t : nullptr));
     fc.n_frames = c.n_frames;
     fc.f_hz.resize(nf * fc.n_formants), fc.bw_hz.resize(nf * fc.n_formants), fc.status.resize(nf);
 }

@@ -758,7 +758,7 @@ int sbv2_debug_spectrum(int device, const void* x, int encoding, int64_t n, int3
  *   measured against a longdouble restatement, and against numpy's own roots, is in DESIGN.md (8y).
  * On a stream the same contour comes frame by frame: sbv2_stream_begin_request_formant_contour / sbv2_stream_next_formant_contour below.
  * Not built: the contour on sbv2_node_*, Burg's method, resampling to 2 f_hi before the analysis (the caller picks
- *   the delivered rate; 16 kHz is the phonetician's), tracking the formants across frames. */
+ *   the delivered rate; 16 kHz is the phonetician's).  Tracking the formants across frames is opt-in: sbv2_formant_track below. */
 typedef struct sbv2_formant_contour {
     int32_t hop, window, order, n_formants; /* in; window / order 0: the defaults */
     double f_lo, f_hi, bw_max;              /* in: Hz; 0: the defaults */
@@ -790,6 +790,70 @@ int sbv2_formant_contour_defaults(int32_t sample_rate, sbv2_formant_contour* con
  * [n_frames] as well. */
 int sbv2_debug_formant_contour(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_formant_contour* contour, double* lpc,
                                int32_t* status);
+
+/* ---- new: the formant contour TRACKED across frames.  sbv2_formant_contour decides every frame on its own: "the first n_formants kept roots by
+ * ascending F".  One spurious root (a wide low root under F1, a root that splits F2) therefore shifts a whole frame by a slot, and F2 arrives as
+ * F1.  Here every frame keeps K candidates and ONE path is chosen through them, as sbv2_pitch_track does for the lag.  Everything after the
+ * contour's f64 values is int64 arithmetic, so the path does not depend on any order of evaluation and equals a sequential restatement bit
+ * for bit.
+ * Parameters (anything else, a NaN included, is refused; 0 never means "default"): n_tracks T in [1, 5]; candidates K in [T, 7] and K <= order /
+ *   2; ref_hz[0 .. T) strictly ascending within (0, sr / 2), a reference frequency per track (the entries from T on are not read); freq_cost,
+ *   bw_cost and jump_cost in [0, 16]; reserved = 0.  The host forms Wf, Wb, Wj = llrint(value * 65536) and Rq_t = max(llrint(ref_hz[t]), 1)
+ *   once.  Usual values at 16 kHz for a vowel-like voice: T = 3, K = 6, ref_hz = 500, 1500, 2500, freq_cost 1.0, bw_cost 1.0, jump_cost 4.0:
+ *   on the experiment of DESIGN.md (8za: the candidates of a 700 / 1200 / 2600 Hz vowel with a wide 250 Hz root entering in bursts) the plain
+ *   first-3 selection is a slot off on 12 of 34 inner frames and the tracked one on 0.  That table is constructed: nearly any positive costs
+ *   win on it, so the counts show what the definition repairs and do not single out these values.
+ * Candidates.  The stage of sbv2_formant_contour runs unchanged with n_formants = K.  Candidate i of a frame is its i-th delivered (F, B); the
+ *   frame has m = the number of entries with F > 0.  Fq_i = max(llrint(F_i), 1) and Bq_i = llrint(min(B_i, 2^24)) (a bandwidth above 2^24 Hz,
+ *   which only a root with |z| < 1e-300 has, counts as 2^24).
+ * States of a frame.  The strictly increasing T-tuples (c_0 < ... < c_{T-1}) over 0 .. m - 1, in lexicographic order: C(m, T) of them, 35 at
+ *   most (C(7, 3) = C(7, 4)).  A frame with m < T is a CUT: it has no state, and its delivered values are its first m candidates followed by
+ *   zeros, which is what sbv2_formant_contour gives with n_formants = T.  Cuts separate runs, and the runs' paths are independent.
+ * Costs (int64, integer division).  local(k) = sum_t ((Wf |Fq_{c_t} - Rq_t|) / Rq_t + (Wb Bq_{c_t}) / Fq_{c_t});
+ *   trans(j -> k) = sum_t (Wj |Fq_{k,t} - Fq_{j,t}|) / max(Fq_{k,t}, Fq_{j,t}), Fq_{k,t} the track-t candidate of state k of the frame and
+ *   Fq_{j,t} that of state j of the frame before.  The first frame of a run takes cost(f, k) = local(k); then cost(f, k) = local(k) + min_j
+ *   (cost(f - 1, j) + trans(j -> k)), bp(f, k) = the smallest j that attains the minimum.  The last frame of a run takes the smallest k that
+ *   attains min cost; the path is the backtrace.
+ * Range.  One frame adds at most P = T (2^20 2^15 + 2^20 2^24 + 2^20) < 2^47 and the costs of one frame lie within P of each other.  A sum over
+ *   n_frames < 2^30 frames could pass 2^63, so the library does not hold the sums: it holds cost(f, k) minus the cost of state 0 of a frame at
+ *   most 16 back (a constant per frame moves no minimum), which stays within 17 P < 2^52 whatever n_frames is.  A restatement in unbounded
+ *   integers gives the same path.
+ * Result.  f_hz / bw_hz [n_frames][T]: the f64 values of the chosen candidates, unchanged; state [n_frames] (the hook's): the index of the
+ *   frame's state, -1 on a cut.  status is sbv2_formant_contour's, unchanged.
+ * Not built: tracking on streams (a best path needs the future) and on sbv2_node_*, smoothing of the values, absent or merged tracks inside a
+ *   run (a frame either fills all T tracks or is a cut), Burg's method. */
+typedef struct sbv2_formant_track {
+    int32_t n_tracks;     /* T in [1, 5]: the columns delivered; sbv2_formant_contour.n_formants must equal it */
+    int32_t candidates;   /* K in [T, min(7, order / 2)]: the kept roots per frame the path chooses among */
+    double ref_hz[5];     /* the first T: strictly ascending within (0, sr / 2) */
+    double freq_cost;     /* [0, 16]: times the relative distance of a candidate from its track's reference */
+    double bw_cost;       /* [0, 16]: times the candidate's bandwidth over its frequency */
+    double jump_cost;     /* [0, 16]: times the relative change of a track's frequency between two frames */
+    int32_t reserved;     /* must be 0 */
+} sbv2_formant_track;
+/* sbv2_pipeline_fetch_request_formant_contour with the contour tracked: two more launches (k_ftrack_runs, k_ftrack_path) behind k_formant_lpc,
+ * before the fetch's only synchronisation.  track == NULL is exactly that call: nothing new is launched or allocated.  With a track, contour
+ * must be given, contour->n_formants must equal n_tracks and f_hz / bw_hz hold n_tracks columns; the audio bytes, out_count, stats, marks,
+ * pitch, spectrum and the contour's status are those of the call without, and two fetches of one ticket give identical bits.  Refused with
+ * nothing written, besides everything that call refuses: a track without a contour, parameters outside the ranges above (at the format's rate
+ * and the contour's order, its default included), n_formants != n_tracks, a non-zero reserved. */
+int sbv2_pipeline_fetch_request_formant_track(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                              const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                              const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                              double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                              sbv2_formant_contour* contour, const sbv2_formant_track* formant_track);
+/* Host only: the checks of *track beside *contour at sample_rate that the fetch makes (capacity and the arrays are not looked at); nothing is
+ * written. */
+int sbv2_formant_track_check(int32_t sample_rate, const sbv2_formant_contour* contour, const sbv2_formant_track* track);
+/* Test hook: the tracker on host samples x[n] (as sbv2_debug_formant_contour): contour (n_formants = n_tracks) receives the TRACKED f_hz /
+ * bw_hz and the stage's status; cand_f_out / cand_b_out [n_frames][K] (the stage's candidates) and state_out [n_frames] may each be NULL.
+ * With cand_f_in / cand_b_in [nf_in][K] the stage is skipped and the path alone is found on the caller's table: x may be NULL, contour's
+ * parameters are checked as ever, its f_hz / bw_hz receive nf_in rows (capacity >= nf_in) and its status is not written.  Refused besides
+ * everything sbv2_debug_formant_contour and the fetch refuse: a table with a negative F or B, F above 32768 or B above 2^24, or a row whose
+ * positive F are not first and in non-descending order. */
+int sbv2_debug_formant_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_formant_contour* contour,
+                             const sbv2_formant_track* track, const double* cand_f_in, const double* cand_b_in, int64_t nf_in, double* cand_f_out,
+                             double* cand_b_out, int32_t* state_out);
 
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
@@ -1343,7 +1407,7 @@ int sbv2_debug_stream_spectrum(int device, const void* x, int encoding, int64_t 
  * Refused before the handles are looked at, with nothing written: a non-zero reserved and everything sbv2_formant_contour's parameters
  *   refuse at the format's rate; besides, everything sbv2_stream_begin_request_spectrum refuses.  2^30 frames or more are refused.
  * Not built: per-token f1_hz / f2_hz on streams; the contour on sbv2_node_*; on the plain sbv2_stream_begin* entries (a request stream of one
- *   row serves them); tracking the formants across frames. */
+ *   row serves them); tracking the formants across frames (sbv2_formant_track: the whole-signal fetch only). */
 typedef struct sbv2_stream_formant_contour {
     int32_t hop, window, order, n_formants; /* as sbv2_formant_contour; window / order 0: the defaults */
     double f_lo, f_hi, bw_max;              /* Hz; 0: the defaults */
@@ -1358,6 +1422,19 @@ int sbv2_stream_begin_request_formant_contour(sbv2_bert* bert, sbv2_vits* vits, 
                                               const sbv2_stream_formant_contour* contour /* may be NULL */, sbv2_stream** out, int64_t* total_samples,
                                               int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch, int64_t* n_spec, int32_t* n_bands,
                                               int64_t* n_formant_frames);
+/* The same entry with a place for a sbv2_formant_track.  A stream does not track its contour: the best path through a run of frames needs the
+ * frames behind it.  formant_track == NULL is exactly the call above; anything else is refused before anything is looked at, with nothing
+ * written, and the message names the whole-signal route, sbv2_pipeline_fetch_request_formant_track. */
+int sbv2_stream_begin_request_formant_track(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts /* may be NULL */,
+                                            const sbv2_assist* assist /* may be NULL */, const int64_t* token_ids, const int64_t* s_lens,
+                                            const int64_t* word2ph, int64_t chunk_frames, const sbv2_stream_request* rq,
+                                            const sbv2_stream_levels* lv /* may be NULL */, const sbv2_stream_pitch* sp /* may be NULL */,
+                                            const sbv2_stream_voice* voice /* may be NULL */, const sbv2_stream_leveler* leveler /* may be NULL */,
+                                            const sbv2_stream_spectrum* spectrum /* may be NULL */,
+                                            const sbv2_stream_formant_contour* contour /* may be NULL */,
+                                            const sbv2_formant_track* formant_track /* must be NULL */, sbv2_stream** out, int64_t* total_samples,
+                                            int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch, int64_t* n_spec, int32_t* n_bands,
+                                            int64_t* n_formant_frames);
 /* Host only: the frames [first, first + n) that became complete since the previous call, f_hz / bw_hz [n][n_formants] and status [n] (may be
  * NULL) as sbv2_formant_contour gives them, and delivered = D.  A capacity (in FRAMES) below n, or a NULL f_hz / bw_hz with frames pending, is
  * refused with nothing written and nothing lost: repeat with more room.  Not calling it loses nothing.  Refused on a stream begun without

@@ -153,6 +153,12 @@ class Sbv2StreamSpectrumPart(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("power", f32p), ("first", C.c_int64), ("n", C.c_int64), ("delivered", C.c_int64)]
 
 
+class Sbv2FormantTrack(C.Structure):
+    """struct sbv2_formant_track (include/sbv2_hip.h)."""
+    _fields_ = [("n_tracks", C.c_int32), ("candidates", C.c_int32), ("ref_hz", C.c_double * 5), ("freq_cost", C.c_double),
+                ("bw_cost", C.c_double), ("jump_cost", C.c_double), ("reserved", C.c_int32)]
+
+
 class Sbv2StreamFormantContour(C.Structure):
     """struct sbv2_stream_formant_contour (include/sbv2_hip.h)."""
     _fields_ = [("hop", C.c_int32), ("window", C.c_int32), ("order", C.c_int32), ("n_formants", C.c_int32), ("f_lo", C.c_double),
@@ -242,6 +248,15 @@ SYMBOLS = {
                                                               C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
                                                               C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch),
                                                               C.POINTER(Sbv2Spectrum), C.POINTER(Sbv2FormantContour)]),
+    "sbv2_pipeline_fetch_request_formant_track": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                            C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch),
+                                                            C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
+                                                            C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch),
+                                                            C.POINTER(Sbv2Spectrum), C.POINTER(Sbv2FormantContour), C.POINTER(Sbv2FormantTrack)]),
+    "sbv2_formant_track_check": (C.c_int, [C.c_int32, C.POINTER(Sbv2FormantContour), C.POINTER(Sbv2FormantTrack)]),
+    "sbv2_debug_formant_track": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2FormantContour),
+                                           C.POINTER(Sbv2FormantTrack), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64,
+                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "sbv2_formant_contour_defaults": (C.c_int, [C.c_int32, C.POINTER(Sbv2FormantContour)]),
     "sbv2_debug_formant_contour": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2FormantContour),
                                              C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
@@ -373,6 +388,12 @@ SYMBOLS = {
                                                             C.POINTER(Sbv2StreamLeveler), C.POINTER(Sbv2StreamSpectrum),
                                                             C.POINTER(Sbv2StreamFormantContour), C.POINTER(C.c_void_p), i64p, i64p, i64p, i64p, i64p,
                                                             C.POINTER(C.c_int32), i64p]),
+    "sbv2_stream_begin_request_formant_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Sbv2Batch), C.POINTER(Sbv2UttOptions),
+                                                          C.POINTER(Sbv2Assist), i64p, i64p, i64p, C.c_int64, C.POINTER(Sbv2StreamRequest),
+                                                          C.POINTER(Sbv2StreamLevels), C.POINTER(Sbv2StreamPitch), C.POINTER(Sbv2StreamVoice),
+                                                          C.POINTER(Sbv2StreamLeveler), C.POINTER(Sbv2StreamSpectrum),
+                                                          C.POINTER(Sbv2StreamFormantContour), C.POINTER(Sbv2FormantTrack), C.POINTER(C.c_void_p),
+                                                          i64p, i64p, i64p, i64p, i64p, C.POINTER(C.c_int32), i64p]),
     "sbv2_stream_next_formant_contour": (C.c_int, [C.c_void_p, C.POINTER(Sbv2StreamFormantPart)]),
     "sbv2_debug_stream_formant_contour": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, i64p, C.c_int, C.c_int32, C.POINTER(Sbv2FormantContour),
                                                     C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, i64p]),

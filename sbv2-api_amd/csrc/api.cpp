@@ -502,6 +502,14 @@ int sbv2_formant_contour_defaults(int32_t sample_rate, sbv2_formant_contour* con
     API_END
 }
 
+int sbv2_formant_track_check(int32_t sample_rate, const sbv2_formant_contour* contour, const sbv2_formant_track* track) {
+    API_BEGIN
+    SBV2_REQUIRE(contour && track, "bad arguments");
+    FormantContourSpec sp;
+    (void)check_formant_track(sample_rate, contour, track, &sp);
+    API_END
+}
+
 int sbv2_marks_spans(const int64_t* durations, int64_t n_tokens, int32_t hop, int64_t place, const sbv2_pcm_format* fmt, int64_t* start, int64_t* end) {
     API_BEGIN
     const PcmFmtSpec spec = pcm_format_spec(fmt);

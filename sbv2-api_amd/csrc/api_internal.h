@@ -9,6 +9,7 @@
 #include "../../include/sbv2_hip.h"
 #include "dynamics.h"
 #include "flac_encode.h"
+#include "formant_track.h"
 #include "formants.h"
 #include "limiter.h"
 #include "loudness.h"
@@ -43,6 +44,7 @@ struct OutputChain {
     Pitch pitch;       // ... and the pitch contour of the same samples (fetch_request_pitch only)
     Spectrum spectrum; // ... and their power spectrum or mel bands (fetch_request_spectrum only)
     Formants formants; // ... and their formant contour (fetch_request_formant_contour only)
+    FormantTrack formant_track;   // ... tracked across frames (fetch_request_formant_track only)
     Voice voice;       // pitch / intonation scale of the listed rows, in front of the formatter (fetch_request_voice only)
     Track track;       // the best path through the delivered contour's candidates (fetch_request_tracked only; the shifter has its own)
 };
@@ -84,6 +86,16 @@ VitsBatch to_batch(const sbv2_batch* b);
 inline FormantContourSpec check_formant_contour(int rate, const sbv2_formant_contour* q) {
     SBV2_REQUIRE(q->reserved == 0, "sbv2_formant_contour.reserved must be 0");
     return formant_contour_spec(rate, q->hop, q->window, q->order, q->n_formants, q->f_lo, q->f_hi, q->bw_max);
+}
+// THE parameter check of an sbv2_formant_track beside its contour at a rate (the fetch, sbv2_formant_track_check and the hook): the contour's
+// own check, n_formants = n_tracks, formant_track_spec (formant_track.h).  *sp: the stage's spec, n_formants widened to the candidates.
+inline FormantTrackSpec check_formant_track(int rate, const sbv2_formant_contour* q, const sbv2_formant_track* t, FormantContourSpec* sp) {
+    *sp = check_formant_contour(rate, q);
+    SBV2_REQUIRE(q->n_formants == t->n_tracks, "a tracked formant contour delivers n_tracks columns: sbv2_formant_contour.n_formants = " +
+                                                   std::to_string(q->n_formants) + " but sbv2_formant_track.n_tracks = " + std::to_string(t->n_tracks));
+    const FormantTrackSpec ts = formant_track_spec(t->n_tracks, t->candidates, t->ref_hz, t->freq_cost, t->bw_cost, t->jump_cost, t->reserved, rate, sp->order);
+    sp->n_formants = ts.K;
+    return ts;
 }
 // The per-row arrays of sbv2_utt_options onto the batch (NULL: nothing); throws for an option out of range, before any GPU work
 void apply_utt_options(sbv2::VitsBatch* v, const sbv2_utt_options* o);

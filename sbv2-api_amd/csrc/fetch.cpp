@@ -41,7 +41,8 @@ struct FetchArgs {
 // track (with pitch, or with a shifter that runs): both contours are tracked (Track, track.h) before they are used.
 // dynamics (with a loudness or limiter stage; ratio 1: nothing): the compressor runs on y first (dynamics.h); dyn_stats (may be NULL): its 3 doubles.
 // spectrum: the power spectrum or mel bands (spectrum.h) of the same delivered samples as marks and pitch, one more launch beside theirs.
-// contour: the formant contour (formants.h) of the same samples, one more launch again.
+// contour: the formant contour (formants.h) of the same samples, one more launch again.  formant_track (with contour): the stage keeps the
+// track's candidates per frame and the tracker (formant_track.h) chooses one path through them, two more launches.
 struct FetchStages {
     const int32_t* utts = nullptr;   // the rows of the one signal (with place[k] belonging to row utts[k]); NULL: no request, all of the run
     int n_utts = 0;
@@ -55,6 +56,7 @@ struct FetchStages {
     sbv2_pitch* pitch = nullptr;
     sbv2_spectrum* spectrum = nullptr;
     sbv2_formant_contour* contour = nullptr;
+    const sbv2_formant_track* formant_track = nullptr;
 };
 // ... and once everything about them that needs no run has been checked (check_stages).  Default: no stage.
 struct CheckedStages : FetchStages {
@@ -64,7 +66,8 @@ struct CheckedStages : FetchStages {
     TrackSpec ts;
     PitchSpec ps;
     SpectrumSpec ss;
-    FormantContourSpec fcs;
+    FormantContourSpec fcs;   // (with a formant track: n_formants = its candidates)
+    FormantTrackSpec fts;
     bool edit = false, scale = false, compress = false;   // a token is edited; the formants move; the compressor is not the identity
     bool shifts() const { return (voice && !vs.identity()) || edit || scale; }   // the shifter has something to do
 };
@@ -104,8 +107,10 @@ SpectrumSpec check_spectrum_static(const sbv2_spectrum* q, int rate) {
 }
 
 // The checks of sbv2_formant_contour that need no run: the parameters at the delivered rate (check_formant_contour), the arrays.
-FormantContourSpec check_contour_static(const sbv2_formant_contour* q, int rate) {
-    const FormantContourSpec sp = check_formant_contour(rate, q);
+FormantContourSpec check_contour_static(const sbv2_formant_contour* q, int rate, const sbv2_formant_track* t, FormantTrackSpec* ts) {
+    FormantContourSpec sp;
+    if (t) *ts = check_formant_track(rate, q, t, &sp);
+    else sp = check_formant_contour(rate, q);
     SBV2_REQUIRE(q->capacity >= 0, "negative sbv2_formant_contour capacity");
     SBV2_REQUIRE(q->f_hz && q->bw_hz, "sbv2_formant_contour.f_hz and bw_hz must not be NULL");
     return sp;
@@ -163,7 +168,8 @@ CheckedStages check_stages(const sbv2_fetch_request* req, const FetchStages& st)
     }
     if (st.pitch) cs.ps = check_pitch_static(st.pitch, pcm_format_spec(req->fmt).rate);
     if (st.spectrum) cs.ss = check_spectrum_static(st.spectrum, pcm_format_spec(req->fmt).rate);
-    if (st.contour) cs.fcs = check_contour_static(st.contour, pcm_format_spec(req->fmt).rate);
+    SBV2_REQUIRE(st.contour || !st.formant_track, "a formant track needs a formant contour to deliver its values in");
+    if (st.contour) cs.fcs = check_contour_static(st.contour, pcm_format_spec(req->fmt).rate, st.formant_track, &cs.fts);
     return cs;
 }
 
@@ -352,6 +358,7 @@ std::vector<int64_t> enqueue_fetch(const FetchArgs& a, const CheckedStages& cs, 
         if (pl.n_pitch > 0) c.pitch.run(dev, spec.encoding, pl.total, cs.ps, s, ts, cs.track ? &c.track : nullptr);
         if (pl.n_spec > 0) c.spectrum.run(dev, spec.encoding, pl.total, cs.ss, s);
         if (pl.n_fc > 0) c.formants.run(dev, spec.encoding, pl.total, cs.fcs, s);
+        if (pl.n_fc > 0 && cs.formant_track) c.formant_track.run(c.formants.f_device(), c.formants.bw_device(), pl.n_fc, cs.fts, s);
         if (a.sink == Sink::kFlac) {   // the signals stay in HBM; the encoder reads the stream sizes back, then exactly the encoded bytes cross PCIe
             std::vector<int64_t> offs(pl.outs.size());
             for (size_t i = 1; i < pl.outs.size(); ++i) offs[i] = offs[i - 1] + pl.outs[i - 1];
@@ -411,10 +418,11 @@ void deliver_fetch(const FetchArgs& a, const CheckedStages& cs, const FetchPlan&
         sp->n_bands = cs.ss.n_bands();
     }
     if (sbv2_formant_contour* fc = cs.contour) {
-        const size_t cnt = (size_t)(pl.n_fc * cs.fcs.n_formants);
+        const bool tracked = cs.formant_track != nullptr;   // (then the stage's own columns are the candidates)
+        const size_t cnt = (size_t)(pl.n_fc * (tracked ? cs.fts.T : cs.fcs.n_formants));
         if (pl.n_fc > 0) {
-            std::memcpy(fc->f_hz, c.formants.f_host(), sizeof(double) * cnt);
-            std::memcpy(fc->bw_hz, c.formants.bw_host(), sizeof(double) * cnt);
+            std::memcpy(fc->f_hz, tracked ? c.formant_track.f_host() : c.formants.f_host(), sizeof(double) * cnt);
+            std::memcpy(fc->bw_hz, tracked ? c.formant_track.bw_host() : c.formants.bw_host(), sizeof(double) * cnt);
             if (fc->status) std::memcpy(fc->status, c.formants.status_host(), sizeof(int32_t) * (size_t)pl.n_fc);
         }
         fc->n_frames = pl.n_fc;
@@ -481,24 +489,32 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
 }
 
 // The widest request fetch; each narrower symbol below is exactly this call with NULL for what it lacks.
-int sbv2_pipeline_fetch_request_formant_contour(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
-                                                const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
-                                                const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
-                                                double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
-                                                sbv2_formant_contour* contour) {
+int sbv2_pipeline_fetch_request_formant_track(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                              const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                              const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                              double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                              sbv2_formant_contour* contour, const sbv2_formant_track* formant_track) {
     API_BEGIN
     static const int32_t no_rows[1] = {0};   // (a request of no rows is still a request: one empty joined signal)
     static const int64_t no_place[1] = {0};
     const bool rows = req && req->n_utts > 0;   // (what is wrong with req is refused in its turn, by check_stages)
     const CheckedStages cs = check_stages(
         req, FetchStages{rows ? req->utts : no_rows, rows ? req->n_utts : 0, voice, track, dynamics, dyn_stats, token_pitch, formant, marks, pitch,
-                         spectrum, contour});
+                         spectrum, contour, formant_track});
     const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter}
                            : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr}
                                            : FetchGain();
     const Sink sink = req->flac ? Sink::kFlac : Sink::kPcm;
     fetch_formatted({p, ticket, req->fmt, gain, rows ? req->place : no_place, req->joined_len, sink, dst, capacity_bytes, out_count, stats}, cs);
     API_END
+}
+int sbv2_pipeline_fetch_request_formant_contour(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                                const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                                const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                                double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                                sbv2_formant_contour* contour) {
+    return sbv2_pipeline_fetch_request_formant_track(p, ticket, req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count, stats,
+                                                     dyn_stats, marks, pitch, spectrum, contour, nullptr);
 }
 int sbv2_pipeline_fetch_request_spectrum(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
                                          const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,

@@ -58,6 +58,9 @@ class Formants {
     const double* bw_host() const { return host_.as<double>() + nf_ * nk_; }
     const double* lpc_host() const { return host_.as<double>() + 2 * nf_ * nk_; }
     const int32_t* status_host() const { return reinterpret_cast<const int32_t*>(host_.as<double>() + 2 * nf_ * nk_ + nlpc_); }
+    // F and B of the last run on the device, [n_frames][n_formants] each: the tracker's candidates (formant_track.h)
+    const double* f_device() const { return dev_.as<double>(); }
+    const double* bw_device() const { return dev_.as<double>() + nf_ * nk_; }
 
   private:
     static constexpr size_t kMaxWindows = 8;

@@ -436,6 +436,24 @@ int sbv2_stream_begin_request_spectrum(sbv2_bert* bert, sbv2_vits* vits, const s
                                                      leveler, spectrum, nullptr, out, total_samples, n_tokens, n_env, n_pitch, n_spec, n_bands, nullptr);
 }
 
+// The entry below with a place for a formant track, which a stream cannot serve: NULL is exactly that entry, anything else is refused before
+// anything is looked at.
+int sbv2_stream_begin_request_formant_track(sbv2_bert* bert, sbv2_vits* vits, const sbv2_batch* batch, const sbv2_utt_options* opts,
+                                            const sbv2_assist* assist, const int64_t* token_ids, const int64_t* s_lens, const int64_t* word2ph,
+                                            int64_t chunk_frames, const sbv2_stream_request* rq, const sbv2_stream_levels* lv, const sbv2_stream_pitch* sp,
+                                            const sbv2_stream_voice* voice, const sbv2_stream_leveler* leveler, const sbv2_stream_spectrum* spectrum,
+                                            const sbv2_stream_formant_contour* contour, const sbv2_formant_track* formant_track, sbv2_stream** out,
+                                            int64_t* total_samples, int64_t* n_tokens, int64_t* n_env, int64_t* n_pitch, int64_t* n_spec,
+                                            int32_t* n_bands, int64_t* n_formant_frames) {
+    if (formant_track) {
+        set_last_error("a stream does not track its formant contour: the best path through a run of frames needs the frames behind it; fetch the whole "
+                       "signal with sbv2_pipeline_fetch_request_formant_track");
+        return 1;
+    }
+    return sbv2_stream_begin_request_formant_contour(bert, vits, batch, opts, assist, token_ids, s_lens, word2ph, chunk_frames, rq, lv, sp, voice, leveler,
+                                                     spectrum, contour, out, total_samples, n_tokens, n_env, n_pitch, n_spec, n_bands, n_formant_frames);
+}
+
 // ... and with the formant contour of the same delivered samples, fed by the same pushes (the contract above sbv2_stream_formant_contour,
 // include/sbv2_hip.h; StreamFormants, formants.hip).  contour NULL: exactly the call above.  Its fields are checked with the others', before
 // the handles are looked at, at the format's rate, by formant_contour_spec as sbv2_formant_contour's are.

@@ -2251,6 +2251,53 @@ int sbv2_debug_formant_contour(int device, const void* x, int encoding, int64_t 
     API_END
 }
 
+// The formant tracker (FormantTrack, formant_track.hip) on host samples, or on the caller's candidate table alone.  Everything is checked
+// before any device call; nothing is written when the call fails.
+int sbv2_debug_formant_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_formant_contour* contour,
+                             const sbv2_formant_track* track, const double* cand_f_in, const double* cand_b_in, int64_t nf_in, double* cand_f_out,
+                             double* cand_b_out, int32_t* state_out) {
+    API_BEGIN
+    SBV2_REQUIRE(contour && track, "bad arguments");
+    FormantContourSpec sp;
+    const FormantTrackSpec ts = check_formant_track(sample_rate, contour, track, &sp);
+    const bool table = cand_f_in || cand_b_in;
+    int64_t nf = nf_in;
+    if (table) {
+        SBV2_REQUIRE(nf_in >= 0 && nf_in < (1 << 30), "bad arguments");
+        formant_track_check_table(cand_f_in, cand_b_in, nf_in, ts.K);
+    } else {
+        SBV2_REQUIRE(pcm_encoding_known(encoding) && n >= 0 && (x || n == 0), "bad arguments");
+        nf = formant_frames(n, sp.hop);
+        SBV2_REQUIRE(nf < (1 << 30), "too many formant frames: " + std::to_string(nf) + " >= 2^30");
+    }
+    SBV2_REQUIRE(contour->capacity >= nf, "formant contour arrays too small: " + std::to_string(contour->capacity) + " < " + std::to_string(nf) + " frames");
+    SBV2_REQUIRE(contour->f_hz && contour->bw_hz, "sbv2_formant_contour.f_hz and bw_hz must not be NULL");
+    HIP_CHECK(hipSetDevice(device));
+    if (nf > 0) {
+        const size_t cand = sizeof(double) * (size_t)(nf * ts.K), cnt = sizeof(double) * (size_t)(nf * ts.T);
+        FormantTrack tk;
+        if (table) {
+            DevMem df(cand_f_in, cand), db(cand_b_in, cand);
+            tk.run(static_cast<const double*>(df.p), static_cast<const double*>(db.p), nf, ts, nullptr);
+            HIP_CHECK(hipStreamSynchronize(nullptr));
+        } else {
+            DevMem dx(x, (size_t)n * pcm_encoding_bytes(encoding));
+            Formants st;
+            st.run(dx.p, encoding, n, sp, nullptr);
+            tk.run(st.f_device(), st.bw_device(), nf, ts, nullptr);
+            HIP_CHECK(hipStreamSynchronize(nullptr));
+            if (cand_f_out) std::memcpy(cand_f_out, st.f_host(), cand);
+            if (cand_b_out) std::memcpy(cand_b_out, st.bw_host(), cand);
+            if (contour->status) std::memcpy(contour->status, st.status_host(), sizeof(int32_t) * (size_t)nf);
+        }
+        std::memcpy(contour->f_hz, tk.f_host(), cnt);
+        std::memcpy(contour->bw_hz, tk.bw_host(), cnt);
+        if (state_out) std::memcpy(state_out, tk.state_host(), sizeof(int32_t) * (size_t)nf);
+    }
+    contour->n_frames = nf;
+    API_END
+}
+
 // The tracker (Track, track.hip) on host samples, or on the caller's candidate table alone.  Everything is checked before any device call;
 // nothing is written when the call fails.
 int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, const sbv2_pitch_track* track,

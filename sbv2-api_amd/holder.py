@@ -168,7 +168,8 @@ class TTSModelHolder:
     def easy_synthesize_marks(self, ident: str, text, style_id: int = 0, speaker_id: int = 0, options=None, noise_seed=None):
         """easy_synthesize with speech marks: (bytes, marks) (orchestrator.easy_synthesize_marks).  The one unbatched route that takes
         options.spectrum_mels and its fields: the marks then carry "spectrum" (easy_synthesize and the streams refuse them); likewise
-        options.formants and its fields: the marks then carry "formants"."""
+        options.formants and its fields: the marks then carry "formants", tracked across frames with options.formants_track (this route and
+        easy_synthesize_batched(marks=True) alone: every stream refuses it)."""
         options = orchestrator.parsed_assist(options or orchestrator.SynthesizeOptions(), self.parse_text)   # (options.assist as a str: parsed here)
         self.find_and_load_model(ident)
         m = self._find(ident)

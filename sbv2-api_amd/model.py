@@ -744,6 +744,66 @@ def debug_formant_contour(x, sample_rate: int, contour: FormantContour, device: 
     return contour, lpc
 
 
+class FormantTrack:
+    """Tracking of a formant contour across frames (struct sbv2_formant_track, include/sbv2_hip.h states it): the stage keeps `candidates`
+    roots per frame and one best path assigns the FormantContour's n_formants tracks to them, run by run between the frames with too few
+    roots.  ref_hz: a reference frequency per track, strictly ascending; the three costs in [0, 16].  Checked by the library."""
+
+    def __init__(self, ref_hz=(500.0, 1500.0, 2500.0), candidates: int = 6, freq_cost: float = 1.0, bw_cost: float = 1.0, jump_cost: float = 4.0):
+        self.ref_hz, self.candidates = tuple(float(v) for v in ref_hz), int(candidates)
+        self.freq_cost, self.bw_cost, self.jump_cost = float(freq_cost), float(bw_cost), float(jump_cost)
+
+    @property
+    def c(self):
+        i32 = lambda v: v if -2 ** 31 <= v < 2 ** 31 else -1
+        ref = (C.c_double * 5)(*(self.ref_hz[:5] + (0.0,) * (5 - min(len(self.ref_hz), 5))))
+        return _lib.Sbv2FormantTrack(len(self.ref_hz), i32(self.candidates), ref, self.freq_cost, self.bw_cost, self.jump_cost, 0)
+
+    def __repr__(self):
+        return f"FormantTrack({self.ref_hz}, candidates={self.candidates}, costs=({self.freq_cost}, {self.bw_cost}, {self.jump_cost}))"
+
+
+def formant_track_check(sample_rate: int, contour: FormantContour, track: FormantTrack) -> None:
+    """The library's checks of a FormantTrack beside its FormantContour at sample_rate (sbv2_formant_track_check; host only)."""
+    fn = getattr(_lib.lib(), "sbv2_formant_track_check", None)
+    if fn is None:
+        raise Sbv2Error("this library has no sbv2_formant_track_check: it tracks no formant contour")
+    c, _ = contour.c_struct(0, int(sample_rate))
+    ct = track.c
+    check(fn(int(sample_rate), C.byref(c), C.byref(ct)))
+
+
+def debug_formant_track(x, sample_rate: int, contour: FormantContour, track: FormantTrack, device: int = 0, cand=None):
+    """Test hook: the formant tracker on host samples (sbv2_debug_formant_track; x as for debug_formant_contour, int16 or float32) -> (contour
+    with the tracked f_hz / bw_hz [n_frames][n_tracks] and status filled, cand_f, cand_b [n_frames][candidates], state [n_frames]).
+    cand = (cand_f, cand_b) [nf][candidates] float64: the stage is skipped and the path alone is found on that table (x is not read);
+    status stays zero."""
+    K = track.candidates
+    ct = track.c
+    if cand is not None:
+        cf, cb = (np.ascontiguousarray(v, np.float64) for v in cand)
+        if cf.shape != cb.shape or cf.ndim != 2 or cf.shape[1] != K:
+            raise Sbv2Error(f"the candidate tables must be two [n_frames][{K}] arrays")
+        nf = cf.shape[0]
+        c, arrays = contour.c_struct(nf * max(contour.hop, 1), int(sample_rate))
+        state = np.zeros(max(nf, 1), np.int32)
+        check(_lib.lib().sbv2_debug_formant_track(int(device), None, 0, 0, int(sample_rate), C.byref(c), C.byref(ct), _f64p(cf) if nf else _f64p(np.zeros(1)),
+                                                  _f64p(cb) if nf else _f64p(np.zeros(1)), nf, None, None, state.ctypes.data_as(C.POINTER(C.c_int32))))
+        contour.take(c, arrays, int(sample_rate))
+        return contour, cf, cb, state[:nf]
+    x = np.ascontiguousarray(x).reshape(-1)
+    if x.dtype not in (np.int16, np.float32):
+        raise Sbv2Error(f"the formant contour is taken of int16 or float32 samples, not {x.dtype}")
+    c, arrays = contour.c_struct(x.size, int(sample_rate))
+    nf = int(c.capacity)
+    cf, cb, state = np.zeros((nf, max(K, 1)), np.float64), np.zeros((nf, max(K, 1)), np.float64), np.zeros(max(nf, 1), np.int32)
+    check(_lib.lib().sbv2_debug_formant_track(int(device), x.ctypes.data_as(C.c_void_p) if x.size else None, int(x.dtype == np.int16), x.size,
+                                              int(sample_rate), C.byref(c), C.byref(ct), None, None, 0, _f64p(cf) if nf else None,
+                                              _f64p(cb) if nf else None, state.ctypes.data_as(C.POINTER(C.c_int32))))
+    contour.take(c, arrays, int(sample_rate))
+    return contour, cf, cb, state[:nf]
+
+
 class PitchTrack:
     """Octave-error repair of a pitch contour (struct sbv2_pitch_track: one best path through the frames' candidates, include/sbv2_hip.h states
     it).  cand_max in (0, 1]: a dip of c at or above it is no candidate; unvoiced_cost and switch_cost in [0, 4], jump_cost in [0, 16], all in
@@ -1495,7 +1555,8 @@ class Pipeline:
         return self._fetch_flac("sbv2_pipeline_fetch_flac", b, fmt, (), place, joined_len)
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
-                      voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0, spectrum=None, formants=None):
+                      voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0, spectrum=None, formants=None,
+                      formant_track=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above.  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
@@ -1524,7 +1585,12 @@ class Pipeline:
         filled.  Everything else is that of the same call without.  A library without the symbol is refused, never served without.
         formants: a FormantContour -> the returned tuple gains a last element: that FormantContour with f_hz / bw_hz [n_frames][n_formants] and
         status [n_frames] of the delivered signal filled (one call of sbv2_pipeline_fetch_request_formant_contour, the widest of the C symbols).
-        Everything else is that of the same call without.  A library without the symbol is refused, never served without."""
+        Everything else is that of the same call without.  A library without the symbol is refused, never served without.
+        formant_track: a FormantTrack (with formants, whose n_formants is the number of tracks) -> f_hz / bw_hz are the TRACKED values (one call
+        of sbv2_pipeline_fetch_request_formant_track); everything else is that of the same call without.  A library without the symbol is
+        refused, never served untracked."""
+        if formant_track is not None and formants is None:
+            raise Sbv2Error("a formant track needs formants (a FormantContour) to deliver its values in")
         fm = None if formant_scale == 1.0 else Formant(formant_scale)   # (a NaN is carried on and refused by the library)
         if flac and fmt.encoding != "s16":
             raise Sbv2Error(f"FLAC needs an s16 PcmFormat, not {fmt.encoding!r}")
@@ -1559,7 +1625,14 @@ class Pipeline:
         opt = lambda o: ref(o.c if o is not None else None)
         args = (self.h, b.ticket, C.byref(req), opt(voice), opt(track), opt(dynamics), ref(ctp), opt(fm), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
                 C.byref(got), _f64p(stats) if nstats else None, _f64p(dst_stats) if dst_stats is not None else None, ref(cm), ref(cp))
-        if formants is not None:
+        if formant_track is not None:
+            fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_formant_track", None)
+            if fn is None:
+                raise Sbv2Error("a tracked formant contour needs a library with sbv2_pipeline_fetch_request_formant_track: the request is not "
+                                "served untracked")
+            cft = formant_track.c
+            check(fn(*args, ref(csp), C.byref(cfc), C.byref(cft)))
+        elif formants is not None:
             fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_formant_contour", None)
             if fn is None:
                 raise Sbv2Error("a formant contour needs a library with sbv2_pipeline_fetch_request_formant_contour: the request is not served "

@@ -63,6 +63,12 @@ class SynthesizeOptions:
     their bandwidths per frame, formants_hz frames per second (an integer in [1, 1000]; sample_rate // formants_hz delivered samples per
     frame), by an LPC fit of formants_order (default 2 + sample_rate // 1000, rounded up to even) to formants_window samples (default 25 ms),
     resonances up to formants_max_hz (default min(5500, sample_rate / 2 - 50)) accepted.  The other four fields need formants.
+    formants_track (new; needs formants in [1, 5]; the same two routes, refused everywhere else, every stream included): the contour is
+    tracked across frames on the device (model.FormantTrack): formants_candidates roots are kept per frame (default formants + 3, at most 7
+    and formants_order / 2) and one best path assigns the formants to them, so a spurious root no longer shifts a frame by a slot.
+    formants_ref_hz: one reference per formant, ascending (default 500, 1500, 2500, ...); formants_freq_cost / formants_bw_cost /
+    formants_jump_cost in [0, 16] (defaults: model.FormantTrack's).  The marks' "formants" block says "tracked": true and the tokens' f1_hz /
+    f2_hz are means of the tracked values.  The five fields need formants_track.  False is the calls there always were.
     pitch_scale in [0.5, 2] / intonation_scale in [0, 2] (new; checked here): the voice is raised or lowered, its melody flattened or
     exaggerated about its mean, by a length-preserving overlap-add of the synthesized rows on the device before anything else of the output
     chain (model.Voice); whole-signal routes only (easy_synthesize, easy_synthesize_marks, the batcher), refused on streams.  The defaults
@@ -102,9 +108,13 @@ class SynthesizeOptions:
                  compressor=False, comp_threshold=8.0, comp_ratio=4.0, comp_attack=600.0, comp_release=60.0, token_pitch=None, token_pitch_kind="hz",
                  token_pitch_smooth=2, formant_scale=1.0, assist=None, assist_weight=0.7, voice_pivot_hz=None, level_target=None,
                  level_range=12.0, level_slew=3.0, level_hold=10, spectrum_mels=None, spectrum_fft=None, spectrum_hop=None, spectrum_fmin=0.0,
-                 spectrum_fmax=None, formants=None, formants_hz=100, formants_max_hz=None, formants_order=None, formants_window=None):
+                 spectrum_fmax=None, formants=None, formants_hz=100, formants_max_hz=None, formants_order=None, formants_window=None,
+                 formants_track=False, formants_candidates=None, formants_ref_hz=None, formants_freq_cost=None, formants_bw_cost=None,
+                 formants_jump_cost=None):
         self.formants, self.formants_hz, self.formants_max_hz = formants, formants_hz, formants_max_hz
         self.formants_order, self.formants_window = formants_order, formants_window
+        self.formants_track, self.formants_candidates, self.formants_ref_hz = formants_track, formants_candidates, formants_ref_hz
+        self.formants_freq_cost, self.formants_bw_cost, self.formants_jump_cost = formants_freq_cost, formants_bw_cost, formants_jump_cost
         formants_options(self, None)   # (the fields' types; the ranges need the rate)
         self.spectrum_mels, self.spectrum_fft, self.spectrum_hop = spectrum_mels, spectrum_fft, spectrum_hop
         self.spectrum_fmin, self.spectrum_fmax = spectrum_fmin, spectrum_fmax
@@ -549,6 +559,7 @@ def formants_options(options, rate):
     """The model.FormantContour of a request with marks (None without formants).  Bad types are refused always, the ranges once the delivered
     rate is known (rate None: the types alone), by the library's own host check, before any GPU work."""
     n, hz, fmax, order, window = (getattr(options, k, d) for k, d in zip(FORMANTS_FIELDS, FORMANTS_DEFAULTS))
+    formants_track_options(options, None)   # (formants_track and its fields: the types, and that formants is named)
     for name, v in (("formants", n), ("formants_order", order), ("formants_window", window)):
         if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
             raise FormantsError(f"{name} must be an integer: {v!r}")
@@ -573,12 +584,65 @@ def formants_options(options, rate):
         model.formant_contour_defaults(rate, fc)
     except model.Sbv2Error as e:
         raise FormantsError(str(e).replace("formant contour:", "formants:")) from None
+    formants_track_options(options, rate, fc)   # (a bad track is refused where a bad contour is)
     return fc
+
+
+FORMANTS_TRACK_FIELDS = ("formants_track", "formants_candidates", "formants_ref_hz", "formants_freq_cost", "formants_bw_cost", "formants_jump_cost")
+FORMANTS_TRACK_DEFAULTS = (False, None, None, None, None, None)
+FORMANTS_TRACK_REF_HZ = (500.0, 1500.0, 2500.0, 3500.0, 4500.0)   # the usual references, one per track
+
+
+def formants_track_options(options, rate, fc=None):
+    """The model.FormantTrack of a request with marks (None without formants_track).  fc: the request's FormantContour (formants_options).  Bad
+    types are refused always, the ranges once the delivered rate is known (rate None: the types alone), by the library's own host check.
+    None fields are the usual values: 3 candidates more than tracks (at most 7 and order / 2), the references 500, 1500, ... Hz, the costs of
+    model.FormantTrack."""
+    on, K, ref, *costs = (getattr(options, k, d) for k, d in zip(FORMANTS_TRACK_FIELDS, FORMANTS_TRACK_DEFAULTS))
+    if not isinstance(on, bool):
+        raise FormantsError(f"formants_track must be true or false: {on!r}")
+    if K is not None and (isinstance(K, bool) or not isinstance(K, int)):
+        raise FormantsError(f"formants_candidates must be an integer: {K!r}")
+    number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float))
+    if ref is not None and (not isinstance(ref, (list, tuple)) or not all(number(v) for v in ref)):
+        raise FormantsError(f"formants_ref_hz must be a list of numbers, one per formant: {ref!r}")
+    for name, v in zip(FORMANTS_TRACK_FIELDS[3:], costs):
+        if v is not None and not number(v):
+            raise FormantsError(f"{name} must be a number: {v!r}")
+    if not on:
+        if (K, ref, *costs) != FORMANTS_TRACK_DEFAULTS[1:]:
+            raise FormantsError("formants_candidates / formants_ref_hz / formants_*_cost describe a tracked formant contour: set formants_track "
+                                "as well")
+        return None
+    n = getattr(options, "formants", None)
+    if n is None:
+        raise FormantsError("formants_track tracks a formant contour: name formants (how many tracks, 1 to 5) as well")
+    if not 1 <= n <= len(FORMANTS_TRACK_REF_HZ):
+        raise FormantsError(f"formants_track follows at most {len(FORMANTS_TRACK_REF_HZ)} formants: formants = {n!r}")
+    if ref is not None and len(ref) != n:
+        raise FormantsError(f"formants_ref_hz must hold one reference per formant, {n}: {ref!r}")
+    if rate is None or fc is None:
+        return None
+    usual = model.FormantTrack()
+    ft = model.FormantTrack(FORMANTS_TRACK_REF_HZ[:n] if ref is None else ref, min(n + 3, 7, fc.order // 2) if K is None else K,
+                            *(getattr(usual, k[9:]) if v is None else v for k, v in zip(FORMANTS_TRACK_FIELDS[3:], costs)))
+    try:
+        model.formant_track_check(rate, fc, ft)
+    except model.Sbv2Error as e:
+        raise FormantsError(str(e).replace("formant track:", "formants_track:")) from None
+    return ft
+
+
+def refuse_formants_track(options, what: str):
+    """formants_track and its fields where the contour leaves chunk by chunk: refused, with the route that tracks a whole signal."""
+    if any(getattr(options, k, d) != d for k, d in zip(FORMANTS_TRACK_FIELDS, FORMANTS_TRACK_DEFAULTS)):
+        raise FormantsError(f"formants_track chooses one path through all frames of a signal: {what} hands out frames before the signal is "
+                            "complete, ask /synthesize_marks (easy_synthesize_marks, Pipeline.fetch_request) or the batcher with marks instead")
 
 
 def refuse_formants(options, what: str):
     """The formants fields where no marks of a whole signal are returned: refused, with the route that carries a formant contour."""
-    if any(getattr(options, k, d) != d for k, d in zip(FORMANTS_FIELDS, FORMANTS_DEFAULTS)):
+    if any(getattr(options, k, d) != d for k, d in zip(FORMANTS_FIELDS + FORMANTS_TRACK_FIELDS, FORMANTS_DEFAULTS + FORMANTS_TRACK_DEFAULTS)):
         raise FormantsError(f"formants and its fields need the speech marks of a whole signal: {what} carries none, ask /synthesize_marks "
                             "(easy_synthesize_marks) instead")
 
@@ -595,12 +659,17 @@ def require_formants(pipe, options):
     if "formants" not in params and not any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
         raise model.Sbv2Error(f"formants needs a pipeline whose fetch_request takes formants: {type(pipe).__name__} does not, and the "
                               "request is not served without its formant contour")
+    if getattr(options, "formants_track", False) and "formant_track" not in params and not any(
+            p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
+        raise model.Sbv2Error(f"formants_track needs a pipeline whose fetch_request takes formant_track: {type(pipe).__name__} does not, and "
+                              "the request is not served with its formants untracked")
 
 
 def formants_dict(fc, tokens) -> dict:
     """The "formants" block of a marks dict from a filled model.FormantContour: {hop, order, f_hz [n][k], bw_hz [n][k]} (0 = the frame has no
     such formant).  Besides, every token of `tokens` gains f1_hz and f2_hz: the mean of the non-zero F1 / F2 of the frames whose centre f hop +
-    hop // 2 lies in its span (None when there is none)."""
+    hop // 2 lies in its span (None when there is none).  A tracked contour (formants_track) brings its tracked values here: the means are
+    of those, and finish_request adds "tracked": true."""
     f = np.asarray(fc.f_hz, np.float64)
     centre = np.arange(f.shape[0], dtype=np.int64) * fc.hop + fc.hop // 2
     for t in tokens:
@@ -799,6 +868,9 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
             if fcon is not None:
                 require_formants(pipe, options)
                 kw["formants"] = fcon
+                ftrack = formants_track_options(options, fmt.sample_rate, fcon)
+                if ftrack is not None:   # (named only when asked for)
+                    kw["formant_track"] = ftrack
         track = track_options(options)
         if track is not None and (pitch is not None or shifts):   # (it needs a contour or a shift)
             kw["track"] = track
@@ -818,6 +890,8 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
                 marks[-1]["spectrum"] = spectrum_dict(got.spectrum)
             if fcon is not None:
                 marks[-1]["formants"] = formants_dict(got.formants, marks[-1]["tokens"])
+                if "formant_track" in kw:
+                    marks[-1]["formants"]["tracked"] = True
         if dstats is not None and dynamics_stats is not None:
             dynamics_stats.append([float(v) for v in dstats])
         if stats is not None and loudness_stats is not None:
@@ -1096,6 +1170,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
             raise FormantsError("formants=True on a stream comes with its speech marks: pass levels=True as well")
         if getattr(options, "formants", None) is None:
             raise FormantsError("formants=True needs options.formants (how many, 1 to 8)")
+        refuse_formants_track(options, "a stream (/synthesize_stream_marks)")
     else:
         refuse_formants(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if spectrum:

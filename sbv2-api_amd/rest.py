@@ -61,6 +61,13 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     formants_hz = 100 (frames per second), formants_max_hz (null: min(5500, sample_rate / 2 - 50)), formants_order (null: 2 +
                     sample_rate // 1000, rounded up to even), formants_window (null: 25 ms).  A bad value answers 400; so does any of the five
                     fields on every other route, the stream routes included, naming /synthesize_marks.
+  formants_track = false (new; /synthesize_marks only, batched or not, with formants in 1 to 5): the contour is tracked across frames on the
+                    device: formants_candidates roots are kept per frame (null: formants + 3, at most 7 and order / 2) and one best path
+                    assigns the formants to them, so a spurious root no longer shifts a frame by a slot.  formants_ref_hz (null: 500, 1500,
+                    2500, ...; one per formant, ascending), formants_freq_cost / formants_bw_cost / formants_jump_cost in [0, 16] (null: the
+                    usual values).  The block then says "tracked": true and f1_hz / f2_hz are means of the tracked values.  A bad value
+                    answers 400; so does any of the six fields on every other route, formants_stream included: a best path needs the whole
+                    signal.
   formants_stream = false (new; /synthesize_stream_marks only, with formants and its fields): the first line gains "formants": {"hop",
                     "order", "n_formants", "n_frames"} and every later line "formants": {"first", "f_hz": [[F1, ...] per frame], "bw_hz": likewise},
                     the frames that piece completed.  The tokens gain no f1_hz / f2_hz.  Without it the stream routes keep answering 400 for
@@ -236,6 +243,12 @@ def make_app(holder, batching=None):
         formants_max_hz: Optional[float] = None   # resonances accepted up to here; null = min(5500, sample_rate / 2 - 50)
         formants_order: Optional[int] = None  # LPC order, even, [4, 50]; null = 2 + sample_rate // 1000 rounded up to even
         formants_window: Optional[int] = None # delivered samples, [64, 2048]; null = 25 ms
+        formants_track: bool = False          # new: /synthesize_marks only (400 elsewhere, every stream route included): the contour tracked across frames; needs formants in [1, 5]
+        formants_candidates: Optional[int] = None   # roots kept per frame, [formants, min(7, order / 2)]; null = formants + 3, capped
+        formants_ref_hz: Optional[List[float]] = None   # one reference per formant, ascending; null = 500, 1500, 2500, ...
+        formants_freq_cost: Optional[float] = None   # [0, 16]; null = the usual value (likewise the next two)
+        formants_bw_cost: Optional[float] = None
+        formants_jump_cost: Optional[float] = None
         voice_pivot_hz: Optional[Union[float, List[float]]] = None   # new: /synthesize_stream, /synthesize_stream_marks: the f0 (Hz, [70, 600]) that intonation_scale pivots about, one number or one per sentence; it opens the three scales on the stream routes; 400 elsewhere
 
     class SynthesizeMarksRequest(SynthesizeRequest):
@@ -301,6 +314,9 @@ def make_app(holder, batching=None):
                                               **({k: getattr(req, k) for k in orchestrator.FORMANTS_FIELDS}
                                                  if any(getattr(req, k, d) != d
                                                         for k, d in zip(orchestrator.FORMANTS_FIELDS, orchestrator.FORMANTS_DEFAULTS)) else {}),
+                                              **({k: getattr(req, k) for k in orchestrator.FORMANTS_TRACK_FIELDS}
+                                                 if any(getattr(req, k, d) != d for k, d in zip(orchestrator.FORMANTS_TRACK_FIELDS,
+                                                                                                orchestrator.FORMANTS_TRACK_DEFAULTS)) else {}),
                                               **({"level_target": req.level_target, "level_range": req.level_range, "level_slew": req.level_slew,
                                                   "level_hold": req.level_hold} if getattr(req, "level_target", None) is not None else {}),
                                               **({"assist": req.assist_text or None, "assist_weight": req.assist_text_weight}
@@ -377,6 +393,7 @@ def make_app(holder, batching=None):
             elif req.formants is None:
                 raise orchestrator.FormantsError("formants_stream needs formants (how many, 1 to 8)")
             else:
+                orchestrator.refuse_formants_track(req, "a stream (/synthesize_stream_marks)")   # (a best path needs the whole signal)
                 orchestrator.formants_options(req, req.sample_rate)   # (a bad field is the request's fault)
             if not spectrum:
                 orchestrator.refuse_spectrum(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
