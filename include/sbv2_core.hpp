@@ -150,6 +150,31 @@ inline void fetch_request_token_pitch(sbv2_pipeline* p, int64_t ticket, const sb
                                                   pitch));
 }
 
+// Not in the reference: per-token volume targets of a fetched request (sbv2_token_gain in sbv2_hip.h states them).  values: one per token of the
+// listed rows in marks order, 0 = not edited; rms: target RMS (full scale = 1.0), else amplitude ratios; ramp: native samples about a token
+// boundary; every factor within [1 / max_ratio, max_ratio].  applied / src_rms are filled by fetch_request_token_gain.
+struct TokenGain {
+    std::vector<double> values;
+    bool rms = false;
+    int64_t ramp = 441;
+    double max_ratio = 4.0;
+    std::vector<double> applied, src_rms;
+};
+// sbv2_pipeline_fetch_request_token_gain with owned arrays: the widest request fetch with the table behind it; everything else may be NULL as
+// there (contour with formant_track, as sbv2_pipeline_fetch_request_formant_track has it).
+inline void fetch_request_token_gain(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,
+                                     const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                     const sbv2_formant* formant, TokenGain& tg, void* dst, int64_t capacity_bytes, int64_t* out_count,
+                                     double* stats = nullptr, double* dyn_stats = nullptr, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr,
+                                     sbv2_spectrum* spectrum = nullptr, sbv2_formant_contour* contour = nullptr,
+                                     const sbv2_formant_track* formant_track = nullptr) {
+    tg.applied.assign(tg.values.size(), 1.0);
+    tg.src_rms.assign(tg.values.size(), 0.0);
+    const sbv2_token_gain c{tg.values.data(), (int64_t)tg.values.size(), tg.ramp, tg.max_ratio, tg.rms ? 1 : 0, 0, tg.applied.data(), tg.src_rms.data()};
+    check(sbv2_pipeline_fetch_request_token_gain(p, ticket, &req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count, stats,
+                                                 dyn_stats, marks, pitch, spectrum, contour, formant_track, &c));
+}
+
 // Not in the reference: the formant scale of a fetched request (sbv2_formant in sbv2_hip.h states it).  sbv2_pipeline_fetch_request_formant with
 // owned arrays: fetch_request_token_pitch with formant_scale behind the table; 1 is exactly that call.
 inline void fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,

@@ -855,6 +855,68 @@ int sbv2_debug_formant_track(int device, const void* x, int encoding, int64_t n,
                              const sbv2_formant_track* track, const double* cand_f_in, const double* cand_b_in, int64_t nf_in, double* cand_f_out,
                              double* cand_b_out, int32_t* state_out);
 
+/* ---- new: per-token volume targets.  The speech marks say that token 17 is 9 dB quieter than its neighbours (tok_sumsq, tok_peak); this says
+ * "bring it to -20 dBFS RMS", or "twice as loud": query, set a target per token, fetch again.  It is the third of the per-token edits beside
+ * sbv2_token_pitch and forced durations.  The stage runs on the rows' native 44.1 kHz f32 samples behind the shifter (sbv2_voice,
+ * sbv2_token_pitch, sbv2_formant) and in front of the formatter: placement, delivered lengths, token spans, resampler, compressor, loudness,
+ * limiter, every sink and every marks block work unchanged on the edited signal.
+ * Input.  x = the shifter's output if a shifter runs, else the run's row.  It is only read; the edited rows go to a buffer of the chain.
+ * Token spans.  Token t of a row covers the native samples [E[t - 1], E[t]) of its row, E[-1] = 0, E[t] = hop c[t + 1] (c = the running sum of
+ *   the row's used durations: the span rule of sbv2_marks at the native rate); len_t = E[t] - E[t - 1].
+ * Measured level.  M_t = S_t / double(len_t), S_t the f64 sum of double(x[n]) double(x[n]) over the span IN THIS ORDER: with stride = 64 for
+ *   len_t <= 4096 and 256 above, partial sum l (0 <= l < stride) adds the squares at offsets l, l + stride, l + 2 stride, ... of the span in
+ *   ascending order from 0.0; then, within each group of 64 consecutive partial sums, for d = 32, 16, 8, 4, 2, 1: sum i += sum i + d (i < d);
+ *   then (stride 256) the four groups' sums are added in ascending order.  src_rms_t = sqrt(M_t) (0 for an empty span).
+ * Factor.  g_t = value_t (kind 0) or value_t / sqrt(M_t) (kind 1), and g_t = 1 where value_t == 0, the span is empty or M_t == 0; then
+ *   g_t = min(max(g_t, 1 / max_ratio), max_ratio).  f64 add, multiply, divide, sqrt and compare only, never contracted, no log / exp / cos:
+ *   every operation is correctly rounded and a restatement in numpy float64 equals the device bit for bit.  The C layer takes ratios and
+ *   linear RMS (full scale = 1.0); dB belongs to the callers.  applied_t = g_t.
+ * Gain curve.  At the boundary b = E[t] between tokens t and t + 1 of one row, R_b = min(ramp, len_t, len_{t+1}) rounded down to an even
+ *   number.  For n in [b - R_b / 2, b + R_b / 2): u = double(2 (n - b) + R_b + 1) / double(2 R_b) and
+ *   g(n) = g_t + (g_{t+1} - g_t) ((u u) (3 - 2 u)), in that order.  Elsewhere g(n) = g_t of the token that holds n.  R_b <= both lengths, so
+ *   the ramps of a token's two ends never overlap, and a zero-duration token has steps at both ends.  A row's first and last tokens hold their
+ *   factor to the row's ends (samples behind a row's last end, which only the hook can have, belong to its last token); nothing crosses rows,
+ *   and the silence between rows is not touched.
+ * Output.  y[n] = float(double(x[n]) g(n)).  The stage CAN exceed full scale: tok_peak of the marks shows it, and a limiter behind it bounds it
+ *   as before; an f32 or s16 sink without one clips or carries the excess as the formatter always did.
+ * Identity.  A value array of all zeros, or kind 0 with every value 0 or 1, launches nothing: the fetch is the call without, byte for byte;
+ *   applied is then 1 and src_rms 0 throughout (nothing was measured), as sbv2_token_pitch reports src_f0.
+ * Not built: token gain on streams (sbv2_stream_*: a kind 0 table could stream, a ramp needs ramp / 2 samples of look-ahead; kind 1 needs the
+ *   whole token) and on sbv2_node_*, a gain lane per time instead of per token, emphasis presets that combine pitch, duration and volume,
+ *   energy compensation of the formant scale through this stage. */
+typedef struct sbv2_token_gain {
+    const double* value;      /* [n_tokens]: tokens of the rows in the order of req->utts, token order within a row (as sbv2_token_pitch); 0 = token not edited */
+    int64_t n_tokens;         /* must equal the sum of t_lens over the listed rows */
+    int64_t ramp;             /* ramp length in native samples, >= 0 (0 = steps at the token boundaries) */
+    double max_ratio;         /* >= 1, finite: every factor is clamped to [1 / max_ratio, max_ratio] */
+    int32_t kind;             /* 0 = value is an amplitude ratio; 1 = value is the token's target RMS, full scale = 1.0, on the native f32 row as the stage sees it */
+    int32_t reserved;         /* must be 0 */
+    double* applied;          /* out, NULL or [n_tokens]: the factor used for the token (shows the clamp; 1.0 where not edited) */
+    double* src_rms;          /* out, NULL or [n_tokens]: the token's measured RMS sqrt(M_t) */
+} sbv2_token_gain;
+/* sbv2_pipeline_fetch_request_formant_track with the listed rows' tokens scaled.  token_gain == NULL, or a table that is the identity (above),
+ * is exactly that call.  Otherwise three launches (k_tgain_level, k_tgain_factors, k_tgain_apply) behind the shifter's, no atomics, no
+ * synchronisation beyond the fetch's one; applied and src_rms reach pinned memory before it and the caller's arrays only after everything else
+ * has succeeded.  The run's PCM is only read: two equal fetches give identical bytes and identical applied / src_rms, and a later fetch
+ * without a table is the unedited signal.  Token spans and delivered lengths are those of the call without.  Refused with nothing written:
+ * n_tokens different from the rows' token count (the message names the count), a NULL value (with n_tokens > 0), kind outside {0, 1},
+ * ramp < 0, max_ratio < 1 or not finite, a value that is negative or not finite, a non-zero reserved, and everything that call refuses. */
+int sbv2_pipeline_fetch_request_token_gain(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                           const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                           const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                           double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                           sbv2_formant_contour* contour, const sbv2_formant_track* formant_track,
+                                           const sbv2_token_gain* token_gain);
+/* Samples of one row per workgroup of k_tgain_apply (tests place token boundaries around it). */
+int32_t sbv2_token_gain_tile(void);
+/* Test hook: the stage on host rows x laid back to back (lens [nrows]; a row of a length that is no multiple of 4 leaves the next one's head
+ * off the 16-byte grid), always through the kernels, the identity included.  tok_counts [nrows]: tokens of every row; tok_ends [sum
+ * tok_counts]: the sample of its row every token ends at, ascending within [0, lens[row]] (arbitrary positions: the hook needs no model);
+ * token_gain as in the fetch, its n_tokens = sum tok_counts.  y receives the edited rows, laid out as x; token_gain->applied and ->src_rms are
+ * filled.  Everything is checked before any device call. */
+int sbv2_debug_token_gain(int device, const float* x, const int64_t* lens, int nrows, const int64_t* tok_counts, const int64_t* tok_ends,
+                          const sbv2_token_gain* token_gain, float* y);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,

@@ -124,6 +124,12 @@ class Sbv2TokenPitch(C.Structure):
                 ("applied", C.POINTER(C.c_double)), ("src_f0", C.POINTER(C.c_double)), ("reserved", C.c_int64)]
 
 
+class Sbv2TokenGain(C.Structure):
+    """struct sbv2_token_gain (include/sbv2_hip.h)."""
+    _fields_ = [("value", C.POINTER(C.c_double)), ("n_tokens", C.c_int64), ("ramp", C.c_int64), ("max_ratio", C.c_double), ("kind", C.c_int32),
+                ("reserved", C.c_int32), ("applied", C.POINTER(C.c_double)), ("src_rms", C.POINTER(C.c_double))]
+
+
 class Sbv2Formant(C.Structure):
     """struct sbv2_formant (include/sbv2_hip.h)."""
     _fields_ = [("formant_scale", C.c_double), ("reserved", C.c_double)]
@@ -253,6 +259,14 @@ SYMBOLS = {
                                                             C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
                                                             C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch),
                                                             C.POINTER(Sbv2Spectrum), C.POINTER(Sbv2FormantContour), C.POINTER(Sbv2FormantTrack)]),
+    "sbv2_pipeline_fetch_request_token_gain": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                         C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch),
+                                                         C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
+                                                         C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch),
+                                                         C.POINTER(Sbv2Spectrum), C.POINTER(Sbv2FormantContour), C.POINTER(Sbv2FormantTrack),
+                                                         C.POINTER(Sbv2TokenGain)]),
+    "sbv2_token_gain_tile": (C.c_int32, []),
+    "sbv2_debug_token_gain": (C.c_int, [C.c_int, f32p, i64p, C.c_int, i64p, i64p, C.POINTER(Sbv2TokenGain), f32p]),
     "sbv2_formant_track_check": (C.c_int, [C.c_int32, C.POINTER(Sbv2FormantContour), C.POINTER(Sbv2FormantTrack)]),
     "sbv2_debug_formant_track": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int32, C.POINTER(Sbv2FormantContour),
                                            C.POINTER(Sbv2FormantTrack), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64,

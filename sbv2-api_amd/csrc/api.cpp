@@ -465,6 +465,8 @@ int32_t sbv2_voice_tile(void) { return Voice::kTile; }
 
 int32_t sbv2_dynamics_tile(void) { return Dynamics::kTile; }
 
+int32_t sbv2_token_gain_tile(void) { return TokenGain::kTile; }
+
 int sbv2_pitch_lags(int32_t sample_rate, double f0_min, double f0_max, int32_t* tau_min, int32_t* tau_max) {
     API_BEGIN
     SBV2_REQUIRE(tau_min && tau_max, "bad arguments");

@@ -17,6 +17,7 @@
 #include "models.h"
 #include "pcm_format.h"
 #include "spectrum.h"
+#include "token_gain.h"
 #include "track.h"
 #include "voice.h"
 
@@ -46,6 +47,7 @@ struct OutputChain {
     Formants formants; // ... and their formant contour (fetch_request_formant_contour only)
     FormantTrack formant_track;   // ... tracked across frames (fetch_request_formant_track only)
     Voice voice;       // pitch / intonation scale of the listed rows, in front of the formatter (fetch_request_voice only)
+    TokenGain token_gain;   // per-token volume of the listed rows, behind the shifter (fetch_request_token_gain only)
     Track track;       // the best path through the delivered contour's candidates (fetch_request_tracked only; the shifter has its own)
 };
 struct sbv2_pipeline {

@@ -43,6 +43,8 @@ struct FetchArgs {
 // spectrum: the power spectrum or mel bands (spectrum.h) of the same delivered samples as marks and pitch, one more launch beside theirs.
 // contour: the formant contour (formants.h) of the same samples, one more launch again.  formant_track (with contour): the stage keeps the
 // track's candidates per frame and the tracker (formant_track.h) chooses one path through them, two more launches.
+// token_gain (the identity: nothing): the listed rows' tokens are scaled (TokenGain, token_gain.h) behind the shifter, into the stage's own buffer,
+// and the pieces point there.
 struct FetchStages {
     const int32_t* utts = nullptr;   // the rows of the one signal (with place[k] belonging to row utts[k]); NULL: no request, all of the run
     int n_utts = 0;
@@ -57,6 +59,7 @@ struct FetchStages {
     sbv2_spectrum* spectrum = nullptr;
     sbv2_formant_contour* contour = nullptr;
     const sbv2_formant_track* formant_track = nullptr;
+    const sbv2_token_gain* token_gain = nullptr;
 };
 // ... and once everything about them that needs no run has been checked (check_stages).  Default: no stage.
 struct CheckedStages : FetchStages {
@@ -68,6 +71,7 @@ struct CheckedStages : FetchStages {
     SpectrumSpec ss;
     FormantContourSpec fcs;   // (with a formant track: n_formants = its candidates)
     FormantTrackSpec fts;
+    TokenGainSpec tgs;        // (tgs.edits: some token's factor can differ from 1)
     bool edit = false, scale = false, compress = false;   // a token is edited; the formants move; the compressor is not the identity
     bool shifts() const { return (voice && !vs.identity()) || edit || scale; }   // the shifter has something to do
 };
@@ -152,6 +156,7 @@ CheckedStages check_stages(const sbv2_fetch_request* req, const FetchStages& st)
     cs.vs = st.voice ? check_voice_static(st.voice, kNativeRate) : voice_spec(kNativeRate, 1.0, 1.0, 0, 0.0, 0.0, 0.0);   // (or the defaults)
     cs.edit = st.token_pitch && check_token_pitch_static(st.token_pitch, cs.vs);
     if (st.formant) cs.fs = check_formant_static(st.formant, cs.vs);
+    if (const sbv2_token_gain* g = st.token_gain) cs.tgs = token_gain_spec(g->value, g->n_tokens, g->kind, g->ramp, g->max_ratio, g->reserved);
     cs.scale = st.formant && !cs.fs.identity();
     if (st.track) {
         cs.ts = check_track_static(st.track);
@@ -271,6 +276,7 @@ struct FetchPlan {
     MarksPlan marks;
     std::vector<int64_t> tok_counts, tok_ends;   // (an edit only) per listed row: its tokens; per token: the native sample it ends at
     bool shift = false;                          // the shifter runs
+    bool tgain = false;                          // the token gain runs
 };
 FetchPlan plan_fetch(const FetchArgs& a, const CheckedStages& cs) {
     FetchPlan pl;
@@ -285,8 +291,8 @@ FetchPlan plan_fetch(const FetchArgs& a, const CheckedStages& cs) {
         SBV2_REQUIRE(a.capacity_bytes >= pl.pcm_bytes,
                      "PCM buffer too small: " + std::to_string(a.capacity_bytes) + " < " + std::to_string(pl.pcm_bytes) + " bytes");
     const std::vector<int64_t>& offs = vm.used_offs();
-    int64_t n_tok = 0;   // the tokens of the listed rows, for marks and token pitch alike
-    if (cs.marks || cs.token_pitch) {
+    int64_t n_tok = 0;   // the tokens of the listed rows, for marks, token pitch and token gain alike
+    if (cs.marks || cs.token_pitch || cs.token_gain) {
         SBV2_REQUIRE(offs.size() == vm.pcm_lens().size() + 1, "internal: the run kept no durations");
         for (int k = 0; k < cs.n_utts; ++k) n_tok += offs[cs.utts[k] + 1] - offs[cs.utts[k]];
     }
@@ -310,7 +316,10 @@ FetchPlan plan_fetch(const FetchArgs& a, const CheckedStages& cs) {
     if (cs.token_pitch)
         SBV2_REQUIRE(cs.token_pitch->n_tokens == n_tok, "sbv2_token_pitch.n_tokens is " + std::to_string(cs.token_pitch->n_tokens) +
                                                             " but the listed rows have " + std::to_string(n_tok) + " tokens");
-    if (cs.edit) {   // token t of a row ends at hop c[t + 1]
+    if (cs.token_gain)
+        SBV2_REQUIRE(cs.token_gain->n_tokens == n_tok, "sbv2_token_gain.n_tokens is " + std::to_string(cs.token_gain->n_tokens) +
+                                                           " but the listed rows have " + std::to_string(n_tok) + " tokens");
+    if (cs.edit || cs.tgs.edits) {   // token t of a row ends at hop c[t + 1]
         pl.tok_ends.reserve((size_t)n_tok);
         for (int k = 0; k < cs.n_utts; ++k) {
             pl.tok_counts.push_back(offs[cs.utts[k] + 1] - offs[cs.utts[k]]);
@@ -320,6 +329,7 @@ FetchPlan plan_fetch(const FetchArgs& a, const CheckedStages& cs) {
         }
     }
     pl.shift = cs.shifts() && cs.n_utts > 0;
+    pl.tgain = cs.tgs.edits && cs.n_utts > 0;
     return pl;
 }
 
@@ -334,6 +344,7 @@ std::vector<int64_t> enqueue_fetch(const FetchArgs& a, const CheckedStages& cs, 
     OutputChain& c = a.p->chains[pl.ctx];
     const hipStream_t s = vm.stream();
     const TrackSpec* const ts = cs.track ? &cs.ts : nullptr;
+    const float* base = vm.pcm_device();   // where the pieces point
     if (pl.shift) {   // the listed rows, shifted, where the formatter will read them
         std::vector<VoiceRow> rows((size_t)cs.n_utts);
         for (int k = 0; k < cs.n_utts; ++k) rows[k] = VoiceRow{vm.pcm_offs()[cs.utts[k]], vm.pcm_lens()[cs.utts[k]]};
@@ -343,6 +354,13 @@ std::vector<int64_t> enqueue_fetch(const FetchArgs& a, const CheckedStages& cs, 
         const float* shifted = c.voice.run(pcm, vm.pcm_total(), rows.data(), cs.n_utts, cs.vs, s, nullptr, nullptr, ts, cs.edit ? &vt : nullptr,
                                            cs.scale ? &cs.fs : nullptr);
         for (FmtPiece& pc : pl.pieces) pc.src = shifted + (pc.src - pcm);
+        base = shifted;
+    }
+    if (pl.tgain) {   // ... and their tokens scaled, read where the formatter would have read them
+        std::vector<TokenGainRow> rows((size_t)cs.n_utts);
+        for (int k = 0; k < cs.n_utts; ++k) rows[k] = TokenGainRow{vm.pcm_offs()[cs.utts[k]], vm.pcm_lens()[cs.utts[k]]};
+        const float* scaled = c.token_gain.run(base, vm.pcm_total(), rows.data(), cs.n_utts, pl.tok_counts.data(), pl.tok_ends.data(), cs.tgs, s);
+        for (FmtPiece& pc : pl.pieces) pc.src = scaled + (pc.src - base);
     }
     if (a.sink == Sink::kPcm && a.gain.kind == FetchGain::kNone && spec.identity() && !a.place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
         HIP_CHECK(hipMemcpyAsync(a.dst, vm.pcm_device(), sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, s));
@@ -376,7 +394,7 @@ std::vector<int64_t> enqueue_fetch(const FetchArgs& a, const CheckedStages& cs, 
     return flac_bytes;
 }
 
-// Phase 3, once everything else has succeeded: the counts, the stats, and the caller's marks, pitch, spectrum and token-pitch arrays, from the chain's pinned
+// Phase 3, once everything else has succeeded: the counts, the stats, and the caller's marks, pitch, spectrum, token-pitch and token-gain arrays, from the chain's pinned
 // buffers.  Nothing here can fail.
 void deliver_fetch(const FetchArgs& a, const CheckedStages& cs, const FetchPlan& pl, const std::vector<int64_t>& flac_bytes) {
     OutputChain& c = a.p->chains[pl.ctx];
@@ -402,6 +420,12 @@ void deliver_fetch(const FetchArgs& a, const CheckedStages& cs, const FetchPlan&
         for (int64_t t = 0; t < tp->n_tokens; ++t) {
             if (tp->applied) tp->applied[t] = ran ? c.voice.applied_host()[t] : 1.0;
             if (tp->src_f0) tp->src_f0[t] = ran ? c.voice.src_f0_host()[t] : 0.0;
+        }
+    }
+    if (const sbv2_token_gain* tg = cs.token_gain) {   // (the identity: nothing was measured)
+        for (int64_t t = 0; t < tg->n_tokens; ++t) {
+            if (tg->applied) tg->applied[t] = pl.tgain ? c.token_gain.applied_host()[t] : 1.0;
+            if (tg->src_rms) tg->src_rms[t] = pl.tgain ? c.token_gain.src_rms_host()[t] : 0.0;
         }
     }
     if (sbv2_pitch* pitch = cs.pitch) {   // (an empty signal has no frames and ran nothing)
@@ -489,24 +513,33 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
 }
 
 // The widest request fetch; each narrower symbol below is exactly this call with NULL for what it lacks.
-int sbv2_pipeline_fetch_request_formant_track(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
-                                              const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
-                                              const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
-                                              double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
-                                              sbv2_formant_contour* contour, const sbv2_formant_track* formant_track) {
+int sbv2_pipeline_fetch_request_token_gain(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                           const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                           const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                           double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                           sbv2_formant_contour* contour, const sbv2_formant_track* formant_track,
+                                           const sbv2_token_gain* token_gain) {
     API_BEGIN
     static const int32_t no_rows[1] = {0};   // (a request of no rows is still a request: one empty joined signal)
     static const int64_t no_place[1] = {0};
     const bool rows = req && req->n_utts > 0;   // (what is wrong with req is refused in its turn, by check_stages)
     const CheckedStages cs = check_stages(
         req, FetchStages{rows ? req->utts : no_rows, rows ? req->n_utts : 0, voice, track, dynamics, dyn_stats, token_pitch, formant, marks, pitch,
-                         spectrum, contour, formant_track});
+                         spectrum, contour, formant_track, token_gain});
     const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter}
                            : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr}
                                            : FetchGain();
     const Sink sink = req->flac ? Sink::kFlac : Sink::kPcm;
     fetch_formatted({p, ticket, req->fmt, gain, rows ? req->place : no_place, req->joined_len, sink, dst, capacity_bytes, out_count, stats}, cs);
     API_END
+}
+int sbv2_pipeline_fetch_request_formant_track(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                              const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                              const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                              double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                              sbv2_formant_contour* contour, const sbv2_formant_track* formant_track) {
+    return sbv2_pipeline_fetch_request_token_gain(p, ticket, req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count, stats,
+                                                  dyn_stats, marks, pitch, spectrum, contour, formant_track, nullptr);
 }
 int sbv2_pipeline_fetch_request_formant_contour(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
                                                 const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,

@@ -2298,6 +2298,34 @@ int sbv2_debug_formant_track(int device, const void* x, int encoding, int64_t n,
     API_END
 }
 
+// The token gain (TokenGain, token_gain.hip) on host rows laid back to back and the caller's token ends, always through its kernels.  The
+// table's parameters here, rows and ends in TokenGain::run, all before any device call; nothing is written when the call fails.
+int sbv2_debug_token_gain(int device, const float* x, const int64_t* lens, int nrows, const int64_t* tok_counts, const int64_t* tok_ends,
+                          const sbv2_token_gain* token_gain, float* y) {
+    API_BEGIN
+    const sbv2_token_gain* g = token_gain;
+    SBV2_REQUIRE(g && nrows >= 0 && (nrows == 0 || (lens && tok_counts)), "bad arguments");
+    const TokenGainSpec sp = token_gain_spec(g->value, g->n_tokens, g->kind, g->ramp, g->max_ratio, g->reserved);
+    std::vector<TokenGainRow> rows((size_t)nrows);
+    int64_t total = 0;
+    for (int i = 0; i < nrows; ++i) {
+        SBV2_REQUIRE(lens[i] >= 0 && lens[i] < (1 << 30) && total < (1 << 30), "bad length of row " + std::to_string(i));
+        rows[i] = TokenGainRow{total, lens[i]};
+        total += lens[i];
+    }
+    SBV2_REQUIRE(total == 0 || (x && y), "bad arguments");
+    SBV2_REQUIRE(g->n_tokens == 0 || tok_ends, "bad arguments");
+    HIP_CHECK(hipSetDevice(device));
+    DevMem dx(x, sizeof(float) * (size_t)total);
+    TokenGain tg;
+    const float* dy = tg.run(dx.f(), total, rows.data(), nrows, tok_counts, tok_ends, sp, nullptr);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    if (total) HIP_CHECK(hipMemcpy(y, dy, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost));
+    if (g->applied) std::memcpy(g->applied, tg.applied_host(), sizeof(double) * (size_t)g->n_tokens);
+    if (g->src_rms) std::memcpy(g->src_rms, tg.src_rms_host(), sizeof(double) * (size_t)g->n_tokens);
+    API_END
+}
+
 // The tracker (Track, track.hip) on host samples, or on the caller's candidate table alone.  Everything is checked before any device call;
 // nothing is written when the call fails.
 int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, const sbv2_pitch_track* track,

@@ -907,6 +907,63 @@ class TokenPitch:
         return f"TokenPitch({self.values.size} tokens, {self.kind!r}, smooth={self.smooth})"
 
 
+class TokenGain:
+    """Per-token volume targets of a fetched request (struct sbv2_token_gain, include/sbv2_hip.h states it): values, one per token of the listed
+    rows in marks order, 0 = not edited; kind "ratio" (an amplitude factor) or "rms" (the token's target RMS, full scale = 1.0, on the native
+    row behind the shifter); ramp = native samples over which the factor changes at a token boundary (0 = steps); every factor is clamped to
+    [1 / max_ratio, max_ratio].  Ranges are checked by the library.  Once a call has filled it: applied [n] (the factor used, 1.0 where not
+    edited) and src_rms [n] (the token's measured RMS; 0 throughout when the table is the identity and nothing ran); None before."""
+    KINDS = {"ratio": 0, "rms": 1}
+
+    def __init__(self, values, kind: str = "ratio", ramp: int = 441, max_ratio: float = 4.0):
+        if kind not in self.KINDS:
+            raise Sbv2Error(f"token gain kind must be \"ratio\" or \"rms\", not {kind!r}")
+        self.values = np.ascontiguousarray(np.asarray(values, np.float64).reshape(-1))
+        self.kind, self.ramp, self.max_ratio = kind, int(ramp), float(max_ratio)
+        self.applied = self.src_rms = None
+
+    def c_struct(self):
+        """A sbv2_token_gain over fresh output arrays; take() keeps them once the call has succeeded."""
+        n = self.values.size
+        arrays = np.ones(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+        pad = self.values if n else np.zeros(1, np.float64)   # (never a NULL for an empty table)
+        c = _lib.Sbv2TokenGain(_f64p(pad), n, self.ramp if -2 ** 63 <= self.ramp < 2 ** 63 else -1, self.max_ratio, self.KINDS[self.kind], 0,
+                               _f64p(arrays[0]), _f64p(arrays[1]))
+        return c, arrays + (pad,)
+
+    def take(self, arrays):
+        self.applied, self.src_rms = arrays[0][:self.values.size], arrays[1][:self.values.size]
+        return self
+
+    def __repr__(self):
+        return f"TokenGain({self.values.size} tokens, {self.kind!r}, ramp={self.ramp}, max_ratio={self.max_ratio})"
+
+
+def token_gain_tile() -> int:
+    """Samples of one row per workgroup of the token gain's hot kernel (sbv2_token_gain_tile)."""
+    return int(_lib.lib().sbv2_token_gain_tile())
+
+
+def debug_token_gain(rows, tok_ends, token_gain: TokenGain, device: int = 0):
+    """Test hook: the token gain on host rows (sbv2_debug_token_gain; rows: float32 arrays, laid back to back on the device; tok_ends: per row
+    the ascending end positions of its tokens in samples of the row; token_gain: the table over all rows' tokens) -> (the edited rows,
+    token_gain with applied / src_rms filled).  Always through the kernels."""
+    rows = [np.ascontiguousarray(r, np.float32).reshape(-1) for r in rows]
+    ends = [np.ascontiguousarray(e, np.int64).reshape(-1) for e in tok_ends]
+    if len(ends) != len(rows):
+        raise Sbv2Error("tok_ends must hold one array per row")
+    x = np.concatenate(rows + [np.zeros(1, np.float32)])   # (never an empty buffer)
+    lens, counts = _i64([r.size for r in rows] or [0])[0], _i64([e.size for e in ends] or [0])[0]
+    flat = np.ascontiguousarray(np.concatenate(ends + [np.zeros(1, np.int64)]))
+    y = np.zeros_like(x)
+    ctg, arr = token_gain.c_struct()
+    check(_lib.lib().sbv2_debug_token_gain(int(device), x.ctypes.data_as(_lib.f32p), lens.ctypes.data_as(_lib.i64p), len(rows),
+                                           counts.ctypes.data_as(_lib.i64p), flat.ctypes.data_as(_lib.i64p), C.byref(ctg),
+                                           y.ctypes.data_as(_lib.f32p)))
+    token_gain.take(arr)
+    return [a.copy() for a in np.split(y[:-1], np.cumsum([r.size for r in rows])[:-1])] if rows else [], token_gain
+
+
 class Formant:
     """Formant scale of a fetched request (struct sbv2_formant, include/sbv2_hip.h states it): every grain of the shifter is read at
     formant_scale times its offset, which moves the spectral envelope by that factor and leaves f0, the marks and the length alone.
@@ -1410,14 +1467,15 @@ def get_trace(session: Session, name: str, utt: int = 0) -> np.ndarray:
 
 
 # What a Pipeline.fetch_request result holds, by name (None: not there, or there and None)
-FetchResult = namedtuple("FetchResult", "signal stats marks pitch dyn_stats token_pitch spectrum formants", defaults=(None,) * 6)
+FetchResult = namedtuple("FetchResult", "signal stats marks pitch dyn_stats token_pitch spectrum formants token_gain", defaults=(None,) * 7)
 
 
-def _fetch_fields(marks=False, pitch=False, dynamics=False, token_pitch=False, spectrum=False, formants=False):
-    """THE rule of the shape of a Pipeline.fetch_request result, from which of these six options were given: (signal, stats); then
+def _fetch_fields(marks=False, pitch=False, dynamics=False, token_pitch=False, spectrum=False, formants=False, token_gain=False):
+    """THE rule of the shape of a Pipeline.fetch_request result, from which of these seven options were given: (signal, stats); then
     marks-or-None if marks or pitch was; then the filled Pitch if pitch was; then the compressor's stats-or-None if dynamics was; then the
-    filled TokenPitch if token_pitch was; then the filled Spectrum if spectrum was; then the filled FormantContour if formants was."""
-    there = (True, True, marks or pitch, pitch, dynamics, token_pitch, spectrum, formants)
+    filled TokenPitch if token_pitch was; then the filled Spectrum if spectrum was; then the filled FormantContour if formants was; then the
+    filled TokenGain if token_gain was."""
+    there = (True, True, marks or pitch, pitch, dynamics, token_pitch, spectrum, formants, token_gain)
     return [name for name, t in zip(FetchResult._fields, there) if t]
 
 
@@ -1556,7 +1614,7 @@ class Pipeline:
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
                       voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0, spectrum=None, formants=None,
-                      formant_track=None):
+                      formant_track=None, token_gain=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above.  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
@@ -1588,7 +1646,11 @@ class Pipeline:
         Everything else is that of the same call without.  A library without the symbol is refused, never served without.
         formant_track: a FormantTrack (with formants, whose n_formants is the number of tracks) -> f_hz / bw_hz are the TRACKED values (one call
         of sbv2_pipeline_fetch_request_formant_track); everything else is that of the same call without.  A library without the symbol is
-        refused, never served untracked."""
+        refused, never served untracked.
+        token_gain: a TokenGain -> the listed rows' tokens are scaled on the device behind the shifter and in front of everything else (one
+        call of sbv2_pipeline_fetch_request_token_gain, the widest of the C symbols), and the returned tuple gains a last element: that
+        TokenGain with applied [n] and src_rms [n] filled.  A table that is the identity: the bytes of the call without.  A library without
+        the symbol is refused, never served unedited."""
         if formant_track is not None and formants is None:
             raise Sbv2Error("a formant track needs formants (a FormantContour) to deliver its values in")
         fm = None if formant_scale == 1.0 else Formant(formant_scale)   # (a NaN is carried on and refused by the library)
@@ -1609,6 +1671,7 @@ class Pipeline:
         dst_stats = None if dynamics is None or dynamics.is_identity() else np.zeros(3, np.float64)
         cp, parr = pitch.c_struct(out_len) if pitch is not None else (None, None)
         ctp, tparr = token_pitch.c_struct() if token_pitch is not None else (None, None)
+        ctg, tgarr = token_gain.c_struct() if token_gain is not None else (None, None)
         csp, sparr = spectrum.c_struct(out_len, fmt.sample_rate) if spectrum is not None else (None, None)
         cfc, fcarr = formants.c_struct(out_len, fmt.sample_rate) if formants is not None else (None, None)
         m = cm = None
@@ -1625,7 +1688,13 @@ class Pipeline:
         opt = lambda o: ref(o.c if o is not None else None)
         args = (self.h, b.ticket, C.byref(req), opt(voice), opt(track), opt(dynamics), ref(ctp), opt(fm), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
                 C.byref(got), _f64p(stats) if nstats else None, _f64p(dst_stats) if dst_stats is not None else None, ref(cm), ref(cp))
-        if formant_track is not None:
+        if token_gain is not None:
+            fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_token_gain", None)
+            if fn is None:
+                raise Sbv2Error("a token gain needs a library with sbv2_pipeline_fetch_request_token_gain: the request is not served unedited")
+            cft = formant_track.c if formant_track is not None else None
+            check(fn(*args, ref(csp), ref(cfc), ref(cft), C.byref(ctg)))
+        elif formant_track is not None:
             fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_formant_track", None)
             if fn is None:
                 raise Sbv2Error("a tracked formant contour needs a library with sbv2_pipeline_fetch_request_formant_track: the request is not "
@@ -1650,9 +1719,10 @@ class Pipeline:
         res = FetchResult(dst[:got.value].tobytes() if flac else dst[:got.value], stats, m, pitch.take(cp, parr) if pitch is not None else None,
                           dst_stats, token_pitch.take(tparr) if token_pitch is not None else None,
                           spectrum.take(csp, sparr) if spectrum is not None else None,
-                          formants.take(cfc, fcarr, fmt.sample_rate) if formants is not None else None)
+                          formants.take(cfc, fcarr, fmt.sample_rate) if formants is not None else None,
+                          token_gain.take(tgarr) if token_gain is not None else None)
         return fetch_result(res, marks=bool(marks), pitch=pitch is not None, dynamics=dynamics is not None, token_pitch=token_pitch is not None,
-                            spectrum=spectrum is not None, formants=formants is not None)
+                            spectrum=spectrum is not None, formants=formants is not None, token_gain=token_gain is not None)
 
     def close(self):
         if self.h:
@@ -1738,7 +1808,11 @@ class StreamHandle:
     def __init__(self, bert: Session, vits: Session, utt, chunk_frames=256, fmt: PcmFormat | None = None, flac: bool = False,
                  level: "StreamLevel | None" = None, gaps=None, levels: bool = False, env_hop: int = 0, pitch: "Pitch | None" = None, track=None,
                  voice: "StreamVoice | None" = None, token_pitch=None, leveler: "StreamLeveler | None" = None,
-                 spectrum: "Spectrum | None" = None, formants: "FormantContour | None" = None, **kw):
+                 spectrum: "Spectrum | None" = None, formants: "FormantContour | None" = None, token_gain=None, **kw):
+        if token_gain is not None:
+            raise Sbv2Error("a stream takes no token_gain: a token's level needs all of the token's samples, and a stream hands its samples out "
+                            "before they exist; fetch the whole signal instead (Pipeline.fetch_request(token_gain=), /synthesize, "
+                            "/synthesize_marks)")
         if formants is not None and not hasattr(_lib.lib(), "sbv2_stream_begin_request_formant_contour"):
             raise Sbv2Error("this library has no sbv2_stream_begin_request_formant_contour: a stream cannot carry a formant contour (it is never "
                             "served without)")

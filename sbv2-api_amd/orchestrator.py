@@ -89,6 +89,15 @@ class SynthesizeOptions:
     shifter of pitch_scale on the device (model.TokenPitch) and composes with the two scales.  A list of another length than the request's token
     count is refused with the expected count (TokenPitchError), before any GPU work.  Whole-signal routes only, refused on streams.  The marks
     then carry "pitch_edit": {"applied", "src_f0_hz"}.  None, or all zeros, is the calls and the bytes there always were.
+    token_gain (new; checked here) with token_gain_kind ("db" | "rms_db"), token_gain_ramp_ms ([0, 1000], default 10) and token_gain_max_db
+    ([0, 60], default 12): one value in dB per token of the request's live sentences, in the order of the speech marks.  "db" raises or lowers
+    the token by that many dB (within [-60, 60]; 0 leaves it alone); "rms_db" brings the token's RMS to that level in dBFS (within [-120, 0);
+    None or 0 leaves it alone), measured on the device behind the shifter.  Every factor is held within +- token_gain_max_db and changes
+    over token_gain_ramp_ms about a token boundary.  This layer turns dB into the ratios and linear RMS of model.TokenGain; the stage runs
+    on the native rows in front of the formatter, so every format, loudness target, limiter and marks block sees the edited signal, and it
+    can exceed full scale (tok_peak shows it; set limiter to bound it).  A list of another length than the request's token count is refused
+    with the expected count (TokenGainError), before any GPU work.  Whole-signal routes only, refused on streams.  The marks then carry
+    "volume_edit": {"applied_db", "src_rms_db"}.  None, or a list of zeros, is the calls and the bytes there always were.
     formant_scale in [0.5, 2] (new; checked here): the voice's formants are moved by that factor, which changes the perceived size, age and
     character of the speaker and leaves f0, the length and the token spans alone; it is made by the shifter of pitch_scale on the device
     (model.Formant: every grain is read at the scaled offset) and composes with pitch_scale, intonation_scale, pitch_track and token_pitch.
@@ -110,7 +119,9 @@ class SynthesizeOptions:
                  level_range=12.0, level_slew=3.0, level_hold=10, spectrum_mels=None, spectrum_fft=None, spectrum_hop=None, spectrum_fmin=0.0,
                  spectrum_fmax=None, formants=None, formants_hz=100, formants_max_hz=None, formants_order=None, formants_window=None,
                  formants_track=False, formants_candidates=None, formants_ref_hz=None, formants_freq_cost=None, formants_bw_cost=None,
-                 formants_jump_cost=None):
+                 formants_jump_cost=None, token_gain=None, token_gain_kind="db", token_gain_ramp_ms=10, token_gain_max_db=12):
+        self.token_gain, self.token_gain_kind, self.token_gain_ramp_ms, self.token_gain_max_db = check_token_gain(
+            token_gain, token_gain_kind, token_gain_ramp_ms, token_gain_max_db)
         self.formants, self.formants_hz, self.formants_max_hz = formants, formants_hz, formants_max_hz
         self.formants_order, self.formants_window = formants_order, formants_window
         self.formants_track, self.formants_candidates, self.formants_ref_hz = formants_track, formants_candidates, formants_ref_hz
@@ -333,6 +344,81 @@ def pitch_edit_dict(tp) -> dict:
             "src_f0_hz": [float(v) if v > 0 else None for v in tp.src_f0]}
 
 
+class TokenGainError(model.Sbv2Error):
+    """A token_gain the request itself is at fault for: a bad value, kind, ramp or ceiling, or a list that does not match the text's token count."""
+
+
+TOKEN_GAIN_RANGES = {"db": (-60.0, 60.0), "rms_db": (-120.0, 0.0)}   # this layer's; the library takes any non-negative ratio or RMS
+NATIVE_RATE = 44100   # the rows the stage works on
+
+
+def check_token_gain(values, kind, ramp_ms, max_db):
+    """(values as a list of floats / None entries, or None; kind; ramp_ms; max_db) under the checks SynthesizeOptions states; TokenGainError
+    otherwise."""
+    number = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+    if kind not in TOKEN_GAIN_RANGES:
+        raise TokenGainError(f"token_gain_kind must be \"db\" or \"rms_db\": {kind!r}")
+    if not number(ramp_ms) or not 0 <= ramp_ms <= 1000:   # (a NaN fails)
+        raise TokenGainError(f"token_gain_ramp_ms must be a number in [0, 1000]: {ramp_ms!r}")
+    if not number(max_db) or not 0 <= max_db <= 60:
+        raise TokenGainError(f"token_gain_max_db must be a number in [0, 60]: {max_db!r}")
+    if values is None:
+        return None, kind, ramp_ms, max_db
+    if isinstance(values, (str, bytes)) or not isinstance(values, (list, tuple, np.ndarray)):
+        raise TokenGainError(f"token_gain must be a list of numbers, one per token: {values!r}")
+    lo, hi = TOKEN_GAIN_RANGES[kind]
+    out = []
+    for t, v in enumerate(values):
+        if v is None and kind == "rms_db":
+            out.append(None)
+            continue
+        if not number(v) or not lo <= v <= hi:
+            raise TokenGainError(f"token_gain[{t}] must be 0 (not edited) or a number in [{lo}, {hi}] dB ({kind}): {v!r}")
+        out.append(float(v))
+    return out, kind, ramp_ms, max_db
+
+
+def token_gain_options(options, utts):
+    """The model.TokenGain of a request over its live sentences `utts` (None when no token is edited): dB become amplitude ratios and linear
+    RMS here, the ramp native samples.  A list of another length than the request's token count is refused with the expected count, edited or
+    not."""
+    v = getattr(options, "token_gain", None)
+    if v is None:
+        return None
+    n = sum(int(np.asarray(u["phones"]).size) for u in utts)
+    if len(v) != n:
+        raise TokenGainError(f"token_gain holds {len(v)} values but the text has {n} tokens: expected {n}, one per token of the speech marks")
+    if not any(x for x in v):   # (None and 0 leave a token alone)
+        return None
+    kind = getattr(options, "token_gain_kind", "db")
+    linear = [10.0 ** (x / 20.0) if x else 0.0 for x in v]
+    return model.TokenGain(linear, "ratio" if kind == "db" else "rms", int(round(getattr(options, "token_gain_ramp_ms", 10) * NATIVE_RATE / 1000.0)),
+                           10.0 ** (getattr(options, "token_gain_max_db", 12) / 20.0))
+
+
+def refuse_token_gain(options, what: str):
+    """token_gain where rows leave chunk by chunk: refused, with the routes that edit a whole signal."""
+    if getattr(options, "token_gain", None) is not None:
+        raise TokenGainError(f"token_gain edits a whole signal: {what} hands out chunks before a token's level is known, ask /synthesize, "
+                             "/synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
+
+
+def require_token_gain(pipe):
+    """A pipeline object whose fetch_request takes no token_gain cannot edit the volume: refused, never served unedited."""
+    import inspect
+    params = inspect.signature(pipe.fetch_request).parameters
+    if "token_gain" not in params and not any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
+        raise model.Sbv2Error(f"token_gain needs a pipeline whose fetch_request takes token_gain: {type(pipe).__name__} does not, and the "
+                              "request is not served unedited")
+
+
+def volume_edit_dict(tg) -> dict:
+    """The "volume_edit" block of a marks dict from a filled model.TokenGain: per token the factor used and its measured RMS behind the
+    shifter, both in dB (None for a token without energy)."""
+    db = lambda v: float(20.0 * np.log10(v)) if v > 0 else None
+    return {"applied_db": [db(v) for v in tg.applied], "src_rms_db": [db(v) for v in tg.src_rms]}
+
+
 def load_style(data: bytes) -> np.ndarray:
     d = json.loads(bytes(data).decode("utf-8"))
     shape = tuple(int(v) for v in d["shape"])
@@ -455,6 +541,7 @@ class RequestPlan:
         self.live = [i for i, _ in live]
         self.utts = with_assist([dict(s, style=style, sid=speaker_id) for _, s in live], options)   # (the pair on every row of the request)
         self.token_pitch = token_pitch_options(options, self.utts)   # (a list of the wrong length is refused before any GPU work)
+        self.token_gain = token_gain_options(options, self.utts)     # (likewise)
 
 
 def envelope_hop(options, rate: int) -> int:
@@ -847,9 +934,12 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
     dyn, voice, tp, fq = getattr(plan, "dynamics", None), voice_options(options), getattr(plan, "token_pitch", None), formant_options(options)
     if fq is not None:
         require_formant(pipe, options)
-    kw = {k: v for k, v in (("voice", voice), ("dynamics", dyn), ("token_pitch", tp), ("formant_scale", fq)) if v is not None}
+    tg = getattr(plan, "token_gain", None)
+    if tg is not None:
+        require_token_gain(pipe)
+    kw = {k: v for k, v in (("voice", voice), ("dynamics", dyn), ("token_pitch", tp), ("formant_scale", fq), ("token_gain", tg)) if v is not None}
     shifts = voice is not None or tp is not None or fq is not None
-    if ln is not None or not fmt.is_default or marks is not None or shifts:
+    if ln is not None or not fmt.is_default or marks is not None or shifts or tg is not None:
         # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
@@ -876,7 +966,8 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
             kw["track"] = track
         got = model.split_fetch_result(pipe.fetch_request(b, range(r0, r1), fmt, place, joined, **kw), marks=marks is not None,
                                        pitch=pitch is not None, dynamics=dyn is not None, token_pitch=tp is not None,
-                                       **({"spectrum": True} if spec is not None else {}), **({"formants": True} if fcon is not None else {}))
+                                       **({"spectrum": True} if spec is not None else {}), **({"formants": True} if fcon is not None else {}),
+                                       **({"token_gain": True} if tg is not None else {}))
         out, stats, dstats = got.signal, got.stats, got.dyn_stats
         if marks is not None:
             marks.append(marks_dict(plan.utts, plan.live, fmt, got.marks, got.pitch, **({"tracked": True} if "track" in kw and pitch is not None else {})))
@@ -886,6 +977,8 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
                 marks[-1]["pitch_edit"] = pitch_edit_dict(got.token_pitch)
             if fq is not None:
                 marks[-1]["formant_scale"] = fq
+            if tg is not None:
+                marks[-1]["volume_edit"] = volume_edit_dict(got.token_gain)
             if spec is not None:
                 marks[-1]["spectrum"] = spectrum_dict(got.spectrum)
             if fcon is not None:
@@ -1163,6 +1256,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     options = options or SynthesizeOptions()
     refuse_voice(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_token_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    refuse_token_gain(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_dynamics(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if formants:

@@ -61,6 +61,13 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     formants_hz = 100 (frames per second), formants_max_hz (null: min(5500, sample_rate / 2 - 50)), formants_order (null: 2 +
                     sample_rate // 1000, rounded up to even), formants_window (null: 25 ms).  A bad value answers 400; so does any of the five
                     fields on every other route, the stream routes included, naming /synthesize_marks.
+  token_gain = null (new; /synthesize and /synthesize_marks, batched or not; token_gain_kind = "db", token_gain_ramp_ms = 10, token_gain_max_db =
+                    12): one value in dB per token of the speech marks.  "db" raises or lowers the token by that much (0 = leave alone);
+                    "rms_db" brings the token's RMS to that level in dBFS (null or 0 = leave alone), measured on the device.  Every factor
+                    stays within +- token_gain_max_db and changes over token_gain_ramp_ms about a boundary.  Query /synthesize_marks for the
+                    tokens' levels, edit, ask again.  The marks then carry "volume_edit": {"applied_db", "src_rms_db"}.  The edit can exceed
+                    full scale: set limiter to bound it.  A bad value, or a list whose length differs from the text's token count, answers
+                    400 with the expected count; so does the field on the stream routes, naming /synthesize_marks.
   formants_track = false (new; /synthesize_marks only, batched or not, with formants in 1 to 5): the contour is tracked across frames on the
                     device: formants_candidates roots are kept per frame (null: formants + 3, at most 7 and order / 2) and one best path
                     assigns the formants to them, so a spurious root no longer shifts a frame by a slot.  formants_ref_hz (null: 500, 1500,
@@ -230,6 +237,10 @@ def make_app(holder, batching=None):
         token_pitch: Optional[List[float]] = None   # new: per token of the speech marks, 0 = not edited; /synthesize, /synthesize_marks; 400 on the stream routes
         token_pitch_kind: str = "hz"        # "hz": the token's target mean f0, [35, 1200]; "ratio": a factor on its f0, [0.5, 2]
         token_pitch_smooth: int = 2         # contour frames to each side over which the ratio changes, [0, 20]
+        token_gain: Optional[List[Optional[float]]] = None   # new: dB per token of the speech marks, 0 (or null with "rms_db") = not edited; /synthesize, /synthesize_marks; 400 on the stream routes
+        token_gain_kind: str = "db"         # "db": raise / lower the token by that many dB, [-60, 60]; "rms_db": the token's target RMS in dBFS, [-120, 0)
+        token_gain_ramp_ms: float = 10      # over how long the factor changes about a token boundary, [0, 1000]
+        token_gain_max_db: float = 12       # every factor is held within +- this many dB, [0, 60]
         assist_text: Optional[str] = None   # new: a second text whose DeBERTa features steer the delivery (upstream's assist_text); all four routes
         assist_text_weight: float = 0.7     # its weight, [0, 1] (upstream's default); 0 = none
         formant_scale: float = 1.0          # new: moves the voice's formants, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); 400 on the stream routes without voice_pivot_hz
@@ -306,6 +317,9 @@ def make_app(holder, batching=None):
                                               **({"token_pitch": req.token_pitch, "token_pitch_kind": req.token_pitch_kind,
                                                   "token_pitch_smooth": req.token_pitch_smooth}
                                                  if getattr(req, "token_pitch", None) is not None else {}),
+                                              **({"token_gain": req.token_gain, "token_gain_kind": req.token_gain_kind,
+                                                  "token_gain_ramp_ms": req.token_gain_ramp_ms, "token_gain_max_db": req.token_gain_max_db}
+                                                 if getattr(req, "token_gain", None) is not None else {}),
                                               **({"formant_scale": req.formant_scale} if getattr(req, "formant_scale", 1.0) != 1.0 else {}),
                                               **({"voice_pivot_hz": req.voice_pivot_hz} if getattr(req, "voice_pivot_hz", None) is not None else {}),
                                               **({k: getattr(req, k) for k in orchestrator.SPECTRUM_FIELDS}
@@ -332,7 +346,7 @@ def make_app(holder, batching=None):
             orchestrator.refuse_formants(req, "/synthesize")
             with lock:
                 wav = holder.easy_synthesize(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
-        except (orchestrator.TokenPitchError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -347,7 +361,7 @@ def make_app(holder, batching=None):
             with lock:                        # parse and queue only: the answer is awaited without it
                 fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching)
             wav = fut.result()
-        except (orchestrator.TokenPitchError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -366,7 +380,7 @@ def make_app(holder, batching=None):
                     fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching,
                                                          marks=True)
                 audio, marks = fut.result()
-        except (orchestrator.TokenPitchError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -386,6 +400,7 @@ def make_app(holder, batching=None):
             orchestrator.check_voice_pivot(getattr(req, "voice_pivot_hz", None))   # (a bad pivot is the request's fault)
             orchestrator.refuse_voice(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            orchestrator.refuse_token_gain(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.check_assist(None, getattr(req, "assist_text_weight", 0.7))   # (a stream takes an assist; a bad weight is the request's fault)
             if not formants:
