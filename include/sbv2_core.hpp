@@ -175,6 +175,40 @@ inline void fetch_request_token_gain(sbv2_pipeline* p, int64_t ticket, const sbv
                                                  dyn_stats, marks, pitch, spectrum, contour, formant_track, &c));
 }
 
+// Not in the reference: a parametric EQ of a fetched request (sbv2_eq in sbv2_hip.h states it).  bands: at most 8, run in the given order; kind
+// 0 high-pass, 1 low-pass, 2 low shelf, 3 high shelf, 4 peak.
+struct Eq {
+    struct Band {
+        int kind = 4;
+        double f0_hz = 1000.0, gain_db = 0.0, q = 0.70710678118654752;
+    };
+    std::vector<Band> bands;
+    sbv2_eq c() const {   // (more than 8 bands: n_bands says so and the library refuses it)
+        sbv2_eq e{};
+        e.n_bands = (int32_t)bands.size();
+        for (size_t i = 0; i < bands.size() && i < SBV2_EQ_MAX_BANDS; ++i)
+            e.kind[i] = bands[i].kind, e.f0_hz[i] = bands[i].f0_hz, e.gain_db[i] = bands[i].gain_db, e.q[i] = bands[i].q;
+        return e;
+    }
+};
+// sbv2_pipeline_fetch_request_eq with owned arrays: the widest request fetch, the EQ behind the token gain (tg NULL: none); everything else may
+// be NULL as in fetch_request_token_gain.
+inline void fetch_request_eq(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice, const sbv2_pitch_track* track,
+                             const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch, const sbv2_formant* formant, TokenGain* tg,
+                             const Eq& eq, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats = nullptr,
+                             double* dyn_stats = nullptr, sbv2_marks* marks = nullptr, sbv2_pitch* pitch = nullptr, sbv2_spectrum* spectrum = nullptr,
+                             sbv2_formant_contour* contour = nullptr, const sbv2_formant_track* formant_track = nullptr) {
+    sbv2_token_gain g{};
+    if (tg) {
+        tg->applied.assign(tg->values.size(), 1.0);
+        tg->src_rms.assign(tg->values.size(), 0.0);
+        g = sbv2_token_gain{tg->values.data(), (int64_t)tg->values.size(), tg->ramp, tg->max_ratio, tg->rms ? 1 : 0, 0, tg->applied.data(), tg->src_rms.data()};
+    }
+    const sbv2_eq e = eq.c();
+    check(sbv2_pipeline_fetch_request_eq(p, ticket, &req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count, stats, dyn_stats,
+                                         marks, pitch, spectrum, contour, formant_track, tg ? &g : nullptr, &e));
+}
+
 // Not in the reference: the formant scale of a fetched request (sbv2_formant in sbv2_hip.h states it).  sbv2_pipeline_fetch_request_formant with
 // owned arrays: fetch_request_token_pitch with formant_scale behind the table; 1 is exactly that call.
 inline void fetch_request_formant(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request& req, const sbv2_voice* voice,

@@ -917,6 +917,61 @@ int32_t sbv2_token_gain_tile(void);
 int sbv2_debug_token_gain(int device, const float* x, const int64_t* lens, int nrows, const int64_t* tok_counts, const int64_t* tok_ends,
                           const sbv2_token_gain* token_gain, float* y);
 
+/* ---- new: a parametric EQ of the voice.  The chain behind a request fetch shifts, scales, compresses, levels, limits, resamples and encodes,
+ * and until now nothing in it could change the TONE: the 300 Hz high-pass and presence lift of a call leg ahead of the G.711 quantiser, the
+ * high-pass that takes DC and rumble off a vocoder's output before it costs limiter depth, the shelf that gives back what formant_scale took,
+ * warmth, brightness, a notch near 6 - 8 kHz.  sbv2_eq is a cascade of up to 8 second-order sections the caller designs by kind, frequency,
+ * gain and Q.  The stage runs on the listed rows' native 44.1 kHz f32 samples behind the shifter (sbv2_voice, sbv2_token_pitch, sbv2_formant)
+ * and the token gain (sbv2_token_gain) and in front of the formatter: placement, delivered lengths, token spans, resampler, compressor,
+ * loudness, limiter, every sink and every marks block work unchanged on the filtered signal.
+ * Bands.  n_bands in [0, 8]; band b has kind[b] (0 high-pass, 1 low-pass, 2 low shelf, 3 high shelf, 4 peak), f0_hz[b] in [10, 0.45 44100],
+ *   gain_db[b] in [-24, 24] (read for kinds 2 - 4, must be 0 for kinds 0 - 1) and q[b] in [0.1, 20].  Frequencies are Hz of the signal,
+ *   whatever rate is delivered.
+ * Sections.  Each band is one biquad by the Audio-EQ-Cookbook (R. Bristow-Johnson) formulas at the native rate with w0 = 2 pi f0 / 44100,
+ *   alpha = sin(w0) / (2 q) and A = 10^(gain_db / 40), the shelves in their q form (2 sqrt(A) alpha), normalised to a0 = 1, computed on the
+ *   host in f64: sbv2_eq_design gives exactly the coefficients that run.
+ * Cascade.  Band by band in the given order, in transposed direct form II, in f64: per sample x and section (b0 b1 b2 a1 a2; s0 s1),
+ *   w = fma(b0, x, s0); s0 = fma(b1, x, fma(-a1, w, s1)); s1 = fma(b2, x, -a2 w); the next section's x is w.  Each row starts from zero
+ *   state at its head; the length is kept (the ringing past a row's end is dropped); nothing crosses rows and the silence between rows
+ *   stays silent.  y[n] = float(w_last[n]): the cast is the only f32 operation.
+ * Order of operations.  The device splits a row into tiles and a tile into lanes and joins them by the recurrence's own algebra (s_end =
+ *   M_m s_start + e, csrc/eq.h), so y64 differs from a sample-by-sample run in the last digits of an f64, four orders of magnitude under an
+ *   f32 ulp; the result depends on the samples and the table alone, never on the batch, and two equal calls give identical bytes.
+ * Identity.  eq == NULL, n_bands == 0, or a table in which every band is a shelf or peak with gain_db == 0 launches nothing: the fetch is
+ *   the call without, byte for byte.  A high-pass or low-pass is never the identity.
+ * Not built: the EQ on streams (sbv2_stream_*: the carry is just the 2 n_bands doubles per row) and on sbv2_node_*, a de-esser (the next
+ *   dynamics stage needs this filter as its side chain), linear-phase filters, filtering at the delivered rate instead of the native one. */
+#define SBV2_EQ_MAX_BANDS 8
+typedef struct sbv2_eq {
+    int32_t n_bands;                      /* [0, 8] */
+    int32_t reserved;                     /* must be 0 */
+    int32_t kind[SBV2_EQ_MAX_BANDS];      /* 0 high-pass, 1 low-pass, 2 low shelf, 3 high shelf, 4 peak */
+    double f0_hz[SBV2_EQ_MAX_BANDS];      /* [10, 0.45 * 44100] */
+    double gain_db[SBV2_EQ_MAX_BANDS];    /* [-24, 24]; 0 for kinds 0 - 1 */
+    double q[SBV2_EQ_MAX_BANDS];          /* [0.1, 20] */
+} sbv2_eq;
+/* Host only: THE check of a table and its design at `rate` (the fetch uses 44100; f0_hz is then bounded by 0.45 rate).  coef (NULL: check
+ * only) receives [5 n_bands]: b0 b1 b2 a1 a2 per band, a0 = 1.  Refused, each by name: n_bands outside [0, 8], a kind, frequency, gain or Q
+ * out of range, a NaN (it fails every comparison), a gain on kinds 0 - 1, reserved != 0. */
+int sbv2_eq_design(const sbv2_eq* eq, int rate, double* coef);
+/* sbv2_pipeline_fetch_request_token_gain with the listed rows filtered.  eq == NULL, or a table that is the identity (above), is exactly
+ * that call.  Otherwise three launches (k_eq_tiles, k_eq_carry, k_eq_apply) behind the token gain's, no atomics, no synchronisation beyond
+ * the fetch's one.  The run's PCM is only read: a later fetch without a table is the unfiltered signal.  Token spans and delivered lengths
+ * are those of the call without.  Refused with nothing written and nothing enqueued: whatever sbv2_eq_design refuses, and everything that
+ * call refuses. */
+int sbv2_pipeline_fetch_request_eq(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                   const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                   const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                   double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                   sbv2_formant_contour* contour, const sbv2_formant_track* formant_track, const sbv2_token_gain* token_gain,
+                                   const sbv2_eq* eq);
+/* Samples of one row per workgroup of the EQ's kernels (256 lanes of sbv2_eq_tile() / 256 samples each; tests aim at both edges). */
+int32_t sbv2_eq_tile(void);
+/* Test hook: the stage on host rows x laid back to back (lens [nrows]; a row of a length that is no multiple of 4 leaves the next one's head
+ * off the 16-byte grid), always through the kernels (n_bands >= 1; a table of 0 dB bands runs too).  y receives the filtered rows, laid out
+ * as x; y64 (NULL or as x) the f64 values before the cast.  Everything is checked before any device call. */
+int sbv2_debug_eq(int device, const float* x, const int64_t* lens, int nrows, const sbv2_eq* eq, float* y, double* y64);
+
 /* Test hook: the device limiter on host f64 signals (as sbv2_debug_loudness): out_x receives x (f64, laid out as the input), stats 6
  * doubles per signal. */
 int sbv2_debug_limiter(int device, const double* x, const int64_t* lens, int nsig, int32_t sample_rate, const sbv2_limiter* lim,

@@ -130,6 +130,12 @@ class Sbv2TokenGain(C.Structure):
                 ("reserved", C.c_int32), ("applied", C.POINTER(C.c_double)), ("src_rms", C.POINTER(C.c_double))]
 
 
+class Sbv2Eq(C.Structure):
+    """struct sbv2_eq (include/sbv2_hip.h)."""
+    _fields_ = [("n_bands", C.c_int32), ("reserved", C.c_int32), ("kind", C.c_int32 * 8), ("f0_hz", C.c_double * 8), ("gain_db", C.c_double * 8),
+                ("q", C.c_double * 8)]
+
+
 class Sbv2Formant(C.Structure):
     """struct sbv2_formant (include/sbv2_hip.h)."""
     _fields_ = [("formant_scale", C.c_double), ("reserved", C.c_double)]
@@ -265,6 +271,15 @@ SYMBOLS = {
                                                          C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch),
                                                          C.POINTER(Sbv2Spectrum), C.POINTER(Sbv2FormantContour), C.POINTER(Sbv2FormantTrack),
                                                          C.POINTER(Sbv2TokenGain)]),
+    "sbv2_pipeline_fetch_request_eq": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(Sbv2FetchRequest), C.POINTER(Sbv2Voice),
+                                                 C.POINTER(Sbv2PitchTrack), C.POINTER(Sbv2Dynamics), C.POINTER(Sbv2TokenPitch),
+                                                 C.POINTER(Sbv2Formant), C.c_void_p, C.c_int64, i64p, C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), C.POINTER(Sbv2Marks), C.POINTER(Sbv2Pitch),
+                                                 C.POINTER(Sbv2Spectrum), C.POINTER(Sbv2FormantContour), C.POINTER(Sbv2FormantTrack),
+                                                 C.POINTER(Sbv2TokenGain), C.POINTER(Sbv2Eq)]),
+    "sbv2_eq_design": (C.c_int, [C.POINTER(Sbv2Eq), C.c_int, C.POINTER(C.c_double)]),
+    "sbv2_eq_tile": (C.c_int32, []),
+    "sbv2_debug_eq": (C.c_int, [C.c_int, f32p, i64p, C.c_int, C.POINTER(Sbv2Eq), f32p, C.POINTER(C.c_double)]),
     "sbv2_token_gain_tile": (C.c_int32, []),
     "sbv2_debug_token_gain": (C.c_int, [C.c_int, f32p, i64p, C.c_int, i64p, i64p, C.POINTER(Sbv2TokenGain), f32p]),
     "sbv2_formant_track_check": (C.c_int, [C.c_int32, C.POINTER(Sbv2FormantContour), C.POINTER(Sbv2FormantTrack)]),

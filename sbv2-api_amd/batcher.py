@@ -193,7 +193,7 @@ class RequestBatcher:
                         continue
                     if (pcm is None and req.plan.gain is None and req.plan.fmt.is_default and orchestrator.voice_options(req.plan.options) is None
                             and getattr(req.plan, "token_pitch", None) is None and getattr(req.plan, "token_gain", None) is None
-                            and orchestrator.formant_options(req.plan.options) is None):
+                            and orchestrator.formant_options(req.plan.options) is None and orchestrator.eq_options(req.plan.options) is None):
                         pcm = self.pipe.fetch(b)   # the plain f32 requests of a run share one fetch
                     req.future.set_result(orchestrator.finish_request(self.pipe, b, r0, r1, req.plan, pcm=pcm))
                 except Exception as e:

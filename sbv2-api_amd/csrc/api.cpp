@@ -467,6 +467,16 @@ int32_t sbv2_dynamics_tile(void) { return Dynamics::kTile; }
 
 int32_t sbv2_token_gain_tile(void) { return TokenGain::kTile; }
 
+int32_t sbv2_eq_tile(void) { return Eq::kTile; }
+
+int sbv2_eq_design(const sbv2_eq* eq, int rate, double* coef) {
+    API_BEGIN
+    SBV2_REQUIRE(eq, "bad arguments");
+    const EqSpec sp = eq_spec(eq->n_bands, eq->kind, eq->f0_hz, eq->gain_db, eq->q, eq->reserved, rate);
+    if (coef) std::memcpy(coef, sp.coef, sizeof(double) * 5 * (size_t)sp.n_bands);
+    API_END
+}
+
 int sbv2_pitch_lags(int32_t sample_rate, double f0_min, double f0_max, int32_t* tau_min, int32_t* tau_max) {
     API_BEGIN
     SBV2_REQUIRE(tau_min && tau_max, "bad arguments");

@@ -8,6 +8,7 @@
 
 #include "../../include/sbv2_hip.h"
 #include "dynamics.h"
+#include "eq.h"
 #include "flac_encode.h"
 #include "formant_track.h"
 #include "formants.h"
@@ -48,6 +49,7 @@ struct OutputChain {
     FormantTrack formant_track;   // ... tracked across frames (fetch_request_formant_track only)
     Voice voice;       // pitch / intonation scale of the listed rows, in front of the formatter (fetch_request_voice only)
     TokenGain token_gain;   // per-token volume of the listed rows, behind the shifter (fetch_request_token_gain only)
+    Eq eq;             // parametric EQ of the listed rows, behind the token gain (fetch_request_eq only)
     Track track;       // the best path through the delivered contour's candidates (fetch_request_tracked only; the shifter has its own)
 };
 struct sbv2_pipeline {

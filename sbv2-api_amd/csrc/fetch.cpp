@@ -44,7 +44,7 @@ struct FetchArgs {
 // contour: the formant contour (formants.h) of the same samples, one more launch again.  formant_track (with contour): the stage keeps the
 // track's candidates per frame and the tracker (formant_track.h) chooses one path through them, two more launches.
 // token_gain (the identity: nothing): the listed rows' tokens are scaled (TokenGain, token_gain.h) behind the shifter, into the stage's own buffer,
-// and the pieces point there.
+// and the pieces point there.  eq (the identity: nothing): the listed rows are filtered (Eq, eq.h) behind that, into the stage's own buffer again.
 struct FetchStages {
     const int32_t* utts = nullptr;   // the rows of the one signal (with place[k] belonging to row utts[k]); NULL: no request, all of the run
     int n_utts = 0;
@@ -60,6 +60,7 @@ struct FetchStages {
     sbv2_formant_contour* contour = nullptr;
     const sbv2_formant_track* formant_track = nullptr;
     const sbv2_token_gain* token_gain = nullptr;
+    const sbv2_eq* eq = nullptr;
 };
 // ... and once everything about them that needs no run has been checked (check_stages).  Default: no stage.
 struct CheckedStages : FetchStages {
@@ -72,6 +73,7 @@ struct CheckedStages : FetchStages {
     FormantContourSpec fcs;   // (with a formant track: n_formants = its candidates)
     FormantTrackSpec fts;
     TokenGainSpec tgs;        // (tgs.edits: some token's factor can differ from 1)
+    EqSpec eqs;               // (eqs.filters: some band is not the identity)
     bool edit = false, scale = false, compress = false;   // a token is edited; the formants move; the compressor is not the identity
     bool shifts() const { return (voice && !vs.identity()) || edit || scale; }   // the shifter has something to do
 };
@@ -157,6 +159,7 @@ CheckedStages check_stages(const sbv2_fetch_request* req, const FetchStages& st)
     cs.edit = st.token_pitch && check_token_pitch_static(st.token_pitch, cs.vs);
     if (st.formant) cs.fs = check_formant_static(st.formant, cs.vs);
     if (const sbv2_token_gain* g = st.token_gain) cs.tgs = token_gain_spec(g->value, g->n_tokens, g->kind, g->ramp, g->max_ratio, g->reserved);
+    if (const sbv2_eq* e = st.eq) cs.eqs = eq_spec(e->n_bands, e->kind, e->f0_hz, e->gain_db, e->q, e->reserved, kNativeRate);
     cs.scale = st.formant && !cs.fs.identity();
     if (st.track) {
         cs.ts = check_track_static(st.track);
@@ -277,6 +280,7 @@ struct FetchPlan {
     std::vector<int64_t> tok_counts, tok_ends;   // (an edit only) per listed row: its tokens; per token: the native sample it ends at
     bool shift = false;                          // the shifter runs
     bool tgain = false;                          // the token gain runs
+    bool eq = false;                             // the EQ runs
 };
 FetchPlan plan_fetch(const FetchArgs& a, const CheckedStages& cs) {
     FetchPlan pl;
@@ -330,6 +334,7 @@ FetchPlan plan_fetch(const FetchArgs& a, const CheckedStages& cs) {
     }
     pl.shift = cs.shifts() && cs.n_utts > 0;
     pl.tgain = cs.tgs.edits && cs.n_utts > 0;
+    pl.eq = cs.eqs.filters && cs.n_utts > 0;
     return pl;
 }
 
@@ -361,6 +366,13 @@ std::vector<int64_t> enqueue_fetch(const FetchArgs& a, const CheckedStages& cs, 
         for (int k = 0; k < cs.n_utts; ++k) rows[k] = TokenGainRow{vm.pcm_offs()[cs.utts[k]], vm.pcm_lens()[cs.utts[k]]};
         const float* scaled = c.token_gain.run(base, vm.pcm_total(), rows.data(), cs.n_utts, pl.tok_counts.data(), pl.tok_ends.data(), cs.tgs, s);
         for (FmtPiece& pc : pl.pieces) pc.src = scaled + (pc.src - base);
+        base = scaled;
+    }
+    if (pl.eq) {   // ... and filtered, read where the formatter would have read them
+        std::vector<EqRow> rows((size_t)cs.n_utts);
+        for (int k = 0; k < cs.n_utts; ++k) rows[k] = EqRow{vm.pcm_offs()[cs.utts[k]], vm.pcm_lens()[cs.utts[k]]};
+        const float* filtered = c.eq.run(base, vm.pcm_total(), rows.data(), cs.n_utts, cs.eqs, s);
+        for (FmtPiece& pc : pl.pieces) pc.src = filtered + (pc.src - base);
     }
     if (a.sink == Sink::kPcm && a.gain.kind == FetchGain::kNone && spec.identity() && !a.place) {   // the bytes of sbv2_pipeline_fetch_pcm_ticket
         HIP_CHECK(hipMemcpyAsync(a.dst, vm.pcm_device(), sizeof(float) * (size_t)vm.pcm_total(), hipMemcpyDeviceToHost, s));
@@ -513,25 +525,34 @@ int sbv2_pipeline_fetch_flac_limited(sbv2_pipeline* p, int64_t ticket, const sbv
 }
 
 // The widest request fetch; each narrower symbol below is exactly this call with NULL for what it lacks.
-int sbv2_pipeline_fetch_request_token_gain(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
-                                           const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
-                                           const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
-                                           double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
-                                           sbv2_formant_contour* contour, const sbv2_formant_track* formant_track,
-                                           const sbv2_token_gain* token_gain) {
+int sbv2_pipeline_fetch_request_eq(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                   const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                   const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                   double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                   sbv2_formant_contour* contour, const sbv2_formant_track* formant_track, const sbv2_token_gain* token_gain,
+                                   const sbv2_eq* eq) {
     API_BEGIN
     static const int32_t no_rows[1] = {0};   // (a request of no rows is still a request: one empty joined signal)
     static const int64_t no_place[1] = {0};
     const bool rows = req && req->n_utts > 0;   // (what is wrong with req is refused in its turn, by check_stages)
     const CheckedStages cs = check_stages(
         req, FetchStages{rows ? req->utts : no_rows, rows ? req->n_utts : 0, voice, track, dynamics, dyn_stats, token_pitch, formant, marks, pitch,
-                         spectrum, contour, formant_track, token_gain});
+                         spectrum, contour, formant_track, token_gain, eq});
     const FetchGain gain = req->limiter    ? FetchGain{FetchGain::kLimiter, nullptr, req->limiter}
                            : req->loudness ? FetchGain{FetchGain::kLoudness, req->loudness, nullptr}
                                            : FetchGain();
     const Sink sink = req->flac ? Sink::kFlac : Sink::kPcm;
     fetch_formatted({p, ticket, req->fmt, gain, rows ? req->place : no_place, req->joined_len, sink, dst, capacity_bytes, out_count, stats}, cs);
     API_END
+}
+int sbv2_pipeline_fetch_request_token_gain(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
+                                           const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,
+                                           const sbv2_formant* formant, void* dst, int64_t capacity_bytes, int64_t* out_count, double* stats,
+                                           double* dyn_stats, sbv2_marks* marks, sbv2_pitch* pitch, sbv2_spectrum* spectrum,
+                                           sbv2_formant_contour* contour, const sbv2_formant_track* formant_track,
+                                           const sbv2_token_gain* token_gain) {
+    return sbv2_pipeline_fetch_request_eq(p, ticket, req, voice, track, dynamics, token_pitch, formant, dst, capacity_bytes, out_count, stats, dyn_stats,
+                                          marks, pitch, spectrum, contour, formant_track, token_gain, nullptr);
 }
 int sbv2_pipeline_fetch_request_formant_track(sbv2_pipeline* p, int64_t ticket, const sbv2_fetch_request* req, const sbv2_voice* voice,
                                               const sbv2_pitch_track* track, const sbv2_dynamics* dynamics, const sbv2_token_pitch* token_pitch,

@@ -2326,6 +2326,31 @@ int sbv2_debug_token_gain(int device, const float* x, const int64_t* lens, int n
     API_END
 }
 
+// The EQ (Eq, eq.hip) on host rows laid back to back, always through its kernels.  The table here, the rows in Eq::run, all before any device
+// call; nothing is written when the call fails.
+int sbv2_debug_eq(int device, const float* x, const int64_t* lens, int nrows, const sbv2_eq* eq, float* y, double* y64) {
+    API_BEGIN
+    SBV2_REQUIRE(eq && nrows >= 0 && (nrows == 0 || lens), "bad arguments");
+    const EqSpec sp = eq_spec(eq->n_bands, eq->kind, eq->f0_hz, eq->gain_db, eq->q, eq->reserved, kNativeRate);
+    SBV2_REQUIRE(sp.n_bands >= 1, "sbv2_debug_eq needs sbv2_eq.n_bands >= 1: without a band there is no kernel to run");
+    std::vector<EqRow> rows((size_t)nrows);
+    int64_t total = 0;
+    for (int i = 0; i < nrows; ++i) {
+        SBV2_REQUIRE(lens[i] >= 0 && lens[i] < (1 << 30) && total < (1 << 30), "bad length of row " + std::to_string(i));
+        rows[i] = EqRow{total, lens[i]};
+        total += lens[i];
+    }
+    SBV2_REQUIRE(total == 0 || (x && y), "bad arguments");
+    HIP_CHECK(hipSetDevice(device));
+    DevMem dx(x, sizeof(float) * (size_t)total), wide(y64 ? sizeof(double) * (size_t)total : 0);
+    Eq eqs;
+    const float* dy = eqs.run(dx.f(), total, rows.data(), nrows, sp, nullptr, y64 ? static_cast<double*>(wide.p) : nullptr);
+    HIP_CHECK(hipStreamSynchronize(nullptr));
+    if (total) HIP_CHECK(hipMemcpy(y, dy, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost));
+    if (total && y64) HIP_CHECK(hipMemcpy(y64, wide.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost));
+    API_END
+}
+
 // The tracker (Track, track.hip) on host samples, or on the caller's candidate table alone.  Everything is checked before any device call;
 // nothing is written when the call fails.
 int sbv2_debug_pitch_track(int device, const void* x, int encoding, int64_t n, int32_t sample_rate, sbv2_pitch* pitch, const sbv2_pitch_track* track,

@@ -964,6 +964,61 @@ def debug_token_gain(rows, tok_ends, token_gain: TokenGain, device: int = 0):
     return [a.copy() for a in np.split(y[:-1], np.cumsum([r.size for r in rows])[:-1])] if rows else [], token_gain
 
 
+class Eq:
+    """Parametric EQ of a fetched request (struct sbv2_eq, include/sbv2_hip.h states it): bands, at most 8, each (kind, f0_hz, gain_db, q) or a
+    dict of those names; kind is "highpass" | "lowpass" | "lowshelf" | "highshelf" | "peak" or its number 0 .. 4; gain_db defaults to 0 and q
+    to 1 / sqrt(2).  The cascade runs in the given order, in f64, on the native 44.1 kHz rows.  Ranges are checked by the library."""
+    KINDS = {"highpass": 0, "lowpass": 1, "lowshelf": 2, "highshelf": 3, "peak": 4}
+
+    def __init__(self, bands=()):
+        self.bands = []
+        for b in bands:
+            if isinstance(b, dict):
+                b = (b["kind"], b["f0_hz"], b.get("gain_db", 0.0), b.get("q", 0.5 ** 0.5))
+            kind, f0, gain, q = (tuple(b) + (0.0, 0.5 ** 0.5))[:4]
+            if isinstance(kind, str) and kind not in self.KINDS:
+                raise Sbv2Error(f"eq kind must be one of {sorted(self.KINDS)}, not {kind!r}")
+            self.bands.append((self.KINDS[kind] if isinstance(kind, str) else int(kind), float(f0), float(gain), float(q)))
+        if len(self.bands) > 8:
+            raise Sbv2Error(f"an eq holds at most 8 bands, not {len(self.bands)}")
+
+    def c_struct(self, reserved: int = 0):
+        c = _lib.Sbv2Eq(len(self.bands), reserved)
+        for i, (kind, f0, gain, q) in enumerate(self.bands):
+            c.kind[i], c.f0_hz[i], c.gain_db[i], c.q[i] = kind, f0, gain, q
+        return c
+
+    def design(self, rate: int = 44100) -> np.ndarray:
+        """[n_bands, 5]: b0 b1 b2 a1 a2 of every band at `rate`, a0 = 1 (sbv2_eq_design: the coefficients that run; it is the checker too)."""
+        coef = np.zeros(max(5 * len(self.bands), 1), np.float64)
+        c = self.c_struct()
+        check(_lib.lib().sbv2_eq_design(C.byref(c), int(rate), _f64p(coef)))
+        return coef[:5 * len(self.bands)].reshape(-1, 5)
+
+    def __repr__(self):
+        return f"Eq({self.bands})"
+
+
+def eq_tile() -> int:
+    """Samples of one row per workgroup of the EQ's kernels (sbv2_eq_tile); a lane walks eq_tile() // 256 of them."""
+    return int(_lib.lib().sbv2_eq_tile())
+
+
+def debug_eq(rows, eq: Eq, device: int = 0, wide: bool = True):
+    """Test hook: the EQ on host rows (sbv2_debug_eq; rows: float32 arrays, laid back to back on the device) -> (the filtered rows as float32,
+    the same as float64 before the cast, or None without wide).  Always through the kernels."""
+    rows = [np.ascontiguousarray(r, np.float32).reshape(-1) for r in rows]
+    x = np.concatenate(rows + [np.zeros(1, np.float32)])   # (never an empty buffer)
+    lens = _i64([r.size for r in rows] or [0])[0]
+    y, y64 = np.zeros_like(x), np.zeros(x.size, np.float64)
+    c = eq.c_struct()
+    check(_lib.lib().sbv2_debug_eq(int(device), x.ctypes.data_as(_lib.f32p), lens.ctypes.data_as(_lib.i64p), len(rows), C.byref(c),
+                                   y.ctypes.data_as(_lib.f32p), _f64p(y64) if wide else None))
+    cut = np.cumsum([r.size for r in rows])[:-1]
+    split = lambda a: [p.copy() for p in np.split(a[:-1], cut)] if rows else []
+    return split(y), split(y64) if wide else None
+
+
 class Formant:
     """Formant scale of a fetched request (struct sbv2_formant, include/sbv2_hip.h states it): every grain of the shifter is read at
     formant_scale times its offset, which moves the spectral envelope by that factor and leaves f0, the marks and the length alone.
@@ -1614,7 +1669,7 @@ class Pipeline:
 
     def fetch_request(self, b, rows, fmt: PcmFormat, place, joined_len, gain=None, flac=False, marks=False, env_hop=0, levels=True, pitch=None,
                       voice=None, track=None, dynamics=None, token_pitch=None, formant_scale=1.0, spectrum=None, formants=None,
-                      formant_track=None, token_gain=None):
+                      formant_track=None, token_gain=None, eq=None):
         """(signal, stats): ONE signal made of the listed rows of run `b` only, row rows[k] starting at place[k] on a silent timeline of
         joined_len native samples, through the same output chain as the fetches above.  gain: None, a Loudness
         or a Limiter (stats [3] / [6], else None); flac: the s16 signal as one FLAC stream (bytes) instead of samples.  The run's PCM is only
@@ -1650,7 +1705,11 @@ class Pipeline:
         token_gain: a TokenGain -> the listed rows' tokens are scaled on the device behind the shifter and in front of everything else (one
         call of sbv2_pipeline_fetch_request_token_gain, the widest of the C symbols), and the returned tuple gains a last element: that
         TokenGain with applied [n] and src_rms [n] filled.  A table that is the identity: the bytes of the call without.  A library without
-        the symbol is refused, never served unedited."""
+        the symbol is refused, never served unedited.
+        eq: an Eq -> the listed rows are filtered on the device behind the shifter and the token gain and in front of everything else (one
+        call of sbv2_pipeline_fetch_request_eq, the widest of the C symbols).  The returned tuple is that of the call without, as with
+        formant_scale.  A table that is the identity (no band, or only shelves and peaks at 0 dB): the bytes of the call without.  A library
+        without the symbol is refused, never served unfiltered."""
         if formant_track is not None and formants is None:
             raise Sbv2Error("a formant track needs formants (a FormantContour) to deliver its values in")
         fm = None if formant_scale == 1.0 else Formant(formant_scale)   # (a NaN is carried on and refused by the library)
@@ -1688,7 +1747,14 @@ class Pipeline:
         opt = lambda o: ref(o.c if o is not None else None)
         args = (self.h, b.ticket, C.byref(req), opt(voice), opt(track), opt(dynamics), ref(ctp), opt(fm), dst.ctypes.data_as(C.c_void_p), dst.nbytes,
                 C.byref(got), _f64p(stats) if nstats else None, _f64p(dst_stats) if dst_stats is not None else None, ref(cm), ref(cp))
-        if token_gain is not None:
+        if eq is not None:
+            fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_eq", None)
+            if fn is None:
+                raise Sbv2Error("an eq needs a library with sbv2_pipeline_fetch_request_eq: the request is not served unfiltered")
+            cft = formant_track.c if formant_track is not None else None
+            ceq = eq.c_struct()
+            check(fn(*args, ref(csp), ref(cfc), ref(cft), ref(ctg), C.byref(ceq)))
+        elif token_gain is not None:
             fn = getattr(_lib.lib(), "sbv2_pipeline_fetch_request_token_gain", None)
             if fn is None:
                 raise Sbv2Error("a token gain needs a library with sbv2_pipeline_fetch_request_token_gain: the request is not served unedited")

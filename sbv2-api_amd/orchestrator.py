@@ -98,6 +98,12 @@ class SynthesizeOptions:
     can exceed full scale (tok_peak shows it; set limiter to bound it).  A list of another length than the request's token count is refused
     with the expected count (TokenGainError), before any GPU work.  Whole-signal routes only, refused on streams.  The marks then carry
     "volume_edit": {"applied_db", "src_rms_db"}.  None, or a list of zeros, is the calls and the bytes there always were.
+    eq (new; checked here): a parametric EQ of the voice, a list of at most 8 bands {"kind": "highpass" | "lowpass" | "lowshelf" | "highshelf"
+    | "peak", "f0_hz" in [10, 19845], "gain_db" in [-24, 24] (shelves and peaks; default 0), "q" in [0.1, 20] (default 1 / sqrt(2))}, run
+    in the given order as a cascade of biquads in f64 on the device (model.Eq), on the native rows behind the shifter and the token gain and
+    in front of the formatter: every format, compressor, loudness target, limiter, sink and marks block sees the filtered signal.
+    Frequencies are Hz of the signal, whatever rate is delivered.  Whole-signal routes only, refused on streams.  The marks then carry
+    "eq": {"bands": [...]}, echoing what ran.  None, no band, or only shelves and peaks at 0 dB, is the calls and the bytes there always were.
     formant_scale in [0.5, 2] (new; checked here): the voice's formants are moved by that factor, which changes the perceived size, age and
     character of the speaker and leaves f0, the length and the token spans alone; it is made by the shifter of pitch_scale on the device
     (model.Formant: every grain is read at the scaled offset) and composes with pitch_scale, intonation_scale, pitch_track and token_pitch.
@@ -119,7 +125,8 @@ class SynthesizeOptions:
                  level_range=12.0, level_slew=3.0, level_hold=10, spectrum_mels=None, spectrum_fft=None, spectrum_hop=None, spectrum_fmin=0.0,
                  spectrum_fmax=None, formants=None, formants_hz=100, formants_max_hz=None, formants_order=None, formants_window=None,
                  formants_track=False, formants_candidates=None, formants_ref_hz=None, formants_freq_cost=None, formants_bw_cost=None,
-                 formants_jump_cost=None, token_gain=None, token_gain_kind="db", token_gain_ramp_ms=10, token_gain_max_db=12):
+                 formants_jump_cost=None, token_gain=None, token_gain_kind="db", token_gain_ramp_ms=10, token_gain_max_db=12, eq=None):
+        self.eq = check_eq(eq)
         self.token_gain, self.token_gain_kind, self.token_gain_ramp_ms, self.token_gain_max_db = check_token_gain(
             token_gain, token_gain_kind, token_gain_ramp_ms, token_gain_max_db)
         self.formants, self.formants_hz, self.formants_max_hz = formants, formants_hz, formants_max_hz
@@ -417,6 +424,69 @@ def volume_edit_dict(tg) -> dict:
     shifter, both in dB (None for a token without energy)."""
     db = lambda v: float(20.0 * np.log10(v)) if v > 0 else None
     return {"applied_db": [db(v) for v in tg.applied], "src_rms_db": [db(v) for v in tg.src_rms]}
+
+
+class EqError(model.Sbv2Error):
+    """An eq the request itself is at fault for: a bad band, kind, frequency, gain or Q."""
+
+
+EQ_MAX_BANDS = 8
+EQ_RANGES = {"f0_hz": (10.0, 0.45 * NATIVE_RATE), "gain_db": (-24.0, 24.0), "q": (0.1, 20.0)}   # those of sbv2_eq
+
+
+def check_eq(bands):
+    """eq as a list of complete band dicts {"kind", "f0_hz", "gain_db", "q"} (gain_db defaults to 0, q to 1 / sqrt(2)), or None, under the
+    checks SynthesizeOptions states; EqError, naming the field, otherwise."""
+    number = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+    if bands is None:
+        return None
+    if isinstance(bands, (str, bytes, dict)) or not isinstance(bands, (list, tuple)):
+        raise EqError(f"eq must be a list of bands, each {{\"kind\", \"f0_hz\", \"gain_db\", \"q\"}}: {bands!r}")
+    if len(bands) > EQ_MAX_BANDS:
+        raise EqError(f"eq holds at most {EQ_MAX_BANDS} bands: {len(bands)}")
+    out = []
+    for i, b in enumerate(bands):
+        if not isinstance(b, dict):
+            raise EqError(f"eq[{i}] must be an object with \"kind\" and \"f0_hz\": {b!r}")
+        unknown = set(b) - {"kind", "f0_hz", "gain_db", "q"}
+        if unknown:
+            raise EqError(f"eq[{i}] has unknown fields {sorted(unknown)}")
+        kind = b.get("kind")
+        if not isinstance(kind, str) or kind not in model.Eq.KINDS:
+            raise EqError(f"eq[{i}].kind must be one of {sorted(model.Eq.KINDS)}: {kind!r}")
+        band = {"kind": kind, "f0_hz": b.get("f0_hz"), "gain_db": b.get("gain_db", 0.0), "q": b.get("q", 0.5 ** 0.5)}
+        for name, (lo, hi) in EQ_RANGES.items():
+            if not number(band[name]) or not lo <= band[name] <= hi:   # (a NaN fails)
+                raise EqError(f"eq[{i}].{name} must be a number in [{lo}, {hi}]: {band[name]!r}")
+            band[name] = float(band[name])
+        if kind in ("highpass", "lowpass") and band["gain_db"] != 0.0:
+            raise EqError(f"eq[{i}].gain_db must be 0 for a {kind}: {band['gain_db']!r}")
+        out.append(band)
+    return out
+
+
+def eq_options(options):
+    """The model.Eq of a request (None when no band filters: without bands, or with shelves and peaks at 0 dB only)."""
+    bands = getattr(options, "eq", None)
+    if not bands or all(b["kind"] not in ("highpass", "lowpass") and b["gain_db"] == 0.0 for b in bands):
+        return None
+    return model.Eq(bands)
+
+
+def refuse_eq(options, what: str):
+    """eq where rows leave chunk by chunk: refused, with the routes that filter a whole signal."""
+    if getattr(options, "eq", None) is not None:
+        raise EqError(f"eq filters a whole signal: {what} does not carry the filter's state from chunk to chunk yet, ask /synthesize, "
+                      "/synthesize_marks (easy_synthesize, easy_synthesize_marks) or the batcher instead")
+
+
+def require_eq(pipe):
+    """A pipeline object whose fetch_request takes no eq cannot filter: refused, never served unfiltered."""
+    import inspect
+    params = inspect.signature(pipe.fetch_request).parameters
+    if "eq" not in params and not any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
+        raise model.Sbv2Error(f"eq needs a pipeline whose fetch_request takes eq: {type(pipe).__name__} does not, and the request is not "
+                              "served unfiltered")
 
 
 def load_style(data: bytes) -> np.ndarray:
@@ -937,9 +1007,13 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
     tg = getattr(plan, "token_gain", None)
     if tg is not None:
         require_token_gain(pipe)
-    kw = {k: v for k, v in (("voice", voice), ("dynamics", dyn), ("token_pitch", tp), ("formant_scale", fq), ("token_gain", tg)) if v is not None}
+    eq = eq_options(options)
+    if eq is not None:
+        require_eq(pipe)
+    kw = {k: v for k, v in (("voice", voice), ("dynamics", dyn), ("token_pitch", tp), ("formant_scale", fq), ("token_gain", tg), ("eq", eq))
+          if v is not None}
     shifts = voice is not None or tp is not None or fq is not None
-    if ln is not None or not fmt.is_default or marks is not None or shifts or tg is not None:
+    if ln is not None or not fmt.is_default or marks is not None or shifts or tg is not None or eq is not None:
         # ONE fetch of the request's rows: the WAV signal below, resampled / normalised / quantised as a whole on the device; with a loudness target
         # it is measured and scaled (or limited) as a whole too (the gates leave the silent gaps out); flac: its s16 form encoded on the device
         place, joined = joined_placement(lens, plan.live, plan.n_lines, options.split_sentences)
@@ -979,6 +1053,8 @@ def finish_request(pipe: "model.Pipeline", b, r0: int, r1: int, plan: RequestPla
                 marks[-1]["formant_scale"] = fq
             if tg is not None:
                 marks[-1]["volume_edit"] = volume_edit_dict(got.token_gain)
+            if eq is not None:
+                marks[-1]["eq"] = {"bands": [dict(b) for b in options.eq]}
             if spec is not None:
                 marks[-1]["spectrum"] = spectrum_dict(got.spectrum)
             if fcon is not None:
@@ -1257,6 +1333,7 @@ def easy_synthesize_stream(bert, vits, sentences, style_vectors, style_id=0, spe
     refuse_voice(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_token_pitch(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_token_gain(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+    refuse_eq(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_track(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     refuse_dynamics(options, "a stream (/synthesize_stream, /synthesize_stream_marks)")
     if formants:

@@ -68,6 +68,12 @@ and error mapping, so that a client of the reference's server cannot tell the di
                     tokens' levels, edit, ask again.  The marks then carry "volume_edit": {"applied_db", "src_rms_db"}.  The edit can exceed
                     full scale: set limiter to bound it.  A bad value, or a list whose length differs from the text's token count, answers
                     400 with the expected count; so does the field on the stream routes, naming /synthesize_marks.
+  eq = null (new; /synthesize and /synthesize_marks, batched or not): a parametric EQ of the voice, at most 8 bands {"kind": "highpass" |
+                    "lowpass" | "lowshelf" | "highshelf" | "peak", "f0_hz": [10, 19845], "gain_db": [-24, 24] (shelves and peaks), "q": [0.1, 20]
+                    (default 0.7071)}, run in the given order on the device in front of every format, gain stage and sink: a 300 Hz
+                    high-pass and a presence peak ahead of a G.711 call leg, a shelf against what formant_scale took.  The marks then
+                    carry "eq": {"bands": [...]}.  A bad band answers 400 and names the field; so does the field on the stream routes,
+                    naming /synthesize.
   formants_track = false (new; /synthesize_marks only, batched or not, with formants in 1 to 5): the contour is tracked across frames on the
                     device: formants_candidates roots are kept per frame (null: formants + 3, at most 7 and order / 2) and one best path
                     assigns the formants to them, so a spurious root no longer shifts a frame by a slot.  formants_ref_hz (null: 500, 1500,
@@ -241,6 +247,7 @@ def make_app(holder, batching=None):
         token_gain_kind: str = "db"         # "db": raise / lower the token by that many dB, [-60, 60]; "rms_db": the token's target RMS in dBFS, [-120, 0)
         token_gain_ramp_ms: float = 10      # over how long the factor changes about a token boundary, [0, 1000]
         token_gain_max_db: float = 12       # every factor is held within +- this many dB, [0, 60]
+        eq: Optional[List[dict]] = None     # new: parametric EQ bands {"kind", "f0_hz", "gain_db", "q"}, at most 8; /synthesize, /synthesize_marks; 400 on the stream routes
         assist_text: Optional[str] = None   # new: a second text whose DeBERTa features steer the delivery (upstream's assist_text); all four routes
         assist_text_weight: float = 0.7     # its weight, [0, 1] (upstream's default); 0 = none
         formant_scale: float = 1.0          # new: moves the voice's formants, [0.5, 2]; /synthesize, /synthesize_marks (batched or not); 400 on the stream routes without voice_pivot_hz
@@ -320,6 +327,7 @@ def make_app(holder, batching=None):
                                               **({"token_gain": req.token_gain, "token_gain_kind": req.token_gain_kind,
                                                   "token_gain_ramp_ms": req.token_gain_ramp_ms, "token_gain_max_db": req.token_gain_max_db}
                                                  if getattr(req, "token_gain", None) is not None else {}),
+                                              **({"eq": req.eq} if getattr(req, "eq", None) is not None else {}),
                                               **({"formant_scale": req.formant_scale} if getattr(req, "formant_scale", 1.0) != 1.0 else {}),
                                               **({"voice_pivot_hz": req.voice_pivot_hz} if getattr(req, "voice_pivot_hz", None) is not None else {}),
                                               **({k: getattr(req, k) for k in orchestrator.SPECTRUM_FIELDS}
@@ -346,7 +354,7 @@ def make_app(holder, batching=None):
             orchestrator.refuse_formants(req, "/synthesize")
             with lock:
                 wav = holder.easy_synthesize(req.ident, req.text, req.style_id, req.speaker_id, options_of(req))
-        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.EqError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:                # any error -> 500 + text, like AppError::into_response
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -361,7 +369,7 @@ def make_app(holder, batching=None):
             with lock:                        # parse and queue only: the answer is awaited without it
                 fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching)
             wav = fut.result()
-        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.EqError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -380,7 +388,7 @@ def make_app(holder, batching=None):
                     fut = holder.easy_synthesize_batched(req.ident, req.text, req.style_id, req.speaker_id, options_of(req), batching=batching,
                                                          marks=True)
                 audio, marks = fut.result()
-        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
+        except (orchestrator.TokenPitchError, orchestrator.TokenGainError, orchestrator.EqError, orchestrator.SpectrumError, orchestrator.FormantsError) as e:
             return bad_request(e)
         except Exception as e:
             return PlainTextResponse(f"Something went wrong: {e}", status_code=500)
@@ -401,6 +409,7 @@ def make_app(holder, batching=None):
             orchestrator.refuse_voice(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_token_pitch(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_token_gain(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
+            orchestrator.refuse_eq(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.refuse_track(req, "a stream (/synthesize_stream, /synthesize_stream_marks)")
             orchestrator.check_assist(None, getattr(req, "assist_text_weight", 0.7))   # (a stream takes an assist; a bad weight is the request's fault)
             if not formants:
